@@ -7,8 +7,12 @@ shading/BSDF sampling -> radiance accumulate; for N > 1 the frame is sharded by 
 step ends with ONE gather of tile radiance to rank 0 (RCCL) + the assembly of the image there.  Total work is fixed as N
 grows ("strong" scaling).  Scene, BVH and blue-noise texture are resident in HBM before the timed region.
 
-Prints one JSON line (rank 0) with the bench contract fields plus `roofline` (dominant kernel: closest-hit traversal of
-extension rays, timed with HIP events on the render stream) and `cpu_baseline` (the scalar CPU oracle on the host cores).
+Prints one JSON line (rank 0) with the bench contract fields.  A plain run sets up, warms up, times the steps and prints it; with
+--dump-outputs DIR it first writes what the last timed step computed (the assembled image, the ray counts) as DIR/*.npy.  --full
+adds everything else, as separate runs after the timed steps: `roofline` (dominant kernel: closest-hit traversal of extension rays,
+timed with HIP events on the render stream in one more step), `stage_ms_per_rank`, `cpu_baseline` (the scalar CPU oracle on the
+host cores), the extra lines (other BASELINE configs, post chain, ingestion, shard costs) and the image's sanity check; the keys
+of what a run did not measure are null.
 """
 import argparse
 import glob
@@ -691,7 +695,15 @@ def main():
     ap.add_argument("--batch-paths", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--traversal", type=int, default=0, help=argparse.SUPPRESS)  # 0 auto (contract run), 1 stack, 2 exhaustive
     ap.add_argument("--scene", default="", help=argparse.SUPPRESS)  # old name of --workload
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline step, the CPU baseline and the extra lines (N = 1) and check "
+                         "the image; a plain run does the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy: image (H x W x 4 float32, accumulated radiance "
+                         "sum + sample count) and rays_per_step (float64: primary, extension, shadow)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.scene:
         args.workload = args.scene
     sponza = args.workload == "sponza"
@@ -757,7 +769,7 @@ def main():
         # every rank builds its own copy of the tree: the builders are deterministic (prefix sums, integer atomics), so the copies are the
         # same bytes -- shown per rank for the tree path's workload (tests/test_comm_gpu.py asserts it)
         wide_sha = None
-        if sponza:
+        if sponza and args.full:
             import hashlib
             wn, wsrc, _, _ = r.bvh_wide_readback()
             wide_sha = hashlib.sha1(np.ascontiguousarray(wn).tobytes() + np.ascontiguousarray(wsrc).tobytes()).hexdigest()
@@ -886,25 +898,37 @@ def main():
         rays_p, rays_e, rays_s, verts = (float(x) for x in cnt.tolist())
         rays = rays_p + rays_e + rays_s
 
-        # dominant kernel, timed live with HIP events on the render stream (one extra step with per-kernel event brackets)
-        r.stats_reset()
-        step(capi.RENDER_STAGE_TIMERS)
-        fence()
-        sp = r.stats()
-        # per-rank stage split of that step (a future SCALE run shows where a rank's time goes as N grows)
-        mine = [sp.ms_primary, sp.ms_trace_closest, sp.ms_trace_any, sp.ms_shade, sp.ms_resolve, sp.ms_total]
-        per_rank = [None] * world
-        if world > 1:
-            dist.all_gather_object(per_rank, mine)
-        else:
-            per_rank = [mine]
-        stage_ms_per_rank = [dict(zip(("primary", "trace_closest", "trace_any", "shade", "resolve", "total"), m)) for m in per_rank]
-        wide_sha_per_rank = [wide_sha]
-        if world > 1:
-            wide_sha_per_rank = [None] * world
-            dist.all_gather_object(wide_sha_per_rank, wide_sha)
-        roofline = None
-        if rank == 0 and sp.launches_trace_closest:
+        # what the last timed step computed, before anything else renders into the same buffers
+        img = None
+        if rank == 0 and (args.full or args.dump_outputs):
+            img = (r.comm_readback() if exchange.startswith("cap_comm") else image.cpu().numpy()).reshape(HEIGHT, WIDTH, 4)
+            if args.full:
+                # sanity of the product of the timed region: finite image, every pixel accumulated spp frames
+                assert np.isfinite(img).all() and (img[..., 3] == spp).all(), "bench image is incomplete"
+        if rank == 0 and args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "image.npy"), np.ascontiguousarray(img, dtype=np.float32))
+            np.save(os.path.join(args.dump_outputs, "rays_per_step.npy"), np.array([rays_p, rays_e, rays_s], dtype=np.float64) / args.steps)
+
+        stage_ms_per_rank, wide_sha_per_rank, roofline = None, [wide_sha], None
+        if args.full:
+            # dominant kernel, timed live with HIP events on the render stream (one extra step with per-kernel event brackets)
+            r.stats_reset()
+            step(capi.RENDER_STAGE_TIMERS)
+            fence()
+            sp = r.stats()
+            # per-rank stage split of that step (a future SCALE run shows where a rank's time goes as N grows)
+            mine = [sp.ms_primary, sp.ms_trace_closest, sp.ms_trace_any, sp.ms_shade, sp.ms_resolve, sp.ms_total]
+            per_rank = [None] * world
+            if world > 1:
+                dist.all_gather_object(per_rank, mine)
+            else:
+                per_rank = [mine]
+            stage_ms_per_rank = [dict(zip(("primary", "trace_closest", "trace_any", "shade", "resolve", "total"), m)) for m in per_rank]
+            if world > 1:
+                wide_sha_per_rank = [None] * world
+                dist.all_gather_object(wide_sha_per_rank, wide_sha)
+        if args.full and rank == 0 and sp.launches_trace_closest:
             fused = sp.launches_shade == 0
             SH_ENTRY = 32  # reference-model shadow entry: (origin, path id) + (contribution, -); see DESIGN.md "Data layout"
             quote = contract and world == 1
@@ -943,13 +967,10 @@ def main():
                              "stage_ms": stage_ms(sp)})
 
         progress("contract steps timed")
-        extras = world == 1 and contract and not args.no_extras
+        extras = world == 1 and contract and not args.no_extras and args.full
         s_h = stream.cuda_stream
         out = None
         if rank == 0:
-            # sanity of the product of the timed region: finite image, every pixel accumulated spp frames
-            img = (r.comm_readback() if exchange.startswith("cap_comm") else image.cpu().numpy()).reshape(HEIGHT, WIDTH, 4)
-            assert np.isfinite(img).all() and (img[..., 3] == spp).all(), "bench image is incomplete"
             metric = "Mrays/sec (primary+secondary), cornell_box 1080p 64spp" if not sponza else \
                 "Mrays/sec (primary+secondary), sponza_class 1080p %dspp (BASELINE configs[3]; not the contract metric)" % spp
             out = {"metric": metric, "value": rays / dt / 1e6, "unit": "Mrays/s",
@@ -968,7 +989,7 @@ def main():
                    "exchange": exchange, "stage_ms_per_rank": stage_ms_per_rank,
                    "roofline": roofline, "ext_variant": None, "tree_variant": None, "big_variant": None, "config3_variant": None,
                    "config5_share": None, "shard_cost": None, "post_chain": None, "realtime_frame": None, "ingest": None, "cpu_baseline": None}
-            if not (args.no_cpu_baseline or world > 1):  # rank 0, N = 1 only; before the extra lines, so that the line below is complete without them
+            if args.full and not (args.no_cpu_baseline or world > 1):  # rank 0, N = 1 only; before the extra lines, so that the line below is complete without them
                 progress("cpu_baseline")
                 out["cpu_baseline"] = cpu_baseline()
 
@@ -999,10 +1020,10 @@ def main():
                 print(json.dumps(out), flush=True)
                 os._exit(0)
 
-        if rank == 0 and world == 1:
+        if rank == 0 and world == 1 and args.full:
             threading.Thread(target=watchdog, args=(int(os.environ.get("CAP_BENCH_EXTRAS_LIMIT_S", "180")),), daemon=True).start()
         # the literal "Lambert+GGX" of BASELINE configs[1] (EXT model: no reference counterpart)
-        if world == 1 and not sponza and not args.no_extras:
+        if world == 1 and not sponza and not args.no_extras and args.full:
             put("ext_variant", guarded(ext_variant, device_index, s_h, args.steps, spp))
         if extras and not args.no_tree_variant:
             put("tree_variant", guarded(tree_variant, device_index, s_h))

@@ -1,16 +1,19 @@
 """Texture decoding pinned by the reference's own decoder.  No GPU.
 
 The reference loads every texture through the stb_image.h it vendors (stbi_load(..., 4), texture_system.cpp:41-45).  That header
-is the one part of the reference that compiles in this container (`make -C oracle ref` -> oracle/_ref/libstb_ref.so), so for this
+is the one part of the reference that compiles on its own (`make -C oracle ref` -> oracle/_ref/libstb_ref.so), so for this
 boundary the product (capsaicin_amd/csrc/image_decode.cpp, jpeg_decode.cpp behind cap_image_decode) is compared with the
 reference itself, tolerance 0:
-  * test_golden_*: tests/golden/images/ (inputs) against expected.npz (stb's outputs, written by tools/make_image_fixtures.py) --
-    runs wherever the product library loads;
-  * test_live_*: only where oracle/_ref exists -- a few hundred more files made on the spot (PIL/libjpeg writes the common JPEG
-    layouts, tests/*_craft.py the rest), each decoded by both, and the committed expectations re-derived.
+  * test_golden_*: tests/golden/images/ (inputs) against expected.npz (stb's outputs, written by tools/make_image_fixtures.py);
+  * test_live_*: a few hundred more files made on the spot (PIL/libjpeg writes the common JPEG layouts, tests/*_craft.py the
+    rest), each decoded by both.  Where oracle/_ref exists stb decodes them live; everywhere else its answers come from
+    tests/golden/stb_live.json, a digest of what it made of each file (input digest -> output digest, or null for a refusal),
+    recorded by `python tools/make_image_fixtures.py --live`.
 """
+import hashlib
 import io
 import itertools
+import json
 import os
 
 import numpy as np
@@ -25,7 +28,9 @@ from oracle import stb_ref
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "images")
 NAMES = sorted(n for n in os.listdir(GOLDEN) if n != "expected.npz")
-needs_ref = pytest.mark.skipif(not stb_ref.available(), reason="oracle/_ref/libstb_ref.so not built (make -C oracle ref)")
+STB_LIVE = os.path.join(os.path.dirname(GOLDEN), "stb_live.json")
+_stored = None
+RECORDED = {}  # what the live decoder answered in this process (tools/make_image_fixtures.py --live writes it to STB_LIVE)
 
 
 def product(data, name):
@@ -37,6 +42,35 @@ def product(data, name):
 
 def same(got, ref):
     return got is not None and ref is not None and got.shape == ref.shape and np.array_equal(got, ref)
+
+
+def digest(img):
+    """Shape and bytes of a decoded image in 20 hex digits; None for a refused file."""
+    if img is None:
+        return None
+    return hashlib.sha1(("%s:" % (img.shape,)).encode() + np.ascontiguousarray(img).tobytes()).hexdigest()[:20]
+
+
+def stb(data, pixels=True):
+    """digest() of what the reference's decoder makes of `data`: live where oracle/_ref is built, else as recorded from it.
+    pixels=False: only whether it decodes the file at all ("decoded"), for files whose pixels it leaves undefined."""
+    global _stored
+    if _stored is None:
+        _stored = json.load(open(STB_LIVE))["digests"] if os.path.exists(STB_LIVE) else {}
+    key = hashlib.sha1(bytes(data)).hexdigest()[:20]
+    if stb_ref.available():
+        d = digest(stb_ref.decode(data))
+        RECORDED[key] = d = "decoded" if d is not None and not pixels else d
+        assert _stored.get(key, d) == d, "tests/golden/stb_live.json disagrees with the live decoder"
+        return d
+    assert key in _stored, "no recorded answer of the reference decoder for this file: tools/make_image_fixtures.py --live"
+    return _stored[key]
+
+
+def agrees(data, name):
+    """The product decodes `data` to exactly what the reference's decoder makes of it (which must not refuse it)."""
+    ref = stb(data)
+    return ref is not None and digest(product(data, name)) == ref
 
 
 def test_golden_set_covers_every_container():
@@ -53,28 +87,25 @@ def test_golden_image(native_lib, name):
     assert np.array_equal(got, expected), "%d pixels differ from the reference's decoder" % (got != expected).any(-1).sum()
 
 
-@needs_ref
 def test_live_expectations_are_the_reference_decoder_s():
-    """expected.npz is not hand-made: the reference's decoder, run here, gives the same arrays."""
+    """expected.npz is not hand-made: the reference's decoder gives the same arrays."""
     expected = np.load(os.path.join(GOLDEN, "expected.npz"))
     assert sorted(expected.files) == NAMES
     for name in NAMES:
-        ref = stb_ref.decode(open(os.path.join(GOLDEN, name), "rb").read())
-        assert same(ref, expected[name]), name
+        assert stb(open(os.path.join(GOLDEN, name), "rb").read()) == digest(expected[name]), name
 
 
-REFERENCE_NOISE = "/root/reference/assets/textures/bluenoise256.png"
+# the reference's assets/textures/bluenoise256.png, byte for byte
+REFERENCE_NOISE = os.path.join(os.path.dirname(GOLDEN), "bluenoise256.png")
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE_NOISE), reason="the reference tree is only in the build container")
 def test_reference_blue_noise_texture(native_lib, bluenoise):
     """The one texture the reference ships is its random-number source (raytracing_system.cpp:642-646): the product's decoder, the
     reference's decoder and the raw copy under assets/ (what cap_bluenoise_upload gets) agree on all 256 x 256 x 4 bytes."""
     data = open(REFERENCE_NOISE, "rb").read()
     got = product(data, "bluenoise256.png")
     assert same(got, bluenoise)
-    if stb_ref.available():
-        assert same(stb_ref.decode(data), bluenoise)
+    assert stb(data) == digest(bluenoise)
 
 
 def _picture(mode, w, h, seed):
@@ -91,7 +122,6 @@ def _picture(mode, w, h, seed):
     return Image.fromarray(a[..., 0] if ch == 1 else a, mode)
 
 
-@needs_ref
 def test_live_libjpeg_layouts(native_lib):
     """Baseline / progressive (spectral selection + successive approximation) x 4:4:4 / 4:2:2 / 4:2:0 / 4:1:1 x optimised tables x
     restart intervals x grey / CMYK / RGB-id files, at sizes around the MCU edges."""
@@ -108,12 +138,10 @@ def test_live_libjpeg_layouts(native_lib):
     for n, (mode, w, h, kw) in enumerate(files):
         b = io.BytesIO()
         _picture(mode, w, h, n).save(b, "JPEG", **kw)
-        ref = stb_ref.decode(b.getvalue())
-        assert ref is not None and same(product(b.getvalue(), "t.jpg"), ref), (mode, w, h, kw)
+        assert agrees(b.getvalue(), "t.jpg"), (mode, w, h, kw)
     assert len(files) > 300
 
 
-@needs_ref
 def test_live_crafted_layouts(native_lib):
     """Everything a sequential JPEG may legally be that libjpeg does not write: vertical / 4x / mixed sampling factors (each with
     its own upsampler in stb), four components under each Adobe transform, one scan per component, restart after every MCU,
@@ -126,31 +154,28 @@ def test_live_crafted_layouts(native_lib):
     count = 0
     for s, (w, h), inter, restart in itertools.product(layouts, [(37, 23), (1, 1), (33, 70)], (True, False), (0, 1, 5)):
         data = jpeg_craft.random_file(rs, w, h, s, interleaved=inter, restart=restart)
-        ref = stb_ref.decode(data)
-        assert ref is not None and same(product(data, "t.jpg"), ref), (s, w, h, inter, restart)
+        assert agrees(data, "t.jpg"), (s, w, h, inter, restart)
         count += 1
     extras = [dict(wide_quant=True), dict(fill_bytes=True), dict(comment=True), dict(dnl=True), dict(interleaved=False, requant=True),
               dict(jfif=False, adobe_transform=0), dict(jfif=True, adobe_transform=0), dict(jfif=False, adobe_transform=1),
               dict(component_ids=[82, 71, 66]), dict(component_ids=[0, 1, 2])]
     for kw in extras:
         data = jpeg_craft.random_file(rs, 45, 31, [(2, 2), (1, 1), (1, 1)], **kw)
-        assert same(product(data, "t.jpg"), stb_ref.decode(data)), kw
+        assert agrees(data, "t.jpg"), kw
     for t, s in itertools.product((0, 1, 2), ([(1, 1)] * 4, [(2, 2), (1, 1), (1, 1), (2, 2)])):
         data = jpeg_craft.random_file(rs, 45, 31, s, adobe_transform=t, jfif=False)
-        assert same(product(data, "t.jpg"), stb_ref.decode(data)), (t, s)
+        assert agrees(data, "t.jpg"), (t, s)
     assert count == 288
 
 
-@needs_ref
 def test_live_texture_sized_jpeg(native_lib):
     """One file of the size real material textures have (1024 x 1024, 4:2:0): every pixel."""
     pytest.importorskip("PIL.Image")
     b = io.BytesIO()
     _picture("RGB", 1024, 1024, 99).save(b, "JPEG", quality=88, subsampling=2, progressive=True)
-    assert same(product(b.getvalue(), "big.jpg"), stb_ref.decode(b.getvalue()))
+    assert agrees(b.getvalue(), "big.jpg")
 
 
-@needs_ref
 def test_live_png_layouts(native_lib):
     """Every colour type x bit depth x {plain, Adam7} at sizes that leave some interlace passes empty, a random filter type per
     scanline, IDAT in pieces, palette alpha and colour keys (half of them equal to a pixel of the image, so the key really fires --
@@ -170,14 +195,12 @@ def test_live_png_layouts(native_lib):
                 pick = smp[rs.randint(0, h), rs.randint(0, w)] if rs.rand() < 0.5 else rs.randint(0, 1 << depth, smp.shape[2])
                 kw["trns"] = b"".join(int(v).to_bytes(2, "big") for v in pick)
             data = png_craft.write(smp, depth, ctype, inter, rs=rs, idat_pieces=int(rs.randint(1, 4)), **kw)
-            ref = stb_ref.decode(data)
-            assert ref is not None and same(product(data, "t.png"), ref), (ctype, depth, inter, w, h, list(kw))
+            assert agrees(data, "t.png"), (ctype, depth, inter, w, h, list(kw))
             count += 1
-            keyed += int("trns" in kw and ctype != 3 and (ref[..., 3] == 0).any())
+            keyed += int("trns" in kw and ctype != 3 and (product(data, "t.png")[..., 3] == 0).any())
     assert count == 300 and keyed > 20
 
 
-@needs_ref
 def test_live_png_refusals_match(native_lib):
     """Files stb refuses are refused: a colour key on a type with alpha, a key of the wrong length, palette alpha before the palette
     or longer than it, a key after the image data, an unknown critical chunk, a palette of broken length."""
@@ -199,14 +222,13 @@ def test_live_png_refusals_match(native_lib):
     plte = palimg.index(b"PLTE") - 4
     cases["alpha_before_palette"] = palimg[:plte] + png_craft.chunk(b"tRNS", bytes(3)) + palimg[plte:]
     for name, data in cases.items():
-        assert stb_ref.decode(data) is None, name + ": the reference decodes this"
+        assert stb(data) is None, name + ": the reference decodes this"
         assert product(data, "t.png") is None, name
     # and an ancillary chunk nobody knows is skipped by both
     ok = good[:idat] + png_craft.chunk(b"abCd", b"xyz") + good[idat:]
-    assert same(product(ok, "t.png"), stb_ref.decode(ok))
+    assert agrees(ok, "t.png")
 
 
-@needs_ref
 def test_live_tga_layouts(native_lib):
     """TGA has no signature and stb reads it its own way (the layout follows the bit count, not the image type; "first colour-map
     entry" skips bytes; the right-to-left bit is ignored; indices beyond the map read entry 0): image types 1 / 2 / 3 x every depth
@@ -221,24 +243,22 @@ def test_live_tga_layouts(native_lib):
             files += [dict(image_type=1, bpp=8, cmap_bits=b, cmap_len=17, cmap_first=3, id_len=5) for b in (16, 24)]
         for kw in files:
             data = tga_craft.random_file(rs, w, h, descriptor=desc, rle=rle, **kw)
-            ref = stb_ref.decode(data)
-            assert ref is not None and same(product(data, "no_extension"), ref), (w, h, rle, hex(desc), kw)
+            assert agrees(data, "no_extension"), (w, h, rle, hex(desc), kw)
             count += 1
     assert count > 450
     # what neither takes for a TGA
     for kw in (dict(image_type=2, bpp=12), dict(image_type=1, bpp=8, cmap_bits=12, cmap_len=4), dict(image_type=4, bpp=8),
                dict(image_type=1, bpp=24, cmap_bits=24, cmap_len=4)):
         data = tga_craft.random_file(rs, 4, 4, **kw)
-        assert stb_ref.decode(data) is None and product(data, "t.tga") is None, kw
+        assert stb(data) is None and product(data, "t.tga") is None, kw
     zero = bytearray(tga_craft.random_file(rs, 4, 4, 2, 24))
     zero[12:14] = b"\0\0"
-    assert stb_ref.decode(bytes(zero)) is None and product(bytes(zero), "t.tga") is None
+    assert stb(bytes(zero)) is None and product(bytes(zero), "t.tga") is None
     # the one deliberate difference: a file shorter than its header demands is an error here; stb pads it with zero bytes
     data = tga_craft.random_file(rs, 7, 5, 2, 24)[:-10]
-    assert stb_ref.decode(data) is not None and product(data, "t.tga") is None
+    assert stb(data, pixels=False) is not None and product(data, "t.tga") is None
 
 
-@needs_ref
 def test_live_bmp_layouts(native_lib):
     """BMP as stb reads it: header sizes 12 / 40 / 56 / 108 / 124, palettes of 1 / 4 / 8 bits (any length), 24 bits, 16 / 32 bits with
     the default masks, BI_BITFIELDS behind a 40-byte header and the V4 / V5 headers' own masks (5-6-5, 4-4-4-4, 6-6-6, swapped
@@ -251,8 +271,7 @@ def test_live_bmp_layouts(native_lib):
 
     def both(data, what):
         nonlocal count
-        ref = stb_ref.decode(data)
-        assert ref is not None and same(product(data, "x.bmp"), ref), what
+        assert agrees(data, "x.bmp"), what
         count += 1
     for (w, h), hdr, td in itertools.product([(13, 7), (1, 1), (8, 3), (5, 2)], (12, 40, 56, 108, 124), (False, True)):
         if hdr == 12:
@@ -285,10 +304,10 @@ def test_live_bmp_layouts(native_lib):
     planes = bytearray(bmp_craft.write(rs, 9, 4, 24, 40))
     planes[26:28] = (2).to_bytes(2, "little")
     for data in (rle, bytes(odd), bytes(planes)):
-        assert stb_ref.decode(data) is None and product(data, "x.bmp") is None
+        assert stb(data) is None and product(data, "x.bmp") is None
     # the deliberate difference again: a file that ends before its last row is an error here (stb pads with zero bytes)
     short = bmp_craft.write(rs, 9, 4, 24, 40)[:-5]
-    assert stb_ref.decode(short) is not None and product(short, "x.bmp") is None
+    assert stb(short, pixels=False) is not None and product(short, "x.bmp") is None
 
 
 def test_corrupt_jpegs_end_as_errors(native_lib):

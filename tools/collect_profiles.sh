@@ -44,4 +44,4 @@ done
         cat gpurun_out/$f.txt
     done
 } > "profiles/${TAG}_shard_cost.txt"
-echo "profiles/${TAG}_* written; now: gpurun -- 'python bench.py > gpurun_out/bench_${TAG}.json' and copy it to profiles/${TAG}_bench.json"
+echo "profiles/${TAG}_* written; now run 'python bench.py --full' on the GPU and save its line as profiles/${TAG}_bench.json"

@@ -6,6 +6,8 @@ arrays are the reference's outputs; tests/test_image_ref.py holds the product de
 over a much larger corpus where oracle/_ref exists.
 
     python tools/make_image_fixtures.py          (needs PIL and oracle/_ref/libstb_ref.so)
+    python tools/make_image_fixtures.py --live   tests/golden/stb_live.json: what stb makes of every file test_image_ref.py's
+                                                 live tests and the golden set decode (digests), for machines without oracle/_ref
 """
 import io
 import os
@@ -153,5 +155,27 @@ def main():
     np.savez_compressed(os.path.join(out, "expected.npz"), **expected)
 
 
+def record_live():
+    """Runs test_image_ref.py's stb-dependent tests against the live decoder and writes the digests they asked for."""
+    import json
+    import test_image_ref as t
+    from capsaicin_amd import capi
+    assert stb_ref.available(), "oracle/_ref/libstb_ref.so not built (make -C oracle ref)"
+    lib = capi.lib()
+    bluenoise = np.fromfile(os.path.join(ROOT, "assets", "bluenoise256.rgba"), np.uint8).reshape(256, 256, 4)
+    t.test_live_expectations_are_the_reference_decoder_s()
+    t.test_reference_blue_noise_texture(lib, bluenoise)
+    for name in sorted(dir(t)):
+        if name.startswith("test_live_") and name != "test_live_expectations_are_the_reference_decoder_s":
+            getattr(t, name)(lib)
+    with open(t.STB_LIVE, "w") as fh:
+        json.dump({"_source": "stb_image.h v2.25 as the reference vendors it (oracle/_ref/libstb_ref.so), stbi_load_from_memory(..., 4): "
+                              "sha1 of the input file -> sha1 of the decoded shape and bytes (null: refused), 20 hex digits each; "
+                              "written by tools/make_image_fixtures.py --live",
+                   "digests": dict(sorted(t.RECORDED.items()))}, fh, indent=0)
+        fh.write("\n")
+    print("%s: %d files" % (os.path.relpath(t.STB_LIVE, ROOT), len(t.RECORDED)))
+
+
 if __name__ == "__main__":
-    main()
+    record_live() if sys.argv[1:] == ["--live"] else main()

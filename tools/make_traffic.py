@@ -96,7 +96,7 @@ PASSES = listed_passes()
 ISSUE = static_issue_costs()
 out = {"source_sha256": bench.kernel_source_sha(), "kernels": {},
        "method": "rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE and the SQ block, each in its own run, no trace options), one workload per "
-                 "run: `python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras` (headline), `bench.py --only ext`, and with "
+                 "run: `python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras` (headline), `bench.py --only ext`, and with "
                  "CAP_NO_TWO_LANES=1 `bench.py --only tree` / `--only big` (tools/prof.sh); counters summed over the kernel's dispatches and "
                  "divided by their number; FETCH_SIZE / WRITE_SIZE are KiB, FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for "
                  "gfx950; per-kernel table in profiles/%s_rocprofv3_summary.txt" % tag}

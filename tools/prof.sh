@@ -2,7 +2,7 @@
 # Profiling recipe for the GPU box (run through gpurun): ONE WORKLOAD PER rocprofv3 RUN -- kernel trace + stats, then PMC passes
 # (separate runs; never with --sys-trace) -- so that every per-kernel average can be recomputed from one file (VERDICT r3 weak 8:
 # one table used to mix Cornell, EXT and the tree path with two overlapping lanes).  Workloads:
-#   cornell  bench.py --no-extras                      the contract line (k_trace_shade<false,false,false,true>)
+#   cornell  bench.py --full --no-extras               the contract line (k_trace_shade<false,false,false,true>)
 #   ext      bench.py --only ext                       BASELINE's literal "Lambert+GGX" (k_trace_shade<false,true,false,true>)
 #   tree     bench.py --only tree, CAP_NO_TWO_LANES=1  262 k-triangle hall, one lane: a launch's duration is its own
 #   big      bench.py --only big,  CAP_NO_TWO_LANES=1  16.8 M-triangle hall (the HBM-bound traversal frames)
@@ -27,7 +27,7 @@ SQ2="SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTI
 for wl in $WORKLOADS; do
   unset CAP_NO_TWO_LANES
   case $wl in
-    cornell) ARGS="$ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras" ;;
+    cornell) ARGS="$ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras" ;;
     ext)     ARGS="$ROOT/bench.py --only ext --steps 2" ;;
     tree)    ARGS="$ROOT/bench.py --only tree"; export CAP_NO_TWO_LANES=1 ;;
     big)     ARGS="$ROOT/bench.py --only big"; export CAP_NO_TWO_LANES=1 ;;
