@@ -56,6 +56,27 @@ class BvhInfo(C.Structure):
                 ("build_ms", C.c_double)]
 
 
+class RayDesc(C.Structure):
+    """CapRayDesc: DXR RayDesc layout (32 bytes)."""
+    _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("direction", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class Hit(C.Structure):
+    """CapHit (16 bytes): closest hit of a ray query; a miss is (tmax, 0, 0, MISS)."""
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("triangle", C.c_uint32)]
+
+
+MISS = 0xFFFFFFFF  # CapHit::triangle of a miss (and the ids CAP_BUF_GBUFFER_GEO stores for one)
+
+
+def hit_triangles(hits):
+    """Global triangle ids of (N, 4) hit records (column 3 holds the id's bits) as int64; a miss reads MISS.  torch in, torch out."""
+    if isinstance(hits, np.ndarray):
+        return np.ascontiguousarray(hits, np.float32).reshape(-1, 4)[:, 3].view(np.uint32).astype(np.int64)
+    import torch
+    return hits[:, 3].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+
+
 OUTPUT_COMBINED, OUTPUT_DIRECT, OUTPUT_INDIRECT, OUTPUT_VARIANCE = range(4)  # SettingsComponent::output, gui_system.h:11-17
 
 
@@ -124,6 +145,8 @@ SYMBOLS = {
     "cap_stats_reset": (_i, [_vp]),
     "cap_tile_buffer_floats": (_i, [_vp, C.POINTER(C.c_size_t)]),
     "cap_resolve_tiles": (_i, [_vp, _vp]),
+    "cap_trace_rays": (_i, [_vp, _vp, _u64, _vp, _u32]),
+    "cap_trace_occlusion": (_i, [_vp, _vp, _u64, _vp, _u32]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
     "cap_post_settings_default": (None, [C.POINTER(PostSettings)]),
     "cap_post_frame": (_i, [_vp, C.POINTER(PostSettings), _u32, C.POINTER(CameraData)]),
@@ -338,6 +361,8 @@ class Renderer:
         self.ctx = C.c_void_p()
         _check(lib().cap_ctx_create(device, C.c_void_p(stream) if stream else None, C.byref(self.ctx)), "cap_ctx_create")
         self.width = self.height = 0
+        self.device = device
+        self._tri_end = np.zeros(0, np.int64)  # inclusive prefix sums of the uploaded mesh table's triangle counts
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -353,9 +378,14 @@ class Renderer:
              np.ascontiguousarray(meshes, np.uint32).reshape(-1, 8)]
         _check(lib().cap_scene_upload(self.ctx, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), _p(a[4]), a[0].size // 3, a[3].size,
                                       a[4].shape[0]), "cap_scene_upload")
+        self._set_mesh_table(a[4])
 
     def upload_geometry(self, geo):
         _check(lib().cap_scene_upload_geometry(self.ctx, geo.h), "cap_scene_upload_geometry")
+        self._set_mesh_table(geo.meshes)
+
+    def _set_mesh_table(self, meshes):
+        self._tri_end = np.cumsum(np.asarray(meshes, np.uint32).reshape(-1, 8)[:, 2].astype(np.int64) // 3)
 
     def upload_texture(self, index, rgba8):
         if rgba8 is None:
@@ -483,6 +513,71 @@ class Renderer:
 
     def stats_reset(self):
         _check(lib().cap_stats_reset(self.ctx), "cap_stats_reset")
+
+    # ---- ray queries (cap_trace_rays / cap_trace_occlusion) ----
+    def trace_rays(self, rays, out=None, sync=True):
+        """Closest hit of each ray.  rays: (N, 8) float32 = CapRayDesc rows (origin, tmin, direction, tmax), a contiguous torch tensor
+        on this context's device or a numpy array (staged through torch; the hits come back as numpy).  Returns (N, 4) float32 hit
+        records (t, u, v, triangle id bits: hit_triangles() reads them).  sync=True orders the call against torch's current stream
+        (waits for it before the launch) and waits for the context's stream before returning: right for a renderer on a stream of its
+        own.  sync=False only enqueues, on the context's stream: for a renderer created on torch's stream (as bench.py creates it)."""
+        return self._query(rays, out, sync, False)
+
+    def trace_occlusion(self, rays, out=None, sync=True):
+        """1 where some triangle occludes the ray's open interval (tmin, tmax), else 0: (N,) int32.  Arguments as trace_rays."""
+        return self._query(rays, out, sync, True)
+
+    def _query(self, rays, out, sync, any_hit):
+        import torch
+        dev = torch.device("cuda", self.device)
+        host = isinstance(rays, np.ndarray)
+        if host:
+            rays = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).to(dev)
+            sync = True  # the result is read back to the host
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.device != dev:
+            raise CapError("rays must be a contiguous (N, 8) float32 tensor on %s, got %s %s on %s" % (dev, rays.dtype, tuple(rays.shape), rays.device))
+        n = rays.shape[0]
+        shape, dtype = ((n,), torch.int32) if any_hit else ((n, 4), torch.float32)
+        host_out = None
+        if isinstance(out, np.ndarray):
+            host_out, out = out, None
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        elif out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+            raise CapError("out must be a contiguous %s %s tensor on %s" % (tuple(shape), dtype, dev))
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the rays (and out's allocation) were made on torch's stream
+        fn = lib().cap_trace_occlusion if any_hit else lib().cap_trace_rays
+        _check(fn(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), 0),
+               "cap_trace_occlusion" if any_hit else "cap_trace_rays")
+        if sync:
+            self.sync()
+        if host or host_out is not None:
+            res = out.cpu().numpy()
+            if host_out is not None:
+                host_out[...] = res.reshape(host_out.shape)
+                return host_out
+            return res
+        return out
+
+    def triangle_to_instance_primitive(self, ids):
+        """Global triangle ids (hit_triangles) -> (instance, primitive) = (mesh index, triangle index within the mesh), the pair
+        CAP_BUF_GBUFFER_GEO stores; a miss (or any id past the scene) maps to (MISS, MISS).  numpy or torch, int64 out."""
+        ends = self._tri_end
+        if isinstance(ids, np.ndarray) or not hasattr(ids, "device"):
+            g = np.asarray(ids).astype(np.int64)
+            m = np.searchsorted(ends, g, side="right")
+            valid = (g >= 0) & (m < len(ends))
+            start = np.concatenate(([0], ends))[np.minimum(m, len(ends))]
+            return np.where(valid, m, MISS).astype(np.int64), np.where(valid, g - start, MISS).astype(np.int64)
+        import torch
+        g = ids.to(torch.int64)
+        e = torch.as_tensor(ends, device=g.device)
+        m = torch.searchsorted(e, g, right=True)
+        valid = (g >= 0) & (m < len(ends))
+        start = torch.cat([torch.zeros(1, dtype=torch.int64, device=g.device), e])[torch.clamp(m, max=len(ends))]
+        miss = torch.full_like(g, MISS)
+        return torch.where(valid, m, miss), torch.where(valid, g - start, miss)
 
     # ---- reconstruction chain ----
     def post_frame(self, settings, frame_count, prev_camera):

@@ -88,6 +88,24 @@ void launch_trace_any(const LaunchCfg& cfg, const BvhDev& bvh, const ShadowQueue
 void launch_trace_any8_refill(const LaunchCfg& cfg, const BvhDev& bvh, const ShadowQueue& q, uint32_t max_count, float4* target, uint32_t pixels_padded,
                               uint32_t n_slots, uint64_t* guard, uint32_t* work, const FrameConst* frames);
 
+// Ray queries of caller-supplied rays (cap_trace_rays / cap_trace_occlusion): rays = CapRayDesc records as float4 pairs, out = CapHit
+// records (float4) or one uint32 per ray.  work: [0] the wide kernels' chunk counter, [kCounterStride] the number of rays they passed
+// to the binary tree in `defer` (zeroed per launch).  safe: origin components beyond it go to the binary tree (query.hip).
+struct QueryArgs
+{
+    const float4* rays;
+    uint32_t      n;
+    void*         out;
+    uint32_t*     work;
+    uint32_t*     defer;
+    float         safe;
+};
+constexpr float kQuerySafeScale = 4.0f;  // safe = this x max(scene extent, largest |coordinate|): see query.hip
+bool query8_stack_matches();  // the wide query kernels' pair stack is the one the host checks the tree's depth against
+void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any);
+// binary tree, per lane: every ray of q (deferred = false), or the q.work[kCounterStride] rays listed in q.defer
+void launch_query_binary(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any, bool deferred);
+
 // ---- shade ----
 struct ShadeArgs
 {

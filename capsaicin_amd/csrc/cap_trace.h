@@ -76,6 +76,17 @@ __device__ __forceinline__ bool tri_occludes(const Ray& r, const float4 t0, cons
     return (det > 0.0f) & (U >= 0.0f) & (V >= 0.0f) & (U + V <= det) & (T > r.tmin * det) & (T < r.tmax * det);
 }
 
+// A caller's ray (CapRayDesc, cap_trace_rays / cap_trace_occlusion) that the query kernels trace: finite origin and direction, a
+// direction that is not zero, tmin < tmax (false when either is NaN).  Any other ray is answered with a miss without a traversal.
+__device__ __forceinline__ bool query_ray_ok(const float4 org_tmin, const float4 dir_tmax)
+{
+    const float big    = 3.40282347e38f;  // FLT_MAX: |x| <= big is false for +-inf and NaN
+    const bool  finite = fabsf(org_tmin.x) <= big && fabsf(org_tmin.y) <= big && fabsf(org_tmin.z) <= big && fabsf(dir_tmax.x) <= big &&
+                        fabsf(dir_tmax.y) <= big && fabsf(dir_tmax.z) <= big;
+    const bool  moves  = dir_tmax.x != 0.0f || dir_tmax.y != 0.0f || dir_tmax.z != 0.0f;
+    return finite && moves && dir_tmax.w > org_tmin.w;
+}
+
 // Work distribution of the queue kernels: the grid is persistent (fixed size, independent of the device-side
 // queue length); each wave takes 64-ray chunks strided by the number of waves in the grid.  A wave whose first
 // chunk is past the end leaves at once, so the grid always drains.

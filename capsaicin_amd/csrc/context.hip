@@ -163,6 +163,7 @@ struct CapContext
     uint32_t         wide8_depth = 0, wide8_top = 0, wide8_nodes = 0;
     float            wide8_ms = 0.f;
     DevBuf<uint32_t> stack_spill;             // traversal-stack entries beyond the LDS part, per thread of the persistent grid
+    DevBuf<uint32_t> query_work, query_defer; // cap_trace_rays / cap_trace_occlusion: chunk and hand-over counters, rays handed to the binary tree
     DevBuf<float4>   fan_pairs, fan_singles;  // exhaustive path: fan-pair records (5 float4) and the unpaired triangles (4 float4)
     uint32_t         fan_pair_count = 0, fan_single_count = 0;
     DevBuf<float4>   fan_pairs_nee;           // the pair records again, potential occluders of next-event rays first (update_nee_pairs)
@@ -1917,6 +1918,93 @@ int cap_assemble_tiles(CapContext* c, const float* device_src, uint32_t shard_co
     launch_assemble(cfg, c->screen, reinterpret_cast<const float4*>(device_src), shard_count, reinterpret_cast<float4*>(device_image));
     HIP_TRY(hipGetLastError());
     return CAP_OK;
+}
+
+// ---- ray queries (query.hip; binary tree: kernels.hip k_query_binary) ----
+namespace
+{
+constexpr uint64_t kQueryRaysPerLaunch = 1ull << 24;  // rays per launch: 32-bit ray indices and chunk counters, a 64-MB hand-over list
+
+int trace_query(CapContext* c, const char* what, const CapRayDesc* rays, uint64_t n, void* out, size_t out_stride, uint32_t flags, bool any)
+{
+    static_assert(sizeof(CapRayDesc) == 2 * sizeof(float4) && sizeof(CapHit) == sizeof(float4), "query records are the kernels' float4 records");
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (flags != 0) return fail(CAP_ERR_INVALID_ARG, "%s: flags is reserved and must be 0 (got 0x%x)", what, flags);
+    if (!c->bvh_ready) return fail(CAP_ERR_STATE, "%s: call cap_bvh_build first", what);
+    if (n == 0) return CAP_OK;
+    if (!rays || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    const uintptr_t r0 = (uintptr_t)rays, o0 = (uintptr_t)out;
+    if ((r0 | o0) & 15u) return fail(CAP_ERR_INVALID_ARG, "%s: rays and output must be 16-byte aligned", what);
+    if (n > (UINTPTR_MAX - r0) / sizeof(CapRayDesc) || n > (UINTPTR_MAX - o0) / out_stride)
+        return fail(CAP_ERR_INVALID_ARG, "%s: %llu rays exceed the address space", what, (unsigned long long)n);
+    const uintptr_t r1 = r0 + n * sizeof(CapRayDesc), o1 = o0 + n * out_stride;
+    if (r0 < o1 && o0 < r1) return fail(CAP_ERR_INVALID_ARG, "%s: the ray and output ranges overlap", what);
+    HIP_TRY(hipSetDevice(c->device));
+
+    BvhDev bvh = bvh_dev(c);  // (lane 0's spill area: a render's second lane has its own, and the stream orders us behind both)
+    bvh.wide8_ok = bvh.wide8_ok && query8_stack_matches();
+    const uint64_t per = std::min<uint64_t>(n, kQueryRaysPerLaunch);
+    if (c->query_work.n < 2 * kCounterStride || (bvh.wide8_ok && c->query_defer.n < per))
+    {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (a grown buffer replaces one an earlier query may still be using)
+        HIP_TRY(c->query_work.ensure(2 * kCounterStride));
+        if (bvh.wide8_ok) HIP_TRY(c->query_defer.ensure(per));
+    }
+    LaunchCfg cfg{c->stream, (uint32_t)c->cu_count * 4u, c->bvh_info.stack_entries, (uint32_t)c->cu_count};
+    cfg.sw = &c->sw;
+    // box-test error budget of the wide view (wide_builder.cpp, query.hip): M as the build computed it
+    double m = 0.0;
+    for (int k = 0; k < 3; ++k)
+        m = std::max({m, (double)c->bvh_info.bounds_hi[k] - (double)c->bvh_info.bounds_lo[k], std::fabs((double)c->bvh_info.bounds_lo[k]),
+                      std::fabs((double)c->bvh_info.bounds_hi[k])});
+    const float safe = (float)(kQuerySafeScale * m);
+    // CAP_TRACE_LAUNCHES=1: name every launch on stderr and drain the stream after it (fault localisation only)
+    const bool trace_launches = c->sw.on(SW_TRACE_LAUNCHES);
+    auto       traced         = [&](const char* kernel, uint64_t first) -> int {
+        HIP_TRY(hipGetLastError());
+        if (!trace_launches) return CAP_OK;
+        fprintf(stderr, "[cap] %s %s rays %llu.. ... ", what, kernel, (unsigned long long)first);
+        fflush(stderr);
+        hipError_t e = hipStreamSynchronize(c->stream);
+        fprintf(stderr, "%s\n", hipGetErrorString(e));
+        fflush(stderr);
+        return e == hipSuccess ? CAP_OK : CAP_ERR_HIP;
+    };
+    for (uint64_t done = 0; done < n; done += per)
+    {
+        QueryArgs q{};
+        q.rays  = reinterpret_cast<const float4*>(rays + done);
+        q.n     = (uint32_t)std::min<uint64_t>(per, n - done);
+        q.out   = static_cast<uint8_t*>(out) + done * out_stride;
+        q.work  = c->query_work.p;
+        q.defer = c->query_defer.p;
+        q.safe  = safe;
+        if (bvh.wide8_ok)
+        {
+            HIP_TRY(hipMemsetAsync(c->query_work.p, 0, sizeof(uint32_t) * 2 * kCounterStride, c->stream));
+            launch_query8(cfg, bvh, q, any);
+            if (traced(any ? "k_query_any8" : "k_query_closest8", done) != CAP_OK) return CAP_ERR_HIP;
+            launch_query_binary(cfg, bvh, q, any, true);
+            if (traced(any ? "k_query_binary<any> (handed-over rays)" : "k_query_binary<closest> (handed-over rays)", done) != CAP_OK) return CAP_ERR_HIP;
+        }
+        else
+        {
+            launch_query_binary(cfg, bvh, q, any, false);
+            if (traced(any ? "k_query_binary<any>" : "k_query_binary<closest>", done) != CAP_OK) return CAP_ERR_HIP;
+        }
+    }
+    return CAP_OK;
+}
+}  // namespace
+
+int cap_trace_rays(CapContext* c, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, uint32_t flags)
+{
+    return trace_query(c, "cap_trace_rays", device_rays, n, device_hits, sizeof(CapHit), flags, false);
+}
+
+int cap_trace_occlusion(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded, uint32_t flags)
+{
+    return trace_query(c, "cap_trace_occlusion", device_rays, n, device_occluded, sizeof(uint32_t), flags, true);
 }
 
 void cap_post_settings_default(CapPostSettings* out)

@@ -2885,4 +2885,53 @@ void launch_geo_aov(const LaunchCfg& cfg, const SceneDev& scene, const float4* h
     if (g > 4096) g = 4096;
     hipLaunchKernelGGL(k_geo_aov, dim3(g ? g : 1), dim3(kBlock), 0, cfg.stream, scene, hits_slot, Ppad, aov_geo);
 }
+
+// Ray queries of caller-supplied rays (cap_trace_rays / cap_trace_occlusion) on the binary tree, one lane per ray: every ray where the
+// compressed 8-wide view is not used (CAP_NO_WIDE8, a tree deeper than the wide kernels' stacks), and the rays the wide query kernels
+// passed on (query.hip: origins beyond the wide box test's error budget).  traverse_closest / traverse_any as k_trace_primary runs them
+// (wide8_ok cleared: the grid need not fit the spill area), so the records are the same bits as the wide kernels' and the render's.
+template <int STACK, bool ANY>
+__global__ __launch_bounds__(kBlock, stack_residency(STACK)) void k_query_binary(BvhDev bvh, QueryArgs q, uint32_t deferred)
+{
+    __shared__ uint32_t lds_stack[STACK * kBlock];
+    uint32_t* const     stack = lds_stack + threadIdx.x;
+    const uint32_t      count = deferred ? q.work[kCounterStride] : q.n;
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < count; j += gridDim.x * kBlock)
+    {
+        const uint32_t i = deferred ? q.defer[j] : j;
+        const float4   a = q.rays[2 * (size_t)i], b = q.rays[2 * (size_t)i + 1];
+        const bool     ok = query_ray_ok(a, b);
+        const Ray      r  = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
+        if (ANY)
+            static_cast<uint32_t*>(q.out)[i] = (ok && traverse_any<STACK>(bvh, r, stack)) ? 1u : 0u;
+        else
+        {
+            float    t = b.w, u = 0.0f, v = 0.0f;
+            uint32_t gid = kInvalidId;
+            if (ok) traverse_closest<STACK>(bvh, r, stack, t, u, v, gid);
+            static_cast<float4*>(q.out)[i] = make_float4(t, u, v, u2f(gid));
+        }
+    }
+}
+
+void launch_query_binary(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any, bool deferred)
+{
+    BvhDev   b    = bvh;
+    b.wide8_ok    = 0;
+    uint32_t want = (q.n + kBlock - 1) / kBlock;
+    // (deferred: the count is on the device and is normally small -- one workgroup per CU at most)
+    if (deferred && cfg.cu_count && want > cfg.cu_count) want = cfg.cu_count;
+    if (want == 0) want = 1;
+#define CAP_LAUNCH_QUERY(S, A) \
+    hipLaunchKernelGGL((k_query_binary<S, A>), dim3(resident_grid<k_query_binary<S, A>>(cfg, want)), dim3(kBlock), 0, cfg.stream, b, q, deferred ? 1u : 0u)
+    if (cfg.stack_entries <= 32)
+    {
+        if (any) CAP_LAUNCH_QUERY(32, true); else CAP_LAUNCH_QUERY(32, false);
+    }
+    else
+    {
+        if (any) CAP_LAUNCH_QUERY(64, true); else CAP_LAUNCH_QUERY(64, false);
+    }
+#undef CAP_LAUNCH_QUERY
+}
 }  // namespace cap

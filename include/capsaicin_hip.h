@@ -296,6 +296,47 @@ int cap_readback(CapContext* ctx, CapBufferKind kind, float* dst);
 int cap_stats_get(CapContext* ctx, CapStats* out);
 int cap_stats_reset(CapContext* ctx);
 
+/* ---- ray queries: TraceRay for rays the caller makes (AO, visibility probes, light baking, picking) ----
+ * The traversal the render uses (the compressed 8-wide tree, or the binary tree where that is not used, CAP_NO_WIDE8) on the caller's
+ * rays.  Hit rule = DESIGN.md "Intersection contract", the DXR triangle rule with identity transforms: two-sided, closest hit
+ * accepted for tmin < t < tmax, minimum t wins, equal t goes to the lower triangle id; (u, v) are the barycentrics that weight v1
+ * and v2 (DXR's BuiltInTriangleIntersectionAttributes).  Occlusion is the division-free form tmin * det < T < tmax * det
+ * (RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH).  Records are bit-identical to the oracle's brute force over every triangle, whichever
+ * builder (cap_set_bvh_build) and tree made them.
+ *
+ * triangle = the global triangle id, in mesh-table order then primitive order: triangle p of mesh m (the m-th CapMeshDesc of
+ * cap_scene_upload) has id sum_{k < m} index_count_k / 3 + p -- not first_index_offset / 3.  The reference's InstanceID() /
+ * PrimitiveIndex() (one instance per mesh, tlas_system.cpp:52-55) are (m, p), the pair CAP_BUF_GBUFFER_GEO stores: the caller
+ * maps an id back with the prefix sums of the mesh table's triangle counts.
+ *
+ * Degenerate rays -- a NaN or infinite component of origin or direction, a zero direction, tmax <= tmin or a NaN in either --
+ * are not traversed and report a miss (occlusion 0).  tmax = +inf is a ray like any other: every hit beyond tmin counts.
+ *
+ * Both calls take device pointers on the context's GPU, 16-byte aligned, with ray and output ranges that do not overlap, and are
+ * asynchronous on the context stream (like cap_resolve_tiles): ordered after everything enqueued on the context (a cap_render's
+ * second batch lane included) and before what follows; cap_sync waits for them.  They use the context's traversal spill area
+ * and nothing of the render's state: accumulation, CapStats, queues, post histories and feedback stay as they were.  flags is
+ * reserved (0).  n may exceed 2^32: the library splits it into launches.  Errors: CAP_ERR_INVALID_ARG (flags, NULL,
+ * misalignment, overlap), CAP_ERR_STATE (before cap_bvh_build).  n = 0 does nothing. */
+typedef struct CapRayDesc /* DXR RayDesc layout: 32 B */
+{
+    float origin[3];
+    float tmin;
+    float direction[3];
+    float tmax;
+} CapRayDesc;
+typedef struct CapHit /* 16 B; a miss is (tmax, 0, 0, 0xFFFFFFFF) */
+{
+    float    t;
+    float    u;
+    float    v;
+    uint32_t triangle;
+} CapHit;
+/* closest hit of each ray: device_hits[i] for device_rays[i] */
+int cap_trace_rays(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, uint32_t flags);
+/* 1 if some triangle satisfies the occlusion rule, else 0; one uint32 per ray */
+int cap_trace_occlusion(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded, uint32_t flags);
+
 /* ---- multi-GPU tile exchange (one gather of tile radiance at frame end) ---- */
 /* floats in this context's tile-ordered radiance buffer: max_tiles_per_shard * 64 * 4 (same on every shard) */
 int cap_tile_buffer_floats(CapContext* ctx, size_t* out_floats);
