@@ -56,6 +56,48 @@ class BvhInfo(C.Structure):
                 ("build_ms", C.c_double)]
 
 
+class RefitInfo(C.Structure):
+    """CapRefitInfo: what cap_bvh_refit reports (the ratio of the two metrics tells when a rebuild pays)."""
+    _fields_ = [("ms", C.c_double), ("expected_node_visits", C.c_double), ("expected_node_visits_built", C.c_double)]
+
+
+VERTICES_DEVICE = 1  # CAP_VERTICES_DEVICE
+
+
+def vertex_update_args(vertex_count, positions=None, normals=None, texcoords=None):
+    """Checks the arrays of Renderer.update_vertices and returns (pointers, flags, keep-alive).  numpy arrays are host arrays; torch
+    tensors must be contiguous float32 on a GPU (device pointers, CAP_VERTICES_DEVICE); one call takes one kind.  Shapes (V, 3) /
+    (V, 3) / (V, 2) or flat."""
+    arrays = (("positions", positions, 3), ("normals", normals, 3), ("texcoords", texcoords, 2))
+    kinds = {("numpy" if isinstance(a, np.ndarray) else "torch" if hasattr(a, "data_ptr") else type(a).__name__)
+             for _, a, _ in arrays if a is not None}
+    if kinds - {"numpy", "torch"}:
+        raise CapError("update_vertices takes numpy arrays or torch tensors, got %s" % ", ".join(sorted(kinds - {"numpy", "torch"})))
+    if len(kinds) > 1:
+        raise CapError("update_vertices: mixing host (numpy) and device (torch) arrays in one call")
+    device = kinds == {"torch"}
+    ptrs, keep = [], []
+    for name, a, width in arrays:
+        if a is None:
+            ptrs.append(None)
+            continue
+        shape = tuple(a.shape)
+        if shape not in ((vertex_count, width), (vertex_count * width,)):
+            raise CapError("update_vertices: %s has shape %s, expected (%d, %d) or (%d,)" % (name, shape, vertex_count, width, vertex_count * width))
+        if device:
+            import torch
+            if a.dtype != torch.float32 or not a.is_contiguous() or a.device.type != "cuda":
+                raise CapError("update_vertices: %s must be a contiguous float32 tensor on the GPU, got %s on %s" % (name, a.dtype, a.device))
+            ptrs.append(C.c_void_p(a.data_ptr()))
+        else:
+            if a.dtype != np.float32:
+                raise CapError("update_vertices: %s must be float32, got %s" % (name, a.dtype))
+            a = np.ascontiguousarray(a)
+            ptrs.append(_p(a))
+        keep.append(a)
+    return ptrs, (VERTICES_DEVICE if device else 0), keep
+
+
 class RayDesc(C.Structure):
     """CapRayDesc: DXR RayDesc layout (32 bytes)."""
     _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("direction", C.c_float * 3), ("tmax", C.c_float)]
@@ -127,6 +169,8 @@ SYMBOLS = {
     "cap_bvh_info": (_i, [_vp, C.POINTER(BvhInfo)]),
     "cap_bvh_readback": (_i, [_vp, _vp, _vp]),
     "cap_bvh_wide_readback": (_i, [_vp, _vp, _vp, _vp]),
+    "cap_scene_update_vertices": (_i, [_vp, _vp, _vp, _vp, _u32]),
+    "cap_bvh_refit": (_i, [_vp, C.POINTER(RefitInfo)]),
     "cap_camera_set": (_i, [_vp, C.POINTER(CameraData)]),
     "cap_prev_camera_set": (_i, [_vp, C.POINTER(CameraData)]),
     "cap_set_resolution": (_i, [_vp, _u32, _u32]),
@@ -363,6 +407,7 @@ class Renderer:
         self.width = self.height = 0
         self.device = device
         self._tri_end = np.zeros(0, np.int64)  # inclusive prefix sums of the uploaded mesh table's triangle counts
+        self._vertex_count = 0
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -379,10 +424,12 @@ class Renderer:
         _check(lib().cap_scene_upload(self.ctx, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), _p(a[4]), a[0].size // 3, a[3].size,
                                       a[4].shape[0]), "cap_scene_upload")
         self._set_mesh_table(a[4])
+        self._vertex_count = a[0].size // 3
 
     def upload_geometry(self, geo):
         _check(lib().cap_scene_upload_geometry(self.ctx, geo.h), "cap_scene_upload_geometry")
         self._set_mesh_table(geo.meshes)
+        self._vertex_count = int(geo.view.vertex_count)
 
     def _set_mesh_table(self, meshes):
         self._tri_end = np.cumsum(np.asarray(meshes, np.uint32).reshape(-1, 8)[:, 2].astype(np.int64) // 3)
@@ -413,6 +460,27 @@ class Renderer:
     def build_bvh(self):
         _check(lib().cap_bvh_build(self.ctx), "cap_bvh_build")
         return self.bvh_info()
+
+    def update_vertices(self, positions=None, normals=None, texcoords=None):
+        """Replace vertex attributes of the uploaded scene (same topology); None keeps an array.  numpy arrays go in as host arrays,
+        contiguous float32 torch tensors on this context's device as device pointers (after torch's current stream is synchronised).
+        The trees are stale until refit_bvh() or build_bvh()."""
+        ptrs, flags, keep = vertex_update_args(self._vertex_count, positions, normals, texcoords)
+        if flags:
+            import torch
+            dev = torch.device("cuda", self.device)
+            for a in keep:
+                if a.device != dev:
+                    raise CapError("update_vertices: tensors must be on %s, got %s" % (dev, a.device))
+            torch.cuda.current_stream(dev).synchronize()  # the arrays were written on torch's stream
+        _check(lib().cap_scene_update_vertices(self.ctx, ptrs[0], ptrs[1], ptrs[2], flags), "cap_scene_update_vertices")
+
+    def refit_bvh(self):
+        """Refit the trees of the last build_bvh() to the current vertices; returns RefitInfo (ms, expected_node_visits,
+        expected_node_visits_built)."""
+        info = RefitInfo()
+        _check(lib().cap_bvh_refit(self.ctx, C.byref(info)), "cap_bvh_refit")
+        return info
 
     def bvh_info(self):
         bi = BvhInfo()

@@ -9,6 +9,7 @@
 // The traversal result does not depend on the tree shape (closest hit = min t, ties to the lower triangle id).
 #include "cap_kernels.h"
 #include "cap_wide.h"
+#include "cap_wide_quant.h"
 
 namespace cap
 {
@@ -573,29 +574,7 @@ __global__ __launch_bounds__(kBlock) void k_wide_level(WideCollapseArgs a)
     }
     uint32_t word[kWideNodeWords];
     for (uint32_t k = 0; k < kWideNodeWords; ++k) word[k] = 0u;
-    // grid origin (the node's low corner rounded down to float) and steps (the smallest power of two with <= 255 steps)
-    float  p[3];
-    double step[3];
-    uint32_t eb[3];
-    for (int k = 0; k < 3; ++k)
-    {
-        p[k] = (float)nlo[k];
-        if ((double)p[k] > nlo[k]) p[k] = u2f(p[k] > 0.0f ? f2u(p[k]) - 1u : (p[k] < 0.0f ? f2u(p[k]) + 1u : 0x80000001u));  // next float down
-        word[k] = f2u(p[k]);
-        const double ext = nhi[k] - (double)p[k];
-        int          e   = -100;
-        if (ext > 0.0)
-        {
-            int fe;
-            (void)frexp(ext / 255.0, &fe);
-            e = fe - 1 > -100 ? fe - 1 : -100;
-        }
-        while (ceil(ext / ldexp(1.0, e)) > 255.0) ++e;
-        step[k] = ldexp(1.0, e);
-        eb[k]   = (uint32_t)(e + 127);
-    }
-    word[3] = eb[0] << 23;
-    word[7] = ((eb[1] << 23) & 0xffff0000u) | ((eb[2] << 23) >> 16);
+    const WideGrid grid = wide_grid(nlo, nhi, word);
     uint32_t imask = 0u, tvalid = 0u, n_inner = 0u, n_tris = 0u;
     uint32_t leaf_tri[8][kWideLeafMax];
     uint32_t leaf_n[8];
@@ -625,14 +604,7 @@ __global__ __launch_bounds__(kBlock) void k_wide_level(WideCollapseArgs a)
             for (uint32_t k = 0; k < leaf_n[s]; ++k) tvalid |= 1u << (k * 8u + (uint32_t)s);
             n_tris += leaf_n[s];
         }
-        for (int k = 0; k < 3; ++k)
-        {
-            double qlo = floor((clo[i][k] - (double)p[k]) / step[k]), qhi = ceil((chi[i][k] - (double)p[k]) / step[k]);
-            qlo = fmin(fmax(qlo, 0.0), 255.0), qhi = fmin(fmax(qhi, 0.0), 255.0);
-            const uint32_t wi = 8u + 2u * (uint32_t)k + ((uint32_t)s >> 2), sh = 8u * ((uint32_t)s & 3u);
-            word[wi] |= (uint32_t)qlo << sh;
-            word[wi + 6] |= (uint32_t)qhi << sh;
-        }
+        wide_quantise(grid, clo[i], chi[i], s, word);
     }
     const uint32_t child_base = n_inner ? a.cnt[2 * (size_t)(w - a.begin)] : 0u;
     const uint32_t tri_base   = n_tris ? a.cnt[2 * (size_t)(w - a.begin) + 1] : 0u;
@@ -648,16 +620,19 @@ __global__ __launch_bounds__(kBlock) void k_wide_level(WideCollapseArgs a)
 }
 }  // namespace
 
-int launch_wide_collapse(hipStream_t stream, WideCollapseArgs a, uint32_t* node_count, uint32_t* depth, uint32_t* top_nodes)
+int launch_wide_collapse(hipStream_t stream, WideCollapseArgs a, uint32_t* node_count, uint32_t* depth, uint32_t* top_nodes,
+                         std::vector<uint32_t>* level_begin)
 {
     // level 0 = the root (binary node 0); alloc[0] counts allocated wide nodes, alloc[1] emitted triangles
     const uint32_t init[2] = {1u, 0u}, root_task = 0u;
     if (hipMemcpyAsync(a.alloc, init, sizeof(init), hipMemcpyHostToDevice, stream) != hipSuccess) return 1;
     if (hipMemcpyAsync(a.task, &root_task, sizeof(root_task), hipMemcpyHostToDevice, stream) != hipSuccess) return 1;
     uint32_t begin = 0u, end = 1u, levels = 0u, top = 0u;
+    if (level_begin) level_begin->clear();
     while (begin < end)
     {
         ++levels;
+        if (level_begin) level_begin->push_back(begin);
         if (levels <= 3) top = end < kWideTopNodes ? end : kWideTopNodes;
         a.begin = begin, a.end = end;
         hipLaunchKernelGGL(k_wide_count, dim3((end - begin + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
@@ -675,11 +650,19 @@ int launch_wide_collapse(hipStream_t stream, WideCollapseArgs a, uint32_t* node_
         if (allocated > a.capacity) return 2;  // cannot happen: a wide node stands for >= 4 triangles
         begin = end, end = allocated;
     }
+    if (level_begin) level_begin->push_back(end);
     *node_count = end, *depth = levels, *top_nodes = top;
     return 0;
 }
 
 size_t bvh_radix_blocks(uint32_t n) { return (n + kSortTile - 1) / kSortTile; }
+
+// refit (refit.hip): the build's climb over the kept tree, leaves in the kept order a.leaf_tri, parent links already derived
+void launch_bvh_refit_climb(hipStream_t stream, const BvhBuildArgs& a)
+{
+    const uint32_t n = a.tri_count;
+    if (n) hipLaunchKernelGGL(k_refit, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a, a.leaf_tri);
+}
 
 static void bvh_setup(hipStream_t stream, const BvhBuildArgs& a)
 {

@@ -3,6 +3,8 @@
 
 #include "cap_device.h"
 
+#include <vector>
+
 namespace cap
 {
 // A/B and diagnostic switches: ONE table per context (round 6; 26 getenv() calls with function-local statics before), filled from the
@@ -233,7 +235,29 @@ struct WideCollapseArgs
     uint32_t*       cnt;  // 2 * capacity + 2 * (capacity / 1024 + 2) words: per node of the level being written, (inner children, triangles) -> their bases; the scan's tile sums behind
     uint32_t        begin, end;
 };
-int      launch_wide_collapse(hipStream_t stream, WideCollapseArgs a, uint32_t* node_count, uint32_t* depth, uint32_t* top_nodes);
+// level_begin (may be null): the first node of every level, then the node count -- level l = [level_begin[l], level_begin[l + 1])
+int      launch_wide_collapse(hipStream_t stream, WideCollapseArgs a, uint32_t* node_count, uint32_t* depth, uint32_t* top_nodes,
+                          std::vector<uint32_t>* level_begin = nullptr);
+// ---- refit of the kept trees to moved vertices (refit.hip, cap_bvh_refit) ----
+// binary tree: triangle setup (bounds reset first), parent links from the nodes, the build's climb (bvh.hip k_refit) in leaf order
+void   launch_bvh_refit_climb(hipStream_t stream, const BvhBuildArgs& a);  // (bvh.hip) the climb alone
+void   launch_refit_binary(hipStream_t stream, const BvhBuildArgs& a);
+// expected node visits of the binary tree, 1 + sum(inner child box area) / root box area, into *out (device); nothing for n_tris < 2.
+// scratch: tree_visits_scratch() doubles.  A fixed reduction order: the same boxes give the same bits.
+size_t tree_visits_scratch();
+void   launch_tree_visits(hipStream_t stream, const float4* nodes, uint32_t n_tris, double* scratch, double* out);
+// 8-wide view, level by level from the deepest (after the binary refit and the gather of tris8): boxes = 6 floats per wide node
+struct WideRefitArgs
+{
+    uint32_t*     nodes8;
+    const float4* tris8;
+    const float4* tri_box;
+    float*        boxes;
+    double        pad;           // kWidePad * max(extent, |coordinate|) of the NEW scene bounds
+    uint32_t      one_triangle;  // the one-triangle scene (host collapse: its child box is the padded scene box)
+    uint32_t      begin, end;
+};
+void launch_refit_wide(hipStream_t stream, WideRefitArgs a, const std::vector<uint32_t>& level_begin);
 uint32_t wide8_stack_pairs();  // (g_base, g_mask) entries a lane of the wide kernels can hold: the tree's depth - 1 must fit
 
 // ---- reconstruction chain (post.hip): Gather -> Accumulate -> BlurDisocclusion -> Blur -> Combine -> TAA ----

@@ -176,6 +176,14 @@ struct CapContext
     DevBuf<uint32_t> sahdev_words;  // CAP_BVH_BUILD_SAH_DEVICE scratch (ploc.hip)
     CapBvhInfo       bvh_info{};
     bool             bvh_ready = false;
+    // vertex updates and refit (cap_scene_update_vertices, cap_bvh_refit, refit.hip)
+    bool                  bvh_stale = false;             // vertices changed since the trees were last brought up to date
+    bool                  positions_host_stale = false;  // positions_host lags a device-side update (read back only when needed)
+    bool                  visits_built_known = false;    // refit_visits_built holds the metric of the last build's boxes
+    double                refit_visits_built = 0.0;
+    std::vector<uint32_t> wide_levels;                   // level l of the 8-wide view = nodes [wide_levels[l], wide_levels[l + 1])
+    DevBuf<float>         wide_boxes;                    // refit scratch: each wide node's box (6 floats)
+    DevBuf<double>        refit_sums;                    // refit scratch: partial sums of the tree metric, then its two values
 
     // camera / screen
     CapCameraData camera{}, prev_camera{};
@@ -695,6 +703,8 @@ int cap_scene_upload(CapContext* c, const float* positions, const float* normals
     c->vertex_count = vertex_count, c->index_count = index_count, c->mesh_count = mesh_count, c->tri_count = (uint32_t)tri_ids.size();
     c->scene_ready = true;
     c->bvh_ready   = false;
+    c->bvh_stale   = false;
+    c->positions_host_stale = false;
     c->lane1_failed_paths = 0;  // another scene, other buffers: a second batch lane that did not fit before may fit now
     return CAP_OK;
 }
@@ -778,12 +788,94 @@ int cap_bluenoise_upload(CapContext* c, const uint8_t* rgba8)
 // Cornell box (its lamp hangs 1 cm below it: rays from the ceiling's rim to the lamp graze it) fails (ii) and stays in the list, as
 // does every pair that is not a hull face.  tests: the EXT parity tests run this list; `tools/build_variant.sh neecheck -DCAP_NEE_CHECK`
 // runs both lists on every ray and counts disagreements in CapStats::guard_shade (0 over BASELINE configs[2]'s 8 G next-event rays).
+static int ensure_positions_host(CapContext* c);
+// the build's (and the refit's) view of the context's scene and tree buffers
+static BvhBuildArgs bvh_args(const CapContext* c)
+{
+    BvhBuildArgs a{};
+    a.positions = c->positions.p, a.normals = c->normals.p, a.texcoords = c->texcoords.p, a.indices = c->indices.p;
+    a.tri_ids = c->tri_ids.p, a.mesh_offsets = c->mesh_offsets.p, a.tri_count = c->tri_count;
+    a.shade_tris = c->shade_tris.p, a.tris_sorted = c->tris_sorted.p, a.nodes = c->nodes.p, a.leaf_tri = c->leaf_tri.p;
+    a.tri_raw = c->tri_raw.p, a.tri_box = c->tri_box.p;
+    a.keys[0] = c->keys0.p, a.keys[1] = c->keys1.p, a.vals[0] = c->vals0.p, a.vals[1] = c->vals1.p;
+    a.hist = c->hist.p, a.parent = c->parent.p, a.flags = c->flags.p, a.bounds = c->bvh_misc.p, a.max_depth = c->bvh_misc.p + 6;
+    return a;
+}
+
+// CapBvhInfo::bounds_lo / hi from the six ordered-uint words k_tri_setup reduced into bvh_misc
+static void set_bounds(CapBvhInfo& bi, const uint32_t misc[6])
+{
+    auto dec = [](uint32_t o) {
+        uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
+        float    f;
+        memcpy(&f, &u, 4);
+        return f;
+    };
+    for (int k = 0; k < 3; ++k) bi.bounds_lo[k] = dec(misc[k]), bi.bounds_hi[k] = dec(misc[3 + k]);
+}
+
+// the 8-wide view's child-box padding, kWidePad * max(scene extent, largest |coordinate|) (wide_builder.cpp: its error budget)
+static double wide_pad(const CapBvhInfo& bi)
+{
+    double m = 0.0;
+    for (int k = 0; k < 3; ++k)
+        m = std::max({m, (double)bi.bounds_hi[k] - (double)bi.bounds_lo[k], std::fabs((double)bi.bounds_lo[k]), std::fabs((double)bi.bounds_hi[k])});
+    return (double)kWidePad * std::max(m, 1e-30);
+}
+
+// Exhaustive path (cap_set_traversal): triangles that come in fans (k, k + 1 share v0 and the edge v0->v2, as every
+// triangulated quad of an OBJ face does) are stored as one record, so the kernels compute tvec, q and the shared edge's dot
+// product once for both.  Same per-triangle arithmetic, same results; the pairing only depends on bit-equal vertices.
+static int upload_fan_records(CapContext* c)
+{
+    const uint32_t n = c->tri_count;
+    c->fan_pair_count = c->fan_single_count = 0;
+    if (n && n <= 4096)
+    {
+        std::vector<float> raw(16 * (size_t)n);
+        HIP_TRY(hipMemcpy(raw.data(), c->tri_raw.p, sizeof(float) * raw.size(), hipMemcpyDeviceToHost));
+        std::vector<float> pairs, singles;
+        auto rec = [&](uint32_t k) { return raw.data() + 16 * (size_t)k; };  // v0(3) e1(3) e2(3) n(3) id(1) pad(3)
+        for (uint32_t k = 0; k < n;)
+        {
+            const float* a = rec(k);
+            const float* b = k + 1 < n ? rec(k + 1) : nullptr;
+            const bool   fan = b && memcmp(a, b, 12) == 0 && memcmp(a + 6, b + 3, 12) == 0;  // same v0, e2(k) == e1(k+1)
+            if (fan)
+            {
+                // (v0, e1, e2, e3 = e2 of k+1, nA, nB, id of k, 0)
+                const float r[20] = {a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], b[6], b[7], b[8], a[9], a[10], a[11],
+                                     b[9], b[10], b[11], a[12], 0.0f};
+                pairs.insert(pairs.end(), r, r + 20);
+                k += 2;
+            }
+            else
+            {
+                singles.insert(singles.end(), a, a + 16);
+                k += 1;
+            }
+        }
+        c->fan_pair_count   = (uint32_t)(pairs.size() / 20);
+        c->fan_single_count = (uint32_t)(singles.size() / 16);
+        // padded by four records so that an unrolled scalar load past the end stays inside the allocation
+        pairs.resize(pairs.size() + 80, 0.0f), singles.resize(singles.size() + 64, 0.0f);
+        c->fan_pairs_host   = pairs;
+        HIP_TRY(c->fan_pairs.ensure(pairs.size() / 4));
+        HIP_TRY(c->fan_singles.ensure(singles.size() / 4));
+        HIP_TRY(hipMemcpy(c->fan_pairs.p, pairs.data(), sizeof(float) * pairs.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->fan_singles.p, singles.data(), sizeof(float) * singles.size(), hipMemcpyHostToDevice));
+    }
+    if (c->fan_pair_count == 0) c->fan_pairs_host.clear();
+    return CAP_OK;
+}
+
 static int update_nee_pairs(CapContext* c)
 {
     c->fan_pair_nee_count = c->fan_pair_count;
     c->fan_pairs_nee.release();
     const uint32_t np = c->fan_pair_count;
     if (!np || !c->materials_ready || c->light_tris_host.empty() || c->fan_pairs_host.size() < 20 * (size_t)np || c->sw.on(SW_NO_NEE_PAIR_CULL)) return CAP_OK;
+    if (const int rc = ensure_positions_host(c)) return rc;
     const size_t nv = c->positions_host.size() / 3;
     if (!nv) return CAP_OK;
     auto P = [&](size_t i, int k) { return (double)c->positions_host[3 * i + k]; };
@@ -873,13 +965,30 @@ static int update_nee_pairs(CapContext* c)
     return CAP_OK;
 }
 
-int cap_materials_upload(CapContext* c, const CapMaterial* materials, uint32_t mesh_count)
+// positions_host after a device-side vertex update: read back once, and only when the light table or the next-event pair list needs it
+// (a large scene without lights does not pay a device-to-host copy per refit)
+static int ensure_positions_host(CapContext* c)
 {
-    if (!c || (!materials && mesh_count)) return fail(CAP_ERR_INVALID_ARG, "cap_materials_upload: NULL argument");
-    if (!c->scene_ready || mesh_count != c->mesh_count) return fail(CAP_ERR_STATE, "cap_materials_upload: expected %u materials (one per mesh)", c->mesh_count);
-    c->materials_host.assign(materials, materials + mesh_count);
-    // Light table of the EXT model: emissive triangles in global triangle order with float prefix sums of their areas
-    // (area = |e1 x e2| / 2 with the arithmetic of cap_math.h, so the table is the one the oracle builds).
+    if (!c->positions_host_stale) return CAP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->positions_host.resize(3 * (size_t)c->vertex_count);
+    if (c->vertex_count)
+        HIP_TRY(hipMemcpy(c->positions_host.data(), c->positions.p, sizeof(float) * c->positions_host.size(), hipMemcpyDeviceToHost));
+    c->positions_host_stale = false;
+    return CAP_OK;
+}
+
+// Light table of the EXT model: emissive triangles in global triangle order with float prefix sums of their areas
+// (area = |e1 x e2| / 2 with the arithmetic of cap_math.h, so the table is the one the oracle builds).  From materials_host and the
+// current vertices: cap_materials_upload and cap_bvh_refit.
+static int upload_light_table(CapContext* c)
+{
+    const CapMaterial* materials = c->materials_host.data();
+    bool               any = false;
+    for (uint32_t m = 0; m < c->mesh_count; ++m) any = any || materials[m].ke[0] > 0.0f || materials[m].ke[1] > 0.0f || materials[m].ke[2] > 0.0f;
+    if (any)
+        if (const int rc = ensure_positions_host(c)) return rc;
     std::vector<uint32_t> light_tris;
     std::vector<float>    light_cdf;
     float                 area = 0.0f;
@@ -905,8 +1014,6 @@ int cap_materials_upload(CapContext* c, const CapMaterial* materials, uint32_t m
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(c->materials.ensure(mesh_count));
-    if (mesh_count) HIP_TRY(hipMemcpy(c->materials.p, materials, sizeof(CapMaterial) * mesh_count, hipMemcpyHostToDevice));
     HIP_TRY(c->light_tris.ensure(light_tris.size()));
     HIP_TRY(c->light_cdf.ensure(light_cdf.size()));
     if (!light_tris.empty())
@@ -916,9 +1023,23 @@ int cap_materials_upload(CapContext* c, const CapMaterial* materials, uint32_t m
     }
     c->light_count     = (uint32_t)light_tris.size();
     c->light_area      = area;
-    c->materials_ready = true;
     c->light_tris_host = light_tris;
-    if (c->bvh_ready) return update_nee_pairs(c);
+    return CAP_OK;
+}
+
+int cap_materials_upload(CapContext* c, const CapMaterial* materials, uint32_t mesh_count)
+{
+    if (!c || (!materials && mesh_count)) return fail(CAP_ERR_INVALID_ARG, "cap_materials_upload: NULL argument");
+    if (!c->scene_ready || mesh_count != c->mesh_count) return fail(CAP_ERR_STATE, "cap_materials_upload: expected %u materials (one per mesh)", c->mesh_count);
+    c->materials_host.assign(materials, materials + mesh_count);
+    c->materials_ready = false;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(c->materials.ensure(mesh_count));
+    if (mesh_count) HIP_TRY(hipMemcpy(c->materials.p, materials, sizeof(CapMaterial) * mesh_count, hipMemcpyHostToDevice));
+    if (const int rc = upload_light_table(c)) return rc;
+    c->materials_ready = true;
+    if (c->bvh_ready && !c->bvh_stale) return update_nee_pairs(c);  // (a stale tree gets its list from cap_bvh_refit / cap_bvh_build)
     return CAP_OK;
 }
 
@@ -946,13 +1067,7 @@ int cap_bvh_build(CapContext* c)
     HIP_TRY(c->parent.ensure(2 * (size_t)n));
     HIP_TRY(c->flags.ensure(n));
     HIP_TRY(c->bvh_misc.ensure(8));
-    BvhBuildArgs a{};
-    a.positions = c->positions.p, a.normals = c->normals.p, a.texcoords = c->texcoords.p, a.indices = c->indices.p;
-    a.tri_ids = c->tri_ids.p, a.mesh_offsets = c->mesh_offsets.p, a.tri_count = n;
-    a.shade_tris = c->shade_tris.p, a.tris_sorted = c->tris_sorted.p, a.nodes = c->nodes.p, a.leaf_tri = c->leaf_tri.p;
-    a.tri_raw = c->tri_raw.p, a.tri_box = c->tri_box.p;
-    a.keys[0] = c->keys0.p, a.keys[1] = c->keys1.p, a.vals[0] = c->vals0.p, a.vals[1] = c->vals1.p;
-    a.hist = c->hist.p, a.parent = c->parent.p, a.flags = c->flags.p, a.bounds = c->bvh_misc.p, a.max_depth = c->bvh_misc.p + 6;
+    const BvhBuildArgs a = bvh_args(c);
     // AUTO: scenes the exhaustive kernels handle need no tree quality (Morton hierarchy); everything else gets the clustering
     // build -- on the device like the driver build it replaces (blas_system.cpp:42-65), within 1 % of the host SAH tree's trace
     // times (builders table) at 1 / 40 of its build time.  The host SAH build stays available by name.
@@ -1015,22 +1130,14 @@ int cap_bvh_build(CapContext* c)
     bi.node_count     = n > 1 ? n - 1 : 0;
     bi.max_depth      = n ? (sah ? host_depth : misc[6]) : 0;
     bi.build_ms       = ms;
-    for (int k = 0; k < 3 && n; ++k)
-    {
-        auto dec = [](uint32_t o) {
-            uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-            float    f;
-            memcpy(&f, &u, 4);
-            return f;
-        };
-        bi.bounds_lo[k] = dec(misc[k]), bi.bounds_hi[k] = dec(misc[3 + k]);
-    }
+    if (n) set_bounds(bi, misc);
     if (bi.max_depth > 64)
         return fail(CAP_ERR_UNSUPPORTED, "LBVH depth %u exceeds the 64-entry traversal stack", bi.max_depth);
     bi.stack_entries = bi.max_depth <= 32 ? 32 : 64;
     // Compressed 8-wide view of the same tree (cap_wide.h) for the extension- and shadow-ray kernels of scenes the exhaustive
     // kernels do not take: collapsed on the host from the binary nodes (read back when the device built them).
     c->wide8_nodes = c->wide8_depth = c->wide8_top = 0;
+    c->wide_levels.clear();
     if (n >= 1)
     {
         const auto w0 = std::chrono::steady_clock::now();
@@ -1047,15 +1154,12 @@ int cap_bvh_build(CapContext* c)
             HIP_TRY(c->wide_task.ensure(cap));
             HIP_TRY(c->wide_cnt.ensure(2 * (size_t)cap + 2 * ((size_t)cap / 1024 + 2)));  // per-level bases + the scan's tile sums
             HIP_TRY(c->wide_alloc.ensure(2));
-            double m = 0.0;
-            for (int k = 0; k < 3; ++k)
-                m = std::max({m, (double)bi.bounds_hi[k] - (double)bi.bounds_lo[k], std::fabs((double)bi.bounds_lo[k]), std::fabs((double)bi.bounds_hi[k])});
             WideCollapseArgs wa{};
             wa.bnodes = c->nodes.p, wa.count = c->keys1.p, wa.n_tris = n, wa.capacity = cap;
-            wa.pad = (double)kWidePad * std::max(m, 1e-30);
+            wa.pad = wide_pad(bi);
             wa.task = c->wide_task.p, wa.cnt = c->wide_cnt.p, wa.alloc = c->wide_alloc.p, wa.nodes8 = reinterpret_cast<uint32_t*>(c->nodes8.p), wa.tri_src = c->wide_src.p;
             uint32_t count = 0;
-            if (launch_wide_collapse(c->stream, wa, &count, &wdepth, &wtop) != 0) return fail(CAP_ERR_HIP, "cap_bvh_build: device collapse into the 8-wide view failed");
+            if (launch_wide_collapse(c->stream, wa, &count, &wdepth, &wtop, &c->wide_levels) != 0) return fail(CAP_ERR_HIP, "cap_bvh_build: device collapse into the 8-wide view failed");
             wn = count;
         }
         else
@@ -1068,6 +1172,8 @@ int cap_bvh_build(CapContext* c)
             WideTree wt;
             build_wide_tree(n >= 2 ? bnodes_host.data() : nullptr, n, bi.bounds_lo, bi.bounds_hi, wt);
             wn = wt.nodes.size() / kWideNodeWords, wdepth = wt.depth, wtop = wt.top_nodes;
+            c->wide_levels = wt.level_begin;
+            c->wide_levels.push_back((uint32_t)wn);
             HIP_TRY(c->nodes8.ensure((kWideNodeStride / 4) * std::max<size_t>(wn + 1, kWideTopNodes)));
             if (wn) HIP_TRY(hipMemcpy2D(c->nodes8.p, sizeof(uint32_t) * kWideNodeStride, wt.nodes.data(), sizeof(uint32_t) * kWideNodeWords,
                                         sizeof(uint32_t) * kWideNodeWords, wn, hipMemcpyHostToDevice));
@@ -1082,48 +1188,113 @@ int cap_bvh_build(CapContext* c)
         if (c->sw.on(SW_TRACE_LAUNCHES))
             fprintf(stderr, "[cap] wide view: %zu nodes, depth %u, top %u, %.1f ms\n", wn, wdepth, wtop, c->wide8_ms);
     }
-    // Exhaustive path (cap_set_traversal): triangles that come in fans (k, k + 1 share v0 and the edge v0->v2, as every
-    // triangulated quad of an OBJ face does) are stored as one record, so the kernels compute tvec, q and the shared edge's dot
-    // product once for both.  Same per-triangle arithmetic, same results; the pairing only depends on bit-equal vertices.
-    c->fan_pair_count = c->fan_single_count = 0;
-    if (n && n <= 4096)
-    {
-        std::vector<float> raw(16 * (size_t)n);
-        HIP_TRY(hipMemcpy(raw.data(), c->tri_raw.p, sizeof(float) * raw.size(), hipMemcpyDeviceToHost));
-        std::vector<float> pairs, singles;
-        auto rec = [&](uint32_t k) { return raw.data() + 16 * (size_t)k; };  // v0(3) e1(3) e2(3) n(3) id(1) pad(3)
-        for (uint32_t k = 0; k < n;)
-        {
-            const float* a = rec(k);
-            const float* b = k + 1 < n ? rec(k + 1) : nullptr;
-            const bool   fan = b && memcmp(a, b, 12) == 0 && memcmp(a + 6, b + 3, 12) == 0;  // same v0, e2(k) == e1(k+1)
-            if (fan)
-            {
-                // (v0, e1, e2, e3 = e2 of k+1, nA, nB, id of k, 0)
-                const float r[20] = {a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], b[6], b[7], b[8], a[9], a[10], a[11],
-                                     b[9], b[10], b[11], a[12], 0.0f};
-                pairs.insert(pairs.end(), r, r + 20);
-                k += 2;
-            }
-            else
-            {
-                singles.insert(singles.end(), a, a + 16);
-                k += 1;
-            }
-        }
-        c->fan_pair_count   = (uint32_t)(pairs.size() / 20);
-        c->fan_single_count = (uint32_t)(singles.size() / 16);
-        // padded by four records so that an unrolled scalar load past the end stays inside the allocation
-        pairs.resize(pairs.size() + 80, 0.0f), singles.resize(singles.size() + 64, 0.0f);
-        c->fan_pairs_host   = pairs;
-        HIP_TRY(c->fan_pairs.ensure(pairs.size() / 4));
-        HIP_TRY(c->fan_singles.ensure(singles.size() / 4));
-        HIP_TRY(hipMemcpy(c->fan_pairs.p, pairs.data(), sizeof(float) * pairs.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->fan_singles.p, singles.data(), sizeof(float) * singles.size(), hipMemcpyHostToDevice));
-    }
-    c->bvh_ready     = true;
-    if (c->fan_pair_count == 0) c->fan_pairs_host.clear();
+    if (const int rc = upload_fan_records(c)) return rc;
+    c->bvh_ready          = true;
+    c->bvh_stale          = false;
+    c->visits_built_known = false;  // the first refit measures the boxes this build leaves
     return update_nee_pairs(c);
+}
+
+int cap_scene_update_vertices(CapContext* c, const float* positions, const float* normals, const float* texcoords, uint32_t flags)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_scene_update_vertices: ctx is NULL");
+    if (!c->scene_ready) return fail(CAP_ERR_STATE, "cap_scene_update_vertices: no scene uploaded");
+    if (flags & ~(uint32_t)CAP_VERTICES_DEVICE) return fail(CAP_ERR_INVALID_ARG, "cap_scene_update_vertices: unknown flags 0x%x", flags);
+    const bool   device = (flags & CAP_VERTICES_DEVICE) != 0;
+    const float* src[3] = {positions, normals, texcoords};
+    const char*  name[3] = {"positions", "normals", "texcoords"};
+    float*       dst[3] = {c->positions.p, c->normals.p, c->texcoords.p};
+    const size_t bytes[3] = {sizeof(float) * 3 * (size_t)c->vertex_count, sizeof(float) * 3 * (size_t)c->vertex_count,
+                             sizeof(float) * 2 * (size_t)c->vertex_count};
+    HIP_TRY(hipSetDevice(c->device));
+    if (device)
+        for (int i = 0; i < 3; ++i)
+        {
+            if (!src[i]) continue;
+            if ((uintptr_t)src[i] & 3u) return fail(CAP_ERR_INVALID_ARG, "cap_scene_update_vertices: %s is not 4-byte aligned", name[i]);
+            hipPointerAttribute_t at{};
+            const hipError_t      e = hipPointerGetAttributes(&at, src[i]);
+            if (e != hipSuccess) (void)hipGetLastError();  // (an unknown pointer is the caller's error, not a sticky one)
+            if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != c->device)
+                return fail(CAP_ERR_INVALID_ARG, "cap_scene_update_vertices: %s is not device memory of device %d", name[i], c->device);
+        }
+    // ordered on the context stream behind everything enqueued (a render's second lane joins it at the end of its call)
+    bool copied = false;
+    for (int i = 0; i < 3; ++i)
+        if (src[i] && bytes[i])
+        {
+            HIP_TRY(hipMemcpyAsync(dst[i], src[i], bytes[i], device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+            copied = true;
+        }
+    if (copied && !device) HIP_TRY(hipStreamSynchronize(c->stream));  // host arrays may go once the call returns
+    if (positions)
+    {
+        if (device)
+            c->positions_host_stale = true;  // read back only if the light table or the next-event list needs it
+        else
+        {
+            c->positions_host.assign(positions, positions + 3 * (size_t)c->vertex_count);
+            c->positions_host_stale = false;
+        }
+    }
+    c->bvh_stale = true;  // normals and uvs too: the shading records hold them
+    return CAP_OK;
+}
+
+int cap_bvh_refit(CapContext* c, CapRefitInfo* out)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_refit: ctx is NULL");
+    if (!c->scene_ready || !c->bvh_ready) return fail(CAP_ERR_STATE, "cap_bvh_refit: no tree built since the last cap_scene_upload");
+    HIP_TRY(hipSetDevice(c->device));
+    const auto         wall0 = std::chrono::steady_clock::now();
+    const uint32_t     n     = c->tri_count;
+    const BvhBuildArgs a     = bvh_args(c);
+    // the tree metric of the build's boxes (first refit after a build only: before they are overwritten), then of the refitted ones
+    const size_t scratch = tree_visits_scratch();
+    HIP_TRY(c->refit_sums.ensure(scratch + 2));
+    double* const visits = c->refit_sums.p + scratch;  // {this refit, the build}
+    if (!c->visits_built_known) launch_tree_visits(c->stream, c->nodes.p, n, c->refit_sums.p, visits + 1);
+    // triangle records, shading records, triangle boxes, scene bounds; binary boxes; records in leaf order
+    launch_refit_binary(c->stream, a);
+    launch_tree_visits(c->stream, c->nodes.p, n, c->refit_sums.p, visits);
+    HIP_TRY(hipGetLastError());
+    // the one read inside the refit: the new scene bounds (the wide view's padding, the render's camera test, the queries' hand-over)
+    CapBvhInfo& bi = c->bvh_info;
+    if (n)
+    {
+        uint32_t misc[6];
+        HIP_TRY(hipMemcpyAsync(misc, c->bvh_misc.p, sizeof(misc), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        set_bounds(bi, misc);
+    }
+    // the 8-wide view: records in its leaf order, then its planes bottom-up
+    if (c->wide8_nodes)
+    {
+        launch_gather_wide(c->stream, c->wide_src.p, c->tris_sorted.p, n, c->tris8.p);
+        HIP_TRY(c->wide_boxes.ensure(6 * (size_t)c->wide8_nodes));
+        WideRefitArgs wa{};
+        wa.nodes8 = reinterpret_cast<uint32_t*>(c->nodes8.p), wa.tris8 = c->tris8.p, wa.tri_box = c->tri_box.p, wa.boxes = c->wide_boxes.p;
+        wa.pad = wide_pad(bi), wa.one_triangle = n == 1 ? 1u : 0u;
+        launch_refit_wide(c->stream, wa, c->wide_levels);
+        HIP_TRY(hipGetLastError());
+    }
+    // the small-scene records, the EXT light table and next-event pair list
+    if (const int rc = upload_fan_records(c)) return rc;
+    if (c->materials_ready && c->light_count)
+        if (const int rc = upload_light_table(c)) return rc;
+    if (const int rc = update_nee_pairs(c)) return rc;
+    double v[2] = {1.0, 1.0};
+    if (n >= 2) HIP_TRY(hipMemcpyAsync(v, visits, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!c->visits_built_known) c->refit_visits_built = v[1], c->visits_built_known = true;
+    c->bvh_stale = false;
+    if (out)
+    {
+        out->ms                         = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        out->expected_node_visits       = v[0];
+        out->expected_node_visits_built = c->refit_visits_built;
+    }
+    return CAP_OK;
 }
 
 int cap_bvh_info(CapContext* c, CapBvhInfo* out)
@@ -1138,6 +1309,7 @@ int cap_bvh_readback(CapContext* c, float* nodes, uint32_t* leaf_triangles)
 {
     if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_readback: ctx is NULL");
     if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_bvh_readback: BVH not built");
+    if (c->bvh_stale) return fail(CAP_ERR_STATE, "cap_bvh_readback: vertices changed; call cap_bvh_refit or cap_bvh_build");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (nodes && c->bvh_info.node_count)
@@ -1151,6 +1323,7 @@ int cap_bvh_wide_readback(CapContext* c, uint32_t* nodes, uint32_t* tri_src, uin
 {
     if (!c || !info) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_wide_readback: NULL argument");
     if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_bvh_wide_readback: BVH not built");
+    if (c->bvh_stale) return fail(CAP_ERR_STATE, "cap_bvh_wide_readback: vertices changed; call cap_bvh_refit or cap_bvh_build");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     info[0] = c->wide8_nodes, info[1] = c->wide8_depth, info[2] = c->wide8_top;
@@ -1384,6 +1557,7 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
 {
     if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_render: ctx is NULL");
     if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_render: call cap_bvh_build first");
+    if (c->bvh_stale) return fail(CAP_ERR_STATE, "cap_render: vertices changed; call cap_bvh_refit or cap_bvh_build");
     if (!c->camera_ready || !c->bluenoise_ready || !c->screen.width) return fail(CAP_ERR_STATE, "cap_render: camera, blue noise and resolution must be set");
     const bool ext = (flags & CAP_RENDER_EXT_MATERIALS) != 0;
     if (ext && !c->materials_ready) return fail(CAP_ERR_STATE, "cap_render: CAP_RENDER_EXT_MATERIALS needs cap_materials_upload (one material per mesh)");
@@ -1931,6 +2105,7 @@ int trace_query(CapContext* c, const char* what, const CapRayDesc* rays, uint64_
     if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
     if (flags != 0) return fail(CAP_ERR_INVALID_ARG, "%s: flags is reserved and must be 0 (got 0x%x)", what, flags);
     if (!c->bvh_ready) return fail(CAP_ERR_STATE, "%s: call cap_bvh_build first", what);
+    if (c->bvh_stale) return fail(CAP_ERR_STATE, "%s: vertices changed; call cap_bvh_refit or cap_bvh_build", what);
     if (n == 0) return CAP_OK;
     if (!rays || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
     const uintptr_t r0 = (uintptr_t)rays, o0 = (uintptr_t)out;

@@ -241,7 +241,7 @@ struct Collapser
 
 void build_wide_tree(const float* bnodes, uint32_t n, const float scene_lo[3], const float scene_hi[3], WideTree& out)
 {
-    out.nodes.clear(), out.tri_src.clear();
+    out.nodes.clear(), out.tri_src.clear(), out.level_begin.clear();
     out.depth = 0, out.top_nodes = 0;
     if (n == 0) return;
     double m = 0.0;
@@ -266,6 +266,7 @@ void build_wide_tree(const float* bnodes, uint32_t n, const float scene_lo[3], c
     while (!level.empty())
     {
         ++out.depth;
+        out.level_begin.push_back(level.front().first);
         if (out.depth <= 3) out.top_nodes = (uint32_t)std::min<size_t>(out.nodes.size() / kWideNodeWords, kWideTopNodes);
         next.clear();
         for (const auto& item : level)

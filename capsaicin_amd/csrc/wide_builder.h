@@ -14,6 +14,7 @@ struct WideTree
     std::vector<uint32_t> tri_src;  // wide-order triangle record i = leaf-order (sorted) triangle tri_src[i] of the binary tree
     uint32_t              depth = 0;  // wide nodes on the longest root-to-leaf path (the traversal stack needs depth - 1 entries)
     uint32_t              top_nodes = 0;  // leading nodes that are the root, its children and grandchildren, capped at kWideTopNodes
+    std::vector<uint32_t> level_begin;    // first node of every level (a level's nodes are contiguous): what a refit walks bottom-up
 };
 
 // bnodes: n - 1 binary nodes, 16 floats each (cap_device.h "BVH node": child boxes lo0 hi0 lo1 hi1, then child0 child1 tchild0

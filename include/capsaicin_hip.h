@@ -210,6 +210,34 @@ int cap_bvh_readback(CapContext* ctx, float* nodes, uint32_t* leaf_triangles);
  * the binary tree (CAP_BVH_BUILD_LBVH), on the host from the host's SAH tree.  For tests and tools. */
 int cap_bvh_wide_readback(CapContext* ctx, uint32_t* nodes, uint32_t* tri_src, uint32_t* info);
 
+/* ---- animated geometry: vertex updates and in-place refit (DXR ALLOW_UPDATE / PERFORM_UPDATE) ----
+ * cap_scene_update_vertices replaces vertex attributes of the uploaded scene; topology (indices, mesh table, triangle count) is
+ * unchanged.  positions / normals: 3 * vertex_count floats, texcoords: 2 * vertex_count floats (vertex_count of cap_scene_upload);
+ * a NULL array keeps the current one.  Host arrays are copied before the call returns.  With CAP_VERTICES_DEVICE the three
+ * pointers are 4-byte aligned device pointers on the context's GPU, copied on the context stream after everything enqueued
+ * (a render's second batch lane included); the source must be ready when the call is made and may be reused once cap_bvh_refit
+ * or cap_sync has returned.  Positions must be finite.  The update marks the trees stale: cap_render, cap_trace_rays,
+ * cap_trace_occlusion, cap_bvh_readback and cap_bvh_wide_readback return CAP_ERR_STATE until cap_bvh_refit or cap_bvh_build.
+ * Errors: CAP_ERR_STATE (no scene), CAP_ERR_INVALID_ARG (unknown flags, a device pointer misaligned or not on the context's GPU).
+ *
+ * cap_bvh_refit refits the trees of the last cap_bvh_build to the current vertices: same topology (binary tree, 8-wide view,
+ * leaf orders), new boxes, and everything else the build derives from the vertices.  Hits and images are bit-identical to a
+ * fresh build of the moved scene; the boxes may be looser (CapRefitInfo).  With unchanged positions it reproduces the build's
+ * trees byte for byte.  A later cap_set_bvh_build does not affect it.  Waits for the device, like cap_bvh_build.
+ * Errors: CAP_ERR_STATE (no tree built since the last cap_scene_upload).  out may be NULL. */
+enum
+{
+    CAP_VERTICES_DEVICE = 1u << 0 /* the three pointers are device pointers on the context's GPU */
+};
+int cap_scene_update_vertices(CapContext* ctx, const float* positions, const float* normals, const float* texcoords, uint32_t flags);
+typedef struct CapRefitInfo
+{
+    double ms;                         /* host wall time of the call (as CapBvhInfo::build_ms) */
+    double expected_node_visits;       /* binary tree after the refit: 1 + sum(inner child box area) / root box area */
+    double expected_node_visits_built; /* the same for the boxes the last cap_bvh_build produced */
+} CapRefitInfo;
+int cap_bvh_refit(CapContext* ctx, CapRefitInfo* out);
+
 /* CameraSystem::Run upload (camera_system.cpp:89-131). sensor_size is used as given (the caller applies
  * AdjustCameraAspectBasedOnWindow, camera_system.cpp:10-17). */
 int cap_camera_set(CapContext* ctx, const CapCameraData* camera);
