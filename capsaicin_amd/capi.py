@@ -191,6 +191,7 @@ SYMBOLS = {
     "cap_resolve_tiles": (_i, [_vp, _vp]),
     "cap_trace_rays": (_i, [_vp, _vp, _u64, _vp, _u32]),
     "cap_trace_occlusion": (_i, [_vp, _vp, _u64, _vp, _u32]),
+    "cap_trace_rays_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
     "cap_post_settings_default": (None, [C.POINTER(PostSettings)]),
     "cap_post_frame": (_i, [_vp, C.POINTER(PostSettings), _u32, C.POINTER(CameraData)]),
@@ -627,6 +628,54 @@ class Renderer:
                 return host_out
             return res
         return out
+
+    MULTI_MAX_K, MULTI_CONTINUE = 16, 1  # CAP_MULTI_MAX_K, CAP_MULTI_CONTINUE
+
+    def trace_rays_multi(self, rays, k, counts=False, resume=None, sync=True):
+        """The first k hits of each ray in (t, triangle) order (cap_trace_rays_multi): (N, k, 4) float32 records as trace_rays writes
+        them, miss records (tmax, 0, 0, MISS) after a ray's last hit.  counts=True also returns the number of ALL hits per ray, (N,)
+        int32 (k = 0: counts only, hits is (N, 0, 4)).  resume=<previous page> (the (N, k, 4) result of a call with the same rays)
+        continues after it with CAP_MULTI_CONTINUE, writes the next page over it and returns it.  rays and sync as trace_rays; numpy
+        rays (or a numpy resume page) give numpy results."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        host = isinstance(rays, np.ndarray) or isinstance(resume, np.ndarray)
+        if isinstance(rays, np.ndarray):
+            rays = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).to(dev)
+        if host:
+            sync = True  # the result is read back to the host
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.device != dev:
+            raise CapError("rays must be a contiguous (N, 8) float32 tensor on %s, got %s %s on %s" % (dev, rays.dtype, tuple(rays.shape), rays.device))
+        n, k = rays.shape[0], int(k)
+        if not 0 <= k <= self.MULTI_MAX_K:
+            raise CapError("k must be in 0 .. %d (page with resume=), got %d" % (self.MULTI_MAX_K, k))
+        if k == 0 and (not counts or resume is not None):
+            raise CapError("k = 0 counts only: pass counts=True and no resume page")
+        host_page = None
+        if resume is None:
+            hits = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
+        elif isinstance(resume, np.ndarray):
+            host_page = resume
+            hits = torch.from_numpy(np.ascontiguousarray(resume, np.float32).reshape(n, k, 4)).to(dev)
+        else:
+            hits = resume
+            if hits.dtype != torch.float32 or tuple(hits.shape) != (n, k, 4) or not hits.is_contiguous() or hits.device != dev:
+                raise CapError("resume must be the contiguous (%d, %d, 4) float32 page of the previous call" % (n, k))
+        cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the rays (and the outputs' allocations) were made on torch's stream
+        _check(lib().cap_trace_rays_multi(self.ctx, C.c_void_p(rays.data_ptr()), n, k, C.c_void_p(hits.data_ptr()) if k else None,
+                                          C.c_void_p(cnt.data_ptr()) if counts else None,
+                                          self.MULTI_CONTINUE if resume is not None else 0), "cap_trace_rays_multi")
+        if sync:
+            self.sync()
+        if host:
+            h = hits.cpu().numpy()
+            if host_page is not None:
+                host_page[...] = h.reshape(host_page.shape)
+                h = host_page
+            return (h, cnt.cpu().numpy()) if counts else h
+        return (hits, cnt) if counts else hits
 
     def triangle_to_instance_primitive(self, ids):
         """Global triangle ids (hit_triangles) -> (instance, primitive) = (mesh index, triangle index within the mesh), the pair

@@ -107,6 +107,20 @@ bool query8_stack_matches();  // the wide query kernels' pair stack is the one t
 void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any);
 // binary tree, per lane: every ray of q (deferred = false), or the q.work[kCounterStride] rays listed in q.defer
 void launch_query_binary(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any, bool deferred);
+// Multi-hit queries (cap_trace_rays_multi, query.hip): q as above with q.out = k CapHit records per ray (NULL when k = 0); counts = n
+// hit counts or NULL (then the k-th hit prunes); resume: slot k - 1 of each page is the cursor (CAP_MULTI_CONTINUE).  The kernels'
+// list capacity is multi_bucket(k) >= k.
+struct MultiArgs
+{
+    QueryArgs q;
+    uint32_t  k;
+    uint32_t* counts;
+    uint32_t  resume;
+};
+constexpr uint32_t kMultiMaxK = 16;
+uint32_t multi_bucket(uint32_t k);
+void     launch_query8_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m);
+void     launch_query_binary_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, bool deferred);
 
 // ---- shade ----
 struct ShadeArgs

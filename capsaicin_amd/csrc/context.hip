@@ -2099,73 +2099,154 @@ namespace
 {
 constexpr uint64_t kQueryRaysPerLaunch = 1ull << 24;  // rays per launch: 32-bit ray indices and chunk counters, a 64-MB hand-over list
 
-int trace_query(CapContext* c, const char* what, const CapRayDesc* rays, uint64_t n, void* out, size_t out_stride, uint32_t flags, bool any)
+// What every query launch shares: the tree view, the launch configuration, the wide view's hand-over bound and the launch tracer.
+struct QueryRun
 {
-    static_assert(sizeof(CapRayDesc) == 2 * sizeof(float4) && sizeof(CapHit) == sizeof(float4), "query records are the kernels' float4 records");
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (flags != 0) return fail(CAP_ERR_INVALID_ARG, "%s: flags is reserved and must be 0 (got 0x%x)", what, flags);
-    if (!c->bvh_ready) return fail(CAP_ERR_STATE, "%s: call cap_bvh_build first", what);
-    if (c->bvh_stale) return fail(CAP_ERR_STATE, "%s: vertices changed; call cap_bvh_refit or cap_bvh_build", what);
-    if (n == 0) return CAP_OK;
-    if (!rays || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    const uintptr_t r0 = (uintptr_t)rays, o0 = (uintptr_t)out;
-    if ((r0 | o0) & 15u) return fail(CAP_ERR_INVALID_ARG, "%s: rays and output must be 16-byte aligned", what);
-    if (n > (UINTPTR_MAX - r0) / sizeof(CapRayDesc) || n > (UINTPTR_MAX - o0) / out_stride)
-        return fail(CAP_ERR_INVALID_ARG, "%s: %llu rays exceed the address space", what, (unsigned long long)n);
-    const uintptr_t r1 = r0 + n * sizeof(CapRayDesc), o1 = o0 + n * out_stride;
-    if (r0 < o1 && o0 < r1) return fail(CAP_ERR_INVALID_ARG, "%s: the ray and output ranges overlap", what);
-    HIP_TRY(hipSetDevice(c->device));
-
-    BvhDev bvh = bvh_dev(c);  // (lane 0's spill area: a render's second lane has its own, and the stream orders us behind both)
-    bvh.wide8_ok = bvh.wide8_ok && query8_stack_matches();
-    const uint64_t per = std::min<uint64_t>(n, kQueryRaysPerLaunch);
-    if (c->query_work.n < 2 * kCounterStride || (bvh.wide8_ok && c->query_defer.n < per))
-    {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (a grown buffer replaces one an earlier query may still be using)
-        HIP_TRY(c->query_work.ensure(2 * kCounterStride));
-        if (bvh.wide8_ok) HIP_TRY(c->query_defer.ensure(per));
-    }
-    LaunchCfg cfg{c->stream, (uint32_t)c->cu_count * 4u, c->bvh_info.stack_entries, (uint32_t)c->cu_count};
-    cfg.sw = &c->sw;
-    // box-test error budget of the wide view (wide_builder.cpp, query.hip): M as the build computed it
-    double m = 0.0;
-    for (int k = 0; k < 3; ++k)
-        m = std::max({m, (double)c->bvh_info.bounds_hi[k] - (double)c->bvh_info.bounds_lo[k], std::fabs((double)c->bvh_info.bounds_lo[k]),
-                      std::fabs((double)c->bvh_info.bounds_hi[k])});
-    const float safe = (float)(kQuerySafeScale * m);
+    CapContext* c;
+    const char* what;
+    BvhDev      bvh;
+    LaunchCfg   cfg;
+    float       safe;
+    uint64_t    per;  // rays per launch
     // CAP_TRACE_LAUNCHES=1: name every launch on stderr and drain the stream after it (fault localisation only)
-    const bool trace_launches = c->sw.on(SW_TRACE_LAUNCHES);
-    auto       traced         = [&](const char* kernel, uint64_t first) -> int {
+    int traced(const char* kernel, uint64_t first) const
+    {
         HIP_TRY(hipGetLastError());
-        if (!trace_launches) return CAP_OK;
+        if (!c->sw.on(SW_TRACE_LAUNCHES)) return CAP_OK;
         fprintf(stderr, "[cap] %s %s rays %llu.. ... ", what, kernel, (unsigned long long)first);
         fflush(stderr);
         hipError_t e = hipStreamSynchronize(c->stream);
         fprintf(stderr, "%s\n", hipGetErrorString(e));
         fflush(stderr);
         return e == hipSuccess ? CAP_OK : CAP_ERR_HIP;
-    };
-    for (uint64_t done = 0; done < n; done += per)
+    }
+};
+
+int query_state(CapContext* c, const char* what)
+{
+    if (!c->bvh_ready) return fail(CAP_ERR_STATE, "%s: call cap_bvh_build first", what);
+    if (c->bvh_stale) return fail(CAP_ERR_STATE, "%s: vertices changed; call cap_bvh_refit or cap_bvh_build", what);
+    return CAP_OK;
+}
+
+// [a0, a0 + bytes) and [b0, b0 + bytes_b) share a byte (an empty range shares none)
+bool ranges_overlap(uintptr_t a0, uint64_t a_bytes, uintptr_t b0, uint64_t b_bytes) { return a0 < b0 + b_bytes && b0 < a0 + a_bytes; }
+
+int query_prepare(CapContext* c, const char* what, uint64_t n, QueryRun& run)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    run.c = c, run.what = what;
+    run.bvh          = bvh_dev(c);  // (lane 0's spill area: a render's second lane has its own, and the stream orders us behind both)
+    run.bvh.wide8_ok = run.bvh.wide8_ok && query8_stack_matches();
+    run.per          = std::min<uint64_t>(n, kQueryRaysPerLaunch);
+    if (c->query_work.n < 2 * kCounterStride || (run.bvh.wide8_ok && c->query_defer.n < run.per))
     {
-        QueryArgs q{};
-        q.rays  = reinterpret_cast<const float4*>(rays + done);
-        q.n     = (uint32_t)std::min<uint64_t>(per, n - done);
-        q.out   = static_cast<uint8_t*>(out) + done * out_stride;
-        q.work  = c->query_work.p;
-        q.defer = c->query_defer.p;
-        q.safe  = safe;
-        if (bvh.wide8_ok)
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (a grown buffer replaces one an earlier query may still be using)
+        HIP_TRY(c->query_work.ensure(2 * kCounterStride));
+        if (run.bvh.wide8_ok) HIP_TRY(c->query_defer.ensure(run.per));
+    }
+    run.cfg    = LaunchCfg{c->stream, (uint32_t)c->cu_count * 4u, c->bvh_info.stack_entries, (uint32_t)c->cu_count};
+    run.cfg.sw = &c->sw;
+    // box-test error budget of the wide view (wide_builder.cpp, query.hip): M as the build computed it
+    double m = 0.0;
+    for (int k = 0; k < 3; ++k)
+        m = std::max({m, (double)c->bvh_info.bounds_hi[k] - (double)c->bvh_info.bounds_lo[k], std::fabs((double)c->bvh_info.bounds_lo[k]),
+                      std::fabs((double)c->bvh_info.bounds_hi[k])});
+    run.safe = (float)(kQuerySafeScale * m);
+    return CAP_OK;
+}
+
+QueryArgs query_args(const QueryRun& run, const CapRayDesc* rays, uint64_t n, uint64_t done)
+{
+    QueryArgs q{};
+    q.rays  = reinterpret_cast<const float4*>(rays + done);
+    q.n     = (uint32_t)std::min<uint64_t>(run.per, n - done);
+    q.work  = run.c->query_work.p;
+    q.defer = run.c->query_defer.p;
+    q.safe  = run.safe;
+    return q;
+}
+
+int trace_query(CapContext* c, const char* what, const CapRayDesc* rays, uint64_t n, void* out, size_t out_stride, uint32_t flags, bool any)
+{
+    static_assert(sizeof(CapRayDesc) == 2 * sizeof(float4) && sizeof(CapHit) == sizeof(float4), "query records are the kernels' float4 records");
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (flags != 0) return fail(CAP_ERR_INVALID_ARG, "%s: flags is reserved and must be 0 (got 0x%x)", what, flags);
+    if (const int rc = query_state(c, what)) return rc;
+    if (n == 0) return CAP_OK;
+    if (!rays || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    const uintptr_t r0 = (uintptr_t)rays, o0 = (uintptr_t)out;
+    if ((r0 | o0) & 15u) return fail(CAP_ERR_INVALID_ARG, "%s: rays and output must be 16-byte aligned", what);
+    if (n > (UINTPTR_MAX - r0) / sizeof(CapRayDesc) || n > (UINTPTR_MAX - o0) / out_stride)
+        return fail(CAP_ERR_INVALID_ARG, "%s: %llu rays exceed the address space", what, (unsigned long long)n);
+    if (ranges_overlap(r0, n * sizeof(CapRayDesc), o0, n * out_stride)) return fail(CAP_ERR_INVALID_ARG, "%s: the ray and output ranges overlap", what);
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run)) return rc;
+    for (uint64_t done = 0; done < n; done += run.per)
+    {
+        QueryArgs q = query_args(run, rays, n, done);
+        q.out       = static_cast<uint8_t*>(out) + done * out_stride;
+        if (run.bvh.wide8_ok)
         {
             HIP_TRY(hipMemsetAsync(c->query_work.p, 0, sizeof(uint32_t) * 2 * kCounterStride, c->stream));
-            launch_query8(cfg, bvh, q, any);
-            if (traced(any ? "k_query_any8" : "k_query_closest8", done) != CAP_OK) return CAP_ERR_HIP;
-            launch_query_binary(cfg, bvh, q, any, true);
-            if (traced(any ? "k_query_binary<any> (handed-over rays)" : "k_query_binary<closest> (handed-over rays)", done) != CAP_OK) return CAP_ERR_HIP;
+            launch_query8(run.cfg, run.bvh, q, any);
+            if (run.traced(any ? "k_query_any8" : "k_query_closest8", done) != CAP_OK) return CAP_ERR_HIP;
+            launch_query_binary(run.cfg, run.bvh, q, any, true);
+            if (run.traced(any ? "k_query_binary<any> (handed-over rays)" : "k_query_binary<closest> (handed-over rays)", done) != CAP_OK) return CAP_ERR_HIP;
         }
         else
         {
-            launch_query_binary(cfg, bvh, q, any, false);
-            if (traced(any ? "k_query_binary<any>" : "k_query_binary<closest>", done) != CAP_OK) return CAP_ERR_HIP;
+            launch_query_binary(run.cfg, run.bvh, q, any, false);
+            if (run.traced(any ? "k_query_binary<any>" : "k_query_binary<closest>", done) != CAP_OK) return CAP_ERR_HIP;
+        }
+    }
+    return CAP_OK;
+}
+
+// cap_trace_rays_multi: the first k hits of each ray in (t, triangle) order, and / or its hit count (query.hip k_query_multi8,
+// k_query_binary_multi).  Validation and launches as trace_query, with k records per ray: their offsets are 64-bit.
+int trace_multi(CapContext* c, const CapRayDesc* rays, uint64_t n, uint32_t k, CapHit* hits, uint32_t* counts, uint32_t flags)
+{
+    static_assert(CAP_MULTI_MAX_K == kMultiMaxK, "the header's page limit is the kernels' largest bucket");
+    const char* what = "cap_trace_rays_multi";
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (flags & ~(uint32_t)CAP_MULTI_CONTINUE) return fail(CAP_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (k > CAP_MULTI_MAX_K) return fail(CAP_ERR_INVALID_ARG, "%s: k = %u exceeds CAP_MULTI_MAX_K (%d); page with CAP_MULTI_CONTINUE", what, k, CAP_MULTI_MAX_K);
+    if (k == 0 && (hits || !counts)) return fail(CAP_ERR_INVALID_ARG, "%s: k = 0 counts only: hits must be NULL and counts given", what);
+    if (k == 0 && (flags & CAP_MULTI_CONTINUE)) return fail(CAP_ERR_INVALID_ARG, "%s: CAP_MULTI_CONTINUE needs k >= 1 (the cursor is slot k - 1)", what);
+    if (const int rc = query_state(c, what)) return rc;
+    if (n == 0) return CAP_OK;
+    if (!rays || (k && !hits)) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    const uintptr_t r0 = (uintptr_t)rays, h0 = (uintptr_t)hits, c0 = (uintptr_t)counts;
+    if (((r0 | h0) & 15u) || (c0 & 3u)) return fail(CAP_ERR_INVALID_ARG, "%s: rays and hits must be 16-byte aligned, counts 4-byte", what);
+    const uint64_t page = (uint64_t)k * sizeof(CapHit);
+    if (n > (UINTPTR_MAX - r0) / sizeof(CapRayDesc) || (k && n > (UINTPTR_MAX - h0) / page) || (counts && n > (UINTPTR_MAX - c0) / sizeof(uint32_t)))
+        return fail(CAP_ERR_INVALID_ARG, "%s: %llu rays x %u records exceed the address space", what, (unsigned long long)n, k);
+    const uint64_t r_bytes = n * sizeof(CapRayDesc), h_bytes = hits ? n * page : 0, c_bytes = counts ? n * sizeof(uint32_t) : 0;
+    if (ranges_overlap(r0, r_bytes, h0, h_bytes) || ranges_overlap(r0, r_bytes, c0, c_bytes) || ranges_overlap(h0, h_bytes, c0, c_bytes))
+        return fail(CAP_ERR_INVALID_ARG, "%s: the ray, hit and count ranges overlap", what);
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run)) return rc;
+    for (uint64_t done = 0; done < n; done += run.per)
+    {
+        MultiArgs m{};
+        m.q      = query_args(run, rays, n, done);
+        m.q.out  = hits ? static_cast<void*>(hits + done * k) : nullptr;
+        m.k      = k;
+        m.counts = counts ? counts + done : nullptr;
+        m.resume = (flags & CAP_MULTI_CONTINUE) ? 1u : 0u;
+        if (run.bvh.wide8_ok)
+        {
+            HIP_TRY(hipMemsetAsync(c->query_work.p, 0, sizeof(uint32_t) * 2 * kCounterStride, c->stream));
+            launch_query8_multi(run.cfg, run.bvh, m);
+            if (run.traced("k_query_multi8", done) != CAP_OK) return CAP_ERR_HIP;
+            launch_query_binary_multi(run.cfg, run.bvh, m, true);
+            if (run.traced("k_query_binary_multi (handed-over rays)", done) != CAP_OK) return CAP_ERR_HIP;
+        }
+        else
+        {
+            launch_query_binary_multi(run.cfg, run.bvh, m, false);
+            if (run.traced("k_query_binary_multi", done) != CAP_OK) return CAP_ERR_HIP;
         }
     }
     return CAP_OK;
@@ -2180,6 +2261,12 @@ int cap_trace_rays(CapContext* c, const CapRayDesc* device_rays, uint64_t n, Cap
 int cap_trace_occlusion(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded, uint32_t flags)
 {
     return trace_query(c, "cap_trace_occlusion", device_rays, n, device_occluded, sizeof(uint32_t), flags, true);
+}
+
+int cap_trace_rays_multi(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits, uint32_t* device_counts,
+                         uint32_t flags)
+{
+    return trace_multi(c, device_rays, n, k, device_hits, device_counts, flags);
 }
 
 void cap_post_settings_default(CapPostSettings* out)

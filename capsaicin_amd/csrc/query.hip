@@ -287,4 +287,355 @@ void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, 
     else
         hipLaunchKernelGGL(k_query_closest8, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill);
 }
+
+// ---- multi-hit queries (cap_trace_rays_multi) ----
+// A ray's first k hits in (t, triangle) order, its hit count, or both.  Each lane keeps a sorted list of K (t, gid) pairs in VGPRs, K a
+// compile-time bucket >= k; every index into it is a compile-time constant, so it never goes to scratch.  The first K - k slots hold
+// (-inf, 0) placeholders, the last k start as the miss (tmax, ~0).  A hit below slot K - 1 replaces it and bubbles towards the front by
+// K - 1 compare-swaps; no hit (t > tmin >= -inf) ever passes a placeholder.  Slot K - 1 is the pruning bound: tmax until the list
+// holds k hits, then the k-th.  Both box tests keep a child whose interval touches [lower bound, bound] (wide_node_test's differences
+// are negative only for a strict miss, slab is inclusive), so a box entered exactly at the k-th t is still opened and an equal-t
+// triangle with a lower id still displaces the k-th entry: the list is exact whatever the visiting order.
+// Paging (CAP_MULTI_CONTINUE): a hit is counted only above the cursor (t_c, g_c) read from slot k - 1 of the page, (-inf, 0) otherwise.
+// Hits below the cursor's t lie outside every page after it, so the box tests may take max(tmin, t_c) as their lower bound: still
+// inclusive, a triangle at t_c with a higher id is kept.
+template <int K>
+struct HitList
+{
+    float    t[K];
+    uint32_t g[K];
+    __device__ __forceinline__ void init(uint32_t k, float tmax)
+    {
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+        {
+            const bool live = j >= K - (int)k;
+            t[j] = live ? tmax : -__builtin_inff(), g[j] = live ? kInvalidId : 0u;
+        }
+    }
+    __device__ __forceinline__ bool admits(float tt, uint32_t gg) const { return tt < t[K - 1] || (tt == t[K - 1] && gg < g[K - 1]); }
+    __device__ __forceinline__ void insert(float tt, uint32_t gg)
+    {
+        t[K - 1] = tt, g[K - 1] = gg;
+#pragma unroll
+        for (int j = K - 1; j > 0; --j)
+        {
+            const bool     sw = t[j] < t[j - 1] || (t[j] == t[j - 1] && g[j] < g[j - 1]);
+            const float    ta = t[j - 1], tb = t[j];
+            const uint32_t ga = g[j - 1], gb = g[j];
+            t[j - 1] = sw ? tb : ta, t[j] = sw ? ta : tb;
+            g[j - 1] = sw ? gb : ga, g[j] = sw ? ga : gb;
+        }
+    }
+};
+
+// The hit (t, gid) of the contract's rule, against a ray's cursor and list.  COUNT: every hit above the cursor adds one.
+template <int K, bool COUNT>
+__device__ __forceinline__ void multi_offer(HitList<K>& L, uint32_t& count, float tc, uint32_t gc, float t, uint32_t gid)
+{
+    if (t > tc || (t == tc && gid > gc))
+    {
+        if (COUNT) ++count;
+        if (L.admits(t, gid)) L.insert(t, gid);
+    }
+}
+
+// The cursor of ray i: slot k - 1 of its page when paging, else (-inf, 0), below every hit.
+__device__ __forceinline__ void multi_cursor(const MultiArgs& m, uint32_t i, float& tc, uint32_t& gc)
+{
+    tc = -__builtin_inff(), gc = 0u;
+    if (m.resume)
+    {
+        const float4 e = static_cast<const float4*>(m.q.out)[(size_t)i * m.k + (m.k - 1u)];
+        tc = e.x, gc = f2u(e.w);
+    }
+}
+
+// A ray the traversal does not answer: k miss records (tmax, 0, 0, ~0) and count 0.
+__device__ __forceinline__ void multi_write_miss(const MultiArgs& m, uint32_t i, float tmax)
+{
+    if (m.counts) m.counts[i] = 0u;
+    float4* const page = static_cast<float4*>(m.q.out) + (size_t)i * m.k;
+    for (uint32_t j = 0; j < m.k; ++j) page[j] = make_float4(tmax, 0.f, 0.f, u2f(kInvalidId));
+}
+
+// Writes ray i's page and count.  (u, v) are not kept in the list (2K registers instead of 4K): the winner's record is tested again
+// from bvh.tris_by_id, the records in global id order.  tris8 (and the binary tree's tris) are byte copies of those records
+// (tri_raw -> tris_sorted -> k_gather_wide, and again after cap_bvh_refit), and tri_test on the same ray and record gives the same
+// bits, so the t found here is the listed one and (u, v) are those of the traversal.
+template <int K, bool COUNT>
+__device__ __forceinline__ void multi_write(const MultiArgs& m, const BvhDev& bvh, uint32_t i, const Ray& r, const HitList<K>& L, uint32_t count)
+{
+    if (COUNT) m.counts[i] = count;
+    float4* const page = static_cast<float4*>(m.q.out) + (size_t)i * m.k;
+    const int     skip = K - (int)m.k;  // the placeholders
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (j >= skip)
+        {
+            float u = 0.f, v = 0.f;
+            if (L.g[j] != kInvalidId)
+            {
+                const float4* rec = bvh.tris_by_id + 4 * (size_t)L.g[j];
+                float         t;
+                tri_test(r, rec[0], rec[1], rec[2], t, u, v);
+            }
+            page[j - skip] = make_float4(L.t[j], u, v, u2f(L.g[j]));
+        }
+}
+
+// Workgroups per CU each K is register-allocated for (waves per SIMD; VGPRs 512 / waves): k_query_closest8 runs six (80 VGPRs, with a
+// spill); with the list, the cursor and the count the most that leave every instantiation without scratch (tools/kernel_regs.sh) are
+// 5 (96) at K = 1, 4 (128) at K = 4, 3 (168) at K = 8 and 2 (256) at K = 16.
+constexpr int multi8_blocks(int K) { return K <= 1 ? 5 : K <= 4 ? 4 : K <= 8 ? 3 : 2; }
+
+// Multi-hit on the wide tree: k_query_closest8's feed, refill, pair stack and hand-over of far origins, with the list instead of the
+// single best record.
+template <int K, bool COUNT>
+__global__ __launch_bounds__(kBlock, multi8_blocks(K)) void k_query_multi8(BvhDev bvh, MultiArgs m, uint32_t refill_idle)
+{
+    __shared__ uint2  lds_stack[kQueryLds * kBlock];
+    __shared__ float4 lds_rays[2 * kBlock];
+    const QueryArgs& q    = m.q;
+    const uint32_t   lane = threadIdx.x & 63u;
+    float4* const    rbuf = lds_rays + (threadIdx.x >> 6) * 128u;
+    QueryFeedState   s{grab_issue(q.work, 0), 0, 0, 0, 0, 0, make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+    query_fetch(s, q, lane);
+
+    WideStack<kQueryLds> st{lds_stack + threadIdx.x, wide_spill_of_thread(bvh), 0};
+    bool              alive = false;
+    Ray               r     = make_ray(mk3(0, 0, 0), mk3(0, 0, 1), 0.f, 0.f);
+    WideRay           w     = make_wide_ray(r.o, r.d);
+    WideCursor        c;
+    wide_cursor_root(c);
+    HitList<K> L;
+    L.init(m.k, 0.f);
+    float    tc = 0.f, lo = 0.f;
+    uint32_t gc = 0u, count = 0u, out = 0;
+    while (true)
+    {
+        unsigned long long m_alive = __ballot(alive);
+        if (64u - (uint32_t)__popcll(m_alive) >= refill_idle)
+            query_refill(s, q, rbuf, lane, alive, m_alive, [&](float4 a, float4 b, uint32_t i) {
+                if (!query_ray_ok(a, b))
+                {
+                    multi_write_miss(m, i, b.w);
+                    return false;
+                }
+                if (!query_origin_safe(a, q.safe))
+                {
+                    q.defer[atomicAdd(q.work + kCounterStride, 1u)] = i;
+                    return false;
+                }
+                r = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
+                w = make_wide_ray(r.o, r.d);
+                L.init(m.k, r.tmax);
+                multi_cursor(m, i, tc, gc);
+                lo    = fmaxf(r.tmin, tc);
+                count = 0u;
+                out   = i;
+                wide_cursor_root(c);
+                st.sp = 0;
+                return true;
+            });
+        if (m_alive == 0ull)
+        {
+            if (s.buf_pos >= s.buf_n && s.pend_n == 0) break;
+            continue;
+        }
+        const bool    tri_lane = alive && c.t_hits != 0u, node_lane = alive && c.t_hits == 0u;
+        const float4* src      = bvh.nodes8;
+        if (tri_lane)
+            src = bvh.tris8 + 4 * (size_t)wide_pick_triangle(c);
+        else if (node_lane)
+        {
+            bool           rest;
+            const uint32_t node = wide_pick_child(c, w.octinv, rest);
+            if (rest) st.push(c.g_base, c.g_mask);
+            src = bvh.nodes8 + (kWideNodeStride / 4u) * (size_t)node;
+        }
+        WideNode nd;
+#define CAP_DEF4(v) asm volatile("" : "=v"((v).x), "=v"((v).y), "=v"((v).z), "=v"((v).w))  // (see k_trace_closest8)
+        CAP_DEF4(nd.h0);
+        CAP_DEF4(nd.h1);
+        CAP_DEF4(nd.q2);
+        CAP_DEF4(nd.q3);
+        CAP_DEF4(nd.q4);
+#undef CAP_DEF4
+        if (alive) nd.h0 = src[0], nd.h1 = src[1], nd.q2 = src[2], nd.q3 = src[3];
+        if (node_lane) nd.q4 = src[4];
+        if (tri_lane)
+        {
+            float t, u, v;
+            if (tri_test(r, nd.h0, nd.h1, nd.q2, t, u, v)) multi_offer<K, COUNT>(L, count, tc, gc, t, f2u(nd.q3.x));
+        }
+        if (node_lane) wide_node_test(nd, w, lo, COUNT ? r.tmax : L.t[K - 1], c);
+        if (alive && c.t_hits == 0u && (c.g_mask >> 24) == 0u)
+        {
+            if (st.sp == 0)
+            {
+                multi_write<K, COUNT>(m, bvh, out, r, L, count);
+                alive = false;
+            }
+            else
+                st.pop(c);
+        }
+    }
+}
+
+// Multi-hit on the binary tree, one lane per ray: traverse_closest's loop (kernels.hip) with the list; every ray where the wide view
+// is not used, and the rays k_query_multi8 handed over.  Workgroups per CU as the binary query kernels (stack_residency: 4 with
+// 32-entry stacks, 2 with 64), except K = 16 on 32 entries: 3, for the registers.
+constexpr int multi_binary_blocks(int STACK, int K) { return STACK <= 32 ? (K <= 8 ? 4 : 3) : 2; }
+
+template <int STACK, int K, bool COUNT>
+__global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, K)) void k_query_binary_multi(BvhDev bvh, MultiArgs m, uint32_t deferred)
+{
+    __shared__ uint32_t lds_stack[STACK * kBlock];
+    uint32_t* const     stack = lds_stack + threadIdx.x;
+    const QueryArgs&    q     = m.q;
+    const uint32_t      n     = deferred ? q.work[kCounterStride] : q.n;
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock)
+    {
+        const uint32_t i = deferred ? q.defer[j] : j;
+        const float4   a = q.rays[2 * (size_t)i], b = q.rays[2 * (size_t)i + 1];
+        if (!query_ray_ok(a, b))
+        {
+            multi_write_miss(m, i, b.w);
+            continue;
+        }
+        const Ray  r = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
+        HitList<K> L;
+        L.init(m.k, r.tmax);
+        float    tc;
+        uint32_t gc, count = 0u;
+        multi_cursor(m, i, tc, gc);
+        Ray rb  = r;  // the box tests' interval: lower bound max(tmin, t_c)
+        rb.tmin = fmaxf(r.tmin, tc);
+        int node = bvh.root, sp = 0;
+        while (bvh.tri_count != 0u)
+        {
+            const float tfar = COUNT ? r.tmax : L.t[K - 1];
+            if (node >= 0)
+            {
+                const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2],
+                             q3 = bvh.nodes[4 * node + 3];
+                float      tn0, tn1;
+                const bool h0 = slab(rb, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, tfar, tn0);
+                const bool h1 = slab(rb, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, tfar, tn1);
+                const int  c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+                if (h0 && h1)
+                {
+                    const bool swap = tn1 < tn0;
+                    if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)(swap ? c0 : c1);
+                    node = swap ? c1 : c0;
+                    continue;
+                }
+                if (h0 || h1)
+                {
+                    node = h0 ? c0 : c1;
+                    continue;
+                }
+            }
+            else
+            {
+                const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                for (uint32_t leaf = first; leaf <= last; ++leaf)
+                {
+                    const float4 t0 = bvh.tris[4 * leaf + 0], t1 = bvh.tris[4 * leaf + 1], t2 = bvh.tris[4 * leaf + 2];
+                    float        t, u, v;
+                    if (tri_test(r, t0, t1, t2, t, u, v)) multi_offer<K, COUNT>(L, count, tc, gc, t, f2u(bvh.tris[4 * leaf + 3].x));
+                }
+            }
+            if (sp == 0) break;
+            node = (int)stack[(--sp) * kBlock];
+        }
+        multi_write<K, COUNT>(m, bvh, i, r, L, count);
+    }
+}
+
+uint32_t multi_bucket(uint32_t k) { return k <= 1 ? 1u : k <= 4 ? 4u : k <= 8 ? 8u : 16u; }
+
+template <auto KERNEL>
+static uint32_t multi_resident(const LaunchCfg& cfg, uint32_t want)  // (resident_grid of kernels.hip)
+{
+    static int per_cu = -1;
+    if (per_cu < 0)
+    {
+        int n  = 0;
+        per_cu = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, KERNEL, (int)kBlock, 0) == hipSuccess && n > 0) ? n : 0;
+    }
+    if (!cfg.cu_count || !per_cu) return want;
+    const uint32_t cap = cfg.cu_count * (uint32_t)per_cu;
+    return want < cap ? want : cap;
+}
+
+template <int K, bool COUNT>
+static void launch_multi8_k(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, uint32_t refill)
+{
+    uint32_t g   = (m.q.n + kBlock - 1) / kBlock;
+    uint32_t cap = cfg.cu_count ? cfg.cu_count * (uint32_t)multi8_blocks(K) : cfg.grid_blocks;
+    if ((uint64_t)cap * kBlock > bvh.spill_threads) cap = bvh.spill_threads / kBlock;  // every thread owns a spill slice
+    if (g > cap) g = cap;
+    if (g == 0) g = 1;
+    hipLaunchKernelGGL((k_query_multi8<K, COUNT>), dim3(g), dim3(kBlock), 0, cfg.stream, bvh, m, refill);
+}
+
+void launch_query8_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m)
+{
+    const long     v      = (long)cfg.sw_get(SW_W8_REFILL, CAP_W8_REFILL);
+    const uint32_t refill = (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v);
+#define CAP_MULTI8(K)                                                         \
+    if (m.counts)                                                             \
+        launch_multi8_k<K, true>(cfg, bvh, m, refill);                        \
+    else                                                                      \
+        launch_multi8_k<K, false>(cfg, bvh, m, refill);
+    switch (multi_bucket(m.k))
+    {
+    case 1: CAP_MULTI8(1) break;
+    case 4: CAP_MULTI8(4) break;
+    case 8: CAP_MULTI8(8) break;
+    default: CAP_MULTI8(16) break;
+    }
+#undef CAP_MULTI8
+}
+
+template <int STACK, int K, bool COUNT>
+static void launch_binary_multi_k(const LaunchCfg& cfg, const BvhDev& b, const MultiArgs& m, bool deferred)
+{
+    uint32_t want = (m.q.n + kBlock - 1) / kBlock;
+    // (deferred: the count is on the device and is normally small -- one workgroup per CU at most)
+    if (deferred && cfg.cu_count && want > cfg.cu_count) want = cfg.cu_count;
+    if (want == 0) want = 1;
+    hipLaunchKernelGGL((k_query_binary_multi<STACK, K, COUNT>), dim3(multi_resident<k_query_binary_multi<STACK, K, COUNT>>(cfg, want)),
+                       dim3(kBlock), 0, cfg.stream, b, m, deferred ? 1u : 0u);
+}
+
+template <int STACK>
+static void launch_binary_multi_s(const LaunchCfg& cfg, const BvhDev& b, const MultiArgs& m, bool deferred)
+{
+#define CAP_MULTI_BIN(K)                                                      \
+    if (m.counts)                                                             \
+        launch_binary_multi_k<STACK, K, true>(cfg, b, m, deferred);           \
+    else                                                                      \
+        launch_binary_multi_k<STACK, K, false>(cfg, b, m, deferred);
+    switch (multi_bucket(m.k))
+    {
+    case 1: CAP_MULTI_BIN(1) break;
+    case 4: CAP_MULTI_BIN(4) break;
+    case 8: CAP_MULTI_BIN(8) break;
+    default: CAP_MULTI_BIN(16) break;
+    }
+#undef CAP_MULTI_BIN
+}
+
+void launch_query_binary_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, bool deferred)
+{
+    BvhDev b   = bvh;
+    b.wide8_ok = 0;
+    if (cfg.stack_entries <= 32)
+        launch_binary_multi_s<32>(cfg, b, m, deferred);
+    else
+        launch_binary_multi_s<64>(cfg, b, m, deferred);
+}
 }  // namespace cap

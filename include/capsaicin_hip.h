@@ -365,6 +365,39 @@ int cap_trace_rays(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, C
 /* 1 if some triangle satisfies the occlusion rule, else 0; one uint32 per ray */
 int cap_trace_occlusion(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded, uint32_t flags);
 
+/* ---- multi-hit ray queries: the first k hits of each ray (LiDAR returns, thickness, depth complexity; DXR / OptiX any-hit loops) ----
+ * A ray's hits are every triangle the closest-hit rule above accepts (tmin < t < tmax, two-sided), sorted by (t, triangle)
+ * ascending: equal t goes to the lower id, the order cap_trace_rays' tie rule uses.  device_hits[i * k + j], j < k, is ray i's j-th
+ * hit as a CapHit (t, u, v, triangle); slots after its last hit hold the miss record (tmax, 0, 0, 0xFFFFFFFF).  A triangle appears at
+ * most once per ray.  With k = 1 every record is exactly what cap_trace_rays returns.  Records are bit-identical to the oracle's
+ * brute force, whichever builder and tree made them.
+ *
+ * device_counts: NULL, or n uint32: the number of ALL hits of ray i, not capped at k (with CAP_MULTI_CONTINUE: of the hits after
+ * the cursor).  Counts follow the contract: a ray through an edge or vertex shared by several triangles counts each of them.
+ * Asking for counts turns off pruning by the k-th hit, so it costs a full traversal of the interval.  k = 0 counts only:
+ * device_hits must be NULL and device_counts given.
+ *
+ * Paging (CAP_MULTI_CONTINUE): on entry, slot k - 1 of each ray's page is read as a cursor (t_c, g_c); only hits with
+ * (t, triangle) > (t_c, g_c) in lexicographic order count, and the next page is written over the old one.  A page that was not
+ * full ends in a miss record, whose cursor (tmax, 0xFFFFFFFF) admits nothing: that ray's next page is empty.  Calling again with
+ * the same rays and buffer walks every hit exactly once, equal-t hits on either side of a page boundary included.  The cursor
+ * slot must hold what the previous call wrote there.
+ *
+ * Everything else is as for cap_trace_rays: degenerate rays give miss pages and count 0 (with CAP_MULTI_CONTINUE too); device
+ * pointers on the context's GPU, asynchronous on the context stream and ordered behind a render's second lane; nothing of the
+ * render's state is used; n may exceed 2^32.  Errors: CAP_ERR_STATE before cap_bvh_build and while the trees are stale after
+ * cap_scene_update_vertices; CAP_ERR_INVALID_ARG for k > CAP_MULTI_MAX_K, k = 0 with hits given or counts NULL,
+ * CAP_MULTI_CONTINUE with k = 0, unknown flags, NULL rays (or hits with k > 0), rays or hits not 16-byte or counts not 4-byte
+ * aligned, any overlap between the ray, hit and count ranges, and n * k records beyond the address space.  Nothing is written on
+ * an error; n = 0 does nothing. */
+#define CAP_MULTI_MAX_K 16
+enum
+{
+    CAP_MULTI_CONTINUE = 1u << 0 /* read slot k - 1 of each page as the cursor and write the next page over it */
+};
+int cap_trace_rays_multi(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits, uint32_t* device_counts,
+                         uint32_t flags);
+
 /* ---- multi-GPU tile exchange (one gather of tile radiance at frame end) ---- */
 /* floats in this context's tile-ordered radiance buffer: max_tiles_per_shard * 64 * 4 (same on every shard) */
 int cap_tile_buffer_floats(CapContext* ctx, size_t* out_floats);

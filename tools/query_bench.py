@@ -8,9 +8,12 @@ Ray sets, each of width x height rays:
   b  cosine-hemisphere rays leaving the primary hit points of (a) around the triangles' geometric normals (tmin 1e-4 x scene size,
      tmax inf): the render's bounce-1 workload;
   c  uniformly random rays: origin uniform in the scene box, direction uniform on the sphere, tmax inf.
-Per scene, set and kind (closest / occlusion) one JSON line: host clock around cap_sync over `reps` back-to-back calls after `warmup`
+Kinds: closest (cap_trace_rays), occlusion (cap_trace_occlusion), multi1 / multi4 / multi16 (cap_trace_rays_multi, k = 1 / 4 / 16, no
+counts), count (cap_trace_rays_multi, k = 0: hit counts only).
+Per scene, set and kind one JSON line: host clock around cap_sync over `reps` back-to-back calls after `warmup`
 calls (the renderer on its own stream, rays and output resident on the device).  Kernel times come from a separate run of this tool
-under `rocprofv3 --kernel-trace --stats` (k_query_closest8 / k_query_any8; k_query_binary for rays handed to the binary tree).
+under `rocprofv3 --kernel-trace --stats` (k_query_closest8 / k_query_any8 / k_query_multi8; k_query_binary / k_query_binary_multi
+for rays handed to the binary tree).
 The hall is tools/make_sponza_class.py at scale 1.0 (262 k triangles), written to a temporary directory."""
 import argparse
 import json
@@ -138,8 +141,18 @@ def main():
                 occ = torch.empty((n,), dtype=torch.int32, device=dev)
                 torch.cuda.synchronize()
                 for kind in a.kinds.split(","):
-                    call = (lambda: r.trace_rays(rays, out=hits, sync=False)) if kind == "closest" else \
-                        (lambda: r.trace_occlusion(rays, out=occ, sync=False))
+                    if kind == "closest":
+                        call = lambda: r.trace_rays(rays, out=hits, sync=False)
+                    elif kind == "occlusion":
+                        call = lambda: r.trace_occlusion(rays, out=occ, sync=False)
+                    elif kind == "count":  # (the C entry point: the binding would allocate the output per call)
+                        call = lambda: capi._check(capi.lib().cap_trace_rays_multi(r.ctx, rays.data_ptr(), n, 0, None, occ.data_ptr(), 0),
+                                                   "cap_trace_rays_multi")
+                    else:  # multiK
+                        k = int(kind[len("multi"):])
+                        page = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
+                        call = lambda: capi._check(capi.lib().cap_trace_rays_multi(r.ctx, rays.data_ptr(), n, k, page.data_ptr(), None, 0),
+                                                   "cap_trace_rays_multi")
                     for _ in range(a.warmup):
                         call()
                     r.sync()
@@ -148,10 +161,16 @@ def main():
                         call()
                     r.sync()
                     ms = (time.perf_counter() - t0) * 1e3 / a.reps
-                    frac = float((hits[:, 3].view(torch.int32) != -1).float().mean()) if kind == "closest" else float(occ.float().mean())
+                    if kind == "closest":
+                        extra = {"hit_fraction": round(float((hits[:, 3].view(torch.int32) != -1).float().mean()), 4)}
+                    elif kind == "occlusion":
+                        extra = {"occluded_fraction": round(float(occ.float().mean()), 4)}
+                    elif kind == "count":
+                        extra = {"mean_hits": round(float(occ.double().mean()), 3)}
+                    else:
+                        extra = {"mean_filled": round(float((page[:, :, 3].view(torch.int32) != -1).double().sum(1).mean()), 3)}
                     print(json.dumps({"scene": sc, "triangles": int(info.triangle_count), "set": s, "kind": kind, "rays": n,
-                                      "ms_per_call": round(ms, 4), "mrays_per_s": round(n / ms / 1e3, 1),
-                                      "hit_fraction" if kind == "closest" else "occluded_fraction": round(frac, 4)}), flush=True)
+                                      "ms_per_call": round(ms, 4), "mrays_per_s": round(n / ms / 1e3, 1), **extra}), flush=True)
             r.close()
 
 
