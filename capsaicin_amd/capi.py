@@ -153,6 +153,10 @@ class GeometryView(C.Structure):
                 ("material_count", C.c_uint32)]
 
 
+class TraceOptions(C.Structure):  # CapTraceOptions
+    _fields_ = [("ray_flags", C.c_uint32), ("instance_mask", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 # every symbol include/capsaicin_hip.h and include/capsaicin_scene.h declare: (restype, argtypes)
 _vp, _u32, _u64, _i = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 SYMBOLS = {
@@ -192,6 +196,10 @@ SYMBOLS = {
     "cap_trace_rays": (_i, [_vp, _vp, _u64, _vp, _u32]),
     "cap_trace_occlusion": (_i, [_vp, _vp, _u64, _vp, _u32]),
     "cap_trace_rays_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32]),
+    "cap_scene_set_instance_masks": (_i, [_vp, _vp, _u32]),
+    "cap_trace_rays_ex": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
+    "cap_trace_occlusion_ex": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
+    "cap_trace_rays_multi_ex": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
     "cap_post_settings_default": (None, [C.POINTER(PostSettings)]),
     "cap_post_frame": (_i, [_vp, C.POINTER(PostSettings), _u32, C.POINTER(CameraData)]),
@@ -583,20 +591,46 @@ class Renderer:
     def stats_reset(self):
         _check(lib().cap_stats_reset(self.ctx), "cap_stats_reset")
 
+    # ---- ray flags and instance masks (CapTraceOptions: DXR RayFlags / InstanceInclusionMask) ----
+    RAY_FLAG_ACCEPT_FIRST_HIT, RAY_FLAG_CULL_BACK_FACING, RAY_FLAG_CULL_FRONT_FACING = 0x04, 0x10, 0x20  # CAP_RAY_FLAG_*
+
+    def set_instance_masks(self, masks):
+        """One mask byte per mesh of the uploaded scene (cap_scene_set_instance_masks); None restores all 0xFF.  A triangle of mesh m
+        is a candidate of a query iff masks[m] & mask != 0 (mask= of the trace_* calls, default 0xFF)."""
+        if masks is None:
+            _check(lib().cap_scene_set_instance_masks(self.ctx, None, len(self._tri_end)), "cap_scene_set_instance_masks")
+            return
+        m = np.ascontiguousarray(masks, np.uint8).reshape(-1)
+        _check(lib().cap_scene_set_instance_masks(self.ctx, _p(m), m.size), "cap_scene_set_instance_masks")
+
+    def trace_options(self, cull=None, mask=None, first_hit=False):
+        """The CapTraceOptions of cull=None | "back" | "front", mask=None | 1..0xFF, first_hit; None when every argument is the
+        default (the trace_* calls then take the plain entry points)."""
+        if cull not in (None, "back", "front"):
+            raise CapError('cull must be None, "back" or "front", got %r' % (cull,))
+        if cull is None and mask is None and not first_hit:
+            return None
+        flags = {None: 0, "back": self.RAY_FLAG_CULL_BACK_FACING, "front": self.RAY_FLAG_CULL_FRONT_FACING}[cull]
+        if first_hit:
+            flags |= self.RAY_FLAG_ACCEPT_FIRST_HIT
+        return TraceOptions(flags, 0 if mask is None else int(mask))
+
     # ---- ray queries (cap_trace_rays / cap_trace_occlusion) ----
-    def trace_rays(self, rays, out=None, sync=True):
+    def trace_rays(self, rays, out=None, sync=True, cull=None, mask=None, first_hit=False):
         """Closest hit of each ray.  rays: (N, 8) float32 = CapRayDesc rows (origin, tmin, direction, tmax), a contiguous torch tensor
         on this context's device or a numpy array (staged through torch; the hits come back as numpy).  Returns (N, 4) float32 hit
         records (t, u, v, triangle id bits: hit_triangles() reads them).  sync=True orders the call against torch's current stream
         (waits for it before the launch) and waits for the context's stream before returning: right for a renderer on a stream of its
-        own.  sync=False only enqueues, on the context's stream: for a renderer created on torch's stream (as bench.py creates it)."""
-        return self._query(rays, out, sync, False)
+        own.  sync=False only enqueues, on the context's stream: for a renderer created on torch's stream (as bench.py creates it).
+        cull="back" | "front" drops the triangles facing away from / towards the ray, mask= is the instance inclusion mask
+        (set_instance_masks), first_hit=True returns some hit instead of the closest (cap_trace_rays_ex)."""
+        return self._query(rays, out, sync, False, self.trace_options(cull, mask, first_hit))
 
-    def trace_occlusion(self, rays, out=None, sync=True):
+    def trace_occlusion(self, rays, out=None, sync=True, cull=None, mask=None):
         """1 where some triangle occludes the ray's open interval (tmin, tmax), else 0: (N,) int32.  Arguments as trace_rays."""
-        return self._query(rays, out, sync, True)
+        return self._query(rays, out, sync, True, self.trace_options(cull, mask))
 
-    def _query(self, rays, out, sync, any_hit):
+    def _query(self, rays, out, sync, any_hit, options=None):
         import torch
         dev = torch.device("cuda", self.device)
         host = isinstance(rays, np.ndarray)
@@ -616,9 +650,14 @@ class Renderer:
             raise CapError("out must be a contiguous %s %s tensor on %s" % (tuple(shape), dtype, dev))
         if sync:
             torch.cuda.current_stream(dev).synchronize()  # the rays (and out's allocation) were made on torch's stream
-        fn = lib().cap_trace_occlusion if any_hit else lib().cap_trace_rays
-        _check(fn(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), 0),
-               "cap_trace_occlusion" if any_hit else "cap_trace_rays")
+        if options is not None:
+            fn = lib().cap_trace_occlusion_ex if any_hit else lib().cap_trace_rays_ex
+            _check(fn(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), C.byref(options)),
+                   "cap_trace_occlusion_ex" if any_hit else "cap_trace_rays_ex")
+        else:
+            fn = lib().cap_trace_occlusion if any_hit else lib().cap_trace_rays
+            _check(fn(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), 0),
+                   "cap_trace_occlusion" if any_hit else "cap_trace_rays")
         if sync:
             self.sync()
         if host or host_out is not None:
@@ -631,13 +670,15 @@ class Renderer:
 
     MULTI_MAX_K, MULTI_CONTINUE = 16, 1  # CAP_MULTI_MAX_K, CAP_MULTI_CONTINUE
 
-    def trace_rays_multi(self, rays, k, counts=False, resume=None, sync=True):
+    def trace_rays_multi(self, rays, k, counts=False, resume=None, sync=True, cull=None, mask=None):
         """The first k hits of each ray in (t, triangle) order (cap_trace_rays_multi): (N, k, 4) float32 records as trace_rays writes
         them, miss records (tmax, 0, 0, MISS) after a ray's last hit.  counts=True also returns the number of ALL hits per ray, (N,)
         int32 (k = 0: counts only, hits is (N, 0, 4)).  resume=<previous page> (the (N, k, 4) result of a call with the same rays)
         continues after it with CAP_MULTI_CONTINUE, writes the next page over it and returns it.  rays and sync as trace_rays; numpy
-        rays (or a numpy resume page) give numpy results."""
+        rays (or a numpy resume page) give numpy results.  cull= and mask= as trace_rays: hits, counts and pages are those of the
+        filtered hit set (cap_trace_rays_multi_ex)."""
         import torch
+        options = self.trace_options(cull, mask)
         dev = torch.device("cuda", self.device)
         host = isinstance(rays, np.ndarray) or isinstance(resume, np.ndarray)
         if isinstance(rays, np.ndarray):
@@ -664,9 +705,12 @@ class Renderer:
         cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
         if sync:
             torch.cuda.current_stream(dev).synchronize()  # the rays (and the outputs' allocations) were made on torch's stream
-        _check(lib().cap_trace_rays_multi(self.ctx, C.c_void_p(rays.data_ptr()), n, k, C.c_void_p(hits.data_ptr()) if k else None,
-                                          C.c_void_p(cnt.data_ptr()) if counts else None,
-                                          self.MULTI_CONTINUE if resume is not None else 0), "cap_trace_rays_multi")
+        args = (self.ctx, C.c_void_p(rays.data_ptr()), n, k, C.c_void_p(hits.data_ptr()) if k else None,
+                C.c_void_p(cnt.data_ptr()) if counts else None, self.MULTI_CONTINUE if resume is not None else 0)
+        if options is not None:
+            _check(lib().cap_trace_rays_multi_ex(*args, C.byref(options)), "cap_trace_rays_multi_ex")
+        else:
+            _check(lib().cap_trace_rays_multi(*args), "cap_trace_rays_multi")
         if sync:
             self.sync()
         if host:

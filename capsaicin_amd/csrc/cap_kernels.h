@@ -104,7 +104,8 @@ struct QueryArgs
 };
 constexpr float kQuerySafeScale = 4.0f;  // safe = this x max(scene extent, largest |coordinate|): see query.hip
 bool query8_stack_matches();  // the wide query kernels' pair stack is the one the host checks the tree's depth against
-void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any);
+struct RayFilter;  // ray flags and instance masks (below); NULL = the plain kernels
+void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any, const RayFilter* f = nullptr, bool first_hit = false);
 // binary tree, per lane: every ray of q (deferred = false), or the q.work[kCounterStride] rays listed in q.defer
 void launch_query_binary(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any, bool deferred);
 // Multi-hit queries (cap_trace_rays_multi, query.hip): q as above with q.out = k CapHit records per ray (NULL when k = 0); counts = n
@@ -119,8 +120,20 @@ struct MultiArgs
 };
 constexpr uint32_t kMultiMaxK = 16;
 uint32_t multi_bucket(uint32_t k);
-void     launch_query8_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m);
-void     launch_query_binary_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, bool deferred);
+void     launch_query8_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, const RayFilter* f = nullptr);
+void     launch_query_binary_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, bool deferred, const RayFilter* f = nullptr);
+
+// Ray flags and instance masks of the _ex queries (query.hip k_query_*_f): the face cull as tri_test_cull's two words, and the instance
+// mask as one byte per GLOBAL triangle id (its mesh's mask; NULL while no table is
+// installed, cap_scene_set_instance_masks) tested against `mask`.  Wave-uniform: kernel arguments, SGPRs.
+struct RayFilter
+{
+    uint32_t       cull_and, cull_xor;
+    uint32_t       mask;      // InstanceInclusionMask, 1..0xFF
+    const uint8_t* tri_mask;  // NULL: no mask test
+};
+// launch_query_binary under a filter (query.hip k_query_binary_f; first_hit: closest only, the lane retires at its first accepted hit)
+void launch_query_binary_filtered(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const RayFilter& f, bool any, bool first_hit, bool deferred);
 
 // ---- shade ----
 struct ShadeArgs

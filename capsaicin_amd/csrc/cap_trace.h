@@ -76,6 +76,41 @@ __device__ __forceinline__ bool tri_occludes(const Ray& r, const float4 t0, cons
     return (det > 0.0f) & (U >= 0.0f) & (V >= 0.0f) & (U + V <= det) & (T > r.tmin * det) & (T < r.tmax * det);
 }
 
+// The same two tests under a face cull (cap_trace_*_ex, CAP_RAY_FLAG_CULL_*).  The cull is two wave-uniform words applied to the sign of
+// det BEFORE the two-sided flip: the triangle is rejected when ((bits(det) ^ cull_xor) & cull_and) != 0 -- cull_and = 0 culls nothing,
+// (0x80000000, 0) culls back faces (det < 0), (0x80000000, 0x80000000) front faces (det > 0).  One xor-and and one compare, no branch;
+// det == +-0 is no hit whatever its sign bit says.  Every other operation is tri_test's, so an accepted hit has tri_test's bits.
+__device__ __forceinline__ bool tri_test_cull(const Ray& r, const float4 t0, const float4 t1, const float4 t2, uint32_t cull_and, uint32_t cull_xor,
+                                              float& t, float& u, float& v)
+{
+    const v3 v0 = mk3(t0.x, t0.y, t0.z), e1 = mk3(t0.w, t1.x, t1.y), e2 = mk3(t1.z, t1.w, t2.x), n = mk3(t2.y, t2.z, t2.w);
+    const v3 tvec = r.o - v0;
+    const v3 q    = cross3(tvec, r.d);
+    float    det  = -dot3(r.d, n);
+    float    U = dot3(e2, q), V = -dot3(e1, q), T = dot3(tvec, n);
+    const bool     kept = ((f2u(det) ^ cull_xor) & cull_and) == 0u;
+    const uint32_t sgn  = f2u(det) & 0x80000000u;
+    det = u2f(f2u(det) ^ sgn), U = u2f(f2u(U) ^ sgn), V = u2f(f2u(V) ^ sgn), T = u2f(f2u(T) ^ sgn);
+    const bool  inside = (U >= 0.0f) & (V >= 0.0f) & (U + V <= det);
+    const float inv    = rcp_c(det);
+    const float tt     = T * inv;
+    t = tt, u = U * inv, v = V * inv;
+    return kept & inside & (tt > r.tmin) & (tt < r.tmax);
+}
+
+__device__ __forceinline__ bool tri_occludes_cull(const Ray& r, const float4 t0, const float4 t1, const float4 t2, uint32_t cull_and, uint32_t cull_xor)
+{
+    const v3 v0 = mk3(t0.x, t0.y, t0.z), e1 = mk3(t0.w, t1.x, t1.y), e2 = mk3(t1.z, t1.w, t2.x), n = mk3(t2.y, t2.z, t2.w);
+    const v3 tvec = r.o - v0;
+    const v3 q    = cross3(tvec, r.d);
+    float    det  = -dot3(r.d, n);
+    float    U = dot3(e2, q), V = -dot3(e1, q), T = dot3(tvec, n);
+    const bool     kept = ((f2u(det) ^ cull_xor) & cull_and) == 0u;
+    const uint32_t sgn  = f2u(det) & 0x80000000u;
+    det = u2f(f2u(det) ^ sgn), U = u2f(f2u(U) ^ sgn), V = u2f(f2u(V) ^ sgn), T = u2f(f2u(T) ^ sgn);
+    return kept & (det > 0.0f) & (U >= 0.0f) & (V >= 0.0f) & (U + V <= det) & (T > r.tmin * det) & (T < r.tmax * det);
+}
+
 // A caller's ray (CapRayDesc, cap_trace_rays / cap_trace_occlusion) that the query kernels trace: finite origin and direction, a
 // direction that is not zero, tmin < tmax (false when either is NaN).  Any other ray is answered with a miss without a traversal.
 __device__ __forceinline__ bool query_ray_ok(const float4 org_tmin, const float4 dir_tmax)

@@ -164,6 +164,8 @@ struct CapContext
     float            wide8_ms = 0.f;
     DevBuf<uint32_t> stack_spill;             // traversal-stack entries beyond the LDS part, per thread of the persistent grid
     DevBuf<uint32_t> query_work, query_defer; // cap_trace_rays / cap_trace_occlusion: chunk and hand-over counters, rays handed to the binary tree
+    DevBuf<uint8_t>  tri_mask;                // cap_scene_set_instance_masks: each triangle's mesh mask, by global triangle id
+    bool             tri_mask_on = false;     // a mask table is installed (some mask differs from 0xFF)
     DevBuf<float4>   fan_pairs, fan_singles;  // exhaustive path: fan-pair records (5 float4) and the unpaired triangles (4 float4)
     uint32_t         fan_pair_count = 0, fan_single_count = 0;
     DevBuf<float4>   fan_pairs_nee;           // the pair records again, potential occluders of next-event rays first (update_nee_pairs)
@@ -706,6 +708,40 @@ int cap_scene_upload(CapContext* c, const float* positions, const float* normals
     c->bvh_stale   = false;
     c->positions_host_stale = false;
     c->lane1_failed_paths = 0;  // another scene, other buffers: a second batch lane that did not fit before may fit now
+    c->tri_mask_on = false;     // instance masks belong to the previous scene's meshes
+    return CAP_OK;
+}
+
+int cap_scene_set_instance_masks(CapContext* c, const uint8_t* masks, uint32_t mesh_count)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_scene_set_instance_masks: ctx is NULL");
+    if (!c->scene_ready) return fail(CAP_ERR_STATE, "cap_scene_set_instance_masks: no scene uploaded");
+    if (mesh_count != c->mesh_count)
+        return fail(CAP_ERR_INVALID_ARG, "cap_scene_set_instance_masks: mesh_count %u is not the uploaded scene's (%u)", mesh_count, c->mesh_count);
+    bool all = true;
+    for (uint32_t m = 0; masks && m < mesh_count; ++m) all = all && masks[m] == 0xFFu;
+    if (all)
+    {
+        c->tri_mask_on = false;  // host state: the queries that follow take the plain kernels; those enqueued keep the table they were given
+        return CAP_OK;
+    }
+    // one byte per global triangle id (mesh-table order, then primitive order: the ids of cap_scene_upload)
+    std::vector<uint8_t> bytes;
+    bytes.reserve(c->tri_count);
+    for (uint32_t m = 0; m < mesh_count; ++m) bytes.insert(bytes.end(), c->meshes_host[m].index_count / 3, masks[m]);
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->tri_mask.n < bytes.size())
+    {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (a grown buffer replaces one an earlier query may still be reading)
+        HIP_TRY(c->tri_mask.ensure(bytes.size()));
+    }
+    // ordered on the context stream behind every query enqueued; the host bytes may go once the call returns
+    if (!bytes.empty())
+    {
+        HIP_TRY(hipMemcpyAsync(c->tri_mask.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    c->tri_mask_on = true;
     return CAP_OK;
 }
 
@@ -2167,11 +2203,47 @@ QueryArgs query_args(const QueryRun& run, const CapRayDesc* rays, uint64_t n, ui
     return q;
 }
 
-int trace_query(CapContext* c, const char* what, const CapRayDesc* rays, uint64_t n, void* out, size_t out_stride, uint32_t flags, bool any)
+// The filter of an _ex call (CapTraceOptions; NULL = the plain call).  on: the call takes the filtered kernels -- it has a cull or
+// first-hit flag, or a mask table is installed (then also through the plain entry points: a mesh with mask 0 is invisible to every
+// query).  With every mask 0xFF no inclusion mask rejects anything and the plain kernels answer.
+struct QueryFilter
+{
+    bool      on = false, first_hit = false;
+    RayFilter f{};
+};
+
+int query_filter(CapContext* c, const char* what, const CapTraceOptions* o, bool multi, QueryFilter& out)
+{
+    static_assert(sizeof(CapTraceOptions) == 16, "CapTraceOptions is four words");
+    const uint32_t flags = o ? o->ray_flags : 0u, mask = o ? o->instance_mask : 0u;
+    const uint32_t known = CAP_RAY_FLAG_ACCEPT_FIRST_HIT | CAP_RAY_FLAG_CULL_BACK_FACING | CAP_RAY_FLAG_CULL_FRONT_FACING;
+    const uint32_t cull  = flags & (CAP_RAY_FLAG_CULL_BACK_FACING | CAP_RAY_FLAG_CULL_FRONT_FACING);
+    if (flags & ~known) return fail(CAP_ERR_INVALID_ARG, "%s: unknown ray_flags 0x%x", what, flags);
+    if (cull == (CAP_RAY_FLAG_CULL_BACK_FACING | CAP_RAY_FLAG_CULL_FRONT_FACING))
+        return fail(CAP_ERR_INVALID_ARG, "%s: CAP_RAY_FLAG_CULL_BACK_FACING and CAP_RAY_FLAG_CULL_FRONT_FACING exclude each other", what);
+    if (multi && (flags & CAP_RAY_FLAG_ACCEPT_FIRST_HIT))
+        return fail(CAP_ERR_INVALID_ARG, "%s: CAP_RAY_FLAG_ACCEPT_FIRST_HIT has no meaning for a multi-hit query", what);
+    if (o && (o->reserved[0] || o->reserved[1])) return fail(CAP_ERR_INVALID_ARG, "%s: options->reserved must be 0", what);
+    if (mask > 0xFFu) return fail(CAP_ERR_INVALID_ARG, "%s: instance_mask 0x%x exceeds 8 bits", what, mask);
+    out.first_hit  = (flags & CAP_RAY_FLAG_ACCEPT_FIRST_HIT) != 0;
+    out.f.cull_and = cull ? 0x80000000u : 0u;
+    out.f.cull_xor = cull == CAP_RAY_FLAG_CULL_FRONT_FACING ? 0x80000000u : 0u;
+    out.f.mask     = mask ? mask : 0xFFu;
+    out.f.tri_mask = c->tri_mask_on ? c->tri_mask.p : nullptr;
+    out.on         = cull || out.first_hit || c->tri_mask_on;
+    return CAP_OK;
+}
+
+int trace_query(CapContext* c, const char* what, const CapRayDesc* rays, uint64_t n, void* out, size_t out_stride, uint32_t flags, bool any,
+                const CapTraceOptions* options = nullptr)
 {
     static_assert(sizeof(CapRayDesc) == 2 * sizeof(float4) && sizeof(CapHit) == sizeof(float4), "query records are the kernels' float4 records");
     if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
     if (flags != 0) return fail(CAP_ERR_INVALID_ARG, "%s: flags is reserved and must be 0 (got 0x%x)", what, flags);
+    QueryFilter flt;
+    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
+    const bool       first = flt.first_hit && !any;  // (an occlusion query ends at its first hit anyway)
+    const RayFilter* f     = flt.on ? &flt.f : nullptr;
     if (const int rc = query_state(c, what)) return rc;
     if (n == 0) return CAP_OK;
     if (!rays || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
@@ -2189,14 +2261,20 @@ int trace_query(CapContext* c, const char* what, const CapRayDesc* rays, uint64_
         if (run.bvh.wide8_ok)
         {
             HIP_TRY(hipMemsetAsync(c->query_work.p, 0, sizeof(uint32_t) * 2 * kCounterStride, c->stream));
-            launch_query8(run.cfg, run.bvh, q, any);
+            launch_query8(run.cfg, run.bvh, q, any, f, first);
             if (run.traced(any ? "k_query_any8" : "k_query_closest8", done) != CAP_OK) return CAP_ERR_HIP;
-            launch_query_binary(run.cfg, run.bvh, q, any, true);
+            if (f)
+                launch_query_binary_filtered(run.cfg, run.bvh, q, *f, any, first, true);
+            else
+                launch_query_binary(run.cfg, run.bvh, q, any, true);
             if (run.traced(any ? "k_query_binary<any> (handed-over rays)" : "k_query_binary<closest> (handed-over rays)", done) != CAP_OK) return CAP_ERR_HIP;
         }
         else
         {
-            launch_query_binary(run.cfg, run.bvh, q, any, false);
+            if (f)
+                launch_query_binary_filtered(run.cfg, run.bvh, q, *f, any, first, false);
+            else
+                launch_query_binary(run.cfg, run.bvh, q, any, false);
             if (run.traced(any ? "k_query_binary<any>" : "k_query_binary<closest>", done) != CAP_OK) return CAP_ERR_HIP;
         }
     }
@@ -2205,12 +2283,15 @@ int trace_query(CapContext* c, const char* what, const CapRayDesc* rays, uint64_
 
 // cap_trace_rays_multi: the first k hits of each ray in (t, triangle) order, and / or its hit count (query.hip k_query_multi8,
 // k_query_binary_multi).  Validation and launches as trace_query, with k records per ray: their offsets are 64-bit.
-int trace_multi(CapContext* c, const CapRayDesc* rays, uint64_t n, uint32_t k, CapHit* hits, uint32_t* counts, uint32_t flags)
+int trace_multi(CapContext* c, const char* what, const CapRayDesc* rays, uint64_t n, uint32_t k, CapHit* hits, uint32_t* counts, uint32_t flags,
+                const CapTraceOptions* options = nullptr)
 {
     static_assert(CAP_MULTI_MAX_K == kMultiMaxK, "the header's page limit is the kernels' largest bucket");
-    const char* what = "cap_trace_rays_multi";
     if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
     if (flags & ~(uint32_t)CAP_MULTI_CONTINUE) return fail(CAP_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    QueryFilter flt;
+    if (const int rc = query_filter(c, what, options, true, flt)) return rc;
+    const RayFilter* f = flt.on ? &flt.f : nullptr;
     if (k > CAP_MULTI_MAX_K) return fail(CAP_ERR_INVALID_ARG, "%s: k = %u exceeds CAP_MULTI_MAX_K (%d); page with CAP_MULTI_CONTINUE", what, k, CAP_MULTI_MAX_K);
     if (k == 0 && (hits || !counts)) return fail(CAP_ERR_INVALID_ARG, "%s: k = 0 counts only: hits must be NULL and counts given", what);
     if (k == 0 && (flags & CAP_MULTI_CONTINUE)) return fail(CAP_ERR_INVALID_ARG, "%s: CAP_MULTI_CONTINUE needs k >= 1 (the cursor is slot k - 1)", what);
@@ -2238,14 +2319,14 @@ int trace_multi(CapContext* c, const CapRayDesc* rays, uint64_t n, uint32_t k, C
         if (run.bvh.wide8_ok)
         {
             HIP_TRY(hipMemsetAsync(c->query_work.p, 0, sizeof(uint32_t) * 2 * kCounterStride, c->stream));
-            launch_query8_multi(run.cfg, run.bvh, m);
+            launch_query8_multi(run.cfg, run.bvh, m, f);
             if (run.traced("k_query_multi8", done) != CAP_OK) return CAP_ERR_HIP;
-            launch_query_binary_multi(run.cfg, run.bvh, m, true);
+            launch_query_binary_multi(run.cfg, run.bvh, m, true, f);
             if (run.traced("k_query_binary_multi (handed-over rays)", done) != CAP_OK) return CAP_ERR_HIP;
         }
         else
         {
-            launch_query_binary_multi(run.cfg, run.bvh, m, false);
+            launch_query_binary_multi(run.cfg, run.bvh, m, false, f);
             if (run.traced("k_query_binary_multi", done) != CAP_OK) return CAP_ERR_HIP;
         }
     }
@@ -2266,7 +2347,23 @@ int cap_trace_occlusion(CapContext* c, const CapRayDesc* device_rays, uint64_t n
 int cap_trace_rays_multi(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits, uint32_t* device_counts,
                          uint32_t flags)
 {
-    return trace_multi(c, device_rays, n, k, device_hits, device_counts, flags);
+    return trace_multi(c, "cap_trace_rays_multi", device_rays, n, k, device_hits, device_counts, flags);
+}
+
+int cap_trace_rays_ex(CapContext* c, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, const CapTraceOptions* options)
+{
+    return trace_query(c, "cap_trace_rays_ex", device_rays, n, device_hits, sizeof(CapHit), 0, false, options);
+}
+
+int cap_trace_occlusion_ex(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded, const CapTraceOptions* options)
+{
+    return trace_query(c, "cap_trace_occlusion_ex", device_rays, n, device_occluded, sizeof(uint32_t), 0, true, options);
+}
+
+int cap_trace_rays_multi_ex(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits, uint32_t* device_counts,
+                            uint32_t multi_flags, const CapTraceOptions* options)
+{
+    return trace_multi(c, "cap_trace_rays_multi_ex", device_rays, n, k, device_hits, device_counts, multi_flags, options);
 }
 
 void cap_post_settings_default(CapPostSettings* out)

@@ -1,5 +1,5 @@
-// query.hip — ray queries of caller-supplied rays (cap_trace_rays / cap_trace_occlusion) on the compressed 8-wide view (cap_wide.h),
-// gfx950.
+// query.hip — ray queries of caller-supplied rays (cap_trace_rays / cap_trace_occlusion, their multi-hit and filtered forms) on the
+// compressed 8-wide view (cap_wide.h), gfx950.
 //
 // The render's extension-ray kernel (trace8.hip k_trace_closest8) reads its rays from a class-partitioned queue; these kernels read the
 // caller's CapRayDesc array instead, with no copy: a 32-B record is exactly the (origin, tmin) (direction, tmax) float4 pair the LDS ray
@@ -108,8 +108,27 @@ __device__ __forceinline__ bool query_admit(const QueryArgs& q, float4 a, float4
     return true;
 }
 
-// Closest hit: CapHit (t, u, v, asfloat(triangle)) per ray; a miss is (tmax, 0, 0, ~0).
-__global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_closest8(BvhDev bvh, QueryArgs q, uint32_t refill_idle)
+// Ray flags and instance masks (cap_trace_*_ex): every kernel of this file exists in a plain and a filtered (_f) form; the wide ones
+// are made from one body, FILTER a template flag, and the plain kernels are instruction for instruction what they were without it.  The cull sits inside the
+// triangle test (tri_test_cull); the mask byte of a triangle is read only once the triangle has passed that test, and only when the
+// call filters by mask (wave-uniform branch).  A rejected triangle is as if it were not in the scene: it never reaches best_t, the
+// list or the count, so nothing is pruned by it.
+__device__ __forceinline__ bool filter_admits(const RayFilter& f, uint32_t gid) { return !f.tri_mask || (f.tri_mask[gid] & f.mask) != 0u; }
+
+template <bool FILTER>
+__device__ __forceinline__ bool query_tri_test(const Ray& r, const float4 t0, const float4 t1, const float4 t2, const RayFilter& f, float& t,
+                                               float& u, float& v)
+{
+    if constexpr (FILTER)
+        return tri_test_cull(r, t0, t1, t2, f.cull_and, f.cull_xor, t, u, v);
+    else
+        return tri_test(r, t0, t1, t2, t, u, v);
+}
+
+// Closest hit: CapHit (t, u, v, asfloat(triangle)) per ray; a miss is (tmax, 0, 0, ~0).  FIRST (CAP_RAY_FLAG_ACCEPT_FIRST_HIT): the
+// lane writes the first hit it accepts and retires, as k_query_any8's lanes do at their first occluder.
+template <bool FILTER, bool FIRST>
+__device__ __forceinline__ void query_closest8(const BvhDev& bvh, const QueryArgs& q, uint32_t refill_idle, const RayFilter& f)
 {
     __shared__ uint2  lds_stack[kQueryLds * kBlock];
     __shared__ float4 lds_rays[2 * kBlock];  // per wave: 64 x (origin, tmin) then 64 x (direction, tmax)
@@ -171,10 +190,19 @@ __global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_closest8(BvhDev
         if (tri_lane)
         {
             float t, u, v;
-            if (tri_test(r, nd.h0, nd.h1, nd.q2, t, u, v))
+            if (query_tri_test<FILTER>(r, nd.h0, nd.h1, nd.q2, f, t, u, v))
             {
                 const uint32_t gid = f2u(nd.q3.x);
-                if (t < best_t || (t == best_t && gid < best_gid)) best_t = t, best_u = u, best_v = v, best_gid = gid;
+                if (!FILTER || filter_admits(f, gid))
+                {
+                    if (FIRST)
+                    {
+                        hits[out] = make_float4(t, u, v, u2f(gid));
+                        alive     = false;
+                    }
+                    else if (t < best_t || (t == best_t && gid < best_gid))
+                        best_t = t, best_u = u, best_v = v, best_gid = gid;
+                }
             }
         }
         if (node_lane) wide_node_test(nd, w, r.tmin, best_t, c);
@@ -191,10 +219,24 @@ __global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_closest8(BvhDev
     }
 }
 
+__global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_closest8(BvhDev bvh, QueryArgs q, uint32_t refill_idle)
+{
+    query_closest8<false, false>(bvh, q, refill_idle, RayFilter{});
+}
+__global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_closest8_f(BvhDev bvh, QueryArgs q, uint32_t refill_idle, RayFilter f)
+{
+    query_closest8<true, false>(bvh, q, refill_idle, f);
+}
+__global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_first8_f(BvhDev bvh, QueryArgs q, uint32_t refill_idle, RayFilter f)
+{
+    query_closest8<true, true>(bvh, q, refill_idle, f);
+}
+
 // Occlusion: 1 when some triangle has tmin det < T < tmax det (tri_occludes), else 0, one word per ray.  The lane-refill form of
 // k_trace_any8_refill with the caller's rays: per-lane octant (caller rays share no light direction), back-to-front visiting order
-// (kAnyOrder) and early exit at the first occluder.
-__global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_any8(BvhDev bvh, QueryArgs q, uint32_t refill_idle)
+// (kAnyOrder) and early exit at the first occluder.  FILTER: a triangle lane reads all 64 bytes of its record, for the id in word 12.
+template <bool FILTER>
+__device__ __forceinline__ void query_any8(const BvhDev& bvh, const QueryArgs& q, uint32_t refill_idle, const RayFilter& f)
 {
     __shared__ uint2  lds_stack[kQueryLds * kBlock];
     __shared__ float4 lds_rays[2 * kBlock];
@@ -249,9 +291,16 @@ __global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_any8(BvhDev bvh
         CAP_DEF4(nd.q4);
 #undef CAP_DEF4
         if (alive) nd.h0 = src[0], nd.h1 = src[1], nd.q2 = src[2];
-        if (node_lane) nd.q3 = src[3], nd.q4 = src[4];  // (an occlusion test reads 48 of a triangle record's 64 bytes)
+        if (FILTER && tri_lane) nd.q3 = src[3];
+        if (node_lane) nd.q3 = src[3], nd.q4 = src[4];  // (a plain occlusion test reads 48 of a triangle record's 64 bytes)
         bool occluded = false;
-        if (tri_lane) occluded = tri_occludes(r, nd.h0, nd.h1, nd.q2);
+        if constexpr (FILTER)
+        {
+            if (tri_lane) occluded = tri_occludes_cull(r, nd.h0, nd.h1, nd.q2, f.cull_and, f.cull_xor);
+            if (occluded) occluded = filter_admits(f, f2u(nd.q3.x));
+        }
+        else if (tri_lane)
+            occluded = tri_occludes(r, nd.h0, nd.h1, nd.q2);
         if (node_lane) wide_node_test<kAnyOrder>(nd, w, r.tmin, r.tmax, c);
         if (occluded)
         {
@@ -271,9 +320,18 @@ __global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_any8(BvhDev bvh
     }
 }
 
+__global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_any8(BvhDev bvh, QueryArgs q, uint32_t refill_idle)
+{
+    query_any8<false>(bvh, q, refill_idle, RayFilter{});
+}
+__global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_any8_f(BvhDev bvh, QueryArgs q, uint32_t refill_idle, RayFilter f)
+{
+    query_any8<true>(bvh, q, refill_idle, f);
+}
+
 bool query8_stack_matches() { return (uint32_t)kQueryLds + kSpillEntries / 2u == wide8_stack_pairs(); }
 
-void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any)
+void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any, const RayFilter* f, bool first_hit)
 {
     uint32_t       g   = (q.n + kBlock - 1) / kBlock;
     uint32_t       cap = cfg.cu_count ? cfg.cu_count * (uint32_t)CAP_W8_BLOCKS : cfg.grid_blocks;
@@ -282,7 +340,16 @@ void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, 
     if (g == 0) g = 1;
     const long     v      = (long)cfg.sw_get(SW_W8_REFILL, CAP_W8_REFILL);  // (clamped as trace8.hip w8_refill_idle does)
     const uint32_t refill = (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v);
-    if (any)
+    if (f)
+    {
+        if (any)
+            hipLaunchKernelGGL(k_query_any8_f, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill, *f);
+        else if (first_hit)
+            hipLaunchKernelGGL(k_query_first8_f, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill, *f);
+        else
+            hipLaunchKernelGGL(k_query_closest8_f, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill, *f);
+    }
+    else if (any)
         hipLaunchKernelGGL(k_query_any8, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill);
     else
         hipLaunchKernelGGL(k_query_closest8, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill);
@@ -391,8 +458,8 @@ constexpr int multi8_blocks(int K) { return K <= 1 ? 5 : K <= 4 ? 4 : K <= 8 ? 3
 
 // Multi-hit on the wide tree: k_query_closest8's feed, refill, pair stack and hand-over of far origins, with the list instead of the
 // single best record.
-template <int K, bool COUNT>
-__global__ __launch_bounds__(kBlock, multi8_blocks(K)) void k_query_multi8(BvhDev bvh, MultiArgs m, uint32_t refill_idle)
+template <int K, bool COUNT, bool FILTER>
+__device__ __forceinline__ void query_multi8(const BvhDev& bvh, const MultiArgs& m, uint32_t refill_idle, const RayFilter& f)
 {
     __shared__ uint2  lds_stack[kQueryLds * kBlock];
     __shared__ float4 lds_rays[2 * kBlock];
@@ -467,7 +534,8 @@ __global__ __launch_bounds__(kBlock, multi8_blocks(K)) void k_query_multi8(BvhDe
         if (tri_lane)
         {
             float t, u, v;
-            if (tri_test(r, nd.h0, nd.h1, nd.q2, t, u, v)) multi_offer<K, COUNT>(L, count, tc, gc, t, f2u(nd.q3.x));
+            if (query_tri_test<FILTER>(r, nd.h0, nd.h1, nd.q2, f, t, u, v) && (!FILTER || filter_admits(f, f2u(nd.q3.x))))
+                multi_offer<K, COUNT>(L, count, tc, gc, t, f2u(nd.q3.x));
         }
         if (node_lane) wide_node_test(nd, w, lo, COUNT ? r.tmax : L.t[K - 1], c);
         if (alive && c.t_hits == 0u && (c.g_mask >> 24) == 0u)
@@ -481,6 +549,17 @@ __global__ __launch_bounds__(kBlock, multi8_blocks(K)) void k_query_multi8(BvhDe
                 st.pop(c);
         }
     }
+}
+
+template <int K, bool COUNT>
+__global__ __launch_bounds__(kBlock, multi8_blocks(K)) void k_query_multi8(BvhDev bvh, MultiArgs m, uint32_t refill_idle)
+{
+    query_multi8<K, COUNT, false>(bvh, m, refill_idle, RayFilter{});
+}
+template <int K, bool COUNT>
+__global__ __launch_bounds__(kBlock, multi8_blocks(K)) void k_query_multi8_f(BvhDev bvh, MultiArgs m, uint32_t refill_idle, RayFilter f)
+{
+    query_multi8<K, COUNT, true>(bvh, m, refill_idle, f);
 }
 
 // Multi-hit on the binary tree, one lane per ray: traverse_closest's loop (kernels.hip) with the list; every ray where the wide view
@@ -554,6 +633,148 @@ __global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, K)) void k_query
     }
 }
 
+// k_query_binary_multi under a filter (cap_trace_rays_multi_ex).  A kernel of its own rather than a second instantiation of one body:
+// here, unlike in the wide kernels, wrapping the loop in a shared function changed the plain kernel's instruction schedule.
+template <int STACK, int K, bool COUNT>
+__global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, K)) void k_query_binary_multi_f(BvhDev bvh, MultiArgs m, uint32_t deferred, RayFilter f)
+{
+    __shared__ uint32_t lds_stack[STACK * kBlock];
+    uint32_t* const     stack = lds_stack + threadIdx.x;
+    const QueryArgs&    q     = m.q;
+    const uint32_t      n     = deferred ? q.work[kCounterStride] : q.n;
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock)
+    {
+        const uint32_t i = deferred ? q.defer[j] : j;
+        const float4   a = q.rays[2 * (size_t)i], b = q.rays[2 * (size_t)i + 1];
+        if (!query_ray_ok(a, b))
+        {
+            multi_write_miss(m, i, b.w);
+            continue;
+        }
+        const Ray  r = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
+        HitList<K> L;
+        L.init(m.k, r.tmax);
+        float    tc;
+        uint32_t gc, count = 0u;
+        multi_cursor(m, i, tc, gc);
+        Ray rb  = r;  // the box tests' interval: lower bound max(tmin, t_c)
+        rb.tmin = fmaxf(r.tmin, tc);
+        int node = bvh.root, sp = 0;
+        while (bvh.tri_count != 0u)
+        {
+            const float tfar = COUNT ? r.tmax : L.t[K - 1];
+            if (node >= 0)
+            {
+                const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2],
+                             q3 = bvh.nodes[4 * node + 3];
+                float      tn0, tn1;
+                const bool h0 = slab(rb, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, tfar, tn0);
+                const bool h1 = slab(rb, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, tfar, tn1);
+                const int  c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+                if (h0 && h1)
+                {
+                    const bool swap = tn1 < tn0;
+                    if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)(swap ? c0 : c1);
+                    node = swap ? c1 : c0;
+                    continue;
+                }
+                if (h0 || h1)
+                {
+                    node = h0 ? c0 : c1;
+                    continue;
+                }
+            }
+            else
+            {
+                const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                for (uint32_t leaf = first; leaf <= last; ++leaf)
+                {
+                    const float4 t0 = bvh.tris[4 * leaf + 0], t1 = bvh.tris[4 * leaf + 1], t2 = bvh.tris[4 * leaf + 2];
+                    float        t, u, v;
+                    if (!tri_test_cull(r, t0, t1, t2, f.cull_and, f.cull_xor, t, u, v)) continue;
+                    const uint32_t gid = f2u(bvh.tris[4 * leaf + 3].x);
+                    if (filter_admits(f, gid)) multi_offer<K, COUNT>(L, count, tc, gc, t, gid);
+                }
+            }
+            if (sp == 0) break;
+            node = (int)stack[(--sp) * kBlock];
+        }
+        multi_write<K, COUNT>(m, bvh, i, r, L, count);
+    }
+}
+
+// Closest / first / occlusion on the binary tree under a filter, one lane per ray: k_query_binary's place (kernels.hip) for the _ex
+// calls -- every ray where the wide view is not used, and the rays the filtered wide kernels handed over.  The loop is
+// traverse_closest's with tri_test_cull and the mask in front of the best record.  MODE 0: closest; 1: first accepted hit ends the
+// walk; 2: occlusion (tri_occludes_cull, the division-free interval; the visiting order does not change the answer).
+template <int STACK, int MODE>
+__global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, 1)) void k_query_binary_f(BvhDev bvh, QueryArgs q, uint32_t deferred, RayFilter f)
+{
+    __shared__ uint32_t lds_stack[STACK * kBlock];
+    uint32_t* const     stack = lds_stack + threadIdx.x;
+    const uint32_t      n     = deferred ? q.work[kCounterStride] : q.n;
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock)
+    {
+        const uint32_t i = deferred ? q.defer[j] : j;
+        const float4   a = q.rays[2 * (size_t)i], b = q.rays[2 * (size_t)i + 1];
+        const Ray      r = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
+        float          best_t = b.w, best_u = 0.f, best_v = 0.f;
+        uint32_t       best_gid = kInvalidId;
+        bool           found = false;  // MODE 1, 2: the walk is over
+        int            node = bvh.root, sp = 0;
+        const bool     ok = query_ray_ok(a, b);
+        while (ok && bvh.tri_count != 0u)
+        {
+            if (node >= 0)
+            {
+                const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2],
+                             q3 = bvh.nodes[4 * node + 3];
+                float      tn0, tn1;
+                const bool h0 = slab(r, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, best_t, tn0);
+                const bool h1 = slab(r, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, best_t, tn1);
+                const int  c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+                if (h0 && h1)
+                {
+                    const bool swap = tn1 < tn0;
+                    if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)(swap ? c0 : c1);
+                    node = swap ? c1 : c0;
+                    continue;
+                }
+                if (h0 || h1)
+                {
+                    node = h0 ? c0 : c1;
+                    continue;
+                }
+            }
+            else
+            {
+                const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                for (uint32_t leaf = first; leaf <= last && !found; ++leaf)
+                {
+                    const float4 t0 = bvh.tris[4 * leaf + 0], t1 = bvh.tris[4 * leaf + 1], t2 = bvh.tris[4 * leaf + 2];
+                    float        t = 0.f, u = 0.f, v = 0.f;
+                    const bool   hit = MODE == 2 ? tri_occludes_cull(r, t0, t1, t2, f.cull_and, f.cull_xor)
+                                                 : tri_test_cull(r, t0, t1, t2, f.cull_and, f.cull_xor, t, u, v);
+                    if (!hit) continue;
+                    const uint32_t gid = f2u(bvh.tris[4 * leaf + 3].x);
+                    if (!filter_admits(f, gid)) continue;
+                    if (MODE != 0)
+                        best_t = t, best_u = u, best_v = v, best_gid = gid, found = true;
+                    else if (t < best_t || (t == best_t && gid < best_gid))
+                        best_t = t, best_u = u, best_v = v, best_gid = gid;
+                }
+                if (found) break;
+            }
+            if (sp == 0) break;
+            node = (int)stack[(--sp) * kBlock];
+        }
+        if (MODE == 2)
+            static_cast<uint32_t*>(q.out)[i] = found ? 1u : 0u;
+        else
+            static_cast<float4*>(q.out)[i] = make_float4(best_t, best_u, best_v, u2f(best_gid));
+    }
+}
+
 uint32_t multi_bucket(uint32_t k) { return k <= 1 ? 1u : k <= 4 ? 4u : k <= 8 ? 8u : 16u; }
 
 template <auto KERNEL>
@@ -571,25 +792,28 @@ static uint32_t multi_resident(const LaunchCfg& cfg, uint32_t want)  // (residen
 }
 
 template <int K, bool COUNT>
-static void launch_multi8_k(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, uint32_t refill)
+static void launch_multi8_k(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, uint32_t refill, const RayFilter* f)
 {
     uint32_t g   = (m.q.n + kBlock - 1) / kBlock;
     uint32_t cap = cfg.cu_count ? cfg.cu_count * (uint32_t)multi8_blocks(K) : cfg.grid_blocks;
     if ((uint64_t)cap * kBlock > bvh.spill_threads) cap = bvh.spill_threads / kBlock;  // every thread owns a spill slice
     if (g > cap) g = cap;
     if (g == 0) g = 1;
-    hipLaunchKernelGGL((k_query_multi8<K, COUNT>), dim3(g), dim3(kBlock), 0, cfg.stream, bvh, m, refill);
+    if (f)
+        hipLaunchKernelGGL((k_query_multi8_f<K, COUNT>), dim3(g), dim3(kBlock), 0, cfg.stream, bvh, m, refill, *f);
+    else
+        hipLaunchKernelGGL((k_query_multi8<K, COUNT>), dim3(g), dim3(kBlock), 0, cfg.stream, bvh, m, refill);
 }
 
-void launch_query8_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m)
+void launch_query8_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, const RayFilter* f)
 {
     const long     v      = (long)cfg.sw_get(SW_W8_REFILL, CAP_W8_REFILL);
     const uint32_t refill = (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v);
 #define CAP_MULTI8(K)                                                         \
     if (m.counts)                                                             \
-        launch_multi8_k<K, true>(cfg, bvh, m, refill);                        \
+        launch_multi8_k<K, true>(cfg, bvh, m, refill, f);                     \
     else                                                                      \
-        launch_multi8_k<K, false>(cfg, bvh, m, refill);
+        launch_multi8_k<K, false>(cfg, bvh, m, refill, f);
     switch (multi_bucket(m.k))
     {
     case 1: CAP_MULTI8(1) break;
@@ -601,24 +825,28 @@ void launch_query8_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArg
 }
 
 template <int STACK, int K, bool COUNT>
-static void launch_binary_multi_k(const LaunchCfg& cfg, const BvhDev& b, const MultiArgs& m, bool deferred)
+static void launch_binary_multi_k(const LaunchCfg& cfg, const BvhDev& b, const MultiArgs& m, bool deferred, const RayFilter* f)
 {
     uint32_t want = (m.q.n + kBlock - 1) / kBlock;
     // (deferred: the count is on the device and is normally small -- one workgroup per CU at most)
     if (deferred && cfg.cu_count && want > cfg.cu_count) want = cfg.cu_count;
     if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_query_binary_multi<STACK, K, COUNT>), dim3(multi_resident<k_query_binary_multi<STACK, K, COUNT>>(cfg, want)),
-                       dim3(kBlock), 0, cfg.stream, b, m, deferred ? 1u : 0u);
+    if (f)
+        hipLaunchKernelGGL((k_query_binary_multi_f<STACK, K, COUNT>), dim3(multi_resident<k_query_binary_multi_f<STACK, K, COUNT>>(cfg, want)),
+                           dim3(kBlock), 0, cfg.stream, b, m, deferred ? 1u : 0u, *f);
+    else
+        hipLaunchKernelGGL((k_query_binary_multi<STACK, K, COUNT>), dim3(multi_resident<k_query_binary_multi<STACK, K, COUNT>>(cfg, want)),
+                           dim3(kBlock), 0, cfg.stream, b, m, deferred ? 1u : 0u);
 }
 
 template <int STACK>
-static void launch_binary_multi_s(const LaunchCfg& cfg, const BvhDev& b, const MultiArgs& m, bool deferred)
+static void launch_binary_multi_s(const LaunchCfg& cfg, const BvhDev& b, const MultiArgs& m, bool deferred, const RayFilter* f)
 {
 #define CAP_MULTI_BIN(K)                                                      \
     if (m.counts)                                                             \
-        launch_binary_multi_k<STACK, K, true>(cfg, b, m, deferred);           \
+        launch_binary_multi_k<STACK, K, true>(cfg, b, m, deferred, f);        \
     else                                                                      \
-        launch_binary_multi_k<STACK, K, false>(cfg, b, m, deferred);
+        launch_binary_multi_k<STACK, K, false>(cfg, b, m, deferred, f);
     switch (multi_bucket(m.k))
     {
     case 1: CAP_MULTI_BIN(1) break;
@@ -629,13 +857,45 @@ static void launch_binary_multi_s(const LaunchCfg& cfg, const BvhDev& b, const M
 #undef CAP_MULTI_BIN
 }
 
-void launch_query_binary_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, bool deferred)
+void launch_query_binary_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, bool deferred, const RayFilter* f)
 {
     BvhDev b   = bvh;
     b.wide8_ok = 0;
     if (cfg.stack_entries <= 32)
-        launch_binary_multi_s<32>(cfg, b, m, deferred);
+        launch_binary_multi_s<32>(cfg, b, m, deferred, f);
     else
-        launch_binary_multi_s<64>(cfg, b, m, deferred);
+        launch_binary_multi_s<64>(cfg, b, m, deferred, f);
+}
+
+template <int STACK, int MODE>
+static void launch_binary_f(const LaunchCfg& cfg, const BvhDev& b, const QueryArgs& q, const RayFilter& f, bool deferred)
+{
+    uint32_t want = (q.n + kBlock - 1) / kBlock;
+    if (deferred && cfg.cu_count && want > cfg.cu_count) want = cfg.cu_count;  // (as launch_query_binary)
+    if (want == 0) want = 1;
+    hipLaunchKernelGGL((k_query_binary_f<STACK, MODE>), dim3(multi_resident<k_query_binary_f<STACK, MODE>>(cfg, want)), dim3(kBlock), 0, cfg.stream,
+                       b, q, deferred ? 1u : 0u, f);
+}
+
+void launch_query_binary_filtered(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const RayFilter& f, bool any, bool first_hit, bool deferred)
+{
+    BvhDev b   = bvh;
+    b.wide8_ok = 0;
+#define CAP_BIN_F(S)                                               \
+    if (any)                                                       \
+        launch_binary_f<S, 2>(cfg, b, q, f, deferred);             \
+    else if (first_hit)                                            \
+        launch_binary_f<S, 1>(cfg, b, q, f, deferred);             \
+    else                                                           \
+        launch_binary_f<S, 0>(cfg, b, q, f, deferred);
+    if (cfg.stack_entries <= 32)
+    {
+        CAP_BIN_F(32)
+    }
+    else
+    {
+        CAP_BIN_F(64)
+    }
+#undef CAP_BIN_F
 }
 }  // namespace cap

@@ -398,6 +398,55 @@ enum
 int cap_trace_rays_multi(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits, uint32_t* device_counts,
                          uint32_t flags);
 
+/* ---- ray flags and instance masks: DXR TraceRay's RayFlags and InstanceInclusionMask for the three queries above ----
+ * The _ex calls are the plain calls with a per-call filter (one CapTraceOptions for all n rays).  A ray's hits under the options are
+ * the hits of the plain rule whose triangle passes both filters below; nothing else changes: cap_trace_rays_ex returns the minimum
+ * of that set in (t, triangle) order, cap_trace_occlusion_ex whether the occlusion form accepts some triangle that passes,
+ * cap_trace_rays_multi_ex the first k of the set, counts of the set and pages over the set (cursor as above).  Records stay
+ * bit-identical to the oracle's brute force over the triangles that pass.
+ *
+ * Facing.  With the contract's det = -d.n, n = e1 x e2 (before the two-sided sign flip), a triangle is front-facing for a ray when
+ * det > 0: the ray travels against n and sees v0, v1, v2 counter-clockwise (right-handed).  CAP_RAY_FLAG_CULL_BACK_FACING drops
+ * the triangles with det < 0, CAP_RAY_FLAG_CULL_FRONT_FACING those with det > 0; det == 0 is no hit either way.  Both together:
+ * CAP_ERR_INVALID_ARG, as in DXR.
+ *
+ * Masks.  One byte per mesh (the reference has one instance per mesh), 0xFF until cap_scene_set_instance_masks says otherwise.  A
+ * triangle of mesh m is a candidate iff masks[m] & instance_mask & 0xFF != 0.  instance_mask = 0 in the options means 0xFF, so a
+ * zero-filled struct is the plain call (the one deviation from DXR, the rule CapPostSettings follows).  A mesh whose mask is 0 is
+ * invisible to every query, the plain calls included, while the table is installed, as in DXR.  cap_render ignores the masks.
+ *
+ * CAP_RAY_FLAG_ACCEPT_FIRST_HIT on cap_trace_rays_ex: the record is SOME member of the filtered hit set with its own exact
+ * (t, u, v, triangle), and the miss record exactly when the set is empty (the divided test, so hit / miss equals the closest
+ * query's, not the occlusion query's).  Which member is unspecified and may differ between runs and trees.  On
+ * cap_trace_occlusion_ex the flag is accepted and changes nothing; on cap_trace_rays_multi_ex it is CAP_ERR_INVALID_ARG.
+ *
+ * options == NULL or all-zero: the call IS the plain call (same validation, same kernels, same bits); so is any call without a
+ * cull or first-hit flag while no mask table is installed.  Errors on top of the plain calls': CAP_ERR_INVALID_ARG for unknown flag
+ * bits, both cull flags, non-zero reserved words, instance_mask > 0xFF.  Nothing is written on an error. */
+enum /* DXR RAY_FLAG_* values */
+{
+    CAP_RAY_FLAG_ACCEPT_FIRST_HIT  = 0x04, /* RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH */
+    CAP_RAY_FLAG_CULL_BACK_FACING  = 0x10, /* RAY_FLAG_CULL_BACK_FACING_TRIANGLES */
+    CAP_RAY_FLAG_CULL_FRONT_FACING = 0x20  /* RAY_FLAG_CULL_FRONT_FACING_TRIANGLES */
+};
+typedef struct CapTraceOptions /* 16 B */
+{
+    uint32_t ray_flags;     /* CAP_RAY_FLAG_* */
+    uint32_t instance_mask; /* InstanceInclusionMask, low 8 bits; 0 means 0xFF (no filtering) */
+    uint32_t reserved[2];   /* must be 0 */
+} CapTraceOptions;
+/* masks: mesh_count host bytes, one per mesh of the uploaded scene, copied before the call returns; NULL restores all 0xFF (and
+ * removes the table).  Ordered on the context stream after every query already enqueued and before those that follow.  Does not
+ * make the trees stale.  cap_scene_upload resets the masks to 0xFF; cap_bvh_build, cap_bvh_refit and cap_scene_update_vertices
+ * keep them.  CAP_ERR_STATE before cap_scene_upload, CAP_ERR_INVALID_ARG when mesh_count is not the uploaded scene's. */
+int cap_scene_set_instance_masks(CapContext* ctx, const uint8_t* masks, uint32_t mesh_count);
+int cap_trace_rays_ex(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, const CapTraceOptions* options);
+int cap_trace_occlusion_ex(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded,
+                           const CapTraceOptions* options);
+/* multi_flags: cap_trace_rays_multi's flags (CAP_MULTI_CONTINUE) */
+int cap_trace_rays_multi_ex(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits,
+                            uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options);
+
 /* ---- multi-GPU tile exchange (one gather of tile radiance at frame end) ---- */
 /* floats in this context's tile-ordered radiance buffer: max_tiles_per_shard * 64 * 4 (same on every shard) */
 int cap_tile_buffer_floats(CapContext* ctx, size_t* out_floats);

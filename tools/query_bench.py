@@ -9,7 +9,16 @@ Ray sets, each of width x height rays:
      tmax inf): the render's bounce-1 workload;
   c  uniformly random rays: origin uniform in the scene box, direction uniform on the sphere, tmax inf.
 Kinds: closest (cap_trace_rays), occlusion (cap_trace_occlusion), multi1 / multi4 / multi16 (cap_trace_rays_multi, k = 1 / 4 / 16, no
-counts), count (cap_trace_rays_multi, k = 0: hit counts only).
+counts), count (cap_trace_rays_multi, k = 0: hit counts only).  Any kind takes ray flags and instance masks as "+" suffixes and then
+runs through the _ex entry points (closest+back, occlusion+half+front, multi4+back, count+front ...):
+  +back / +front  CAP_RAY_FLAG_CULL_BACK_FACING / CULL_FRONT_FACING;
+  +first          CAP_RAY_FLAG_ACCEPT_FIRST_HIT (closest only);
+  +pass           every mesh mask 0x0F, inclusion mask 0x01: a mask table is installed and passes everything, so the filtered kernels
+                  run the plain call's traversal -- the ratio to the plain kind is the filter's own cost;
+  +half           mesh m has mask 1 << (m & 1), inclusion mask 0x01: every other mesh is invisible;
+  +null           options = NULL: the plain call through the _ex entry point.
+--old-abi binds only the symbols the plain kinds need, for a library built from a commit before the _ex entry points
+(CAP_LIB_VARIANT=<name>, tools/build_variant.sh).
 Per scene, set and kind one JSON line: host clock around cap_sync over `reps` back-to-back calls after `warmup`
 calls (the renderer on its own stream, rays and output resident on the device).  Kernel times come from a separate run of this tool
 under `rocprofv3 --kernel-trace --stats` (k_query_closest8 / k_query_any8 / k_query_multi8; k_query_binary / k_query_binary_multi
@@ -116,7 +125,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--old-abi", action="store_true")
     a = ap.parse_args()
+    if a.old_abi:
+        for name in ("cap_scene_set_instance_masks", "cap_trace_rays_ex", "cap_trace_occlusion_ex", "cap_trace_rays_multi_ex"):
+            capi.SYMBOLS.pop(name)
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(1)
     n = a.width * a.height
@@ -140,19 +153,34 @@ def main():
                 hits = torch.empty((n, 4), dtype=torch.float32, device=dev)
                 occ = torch.empty((n,), dtype=torch.int32, device=dev)
                 torch.cuda.synchronize()
-                for kind in a.kinds.split(","):
+                for full_kind in a.kinds.split(","):
+                    kind, *mods = full_kind.split("+")
+                    unknown = set(mods) - {"back", "front", "first", "pass", "half", "null"}
+                    if unknown or ("pass" in mods and "half" in mods):
+                        raise SystemExit("kind %s: bad suffixes" % full_kind)
+                    opts = None  # CapTraceOptions of the suffixes; with any suffix the call goes through the _ex entry point
+                    if mods:
+                        import ctypes
+                        L = capi.lib()
+                        flags = (0x10 if "back" in mods else 0) | (0x20 if "front" in mods else 0) | (0x04 if "first" in mods else 0)
+                        masked = "pass" in mods or "half" in mods
+                        opts = None if mods == ["null"] else ctypes.byref(capi.TraceOptions(flags, 0x01 if masked else 0))
+                        if masked:
+                            m = np.arange(len(geo.meshes)) & 1
+                            r.set_instance_masks(np.full(len(m), 0x0F, np.uint8) if "pass" in mods else (1 << m).astype(np.uint8))
                     if kind == "closest":
-                        call = lambda: r.trace_rays(rays, out=hits, sync=False)
+                        call = (lambda: r.trace_rays(rays, out=hits, sync=False)) if not mods else (
+                            lambda: capi._check(L.cap_trace_rays_ex(r.ctx, rays.data_ptr(), n, hits.data_ptr(), opts), "cap_trace_rays_ex"))
                     elif kind == "occlusion":
-                        call = lambda: r.trace_occlusion(rays, out=occ, sync=False)
-                    elif kind == "count":  # (the C entry point: the binding would allocate the output per call)
-                        call = lambda: capi._check(capi.lib().cap_trace_rays_multi(r.ctx, rays.data_ptr(), n, 0, None, occ.data_ptr(), 0),
-                                                   "cap_trace_rays_multi")
-                    else:  # multiK
-                        k = int(kind[len("multi"):])
-                        page = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
-                        call = lambda: capi._check(capi.lib().cap_trace_rays_multi(r.ctx, rays.data_ptr(), n, k, page.data_ptr(), None, 0),
-                                                   "cap_trace_rays_multi")
+                        call = (lambda: r.trace_occlusion(rays, out=occ, sync=False)) if not mods else (
+                            lambda: capi._check(L.cap_trace_occlusion_ex(r.ctx, rays.data_ptr(), n, occ.data_ptr(), opts), "cap_trace_occlusion_ex"))
+                    else:  # count (k = 0) and multiK, through the C entry points: the binding would allocate the output per call
+                        k = 0 if kind == "count" else int(kind[len("multi"):])
+                        page = torch.empty((n, k, 4), dtype=torch.float32, device=dev) if k else None
+                        pp, cp = (page.data_ptr(), None) if k else (None, occ.data_ptr())
+                        call = (lambda: capi._check(capi.lib().cap_trace_rays_multi(r.ctx, rays.data_ptr(), n, k, pp, cp, 0), "cap_trace_rays_multi")) \
+                            if not mods else (lambda: capi._check(L.cap_trace_rays_multi_ex(r.ctx, rays.data_ptr(), n, k, pp, cp, 0, opts),
+                                                                  "cap_trace_rays_multi_ex"))
                     for _ in range(a.warmup):
                         call()
                     r.sync()
@@ -169,8 +197,10 @@ def main():
                         extra = {"mean_hits": round(float(occ.double().mean()), 3)}
                     else:
                         extra = {"mean_filled": round(float((page[:, :, 3].view(torch.int32) != -1).double().sum(1).mean()), 3)}
-                    print(json.dumps({"scene": sc, "triangles": int(info.triangle_count), "set": s, "kind": kind, "rays": n,
+                    print(json.dumps({"scene": sc, "triangles": int(info.triangle_count), "set": s, "kind": full_kind, "rays": n,
                                       "ms_per_call": round(ms, 4), "mrays_per_s": round(n / ms / 1e3, 1), **extra}), flush=True)
+                    if mods:
+                        r.set_instance_masks(None)
             r.close()
 
 
