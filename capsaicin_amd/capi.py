@@ -157,6 +157,18 @@ class TraceOptions(C.Structure):  # CapTraceOptions
     _fields_ = [("ray_flags", C.c_uint32), ("instance_mask", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class InstanceDesc(C.Structure):  # CapInstanceDesc, 64 B
+    _fields_ = [("transform", C.c_float * 12), ("mask", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class InstancesInfo(C.Structure):  # CapInstancesInfo
+    _fields_ = [("count", C.c_uint32), ("inert", C.c_uint32), ("tlas_nodes", C.c_uint32), ("tlas_depth", C.c_uint32), ("ms", C.c_double)]
+
+
+INSTANCES_DEVICE = 1  # CAP_INSTANCES_DEVICE
+INSTANCE_MAX_CONDITION = 4096.0  # CAP_INSTANCE_MAX_CONDITION
+INSTANCE_DESC_DTYPE = np.dtype([("transform", np.float32, (12,)), ("mask", np.uint32), ("reserved", np.uint32, (3,))])
+
 # every symbol include/capsaicin_hip.h and include/capsaicin_scene.h declare: (restype, argtypes)
 _vp, _u32, _u64, _i = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 SYMBOLS = {
@@ -200,6 +212,10 @@ SYMBOLS = {
     "cap_trace_rays_ex": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_trace_occlusion_ex": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_trace_rays_multi_ex": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
+    "cap_instances_set": (_i, [_vp, _vp, _u32, _u32, C.POINTER(InstancesInfo)]),
+    "cap_instances_readback": (_i, [_vp, _vp, _vp]),
+    "cap_trace_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
+    "cap_trace_instances_occlusion": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
     "cap_post_settings_default": (None, [C.POINTER(PostSettings)]),
     "cap_post_frame": (_i, [_vp, C.POINTER(PostSettings), _u32, C.POINTER(CameraData)]),
@@ -667,6 +683,95 @@ class Renderer:
                 return host_out
             return res
         return out
+
+    # ---- instanced ray queries (cap_instances_set, cap_trace_instances*) ----
+    def set_instances(self, transforms, masks=None, sync=True):
+        """Installs N instances of the uploaded scene (cap_instances_set) and builds the top-level tree; None removes the table.
+        transforms: (N, 3, 4) or (N, 12) float32 object-to-world matrices, row-major -- a numpy array (host path), or a torch tensor on
+        this context's device: then the 64-byte descriptors are assembled on the device and the call takes CAP_INSTANCES_DEVICE, nothing
+        goes through the host.  masks: N values 0..0xFF, default 0xFF.  sync as trace_rays (the device path with sync=False only
+        enqueues and returns None).  Returns the CapInstancesInfo (count, inert, tlas_nodes, tlas_depth, ms)."""
+        info = InstancesInfo()
+        if transforms is None:
+            _check(lib().cap_instances_set(self.ctx, None, 0, 0, C.byref(info)), "cap_instances_set")
+            self._instances_n = 0
+            return info
+        if isinstance(transforms, np.ndarray) or not hasattr(transforms, "device"):
+            t = np.ascontiguousarray(transforms, np.float32)
+            if t.ndim < 2 or t.size != t.shape[0] * 12:
+                raise CapError("transforms must be (N, 3, 4) or (N, 12), got %s" % (t.shape,))
+            d = np.zeros(t.shape[0], INSTANCE_DESC_DTYPE)
+            d["transform"] = t.reshape(-1, 12)
+            d["mask"] = 0xFF if masks is None else np.asarray(masks).astype(np.uint32).reshape(-1)
+            _check(lib().cap_instances_set(self.ctx, _p(d), d.shape[0], 0, C.byref(info)), "cap_instances_set")
+            self._instances_n = d.shape[0]
+            return info
+        import torch
+        dev = torch.device("cuda", self.device)
+        if transforms.dtype != torch.float32 or transforms.device != dev or transforms.numel() != transforms.shape[0] * 12:
+            raise CapError("transforms must be an (N, 3, 4) or (N, 12) float32 tensor on %s" % (dev,))
+        n = transforms.shape[0]
+        d = torch.zeros((n, 16), dtype=torch.float32, device=dev)
+        d[:, :12] = transforms.reshape(n, 12)
+        m = torch.full((n,), 0xFF, dtype=torch.int32, device=dev) if masks is None else torch.as_tensor(masks, device=dev).to(torch.int32).reshape(n)
+        d[:, 12] = m.view(torch.float32)
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the descriptors were written on torch's stream
+        _check(lib().cap_instances_set(self.ctx, C.c_void_p(d.data_ptr()), n, INSTANCES_DEVICE, C.byref(info) if sync else None), "cap_instances_set")
+        self._instances_n = n
+        if not sync:
+            self._instances_keepalive = d  # read on the context's stream after the call returns
+            return None
+        return info
+
+    def instances_readback(self):
+        """(W, boxes) of the table set_instances installed (cap_instances_readback): W (N, 3, 4) float32 world-to-object as stored --
+        all zero for an inert instance -- and the padded world boxes (N, 2, 3) float32 (lo, hi)."""
+        count = getattr(self, "_instances_n", 0)
+        w = np.zeros((count, 3, 4), np.float32)
+        b = np.zeros((count, 2, 3), np.float32)
+        _check(lib().cap_instances_readback(self.ctx, _p(w), _p(b)), "cap_instances_readback")
+        return w, b
+
+    def trace_instances(self, rays, out=None, sync=True, cull=None, mask=None, first_hit=False):
+        """Closest hit of each ray over the instance table (cap_trace_instances): (hits (N, 4) float32, instance (N,) int32, -1 on a
+        miss).  Records as trace_rays, with object-space (u, v) and the scene's triangle id.  Arguments as trace_rays."""
+        return self._query_instances(rays, out, sync, False, self.trace_options(cull, mask, first_hit))
+
+    def trace_instances_occlusion(self, rays, out=None, sync=True, cull=None, mask=None):
+        """1 where some triangle of some instance occludes the ray's open interval, else 0: (N,) int32 (cap_trace_instances_occlusion)."""
+        return self._query_instances(rays, out, sync, True, self.trace_options(cull, mask))
+
+    def _query_instances(self, rays, out, sync, any_hit, options):
+        import torch
+        dev = torch.device("cuda", self.device)
+        host = isinstance(rays, np.ndarray)
+        if host:
+            rays = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).to(dev)
+            sync = True  # the result is read back to the host
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.device != dev:
+            raise CapError("rays must be a contiguous (N, 8) float32 tensor on %s, got %s %s on %s" % (dev, rays.dtype, tuple(rays.shape), rays.device))
+        n = rays.shape[0]
+        shape, dtype = ((n,), torch.int32) if any_hit else ((n, 4), torch.float32)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        elif out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+            raise CapError("out must be a contiguous %s %s tensor on %s" % (tuple(shape), dtype, dev))
+        inst = None if any_hit else torch.empty((n,), dtype=torch.int32, device=dev)
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the rays (and the outputs' allocations) were made on torch's stream
+        opt = C.byref(options) if options is not None else None
+        if any_hit:
+            _check(lib().cap_trace_instances_occlusion(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), opt),
+                   "cap_trace_instances_occlusion")
+        else:
+            _check(lib().cap_trace_instances(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(inst.data_ptr()), opt),
+                   "cap_trace_instances")
+        if sync:
+            self.sync()
+        if any_hit:
+            return out.cpu().numpy() if host else out
+        return (out.cpu().numpy(), inst.cpu().numpy()) if host else (out, inst)
 
     MULTI_MAX_K, MULTI_CONTINUE = 16, 1  # CAP_MULTI_MAX_K, CAP_MULTI_CONTINUE
 

@@ -690,6 +690,23 @@ void launch_bvh_finish_host(hipStream_t stream, const BvhBuildArgs& a)
 }
 
 
+// stable LSD radix sort of n (32-bit key, value) pairs, four 8-bit passes between the two buffer pairs: the sorted pairs are
+// keys[r], vals[r] for the returned r.  hist: 256 * bvh_radix_blocks(n) words; scan: bvh_radix_scan_words(n) words.
+size_t bvh_radix_scan_words(uint32_t n) { return (256u * bvh_radix_blocks(n) + kScanTile - 1) / kScanTile; }
+int    launch_radix_sort_pairs(hipStream_t stream, uint32_t* const keys[2], uint32_t* const vals[2], uint32_t n, uint32_t* hist, uint32_t* scan)
+{
+    int            src = 0;
+    const uint32_t nb  = (uint32_t)bvh_radix_blocks(n);
+    for (uint32_t shift = 0; shift < 32; shift += 8)
+    {
+        hipLaunchKernelGGL(k_radix_hist, dim3(nb), dim3(kBlock), 0, stream, keys[src], n, shift, nb, hist);
+        launch_exclusive_scan(stream, hist, 256u * nb, scan);
+        hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(kBlock), 0, stream, keys[src], vals[src], keys[src ^ 1], vals[src ^ 1], n, shift, nb, hist);
+        src ^= 1;
+    }
+    return src;
+}
+
 // setup + Morton codes + radix sort; the sorted (key, triangle) arrays are a.keys[r], a.vals[r] for the returned r
 int launch_bvh_sort(hipStream_t stream, const BvhBuildArgs& a)
 {
@@ -701,15 +718,7 @@ int launch_bvh_sort(hipStream_t stream, const BvhBuildArgs& a)
     if (n >= 2)
     {
         hipLaunchKernelGGL(k_morton, dim3(blocks), dim3(kBlock), 0, stream, a);
-        const uint32_t nb = (uint32_t)bvh_radix_blocks(n);
-        for (uint32_t shift = 0; shift < 32; shift += 8)
-        {
-            hipLaunchKernelGGL(k_radix_hist, dim3(nb), dim3(kBlock), 0, stream, a.keys[src], n, shift, nb, a.hist);
-            launch_exclusive_scan(stream, a.hist, 256u * nb, a.parent);  // (a.parent: 2 n words that every builder writes in full after the sort)
-            hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(kBlock), 0, stream, a.keys[src], a.vals[src], a.keys[src ^ 1],
-                               a.vals[src ^ 1], n, shift, nb, a.hist);
-            src ^= 1;
-        }
+        src = launch_radix_sort_pairs(stream, a.keys, a.vals, n, a.hist, a.parent);  // (a.parent: 2 n words that every builder writes in full after the sort)
     }
     else
     {

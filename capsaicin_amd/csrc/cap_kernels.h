@@ -135,6 +135,43 @@ struct RayFilter
 // launch_query_binary under a filter (query.hip k_query_binary_f; first_hit: closest only, the lane retires at its first accepted hit)
 void launch_query_binary_filtered(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const RayFilter& f, bool any, bool first_hit, bool deferred);
 
+// ---- instances (instance.hip): cap_instances_set, cap_trace_instances* ----
+// The table on the device.  rec: 4 float4 per instance = the three rows of W (world to object, row r = (W_r0, W_r1, W_r2, W_r3)) and
+// (asfloat(mask), -, -, -); an inert instance has W = 0 and mask 0.  box: 2 float4 per instance = (lo.xyz, k) (hi.xyz, asfloat(index)),
+// k >= 0 the per-ray inflation factor of tlas_slab (instance.hip), k < 0 for an inert instance or a padding entry.
+// tlas: the top-level tree, an implicit binary tree over the instances in Morton order.  Level 0 holds the instances' box records in
+// that order, level l + 1 entry j the union of level l entries 2 j and 2 j + 1; every level is padded to an even number of entries with
+// k < 0 records, level l starts at entry level_off[l], the last level (`top`) has one entry.
+struct InstanceBuildArgs
+{
+    const float* descs;  // CapInstanceDesc records, 16 words each (device)
+    uint32_t     n;
+    double       blo[3], bhi[3];  // the object-space box every reported hit point lies in (scene bounds + the build's padding)
+    float4*      rec;
+    float4*      box;
+    float4*      tlas;
+    uint32_t*    keys[2];
+    uint32_t*    vals[2];
+    uint32_t*    hist;
+    uint32_t*    scan;
+    uint32_t*    misc;  // 8 words: 6 ordered-uint bounds of the live boxes' centres, the inert count, -
+};
+constexpr uint32_t kTlasMaxLevels = 25;  // n <= 2^24: levels 0 .. 24
+// level_off[0 .. top] and the total number of entries for n instances; returns top
+uint32_t tlas_layout(uint32_t n, uint32_t level_off[kTlasMaxLevels], uint32_t* total);
+void     launch_instances_build(hipStream_t stream, const InstanceBuildArgs& a);
+struct TlasDev
+{
+    const float4*   rec;
+    const float4*   tlas;
+    const uint32_t* level_off;  // device copy of tlas_layout's table
+    uint32_t        top;
+};
+// mode 0: closest, 1: first accepted hit, 2: occlusion.  q.out as the other queries'; inst_out (closest / first only) may be NULL.
+// f.tri_mask NULL: no per-mesh masks.  Always the binary tree below an instance (DESIGN.md "Instances"); depth = its CapBvhInfo::max_depth.
+void launch_query_instances(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const TlasDev& tl, const RayFilter& f, int mode, uint32_t* inst_out,
+                            uint32_t depth);
+
 // ---- shade ----
 struct ShadeArgs
 {
@@ -231,6 +268,10 @@ struct BvhBuildArgs
 size_t bvh_radix_blocks(uint32_t n);
 void   launch_bvh_build(hipStream_t stream, const BvhBuildArgs& a);
 int    launch_bvh_sort(hipStream_t stream, const BvhBuildArgs& a);  // setup + Morton order only: a.keys[r] / a.vals[r] sorted, returns r
+// the build's radix sort alone (also the instance table's, instance.hip): n (key, value) pairs sorted by key, stable; the result is
+// keys[r] / vals[r] for the returned r.  hist: 256 * bvh_radix_blocks(n) words, scan: bvh_radix_scan_words(n) words of scratch.
+size_t bvh_radix_scan_words(uint32_t n);
+int    launch_radix_sort_pairs(hipStream_t stream, uint32_t* const keys[2], uint32_t* const vals[2], uint32_t n, uint32_t* hist, uint32_t* scan);
 // Agglomerative build with a surface-area distance over the Morton order (ploc.hip); same outputs as launch_bvh_build,
 // incl. the subtree counts in a.keys[1].  boxes: 4 * tri_count float4; ints: 3 * tri_count + 4 words.  Returns 0 on success.
 struct PlocScratch

@@ -166,6 +166,10 @@ struct CapContext
     DevBuf<uint32_t> query_work, query_defer; // cap_trace_rays / cap_trace_occlusion: chunk and hand-over counters, rays handed to the binary tree
     DevBuf<uint8_t>  tri_mask;                // cap_scene_set_instance_masks: each triangle's mesh mask, by global triangle id
     bool             tri_mask_on = false;     // a mask table is installed (some mask differs from 0xFF)
+    // instance table and top-level tree (cap_instances_set, instance.hip); inst_count = 0: no table
+    DevBuf<float4>   inst_desc, inst_rec, inst_box, inst_tlas;
+    DevBuf<uint32_t> inst_keys[2], inst_vals[2], inst_hist, inst_scan, inst_misc, inst_level_off;
+    uint32_t         inst_count = 0, inst_top = 0, inst_nodes = 0;
     DevBuf<float4>   fan_pairs, fan_singles;  // exhaustive path: fan-pair records (5 float4) and the unpaired triangles (4 float4)
     uint32_t         fan_pair_count = 0, fan_single_count = 0;
     DevBuf<float4>   fan_pairs_nee;           // the pair records again, potential occluders of next-event rays first (update_nee_pairs)
@@ -709,6 +713,7 @@ int cap_scene_upload(CapContext* c, const float* positions, const float* normals
     c->positions_host_stale = false;
     c->lane1_failed_paths = 0;  // another scene, other buffers: a second batch lane that did not fit before may fit now
     c->tri_mask_on = false;     // instance masks belong to the previous scene's meshes
+    c->inst_count  = 0;         // ... and the instance table to its trees
     return CAP_OK;
 }
 
@@ -1079,6 +1084,30 @@ int cap_materials_upload(CapContext* c, const CapMaterial* materials, uint32_t m
     return CAP_OK;
 }
 
+// World boxes and top-level tree of the installed instance table from the kept descriptors and the current scene bounds: what
+// cap_instances_set, cap_bvh_build and cap_bvh_refit share.  Enqueues on the context stream; nothing when no table is installed.
+static int instances_rebuild(CapContext* c)
+{
+    const uint32_t n = c->inst_count;
+    if (n == 0) return CAP_OK;
+    InstanceBuildArgs a{};
+    a.descs = reinterpret_cast<const float*>(c->inst_desc.p), a.n = n;
+    // the object box: every point the triangle test can report lies in a leaf box, the triangle's box padded by
+    // 1e-5 max(1, |coordinate|) (bvh.hip k_refit); twice that around the scene bounds, in double
+    for (int k = 0; k < 3; ++k)
+    {
+        const double lo = c->bvh_info.bounds_lo[k], hi = c->bvh_info.bounds_hi[k];
+        const double pad = 2e-5 * std::max(1.0, std::max(std::fabs(lo), std::fabs(hi)));
+        a.blo[k] = lo - pad, a.bhi[k] = hi + pad;
+    }
+    a.rec = c->inst_rec.p, a.box = c->inst_box.p, a.tlas = c->inst_tlas.p;
+    a.keys[0] = c->inst_keys[0].p, a.keys[1] = c->inst_keys[1].p, a.vals[0] = c->inst_vals[0].p, a.vals[1] = c->inst_vals[1].p;
+    a.hist = c->inst_hist.p, a.scan = c->inst_scan.p, a.misc = c->inst_misc.p;
+    launch_instances_build(c->stream, a);
+    HIP_TRY(hipGetLastError());
+    return CAP_OK;
+}
+
 int cap_bvh_build(CapContext* c)
 {
     if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_build: ctx is NULL");
@@ -1228,7 +1257,8 @@ int cap_bvh_build(CapContext* c)
     c->bvh_ready          = true;
     c->bvh_stale          = false;
     c->visits_built_known = false;  // the first refit measures the boxes this build leaves
-    return update_nee_pairs(c);
+    if (const int rc = update_nee_pairs(c)) return rc;
+    return instances_rebuild(c);  // (nothing without a table)
 }
 
 int cap_scene_update_vertices(CapContext* c, const float* positions, const float* normals, const float* texcoords, uint32_t flags)
@@ -1324,6 +1354,7 @@ int cap_bvh_refit(CapContext* c, CapRefitInfo* out)
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (!c->visits_built_known) c->refit_visits_built = v[1], c->visits_built_known = true;
     c->bvh_stale = false;
+    if (const int rc = instances_rebuild(c)) return rc;  // world boxes and TLAS from the new bounds (nothing without a table)
     if (out)
     {
         out->ms                         = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
@@ -2364,6 +2395,143 @@ int cap_trace_rays_multi_ex(CapContext* c, const CapRayDesc* device_rays, uint64
                             uint32_t multi_flags, const CapTraceOptions* options)
 {
     return trace_multi(c, "cap_trace_rays_multi_ex", device_rays, n, k, device_hits, device_counts, multi_flags, options);
+}
+
+// ---- instanced ray queries (instance.hip) ----
+int cap_instances_set(CapContext* c, const CapInstanceDesc* descs, uint32_t count, uint32_t flags, CapInstancesInfo* out)
+{
+    static_assert(sizeof(CapInstanceDesc) == 64, "CapInstanceDesc is 16 words");
+    const char* what = "cap_instances_set";
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (flags & ~(uint32_t)CAP_INSTANCES_DEVICE) return fail(CAP_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (count > CAP_INSTANCE_MAX_COUNT) return fail(CAP_ERR_INVALID_ARG, "%s: %u instances exceed CAP_INSTANCE_MAX_COUNT (%u)", what, count, CAP_INSTANCE_MAX_COUNT);
+    if (count && !descs) return fail(CAP_ERR_INVALID_ARG, "%s: descs is NULL", what);
+    const bool device = (flags & CAP_INSTANCES_DEVICE) != 0;
+    if (!device)
+        for (uint32_t i = 0; i < count; ++i)
+            if (descs[i].reserved[0] | descs[i].reserved[1] | descs[i].reserved[2])
+                return fail(CAP_ERR_INVALID_ARG, "%s: descs[%u].reserved must be 0", what, i);
+    if (const int rc = query_state(c, what)) return rc;
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(c->device));
+    if (device && count)
+    {
+        if ((uintptr_t)descs & 3u) return fail(CAP_ERR_INVALID_ARG, "%s: descs is not 4-byte aligned", what);
+        hipPointerAttribute_t at{};
+        const hipError_t      e = hipPointerGetAttributes(&at, descs);
+        if (e != hipSuccess) (void)hipGetLastError();  // (an unknown pointer is the caller's error, not a sticky one)
+        if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != c->device)
+            return fail(CAP_ERR_INVALID_ARG, "%s: descs is not device memory of device %d", what, c->device);
+    }
+    if (count == 0)
+    {
+        c->inst_count = 0;  // host state: queries already enqueued keep the table they were given
+        if (out) *out = CapInstancesInfo{};
+        return CAP_OK;
+    }
+    uint32_t       off[kTlasMaxLevels], total = 0;
+    const uint32_t top = tlas_layout(count, off, &total);
+    if (c->inst_desc.n < 4 * (size_t)count || c->inst_misc.n < 8)
+    {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (grown buffers replace ones an earlier query may still be reading)
+        HIP_TRY(c->inst_desc.ensure(4 * (size_t)count));
+        HIP_TRY(c->inst_rec.ensure(4 * (size_t)count));
+        HIP_TRY(c->inst_box.ensure(2 * (size_t)count));
+        HIP_TRY(c->inst_tlas.ensure(2 * ((size_t)count + (size_t)count + 2 * kTlasMaxLevels + 2)));
+        for (int k = 0; k < 2; ++k)
+        {
+            HIP_TRY(c->inst_keys[k].ensure(count));
+            HIP_TRY(c->inst_vals[k].ensure(count));
+        }
+        HIP_TRY(c->inst_hist.ensure(256 * bvh_radix_blocks(count)));
+        HIP_TRY(c->inst_scan.ensure(bvh_radix_scan_words(count) + 1));
+        HIP_TRY(c->inst_misc.ensure(8));
+        HIP_TRY(c->inst_level_off.ensure(kTlasMaxLevels + 1));
+    }
+    if ((size_t)total * 2 > c->inst_tlas.n) return fail(CAP_ERR_HIP, "%s: top-level tree of %u entries exceeds its buffer", what, total);
+    // ordered on the context stream behind every query enqueued
+    HIP_TRY(hipMemcpyAsync(c->inst_desc.p, descs, sizeof(CapInstanceDesc) * (size_t)count, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync(c->inst_level_off.p, off, sizeof(uint32_t) * (top + 1), hipMemcpyHostToDevice, c->stream));
+    c->inst_count = count, c->inst_top = top, c->inst_nodes = total - (count + (count & 1u));
+    if (const int rc = instances_rebuild(c))
+    {
+        c->inst_count = 0;
+        return rc;
+    }
+    uint32_t inert = 0;
+    if (out) HIP_TRY(hipMemcpyAsync(&inert, c->inst_misc.p + 6, sizeof(inert), hipMemcpyDeviceToHost, c->stream));
+    if (out || !device) HIP_TRY(hipStreamSynchronize(c->stream));  // host descriptors and `off` may go once the call returns
+    if (out)
+    {
+        out->count = count, out->inert = inert, out->tlas_nodes = c->inst_nodes, out->tlas_depth = top + 1;
+        out->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return CAP_OK;
+}
+
+int cap_instances_readback(CapContext* c, float* world_to_object, float* world_boxes)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_instances_readback: ctx is NULL");
+    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "cap_instances_readback: no instance table installed");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t n = c->inst_count;
+    std::vector<float> rec(16 * n), box(8 * n);
+    HIP_TRY(hipMemcpy(rec.data(), c->inst_rec.p, sizeof(float) * rec.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(box.data(), c->inst_box.p, sizeof(float) * box.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i)
+    {
+        if (world_to_object) std::copy(rec.begin() + 16 * i, rec.begin() + 16 * i + 12, world_to_object + 12 * i);
+        if (world_boxes)
+            for (int k = 0; k < 3; ++k) world_boxes[6 * i + k] = box[8 * i + k], world_boxes[6 * i + 3 + k] = box[8 * i + 4 + k];
+    }
+    return CAP_OK;
+}
+
+namespace
+{
+int trace_instances(CapContext* c, const char* what, const CapRayDesc* rays, uint64_t n, void* out, size_t out_stride, uint32_t* inst, bool any,
+                    const CapTraceOptions* options)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    QueryFilter flt;
+    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
+    if (const int rc = query_state(c, what)) return rc;
+    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
+    if (n == 0) return CAP_OK;
+    if (!rays || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    const uintptr_t r0 = (uintptr_t)rays, o0 = (uintptr_t)out, i0 = (uintptr_t)inst;
+    if (((r0 | o0) & 15u) || (i0 & 3u)) return fail(CAP_ERR_INVALID_ARG, "%s: rays and output must be 16-byte aligned, instances 4-byte", what);
+    if (n > (UINTPTR_MAX - r0) / sizeof(CapRayDesc) || n > (UINTPTR_MAX - o0) / out_stride || (inst && n > (UINTPTR_MAX - i0) / sizeof(uint32_t)))
+        return fail(CAP_ERR_INVALID_ARG, "%s: %llu rays exceed the address space", what, (unsigned long long)n);
+    const uint64_t r_bytes = n * sizeof(CapRayDesc), o_bytes = n * out_stride, i_bytes = inst ? n * sizeof(uint32_t) : 0;
+    if (ranges_overlap(r0, r_bytes, o0, o_bytes) || ranges_overlap(r0, r_bytes, i0, i_bytes) || ranges_overlap(o0, o_bytes, i0, i_bytes))
+        return fail(CAP_ERR_INVALID_ARG, "%s: the ray and output ranges overlap", what);
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run)) return rc;
+    const TlasDev tl{c->inst_rec.p, c->inst_tlas.p, c->inst_level_off.p, c->inst_top};
+    const int     mode = any ? 2 : flt.first_hit ? 1 : 0;
+    for (uint64_t done = 0; done < n; done += run.per)
+    {
+        QueryArgs q = query_args(run, rays, n, done);
+        q.out       = static_cast<uint8_t*>(out) + done * out_stride;
+        launch_query_instances(run.cfg, run.bvh, q, tl, flt.f, mode, inst ? inst + done : nullptr, c->bvh_info.max_depth);
+        if (run.traced(any ? "k_query_inst<any>" : "k_query_inst<closest>", done) != CAP_OK) return CAP_ERR_HIP;
+    }
+    return CAP_OK;
+}
+}  // namespace
+
+int cap_trace_instances(CapContext* c, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, uint32_t* device_instances,
+                        const CapTraceOptions* options)
+{
+    return trace_instances(c, "cap_trace_instances", device_rays, n, device_hits, sizeof(CapHit), device_instances, false, options);
+}
+
+int cap_trace_instances_occlusion(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded, const CapTraceOptions* options)
+{
+    return trace_instances(c, "cap_trace_instances_occlusion", device_rays, n, device_occluded, sizeof(uint32_t), nullptr, true, options);
 }
 
 void cap_post_settings_default(CapPostSettings* out)

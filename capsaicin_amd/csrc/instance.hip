@@ -1,0 +1,489 @@
+// instance.hip — instanced ray queries (cap_instances_set, cap_trace_instances, cap_trace_instances_occlusion), gfx950.
+//
+// One bottom-level structure -- the uploaded scene and its binary tree, read as object space -- and a table of N instances of it, each
+// with an object-to-world transform and a mask.  This file holds the per-instance setup (inverse, conditioning, world box: fp64 on the
+// device, so device descriptors never travel to the host), the top-level tree over the world boxes, and the two-level query kernels.
+//
+// Hit set (include/capsaicin_hip.h): defined from the STORED W = fl32(inverse(M)) and the rounded object-space ray
+// o' = fl(W o + W_t), d' = fl(W d) alone; the closest record is the minimum in (t, instance, triangle) order.  Boxes never decide:
+//   * below an instance the walk is the binary tree's with `slab` on the object-space ray: the walk k_query_binary_f does on a
+//     caller's ray, conservative for the ray it is given wherever its origin lies.  (The wide view's padding assumes origins within
+//     4 M of the scene, query.hip; an object-space origin is usually far outside that, so the wide view is not used here.)
+//   * the top level sees the WORLD ray, which is not the image of the rounded object-space ray.  With A = inverse(W) (exact), the image
+//     of the object-space point o' + t d' is  o + t d + A (do + t dd),  do, dd the rounding errors of the twelve dot products:
+//       |do| <= g4 (|W| |o| + |W_t|),  |dd| <= g3 |W| |d|   (g_k = k eps / (1 - k eps), eps = 2^-24; row-sum norms throughout)
+//     so the world ray passes within  e(t) <= g4 kappa (|o| + t |d|) + g4 |A| |W_t|,  kappa = |A| |W|,  of the image of every
+//     object-space point it reports a hit at.  Such a point lies in the object box B (scene bounds + twice the build's leaf padding,
+//     context.hip), its image in the box of A(B)'s corners, so |o + t d| <= X + e(t), X the largest |coordinate| of that box, and
+//     t |d| <= |o| + X + e(t):   e(t) <= (g4 kappa (2 |o| + X) + g4 |A| |W_t|) / (1 - g4 kappa).
+//     The part that does not depend on the ray goes into the stored box (k_instance_setup: pad = c eps (kappa X + |A| |W_t|) + 4 eps X,
+//     then rounded outwards), the part that does into tlas_slab: every box is inflated by k |o| per ray, k = 2 c eps kappa the
+//     largest of its subtree.  c = kInstSlack = 32, eight times g4 / eps: the rest covers the float evaluation of the inflated
+//     planes (2 eps (X + k |o|)), 1 / (1 - g4 kappa) <= 1.001 and the distance-proportional error of the triangle test itself, for
+//     kappa <= CAP_INSTANCE_MAX_CONDITION = 4096, the domain of the proof; an instance beyond it is inert.  The interval test keeps
+//     the binary tree's relative slack (4e-7 >= 6 eps: one subtraction, one rounded reciprocal, one product per plane).
+#include "cap_kernels.h"
+#include "cap_trace.h"
+
+#include "../../include/capsaicin_hip.h"
+
+namespace cap
+{
+namespace
+{
+constexpr double kInstEps   = 5.9604644775390625e-8;  // 2^-24
+constexpr double kInstSlack = 32.0;
+
+__device__ __forceinline__ uint32_t inst_float_to_ordered(float f)
+{
+    const uint32_t u = f2u(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float inst_ordered_to_float(uint32_t o) { return u2f((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+__device__ __forceinline__ bool  finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }
+__device__ __forceinline__ bool  finite_f(float x) { return fabsf(x) <= 3.40282347e38f; }
+
+// inverse of the affine map m (row-major 3x4) in double; false when it is singular or the result is not finite
+__device__ __forceinline__ bool invert_affine(const double m[12], double w[12])
+{
+    const double c00 = m[5] * m[10] - m[6] * m[9], c01 = m[6] * m[8] - m[4] * m[10], c02 = m[4] * m[9] - m[5] * m[8];
+    const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
+    if (!(fabs(det) > 0.0) || !finite_d(det)) return false;
+    const double id = 1.0 / det;
+    w[0] = c00 * id, w[1] = (m[2] * m[9] - m[1] * m[10]) * id, w[2] = (m[1] * m[6] - m[2] * m[5]) * id;
+    w[4] = c01 * id, w[5] = (m[0] * m[10] - m[2] * m[8]) * id, w[6] = (m[2] * m[4] - m[0] * m[6]) * id;
+    w[8] = c02 * id, w[9] = (m[1] * m[8] - m[0] * m[9]) * id, w[10] = (m[0] * m[5] - m[1] * m[4]) * id;
+    bool ok = true;
+    for (int r = 0; r < 3; ++r)
+    {
+        w[4 * r + 3] = -(w[4 * r] * m[3] + w[4 * r + 1] * m[7] + w[4 * r + 2] * m[11]);
+        for (int k = 0; k < 4; ++k) ok = ok && finite_d(w[4 * r + k]);
+    }
+    return ok;
+}
+__device__ __forceinline__ double norm_inf3(const double m[12])
+{
+    double n = 0.0;
+    for (int r = 0; r < 3; ++r) n = fmax(n, fabs(m[4 * r]) + fabs(m[4 * r + 1]) + fabs(m[4 * r + 2]));
+    return n;
+}
+
+// Per instance: W = fl32(inverse(M)), A = inverse(W), kappa, the inert decision, the padded world box and its inflation factor.
+__global__ __launch_bounds__(kBlock) void k_instance_setup(InstanceBuildArgs a)
+{
+    float    clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    uint32_t inert = 0;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += gridDim.x * kBlock)
+    {
+        const float* d = a.descs + 16 * (size_t)i;
+        double       m[12], w[12], wd[12], A[12];
+        bool         live = true;
+        for (int k = 0; k < 12; ++k) m[k] = (double)d[k], live = live && finite_d(m[k]);
+        const uint32_t mask = f2u(d[12]) & 0xFFu;
+        live                = live && invert_affine(m, w);
+        float wf[12];
+        for (int k = 0; k < 12; ++k) wf[k] = live ? (float)w[k] : 0.0f, wd[k] = (double)wf[k], live = live && finite_f(wf[k]);
+        live               = live && invert_affine(wd, A);
+        const double nA    = live ? norm_inf3(A) : 0.0;
+        const double kappa = nA * norm_inf3(wd);
+        live               = live && kappa <= CAP_INSTANCE_MAX_CONDITION;
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, kf = -1.0f;
+        if (live)
+        {
+            double wlo[3] = {1e308, 1e308, 1e308}, whi[3] = {-1e308, -1e308, -1e308};
+            for (int c = 0; c < 8; ++c)
+            {
+                const double p[3] = {(c & 1) ? a.bhi[0] : a.blo[0], (c & 2) ? a.bhi[1] : a.blo[1], (c & 4) ? a.bhi[2] : a.blo[2]};
+                for (int r = 0; r < 3; ++r)
+                {
+                    const double x = A[4 * r] * p[0] + A[4 * r + 1] * p[1] + A[4 * r + 2] * p[2] + A[4 * r + 3];
+                    wlo[r] = fmin(wlo[r], x), whi[r] = fmax(whi[r], x);
+                }
+            }
+            double X = 0.0;
+            for (int r = 0; r < 3; ++r) X = fmax(X, fmax(fabs(wlo[r]), fabs(whi[r])));
+            const double wt  = fmax(fabs(wd[3]), fmax(fabs(wd[7]), fabs(wd[11])));
+            const double pad = kInstSlack * kInstEps * (kappa * X + nA * wt) + 4.0 * kInstEps * X;
+            for (int r = 0; r < 3; ++r)
+            {
+                // one ulp outwards of the rounded plane: the stored box contains the padded one
+                lo[r] = nextafterf((float)(wlo[r] - pad), -INFINITY), hi[r] = nextafterf((float)(whi[r] + pad), INFINITY);
+                live  = live && finite_f(lo[r]) && finite_f(hi[r]);
+            }
+            kf = (float)(2.0 * kInstSlack * kInstEps * kappa * 1.000001);
+        }
+        if (!live)
+        {
+            for (int k = 0; k < 12; ++k) wf[k] = 0.0f;
+            for (int r = 0; r < 3; ++r) lo[r] = INFINITY, hi[r] = -INFINITY;
+            kf = -1.0f;
+            ++inert;
+        }
+        else
+            for (int r = 0; r < 3; ++r)
+            {
+                const float c = (lo[r] + hi[r]) * 0.5f;
+                if (finite_f(c)) clo[r] = fminf(clo[r], c), chi[r] = fmaxf(chi[r], c);
+            }
+        a.rec[4 * (size_t)i + 0] = make_float4(wf[0], wf[1], wf[2], wf[3]);
+        a.rec[4 * (size_t)i + 1] = make_float4(wf[4], wf[5], wf[6], wf[7]);
+        a.rec[4 * (size_t)i + 2] = make_float4(wf[8], wf[9], wf[10], wf[11]);
+        a.rec[4 * (size_t)i + 3] = make_float4(u2f(live ? mask : 0u), 0.f, 0.f, 0.f);
+        a.box[2 * (size_t)i + 0] = make_float4(lo[0], lo[1], lo[2], kf);
+        a.box[2 * (size_t)i + 1] = make_float4(hi[0], hi[1], hi[2], u2f(i));
+    }
+    // bounds of the live boxes' centres (the Morton grid) and the inert count: one atomic per wave and word
+    for (int r = 0; r < 3; ++r)
+    {
+        float l = clo[r], h = chi[r];
+        for (int off = 32; off > 0; off >>= 1) l = fminf(l, __shfl_down(l, off)), h = fmaxf(h, __shfl_down(h, off));
+        if ((threadIdx.x & 63u) == 0)
+        {
+            if (l != INFINITY) atomicMin(&a.misc[r], inst_float_to_ordered(l));
+            if (h != -INFINITY) atomicMax(&a.misc[3 + r], inst_float_to_ordered(h));
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) inert += (uint32_t)__shfl_down((int)inert, off);
+    if ((threadIdx.x & 63u) == 0 && inert) atomicAdd(&a.misc[6], inert);
+}
+
+__device__ __forceinline__ uint32_t inst_expand_bits10(uint32_t v)
+{
+    v = (v * 0x00010001u) & 0xFF0000FFu;
+    v = (v * 0x00000101u) & 0x0F00F00Fu;
+    v = (v * 0x00000011u) & 0xC30C30C3u;
+    v = (v * 0x00000005u) & 0x49249249u;
+    return v;
+}
+
+// 30-bit Morton code of each live box's centre; inert instances sort behind every live one
+__global__ __launch_bounds__(kBlock) void k_instance_morton(InstanceBuildArgs a)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float4 lo = a.box[2 * (size_t)i], hi = a.box[2 * (size_t)i + 1];
+    uint32_t     key = 0xFFFFFFFFu;
+    if (lo.w >= 0.0f)
+    {
+        const float c[3] = {(lo.x + hi.x) * 0.5f, (lo.y + hi.y) * 0.5f, (lo.z + hi.z) * 0.5f};
+        uint32_t    q[3];
+        // one cell size for the three axes (the largest extent): instances on a plane or a line -- a forest, a street -- are ordered
+        // along the axes they spread over, not by the jitter across them
+        float ext = 0.0f;
+        for (int k = 0; k < 3; ++k) ext = fmaxf(ext, inst_ordered_to_float(a.misc[3 + k]) - inst_ordered_to_float(a.misc[k]));
+        for (int k = 0; k < 3; ++k)
+        {
+            const float n = ext > 0.0f && finite_f(ext) ? (c[k] - inst_ordered_to_float(a.misc[k])) / ext : 0.0f;
+            q[k]          = (uint32_t)fminf(fmaxf(n * 1024.0f, 0.0f), 1023.0f);
+        }
+        key = (inst_expand_bits10(q[0]) << 2) | (inst_expand_bits10(q[1]) << 1) | inst_expand_bits10(q[2]);
+    }
+    a.keys[0][i] = key;
+    a.vals[0][i] = i;
+}
+
+__device__ __forceinline__ void tlas_store_empty(float4* e)
+{
+    e[0] = make_float4(INFINITY, INFINITY, INFINITY, -1.0f);
+    e[1] = make_float4(-INFINITY, -INFINITY, -INFINITY, u2f(kInvalidId));
+}
+
+// level 0: the instances' box records in sorted order (order == NULL: as they are), padded to an even count
+__global__ __launch_bounds__(kBlock) void k_tlas_leaves(const float4* box, const uint32_t* order, uint32_t n, float4* level0)
+{
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n + (n & 1u)) return;
+    if (j >= n)
+    {
+        tlas_store_empty(level0 + 2 * (size_t)j);
+        return;
+    }
+    const uint32_t i = order ? order[j] : j;
+    level0[2 * (size_t)j] = box[2 * (size_t)i], level0[2 * (size_t)j + 1] = box[2 * (size_t)i + 1];
+}
+
+// one level from the one below: entry j = union of entries 2 j and 2 j + 1 (records with k < 0 hold nothing), padded to an even count
+__global__ __launch_bounds__(kBlock) void k_tlas_level(const float4* src, uint32_t n_src, float4* dst, uint32_t n_dst)
+{
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n_dst + (n_dst & 1u)) return;
+    if (j >= n_dst)
+    {
+        tlas_store_empty(dst + 2 * (size_t)j);
+        return;
+    }
+    // (the level below is padded to an even count: entry 2 j + 1 exists)
+    const float4 a0 = src[4 * (size_t)j], a1 = src[4 * (size_t)j + 1], b0 = src[4 * (size_t)j + 2], b1 = src[4 * (size_t)j + 3];
+    const bool   va = a0.w >= 0.0f, vb = b0.w >= 0.0f && 2 * j + 1 < n_src + (n_src & 1u);
+    float4       lo = make_float4(INFINITY, INFINITY, INFINITY, -1.0f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, u2f(kInvalidId));
+    if (va) lo = a0, hi = a1;
+    if (vb)
+    {
+        lo = make_float4(fminf(lo.x, b0.x), fminf(lo.y, b0.y), fminf(lo.z, b0.z), fmaxf(lo.w, b0.w));
+        hi = make_float4(fmaxf(hi.x, b1.x), fmaxf(hi.y, b1.y), fmaxf(hi.z, b1.z), u2f(kInvalidId));
+    }
+    hi.w = u2f(kInvalidId);
+    dst[2 * (size_t)j] = lo, dst[2 * (size_t)j + 1] = hi;
+}
+
+// The top level's box test: `slab` (cap_trace.h) on the box inflated by k |o| (see the head of this file), inclusive at both ends
+// like slab, with the relative slack applied to |exit| so that it widens for a negative exit as well.
+__device__ __forceinline__ bool tlas_slab(const Ray& r, const float4 lo, const float4 hi, float omax, float tfar, float& tnear_out)
+{
+    const float g  = lo.w * omax;
+    const float ax = ((lo.x - g) - r.o.x) * r.inv.x, bx = ((hi.x + g) - r.o.x) * r.inv.x;
+    const float ay = ((lo.y - g) - r.o.y) * r.inv.y, by = ((hi.y + g) - r.o.y) * r.inv.y;
+    const float az = ((lo.z - g) - r.o.z) * r.inv.z, bz = ((hi.z + g) - r.o.z) * r.inv.z;
+    const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), r.tmin));
+    const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tfar));
+    tnear_out      = tn;
+    return lo.w >= 0.0f && tn <= tf + 4e-7f * fabsf(tf);
+}
+
+// Closest (MODE 0) / first accepted (1) / occlusion (2) over the instances, one ray per lane.
+// Top level: no stack.  The tree is implicit, so a node is (level, index), its sibling index ^ 1 and its ancestors index >> levels;
+// `pending` holds one bit per level, set where the walk went to the nearer of two children that both passed and still owes the other.
+// Bottom level: k_query_binary_f's walk of the scene's binary tree on the object-space ray of the contract, with the shared best_t;
+// the lane's LDS slice is that walk's stack alone.
+// One loop, three kinds of step -- a top-level node, entering an instance (the ray transform: 12 FMAs and make_ray's divisions), a
+// bottom-level node or leaf -- so that the lanes of a wave that are at the top level advance while others are inside an instance.
+// The two instances under a level-1 node wait in (todo0, todo1), the nearer box first; each is entered only if its entry distance
+// still passes against best_t as it is then (the comparison tlas_slab made, with the bound the nearer instance left).
+constexpr int inst_blocks(int STACK) { return STACK <= 24 ? 6 : STACK <= 32 ? 4 : 2; }
+
+template <int STACK, int MODE>
+__global__ __launch_bounds__(kBlock, inst_blocks(STACK)) void k_query_inst(BvhDev bvh, QueryArgs q, TlasDev tl, RayFilter f, uint32_t* inst_out)
+{
+    __shared__ uint32_t lds_stack[STACK * kBlock];
+    __shared__ uint32_t lds_off[kTlasMaxLevels + 1];
+    uint32_t* const     stack = lds_stack + threadIdx.x;
+    if (threadIdx.x <= tl.top) lds_off[threadIdx.x] = tl.level_off[threadIdx.x];
+    __syncthreads();
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < q.n; j += gridDim.x * kBlock)
+    {
+        const float4 a = q.rays[2 * (size_t)j], b = q.rays[2 * (size_t)j + 1];
+        const Ray    rw   = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
+        const float  omax = fmaxf(fabsf(a.x), fmaxf(fabsf(a.y), fabsf(a.z)));
+        float        best_t = b.w, best_u = 0.f, best_v = 0.f;
+        uint32_t     best_gid = kInvalidId, best_inst = kInvalidId;
+        bool         found = false;  // MODE 1, 2: the query is over
+        // top level: the node whose two children (level - 1, 2 idx + {0, 1}) are tested next
+        uint32_t level = tl.top + 1u, idx = 0u, pending = 0u;
+        bool     top_done = false;
+        uint32_t todo0 = kInvalidId, todo1 = kInvalidId;
+        float    todo0_tn = 0.f, todo1_tn = 0.f;
+        // bottom level
+        bool     in_blas = false;
+        Ray      r       = rw;
+        uint32_t inst = 0u, imask = 0u;
+        int      node = 0, sp = 0;
+        bool     walk = query_ray_ok(a, b) && bvh.tri_count != 0u;
+        while (walk)
+        {
+            if (in_blas)
+            {
+                if (node >= 0)
+                {
+                    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2], q3 = bvh.nodes[4 * node + 3];
+                    float      tn0, tn1;
+                    const bool h0 = slab(r, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, best_t, tn0);
+                    const bool h1 = slab(r, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, best_t, tn1);
+                    const int  c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+                    if (h0 && h1)
+                    {
+                        const bool swap = tn1 < tn0;
+                        if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)(swap ? c0 : c1);
+                        node = swap ? c1 : c0;
+                        continue;
+                    }
+                    if (h0 || h1)
+                    {
+                        node = h0 ? c0 : c1;
+                        continue;
+                    }
+                }
+                else
+                {
+                    const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                    for (uint32_t leaf = first; leaf <= last && !found; ++leaf)
+                    {
+                        const float4 t0 = bvh.tris[4 * leaf + 0], t1 = bvh.tris[4 * leaf + 1], t2 = bvh.tris[4 * leaf + 2];
+                        float        t = 0.f, u = 0.f, v = 0.f;
+                        const bool   hit = MODE == 2 ? tri_occludes_cull(r, t0, t1, t2, f.cull_and, f.cull_xor)
+                                                     : tri_test_cull(r, t0, t1, t2, f.cull_and, f.cull_xor, t, u, v);
+                        if (!hit) continue;
+                        const uint32_t gid = f2u(bvh.tris[4 * leaf + 3].x);
+                        if (f.tri_mask && (f.tri_mask[gid] & imask) == 0u) continue;
+                        if (MODE != 0)
+                            best_t = t, best_u = u, best_v = v, best_gid = gid, best_inst = inst, found = true;
+                        else if (t < best_t || (t == best_t && (inst < best_inst || (inst == best_inst && gid < best_gid))))
+                            best_t = t, best_u = u, best_v = v, best_gid = gid, best_inst = inst;
+                    }
+                    if (found) break;
+                }
+                if (sp == 0)
+                    in_blas = false;
+                else
+                    node = (int)stack[(--sp) * kBlock];
+                continue;
+            }
+            if (todo0 != kInvalidId)
+            {
+                // enter an instance: mask, then the object-space ray of the contract
+                inst = todo0;
+                const bool still = todo0_tn <= best_t + 4e-7f * fabsf(best_t);  // tlas_slab's comparison against the bound as it is now
+                todo0 = todo1, todo0_tn = todo1_tn, todo1 = kInvalidId;
+                if (!still) continue;
+                const float4 w3 = tl.rec[4 * (size_t)inst + 3];
+                imask           = f2u(w3.x) & f.mask;  // desc.mask & inclusion: the mesh byte joins it per triangle
+                if (imask == 0u) continue;
+                const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
+                const v3     r0 = mk3(w0.x, w0.y, w0.z), r1 = mk3(w1.x, w1.y, w1.z), r2 = mk3(w2.x, w2.y, w2.z);
+                const v3     o  = mk3(dot3(r0, rw.o) + w0.w, dot3(r1, rw.o) + w1.w, dot3(r2, rw.o) + w2.w);
+                const v3     d  = mk3(dot3(r0, rw.d), dot3(r1, rw.d), dot3(r2, rw.d));
+                if (!query_ray_ok(make_float4(o.x, o.y, o.z, rw.tmin), make_float4(d.x, d.y, d.z, rw.tmax))) continue;
+                r       = make_ray(o, d, rw.tmin, rw.tmax);
+                node    = bvh.root, sp = 0;
+                in_blas = true;
+                continue;
+            }
+            if (top_done) break;
+            const float4* c = tl.tlas + 2 * (size_t)(lds_off[level - 1u] + 2u * idx);
+            const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
+            float         tn0, tn1;
+            const bool    h0 = tlas_slab(rw, lo0, hi0, omax, best_t, tn0), h1 = tlas_slab(rw, lo1, hi1, omax, best_t, tn1);
+            const bool    far_first = h0 && h1 && tn1 < tn0;
+            if (level > 1u)
+            {
+                if (h0 || h1)
+                {
+                    if (h0 && h1) pending |= 1u << (level - 1u);
+                    idx   = 2u * idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
+                    level = level - 1u;
+                    continue;
+                }
+            }
+            else if (h0 || h1)
+            {
+                // the children are instances: the nearer box first
+                const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
+                if (h0 && h1)
+                    todo0 = far_first ? i1 : i0, todo0_tn = far_first ? tn1 : tn0, todo1 = far_first ? i0 : i1, todo1_tn = far_first ? tn0 : tn1;
+                else
+                    todo0 = h0 ? i0 : i1, todo0_tn = h0 ? tn0 : tn1;
+            }
+            const uint32_t owed = pending >> level;
+            if (owed == 0u)
+            {
+                top_done = true;
+                continue;
+            }
+            const uint32_t up = (uint32_t)__builtin_ctz(owed);
+            idx     = (idx >> up) ^ 1u;
+            level   = level + up;
+            pending = pending & ~(1u << level);
+        }
+        if (MODE == 2)
+            static_cast<uint32_t*>(q.out)[j] = found ? 1u : 0u;
+        else
+        {
+            static_cast<float4*>(q.out)[j] = make_float4(best_t, best_u, best_v, u2f(best_gid));
+            if (inst_out) inst_out[j] = best_inst;
+        }
+    }
+}
+
+template <auto KERNEL>
+uint32_t inst_resident(const LaunchCfg& cfg, uint32_t want)  // (resident_grid of kernels.hip)
+{
+    static int per_cu = -1;
+    if (per_cu < 0)
+    {
+        int n  = 0;
+        per_cu = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, KERNEL, (int)kBlock, 0) == hipSuccess && n > 0) ? n : 0;
+    }
+    if (!cfg.cu_count || !per_cu) return want;
+    const uint32_t cap = cfg.cu_count * (uint32_t)per_cu;
+    return want < cap ? want : cap;
+}
+
+template <int STACK, int MODE>
+void launch_inst(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const TlasDev& tl, const RayFilter& f, uint32_t* inst_out)
+{
+    uint32_t want = (q.n + kBlock - 1) / kBlock;
+    if (want == 0) want = 1;
+    hipLaunchKernelGGL((k_query_inst<STACK, MODE>), dim3(inst_resident<k_query_inst<STACK, MODE>>(cfg, want)), dim3(kBlock), 0, cfg.stream, bvh, q, tl, f,
+                       inst_out);
+}
+}  // namespace
+
+uint32_t tlas_layout(uint32_t n, uint32_t level_off[kTlasMaxLevels], uint32_t* total)
+{
+    uint32_t level = 0, off = 0, cnt = n;
+    while (true)
+    {
+        level_off[level] = off;
+        off += cnt + (cnt & 1u);
+        if (cnt <= 1u) break;
+        cnt = (cnt + 1u) / 2u;
+        ++level;
+    }
+    if (total) *total = off;
+    return level;
+}
+
+void launch_instances_build(hipStream_t stream, const InstanceBuildArgs& a)
+{
+    const uint32_t n = a.n;
+    if (n == 0) return;
+    const uint32_t blocks = (n + kBlock - 1) / kBlock;
+    // bounds = (+inf x 3, -inf x 3) in the ordered encoding, inert count 0
+    const uint32_t init[8] = {0xFF800000u, 0xFF800000u, 0xFF800000u, 0x007FFFFFu, 0x007FFFFFu, 0x007FFFFFu, 0u, 0u};
+    (void)hipMemcpyAsync(a.misc, init, sizeof(init), hipMemcpyHostToDevice, stream);
+    hipLaunchKernelGGL(k_instance_setup, dim3(blocks < 1024u ? blocks : 1024u), dim3(kBlock), 0, stream, a);
+    const uint32_t* order = nullptr;
+    if (n > 2)  // (one or two instances are the two children of the walk's first step in any order)
+    {
+        hipLaunchKernelGGL(k_instance_morton, dim3(blocks), dim3(kBlock), 0, stream, a);
+        order = a.vals[launch_radix_sort_pairs(stream, a.keys, a.vals, n, a.hist, a.scan)];
+    }
+    uint32_t       off[kTlasMaxLevels];
+    const uint32_t top = tlas_layout(n, off, nullptr);
+    hipLaunchKernelGGL(k_tlas_leaves, dim3((n + 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a.box, order, n, a.tlas);
+    uint32_t cnt = n;
+    for (uint32_t l = 1; l <= top; ++l)
+    {
+        const uint32_t next = (cnt + 1u) / 2u;
+        hipLaunchKernelGGL(k_tlas_level, dim3((next + 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a.tlas + 2 * (size_t)off[l - 1], cnt,
+                           a.tlas + 2 * (size_t)off[l], next);
+        cnt = next;
+    }
+}
+
+void launch_query_instances(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const TlasDev& tl, const RayFilter& f, int mode, uint32_t* inst_out,
+                            uint32_t depth)
+{
+#define CAP_INST(S)                                                  \
+    if (mode == 2)                                                   \
+        launch_inst<S, 2>(cfg, bvh, q, tl, f, nullptr);              \
+    else if (mode == 1)                                              \
+        launch_inst<S, 1>(cfg, bvh, q, tl, f, inst_out);             \
+    else                                                             \
+        launch_inst<S, 0>(cfg, bvh, q, tl, f, inst_out);
+    // the bottom-level stack: the binary tree's depth bounds it; an instanced object is usually small, and a 24-entry slice lets six
+    // workgroups share a CU's LDS where the 32-entry one of the plain binary kernels lets four
+    if (depth <= 24 && cfg.stack_entries <= 32)
+    {
+        CAP_INST(24)
+    }
+    else if (cfg.stack_entries <= 32)
+    {
+        CAP_INST(32)
+    }
+    else
+    {
+        CAP_INST(64)
+    }
+#undef CAP_INST
+}
+}  // namespace cap

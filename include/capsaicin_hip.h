@@ -447,6 +447,71 @@ int cap_trace_occlusion_ex(CapContext* ctx, const CapRayDesc* device_rays, uint6
 int cap_trace_rays_multi_ex(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits,
                             uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options);
 
+/* ---- instanced ray queries: N transformed instances of the uploaded scene under a device-built top-level tree ----
+ * The uploaded scene and the trees cap_bvh_build makes of it are read as OBJECT space; cap_instances_set installs a table of N
+ * instances of it, each with an object-to-world transform and an 8-bit mask, and builds a top-level tree (TLAS) over the instances'
+ * world boxes on the device.  cap_trace_instances / cap_trace_instances_occlusion walk TLAS -> ray into object space -> the binary
+ * tree of the scene.  Nothing else changes: the plain cap_trace_rays* calls keep tracing the object-space scene, cap_render ignores
+ * the table (as it ignores the mesh masks).
+ *
+ * World-to-object.  Per instance the library computes W = fl32(inverse(M)) once, the inverse of the affine map taken in double and
+ * each of its twelve entries rounded once to binary32.  W as stored is part of the contract (cap_instances_readback returns it);
+ * everything below is defined from W, not from M.
+ * Object-space ray (the DXR rule: the direction is not normalised, so t means the same on both sides), row r of W:
+ *   o'_r = dot(W_r.xyz, o) + W_r.w      d'_r = dot(W_r.xyz, d)      dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x))
+ * with one rounded add; tmin and tmax unchanged.  An object-space ray that is degenerate by the queries' rule (a non-finite
+ * component, zero direction) has no hit in that instance.
+ * Hit set of a ray: the pairs (instance i, triangle g) with i not inert, g passing the closest (cap_trace_instances) or occlusion
+ * (cap_trace_instances_occlusion) triangle test against ray's object-space ray in instance i, and the filters.  The closest record
+ * is the minimum in (t, i, g) lexicographic order: the existing tie rule with the instance in front, so the answer depends on
+ * neither tree nor on the visiting order.  (u, v) are object-space barycentrics, `triangle` the global triangle id of the scene.
+ * Filters (CapTraceOptions): facing is decided in object space from det's sign exactly as in cap_trace_rays_ex and is NOT affected
+ * by the instance transform, a mirroring one included (the DXR rule).  A triangle of mesh m in instance i is a candidate iff
+ * desc[i].mask & mesh_mask[m] & instance_mask != 0 (instance_mask = 0 means 0xFF; mesh masks are 0xFF unless
+ * cap_scene_set_instance_masks set them).  So a caller can pack up to eight different objects into the scene as meshes with masks
+ * 1 << k and give each instance the bit of the object it shows.  CAP_RAY_FLAG_ACCEPT_FIRST_HIT on cap_trace_instances returns some
+ * member of the set, a miss exactly when it is empty.
+ * Inert instances.  An instance whose transform has a non-finite entry, is singular, whose inverse does not fit binary32, or whose
+ * condition number kappa = ||W^-1||_inf * ||W||_inf (3x3 parts, row-sum norms, W as stored) exceeds CAP_INSTANCE_MAX_CONDITION is
+ * INERT: never hit, counted in CapInstancesInfo::inert, not an error; decided on the device, the same for host and device
+ * descriptors.  Its read-back W is all zero and its box empty (lo = +inf, hi = -inf).  The bound is the domain in which the
+ * top-level boxes are proven conservative for the rounded object-space ray (DESIGN.md "Instances"); any transform with a 2-norm
+ * condition number up to CAP_INSTANCE_MAX_CONDITION / 3 is inside it. */
+#define CAP_INSTANCE_MAX_CONDITION 4096.0
+#define CAP_INSTANCE_MAX_COUNT (1u << 24) /* DXR's limit */
+typedef struct CapInstanceDesc /* 64 B */
+{
+    float    transform[12]; /* object-to-world, row-major 3x4 (rows of the rotation / scale part, translation in column 3) */
+    uint32_t mask;          /* InstanceMask, low 8 bits; 0 = never hit, as in DXR */
+    uint32_t reserved[3];   /* must be 0 */
+} CapInstanceDesc;
+enum
+{
+    CAP_INSTANCES_DEVICE = 1u << 0 /* descs is a device pointer on the context's GPU, read on the context stream; never copied to the host */
+};
+typedef struct CapInstancesInfo
+{
+    uint32_t count, inert, tlas_nodes, tlas_depth;
+    double   ms; /* host time of the call; includes the wait for the device only when the call waits (see below) */
+} CapInstancesInfo;
+/* Installs (or, called again, replaces) the table and builds the TLAS: the whole cost of a rigid-motion frame.  count = 0 removes
+ * the table; count <= CAP_INSTANCE_MAX_COUNT.  Needs a built tree: CAP_ERR_STATE before cap_bvh_build and while the trees are stale
+ * after cap_scene_update_vertices.  Host descriptors are copied before the call returns (the call waits for the stream) and are
+ * checked: non-zero reserved words are CAP_ERR_INVALID_ARG.  Device descriptors (4-byte aligned) are copied on the stream; the call
+ * is asynchronous unless `out` is given (the inert count is read back).  cap_scene_upload drops the table; cap_bvh_build and
+ * cap_bvh_refit keep the descriptors and rebuild world boxes and TLAS from the new scene bounds by the same routine;
+ * cap_scene_set_instance_masks does not touch it. */
+int cap_instances_set(CapContext* ctx, const CapInstanceDesc* descs, uint32_t count, uint32_t flags, CapInstancesInfo* out /* may be NULL */);
+/* host arrays, either may be NULL: W (12 floats per instance, row-major 3x4) and the padded world box (lo.xyz, hi.xyz) */
+int cap_instances_readback(CapContext* ctx, float* world_to_object, float* world_boxes);
+/* cap_trace_rays_ex / cap_trace_occlusion_ex in every convention (device pointers, 16-byte alignment of rays and hits, no overlap,
+ * asynchronous on the context stream, n above 2^24 split into launches, nothing written on an error); CAP_ERR_STATE without a
+ * table.  device_instances[i] (4-byte aligned, may be NULL) is the table index of ray i's hit, 0xFFFFFFFF on a miss. */
+int cap_trace_instances(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, uint32_t* device_instances,
+                        const CapTraceOptions* options /* may be NULL */);
+int cap_trace_instances_occlusion(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded,
+                                  const CapTraceOptions* options /* may be NULL */);
+
 /* ---- multi-GPU tile exchange (one gather of tile radiance at frame end) ---- */
 /* floats in this context's tile-ordered radiance buffer: max_tiles_per_shard * 64 * 4 (same on every shard) */
 int cap_tile_buffer_floats(CapContext* ctx, size_t* out_floats);
