@@ -162,7 +162,6 @@ struct CapContext
     DevBuf<uint32_t> wide_task, wide_alloc, wide_cnt;   // device collapse: binary node per wide node, allocation counters, per-level bases
     uint32_t         wide8_depth = 0, wide8_top = 0, wide8_nodes = 0;
     float            wide8_ms = 0.f;
-    DevBuf<uint32_t> stack_spill;             // traversal-stack entries beyond the LDS part, per thread of the persistent grid
     DevBuf<uint32_t> query_work, query_defer; // cap_trace_rays / cap_trace_occlusion: chunk and hand-over counters, rays handed to the binary tree
     DevBuf<uint8_t>  tri_mask;                // cap_scene_set_instance_masks: each triangle's mesh mask, by global triangle id
     bool             tri_mask_on = false;     // a mask table is installed (some mask differs from 0xFF)
@@ -199,7 +198,7 @@ struct CapContext
     SwitchTable   sw{};                    // A/B switches: environment at creation, then cap_debug_set(CAP_DEBUG_SWITCH_BASE + i)
     uint32_t      debug_capacity_div = 1;  // cap_debug_set(CAP_DEBUG_QUEUE_CAPACITY_DIV): tests of the append guard only
     uint32_t      debug_wide_depth_limit = 0;  // cap_debug_set(CAP_DEBUG_WIDE_DEPTH_LIMIT): pretend the wide kernels' stacks end here
-    bool          debug_fail_lane1 = false;    // cap_debug_set(CAP_DEBUG_FAIL_LANE1): the second working set "cannot be allocated"
+    bool          debug_fail_lane = false;     // cap_debug_set(CAP_DEBUG_FAIL_LANE1): the second working set "cannot be allocated"
     // The smallest second working set (paths = slots x padded pixels) whose allocation has failed since the last call that can free
     // memory: cap_render does not try that size or a larger one again (every call repeated ~28 GB of hipMalloc / hipFree).
     uint64_t      lane1_failed_paths = 0;
@@ -210,18 +209,19 @@ struct CapContext
     uint32_t      bvh_build_mode  = CAP_BVH_BUILD_AUTO;
 
     // wavefront state
-    DevBuf<float4>     hits, q_org[2], q_dir[2], q_thr[2], s_org, s_dir, s_con, pl_color, pl_direct, pl_albedo, aov_geo, aov_nd,
-        accum, image_tmp;
-    DevBuf<uint32_t>   counters;  // per batch: ext[0..D], shadow[0..D]
+    DevBuf<float4>     aov_geo, aov_nd, accum, image_tmp;
     DevBuf<uint64_t>   shaded_counter;
-    // Second working set for batches in flight beside the first (cap_render "two lanes"): queues, planes, counters and traversal
-    // spill slices of its own, on a stream of its own.  Lane 0 is the set above on `stream`; the LAST batch of a call always runs
-    // there, so everything that reads a finished frame's planes (AOV read-backs, the reconstruction chain) finds them where it did.
+    // A batch working set of cap_render: queues, planes, counters and a slice of traversal-stack spill, and the stream its batches
+    // run on.  There are two ("two lanes"), for batches in flight beside each other: lane[0] on the context's `stream`, lane[1] on
+    // `stream2` (both sized by ensure_lane).  Lane 0's spill area is the one cap_bvh_build allocates and every ray query uses.  The
+    // LAST batch of a call always runs on lane 0, so everything that reads a finished frame's planes finds them there (aov_planes).
     struct Lane
     {
+        hipStream_t      stream = nullptr;  // not owned: the context's `stream` (lane 0) or `stream2` (lane 1)
         DevBuf<float4>   hits, q_org[2], q_dir[2], q_thr[2], s_org, s_dir, s_con, pl_color, pl_direct, pl_albedo;
-        DevBuf<uint32_t> counters, stack_spill;
-    } lane1;
+        DevBuf<uint32_t> counters;     // per batch: ext[0..D], shadow[0..D]
+        DevBuf<uint32_t> stack_spill;  // traversal-stack entries beyond the LDS part, per thread of the persistent grid
+    } lane[2];
     hipStream_t stream2 = nullptr;
     hipEvent_t  lane_ev[2] = {nullptr, nullptr}, fork_ev = nullptr, join_ev = nullptr;
     // per-frame constants of a cap_render call: a ring of device buffers fed from pinned staging, so that a call need not wait
@@ -232,7 +232,6 @@ struct CapContext
     size_t             frames_pinned_n[kFrameRing] = {0, 0, 0, 0};
     hipEvent_t         frames_event[kFrameRing] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t           frames_next = 0;
-    uint32_t           slots_alloc = 0, bounces_alloc = 0;
     uint32_t           last_slots = 0;     // frame slots of the last batch rendered (AOV readback)
     bool               aov_valid = false;
     bool               aov_lowres = false;  // the AOV frame was rendered with CAP_RENDER_LOWRES_INDIRECT
@@ -257,15 +256,9 @@ struct CapContext
     std::vector<TimedSpan> spans;
     std::vector<std::array<hipEvent_t, 6>> post_marks;  // pass-boundary events of every cap_post_frame since the last sync
     std::vector<hipEvent_t> event_pool;
-    struct PendingCounters
-    {
-        std::vector<uint32_t> host;  // filled by an async copy
-        uint32_t              bounces;
-    };
     std::vector<uint32_t*> pinned_pool;
     std::vector<std::pair<uint32_t*, uint32_t>> pending;  // (pinned counters, bounces) per batch, read at sync
     uint64_t*              pinned_shaded = nullptr;
-    hipEvent_t             ev_begin = nullptr, ev_end = nullptr;
 };
 
 namespace
@@ -424,18 +417,19 @@ FrameConst frame_const(uint32_t frame_count, bool lowres_indirect)
     return f;
 }
 
-BvhDev bvh_dev(const CapContext* c)
+// the tree view of a launch whose traversal stacks spill into `lane`'s area
+BvhDev bvh_dev(const CapContext* c, const CapContext::Lane& lane)
 {
     BvhDev b{};
     b.nodes     = c->nodes.p;
     b.tris      = c->tris_sorted.p;
     b.tris_by_id = c->tri_raw.p;
-    b.stack_spill   = c->stack_spill.p;
-    b.spill_threads = (uint32_t)(c->stack_spill.n / kSpillEntries);
+    b.stack_spill   = lane.stack_spill.p;
+    b.spill_threads = (uint32_t)(lane.stack_spill.n / kSpillEntries);
     // A/B switch: the binary-tree kernels (also what runs if the 8-wide view's depth ever exceeds the pair stacks)
     const bool no_wide8 = c->sw.on(SW_NO_WIDE8);
     b.nodes8 = c->nodes8.p, b.tris8 = c->tris8.p;
-    b.wide8_ok  = !no_wide8 && c->stack_spill.p && c->wide8_nodes != 0 && c->wide8_depth <= wide8_stack_pairs() + 1u &&
+    b.wide8_ok  = !no_wide8 && lane.stack_spill.p && c->wide8_nodes != 0 && c->wide8_depth <= wide8_stack_pairs() + 1u &&
                  c->wide8_depth <= kWideLdsEntries / 2u + kSpillEntries / 2u + 1u &&
                  (c->debug_wide_depth_limit == 0u || c->wide8_depth <= c->debug_wide_depth_limit);
     b.wide8_top = c->wide8_top;
@@ -468,30 +462,46 @@ SceneDev scene_dev(const CapContext* c)
     return s;
 }
 
-int ensure_wavefront(CapContext* c, uint32_t slots, uint32_t bounces)
+// Element counts of one lane's working set for `slots` frame slots and `bounces` bounces: what ensure_lane allocates, and what
+// cap_render tests to learn whether a call grows a lane (growing frees the old buffers, so the streams are drained first)
+struct LaneSizes
 {
-    const size_t planes_np = (size_t)slots * c->screen.pixels_padded;
-    const size_t np        = planes_np + (size_t)kQueueClasses * 64;  // queue regions round up to whole chunks per class
-    HIP_TRY(c->hits.ensure(np));
-    for (int k = 0; k < 2; ++k)
-    {
-        HIP_TRY(c->q_org[k].ensure(np));
-        HIP_TRY(c->q_dir[k].ensure(np));
-        HIP_TRY(c->q_thr[k].ensure(np));
-    }
+    size_t planes, queues, rings, counters;
+};
+
+LaneSizes lane_sizes(const CapContext* c, uint32_t slots, uint32_t bounces)
+{
+    LaneSizes z;
+    z.planes = (size_t)slots * c->screen.pixels_padded;
+    z.queues = z.planes + (size_t)kQueueClasses * 64;  // queue regions round up to whole chunks per class
     // the shadow queue's memory also holds the fused kernels' per-wave survivor rings (ShadeArgs::wave_ring): 128 entries for
     // every wave of the largest persistent grid (8 workgroups per CU)
-    const size_t ring_np = (size_t)std::max(c->cu_count, 1) * 8 * (kBlock / 64) * 128;
-    HIP_TRY(c->s_org.ensure(std::max(np, ring_np)));
-    HIP_TRY(c->s_dir.ensure(np));
-    HIP_TRY(c->s_con.ensure(std::max(np, ring_np)));
-    HIP_TRY(c->pl_color.ensure(planes_np));
-    HIP_TRY(c->pl_direct.ensure(planes_np));
-    HIP_TRY(c->pl_albedo.ensure(planes_np));
+    z.rings = std::max(z.queues, (size_t)std::max(c->cu_count, 1) * 8 * (kBlock / 64) * 128);
+    // queue counters (ext + shadow share words) + chunk-grab counters of the fused and of the any-hit launch, per bounce
+    z.counters = (3 * (size_t)(bounces + 1) + 1) * kQueueClasses * kCounterStride;  // + 1: the camera rays' identity queue
+    return z;
+}
+
+bool lane_grows(const CapContext::Lane& L, const LaneSizes& z) { return L.pl_color.n < z.planes || L.counters.n < z.counters; }
+
+int ensure_lane(CapContext* c, CapContext::Lane& L, uint32_t slots, uint32_t bounces)
+{
+    const LaneSizes z = lane_sizes(c, slots, bounces);
+    for (DevBuf<float4>* b : {&L.hits, &L.q_org[0], &L.q_org[1], &L.q_dir[0], &L.q_dir[1], &L.q_thr[0], &L.q_thr[1], &L.s_dir})
+        HIP_TRY(b->ensure(z.queues));
+    for (DevBuf<float4>* b : {&L.s_org, &L.s_con}) HIP_TRY(b->ensure(z.rings));
+    for (DevBuf<float4>* b : {&L.pl_color, &L.pl_direct, &L.pl_albedo}) HIP_TRY(b->ensure(z.planes));
+    HIP_TRY(L.counters.ensure(z.counters));
+    // as much spill as lane 0, whose area cap_bvh_build allocates (for lane 0 itself: nothing to do)
+    if (c->lane[0].stack_spill.n) HIP_TRY(L.stack_spill.ensure(c->lane[0].stack_spill.n));
+    return CAP_OK;
+}
+
+// what a render needs beside its lanes: the AOV frame's geometry planes, the guard block, the accumulation buffer
+int ensure_frame_buffers(CapContext* c)
+{
     HIP_TRY(c->aov_geo.ensure(c->screen.pixels_padded));
     HIP_TRY(c->aov_nd.ensure(c->screen.pixels_padded));
-    // queue counters (ext + shadow share words) + chunk-grab counters of the fused and of the any-hit launch, per bounce
-    HIP_TRY(c->counters.ensure((3 * (size_t)(bounces + 1) + 1) * kQueueClasses * kCounterStride));  // + 1: the camera rays' identity queue
     if (!c->shaded_counter.p)
     {
         HIP_TRY(c->shaded_counter.ensure(kGuardWords));
@@ -506,28 +516,9 @@ int ensure_wavefront(CapContext* c, uint32_t slots, uint32_t bounces)
     return CAP_OK;
 }
 
-// the second lane's working set (same sizes as lane 0's), its stream and the events that order the two
-int ensure_lane1(CapContext* c, uint32_t slots, uint32_t bounces)
+// the second lane's stream and the events that order the two lanes
+int ensure_lane_streams(CapContext* c)
 {
-    CapContext::Lane& L = c->lane1;
-    const size_t planes_np = (size_t)slots * c->screen.pixels_padded;
-    const size_t np        = planes_np + (size_t)kQueueClasses * 64;
-    HIP_TRY(L.hits.ensure(np));
-    for (int k = 0; k < 2; ++k)
-    {
-        HIP_TRY(L.q_org[k].ensure(np));
-        HIP_TRY(L.q_dir[k].ensure(np));
-        HIP_TRY(L.q_thr[k].ensure(np));
-    }
-    const size_t ring_np = (size_t)std::max(c->cu_count, 1) * 8 * (kBlock / 64) * 128;
-    HIP_TRY(L.s_org.ensure(std::max(np, ring_np)));
-    HIP_TRY(L.s_dir.ensure(np));
-    HIP_TRY(L.s_con.ensure(std::max(np, ring_np)));
-    HIP_TRY(L.pl_color.ensure(planes_np));
-    HIP_TRY(L.pl_direct.ensure(planes_np));
-    HIP_TRY(L.pl_albedo.ensure(planes_np));
-    HIP_TRY(L.counters.ensure((3 * (size_t)(bounces + 1) + 1) * kQueueClasses * kCounterStride));
-    if (c->stack_spill.n) HIP_TRY(L.stack_spill.ensure(c->stack_spill.n));
     if (!c->stream2)
     {
         // (A/B switch: the second lane's stream priority -- streams of different priority never share a hardware queue)
@@ -536,9 +527,105 @@ int ensure_lane1(CapContext* c, uint32_t slots, uint32_t bounces)
         else
             HIP_TRY(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
     }
+    c->lane[1].stream = c->stream2;
     for (hipEvent_t* e : {&c->lane_ev[0], &c->lane_ev[1], &c->fork_ev, &c->join_ev})
         if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     return CAP_OK;
+}
+
+// How cap_render cuts a call into batches.
+struct BatchPolicy
+{
+    uint32_t slots;               // frame slots of a batch (the last one may fill fewer)
+    bool     two_lanes;           // consecutive batches alternate between the two lanes
+    bool     lane1_failed_before; // two_lanes, but a second working set of this size could not be allocated earlier
+};
+
+// Reads the context and changes nothing (it may ask the device how much memory is free).  tree_path: the render goes through the
+// tree kernels, not the small-scene fused ones.
+BatchPolicy batch_policy(const CapContext* c, uint32_t n_frames, uint32_t num_bounces, uint32_t flags, bool tree_path)
+{
+    const uint32_t Ppad = c->screen.pixels_padded;
+    // paths in flight per batch; measured on the headline workload (tools/batch_sweep.sh, end of round 2): 8 Mi 31.0 ms, 16 Mi 25.5,
+    // 32 Mi 22.1, 64 Mi 21.2, 128 Mi 21.1 per step -- every launch has a fixed cost (grid start, tables, tail) that fewer, larger
+    // batches amortise; 64 Mi paths are ~14 GB of queues and planes
+    uint64_t       budget = c->max_batch_paths ? c->max_batch_paths : (uint64_t)64 << 20;
+    if (!c->max_batch_paths && (uint64_t)n_frames * Ppad > budget)
+    {
+        // Twice that when the card has the room (round 6, docs/experiments.md (88)): the tree path has 27 launches per batch, most of
+        // them short, and gains 1.7 % (the 262 k hall at 128 spp: 92.1 -> 90.5 ms; round 4 measured 101.2 -> 99.4 and kept 64 Mi for
+        // its 14 GB per lane), the small-scene path 1.0 % (headline 20.22 -> 20.01 ms).  Taken when the working set is already that
+        // large or the device reports room for it with a margin -- 128 Mi paths are ~28 GB per lane of the card's 288, and the tree
+        // path runs two lanes; cap_set_batch_paths overrides either way.
+        const uint64_t big       = (uint64_t)128 << 20;
+        const uint64_t big_slots = std::max<uint64_t>(1, std::min<uint64_t>(big / std::max(1u, Ppad), kMaxFrameSlots));
+        bool           room      = c->lane[0].pl_color.n >= big_slots * Ppad && (!tree_path || c->lane[1].pl_color.n >= big_slots * Ppad);
+        if (!room)
+        {
+            size_t free_b = 0, total_b = 0;
+            room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 3u * big_slots * Ppad * 256u;  // ~208 B per path and lane
+        }
+        if (room) budget = big;
+    }
+    uint32_t       slots  = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(budget / std::max(1u, Ppad), kMaxFrameSlots));
+    slots                 = std::min(slots, n_frames);
+    // Two lanes (CapContext::Lane): consecutive batches alternate between two working sets on two streams, so that the tail of
+    // one batch's launch -- the last chunks, a workgroup at a time, with most of the chip idle -- is filled by the other batch's
+    // next launch instead of waiting for the stream's next kernel (measured with two contexts side by side, tools/dual_test.py:
+    // 21.0 -> 20.55 ms per step on the headline, 3.30 -> 3.05 ms for shard 0 of 8, 28.3 -> 27.1 ms on the 262 k scene).  A call
+    // that fits one batch is cut in two halves when the halves are still large.  Per-stage timers need one stream.
+    const bool no_two_lanes = c->sw.on(SW_NO_TWO_LANES);  // A/B switch
+    // Only on the tree path: its bounces are three launches each, and from the third bounce on they are short (the 262 k scene: 27
+    // launches per batch, the last 15 under 0.2 ms each) -- 28.3 -> 26.4 ms per 32 spp.  The small-scene path's nine long fused
+    // launches gain nothing measurable (20.45 -> 20.25 ms with the context's own stream, 20.56 -> 20.9 beside a torch stream).
+    bool two_lanes = !no_two_lanes && tree_path && c->bvh_info.stack_entries != 0 && !(flags & CAP_RENDER_GBUFFER_FEEDBACK) &&
+                     !(flags & CAP_RENDER_LOWRES_INDIRECT) && n_frames >= 2;
+    if (two_lanes && slots >= n_frames)
+    {
+        const uint64_t split_min = (uint64_t)c->sw.get(SW_LANE_SPLIT_MIN, (int64_t)4 << 20);  // A/B switch (shard 0 of 8 of the 262 k scene: 4.55 -> 4.35 ms with halves of 4 Mi paths)
+        if ((uint64_t)n_frames * Ppad >= split_min)
+            slots = (n_frames + 1) / 2;
+        else
+            two_lanes = false;
+    }
+    // (per-stage timers and launch tracing need one stream: the batches keep the size the two lanes gave them -- so that a stage-timed
+    // render launches what the plain one does -- and run one after the other on lane 0)
+    if ((flags & CAP_RENDER_STAGE_TIMERS) || c->sw.on(SW_TRACE_LAUNCHES)) two_lanes = false;
+    // (cap_render does not try a second working set of a size that has failed, or a larger one, again at once: see there)
+    const bool failed_before =
+        two_lanes && c->lane1_failed_paths && (uint64_t)slots * Ppad >= c->lane1_failed_paths && num_bounces >= c->lane1_failed_bounces;
+    return BatchPolicy{slots, two_lanes, failed_before};
+}
+
+// The AOV frame's tile-ordered planes (what CAP_RENDER_AOV leaves for read-backs and the reconstruction chain): the last frame slot
+// of the last batch.  The LAST batch of a cap_render call always runs on lane 0 (its lane is (n_batches - 1 - batch) & 1), so
+// they are lane 0's planes whichever lanes the call used.
+struct AovPlanes
+{
+    const float4 *color, *direct, *albedo;
+};
+
+AovPlanes aov_planes(const CapContext* c)
+{
+    const size_t off = (size_t)(c->last_slots ? c->last_slots - 1 : 0) * c->screen.pixels_padded;
+    return AovPlanes{c->lane[0].pl_color.p + off, c->lane[0].pl_direct.p + off, c->lane[0].pl_albedo.p + off};
+}
+
+// CAP_TRACE_LAUNCHES=1: name every launch on stderr and drain the stream after it (fault localisation only)
+int trace_launch(const CapContext* c, const char* fmt, ...)
+{
+    if (!c->sw.on(SW_TRACE_LAUNCHES)) return CAP_OK;
+    va_list ap;
+    va_start(ap, fmt);
+    fputs("[cap] ", stderr);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    fputs(" ... ", stderr);
+    fflush(stderr);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    fprintf(stderr, "%s\n", hipGetErrorString(e));
+    fflush(stderr);
+    return e == hipSuccess ? CAP_OK : CAP_ERR_HIP;
 }
 }  // namespace
 
@@ -619,6 +706,7 @@ int cap_ctx_create(int device_id, void* hip_stream, CapContext** out_ctx)
         }
         c->own_stream = true;
     }
+    c->lane[0].stream = c->stream;
     (void)hipHostMalloc((void**)&c->pinned_shaded, kGuardWords * sizeof(uint64_t), hipHostMallocDefault);
     update_screen(c, 0, 0, 0, 1);
     *out_ctx = c;
@@ -1122,7 +1210,7 @@ int cap_bvh_build(CapContext* c)
     HIP_TRY(c->tri_raw.ensure(4 * (size_t)n));
     HIP_TRY(c->tri_box.ensure(2 * (size_t)n));
     HIP_TRY(c->nodes.ensure(4 * (size_t)(n > 1 ? n - 1 : 1)));
-    HIP_TRY(c->stack_spill.ensure((size_t)c->cu_count * 8 * kBlock * kSpillEntries));  // up to 8 workgroups per CU
+    HIP_TRY(c->lane[0].stack_spill.ensure((size_t)c->cu_count * 8 * kBlock * kSpillEntries));  // up to 8 workgroups per CU
     HIP_TRY(c->leaf_tri.ensure(n));
     HIP_TRY(c->keys0.ensure(n));
     HIP_TRY(c->keys1.ensure(n));
@@ -1468,15 +1556,16 @@ __global__ __launch_bounds__(256) void k_canary_count(const uint4* p, size_t beg
 }
 static int canary_count(CapContext* c, bool behind, uint64_t* value)
 {
-    if (!c->q_org[0].p || !c->last_class_capacity) return fail(CAP_ERR_STATE, "cap_debug_get: no render yet");
+    CapContext::Lane& L = c->lane[0];
+    if (!L.q_org[0].p || !c->last_class_capacity) return fail(CAP_ERR_STATE, "cap_debug_get: no render yet");
     HIP_TRY(hipSetDevice(c->device));
     DevBuf<unsigned long long> dbuf;  // (released on every path: ADVICE r5)
     HIP_TRY(dbuf.ensure(1));
     unsigned long long* d = dbuf.p;
     HIP_TRY(hipMemsetAsync(d, 0, sizeof(*d), c->stream));
-    const size_t used = std::min((size_t)kQueueClasses * c->last_class_capacity, c->q_org[0].n);
+    const size_t used = std::min((size_t)kQueueClasses * c->last_class_capacity, L.q_org[0].n);
     for (int k = 0; k < 2; ++k)
-        for (DevBuf<float4>* b : {&c->q_org[k], &c->q_dir[k], &c->q_thr[k]})
+        for (DevBuf<float4>* b : {&L.q_org[k], &L.q_dir[k], &L.q_thr[k]})
         {
             const size_t lo = behind ? used : 0, hi = behind ? b->n : used;
             if (hi > lo) hipLaunchKernelGGL(k_canary_count, dim3(512), dim3(256), 0, c->stream, reinterpret_cast<const uint4*>(b->p), lo, hi, d);
@@ -1502,14 +1591,14 @@ int cap_debug_set(CapContext* c, uint32_t key, uint64_t value)
         c->debug_wide_depth_limit = (uint32_t)value;
         return CAP_OK;
     case CAP_DEBUG_QUEUE_CANARY_FILL:
-        if (!c->q_org[0].p) return fail(CAP_ERR_STATE, "cap_debug_set: the queues are allocated by the first cap_render");
+        if (!c->lane[0].q_org[0].p) return fail(CAP_ERR_STATE, "cap_debug_set: the queues are allocated by the first cap_render");
         HIP_TRY(hipSetDevice(c->device));
         for (int k = 0; k < 2; ++k)
-            for (DevBuf<float4>* b : {&c->q_org[k], &c->q_dir[k], &c->q_thr[k]})
+            for (DevBuf<float4>* b : {&c->lane[0].q_org[k], &c->lane[0].q_dir[k], &c->lane[0].q_thr[k]})
                 HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b->p, (int)kCanaryWord, b->n * 4, c->stream));
         return CAP_OK;
     case CAP_DEBUG_FAIL_LANE1:
-        c->debug_fail_lane1 = value != 0;
+        c->debug_fail_lane = value != 0;
         if (!value) c->lane1_failed_paths = 0;  // "memory has been released"
         return CAP_OK;
     default:
@@ -1531,7 +1620,7 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
     {
     case CAP_DEBUG_QUEUE_CAPACITY_DIV: *value = c->debug_capacity_div; return CAP_OK;
     case CAP_DEBUG_WIDE_DEPTH_LIMIT: *value = c->debug_wide_depth_limit; return CAP_OK;
-    case CAP_DEBUG_FAIL_LANE1: *value = c->debug_fail_lane1 ? 1u : 0u; return CAP_OK;
+    case CAP_DEBUG_FAIL_LANE1: *value = c->debug_fail_lane ? 1u : 0u; return CAP_OK;
     case CAP_DEBUG_LANES_USED: *value = c->lanes_last_render; return CAP_OK;
     case CAP_DEBUG_SELFTEST_DIV:
     {
@@ -1558,7 +1647,7 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
     case CAP_DEBUG_QUEUE_CANARY_USED: return canary_count(c, false, value);
     case CAP_DEBUG_WIDE_IN_USE:
         if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_debug_get: BVH not built");
-        *value = bvh_dev(c).wide8_ok;
+        *value = bvh_dev(c, c->lane[0]).wide8_ok;
         return CAP_OK;
     default:
         if (key >= CAP_DEBUG_SWITCH_BASE && key < CAP_DEBUG_SWITCH_BASE + SW_COUNT)
@@ -1653,67 +1742,28 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
         if ((c->screen.width | c->screen.height) & 1u) return fail(CAP_ERR_INVALID_ARG, "cap_render: CAP_RENDER_LOWRES_INDIRECT needs even width and height (%ux%u)", c->screen.width, c->screen.height);
     }
 
-    const uint32_t Ppad = c->screen.pixels_padded;
-    // paths in flight per batch; measured on the headline workload (tools/batch_sweep.sh, end of round 2): 8 Mi 31.0 ms, 16 Mi 25.5,
-    // 32 Mi 22.1, 64 Mi 21.2, 128 Mi 21.1 per step -- every launch has a fixed cost (grid start, tables, tail) that fewer, larger
-    // batches amortise; 64 Mi paths are ~14 GB of queues and planes
-    uint64_t       budget = c->max_batch_paths ? c->max_batch_paths : (uint64_t)64 << 20;
-    const bool tree_path = c->traversal_mode == CAP_TRAVERSAL_EXHAUSTIVE ? false
-                                                                         : !(c->traversal_mode == CAP_TRAVERSAL_AUTO && c->tri_count <= kExhaustiveMax);
-    if (!c->max_batch_paths && (uint64_t)n_frames * Ppad > budget)
-    {
-        // Twice that when the card has the room (round 6, docs/experiments.md (88)): the tree path has 27 launches per batch, most of
-        // them short, and gains 1.7 % (the 262 k hall at 128 spp: 92.1 -> 90.5 ms; round 4 measured 101.2 -> 99.4 and kept 64 Mi for
-        // its 14 GB per lane), the small-scene path 1.0 % (headline 20.22 -> 20.01 ms).  Taken when the working set is already that
-        // large or the device reports room for it with a margin -- 128 Mi paths are ~28 GB per lane of the card's 288, and the tree
-        // path runs two lanes; cap_set_batch_paths overrides either way.
-        const uint64_t big       = (uint64_t)128 << 20;
-        const uint64_t big_slots = std::max<uint64_t>(1, std::min<uint64_t>(big / std::max(1u, Ppad), kMaxFrameSlots));
-        bool           room      = c->pl_color.n >= big_slots * Ppad && (!tree_path || c->lane1.pl_color.n >= big_slots * Ppad);
-        if (!room)
-        {
-            size_t free_b = 0, total_b = 0;
-            room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 3u * big_slots * Ppad * 256u;  // ~208 B per path and lane
-        }
-        if (room) budget = big;
-    }
-    uint32_t       slots  = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(budget / std::max(1u, Ppad), kMaxFrameSlots));
-    slots                 = std::min(slots, n_frames);
-    // Two lanes (CapContext::Lane): consecutive batches alternate between two working sets on two streams, so that the tail of
-    // one batch's launch -- the last chunks, a workgroup at a time, with most of the chip idle -- is filled by the other batch's
-    // next launch instead of waiting for the stream's next kernel (measured with two contexts side by side, tools/dual_test.py:
-    // 21.0 -> 20.55 ms per step on the headline, 3.30 -> 3.05 ms for shard 0 of 8, 28.3 -> 27.1 ms on the 262 k scene).  A call
-    // that fits one batch is cut in two halves when the halves are still large.  Per-stage timers need one stream.
-    const bool no_two_lanes = c->sw.on(SW_NO_TWO_LANES);  // A/B switch
-    // Only on the tree path: its bounces are three launches each, and from the third bounce on they are short (the 262 k scene: 27
-    // launches per batch, the last 15 under 0.2 ms each) -- 28.3 -> 26.4 ms per 32 spp.  The small-scene path's nine long fused
-    // launches gain nothing measurable (20.45 -> 20.25 ms with the context's own stream, 20.56 -> 20.9 beside a torch stream).
-    bool two_lanes = !no_two_lanes && tree_path && c->bvh_info.stack_entries != 0 && !(flags & CAP_RENDER_GBUFFER_FEEDBACK) &&
-                     !(flags & CAP_RENDER_LOWRES_INDIRECT) && n_frames >= 2;
-    if (two_lanes && slots >= n_frames)
-    {
-        const uint64_t split_min = (uint64_t)c->sw.get(SW_LANE_SPLIT_MIN, (int64_t)4 << 20);  // A/B switch (shard 0 of 8 of the 262 k scene: 4.55 -> 4.35 ms with halves of 4 Mi paths)
-        if ((uint64_t)n_frames * Ppad >= split_min)
-            slots = (n_frames + 1) / 2;
-        else
-            two_lanes = false;
-    }
+    // Which traversal path the render takes, decided here once: the small-scene kernels (closest hit and shading fused in one
+    // launch per bounce, every triangle tested) or the tree path.  stack_entries == 0 selects the former in the launchers.
+    if (c->traversal_mode == CAP_TRAVERSAL_EXHAUSTIVE && c->tri_count > 4096)
+        return fail(CAP_ERR_UNSUPPORTED, "cap_render: exhaustive traversal refused for %u triangles", c->tri_count);
+    const bool     tree_path     = c->traversal_mode == CAP_TRAVERSAL_EXHAUSTIVE ? false
+                                                                                 : !(c->traversal_mode == CAP_TRAVERSAL_AUTO && c->tri_count <= kExhaustiveMax);
+    const uint32_t stack_entries = tree_path ? c->bvh_info.stack_entries : 0u;
+    const bool     fused         = stack_entries == 0;  // small-scene path: closest hit and shading in one kernel per bounce
+
+    const uint32_t    Ppad      = c->screen.pixels_padded;
+    const BatchPolicy policy    = batch_policy(c, n_frames, num_bounces, flags, tree_path);
+    const uint32_t    slots     = policy.slots;
+    bool              two_lanes = policy.two_lanes;
     // No host synchronisation with the previous call: everything it still uses is either ordered behind it on the stream (queues,
     // counters, planes) or lives in another slot of the constants ring.  Only a long backlog of unread events / counters is
     // drained (what cap_sync / cap_stats_get do anyway), and a growing allocation (which frees the old buffers).
     if (c->spans.size() > 2048 || c->pending.size() > 64 || c->post_marks.size() > 256)
         if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
-    {
-        const size_t planes_np = (size_t)slots * c->screen.pixels_padded;
-        const bool   grows     = c->pl_color.n < planes_np || c->counters.n < (3 * (size_t)(num_bounces + 1) + 1) * kQueueClasses * kCounterStride ||
-                           !c->accum.p || c->accum.n < c->screen.pixels_padded;
-        if (grows) HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    // (per-stage timers and launch tracing need one stream: the batches keep the size the two lanes gave them -- so that a stage-timed
-    // render launches what the plain one does -- and run one after the other on lane 0)
-    if ((flags & CAP_RENDER_STAGE_TIMERS) || c->sw.on(SW_TRACE_LAUNCHES)) two_lanes = false;
-    if (ensure_wavefront(c, slots, num_bounces) != CAP_OK) return CAP_ERR_HIP;
-    if (two_lanes && c->lane1_failed_paths && (uint64_t)slots * Ppad >= c->lane1_failed_paths && num_bounces >= c->lane1_failed_bounces)
+    const LaneSizes need = lane_sizes(c, slots, num_bounces);
+    if (lane_grows(c->lane[0], need) || !c->accum.p || c->accum.n < Ppad) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (ensure_lane(c, c->lane[0], slots, num_bounces) != CAP_OK || ensure_frame_buffers(c) != CAP_OK) return CAP_ERR_HIP;
+    if (policy.lane1_failed_before)
     {
         // this size has already failed: one lane, without asking again -- except every 32nd time, and at once when the device reports
         // room for it (memory can come back without any call on this context: another context closed, a co-tenant left)
@@ -1727,19 +1777,19 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
     }
     if (two_lanes)
     {
-        if (c->lane1.pl_color.n < (size_t)slots * Ppad || c->lane1.counters.n < c->counters.n)
+        if (lane_grows(c->lane[1], need))
         {
             HIP_TRY(hipStreamSynchronize(c->stream));  // growing frees the old buffers
             if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
         }
-        if (c->debug_fail_lane1 || ensure_lane1(c, slots, num_bounces) != CAP_OK)
+        if (c->debug_fail_lane || ensure_lane(c, c->lane[1], slots, num_bounces) != CAP_OK || ensure_lane_streams(c) != CAP_OK)
         {
             // the second working set doubles the batch's memory (~28 GB at the default budget): without it the batches of this call
             // simply run one after the other on lane 0 -- counted in CapStats::lane1_dropped, and not tried again at this
             // size until something is freed
             (void)hipGetLastError();
-            c->lane1 = CapContext::Lane{};
-            c->lane1_failed_paths = (uint64_t)slots * Ppad, c->lane1_failed_bounces = num_bounces;  // (ensure_lane1's size depends on both)
+            c->lane[1] = CapContext::Lane{};
+            c->lane1_failed_paths = (uint64_t)slots * Ppad, c->lane1_failed_bounces = num_bounces;  // (ensure_lane's size depends on both)
             ++c->stats.lane1_dropped;
             two_lanes = false;
         }
@@ -1773,42 +1823,16 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
         c->textures_dirty = false;
     }
 
-    uint32_t stack_entries = c->bvh_info.stack_entries;
-    if (c->traversal_mode == CAP_TRAVERSAL_EXHAUSTIVE)
-    {
-        if (c->tri_count > 4096) return fail(CAP_ERR_UNSUPPORTED, "cap_render: exhaustive traversal refused for %u triangles", c->tri_count);
-        stack_entries = 0;
-    }
-    else if (c->traversal_mode == CAP_TRAVERSAL_AUTO && c->tri_count <= kExhaustiveMax)
-        stack_entries = 0;
     // Persistent grids must be fully resident: a workgroup that cannot be co-scheduled runs as a second round after the first
     // waves retire and doubles the kernel's tail.  blocks_per_cu is therefore the residency the kernels are built for
     // (launch bounds in kernels.hip), not the 8 a register-light kernel could reach.
-    uint32_t blocks_per_cu = stack_entries == 0 ? 6u : (stack_entries <= 32 ? 5u : 2u);  // measured: 4..8 within 4 %, 6 best
+    uint32_t blocks_per_cu = fused ? 6u : (stack_entries <= 32 ? 5u : 2u);  // measured: 4..8 within 4 %, 6 best
     if (c->sw.v[SW_BLOCKS_PER_CU] >= 0) blocks_per_cu = (uint32_t)std::max<int64_t>(1, c->sw.v[SW_BLOCKS_PER_CU]);
-    LaunchCfg cfg{c->stream, (uint32_t)c->cu_count * blocks_per_cu, stack_entries, (uint32_t)c->cu_count};
-    cfg.sw = &c->sw;
-    BvhDev          bvh   = bvh_dev(c);
     const SceneDev  scene = scene_dev(c);
     const CameraDev cam   = camera_dev(c->camera);
     const uint32_t  D     = num_bounces;
     std::unique_ptr<StageTimer> total(new StageTimer(c, ST_COUNT));  // its destructor closes the span on every exit path
 
-    // per-lane view of the batch working set
-    struct LaneView
-    {
-        float4 *  hits, *q_org[2], *q_dir[2], *q_thr[2], *s_org, *s_dir, *s_con, *pl_color, *pl_direct, *pl_albedo;
-        uint32_t *counters, *spill;
-        size_t    ring_n;
-        hipStream_t stream;
-    };
-    const LaneView views[2] = {
-        {c->hits.p, {c->q_org[0].p, c->q_org[1].p}, {c->q_dir[0].p, c->q_dir[1].p}, {c->q_thr[0].p, c->q_thr[1].p}, c->s_org.p, c->s_dir.p, c->s_con.p,
-         c->pl_color.p, c->pl_direct.p, c->pl_albedo.p, c->counters.p, c->stack_spill.p, std::min(c->s_org.n, c->s_con.n), c->stream},
-        {c->lane1.hits.p, {c->lane1.q_org[0].p, c->lane1.q_org[1].p}, {c->lane1.q_dir[0].p, c->lane1.q_dir[1].p},
-         {c->lane1.q_thr[0].p, c->lane1.q_thr[1].p}, c->lane1.s_org.p, c->lane1.s_dir.p, c->lane1.s_con.p, c->lane1.pl_color.p,
-         c->lane1.pl_direct.p, c->lane1.pl_albedo.p, c->lane1.counters.p, c->lane1.stack_spill.p, std::min(c->lane1.s_org.n, c->lane1.s_con.n),
-         c->stream2}};
     const uint32_t n_batches = (n_frames + slots - 1) / slots;
     // Every way out of this function after the fork -- the early returns of HIP_TRY and of the launch tracing included -- leaves the
     // context's stream, the one callers order cap_sync / cap_readback / buffer growth behind, waiting for lane 1 (an error
@@ -1836,20 +1860,21 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
 
     for (uint32_t done = 0; done < n_frames; done += slots, ++batch)
     {
-        const uint32_t  lane = two_lanes ? ((n_batches - 1u - batch) & 1u) : 0u;  // the last batch on lane 0
-        const LaneView& L    = views[lane];
-        cfg.stream           = L.stream;
-        bvh.stack_spill      = L.spill;
+        const uint32_t    lane = two_lanes ? ((n_batches - 1u - batch) & 1u) : 0u;  // the last batch on lane 0
+        CapContext::Lane& L    = c->lane[lane];
+        const BvhDev      bvh  = bvh_dev(c, L);
+        LaunchCfg         cfg{L.stream, (uint32_t)c->cu_count * blocks_per_cu, stack_entries, (uint32_t)c->cu_count};
+        cfg.sw = &c->sw;
         const uint32_t ns = std::min(slots, n_frames - done);
         const FrameConst* frames = c->frames_ring[ring].p + done;
         const size_t   per_queue     = (size_t)kQueueClasses * kCounterStride;  // counter words of one queue
         // per bounce and class one 64-bit word: low half = extension entries, high half = shadow entries (one atomic serves both)
         const size_t   counter_words = (size_t)(D + 1) * per_queue;
-        HIP_TRY(hipMemsetAsync(L.counters, 0, sizeof(uint32_t) * 3 * counter_words, L.stream));
-        uint32_t*      ext_count = L.counters;
-        uint32_t*      sh_count  = L.counters + 1;
-        uint32_t*      work_shade = L.counters + counter_words;      // + b * per_queue: grab counters of bounce b's fused launch
-        uint32_t*      work_any   = L.counters + 2 * counter_words;  // ... and of its any-hit launch
+        HIP_TRY(hipMemsetAsync(L.counters.p, 0, sizeof(uint32_t) * 3 * counter_words, L.stream));
+        uint32_t*      ext_count = L.counters.p;
+        uint32_t*      sh_count  = L.counters.p + 1;
+        uint32_t*      work_shade = L.counters.p + counter_words;      // + b * per_queue: grab counters of bounce b's fused launch
+        uint32_t*      work_any   = L.counters.p + 2 * counter_words;  // ... and of its any-hit launch
         const uint32_t total_chunks   = ns * (Ppad >> 6);
         uint32_t       class_capacity = ((total_chunks + kQueueClasses - 1) / kQueueClasses) * 64u;
         // (tests of the append guard: sub-queues deliberately too small -- the appends beyond them must be dropped and counted)
@@ -1860,8 +1885,8 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
         const uint32_t max_count  = ns * Ppad;
 
         ShadeArgs sa{};
-        sa.scene = scene, sa.cam = cam, sa.screen = c->screen, sa.frames = frames, sa.hits = L.hits;
-        sa.planes = Planes{L.pl_color, L.pl_direct, L.pl_albedo, c->aov_geo.p, c->aov_nd.p};
+        sa.scene = scene, sa.cam = cam, sa.screen = c->screen, sa.frames = frames, sa.hits = L.hits.p;
+        sa.planes = Planes{L.pl_color.p, L.pl_direct.p, L.pl_albedo.p, c->aov_geo.p, c->aov_nd.p};
         sa.n_slots = ns, sa.num_bounces = D, sa.max_count = max_count, sa.aov_slot = aov_slot, sa.shaded_counter = c->shaded_counter.p;
         {
             // screen-space culling of bounce 0 inverts primary_dir (camera.h:39-63), which needs an orthonormal basis
@@ -1878,7 +1903,6 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
         sa.albedo_in_w = (!no_albedo_w && !feedback && !lowres && !(flags & CAP_RENDER_AOV) && (ext || scene.texture_count == 0)) ? 1u : 0u;  // (the EXT model's first-vertex albedo is 1: it folds kd into the throughput)
         if (feedback)  // g_color_history = combined_history[(frame_count + 1) % 2], raytracing_system.cpp:1754-1759
             sa.fb = FeedbackDev{camera_dev(c->prev_camera), c->post_prev_nd.p, c->post_chist[(frame_begin + 1) % 2].p};
-        const bool fused = cfg.stack_entries == 0;  // small-scene path: closest hit and shading in one kernel per bounce
         const bool no_inline_nee = c->sw.on(SW_NO_INLINE_NEE);  // A/B switch
         sa.inline_nee = (ext && fused && !no_inline_nee) ? 1u : 0u;
         const bool no_inline_probe = c->sw.on(SW_NO_INLINE_PROBE);  // A/B switch
@@ -1887,20 +1911,9 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
                               ? 1u
                               : 0u;
         const bool no_wave_ring = c->sw.on(SW_NO_WAVE_RING);  // A/B switch
-        sa.wave_ring = (sa.inline_probe && !no_wave_ring && (size_t)cfg.grid_blocks * (kBlock / 64) * 128 <= L.ring_n) ? 1u : 0u;  // (a grid beyond what ensure_wavefront sized the rings for: CAP_BLOCKS_PER_CU)
+        sa.wave_ring = (sa.inline_probe && !no_wave_ring && (size_t)cfg.grid_blocks * (kBlock / 64) * 128 <= std::min(L.s_org.n, L.s_con.n)) ? 1u : 0u;  // (a grid beyond what ensure_lane sized the rings for: CAP_BLOCKS_PER_CU)
         LaunchCfg cfg_any    = cfg;
         cfg_any.any_no_probe = sa.inline_probe;
-        // CAP_TRACE_LAUNCHES=1: name every launch on stderr and drain the stream after it (fault localisation only)
-        const bool trace_launches = c->sw.on(SW_TRACE_LAUNCHES);
-        auto              traced         = [&](const char* what, uint32_t b) -> int {
-            if (!trace_launches) return CAP_OK;
-            fprintf(stderr, "[cap] %s bounce %u batch %u ... ", what, b, done / slots);
-            fflush(stderr);
-            hipError_t e = hipStreamSynchronize(c->stream);
-            fprintf(stderr, "%s\n", hipGetErrorString(e));
-            fflush(stderr);
-            return e == hipSuccess ? CAP_OK : CAP_ERR_HIP;
-        };
         bool primary_shaded = false;  // tree path: bounce 0's shading done by the camera-ray kernel
         // Camera rays of a DENSE scene.  The packet walk (one node sequence per 8x8-pixel tile) is the fast form while a tile's 64
         // rays meet few triangles: 9.3 per packet on the 262 k-triangle hall at 1080p (0.13 triangles per pixel).  At 16.8 M
@@ -1935,18 +1948,18 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
             const int pi = (int)(b & 1u), po = pi ^ 1;
             sa.bounce    = b;
             // (inline_nee: no shadow entries are written, so the shadow queue's two 16-byte planes carry the paths' gathered radiance)
-            sa.in        = RayQueue{L.q_org[pi], L.q_dir[pi], L.q_thr[pi], b ? ext_count + (b - 1) * per_queue : nullptr, class_capacity,
-                                    pi ? L.s_dir : L.s_org};
-            sa.out       = RayQueue{L.q_org[po], L.q_dir[po], L.q_thr[po], ext_count + b * per_queue, class_capacity,
-                                    po ? L.s_dir : L.s_org};
-            sa.shadow    = ShadowQueue{L.s_org, L.s_dir, L.s_con, sh_count + b * per_queue, class_capacity};
+            sa.in        = RayQueue{L.q_org[pi].p, L.q_dir[pi].p, L.q_thr[pi].p, b ? ext_count + (b - 1) * per_queue : nullptr, class_capacity,
+                                    pi ? L.s_dir.p : L.s_org.p};
+            sa.out       = RayQueue{L.q_org[po].p, L.q_dir[po].p, L.q_thr[po].p, ext_count + b * per_queue, class_capacity,
+                                    po ? L.s_dir.p : L.s_org.p};
+            sa.shadow    = ShadowQueue{L.s_org.p, L.s_dir.p, L.s_con.p, sh_count + b * per_queue, class_capacity};
             sa.work      = work_shade + b * per_queue;
             if (fused)
             {
                 StageTimer t(c, b == 0 ? ST_PRIMARY : ST_CLOSEST, st);
                 launch_trace_shade(cfg, bvh, sa, ext, feedback);
                 if (b) ++c->stats.launches_trace_closest;
-                if (traced("trace_shade", b)) return fail(CAP_ERR_HIP, "trace_shade failed");
+                if (trace_launch(c, "trace_shade bounce %u batch %u", b, batch)) return fail(CAP_ERR_HIP, "trace_shade failed");
             }
             else
             {
@@ -1958,22 +1971,22 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
                         {
                             // dense scene: camera rays as an identity queue through the wide per-lane kernel (see above)
                             const uint32_t id_cap = (((max_count + kQueueClasses - 1) / kQueueClasses) + 63u) & ~63u;
-                            const RayQueue idq{L.q_org[0], L.q_dir[0], nullptr, L.counters + 3 * counter_words, id_cap, nullptr};
+                            const RayQueue idq{L.q_org[0].p, L.q_dir[0].p, nullptr, L.counters.p + 3 * counter_words, id_cap, nullptr};
                             if (c->sw.on(SW_RAYGEN_KERNEL) || bvh.tri_count == 0)  // A/B switch: the identity queue written out by its own kernel
                             {
                                 launch_raygen_identity(cfg, cam, c->screen, frames, ns, idq);
-                                launch_trace_closest8(cfg, bvh, idq, max_count, L.hits, sa.work);
+                                launch_trace_closest8(cfg, bvh, idq, max_count, L.hits.p, sa.work);
                             }
                             else
-                                launch_trace_closest8_camera(cfg, bvh, idq, max_count, L.hits, sa.work, cam, c->screen, frames, ns);
+                                launch_trace_closest8_camera(cfg, bvh, idq, max_count, L.hits.p, sa.work, cam, c->screen, frames, ns);
                         }
                         else
                         {
-                            primary_shaded = launch_primary_shade(cfg, bvh, sa, L.hits, ext);
-                            if (!primary_shaded) launch_trace_primary(cfg, bvh, cam, c->screen, frames, ns, L.hits, sa.work);
+                            primary_shaded = launch_primary_shade(cfg, bvh, sa, L.hits.p, ext);
+                            if (!primary_shaded) launch_trace_primary(cfg, bvh, cam, c->screen, frames, ns, L.hits.p, sa.work);
                         }
                     }
-                    if (aov_slot != ~0u) launch_geo_aov(cfg, scene, L.hits + (size_t)aov_slot * Ppad, Ppad, c->aov_geo.p);
+                    if (aov_slot != ~0u) launch_geo_aov(cfg, scene, L.hits.p + (size_t)aov_slot * Ppad, Ppad, c->aov_geo.p);
                 }
                 if (b != 0 || !primary_shaded)
                 {
@@ -1986,21 +1999,21 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
             {
                 StageTimer t(c, ST_ANY, st, b == 0 ? ST_DIRECT : ST_NONE);
                 if (any_refill)
-                    launch_trace_any8_refill(cfg_any, bvh, sa.shadow, max_count, b == 0 ? L.pl_direct : L.pl_color, Ppad, ns, c->shaded_counter.p,
+                    launch_trace_any8_refill(cfg_any, bvh, sa.shadow, max_count, b == 0 ? L.pl_direct.p : L.pl_color.p, Ppad, ns, c->shaded_counter.p,
                                              work_any + b * per_queue, frames);
                 else
-                    launch_trace_any(cfg_any, bvh, sa.shadow, max_count, b == 0 ? L.pl_direct : L.pl_color, Ppad, ns, c->shaded_counter.p,
+                    launch_trace_any(cfg_any, bvh, sa.shadow, max_count, b == 0 ? L.pl_direct.p : L.pl_color.p, Ppad, ns, c->shaded_counter.p,
                                      work_any + b * per_queue, /* next-event estimation: most shadow rays reach the light */ ext, frames);
                 ++c->stats.launches_trace_any;
-                if (traced("trace_any", b)) return fail(CAP_ERR_HIP, "trace_any failed");
+                if (trace_launch(c, "trace_any bounce %u batch %u", b, batch)) return fail(CAP_ERR_HIP, "trace_any failed");
             }
             if (!fused && b < D)
             {
                 StageTimer t(c, ST_CLOSEST, st);
                 if (bvh.wide8_ok)  // bounce b + 1's slot of the fused kernels' grab counters is free on this path
-                    launch_trace_closest8(cfg, bvh, sa.out, max_count, L.hits, work_shade + (b + 1) * per_queue);
+                    launch_trace_closest8(cfg, bvh, sa.out, max_count, L.hits.p, work_shade + (b + 1) * per_queue);
                 else
-                    launch_trace_closest(cfg, bvh, sa.out, max_count, L.hits);
+                    launch_trace_closest(cfg, bvh, sa.out, max_count, L.hits.p);
                 ++c->stats.launches_trace_closest;
             }
         }
@@ -2024,7 +2037,7 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
         }
         else
             HIP_TRY(hipHostMalloc((void**)&pinned, sizeof(uint32_t) * 2 * 256 * kQueueClasses * kCounterStride, hipHostMallocDefault));
-        HIP_TRY(hipMemcpyAsync(pinned, L.counters, sizeof(uint32_t) * counter_words, hipMemcpyDeviceToHost, L.stream));
+        HIP_TRY(hipMemcpyAsync(pinned, L.counters.p, sizeof(uint32_t) * counter_words, hipMemcpyDeviceToHost, L.stream));
         c->pending.push_back({pinned, D | (sa.inline_nee ? 1u << 16 : 0u)});
         HIP_TRY(hipGetLastError());
 
@@ -2072,30 +2085,29 @@ int cap_readback(CapContext* c, CapBufferKind kind, float* dst)
     HIP_TRY(hipSetDevice(c->device));
     if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
     const size_t npix = (size_t)c->screen.width * c->screen.height;
-    const uint32_t Ppad = c->screen.pixels_padded;
     HIP_TRY(c->image_tmp.ensure(npix));
     HIP_TRY(hipMemsetAsync(c->image_tmp.p, 0, sizeof(float4) * npix, c->stream));
     LaunchCfg cfg{c->stream, (uint32_t)c->cu_count * 8u, 32};
     const bool is_aov = kind <= CAP_BUF_COMBINED || kind == CAP_BUF_INDIRECT_LOWRES;
     if (is_aov && !c->aov_valid) return fail(CAP_ERR_STATE, "cap_readback: no frame rendered with CAP_RENDER_AOV");
     if (!is_aov && !c->accum.p) return fail(CAP_ERR_STATE, "cap_readback: nothing rendered");
-    const size_t off = (size_t)(c->last_slots ? c->last_slots - 1 : 0) * Ppad;
+    const AovPlanes aov = aov_planes(c);
     switch (kind)
     {
     case CAP_BUF_GBUFFER_GEO: launch_untile(cfg, c->screen, c->aov_geo.p, nullptr, nullptr, 0, c->image_tmp.p); break;
     case CAP_BUF_NORMAL_DEPTH: launch_untile(cfg, c->screen, c->aov_nd.p, nullptr, nullptr, 0, c->image_tmp.p); break;
-    case CAP_BUF_DIRECT: launch_untile(cfg, c->screen, c->pl_direct.p + off, nullptr, nullptr, 0, c->image_tmp.p); break;
-    case CAP_BUF_ALBEDO: launch_untile(cfg, c->screen, c->pl_albedo.p + off, nullptr, nullptr, 0, c->image_tmp.p); break;
-    case CAP_BUF_INDIRECT: launch_untile(cfg, c->screen, c->pl_color.p + off, nullptr, nullptr, 0, c->image_tmp.p); break;
+    case CAP_BUF_DIRECT: launch_untile(cfg, c->screen, aov.direct, nullptr, nullptr, 0, c->image_tmp.p); break;
+    case CAP_BUF_ALBEDO: launch_untile(cfg, c->screen, aov.albedo, nullptr, nullptr, 0, c->image_tmp.p); break;
+    case CAP_BUF_INDIRECT: launch_untile(cfg, c->screen, aov.color, nullptr, nullptr, 0, c->image_tmp.p); break;
     case CAP_BUF_COMBINED:
-        launch_untile(cfg, c->screen, c->pl_color.p + off, c->pl_albedo.p + off, c->pl_direct.p + off, 1, c->image_tmp.p);
+        launch_untile(cfg, c->screen, aov.color, aov.albedo, aov.direct, 1, c->image_tmp.p);
         break;
     case CAP_BUF_ACCUM_SUM: launch_untile(cfg, c->screen, c->accum.p, nullptr, nullptr, 0, c->image_tmp.p); break;
     case CAP_BUF_ACCUM_MEAN: launch_untile(cfg, c->screen, c->accum.p, nullptr, nullptr, 2, c->image_tmp.p); break;
     case CAP_BUF_INDIRECT_LOWRES:
     {
         if (!c->aov_lowres) return fail(CAP_ERR_STATE, "cap_readback: the last CAP_RENDER_AOV frame was not rendered with CAP_RENDER_LOWRES_INDIRECT");
-        launch_untile(cfg, c->screen, c->pl_color.p + off, nullptr, nullptr, 0, c->image_tmp.p);
+        launch_untile(cfg, c->screen, aov.color, nullptr, nullptr, 0, c->image_tmp.p);
         HIP_TRY(c->post_itemp.ensure(npix));
         launch_decimate2x(c->stream, c->image_tmp.p, c->screen.width, c->screen.height, (c->aov_frame % 4u) / 2u, (c->aov_frame % 4u) % 2u,
                           c->post_itemp.p);
@@ -2175,17 +2187,10 @@ struct QueryRun
     LaunchCfg   cfg;
     float       safe;
     uint64_t    per;  // rays per launch
-    // CAP_TRACE_LAUNCHES=1: name every launch on stderr and drain the stream after it (fault localisation only)
     int traced(const char* kernel, uint64_t first) const
     {
         HIP_TRY(hipGetLastError());
-        if (!c->sw.on(SW_TRACE_LAUNCHES)) return CAP_OK;
-        fprintf(stderr, "[cap] %s %s rays %llu.. ... ", what, kernel, (unsigned long long)first);
-        fflush(stderr);
-        hipError_t e = hipStreamSynchronize(c->stream);
-        fprintf(stderr, "%s\n", hipGetErrorString(e));
-        fflush(stderr);
-        return e == hipSuccess ? CAP_OK : CAP_ERR_HIP;
+        return trace_launch(c, "%s %s rays %llu..", what, kernel, (unsigned long long)first);
     }
 };
 
@@ -2203,7 +2208,7 @@ int query_prepare(CapContext* c, const char* what, uint64_t n, QueryRun& run)
 {
     HIP_TRY(hipSetDevice(c->device));
     run.c = c, run.what = what;
-    run.bvh          = bvh_dev(c);  // (lane 0's spill area: a render's second lane has its own, and the stream orders us behind both)
+    run.bvh          = bvh_dev(c, c->lane[0]);  // (lane 0's spill area: a render's second lane has its own, and the stream orders us behind both)
     run.bvh.wide8_ok = run.bvh.wide8_ok && query8_stack_matches();
     run.per          = std::min<uint64_t>(n, kQueryRaysPerLaunch);
     if (c->query_work.n < 2 * kCounterStride || (run.bvh.wide8_ok && c->query_defer.n < run.per))
@@ -2620,11 +2625,11 @@ int cap_resolve_aov_tiles(CapContext* c, float* device_dst)
     if (!c->aov_valid) return fail(CAP_ERR_STATE, "cap_resolve_aov_tiles: no frame rendered with CAP_RENDER_AOV");
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t Ppad  = c->screen.pixels_padded;
-    const size_t   off   = (size_t)(c->last_slots ? c->last_slots - 1 : 0) * Ppad;
+    const AovPlanes aov  = aov_planes(c);
     const size_t   bytes = sizeof(float4) * (size_t)Ppad;
     float4*        dst   = reinterpret_cast<float4*>(device_dst);
     // the four inputs of the chain, in its order (cap_post_frame): indirect, direct, albedo, normal/depth
-    const float4* src[4] = {c->pl_color.p + off, c->pl_direct.p + off, c->pl_albedo.p + off, c->aov_nd.p};
+    const float4* src[4] = {aov.color, aov.direct, aov.albedo, c->aov_nd.p};
     for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpyAsync(dst + (size_t)k * Ppad, src[k], bytes, hipMemcpyDeviceToDevice, c->stream));
     return CAP_OK;
 }
@@ -2706,9 +2711,8 @@ int cap_post_frame(CapContext* c, const CapPostSettings* s, uint32_t frame_count
     HIP_TRY(hipSetDevice(c->device));
     if (c->post_w != c->screen.width || c->post_h != c->screen.height)
         if (int e = cap_post_reset(c)) return e;
-    const uint32_t Ppad = c->screen.pixels_padded;
-    const size_t   off  = (size_t)(c->last_slots ? c->last_slots - 1 : 0) * Ppad;
-    LaunchCfg      cfg{c->stream, (uint32_t)c->cu_count * 8u, 32};
+    const AovPlanes aov = aov_planes(c);
+    LaunchCfg       cfg{c->stream, (uint32_t)c->cu_count * 8u, 32};
     const bool lowres = s->lowres_indirect != 0;
     if (lowres != c->aov_lowres)
         return fail(CAP_ERR_STATE, "cap_post_frame: settings.lowres_indirect is %d but the frame was rendered %s CAP_RENDER_LOWRES_INDIRECT",
@@ -2719,13 +2723,13 @@ int cap_post_frame(CapContext* c, const CapPostSettings* s, uint32_t frame_count
     {
         // output_indirect_ is the (W/2, H/2) image of the pixels at sp_offset (raytracing_system.cpp:499-512)
         HIP_TRY(c->image_tmp.ensure((size_t)c->screen.width * c->screen.height));
-        launch_untile(cfg, c->screen, c->pl_color.p + off, nullptr, nullptr, 0, c->image_tmp.p);
+        launch_untile(cfg, c->screen, aov.color, nullptr, nullptr, 0, c->image_tmp.p);
         launch_decimate2x(c->stream, c->image_tmp.p, c->screen.width, c->screen.height, (frame_count % 4u) / 2u, (frame_count % 4u) % 2u,
                           c->post_in[0].p);
     }
     // the chain takes the render's tile-ordered planes as they are (PostChainArgs::tiled): its first kernel untiles the indirect
     // plane and decodes the normals in one pass, Combine reads direct / albedo in tile order
-    PostTiledInputs ti{lowres ? nullptr : c->pl_color.p + off, c->pl_direct.p + off, c->pl_albedo.p + off, c->aov_nd.p};
+    PostTiledInputs ti{lowres ? nullptr : aov.color, aov.direct, aov.albedo, c->aov_nd.p};
     return run_post_chain(c, s, frame_count, prev_camera, &ti);
 }
 
