@@ -165,7 +165,24 @@ class InstancesInfo(C.Structure):  # CapInstancesInfo
     _fields_ = [("count", C.c_uint32), ("inert", C.c_uint32), ("tlas_nodes", C.c_uint32), ("tlas_depth", C.c_uint32), ("ms", C.c_double)]
 
 
+class ObjectRange(C.Structure):  # CapObjectRange
+    _fields_ = [("first_mesh", C.c_uint32), ("mesh_count", C.c_uint32)]
+
+
+class ObjectInfo(C.Structure):  # CapObjectInfo, 48 B
+    _fields_ = [("first_triangle", C.c_uint32), ("triangle_count", C.c_uint32), ("node_count", C.c_uint32), ("max_depth", C.c_uint32),
+                ("bounds_lo", C.c_float * 3), ("bounds_hi", C.c_float * 3), ("builder", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ObjectsInfo(C.Structure):  # CapObjectsInfo
+    _fields_ = [("count", C.c_uint32), ("triangles", C.c_uint32), ("nodes", C.c_uint32), ("max_depth", C.c_uint32), ("ms", C.c_double)]
+
+
 INSTANCES_DEVICE = 1  # CAP_INSTANCES_DEVICE
+OBJECT_MAX_COUNT = 4096  # CAP_OBJECT_MAX_COUNT
+OBJECT_RANGE_DTYPE = np.dtype([("first_mesh", np.uint32), ("mesh_count", np.uint32)])
+OBJECT_INFO_DTYPE = np.dtype([("first_triangle", np.uint32), ("triangle_count", np.uint32), ("node_count", np.uint32), ("max_depth", np.uint32),
+                              ("bounds_lo", np.float32, (3,)), ("bounds_hi", np.float32, (3,)), ("builder", np.uint32), ("reserved", np.uint32)])
 INSTANCE_MAX_CONDITION = 4096.0  # CAP_INSTANCE_MAX_CONDITION
 INSTANCE_DESC_DTYPE = np.dtype([("transform", np.float32, (12,)), ("mask", np.uint32), ("reserved", np.uint32, (3,))])
 
@@ -213,6 +230,9 @@ SYMBOLS = {
     "cap_trace_occlusion_ex": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_trace_rays_multi_ex": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_instances_set": (_i, [_vp, _vp, _u32, _u32, C.POINTER(InstancesInfo)]),
+    "cap_instances_set_ex": (_i, [_vp, _vp, _vp, _u32, _u32, C.POINTER(InstancesInfo)]),
+    "cap_objects_set": (_i, [_vp, _vp, _u32, C.POINTER(ObjectsInfo)]),
+    "cap_objects_info": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
     "cap_instances_readback": (_i, [_vp, _vp, _vp]),
     "cap_trace_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_trace_instances_occlusion": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
@@ -685,8 +705,30 @@ class Renderer:
         return out
 
     # ---- instanced ray queries (cap_instances_set, cap_trace_instances*) ----
-    def set_instances(self, transforms, masks=None, sync=True):
+    def set_objects(self, ranges):
+        """Installs the object table (cap_objects_set): ranges is (K, 2) (first_mesh, mesh_count) rows, disjoint mesh ranges of the
+        uploaded scene, each built into a tree of its own; None or an empty list removes the table.  Drops the instance table: call
+        set_instances(..., objects=...) afterwards.  Returns the CapObjectsInfo (count, triangles, nodes, max_depth, ms)."""
+        info = ObjectsInfo()
+        r = np.zeros((0, 2), np.uint32) if ranges is None else np.ascontiguousarray(ranges, np.uint32).reshape(-1, 2)
+        _check(lib().cap_objects_set(self.ctx, _p(r) if len(r) else None, len(r), C.byref(info)), "cap_objects_set")
+        self._instances_n = 0
+        return info
+
+    def objects_info(self):
+        """One OBJECT_INFO_DTYPE record per object of the installed table (cap_objects_info): triangle range, node count, depth, exact
+        bounds and the builder that made its tree; empty without a table."""
+        n = C.c_uint32(0)
+        _check(lib().cap_objects_info(self.ctx, None, 0, C.byref(n)), "cap_objects_info")
+        out = np.zeros(n.value, OBJECT_INFO_DTYPE)
+        if n.value:
+            _check(lib().cap_objects_info(self.ctx, _p(out), n.value, None), "cap_objects_info")
+        return out
+
+    def set_instances(self, transforms, masks=None, sync=True, objects=None):
         """Installs N instances of the uploaded scene (cap_instances_set) and builds the top-level tree; None removes the table.
+        objects: N object indices into the table set_objects installed (cap_instances_set_ex) -- a numpy array with numpy transforms, a
+        tensor on the device with device transforms; None shows object 0 (without an object table: the whole scene).
         transforms: (N, 3, 4) or (N, 12) float32 object-to-world matrices, row-major -- a numpy array (host path), or a torch tensor on
         this context's device: then the 64-byte descriptors are assembled on the device and the call takes CAP_INSTANCES_DEVICE, nothing
         goes through the host.  masks: N values 0..0xFF, default 0xFF.  sync as trace_rays (the device path with sync=False only
@@ -703,7 +745,13 @@ class Renderer:
             d = np.zeros(t.shape[0], INSTANCE_DESC_DTYPE)
             d["transform"] = t.reshape(-1, 12)
             d["mask"] = 0xFF if masks is None else np.asarray(masks).astype(np.uint32).reshape(-1)
-            _check(lib().cap_instances_set(self.ctx, _p(d), d.shape[0], 0, C.byref(info)), "cap_instances_set")
+            if objects is None:
+                _check(lib().cap_instances_set(self.ctx, _p(d), d.shape[0], 0, C.byref(info)), "cap_instances_set")
+            else:
+                o = np.ascontiguousarray(np.asarray(objects).astype(np.uint32).reshape(-1))
+                if o.size != d.shape[0]:
+                    raise CapError("objects must hold one index per instance (%d), got %d" % (d.shape[0], o.size))
+                _check(lib().cap_instances_set_ex(self.ctx, _p(d), _p(o), d.shape[0], 0, C.byref(info)), "cap_instances_set_ex")
             self._instances_n = d.shape[0]
             return info
         import torch
@@ -715,12 +763,19 @@ class Renderer:
         d[:, :12] = transforms.reshape(n, 12)
         m = torch.full((n,), 0xFF, dtype=torch.int32, device=dev) if masks is None else torch.as_tensor(masks, device=dev).to(torch.int32).reshape(n)
         d[:, 12] = m.view(torch.float32)
+        o = None
+        if objects is not None:
+            o = torch.as_tensor(objects, device=dev).to(torch.int32).reshape(n).contiguous()
         if sync:
             torch.cuda.current_stream(dev).synchronize()  # the descriptors were written on torch's stream
-        _check(lib().cap_instances_set(self.ctx, C.c_void_p(d.data_ptr()), n, INSTANCES_DEVICE, C.byref(info) if sync else None), "cap_instances_set")
+        if o is None:
+            _check(lib().cap_instances_set(self.ctx, C.c_void_p(d.data_ptr()), n, INSTANCES_DEVICE, C.byref(info) if sync else None), "cap_instances_set")
+        else:
+            _check(lib().cap_instances_set_ex(self.ctx, C.c_void_p(d.data_ptr()), C.c_void_p(o.data_ptr()), n, INSTANCES_DEVICE,
+                                              C.byref(info) if sync else None), "cap_instances_set_ex")
         self._instances_n = n
         if not sync:
-            self._instances_keepalive = d  # read on the context's stream after the call returns
+            self._instances_keepalive = (d, o)  # read on the context's stream after the call returns
             return None
         return info
 

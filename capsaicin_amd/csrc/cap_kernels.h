@@ -137,16 +137,25 @@ void launch_query_binary_filtered(const LaunchCfg& cfg, const BvhDev& bvh, const
 
 // ---- instances (instance.hip): cap_instances_set, cap_trace_instances* ----
 // The table on the device.  rec: 4 float4 per instance = the three rows of W (world to object, row r = (W_r0, W_r1, W_r2, W_r3)) and
-// (asfloat(mask), -, -, -); an inert instance has W = 0 and mask 0.  box: 2 float4 per instance = (lo.xyz, k) (hi.xyz, asfloat(index)),
+// (asfloat(mask), asfloat(root of the object's tree), asfloat(object index), -); an inert instance has W = 0 and mask 0.  box: 2 float4 per instance = (lo.xyz, k) (hi.xyz, asfloat(index)),
 // k >= 0 the per-ray inflation factor of tlas_slab (instance.hip), k < 0 for an inert instance or a padding entry.
 // tlas: the top-level tree, an implicit binary tree over the instances in Morton order.  Level 0 holds the instances' box records in
 // that order, level l + 1 entry j the union of level l entries 2 j and 2 j + 1; every level is padded to an even number of entries with
 // k < 0 records, level l starts at entry level_off[l], the last level (`top`) has one entry.
+// objects: what an instance can show -- the objects of cap_objects_set, or one entry, the scene, without an object table.
+struct InstObject
+{
+    double   blo[3], bhi[3];  // the object-space box every reported hit point lies in (the object's bounds + the build's padding)
+    int32_t  root;            // root of the object's tree as BvhDev::root, in the pools the query is given
+    uint32_t reserved;
+};
 struct InstanceBuildArgs
 {
-    const float* descs;  // CapInstanceDesc records, 16 words each (device)
-    uint32_t     n;
-    double       blo[3], bhi[3];  // the object-space box every reported hit point lies in (scene bounds + the build's padding)
+    const float*      descs;  // CapInstanceDesc records, 16 words each (device)
+    uint32_t          n;
+    const InstObject* objects;       // (device)
+    uint32_t          n_objects;
+    const uint32_t*   object_index;  // per instance (device); NULL: all 0.  An index >= n_objects makes the instance inert
     float4*      rec;
     float4*      box;
     float4*      tlas;
@@ -168,9 +177,21 @@ struct TlasDev
     uint32_t        top;
 };
 // mode 0: closest, 1: first accepted hit, 2: occlusion.  q.out as the other queries'; inst_out (closest / first only) may be NULL.
-// f.tri_mask NULL: no per-mesh masks.  Always the binary tree below an instance (DESIGN.md "Instances"); depth = its CapBvhInfo::max_depth.
+// f.tri_mask NULL: no per-mesh masks.  Always a binary tree below an instance (DESIGN.md "Instances"): bvh.nodes / bvh.tris are the
+// pools the instance records' roots refer to -- the scene's tree, or the forest of an object table -- and depth the largest
+// max_depth of the trees in them.
 void launch_query_instances(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const TlasDev& tl, const RayFilter& f, int mode, uint32_t* inst_out,
                             uint32_t depth);
+// An object's tree as a builder left it at its place in the forest (cap_objects_set): nodes = the object's n_tris - 1 nodes, tris its
+// n_tris leaf-order records, both numbered from 0 with triangle ids local to the object.  Adds node_base to inner child references,
+// rec_base to leaf references and first_triangle to the records' id words, in place.
+struct ForestRelocArgs
+{
+    float4*  nodes;
+    float4*  tris;
+    uint32_t n_tris, node_base, rec_base, first_triangle;
+};
+void launch_forest_relocate(hipStream_t stream, const ForestRelocArgs& a);
 
 // ---- shade ----
 struct ShadeArgs

@@ -169,6 +169,19 @@ struct CapContext
     DevBuf<float4>   inst_desc, inst_rec, inst_box, inst_tlas;
     DevBuf<uint32_t> inst_keys[2], inst_vals[2], inst_hist, inst_scan, inst_misc, inst_level_off;
     uint32_t         inst_count = 0, inst_top = 0, inst_nodes = 0;
+    DevBuf<uint32_t> inst_obj;                // each instance's object index (cap_instances_set_ex)
+    bool             inst_obj_on = false;     // ... given with the installed table (false: every instance shows object 0)
+    InstObject       scene_object_host{};     // the scene as the one object of a context without an object table ...
+    DevBuf<InstObject> scene_object;          // ... and its device copy (instances_rebuild)
+    // object table and forest (cap_objects_set, instance.hip); obj_count = 0: no table.  Object k's tree: nodes
+    // [obj_node_base[k], + triangle_count - 1) of forest_nodes, records [obj_rec_base[k], + triangle_count) of forest_tris.
+    std::vector<CapObjectInfo> obj_info;
+    std::vector<uint32_t>      obj_node_base, obj_rec_base;
+    uint32_t                   obj_count = 0, obj_max_depth = 0;
+    DevBuf<float4>             forest_nodes, forest_tris;
+    DevBuf<InstObject>         obj_table;     // per object: padded box and root (k_instance_setup)
+    DevBuf<float4>             obj_tri_raw, obj_tri_box;  // build scratch of the largest object (the builders' tri_raw / tri_box / leaf_tri)
+    DevBuf<uint32_t>           obj_leaf_tri, obj_misc;    // obj_misc: 8 words per object, 6 bounds + depth
     DevBuf<float4>   fan_pairs, fan_singles;  // exhaustive path: fan-pair records (5 float4) and the unpaired triangles (4 float4)
     uint32_t         fan_pair_count = 0, fan_single_count = 0;
     DevBuf<float4>   fan_pairs_nee;           // the pair records again, potential occluders of next-event rays first (update_nee_pairs)
@@ -802,6 +815,7 @@ int cap_scene_upload(CapContext* c, const float* positions, const float* normals
     c->lane1_failed_paths = 0;  // another scene, other buffers: a second batch lane that did not fit before may fit now
     c->tri_mask_on = false;     // instance masks belong to the previous scene's meshes
     c->inst_count  = 0;         // ... and the instance table to its trees
+    c->obj_count   = 0;         // ... and the object table to its mesh table
     return CAP_OK;
 }
 
@@ -1172,7 +1186,101 @@ int cap_materials_upload(CapContext* c, const CapMaterial* materials, uint32_t m
     return CAP_OK;
 }
 
-// World boxes and top-level tree of the installed instance table from the kept descriptors and the current scene bounds: what
+// The object box of k_instance_setup: every point the triangle test can report lies in a leaf box, the triangle's box padded by
+// 1e-5 max(1, |coordinate|) (bvh.hip k_refit); twice that around the bounds, in double
+static InstObject object_box(const float lo3[3], const float hi3[3], int32_t root)
+{
+    InstObject o{};
+    for (int k = 0; k < 3; ++k)
+    {
+        const double lo = lo3[k], hi = hi3[k];
+        const double pad = 2e-5 * std::max(1.0, std::max(std::fabs(lo), std::fabs(hi)));
+        o.blo[k] = lo - pad, o.bhi[k] = hi + pad;
+    }
+    o.root = root;
+    return o;
+}
+
+// The builder cap_bvh_build takes for n triangles under the context's mode; for an object, the host builder is replaced by its
+// device counterpart (include/capsaicin_hip.h cap_objects_set)
+static uint32_t object_builder(const CapContext* c, uint32_t n)
+{
+    const uint32_t mode = c->bvh_build_mode;
+    if (n >= 2 && (mode == CAP_BVH_BUILD_SAH || mode == CAP_BVH_BUILD_SAH_DEVICE ||
+                   (mode == CAP_BVH_BUILD_AUTO && n >= (uint32_t)c->sw.get(SW_AUTO_SAH_TRIANGLES, kAutoSahTriangles))))
+        return CAP_BVH_BUILD_SAH_DEVICE;
+    if (n >= 2 && (mode == CAP_BVH_BUILD_PLOC || (mode == CAP_BVH_BUILD_AUTO && n > kExhaustiveMax))) return CAP_BVH_BUILD_PLOC;
+    return CAP_BVH_BUILD_LBVH;
+}
+
+// The forest of the installed object table from the current vertices: what cap_objects_set, cap_bvh_build and cap_bvh_refit share.
+// Each object's tree is built by the scene's builders on the object's triangle range (offset pointers; the scene's build scratch,
+// which no kept structure lives in, and the forest's own tri_raw / tri_box / leaf_tri so that the scene's stay as they are) straight
+// into its place in the pools, then relocated in place (instance.hip).  The shading records the triangle setup rewrites get the
+// values they hold.  Waits for the stream: depths and bounds are read back.  Nothing when no table is installed; a failure drops it.
+static int objects_rebuild(CapContext* c, const char* what)
+{
+    const uint32_t count = c->obj_count;
+    if (count == 0) return CAP_OK;
+    c->obj_count = 0;  // (until the forest stands)
+    uint32_t max_n = 0;
+    for (const CapObjectInfo& o : c->obj_info) max_n = std::max(max_n, o.triangle_count);
+    const int radius = (int)c->sw.get(SW_PLOC_RADIUS, 16), leaf = (int)c->sw.get(SW_SAHDEV_LEAF, 32);
+    DevBuf<uint32_t> sahdev;  // the surface-area builder's scratch, of no use after the build
+    for (uint32_t k = 0; k < count; ++k)
+    {
+        CapObjectInfo& o = c->obj_info[k];
+        const uint32_t n = o.triangle_count, first = o.first_triangle;
+        o.builder        = object_builder(c, n);
+        BvhBuildArgs a   = bvh_args(c);
+        a.tri_ids = c->tri_ids.p + first, a.tri_count = n;
+        a.shade_tris  = c->shade_tris.p + kShadeRec * (size_t)first;
+        a.tris_sorted = c->forest_tris.p + 4 * (size_t)c->obj_rec_base[k], a.nodes = c->forest_nodes.p + 4 * (size_t)c->obj_node_base[k];
+        a.leaf_tri = c->obj_leaf_tri.p, a.tri_raw = c->obj_tri_raw.p, a.tri_box = c->obj_tri_box.p;
+        a.bounds = c->obj_misc.p + 8 * (size_t)k, a.max_depth = a.bounds + 6;
+        int rc = 0;
+        if (o.builder == CAP_BVH_BUILD_LBVH)
+            launch_bvh_build(c->stream, a);
+        else
+        {
+            HIP_TRY(c->ploc_boxes.ensure(4 * (size_t)max_n));
+            HIP_TRY(c->ploc_ints.ensure(3 * (size_t)max_n + 4));
+            const PlocScratch ps{c->ploc_boxes.p, c->ploc_ints.p};
+            if (o.builder == CAP_BVH_BUILD_SAH_DEVICE)
+            {
+                HIP_TRY(sahdev.ensure(bvh_sah_device_scratch_words(max_n)));
+                rc = launch_bvh_build_sah_device(c->stream, a, ps, sahdev.p, (uint32_t)radius, (uint32_t)(leaf < 1 ? 1 : leaf));
+            }
+            else
+                rc = launch_bvh_build_ploc(c->stream, a, ps, (uint32_t)radius);
+        }
+        if (rc != 0) return fail(CAP_ERR_HIP, "%s: device build of object %u failed (%d)", what, k, rc);
+        launch_forest_relocate(c->stream, ForestRelocArgs{a.nodes, a.tris_sorted, n, c->obj_node_base[k], c->obj_rec_base[k], first});
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<uint32_t> misc(8 * (size_t)count);
+    HIP_TRY(hipMemcpyAsync(misc.data(), c->obj_misc.p, sizeof(uint32_t) * misc.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<InstObject> table(count);
+    uint32_t depth = 0;
+    for (uint32_t k = 0; k < count; ++k)
+    {
+        CapObjectInfo& o = c->obj_info[k];
+        CapBvhInfo     b{};
+        set_bounds(b, misc.data() + 8 * (size_t)k);
+        for (int j = 0; j < 3; ++j) o.bounds_lo[j] = b.bounds_lo[j], o.bounds_hi[j] = b.bounds_hi[j];
+        o.max_depth = misc[8 * (size_t)k + 6];
+        depth       = std::max(depth, o.max_depth);
+        // a one-triangle object has no node: its root is the leaf code of its record
+        table[k] = object_box(o.bounds_lo, o.bounds_hi, o.triangle_count >= 2 ? (int32_t)c->obj_node_base[k] : (int32_t)~c->obj_rec_base[k]);
+    }
+    if (depth > 64) return fail(CAP_ERR_UNSUPPORTED, "%s: object tree depth %u exceeds the 64-entry traversal stack", what, depth);
+    HIP_TRY(hipMemcpy(c->obj_table.p, table.data(), sizeof(InstObject) * count, hipMemcpyHostToDevice));
+    c->obj_count = count, c->obj_max_depth = depth;
+    return CAP_OK;
+}
+
+// World boxes and top-level tree of the installed instance table from the kept descriptors and the current bounds: what
 // cap_instances_set, cap_bvh_build and cap_bvh_refit share.  Enqueues on the context stream; nothing when no table is installed.
 static int instances_rebuild(CapContext* c)
 {
@@ -1180,14 +1288,17 @@ static int instances_rebuild(CapContext* c)
     if (n == 0) return CAP_OK;
     InstanceBuildArgs a{};
     a.descs = reinterpret_cast<const float*>(c->inst_desc.p), a.n = n;
-    // the object box: every point the triangle test can report lies in a leaf box, the triangle's box padded by
-    // 1e-5 max(1, |coordinate|) (bvh.hip k_refit); twice that around the scene bounds, in double
-    for (int k = 0; k < 3; ++k)
+    if (c->obj_count)
+        a.objects = c->obj_table.p, a.n_objects = c->obj_count;
+    else
     {
-        const double lo = c->bvh_info.bounds_lo[k], hi = c->bvh_info.bounds_hi[k];
-        const double pad = 2e-5 * std::max(1.0, std::max(std::fabs(lo), std::fabs(hi)));
-        a.blo[k] = lo - pad, a.bhi[k] = hi + pad;
+        // no object table: the one object is the scene, its tree the scene's
+        c->scene_object_host = object_box(c->bvh_info.bounds_lo, c->bvh_info.bounds_hi, c->tri_count >= 2 ? 0 : ~0);
+        HIP_TRY(c->scene_object.ensure(1));
+        HIP_TRY(hipMemcpyAsync(c->scene_object.p, &c->scene_object_host, sizeof(InstObject), hipMemcpyHostToDevice, c->stream));
+        a.objects = c->scene_object.p, a.n_objects = 1;
     }
+    a.object_index = c->inst_obj_on ? c->inst_obj.p : nullptr;
     a.rec = c->inst_rec.p, a.box = c->inst_box.p, a.tlas = c->inst_tlas.p;
     a.keys[0] = c->inst_keys[0].p, a.keys[1] = c->inst_keys[1].p, a.vals[0] = c->inst_vals[0].p, a.vals[1] = c->inst_vals[1].p;
     a.hist = c->inst_hist.p, a.scan = c->inst_scan.p, a.misc = c->inst_misc.p;
@@ -1346,6 +1457,11 @@ int cap_bvh_build(CapContext* c)
     c->bvh_stale          = false;
     c->visits_built_known = false;  // the first refit measures the boxes this build leaves
     if (const int rc = update_nee_pairs(c)) return rc;
+    if (const int rc = objects_rebuild(c, "cap_bvh_build"))  // the objects' trees from the same vertices (nothing without a table)
+    {
+        c->inst_count = 0;  // (the instances' objects are gone)
+        return rc;
+    }
     return instances_rebuild(c);  // (nothing without a table)
 }
 
@@ -1442,6 +1558,11 @@ int cap_bvh_refit(CapContext* c, CapRefitInfo* out)
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (!c->visits_built_known) c->refit_visits_built = v[1], c->visits_built_known = true;
     c->bvh_stale = false;
+    if (const int rc = objects_rebuild(c, "cap_bvh_refit"))  // the objects' trees: rebuilt, not refitted (nothing without a table)
+    {
+        c->inst_count = 0;
+        return rc;
+    }
     if (const int rc = instances_rebuild(c)) return rc;  // world boxes and TLAS from the new bounds (nothing without a table)
     if (out)
     {
@@ -2403,10 +2524,24 @@ int cap_trace_rays_multi_ex(CapContext* c, const CapRayDesc* device_rays, uint64
 }
 
 // ---- instanced ray queries (instance.hip) ----
-int cap_instances_set(CapContext* c, const CapInstanceDesc* descs, uint32_t count, uint32_t flags, CapInstancesInfo* out)
+namespace
+{
+// `p` is usable as a device array of the context's GPU (what CAP_INSTANCES_DEVICE promises)
+int device_array(CapContext* c, const char* what, const char* name, const void* p)
+{
+    if ((uintptr_t)p & 3u) return fail(CAP_ERR_INVALID_ARG, "%s: %s is not 4-byte aligned", what, name);
+    hipPointerAttribute_t at{};
+    const hipError_t      e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();  // (an unknown pointer is the caller's error, not a sticky one)
+    if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != c->device)
+        return fail(CAP_ERR_INVALID_ARG, "%s: %s is not device memory of device %d", what, name, c->device);
+    return CAP_OK;
+}
+
+int instances_set(CapContext* c, const char* what, const CapInstanceDesc* descs, const uint32_t* object_index, uint32_t count, uint32_t flags,
+                  CapInstancesInfo* out)
 {
     static_assert(sizeof(CapInstanceDesc) == 64, "CapInstanceDesc is 16 words");
-    const char* what = "cap_instances_set";
     if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
     if (flags & ~(uint32_t)CAP_INSTANCES_DEVICE) return fail(CAP_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
     if (count > CAP_INSTANCE_MAX_COUNT) return fail(CAP_ERR_INVALID_ARG, "%s: %u instances exceed CAP_INSTANCE_MAX_COUNT (%u)", what, count, CAP_INSTANCE_MAX_COUNT);
@@ -2417,16 +2552,21 @@ int cap_instances_set(CapContext* c, const CapInstanceDesc* descs, uint32_t coun
             if (descs[i].reserved[0] | descs[i].reserved[1] | descs[i].reserved[2])
                 return fail(CAP_ERR_INVALID_ARG, "%s: descs[%u].reserved must be 0", what, i);
     if (const int rc = query_state(c, what)) return rc;
+    // host object indices are checked here; device ones in k_instance_setup, where an out-of-range one makes the instance inert
+    const uint32_t n_objects = c->obj_count ? c->obj_count : 1u;
+    if (!device && object_index)
+        for (uint32_t i = 0; i < count; ++i)
+            if (object_index[i] >= n_objects)
+                return fail(CAP_ERR_INVALID_ARG, c->obj_count ? "%s: object_index[%u] = %u, the object table has %u objects"
+                                                              : "%s: object_index[%u] = %u without an object table (%u object: the scene)",
+                            what, i, object_index[i], n_objects);
     const auto wall0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(c->device));
     if (device && count)
     {
-        if ((uintptr_t)descs & 3u) return fail(CAP_ERR_INVALID_ARG, "%s: descs is not 4-byte aligned", what);
-        hipPointerAttribute_t at{};
-        const hipError_t      e = hipPointerGetAttributes(&at, descs);
-        if (e != hipSuccess) (void)hipGetLastError();  // (an unknown pointer is the caller's error, not a sticky one)
-        if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != c->device)
-            return fail(CAP_ERR_INVALID_ARG, "%s: descs is not device memory of device %d", what, c->device);
+        if (const int rc = device_array(c, what, "descs", descs)) return rc;
+        if (object_index)
+            if (const int rc = device_array(c, what, "object_index", object_index)) return rc;
     }
     if (count == 0)
     {
@@ -2436,7 +2576,7 @@ int cap_instances_set(CapContext* c, const CapInstanceDesc* descs, uint32_t coun
     }
     uint32_t       off[kTlasMaxLevels], total = 0;
     const uint32_t top = tlas_layout(count, off, &total);
-    if (c->inst_desc.n < 4 * (size_t)count || c->inst_misc.n < 8)
+    if (c->inst_desc.n < 4 * (size_t)count || c->inst_misc.n < 8 || c->inst_obj.n < count)
     {
         HIP_TRY(hipStreamSynchronize(c->stream));  // (grown buffers replace ones an earlier query may still be reading)
         HIP_TRY(c->inst_desc.ensure(4 * (size_t)count));
@@ -2452,12 +2592,17 @@ int cap_instances_set(CapContext* c, const CapInstanceDesc* descs, uint32_t coun
         HIP_TRY(c->inst_scan.ensure(bvh_radix_scan_words(count) + 1));
         HIP_TRY(c->inst_misc.ensure(8));
         HIP_TRY(c->inst_level_off.ensure(kTlasMaxLevels + 1));
+        HIP_TRY(c->inst_obj.ensure(count));
     }
     if ((size_t)total * 2 > c->inst_tlas.n) return fail(CAP_ERR_HIP, "%s: top-level tree of %u entries exceeds its buffer", what, total);
     // ordered on the context stream behind every query enqueued
     HIP_TRY(hipMemcpyAsync(c->inst_desc.p, descs, sizeof(CapInstanceDesc) * (size_t)count, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                            c->stream));
     HIP_TRY(hipMemcpyAsync(c->inst_level_off.p, off, sizeof(uint32_t) * (top + 1), hipMemcpyHostToDevice, c->stream));
+    if (object_index)
+        HIP_TRY(hipMemcpyAsync(c->inst_obj.p, object_index, sizeof(uint32_t) * (size_t)count, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                               c->stream));
+    c->inst_obj_on = object_index != nullptr;
     c->inst_count = count, c->inst_top = top, c->inst_nodes = total - (count + (count & 1u));
     if (const int rc = instances_rebuild(c))
     {
@@ -2472,6 +2617,101 @@ int cap_instances_set(CapContext* c, const CapInstanceDesc* descs, uint32_t coun
         out->count = count, out->inert = inert, out->tlas_nodes = c->inst_nodes, out->tlas_depth = top + 1;
         out->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     }
+    return CAP_OK;
+}
+}  // namespace
+
+int cap_instances_set(CapContext* c, const CapInstanceDesc* descs, uint32_t count, uint32_t flags, CapInstancesInfo* out)
+{
+    return instances_set(c, "cap_instances_set", descs, nullptr, count, flags, out);
+}
+
+int cap_instances_set_ex(CapContext* c, const CapInstanceDesc* descs, const uint32_t* object_index, uint32_t count, uint32_t flags, CapInstancesInfo* out)
+{
+    return instances_set(c, "cap_instances_set_ex", descs, object_index, count, flags, out);
+}
+
+// ---- objects: per-mesh-range trees below the instances (objects_rebuild; instance.hip) ----
+int cap_objects_set(CapContext* c, const CapObjectRange* ranges, uint32_t count, CapObjectsInfo* out)
+{
+    static_assert(sizeof(CapObjectRange) == 8 && sizeof(CapObjectInfo) == 48 && sizeof(CapObjectsInfo) == 24, "the header's object records");
+    const char* what = "cap_objects_set";
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (count > CAP_OBJECT_MAX_COUNT) return fail(CAP_ERR_INVALID_ARG, "%s: %u objects exceed CAP_OBJECT_MAX_COUNT (%u)", what, count, CAP_OBJECT_MAX_COUNT);
+    if (count && !ranges) return fail(CAP_ERR_INVALID_ARG, "%s: ranges is NULL", what);
+    if (const int rc = query_state(c, what)) return rc;
+    const auto wall0 = std::chrono::steady_clock::now();
+    // global triangle ids are assigned mesh by mesh in upload order: a mesh range is a triangle range
+    std::vector<uint64_t> tri_begin(c->mesh_count + 1, 0);
+    for (uint32_t m = 0; m < c->mesh_count; ++m) tri_begin[m + 1] = tri_begin[m] + c->meshes_host[m].index_count / 3;
+    std::vector<CapObjectInfo> info(count);
+    std::vector<uint32_t>      node_base(count), rec_base(count);
+    std::vector<std::pair<uint32_t, uint32_t>> sorted;  // (first mesh, object)
+    uint64_t nodes = 0, recs = 0;
+    for (uint32_t k = 0; k < count; ++k)
+    {
+        const CapObjectRange& r = ranges[k];
+        if (r.mesh_count == 0) return fail(CAP_ERR_INVALID_ARG, "%s: ranges[%u].mesh_count is 0", what, k);
+        if ((uint64_t)r.first_mesh + r.mesh_count > c->mesh_count)
+            return fail(CAP_ERR_INVALID_ARG, "%s: ranges[%u] = meshes %u + %u exceeds the scene's %u", what, k, r.first_mesh, r.mesh_count, c->mesh_count);
+        const uint64_t first = tri_begin[r.first_mesh], n = tri_begin[r.first_mesh + r.mesh_count] - first;
+        if (n == 0) return fail(CAP_ERR_INVALID_ARG, "%s: ranges[%u] holds no triangle", what, k);
+        // the walk's leaf code keeps a record's forest position in kLeafCountShift bits (cap_leaf.h)
+        if (recs + n > kLeafFirstMask) return fail(CAP_ERR_UNSUPPORTED, "%s: forest position %llu of object %u does not fit the traversal-leaf code (limit %u)", what, (unsigned long long)(recs + n), k, kLeafFirstMask);
+        info[k]                = CapObjectInfo{};
+        info[k].first_triangle = (uint32_t)first, info[k].triangle_count = (uint32_t)n, info[k].node_count = (uint32_t)n - 1u;
+        node_base[k] = (uint32_t)nodes, rec_base[k] = (uint32_t)recs;
+        nodes += n - 1, recs += n;
+        sorted.emplace_back(r.first_mesh, k);
+    }
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t j = 1; j < sorted.size(); ++j)
+    {
+        const CapObjectRange& a = ranges[sorted[j - 1].second];
+        if (a.first_mesh + a.mesh_count > sorted[j].first)
+            return fail(CAP_ERR_INVALID_ARG, "%s: ranges[%u] and ranges[%u] overlap", what, sorted[j - 1].second, sorted[j].second);
+    }
+    // from here on the tables change: object indices lose their meaning, so the instance table goes with the old object table
+    c->inst_count = 0;
+    c->obj_count  = 0;
+    if (count == 0)
+    {
+        if (out) *out = CapObjectsInfo{};
+        return CAP_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t max_n = 0;
+    for (const CapObjectInfo& o : info) max_n = std::max(max_n, o.triangle_count);
+    if (c->forest_tris.n < 4 * (size_t)recs || c->forest_nodes.n < 4 * (size_t)std::max<uint64_t>(nodes, 1) || c->obj_table.n < count || c->obj_misc.n < 8 * (size_t)count ||
+        c->obj_tri_raw.n < 4 * (size_t)max_n)
+    {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (grown buffers replace ones an earlier query may still be reading)
+        HIP_TRY(c->forest_tris.ensure(4 * (size_t)recs));
+        HIP_TRY(c->forest_nodes.ensure(4 * (size_t)std::max<uint64_t>(nodes, 1)));
+        HIP_TRY(c->obj_table.ensure(count));
+        HIP_TRY(c->obj_misc.ensure(8 * (size_t)count));
+        HIP_TRY(c->obj_tri_raw.ensure(4 * (size_t)max_n));
+        HIP_TRY(c->obj_tri_box.ensure(2 * (size_t)max_n));
+        HIP_TRY(c->obj_leaf_tri.ensure(max_n));
+    }
+    c->obj_info.swap(info), c->obj_node_base.swap(node_base), c->obj_rec_base.swap(rec_base);
+    c->obj_count = count;
+    if (const int rc = objects_rebuild(c, what)) return rc;
+    if (out)
+    {
+        out->count = count, out->triangles = (uint32_t)recs, out->nodes = (uint32_t)nodes, out->max_depth = c->obj_max_depth;
+        out->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return CAP_OK;
+}
+
+int cap_objects_info(CapContext* c, CapObjectInfo* out, uint32_t capacity, uint32_t* count_out)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_objects_info: ctx is NULL");
+    if (capacity && !out) return fail(CAP_ERR_INVALID_ARG, "cap_objects_info: out is NULL with capacity %u", capacity);
+    if (count_out) *count_out = c->obj_count;
+    const uint32_t n = std::min(capacity, c->obj_count);
+    if (n) std::copy(c->obj_info.begin(), c->obj_info.begin() + n, out);
     return CAP_OK;
 }
 
@@ -2517,11 +2757,18 @@ int trace_instances(CapContext* c, const char* what, const CapRayDesc* rays, uin
     if (const int rc = query_prepare(c, what, n, run)) return rc;
     const TlasDev tl{c->inst_rec.p, c->inst_tlas.p, c->inst_level_off.p, c->inst_top};
     const int     mode = any ? 2 : flt.first_hit ? 1 : 0;
+    // the pools the instance records' roots refer to: the scene's tree, or with an object table the forest
+    uint32_t depth = c->bvh_info.max_depth;
+    if (c->obj_count)
+    {
+        run.bvh.nodes = c->forest_nodes.p, run.bvh.tris = c->forest_tris.p;
+        depth = c->obj_max_depth, run.cfg.stack_entries = depth <= 32 ? 32 : 64;
+    }
     for (uint64_t done = 0; done < n; done += run.per)
     {
         QueryArgs q = query_args(run, rays, n, done);
         q.out       = static_cast<uint8_t*>(out) + done * out_stride;
-        launch_query_instances(run.cfg, run.bvh, q, tl, flt.f, mode, inst ? inst + done : nullptr, c->bvh_info.max_depth);
+        launch_query_instances(run.cfg, run.bvh, q, tl, flt.f, mode, inst ? inst + done : nullptr, depth);
         if (run.traced(any ? "k_query_inst<any>" : "k_query_inst<closest>", done) != CAP_OK) return CAP_ERR_HIP;
     }
     return CAP_OK;

@@ -1,8 +1,11 @@
 // instance.hip — instanced ray queries (cap_instances_set, cap_trace_instances, cap_trace_instances_occlusion), gfx950.
 //
-// One bottom-level structure -- the uploaded scene and its binary tree, read as object space -- and a table of N instances of it, each
-// with an object-to-world transform and a mask.  This file holds the per-instance setup (inverse, conditioning, world box: fp64 on the
-// device, so device descriptors never travel to the host), the top-level tree over the world boxes, and the two-level query kernels.
+// Bottom-level structures -- the uploaded scene and its binary tree, or the objects of cap_objects_set (mesh ranges of the scene, one
+// binary tree each in a forest laid out as the scene's tree), read as object space -- and a table of N instances, each with an
+// object-to-world transform, a mask and the index of the object it shows.  This file holds the per-instance setup (inverse,
+// conditioning, world box: fp64 on the device, so device descriptors never travel to the host), the top-level tree over the world boxes,
+// the two-level query kernels and the relocation of an object's tree into the forest.  Below, "object" is the instance's object:
+// without an object table the one object is the scene.
 //
 // Hit set (include/capsaicin_hip.h): defined from the STORED W = fl32(inverse(M)) and the rounded object-space ray
 // o' = fl(W o + W_t), d' = fl(W d) alone; the closest record is the minimum in (t, instance, triangle) order.  Boxes never decide:
@@ -13,11 +16,14 @@
 //     of the object-space point o' + t d' is  o + t d + A (do + t dd),  do, dd the rounding errors of the twelve dot products:
 //       |do| <= g4 (|W| |o| + |W_t|),  |dd| <= g3 |W| |d|   (g_k = k eps / (1 - k eps), eps = 2^-24; row-sum norms throughout)
 //     so the world ray passes within  e(t) <= g4 kappa (|o| + t |d|) + g4 |A| |W_t|,  kappa = |A| |W|,  of the image of every
-//     object-space point it reports a hit at.  Such a point lies in the object box B (scene bounds + twice the build's leaf padding,
-//     context.hip), its image in the box of A(B)'s corners, so |o + t d| <= X + e(t), X the largest |coordinate| of that box, and
+//     object-space point it reports a hit at.  Such a point lies in the object box B (the object's bounds + twice the build's leaf
+//     padding, context.hip object_box), its image in the box of A(B)'s corners, so |o + t d| <= X + e(t), X the largest |coordinate| of that box, and
 //     t |d| <= |o| + X + e(t):   e(t) <= (g4 kappa (2 |o| + X) + g4 |A| |W_t|) / (1 - g4 kappa).
-//     The part that does not depend on the ray goes into the stored box (k_instance_setup: pad = c eps (kappa X + |A| |W_t|) + 4 eps X,
-//     then rounded outwards), the part that does into tlas_slab: every box is inflated by k |o| per ray, k = 2 c eps kappa the
+//     Per world axis r the same holds with the row sum |A_r| in place of |A| (component r of A v is at most |A_r| |v|):
+//       e_r(t) <= (g4 kappa_r (2 |o| + X) + g4 |A_r| |W_t|) / (1 - g4 kappa),  kappa_r = |A_r| |W| <= kappa,
+//     so a transform that stretches one axis does not pad the others with that axis' error.
+//     The part that does not depend on the ray goes into the stored box (k_instance_setup: pad_r = c eps (kappa_r X + |A_r| |W_t|)
+//     + 4 eps X per axis, then rounded outwards), the part that does into tlas_slab: every box is inflated by k |o| per ray, k = 2 c eps kappa the
 //     largest of its subtree.  c = kInstSlack = 32, eight times g4 / eps: the rest covers the float evaluation of the inflated
 //     planes (2 eps (X + k |o|)), 1 / (1 - g4 kappa) <= 1.001 and the distance-proportional error of the triangle test itself, for
 //     kappa <= CAP_INSTANCE_MAX_CONDITION = 4096, the domain of the proof; an instance beyond it is inert.  The interval test keeps
@@ -77,7 +83,10 @@ __global__ __launch_bounds__(kBlock) void k_instance_setup(InstanceBuildArgs a)
     {
         const float* d = a.descs + 16 * (size_t)i;
         double       m[12], w[12], wd[12], A[12];
-        bool         live = true;
+        // the object: an index beyond the table (device indices are not read on the host) makes the instance inert
+        const uint32_t    obj  = a.object_index ? a.object_index[i] : 0u;
+        bool              live = obj < a.n_objects;
+        const InstObject& ob   = a.objects[live ? obj : 0u];
         for (int k = 0; k < 12; ++k) m[k] = (double)d[k], live = live && finite_d(m[k]);
         const uint32_t mask = f2u(d[12]) & 0xFFu;
         live                = live && invert_affine(m, w);
@@ -93,7 +102,7 @@ __global__ __launch_bounds__(kBlock) void k_instance_setup(InstanceBuildArgs a)
             double wlo[3] = {1e308, 1e308, 1e308}, whi[3] = {-1e308, -1e308, -1e308};
             for (int c = 0; c < 8; ++c)
             {
-                const double p[3] = {(c & 1) ? a.bhi[0] : a.blo[0], (c & 2) ? a.bhi[1] : a.blo[1], (c & 4) ? a.bhi[2] : a.blo[2]};
+                const double p[3] = {(c & 1) ? ob.bhi[0] : ob.blo[0], (c & 2) ? ob.bhi[1] : ob.blo[1], (c & 4) ? ob.bhi[2] : ob.blo[2]};
                 for (int r = 0; r < 3; ++r)
                 {
                     const double x = A[4 * r] * p[0] + A[4 * r + 1] * p[1] + A[4 * r + 2] * p[2] + A[4 * r + 3];
@@ -102,10 +111,12 @@ __global__ __launch_bounds__(kBlock) void k_instance_setup(InstanceBuildArgs a)
             }
             double X = 0.0;
             for (int r = 0; r < 3; ++r) X = fmax(X, fmax(fabs(wlo[r]), fabs(whi[r])));
-            const double wt  = fmax(fabs(wd[3]), fmax(fabs(wd[7]), fabs(wd[11])));
-            const double pad = kInstSlack * kInstEps * (kappa * X + nA * wt) + 4.0 * kInstEps * X;
+            const double wt = fmax(fabs(wd[3]), fmax(fabs(wd[7]), fabs(wd[11]))), nW = norm_inf3(wd);
             for (int r = 0; r < 3; ++r)
             {
+                // the axis' own share of the error: row r of A (head of this file)
+                const double nAr = fabs(A[4 * r]) + fabs(A[4 * r + 1]) + fabs(A[4 * r + 2]);
+                const double pad = kInstSlack * kInstEps * (nAr * nW * X + nAr * wt) + 4.0 * kInstEps * X;
                 // one ulp outwards of the rounded plane: the stored box contains the padded one
                 lo[r] = nextafterf((float)(wlo[r] - pad), -INFINITY), hi[r] = nextafterf((float)(whi[r] + pad), INFINITY);
                 live  = live && finite_f(lo[r]) && finite_f(hi[r]);
@@ -128,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void k_instance_setup(InstanceBuildArgs a)
         a.rec[4 * (size_t)i + 0] = make_float4(wf[0], wf[1], wf[2], wf[3]);
         a.rec[4 * (size_t)i + 1] = make_float4(wf[4], wf[5], wf[6], wf[7]);
         a.rec[4 * (size_t)i + 2] = make_float4(wf[8], wf[9], wf[10], wf[11]);
-        a.rec[4 * (size_t)i + 3] = make_float4(u2f(live ? mask : 0u), 0.f, 0.f, 0.f);
+        a.rec[4 * (size_t)i + 3] = make_float4(u2f(live ? mask : 0u), u2f((uint32_t)ob.root), u2f(obj), 0.f);
         a.box[2 * (size_t)i + 0] = make_float4(lo[0], lo[1], lo[2], kf);
         a.box[2 * (size_t)i + 1] = make_float4(hi[0], hi[1], hi[2], u2f(i));
     }
@@ -243,8 +254,9 @@ __device__ __forceinline__ bool tlas_slab(const Ray& r, const float4 lo, const f
 // Closest (MODE 0) / first accepted (1) / occlusion (2) over the instances, one ray per lane.
 // Top level: no stack.  The tree is implicit, so a node is (level, index), its sibling index ^ 1 and its ancestors index >> levels;
 // `pending` holds one bit per level, set where the walk went to the nearer of two children that both passed and still owes the other.
-// Bottom level: k_query_binary_f's walk of the scene's binary tree on the object-space ray of the contract, with the shared best_t;
-// the lane's LDS slice is that walk's stack alone.
+// Bottom level: k_query_binary_f's walk of the object's binary tree on the object-space ray of the contract, with the shared best_t;
+// the lane's LDS slice is that walk's stack alone.  The tree's root rides in the instance record's mask word (w3.y): the scene's
+// root in the scene's pools, or the object's in the forest's (bvh.nodes / bvh.tris point at either; bvh.root is not read).
 // One loop, three kinds of step -- a top-level node, entering an instance (the ray transform: 12 FMAs and make_ray's divisions), a
 // bottom-level node or leaf -- so that the lanes of a wave that are at the top level advance while others are inside an instance.
 // The two instances under a level-1 node wait in (todo0, todo1), the nearer box first; each is entered only if its entry distance
@@ -343,7 +355,7 @@ __global__ __launch_bounds__(kBlock, inst_blocks(STACK)) void k_query_inst(BvhDe
                 const v3     d  = mk3(dot3(r0, rw.d), dot3(r1, rw.d), dot3(r2, rw.d));
                 if (!query_ray_ok(make_float4(o.x, o.y, o.z, rw.tmin), make_float4(d.x, d.y, d.z, rw.tmax))) continue;
                 r       = make_ray(o, d, rw.tmin, rw.tmax);
-                node    = bvh.root, sp = 0;
+                node    = (int)f2u(w3.y), sp = 0;
                 in_blas = true;
                 continue;
             }
@@ -391,6 +403,33 @@ __global__ __launch_bounds__(kBlock, inst_blocks(STACK)) void k_query_inst(BvhDe
             if (inst_out) inst_out[j] = best_inst;
         }
     }
+}
+
+// An object's tree, built by the scene's builders on the object's triangles alone (local node, record and triangle numbers), made part
+// of the forest in place: node and record numbers of the pools, the scene's triangle ids.
+__global__ __launch_bounds__(kBlock) void k_forest_relocate(ForestRelocArgs a)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n_tris) return;
+    float4 id = a.tris[4 * (size_t)i + 3];
+    id.x      = u2f(f2u(id.x) + a.first_triangle);
+    a.tris[4 * (size_t)i + 3] = id;
+    if (i + 1u >= a.n_tris) return;
+    const float4 q3 = a.nodes[4 * (size_t)i + 3];
+    uint32_t     link[4] = {f2u(q3.x), f2u(q3.y), f2u(q3.z), f2u(q3.w)};
+    for (int k = 0; k < 4; ++k)
+    {
+        if ((int)link[k] >= 0)
+            link[k] += a.node_base;  // an inner node
+        else if (k < 2)
+            link[k] = ~(~link[k] + a.rec_base);  // the binary tree's leaf: ~record
+        else
+        {
+            const uint32_t code = ~link[k];  // the walk's leaf: ~(first | (count - 1) << kLeafCountShift)
+            link[k]             = ~(((code & kLeafFirstMask) + a.rec_base) | (code & ~kLeafFirstMask));
+        }
+    }
+    a.nodes[4 * (size_t)i + 3] = make_float4(u2f(link[0]), u2f(link[1]), u2f(link[2]), u2f(link[3]));
 }
 
 template <auto KERNEL>
@@ -458,6 +497,11 @@ void launch_instances_build(hipStream_t stream, const InstanceBuildArgs& a)
                            a.tlas + 2 * (size_t)off[l], next);
         cnt = next;
     }
+}
+
+void launch_forest_relocate(hipStream_t stream, const ForestRelocArgs& a)
+{
+    if (a.n_tris) hipLaunchKernelGGL(k_forest_relocate, dim3((a.n_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
 }
 
 void launch_query_instances(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const TlasDev& tl, const RayFilter& f, int mode, uint32_t* inst_out,

@@ -447,12 +447,19 @@ int cap_trace_occlusion_ex(CapContext* ctx, const CapRayDesc* device_rays, uint6
 int cap_trace_rays_multi_ex(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits,
                             uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options);
 
-/* ---- instanced ray queries: N transformed instances of the uploaded scene under a device-built top-level tree ----
+/* ---- instanced ray queries: N transformed instances of the uploaded scene, or of objects of it, under a device-built top-level tree ----
  * The uploaded scene and the trees cap_bvh_build makes of it are read as OBJECT space; cap_instances_set installs a table of N
  * instances of it, each with an object-to-world transform and an 8-bit mask, and builds a top-level tree (TLAS) over the instances'
  * world boxes on the device.  cap_trace_instances / cap_trace_instances_occlusion walk TLAS -> ray into object space -> the binary
  * tree of the scene.  Nothing else changes: the plain cap_trace_rays* calls keep tracing the object-space scene, cap_render ignores
  * the table (as it ignores the mesh masks).
+ *
+ * Objects (cap_objects_set, below).  Without an object table an instance shows the whole scene.  With one, the scene is a container
+ * of OBJECTS -- contiguous mesh ranges, hence contiguous ranges of global triangle ids -- each with a binary tree of its own (a
+ * bottom-level structure in DXR's terms), and every instance shows ONE object (cap_instances_set_ex's object_index; plain
+ * cap_instances_set shows object 0).  Everything below holds with "scene" read as "the instance's object": the hit set of an instance
+ * holds triangles of its object only, its world box is the image of the object's bounds, and the walk below it visits the object's
+ * tree alone.  `triangle` stays the scene's global id, mesh masks stay per mesh of the scene.
  *
  * World-to-object.  Per instance the library computes W = fl32(inverse(M)) once, the inverse of the affine map taken in double and
  * each of its twelve entries rounded once to binary32.  W as stored is part of the contract (cap_instances_readback returns it);
@@ -468,8 +475,11 @@ int cap_trace_rays_multi_ex(CapContext* ctx, const CapRayDesc* device_rays, uint
  * Filters (CapTraceOptions): facing is decided in object space from det's sign exactly as in cap_trace_rays_ex and is NOT affected
  * by the instance transform, a mirroring one included (the DXR rule).  A triangle of mesh m in instance i is a candidate iff
  * desc[i].mask & mesh_mask[m] & instance_mask != 0 (instance_mask = 0 means 0xFF; mesh masks are 0xFF unless
- * cap_scene_set_instance_masks set them).  So a caller can pack up to eight different objects into the scene as meshes with masks
- * 1 << k and give each instance the bit of the object it shows.  CAP_RAY_FLAG_ACCEPT_FIRST_HIT on cap_trace_instances returns some
+ * cap_scene_set_instance_masks set them).  The masks are for visibility groups.  They can also stand in for objects -- meshes with
+ * masks 1 << k, each instance given the bit of what it shows -- and that is still the right tool for switching PARTS of an object on
+ * and off per instance (at most eight, sharing one tree); for different objects in different places use cap_objects_set: under the
+ * mask trick every instance has the scene's box and its walk tests every object's triangles before the mask rejects them.
+ * CAP_RAY_FLAG_ACCEPT_FIRST_HIT on cap_trace_instances returns some
  * member of the set, a miss exactly when it is empty.
  * Inert instances.  An instance whose transform has a non-finite entry, is singular, whose inverse does not fit binary32, or whose
  * condition number kappa = ||W^-1||_inf * ||W||_inf (3x3 parts, row-sum norms, W as stored) exceeds CAP_INSTANCE_MAX_CONDITION is
@@ -498,10 +508,17 @@ typedef struct CapInstancesInfo
  * the table; count <= CAP_INSTANCE_MAX_COUNT.  Needs a built tree: CAP_ERR_STATE before cap_bvh_build and while the trees are stale
  * after cap_scene_update_vertices.  Host descriptors are copied before the call returns (the call waits for the stream) and are
  * checked: non-zero reserved words are CAP_ERR_INVALID_ARG.  Device descriptors (4-byte aligned) are copied on the stream; the call
- * is asynchronous unless `out` is given (the inert count is read back).  cap_scene_upload drops the table; cap_bvh_build and
- * cap_bvh_refit keep the descriptors and rebuild world boxes and TLAS from the new scene bounds by the same routine;
+ * is asynchronous unless `out` is given (the inert count is read back).  cap_scene_upload and cap_objects_set drop the table;
+ * cap_bvh_build and cap_bvh_refit keep the descriptors and rebuild world boxes and TLAS from the new bounds by the same routine;
  * cap_scene_set_instance_masks does not touch it. */
 int cap_instances_set(CapContext* ctx, const CapInstanceDesc* descs, uint32_t count, uint32_t flags, CapInstancesInfo* out /* may be NULL */);
+/* cap_instances_set with an object per instance.  object_index lives where descs lives -- `count` host words, or with
+ * CAP_INSTANCES_DEVICE a 4-byte aligned device pointer -- and is copied like the descriptors; NULL means all 0, and
+ * cap_instances_set is this call with NULL.  Without an object table every index must be 0 (the whole scene); with one it selects
+ * the object.  Host indices are checked: one >= the number of objects (>= 1 without a table) is CAP_ERR_INVALID_ARG with nothing
+ * installed.  Device indices are not read on the host: an out-of-range one makes the instance INERT (counted, never hit, empty box). */
+int cap_instances_set_ex(CapContext* ctx, const CapInstanceDesc* descs, const uint32_t* object_index /* may be NULL */, uint32_t count,
+                         uint32_t flags, CapInstancesInfo* out /* may be NULL */);
 /* host arrays, either may be NULL: W (12 floats per instance, row-major 3x4) and the padded world box (lo.xyz, hi.xyz) */
 int cap_instances_readback(CapContext* ctx, float* world_to_object, float* world_boxes);
 /* cap_trace_rays_ex / cap_trace_occlusion_ex in every convention (device pointers, 16-byte alignment of rays and hits, no overlap,
@@ -511,6 +528,45 @@ int cap_trace_instances(CapContext* ctx, const CapRayDesc* device_rays, uint64_t
                         const CapTraceOptions* options /* may be NULL */);
 int cap_trace_instances_occlusion(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded,
                                   const CapTraceOptions* options /* may be NULL */);
+
+/* ---- objects: per-mesh-range bottom-level trees for the instanced queries ----
+ * An object is the mesh range [first_mesh, first_mesh + mesh_count) of the uploaded scene: mesh_count >= 1, at least one triangle,
+ * inside the mesh table.  Ranges are pairwise disjoint, in any order, and need not cover the scene; anything else, or count >
+ * CAP_OBJECT_MAX_COUNT, is CAP_ERR_INVALID_ARG with nothing changed.  Needs a built tree that is not stale (CAP_ERR_STATE), as
+ * cap_instances_set.  count = 0 removes the table: instances are instances of the whole scene again.
+ * cap_objects_set builds one binary tree per object from the current vertices, each with the builder cap_bvh_build would take for a
+ * scene of the object's triangle count under the context's cap_set_bvh_build mode (the AUTO thresholds included); the host builder
+ * CAP_BVH_BUILD_SAH is mapped to CAP_BVH_BUILD_SAH_DEVICE.  CapObjectInfo::builder says which one built an object.  A one-triangle
+ * object has no node.  An object tree deeper than 64 is CAP_ERR_UNSUPPORTED (the scene tree's rule), as is a forest position that does
+ * not fit the traversal-leaf code; the table is then dropped.
+ * Life cycle.  cap_scene_upload drops the object table and the instance table.  cap_objects_set -- a new table or count = 0 -- drops
+ * the INSTANCE table, because object indices change meaning: call cap_instances_set(_ex) again.  cap_bvh_build and cap_bvh_refit
+ * rebuild every object's tree from the current vertices by the same routine (not an in-place refit: the cost is one build per object)
+ * and then the instances' world boxes and TLAS.  The call waits for the device once, to read the trees' depths and bounds.
+ * Memory: the forest holds 64 B per covered triangle (intersection records) and 64 B per node (triangles - 1 per object) beside the
+ * scene's own trees, plus build scratch of about 100 B per triangle of the largest object.
+ * cap_render, the plain queries and the multi-hit queries do not read the table. */
+#define CAP_OBJECT_MAX_COUNT 4096u
+typedef struct CapObjectRange
+{
+    uint32_t first_mesh, mesh_count;
+} CapObjectRange;
+typedef struct CapObjectInfo /* 48 B */
+{
+    uint32_t first_triangle, triangle_count, node_count, max_depth;
+    float    bounds_lo[3], bounds_hi[3]; /* exact min / max of the object's vertices, as CapBvhInfo's */
+    uint32_t builder;                    /* the CAP_BVH_BUILD_* that built it (never AUTO or SAH) */
+    uint32_t reserved;
+} CapObjectInfo;
+typedef struct CapObjectsInfo
+{
+    uint32_t count, triangles, nodes, max_depth; /* objects, covered triangles, forest nodes, largest depth */
+    double   ms;                                 /* host time of the call, the wait for the device included */
+} CapObjectsInfo;
+int cap_objects_set(CapContext* ctx, const CapObjectRange* ranges /* host */, uint32_t count, CapObjectsInfo* out /* may be NULL */);
+/* the first min(capacity, count) entries into `out` (host; may be NULL when capacity is 0), the table's count into *count_out (may be
+ * NULL); 0 objects without a table */
+int cap_objects_info(CapContext* ctx, CapObjectInfo* out, uint32_t capacity, uint32_t* count_out);
 
 /* ---- multi-GPU tile exchange (one gather of tile radiance at frame end) ---- */
 /* floats in this context's tile-ordered radiance buffer: max_tiles_per_shard * 64 * 4 (same on every shard) */
