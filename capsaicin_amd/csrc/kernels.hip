@@ -363,6 +363,116 @@ __device__ __forceinline__ void exhaustive_closest(const BvhDev& bvh, const floa
     }
 }
 
+// Two-phase form of exhaustive_closest() for the LDS-resident small-scene kernels of bounce >= 1 (k_trace_shade, LDS && !ORG;
+// -DCAP_CLOSEST_V1 keeps the one-phase form there for A/B runs: tools/build_variant.sh closestv1 -DCAP_CLOSEST_V1).
+// About 26 of the pair loop's 58 vector instructions only produce t = T * rcp_c(det) and the running (t, id) minimum, for all 64
+// lanes and every triangle, while a lane is inside 2.6-2.8 of the Cornell box's 32 triangles (whole line, either sign of t).
+// Phase 1 (wave-uniform, the counted loop over the records through the scalar cache): the inside test alone -- tvec, q, the three
+// edge products, the two d.n with their sign words, six compares -- recorded per lane as one bit per GLOBAL triangle id.
+// Phase 2 (per lane): for every marked id in ascending order, v0 and n from the LDS copy of tris_by_id, T, det and
+// t = T * rcp_c(det) with tri_scaled()'s operations and operand order -- bit for bit the value the one-phase loop computes --
+// accepted when t > tmin and t < best_t, strict: ascending ids with a strict compare are "minimum t, ties to the lower id".
+// WIDE: more than 32 triangles (up to kExhaustiveMax = 64): two mask words; wave-uniform, chosen once per launch.
+// has_ray: false for the lanes past the end of a class's last chunk; they mark nothing.
+struct PairInside
+{
+    bool     a, b;
+    uint32_t id;
+};
+__device__ __forceinline__ bool tri_inside(float ddn, float e2q_u, float e1q_v)
+{
+    // tri_scaled()'s det, U and V (V = -(e1.q): its negation is folded into the flip mask there and here)
+    const uint32_t s   = f2u(ddn) & 0x80000000u;
+    const float    det = fabsf(ddn);
+    const float    U   = u2f(f2u(e2q_u) ^ (s ^ 0x80000000u));
+    const float    V   = u2f(f2u(e1q_v) ^ s);
+    return (U >= 0.0f) & (V >= 0.0f) & (U + V <= det);
+}
+__device__ __forceinline__ PairInside pair_inside(const Ray& r, const float4* base, uint32_t k)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(4))) const RawPair ConstPair;
+    const RawPair p = ((const ConstPair*)base)[k];
+#else
+    RawPair p;
+    for (int i = 0; i < 20; ++i) p.f[i] = reinterpret_cast<const float*>(base)[20 * k + i];
+#endif
+    const v3 v0 = mk3(p.f[0], p.f[1], p.f[2]), e1 = mk3(p.f[3], p.f[4], p.f[5]), e2 = mk3(p.f[6], p.f[7], p.f[8]),
+             e3 = mk3(p.f[9], p.f[10], p.f[11]), na = mk3(p.f[12], p.f[13], p.f[14]), nb = mk3(p.f[15], p.f[16], p.f[17]);
+    const v3    tvec = r.o - v0;
+    const v3    q    = cross3(tvec, r.d);
+    const float e2q  = dot3(e2, q);  // as in pair_scaled(): U of the first triangle, V (before its negation) of the second
+    PairInside  o;
+    o.a  = tri_inside(dot3(r.d, na), e2q, dot3(e1, q));
+    o.b  = tri_inside(dot3(r.d, nb), dot3(e3, q), e2q);
+    o.id = f2u(p.f[18]);
+    return o;
+}
+template <bool WIDE>
+__device__ __forceinline__ void exhaustive_closest_marked(const BvhDev& bvh, const float4* rec_tab, const Ray& r, bool has_ray, float& best_t,
+                                                          float& best_u, float& best_v, uint32_t& best_gid)
+{
+    best_t = r.tmax, best_u = 0.0f, best_v = 0.0f, best_gid = kInvalidId;
+    // ---- phase 1: candidate mask ----
+    uint32_t m0 = 0u, m1 = 0u;
+    // bit `id` of (m0, m1); id is wave-uniform, so the bit words are scalar and the branch-free two-word form costs selects only
+    auto mark = [&](bool inside, uint32_t id) {
+        if (WIDE)
+        {
+            const uint32_t lo = id < 32u ? 1u << id : 0u, hi = id < 32u ? 0u : 1u << (id - 32u);
+            m0 |= inside ? lo : 0u, m1 |= inside ? hi : 0u;
+        }
+        else
+            m0 |= inside ? 1u << id : 0u;
+    };
+    const uint32_t np = bvh.fan_pair_count;
+#pragma unroll 2
+    for (uint32_t k = 0; k < np; ++k)
+    {
+        const PairInside p = pair_inside(r, bvh.fan_pairs, k);
+        mark(p.a, p.id);
+        mark(p.b, p.id + 1u);
+    }
+    const uint32_t ns = bvh.fan_single_count;
+#pragma unroll 2
+    for (uint32_t j = 0; j < ns; ++j)
+    {
+        float4 t0, t1, t2, t3;
+        load_const_tri(bvh.fan_singles, j, t0, t1, t2, t3);
+        const v3 v0 = mk3(t0.x, t0.y, t0.z), e1 = mk3(t0.w, t1.x, t1.y), e2 = mk3(t1.z, t1.w, t2.x), n = mk3(t2.y, t2.z, t2.w);
+        const v3 q  = cross3(r.o - v0, r.d);
+        mark(tri_inside(dot3(r.d, n), dot3(e2, q), dot3(e1, q)), f2u(t3.x));
+    }
+    if (!has_ray) m0 = 0u, m1 = 0u;
+    // ---- phase 2: the marked triangles of this lane, ascending id ----
+    while ((m0 | (WIDE ? m1 : 0u)) != 0u)
+    {
+        uint32_t id;
+        if (WIDE && m0 == 0u)
+            id = 32u + (uint32_t)__builtin_ctz(m1), m1 &= m1 - 1u;
+        else
+            id = (uint32_t)__builtin_ctz(m0), m0 &= m0 - 1u;
+        const float4*  rec = rec_tab + 4 * (size_t)id;
+        const float4   t0 = rec[0], t2 = rec[2];
+        const v3       v0 = mk3(t0.x, t0.y, t0.z), n = mk3(t2.y, t2.z, t2.w);
+        const v3       tvec = r.o - v0;
+        const float    ddn  = dot3(r.d, n);
+        const uint32_t s    = f2u(ddn) & 0x80000000u;
+        const float    T    = u2f(f2u(dot3(tvec, n)) ^ (s ^ 0x80000000u));
+        const float    tt   = T * rcp_c(fabsf(ddn));
+        const bool     better = (tt > r.tmin) & (tt < best_t);
+        best_t   = better ? tt : best_t;
+        best_gid = better ? id : best_gid;
+    }
+    if (best_gid != kInvalidId)
+    {
+        const float4*   rec = rec_tab + 4 * (size_t)best_gid;
+        const TriScaled s   = tri_scaled(r, rec[0], rec[1], rec[2]);
+        const float     inv = rcp_c(s.det);
+        best_u = s.U * inv, best_v = s.V * inv;
+    }
+}
+
 // Everything of the occlusion test that depends on the ray's DIRECTION and the triangle only: sign mask of d.n, |d.n| and the two
 // interval bounds tmin * |d.n|, tmax * |d.n|.  The reference model's shadow rays of one frame share the direction (the frame's
 // light) and tmin / tmax are constants, so k_trace_any computes these once per (frame slot, fan pair) and workgroup -- the same
@@ -2609,7 +2719,17 @@ __global__ __launch_bounds__(kBlock, FB ? 4 : (EXT ? (FIRST ? 5 : CAP_TS_EXT) : 
             pair_mask         = (uint32_t)__ballot(over);
         }
         __builtin_amdgcn_s_setprio(0);
-        exhaustive_closest<ORG, !LDS>(bvh, rec_tab, r, t, u, v, gid, lds_org, pair_mask);
+#if !defined(CAP_CLOSEST_V1)
+        if constexpr (LDS && !ORG)
+        {
+            if (bvh.tri_count > 32u)  // wave-uniform, the same for the whole launch
+                exhaustive_closest_marked<true>(bvh, rec_tab, r, active, t, u, v, gid);
+            else
+                exhaustive_closest_marked<false>(bvh, rec_tab, r, active, t, u, v, gid);
+        }
+        else
+#endif
+            exhaustive_closest<ORG, !LDS>(bvh, rec_tab, r, t, u, v, gid, lds_org, pair_mask);
         __builtin_amdgcn_s_setprio(3);
         STAMP(st, 1, true);  // triangle loop + winner's record
         const ShadePre pre = shade_prefetch<EXT, FIRST, CARRY>(a, lds_frames, active, pid, carried_r1, carried_r2);
