@@ -34,6 +34,7 @@ __global__ __launch_bounds__(kBlock) void k_tri_setup(BvhBuildArgs a)
     __shared__ float s_lo[kBlock / 64][3], s_hi[kBlock / 64][3];
     float4* tri_box = a.tri_box;
     float   slo[3] = {INFINITY, INFINITY, INFINITY}, shi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool    untame = false;  // a triangle whose stored normals are outside SceneDev::shade_tame's bounds (a NaN fails every compare)
     // a fixed grid strides over the triangles: the scene bounds cost six atomics per WORKGROUP (one per wave and component was 1.6 M
     // atomics on six words at 16.8 M triangles: 17 of the kernel's 18 ms)
     for (uint32_t g = blockIdx.x * kBlock + threadIdx.x; g < a.tri_count; g += gridDim.x * kBlock)
@@ -61,6 +62,13 @@ __global__ __launch_bounds__(kBlock) void k_tri_setup(BvhBuildArgs a)
         st[3] = make_float4(N[3 * i0], N[3 * i0 + 1], N[3 * i0 + 2], T[2 * i1 + 1]);
         st[4] = make_float4(N[3 * i1], N[3 * i1 + 1], N[3 * i1 + 2], T[2 * i2]);
         st[5] = make_float4(N[3 * i2], N[3 * i2 + 1], N[3 * i2 + 2], T[2 * i2 + 1]);
+        {
+            const v3    n0 = mk3(N[3 * i0], N[3 * i0 + 1], N[3 * i0 + 2]), n1 = mk3(N[3 * i1], N[3 * i1 + 1], N[3 * i1 + 2]),
+                     n2 = mk3(N[3 * i2], N[3 * i2 + 1], N[3 * i2 + 2]);
+            const float l0 = dot3(n0, n0), l1 = dot3(n1, n1), l2 = dot3(n2, n2);
+            const bool  len = l0 >= 0.5f && l0 <= 2.0f && l1 >= 0.5f && l1 <= 2.0f && l2 >= 0.5f && l2 <= 2.0f;
+            untame |= !(len && dot3(n0, n1) >= 0.25f && dot3(n0, n2) >= 0.25f && dot3(n1, n2) >= 0.25f);
+        }
         st[6] = make_float4(u2f(id.x), u2f(id.y), u2f(id.z), 0.f);  // (instance, primitive, texture index): rides in the record's second sector
         st[7] = make_float4(0.f, 0.f, 0.f, 0.f);
         lo[0] = fminf(p0.x, fminf(p1.x, p2.x)), lo[1] = fminf(p0.y, fminf(p1.y, p2.y)), lo[2] = fminf(p0.z, fminf(p1.z, p2.z));
@@ -69,6 +77,7 @@ __global__ __launch_bounds__(kBlock) void k_tri_setup(BvhBuildArgs a)
         tri_box[2 * (size_t)g + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
         for (int k = 0; k < 3; ++k) slo[k] = fminf(slo[k], lo[k]), shi[k] = fmaxf(shi[k], hi[k]);
     }
+    if (__any(untame) && (threadIdx.x & 63u) == 0) atomicOr(&a.max_depth[1], 1u);  // (rare: at most one per wave)
     // wave reduction, workgroup reduction, then one atomic per workgroup and component
     for (int k = 0; k < 3; ++k)
     {
@@ -672,7 +681,7 @@ static void bvh_setup(hipStream_t stream, const BvhBuildArgs& a)
     const uint32_t init[6] = {0xFF800000u, 0xFF800000u, 0xFF800000u, 0x007FFFFFu, 0x007FFFFFu, 0x007FFFFFu};
     (void)hipMemcpyAsync(a.bounds, init, sizeof(init), hipMemcpyHostToDevice, stream);
     (void)hipMemsetAsync(a.flags, 0, sizeof(uint32_t) * n, stream);
-    (void)hipMemsetAsync(a.max_depth, 0, sizeof(uint32_t), stream);
+    (void)hipMemsetAsync(a.max_depth, 0, 2 * sizeof(uint32_t), stream);  // depth; 1 = a triangle with untame normals (k_tri_setup)
     hipLaunchKernelGGL(k_tri_setup, dim3(blocks < 4096u ? blocks : 4096u), dim3(kBlock), 0, stream, a);
 }
 

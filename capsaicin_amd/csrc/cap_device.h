@@ -200,6 +200,11 @@ struct SceneDev
     uint32_t          texture_count;
     const float2*     bluenoise;   // 256*256 (R,G)/255
     float             kd_untextured;  // pow(0.75, 2.2), scene.h:55-58
+    // every triangle's stored vertex normals have squared lengths in [0.5, 2] and pairwise dot products >= 0.25 (reduced where the
+    // records are written: bvh.hip k_tri_setup; kept by the context, no read in a render call).  Then |w n0 + u n1 + v n2|^2 is in
+    // [0.24, 2.01] for every u, v >= 0 with u + v <= 1 + 2^-20, which is what the unscaled normalize3 of the fused small-scene
+    // kernels needs (kernels.hip normalize3_tame, DESIGN.md "fp32 arithmetic contract")
+    uint32_t          shade_tame;
     // EXT shading model (no reference counterpart; DESIGN.md "EXT shading model")
     const float2*      bluenoise_ba;  // 256*256 (B,A)/255
     const MaterialDev* materials;     // one per mesh

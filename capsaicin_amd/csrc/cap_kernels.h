@@ -284,7 +284,7 @@ struct BvhBuildArgs
     uint32_t*       parent;         // [2*tri_count] parents of internal nodes then leaves, (parent << 1) | slot
     uint32_t*       flags;          // [tri_count] refit arrival counters
     uint32_t*       bounds;         // 6 orderable-uint encoded floats
-    uint32_t*       max_depth;      // 1
+    uint32_t*       max_depth;      // 2: the tree's depth; 1 if any triangle's stored normals are not tame (SceneDev::shade_tame)
 };
 size_t bvh_radix_blocks(uint32_t n);
 void   launch_bvh_build(hipStream_t stream, const BvhBuildArgs& a);
@@ -390,6 +390,9 @@ void launch_post_chain(hipStream_t stream, const PostChainArgs& a);
 // post.hip's unscaled IEEE division against the compiler's, on the device: out[0] mismatches of log2 over every normal float,
 // out[1] over 2^30 operand pairs of the range it is used on (both must be 0; cap_debug_get(CAP_DEBUG_SELFTEST_DIV))
 void launch_div_selftest(hipStream_t stream, unsigned long long* out_device);
+// kernels.hip's unscaled square roots and divisions of the small-scene shading against the compiler's: out[0] mismatches, out[1]
+// comparisons made; which = 0 the unary forms over every float of their ranges, 1 = ortho_vector's pair over 2^31 candidates
+void launch_shade_forms_selftest(hipStream_t stream, unsigned long long* out_device, uint32_t which);
 // out[(y, x)] = full[(2y + oy, 2x + ox)]: the half-resolution indirect image of LOWRES_INDIRECT (rt_indirect.hlsl:53-59, :176)
 void launch_decimate2x(hipStream_t stream, const float4* full, uint32_t width, uint32_t height, uint32_t ox, uint32_t oy, float4* out);
 }  // namespace cap

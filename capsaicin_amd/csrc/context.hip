@@ -188,11 +188,12 @@ struct CapContext
     uint32_t         fan_pair_nee_count = 0;
     std::vector<float>    fan_pairs_host;     // 20 floats per pair (+ padding records), as uploaded
     std::vector<uint32_t> light_tris_host;    // global ids of the emissive triangles (cap_materials_upload)
-    DevBuf<uint32_t> leaf_tri, keys0, keys1, vals0, vals1, hist, parent, flags, bvh_misc;  // bvh_misc: 6 bounds + depth
+    DevBuf<uint32_t> leaf_tri, keys0, keys1, vals0, vals1, hist, parent, flags, bvh_misc;  // bvh_misc: 6 bounds + depth + 1 if a triangle's stored normals are not tame (SceneDev::shade_tame)
     DevBuf<float4>   ploc_boxes;  // CAP_BVH_BUILD_PLOC scratch (ploc.hip)
     DevBuf<uint32_t> ploc_ints;
     DevBuf<uint32_t> sahdev_words;  // CAP_BVH_BUILD_SAH_DEVICE scratch (ploc.hip)
     CapBvhInfo       bvh_info{};
+    bool             shade_tame = false;  // SceneDev::shade_tame of the shading records as cap_bvh_build / cap_bvh_refit last wrote them
     bool             bvh_ready = false;
     // vertex updates and refit (cap_scene_update_vertices, cap_bvh_refit, refit.hip)
     bool                  bvh_stale = false;             // vertices changed since the trees were last brought up to date
@@ -465,6 +466,7 @@ SceneDev scene_dev(const CapContext* c)
     s.texture_count = (uint32_t)c->texture_host.size();
     s.bluenoise     = c->bluenoise.p;
     s.kd_untextured = pow22_c(0.75f);
+    s.shade_tame    = c->shade_tame ? 1u : 0u;
     s.bluenoise_ba  = c->bluenoise_ba.p;
     s.materials     = reinterpret_cast<const MaterialDev*>(c->materials.p);
     s.material_count = c->materials_ready ? c->mesh_count : 0u;
@@ -1395,6 +1397,7 @@ int cap_bvh_build(CapContext* c)
     bi.max_depth      = n ? (sah ? host_depth : misc[6]) : 0;
     bi.build_ms       = ms;
     if (n) set_bounds(bi, misc);
+    c->shade_tame = n != 0 && misc[7] == 0;
     if (bi.max_depth > 64)
         return fail(CAP_ERR_UNSUPPORTED, "LBVH depth %u exceeds the 64-entry traversal stack", bi.max_depth);
     bi.stack_entries = bi.max_depth <= 32 ? 32 : 64;
@@ -1532,10 +1535,11 @@ int cap_bvh_refit(CapContext* c, CapRefitInfo* out)
     CapBvhInfo& bi = c->bvh_info;
     if (n)
     {
-        uint32_t misc[6];
+        uint32_t misc[8];  // ... and whether the rewritten shading records are tame
         HIP_TRY(hipMemcpyAsync(misc, c->bvh_misc.p, sizeof(misc), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         set_bounds(bi, misc);
+        c->shade_tame = misc[7] == 0;
     }
     // the 8-wide view: records in its leaf order, then its planes bottom-up
     if (c->wide8_nodes)
@@ -1760,6 +1764,30 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
         *value = h[0] + h[1];
         return CAP_OK;
     }
+    case CAP_DEBUG_SELFTEST_SHADE_UNARY:
+    case CAP_DEBUG_SELFTEST_SHADE_DIV2:
+    {
+        HIP_TRY(hipSetDevice(c->device));
+        DevBuf<unsigned long long> d;
+        unsigned long long         h[2] = {0, 0};
+        HIP_TRY(d.ensure(2));
+        HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(h), c->stream));
+        launch_shade_forms_selftest(c->stream, d.p, key == CAP_DEBUG_SELFTEST_SHADE_DIV2 ? 1u : 0u);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        // positive control: two square roots per normal float from 2^-96 on + 3 special operands, the normalize range [2^-3, 4],
+        // x / pi over [0, 2] and f over at least half of it; at least 2^30 pairs inside ortho_vector's guard
+        const unsigned long long floats_sqrt = 0x7f7fffffull - ((127ull - 96ull) << 23) + 1ull;
+        const unsigned long long least = key == CAP_DEBUG_SELFTEST_SHADE_DIV2 ? (1ull << 30) : 2ull * floats_sqrt + 3ull + (5ull << 23) + 1ull + 0x40000001ull + (8ull << 23);
+        if (h[1] < least) return fail(CAP_ERR_HIP, "cap_debug_get: the shading self-test compared %llu of at least %llu cases", h[1], least);
+        *value = h[0];
+        return CAP_OK;
+    }
+    case CAP_DEBUG_SHADE_TAME:
+        if (!c->bvh_ready || c->bvh_stale) return fail(CAP_ERR_STATE, "cap_debug_get: BVH not built or stale");
+        *value = c->shade_tame ? 1u : 0u;
+        return CAP_OK;
     case CAP_DEBUG_NEE_PAIRS:
         if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_debug_get: BVH not built");
         *value = ((uint64_t)(c->fan_pairs_nee.p ? c->fan_pair_nee_count : c->fan_pair_count) << 32) | c->fan_pair_count;

@@ -8,6 +8,7 @@
 #include "cap_kernels.h"
 #include "cap_reproject.h"
 #include "cap_trace.h"
+#include "cap_unscaled.h"
 #include "cap_wide_trace.h"
 
 namespace cap
@@ -1585,6 +1586,60 @@ __device__ __forceinline__ v3 map_to_hemisphere(float r1, float r2, v3 n)
                           fmaf(n.z, cos_theta, fmaf(v.z, b, u.z * a))));
 }
 
+// ---- the same shading arithmetic without the scaling steps of hipcc's sqrtf and `/` (cap_unscaled.h; the fused small-scene
+// kernels of a scene with tame shading records, k_trace_shade<..., TAME>).  Every form below gives the bits of the plain one on the
+// range its operand is proven to lie in; cap_debug_get(CAP_DEBUG_SELFTEST_SHADE_UNARY / _DIV2) compares them on the device over
+// exactly these ranges.  The proofs, operand by operand, are in DESIGN.md "fp32 arithmetic contract".
+constexpr float kNormLo = 0.125f, kNormHi = 4.0f;  // |v|^2 of every vector normalize3_tame is given (tame records: [0.24, 2.01]; the sampled direction: 1 +- 1e-5)
+__device__ __forceinline__ v3 normalize3_tame(v3 v)
+{
+    return v * div_unscaled(1.0f, sqrt_pos(dot3(v, v)));
+}
+// ortho_vector's operands (a, b, g = fmaf(a, a, b * b)) are inside the ranges of sqrt_pos and div2_unscaled: g in [2^-78, 2^80), so
+// that k = sqrt(g) is in [2^-39, 2^40), and each of |a|, |b| zero or >= 2^-80 (both are <= k (1 + 2^-22) < 2^41).  A unit normal next
+// to an axis fails it -- (1, 0, 1e-30): g underflows -- and so does one with a component below 2^-80 beside an ordinary one.
+// Integer compares on the bit patterns: g >= +0 or NaN (above the upper bound), x - 1 wraps for a zero.
+__device__ __forceinline__ bool ortho_in_range(float a, float b, float g)
+{
+    constexpr uint32_t kG0 = (127u - 78u) << 23, kG1 = (127u + 80u) << 23, kX0 = (127u - 80u) << 23;
+    const uint32_t     xa = (f2u(a) & 0x7fffffffu) - 1u, xb = (f2u(b) & 0x7fffffffu) - 1u;
+    return (f2u(g) - kG0 < kG1 - kG0) & ((xa < xb ? xa : xb) >= kX0 - 1u);
+}
+__device__ __forceinline__ v3 map_to_hemisphere_tame(float r1, float r2, v3 n)
+{
+    // ortho_vector under one wave-uniform guard: a wave with a lane outside it takes the plain forms for these three operations and
+    // for the final normalize3 (whose operand is 1 +- 1e-5 only for a finite orthonormal frame)
+    const bool  zn = fabsf(n.z) > 0.0f;
+    const float a = zn ? n.z : n.y, b = zn ? n.y : n.x;
+    const float g = fmaf(a, a, b * b);
+#if defined(CAP_SHADE_ORTHO_PLAIN)  // A/B: ortho_vector and the final normalize3 as they were, no guard (capsaicin_amd/variants/orthoplain.flags)
+    const bool fast = false;
+#else
+    const bool  fast = __ballot(!ortho_in_range(a, b, g)) == 0ull;
+#endif
+    float       q1, q2;
+    if (fast)
+        div2_unscaled(a, b, sqrt_pos(g), q1, q2);
+    else
+    {
+        const float k = sqrtf(g);
+        q1 = a / k, q2 = b / k;
+    }
+    v3       u = zn ? mk3(0.0f, -q1, q2) : mk3(q1, -q2, 0.0f);
+    const v3 v = cross3(u, n);
+    u          = cross3(n, v);
+    float sin_psi, cos_psi;
+    sincos_c((2.0f * kPi) * r1, sin_psi, cos_psi);
+    // r2 = x - floorf(x) is in [0, 1 - 2^-24] (0 on lanes without a sample): 1 - r2 in [2^-24, 1].  cos_theta^2 rounds into [2^-24, 1],
+    // so 1 - cos_theta^2 is 0 or in [2^-24, 1): the zero needs the fix-up
+    const float cos_theta = sqrt_pos(1.0f - r2);
+    const float sin_theta = sqrt_unscaled(1.0f - cos_theta * cos_theta);
+    const float ca = sin_theta * cos_psi, cb = sin_theta * sin_psi;
+    const v3    d = mk3(fmaf(n.x, cos_theta, fmaf(v.x, cb, u.x * ca)), fmaf(n.y, cos_theta, fmaf(v.y, cb, u.y * ca)),
+                        fmaf(n.z, cos_theta, fmaf(v.z, cb, u.z * ca)));
+    return fast ? normalize3_tame(d) : normalize3(d);
+}
+
 // math_functions.h:36-47
 __device__ __forceinline__ void oct_encode(v3 n, float& ox, float& oy)
 {
@@ -1684,7 +1739,8 @@ __device__ __forceinline__ void stage_frames(const ShadeArgs& a, FrameConst* lds
 // slots of its queue entry carry the blue-noise sample of the vertex it will find.  The vertex that emits the ray fetches
 // that sample next to its other inputs, where nothing waits for it before the final stores; the vertex that receives it starts
 // shading without a dependent global load.  carried_* = the .w slots of the entry this vertex came from (bounce >= 1).
-template <bool EXT = false, bool FIRST = true, bool CARRY = false>
+// FAST (k_trace_shade<..., TAME>): the last bounce emits no extension ray, so nothing reads the next vertex's sample
+template <bool EXT = false, bool FIRST = true, bool CARRY = false, bool FAST = false>
 __device__ __forceinline__ ShadePre shade_prefetch(const ShadeArgs& a, const FrameConst* lds_frames, bool active, uint32_t pid,
                                                    float carried_r1 = 0.f, float carried_r2 = 0.f)
 {
@@ -1707,7 +1763,7 @@ __device__ __forceinline__ ShadePre shade_prefetch(const ShadeArgs& a, const Fra
             s.r1 = carried_r1, s.r2 = carried_r2;
         else
             bluenoise4x4(a.scene.bluenoise, x, y, count, s.r1, s.r2);  // rt_indirect.hlsl:149
-        if (CARRY) bluenoise4x4(a.scene.bluenoise, x, y, count + 1u, s.r1n, s.r2n);
+        if (CARRY && (!FAST || a.bounce < a.num_bounces)) bluenoise4x4(a.scene.bluenoise, x, y, count + 1u, s.r1n, s.r2n);
         if (EXT)
         {
             bluenoise4x4(a.scene.bluenoise_ba, x, y, count, s.r3, s.r4);
@@ -1810,7 +1866,9 @@ struct ProbeArgs
     float4*       ring_con = nullptr;
 };
 constexpr uint32_t kWaveRing = 128;  // <= 63 parked + <= 64 new
-template <bool FIRST, bool FB = false, bool CARRY = false, bool SKY_RMW = false, bool PROBE = false>
+// FAST (k_trace_shade<..., TAME>, scenes whose shading records are tame: SceneDev::shade_tame): the square roots and divisions
+// of the vertex in their unscaled forms (map_to_hemisphere_tame and above), and nothing of the direction sample at the last bounce
+template <bool FIRST, bool FB = false, bool CARRY = false, bool SKY_RMW = false, bool PROBE = false, bool FAST = false>
 __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* shade_tab, const ShadePre& pre, uint32_t klass,
                                              uint32_t pid, float4 hit, v3 thr, uint32_t& n_shaded, Stamps& st,
                                              const ProbeArgs probe = ProbeArgs(), uint32_t* n_probed = nullptr, uint32_t ring_head = 0,
@@ -1881,7 +1939,8 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
             const float4  s0 = tab[0], s1 = tab[1], s2 = tab[2], s3 = tab[3], s4 = tab[4], s5 = tab[5];
             const float   u = hit.x, v = hit.y, w = (1.0f - u) - v;
             auto          mix = [&](float c0, float c1, float c2) { return fmaf(c2, v, fmaf(c1, u, c0 * w)); };
-            const v3      n = normalize3(mk3(mix(s3.x, s4.x, s5.x), mix(s3.y, s4.y, s5.y), mix(s3.z, s4.z, s5.z)));
+            const v3      nm = mk3(mix(s3.x, s4.x, s5.x), mix(s3.y, s4.y, s5.y), mix(s3.z, s4.z, s5.z));
+            const v3      n  = FAST ? normalize3_tame(nm) : normalize3(nm);  // tame records: |nm|^2 in [0.24, 2.01] (bvh.hip k_tri_setup)
             p = mk3(mix(s0.x, s1.x, s2.x), mix(s0.y, s1.y, s2.y), mix(s0.z, s1.z, s2.z));
             // scene.h:52-61 GetMaterial
             v3       kd   = mk3(a.scene.kd_untextured, a.scene.kd_untextured, a.scene.kd_untextured);
@@ -1956,16 +2015,26 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
                     contrib     = FIRST ? c : thr * c;  // rt_direct_lighting.hlsl:77 / rt_indirect.hlsl:136
                 }
                 // rt_indirect.hlsl:149-170
-                dir             = map_to_hemisphere(pre.r1, pre.r2, n);
-                const float ndd = dot3(n, dir);
-                const float pdf = fmaxf(0.0f, ndd) / kPi;  // shading.h:19-22
-                if (!(pdf < 1e-5f))
+                // the reference traces one more ray after the last bounce whose payload is never read (:91,:173): at that bounce
+                // (launch-uniform) no extension ray is emitted.  FAST: the sampled direction, its pdf and the throughput feed nothing
+                // else there and are not computed
+                const bool more = a.bounce < a.num_bounces;
+                if (!FAST || more)
                 {
-                    const float f = (kInvPi * fmaxf(ndd, 0.0f)) / pdf;
-                    thr           = thr * f;
-                    if (!FIRST) thr = thr * kd;
-                    // the reference traces one more ray after the last bounce whose payload is never read (:91,:173)
-                    emit_ext = a.bounce < a.num_bounces && (!FIRST || pre.indirect_on);
+                    dir             = FAST ? map_to_hemisphere_tame(pre.r1, pre.r2, n) : map_to_hemisphere(pre.r1, pre.r2, n);
+                    const float ndd = dot3(n, dir);
+                    // FAST: n and dir are unit vectors (or dir is NaN: numerator 0), so the numerator is 0 or in (0, 1.01].  From 2^-80 on
+                    // the quotient has the bits of the plain one; below, it is some finite value < 2^-78, which `pdf < 1e-5f` rejects like
+                    // the plain quotient.  Past that test the numerator of f is >= 0.99e-5 and its denominator >= 1e-5.
+                    const float pdf = FAST ? div_unscaled(fmaxf(0.0f, ndd), kPi) : fmaxf(0.0f, ndd) / kPi;  // shading.h:19-22
+                    if (!(pdf < 1e-5f))
+                    {
+                        const float fn = kInvPi * fmaxf(ndd, 0.0f);
+                        const float f  = FAST ? div_unscaled(fn, pdf) : fn / pdf;
+                        thr            = thr * f;
+                        if (!FIRST) thr = thr * kd;
+                        emit_ext = more && (!FIRST || pre.indirect_on);
+                    }
                 }
             }
         }
@@ -2484,9 +2553,13 @@ void launch_shade(const LaunchCfg& cfg, const ShadeArgs& args, bool ext, bool fe
 #endif
 // LDS: scenes of at most kExhaustiveMax triangles keep their shading records (96 B each) and intersection records in LDS
 // (<= 10 KB per workgroup), so the gathers by hit triangle after the loop are ds_reads instead of a global round trip.
-template <bool FIRST, bool EXT, bool FB = false, bool LDS = false>
+// TAME: the scene's shading records are tame (SceneDev::shade_tame, established where they are written), which is what lets the
+// vertex's normalize3 -- and with it everything downstream of a unit normal -- take the unscaled forms (shade_vertex FAST).  Chosen
+// at launch like LDS; only the reference model's kernels with the scene in LDS have the instantiation.
+template <bool FIRST, bool EXT, bool FB = false, bool LDS = false, bool TAME = false>
 __global__ __launch_bounds__(kBlock, FB ? 4 : (EXT ? (FIRST ? 5 : CAP_TS_EXT) : (FIRST ? CAP_TS_FIRST : CAP_TS_NEXT))) void k_trace_shade(BvhDev bvh, ShadeArgs a)
 {
+    static_assert(!TAME || (!EXT && !FB && LDS), "TAME: reference model, scene in LDS");
     constexpr bool CARRY    = !EXT;
     const uint32_t Ppad     = a.screen.pixels_padded;
     // FIRST: the identity queue of the whole batch, chunk = slot * (Ppad / 64) + 64-pixel group.  Otherwise: chunk slots of the
@@ -2732,7 +2805,7 @@ __global__ __launch_bounds__(kBlock, FB ? 4 : (EXT ? (FIRST ? 5 : CAP_TS_EXT) : 
             exhaustive_closest<ORG, !LDS>(bvh, rec_tab, r, t, u, v, gid, lds_org, pair_mask);
         __builtin_amdgcn_s_setprio(3);
         STAMP(st, 1, true);  // triangle loop + winner's record
-        const ShadePre pre = shade_prefetch<EXT, FIRST, CARRY>(a, lds_frames, active, pid, carried_r1, carried_r2);
+        const ShadePre pre = shade_prefetch<EXT, FIRST, CARRY, TAME>(a, lds_frames, active, pid, carried_r1, carried_r2);
         if (FIRST && slot == a.aov_slot)
         {
             // rt_primary_visibility.hlsl:46: (uv, asfloat(InstanceID), asfloat(PrimitiveIndex)); a miss keeps uv = 0, ids = ~0u
@@ -2761,7 +2834,7 @@ __global__ __launch_bounds__(kBlock, FB ? 4 : (EXT ? (FIRST ? 5 : CAP_TS_EXT) : 
         }
         else
         {
-            shade_vertex<FIRST, FB, CARRY, false, PROBE>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr, n_shaded, st, probe, &n_probed,
+            shade_vertex<FIRST, FB, CARRY, false, PROBE, TAME>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr, n_shaded, st, probe, &n_probed,
                                                          ring_head, &ring_n);
             if (PROBE && ring_n >= 64u) trace_ring(64u);
         }
@@ -2793,9 +2866,91 @@ extern "C" int cap_debug_stamps(unsigned long long* out, int reset)
 }
 #endif
 
+// cap_debug_get(CAP_DEBUG_SELFTEST_SHADE_UNARY / _DIV2): the unscaled forms of the small-scene shading against the plain sqrtf and `/`
+// compiled in the same kernel, bit for bit, over every float of the range each is used on (out[0]: mismatches, out[1]: comparisons made).
+//   which 0: sqrt_pos and sqrt_unscaled over every normal x >= 2^-96 (both), sqrt_unscaled at +0, -0 and +inf;
+//            1 / sqrt(x) as normalize3_tame computes it over every x in [kNormLo, kNormHi];
+//            x / kPi over x = 0 and every x in [2^-80, 2]; over every 0 < x < 2^-80, denormals included, the unscaled quotient must be
+//            finite and below 1e-5 (what `pdf < 1e-5f` needs of it);
+//            f = (kInvPi x) / (x / kPi) over every x in [0, 2] whose pdf passes !(pdf < 1e-5f).
+//   which 1: ortho_vector's sqrt and two quotients over 2^31 pseudo-random (a, b), signs, zeros and -0 included, of which those inside the
+//            guard (ortho_in_range, the kernel's own) are compared: the host asks for >= 2^30.
+__device__ __forceinline__ uint32_t selftest_hash32(uint32_t x)
+{
+    x ^= x >> 16, x *= 0x7feb352du, x ^= x >> 15, x *= 0x846ca68bu, x ^= x >> 16;
+    return x;
+}
+__global__ __launch_bounds__(kBlock) void k_shade_forms_selftest(unsigned long long* out, uint32_t which)
+{
+    const uint32_t     tid = blockIdx.x * kBlock + threadIdx.x, total = gridDim.x * kBlock;
+    unsigned long long bad = 0, n = 0;
+    auto               differ = [](float x, float y) { return f2u(x) != f2u(y) ? 1u : 0u; };
+    if (which == 0)
+    {
+        for (uint64_t b = ((127ull - 96ull) << 23) + tid; b <= 0x7f7fffffull; b += total)
+        {
+            const float x = u2f((uint32_t)b), s = sqrtf(x);
+            bad += differ(sqrt_pos(x), s) + differ(sqrt_unscaled(x), s), n += 2;
+        }
+        if (tid < 3)
+        {
+            const float x = tid == 0 ? 0.0f : (tid == 1 ? -0.0f : __builtin_inff());
+            bad += differ(sqrt_unscaled(x), sqrtf(x)), ++n;
+        }
+        for (uint64_t b = (uint64_t)f2u(kNormLo) + tid; b <= f2u(kNormHi); b += total)
+        {
+            const float x = u2f((uint32_t)b);
+            bad += differ(div_unscaled(1.0f, sqrt_pos(x)), 1.0f / sqrtf(x)), ++n;
+        }
+        for (uint64_t b = tid; b <= f2u(2.0f); b += total)
+        {
+            const float x = u2f((uint32_t)b), pdf = x / kPi, fast = div_unscaled(x, kPi);
+            if (b == 0 || b >= ((127ull - 80ull) << 23))
+                bad += differ(fast, pdf);
+            else
+                bad += (fast < 1e-5f && fast > -1e-5f) ? 0u : 1u;  // (false for NaN and inf)
+            ++n;
+            if (!(pdf < 1e-5f)) bad += differ(div_unscaled(kInvPi * fmaxf(x, 0.0f), pdf), (kInvPi * fmaxf(x, 0.0f)) / pdf), ++n;
+        }
+    }
+    else
+    {
+        for (uint64_t i = tid; i < (1ull << 31); i += total)
+        {
+            const uint32_t h0 = selftest_hash32((uint32_t)i), h1 = selftest_hash32((uint32_t)i ^ 0x9e3779b9u), h2 = selftest_hash32(h0 + h1);
+            // exponent fields: the larger operand 2^-45 .. 2^44, the other 0 .. 95 binades below it (both ends beyond the guard)
+            const uint32_t e1 = 82u + h2 % 90u, d = (h2 >> 8) % 96u, e0 = e1 > d ? e1 - d : 1u;
+            float          p = u2f((e1 << 23) | (h0 & 0x007fffffu) | ((h2 << 3) & 0x80000000u));
+            float          q = u2f((e0 << 23) | (h1 & 0x007fffffu) | ((h2 << 2) & 0x80000000u));
+            if ((h2 >> 24 & 7u) == 0u) q = (h2 & 0x08000000u) ? 0.0f : -0.0f;
+            const bool  sw = (h2 >> 27 & 1u) != 0u;
+            const float a = sw ? q : p, b = sw ? p : q, g = fmaf(a, a, b * b);
+            if (!ortho_in_range(a, b, g)) continue;
+            const float k = sqrtf(g), kf = sqrt_pos(g);
+            float       qa, qb;
+            div2_unscaled(a, b, kf, qa, qb);
+            bad += differ(kf, k) + differ(qa, a / k) + differ(qb, b / k), ++n;
+        }
+    }
+    if (bad) atomicAdd(&out[0], bad);
+    atomicAdd(&out[1], n);
+}
+
+void launch_shade_forms_selftest(hipStream_t stream, unsigned long long* out_device, uint32_t which)
+{
+    hipLaunchKernelGGL(k_shade_forms_selftest, dim3(4096), dim3(kBlock), 0, stream, out_device, which);
+}
+
 void launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback)
 {
     const bool lds = bvh.tri_count <= kExhaustiveMax;
+    // the unscaled forms: reference model, scene in LDS, tame shading records (-DCAP_SHADE_IEEE keeps the plain sqrtf and `/`
+    // everywhere for A/B runs: capsaicin_amd/variants/shadeieee.flags)
+#if defined(CAP_SHADE_IEEE)
+    const bool tame = false;
+#else
+    const bool tame = lds && !ext && args.scene.shade_tame != 0;
+#endif
     if (args.bounce == 0)
     {
         const uint32_t chunks = (args.screen.pixels_padded >> 6) * args.n_slots;
@@ -2807,6 +2962,8 @@ void launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs
             hipLaunchKernelGGL((k_trace_shade<true, true, false, true>), grid, block, 0, cfg.stream, bvh, args);
         else if (ext)
             hipLaunchKernelGGL((k_trace_shade<true, true, false, false>), grid, block, 0, cfg.stream, bvh, args);
+        else if (tame)
+            hipLaunchKernelGGL((k_trace_shade<true, false, false, true, true>), grid, block, 0, cfg.stream, bvh, args);
         else if (lds)
             hipLaunchKernelGGL((k_trace_shade<true, false, false, true>), grid, block, 0, cfg.stream, bvh, args);
         else
@@ -2822,6 +2979,8 @@ void launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs
         hipLaunchKernelGGL((k_trace_shade<false, false, true, true>), grid, block, 0, cfg.stream, bvh, args);
     else if (feedback)
         hipLaunchKernelGGL((k_trace_shade<false, false, true, false>), grid, block, 0, cfg.stream, bvh, args);
+    else if (tame)
+        hipLaunchKernelGGL((k_trace_shade<false, false, false, true, true>), grid, block, 0, cfg.stream, bvh, args);
     else if (lds)
         hipLaunchKernelGGL((k_trace_shade<false, false, false, true>), grid, block, 0, cfg.stream, bvh, args);
     else

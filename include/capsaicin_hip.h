@@ -283,6 +283,15 @@ enum
      * support the scene's convex hull with every light at a safe distance inside cannot occlude a segment between a scene point and a
      * light point under the intersection contract (rule and error bound: context.hip update_nee_pairs) and are left out. */
     CAP_DEBUG_NEE_PAIRS           = 10,
+    /* The fused small-scene kernels evaluate the square roots and divisions of a vertex's shading without the scaling steps of the
+     * compiler's IEEE expansions where the operands cannot trigger them (csrc/cap_unscaled.h).  SELFTEST_SHADE_UNARY (get, ~1 s): every
+     * such unary form against the plain one over every float of its range; SELFTEST_SHADE_DIV2 (get): the pair of quotients of the
+     * tangent frame over more than 2^30 operand pairs inside its guard.  Both return the number of results that differ in any bit: 0.
+     * SHADE_TAME (get, after cap_bvh_build / cap_bvh_refit): 1 if every triangle's stored vertex normals have squared lengths in
+     * [0.5, 2] and pairwise dot products >= 0.25 -- what those kernels need to take the unscaled forms; 0: they take the plain ones. */
+    CAP_DEBUG_SELFTEST_SHADE_UNARY = 11,
+    CAP_DEBUG_SELFTEST_SHADE_DIV2  = 12,
+    CAP_DEBUG_SHADE_TAME           = 13,
     /* A/B and diagnostic switches of the build and render paths (which kernels trace the camera and the shadow rays, one or two batch
      * lanes, the builders' parameters ...): ONE table per context, key = SWITCH_BASE + cap_debug_switch_index("CAP_..."), the names being
      * the environment variables that fill the table once, at cap_ctx_create (tools set those around a whole process; nothing else in the

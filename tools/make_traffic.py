@@ -16,12 +16,15 @@ sys.path.insert(0, root)
 import bench  # noqa: E402
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
-# key -> (workload whose passes are read, kernel name)
-KERNELS = {"headline": ("cornell", "k_trace_shade<false, false, false, true>"), "ext": ("ext", "k_trace_shade<false, true, false, true>"),
+# key -> (workload whose passes are read, kernel name: a substring of the profiler's).  The k_trace_shade names stop before the last
+# template argument (TAME): the headline launches <..., true> for a scene with tame shading records and <..., false> otherwise or in a
+# -DCAP_SHADE_IEEE build, never both in one run
+HEADLINE, EXT = "k_trace_shade<false, false, false, true", "k_trace_shade<false, true, false, true"
+KERNELS = {"headline": ("cornell", HEADLINE), "ext": ("ext", EXT),
            "tree": ("tree", "k_trace_closest8"), "tree_shade": ("tree", "k_shade<"), "tree_any": ("tree", "k_trace_any<"),
            "tree_primary": ("tree", "k_primary_shade"),
            "big": ("big", "k_trace_closest8"), "big_shade": ("big", "k_shade<"), "big_any": ("big", "k_trace_any"),
-           "config3": ("config3", "k_trace_shade<false, true, false, true>"), "config5": ("config5", "k_trace_shade<false, true, false, true>")}
+           "config3": ("config3", EXT), "config5": ("config5", EXT)}
 # every kernel of a render step (tree path): bench.py big_variant.step_traffic = the FRAME's measured bytes, not one kernel's
 STEP_KERNELS = ("k_trace_closest8", "k_trace_any", "k_shade<", "k_raygen_identity", "k_resolve", "k_primary_shade", "k_trace_primary")
 
@@ -75,8 +78,8 @@ def static_issue_costs():
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         for src, keys in (("trace8.hip", {"k_trace_closest8": "k_trace_closest8"}),
-                          ("kernels.hip", {"k_trace_shade<false, false, false, true>": "k_trace_shadeILb0ELb0ELb0ELb1E",
-                                           "k_trace_shade<false, true, false, true>": "k_trace_shadeILb0ELb1ELb0ELb1E", "k_shade<": "k_shadeILb0E",
+                          ("kernels.hip", {HEADLINE: "k_trace_shadeILb0ELb0ELb0ELb1ELb%dE" % (os.environ.get("CAP_LIB_VARIANT") != "shadeieee"),
+                                           EXT: "k_trace_shadeILb0ELb1ELb0ELb1ELb0E", "k_shade<": "k_shadeILb0E",
                                            "k_trace_any<": "k_trace_anyILi24E", "k_primary_shade": "k_primary_shadeILb0E"})):
             lst = os.path.join(tmp, src + ".s")
             try:
