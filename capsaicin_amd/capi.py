@@ -575,6 +575,7 @@ class Renderer:
     DEBUG_QUEUE_CAPACITY_DIV, DEBUG_WIDE_DEPTH_LIMIT, DEBUG_WIDE_IN_USE, DEBUG_FAIL_LANE1, DEBUG_LANES_USED = 1, 2, 3, 4, 5
     DEBUG_QUEUE_CANARY_FILL, DEBUG_QUEUE_CANARY_BEHIND, DEBUG_QUEUE_CANARY_USED, DEBUG_SELFTEST_DIV, DEBUG_NEE_PAIRS = 6, 7, 8, 9, 10
     DEBUG_SELFTEST_SHADE_UNARY, DEBUG_SELFTEST_SHADE_DIV2, DEBUG_SHADE_TAME = 11, 12, 13
+    DEBUG_CAMERA_CULL = 14
 
     def debug_set(self, key, value):
         _check(lib().cap_debug_set(self.ctx, key, value), "cap_debug_set")

@@ -232,6 +232,9 @@ struct ShadeArgs
     uint32_t          wave_ring;
     uint32_t          cull_camera_pairs;  // bounce 0 of the small-scene path: the camera basis is orthonormal, so a tile may skip the pairs off its screen area
 };
+// Pixels the bounce-0 kernel grows every fan pair's screen bounds by (kernels.hip lds_bounds).  The host's gate for
+// cull_camera_pairs (context.hip cap_render) allows a camera basis to move a projected point by an eighth of it.
+constexpr float kCameraCullPad = 2.0f;
 // feedback: vertices of bounce >= 1 that the previous frame saw take its shaded colour and end the path (rt_indirect.hlsl:116-145;
 // reference shading model only)
 void launch_shade(const LaunchCfg& cfg, const ShadeArgs& args, bool ext, bool feedback = false);

@@ -219,6 +219,7 @@ struct CapContext
     uint32_t      lane1_failed_bounces = 0, lane1_retry_tick = 0;
     uint32_t      lanes_last_render = 0;       // cap_debug_get(CAP_DEBUG_LANES_USED)
     uint32_t      last_class_capacity = 0;     // sub-queue capacity of the last cap_render batch (CAP_DEBUG_QUEUE_CANARY_*)
+    uint32_t      last_cull_camera_pairs = 0;  // ShadeArgs::cull_camera_pairs of the last cap_render batch (CAP_DEBUG_CAMERA_CULL)
     uint32_t      traversal_mode  = CAP_TRAVERSAL_AUTO;
     uint32_t      bvh_build_mode  = CAP_BVH_BUILD_AUTO;
 
@@ -918,18 +919,23 @@ int cap_bluenoise_upload(CapContext* c, const uint8_t* rgba8)
 // "Lambert+GGX" step, docs/experiments.md (48)); a pair that provably never reports an occlusion is moved behind the count that loop runs to.
 //
 // Rule (in double, over the vertices as uploaded).  A pair is left out iff for BOTH of its triangles, with plane (v0, n):
-//   (i)  every scene vertex lies on one closed side of the plane (signed distance <= 1e-6 D on the other, D = the scene's diagonal): the
-//        plane supports the scene's convex hull, so p (a convex combination of scene vertices) and y are both on its inner side;
-//   (ii) every vertex of every light triangle is at least delta = 1e-2 * D * Dv inside it, Dv = the largest distance from v0 to a scene
-//        vertex (numbers in scene units: the bound is against the contract's ABSOLUTE tmin = 1e-4).
+//   (i)  every scene vertex lies on one closed side of the plane, at most eps = 2.5e-7 * Dv beyond it (Dv = the largest distance from
+//        v0 to a scene vertex): the plane supports the scene's convex hull to within eps, so p (a convex combination of scene vertices)
+//        is at most eps outside it;
+//   (ii) every vertex of every light triangle is at least delta = 1e-2 * D * Dv inside it, D = the scene's diagonal (numbers in scene
+//        units: the bound is against the contract's ABSOLUTE tmin = 1e-4).
 // Why that is exact under the intersection contract, whose occlusion test is  tmin * det < T < tmax * det  with
 // T = +-(p - v0).n, det = |d.n|, d the unit direction, tmax = 0.999 |y - p|:  in exact arithmetic the segment meets the plane at t* =
 // T / det, and with both ends on the inner side t* <= 0 or t* >= |y - p| + delta / sin(theta) (theta = the angle between d and the plane),
-// never inside (tmin, tmax).  The computed T differs from the exact one by at most ~4 ulp of |p - v0| |n| (a three-term fma chain on a
+// never inside (tmin, tmax).  A p that is s <= eps OUTSIDE the plane crosses it on its way in, at t* = s |y - p| / (s + h) with h >= delta
+// the light point's depth: t* <= eps D / delta = 2.5e-5, a quarter of tmin.  (eps was 1e-6 D until the tests built the case: a decal
+// 1e-6 D outside a wall whose Dv is half the room, segments 1.5 Dv long, t* = 1.5e-4 -- inside the interval, where the wall, culled,
+// cannot shadow the decal next to its edge; tests/pair_cull_support.py nee_truth, tests/test_pair_culls_gpu.py N3.)
+// The computed T differs from the exact one by at most ~4 ulp of |p - v0| |n| (a three-term fma chain on a
 // difference that is exact to an ulp; p itself is off its surface by as much): |t_computed - t*| <= 2.4e-7 |p - v0| / sin(theta) --
 // the classic grazing-ray blow-up ((25), (64) of docs/experiments.md closed two earlier culls over it).  (ii) bounds the grazing angle:
 // sin(theta) >= delta / |y - p| >= delta / D, so the error is below 2.4e-7 * Dv * D / delta = 2.4e-5, a quarter of tmin on the near side
-// (t* <= 0 stays below tmin) and nothing against the 1e-3 |y - p| + delta between tmax and t* on the far side.  The ceiling of the
+// (t* <= 2.5e-5 stays below tmin) and nothing against the 1e-3 |y - p| + delta between tmax and t* on the far side.  The ceiling of the
 // Cornell box (its lamp hangs 1 cm below it: rays from the ceiling's rim to the lamp graze it) fails (ii) and stays in the list, as
 // does every pair that is not a hull face.  tests: the EXT parity tests run this list; `tools/build_variant.sh neecheck -DCAP_NEE_CHECK`
 // runs both lists on every ray and counts disagreements in CapStats::guard_shade (0 over BASELINE configs[2]'s 8 G next-event rays).
@@ -1074,7 +1080,7 @@ static int update_nee_pairs(CapContext* c)
                 smin = std::min(smin, sd), smax = std::max(smax, sd);
                 dv   = std::max(dv, std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]));
             }
-            const double tol = 1e-6 * D;
+            const double tol = 2.5e-7 * dv;  // (i): t* of a point this far outside stays below tmin / 4, see above
             double       sign;
             if (smax <= tol)
                 sign = -1.0;  // the scene lies on the negative side
@@ -1788,6 +1794,7 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
         if (!c->bvh_ready || c->bvh_stale) return fail(CAP_ERR_STATE, "cap_debug_get: BVH not built or stale");
         *value = c->shade_tame ? 1u : 0u;
         return CAP_OK;
+    case CAP_DEBUG_CAMERA_CULL: *value = c->last_cull_camera_pairs; return CAP_OK;
     case CAP_DEBUG_NEE_PAIRS:
         if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_debug_get: BVH not built");
         *value = ((uint64_t)(c->fan_pairs_nee.p ? c->fan_pair_nee_count : c->fan_pair_count) << 32) | c->fan_pair_count;
@@ -2038,14 +2045,29 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
         sa.planes = Planes{L.pl_color.p, L.pl_direct.p, L.pl_albedo.p, c->aov_geo.p, c->aov_nd.p};
         sa.n_slots = ns, sa.num_bounces = D, sa.max_count = max_count, sa.aov_slot = aov_slot, sa.shaded_counter = c->shaded_counter.p;
         {
-            // screen-space culling of bounce 0 inverts primary_dir (camera.h:39-63), which needs an orthonormal basis
+            // Screen-space culling of bounce 0 inverts primary_dir (camera.h:39-63) with the transpose of (right, up, forward), which is
+            // the inverse only for an orthonormal basis.  With G = the basis' Gram matrix and skew = max |G - I|, a ray through the
+            // sensor point (cx, cy, f) projects to (G c).x / (G c).z * f instead of cx: off by at most
+            //   skew * (f + 2 |cx| + |cy| + |cx| (|cx| + |cy|) / f)  <=  skew * (f + sx + sy / 2 + (sx + sy) sx / (4 f))
+            // on the sensor (|cx| <= sx / 2, |cy| <= sy / 2), i.e. skew * width * (f / sx + 1 + sy / (2 sx) + (sx + sy) / (4 f)) pixels,
+            // and likewise in y.  The tiles' test (kernels.hip lds_bounds) grows every bound by kCameraCullPad = 2 pixels for this, the
+            // rounding of the projection and nothing else (the jitter stays inside its pixel): the cull is on only while the worst-case
+            // shift on the sensor is at most an eighth of that pad.  The rest is for vertices off the sensor, whose error grows with
+            // the tangent of their angle to the axis (|cy| / f = 5, 79 degrees: five times the shift; tests/test_pair_culls_gpu.py C7
+            // renders both at 0.24 pixels).  A telephoto lens or a wide image tightens the tolerance (f / sx = 500 at 72 pixels: 7e-6); a basis made by
+            // normalising cross products (skew ~1e-7) passes up to f / sx * width ~ 2e6.  Beyond the tolerance every tile tests every pair.
             const bool no_cull = c->sw.on(SW_NO_CAMERA_CULL);  // A/B switch
             auto dotf = [](const float* x, const float* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
             const CapCameraData& cd = c->camera;
-            const bool ortho = std::fabs(dotf(cd.right, cd.up)) < 1e-4f && std::fabs(dotf(cd.right, cd.forward)) < 1e-4f &&
-                               std::fabs(dotf(cd.up, cd.forward)) < 1e-4f && std::fabs(dotf(cd.right, cd.right) - 1.f) < 1e-4f &&
-                               std::fabs(dotf(cd.up, cd.up) - 1.f) < 1e-4f && std::fabs(dotf(cd.forward, cd.forward) - 1.f) < 1e-4f;
+            const float skew = std::max({std::fabs(dotf(cd.right, cd.up)), std::fabs(dotf(cd.right, cd.forward)), std::fabs(dotf(cd.up, cd.forward)),
+                                         std::fabs(dotf(cd.right, cd.right) - 1.f), std::fabs(dotf(cd.up, cd.up) - 1.f),
+                                         std::fabs(dotf(cd.forward, cd.forward) - 1.f)});
+            const double f = cd.focal_length, sx = cd.sensor_size[0], sy = cd.sensor_size[1];
+            const double shift_x = (double)skew * c->screen.width * (f / sx + 1.0 + sy / (2.0 * sx) + (sx + sy) / (4.0 * f));
+            const double shift_y = (double)skew * c->screen.height * (f / sy + 1.0 + sx / (2.0 * sy) + (sx + sy) / (4.0 * f));
+            const bool   ortho   = skew < 1e-4f && shift_x <= 0.125 * (double)kCameraCullPad && shift_y <= 0.125 * (double)kCameraCullPad;  // (NaN: off)
             sa.cull_camera_pairs = (ortho && !no_cull) ? 1u : 0u;
+            c->last_cull_camera_pairs = sa.cull_camera_pairs;
         }
         // Nobody reads this batch's planes but the resolve (plane read-backs and the reconstruction chain need CAP_RENDER_AOV)
         const bool no_albedo_w = c->sw.on(SW_NO_ALBEDO_IN_W);  // A/B switch

@@ -2638,7 +2638,7 @@ __global__ __launch_bounds__(kBlock, FB ? 4 : (EXT ? (FIRST ? 5 : CAP_TS_EXT) : 
                     x0 = fminf(x0, px), x1 = fmaxf(x1, px), y0 = fminf(y0, py), y1 = fmaxf(y1, py);
                 }
                 const bool usable = a.cull_camera_pairs != 0u && !behind && x0 == x0 && y0 == y0 && x1 == x1 && y1 == y1;
-                lds_bounds[k] = usable ? make_float4(x0 - 2.0f, y0 - 2.0f, x1 + 2.0f, y1 + 2.0f) : make_float4(-3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f);
+                lds_bounds[k] = usable ? make_float4(x0 - kCameraCullPad, y0 - kCameraCullPad, x1 + kCameraCullPad, y1 + kCameraCullPad) : make_float4(-3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f);
             }
         }
     }

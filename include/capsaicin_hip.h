@@ -292,6 +292,10 @@ enum
     CAP_DEBUG_SELFTEST_SHADE_UNARY = 11,
     CAP_DEBUG_SELFTEST_SHADE_DIV2  = 12,
     CAP_DEBUG_SHADE_TAME           = 13,
+    /* CAMERA_CULL (get): 1 if the last cap_render let the camera-ray tiles of the small-scene path skip the fan pairs whose screen
+     * bounds miss them, 0 if every tile tested every pair: the switch CAP_NO_CAMERA_CULL, or a camera basis whose deviation from an
+     * orthonormal one could move a projected vertex by more than an eighth of the bounds' two-pixel pad (context.hip cap_render). */
+    CAP_DEBUG_CAMERA_CULL          = 14,
     /* A/B and diagnostic switches of the build and render paths (which kernels trace the camera and the shadow rays, one or two batch
      * lanes, the builders' parameters ...): ONE table per context, key = SWITCH_BASE + cap_debug_switch_index("CAP_..."), the names being
      * the environment variables that fill the table once, at cap_ctx_create (tools set those around a whole process; nothing else in the

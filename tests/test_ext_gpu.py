@@ -142,7 +142,8 @@ def test_nee_pair_cull_is_exact_and_used(native_lib, bluenoise, tmp_path):
     (hull faces with the lamp at a safe distance inside; context.hip update_nee_pairs: rule + error bound against the contract's absolute
     tmin).  On the Cornell box that is the floor, the back and the two side walls -- NOT the ceiling, 1 cm above the lamp, whose rim
     rays graze it.  With the cull and without it (switch table, same context): the same bits in every plane, the accumulated image and
-    the counters, over frames whose rays reach every corner; a lamp moved to the middle of the room keeps its pairs' count."""
+    the counters, over frames whose rays reach every corner.  (Other scales, lamps at and around the rule's distance, a lamp moved by
+    a refit and the list's count against a model of the rule: tests/test_pair_culls_gpu.py.)"""
     geo, mats = cornell_with_materials(tmp_path)
     w, h, D = 160, 120, 6
     r = capi.Renderer(0)
