@@ -92,9 +92,9 @@ struct FrameConst
     uint32_t frame_count;
     uint32_t lowres_sel;  // LOWRES_INDIRECT (rt_indirect.hlsl:53-59): bit 2 = on, bit 1 = sp_offset.x, bit 0 = sp_offset.y
     float    light_dir[3];
-    float    pad1;
+    float    pad1;  // pad1, pad2: unused in memory; the LDS copy of the lean small-scene kernels keeps the next vertex's sample
     float    light_intensity[3];
-    float    pad2;
+    float    pad2;  //   constants there (kernels.hip stage_frames_samples)
 };
 
 struct CameraDev
@@ -124,7 +124,32 @@ struct ScreenDev
     uint32_t shard_index, shard_count;
     uint32_t local_tiles;       // tiles owned by this shard
     uint32_t pixels_padded;     // Ppad = max_tiles_per_shard * 64 (identical on every shard)
+    uint32_t tiles_x_mul, tiles_x_shift;  // tile_div(): gt / tiles_x for every gt < 2^26 without the run-time division
 };
+
+// Division of a global tile index by tiles_x as one multiply-high and one shift.  A path id holds 26 bits of local pixel, so
+// n = gt < 2^26 (a well-formed gt is below tile_count; the form is exact for the whole range so that no queue content can break
+// it).  With s = ceil(log2 d) and M = ceil(2^(26+s) / d) < 2^27 + 1, e = M d - 2^(26+s) lies in [0, d) and
+//   floor(n M / 2^(26+s)) = floor(n / d + n e / (d 2^(26+s))) = floor(n / d)   as long as n e < 2^(26+s),
+// which n < 2^26 and e < d <= 2^s give.  The dividend goes in shifted left by 6 (n << 6 < 2^32), which makes the 2^(26+s) a
+// multiply-high and a shift by s for every d >= 1, d = 1 included (M = 2^26).  The argument needs nothing else of d; the
+// largest tiles_x is 4096 (cap_set_resolution).  tests/test_tile_div.py checks every tiles_x up to 2048 at the multiples' neighbours
+// through cap_debug_tile_divmod().
+constexpr uint32_t kTileDivBits = 26;
+__host__ __device__ __forceinline__ void tile_div_setup(uint32_t d, uint32_t& mul, uint32_t& shift)
+{
+    shift = 0;
+    while (shift < 32u && (1ull << shift) < d) ++shift;
+    mul = d == 0 ? 0u : (uint32_t)((((unsigned long long)1 << (kTileDivBits + shift)) + d - 1u) / d);
+}
+__host__ __device__ __forceinline__ uint32_t tile_div(uint32_t n, uint32_t mul, uint32_t shift)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umulhi(n << (32u - kTileDivBits), mul) >> shift;
+#else
+    return (uint32_t)(((unsigned long long)(n << (32u - kTileDivBits)) * mul) >> 32) >> shift;
+#endif
+}
 
 __device__ __forceinline__ bool local_pixel_to_xy(const ScreenDev& sc, uint32_t pl, uint32_t& x, uint32_t& y)
 {

@@ -399,6 +399,7 @@ void update_screen(CapContext* c, uint32_t w, uint32_t h, uint32_t shard_index, 
     const uint32_t max_local = (s.tile_count + s.shard_count - 1) / s.shard_count;
     s.local_tiles   = s.tile_count > s.shard_index ? (s.tile_count - s.shard_index + s.shard_count - 1) / s.shard_count : 0;
     s.pixels_padded = max_local * kTilePixels;
+    tile_div_setup(s.tiles_x, s.tiles_x_mul, s.tiles_x_shift);
     c->frames_accumulated = 0;
     c->aov_valid = false;
 }
@@ -695,6 +696,22 @@ int cap_debug_switch_index(const char* name)
     for (uint32_t k = 0; name && k < SW_COUNT; ++k)
         if (strcmp(name, kSwitchNames[k]) == 0) return (int)k;
     return -1;
+}
+
+// Host-callable check of tile_div() (cap_device.h), the division by tiles_x of the small-scene kernels' bounce >= 1 plumbing: quotient
+// and remainder of n[k] / tiles_x by the multiplier and shift update_screen() stores, the remainder by the kernel's gt - ty * tiles_x.
+// No context, no device: tests/test_tile_div.py compares it with // and % (like cap_debug_stamps, not part of the declared ABI).
+extern "C" int cap_debug_tile_divmod(uint32_t tiles_x, const uint32_t* n, uint64_t count, uint32_t* quotient, uint32_t* remainder)
+{
+    if (!tiles_x || !n || !quotient || !remainder) return CAP_ERR_INVALID_ARG;
+    uint32_t mul, shift;
+    tile_div_setup(tiles_x, mul, shift);
+    for (uint64_t k = 0; k < count; ++k)
+    {
+        quotient[k]  = tile_div(n[k], mul, shift);
+        remainder[k] = n[k] - quotient[k] * tiles_x;
+    }
+    return CAP_OK;
 }
 
 int cap_ctx_create(int device_id, void* hip_stream, CapContext** out_ctx)

@@ -1735,17 +1735,152 @@ __device__ __forceinline__ void stage_frames(const ShadeArgs& a, FrameConst* lds
     __syncthreads();
 }
 
+// Per-chunk plumbing of the fused small-scene kernels (LEAN: reference model, scene in LDS; docs/experiments.md (98)).  The vector
+// instructions of a chunk that are neither the pair loop, phase 2, the shading arithmetic nor the probe were 15 % of the bounce >= 1
+// kernel, and most of them produced what is the same for every path of a frame slot, the same at every bounce of a path, or never
+// read.  -DCAP_CHUNK_PLAIN (capsaicin_amd/variants/chunkplain.flags) keeps the forms of round 8 for A/B runs.
+#if defined(CAP_CHUNK_PLAIN)
+constexpr bool kChunkLean = false;
+#else
+constexpr bool kChunkLean = true;
+#endif
+
+// A value nothing reads on the paths where it is not assigned: any register's content, no instruction (where `= 0` costs a v_mov per
+// component and chunk).  Unspecified, not undefined: a lane may compute with it, as the probe does, as long as the result is discarded.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wuninitialized"
+__device__ __forceinline__ float unread_f()
+{
+    float x;
+    return x;
+}
+#pragma clang diagnostic pop
+__device__ __forceinline__ v3 unread3() { return mk3(unread_f(), unread_f(), unread_f()); }
+
+// What bluenoise4x4() makes of `count` alone: count = frame_count * 25 + bounce is the same for every path of a frame slot, so the
+// workgroup computes it once per slot (the integer operations and the one fp32 multiply of bluenoise4x4, hence its bits) where it
+// stages the frame constants, and a lane reads its slot's values instead of deriving them per vertex.
+//  * count + 1 (CARRY: the sample of the path's next vertex, what every bounce needs) sits in the two pad words of the LDS copy of
+//    FrameConst, next to the light it is read with: no LDS beyond the 3 KB that were there, one ds_read fewer per chunk.
+//  * count itself is only needed where no sample is carried in, at bounce 0: a table of its own in that kernel.
+struct SlotSample
+{
+    uint32_t off;  // (py << 8) | px: the texel inside the pixel's 4 x 4 block, as an address offset (<= 0x0303)
+    float    k;    // 0.61803398875f * (float)(count / 16)
+};
+__device__ __forceinline__ uint32_t bluenoise_offset(uint32_t count) { return (((count % 16u) / 4u) << 8) | ((count % 16u) % 4u); }
+__device__ __forceinline__ float    bluenoise_shift(uint32_t count) { return 0.61803398875f * (float)(count / 16u); }
+// the pixel's part of the address: ((y * 4) % 256) * 256 + (x * 4) % 256.  px, py < 4 fill the two bits below each field, so
+// bluenoise4x4's sy * 256 + sx is texel_base | offset.
+__device__ __forceinline__ uint32_t bluenoise_base(uint32_t x, uint32_t y) { return ((y & 63u) << 10) | ((x & 63u) << 2); }
+__device__ __forceinline__ void     bluenoise_at(const float2* tex, uint32_t base, uint32_t off, float k, float& s0, float& s1)
+{
+    const float2 t = tex[base | off];  // base <= 0xfcfc and off <= 0x0303 by construction (every staged row, also behind n_slots): inside the 256 x 256 texels whatever the path id holds
+    const float  a = t.x + k, b = t.y + k;
+    s0 = a - floorf(a);
+    s1 = b - floorf(b);
+}
+// stage_frames() of the lean kernels.  All kMaxFrameSlots entries are defined (zeros behind n_slots), so that even a malformed path
+// id finds an offset <= 0x0303 in its slot's row.
+template <bool FIRST>
+__device__ __forceinline__ void stage_frames_samples(const ShadeArgs& a, FrameConst* lds_frames, SlotSample* lds_first)
+{
+    constexpr uint32_t kWords = (uint32_t)(sizeof(FrameConst) / 4);
+    static_assert(kWords == 12 && offsetof(FrameConst, frame_count) == 8 && offsetof(FrameConst, pad1) == 28 && offsetof(FrameConst, pad2) == 44, "FrameConst layout");
+    const uint32_t  words = (a.n_slots < kMaxFrameSlots ? a.n_slots : kMaxFrameSlots) * kWords;
+    const uint32_t* src   = reinterpret_cast<const uint32_t*>(a.frames);
+    uint32_t*       dst   = reinterpret_cast<uint32_t*>(lds_frames);
+    for (uint32_t i = threadIdx.x; i < kMaxFrameSlots * kWords; i += kBlock)
+    {
+        uint32_t v = 0u;
+        if (i < words)
+        {
+            const uint32_t sl = i / kWords, w = i - sl * kWords;
+            v = src[i];
+            if (w == 7u || w == 11u)
+            {
+                const uint32_t next = src[sl * kWords + 2u] * 25u + a.bounce + 1u;
+                v = w == 7u ? bluenoise_offset(next) : f2u(bluenoise_shift(next));
+            }
+        }
+        dst[i] = v;
+    }
+    if (FIRST)
+        for (uint32_t sl = threadIdx.x; sl < kMaxFrameSlots; sl += kBlock)
+        {
+            SlotSample ss = {0u, 0.0f};
+            if (sl < a.n_slots)
+            {
+                const uint32_t count = a.frames[sl].frame_count * 25u + a.bounce;
+                ss.off = bluenoise_offset(count), ss.k = bluenoise_shift(count);
+            }
+            lds_first[sl] = ss;
+        }
+    __syncthreads();
+}
+
 // CARRY (fused reference-model kernels): an extension ray's tmin / tmax are the constants kRayEps / kRayFar, so the two .w
 // slots of its queue entry carry the blue-noise sample of the vertex it will find.  The vertex that emits the ray fetches
 // that sample next to its other inputs, where nothing waits for it before the final stores; the vertex that receives it starts
 // shading without a dependent global load.  carried_* = the .w slots of the entry this vertex came from (bounce >= 1).
 // FAST (k_trace_shade<..., TAME>): the last bounce emits no extension ray, so nothing reads the next vertex's sample
-template <bool EXT = false, bool FIRST = true, bool CARRY = false, bool FAST = false>
+// LEAN (k_trace_shade; lds_first at bounce 0): the same values with less work per chunk.
+//  * No defaults: on a lane without a vertex (valid == false) L, I and the samples are whatever the registers hold; shade_vertex reads
+//    them on valid lanes only, and the probe's answer on the others is discarded.
+//  * bounce >= 1: the only consumer of the pixel coordinates is the blue-noise address, i.e. x mod 64 and y mod 64, which come from
+//    the tile's row and column mod 8 (tile_div: no run-time division).  The three bounds compares of local_pixel_to_xy are dropped:
+//    the path was in bounds when bounce 0 emitted it, and for a malformed queue shade_vertex's own guard (slot >= n_slots ||
+//    pl >= Ppad) is what keeps every plane index inside the planes -- plane_idx depends on slot and pl alone -- while the blue-noise
+//    address is inside the texture for any path id (bluenoise_at).
+//  * the sample constants of the slot come from where stage_frames_samples() put them.
+template <bool EXT = false, bool FIRST = true, bool CARRY = false, bool FAST = false, bool LEAN = false>
 __device__ __forceinline__ ShadePre shade_prefetch(const ShadeArgs& a, const FrameConst* lds_frames, bool active, uint32_t pid,
-                                                   float carried_r1 = 0.f, float carried_r2 = 0.f)
+                                                   float carried_r1 = 0.f, float carried_r2 = 0.f, const SlotSample* lds_first = nullptr)
 {
     ShadePre       s;
     const uint32_t slot = pid >> kPidShift, pl = pid & kPidMask;
+    if constexpr (LEAN)
+    {
+        static_assert(CARRY && !EXT, "LEAN: the reference model's fused kernels");
+        const uint32_t    sl = slot < kMaxFrameSlots ? slot : 0;
+        const FrameConst& fc = lds_frames[sl];
+        uint32_t          base;
+        s.indirect_on = true;
+        if (FIRST)
+        {
+            uint32_t x = 0, y = 0;
+            s.valid = active && local_pixel_to_xy(a.screen, pl, x, y);
+            if (fc.lowres_sel & 4u) s.indirect_on = (x & 1u) == ((fc.lowres_sel >> 1) & 1u) && (y & 1u) == (fc.lowres_sel & 1u);
+            base = bluenoise_base(x, y);
+        }
+        else
+        {
+            s.valid = active;
+            const uint32_t gt = __umul24(pl >> 6, a.screen.shard_count) + a.screen.shard_index;  // 20-bit local tile, shard_count <= tile_count < 2^24
+            const uint32_t ty = tile_div(gt, a.screen.tiles_x_mul, a.screen.tiles_x_shift);  // (a malformed gt >= 2^26: some other texel, discarded by the guard)
+            // tx = gt - ty * tiles_x, of which only tx mod 8 is used: the low three bits of a product need those of its factors alone
+            const uint32_t tx = gt + (ty & 7u) * ((0u - a.screen.tiles_x) & 7u);
+            // x mod 64 = (tx mod 8) * 8 + (w & 7), y mod 64 = (ty mod 8) * 8 + (w >> 3) with w = pl & 63, placed as bluenoise_base() does
+            base = ((ty & 7u) << 13) | ((pl & 0x38u) << 7) | ((tx & 7u) << 5) | ((pl & 7u) << 2);
+        }
+        s.L = unread3(), s.I = unread3(), s.r1 = s.r2 = s.r1n = s.r2n = unread_f();
+        s.r3 = s.r4 = s.r5 = s.r6 = 0.f;  // EXT only
+        if (s.valid)
+        {
+            s.L = mk3(fc.light_dir[0], fc.light_dir[1], fc.light_dir[2]);
+            s.I = mk3(fc.light_intensity[0], fc.light_intensity[1], fc.light_intensity[2]);
+            if (FIRST)
+            {
+                const SlotSample ss = lds_first[sl];
+                bluenoise_at(a.scene.bluenoise, base, ss.off, ss.k, s.r1, s.r2);  // rt_indirect.hlsl:149
+            }
+            else
+                s.r1 = carried_r1, s.r2 = carried_r2;
+            // the pad words of the LDS copy: the constants of count + 1 (stage_frames_samples)
+            if (!FAST || a.bounce < a.num_bounces) bluenoise_at(a.scene.bluenoise, base, f2u(fc.pad1), fc.pad2, s.r1n, s.r2n);
+        }
+        return s;
+    }
     uint32_t       x = 0, y = 0;
     s.valid = active && local_pixel_to_xy(a.screen, pl, x, y);
     s.L = mk3(0, 0, 0), s.I = mk3(0, 0, 0), s.r1 = 0.f, s.r2 = 0.f;
@@ -1868,7 +2003,9 @@ struct ProbeArgs
 constexpr uint32_t kWaveRing = 128;  // <= 63 parked + <= 64 new
 // FAST (k_trace_shade<..., TAME>, scenes whose shading records are tame: SceneDev::shade_tame): the square roots and divisions
 // of the vertex in their unscaled forms (map_to_hemisphere_tame and above), and nothing of the direction sample at the last bounce
-template <bool FIRST, bool FB = false, bool CARRY = false, bool SKY_RMW = false, bool PROBE = false, bool FAST = false>
+// LEAN: p, dir and contrib exist only under the flag that stores them (emit_shadow: p, contrib; emit_ext: p, dir, thr); elsewhere they
+// are whatever the registers hold.  The probe runs on all lanes and reads p: on a lane without a shadow ray its answer is discarded.
+template <bool FIRST, bool FB = false, bool CARRY = false, bool SKY_RMW = false, bool PROBE = false, bool FAST = false, bool LEAN = false>
 __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* shade_tab, const ShadePre& pre, uint32_t klass,
                                              uint32_t pid, float4 hit, v3 thr, uint32_t& n_shaded, Stamps& st,
                                              const ProbeArgs probe = ProbeArgs(), uint32_t* n_probed = nullptr, uint32_t ring_head = 0,
@@ -1890,6 +2027,7 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
 
         bool   emit_shadow = false, emit_ext = false;
         v3     p = mk3(0, 0, 0), dir = mk3(0, 0, 0), contrib = mk3(0, 0, 0);
+        if constexpr (LEAN) p = unread3(), dir = unread3(), contrib = unread3();
 
         if (FIRST && !valid)
         {
@@ -2574,6 +2712,10 @@ __global__ __launch_bounds__(kBlock, FB ? 4 : (EXT ? (FIRST ? 5 : CAP_TS_EXT) : 
     constexpr bool        PROBE = !EXT && !FB && LDS;
     __shared__ float4     lds_probe[PROBE ? 2 * kMaxFrameSlots : 1];
     __shared__ float      lds_pscore[PROBE ? kExhaustiveMax / 2 : 1];
+    // the lean per-chunk plumbing (see kChunkLean): the reference model's kernels with the scene in LDS and tame records.  (The
+    // instantiations without TAME pay for it with 8 and 4 B of scratch, the EXT and feedback kernels were not tried: they keep round 8's.)
+    constexpr bool        LEAN = PROBE && TAME && kChunkLean;
+    __shared__ SlotSample lds_first[(LEAN && FIRST) ? kMaxFrameSlots : 1];  // bounce 0 only (512 B; bounce >= 1 stays at its 25 732 B)
     __shared__ uint32_t   lds_probe_k;
     __shared__ float4     lds_ring[(PROBE && !FIRST) ? (kBlock / 64) * kWaveRing : 1];  // per wave: (origin, path id) of its parked shadow rays
     uint32_t              n_probed = 0;
@@ -2677,7 +2819,10 @@ __global__ __launch_bounds__(kBlock, FB ? 4 : (EXT ? (FIRST ? 5 : CAP_TS_EXT) : 
             lds_probe[2 * sl + 1] = tri_pre(d, mk3(rec[15], rec[16], rec[17]), kRayEps, kRayFar);
         }
     }
-    stage_frames(a, lds_frames);  // ends with the workgroup barrier
+    if constexpr (LEAN)
+        stage_frames_samples<FIRST>(a, lds_frames, lds_first);  // ends with the workgroup barrier
+    else
+        stage_frames(a, lds_frames);  // ends with the workgroup barrier
     ProbeArgs probe;
     if (PROBE && a.inline_probe) probe.rows = lds_probe, probe.pairs = bvh.fan_pairs, probe.k = lds_probe_k;
     // The probe's survivors stay with the wave that found them (ShadeArgs::wave_ring): parked in its own 128-entry ring and traced
@@ -2762,16 +2907,35 @@ __global__ __launch_bounds__(kBlock, FB ? 4 : (EXT ? (FIRST ? 5 : CAP_TS_EXT) : 
         {
             if (j * 64u >= n_class) break;  // past the end of this class's sub-queue
             active = j * 64u + lane < n_class;
-            i      = my_class * a.in.class_capacity + j * 64u + lane;
-            // extension rays: tmin / tmax are constants (rt_indirect.hlsl:154-157); with CARRY the .w slots hold the sample
-            float4 o = make_float4(0.f, 0.f, 0.f, 0.f), d = make_float4(0.f, 0.f, 1.f, 0.f), tp = make_float4(1.f, 1.f, 1.f, 0.f);
-            if (active) o = a.in.org_tmin[i], d = a.in.dir_tmax[i], tp = a.in.thr_pid[i];
-            grab = grab_issue(a.work, my_class);
-            if (active)
+            if constexpr (LEAN)
             {
-                r   = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), kRayEps, kRayFar);
-                thr = mk3(tp.x, tp.y, tp.z), pid = f2u(tp.w);
+                // A lane past the end of the class's last chunk loads the class's LAST entry (n_class > j * 64 >= 0 here, and
+                // n_class <= class_capacity: inside the sub-queue) instead of taking defaults that cost a v_mov per register and chunk, and
+                // the entry's registers are used where they land.  Such a lane holds a real path's ray and id, but active == false, and
+                // that alone keeps it silent: has_ray == false clears its candidate mask (so it hits nothing and reads no record),
+                // pre.valid == false makes shade_vertex skip every store, count and emit for it, and the only tables it indexes -- the
+                // frame slot's rows -- it indexes with that real, in-range slot.
+                const uint32_t local = j * 64u + lane;
+                i                    = my_class * a.in.class_capacity + (local < n_class ? local : n_class - 1u);
+                const float4 o = a.in.org_tmin[i], d = a.in.dir_tmax[i], tp = a.in.thr_pid[i];
+                grab = grab_issue(a.work, my_class);
+                r    = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), kRayEps, kRayFar);
+                thr  = mk3(tp.x, tp.y, tp.z), pid = f2u(tp.w);
                 carried_r1 = o.w, carried_r2 = d.w;
+            }
+            else
+            {
+                i      = my_class * a.in.class_capacity + j * 64u + lane;
+                // extension rays: tmin / tmax are constants (rt_indirect.hlsl:154-157); with CARRY the .w slots hold the sample
+                float4 o = make_float4(0.f, 0.f, 0.f, 0.f), d = make_float4(0.f, 0.f, 1.f, 0.f), tp = make_float4(1.f, 1.f, 1.f, 0.f);
+                if (active) o = a.in.org_tmin[i], d = a.in.dir_tmax[i], tp = a.in.thr_pid[i];
+                grab = grab_issue(a.work, my_class);
+                if (active)
+                {
+                    r   = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), kRayEps, kRayFar);
+                    thr = mk3(tp.x, tp.y, tp.z), pid = f2u(tp.w);
+                    carried_r1 = o.w, carried_r2 = d.w;
+                }
             }
         }
         float    t, u, v;
@@ -2805,7 +2969,7 @@ __global__ __launch_bounds__(kBlock, FB ? 4 : (EXT ? (FIRST ? 5 : CAP_TS_EXT) : 
             exhaustive_closest<ORG, !LDS>(bvh, rec_tab, r, t, u, v, gid, lds_org, pair_mask);
         __builtin_amdgcn_s_setprio(3);
         STAMP(st, 1, true);  // triangle loop + winner's record
-        const ShadePre pre = shade_prefetch<EXT, FIRST, CARRY, TAME>(a, lds_frames, active, pid, carried_r1, carried_r2);
+        const ShadePre pre = shade_prefetch<EXT, FIRST, CARRY, TAME, LEAN>(a, lds_frames, active, pid, carried_r1, carried_r2, lds_first);
         if (FIRST && slot == a.aov_slot)
         {
             // rt_primary_visibility.hlsl:46: (uv, asfloat(InstanceID), asfloat(PrimitiveIndex)); a miss keeps uv = 0, ids = ~0u
@@ -2834,7 +2998,7 @@ __global__ __launch_bounds__(kBlock, FB ? 4 : (EXT ? (FIRST ? 5 : CAP_TS_EXT) : 
         }
         else
         {
-            shade_vertex<FIRST, FB, CARRY, false, PROBE, TAME>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr, n_shaded, st, probe, &n_probed,
+            shade_vertex<FIRST, FB, CARRY, false, PROBE, TAME, LEAN>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr, n_shaded, st, probe, &n_probed,
                                                          ring_head, &ring_n);
             if (PROBE && ring_n >= 64u) trace_ring(64u);
         }

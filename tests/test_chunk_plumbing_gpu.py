@@ -1,0 +1,121 @@
+"""Per-chunk plumbing of the fused small-scene kernels (kernels.hip kChunkLean): lanes past the end of a class's last chunk load the
+class's last entry, the blue-noise coordinates of bounce >= 1 come from a multiply-high by a host-computed reciprocal of tiles_x, and
+the per-slot sample constants (count = frame * 25 + bounce) are staged once per workgroup.  Cornell box, reference model, depth 4, at
+the smallest shapes where each can go wrong; every plane and every ray counter bit for bit against the oracle.  The EXT and feedback
+kernels keep the earlier plumbing and have no case here."""
+import numpy as np
+import pytest
+
+from capsaicin_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+PLANES = (("gbuffer_geo", capi.BUF_GBUFFER_GEO), ("direct", capi.BUF_DIRECT), ("albedo", capi.BUF_ALBEDO),
+          ("normal_depth", capi.BUF_NORMAL_DEPTH), ("indirect", capi.BUF_INDIRECT), ("combined", capi.BUF_COMBINED))
+DEPTH = 4
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def oracle_scene(cornell_path):
+    from oracle import cap_oracle as O
+    from oracle import obj_oracle
+    g = obj_oracle.load_geometry(cornell_path)
+    return O.Scene(g["positions"], g["normals"], g["texcoords"], g["indices"], g["meshes"])
+
+
+def oracle_camera(w, h):
+    from oracle import cap_oracle as O
+    cam = capi.cornell_camera(w, h)
+    return O.make_camera(tuple(cam.position), tuple(cam.forward), tuple(cam.right), tuple(cam.up), cam.sensor_size[0], cam.sensor_size[1],
+                         cam.focal_length)
+
+
+def renderer(cornell_path, bluenoise, w, h, shard=(0, 1)):
+    r = capi.Renderer(0)
+    r.upload_geometry(capi.Geometry(cornell_path))
+    r.upload_bluenoise(bluenoise)
+    info = r.build_bvh()
+    assert info.triangle_count <= 64  # the fused kernels with the scene in LDS
+    r.set_resolution(w, h)
+    r.set_shard(*shard)
+    r.set_camera(capi.cornell_camera(w, h))
+    return r
+
+
+def owned(w, h, shard):
+    """Pixels of the tiles shard (index, count) owns: global tile = local tile * count + index, tiles row-major."""
+    tx = (w + 7) // 8
+    y, x = np.mgrid[0:h, 0:w]
+    return ((y // 8) * tx + x // 8) % shard[1] == shard[0]
+
+
+def assert_planes(r, ref, mask=None):
+    for name, kind in PLANES:
+        g, o = bits(r.readback(kind)), bits(ref[name])
+        bad = (g != o).any(-1)
+        if mask is not None:
+            bad &= mask
+        assert not bad.any(), "%s: %d pixels differ, first (y, x) = %s" % (name, int(bad.sum()), tuple(np.argwhere(bad)[0]))
+
+
+def assert_clean(s):
+    assert s.guard_shade == 0 and s.guard_trace_any == 0 and s.guard_append == 0
+
+
+@pytest.mark.parametrize("w,h,frame", [
+    (104, 56, 3),  # tiles_x = 13: neither a power of two nor a multiple of 8
+    (100, 52, 3),  # partial tiles on the right and bottom edges
+    (16, 8, 3),    # two chunks in 64 classes: 62 empty classes, every class tail partial
+])
+def test_one_slot(native_lib, bluenoise, cornell_path, oracle_scene, w, h, frame):
+    ref = oracle_scene.render_frame(oracle_camera(w, h), bluenoise, w, h, frame, DEPTH, threads=8)
+    assert ref["rays"][1] > w * h  # paths go on past bounce 1
+    r = renderer(cornell_path, bluenoise, w, h)
+    r.render(frame, 1, DEPTH, capi.RENDER_AOV)
+    assert_planes(r, ref)
+    s = r.stats()
+    assert (s.rays_primary, s.rays_extension, s.rays_shadow) == ref["rays"]
+    assert_clean(s)
+    r.close()
+
+
+def test_shards_of_three(native_lib, bluenoise, cornell_path, oracle_scene):
+    """100 x 52 = 13 x 7 tiles over three shards: gt = 3 lt + s, padded local tiles beyond tile_count on shards 1 and 2.  Every shard's
+    own pixels against the oracle's frame; the three shards' rays add up to the oracle's."""
+    w, h, frame = 100, 52, 3
+    ref = oracle_scene.render_frame(oracle_camera(w, h), bluenoise, w, h, frame, DEPTH, threads=8)
+    rays = np.zeros(3, np.int64)
+    for index in (1, 0, 2):
+        r = renderer(cornell_path, bluenoise, w, h, (index, 3))
+        r.render(frame, 1, DEPTH, capi.RENDER_AOV)
+        mask = owned(w, h, (index, 3))
+        assert mask.any()
+        assert_planes(r, ref, mask)
+        s = r.stats()
+        assert_clean(s)
+        rays += (s.rays_primary, s.rays_extension, s.rays_shadow)
+        r.close()
+    assert tuple(int(x) for x in rays) == ref["rays"]
+
+
+@pytest.mark.parametrize("w,h,first,n", [
+    (104, 56, 5, 3),     # frame * 25 + bounce: 125 .. 179, crosses multiples of 16 inside the batch; slots mix in a compacted chunk
+    (100, 52, 1021, 3),  # a large count / 16 (1595 .. 1598)
+])
+def test_frame_slots(native_lib, bluenoise, cornell_path, oracle_scene, w, h, first, n):
+    ocam = oracle_camera(w, h)
+    acc, rays = oracle_scene.render_accumulate(ocam, bluenoise, w, h, first, n, DEPTH, threads=8)
+    last = oracle_scene.render_frame(ocam, bluenoise, w, h, first + n - 1, DEPTH, threads=8)
+    r = renderer(cornell_path, bluenoise, w, h)
+    r.render(first, n, DEPTH, capi.RENDER_AOV)  # one batch: the frames are the batch's slots
+    assert_planes(r, last)  # the per-frame planes of the batch's last slot
+    got = r.readback(capi.BUF_ACCUM_SUM)
+    assert np.array_equal(bits(got[..., :3]), bits(acc[..., :3])), "running sum of the %d frames differs" % n
+    s = r.stats()
+    assert (s.rays_primary, s.rays_extension, s.rays_shadow) == rays
+    assert_clean(s)
+    r.close()
