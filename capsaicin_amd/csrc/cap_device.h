@@ -34,7 +34,7 @@ __host__ __device__ __forceinline__ uint32_t class_chunk(uint32_t j, uint32_t kl
 constexpr uint32_t kCounterStride = 32;  // uint32 words between two class counters (128 B)
 // Words 2 and 3 of a class's counter line: shadow rays answered by the producer's probe, shaded vertices (flush_stats)
 constexpr uint32_t kShadeRec      = 8;   // float4 per shading record
-constexpr uint32_t kExhaustiveMax = 64;  // scenes up to this many triangles are traced exhaustively (kernels.hip)
+constexpr uint32_t kExhaustiveMax = 64;  // scenes up to this many triangles are traced exhaustively (cap_exhaustive.h)
 constexpr int      kNoChild        = 0x7fffffff;  // unused slot of a wide node
 // k_trace_any on the 8-wide view: 24 LDS words per lane = 12 (g_base, g_mask) pairs (24 KB per workgroup: six workgroups per CU)
 constexpr uint32_t kWideLdsEntries = 24;
@@ -94,7 +94,7 @@ struct FrameConst
     float    light_dir[3];
     float    pad1;  // pad1, pad2: unused in memory; the LDS copy of the lean small-scene kernels keeps the next vertex's sample
     float    light_intensity[3];
-    float    pad2;  //   constants there (kernels.hip stage_frames_samples)
+    float    pad2;  //   constants there (cap_shade.h stage_frames_samples)
 };
 
 struct CameraDev
@@ -228,7 +228,7 @@ struct SceneDev
     // every triangle's stored vertex normals have squared lengths in [0.5, 2] and pairwise dot products >= 0.25 (reduced where the
     // records are written: bvh.hip k_tri_setup; kept by the context, no read in a render call).  Then |w n0 + u n1 + v n2|^2 is in
     // [0.24, 2.01] for every u, v >= 0 with u + v <= 1 + 2^-20, which is what the unscaled normalize3 of the fused small-scene
-    // kernels needs (kernels.hip normalize3_tame, DESIGN.md "fp32 arithmetic contract")
+    // kernels needs (cap_shade.h normalize3_tame, DESIGN.md "fp32 arithmetic contract")
     uint32_t          shade_tame;
     // EXT shading model (no reference counterpart; DESIGN.md "EXT shading model")
     const float2*      bluenoise_ba;  // 256*256 (B,A)/255

@@ -1,8 +1,9 @@
-// cap_kernels.h — host-callable launchers of the gfx950 kernels (kernels.hip, bvh.hip).
+// cap_kernels.h — host-callable launchers of the gfx950 kernels, one section per translation unit.
 #pragma once
 
 #include "cap_device.h"
 
+#include <cstdio>
 #include <vector>
 
 namespace cap
@@ -54,12 +55,38 @@ struct LaunchCfg
     uint32_t    grid_blocks;    // persistent grid size for queue kernels
     uint32_t    stack_entries;  // 32 or 64 (per-lane LDS traversal stack)
     uint32_t    cu_count = 0;   // compute units (0: unknown) -- persistent kernels with a static chunk assignment clamp their grid
-                                // to what is resident at once, see resident_grid() in kernels.hip
+                                // to what is resident at once, see resident_grid() below
     uint32_t    any_no_probe = 0;  // launch_trace_any: the producer already probed (ShadeArgs::inline_probe): plain per-chunk kernel
     const SwitchTable* sw = nullptr;  // the context's A/B switches (null: every switch at the product's choice)
     bool    sw_on(CapSwitch k) const { return sw && sw->on(k); }
     int64_t sw_get(CapSwitch k, int64_t dflt) const { return sw ? sw->get(k, dflt) : dflt; }
 };
+
+// Kernels that deal their chunks out statically (wave w takes slots w, w + W, ...): a workgroup that is not resident from the start
+// runs its whole share after the others have finished.  Their grids are therefore clamped to what the runtime says fits at once
+// (measured on the 262 k-triangle scene: 5 workgroups per CU requested with 32-KB stacks, 4 resident, closest hit 11.3 ms; 24-KB
+// stacks, 5 resident, 7.9 ms).  One answer per kernel instantiation, asked once.
+template <auto K>
+uint32_t resident_grid(const LaunchCfg& cfg, uint32_t want)
+{
+    static int per_cu = -1;
+    if (per_cu < 0)
+    {
+        int n = 0;
+        per_cu = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K, (int)kBlock, 0) == hipSuccess && n > 0) ? n : 0;
+        if (cfg.sw_on(SW_TRACE_LAUNCHES)) fprintf(stderr, "[cap] resident workgroups per CU: %d\n", per_cu);
+    }
+    if (!cfg.cu_count || !per_cu) return want;
+    const uint32_t cap = cfg.cu_count * (uint32_t)per_cu;
+    return want < cap ? want : cap;
+}
+// the persistent grid of a queue kernel: one workgroup per kBlock entries, at most cfg.grid_blocks
+inline uint32_t queue_grid(const LaunchCfg& cfg, uint32_t max_count)
+{
+    uint32_t g = (max_count + kBlock - 1) / kBlock;
+    if (g > cfg.grid_blocks) g = cfg.grid_blocks;
+    return g ? g : 1;
+}
 
 // ---- trace ----
 // Primary visibility (rt_primary_visibility.hlsl:35-49): generates camera rays for frame slots [0, n_slots) of
@@ -214,7 +241,7 @@ struct ShadeArgs
     uint32_t*         work;        // fused kernels: kQueueClasses chunk-grab counters of this launch (zeroed), kCounterStride apart
     FeedbackDev       fb;          // read only by the feedback variants
     // untextured scene, reference shading, accumulate-only render (nobody but the resolve reads the planes): the first vertex's albedo
-    // is one of four constants, so the albedo plane is not used and direct.w carries a code instead of 1 (kernels.hip shade_vertex)
+    // is one of four constants, so the albedo plane is not used and direct.w carries a code instead of 1 (cap_shade.h shade_vertex)
     uint32_t          albedo_in_w;
     // EXT model on the small-scene path: the next-event shadow ray is tested inside the fused kernel (same exhaustive loop as the
     // any-hit kernel's) and the path carries its gathered radiance in the extension queue (RayQueue::acc); the colour plane is
@@ -232,7 +259,7 @@ struct ShadeArgs
     uint32_t          wave_ring;
     uint32_t          cull_camera_pairs;  // bounce 0 of the small-scene path: the camera basis is orthonormal, so a tile may skip the pairs off its screen area
 };
-// Pixels the bounce-0 kernel grows every fan pair's screen bounds by (kernels.hip lds_bounds).  The host's gate for
+// Pixels the bounce-0 kernel grows every fan pair's screen bounds by (small_scene.hip stage_camera_pairs).  The host's gate for
 // cull_camera_pairs (context.hip cap_render) allows a camera basis to move a projected point by an eighth of it.
 constexpr float kCameraCullPad = 2.0f;
 // feedback: vertices of bounce >= 1 that the previous frame saw take its shaded colour and end the path (rt_indirect.hlsl:116-145;
@@ -393,7 +420,7 @@ void launch_post_chain(hipStream_t stream, const PostChainArgs& a);
 // post.hip's unscaled IEEE division against the compiler's, on the device: out[0] mismatches of log2 over every normal float,
 // out[1] over 2^30 operand pairs of the range it is used on (both must be 0; cap_debug_get(CAP_DEBUG_SELFTEST_DIV))
 void launch_div_selftest(hipStream_t stream, unsigned long long* out_device);
-// kernels.hip's unscaled square roots and divisions of the small-scene shading against the compiler's: out[0] mismatches, out[1]
+// cap_shade.h's unscaled square roots and divisions of the small-scene shading against the compiler's: out[0] mismatches, out[1]
 // comparisons made; which = 0 the unary forms over every float of their ranges, 1 = ortho_vector's pair over 2^31 candidates
 void launch_shade_forms_selftest(hipStream_t stream, unsigned long long* out_device, uint32_t which);
 // out[(y, x)] = full[(2y + oy, 2x + ox)]: the half-resolution indirect image of LOWRES_INDIRECT (rt_indirect.hlsl:53-59, :176)

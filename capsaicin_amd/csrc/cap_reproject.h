@@ -1,5 +1,5 @@
 // cap_reproject.h — device helpers shared by the reconstruction chain (post.hip) and the G-buffer feedback branch of the
-// indirect pass (kernels.hip): row-major float4 images with D3D-style out-of-bounds reads, the reference's UV<->pixel rules,
+// indirect pass (cap_shade.h shade_vertex): row-major float4 images with D3D-style out-of-bounds reads, the reference's UV<->pixel rules,
 // its hand-written bilinear tap and the camera reprojection (reference utils.h:6-35, camera.h:8-37).
 #pragma once
 

@@ -8,7 +8,7 @@
 // be in range -- |a| = 0 or in [2^-80, 2^41], b in [2^-40, 2^41) (a sigma <= 2^38 times a tap length <= sqrt(18): the range the self-test draws from); the reconstruction chain establishes that per tile (post.hip) and
 // takes the plain `/` for a tile or wave that fails: the same result by definition.  cap_debug_get(CAP_DEBUG_SELFTEST_DIV) compares both
 // forms on the device, bit for bit.  The small-scene shading uses it, div2_unscaled and the square roots below on operands whose range
-// follows from the contract's own arithmetic or from a property of the scene established once (kernels.hip map_to_hemisphere_tame,
+// follows from the contract's own arithmetic or from a property of the scene established once (cap_shade.h map_to_hemisphere_tame,
 // DESIGN.md "fp32 arithmetic contract"); per-vertex range checks with a second copy of the shading body had measured slower
 // (docs/experiments.md (70), (97)).
 #pragma once

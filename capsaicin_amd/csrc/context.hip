@@ -1339,7 +1339,7 @@ int cap_bvh_build(CapContext* c)
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t n = c->tri_count;
     HIP_TRY(c->shade_tris.ensure(kShadeRec * (size_t)n));
-    // + 4 zero records: the exhaustive kernels test triangles in pairs and fetch one pair ahead (kernels.hip); a zero record
+    // + 4 zero records: the exhaustive kernels test triangles in pairs and fetch one pair ahead (cap_exhaustive.h); a zero record
     // has det == 0 and is never hit
     HIP_TRY(c->tris_sorted.ensure(4 * ((size_t)n + 4)));
     HIP_TRY(hipMemsetAsync(c->tris_sorted.p, 0, sizeof(float4) * 4 * ((size_t)n + 4), c->stream));
@@ -1998,7 +1998,7 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
 
     // Persistent grids must be fully resident: a workgroup that cannot be co-scheduled runs as a second round after the first
     // waves retire and doubles the kernel's tail.  blocks_per_cu is therefore the residency the kernels are built for
-    // (launch bounds in kernels.hip), not the 8 a register-light kernel could reach.
+    // (launch bounds in kernels.hip and small_scene.hip), not the 8 a register-light kernel could reach.
     uint32_t blocks_per_cu = fused ? 6u : (stack_entries <= 32 ? 5u : 2u);  // measured: 4..8 within 4 %, 6 best
     if (c->sw.v[SW_BLOCKS_PER_CU] >= 0) blocks_per_cu = (uint32_t)std::max<int64_t>(1, c->sw.v[SW_BLOCKS_PER_CU]);
     const SceneDev  scene = scene_dev(c);
@@ -2067,7 +2067,7 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
             // sensor point (cx, cy, f) projects to (G c).x / (G c).z * f instead of cx: off by at most
             //   skew * (f + 2 |cx| + |cy| + |cx| (|cx| + |cy|) / f)  <=  skew * (f + sx + sy / 2 + (sx + sy) sx / (4 f))
             // on the sensor (|cx| <= sx / 2, |cy| <= sy / 2), i.e. skew * width * (f / sx + 1 + sy / (2 sx) + (sx + sy) / (4 f)) pixels,
-            // and likewise in y.  The tiles' test (kernels.hip lds_bounds) grows every bound by kCameraCullPad = 2 pixels for this, the
+            // and likewise in y.  The tiles' test (small_scene.hip stage_camera_pairs) grows every bound by kCameraCullPad = 2 pixels for this, the
             // rounding of the projection and nothing else (the jitter stays inside its pixel): the cull is on only while the worst-case
             // shift on the sensor is at most an eighth of that pad.  The rest is for vertices off the sensor, whose error grows with
             // the tangent of their angle to the axis (|cy| / f = 5, 79 degrees: five times the shift; tests/test_pair_culls_gpu.py C7

@@ -432,26 +432,12 @@ __global__ __launch_bounds__(kBlock) void k_forest_relocate(ForestRelocArgs a)
     a.nodes[4 * (size_t)i + 3] = make_float4(u2f(link[0]), u2f(link[1]), u2f(link[2]), u2f(link[3]));
 }
 
-template <auto KERNEL>
-uint32_t inst_resident(const LaunchCfg& cfg, uint32_t want)  // (resident_grid of kernels.hip)
-{
-    static int per_cu = -1;
-    if (per_cu < 0)
-    {
-        int n  = 0;
-        per_cu = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, KERNEL, (int)kBlock, 0) == hipSuccess && n > 0) ? n : 0;
-    }
-    if (!cfg.cu_count || !per_cu) return want;
-    const uint32_t cap = cfg.cu_count * (uint32_t)per_cu;
-    return want < cap ? want : cap;
-}
-
 template <int STACK, int MODE>
 void launch_inst(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const TlasDev& tl, const RayFilter& f, uint32_t* inst_out)
 {
     uint32_t want = (q.n + kBlock - 1) / kBlock;
     if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_query_inst<STACK, MODE>), dim3(inst_resident<k_query_inst<STACK, MODE>>(cfg, want)), dim3(kBlock), 0, cfg.stream, bvh, q, tl, f,
+    hipLaunchKernelGGL((k_query_inst<STACK, MODE>), dim3(resident_grid<k_query_inst<STACK, MODE>>(cfg, want)), dim3(kBlock), 0, cfg.stream, bvh, q, tl, f,
                        inst_out);
 }
 }  // namespace

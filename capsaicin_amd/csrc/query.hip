@@ -777,20 +777,6 @@ __global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, 1)) void k_query
 
 uint32_t multi_bucket(uint32_t k) { return k <= 1 ? 1u : k <= 4 ? 4u : k <= 8 ? 8u : 16u; }
 
-template <auto KERNEL>
-static uint32_t multi_resident(const LaunchCfg& cfg, uint32_t want)  // (resident_grid of kernels.hip)
-{
-    static int per_cu = -1;
-    if (per_cu < 0)
-    {
-        int n  = 0;
-        per_cu = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, KERNEL, (int)kBlock, 0) == hipSuccess && n > 0) ? n : 0;
-    }
-    if (!cfg.cu_count || !per_cu) return want;
-    const uint32_t cap = cfg.cu_count * (uint32_t)per_cu;
-    return want < cap ? want : cap;
-}
-
 template <int K, bool COUNT>
 static void launch_multi8_k(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, uint32_t refill, const RayFilter* f)
 {
@@ -832,10 +818,10 @@ static void launch_binary_multi_k(const LaunchCfg& cfg, const BvhDev& b, const M
     if (deferred && cfg.cu_count && want > cfg.cu_count) want = cfg.cu_count;
     if (want == 0) want = 1;
     if (f)
-        hipLaunchKernelGGL((k_query_binary_multi_f<STACK, K, COUNT>), dim3(multi_resident<k_query_binary_multi_f<STACK, K, COUNT>>(cfg, want)),
+        hipLaunchKernelGGL((k_query_binary_multi_f<STACK, K, COUNT>), dim3(resident_grid<k_query_binary_multi_f<STACK, K, COUNT>>(cfg, want)),
                            dim3(kBlock), 0, cfg.stream, b, m, deferred ? 1u : 0u, *f);
     else
-        hipLaunchKernelGGL((k_query_binary_multi<STACK, K, COUNT>), dim3(multi_resident<k_query_binary_multi<STACK, K, COUNT>>(cfg, want)),
+        hipLaunchKernelGGL((k_query_binary_multi<STACK, K, COUNT>), dim3(resident_grid<k_query_binary_multi<STACK, K, COUNT>>(cfg, want)),
                            dim3(kBlock), 0, cfg.stream, b, m, deferred ? 1u : 0u);
 }
 
@@ -873,7 +859,7 @@ static void launch_binary_f(const LaunchCfg& cfg, const BvhDev& b, const QueryAr
     uint32_t want = (q.n + kBlock - 1) / kBlock;
     if (deferred && cfg.cu_count && want > cfg.cu_count) want = cfg.cu_count;  // (as launch_query_binary)
     if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_query_binary_f<STACK, MODE>), dim3(multi_resident<k_query_binary_f<STACK, MODE>>(cfg, want)), dim3(kBlock), 0, cfg.stream,
+    hipLaunchKernelGGL((k_query_binary_f<STACK, MODE>), dim3(resident_grid<k_query_binary_f<STACK, MODE>>(cfg, want)), dim3(kBlock), 0, cfg.stream,
                        b, q, deferred ? 1u : 0u, f);
 }
 

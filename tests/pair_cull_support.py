@@ -2,7 +2,7 @@
 
 The fused kernels of scenes of at most 64 triangles skip work on three decisions, each claimed to change no result bit:
   * the next-event pair cull of the EXT model (context.hip update_nee_pairs): `nee_rule` restates its rule;
-  * the camera pair cull of bounce 0 (kernels.hip lds_bounds / pair_mask, host gate in context.hip cap_render): `camera_bounds` restates
+  * the camera pair cull of bounce 0 (small_scene.hip stage_camera_pairs / pair_mask, host gate in context.hip cap_render): `camera_bounds` restates
     the bounds and the gate, `camera_truth` says which of the model's culls are wrong;
   * the occluder-first probes of the reference model: `probe_scores` restates the order they probe in.
 Everything is numpy: fp32 where the code under test works in fp32 (fused multiply-adds where it writes fmaf), float64 where it works in

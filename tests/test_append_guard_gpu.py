@@ -1,4 +1,4 @@
-"""The kernels' queue-append guard (CapStats::guard_append, kernels.hip wave_append2).
+"""The kernels' queue-append guard (CapStats::guard_append, cap_shade.h wave_append2).
 
 A sub-queue's capacity is static because a path keeps the class it got at bounce 0; until round 4 the appends rested on that
 argument alone and wrote `slot + class * class_capacity` unchecked.  Here the capacity is made too small on purpose

@@ -1,4 +1,4 @@
-"""Per-chunk plumbing of the fused small-scene kernels (kernels.hip kChunkLean): lanes past the end of a class's last chunk load the
+"""Per-chunk plumbing of the fused small-scene kernels (cap_shade.h kChunkLean): lanes past the end of a class's last chunk load the
 class's last entry, the blue-noise coordinates of bounce >= 1 come from a multiply-high by a host-computed reciprocal of tiles_x, and
 the per-slot sample constants (count = frame * 25 + bounce) are staged once per workgroup.  Cornell box, reference model, depth 4, at
 the smallest shapes where each can go wrong; every plane and every ray counter bit for bit against the oracle.  The EXT and feedback

@@ -154,7 +154,7 @@ def test_depth_zero_and_max_depth(native_lib, bluenoise, cornell_path):
 def _open_top_scene():
     """A floor and two low walls under an open sky: the occluder the producer-side probe tests first (the pair farthest along the
     light, which points up: lighting.h:20-33) shadows almost nothing, so nearly every shadow ray of bounces >= 1 survives the probe
-    and travels through its wave's 128-entry ring (kernels.hip trace_ring)."""
+    and travels through its wave's 128-entry ring (small_scene.hip trace_ring)."""
     def quad(a, b, c, d):
         return [[a, b, c], [a, c, d]]
     tris = quad([-2, 0, 2], [2, 0, 2], [2, 0, -2], [-2, 0, -2])                    # floor, normal +y

@@ -228,7 +228,7 @@ def test_texture_sampling():
 
 
 def test_unorm8_is_the_division():
-    """kernels.hip sample_texture() turns a texel byte into b / 255.0f with a multiply and one residual step (two fmaf) instead of
+    """cap_shade.h sample_texture() turns a texel byte into b / 255.0f with a multiply and one residual step (two fmaf) instead of
     the division the oracle performs (cap_oracle.cpp sample_texture): equal for all 256 bytes, in exact arithmetic rounded to fp32
     once per operation (round to nearest even), which is what v_mul_f32 / v_fma_f32 and fmaf do."""
     from fractions import Fraction

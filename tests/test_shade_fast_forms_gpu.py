@@ -1,4 +1,4 @@
-"""Unscaled square roots and divisions in the shading of the fused small-scene kernels (csrc/cap_unscaled.h, kernels.hip
+"""Unscaled square roots and divisions in the shading of the fused small-scene kernels (csrc/cap_unscaled.h, cap_shade.h
 map_to_hemisphere_tame, k_trace_shade<..., TAME>): the device self-tests report no differing bit, and renders whose operands sit on
 the edges of the proven ranges -- blue-noise texels 0 / 255 and their neighbours (r2 = 0: sin_theta exactly 0; r2 next to 1),
 normals with -0 components, unit normals (1, 0, 1e-30) and (0.6, 0.8, 1e-30) that trip the two halves of ortho_vector's guard beside normals that do not, a scene whose

@@ -78,9 +78,9 @@ def static_issue_costs():
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         for src, keys in (("trace8.hip", {"k_trace_closest8": "k_trace_closest8"}),
-                          ("kernels.hip", {HEADLINE: "k_trace_shadeILb0ELb0ELb0ELb1ELb%dE" % (os.environ.get("CAP_LIB_VARIANT") != "shadeieee"),
-                                           EXT: "k_trace_shadeILb0ELb1ELb0ELb1ELb0E", "k_shade<": "k_shadeILb0E",
-                                           "k_trace_any<": "k_trace_anyILi24E", "k_primary_shade": "k_primary_shadeILb0E"})):
+                          ("small_scene.hip", {HEADLINE: "k_trace_shadeILb0ELb0ELb0ELb1ELb%dE" % (os.environ.get("CAP_LIB_VARIANT") != "shadeieee"),
+                                               EXT: "k_trace_shadeILb0ELb1ELb0ELb1ELb0E"}),
+                          ("kernels.hip", {"k_shade<": "k_shadeILb0E", "k_trace_any<": "k_trace_anyILi24E", "k_primary_shade": "k_primary_shadeILb0E"})):
             lst = os.path.join(tmp, src + ".s")
             try:
                 subprocess.run(["/opt/rocm/bin/hipcc"] + flags + [os.path.join(csrc, src), "-o", lst], check=True, capture_output=True, timeout=900)

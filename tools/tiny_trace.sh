@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-launch durations of a Cornell step with very little work (1 spp and 8 spp at 1080p): T = fixed cost + work, the measurement
-# behind the 77-us-per-launch finding of round 3 (kernels.hip flush_stats).  Run through gpurun.
+# behind the 77-us-per-launch finding of round 3 (cap_shade.h flush_stats).  Run on the GPU box.
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
