@@ -40,6 +40,7 @@ enum CapSwitch : uint32_t
     SW_AUTO_SAH_TRIANGLES,  // AUTO builds with surface-area splits from this many triangles on
     SW_NO_NEE_PAIR_CULL,    // EXT model: next-event rays test every fan pair (read by the next cap_bvh_build / cap_materials_upload)
     SW_RAYGEN_KERNEL,       // dense scenes: the camera rays' identity queue written out by k_raygen_identity instead of generated in the trace kernel
+    SW_NO_PLANE_CODE,       // small-scene path under albedo_in_w: bounce 0 writes the constant direct plane as before (ShadeArgs::code_in_color off)
     SW_COUNT
 };
 struct SwitchTable
@@ -110,7 +111,12 @@ void launch_trace_closest8_camera(const LaunchCfg& cfg, const BvhDev& bvh, const
 // work: kQueueClasses zeroed chunk-grab counters for this launch (exhaustive path; may be NULL for the LBVH kernels)
 void launch_trace_any(const LaunchCfg& cfg, const BvhDev& bvh, const ShadowQueue& q, uint32_t max_count, float4* target,
                       uint32_t pixels_padded, uint32_t n_slots, uint64_t* guard, uint32_t* work, bool mostly_unoccluded,
-                      const FrameConst* frames);
+                      const FrameConst* frames, float4* code_plane = nullptr);
+// code_plane (ShadeArgs::code_in_color, bounce 0 of the small-scene path): target holds nothing yet.  An unoccluded ray stores its
+// contribution there instead of adding it, and marks the path's word code_plane[plane index].w (code -> code + kCodeLit).
+// Only the two small-scene kernels of the reference model have the form (stack_entries == 0, !mostly_unoccluded).  Any other kernel
+// would ignore code_plane and ADD to a `direct` nobody has written, unmarked and without an error: launch_trace_any asserts the
+// condition, and the only caller that passes a plane derives it from code_in_color, whose own condition (context.hip) implies it.
 
 // The same for the reference model's shadow rays on the wide view with lane refill (trace8.hip): dense scenes, where a traversal step's
 // round trip ends in HBM.  Needs bvh.wide8_ok and the zeroed grab counters `work`.
@@ -258,7 +264,18 @@ struct ShadeArgs
     // any-hit launch left on the small-scene path is bounce 0's
     uint32_t          wave_ring;
     uint32_t          cull_camera_pairs;  // bounce 0 of the small-scene path: the camera basis is orthonormal, so a tile may skip the pairs off its screen area
+    // albedo_in_w on the small-scene path (reference model): the code sits in color.w, which every later writer of the colour plane carries
+    // through, and bounce 0 writes no direct plane at all: zeros and the sky constant are what the code already says.  The bounce-0
+    // any-hit launch stores the contribution of an unoccluded ray into `direct` and turns the code c into c + 4, "direct holds a value";
+    // the resolve loads `direct` only there.  An entry of `direct` an earlier batch left is never read: the word that says whether to
+    // read it is rewritten by every batch's bounce 0.  Set by the host only where every kernel involved has the form: the fused
+    // kernel of bounce 0 (trace_shade_has_code_form), the small-scene any-hit kernels (launch_trace_any's code_plane) and the resolve.
+    uint32_t          code_in_color;
 };
+// The first vertex's code (direct.w under albedo_in_w, color.w under code_in_color).  Three places must agree on it: shade_vertex
+// (the plane's word, and under CODE the spare word of a bounce-0 shadow entry), store_first_direct (+ kCodeLit) and the resolves.
+constexpr float kCodePadding = 0.f, kCodeSky = 1.f, kCodeKd = 2.f, kCodeBlack = 3.f;
+constexpr float kCodeLit = 4.f;  // code_in_color: added where the bounce-0 any-hit launch stored a contribution into `direct`
 // Pixels the bounce-0 kernel grows every fan pair's screen bounds by (small_scene.hip stage_camera_pairs).  The host's gate for
 // cull_camera_pairs (context.hip cap_render) allows a camera basis to move a projected point by an eighth of it.
 constexpr float kCameraCullPad = 2.0f;
@@ -270,11 +287,13 @@ void launch_shade(const LaunchCfg& cfg, const ShadeArgs& args, bool ext, bool fe
 bool launch_primary_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, float4* hits, bool ext);
 // small-scene path: exhaustive closest hit fused with the shading of the vertex found (bounce 0 generates the camera rays)
 void launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback = false);
+// whether the reference model's bounce 0 of this scene has the form ShadeArgs::code_in_color asks for (the kernel of tame records in LDS)
+bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene);
 
 // ---- accumulate / exchange ----
 // accum[pl] += sum over slots (in slot order) of color*albedo + direct; .w counts frames.
 void launch_resolve(const LaunchCfg& cfg, const Planes& planes, uint32_t n_slots, uint32_t pixels_padded, float4* accum,
-                    bool albedo_in_w = false, float kd_untextured = 0.0f);
+                    bool albedo_in_w = false, float kd_untextured = 0.0f, bool code_in_color = false);
 // plane_kind: 0 copy, 1 combined (color*albedo+direct from the three planes at slot offset), 2 mean (xyz / w)
 void launch_untile(const LaunchCfg& cfg, const ScreenDev& screen, const float4* src, const float4* albedo, const float4* direct,
                    int plane_kind, float4* image);

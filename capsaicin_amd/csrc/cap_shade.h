@@ -190,6 +190,7 @@ __device__ __forceinline__ uint32_t wave_append(bool emit, uint32_t* counter)
 //   PROBE    the producer-side shadow probe and the per-wave ring (see ProbeArgs)
 //   TAME     the scene's shading records are tame (SceneDev::shade_tame): square roots and divisions in their unscaled forms
 //   LEAN     the lean per-chunk plumbing (see kChunkLean)
+//   CODE     bounce 0 under ShadeArgs::code_in_color: the first vertex's code goes to color.w and the direct plane is not written
 struct ShadePre
 {
     bool  valid;
@@ -506,18 +507,18 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
         if (C::FIRST && !valid)
         {
             // padding lane of a partial / absent tile: define the planes so the resolve adds exact zeros
-            a.planes.color[plane_idx]  = make_float4(0, 0, 0, 0);
-            a.planes.direct[plane_idx] = make_float4(0, 0, 0, 0);  // albedo_in_w: code 0
-            if (!a.albedo_in_w) a.planes.albedo[plane_idx] = make_float4(0, 0, 0, 0);
+            a.planes.color[plane_idx]  = make_float4(0, 0, 0, 0);  // CODE: code 0
+            if (!C::CODE) a.planes.direct[plane_idx] = make_float4(0, 0, 0, 0);  // albedo_in_w: code 0
+            if (!C::CODE && !a.albedo_in_w) a.planes.albedo[plane_idx] = make_float4(0, 0, 0, 0);
         }
         if (valid && gid == kInvalidId)
         {
             if (C::FIRST)
             {
                 // rt_direct_lighting.hlsl:53-59, rt_indirect.hlsl:75-79
-                a.planes.color[plane_idx]  = make_float4(0.f, 0.f, 0.f, 1.f);
-                a.planes.direct[plane_idx] = make_float4(0.7f, 0.7f, 0.85f, 1.f);  // albedo_in_w: code 1
-                if (!a.albedo_in_w) a.planes.albedo[plane_idx] = make_float4(1.f, 1.f, 1.f, 1.f);
+                a.planes.color[plane_idx]  = make_float4(0.f, 0.f, 0.f, 1.f);  // CODE: code 1, which is also what says (0.7, 0.7, 0.85)
+                if (!C::CODE) a.planes.direct[plane_idx] = make_float4(0.7f, 0.7f, 0.85f, 1.f);  // albedo_in_w: code 1
+                if (!C::CODE && !a.albedo_in_w) a.planes.albedo[plane_idx] = make_float4(1.f, 1.f, 1.f, 1.f);
                 if (slot == a.aov_slot) a.planes.aov_normal_depth[pl] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
             else
@@ -572,11 +573,18 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
             const bool black = kd.x < 1e-5f && kd.y < 1e-5f && kd.z < 1e-5f;  // rt_direct_lighting.hlsl:68, rt_indirect.hlsl:108
             if (C::FIRST)
             {
-                a.planes.color[plane_idx]  = make_float4(0.f, 0.f, 0.f, 1.f);
                 // albedo_in_w (untextured scene, accumulate-only render): the albedo is one of four constants, so its plane is
                 // neither written nor read; direct.w carries which -- 0: (0,0,0) padding, 1: (1,1,1) sky, 2: the untextured kd, 3: black
-                a.planes.direct[plane_idx] = make_float4(0.f, 0.f, 0.f, a.albedo_in_w ? (black ? 3.f : 2.f) : 1.f);
-                if (!a.albedo_in_w) a.planes.albedo[plane_idx] = black ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(kd.x, kd.y, kd.z, 1.f);
+                // CODE: color.w carries it and `direct` is not written here -- all it would say is "nothing yet".  The word is safe
+                // there: the load-add-stores of the later bounces carry cur.w through and the sky term's atomics touch x, y, z only.
+                if (C::CODE)
+                    a.planes.color[plane_idx] = make_float4(0.f, 0.f, 0.f, black ? kCodeBlack : kCodeKd);  // (the shadow entry below repeats it)
+                else
+                {
+                    a.planes.color[plane_idx]  = make_float4(0.f, 0.f, 0.f, 1.f);
+                    a.planes.direct[plane_idx] = make_float4(0.f, 0.f, 0.f, a.albedo_in_w ? (black ? kCodeBlack : kCodeKd) : 1.f);
+                }
+                if (!C::CODE && !a.albedo_in_w) a.planes.albedo[plane_idx] = black ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(kd.x, kd.y, kd.z, 1.f);
                 if (slot == a.aov_slot)
                 {
                     float4 nd = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -691,8 +699,11 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
         {
             // reference model: the shadow ray's direction is its frame's light and tmin / tmax are constants (lighting.h:39-47), so
             // the entry is 32 B -- (origin, path id) and the contribution; the any-hit kernel looks the direction up by frame slot
+            // CODE: the spare word is the path's code for the any-hit kernel, which rewrites color.w without loading it.  It must be
+            // the word stored into color.w above, `black ? kCodeBlack : kCodeKd`: emit_shadow is only ever set under !black, so that
+            // is kCodeKd here.  A code that depends on more than `black` has to be carried to this store as a value.
             a.shadow.org_tmin[si]    = make_float4(p.x, p.y, p.z, u2f(pid));
-            a.shadow.contrib_pid[si] = make_float4(contrib.x, contrib.y, contrib.z, 0.0f);
+            a.shadow.contrib_pid[si] = make_float4(contrib.x, contrib.y, contrib.z, C::CODE ? kCodeKd : 0.0f);
         }
         if (emit_ext)
         {

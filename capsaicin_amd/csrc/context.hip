@@ -675,7 +675,7 @@ static const char* const kSwitchNames[SW_COUNT] = {
     "CAP_NO_WIDE8", "CAP_LANE1_PRIORITY", "CAP_PLOC_RADIUS", "CAP_SAHDEV_LEAF", "CAP_WIDE_HOST_COLLAPSE", "CAP_TRACE_LAUNCHES", "CAP_NO_TWO_LANES",
     "CAP_LANE_SPLIT_MIN", "CAP_BLOCKS_PER_CU", "CAP_NO_CAMERA_CULL", "CAP_NO_ALBEDO_IN_W", "CAP_NO_INLINE_NEE", "CAP_NO_INLINE_PROBE", "CAP_NO_WAVE_RING",
     "CAP_ANY_REFILL", "CAP_PRIMARY_WIDE", "CAP_NO_PACKET", "CAP_NO_ANY_PROBE", "CAP_ANY_PROBE", "CAP_ANY_BLOCKS", "CAP_NO_PRIMARY_FUSE", "CAP_W8_REFILL",
-    "CAP_W8_GRID", "CAP_AUTO_SAH_TRIANGLES", "CAP_NO_NEE_PAIR_CULL", "CAP_RAYGEN_KERNEL"};
+    "CAP_W8_GRID", "CAP_AUTO_SAH_TRIANGLES", "CAP_NO_NEE_PAIR_CULL", "CAP_RAYGEN_KERNEL", "CAP_NO_PLANE_CODE"};
 
 static void switches_from_environment(SwitchTable& t)
 {
@@ -2089,6 +2089,10 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
         // Nobody reads this batch's planes but the resolve (plane read-backs and the reconstruction chain need CAP_RENDER_AOV)
         const bool no_albedo_w = c->sw.on(SW_NO_ALBEDO_IN_W);  // A/B switch
         sa.albedo_in_w = (!no_albedo_w && !feedback && !lowres && !(flags & CAP_RENDER_AOV) && (ext || scene.texture_count == 0)) ? 1u : 0u;  // (the EXT model's first-vertex albedo is 1: it folds kd into the throughput)
+        // ... and on the small-scene path the constants bounce 0 would write into `direct` stay unwritten (ShadeArgs::code_in_color).  The
+        // EXT model is left out: its bounce 0 adds emission to `direct` and its shadow rays are traced inline, so it keeps two planes.
+        const bool no_plane_code = c->sw.on(SW_NO_PLANE_CODE);  // A/B switch
+        sa.code_in_color = (sa.albedo_in_w && fused && !ext && !no_plane_code && trace_shade_has_code_form(bvh, scene)) ? 1u : 0u;
         if (feedback)  // g_color_history = combined_history[(frame_count + 1) % 2], raytracing_system.cpp:1754-1759
             sa.fb = FeedbackDev{camera_dev(c->prev_camera), c->post_prev_nd.p, c->post_chist[(frame_begin + 1) % 2].p};
         const bool no_inline_nee = c->sw.on(SW_NO_INLINE_NEE);  // A/B switch
@@ -2191,7 +2195,8 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
                                              work_any + b * per_queue, frames);
                 else
                     launch_trace_any(cfg_any, bvh, sa.shadow, max_count, b == 0 ? L.pl_direct.p : L.pl_color.p, Ppad, ns, c->shaded_counter.p,
-                                     work_any + b * per_queue, /* next-event estimation: most shadow rays reach the light */ ext, frames);
+                                     work_any + b * per_queue, /* next-event estimation: most shadow rays reach the light */ ext, frames,
+                                     (b == 0 && sa.code_in_color) ? L.pl_color.p : nullptr);
                 ++c->stats.launches_trace_any;
                 if (trace_launch(c, "trace_any bounce %u batch %u", b, batch)) return fail(CAP_ERR_HIP, "trace_any failed");
             }
@@ -2209,7 +2214,7 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
         {
             StageTimer t(c, ST_RESOLVE, st);
             if (two_lanes && last_resolve) HIP_TRY(hipStreamWaitEvent(L.stream, last_resolve, 0));  // frame order of the additions
-            launch_resolve(cfg, sa.planes, ns, Ppad, c->accum.p, sa.albedo_in_w != 0u, scene.kd_untextured);
+            launch_resolve(cfg, sa.planes, ns, Ppad, c->accum.p, sa.albedo_in_w != 0u, scene.kd_untextured, sa.code_in_color != 0u);
             if (two_lanes)
             {
                 HIP_TRY(hipEventRecord(c->lane_ev[lane], L.stream));

@@ -15,6 +15,8 @@
 #include "cap_unscaled.h"
 #include "cap_wide_trace.h"
 
+#include <cassert>
+
 namespace cap
 {
 // Closest hit: minimum t, equal t resolved towards the lower global triangle id (visit-order independent).
@@ -441,10 +443,22 @@ static inline uint32_t pre_table_bytes(uint32_t n_slots, uint32_t pairs)
     const uint64_t b = (uint64_t)n_slots * (2u * pairs + 1u) * sizeof(float4);
     return (pairs && n_slots <= kMaxFrameSlots && b <= kPreTableMaxBytes) ? (uint32_t)b : 0u;
 }
-template <int STACK, bool RMW>
-__global__ __launch_bounds__(kBlock, stack_residency(STACK)) void k_trace_any(BvhDev bvh, ShadowQueue q, float4* target, uint32_t pixels_padded, uint32_t n_slots,
-                                                      uint64_t* guard, uint32_t* work, const FrameConst* frames, uint32_t pre_bytes)
+// CODE (launch_trace_any's code_plane, bounce 0 under ShadeArgs::code_in_color): nothing has written target[idx] in this batch.  The
+// parent form added the contribution c to the (0, 0, 0) bounce 0 had stored there; 0 + c has the bits of c because no component of c
+// is -0 -- every factor of it is >= +0 (light intensity, kd, 1 / pi, ndl = fmaxf(0, .)) -- so c is stored as it is, without the load.
+// The path's word in the colour plane goes from its code (the entry's spare word) to code + 4: "direct holds a value" (k_resolve_coded).
+// This launch runs before bounce 1's on the same stream, and the path is the only writer of both entries in it.
+__device__ __forceinline__ void store_first_direct(float4* target, float4* code_plane, size_t idx, float4 c)
 {
+    target[idx] = make_float4(c.x, c.y, c.z, 0.0f);
+    reinterpret_cast<float*>(code_plane + idx)[3] = c.w + kCodeLit;  // c.w: the entry's spare word, the code shade_vertex put into color.w
+}
+template <int STACK, bool RMW, bool CODE = false>
+__global__ __launch_bounds__(kBlock, stack_residency(STACK)) void k_trace_any(BvhDev bvh, ShadowQueue q, float4* target, uint32_t pixels_padded, uint32_t n_slots,
+                                                      uint64_t* guard, uint32_t* work, const FrameConst* frames, uint32_t pre_bytes,
+                                                      float4* code_plane)
+{
+    static_assert(!CODE || (STACK == 0 && !RMW), "CODE: the small-scene path's reference-model shadow rays");
     extern __shared__ float4 lds_pre[];
     __shared__ uint32_t lds_stack[(STACK ? STACK : 1) * (STACK ? kBlock : 1)];
     __shared__ float4   lds_light[RMW ? 1 : kMaxFrameSlots];
@@ -560,6 +574,8 @@ __global__ __launch_bounds__(kBlock, stack_residency(STACK)) void k_trace_any(Bv
                 {
                     if (RMW)
                         target[idx] = make_float4(cur.x + c.x, cur.y + c.y, cur.z + c.z, cur.w);
+                    else if constexpr (CODE)
+                        store_first_direct(target, code_plane, idx, q.contrib_pid[i]);
                     else
                     {
                         c           = q.contrib_pid[i];
@@ -593,8 +609,10 @@ __global__ __launch_bounds__(kBlock, stack_residency(STACK)) void k_trace_any(Bv
 #define CAP_ANY_PROBE 1
 #endif
 constexpr uint32_t kSurvivorCap = 128;  // per wave: <= 63 parked + <= 64 new
+template <bool CODE>  // see k_trace_any
 __global__ __launch_bounds__(kBlock) void k_trace_any_small(BvhDev bvh, ShadowQueue q, float4* target, uint32_t pixels_padded, uint32_t n_slots,
-                                                           uint64_t* guard, uint32_t* work, const FrameConst* frames, uint32_t probe)
+                                                           uint64_t* guard, uint32_t* work, const FrameConst* frames, uint32_t probe,
+                                                           float4* code_plane)
 {
     extern __shared__ float4 lds_pre[];  // PairPre rows per frame slot, see k_trace_any
     __shared__ float4   lds_light[kMaxFrameSlots];
@@ -673,8 +691,13 @@ __global__ __launch_bounds__(kBlock) void k_trace_any_small(BvhDev bvh, ShadowQu
             {
                 // lighting.h:57-60: unoccluded -> the contribution evaluated at shading time is added
                 const size_t idx = (size_t)(pid >> kPidShift) * pixels_padded + (pid & kPidMask);
-                const float4 c = q.contrib_pid[i], cur = target[idx];
-                target[idx]    = make_float4(cur.x + c.x, cur.y + c.y, cur.z + c.z, cur.w);
+                if constexpr (CODE)
+                    store_first_direct(target, code_plane, idx, q.contrib_pid[i]);
+                else
+                {
+                    const float4 c = q.contrib_pid[i], cur = target[idx];
+                    target[idx]    = make_float4(cur.x + c.x, cur.y + c.y, cur.z + c.z, cur.w);
+                }
             }
         }
     };
@@ -977,8 +1000,9 @@ void launch_trace_closest(const LaunchCfg& cfg, const BvhDev& bvh, const RayQueu
 
 void launch_trace_any(const LaunchCfg& cfg, const BvhDev& bvh, const ShadowQueue& q, uint32_t max_count, float4* target,
                       uint32_t pixels_padded, uint32_t n_slots, uint64_t* guard, uint32_t* work, bool mostly_unoccluded,
-                      const FrameConst* frames)
+                      const FrameConst* frames, float4* code_plane)
 {
+    assert(!code_plane || (cfg.stack_entries == 0 && !mostly_unoccluded));  // the two kernels below that have the form
     dim3         grid(queue_grid(cfg, max_count));
     const BvhDev bw = for_grid(bvh, grid.x);
     // shadow rays share one direction per frame and retire early: the plain per-chunk kernel beats the refill variant here
@@ -994,14 +1018,20 @@ void launch_trace_any(const LaunchCfg& cfg, const BvhDev& bvh, const ShadowQueue
         const uint32_t cap = cfg.cu_count ? cfg.cu_count * per_cu : cfg.grid_blocks;
         g = g > cap ? cap : (g ? g : 1u);
         grid = dim3(g);
-        hipLaunchKernelGGL(k_trace_any_small, grid, dim3(kBlock), pre, cfg.stream, bw, q, target, pixels_padded, n_slots, guard, work, frames, probe);
+        const auto kernel = code_plane ? k_trace_any_small<true> : k_trace_any_small<false>;
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), pre, cfg.stream, bw, q, target, pixels_padded, n_slots, guard, work, frames, probe, code_plane);
         return;
     }
-#define CAP_LAUNCH_ANY(S, R) \
-    hipLaunchKernelGGL((k_trace_any<S, R>), grid, dim3(kBlock), pre, cfg.stream, bw, q, target, pixels_padded, n_slots, guard, work, frames, pre)
+#define CAP_LAUNCH_ANY(S, R, ...) \
+    hipLaunchKernelGGL((k_trace_any<S, R, ##__VA_ARGS__>), grid, dim3(kBlock), pre, cfg.stream, bw, q, target, pixels_padded, n_slots, guard, work, frames, pre, code_plane)
     if (cfg.stack_entries == 0)
     {
-        if (mostly_unoccluded) CAP_LAUNCH_ANY(0, true); else CAP_LAUNCH_ANY(0, false);
+        if (mostly_unoccluded)
+            CAP_LAUNCH_ANY(0, true);
+        else if (code_plane)
+            CAP_LAUNCH_ANY(0, false, true);
+        else
+            CAP_LAUNCH_ANY(0, false);
     }
     else if (bw.wide8_ok)
     {
@@ -1025,7 +1055,7 @@ template <bool FIRST_, bool EXT_, bool FB_ = false>
 struct ShadeStageCfg
 {
     static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_;
-    static constexpr bool CARRY = false, SKY_RMW = true, PROBE = false, TAME = false, LEAN = false;
+    static constexpr bool CARRY = false, SKY_RMW = true, PROBE = false, TAME = false, LEAN = false, CODE = false;
 };
 
 // Stand-alone shade stage (used with the LBVH stack traversal): consumes the hit records of the preceding trace kernel.

@@ -9,6 +9,7 @@ namespace cap
 // ------------------------------------------------------------------------------------------------
 // combine_illumination.hlsl:29 per frame, then a plain running fp32 sum in frame order.
 // ALBEDO_IN_W (ShadeArgs::albedo_in_w): no albedo plane; direct.w says which of the four constant albedos the path's first vertex has
+// (the form with the code in color.w is k_resolve_coded below)
 template <bool ALBEDO_IN_W>
 __global__ __launch_bounds__(kBlock) void k_resolve(Planes planes, uint32_t n_slots, uint32_t Ppad, float4* accum, float kd_untextured)
 {
@@ -36,12 +37,57 @@ __global__ __launch_bounds__(kBlock) void k_resolve(Planes planes, uint32_t n_sl
     }
 }
 
+// ShadeArgs::code_in_color: the code is color.w -- 0 padding, 1 sky, 2 the untextured kd, 3 black, and + 4 where the bounce-0 any-hit
+// launch stored a contribution into `direct`.  Everything else `direct` would hold is a constant the code names (zeros; the sky's
+// (0.7, 0.7, 0.85)), so the plane is loaded only under the flag: the same expression on the same values as k_resolve<true>, and an
+// entry of `direct` that an earlier batch left behind is not looked at.
+// The slots of a pixel go eight at a time: the eight colour loads, then the `direct` loads they ask for, all in flight together (a
+// slot-by-slot loop would chain two round trips per slot), then the additions in slot order.
+__global__ __launch_bounds__(kBlock) void k_resolve_coded(Planes planes, uint32_t n_slots, uint32_t Ppad, float4* accum, float kd_untextured)
+{
+    constexpr uint32_t kGroup = 8;
+    for (uint32_t pl = blockIdx.x * kBlock + threadIdx.x; pl < Ppad; pl += gridDim.x * kBlock)
+    {
+        float4 acc = accum[pl];
+        for (uint32_t s0 = 0; s0 < n_slots; s0 += kGroup)
+        {
+            float4 c[kGroup], d[kGroup];
+#pragma unroll
+            for (uint32_t k = 0; k < kGroup; ++k)
+            {
+                c[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (s0 + k < n_slots) c[k] = planes.color[(size_t)(s0 + k) * Ppad + pl];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < kGroup; ++k)
+            {
+                d[k] = c[k].w == kCodeSky ? make_float4(0.7f, 0.7f, 0.85f, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (c[k].w >= kCodeLit) d[k] = planes.direct[(size_t)(s0 + k) * Ppad + pl];  // (never on a slot behind n_slots: its c is 0)
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < kGroup; ++k)
+                if (s0 + k < n_slots)
+                {
+                    const float code = c[k].w >= kCodeLit ? c[k].w - kCodeLit : c[k].w;
+                    const float al   = code == kCodeSky ? 1.0f : (code == kCodeKd ? kd_untextured : 0.0f);
+                    acc.x = acc.x + (c[k].x * al + d[k].x);
+                    acc.y = acc.y + (c[k].y * al + d[k].y);
+                    acc.z = acc.z + (c[k].z * al + d[k].z);
+                    acc.w = acc.w + 1.0f;
+                }
+        }
+        accum[pl] = acc;
+    }
+}
+
 void launch_resolve(const LaunchCfg& cfg, const Planes& planes, uint32_t n_slots, uint32_t Ppad, float4* accum, bool albedo_in_w,
-                    float kd_untextured)
+                    float kd_untextured, bool code_in_color)
 {
     uint32_t g = (Ppad + kBlock - 1) / kBlock;
     if (g > 4096) g = 4096;
-    if (albedo_in_w)
+    if (code_in_color)
+        hipLaunchKernelGGL(k_resolve_coded, dim3(g ? g : 1), dim3(kBlock), 0, cfg.stream, planes, n_slots, Ppad, accum, kd_untextured);
+    else if (albedo_in_w)
         hipLaunchKernelGGL(k_resolve<true>, dim3(g ? g : 1), dim3(kBlock), 0, cfg.stream, planes, n_slots, Ppad, accum, kd_untextured);
     else
         hipLaunchKernelGGL(k_resolve<false>, dim3(g ? g : 1), dim3(kBlock), 0, cfg.stream, planes, n_slots, Ppad, accum, kd_untextured);

@@ -28,11 +28,13 @@ __device__ unsigned long long g_wave_times[2 * 16384];  // (start, end) s_memrea
 // TAME: the scene's shading records are tame (SceneDev::shade_tame, established where they are written), which is what lets the
 // vertex's normalize3 -- and with it everything downstream of a unit normal -- take the unscaled forms.  Chosen at launch like LDS;
 // only the reference model's kernels with the scene in LDS have the instantiation.
-template <bool FIRST_, bool EXT_, bool FB_, bool LDS_, bool TAME_>
+// CODE: ShadeArgs::code_in_color, bounce 0's form without the direct plane.  Only the TAME kernel has it (trace_shade_has_code_form).
+template <bool FIRST_, bool EXT_, bool FB_, bool LDS_, bool TAME_, bool CODE_ = false>
 struct TraceShadeCfg
 {
     static_assert(!TAME_ || (!EXT_ && !FB_ && LDS_), "TAME: reference model, scene in LDS");
-    static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_, LDS = LDS_, TAME = TAME_;
+    static_assert(!CODE_ || (FIRST_ && TAME_), "CODE: bounce 0 of the reference model, scene in LDS, tame records");
+    static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_, LDS = LDS_, TAME = TAME_, CODE = CODE_;
     static constexpr bool CARRY = !EXT, SKY_RMW = false;
     static constexpr bool PROBE = !EXT && !FB && LDS;  // the producer-side shadow probe (ShadeArgs::inline_probe) and the per-wave ring
     // the lean per-chunk plumbing (see kChunkLean): the reference model's kernels with the scene in LDS and tame records.  (The
@@ -140,10 +142,10 @@ __device__ __forceinline__ void stage_probe_rows(const BvhDev& bvh, const ShadeA
     }
 }
 
-template <bool FIRST, bool EXT, bool FB = false, bool LDS = false, bool TAME = false>
-__global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, EXT, FB, LDS, TAME>::kBlocksPerCu)) void k_trace_shade(BvhDev bvh, ShadeArgs a)
+template <bool FIRST, bool EXT, bool FB = false, bool LDS = false, bool TAME = false, bool CODE = false>
+__global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, EXT, FB, LDS, TAME, CODE>::kBlocksPerCu)) void k_trace_shade(BvhDev bvh, ShadeArgs a)
 {
-    using C = TraceShadeCfg<FIRST, EXT, FB, LDS, TAME>;
+    using C = TraceShadeCfg<FIRST, EXT, FB, LDS, TAME, CODE>;
     const uint32_t Ppad     = a.screen.pixels_padded;
     // FIRST: the identity queue of the whole batch, chunk = slot * (Ppad / 64) + 64-pixel group.  Otherwise: chunk slots of the
     // input queue.  Either way the grid is persistent (the LDS tables are staged once per workgroup, not once per frame slot).
@@ -456,9 +458,9 @@ void launch_shade_forms_selftest(hipStream_t stream, unsigned long long* out_dev
     hipLaunchKernelGGL(k_shade_forms_selftest, dim3(4096), dim3(kBlock), 0, stream, out_device, which);
 }
 
-// The twelve instantiations that exist, each under the tuple it was instantiated with.  Bounce 0 has no feedback form, the two
-// models and feedback exclude each other, and TAME is the reference model with the scene in LDS (TraceShadeCfg).
-enum : uint32_t { TS_FIRST = 1, TS_EXT = 2, TS_FB = 4, TS_LDS = 8, TS_TAME = 16 };
+// The thirteen instantiations that exist, each under the tuple it was instantiated with.  Bounce 0 has no feedback form, the two
+// models and feedback exclude each other, TAME is the reference model with the scene in LDS and CODE its bounce 0 (TraceShadeCfg).
+enum : uint32_t { TS_FIRST = 1, TS_EXT = 2, TS_FB = 4, TS_LDS = 8, TS_TAME = 16, TS_CODE = 32 };
 struct TraceShadeKernel
 {
     uint32_t is;
@@ -467,9 +469,10 @@ struct TraceShadeKernel
 template <uint32_t IS>
 constexpr TraceShadeKernel trace_shade_kernel()
 {
-    return {IS, k_trace_shade<(IS & TS_FIRST) != 0, (IS & TS_EXT) != 0, (IS & TS_FB) != 0, (IS & TS_LDS) != 0, (IS & TS_TAME) != 0>};
+    return {IS, k_trace_shade<(IS & TS_FIRST) != 0, (IS & TS_EXT) != 0, (IS & TS_FB) != 0, (IS & TS_LDS) != 0, (IS & TS_TAME) != 0, (IS & TS_CODE) != 0>};
 }
-constexpr TraceShadeKernel kTraceShadeKernels[12] = {
+constexpr TraceShadeKernel kTraceShadeKernels[13] = {
+    trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_CODE>(),
     trace_shade_kernel<TS_FIRST | TS_EXT | TS_LDS>(), trace_shade_kernel<TS_FIRST | TS_EXT>(),
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME>(), trace_shade_kernel<TS_FIRST | TS_LDS>(), trace_shade_kernel<TS_FIRST>(),
     trace_shade_kernel<TS_EXT | TS_LDS>(), trace_shade_kernel<TS_EXT>(),
@@ -477,23 +480,31 @@ constexpr TraceShadeKernel kTraceShadeKernels[12] = {
     trace_shade_kernel<TS_LDS | TS_TAME>(), trace_shade_kernel<TS_LDS>(), trace_shade_kernel<0>(),
 };
 
+// the unscaled forms: reference model, scene in LDS, tame shading records (-DCAP_SHADE_IEEE keeps the plain sqrtf and `/`
+// everywhere for A/B runs: capsaicin_amd/variants/shadeieee.flags)
+static bool tame_kernels(const BvhDev& bvh, const SceneDev& scene)
+{
+#if defined(CAP_SHADE_IEEE)
+    return false;
+#else
+    return bvh.tri_count <= kExhaustiveMax && scene.shade_tame != 0;
+#endif
+}
+bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene) { return tame_kernels(bvh, scene); }
+
 void launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback)
 {
     const bool first = args.bounce == 0;
     const bool fb    = feedback && !ext && !first;  // (bounce 0 defines the planes' entries: nothing to reuse yet)
     const bool lds   = bvh.tri_count <= kExhaustiveMax;
-    // the unscaled forms: reference model, scene in LDS, tame shading records (-DCAP_SHADE_IEEE keeps the plain sqrtf and `/`
-    // everywhere for A/B runs: capsaicin_amd/variants/shadeieee.flags)
-#if defined(CAP_SHADE_IEEE)
-    const bool tame = false;
-#else
-    const bool tame = lds && !ext && !fb && args.scene.shade_tame != 0;
-#endif
-    const uint32_t is = (first ? TS_FIRST : 0u) | (ext ? TS_EXT : 0u) | (fb ? TS_FB : 0u) | (lds ? TS_LDS : 0u) | (tame ? TS_TAME : 0u);
+    const bool tame  = !ext && !fb && tame_kernels(bvh, args.scene);
+    const bool code  = first && args.code_in_color != 0u;
+    assert(!code || tame);  // the host's condition for code_in_color: reference model and trace_shade_has_code_form()
+    const uint32_t is = (first ? TS_FIRST : 0u) | (ext ? TS_EXT : 0u) | (fb ? TS_FB : 0u) | (lds ? TS_LDS : 0u) | (tame ? TS_TAME : 0u) | (code ? TS_CODE : 0u);
     // the queue's persistent grid; bounce 0's queue is the identity queue of the batch, one entry per padded pixel and frame slot
     const uint32_t gx = queue_grid(cfg, first ? args.screen.pixels_padded * args.n_slots : args.max_count);
     const TraceShadeKernel* k = kTraceShadeKernels;
-    while (k->is != is && k + 1 < kTraceShadeKernels + 12) ++k;
+    while (k->is != is && k + 1 < kTraceShadeKernels + 13) ++k;
     assert(k->is == is);  // the table holds every tuple the lines above can derive
     hipLaunchKernelGGL(k->kernel, dim3(gx), dim3(kBlock), 0, cfg.stream, bvh, args);
 }
