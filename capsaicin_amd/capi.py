@@ -213,6 +213,7 @@ SYMBOLS = {
     "cap_debug_set": (_i, [_vp, _u32, _u64]),
     "cap_debug_get": (_i, [_vp, _u32, C.POINTER(_u64)]),
     "cap_debug_switch_index": (_i, [C.c_char_p]),
+    "cap_debug_pair_ids_dense": (_i, [_vp, _u32, _u32, _u32]),
     "cap_render": (_i, [_vp, _u32, _u32, _u32, _u32]),
     "cap_accum_reset": (_i, [_vp]),
     "cap_accum_import": (_i, [_vp, _vp, _u64]),
@@ -576,6 +577,7 @@ class Renderer:
     DEBUG_QUEUE_CANARY_FILL, DEBUG_QUEUE_CANARY_BEHIND, DEBUG_QUEUE_CANARY_USED, DEBUG_SELFTEST_DIV, DEBUG_NEE_PAIRS = 6, 7, 8, 9, 10
     DEBUG_SELFTEST_SHADE_UNARY, DEBUG_SELFTEST_SHADE_DIV2, DEBUG_SHADE_TAME = 11, 12, 13
     DEBUG_CAMERA_CULL = 14
+    DEBUG_MARK_FORM = 15  # form << 8 | dense; form 0 none, 1 by id, 2 carry chain, 3 carry chain over two words
 
     def debug_set(self, key, value):
         _check(lib().cap_debug_set(self.ctx, key, value), "cap_debug_set")

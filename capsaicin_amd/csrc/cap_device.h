@@ -70,6 +70,9 @@ struct BvhDev
     uint32_t      fan_pair_nee_count;
     int32_t       root;       // 0, or ~0 for a single triangle
     uint32_t      tri_count;  // 0 -> every ray misses
+    // fan pairs only and pair j holds triangles 2j, 2j + 1: a triangle's id is its position in the pair list (pair_ids_dense();
+    // cap_exhaustive.h builds the candidate mask of such a scene by position)
+    uint32_t      tri_ids_dense;
     // compressed 8-wide view (cap_wide.h): 5 x float4 per node, breadth-first; 64-B intersection records in its own leaf order
     const float4* nodes8;
     const float4* tris8;

@@ -36,6 +36,26 @@ __device__ __forceinline__ void load_const_tri(const float4* base, uint32_t k, f
 #endif
 }
 
+// The two sign flips of tri_scaled(), each as one v_bitop3_b32 on the device.  With K = 0x80000000 and s = f2u(ddn) & K:
+//   CAP_FLIP_SAME(s, x) = x ^ s        = x ^ (ddn & K)     (V, whose own negation is folded in: see tri_scaled)
+//   CAP_FLIP_OPP(s, x)  = x ^ (s ^ K)  = x ^ (~ddn & K)    (U and T)
+// Truth table of bitop3(a, b, c, TABLE): bit i of the result is TABLE's bit (a_i << 2 | b_i << 1 | c_i), i.e. TABLE is the expression
+// evaluated on a = 0xf0, b = 0xcc, c = 0xaa.  With (a, b, c) = (ddn, x, K): 0xcc ^ (0xf0 & 0xaa) = 0xcc ^ 0xa0 = 0x6c and
+// 0xcc ^ (~0xf0 & 0xaa) = 0xcc ^ 0x0a = 0xc6.  The same bit function as the plain expression, which the compiler turns into a v_xor
+// with K followed by a 0x6c bitop3 inside the loops (and canonicalises `~f2u(ddn) & K` back to); the builtin is kept as written, and
+// ddn goes in unmasked -- as does a sign word that is masked already (PairPre).  -DCAP_MARK_V1 and host code keep the plain expressions.
+// Macros, not functions: inside a function of its own the optimiser rewrites the plain x ^ (s ^ K) as a negation of x ^ s before it
+// is inlined, and the -DCAP_MARK_V1 build would no longer be the parent's code.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(CAP_MARK_V1)
+#define CAP_SIGN_WORD(ddn) f2u(ddn)
+#define CAP_FLIP_SAME(s, x) u2f(__builtin_amdgcn_bitop3_b32((s), f2u(x), 0x80000000u, 0x6c))
+#define CAP_FLIP_OPP(s, x) u2f(__builtin_amdgcn_bitop3_b32((s), f2u(x), 0x80000000u, 0xc6))
+#else
+#define CAP_SIGN_WORD(ddn) (f2u(ddn) & 0x80000000u)
+#define CAP_FLIP_SAME(s, x) u2f(f2u(x) ^ (s))
+#define CAP_FLIP_OPP(s, x) u2f(f2u(x) ^ ((s) ^ 0x80000000u))
+#endif
+
 // The determinant-scaled quantities of tri_test() for one triangle record, sign-flipped so that det >= 0.  Same values bit for
 // bit: det = -(d.n) and V = -(e1.q) are exact negations, so their sign bits are folded into the flip masks instead of being
 // applied first (three bit operations instead of five).
@@ -48,13 +68,13 @@ __device__ __forceinline__ TriScaled tri_scaled(const Ray& r, const float4 t0, c
     const v3 v0 = mk3(t0.x, t0.y, t0.z), e1 = mk3(t0.w, t1.x, t1.y), e2 = mk3(t1.z, t1.w, t2.x), n = mk3(t2.y, t2.z, t2.w);
     const v3 tvec = r.o - v0;
     const v3 q    = cross3(tvec, r.d);
-    const float    ddn = dot3(r.d, n);                 // det = -ddn
-    const uint32_t s   = f2u(ddn) & 0x80000000u;       // sign of ddn = NOT sign of det
-    TriScaled o;
+    const float    ddn = dot3(r.d, n);  // det = -ddn
+    const uint32_t s   = CAP_SIGN_WORD(ddn);  // sign of ddn = NOT sign of det
+    TriScaled      o;
     o.det = fabsf(ddn);
-    o.U   = u2f(f2u(dot3(e2, q)) ^ (s ^ 0x80000000u));  // U ^ sign(det)
-    o.V   = u2f(f2u(dot3(e1, q)) ^ s);                  // (-e1.q) ^ sign(det)
-    o.T   = u2f(f2u(dot3(tvec, n)) ^ (s ^ 0x80000000u));
+    o.U   = CAP_FLIP_OPP(s, dot3(e2, q));   // U ^ sign(det)
+    o.V   = CAP_FLIP_SAME(s, dot3(e1, q));  // (-e1.q) ^ sign(det)
+    o.T   = CAP_FLIP_OPP(s, dot3(tvec, n));
     return o;
 }
 
@@ -99,19 +119,19 @@ __device__ __forceinline__ PairScaled pair_scaled(const Ray& r, const float4* ba
     PairScaled  o;
     {
         const float    ddn = dot3(r.d, na);
-        const uint32_t s   = f2u(ddn) & 0x80000000u;
+        const uint32_t s   = CAP_SIGN_WORD(ddn);
         o.a.det = fabsf(ddn);
-        o.a.U   = u2f(f2u(e2q) ^ (s ^ 0x80000000u));
-        o.a.V   = u2f(f2u(dot3(e1, q)) ^ s);
-        o.a.T   = u2f(f2u(tna) ^ (s ^ 0x80000000u));
+        o.a.U   = CAP_FLIP_OPP(s, e2q);
+        o.a.V   = CAP_FLIP_SAME(s, dot3(e1, q));
+        o.a.T   = CAP_FLIP_OPP(s, tna);
     }
     {
         const float    ddn = dot3(r.d, nb);
-        const uint32_t s   = f2u(ddn) & 0x80000000u;
+        const uint32_t s   = CAP_SIGN_WORD(ddn);
         o.b.det = fabsf(ddn);
-        o.b.U   = u2f(f2u(dot3(e3, q)) ^ (s ^ 0x80000000u));
-        o.b.V   = u2f(f2u(e2q) ^ s);
-        o.b.T   = u2f(f2u(tnb) ^ (s ^ 0x80000000u));
+        o.b.U   = CAP_FLIP_OPP(s, dot3(e3, q));
+        o.b.V   = CAP_FLIP_SAME(s, e2q);
+        o.b.T   = CAP_FLIP_OPP(s, tnb);
     }
     o.id = f2u(p.f[18]);
     return o;
@@ -279,10 +299,10 @@ struct PairInside
 __device__ __forceinline__ bool tri_inside(float ddn, float e2q_u, float e1q_v)
 {
     // tri_scaled()'s det, U and V (V = -(e1.q): its negation is folded into the flip mask there and here)
-    const uint32_t s   = f2u(ddn) & 0x80000000u;
+    const uint32_t s   = CAP_SIGN_WORD(ddn);
     const float    det = fabsf(ddn);
-    const float    U   = u2f(f2u(e2q_u) ^ (s ^ 0x80000000u));
-    const float    V   = u2f(f2u(e1q_v) ^ s);
+    const float    U   = CAP_FLIP_OPP(s, e2q_u);
+    const float    V   = CAP_FLIP_SAME(s, e1q_v);
     return (U >= 0.0f) & (V >= 0.0f) & (U + V <= det);
 }
 __device__ __forceinline__ PairInside pair_inside(const Ray& r, const float4* base, uint32_t k)
@@ -305,6 +325,52 @@ __device__ __forceinline__ PairInside pair_inside(const Ray& r, const float4* ba
     o.id = f2u(p.f[18]);
     return o;
 }
+// Phase 1 of a DENSE scene (BvhDev::tri_ids_dense: fan pairs only and pair j holds triangles 2j and 2j + 1, so a triangle's id is its
+// position in the list -- every scene made of quads, the Cornell box among them).  No bit word is built from the id: the list is
+// walked from its last triangle to its first and every triangle shifts its inside bit in from the right,
+//     m = 2 m + inside      one v_addc_co_u32 m, -, m, m, <lane mask>: the carry-in IS the compares' lane mask,
+// so after tri_count steps triangle i sits in bit i, the mask the id-indexed form builds (the bits above tri_count are the zeros m started
+// with).  The lane mask is the AND of the three compares' own ballots (scalar; a ballot of the computed bool would cost a select and a
+// compare per triangle again, experiment (87)) and is the instruction's one scalar operand.  Against the id-indexed form: per pair two
+// vector instructions instead of five (2 v_mov of a bit word, 2 v_cndmask, v_or3) and none of the three scalar ones that made the bit words.
+// Two words (33-64 triangles): the low word's carry-out is the high word's carry-in.  Both steps of a pair are one asm statement: the
+// compiler pads after every statement whose outputs the next instruction reads.  -DCAP_MARK_V1 compiles the id-indexed form alone.
+#if defined(CAP_MARK_V1)
+constexpr bool kMarkCarry = false;
+#else
+constexpr bool kMarkCarry = true;
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(CAP_MARK_V1)
+__device__ __forceinline__ unsigned long long tri_inside_lanes(float ddn, float e2q_u, float e1q_v)
+{
+    const uint32_t s   = CAP_SIGN_WORD(ddn);
+    const float    det = fabsf(ddn);
+    const float    U   = CAP_FLIP_OPP(s, e2q_u);
+    const float    V   = CAP_FLIP_SAME(s, e1q_v);
+    return __builtin_amdgcn_ballot_w64(U >= 0.0f) & __builtin_amdgcn_ballot_w64(V >= 0.0f) & __builtin_amdgcn_ballot_w64(U + V <= det);
+}
+// the pair at rec (scalar loads, as pair_inside): its second triangle shifted in, then its first
+template <bool WIDE>
+__device__ __forceinline__ void pair_shift_in(const Ray& r, const __attribute__((address_space(4))) RawPair* rec, uint32_t& m0, uint32_t& m1)
+{
+    const RawPair p = *rec;
+    const v3 v0 = mk3(p.f[0], p.f[1], p.f[2]), e1 = mk3(p.f[3], p.f[4], p.f[5]), e2 = mk3(p.f[6], p.f[7], p.f[8]),
+             e3 = mk3(p.f[9], p.f[10], p.f[11]), na = mk3(p.f[12], p.f[13], p.f[14]), nb = mk3(p.f[15], p.f[16], p.f[17]);
+    const v3    tvec = r.o - v0;
+    const v3    q    = cross3(tvec, r.d);
+    const float e2q  = dot3(e2, q);
+    const unsigned long long ia = tri_inside_lanes(dot3(r.d, na), e2q, dot3(e1, q));
+    const unsigned long long ib = tri_inside_lanes(dot3(r.d, nb), dot3(e3, q), e2q);
+    unsigned long long       c;  // carry out: between the two words, otherwise unused (always 0 in the high word: <= 64 steps)
+    if (WIDE)
+        asm("v_addc_co_u32_e64 %0, %2, %0, %0, %3\n\tv_addc_co_u32_e64 %1, %2, %1, %1, %2\n\t"
+            "v_addc_co_u32_e64 %0, %2, %0, %0, %4\n\tv_addc_co_u32_e64 %1, %2, %1, %1, %2"
+            : "+v"(m0), "+v"(m1), "=&s"(c)
+            : "s"(ib), "s"(ia));
+    else
+        asm("v_addc_co_u32_e64 %0, %1, %0, %0, %2\n\tv_addc_co_u32_e64 %0, %1, %0, %0, %3" : "+v"(m0), "=&s"(c) : "s"(ib), "s"(ia));
+}
+#endif
 template <bool WIDE>
 __device__ __forceinline__ void exhaustive_closest_marked(const BvhDev& bvh, const float4* rec_tab, const Ray& r, bool has_ray, float& best_t,
                                                           float& best_u, float& best_v, uint32_t& best_gid)
@@ -323,22 +389,39 @@ __device__ __forceinline__ void exhaustive_closest_marked(const BvhDev& bvh, con
             m0 |= inside ? 1u << id : 0u;
     };
     const uint32_t np = bvh.fan_pair_count;
-#pragma unroll 2
-    for (uint32_t k = 0; k < np; ++k)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(CAP_MARK_V1)
+    if (bvh.tri_ids_dense)  // wave-uniform, the same for the whole launch
     {
-        const PairInside p = pair_inside(r, bvh.fan_pairs, k);
-        mark(p.a, p.id);
-        mark(p.b, p.id + 1u);
+        // last pair first, two per iteration (written out: the asm statement defeats #pragma unroll); an odd count's last pair goes first
+        const __attribute__((address_space(4))) RawPair* rec = (const __attribute__((address_space(4))) RawPair*)bvh.fan_pairs + np;
+        if (np & 1u) pair_shift_in<WIDE>(r, --rec, m0, m1);
+        for (uint32_t k = np >> 1; k != 0u; --k)
+        {
+            pair_shift_in<WIDE>(r, rec - 1, m0, m1);
+            pair_shift_in<WIDE>(r, rec - 2, m0, m1);
+            rec -= 2;
+        }
     }
-    const uint32_t ns = bvh.fan_single_count;
-#pragma unroll 2
-    for (uint32_t j = 0; j < ns; ++j)
+    else
+#endif
     {
-        float4 t0, t1, t2, t3;
-        load_const_tri(bvh.fan_singles, j, t0, t1, t2, t3);
-        const v3 v0 = mk3(t0.x, t0.y, t0.z), e1 = mk3(t0.w, t1.x, t1.y), e2 = mk3(t1.z, t1.w, t2.x), n = mk3(t2.y, t2.z, t2.w);
-        const v3 q  = cross3(r.o - v0, r.d);
-        mark(tri_inside(dot3(r.d, n), dot3(e2, q), dot3(e1, q)), f2u(t3.x));
+#pragma unroll 2
+        for (uint32_t k = 0; k < np; ++k)
+        {
+            const PairInside p = pair_inside(r, bvh.fan_pairs, k);
+            mark(p.a, p.id);
+            mark(p.b, p.id + 1u);
+        }
+        const uint32_t ns = bvh.fan_single_count;
+#pragma unroll 2
+        for (uint32_t j = 0; j < ns; ++j)
+        {
+            float4 t0, t1, t2, t3;
+            load_const_tri(bvh.fan_singles, j, t0, t1, t2, t3);
+            const v3 v0 = mk3(t0.x, t0.y, t0.z), e1 = mk3(t0.w, t1.x, t1.y), e2 = mk3(t1.z, t1.w, t2.x), n = mk3(t2.y, t2.z, t2.w);
+            const v3 q  = cross3(r.o - v0, r.d);
+            mark(tri_inside(dot3(r.d, n), dot3(e2, q), dot3(e1, q)), f2u(t3.x));
+        }
     }
     if (!has_ray) m0 = 0u, m1 = 0u;
     // ---- phase 2: the marked triangles of this lane, ascending id ----
@@ -354,8 +437,8 @@ __device__ __forceinline__ void exhaustive_closest_marked(const BvhDev& bvh, con
         const v3       v0 = mk3(t0.x, t0.y, t0.z), n = mk3(t2.y, t2.z, t2.w);
         const v3       tvec = r.o - v0;
         const float    ddn  = dot3(r.d, n);
-        const uint32_t s    = f2u(ddn) & 0x80000000u;
-        const float    T    = u2f(f2u(dot3(tvec, n)) ^ (s ^ 0x80000000u));
+        const uint32_t s    = CAP_SIGN_WORD(ddn);
+        const float    T    = CAP_FLIP_OPP(s, dot3(tvec, n));
         const float    tt   = T * rcp_c(fabsf(ddn));
         const bool     better = (tt > r.tmin) & (tt < best_t);
         best_t   = better ? tt : best_t;
@@ -404,12 +487,12 @@ __device__ __forceinline__ bool pair_occludes_pre(const Ray& r, const float4* ba
     bool        hit;
     {
         const uint32_t s = f2u(pa.x);
-        const float    U = u2f(f2u(e2q) ^ (s ^ 0x80000000u)), V = u2f(f2u(dot3(e1, q)) ^ s), T = u2f(f2u(dot3(tvec, na)) ^ (s ^ 0x80000000u));
+        const float    U = CAP_FLIP_OPP(s, e2q), V = CAP_FLIP_SAME(s, dot3(e1, q)), T = CAP_FLIP_OPP(s, dot3(tvec, na));
         hit = (U >= 0.0f) & (V >= 0.0f) & (U + V <= pa.y) & (T > pa.z) & (T < pa.w);
     }
     {
         const uint32_t s = f2u(pb.x);
-        const float    U = u2f(f2u(dot3(e3, q)) ^ (s ^ 0x80000000u)), V = u2f(f2u(e2q) ^ s), T = u2f(f2u(dot3(tvec, nb)) ^ (s ^ 0x80000000u));
+        const float    U = CAP_FLIP_OPP(s, dot3(e3, q)), V = CAP_FLIP_SAME(s, e2q), T = CAP_FLIP_OPP(s, dot3(tvec, nb));
         hit |= (U >= 0.0f) & (V >= 0.0f) & (U + V <= pb.y) & (T > pb.z) & (T < pb.w);
     }
     return hit;

@@ -286,7 +286,8 @@ void launch_shade(const LaunchCfg& cfg, const ShadeArgs& args, bool ext, bool fe
 // configuration does not take the packet walk -- then launch_trace_primary + launch_shade do the same in two kernels
 bool launch_primary_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, float4* hits, bool ext);
 // small-scene path: exhaustive closest hit fused with the shading of the vertex found (bounce 0 generates the camera rays)
-void launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback = false);
+// returns how the launched kernel builds the closest-hit candidate mask (CAP_DEBUG_MARK_FORM's form)
+uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback = false);
 // whether the reference model's bounce 0 of this scene has the form ShadeArgs::code_in_color asks for (the kernel of tame records in LDS)
 bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene);
 

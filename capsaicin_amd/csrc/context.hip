@@ -219,6 +219,8 @@ struct CapContext
     uint32_t      lane1_failed_bounces = 0, lane1_retry_tick = 0;
     uint32_t      lanes_last_render = 0;       // cap_debug_get(CAP_DEBUG_LANES_USED)
     uint32_t      last_class_capacity = 0;     // sub-queue capacity of the last cap_render batch (CAP_DEBUG_QUEUE_CANARY_*)
+    uint32_t      tri_ids_dense = 0;           // pair_ids_dense() of the uploaded fan records (BvhDev::tri_ids_dense)
+    uint32_t      last_mark_form = 0;          // launch_trace_shade()'s answer for bounce >= 1 of the last cap_render (CAP_DEBUG_MARK_FORM)
     uint32_t      last_cull_camera_pairs = 0;  // ShadeArgs::cull_camera_pairs of the last cap_render batch (CAP_DEBUG_CAMERA_CULL)
     uint32_t      traversal_mode  = CAP_TRAVERSAL_AUTO;
     uint32_t      bvh_build_mode  = CAP_BVH_BUILD_AUTO;
@@ -451,6 +453,7 @@ BvhDev bvh_dev(const CapContext* c, const CapContext::Lane& lane)
     b.wide8_top = c->wide8_top;
     b.fan_pairs = c->fan_pairs.p, b.fan_singles = c->fan_singles.p;
     b.fan_pair_count = c->fan_pair_count, b.fan_single_count = c->fan_single_count;
+    b.tri_ids_dense = c->tri_ids_dense;
     b.fan_pairs_nee = c->fan_pairs_nee.p ? c->fan_pairs_nee.p : c->fan_pairs.p;
     b.fan_pair_nee_count = c->fan_pairs_nee.p ? c->fan_pair_nee_count : c->fan_pair_count;
     b.tri_count = c->tri_count;
@@ -994,10 +997,29 @@ static double wide_pad(const CapBvhInfo& bi)
 // Exhaustive path (cap_set_traversal): triangles that come in fans (k, k + 1 share v0 and the edge v0->v2, as every
 // triangulated quad of an OBJ face does) are stored as one record, so the kernels compute tvec, q and the shared edge's dot
 // product once for both.  Same per-triangle arithmetic, same results; the pairing only depends on bit-equal vertices.
+// BvhDev::tri_ids_dense: a triangle's id is its position in the pair list.  (No triangles: nothing to walk, not dense.)
+static bool pair_ids_dense(const float* pairs, uint32_t pair_count, uint32_t single_count, uint32_t tri_count)
+{
+    if (!tri_count || single_count || tri_count != 2u * (uint64_t)pair_count) return false;
+    for (uint32_t j = 0; j < pair_count; ++j)
+    {
+        uint32_t id;
+        memcpy(&id, pairs + 20 * (size_t)j + 18, sizeof(id));
+        if (id != 2u * j) return false;
+    }
+    return true;
+}
+int cap_debug_pair_ids_dense(const float* pair_records, uint32_t pair_count, uint32_t single_count, uint32_t tri_count)
+{
+    if (!pair_records && pair_count) return 0;
+    return pair_ids_dense(pair_records, pair_count, single_count, tri_count) ? 1 : 0;
+}
+
 static int upload_fan_records(CapContext* c)
 {
     const uint32_t n = c->tri_count;
     c->fan_pair_count = c->fan_single_count = 0;
+    c->tri_ids_dense = 0;
     if (n && n <= 4096)
     {
         std::vector<float> raw(16 * (size_t)n);
@@ -1025,6 +1047,7 @@ static int upload_fan_records(CapContext* c)
         }
         c->fan_pair_count   = (uint32_t)(pairs.size() / 20);
         c->fan_single_count = (uint32_t)(singles.size() / 16);
+        c->tri_ids_dense    = pair_ids_dense(pairs.data(), c->fan_pair_count, c->fan_single_count, n) ? 1u : 0u;
         // padded by four records so that an unrolled scalar load past the end stays inside the allocation
         pairs.resize(pairs.size() + 80, 0.0f), singles.resize(singles.size() + 64, 0.0f);
         c->fan_pairs_host   = pairs;
@@ -1812,6 +1835,10 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
         *value = c->shade_tame ? 1u : 0u;
         return CAP_OK;
     case CAP_DEBUG_CAMERA_CULL: *value = c->last_cull_camera_pairs; return CAP_OK;
+    case CAP_DEBUG_MARK_FORM:
+        if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_debug_get: BVH not built");
+        *value = ((uint64_t)c->last_mark_form << 8) | c->tri_ids_dense;
+        return CAP_OK;
     case CAP_DEBUG_NEE_PAIRS:
         if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_debug_get: BVH not built");
         *value = ((uint64_t)(c->fan_pairs_nee.p ? c->fan_pair_nee_count : c->fan_pair_count) << 32) | c->fan_pair_count;
@@ -1894,6 +1921,7 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
     if (num_bounces > 255) return fail(CAP_ERR_INVALID_ARG, "cap_render: num_bounces %u exceeds 255", num_bounces);
     if (!n_frames) return CAP_OK;
     HIP_TRY(hipSetDevice(c->device));
+    c->last_mark_form   = 0;
     const bool feedback = (flags & CAP_RENDER_GBUFFER_FEEDBACK) != 0;
     if (feedback)
     {
@@ -2149,8 +2177,8 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
             if (fused)
             {
                 StageTimer t(c, b == 0 ? ST_PRIMARY : ST_CLOSEST, st);
-                launch_trace_shade(cfg, bvh, sa, ext, feedback);
-                if (b) ++c->stats.launches_trace_closest;
+                const uint32_t form = launch_trace_shade(cfg, bvh, sa, ext, feedback);
+                if (b) ++c->stats.launches_trace_closest, c->last_mark_form = form;
                 if (trace_launch(c, "trace_shade bounce %u batch %u", b, batch)) return fail(CAP_ERR_HIP, "trace_shade failed");
             }
             else

@@ -492,7 +492,7 @@ static bool tame_kernels(const BvhDev& bvh, const SceneDev& scene)
 }
 bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene) { return tame_kernels(bvh, scene); }
 
-void launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback)
+uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback)
 {
     const bool first = args.bounce == 0;
     const bool fb    = feedback && !ext && !first;  // (bounce 0 defines the planes' entries: nothing to reuse yet)
@@ -507,5 +507,12 @@ void launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs
     while (k->is != is && k + 1 < kTraceShadeKernels + 13) ++k;
     assert(k->is == is);  // the table holds every tuple the lines above can derive
     hipLaunchKernelGGL(k->kernel, dim3(gx), dim3(kBlock), 0, cfg.stream, bvh, args);
+    // the kernel's own conditions: the marked loop where it calls exhaustive_closest_marked, the carry chain where that takes it
+#if defined(CAP_CLOSEST_V1)
+    return 0u;
+#else
+    if (!lds || first) return 0u;
+    return (kMarkCarry && bvh.tri_ids_dense) ? (bvh.tri_count > 32u ? 3u : 2u) : 1u;
+#endif
 }
 }  // namespace cap

@@ -296,6 +296,12 @@ enum
      * bounds miss them, 0 if every tile tested every pair: the switch CAP_NO_CAMERA_CULL, or a camera basis whose deviation from an
      * orthonormal one could move a projected vertex by more than an eighth of the bounds' two-pixel pad (context.hip cap_render). */
     CAP_DEBUG_CAMERA_CULL          = 14,
+    /* MARK_FORM (get, after cap_bvh_build): form << 8 | dense.  dense: 1 if the scene's small-scene records are fan pairs only with pair j
+     * holding triangles 2j and 2j + 1 (cap_debug_pair_ids_dense), so that a triangle's id is its position in the list.  form: how the
+     * last cap_render's fused small-scene launches of bounce >= 1 built the closest-hit candidate mask -- 0: no such launch, or a kernel
+     * without the two-phase loop; 1: by triangle id (one bit word per triangle); 2: by position, one carry-chain step per triangle (dense
+     * scenes); 3: the same over two words (33-64 triangles). */
+    CAP_DEBUG_MARK_FORM            = 15,
     /* A/B and diagnostic switches of the build and render paths (which kernels trace the camera and the shadow rays, one or two batch
      * lanes, the builders' parameters ...): ONE table per context, key = SWITCH_BASE + cap_debug_switch_index("CAP_..."), the names being
      * the environment variables that fill the table once, at cap_ctx_create (tools set those around a whole process; nothing else in the
@@ -308,6 +314,10 @@ int cap_debug_set(CapContext* ctx, uint32_t key, uint64_t value);
 int cap_debug_get(CapContext* ctx, uint32_t key, uint64_t* value);
 /* Index of a switch by its name ("CAP_NO_WIDE8", "CAP_PRIMARY_WIDE", ...; capsaicin_amd/csrc/cap_kernels.h CapSwitch), -1 if unknown. */
 int cap_debug_switch_index(const char* name);
+/* The rule behind CAP_DEBUG_MARK_FORM's dense bit, on a host copy of the small-scene record lists: pair_count fan pair records of 20 floats
+ * (float 18 = the first triangle's id as bits), single_count unpaired triangles, tri_count triangles in all.  1 if tri_count > 0, there is
+ * no unpaired triangle, tri_count == 2 * pair_count and pair j's id is 2j for every j; else 0.  Needs no device. */
+int cap_debug_pair_ids_dense(const float* pair_records, uint32_t pair_count, uint32_t single_count, uint32_t tri_count);
 /* Traversal strategy of the trace kernels (same hits either way): AUTO picks EXHAUSTIVE for scenes of at most 64
  * triangles (wave-uniform test of every triangle, no stack) and STACK (LBVH + per-lane LDS stack) otherwise. */
 typedef enum CapTraversal
