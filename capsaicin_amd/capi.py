@@ -237,6 +237,7 @@ SYMBOLS = {
     "cap_instances_readback": (_i, [_vp, _vp, _vp]),
     "cap_trace_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_trace_instances_occlusion": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
+    "cap_trace_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
     "cap_post_settings_default": (None, [C.POINTER(PostSettings)]),
     "cap_post_frame": (_i, [_vp, C.POINTER(PostSettings), _u32, C.POINTER(CameraData)]),
@@ -884,6 +885,65 @@ class Renderer:
                 h = host_page
             return (h, cnt.cpu().numpy()) if counts else h
         return (hits, cnt) if counts else hits
+
+    def trace_instances_multi(self, rays, k, counts=False, resume=None, sync=True, cull=None, mask=None):
+        """The first k (instance, triangle) pairs of each ray over the instance table, in (t, instance, triangle) order
+        (cap_trace_instances_multi): (hits (N, k, 4) float32 records as trace_instances writes them, instances (N, k) int32, -1 in the
+        miss slots after a ray's last pair[, counts (N,) int32 = the number of ALL pairs per ray with counts=True]).  k = 0: counts
+        only, hits is (N, 0, 4) and instances (N, 0).  resume=(hits, instances) of the previous call with the same rays continues
+        after it with CAP_MULTI_CONTINUE and writes the next pages over both.  rays, sync, cull= and mask= as trace_rays_multi; numpy
+        rays (or numpy resume pages) give numpy results."""
+        import torch
+        options = self.trace_options(cull, mask)
+        dev = torch.device("cuda", self.device)
+        if resume is not None and (not isinstance(resume, (tuple, list)) or len(resume) != 2):
+            raise CapError("resume must be the (hits, instances) pair of the previous call")
+        host = isinstance(rays, np.ndarray) or (resume is not None and any(isinstance(p, np.ndarray) for p in resume))
+        if isinstance(rays, np.ndarray):
+            rays = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).to(dev)
+        if host:
+            sync = True  # the result is read back to the host
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.device != dev:
+            raise CapError("rays must be a contiguous (N, 8) float32 tensor on %s, got %s %s on %s" % (dev, rays.dtype, tuple(rays.shape), rays.device))
+        n, k = rays.shape[0], int(k)
+        if not 0 <= k <= self.MULTI_MAX_K:
+            raise CapError("k must be in 0 .. %d (page with resume=), got %d" % (self.MULTI_MAX_K, k))
+        if k == 0 and (not counts or resume is not None):
+            raise CapError("k = 0 counts only: pass counts=True and no resume pages")
+        host_pages = [None, None]
+        if resume is None:
+            hits = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
+            inst = torch.empty((n, k), dtype=torch.int32, device=dev)
+        else:
+            pages = []
+            for j, (page, shape, dtype, np_dtype) in enumerate(((resume[0], (n, k, 4), torch.float32, np.float32),
+                                                                 (resume[1], (n, k), torch.int32, np.int32))):
+                if isinstance(page, np.ndarray):
+                    if page.size != int(np.prod(shape)):
+                        raise CapError("resume[%d] must hold the %s page of the previous call, got %s" % (j, shape, page.shape))
+                    host_pages[j] = page
+                    page = torch.from_numpy(np.ascontiguousarray(page, np_dtype).reshape(shape)).to(dev)
+                elif page.dtype != dtype or tuple(page.shape) != shape or not page.is_contiguous() or page.device != dev:
+                    raise CapError("resume[%d] must be the contiguous %s %s page of the previous call" % (j, shape, dtype))
+                pages.append(page)
+            hits, inst = pages
+        cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the rays (and the outputs' allocations) were made on torch's stream
+        _check(lib().cap_trace_instances_multi(self.ctx, C.c_void_p(rays.data_ptr()), n, k, C.c_void_p(hits.data_ptr()) if k else None,
+                                               C.c_void_p(inst.data_ptr()) if k else None, C.c_void_p(cnt.data_ptr()) if counts else None,
+                                               self.MULTI_CONTINUE if resume is not None else 0, C.byref(options) if options is not None else None),
+               "cap_trace_instances_multi")
+        if sync:
+            self.sync()
+        if host:
+            out = [hits.cpu().numpy(), inst.cpu().numpy()]
+            for j in range(2):
+                if host_pages[j] is not None:
+                    host_pages[j][...] = out[j].reshape(host_pages[j].shape)
+                    out[j] = host_pages[j]
+            return (out[0], out[1], cnt.cpu().numpy()) if counts else (out[0], out[1])
+        return (hits, inst, cnt) if counts else (hits, inst)
 
     def triangle_to_instance_primitive(self, ids):
         """Global triangle ids (hit_triangles) -> (instance, primitive) = (mesh index, triangle index within the mesh), the pair

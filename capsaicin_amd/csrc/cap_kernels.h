@@ -215,6 +215,11 @@ struct TlasDev
 // max_depth of the trees in them.
 void launch_query_instances(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const TlasDev& tl, const RayFilter& f, int mode, uint32_t* inst_out,
                             uint32_t depth);
+// Multi-hit over the instances (cap_trace_instances_multi, instance.hip k_query_inst_multi): m as launch_query_binary_multi's, pages of
+// m.k records per ray in m.q.out and of m.k instance indices in inst_out (both NULL when m.k = 0); with m.resume slot k - 1 of both
+// is the cursor (t, instance, triangle).  bvh.tris_by_id must be the scene's records whichever pools bvh.nodes / bvh.tris are.
+void launch_query_instances_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, const TlasDev& tl, const RayFilter& f, uint32_t* inst_out,
+                                  uint32_t depth);
 // An object's tree as a builder left it at its place in the forest (cap_objects_set): nodes = the object's n_tris - 1 nodes, tris its
 // n_tris leaf-order records, both numbered from 0 with triangle ids local to the object.  Adds node_base to inner child references,
 // rec_base to leaf references and first_triangle to the records' id words, in place.

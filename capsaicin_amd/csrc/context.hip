@@ -2886,6 +2886,62 @@ int cap_trace_instances_occlusion(CapContext* c, const CapRayDesc* device_rays, 
     return trace_instances(c, "cap_trace_instances_occlusion", device_rays, n, device_occluded, sizeof(uint32_t), nullptr, true, options);
 }
 
+// cap_trace_instances_multi: the first k pairs of each ray in (t, instance, triangle) order and / or the number of its pairs
+// (instance.hip k_query_inst_multi).  trace_multi's validation with the instance page as a fourth range, trace_instances' state and
+// pools.
+int cap_trace_instances_multi(CapContext* c, const CapRayDesc* rays, uint64_t n, uint32_t k, CapHit* hits, uint32_t* inst, uint32_t* counts,
+                              uint32_t flags, const CapTraceOptions* options)
+{
+    const char* what = "cap_trace_instances_multi";
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (flags & ~(uint32_t)CAP_MULTI_CONTINUE) return fail(CAP_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    QueryFilter flt;
+    if (const int rc = query_filter(c, what, options, true, flt)) return rc;
+    if (k > CAP_MULTI_MAX_K) return fail(CAP_ERR_INVALID_ARG, "%s: k = %u exceeds CAP_MULTI_MAX_K (%d); page with CAP_MULTI_CONTINUE", what, k, CAP_MULTI_MAX_K);
+    if (k == 0 && (hits || inst || !counts))
+        return fail(CAP_ERR_INVALID_ARG, "%s: k = 0 counts only: hits and instances must be NULL and counts given", what);
+    if (k == 0 && (flags & CAP_MULTI_CONTINUE)) return fail(CAP_ERR_INVALID_ARG, "%s: CAP_MULTI_CONTINUE needs k >= 1 (the cursor is slot k - 1)", what);
+    if (const int rc = query_state(c, what)) return rc;
+    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
+    if (n == 0) return CAP_OK;
+    if (!rays || (k && (!hits || !inst))) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer (k = %u needs hits and instances)", what, k);
+    const uintptr_t r0 = (uintptr_t)rays, h0 = (uintptr_t)hits, i0 = (uintptr_t)inst, c0 = (uintptr_t)counts;
+    if (((r0 | h0) & 15u) || ((i0 | c0) & 3u))
+        return fail(CAP_ERR_INVALID_ARG, "%s: rays and hits must be 16-byte aligned, instances and counts 4-byte", what);
+    const uint64_t page = (uint64_t)k * sizeof(CapHit), ipage = (uint64_t)k * sizeof(uint32_t);
+    if (n > (UINTPTR_MAX - r0) / sizeof(CapRayDesc) || (k && (n > (UINTPTR_MAX - h0) / page || n > (UINTPTR_MAX - i0) / ipage)) ||
+        (counts && n > (UINTPTR_MAX - c0) / sizeof(uint32_t)))
+        return fail(CAP_ERR_INVALID_ARG, "%s: %llu rays x %u records exceed the address space", what, (unsigned long long)n, k);
+    const uintptr_t base[4]  = {r0, h0, i0, c0};
+    const uint64_t  bytes[4] = {n * sizeof(CapRayDesc), k ? n * page : 0, k ? n * ipage : 0, counts ? n * sizeof(uint32_t) : 0};
+    for (int x = 0; x < 4; ++x)
+        for (int y = x + 1; y < 4; ++y)
+            if (ranges_overlap(base[x], bytes[x], base[y], bytes[y]))
+                return fail(CAP_ERR_INVALID_ARG, "%s: the ray, hit, instance and count ranges overlap", what);
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run)) return rc;
+    const TlasDev tl{c->inst_rec.p, c->inst_tlas.p, c->inst_level_off.p, c->inst_top};
+    // the pools as trace_instances substitutes them; run.bvh.tris_by_id stays the scene's (the write-out reads it)
+    uint32_t depth = c->bvh_info.max_depth;
+    if (c->obj_count)
+    {
+        run.bvh.nodes = c->forest_nodes.p, run.bvh.tris = c->forest_tris.p;
+        depth = c->obj_max_depth, run.cfg.stack_entries = depth <= 32 ? 32 : 64;
+    }
+    for (uint64_t done = 0; done < n; done += run.per)
+    {
+        MultiArgs m{};
+        m.q      = query_args(run, rays, n, done);
+        m.q.out  = hits ? static_cast<void*>(hits + done * k) : nullptr;
+        m.k      = k;
+        m.counts = counts ? counts + done : nullptr;
+        m.resume = (flags & CAP_MULTI_CONTINUE) ? 1u : 0u;
+        launch_query_instances_multi(run.cfg, run.bvh, m, tl, flt.f, inst ? inst + done * k : nullptr, depth);
+        if (run.traced("k_query_inst_multi", done) != CAP_OK) return CAP_ERR_HIP;
+    }
+    return CAP_OK;
+}
+
 void cap_post_settings_default(CapPostSettings* out)
 {
     if (!out) return;

@@ -1,4 +1,4 @@
-// instance.hip — instanced ray queries (cap_instances_set, cap_trace_instances, cap_trace_instances_occlusion), gfx950.
+// instance.hip — instanced ray queries (cap_instances_set, cap_trace_instances, cap_trace_instances_occlusion, cap_trace_instances_multi), gfx950.
 //
 // Bottom-level structures -- the uploaded scene and its binary tree, or the objects of cap_objects_set (mesh ranges of the scene, one
 // binary tree each in a forest laid out as the scene's tree), read as object space -- and a table of N instances, each with an
@@ -405,6 +405,246 @@ __global__ __launch_bounds__(kBlock, inst_blocks(STACK)) void k_query_inst(BvhDe
     }
 }
 
+// ---- multi-hit over the instances (cap_trace_instances_multi) ----
+// A ray's first k pairs in (t, instance, triangle) order, the number of its pairs, or both: query.hip's HitList with the instance
+// between t and the triangle.  K (t, inst, gid) triples in VGPRs, K a compile-time bucket >= k, every index a compile-time constant;
+// the first K - k slots hold (-inf, 0, 0) placeholders no hit passes (t > tmin >= -inf), the last k start as the miss (tmax, ~0, ~0).
+// A pair below slot K - 1 replaces it and bubbles towards the front by K - 1 compare-swaps.
+template <int K>
+struct InstHitList
+{
+    float    t[K];
+    uint32_t i[K], g[K];
+    static __device__ __forceinline__ bool before(float ta, uint32_t ia, uint32_t ga, float tb, uint32_t ib, uint32_t gb)
+    {
+        return ta < tb || (ta == tb && (ia < ib || (ia == ib && ga < gb)));
+    }
+    __device__ __forceinline__ void init(uint32_t k, float tmax)
+    {
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+        {
+            const bool live = j >= K - (int)k;
+            t[j] = live ? tmax : -__builtin_inff(), i[j] = live ? kInvalidId : 0u, g[j] = live ? kInvalidId : 0u;
+        }
+    }
+    __device__ __forceinline__ bool admits(float tt, uint32_t ii, uint32_t gg) const { return before(tt, ii, gg, t[K - 1], i[K - 1], g[K - 1]); }
+    __device__ __forceinline__ void insert(float tt, uint32_t ii, uint32_t gg)
+    {
+        t[K - 1] = tt, i[K - 1] = ii, g[K - 1] = gg;
+#pragma unroll
+        for (int j = K - 1; j > 0; --j)
+        {
+            const bool     sw = before(t[j], i[j], g[j], t[j - 1], i[j - 1], g[j - 1]);
+            const float    ta = t[j - 1], tb = t[j];
+            const uint32_t ia = i[j - 1], ib = i[j], ga = g[j - 1], gb = g[j];
+            t[j - 1] = sw ? tb : ta, t[j] = sw ? ta : tb;
+            i[j - 1] = sw ? ib : ia, i[j] = sw ? ia : ib;
+            g[j - 1] = sw ? gb : ga, g[j] = sw ? ga : gb;
+        }
+    }
+};
+
+// The object-space ray of the contract in instance `inst`: the twelve operations of k_query_inst's entry step, so the same bits.
+__device__ __forceinline__ void inst_object_ray(const TlasDev& tl, uint32_t inst, const Ray& rw, v3& o, v3& d)
+{
+    const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
+    const v3     r0 = mk3(w0.x, w0.y, w0.z), r1 = mk3(w1.x, w1.y, w1.z), r2 = mk3(w2.x, w2.y, w2.z);
+    o = mk3(dot3(r0, rw.o) + w0.w, dot3(r1, rw.o) + w1.w, dot3(r2, rw.o) + w2.w);
+    d = mk3(dot3(r0, rw.d), dot3(r1, rw.d), dot3(r2, rw.d));
+}
+
+// Workgroups per CU: the LDS slice allows inst_blocks(STACK); the list's 3 K registers (and cursor, count, the second lower bound) take
+// it down to the most that leave every instantiation without scratch (tools/kernel_regs.sh; the table is in DESIGN.md): six (80
+// VGPRs) at K = 1, four (128) at K = 4 -- five (96) spill --, three (168) at K = 8 -- four spill -- and two (256) at K = 16.
+constexpr int inst_multi_blocks(int STACK, int K)
+{
+    const int by_regs = K <= 1 ? 6 : K <= 4 ? 4 : K <= 8 ? 3 : 2;
+    return inst_blocks(STACK) < by_regs ? inst_blocks(STACK) : by_regs;
+}
+
+// k_query_inst's closest-mode loop with the list in place of the best record.  The pruning bound `tfar` -- slot K - 1's t, or tmax
+// while counting -- stands wherever best_t stands there: the bottom-level slab, tlas_slab and the `still` re-check of a queued
+// instance.  All three are inclusive (tn <= tf (1 + slack), tf = min(exit, tfar)), so an instance or box entered exactly at the k-th
+// t is still opened and an equal-t pair with a lower (instance, triangle) still displaces the k-th entry: the list is exact whatever
+// the visiting order.  Paging: only pairs above the cursor (t_c, i_c, g_c) -- slot k - 1 of the ray's two pages -- are offered; pairs
+// below t_c lie outside every later page, so the BOX tests take lo = max(tmin, t_c) as their lower bound (inclusive too: a pair at
+// t_c with a higher (instance, triangle) is kept), while the triangle test keeps the ray's own tmin and with it its bits.
+// Write-out as query.hip's multi_write: (u, v) are not kept in the list; each listed pair is tested again, on the object-space ray
+// rebuilt from its instance record and the triangle's record in bvh.tris_by_id.  That record equals the one the walk read in its
+// first twelve words (the scene's and the forest's are written by the same triangle setup from the same vertices; only word 12, the
+// id, is renumbered by k_forest_relocate), and the ray is rebuilt by the same operations, so (t, u, v) are the traversal's.
+template <int STACK, int K, bool COUNT>
+__global__ __launch_bounds__(kBlock, inst_multi_blocks(STACK, K)) void k_query_inst_multi(BvhDev bvh, MultiArgs m, TlasDev tl, RayFilter f, uint32_t* inst_out)
+{
+    __shared__ uint32_t lds_stack[STACK * kBlock];
+    __shared__ uint32_t lds_off[kTlasMaxLevels + 1];
+    uint32_t* const     stack = lds_stack + threadIdx.x;
+    if (threadIdx.x <= tl.top) lds_off[threadIdx.x] = tl.level_off[threadIdx.x];
+    __syncthreads();
+    const QueryArgs& q = m.q;
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < q.n; j += gridDim.x * kBlock)
+    {
+        const float4 a = q.rays[2 * (size_t)j], b = q.rays[2 * (size_t)j + 1];
+        const Ray    rw   = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
+        const float  omax = fmaxf(fabsf(a.x), fmaxf(fabsf(a.y), fabsf(a.z)));
+        float4* const   page  = static_cast<float4*>(q.out) + (size_t)j * m.k;
+        uint32_t* const ipage = inst_out + (size_t)j * m.k;
+        InstHitList<K>  L;
+        L.init(m.k, rw.tmax);
+        // the cursor: slot k - 1 of both pages when paging, else (-inf, 0, 0), below every pair
+        float    tc = -__builtin_inff();
+        uint32_t ic = 0u, gc = 0u, count = 0u;
+        if (m.resume)
+        {
+            const float4 e = page[m.k - 1u];
+            tc = e.x, gc = f2u(e.w), ic = ipage[m.k - 1u];
+        }
+        const float lo  = fmaxf(rw.tmin, tc);  // the box tests' lower bound
+        Ray         rwb = rw;
+        rwb.tmin        = lo;
+        // top level: the node whose two children (level - 1, 2 idx + {0, 1}) are tested next
+        uint32_t level = tl.top + 1u, idx = 0u, pending = 0u;
+        bool     top_done = false;
+        uint32_t todo0 = kInvalidId, todo1 = kInvalidId;
+        float    todo0_tn = 0.f, todo1_tn = 0.f;
+        // bottom level: r for the triangles, rb (its tmin = lo) for the boxes
+        bool     in_blas = false;
+        Ray      r = rw, rb = rwb;
+        uint32_t inst = 0u, imask = 0u;
+        int      node = 0, sp = 0;
+        bool     walk = query_ray_ok(a, b) && bvh.tri_count != 0u;
+        while (walk)
+        {
+            const float tfar = COUNT ? rw.tmax : L.t[K - 1];
+            if (in_blas)
+            {
+                if (node >= 0)
+                {
+                    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2], q3 = bvh.nodes[4 * node + 3];
+                    float      tn0, tn1;
+                    const bool h0 = slab(rb, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, tfar, tn0);
+                    const bool h1 = slab(rb, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, tfar, tn1);
+                    const int  c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+                    if (h0 && h1)
+                    {
+                        const bool swap = tn1 < tn0;
+                        if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)(swap ? c0 : c1);
+                        node = swap ? c1 : c0;
+                        continue;
+                    }
+                    if (h0 || h1)
+                    {
+                        node = h0 ? c0 : c1;
+                        continue;
+                    }
+                }
+                else
+                {
+                    const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                    for (uint32_t leaf = first; leaf <= last; ++leaf)
+                    {
+                        const float4 t0 = bvh.tris[4 * leaf + 0], t1 = bvh.tris[4 * leaf + 1], t2 = bvh.tris[4 * leaf + 2];
+                        float        t, u, v;
+                        if (!tri_test_cull(r, t0, t1, t2, f.cull_and, f.cull_xor, t, u, v)) continue;
+                        const uint32_t gid = f2u(bvh.tris[4 * leaf + 3].x);
+                        if (f.tri_mask && (f.tri_mask[gid] & imask) == 0u) continue;
+                        // multi_offer's rule with the instance between t and the triangle
+                        if (InstHitList<K>::before(tc, ic, gc, t, inst, gid))
+                        {
+                            if (COUNT) ++count;
+                            if (L.admits(t, inst, gid)) L.insert(t, inst, gid);
+                        }
+                    }
+                }
+                if (sp == 0)
+                    in_blas = false;
+                else
+                    node = (int)stack[(--sp) * kBlock];
+                continue;
+            }
+            if (todo0 != kInvalidId)
+            {
+                // enter an instance: mask, then the object-space ray of the contract
+                inst = todo0;
+                const bool still = todo0_tn <= tfar + 4e-7f * fabsf(tfar);  // tlas_slab's comparison against the bound as it is now
+                todo0 = todo1, todo0_tn = todo1_tn, todo1 = kInvalidId;
+                if (!still) continue;
+                const float4 w3 = tl.rec[4 * (size_t)inst + 3];
+                imask           = f2u(w3.x) & f.mask;  // desc.mask & inclusion: the mesh byte joins it per triangle
+                if (imask == 0u) continue;
+                v3 o, d;
+                inst_object_ray(tl, inst, rw, o, d);
+                if (!query_ray_ok(make_float4(o.x, o.y, o.z, rw.tmin), make_float4(d.x, d.y, d.z, rw.tmax))) continue;
+                r       = make_ray(o, d, rw.tmin, rw.tmax);
+                rb      = r, rb.tmin = lo;
+                node    = (int)f2u(w3.y), sp = 0;
+                in_blas = true;
+                continue;
+            }
+            if (top_done) break;
+            const float4* c = tl.tlas + 2 * (size_t)(lds_off[level - 1u] + 2u * idx);
+            const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
+            float         tn0, tn1;
+            const bool    h0 = tlas_slab(rwb, lo0, hi0, omax, tfar, tn0), h1 = tlas_slab(rwb, lo1, hi1, omax, tfar, tn1);
+            const bool    far_first = h0 && h1 && tn1 < tn0;
+            if (level > 1u)
+            {
+                if (h0 || h1)
+                {
+                    if (h0 && h1) pending |= 1u << (level - 1u);
+                    idx   = 2u * idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
+                    level = level - 1u;
+                    continue;
+                }
+            }
+            else if (h0 || h1)
+            {
+                // the children are instances: the nearer box first
+                const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
+                if (h0 && h1)
+                    todo0 = far_first ? i1 : i0, todo0_tn = far_first ? tn1 : tn0, todo1 = far_first ? i0 : i1, todo1_tn = far_first ? tn0 : tn1;
+                else
+                    todo0 = h0 ? i0 : i1, todo0_tn = h0 ? tn0 : tn1;
+            }
+            const uint32_t owed = pending >> level;
+            if (owed == 0u)
+            {
+                top_done = true;
+                continue;
+            }
+            const uint32_t up = (uint32_t)__builtin_ctz(owed);
+            idx     = (idx >> up) ^ 1u;
+            level   = level + up;
+            pending = pending & ~(1u << level);
+        }
+        if (COUNT) m.counts[j] = count;
+        const int skip = K - (int)m.k;  // the placeholders
+        uint32_t  cur  = kInvalidId;    // the instance r holds the object-space ray of: consecutive listed pairs often share one
+#pragma unroll
+        for (int s = 0; s < K; ++s)
+            if (s >= skip)
+            {
+                float u = 0.f, v = 0.f;
+                if (L.g[s] != kInvalidId)
+                {
+                    if (L.i[s] != cur)
+                    {
+                        v3 o, d;
+                        inst_object_ray(tl, L.i[s], rw, o, d);
+                        r   = make_ray(o, d, rw.tmin, rw.tmax);
+                        cur = L.i[s];
+                    }
+                    const float4* rec = bvh.tris_by_id + 4 * (size_t)L.g[s];
+                    float         t;
+                    tri_test(r, rec[0], rec[1], rec[2], t, u, v);
+                }
+                page[s - skip]  = make_float4(L.t[s], u, v, u2f(L.g[s]));
+                ipage[s - skip] = L.i[s];
+            }
+    }
+}
+
 // An object's tree, built by the scene's builders on the object's triangles alone (local node, record and triangle numbers), made part
 // of the forest in place: node and record numbers of the pools, the scene's triangle ids.
 __global__ __launch_bounds__(kBlock) void k_forest_relocate(ForestRelocArgs a)
@@ -515,5 +755,44 @@ void launch_query_instances(const LaunchCfg& cfg, const BvhDev& bvh, const Query
         CAP_INST(64)
     }
 #undef CAP_INST
+}
+
+template <int STACK, int K, bool COUNT>
+static void launch_inst_multi_k(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, const TlasDev& tl, const RayFilter& f, uint32_t* inst_out)
+{
+    uint32_t want = (m.q.n + kBlock - 1) / kBlock;
+    if (want == 0) want = 1;
+    hipLaunchKernelGGL((k_query_inst_multi<STACK, K, COUNT>), dim3(resident_grid<k_query_inst_multi<STACK, K, COUNT>>(cfg, want)), dim3(kBlock), 0,
+                       cfg.stream, bvh, m, tl, f, inst_out);
+}
+
+template <int STACK>
+static void launch_inst_multi_s(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, const TlasDev& tl, const RayFilter& f, uint32_t* inst_out)
+{
+#define CAP_INST_MULTI(K)                                                     \
+    if (m.counts)                                                             \
+        launch_inst_multi_k<STACK, K, true>(cfg, bvh, m, tl, f, inst_out);    \
+    else                                                                      \
+        launch_inst_multi_k<STACK, K, false>(cfg, bvh, m, tl, f, inst_out);
+    switch (multi_bucket(m.k))
+    {
+    case 1: CAP_INST_MULTI(1) break;
+    case 4: CAP_INST_MULTI(4) break;
+    case 8: CAP_INST_MULTI(8) break;
+    default: CAP_INST_MULTI(16) break;
+    }
+#undef CAP_INST_MULTI
+}
+
+void launch_query_instances_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, const TlasDev& tl, const RayFilter& f, uint32_t* inst_out,
+                                  uint32_t depth)
+{
+    // the bottom-level stack as launch_query_instances chooses it
+    if (depth <= 24 && cfg.stack_entries <= 32)
+        launch_inst_multi_s<24>(cfg, bvh, m, tl, f, inst_out);
+    else if (cfg.stack_entries <= 32)
+        launch_inst_multi_s<32>(cfg, bvh, m, tl, f, inst_out);
+    else
+        launch_inst_multi_s<64>(cfg, bvh, m, tl, f, inst_out);
 }
 }  // namespace cap

@@ -551,6 +551,35 @@ int cap_trace_instances(CapContext* ctx, const CapRayDesc* device_rays, uint64_t
                         const CapTraceOptions* options /* may be NULL */);
 int cap_trace_instances_occlusion(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded,
                                   const CapTraceOptions* options /* may be NULL */);
+/* Multi-hit over the instances: cap_trace_rays_multi_ex's pages, counts and paging over cap_trace_instances' hit set.
+ * Hit set of a ray: exactly cap_trace_instances' -- the pairs (instance i, triangle g) with i not inert, g passing the closest
+ * triangle test against the ray's object-space ray in instance i, and the filters of `options` (facing in object space;
+ * desc[i].mask & mesh_mask[m] & instance_mask != 0).  With an object table g ranges over the instance's object only.  Sorted by
+ * (t, i, g) ascending, the order cap_trace_instances' tie rule defines; a pair appears at most once.
+ * Pages: device_hits[r * k + j] and device_instances[r * k + j], j < k, are ray r's j-th pair: the CapHit holds t, object-space
+ * (u, v) and the scene's global triangle id, device_instances the table index.  Slots after the last pair hold the miss record
+ * (tmax, 0, 0, 0xFFFFFFFF) and instance 0xFFFFFFFF.  With k = 1 record and instance are bit-identical to what cap_trace_instances
+ * writes for the same options without CAP_RAY_FLAG_ACCEPT_FIRST_HIT.  Records depend on neither tree nor on the visiting order.
+ * device_counts: NULL, or n uint32: the number of ALL pairs of the set, not capped at k (with CAP_MULTI_CONTINUE: of the pairs above
+ * the cursor).  Asking for counts turns off pruning by the k-th hit.  k = 0 counts only: device_hits and device_instances must be
+ * NULL and device_counts given.
+ * Paging (CAP_MULTI_CONTINUE): on entry, slot k - 1 of each ray's hit page and of its instance page is read as the cursor
+ * (t_c, i_c, g_c); only pairs with (t, i, g) > (t_c, i_c, g_c) in lexicographic order count, and the next page is written over the
+ * old one.  A short page ends in the miss record, whose cursor (tmax, 0xFFFFFFFF, 0xFFFFFFFF) admits nothing.  Calling again with the
+ * same rays and buffers walks every pair exactly once, equal-t pairs of coinciding or abutting instances on either side of a page
+ * boundary included (a loop over cap_trace_instances with tmin = t loses those: the interval is open).  Both cursor slots must hold
+ * what the previous call wrote there.
+ * Everything else is as for cap_trace_rays_multi_ex and cap_trace_instances: device pointers on the context's GPU; rays and hits
+ * 16-byte, instances and counts 4-byte aligned; no overlap between any two of the four ranges; asynchronous on the context stream,
+ * ordered behind a render's second lane; n above 2^24 split into launches, n = 0 does nothing; degenerate rays give miss pages and
+ * count 0 (with CAP_MULTI_CONTINUE too); nothing of the render's state is touched.  Errors: CAP_ERR_STATE without an instance table,
+ * before cap_bvh_build and while the trees are stale; CAP_ERR_INVALID_ARG for k > CAP_MULTI_MAX_K, k = 0 with hits or instances given
+ * or counts NULL, k > 0 with hits or instances NULL, CAP_MULTI_CONTINUE with k = 0, unknown multi flags,
+ * CAP_RAY_FLAG_ACCEPT_FIRST_HIT, both cull flags, unknown ray flags, non-zero reserved words, instance_mask > 0xFF, misalignment,
+ * overlap, and n * k records beyond the address space.  Nothing is written on an error. */
+int cap_trace_instances_multi(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits,
+                              uint32_t* device_instances, uint32_t* device_counts, uint32_t multi_flags,
+                              const CapTraceOptions* options /* may be NULL */);
 
 /* ---- objects: per-mesh-range bottom-level trees for the instanced queries ----
  * An object is the mesh range [first_mesh, first_mesh + mesh_count) of the uploaded scene: mesh_count >= 1, at least one triangle,
@@ -568,7 +597,7 @@ int cap_trace_instances_occlusion(CapContext* ctx, const CapRayDesc* device_rays
  * and then the instances' world boxes and TLAS.  The call waits for the device once, to read the trees' depths and bounds.
  * Memory: the forest holds 64 B per covered triangle (intersection records) and 64 B per node (triangles - 1 per object) beside the
  * scene's own trees, plus build scratch of about 100 B per triangle of the largest object.
- * cap_render, the plain queries and the multi-hit queries do not read the table. */
+ * cap_render, the plain queries and the flat multi-hit queries (cap_trace_rays_multi*) do not read the table. */
 #define CAP_OBJECT_MAX_COUNT 4096u
 typedef struct CapObjectRange
 {
