@@ -214,6 +214,7 @@ SYMBOLS = {
     "cap_debug_get": (_i, [_vp, _u32, C.POINTER(_u64)]),
     "cap_debug_switch_index": (_i, [C.c_char_p]),
     "cap_debug_pair_ids_dense": (_i, [_vp, _u32, _u32, _u32]),
+    "cap_debug_query_ranges": (_i, [_u64, _u32, _vp, _vp, _vp]),
     "cap_render": (_i, [_vp, _u32, _u32, _u32, _u32]),
     "cap_accum_reset": (_i, [_vp]),
     "cap_accum_import": (_i, [_vp, _vp, _u64]),

@@ -64,7 +64,7 @@ struct BvhDev
     const float4* fan_singles;
     uint32_t      fan_pair_count, fan_single_count;
     // EXT model, next-event rays (round 6): the same pair records with the pairs that can never occlude a segment between a scene point
-    // and a point of a light triangle moved behind the first fan_pair_nee_count -- see update_nee_pairs() in context.hip for the rule
+    // and a point of a light triangle moved behind the first fan_pair_nee_count -- see update_nee_pairs() in ctx_scene.hip for the rule
     // and its exactness argument.  An occlusion test is an OR over the pairs, so their order is free there.
     const float4* fan_pairs_nee;
     uint32_t      fan_pair_nee_count;

@@ -1,34 +1,44 @@
-// context.hip — implementation of the C ABI in include/capsaicin_hip.h: device memory ownership, uploads, the
+// context.hip — the context behind the C ABI of include/capsaicin_hip.h: creation, settings, the working sets of a render, the
 // per-batch wavefront loop (the MI355X counterpart of RaytracingSystem::Run, reference
 // src/systems/raytracing_system.cpp:230-318, ray passes only), readback, statistics.
 //
 // The product path is HIP only: every entry point that needs the GPU fails with CAP_ERR_HIP when no device or
 // kernel is available; there is no CPU fallback.
+//
+// The rest of the ABI by role: ctx_scene.hip (uploads, light table), ctx_bvh.hip (builds, refit, objects, instances), ctx_query.hip (ray
+// queries), ctx_post.hip (reconstruction chain), ctx_comm.hip (RCCL frame exchange); cap_context.h is what they share.
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <string>
-#include <vector>
 
-#include "../../include/capsaicin_hip.h"
-#include <chrono>
-
-#include "cap_kernels.h"
-#include "sah_builder.h"
-#include "wide_builder.h"
+#include "cap_context.h"
 #include "cap_wide.h"
-
-using namespace cap;
+#include "query_ranges.h"
 
 namespace
 {
 thread_local std::string g_error;
 
+// camera rays take the per-lane wide kernel instead of the packet walk from this many triangles per pixel on (measured: cap_render;
+// 1.0 until the walk's node step was rewritten in round 6 -- at 1.0 the walk now wins by 6 % of the step, at 2.0 the two are level)
+constexpr double kPrimaryWideTrianglesPerPixel = 2.0;
+// shadow rays take the lane-refill kernel from this many bytes of wide nodes + intersection records on (measured: cap_render).
+// Round 6: never by default.  Until the per-chunk kernel's traversal was compiled per light octant (docs/experiments.md (86)) the refill
+// kernel won by 3 % from 512 MiB of tree on; now the per-chunk kernel wins by 6 - 8 % at 8.4 M and 16.8 M triangles (1.5 GB of tree),
+// as it always did below.  CAP_ANY_REFILL=1 still selects the refill kernel (tests/test_fallback_kernels_gpu.py keeps it honest).
+constexpr uint64_t kAnyRefillTreeBytes = ~0ull;
+
+// guard block of a context (ShadeArgs::shaded_counter): {-, malformed path ids seen by shade, by trace_any, last offender, appends
+// beyond a class's capacity, -, -, -}
+constexpr size_t kGuardWords = 8;
+}  // namespace
+
+namespace cap
+{
 int fail(int code, const char* fmt, ...)
 {
     char    buf[512];
@@ -40,246 +50,6 @@ int fail(int code, const char* fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                         \
-    do                                                                                                        \
-    {                                                                                                         \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess) return fail(CAP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                          __FILE__, __LINE__);                                                \
-    } while (0)
-
-template <typename T>
-struct DevBuf
-{
-    T*     p = nullptr;
-    size_t n = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept
-    {
-        if (this != &o)
-        {
-            release();
-            p = o.p, n = o.n, o.p = nullptr, o.n = 0;
-        }
-        return *this;
-    }
-    ~DevBuf() { release(); }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr, n = 0;
-    }
-    hipError_t ensure(size_t count)
-    {
-        if (count <= n && p) return hipSuccess;
-        release();
-        if (count == 0) count = 1;
-        hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-};
-
-// camera rays take the per-lane wide kernel instead of the packet walk from this many triangles per pixel on (measured: cap_render;
-// 1.0 until the walk's node step was rewritten in round 6 -- at 1.0 the walk now wins by 6 % of the step, at 2.0 the two are level)
-constexpr double kPrimaryWideTrianglesPerPixel = 2.0;
-// shadow rays take the lane-refill kernel from this many bytes of wide nodes + intersection records on (measured: cap_render).
-// Round 6: never by default.  Until the per-chunk kernel's traversal was compiled per light octant (docs/experiments.md (86)) the refill
-// kernel won by 3 % from 512 MiB of tree on; now the per-chunk kernel wins by 6 - 8 % at 8.4 M and 16.8 M triangles (1.5 GB of tree),
-// as it always did below.  CAP_ANY_REFILL=1 still selects the refill kernel (tests/test_fallback_kernels_gpu.py keeps it honest).
-constexpr uint64_t kAnyRefillTreeBytes = ~0ull;
-// AUTO builds with surface-area splits (ploc.hip, sah_device) from this many triangles on, the clustering alone below (see cap_bvh_build)
-constexpr uint32_t kAutoSahTriangles = 4096;
-
-// guard block of a context (ShadeArgs::shaded_counter): {-, malformed path ids seen by shade, by trace_any, last offender, appends
-// beyond a class's capacity, -, -, -}
-constexpr size_t kGuardWords = 8;
-
-enum StageId
-{
-    ST_PRIMARY,
-    ST_CLOSEST,
-    ST_ANY,
-    ST_SHADE,
-    ST_RESOLVE,
-    ST_POST,
-    ST_COUNT,
-    ST_DIRECT,      // "RT Direct lighting": second label of the bounce-0 shading / shadow-ray spans
-    ST_POST_PASS0,  // .. ST_POST_PASS0 + 4: "Spatial gather", "Temporal upscale", "EAW", "Combine illumination", "TAA"
-    ST_NONE = -1
-};
-
-struct TimedSpan
-{
-    hipEvent_t a, b;
-    int        stage;
-    int        also = ST_NONE;  // a span may count under a second label
-};
-}  // namespace
-
-struct CapContext
-{
-    int         device = 0;
-    hipStream_t stream = nullptr;
-    bool        own_stream = false;
-    int         cu_count = 256;
-
-    // scene (GeometryStorage layout, asset_load_system.h:16-27)
-    DevBuf<float>    positions, normals, texcoords;
-    DevBuf<uint32_t> indices;
-    DevBuf<uint4>    tri_ids;
-    DevBuf<uint4>    mesh_offsets;
-    DevBuf<uint32_t> mesh_texture;
-    uint32_t         vertex_count = 0, index_count = 0, mesh_count = 0, tri_count = 0;
-    bool             scene_ready = false;
-
-    std::vector<DevBuf<uint8_t>> texture_data;
-    std::vector<TextureDev>      texture_host;
-    DevBuf<TextureDev>           textures;
-    bool                         textures_dirty = true;
-    DevBuf<float2>               bluenoise;
-    bool                         bluenoise_ready = false;
-    std::vector<CapMaterial>     materials_host;
-    DevBuf<CapMaterial>          materials;
-    // EXT: host copies needed to build the light table, the table itself, the B/A blue-noise channels
-    std::vector<float>           positions_host;
-    std::vector<uint32_t>        indices_host;
-    std::vector<CapMeshDesc>     meshes_host;
-    DevBuf<uint32_t>             light_tris;
-    DevBuf<float>                light_cdf;
-    DevBuf<float2>               bluenoise_ba;
-    uint32_t                     light_count = 0;
-    float                        light_area  = 0.0f;
-    bool                         materials_ready = false;
-
-    // BVH
-    DevBuf<float4>   shade_tris, tris_sorted, nodes, tri_raw, tri_box;
-    DevBuf<float4>   nodes8, tris8;           // compressed 8-wide view (cap_wide.h) and its intersection records
-    DevBuf<uint32_t> wide_src;                // leaf-order index per wide-order record
-    DevBuf<uint32_t> wide_task, wide_alloc, wide_cnt;   // device collapse: binary node per wide node, allocation counters, per-level bases
-    uint32_t         wide8_depth = 0, wide8_top = 0, wide8_nodes = 0;
-    float            wide8_ms = 0.f;
-    DevBuf<uint32_t> query_work, query_defer; // cap_trace_rays / cap_trace_occlusion: chunk and hand-over counters, rays handed to the binary tree
-    DevBuf<uint8_t>  tri_mask;                // cap_scene_set_instance_masks: each triangle's mesh mask, by global triangle id
-    bool             tri_mask_on = false;     // a mask table is installed (some mask differs from 0xFF)
-    // instance table and top-level tree (cap_instances_set, instance.hip); inst_count = 0: no table
-    DevBuf<float4>   inst_desc, inst_rec, inst_box, inst_tlas;
-    DevBuf<uint32_t> inst_keys[2], inst_vals[2], inst_hist, inst_scan, inst_misc, inst_level_off;
-    uint32_t         inst_count = 0, inst_top = 0, inst_nodes = 0;
-    DevBuf<uint32_t> inst_obj;                // each instance's object index (cap_instances_set_ex)
-    bool             inst_obj_on = false;     // ... given with the installed table (false: every instance shows object 0)
-    InstObject       scene_object_host{};     // the scene as the one object of a context without an object table ...
-    DevBuf<InstObject> scene_object;          // ... and its device copy (instances_rebuild)
-    // object table and forest (cap_objects_set, instance.hip); obj_count = 0: no table.  Object k's tree: nodes
-    // [obj_node_base[k], + triangle_count - 1) of forest_nodes, records [obj_rec_base[k], + triangle_count) of forest_tris.
-    std::vector<CapObjectInfo> obj_info;
-    std::vector<uint32_t>      obj_node_base, obj_rec_base;
-    uint32_t                   obj_count = 0, obj_max_depth = 0;
-    DevBuf<float4>             forest_nodes, forest_tris;
-    DevBuf<InstObject>         obj_table;     // per object: padded box and root (k_instance_setup)
-    DevBuf<float4>             obj_tri_raw, obj_tri_box;  // build scratch of the largest object (the builders' tri_raw / tri_box / leaf_tri)
-    DevBuf<uint32_t>           obj_leaf_tri, obj_misc;    // obj_misc: 8 words per object, 6 bounds + depth
-    DevBuf<float4>   fan_pairs, fan_singles;  // exhaustive path: fan-pair records (5 float4) and the unpaired triangles (4 float4)
-    uint32_t         fan_pair_count = 0, fan_single_count = 0;
-    DevBuf<float4>   fan_pairs_nee;           // the pair records again, potential occluders of next-event rays first (update_nee_pairs)
-    uint32_t         fan_pair_nee_count = 0;
-    std::vector<float>    fan_pairs_host;     // 20 floats per pair (+ padding records), as uploaded
-    std::vector<uint32_t> light_tris_host;    // global ids of the emissive triangles (cap_materials_upload)
-    DevBuf<uint32_t> leaf_tri, keys0, keys1, vals0, vals1, hist, parent, flags, bvh_misc;  // bvh_misc: 6 bounds + depth + 1 if a triangle's stored normals are not tame (SceneDev::shade_tame)
-    DevBuf<float4>   ploc_boxes;  // CAP_BVH_BUILD_PLOC scratch (ploc.hip)
-    DevBuf<uint32_t> ploc_ints;
-    DevBuf<uint32_t> sahdev_words;  // CAP_BVH_BUILD_SAH_DEVICE scratch (ploc.hip)
-    CapBvhInfo       bvh_info{};
-    bool             shade_tame = false;  // SceneDev::shade_tame of the shading records as cap_bvh_build / cap_bvh_refit last wrote them
-    bool             bvh_ready = false;
-    // vertex updates and refit (cap_scene_update_vertices, cap_bvh_refit, refit.hip)
-    bool                  bvh_stale = false;             // vertices changed since the trees were last brought up to date
-    bool                  positions_host_stale = false;  // positions_host lags a device-side update (read back only when needed)
-    bool                  visits_built_known = false;    // refit_visits_built holds the metric of the last build's boxes
-    double                refit_visits_built = 0.0;
-    std::vector<uint32_t> wide_levels;                   // level l of the 8-wide view = nodes [wide_levels[l], wide_levels[l + 1])
-    DevBuf<float>         wide_boxes;                    // refit scratch: each wide node's box (6 floats)
-    DevBuf<double>        refit_sums;                    // refit scratch: partial sums of the tree metric, then its two values
-
-    // camera / screen
-    CapCameraData camera{}, prev_camera{};
-    bool          camera_ready = false, prev_camera_ready = false;
-    ScreenDev     screen{};
-    uint64_t      max_batch_paths = 0;
-    SwitchTable   sw{};                    // A/B switches: environment at creation, then cap_debug_set(CAP_DEBUG_SWITCH_BASE + i)
-    uint32_t      debug_capacity_div = 1;  // cap_debug_set(CAP_DEBUG_QUEUE_CAPACITY_DIV): tests of the append guard only
-    uint32_t      debug_wide_depth_limit = 0;  // cap_debug_set(CAP_DEBUG_WIDE_DEPTH_LIMIT): pretend the wide kernels' stacks end here
-    bool          debug_fail_lane = false;     // cap_debug_set(CAP_DEBUG_FAIL_LANE1): the second working set "cannot be allocated"
-    // The smallest second working set (paths = slots x padded pixels) whose allocation has failed since the last call that can free
-    // memory: cap_render does not try that size or a larger one again (every call repeated ~28 GB of hipMalloc / hipFree).
-    uint64_t      lane1_failed_paths = 0;
-    uint32_t      lane1_failed_bounces = 0, lane1_retry_tick = 0;
-    uint32_t      lanes_last_render = 0;       // cap_debug_get(CAP_DEBUG_LANES_USED)
-    uint32_t      last_class_capacity = 0;     // sub-queue capacity of the last cap_render batch (CAP_DEBUG_QUEUE_CANARY_*)
-    uint32_t      tri_ids_dense = 0;           // pair_ids_dense() of the uploaded fan records (BvhDev::tri_ids_dense)
-    uint32_t      last_mark_form = 0;          // launch_trace_shade()'s answer for bounce >= 1 of the last cap_render (CAP_DEBUG_MARK_FORM)
-    uint32_t      last_cull_camera_pairs = 0;  // ShadeArgs::cull_camera_pairs of the last cap_render batch (CAP_DEBUG_CAMERA_CULL)
-    uint32_t      traversal_mode  = CAP_TRAVERSAL_AUTO;
-    uint32_t      bvh_build_mode  = CAP_BVH_BUILD_AUTO;
-
-    // wavefront state
-    DevBuf<float4>     aov_geo, aov_nd, accum, image_tmp;
-    DevBuf<uint64_t>   shaded_counter;
-    // A batch working set of cap_render: queues, planes, counters and a slice of traversal-stack spill, and the stream its batches
-    // run on.  There are two ("two lanes"), for batches in flight beside each other: lane[0] on the context's `stream`, lane[1] on
-    // `stream2` (both sized by ensure_lane).  Lane 0's spill area is the one cap_bvh_build allocates and every ray query uses.  The
-    // LAST batch of a call always runs on lane 0, so everything that reads a finished frame's planes finds them there (aov_planes).
-    struct Lane
-    {
-        hipStream_t      stream = nullptr;  // not owned: the context's `stream` (lane 0) or `stream2` (lane 1)
-        DevBuf<float4>   hits, q_org[2], q_dir[2], q_thr[2], s_org, s_dir, s_con, pl_color, pl_direct, pl_albedo;
-        DevBuf<uint32_t> counters;     // per batch: ext[0..D], shadow[0..D]
-        DevBuf<uint32_t> stack_spill;  // traversal-stack entries beyond the LDS part, per thread of the persistent grid
-    } lane[2];
-    hipStream_t stream2 = nullptr;
-    hipEvent_t  lane_ev[2] = {nullptr, nullptr}, fork_ev = nullptr, join_ev = nullptr;
-    // per-frame constants of a cap_render call: a ring of device buffers fed from pinned staging, so that a call need not wait
-    // for the previous one (which may still be reading its own slot)
-    static constexpr int kFrameRing = 4;
-    DevBuf<FrameConst> frames_ring[kFrameRing];
-    FrameConst*        frames_pinned[kFrameRing] = {nullptr, nullptr, nullptr, nullptr};
-    size_t             frames_pinned_n[kFrameRing] = {0, 0, 0, 0};
-    hipEvent_t         frames_event[kFrameRing] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t           frames_next = 0;
-    uint32_t           last_slots = 0;     // frame slots of the last batch rendered (AOV readback)
-    bool               aov_valid = false;
-    bool               aov_lowres = false;  // the AOV frame was rendered with CAP_RENDER_LOWRES_INDIRECT
-    uint32_t           aov_frame  = 0;      // its frame_count (selects the 2x2 interleave offset)
-    uint64_t           frames_accumulated = 0;
-
-    // reconstruction chain (row-major W*H images)
-    DevBuf<float4> post_in[4];  // indirect, direct, albedo, normal_depth of the frame
-    DevBuf<float4> post_ihist[2], post_mhist[2], post_chist[2], post_prev_nd, post_itemp, post_temp[2], post_normals;
-    uint32_t       post_w = 0, post_h = 0;
-    int            post_last_dst = -1;
-
-    // multi-GPU frame exchange (cap_comm_*): RCCL communicator, or `comm_local` when the shards of one process share a device
-    void*           comm = nullptr;  // ncclComm_t
-    uint32_t        comm_rank = 0, comm_size = 0;
-    bool            comm_local = false;
-    DevBuf<float>   comm_send, comm_gathered, comm_image;
-    hipEvent_t      comm_event = nullptr;
-
-    // statistics
-    CapStats               stats{};
-    std::vector<TimedSpan> spans;
-    std::vector<std::array<hipEvent_t, 6>> post_marks;  // pass-boundary events of every cap_post_frame since the last sync
-    std::vector<hipEvent_t> event_pool;
-    std::vector<uint32_t*> pinned_pool;
-    std::vector<std::pair<uint32_t*, uint32_t>> pending;  // (pinned counters, bounces) per batch, read at sync
-    uint64_t*              pinned_shaded = nullptr;
-};
-
-namespace
-{
 int sync_and_collect(CapContext* c)
 {
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -366,6 +136,68 @@ hipEvent_t get_event(CapContext* c)
     return e;
 }
 
+CameraDev camera_dev(const CapCameraData& cd)
+{
+    CameraDev d{};
+    for (int k = 0; k < 3; ++k) d.position[k] = cd.position[k], d.right[k] = cd.right[k], d.forward[k] = cd.forward[k], d.up[k] = cd.up[k];
+    d.focal_length = cd.focal_length;
+    d.sensor_x     = cd.sensor_size[0];
+    d.sensor_y     = cd.sensor_size[1];
+    return d;
+}
+
+// the tree view of a launch whose traversal stacks spill into `lane`'s area
+BvhDev bvh_dev(const CapContext* c, const CapContext::Lane& lane)
+{
+    BvhDev b{};
+    b.nodes     = c->nodes.p;
+    b.tris      = c->tris_sorted.p;
+    b.tris_by_id = c->tri_raw.p;
+    b.stack_spill   = lane.stack_spill.p;
+    b.spill_threads = (uint32_t)(lane.stack_spill.n / kSpillEntries);
+    // A/B switch: the binary-tree kernels (also what runs if the 8-wide view's depth ever exceeds the pair stacks)
+    const bool no_wide8 = c->sw.on(SW_NO_WIDE8);
+    b.nodes8 = c->nodes8.p, b.tris8 = c->tris8.p;
+    b.wide8_ok  = !no_wide8 && lane.stack_spill.p && c->wide8_nodes != 0 && c->wide8_depth <= wide8_stack_pairs() + 1u &&
+                 c->wide8_depth <= kWideLdsEntries / 2u + kSpillEntries / 2u + 1u &&
+                 (c->debug_wide_depth_limit == 0u || c->wide8_depth <= c->debug_wide_depth_limit);
+    b.wide8_top = c->wide8_top;
+    b.fan_pairs = c->fan_pairs.p, b.fan_singles = c->fan_singles.p;
+    b.fan_pair_count = c->fan_pair_count, b.fan_single_count = c->fan_single_count;
+    b.tri_ids_dense = c->tri_ids_dense;
+    b.fan_pairs_nee = c->fan_pairs_nee.p ? c->fan_pairs_nee.p : c->fan_pairs.p;
+    b.fan_pair_nee_count = c->fan_pairs_nee.p ? c->fan_pair_nee_count : c->fan_pair_count;
+    b.tri_count = c->tri_count;
+    b.root      = c->tri_count >= 2 ? 0 : ~0;
+    return b;
+}
+
+AovPlanes aov_planes(const CapContext* c)
+{
+    const size_t off = (size_t)(c->last_slots ? c->last_slots - 1 : 0) * c->screen.pixels_padded;
+    return AovPlanes{c->lane[0].pl_color.p + off, c->lane[0].pl_direct.p + off, c->lane[0].pl_albedo.p + off};
+}
+
+// CAP_TRACE_LAUNCHES=1: name every launch on stderr and drain the stream after it (fault localisation only)
+int trace_launch(const CapContext* c, const char* fmt, ...)
+{
+    if (!c->sw.on(SW_TRACE_LAUNCHES)) return CAP_OK;
+    va_list ap;
+    va_start(ap, fmt);
+    fputs("[cap] ", stderr);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    fputs(" ... ", stderr);
+    fflush(stderr);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    fprintf(stderr, "%s\n", hipGetErrorString(e));
+    fflush(stderr);
+    return e == hipSuccess ? CAP_OK : CAP_ERR_HIP;
+}
+}  // namespace cap
+
+namespace
+{
 struct StageTimer
 {
     CapContext* c;
@@ -406,16 +238,6 @@ void update_screen(CapContext* c, uint32_t w, uint32_t h, uint32_t shard_index, 
     c->aov_valid = false;
 }
 
-CameraDev camera_dev(const CapCameraData& cd)
-{
-    CameraDev d{};
-    for (int k = 0; k < 3; ++k) d.position[k] = cd.position[k], d.right[k] = cd.right[k], d.forward[k] = cd.forward[k], d.up[k] = cd.up[k];
-    d.focal_length = cd.focal_length;
-    d.sensor_x     = cd.sensor_size[0];
-    d.sensor_y     = cd.sensor_size[1];
-    return d;
-}
-
 // lighting.h:20-33 + camera.h:41, evaluated once per frame on the host with the shared arithmetic contract
 FrameConst frame_const(uint32_t frame_count, bool lowres_indirect)
 {
@@ -433,32 +255,6 @@ FrameConst frame_const(uint32_t frame_count, bool lowres_indirect)
     f.light_intensity[1] = 1.0f * (2.0f * 12.0f + 0.0f);
     f.light_intensity[2] = 1.0f * (2.0f * 10.0f + (2.0f + 2.0f * ct));
     return f;
-}
-
-// the tree view of a launch whose traversal stacks spill into `lane`'s area
-BvhDev bvh_dev(const CapContext* c, const CapContext::Lane& lane)
-{
-    BvhDev b{};
-    b.nodes     = c->nodes.p;
-    b.tris      = c->tris_sorted.p;
-    b.tris_by_id = c->tri_raw.p;
-    b.stack_spill   = lane.stack_spill.p;
-    b.spill_threads = (uint32_t)(lane.stack_spill.n / kSpillEntries);
-    // A/B switch: the binary-tree kernels (also what runs if the 8-wide view's depth ever exceeds the pair stacks)
-    const bool no_wide8 = c->sw.on(SW_NO_WIDE8);
-    b.nodes8 = c->nodes8.p, b.tris8 = c->tris8.p;
-    b.wide8_ok  = !no_wide8 && lane.stack_spill.p && c->wide8_nodes != 0 && c->wide8_depth <= wide8_stack_pairs() + 1u &&
-                 c->wide8_depth <= kWideLdsEntries / 2u + kSpillEntries / 2u + 1u &&
-                 (c->debug_wide_depth_limit == 0u || c->wide8_depth <= c->debug_wide_depth_limit);
-    b.wide8_top = c->wide8_top;
-    b.fan_pairs = c->fan_pairs.p, b.fan_singles = c->fan_singles.p;
-    b.fan_pair_count = c->fan_pair_count, b.fan_single_count = c->fan_single_count;
-    b.tri_ids_dense = c->tri_ids_dense;
-    b.fan_pairs_nee = c->fan_pairs_nee.p ? c->fan_pairs_nee.p : c->fan_pairs.p;
-    b.fan_pair_nee_count = c->fan_pairs_nee.p ? c->fan_pair_nee_count : c->fan_pair_count;
-    b.tri_count = c->tri_count;
-    b.root      = c->tri_count >= 2 ? 0 : ~0;
-    return b;
 }
 
 SceneDev scene_dev(const CapContext* c)
@@ -616,37 +412,6 @@ BatchPolicy batch_policy(const CapContext* c, uint32_t n_frames, uint32_t num_bo
         two_lanes && c->lane1_failed_paths && (uint64_t)slots * Ppad >= c->lane1_failed_paths && num_bounces >= c->lane1_failed_bounces;
     return BatchPolicy{slots, two_lanes, failed_before};
 }
-
-// The AOV frame's tile-ordered planes (what CAP_RENDER_AOV leaves for read-backs and the reconstruction chain): the last frame slot
-// of the last batch.  The LAST batch of a cap_render call always runs on lane 0 (its lane is (n_batches - 1 - batch) & 1), so
-// they are lane 0's planes whichever lanes the call used.
-struct AovPlanes
-{
-    const float4 *color, *direct, *albedo;
-};
-
-AovPlanes aov_planes(const CapContext* c)
-{
-    const size_t off = (size_t)(c->last_slots ? c->last_slots - 1 : 0) * c->screen.pixels_padded;
-    return AovPlanes{c->lane[0].pl_color.p + off, c->lane[0].pl_direct.p + off, c->lane[0].pl_albedo.p + off};
-}
-
-// CAP_TRACE_LAUNCHES=1: name every launch on stderr and drain the stream after it (fault localisation only)
-int trace_launch(const CapContext* c, const char* fmt, ...)
-{
-    if (!c->sw.on(SW_TRACE_LAUNCHES)) return CAP_OK;
-    va_list ap;
-    va_start(ap, fmt);
-    fputs("[cap] ", stderr);
-    vfprintf(stderr, fmt, ap);
-    va_end(ap);
-    fputs(" ... ", stderr);
-    fflush(stderr);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    fprintf(stderr, "%s\n", hipGetErrorString(e));
-    fflush(stderr);
-    return e == hipSuccess ? CAP_OK : CAP_ERR_HIP;
-}
 }  // namespace
 
 // (x, y) -> the four RGBA8 words a bilinear WRAP sample at that texel reads (cap_device.h TextureDev)
@@ -657,6 +422,12 @@ __global__ __launch_bounds__(256) void k_texture_footprints(const uint32_t* src,
     const uint32_t y = (uint32_t)(i / width), x = (uint32_t)(i - (size_t)y * width);
     const uint32_t x1 = x + 1 == width ? 0 : x + 1, y1 = y + 1 == height ? 0 : y + 1;
     dst[i] = make_uint4(src[(size_t)y * width + x], src[(size_t)y * width + x1], src[(size_t)y1 * width + x], src[(size_t)y1 * width + x1]);
+}
+
+void cap::launch_texture_footprints(hipStream_t stream, const uint32_t* src, uint4* dst, uint32_t width, uint32_t height)
+{
+    const size_t texels = (size_t)width * height;
+    hipLaunchKernelGGL(k_texture_footprints, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, stream, src, dst, width, height);
 }
 
 extern "C" {
@@ -717,6 +488,30 @@ extern "C" int cap_debug_tile_divmod(uint32_t tiles_x, const uint32_t* n, uint64
     return CAP_OK;
 }
 
+// The rule behind upload_fan_records' dense bit (ctx_scene.hip pair_ids_dense), for tests/test_pair_carry.py.  No device.
+int cap_debug_pair_ids_dense(const float* pair_records, uint32_t pair_count, uint32_t single_count, uint32_t tri_count)
+{
+    if (!pair_records && pair_count) return 0;
+    return pair_ids_dense(pair_records, pair_count, single_count, tri_count) ? 1 : 0;
+}
+
+// The address checks of the ray-query entry points (query_ranges.h) on `count` ranges of n x stride[i] bytes from base[i], base[i] to be a
+// multiple of align[i] (a power of two); stride[i] == 0: the caller left array i out.  CAP_OK, or CAP_ERR_INVALID_ARG with the message the
+// entry points give.  No context, no device: tests/test_query_ranges.py.
+int cap_debug_query_ranges(uint64_t n, uint32_t count, const uint64_t* base, const uint64_t* stride, const uint32_t* align)
+{
+    static const char* const names[4] = {"range 0", "range 1", "range 2", "range 3"};
+    if (count > 4 || (count && (!base || !stride || !align))) return fail(CAP_ERR_INVALID_ARG, "cap_debug_query_ranges: at most 4 ranges, no NULL array");
+    QueryRange r[4];
+    for (uint32_t i = 0; i < count; ++i)
+    {
+        if (!align[i] || (align[i] & (align[i] - 1u))) return fail(CAP_ERR_INVALID_ARG, "cap_debug_query_ranges: align[%u] is not a power of two", i);
+        r[i] = QueryRange{names[i], (uintptr_t)base[i], stride[i], align[i], stride[i] != 0};
+    }
+    char msg[256];
+    return query_ranges_ok("cap_debug_query_ranges", n, r, count, msg, sizeof(msg)) ? CAP_OK : fail(CAP_ERR_INVALID_ARG, "%s", msg);
+}
+
 int cap_ctx_create(int device_id, void* hip_stream, CapContext** out_ctx)
 {
     if (!out_ctx) return fail(CAP_ERR_INVALID_ARG, "cap_ctx_create: out_ctx is NULL");
@@ -774,890 +569,6 @@ void cap_ctx_destroy(CapContext* c)
         if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
-}
-
-int cap_scene_upload(CapContext* c, const float* positions, const float* normals, const float* texcoords, const uint32_t* indices,
-                     const CapMeshDesc* meshes, uint32_t vertex_count, uint32_t index_count, uint32_t mesh_count)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_scene_upload: ctx is NULL");
-    if ((vertex_count && (!positions || !normals || !texcoords)) || (index_count && !indices) || (mesh_count && !meshes))
-        return fail(CAP_ERR_INVALID_ARG, "cap_scene_upload: NULL array with non-zero count");
-    // validate the descriptors on the host: the kernels index with them unchecked
-    std::vector<uint4> tri_ids;
-    std::vector<uint4> mesh_offsets(mesh_count);
-    std::vector<uint32_t> mesh_texture(mesh_count);
-    for (uint32_t m = 0; m < mesh_count; ++m)
-    {
-        const CapMeshDesc& d = meshes[m];
-        if (d.index != m) return fail(CAP_ERR_INVALID_ARG, "mesh %u: index field is %u (InstanceID must equal the mesh slot)", m, d.index);
-        if (d.index_count % 3) return fail(CAP_ERR_INVALID_ARG, "mesh %u: index_count %u is not a multiple of 3", m, d.index_count);
-        if ((uint64_t)d.first_index_offset + d.index_count > index_count || (uint64_t)d.first_vertex_offset + d.vertex_count > vertex_count)
-            return fail(CAP_ERR_INVALID_ARG, "mesh %u: ranges exceed the pools", m);
-        for (uint32_t k = 0; k < d.index_count; ++k)
-            if (indices[d.first_index_offset + k] >= d.vertex_count)
-                return fail(CAP_ERR_INVALID_ARG, "mesh %u: index %u out of range", m, indices[d.first_index_offset + k]);
-        mesh_offsets[m] = make_uint4(d.first_vertex_offset, d.first_index_offset, 0, 0);
-        mesh_texture[m] = d.texture_index;
-        for (uint32_t p = 0; p < d.index_count / 3; ++p) tri_ids.push_back(make_uint4(m, p, d.texture_index, 0u));
-    }
-    // the traversal-leaf code keeps the first sorted triangle in kLeafCountShift bits (cap_leaf.h)
-    if (tri_ids.size() > kLeafFirstMask) return fail(CAP_ERR_UNSUPPORTED, "too many triangles: %zu (limit %u)", tri_ids.size(), kLeafFirstMask);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(c->positions.ensure(3 * (size_t)vertex_count));
-    HIP_TRY(c->normals.ensure(3 * (size_t)vertex_count));
-    HIP_TRY(c->texcoords.ensure(2 * (size_t)vertex_count));
-    HIP_TRY(c->indices.ensure(index_count));
-    HIP_TRY(c->tri_ids.ensure(tri_ids.size()));
-    HIP_TRY(c->mesh_offsets.ensure(mesh_count));
-    HIP_TRY(c->mesh_texture.ensure(mesh_count));
-    if (vertex_count)
-    {
-        HIP_TRY(hipMemcpy(c->positions.p, positions, sizeof(float) * 3 * vertex_count, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->normals.p, normals, sizeof(float) * 3 * vertex_count, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->texcoords.p, texcoords, sizeof(float) * 2 * vertex_count, hipMemcpyHostToDevice));
-    }
-    if (index_count) HIP_TRY(hipMemcpy(c->indices.p, indices, sizeof(uint32_t) * index_count, hipMemcpyHostToDevice));
-    if (!tri_ids.empty()) HIP_TRY(hipMemcpy(c->tri_ids.p, tri_ids.data(), sizeof(uint4) * tri_ids.size(), hipMemcpyHostToDevice));
-    if (mesh_count)
-    {
-        HIP_TRY(hipMemcpy(c->mesh_offsets.p, mesh_offsets.data(), sizeof(uint4) * mesh_count, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->mesh_texture.p, mesh_texture.data(), sizeof(uint32_t) * mesh_count, hipMemcpyHostToDevice));
-    }
-    c->positions_host.assign(positions, positions + 3 * (size_t)vertex_count);
-    c->indices_host.assign(indices, indices + index_count);
-    c->meshes_host.assign(meshes, meshes + mesh_count);
-    c->materials_ready = false;  // per-mesh materials belong to the previous scene
-    c->light_count     = 0;
-    c->light_tris_host.clear();  // (and with them the next-event pair list: rebuilt by the next cap_materials_upload)
-    c->vertex_count = vertex_count, c->index_count = index_count, c->mesh_count = mesh_count, c->tri_count = (uint32_t)tri_ids.size();
-    c->scene_ready = true;
-    c->bvh_ready   = false;
-    c->bvh_stale   = false;
-    c->positions_host_stale = false;
-    c->lane1_failed_paths = 0;  // another scene, other buffers: a second batch lane that did not fit before may fit now
-    c->tri_mask_on = false;     // instance masks belong to the previous scene's meshes
-    c->inst_count  = 0;         // ... and the instance table to its trees
-    c->obj_count   = 0;         // ... and the object table to its mesh table
-    return CAP_OK;
-}
-
-int cap_scene_set_instance_masks(CapContext* c, const uint8_t* masks, uint32_t mesh_count)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_scene_set_instance_masks: ctx is NULL");
-    if (!c->scene_ready) return fail(CAP_ERR_STATE, "cap_scene_set_instance_masks: no scene uploaded");
-    if (mesh_count != c->mesh_count)
-        return fail(CAP_ERR_INVALID_ARG, "cap_scene_set_instance_masks: mesh_count %u is not the uploaded scene's (%u)", mesh_count, c->mesh_count);
-    bool all = true;
-    for (uint32_t m = 0; masks && m < mesh_count; ++m) all = all && masks[m] == 0xFFu;
-    if (all)
-    {
-        c->tri_mask_on = false;  // host state: the queries that follow take the plain kernels; those enqueued keep the table they were given
-        return CAP_OK;
-    }
-    // one byte per global triangle id (mesh-table order, then primitive order: the ids of cap_scene_upload)
-    std::vector<uint8_t> bytes;
-    bytes.reserve(c->tri_count);
-    for (uint32_t m = 0; m < mesh_count; ++m) bytes.insert(bytes.end(), c->meshes_host[m].index_count / 3, masks[m]);
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->tri_mask.n < bytes.size())
-    {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (a grown buffer replaces one an earlier query may still be reading)
-        HIP_TRY(c->tri_mask.ensure(bytes.size()));
-    }
-    // ordered on the context stream behind every query enqueued; the host bytes may go once the call returns
-    if (!bytes.empty())
-    {
-        HIP_TRY(hipMemcpyAsync(c->tri_mask.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    c->tri_mask_on = true;
-    return CAP_OK;
-}
-
-int cap_texture_upload(CapContext* c, uint32_t index, const uint8_t* rgba8, uint32_t width, uint32_t height)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_texture_upload: ctx is NULL");
-    if (index >= 1024) return fail(CAP_ERR_INVALID_ARG, "texture index %u exceeds the reference's 1024-entry table", index);
-    static const uint8_t zero_texel[4] = {0, 0, 0, 0};  // texture_system.cpp:47-56
-    if (!rgba8) rgba8 = zero_texel, width = height = 1;
-    if (!width || !height) return fail(CAP_ERR_INVALID_ARG, "texture %u: empty extent", index);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->texture_host.size() <= index)
-    {
-        const size_t old = c->texture_host.size();
-        c->texture_data.resize(index + 1);
-        c->texture_host.resize(index + 1);
-        for (size_t i = old; i <= index; ++i)
-        {
-            // holes behave like the missing-texture texel
-            static const uint8_t zero_quad[16] = {0};
-            HIP_TRY(c->texture_data[i].ensure(16));
-            HIP_TRY(hipMemcpy(c->texture_data[i].p, zero_quad, 16, hipMemcpyHostToDevice));
-            c->texture_host[i] = TextureDev{reinterpret_cast<const uint4*>(c->texture_data[i].p), 1, 1};
-        }
-    }
-    // stored as the bilinear footprint of every texel: (x, y), (x + 1, y), (x, y + 1), (x + 1, y + 1) with WRAP, four RGBA8 words --
-    // expanded on the device from the plain image (4 bytes per texel cross the bus, not 16)
-    const size_t texels = (size_t)width * height;
-    c->texture_data[index].release();
-    HIP_TRY(c->texture_data[index].ensure(16 * texels));
-    DevBuf<uint8_t> plain;
-    HIP_TRY(plain.ensure(4 * texels));
-    HIP_TRY(hipMemcpy(plain.p, rgba8, 4 * texels, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_texture_footprints, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, c->stream, reinterpret_cast<const uint32_t*>(plain.p),
-                       reinterpret_cast<uint4*>(c->texture_data[index].p), width, height);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    plain.release();
-    c->texture_host[index] = TextureDev{reinterpret_cast<const uint4*>(c->texture_data[index].p), width, height};
-    c->textures_dirty = true;
-    return CAP_OK;
-}
-
-int cap_bluenoise_upload(CapContext* c, const uint8_t* rgba8)
-{
-    if (!c || !rgba8) return fail(CAP_ERR_INVALID_ARG, "cap_bluenoise_upload: NULL argument");
-    std::vector<float2> lut(256 * 256);
-    for (size_t i = 0; i < lut.size(); ++i) lut[i] = make_float2((float)rgba8[4 * i] / 255.0f, (float)rgba8[4 * i + 1] / 255.0f);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(c->bluenoise.ensure(lut.size()));
-    HIP_TRY(hipMemcpy(c->bluenoise.p, lut.data(), sizeof(float2) * lut.size(), hipMemcpyHostToDevice));
-    // EXT: the B and A channels feed the extra random numbers of the EXT shading model (lobe choice, light triangle)
-    for (size_t i = 0; i < lut.size(); ++i) lut[i] = make_float2((float)rgba8[4 * i + 2] / 255.0f, (float)rgba8[4 * i + 3] / 255.0f);
-    HIP_TRY(c->bluenoise_ba.ensure(lut.size()));
-    HIP_TRY(hipMemcpy(c->bluenoise_ba.p, lut.data(), sizeof(float2) * lut.size(), hipMemcpyHostToDevice));
-    c->bluenoise_ready = true;
-    return CAP_OK;
-}
-
-
-// EXT model, next-event rays on the small-scene path: which fan pairs can occlude a segment from a scene point p to a point y of a light
-// triangle?  The fused kernel tests every pair for every such ray (an OR without an early exit, 8.3 of the 31 ms of BASELINE's literal
-// "Lambert+GGX" step, docs/experiments.md (48)); a pair that provably never reports an occlusion is moved behind the count that loop runs to.
-//
-// Rule (in double, over the vertices as uploaded).  A pair is left out iff for BOTH of its triangles, with plane (v0, n):
-//   (i)  every scene vertex lies on one closed side of the plane, at most eps = 2.5e-7 * Dv beyond it (Dv = the largest distance from
-//        v0 to a scene vertex): the plane supports the scene's convex hull to within eps, so p (a convex combination of scene vertices)
-//        is at most eps outside it;
-//   (ii) every vertex of every light triangle is at least delta = 1e-2 * D * Dv inside it, D = the scene's diagonal (numbers in scene
-//        units: the bound is against the contract's ABSOLUTE tmin = 1e-4).
-// Why that is exact under the intersection contract, whose occlusion test is  tmin * det < T < tmax * det  with
-// T = +-(p - v0).n, det = |d.n|, d the unit direction, tmax = 0.999 |y - p|:  in exact arithmetic the segment meets the plane at t* =
-// T / det, and with both ends on the inner side t* <= 0 or t* >= |y - p| + delta / sin(theta) (theta = the angle between d and the plane),
-// never inside (tmin, tmax).  A p that is s <= eps OUTSIDE the plane crosses it on its way in, at t* = s |y - p| / (s + h) with h >= delta
-// the light point's depth: t* <= eps D / delta = 2.5e-5, a quarter of tmin.  (eps was 1e-6 D until the tests built the case: a decal
-// 1e-6 D outside a wall whose Dv is half the room, segments 1.5 Dv long, t* = 1.5e-4 -- inside the interval, where the wall, culled,
-// cannot shadow the decal next to its edge; tests/pair_cull_support.py nee_truth, tests/test_pair_culls_gpu.py N3.)
-// The computed T differs from the exact one by at most ~4 ulp of |p - v0| |n| (a three-term fma chain on a
-// difference that is exact to an ulp; p itself is off its surface by as much): |t_computed - t*| <= 2.4e-7 |p - v0| / sin(theta) --
-// the classic grazing-ray blow-up ((25), (64) of docs/experiments.md closed two earlier culls over it).  (ii) bounds the grazing angle:
-// sin(theta) >= delta / |y - p| >= delta / D, so the error is below 2.4e-7 * Dv * D / delta = 2.4e-5, a quarter of tmin on the near side
-// (t* <= 2.5e-5 stays below tmin) and nothing against the 1e-3 |y - p| + delta between tmax and t* on the far side.  The ceiling of the
-// Cornell box (its lamp hangs 1 cm below it: rays from the ceiling's rim to the lamp graze it) fails (ii) and stays in the list, as
-// does every pair that is not a hull face.  tests: the EXT parity tests run this list; `tools/build_variant.sh neecheck -DCAP_NEE_CHECK`
-// runs both lists on every ray and counts disagreements in CapStats::guard_shade (0 over BASELINE configs[2]'s 8 G next-event rays).
-static int ensure_positions_host(CapContext* c);
-// the build's (and the refit's) view of the context's scene and tree buffers
-static BvhBuildArgs bvh_args(const CapContext* c)
-{
-    BvhBuildArgs a{};
-    a.positions = c->positions.p, a.normals = c->normals.p, a.texcoords = c->texcoords.p, a.indices = c->indices.p;
-    a.tri_ids = c->tri_ids.p, a.mesh_offsets = c->mesh_offsets.p, a.tri_count = c->tri_count;
-    a.shade_tris = c->shade_tris.p, a.tris_sorted = c->tris_sorted.p, a.nodes = c->nodes.p, a.leaf_tri = c->leaf_tri.p;
-    a.tri_raw = c->tri_raw.p, a.tri_box = c->tri_box.p;
-    a.keys[0] = c->keys0.p, a.keys[1] = c->keys1.p, a.vals[0] = c->vals0.p, a.vals[1] = c->vals1.p;
-    a.hist = c->hist.p, a.parent = c->parent.p, a.flags = c->flags.p, a.bounds = c->bvh_misc.p, a.max_depth = c->bvh_misc.p + 6;
-    return a;
-}
-
-// CapBvhInfo::bounds_lo / hi from the six ordered-uint words k_tri_setup reduced into bvh_misc
-static void set_bounds(CapBvhInfo& bi, const uint32_t misc[6])
-{
-    auto dec = [](uint32_t o) {
-        uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-        float    f;
-        memcpy(&f, &u, 4);
-        return f;
-    };
-    for (int k = 0; k < 3; ++k) bi.bounds_lo[k] = dec(misc[k]), bi.bounds_hi[k] = dec(misc[3 + k]);
-}
-
-// the 8-wide view's child-box padding, kWidePad * max(scene extent, largest |coordinate|) (wide_builder.cpp: its error budget)
-static double wide_pad(const CapBvhInfo& bi)
-{
-    double m = 0.0;
-    for (int k = 0; k < 3; ++k)
-        m = std::max({m, (double)bi.bounds_hi[k] - (double)bi.bounds_lo[k], std::fabs((double)bi.bounds_lo[k]), std::fabs((double)bi.bounds_hi[k])});
-    return (double)kWidePad * std::max(m, 1e-30);
-}
-
-// Exhaustive path (cap_set_traversal): triangles that come in fans (k, k + 1 share v0 and the edge v0->v2, as every
-// triangulated quad of an OBJ face does) are stored as one record, so the kernels compute tvec, q and the shared edge's dot
-// product once for both.  Same per-triangle arithmetic, same results; the pairing only depends on bit-equal vertices.
-// BvhDev::tri_ids_dense: a triangle's id is its position in the pair list.  (No triangles: nothing to walk, not dense.)
-static bool pair_ids_dense(const float* pairs, uint32_t pair_count, uint32_t single_count, uint32_t tri_count)
-{
-    if (!tri_count || single_count || tri_count != 2u * (uint64_t)pair_count) return false;
-    for (uint32_t j = 0; j < pair_count; ++j)
-    {
-        uint32_t id;
-        memcpy(&id, pairs + 20 * (size_t)j + 18, sizeof(id));
-        if (id != 2u * j) return false;
-    }
-    return true;
-}
-int cap_debug_pair_ids_dense(const float* pair_records, uint32_t pair_count, uint32_t single_count, uint32_t tri_count)
-{
-    if (!pair_records && pair_count) return 0;
-    return pair_ids_dense(pair_records, pair_count, single_count, tri_count) ? 1 : 0;
-}
-
-static int upload_fan_records(CapContext* c)
-{
-    const uint32_t n = c->tri_count;
-    c->fan_pair_count = c->fan_single_count = 0;
-    c->tri_ids_dense = 0;
-    if (n && n <= 4096)
-    {
-        std::vector<float> raw(16 * (size_t)n);
-        HIP_TRY(hipMemcpy(raw.data(), c->tri_raw.p, sizeof(float) * raw.size(), hipMemcpyDeviceToHost));
-        std::vector<float> pairs, singles;
-        auto rec = [&](uint32_t k) { return raw.data() + 16 * (size_t)k; };  // v0(3) e1(3) e2(3) n(3) id(1) pad(3)
-        for (uint32_t k = 0; k < n;)
-        {
-            const float* a = rec(k);
-            const float* b = k + 1 < n ? rec(k + 1) : nullptr;
-            const bool   fan = b && memcmp(a, b, 12) == 0 && memcmp(a + 6, b + 3, 12) == 0;  // same v0, e2(k) == e1(k+1)
-            if (fan)
-            {
-                // (v0, e1, e2, e3 = e2 of k+1, nA, nB, id of k, 0)
-                const float r[20] = {a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], b[6], b[7], b[8], a[9], a[10], a[11],
-                                     b[9], b[10], b[11], a[12], 0.0f};
-                pairs.insert(pairs.end(), r, r + 20);
-                k += 2;
-            }
-            else
-            {
-                singles.insert(singles.end(), a, a + 16);
-                k += 1;
-            }
-        }
-        c->fan_pair_count   = (uint32_t)(pairs.size() / 20);
-        c->fan_single_count = (uint32_t)(singles.size() / 16);
-        c->tri_ids_dense    = pair_ids_dense(pairs.data(), c->fan_pair_count, c->fan_single_count, n) ? 1u : 0u;
-        // padded by four records so that an unrolled scalar load past the end stays inside the allocation
-        pairs.resize(pairs.size() + 80, 0.0f), singles.resize(singles.size() + 64, 0.0f);
-        c->fan_pairs_host   = pairs;
-        HIP_TRY(c->fan_pairs.ensure(pairs.size() / 4));
-        HIP_TRY(c->fan_singles.ensure(singles.size() / 4));
-        HIP_TRY(hipMemcpy(c->fan_pairs.p, pairs.data(), sizeof(float) * pairs.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->fan_singles.p, singles.data(), sizeof(float) * singles.size(), hipMemcpyHostToDevice));
-    }
-    if (c->fan_pair_count == 0) c->fan_pairs_host.clear();
-    return CAP_OK;
-}
-
-static int update_nee_pairs(CapContext* c)
-{
-    c->fan_pair_nee_count = c->fan_pair_count;
-    c->fan_pairs_nee.release();
-    const uint32_t np = c->fan_pair_count;
-    if (!np || !c->materials_ready || c->light_tris_host.empty() || c->fan_pairs_host.size() < 20 * (size_t)np || c->sw.on(SW_NO_NEE_PAIR_CULL)) return CAP_OK;
-    if (const int rc = ensure_positions_host(c)) return rc;
-    const size_t nv = c->positions_host.size() / 3;
-    if (!nv) return CAP_OK;
-    auto P = [&](size_t i, int k) { return (double)c->positions_host[3 * i + k]; };
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (size_t i = 0; i < nv; ++i)
-        for (int k = 0; k < 3; ++k) lo[k] = std::min(lo[k], P(i, k)), hi[k] = std::max(hi[k], P(i, k));
-    const double D = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
-    if (!(D > 0.0)) return CAP_OK;
-    // the light triangles' vertices (global triangle id -> mesh -> indices, as cap_materials_upload walks them)
-    std::vector<double> lv;
-    {
-        uint32_t g = 0;
-        size_t   li = 0;
-        for (uint32_t m = 0; m < c->mesh_count && li < c->light_tris_host.size(); ++m)
-        {
-            const CapMeshDesc& d = c->meshes_host[m];
-            for (uint32_t k = 0; k + 2 < d.index_count + 0u && li < c->light_tris_host.size(); k += 3, ++g)
-            {
-                if (c->light_tris_host[li] != g) continue;
-                ++li;
-                for (int j = 0; j < 3; ++j)
-                {
-                    const uint32_t vi = d.first_vertex_offset + c->indices_host[d.first_index_offset + k + j];
-                    for (int x = 0; x < 3; ++x) lv.push_back(P(vi, x));
-                }
-            }
-        }
-        if (li != c->light_tris_host.size()) return CAP_OK;  // (cannot happen: the ids come from the same walk) -- keep every pair
-    }
-    std::vector<uint8_t> skip(np, 0);
-    uint32_t             n_skip = 0;
-    for (uint32_t k = 0; k < np; ++k)
-    {
-        const float* r  = c->fan_pairs_host.data() + 20 * (size_t)k;
-        const double v0[3] = {r[0], r[1], r[2]};
-        bool         ok = true;
-        for (int t = 0; t < 2 && ok; ++t)
-        {
-            const double n[3] = {r[12 + 3 * t], r[13 + 3 * t], r[14 + 3 * t]};
-            const double nl   = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-            if (!(nl > 0.0))
-            {
-                ok = false;
-                break;
-            }
-            double smin = 0.0, smax = 0.0, dv = 0.0;
-            for (size_t i = 0; i < nv; ++i)
-            {
-                const double e[3] = {P(i, 0) - v0[0], P(i, 1) - v0[1], P(i, 2) - v0[2]};
-                const double sd   = (e[0] * n[0] + e[1] * n[1] + e[2] * n[2]) / nl;
-                smin = std::min(smin, sd), smax = std::max(smax, sd);
-                dv   = std::max(dv, std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]));
-            }
-            const double tol = 2.5e-7 * dv;  // (i): t* of a point this far outside stays below tmin / 4, see above
-            double       sign;
-            if (smax <= tol)
-                sign = -1.0;  // the scene lies on the negative side
-            else if (smin >= -tol)
-                sign = 1.0;
-            else
-            {
-                ok = false;
-                break;
-            }
-            const double delta = 1e-2 * D * dv;
-            for (size_t i = 0; i + 2 < lv.size() && ok; i += 3)
-            {
-                const double sd = ((lv[i] - v0[0]) * n[0] + (lv[i + 1] - v0[1]) * n[1] + (lv[i + 2] - v0[2]) * n[2]) / nl;
-                if (!(sign * sd >= delta)) ok = false;
-            }
-        }
-        skip[k] = ok ? 1 : 0;
-        n_skip += ok ? 1u : 0u;
-    }
-    if (!n_skip) return CAP_OK;
-    std::vector<float> list;
-    list.reserve(c->fan_pairs_host.size());
-    for (int pass = 0; pass < 2; ++pass)
-        for (uint32_t k = 0; k < np; ++k)
-            if ((int)skip[k] == pass) list.insert(list.end(), c->fan_pairs_host.begin() + 20 * (size_t)k, c->fan_pairs_host.begin() + 20 * (size_t)(k + 1));
-    list.resize(c->fan_pairs_host.size(), 0.0f);  // the same zero padding records behind the list
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(c->fan_pairs_nee.ensure(list.size() / 4));
-    HIP_TRY(hipMemcpy(c->fan_pairs_nee.p, list.data(), sizeof(float) * list.size(), hipMemcpyHostToDevice));
-    c->fan_pair_nee_count = np - n_skip;
-    return CAP_OK;
-}
-
-// positions_host after a device-side vertex update: read back once, and only when the light table or the next-event pair list needs it
-// (a large scene without lights does not pay a device-to-host copy per refit)
-static int ensure_positions_host(CapContext* c)
-{
-    if (!c->positions_host_stale) return CAP_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->positions_host.resize(3 * (size_t)c->vertex_count);
-    if (c->vertex_count)
-        HIP_TRY(hipMemcpy(c->positions_host.data(), c->positions.p, sizeof(float) * c->positions_host.size(), hipMemcpyDeviceToHost));
-    c->positions_host_stale = false;
-    return CAP_OK;
-}
-
-// Light table of the EXT model: emissive triangles in global triangle order with float prefix sums of their areas
-// (area = |e1 x e2| / 2 with the arithmetic of cap_math.h, so the table is the one the oracle builds).  From materials_host and the
-// current vertices: cap_materials_upload and cap_bvh_refit.
-static int upload_light_table(CapContext* c)
-{
-    const CapMaterial* materials = c->materials_host.data();
-    bool               any = false;
-    for (uint32_t m = 0; m < c->mesh_count; ++m) any = any || materials[m].ke[0] > 0.0f || materials[m].ke[1] > 0.0f || materials[m].ke[2] > 0.0f;
-    if (any)
-        if (const int rc = ensure_positions_host(c)) return rc;
-    std::vector<uint32_t> light_tris;
-    std::vector<float>    light_cdf;
-    float                 area = 0.0f;
-    uint32_t              g    = 0;
-    for (uint32_t m = 0; m < c->mesh_count; ++m)
-    {
-        const CapMeshDesc& d  = c->meshes_host[m];
-        const CapMaterial& mt = materials[m];
-        const bool         emissive = mt.ke[0] > 0.0f || mt.ke[1] > 0.0f || mt.ke[2] > 0.0f;
-        for (uint32_t k = 0; k + 2 < d.index_count; k += 3, ++g)
-        {
-            if (!emissive) continue;
-            v3 p[3];
-            for (int j = 0; j < 3; ++j)
-            {
-                const uint32_t vi = d.first_vertex_offset + c->indices_host[d.first_index_offset + k + j];
-                p[j]              = mk3(c->positions_host[3 * vi], c->positions_host[3 * vi + 1], c->positions_host[3 * vi + 2]);
-            }
-            area = area + 0.5f * length3(cross3(p[1] - p[0], p[2] - p[0]));
-            light_tris.push_back(g);
-            light_cdf.push_back(area);
-        }
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(c->light_tris.ensure(light_tris.size()));
-    HIP_TRY(c->light_cdf.ensure(light_cdf.size()));
-    if (!light_tris.empty())
-    {
-        HIP_TRY(hipMemcpy(c->light_tris.p, light_tris.data(), sizeof(uint32_t) * light_tris.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->light_cdf.p, light_cdf.data(), sizeof(float) * light_cdf.size(), hipMemcpyHostToDevice));
-    }
-    c->light_count     = (uint32_t)light_tris.size();
-    c->light_area      = area;
-    c->light_tris_host = light_tris;
-    return CAP_OK;
-}
-
-int cap_materials_upload(CapContext* c, const CapMaterial* materials, uint32_t mesh_count)
-{
-    if (!c || (!materials && mesh_count)) return fail(CAP_ERR_INVALID_ARG, "cap_materials_upload: NULL argument");
-    if (!c->scene_ready || mesh_count != c->mesh_count) return fail(CAP_ERR_STATE, "cap_materials_upload: expected %u materials (one per mesh)", c->mesh_count);
-    c->materials_host.assign(materials, materials + mesh_count);
-    c->materials_ready = false;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(c->materials.ensure(mesh_count));
-    if (mesh_count) HIP_TRY(hipMemcpy(c->materials.p, materials, sizeof(CapMaterial) * mesh_count, hipMemcpyHostToDevice));
-    if (const int rc = upload_light_table(c)) return rc;
-    c->materials_ready = true;
-    if (c->bvh_ready && !c->bvh_stale) return update_nee_pairs(c);  // (a stale tree gets its list from cap_bvh_refit / cap_bvh_build)
-    return CAP_OK;
-}
-
-// The object box of k_instance_setup: every point the triangle test can report lies in a leaf box, the triangle's box padded by
-// 1e-5 max(1, |coordinate|) (bvh.hip k_refit); twice that around the bounds, in double
-static InstObject object_box(const float lo3[3], const float hi3[3], int32_t root)
-{
-    InstObject o{};
-    for (int k = 0; k < 3; ++k)
-    {
-        const double lo = lo3[k], hi = hi3[k];
-        const double pad = 2e-5 * std::max(1.0, std::max(std::fabs(lo), std::fabs(hi)));
-        o.blo[k] = lo - pad, o.bhi[k] = hi + pad;
-    }
-    o.root = root;
-    return o;
-}
-
-// The builder cap_bvh_build takes for n triangles under the context's mode; for an object, the host builder is replaced by its
-// device counterpart (include/capsaicin_hip.h cap_objects_set)
-static uint32_t object_builder(const CapContext* c, uint32_t n)
-{
-    const uint32_t mode = c->bvh_build_mode;
-    if (n >= 2 && (mode == CAP_BVH_BUILD_SAH || mode == CAP_BVH_BUILD_SAH_DEVICE ||
-                   (mode == CAP_BVH_BUILD_AUTO && n >= (uint32_t)c->sw.get(SW_AUTO_SAH_TRIANGLES, kAutoSahTriangles))))
-        return CAP_BVH_BUILD_SAH_DEVICE;
-    if (n >= 2 && (mode == CAP_BVH_BUILD_PLOC || (mode == CAP_BVH_BUILD_AUTO && n > kExhaustiveMax))) return CAP_BVH_BUILD_PLOC;
-    return CAP_BVH_BUILD_LBVH;
-}
-
-// The forest of the installed object table from the current vertices: what cap_objects_set, cap_bvh_build and cap_bvh_refit share.
-// Each object's tree is built by the scene's builders on the object's triangle range (offset pointers; the scene's build scratch,
-// which no kept structure lives in, and the forest's own tri_raw / tri_box / leaf_tri so that the scene's stay as they are) straight
-// into its place in the pools, then relocated in place (instance.hip).  The shading records the triangle setup rewrites get the
-// values they hold.  Waits for the stream: depths and bounds are read back.  Nothing when no table is installed; a failure drops it.
-static int objects_rebuild(CapContext* c, const char* what)
-{
-    const uint32_t count = c->obj_count;
-    if (count == 0) return CAP_OK;
-    c->obj_count = 0;  // (until the forest stands)
-    uint32_t max_n = 0;
-    for (const CapObjectInfo& o : c->obj_info) max_n = std::max(max_n, o.triangle_count);
-    const int radius = (int)c->sw.get(SW_PLOC_RADIUS, 16), leaf = (int)c->sw.get(SW_SAHDEV_LEAF, 32);
-    DevBuf<uint32_t> sahdev;  // the surface-area builder's scratch, of no use after the build
-    for (uint32_t k = 0; k < count; ++k)
-    {
-        CapObjectInfo& o = c->obj_info[k];
-        const uint32_t n = o.triangle_count, first = o.first_triangle;
-        o.builder        = object_builder(c, n);
-        BvhBuildArgs a   = bvh_args(c);
-        a.tri_ids = c->tri_ids.p + first, a.tri_count = n;
-        a.shade_tris  = c->shade_tris.p + kShadeRec * (size_t)first;
-        a.tris_sorted = c->forest_tris.p + 4 * (size_t)c->obj_rec_base[k], a.nodes = c->forest_nodes.p + 4 * (size_t)c->obj_node_base[k];
-        a.leaf_tri = c->obj_leaf_tri.p, a.tri_raw = c->obj_tri_raw.p, a.tri_box = c->obj_tri_box.p;
-        a.bounds = c->obj_misc.p + 8 * (size_t)k, a.max_depth = a.bounds + 6;
-        int rc = 0;
-        if (o.builder == CAP_BVH_BUILD_LBVH)
-            launch_bvh_build(c->stream, a);
-        else
-        {
-            HIP_TRY(c->ploc_boxes.ensure(4 * (size_t)max_n));
-            HIP_TRY(c->ploc_ints.ensure(3 * (size_t)max_n + 4));
-            const PlocScratch ps{c->ploc_boxes.p, c->ploc_ints.p};
-            if (o.builder == CAP_BVH_BUILD_SAH_DEVICE)
-            {
-                HIP_TRY(sahdev.ensure(bvh_sah_device_scratch_words(max_n)));
-                rc = launch_bvh_build_sah_device(c->stream, a, ps, sahdev.p, (uint32_t)radius, (uint32_t)(leaf < 1 ? 1 : leaf));
-            }
-            else
-                rc = launch_bvh_build_ploc(c->stream, a, ps, (uint32_t)radius);
-        }
-        if (rc != 0) return fail(CAP_ERR_HIP, "%s: device build of object %u failed (%d)", what, k, rc);
-        launch_forest_relocate(c->stream, ForestRelocArgs{a.nodes, a.tris_sorted, n, c->obj_node_base[k], c->obj_rec_base[k], first});
-        HIP_TRY(hipGetLastError());
-    }
-    std::vector<uint32_t> misc(8 * (size_t)count);
-    HIP_TRY(hipMemcpyAsync(misc.data(), c->obj_misc.p, sizeof(uint32_t) * misc.size(), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    std::vector<InstObject> table(count);
-    uint32_t depth = 0;
-    for (uint32_t k = 0; k < count; ++k)
-    {
-        CapObjectInfo& o = c->obj_info[k];
-        CapBvhInfo     b{};
-        set_bounds(b, misc.data() + 8 * (size_t)k);
-        for (int j = 0; j < 3; ++j) o.bounds_lo[j] = b.bounds_lo[j], o.bounds_hi[j] = b.bounds_hi[j];
-        o.max_depth = misc[8 * (size_t)k + 6];
-        depth       = std::max(depth, o.max_depth);
-        // a one-triangle object has no node: its root is the leaf code of its record
-        table[k] = object_box(o.bounds_lo, o.bounds_hi, o.triangle_count >= 2 ? (int32_t)c->obj_node_base[k] : (int32_t)~c->obj_rec_base[k]);
-    }
-    if (depth > 64) return fail(CAP_ERR_UNSUPPORTED, "%s: object tree depth %u exceeds the 64-entry traversal stack", what, depth);
-    HIP_TRY(hipMemcpy(c->obj_table.p, table.data(), sizeof(InstObject) * count, hipMemcpyHostToDevice));
-    c->obj_count = count, c->obj_max_depth = depth;
-    return CAP_OK;
-}
-
-// World boxes and top-level tree of the installed instance table from the kept descriptors and the current bounds: what
-// cap_instances_set, cap_bvh_build and cap_bvh_refit share.  Enqueues on the context stream; nothing when no table is installed.
-static int instances_rebuild(CapContext* c)
-{
-    const uint32_t n = c->inst_count;
-    if (n == 0) return CAP_OK;
-    InstanceBuildArgs a{};
-    a.descs = reinterpret_cast<const float*>(c->inst_desc.p), a.n = n;
-    if (c->obj_count)
-        a.objects = c->obj_table.p, a.n_objects = c->obj_count;
-    else
-    {
-        // no object table: the one object is the scene, its tree the scene's
-        c->scene_object_host = object_box(c->bvh_info.bounds_lo, c->bvh_info.bounds_hi, c->tri_count >= 2 ? 0 : ~0);
-        HIP_TRY(c->scene_object.ensure(1));
-        HIP_TRY(hipMemcpyAsync(c->scene_object.p, &c->scene_object_host, sizeof(InstObject), hipMemcpyHostToDevice, c->stream));
-        a.objects = c->scene_object.p, a.n_objects = 1;
-    }
-    a.object_index = c->inst_obj_on ? c->inst_obj.p : nullptr;
-    a.rec = c->inst_rec.p, a.box = c->inst_box.p, a.tlas = c->inst_tlas.p;
-    a.keys[0] = c->inst_keys[0].p, a.keys[1] = c->inst_keys[1].p, a.vals[0] = c->inst_vals[0].p, a.vals[1] = c->inst_vals[1].p;
-    a.hist = c->inst_hist.p, a.scan = c->inst_scan.p, a.misc = c->inst_misc.p;
-    launch_instances_build(c->stream, a);
-    HIP_TRY(hipGetLastError());
-    return CAP_OK;
-}
-
-int cap_bvh_build(CapContext* c)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_build: ctx is NULL");
-    if (!c->scene_ready) return fail(CAP_ERR_STATE, "cap_bvh_build: no scene uploaded");
-    HIP_TRY(hipSetDevice(c->device));
-    const uint32_t n = c->tri_count;
-    HIP_TRY(c->shade_tris.ensure(kShadeRec * (size_t)n));
-    // + 4 zero records: the exhaustive kernels test triangles in pairs and fetch one pair ahead (cap_exhaustive.h); a zero record
-    // has det == 0 and is never hit
-    HIP_TRY(c->tris_sorted.ensure(4 * ((size_t)n + 4)));
-    HIP_TRY(hipMemsetAsync(c->tris_sorted.p, 0, sizeof(float4) * 4 * ((size_t)n + 4), c->stream));
-    HIP_TRY(c->tri_raw.ensure(4 * (size_t)n));
-    HIP_TRY(c->tri_box.ensure(2 * (size_t)n));
-    HIP_TRY(c->nodes.ensure(4 * (size_t)(n > 1 ? n - 1 : 1)));
-    HIP_TRY(c->lane[0].stack_spill.ensure((size_t)c->cu_count * 8 * kBlock * kSpillEntries));  // up to 8 workgroups per CU
-    HIP_TRY(c->leaf_tri.ensure(n));
-    HIP_TRY(c->keys0.ensure(n));
-    HIP_TRY(c->keys1.ensure(n));
-    HIP_TRY(c->vals0.ensure(n));
-    HIP_TRY(c->vals1.ensure(n));
-    HIP_TRY(c->hist.ensure(256 * bvh_radix_blocks(n)));
-    HIP_TRY(c->parent.ensure(2 * (size_t)n));
-    HIP_TRY(c->flags.ensure(n));
-    HIP_TRY(c->bvh_misc.ensure(8));
-    const BvhBuildArgs a = bvh_args(c);
-    // AUTO: scenes the exhaustive kernels handle need no tree quality (Morton hierarchy); everything else gets the clustering
-    // build -- on the device like the driver build it replaces (blas_system.cpp:42-65), within 1 % of the host SAH tree's trace
-    // times (builders table) at 1 / 40 of its build time.  The host SAH build stays available by name.
-    const bool sah  = n >= 2 && c->bvh_build_mode == CAP_BVH_BUILD_SAH;
-    // ... and from kAutoSahTriangles on the surface-area splits on top of it (round 6): host-SAH quality (expected node visits 44.6 against
-    // 44.4 and the clustering's 47.6 on the 262 k hall) for 10 ms at 262 k and 0.2 s at 16.8 M triangles, built once like the reference's
-    // PREFER_FAST_TRACE structures (blas_system.cpp:44); below, a build is a few dozen launches whatever it holds and the trees do not differ.
-    const bool sahdev = n >= 2 && (c->bvh_build_mode == CAP_BVH_BUILD_SAH_DEVICE || (c->bvh_build_mode == CAP_BVH_BUILD_AUTO && n >= (uint32_t)c->sw.get(SW_AUTO_SAH_TRIANGLES, kAutoSahTriangles)));
-    const bool ploc = n >= 2 && !sahdev && (c->bvh_build_mode == CAP_BVH_BUILD_PLOC || (c->bvh_build_mode == CAP_BVH_BUILD_AUTO && n > kExhaustiveMax));
-    const auto wall0 = std::chrono::steady_clock::now();
-    uint32_t   host_depth = 0;
-    std::vector<float> bnodes_host;  // the binary tree on the host, for the collapse into the compressed 8-wide view
-    if (sah)
-    {
-        launch_bvh_setup(c->stream, a);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        std::vector<float> boxes(8 * (size_t)n);
-        HIP_TRY(hipMemcpy(boxes.data(), c->tri_box.p, sizeof(float) * boxes.size(), hipMemcpyDeviceToHost));
-        HostTree tree;
-        build_sah_tree(boxes.data(), n, kLeafMax, kLeafCountShift, tree);
-        host_depth = tree.depth;
-        HIP_TRY(hipMemcpy(c->nodes.p, tree.nodes.data(), sizeof(float) * tree.nodes.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->leaf_tri.p, tree.order.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-        launch_bvh_finish_host(c->stream, a);
-        bnodes_host.swap(tree.nodes);
-    }
-    else if (sahdev)
-    {
-        // surface-area splits from the root down, the clustering inside the finished segments: the PREFER_FAST_TRACE tree the reference
-        // asks its driver for (blas_system.cpp:44), built where the geometry is
-        HIP_TRY(c->ploc_boxes.ensure(4 * (size_t)n));
-        HIP_TRY(c->ploc_ints.ensure(3 * (size_t)n + 4));
-        HIP_TRY(c->sahdev_words.ensure(bvh_sah_device_scratch_words(n)));
-        const int radius = (int)c->sw.get(SW_PLOC_RADIUS, 16), leaf = (int)c->sw.get(SW_SAHDEV_LEAF, 32);  // A/B switches
-        const int rc = launch_bvh_build_sah_device(c->stream, a, PlocScratch{c->ploc_boxes.p, c->ploc_ints.p}, c->sahdev_words.p, (uint32_t)radius,
-                                                   (uint32_t)(leaf < 1 ? 1 : leaf));
-        if (rc != 0) return fail(CAP_ERR_HIP, "cap_bvh_build: device surface-area build failed (%d)", rc);
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->sahdev_words.release();  // 90 B per triangle, of no use after the build
-    }
-    else if (ploc)
-    {
-        HIP_TRY(c->ploc_boxes.ensure(4 * (size_t)n));
-        HIP_TRY(c->ploc_ints.ensure(3 * (size_t)n + 4));
-        const int radius = (int)c->sw.get(SW_PLOC_RADIUS, 16);  // A/B switch
-        const int rc = launch_bvh_build_ploc(c->stream, a, PlocScratch{c->ploc_boxes.p, c->ploc_ints.p}, (uint32_t)radius);
-        if (rc != 0) return fail(CAP_ERR_HIP, "cap_bvh_build: clustering build failed (%d)", rc);
-    }
-    else
-        launch_bvh_build(c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    uint32_t misc[8] = {0};
-    if (n) HIP_TRY(hipMemcpy(misc, c->bvh_misc.p, sizeof(misc), hipMemcpyDeviceToHost));
-    CapBvhInfo& bi    = c->bvh_info;
-    bi                = CapBvhInfo{};
-    bi.triangle_count = n;
-    bi.node_count     = n > 1 ? n - 1 : 0;
-    bi.max_depth      = n ? (sah ? host_depth : misc[6]) : 0;
-    bi.build_ms       = ms;
-    if (n) set_bounds(bi, misc);
-    c->shade_tame = n != 0 && misc[7] == 0;
-    if (bi.max_depth > 64)
-        return fail(CAP_ERR_UNSUPPORTED, "LBVH depth %u exceeds the 64-entry traversal stack", bi.max_depth);
-    bi.stack_entries = bi.max_depth <= 32 ? 32 : 64;
-    // Compressed 8-wide view of the same tree (cap_wide.h) for the extension- and shadow-ray kernels of scenes the exhaustive
-    // kernels do not take: collapsed on the host from the binary nodes (read back when the device built them).
-    c->wide8_nodes = c->wide8_depth = c->wide8_top = 0;
-    c->wide_levels.clear();
-    if (n >= 1)
-    {
-        const auto w0 = std::chrono::steady_clock::now();
-        HIP_TRY(c->tris8.ensure(4 * (size_t)n));
-        HIP_TRY(c->wide_src.ensure(n));
-        size_t   wn = 0;
-        uint32_t wdepth = 0, wtop = 0;
-        const bool host_collapse = c->sw.on(SW_WIDE_HOST_COLLAPSE);  // A/B switch
-        if (!sah && n >= 2 && !host_collapse)
-        {
-            // the device built the binary tree: collapse it there too (bvh.hip k_wide_level), nothing leaves the GPU
-            const uint32_t cap = n / 2u + 16u;  // an inner child stands for >= 4 triangles
-            HIP_TRY(c->nodes8.ensure((kWideNodeStride / 4) * std::max<size_t>((size_t)cap + 1, kWideTopNodes)));
-            HIP_TRY(c->wide_task.ensure(cap));
-            HIP_TRY(c->wide_cnt.ensure(2 * (size_t)cap + 2 * ((size_t)cap / 1024 + 2)));  // per-level bases + the scan's tile sums
-            HIP_TRY(c->wide_alloc.ensure(2));
-            WideCollapseArgs wa{};
-            wa.bnodes = c->nodes.p, wa.count = c->keys1.p, wa.n_tris = n, wa.capacity = cap;
-            wa.pad = wide_pad(bi);
-            wa.task = c->wide_task.p, wa.cnt = c->wide_cnt.p, wa.alloc = c->wide_alloc.p, wa.nodes8 = reinterpret_cast<uint32_t*>(c->nodes8.p), wa.tri_src = c->wide_src.p;
-            uint32_t count = 0;
-            if (launch_wide_collapse(c->stream, wa, &count, &wdepth, &wtop, &c->wide_levels) != 0) return fail(CAP_ERR_HIP, "cap_bvh_build: device collapse into the 8-wide view failed");
-            wn = count;
-        }
-        else
-        {
-            if (n >= 2 && bnodes_host.empty())
-            {
-                bnodes_host.resize(16 * (size_t)(n - 1));
-                HIP_TRY(hipMemcpy(bnodes_host.data(), c->nodes.p, sizeof(float) * bnodes_host.size(), hipMemcpyDeviceToHost));
-            }
-            WideTree wt;
-            build_wide_tree(n >= 2 ? bnodes_host.data() : nullptr, n, bi.bounds_lo, bi.bounds_hi, wt);
-            wn = wt.nodes.size() / kWideNodeWords, wdepth = wt.depth, wtop = wt.top_nodes;
-            c->wide_levels = wt.level_begin;
-            c->wide_levels.push_back((uint32_t)wn);
-            HIP_TRY(c->nodes8.ensure((kWideNodeStride / 4) * std::max<size_t>(wn + 1, kWideTopNodes)));
-            if (wn) HIP_TRY(hipMemcpy2D(c->nodes8.p, sizeof(uint32_t) * kWideNodeStride, wt.nodes.data(), sizeof(uint32_t) * kWideNodeWords,
-                                        sizeof(uint32_t) * kWideNodeWords, wn, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(c->wide_src.p, wt.tri_src.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-        }
-        launch_gather_wide(c->stream, c->wide_src.p, c->tris_sorted.p, n, c->tris8.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->wide8_nodes = (uint32_t)wn, c->wide8_depth = wdepth, c->wide8_top = wtop;
-        c->wide8_ms    = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - w0).count();
-        bi.build_ms += c->wide8_ms;  // the collapse is part of the build
-        if (c->sw.on(SW_TRACE_LAUNCHES))
-            fprintf(stderr, "[cap] wide view: %zu nodes, depth %u, top %u, %.1f ms\n", wn, wdepth, wtop, c->wide8_ms);
-    }
-    if (const int rc = upload_fan_records(c)) return rc;
-    c->bvh_ready          = true;
-    c->bvh_stale          = false;
-    c->visits_built_known = false;  // the first refit measures the boxes this build leaves
-    if (const int rc = update_nee_pairs(c)) return rc;
-    if (const int rc = objects_rebuild(c, "cap_bvh_build"))  // the objects' trees from the same vertices (nothing without a table)
-    {
-        c->inst_count = 0;  // (the instances' objects are gone)
-        return rc;
-    }
-    return instances_rebuild(c);  // (nothing without a table)
-}
-
-int cap_scene_update_vertices(CapContext* c, const float* positions, const float* normals, const float* texcoords, uint32_t flags)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_scene_update_vertices: ctx is NULL");
-    if (!c->scene_ready) return fail(CAP_ERR_STATE, "cap_scene_update_vertices: no scene uploaded");
-    if (flags & ~(uint32_t)CAP_VERTICES_DEVICE) return fail(CAP_ERR_INVALID_ARG, "cap_scene_update_vertices: unknown flags 0x%x", flags);
-    const bool   device = (flags & CAP_VERTICES_DEVICE) != 0;
-    const float* src[3] = {positions, normals, texcoords};
-    const char*  name[3] = {"positions", "normals", "texcoords"};
-    float*       dst[3] = {c->positions.p, c->normals.p, c->texcoords.p};
-    const size_t bytes[3] = {sizeof(float) * 3 * (size_t)c->vertex_count, sizeof(float) * 3 * (size_t)c->vertex_count,
-                             sizeof(float) * 2 * (size_t)c->vertex_count};
-    HIP_TRY(hipSetDevice(c->device));
-    if (device)
-        for (int i = 0; i < 3; ++i)
-        {
-            if (!src[i]) continue;
-            if ((uintptr_t)src[i] & 3u) return fail(CAP_ERR_INVALID_ARG, "cap_scene_update_vertices: %s is not 4-byte aligned", name[i]);
-            hipPointerAttribute_t at{};
-            const hipError_t      e = hipPointerGetAttributes(&at, src[i]);
-            if (e != hipSuccess) (void)hipGetLastError();  // (an unknown pointer is the caller's error, not a sticky one)
-            if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != c->device)
-                return fail(CAP_ERR_INVALID_ARG, "cap_scene_update_vertices: %s is not device memory of device %d", name[i], c->device);
-        }
-    // ordered on the context stream behind everything enqueued (a render's second lane joins it at the end of its call)
-    bool copied = false;
-    for (int i = 0; i < 3; ++i)
-        if (src[i] && bytes[i])
-        {
-            HIP_TRY(hipMemcpyAsync(dst[i], src[i], bytes[i], device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-            copied = true;
-        }
-    if (copied && !device) HIP_TRY(hipStreamSynchronize(c->stream));  // host arrays may go once the call returns
-    if (positions)
-    {
-        if (device)
-            c->positions_host_stale = true;  // read back only if the light table or the next-event list needs it
-        else
-        {
-            c->positions_host.assign(positions, positions + 3 * (size_t)c->vertex_count);
-            c->positions_host_stale = false;
-        }
-    }
-    c->bvh_stale = true;  // normals and uvs too: the shading records hold them
-    return CAP_OK;
-}
-
-int cap_bvh_refit(CapContext* c, CapRefitInfo* out)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_refit: ctx is NULL");
-    if (!c->scene_ready || !c->bvh_ready) return fail(CAP_ERR_STATE, "cap_bvh_refit: no tree built since the last cap_scene_upload");
-    HIP_TRY(hipSetDevice(c->device));
-    const auto         wall0 = std::chrono::steady_clock::now();
-    const uint32_t     n     = c->tri_count;
-    const BvhBuildArgs a     = bvh_args(c);
-    // the tree metric of the build's boxes (first refit after a build only: before they are overwritten), then of the refitted ones
-    const size_t scratch = tree_visits_scratch();
-    HIP_TRY(c->refit_sums.ensure(scratch + 2));
-    double* const visits = c->refit_sums.p + scratch;  // {this refit, the build}
-    if (!c->visits_built_known) launch_tree_visits(c->stream, c->nodes.p, n, c->refit_sums.p, visits + 1);
-    // triangle records, shading records, triangle boxes, scene bounds; binary boxes; records in leaf order
-    launch_refit_binary(c->stream, a);
-    launch_tree_visits(c->stream, c->nodes.p, n, c->refit_sums.p, visits);
-    HIP_TRY(hipGetLastError());
-    // the one read inside the refit: the new scene bounds (the wide view's padding, the render's camera test, the queries' hand-over)
-    CapBvhInfo& bi = c->bvh_info;
-    if (n)
-    {
-        uint32_t misc[8];  // ... and whether the rewritten shading records are tame
-        HIP_TRY(hipMemcpyAsync(misc, c->bvh_misc.p, sizeof(misc), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        set_bounds(bi, misc);
-        c->shade_tame = misc[7] == 0;
-    }
-    // the 8-wide view: records in its leaf order, then its planes bottom-up
-    if (c->wide8_nodes)
-    {
-        launch_gather_wide(c->stream, c->wide_src.p, c->tris_sorted.p, n, c->tris8.p);
-        HIP_TRY(c->wide_boxes.ensure(6 * (size_t)c->wide8_nodes));
-        WideRefitArgs wa{};
-        wa.nodes8 = reinterpret_cast<uint32_t*>(c->nodes8.p), wa.tris8 = c->tris8.p, wa.tri_box = c->tri_box.p, wa.boxes = c->wide_boxes.p;
-        wa.pad = wide_pad(bi), wa.one_triangle = n == 1 ? 1u : 0u;
-        launch_refit_wide(c->stream, wa, c->wide_levels);
-        HIP_TRY(hipGetLastError());
-    }
-    // the small-scene records, the EXT light table and next-event pair list
-    if (const int rc = upload_fan_records(c)) return rc;
-    if (c->materials_ready && c->light_count)
-        if (const int rc = upload_light_table(c)) return rc;
-    if (const int rc = update_nee_pairs(c)) return rc;
-    double v[2] = {1.0, 1.0};
-    if (n >= 2) HIP_TRY(hipMemcpyAsync(v, visits, sizeof(v), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (!c->visits_built_known) c->refit_visits_built = v[1], c->visits_built_known = true;
-    c->bvh_stale = false;
-    if (const int rc = objects_rebuild(c, "cap_bvh_refit"))  // the objects' trees: rebuilt, not refitted (nothing without a table)
-    {
-        c->inst_count = 0;
-        return rc;
-    }
-    if (const int rc = instances_rebuild(c)) return rc;  // world boxes and TLAS from the new bounds (nothing without a table)
-    if (out)
-    {
-        out->ms                         = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-        out->expected_node_visits       = v[0];
-        out->expected_node_visits_built = c->refit_visits_built;
-    }
-    return CAP_OK;
-}
-
-int cap_bvh_info(CapContext* c, CapBvhInfo* out)
-{
-    if (!c || !out) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_info: NULL argument");
-    if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_bvh_info: BVH not built");
-    *out = c->bvh_info;
-    return CAP_OK;
-}
-
-int cap_bvh_readback(CapContext* c, float* nodes, uint32_t* leaf_triangles)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_readback: ctx is NULL");
-    if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_bvh_readback: BVH not built");
-    if (c->bvh_stale) return fail(CAP_ERR_STATE, "cap_bvh_readback: vertices changed; call cap_bvh_refit or cap_bvh_build");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (nodes && c->bvh_info.node_count)
-        HIP_TRY(hipMemcpy(nodes, c->nodes.p, sizeof(float4) * 4 * c->bvh_info.node_count, hipMemcpyDeviceToHost));
-    if (leaf_triangles && c->tri_count)
-        HIP_TRY(hipMemcpy(leaf_triangles, c->leaf_tri.p, sizeof(uint32_t) * c->tri_count, hipMemcpyDeviceToHost));
-    return CAP_OK;
-}
-
-int cap_bvh_wide_readback(CapContext* c, uint32_t* nodes, uint32_t* tri_src, uint32_t* info)
-{
-    if (!c || !info) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_wide_readback: NULL argument");
-    if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_bvh_wide_readback: BVH not built");
-    if (c->bvh_stale) return fail(CAP_ERR_STATE, "cap_bvh_wide_readback: vertices changed; call cap_bvh_refit or cap_bvh_build");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    info[0] = c->wide8_nodes, info[1] = c->wide8_depth, info[2] = c->wide8_top;
-    if (nodes && c->wide8_nodes)
-        HIP_TRY(hipMemcpy2D(nodes, sizeof(uint32_t) * kWideNodeWords, c->nodes8.p, sizeof(uint32_t) * kWideNodeStride, sizeof(uint32_t) * kWideNodeWords,
-                            c->wide8_nodes, hipMemcpyDeviceToHost));
-    if (tri_src && c->tri_count) HIP_TRY(hipMemcpy(tri_src, c->wide_src.p, sizeof(uint32_t) * c->tri_count, hipMemcpyDeviceToHost));
-    return CAP_OK;
 }
 
 int cap_camera_set(CapContext* c, const CapCameraData* camera)
@@ -2393,1095 +1304,4 @@ int cap_assemble_tiles(CapContext* c, const float* device_src, uint32_t shard_co
     HIP_TRY(hipGetLastError());
     return CAP_OK;
 }
-
-// ---- ray queries (query.hip; binary tree: kernels.hip k_query_binary) ----
-namespace
-{
-constexpr uint64_t kQueryRaysPerLaunch = 1ull << 24;  // rays per launch: 32-bit ray indices and chunk counters, a 64-MB hand-over list
-
-// What every query launch shares: the tree view, the launch configuration, the wide view's hand-over bound and the launch tracer.
-struct QueryRun
-{
-    CapContext* c;
-    const char* what;
-    BvhDev      bvh;
-    LaunchCfg   cfg;
-    float       safe;
-    uint64_t    per;  // rays per launch
-    int traced(const char* kernel, uint64_t first) const
-    {
-        HIP_TRY(hipGetLastError());
-        return trace_launch(c, "%s %s rays %llu..", what, kernel, (unsigned long long)first);
-    }
-};
-
-int query_state(CapContext* c, const char* what)
-{
-    if (!c->bvh_ready) return fail(CAP_ERR_STATE, "%s: call cap_bvh_build first", what);
-    if (c->bvh_stale) return fail(CAP_ERR_STATE, "%s: vertices changed; call cap_bvh_refit or cap_bvh_build", what);
-    return CAP_OK;
-}
-
-// [a0, a0 + bytes) and [b0, b0 + bytes_b) share a byte (an empty range shares none)
-bool ranges_overlap(uintptr_t a0, uint64_t a_bytes, uintptr_t b0, uint64_t b_bytes) { return a0 < b0 + b_bytes && b0 < a0 + a_bytes; }
-
-int query_prepare(CapContext* c, const char* what, uint64_t n, QueryRun& run)
-{
-    HIP_TRY(hipSetDevice(c->device));
-    run.c = c, run.what = what;
-    run.bvh          = bvh_dev(c, c->lane[0]);  // (lane 0's spill area: a render's second lane has its own, and the stream orders us behind both)
-    run.bvh.wide8_ok = run.bvh.wide8_ok && query8_stack_matches();
-    run.per          = std::min<uint64_t>(n, kQueryRaysPerLaunch);
-    if (c->query_work.n < 2 * kCounterStride || (run.bvh.wide8_ok && c->query_defer.n < run.per))
-    {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (a grown buffer replaces one an earlier query may still be using)
-        HIP_TRY(c->query_work.ensure(2 * kCounterStride));
-        if (run.bvh.wide8_ok) HIP_TRY(c->query_defer.ensure(run.per));
-    }
-    run.cfg    = LaunchCfg{c->stream, (uint32_t)c->cu_count * 4u, c->bvh_info.stack_entries, (uint32_t)c->cu_count};
-    run.cfg.sw = &c->sw;
-    // box-test error budget of the wide view (wide_builder.cpp, query.hip): M as the build computed it
-    double m = 0.0;
-    for (int k = 0; k < 3; ++k)
-        m = std::max({m, (double)c->bvh_info.bounds_hi[k] - (double)c->bvh_info.bounds_lo[k], std::fabs((double)c->bvh_info.bounds_lo[k]),
-                      std::fabs((double)c->bvh_info.bounds_hi[k])});
-    run.safe = (float)(kQuerySafeScale * m);
-    return CAP_OK;
-}
-
-QueryArgs query_args(const QueryRun& run, const CapRayDesc* rays, uint64_t n, uint64_t done)
-{
-    QueryArgs q{};
-    q.rays  = reinterpret_cast<const float4*>(rays + done);
-    q.n     = (uint32_t)std::min<uint64_t>(run.per, n - done);
-    q.work  = run.c->query_work.p;
-    q.defer = run.c->query_defer.p;
-    q.safe  = run.safe;
-    return q;
-}
-
-// The filter of an _ex call (CapTraceOptions; NULL = the plain call).  on: the call takes the filtered kernels -- it has a cull or
-// first-hit flag, or a mask table is installed (then also through the plain entry points: a mesh with mask 0 is invisible to every
-// query).  With every mask 0xFF no inclusion mask rejects anything and the plain kernels answer.
-struct QueryFilter
-{
-    bool      on = false, first_hit = false;
-    RayFilter f{};
-};
-
-int query_filter(CapContext* c, const char* what, const CapTraceOptions* o, bool multi, QueryFilter& out)
-{
-    static_assert(sizeof(CapTraceOptions) == 16, "CapTraceOptions is four words");
-    const uint32_t flags = o ? o->ray_flags : 0u, mask = o ? o->instance_mask : 0u;
-    const uint32_t known = CAP_RAY_FLAG_ACCEPT_FIRST_HIT | CAP_RAY_FLAG_CULL_BACK_FACING | CAP_RAY_FLAG_CULL_FRONT_FACING;
-    const uint32_t cull  = flags & (CAP_RAY_FLAG_CULL_BACK_FACING | CAP_RAY_FLAG_CULL_FRONT_FACING);
-    if (flags & ~known) return fail(CAP_ERR_INVALID_ARG, "%s: unknown ray_flags 0x%x", what, flags);
-    if (cull == (CAP_RAY_FLAG_CULL_BACK_FACING | CAP_RAY_FLAG_CULL_FRONT_FACING))
-        return fail(CAP_ERR_INVALID_ARG, "%s: CAP_RAY_FLAG_CULL_BACK_FACING and CAP_RAY_FLAG_CULL_FRONT_FACING exclude each other", what);
-    if (multi && (flags & CAP_RAY_FLAG_ACCEPT_FIRST_HIT))
-        return fail(CAP_ERR_INVALID_ARG, "%s: CAP_RAY_FLAG_ACCEPT_FIRST_HIT has no meaning for a multi-hit query", what);
-    if (o && (o->reserved[0] || o->reserved[1])) return fail(CAP_ERR_INVALID_ARG, "%s: options->reserved must be 0", what);
-    if (mask > 0xFFu) return fail(CAP_ERR_INVALID_ARG, "%s: instance_mask 0x%x exceeds 8 bits", what, mask);
-    out.first_hit  = (flags & CAP_RAY_FLAG_ACCEPT_FIRST_HIT) != 0;
-    out.f.cull_and = cull ? 0x80000000u : 0u;
-    out.f.cull_xor = cull == CAP_RAY_FLAG_CULL_FRONT_FACING ? 0x80000000u : 0u;
-    out.f.mask     = mask ? mask : 0xFFu;
-    out.f.tri_mask = c->tri_mask_on ? c->tri_mask.p : nullptr;
-    out.on         = cull || out.first_hit || c->tri_mask_on;
-    return CAP_OK;
-}
-
-int trace_query(CapContext* c, const char* what, const CapRayDesc* rays, uint64_t n, void* out, size_t out_stride, uint32_t flags, bool any,
-                const CapTraceOptions* options = nullptr)
-{
-    static_assert(sizeof(CapRayDesc) == 2 * sizeof(float4) && sizeof(CapHit) == sizeof(float4), "query records are the kernels' float4 records");
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (flags != 0) return fail(CAP_ERR_INVALID_ARG, "%s: flags is reserved and must be 0 (got 0x%x)", what, flags);
-    QueryFilter flt;
-    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
-    const bool       first = flt.first_hit && !any;  // (an occlusion query ends at its first hit anyway)
-    const RayFilter* f     = flt.on ? &flt.f : nullptr;
-    if (const int rc = query_state(c, what)) return rc;
-    if (n == 0) return CAP_OK;
-    if (!rays || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    const uintptr_t r0 = (uintptr_t)rays, o0 = (uintptr_t)out;
-    if ((r0 | o0) & 15u) return fail(CAP_ERR_INVALID_ARG, "%s: rays and output must be 16-byte aligned", what);
-    if (n > (UINTPTR_MAX - r0) / sizeof(CapRayDesc) || n > (UINTPTR_MAX - o0) / out_stride)
-        return fail(CAP_ERR_INVALID_ARG, "%s: %llu rays exceed the address space", what, (unsigned long long)n);
-    if (ranges_overlap(r0, n * sizeof(CapRayDesc), o0, n * out_stride)) return fail(CAP_ERR_INVALID_ARG, "%s: the ray and output ranges overlap", what);
-    QueryRun run;
-    if (const int rc = query_prepare(c, what, n, run)) return rc;
-    for (uint64_t done = 0; done < n; done += run.per)
-    {
-        QueryArgs q = query_args(run, rays, n, done);
-        q.out       = static_cast<uint8_t*>(out) + done * out_stride;
-        if (run.bvh.wide8_ok)
-        {
-            HIP_TRY(hipMemsetAsync(c->query_work.p, 0, sizeof(uint32_t) * 2 * kCounterStride, c->stream));
-            launch_query8(run.cfg, run.bvh, q, any, f, first);
-            if (run.traced(any ? "k_query_any8" : "k_query_closest8", done) != CAP_OK) return CAP_ERR_HIP;
-            if (f)
-                launch_query_binary_filtered(run.cfg, run.bvh, q, *f, any, first, true);
-            else
-                launch_query_binary(run.cfg, run.bvh, q, any, true);
-            if (run.traced(any ? "k_query_binary<any> (handed-over rays)" : "k_query_binary<closest> (handed-over rays)", done) != CAP_OK) return CAP_ERR_HIP;
-        }
-        else
-        {
-            if (f)
-                launch_query_binary_filtered(run.cfg, run.bvh, q, *f, any, first, false);
-            else
-                launch_query_binary(run.cfg, run.bvh, q, any, false);
-            if (run.traced(any ? "k_query_binary<any>" : "k_query_binary<closest>", done) != CAP_OK) return CAP_ERR_HIP;
-        }
-    }
-    return CAP_OK;
-}
-
-// cap_trace_rays_multi: the first k hits of each ray in (t, triangle) order, and / or its hit count (query.hip k_query_multi8,
-// k_query_binary_multi).  Validation and launches as trace_query, with k records per ray: their offsets are 64-bit.
-int trace_multi(CapContext* c, const char* what, const CapRayDesc* rays, uint64_t n, uint32_t k, CapHit* hits, uint32_t* counts, uint32_t flags,
-                const CapTraceOptions* options = nullptr)
-{
-    static_assert(CAP_MULTI_MAX_K == kMultiMaxK, "the header's page limit is the kernels' largest bucket");
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (flags & ~(uint32_t)CAP_MULTI_CONTINUE) return fail(CAP_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
-    QueryFilter flt;
-    if (const int rc = query_filter(c, what, options, true, flt)) return rc;
-    const RayFilter* f = flt.on ? &flt.f : nullptr;
-    if (k > CAP_MULTI_MAX_K) return fail(CAP_ERR_INVALID_ARG, "%s: k = %u exceeds CAP_MULTI_MAX_K (%d); page with CAP_MULTI_CONTINUE", what, k, CAP_MULTI_MAX_K);
-    if (k == 0 && (hits || !counts)) return fail(CAP_ERR_INVALID_ARG, "%s: k = 0 counts only: hits must be NULL and counts given", what);
-    if (k == 0 && (flags & CAP_MULTI_CONTINUE)) return fail(CAP_ERR_INVALID_ARG, "%s: CAP_MULTI_CONTINUE needs k >= 1 (the cursor is slot k - 1)", what);
-    if (const int rc = query_state(c, what)) return rc;
-    if (n == 0) return CAP_OK;
-    if (!rays || (k && !hits)) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    const uintptr_t r0 = (uintptr_t)rays, h0 = (uintptr_t)hits, c0 = (uintptr_t)counts;
-    if (((r0 | h0) & 15u) || (c0 & 3u)) return fail(CAP_ERR_INVALID_ARG, "%s: rays and hits must be 16-byte aligned, counts 4-byte", what);
-    const uint64_t page = (uint64_t)k * sizeof(CapHit);
-    if (n > (UINTPTR_MAX - r0) / sizeof(CapRayDesc) || (k && n > (UINTPTR_MAX - h0) / page) || (counts && n > (UINTPTR_MAX - c0) / sizeof(uint32_t)))
-        return fail(CAP_ERR_INVALID_ARG, "%s: %llu rays x %u records exceed the address space", what, (unsigned long long)n, k);
-    const uint64_t r_bytes = n * sizeof(CapRayDesc), h_bytes = hits ? n * page : 0, c_bytes = counts ? n * sizeof(uint32_t) : 0;
-    if (ranges_overlap(r0, r_bytes, h0, h_bytes) || ranges_overlap(r0, r_bytes, c0, c_bytes) || ranges_overlap(h0, h_bytes, c0, c_bytes))
-        return fail(CAP_ERR_INVALID_ARG, "%s: the ray, hit and count ranges overlap", what);
-    QueryRun run;
-    if (const int rc = query_prepare(c, what, n, run)) return rc;
-    for (uint64_t done = 0; done < n; done += run.per)
-    {
-        MultiArgs m{};
-        m.q      = query_args(run, rays, n, done);
-        m.q.out  = hits ? static_cast<void*>(hits + done * k) : nullptr;
-        m.k      = k;
-        m.counts = counts ? counts + done : nullptr;
-        m.resume = (flags & CAP_MULTI_CONTINUE) ? 1u : 0u;
-        if (run.bvh.wide8_ok)
-        {
-            HIP_TRY(hipMemsetAsync(c->query_work.p, 0, sizeof(uint32_t) * 2 * kCounterStride, c->stream));
-            launch_query8_multi(run.cfg, run.bvh, m, f);
-            if (run.traced("k_query_multi8", done) != CAP_OK) return CAP_ERR_HIP;
-            launch_query_binary_multi(run.cfg, run.bvh, m, true, f);
-            if (run.traced("k_query_binary_multi (handed-over rays)", done) != CAP_OK) return CAP_ERR_HIP;
-        }
-        else
-        {
-            launch_query_binary_multi(run.cfg, run.bvh, m, false, f);
-            if (run.traced("k_query_binary_multi", done) != CAP_OK) return CAP_ERR_HIP;
-        }
-    }
-    return CAP_OK;
-}
-}  // namespace
-
-int cap_trace_rays(CapContext* c, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, uint32_t flags)
-{
-    return trace_query(c, "cap_trace_rays", device_rays, n, device_hits, sizeof(CapHit), flags, false);
-}
-
-int cap_trace_occlusion(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded, uint32_t flags)
-{
-    return trace_query(c, "cap_trace_occlusion", device_rays, n, device_occluded, sizeof(uint32_t), flags, true);
-}
-
-int cap_trace_rays_multi(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits, uint32_t* device_counts,
-                         uint32_t flags)
-{
-    return trace_multi(c, "cap_trace_rays_multi", device_rays, n, k, device_hits, device_counts, flags);
-}
-
-int cap_trace_rays_ex(CapContext* c, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, const CapTraceOptions* options)
-{
-    return trace_query(c, "cap_trace_rays_ex", device_rays, n, device_hits, sizeof(CapHit), 0, false, options);
-}
-
-int cap_trace_occlusion_ex(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded, const CapTraceOptions* options)
-{
-    return trace_query(c, "cap_trace_occlusion_ex", device_rays, n, device_occluded, sizeof(uint32_t), 0, true, options);
-}
-
-int cap_trace_rays_multi_ex(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits, uint32_t* device_counts,
-                            uint32_t multi_flags, const CapTraceOptions* options)
-{
-    return trace_multi(c, "cap_trace_rays_multi_ex", device_rays, n, k, device_hits, device_counts, multi_flags, options);
-}
-
-// ---- instanced ray queries (instance.hip) ----
-namespace
-{
-// `p` is usable as a device array of the context's GPU (what CAP_INSTANCES_DEVICE promises)
-int device_array(CapContext* c, const char* what, const char* name, const void* p)
-{
-    if ((uintptr_t)p & 3u) return fail(CAP_ERR_INVALID_ARG, "%s: %s is not 4-byte aligned", what, name);
-    hipPointerAttribute_t at{};
-    const hipError_t      e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) (void)hipGetLastError();  // (an unknown pointer is the caller's error, not a sticky one)
-    if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != c->device)
-        return fail(CAP_ERR_INVALID_ARG, "%s: %s is not device memory of device %d", what, name, c->device);
-    return CAP_OK;
-}
-
-int instances_set(CapContext* c, const char* what, const CapInstanceDesc* descs, const uint32_t* object_index, uint32_t count, uint32_t flags,
-                  CapInstancesInfo* out)
-{
-    static_assert(sizeof(CapInstanceDesc) == 64, "CapInstanceDesc is 16 words");
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (flags & ~(uint32_t)CAP_INSTANCES_DEVICE) return fail(CAP_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
-    if (count > CAP_INSTANCE_MAX_COUNT) return fail(CAP_ERR_INVALID_ARG, "%s: %u instances exceed CAP_INSTANCE_MAX_COUNT (%u)", what, count, CAP_INSTANCE_MAX_COUNT);
-    if (count && !descs) return fail(CAP_ERR_INVALID_ARG, "%s: descs is NULL", what);
-    const bool device = (flags & CAP_INSTANCES_DEVICE) != 0;
-    if (!device)
-        for (uint32_t i = 0; i < count; ++i)
-            if (descs[i].reserved[0] | descs[i].reserved[1] | descs[i].reserved[2])
-                return fail(CAP_ERR_INVALID_ARG, "%s: descs[%u].reserved must be 0", what, i);
-    if (const int rc = query_state(c, what)) return rc;
-    // host object indices are checked here; device ones in k_instance_setup, where an out-of-range one makes the instance inert
-    const uint32_t n_objects = c->obj_count ? c->obj_count : 1u;
-    if (!device && object_index)
-        for (uint32_t i = 0; i < count; ++i)
-            if (object_index[i] >= n_objects)
-                return fail(CAP_ERR_INVALID_ARG, c->obj_count ? "%s: object_index[%u] = %u, the object table has %u objects"
-                                                              : "%s: object_index[%u] = %u without an object table (%u object: the scene)",
-                            what, i, object_index[i], n_objects);
-    const auto wall0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipSetDevice(c->device));
-    if (device && count)
-    {
-        if (const int rc = device_array(c, what, "descs", descs)) return rc;
-        if (object_index)
-            if (const int rc = device_array(c, what, "object_index", object_index)) return rc;
-    }
-    if (count == 0)
-    {
-        c->inst_count = 0;  // host state: queries already enqueued keep the table they were given
-        if (out) *out = CapInstancesInfo{};
-        return CAP_OK;
-    }
-    uint32_t       off[kTlasMaxLevels], total = 0;
-    const uint32_t top = tlas_layout(count, off, &total);
-    if (c->inst_desc.n < 4 * (size_t)count || c->inst_misc.n < 8 || c->inst_obj.n < count)
-    {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (grown buffers replace ones an earlier query may still be reading)
-        HIP_TRY(c->inst_desc.ensure(4 * (size_t)count));
-        HIP_TRY(c->inst_rec.ensure(4 * (size_t)count));
-        HIP_TRY(c->inst_box.ensure(2 * (size_t)count));
-        HIP_TRY(c->inst_tlas.ensure(2 * ((size_t)count + (size_t)count + 2 * kTlasMaxLevels + 2)));
-        for (int k = 0; k < 2; ++k)
-        {
-            HIP_TRY(c->inst_keys[k].ensure(count));
-            HIP_TRY(c->inst_vals[k].ensure(count));
-        }
-        HIP_TRY(c->inst_hist.ensure(256 * bvh_radix_blocks(count)));
-        HIP_TRY(c->inst_scan.ensure(bvh_radix_scan_words(count) + 1));
-        HIP_TRY(c->inst_misc.ensure(8));
-        HIP_TRY(c->inst_level_off.ensure(kTlasMaxLevels + 1));
-        HIP_TRY(c->inst_obj.ensure(count));
-    }
-    if ((size_t)total * 2 > c->inst_tlas.n) return fail(CAP_ERR_HIP, "%s: top-level tree of %u entries exceeds its buffer", what, total);
-    // ordered on the context stream behind every query enqueued
-    HIP_TRY(hipMemcpyAsync(c->inst_desc.p, descs, sizeof(CapInstanceDesc) * (size_t)count, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                           c->stream));
-    HIP_TRY(hipMemcpyAsync(c->inst_level_off.p, off, sizeof(uint32_t) * (top + 1), hipMemcpyHostToDevice, c->stream));
-    if (object_index)
-        HIP_TRY(hipMemcpyAsync(c->inst_obj.p, object_index, sizeof(uint32_t) * (size_t)count, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                               c->stream));
-    c->inst_obj_on = object_index != nullptr;
-    c->inst_count = count, c->inst_top = top, c->inst_nodes = total - (count + (count & 1u));
-    if (const int rc = instances_rebuild(c))
-    {
-        c->inst_count = 0;
-        return rc;
-    }
-    uint32_t inert = 0;
-    if (out) HIP_TRY(hipMemcpyAsync(&inert, c->inst_misc.p + 6, sizeof(inert), hipMemcpyDeviceToHost, c->stream));
-    if (out || !device) HIP_TRY(hipStreamSynchronize(c->stream));  // host descriptors and `off` may go once the call returns
-    if (out)
-    {
-        out->count = count, out->inert = inert, out->tlas_nodes = c->inst_nodes, out->tlas_depth = top + 1;
-        out->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    }
-    return CAP_OK;
-}
-}  // namespace
-
-int cap_instances_set(CapContext* c, const CapInstanceDesc* descs, uint32_t count, uint32_t flags, CapInstancesInfo* out)
-{
-    return instances_set(c, "cap_instances_set", descs, nullptr, count, flags, out);
-}
-
-int cap_instances_set_ex(CapContext* c, const CapInstanceDesc* descs, const uint32_t* object_index, uint32_t count, uint32_t flags, CapInstancesInfo* out)
-{
-    return instances_set(c, "cap_instances_set_ex", descs, object_index, count, flags, out);
-}
-
-// ---- objects: per-mesh-range trees below the instances (objects_rebuild; instance.hip) ----
-int cap_objects_set(CapContext* c, const CapObjectRange* ranges, uint32_t count, CapObjectsInfo* out)
-{
-    static_assert(sizeof(CapObjectRange) == 8 && sizeof(CapObjectInfo) == 48 && sizeof(CapObjectsInfo) == 24, "the header's object records");
-    const char* what = "cap_objects_set";
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (count > CAP_OBJECT_MAX_COUNT) return fail(CAP_ERR_INVALID_ARG, "%s: %u objects exceed CAP_OBJECT_MAX_COUNT (%u)", what, count, CAP_OBJECT_MAX_COUNT);
-    if (count && !ranges) return fail(CAP_ERR_INVALID_ARG, "%s: ranges is NULL", what);
-    if (const int rc = query_state(c, what)) return rc;
-    const auto wall0 = std::chrono::steady_clock::now();
-    // global triangle ids are assigned mesh by mesh in upload order: a mesh range is a triangle range
-    std::vector<uint64_t> tri_begin(c->mesh_count + 1, 0);
-    for (uint32_t m = 0; m < c->mesh_count; ++m) tri_begin[m + 1] = tri_begin[m] + c->meshes_host[m].index_count / 3;
-    std::vector<CapObjectInfo> info(count);
-    std::vector<uint32_t>      node_base(count), rec_base(count);
-    std::vector<std::pair<uint32_t, uint32_t>> sorted;  // (first mesh, object)
-    uint64_t nodes = 0, recs = 0;
-    for (uint32_t k = 0; k < count; ++k)
-    {
-        const CapObjectRange& r = ranges[k];
-        if (r.mesh_count == 0) return fail(CAP_ERR_INVALID_ARG, "%s: ranges[%u].mesh_count is 0", what, k);
-        if ((uint64_t)r.first_mesh + r.mesh_count > c->mesh_count)
-            return fail(CAP_ERR_INVALID_ARG, "%s: ranges[%u] = meshes %u + %u exceeds the scene's %u", what, k, r.first_mesh, r.mesh_count, c->mesh_count);
-        const uint64_t first = tri_begin[r.first_mesh], n = tri_begin[r.first_mesh + r.mesh_count] - first;
-        if (n == 0) return fail(CAP_ERR_INVALID_ARG, "%s: ranges[%u] holds no triangle", what, k);
-        // the walk's leaf code keeps a record's forest position in kLeafCountShift bits (cap_leaf.h)
-        if (recs + n > kLeafFirstMask) return fail(CAP_ERR_UNSUPPORTED, "%s: forest position %llu of object %u does not fit the traversal-leaf code (limit %u)", what, (unsigned long long)(recs + n), k, kLeafFirstMask);
-        info[k]                = CapObjectInfo{};
-        info[k].first_triangle = (uint32_t)first, info[k].triangle_count = (uint32_t)n, info[k].node_count = (uint32_t)n - 1u;
-        node_base[k] = (uint32_t)nodes, rec_base[k] = (uint32_t)recs;
-        nodes += n - 1, recs += n;
-        sorted.emplace_back(r.first_mesh, k);
-    }
-    std::sort(sorted.begin(), sorted.end());
-    for (size_t j = 1; j < sorted.size(); ++j)
-    {
-        const CapObjectRange& a = ranges[sorted[j - 1].second];
-        if (a.first_mesh + a.mesh_count > sorted[j].first)
-            return fail(CAP_ERR_INVALID_ARG, "%s: ranges[%u] and ranges[%u] overlap", what, sorted[j - 1].second, sorted[j].second);
-    }
-    // from here on the tables change: object indices lose their meaning, so the instance table goes with the old object table
-    c->inst_count = 0;
-    c->obj_count  = 0;
-    if (count == 0)
-    {
-        if (out) *out = CapObjectsInfo{};
-        return CAP_OK;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    uint32_t max_n = 0;
-    for (const CapObjectInfo& o : info) max_n = std::max(max_n, o.triangle_count);
-    if (c->forest_tris.n < 4 * (size_t)recs || c->forest_nodes.n < 4 * (size_t)std::max<uint64_t>(nodes, 1) || c->obj_table.n < count || c->obj_misc.n < 8 * (size_t)count ||
-        c->obj_tri_raw.n < 4 * (size_t)max_n)
-    {
-        HIP_TRY(hipStreamSynchronize(c->stream));  // (grown buffers replace ones an earlier query may still be reading)
-        HIP_TRY(c->forest_tris.ensure(4 * (size_t)recs));
-        HIP_TRY(c->forest_nodes.ensure(4 * (size_t)std::max<uint64_t>(nodes, 1)));
-        HIP_TRY(c->obj_table.ensure(count));
-        HIP_TRY(c->obj_misc.ensure(8 * (size_t)count));
-        HIP_TRY(c->obj_tri_raw.ensure(4 * (size_t)max_n));
-        HIP_TRY(c->obj_tri_box.ensure(2 * (size_t)max_n));
-        HIP_TRY(c->obj_leaf_tri.ensure(max_n));
-    }
-    c->obj_info.swap(info), c->obj_node_base.swap(node_base), c->obj_rec_base.swap(rec_base);
-    c->obj_count = count;
-    if (const int rc = objects_rebuild(c, what)) return rc;
-    if (out)
-    {
-        out->count = count, out->triangles = (uint32_t)recs, out->nodes = (uint32_t)nodes, out->max_depth = c->obj_max_depth;
-        out->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    }
-    return CAP_OK;
-}
-
-int cap_objects_info(CapContext* c, CapObjectInfo* out, uint32_t capacity, uint32_t* count_out)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_objects_info: ctx is NULL");
-    if (capacity && !out) return fail(CAP_ERR_INVALID_ARG, "cap_objects_info: out is NULL with capacity %u", capacity);
-    if (count_out) *count_out = c->obj_count;
-    const uint32_t n = std::min(capacity, c->obj_count);
-    if (n) std::copy(c->obj_info.begin(), c->obj_info.begin() + n, out);
-    return CAP_OK;
-}
-
-int cap_instances_readback(CapContext* c, float* world_to_object, float* world_boxes)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_instances_readback: ctx is NULL");
-    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "cap_instances_readback: no instance table installed");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const size_t n = c->inst_count;
-    std::vector<float> rec(16 * n), box(8 * n);
-    HIP_TRY(hipMemcpy(rec.data(), c->inst_rec.p, sizeof(float) * rec.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(box.data(), c->inst_box.p, sizeof(float) * box.size(), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i)
-    {
-        if (world_to_object) std::copy(rec.begin() + 16 * i, rec.begin() + 16 * i + 12, world_to_object + 12 * i);
-        if (world_boxes)
-            for (int k = 0; k < 3; ++k) world_boxes[6 * i + k] = box[8 * i + k], world_boxes[6 * i + 3 + k] = box[8 * i + 4 + k];
-    }
-    return CAP_OK;
-}
-
-namespace
-{
-int trace_instances(CapContext* c, const char* what, const CapRayDesc* rays, uint64_t n, void* out, size_t out_stride, uint32_t* inst, bool any,
-                    const CapTraceOptions* options)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    QueryFilter flt;
-    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
-    if (const int rc = query_state(c, what)) return rc;
-    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
-    if (n == 0) return CAP_OK;
-    if (!rays || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    const uintptr_t r0 = (uintptr_t)rays, o0 = (uintptr_t)out, i0 = (uintptr_t)inst;
-    if (((r0 | o0) & 15u) || (i0 & 3u)) return fail(CAP_ERR_INVALID_ARG, "%s: rays and output must be 16-byte aligned, instances 4-byte", what);
-    if (n > (UINTPTR_MAX - r0) / sizeof(CapRayDesc) || n > (UINTPTR_MAX - o0) / out_stride || (inst && n > (UINTPTR_MAX - i0) / sizeof(uint32_t)))
-        return fail(CAP_ERR_INVALID_ARG, "%s: %llu rays exceed the address space", what, (unsigned long long)n);
-    const uint64_t r_bytes = n * sizeof(CapRayDesc), o_bytes = n * out_stride, i_bytes = inst ? n * sizeof(uint32_t) : 0;
-    if (ranges_overlap(r0, r_bytes, o0, o_bytes) || ranges_overlap(r0, r_bytes, i0, i_bytes) || ranges_overlap(o0, o_bytes, i0, i_bytes))
-        return fail(CAP_ERR_INVALID_ARG, "%s: the ray and output ranges overlap", what);
-    QueryRun run;
-    if (const int rc = query_prepare(c, what, n, run)) return rc;
-    const TlasDev tl{c->inst_rec.p, c->inst_tlas.p, c->inst_level_off.p, c->inst_top};
-    const int     mode = any ? 2 : flt.first_hit ? 1 : 0;
-    // the pools the instance records' roots refer to: the scene's tree, or with an object table the forest
-    uint32_t depth = c->bvh_info.max_depth;
-    if (c->obj_count)
-    {
-        run.bvh.nodes = c->forest_nodes.p, run.bvh.tris = c->forest_tris.p;
-        depth = c->obj_max_depth, run.cfg.stack_entries = depth <= 32 ? 32 : 64;
-    }
-    for (uint64_t done = 0; done < n; done += run.per)
-    {
-        QueryArgs q = query_args(run, rays, n, done);
-        q.out       = static_cast<uint8_t*>(out) + done * out_stride;
-        launch_query_instances(run.cfg, run.bvh, q, tl, flt.f, mode, inst ? inst + done : nullptr, depth);
-        if (run.traced(any ? "k_query_inst<any>" : "k_query_inst<closest>", done) != CAP_OK) return CAP_ERR_HIP;
-    }
-    return CAP_OK;
-}
-}  // namespace
-
-int cap_trace_instances(CapContext* c, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, uint32_t* device_instances,
-                        const CapTraceOptions* options)
-{
-    return trace_instances(c, "cap_trace_instances", device_rays, n, device_hits, sizeof(CapHit), device_instances, false, options);
-}
-
-int cap_trace_instances_occlusion(CapContext* c, const CapRayDesc* device_rays, uint64_t n, uint32_t* device_occluded, const CapTraceOptions* options)
-{
-    return trace_instances(c, "cap_trace_instances_occlusion", device_rays, n, device_occluded, sizeof(uint32_t), nullptr, true, options);
-}
-
-// cap_trace_instances_multi: the first k pairs of each ray in (t, instance, triangle) order and / or the number of its pairs
-// (instance.hip k_query_inst_multi).  trace_multi's validation with the instance page as a fourth range, trace_instances' state and
-// pools.
-int cap_trace_instances_multi(CapContext* c, const CapRayDesc* rays, uint64_t n, uint32_t k, CapHit* hits, uint32_t* inst, uint32_t* counts,
-                              uint32_t flags, const CapTraceOptions* options)
-{
-    const char* what = "cap_trace_instances_multi";
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (flags & ~(uint32_t)CAP_MULTI_CONTINUE) return fail(CAP_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
-    QueryFilter flt;
-    if (const int rc = query_filter(c, what, options, true, flt)) return rc;
-    if (k > CAP_MULTI_MAX_K) return fail(CAP_ERR_INVALID_ARG, "%s: k = %u exceeds CAP_MULTI_MAX_K (%d); page with CAP_MULTI_CONTINUE", what, k, CAP_MULTI_MAX_K);
-    if (k == 0 && (hits || inst || !counts))
-        return fail(CAP_ERR_INVALID_ARG, "%s: k = 0 counts only: hits and instances must be NULL and counts given", what);
-    if (k == 0 && (flags & CAP_MULTI_CONTINUE)) return fail(CAP_ERR_INVALID_ARG, "%s: CAP_MULTI_CONTINUE needs k >= 1 (the cursor is slot k - 1)", what);
-    if (const int rc = query_state(c, what)) return rc;
-    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
-    if (n == 0) return CAP_OK;
-    if (!rays || (k && (!hits || !inst))) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer (k = %u needs hits and instances)", what, k);
-    const uintptr_t r0 = (uintptr_t)rays, h0 = (uintptr_t)hits, i0 = (uintptr_t)inst, c0 = (uintptr_t)counts;
-    if (((r0 | h0) & 15u) || ((i0 | c0) & 3u))
-        return fail(CAP_ERR_INVALID_ARG, "%s: rays and hits must be 16-byte aligned, instances and counts 4-byte", what);
-    const uint64_t page = (uint64_t)k * sizeof(CapHit), ipage = (uint64_t)k * sizeof(uint32_t);
-    if (n > (UINTPTR_MAX - r0) / sizeof(CapRayDesc) || (k && (n > (UINTPTR_MAX - h0) / page || n > (UINTPTR_MAX - i0) / ipage)) ||
-        (counts && n > (UINTPTR_MAX - c0) / sizeof(uint32_t)))
-        return fail(CAP_ERR_INVALID_ARG, "%s: %llu rays x %u records exceed the address space", what, (unsigned long long)n, k);
-    const uintptr_t base[4]  = {r0, h0, i0, c0};
-    const uint64_t  bytes[4] = {n * sizeof(CapRayDesc), k ? n * page : 0, k ? n * ipage : 0, counts ? n * sizeof(uint32_t) : 0};
-    for (int x = 0; x < 4; ++x)
-        for (int y = x + 1; y < 4; ++y)
-            if (ranges_overlap(base[x], bytes[x], base[y], bytes[y]))
-                return fail(CAP_ERR_INVALID_ARG, "%s: the ray, hit, instance and count ranges overlap", what);
-    QueryRun run;
-    if (const int rc = query_prepare(c, what, n, run)) return rc;
-    const TlasDev tl{c->inst_rec.p, c->inst_tlas.p, c->inst_level_off.p, c->inst_top};
-    // the pools as trace_instances substitutes them; run.bvh.tris_by_id stays the scene's (the write-out reads it)
-    uint32_t depth = c->bvh_info.max_depth;
-    if (c->obj_count)
-    {
-        run.bvh.nodes = c->forest_nodes.p, run.bvh.tris = c->forest_tris.p;
-        depth = c->obj_max_depth, run.cfg.stack_entries = depth <= 32 ? 32 : 64;
-    }
-    for (uint64_t done = 0; done < n; done += run.per)
-    {
-        MultiArgs m{};
-        m.q      = query_args(run, rays, n, done);
-        m.q.out  = hits ? static_cast<void*>(hits + done * k) : nullptr;
-        m.k      = k;
-        m.counts = counts ? counts + done : nullptr;
-        m.resume = (flags & CAP_MULTI_CONTINUE) ? 1u : 0u;
-        launch_query_instances_multi(run.cfg, run.bvh, m, tl, flt.f, inst ? inst + done * k : nullptr, depth);
-        if (run.traced("k_query_inst_multi", done) != CAP_OK) return CAP_ERR_HIP;
-    }
-    return CAP_OK;
-}
-
-void cap_post_settings_default(CapPostSettings* out)
-{
-    if (!out) return;
-    *out = CapPostSettings{1, 1, 1, 128.0f, 3.0f, 3.0f, 64.0f, 2.0f, 3.0f, 0.975f, 0.9f, 0, 0, 0, 0};
-}
-
-int cap_post_reset(CapContext* c)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_post_reset: ctx is NULL");
-    if (!c->screen.width) return fail(CAP_ERR_STATE, "cap_post_reset: resolution not set");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t npix = (size_t)c->screen.width * c->screen.height;
-    DevBuf<float4>* all[] = {&c->post_in[0],   &c->post_in[1],   &c->post_in[2],   &c->post_in[3],  &c->post_ihist[0], &c->post_ihist[1],
-                             &c->post_mhist[0], &c->post_mhist[1], &c->post_chist[0], &c->post_chist[1], &c->post_prev_nd, &c->post_itemp,
-                             &c->post_temp[0],  &c->post_temp[1], &c->post_normals};
-    for (DevBuf<float4>* b : all)
-    {
-        HIP_TRY(b->ensure(npix));
-        HIP_TRY(hipMemsetAsync(b->p, 0, sizeof(float4) * npix, c->stream));  // the reference's textures start cleared
-    }
-    c->post_w = c->screen.width, c->post_h = c->screen.height;
-    c->post_last_dst = -1;
-    return CAP_OK;
-}
-
-// Common tail of cap_post_frame / cap_post_frame_gathered: the chain on post_in[0..3] (row-major, assembled from the ranks'
-// gathered tiles), or -- `tiled` -- on this context's own tile-ordered planes
-struct PostTiledInputs
-{
-    const float4 *indirect, *direct, *albedo, *normal_depth;
-};
-static int run_post_chain(CapContext* c, const CapPostSettings* s, uint32_t frame_count, const CapCameraData* prev_camera,
-                          const PostTiledInputs* tiled = nullptr)
-{
-    PostChainArgs a{};
-    a.settings = PostSettingsDev{s->gather, s->denoise, s->eaw5, s->eaw_normal_sigma, s->eaw_depth_sigma, s->eaw_luma_sigma, s->gather_normal_sigma,
-                                 s->gather_depth_sigma, s->gather_luma_sigma, s->temporal_upscale_feedback, s->taa_feedback, s->lowres_indirect,
-                                 s->disable_variance ? 0 : 1, s->fast_weights, s->output};
-    a.width = c->screen.width, a.height = c->screen.height, a.frame_count = frame_count;
-    a.camera = camera_dev(c->camera), a.prev_camera = camera_dev(*prev_camera);
-    a.indirect = c->post_in[0].p, a.direct = c->post_in[1].p, a.albedo = c->post_in[2].p, a.normal_depth = c->post_in[3].p;
-    if (tiled)
-    {
-        a.tiled = c->screen.tiles_x, a.screen = c->screen;
-        a.tiled_indirect = tiled->indirect, a.tiled_normal_depth = tiled->normal_depth, a.indirect_rowmajor = c->post_in[0].p;
-        a.direct = tiled->direct, a.albedo = tiled->albedo, a.normal_depth = nullptr;
-    }
-    for (int k = 0; k < 2; ++k)
-        a.indirect_history[k] = c->post_ihist[k].p, a.moments_history[k] = c->post_mhist[k].p, a.combined_history[k] = c->post_chist[k].p,
-        a.temp[k] = c->post_temp[k].p;
-    a.prev_normal_depth = c->post_prev_nd.p, a.indirect_temp = c->post_itemp.p, a.normals = c->post_normals.p;
-    // one timestamp per pass boundary, like the reference's AllocateTimestampQueryPair per pass (raytracing_system.cpp:1023-1035)
-    struct Marks
-    {
-        CapContext* c;
-        hipEvent_t  e[6];
-    } marks{c, {}};
-    a.mark_user = &marks;
-    a.mark      = [](void* user, int pass) {
-        Marks* m   = static_cast<Marks*>(user);
-        m->e[pass] = get_event(m->c);
-        (void)hipEventRecord(m->e[pass], m->c->stream);
-    };
-    launch_post_chain(c->stream, a);
-    std::swap(c->post_prev_nd, c->post_normals);  // this frame's decoded normal/depth image is the next frame's previous one
-    c->post_marks.push_back({marks.e[0], marks.e[1], marks.e[2], marks.e[3], marks.e[4], marks.e[5]});
-    HIP_TRY(hipGetLastError());
-    ++c->stats.post_frames;
-    c->post_last_dst = (int)(frame_count % 2);
-    return CAP_OK;
-}
-
-int cap_aov_tile_buffer_floats(CapContext* c, size_t* out_floats)
-{
-    if (!c || !out_floats) return fail(CAP_ERR_INVALID_ARG, "cap_aov_tile_buffer_floats: NULL argument");
-    if (!c->screen.width) return fail(CAP_ERR_STATE, "cap_aov_tile_buffer_floats: resolution not set");
-    *out_floats = (size_t)c->screen.pixels_padded * 4 * 4;
-    return CAP_OK;
-}
-
-int cap_resolve_aov_tiles(CapContext* c, float* device_dst)
-{
-    if (!c || !device_dst) return fail(CAP_ERR_INVALID_ARG, "cap_resolve_aov_tiles: NULL argument");
-    if (!c->aov_valid) return fail(CAP_ERR_STATE, "cap_resolve_aov_tiles: no frame rendered with CAP_RENDER_AOV");
-    HIP_TRY(hipSetDevice(c->device));
-    const uint32_t Ppad  = c->screen.pixels_padded;
-    const AovPlanes aov  = aov_planes(c);
-    const size_t   bytes = sizeof(float4) * (size_t)Ppad;
-    float4*        dst   = reinterpret_cast<float4*>(device_dst);
-    // the four inputs of the chain, in its order (cap_post_frame): indirect, direct, albedo, normal/depth
-    const float4* src[4] = {aov.color, aov.direct, aov.albedo, c->aov_nd.p};
-    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpyAsync(dst + (size_t)k * Ppad, src[k], bytes, hipMemcpyDeviceToDevice, c->stream));
-    return CAP_OK;
-}
-
-int cap_post_frame_gathered(CapContext* c, const CapPostSettings* s, uint32_t frame_count, const CapCameraData* prev_camera,
-                            const float* device_gathered, uint32_t shard_count)
-{
-    if (!c || !s || !prev_camera || !device_gathered) return fail(CAP_ERR_INVALID_ARG, "cap_post_frame_gathered: NULL argument");
-    if (!c->screen.width) return fail(CAP_ERR_STATE, "cap_post_frame_gathered: resolution not set");
-    if (shard_count != c->screen.shard_count)
-        return fail(CAP_ERR_INVALID_ARG, "cap_post_frame_gathered: shard_count %u != context's %u", shard_count, c->screen.shard_count);
-    const bool lowres = s->lowres_indirect != 0;
-    if (lowres && ((c->screen.width | c->screen.height) & 1u))
-        return fail(CAP_ERR_INVALID_ARG, "cap_post_frame_gathered: lowres_indirect needs even width and height (%ux%u)", c->screen.width, c->screen.height);
-    if (!(s->eaw_luma_sigma > 0.0f) || !(s->gather_luma_sigma > 0.0f)) return fail(CAP_ERR_INVALID_ARG, "cap_post_frame_gathered: luma sigmas must be > 0");
-    if (s->output < CAP_OUTPUT_COMBINED || s->output > CAP_OUTPUT_VARIANCE) return fail(CAP_ERR_INVALID_ARG, "cap_post_frame_gathered: output %d is not one of CAP_OUTPUT_*", s->output);
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->post_w != c->screen.width || c->post_h != c->screen.height)
-        if (int e = cap_post_reset(c)) return e;
-    const uint32_t Ppad = c->screen.pixels_padded;
-    LaunchCfg      cfg{c->stream, (uint32_t)c->cu_count * 8u, 32};
-    const float4*  g = reinterpret_cast<const float4*>(device_gathered);
-    for (int k = lowres ? 1 : 0; k < 4; ++k) launch_assemble(cfg, c->screen, g + (size_t)k * Ppad, shard_count, c->post_in[k].p, (size_t)4 * Ppad);
-    if (lowres)
-    {
-        // output_indirect_ is the (W/2, H/2) image of the pixels at this frame's interleave offset, as in cap_post_frame
-        HIP_TRY(c->image_tmp.ensure((size_t)c->screen.width * c->screen.height));
-        launch_assemble(cfg, c->screen, g, shard_count, c->image_tmp.p, (size_t)4 * Ppad);
-        launch_decimate2x(c->stream, c->image_tmp.p, c->screen.width, c->screen.height, (frame_count % 4u) / 2u, (frame_count % 4u) % 2u,
-                          c->post_in[0].p);
-    }
-    return run_post_chain(c, s, frame_count, prev_camera);
-}
-
-int cap_feedback_buffer_floats(CapContext* c, size_t* out_floats)
-{
-    if (!c || !out_floats) return fail(CAP_ERR_INVALID_ARG, "cap_feedback_buffer_floats: NULL argument");
-    if (!c->screen.width) return fail(CAP_ERR_STATE, "cap_feedback_buffer_floats: resolution not set");
-    *out_floats = (size_t)c->screen.width * c->screen.height * 4 * 2;
-    return CAP_OK;
-}
-
-int cap_feedback_export(CapContext* c, float* device_dst)
-{
-    if (!c || !device_dst) return fail(CAP_ERR_INVALID_ARG, "cap_feedback_export: NULL argument");
-    if (c->post_last_dst < 0 || c->post_w != c->screen.width || c->post_h != c->screen.height)
-        return fail(CAP_ERR_STATE, "cap_feedback_export: the chain has not run at this resolution");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t npix = (size_t)c->post_w * c->post_h;
-    float4*      dst  = reinterpret_cast<float4*>(device_dst);
-    HIP_TRY(hipMemcpyAsync(dst, c->post_chist[c->post_last_dst].p, sizeof(float4) * npix, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dst + npix, c->post_prev_nd.p, sizeof(float4) * npix, hipMemcpyDeviceToDevice, c->stream));
-    return CAP_OK;
-}
-
-int cap_feedback_import(CapContext* c, const float* device_src, uint32_t frame_count)
-{
-    if (!c || !device_src) return fail(CAP_ERR_INVALID_ARG, "cap_feedback_import: NULL argument");
-    if (!c->screen.width) return fail(CAP_ERR_STATE, "cap_feedback_import: resolution not set");
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->post_w != c->screen.width || c->post_h != c->screen.height)
-        if (int e = cap_post_reset(c)) return e;
-    const size_t  npix = (size_t)c->post_w * c->post_h;
-    const float4* src  = reinterpret_cast<const float4*>(device_src);
-    // what cap_render(frame_count + 1, CAP_RENDER_GBUFFER_FEEDBACK) reads: combined_history[(frame_count + 2) % 2] and the previous normal/depth
-    HIP_TRY(hipMemcpyAsync(c->post_chist[frame_count % 2].p, src, sizeof(float4) * npix, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->post_prev_nd.p, src + npix, sizeof(float4) * npix, hipMemcpyDeviceToDevice, c->stream));
-    return CAP_OK;
-}
-
-int cap_post_frame(CapContext* c, const CapPostSettings* s, uint32_t frame_count, const CapCameraData* prev_camera)
-{
-    if (!c || !s || !prev_camera) return fail(CAP_ERR_INVALID_ARG, "cap_post_frame: NULL argument");
-    if (!c->screen.width) return fail(CAP_ERR_STATE, "cap_post_frame: resolution not set");
-    if (c->screen.shard_count != 1) return fail(CAP_ERR_UNSUPPORTED, "cap_post_frame: needs an unsharded context (shard_count is %u)", c->screen.shard_count);
-    if (!c->aov_valid) return fail(CAP_ERR_STATE, "cap_post_frame: no frame rendered with CAP_RENDER_AOV");
-    if (!(s->eaw_luma_sigma > 0.0f) || !(s->gather_luma_sigma > 0.0f)) return fail(CAP_ERR_INVALID_ARG, "cap_post_frame: luma sigmas must be > 0");
-    if (s->output < CAP_OUTPUT_COMBINED || s->output > CAP_OUTPUT_VARIANCE) return fail(CAP_ERR_INVALID_ARG, "cap_post_frame: output %d is not one of CAP_OUTPUT_*", s->output);
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->post_w != c->screen.width || c->post_h != c->screen.height)
-        if (int e = cap_post_reset(c)) return e;
-    const AovPlanes aov = aov_planes(c);
-    LaunchCfg       cfg{c->stream, (uint32_t)c->cu_count * 8u, 32};
-    const bool lowres = s->lowres_indirect != 0;
-    if (lowres != c->aov_lowres)
-        return fail(CAP_ERR_STATE, "cap_post_frame: settings.lowres_indirect is %d but the frame was rendered %s CAP_RENDER_LOWRES_INDIRECT",
-                    (int)lowres, c->aov_lowres ? "with" : "without");
-    if (lowres && frame_count != c->aov_frame)
-        return fail(CAP_ERR_INVALID_ARG, "cap_post_frame: frame_count %u is not the rendered frame %u (it selects the 2x2 interleave offset)", frame_count, c->aov_frame);
-    if (lowres)
-    {
-        // output_indirect_ is the (W/2, H/2) image of the pixels at sp_offset (raytracing_system.cpp:499-512)
-        HIP_TRY(c->image_tmp.ensure((size_t)c->screen.width * c->screen.height));
-        launch_untile(cfg, c->screen, aov.color, nullptr, nullptr, 0, c->image_tmp.p);
-        launch_decimate2x(c->stream, c->image_tmp.p, c->screen.width, c->screen.height, (frame_count % 4u) / 2u, (frame_count % 4u) % 2u,
-                          c->post_in[0].p);
-    }
-    // the chain takes the render's tile-ordered planes as they are (PostChainArgs::tiled): its first kernel untiles the indirect
-    // plane and decodes the normals in one pass, Combine reads direct / albedo in tile order
-    PostTiledInputs ti{lowres ? nullptr : aov.color, aov.direct, aov.albedo, c->aov_nd.p};
-    return run_post_chain(c, s, frame_count, prev_camera, &ti);
-}
-
-int cap_post_readback(CapContext* c, float* dst)
-{
-    if (!c || !dst) return fail(CAP_ERR_INVALID_ARG, "cap_post_readback: NULL argument");
-    if (c->post_last_dst < 0) return fail(CAP_ERR_STATE, "cap_post_readback: cap_post_frame has not run");
-    HIP_TRY(hipSetDevice(c->device));
-    if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
-    HIP_TRY(hipMemcpy(dst, c->post_chist[c->post_last_dst].p, sizeof(float4) * (size_t)c->post_w * c->post_h, hipMemcpyDeviceToHost));
-    return CAP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Multi-GPU frame exchange: ONE gather of tile radiance to rank 0 at frame end, over RCCL (xGMI) -- the only data-path
-// collective of the design.  RCCL is loaded on first use (dlopen), so the library has no link-time dependency on
-// it and single-GPU users never touch it; a process that already has an RCCL loaded (e.g. through torch) shares that copy.
-// ------------------------------------------------------------------------------------------------
 }  // extern "C"
-
-#include <dlfcn.h>
-#include <rccl/rccl.h>
-
-namespace
-{
-struct Rccl
-{
-    void* lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*)                                                              = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int)                                       = nullptr;
-    ncclResult_t (*CommInitAll)(ncclComm_t*, int, const int*)                                               = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t)                                                                 = nullptr;
-    ncclResult_t (*CommAbort)(ncclComm_t)                                                                   = nullptr;
-    ncclResult_t (*GroupStart)()                                                                            = nullptr;
-    ncclResult_t (*GroupEnd)()                                                                              = nullptr;
-    ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t)                 = nullptr;
-    ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t)                       = nullptr;
-    ncclResult_t (*Gather)(const void*, void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t)        = nullptr;  // RCCL extension
-    ncclResult_t (*CommGetAsyncError)(ncclComm_t, ncclResult_t*)                                            = nullptr;
-    const char* (*GetErrorString)(ncclResult_t)                                                             = nullptr;
-    std::string  path;
-};
-
-Rccl* rccl()
-{
-    static Rccl r;
-    static bool tried = false;
-    if (!tried)
-    {
-        tried = true;
-        std::vector<std::pair<std::string, int>> names;
-        if (const char* e = getenv("CAP_RCCL_LIBRARY")) names.push_back({e, RTLD_NOW});
-        // a copy the process already has (torch ships its own librccl.so), then the ROCm installation's
-        names.push_back({"librccl.so", RTLD_NOW | RTLD_NOLOAD});
-        names.push_back({"librccl.so.1", RTLD_NOW | RTLD_NOLOAD});
-        names.push_back({"librccl.so.1", RTLD_NOW});
-        names.push_back({"librccl.so", RTLD_NOW});
-        names.push_back({"/opt/rocm/lib/librccl.so.1", RTLD_NOW});
-        for (auto& n : names)
-            if ((r.lib = dlopen(n.first.c_str(), n.second | RTLD_GLOBAL)))
-            {
-                r.path = n.first;
-                break;
-            }
-        if (r.lib)
-        {
-#define CAP_SYM(field, name) r.field = reinterpret_cast<decltype(r.field)>(dlsym(r.lib, name))
-            CAP_SYM(GetUniqueId, "ncclGetUniqueId"), CAP_SYM(CommInitRank, "ncclCommInitRank"), CAP_SYM(CommInitAll, "ncclCommInitAll");
-            CAP_SYM(CommDestroy, "ncclCommDestroy"), CAP_SYM(GroupStart, "ncclGroupStart"), CAP_SYM(GroupEnd, "ncclGroupEnd");
-            CAP_SYM(Send, "ncclSend"), CAP_SYM(Recv, "ncclRecv"), CAP_SYM(Gather, "ncclGather"), CAP_SYM(GetErrorString, "ncclGetErrorString");
-            CAP_SYM(CommGetAsyncError, "ncclCommGetAsyncError"), CAP_SYM(CommAbort, "ncclCommAbort");
-#undef CAP_SYM
-            if (!r.GetUniqueId || !r.CommInitRank || !r.CommInitAll || !r.CommDestroy || !r.GroupStart || !r.GroupEnd || !r.Send || !r.Recv)
-                r.lib = nullptr;
-        }
-    }
-    return r.lib ? &r : nullptr;
-}
-
-#define NCCL_TRY(expr)                                                                                                             \
-    do                                                                                                                             \
-    {                                                                                                                              \
-        ncclResult_t r_ = (expr);                                                                                                  \
-        if (r_ != ncclSuccess)                                                                                                     \
-            return fail(CAP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, R->GetErrorString ? R->GetErrorString(r_) : "rccl error", __FILE__, \
-                        __LINE__);                                                                                                 \
-    } while (0)
-
-// Inside ncclGroupStart .. ncclGroupEnd nothing may return: an early exit would leave the group open and every later RCCL call
-// of the thread would be queued into it (VERDICT r2 missing 3).  The calls are chained through this accumulator, which
-// remembers the first failure and skips the rest; the caller always reaches GroupEnd and reports afterwards.
-struct NcclChain
-{
-    ncclResult_t first = ncclSuccess;
-    const char*  what  = "";
-    void operator()(ncclResult_t r, const char* expr)
-    {
-        if (first == ncclSuccess && r != ncclSuccess) first = r, what = expr;
-    }
-    bool ok() const { return first == ncclSuccess; }
-};
-#define NCCL_CHAIN(chain, expr)                                                                                                    \
-    do                                                                                                                             \
-    {                                                                                                                              \
-        if ((chain).ok()) (chain)((expr), #expr);                                                                                  \
-    } while (0)
-
-// the communicator's asynchronous error state, polled once per frame before the frame's collective is issued (a
-// failed kernel or link of an earlier frame surfaces here instead of as a hang in the next one).
-int comm_poll_async(Rccl* R, CapContext* c, const char* who)
-{
-    if (!c->comm || !R->CommGetAsyncError) return CAP_OK;
-    ncclResult_t async = ncclSuccess;
-    const ncclResult_t r = R->CommGetAsyncError((ncclComm_t)c->comm, &async);
-    if (r != ncclSuccess) return fail(CAP_ERR_HIP, "%s: ncclCommGetAsyncError failed: %s", who, R->GetErrorString ? R->GetErrorString(r) : "rccl error");
-    if (async != ncclSuccess && async != ncclInProgress)
-        return fail(CAP_ERR_HIP, "%s: rank %u's communicator reports an asynchronous error: %s", who, c->comm_rank,
-                    R->GetErrorString ? R->GetErrorString(async) : "rccl error");
-    return CAP_OK;
-}
-
-// this context's tiles (mean radiance, tile order) into its send buffer; the root's receive buffers
-int comm_stage(CapContext* c)
-{
-    if (!c->accum.p) return fail(CAP_ERR_STATE, "cap_comm_gather_frame: nothing rendered");
-    if (c->screen.shard_count != c->comm_size || c->screen.shard_index != c->comm_rank)
-        return fail(CAP_ERR_STATE, "cap_comm_gather_frame: the context renders shard %u of %u but is rank %u of %u", c->screen.shard_index,
-                    c->screen.shard_count, c->comm_rank, c->comm_size);
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t floats = (size_t)c->screen.pixels_padded * 4;
-    HIP_TRY(c->comm_send.ensure(floats));
-    if (c->comm_rank == 0)
-    {
-        HIP_TRY(c->comm_gathered.ensure(floats * c->comm_size));
-        HIP_TRY(c->comm_image.ensure((size_t)c->screen.width * c->screen.height * 4));
-    }
-    LaunchCfg cfg{c->stream, (uint32_t)c->cu_count * 8u, 32};
-    launch_tiles_mean(cfg, c->accum.p, c->screen.pixels_padded, reinterpret_cast<float4*>(c->comm_send.p));
-    HIP_TRY(hipGetLastError());
-    return CAP_OK;
-}
-
-int comm_assemble(CapContext* root)
-{
-    HIP_TRY(hipSetDevice(root->device));
-    LaunchCfg cfg{root->stream, (uint32_t)root->cu_count * 8u, 32};
-    launch_assemble(cfg, root->screen, reinterpret_cast<const float4*>(root->comm_gathered.p), root->comm_size,
-                    reinterpret_cast<float4*>(root->comm_image.p));
-    HIP_TRY(hipGetLastError());
-    return CAP_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int cap_comm_unique_id(uint8_t* id)
-{
-    if (!id) return fail(CAP_ERR_INVALID_ARG, "cap_comm_unique_id: NULL argument");
-    Rccl* R = rccl();
-    if (!R) return fail(CAP_ERR_UNSUPPORTED, "cap_comm_unique_id: no RCCL library could be loaded (librccl.so.1; set CAP_RCCL_LIBRARY)");
-    static_assert(sizeof(ncclUniqueId) == CAP_COMM_ID_BYTES, "id size");
-    ncclUniqueId u;
-    NCCL_TRY(R->GetUniqueId(&u));
-    memcpy(id, &u, sizeof(u));
-    return CAP_OK;
-}
-
-int cap_comm_init_rank(CapContext* c, const uint8_t* id, uint32_t rank, uint32_t nranks)
-{
-    if (!c || !id || !nranks || rank >= nranks) return fail(CAP_ERR_INVALID_ARG, "cap_comm_init_rank: bad argument");
-    if (c->comm || c->comm_local) return fail(CAP_ERR_STATE, "cap_comm_init_rank: the context already has a communicator");
-    Rccl* R = rccl();
-    if (!R) return fail(CAP_ERR_UNSUPPORTED, "cap_comm_init_rank: no RCCL library could be loaded (librccl.so.1; set CAP_RCCL_LIBRARY)");
-    HIP_TRY(hipSetDevice(c->device));
-    ncclUniqueId u;
-    memcpy(&u, id, sizeof(u));
-    ncclComm_t comm = nullptr;
-    NCCL_TRY(R->CommInitRank(&comm, (int)nranks, u, (int)rank));
-    c->comm = comm, c->comm_rank = rank, c->comm_size = nranks;
-    return CAP_OK;
-}
-
-int cap_comm_init_all(CapContext* const* ctxs, uint32_t n)
-{
-    if (!ctxs || !n) return fail(CAP_ERR_INVALID_ARG, "cap_comm_init_all: bad argument");
-    std::vector<int> devs(n);
-    bool             distinct = true;
-    for (uint32_t i = 0; i < n; ++i)
-    {
-        if (!ctxs[i]) return fail(CAP_ERR_INVALID_ARG, "cap_comm_init_all: context %u is NULL", i);
-        if (ctxs[i]->comm || ctxs[i]->comm_local) return fail(CAP_ERR_STATE, "cap_comm_init_all: context %u already has a communicator", i);
-        devs[i] = ctxs[i]->device;
-        for (uint32_t j = 0; j < i; ++j) distinct &= devs[j] != devs[i];
-    }
-    if (n == 1 || !distinct)
-    {
-        // shards of one process on one device (or a single shard): nothing to send over a link, the "gather" is device copies
-        for (uint32_t i = 0; i < n; ++i)
-            if (devs[i] != devs[0]) return fail(CAP_ERR_UNSUPPORTED, "cap_comm_init_all: contexts must sit on pairwise distinct devices or all on one");
-        for (uint32_t i = 0; i < n; ++i) ctxs[i]->comm_local = true, ctxs[i]->comm_rank = i, ctxs[i]->comm_size = n;
-        return CAP_OK;
-    }
-    Rccl* R = rccl();
-    if (!R) return fail(CAP_ERR_UNSUPPORTED, "cap_comm_init_all: no RCCL library could be loaded (librccl.so.1; set CAP_RCCL_LIBRARY)");
-    std::vector<ncclComm_t> comms(n);
-    NCCL_TRY(R->CommInitAll(comms.data(), (int)n, devs.data()));
-    for (uint32_t i = 0; i < n; ++i) ctxs[i]->comm = comms[i], ctxs[i]->comm_rank = i, ctxs[i]->comm_size = n;
-    return CAP_OK;
-}
-
-int cap_comm_gather_frame(CapContext* c)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_comm_gather_frame: ctx is NULL");
-    if (c->comm_local && c->comm_size == 1)
-    {
-        CapContext* one[1] = {c};
-        return cap_comm_gather_frame_all(one, 1);
-    }
-    if (!c->comm) return fail(CAP_ERR_STATE, "cap_comm_gather_frame: cap_comm_init_rank has not run (contexts of cap_comm_init_all use cap_comm_gather_frame_all)");
-    Rccl* R = rccl();
-    if (int e = comm_poll_async(R, c, "cap_comm_gather_frame")) return e;
-    if (int e = comm_stage(c)) return e;
-    const size_t floats = (size_t)c->screen.pixels_padded * 4;
-    if (R->Gather)
-        NCCL_TRY(R->Gather(c->comm_send.p, c->comm_gathered.p, floats, ncclFloat, 0, (ncclComm_t)c->comm, c->stream));
-    else
-    {
-        NcclChain ch;
-        NCCL_TRY(R->GroupStart());
-        NCCL_CHAIN(ch, R->Send(c->comm_send.p, floats, ncclFloat, 0, (ncclComm_t)c->comm, c->stream));
-        if (c->comm_rank == 0)
-            for (uint32_t r = 0; r < c->comm_size; ++r)
-                NCCL_CHAIN(ch, R->Recv(c->comm_gathered.p + r * floats, floats, ncclFloat, (int)r, (ncclComm_t)c->comm, c->stream));
-        const ncclResult_t ge = R->GroupEnd();  // always: the group is closed on the error path too
-        if (!ch.ok()) return fail(CAP_ERR_HIP, "%s failed: %s", ch.what, R->GetErrorString ? R->GetErrorString(ch.first) : "rccl error");
-        NCCL_TRY(ge);
-    }
-    return c->comm_rank == 0 ? comm_assemble(c) : CAP_OK;
-}
-
-int cap_comm_gather_frame_all(CapContext* const* ctxs, uint32_t n)
-{
-    if (!ctxs || !n) return fail(CAP_ERR_INVALID_ARG, "cap_comm_gather_frame_all: bad argument");
-    for (uint32_t i = 0; i < n; ++i)
-    {
-        if (!ctxs[i] || ctxs[i]->comm_size != n || ctxs[i]->comm_rank != i || (!ctxs[i]->comm && !ctxs[i]->comm_local))
-            return fail(CAP_ERR_STATE, "cap_comm_gather_frame_all: pass the contexts of cap_comm_init_all in the same order");
-        if (int e = comm_stage(ctxs[i])) return e;
-    }
-    CapContext*  root   = ctxs[0];
-    const size_t floats = (size_t)root->screen.pixels_padded * 4;
-    if (root->comm_local)
-    {
-        // one device: the root's stream waits for every shard's tiles, then copies them into rank-major order
-        for (uint32_t i = 0; i < n; ++i)
-        {
-            CapContext* c = ctxs[i];
-            if (c != root)
-            {
-                if (!c->comm_event) HIP_TRY(hipEventCreateWithFlags(&c->comm_event, hipEventDisableTiming));
-                HIP_TRY(hipEventRecord(c->comm_event, c->stream));
-                HIP_TRY(hipStreamWaitEvent(root->stream, c->comm_event, 0));
-            }
-            HIP_TRY(hipMemcpyAsync(root->comm_gathered.p + i * floats, c->comm_send.p, sizeof(float) * floats, hipMemcpyDeviceToDevice, root->stream));
-        }
-        // ... and every shard's stream waits for those copies before it may overwrite its send buffer (the next frame's
-        // comm_stage): without this a second gather without a cap_sync in between raced with the root's reads
-        if (n > 1)
-        {
-            if (!root->comm_event) HIP_TRY(hipEventCreateWithFlags(&root->comm_event, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(root->comm_event, root->stream));
-            for (uint32_t i = 1; i < n; ++i) HIP_TRY(hipStreamWaitEvent(ctxs[i]->stream, root->comm_event, 0));
-        }
-        return comm_assemble(root);
-    }
-    Rccl* R = rccl();
-    for (uint32_t i = 0; i < n; ++i)
-        if (int e = comm_poll_async(R, ctxs[i], "cap_comm_gather_frame_all")) return e;
-    NcclChain  ch;
-    hipError_t he = hipSuccess;
-    NCCL_TRY(R->GroupStart());
-    for (uint32_t i = 0; i < n && ch.ok() && he == hipSuccess; ++i)
-    {
-        he = hipSetDevice(ctxs[i]->device);
-        if (he == hipSuccess) NCCL_CHAIN(ch, R->Send(ctxs[i]->comm_send.p, floats, ncclFloat, 0, (ncclComm_t)ctxs[i]->comm, ctxs[i]->stream));
-    }
-    if (he == hipSuccess) he = hipSetDevice(root->device);
-    for (uint32_t r = 0; r < n && he == hipSuccess; ++r)
-        NCCL_CHAIN(ch, R->Recv(root->comm_gathered.p + r * floats, floats, ncclFloat, (int)r, (ncclComm_t)root->comm, root->stream));
-    const ncclResult_t ge = R->GroupEnd();  // always: the group is closed on the error path too
-    HIP_TRY(he);
-    if (!ch.ok()) return fail(CAP_ERR_HIP, "%s failed: %s", ch.what, R->GetErrorString ? R->GetErrorString(ch.first) : "rccl error");
-    NCCL_TRY(ge);
-    return comm_assemble(root);
-}
-
-int cap_comm_image(CapContext* c, float** device_image)
-{
-    if (!c || !device_image) return fail(CAP_ERR_INVALID_ARG, "cap_comm_image: NULL argument");
-    if (c->comm_rank != 0 || !c->comm_image.p) return fail(CAP_ERR_STATE, "cap_comm_image: the assembled frame lives on rank 0 after cap_comm_gather_frame");
-    *device_image = c->comm_image.p;
-    return CAP_OK;
-}
-
-int cap_comm_readback(CapContext* c, float* dst)
-{
-    if (!c || !dst) return fail(CAP_ERR_INVALID_ARG, "cap_comm_readback: NULL argument");
-    if (c->comm_rank != 0 || !c->comm_image.p) return fail(CAP_ERR_STATE, "cap_comm_readback: the assembled frame lives on rank 0 after cap_comm_gather_frame");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(dst, c->comm_image.p, sizeof(float) * 4 * (size_t)c->screen.width * c->screen.height, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return CAP_OK;
-}
-
-int cap_comm_info(CapContext* c, uint32_t* rank, uint32_t* size, uint32_t* uses_rccl)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_comm_info: ctx is NULL");
-    if (rank) *rank = c->comm_rank;
-    if (size) *size = c->comm_size;
-    if (uses_rccl) *uses_rccl = c->comm ? 1u : 0u;
-    return CAP_OK;
-}
-
-int cap_comm_abort(CapContext* c)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_comm_abort: ctx is NULL");
-    if (c->comm)
-    {
-        Rccl* R = rccl();
-        (void)hipSetDevice(c->device);
-        if (R && R->CommAbort)
-            (void)R->CommAbort((ncclComm_t)c->comm);  // no stream synchronisation: the queued collective may never complete
-        c->comm = nullptr;
-    }
-    return cap_comm_destroy(c);
-}
-
-int cap_comm_destroy(CapContext* c)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_comm_destroy: ctx is NULL");
-    if (c->comm)
-    {
-        Rccl* R = rccl();
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-        if (R) (void)R->CommDestroy((ncclComm_t)c->comm);
-    }
-    if (c->comm_event) (void)hipEventDestroy(c->comm_event);
-    c->comm = nullptr, c->comm_event = nullptr, c->comm_local = false, c->comm_rank = c->comm_size = 0;
-    return CAP_OK;
-}
-}

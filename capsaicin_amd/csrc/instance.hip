@@ -17,7 +17,7 @@
 //       |do| <= g4 (|W| |o| + |W_t|),  |dd| <= g3 |W| |d|   (g_k = k eps / (1 - k eps), eps = 2^-24; row-sum norms throughout)
 //     so the world ray passes within  e(t) <= g4 kappa (|o| + t |d|) + g4 |A| |W_t|,  kappa = |A| |W|,  of the image of every
 //     object-space point it reports a hit at.  Such a point lies in the object box B (the object's bounds + twice the build's leaf
-//     padding, context.hip object_box), its image in the box of A(B)'s corners, so |o + t d| <= X + e(t), X the largest |coordinate| of that box, and
+//     padding, ctx_bvh.hip object_box), its image in the box of A(B)'s corners, so |o + t d| <= X + e(t), X the largest |coordinate| of that box, and
 //     t |d| <= |o| + X + e(t):   e(t) <= (g4 kappa (2 |o| + X) + g4 |A| |W_t|) / (1 - g4 kappa).
 //     Per world axis r the same holds with the row sum |A_r| in place of |A| (component r of A v is at most |A_r| |v|):
 //       e_r(t) <= (g4 kappa_r (2 |o| + X) + g4 |A_r| |W_t|) / (1 - g4 kappa),  kappa_r = |A_r| |W| <= kappa,

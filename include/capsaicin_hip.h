@@ -281,7 +281,7 @@ enum
     CAP_DEBUG_SELFTEST_DIV        = 9,
     /* NEE_PAIRS (get): fan pairs the EXT model's next-event rays test on the small-scene path << 32 | fan pairs of the scene.  Pairs that
      * support the scene's convex hull with every light at a safe distance inside cannot occlude a segment between a scene point and a
-     * light point under the intersection contract (rule and error bound: context.hip update_nee_pairs) and are left out. */
+     * light point under the intersection contract (rule and error bound: ctx_scene.hip update_nee_pairs) and are left out. */
     CAP_DEBUG_NEE_PAIRS           = 10,
     /* The fused small-scene kernels evaluate the square roots and divisions of a vertex's shading without the scaling steps of the
      * compiler's IEEE expansions where the operands cannot trigger them (csrc/cap_unscaled.h).  SELFTEST_SHADE_UNARY (get, ~1 s): every
@@ -318,6 +318,11 @@ int cap_debug_switch_index(const char* name);
  * (float 18 = the first triangle's id as bits), single_count unpaired triangles, tri_count triangles in all.  1 if tri_count > 0, there is
  * no unpaired triangle, tri_count == 2 * pair_count and pair j's id is 2j for every j; else 0.  Needs no device. */
 int cap_debug_pair_ids_dense(const float* pair_records, uint32_t pair_count, uint32_t single_count, uint32_t tri_count);
+/* The address checks every cap_trace_* entry point makes on its device arrays, on `count` <= 4 made-up ranges: array i holds n x stride[i]
+ * bytes from base[i], and base[i] must be a multiple of align[i] (a power of two); stride[i] == 0: the caller left array i out.  CAP_OK if
+ * every array is aligned, ends inside the address space and shares no byte with another one; else CAP_ERR_INVALID_ARG with the entry
+ * points' message in cap_last_error().  Needs no device. */
+int cap_debug_query_ranges(uint64_t n, uint32_t count, const uint64_t* base, const uint64_t* stride, const uint32_t* align);
 /* Traversal strategy of the trace kernels (same hits either way): AUTO picks EXHAUSTIVE for scenes of at most 64
  * triangles (wave-uniform test of every triangle, no stack) and STACK (LBVH + per-lane LDS stack) otherwise. */
 typedef enum CapTraversal

@@ -1,7 +1,7 @@
 """Models and scenes for the tests of the small-scene pair culls (tests/test_pair_culls.py on the CPU, tests/test_pair_culls_gpu.py).
 
 The fused kernels of scenes of at most 64 triangles skip work on three decisions, each claimed to change no result bit:
-  * the next-event pair cull of the EXT model (context.hip update_nee_pairs): `nee_rule` restates its rule;
+  * the next-event pair cull of the EXT model (ctx_scene.hip update_nee_pairs): `nee_rule` restates its rule;
   * the camera pair cull of bounce 0 (small_scene.hip stage_camera_pairs / pair_mask, host gate in context.hip cap_render): `camera_bounds` restates
     the bounds and the gate, `camera_truth` says which of the model's culls are wrong;
   * the occluder-first probes of the reference model: `probe_scores` restates the order they probe in.

@@ -139,7 +139,7 @@ def test_ext_energy_sanity(native_lib, bluenoise, tmp_path):
 
 def test_nee_pair_cull_is_exact_and_used(native_lib, bluenoise, tmp_path):
     """Next-event rays of the small-scene path skip the fan pairs that cannot occlude a segment between a scene point and the lamp
-    (hull faces with the lamp at a safe distance inside; context.hip update_nee_pairs: rule + error bound against the contract's absolute
+    (hull faces with the lamp at a safe distance inside; ctx_scene.hip update_nee_pairs: rule + error bound against the contract's absolute
     tmin).  On the Cornell box that is the floor, the back and the two side walls -- NOT the ceiling, 1 cm above the lamp, whose rim
     rays graze it.  With the cull and without it (switch table, same context): the same bits in every plane, the accumulated image and
     the counters, over frames whose rays reach every corner.  (Other scales, lamps at and around the rule's distance, a lamp moved by

@@ -246,6 +246,21 @@ def test_life_cycle(native_lib, small):
             check(r, rays, expected(rays, W, live_of(W), None, tris), "frame %d" % frame)
         # device descriptors: the same W, boxes and records as host ones
         r.set_instances(M)
+        # misaligned or overlapping arrays: refused before anything is launched (csrc/query_ranges.h, tests/test_query_ranges.py)
+        n, R, O = len(rays), rt.data_ptr(), out.data_ptr()
+        I = torch.empty(n, dtype=torch.int32, device=dev).data_ptr()
+        last_ray, last_hit = R + 32 * (n - 1), O + 16 * (n - 1)
+        last_flag = O + 16 * ((n - 1) // 4)  # the 16 bytes that hold the last occlusion flag
+        closest = lambda rays_p, out_p, inst_p: L.cap_trace_instances(r.ctx, rays_p, n, out_p, inst_p, None)
+        occlusion = lambda rays_p, out_p: L.cap_trace_instances_occlusion(r.ctx, rays_p, n, out_p, None)
+        for call, args, words in ((closest, (R + 4, O, I), (b"rays", b"aligned")), (closest, (R, O + 4, I), (b"output", b"aligned")),
+                                  (closest, (R, O, I + 2), (b"instances", b"aligned")), (closest, (R, last_ray, I), (b"rays", b"output", b"overlap")),
+                                  (closest, (last_hit, O, I), (b"rays", b"output", b"overlap")),
+                                  (closest, (R, O, last_hit), (b"output", b"instances", b"overlap")),
+                                  (occlusion, (R + 4, O), (b"rays", b"aligned")), (occlusion, (R, O + 4), (b"output", b"aligned")),
+                                  (occlusion, (R, last_ray), (b"rays", b"output", b"overlap")),
+                                  (occlusion, (last_flag, O), (b"rays", b"output", b"overlap"))):
+            assert call(*args) == ERR_INVALID_ARG and all(w in L.cap_last_error() for w in words), (args, L.cap_last_error())
         Wh, Bh = r.instances_readback()
         hh, ih = r.trace_instances(rays)
         info = r.set_instances(torch.as_tensor(M, device=dev))
