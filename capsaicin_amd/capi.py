@@ -119,6 +119,32 @@ def hit_triangles(hits):
     return hits[:, 3].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
 
 
+class PointDesc(C.Structure):
+    """CapPointDesc (16 bytes): a query point and its search radius (+inf: unbounded)."""
+    _fields_ = [("point", C.c_float * 3), ("radius", C.c_float)]
+
+
+class Closest(C.Structure):
+    """CapClosest (32 bytes): the closest point, its squared distance, the weights of v1 and v2, the triangle (MISS: none within the
+    radius) and the feature the point lies on."""
+    _fields_ = [("point", C.c_float * 3), ("dist2", C.c_float), ("u", C.c_float), ("v", C.c_float), ("triangle", C.c_uint32),
+                ("feature", C.c_uint32)]
+
+
+FEATURE_FACE, FEATURE_EDGE_V0V1, FEATURE_EDGE_V1V2, FEATURE_EDGE_V2V0, FEATURE_V0, FEATURE_V1, FEATURE_V2 = range(7)  # CAP_FEATURE_*
+
+
+def closest_triangles(records):
+    """(triangle ids, features) of (N, 8) closest-point records (columns 6 and 7 hold their bits) as int64; a miss reads MISS.  torch
+    in, torch out."""
+    if isinstance(records, np.ndarray):
+        w = np.ascontiguousarray(records, np.float32).reshape(-1, 8)[:, 6:8].view(np.uint32).astype(np.int64)
+        return w[:, 0], w[:, 1]
+    import torch
+    w = records[:, 6:8].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    return w[:, 0], w[:, 1]
+
+
 OUTPUT_COMBINED, OUTPUT_DIRECT, OUTPUT_INDIRECT, OUTPUT_VARIANCE = range(4)  # SettingsComponent::output, gui_system.h:11-17
 
 
@@ -239,6 +265,7 @@ SYMBOLS = {
     "cap_trace_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_trace_instances_occlusion": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_trace_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
+    "cap_closest_points": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
     "cap_post_settings_default": (None, [C.POINTER(PostSettings)]),
     "cap_post_frame": (_i, [_vp, C.POINTER(PostSettings), _u32, C.POINTER(CameraData)]),
@@ -700,6 +727,44 @@ class Renderer:
             fn = lib().cap_trace_occlusion if any_hit else lib().cap_trace_rays
             _check(fn(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), 0),
                    "cap_trace_occlusion" if any_hit else "cap_trace_rays")
+        if sync:
+            self.sync()
+        if host or host_out is not None:
+            res = out.cpu().numpy()
+            if host_out is not None:
+                host_out[...] = res.reshape(host_out.shape)
+                return host_out
+            return res
+        return out
+
+    # ---- closest-point queries (cap_closest_points) ----
+    def closest_points(self, points, out=None, sync=True, mask=None):
+        """The triangle nearest to each point within its radius.  points: (N, 4) float32 = CapPointDesc rows (x, y, z, radius; +inf:
+        unbounded), a contiguous torch tensor on this context's device or a numpy array (staged through torch; the records come back as
+        numpy).  Returns (N, 8) float32 CapClosest records (closest point, dist2, u, v, triangle and feature bits: closest_triangles()
+        reads those); a miss is (0, 0, 0, radius^2, 0, 0, MISS, 0).  mask= is the instance inclusion mask (set_instance_masks).  sync as
+        trace_rays."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        host = isinstance(points, np.ndarray)
+        if host:
+            points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
+            sync = True  # the result is read back to the host
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
+            raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
+        n = points.shape[0]
+        host_out = None
+        if isinstance(out, np.ndarray):
+            host_out, out = out, None
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (n, 8) or not out.is_contiguous() or out.device != dev:
+            raise CapError("out must be a contiguous (%d, 8) float32 tensor on %s" % (n, dev))
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the points (and out's allocation) were made on torch's stream
+        options = self.trace_options(None, mask)
+        _check(lib().cap_closest_points(self.ctx, C.c_void_p(points.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                                        C.byref(options) if options is not None else None), "cap_closest_points")
         if sync:
             self.sync()
         if host or host_out is not None:

@@ -168,6 +168,19 @@ struct RayFilter
 // launch_query_binary under a filter (query.hip k_query_binary_f; first_hit: closest only, the lane retires at its first accepted hit)
 void launch_query_binary_filtered(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const RayFilter& f, bool any, bool first_hit, bool deferred);
 
+// Closest-point queries (cap_closest_points, point_query.hip): points = CapPointDesc records (float4: point, radius), out = CapClosest
+// records (two float4 per point).  slack: the absolute part of the pruning bound, kClosestSlackScale x the largest coordinate magnitude
+// of the scene bounds (DESIGN.md "Closest-point queries").  depth: the tree's max_depth, which picks the stack size.  f NULL: no mask table.
+struct ClosestArgs
+{
+    const float4* points;
+    uint32_t      n;
+    float4*       out;
+    float         slack;
+};
+constexpr float kClosestSlackScale = 1.0f / 262144.0f;  // 64 x 2^-24: the proof needs 52
+void launch_closest_points(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const RayFilter* f, uint32_t depth);
+
 // ---- instances (instance.hip): cap_instances_set, cap_trace_instances* ----
 // The table on the device.  rec: 4 float4 per instance = the three rows of W (world to object, row r = (W_r0, W_r1, W_r2, W_r3)) and
 // (asfloat(mask), asfloat(root of the object's tree), asfloat(object index), -); an inert instance has W = 0 and mask 0.  box: 2 float4 per instance = (lo.xyz, k) (hi.xyz, asfloat(index)),

@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point query (cap_closest_points, point_query.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -30,6 +30,7 @@ struct QueryRun
     BvhDev      bvh;
     LaunchCfg   cfg;
     float       safe;
+    float       slack;  // closest-point queries: the absolute part of the pruning bound
     uint64_t    per;    // rays per launch
     TlasDev     tl;     // instanced queries (use_instance_pools): the top-level tree ...
     uint32_t    depth;  // ... and the depth of the deepest tree below it
@@ -40,12 +41,13 @@ struct QueryRun
     }
 };
 
-int query_prepare(CapContext* c, const char* what, uint64_t n, QueryRun& run)
+// wide = false: a query that walks the binary tree alone (no hand-over list)
+int query_prepare(CapContext* c, const char* what, uint64_t n, QueryRun& run, bool wide = true)
 {
     HIP_TRY(hipSetDevice(c->device));
     run.c = c, run.what = what;
     run.bvh          = bvh_dev(c, c->lane[0]);  // (lane 0's spill area: a render's second lane has its own, and the stream orders us behind both)
-    run.bvh.wide8_ok = run.bvh.wide8_ok && query8_stack_matches();
+    run.bvh.wide8_ok = wide && run.bvh.wide8_ok && query8_stack_matches();
     run.per          = std::min<uint64_t>(n, kQueryRaysPerLaunch);
     if (c->query_work.n < 2 * kCounterStride || (run.bvh.wide8_ok && c->query_defer.n < run.per))
     {
@@ -61,6 +63,7 @@ int query_prepare(CapContext* c, const char* what, uint64_t n, QueryRun& run)
         m = std::max({m, (double)c->bvh_info.bounds_hi[k] - (double)c->bvh_info.bounds_lo[k], std::fabs((double)c->bvh_info.bounds_lo[k]),
                       std::fabs((double)c->bvh_info.bounds_hi[k])});
     run.safe = (float)(kQuerySafeScale * m);
+    run.slack = (float)((double)kClosestSlackScale * m);  // (m >= the largest |coordinate|: the bound only grows)
     return CAP_OK;
 }
 
@@ -133,9 +136,9 @@ int check_ranges(const char* what, uint64_t n, std::initializer_list<QueryRange>
 template <typename T>
 T* at(T* p, uint64_t i) { return p ? p + i : nullptr; }  // element i of an array the caller may have left out
 
-// launch(q, first) for every run.per rays of the call: q holds the chunk's rays, counters and hand-over bound, first is its first ray
-template <typename Launch>
-int for_each_chunk(const QueryRun& run, const CapRayDesc* rays, uint64_t n, Launch&& launch)
+// launch(q, first) for every run.per rays (or points: Record = CapPointDesc) of the call: q holds the chunk's rays, counters and hand-over bound, first is its first ray
+template <typename Record, typename Launch>
+int for_each_chunk(const QueryRun& run, const Record* rays, uint64_t n, Launch&& launch)
 {
     for (uint64_t first = 0; first < n; first += run.per)
     {
@@ -273,6 +276,27 @@ int trace_instances_multi(CapContext* c, const char* what, const CapRayDesc* ray
         return run.traced("k_query_inst_multi", first);
     });
 }
+
+// cap_closest_points (point_query.hip k_closest_points): the binary tree alone
+int closest_points(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, CapClosest* out, const CapTraceOptions* options)
+{
+    static_assert(sizeof(CapPointDesc) == sizeof(float4) && sizeof(CapClosest) == 2 * sizeof(float4), "point records are the kernel's float4 records");
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a point", what, options->ray_flags);
+    QueryFilter flt;
+    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
+    if (const int rc = query_state(c, what)) return rc;
+    if (n == 0) return CAP_OK;
+    if (!points || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, sizeof(CapClosest), 16)})) return rc;
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    const RayFilter* f = flt.scene();
+    return for_each_chunk(run, points, n, [&](const QueryArgs& q, uint64_t first) {
+        launch_closest_points(run.cfg, run.bvh, ClosestArgs{q.rays, q.n, reinterpret_cast<float4*>(out + first), run.slack}, f, c->bvh_info.max_depth);
+        return run.traced("k_closest_points", first);
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -324,5 +348,10 @@ int cap_trace_instances_multi(CapContext* c, const CapRayDesc* device_rays, uint
                               uint32_t* device_counts, uint32_t flags, const CapTraceOptions* options)
 {
     return trace_instances_multi(c, "cap_trace_instances_multi", device_rays, n, k, device_hits, device_instances, device_counts, flags, options);
+}
+
+int cap_closest_points(CapContext* c, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, const CapTraceOptions* options)
+{
+    return closest_points(c, "cap_closest_points", device_points, n, device_out, options);
 }
 }  // extern "C"

@@ -475,6 +475,66 @@ int cap_trace_occlusion_ex(CapContext* ctx, const CapRayDesc* device_rays, uint6
 int cap_trace_rays_multi_ex(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits,
                             uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options);
 
+/* ---- closest-point queries: the triangle nearest to a point, and how far away it is (Embree's rtcPointQuery) ----
+ * For distance fields, proximity and collision tests against the scene (animated ones included: the trees stay current under
+ * cap_bvh_refit), ICP registration, snapping and projecting points onto the scene.  Walks the binary tree of the scene.
+ *
+ * The per-triangle function is defined on the stored intersection record (v0, e1 = fl(v1 - v0), e2 = fl(v2 - v0)), not on the original
+ * vertices.  Every operation is one rounded binary32 operation in the order written, there is no fused multiply-add anywhere, division
+ * is correctly rounded, and dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z -- so a plain float32 brute force is bit-identical to the
+ * kernel.  It is the Voronoi-region cascade (Ericson, Real-Time Collision Detection 5.1.5); the first matching case wins:
+ *   ap = p - v0, d1 = dot(e1, ap), d2 = dot(e2, ap).          d1 <= 0 && d2 <= 0:                   v0, (u, v) = (0, 0)
+ *   bp = ap - e1, d3 = dot(e1, bp), d4 = dot(e2, bp).         d3 >= 0 && d4 <= d3:                  v1, (1, 0)
+ *   vc = d1*d4 - d3*d2.                                       vc <= 0 && d1 >= 0 && d3 <= 0:        edge v0v1, (d1 / (d1 - d3), 0)
+ *   cp = ap - e2, d5 = dot(e1, cp), d6 = dot(e2, cp).         d6 >= 0 && d5 <= d6:                  v2, (0, 1)
+ *   vb = d5*d2 - d1*d6.                                       vb <= 0 && d2 >= 0 && d6 <= 0:        edge v2v0, (0, d2 / (d2 - d6))
+ *   va = d3*d6 - d5*d4.                                       va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0:
+ *                                                             edge v1v2, w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), (1 - w, w)
+ *   otherwise the face: s = (va + vb) + vc, (vb / s, vc / s).
+ * Then, component-wise, m = e1*u + e2*v, delta = ap - m, dist2 = dot(delta, delta), point = v0 + m.  delta is taken from ap rather
+ * than from p - point, so that the error scales with the local geometry and not with the absolute coordinates.
+ *
+ * The answer.  A triangle is a candidate iff it passes the mask filter and dist2 <= r2, r2 = fl(radius * radius).  A NaN dist2 (a
+ * zero-area triangle can produce one) fails the comparison and is never an answer.  The record is the candidate minimal in
+ * (dist2, triangle) lexicographic order, the tie rule of the ray queries: the answer depends on neither the tree, nor the builder,
+ * nor the visiting order.  The miss record is (0, 0, 0, r2, 0, 0, 0xFFFFFFFF, 0).  radius = +inf is a query like any other; radius = 0
+ * admits only triangles with computed dist2 == 0.  Degenerate queries -- a non-finite coordinate, a radius that is NaN or negative --
+ * are not traversed and give the miss record with dist2 = 0.
+ *
+ * Conventions are cap_trace_rays_ex's: device pointers on the context's GPU, both 16-byte aligned, ranges that do not overlap;
+ * asynchronous on the context stream and ordered behind a render's second lane; n above 2^24 split into launches, n = 0 does nothing;
+ * nothing of the render's state is touched; nothing is written on an error.  CAP_ERR_STATE before cap_bvh_build and while the trees
+ * are stale after cap_scene_update_vertices.  options: instance_mask and the mesh-mask table act exactly as in the ray queries (a mesh
+ * with mask 0 is invisible here too); any ray_flags bit is CAP_ERR_INVALID_ARG (facing and first hit mean nothing for a point), as are
+ * non-zero reserved words and instance_mask > 0xFF; NULL or all-zero is the plain call.
+ * Not covered: instances and objects (a non-rigid transform does not preserve nearest), k nearest, per-point masks, the sign of the
+ * distance (`feature` is what a caller needs to build it from the normals of the face, edge or vertex). */
+typedef struct CapPointDesc /* 16 B */
+{
+    float point[3];
+    float radius; /* search radius, >= 0; +inf: unbounded */
+} CapPointDesc;
+typedef struct CapClosest /* 32 B */
+{
+    float    point[3]; /* the closest point q */
+    float    dist2;    /* squared distance */
+    float    u, v;     /* q = v0 + u*e1 + v*e2, the weights of v1 and v2 */
+    uint32_t triangle; /* global id, as CapHit's; 0xFFFFFFFF = miss */
+    uint32_t feature;  /* CAP_FEATURE_*: where on the triangle q lies */
+} CapClosest;
+enum
+{
+    CAP_FEATURE_FACE = 0,
+    CAP_FEATURE_EDGE_V0V1 = 1,
+    CAP_FEATURE_EDGE_V1V2 = 2,
+    CAP_FEATURE_EDGE_V2V0 = 3,
+    CAP_FEATURE_V0 = 4,
+    CAP_FEATURE_V1 = 5,
+    CAP_FEATURE_V2 = 6
+};
+int cap_closest_points(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out,
+                       const CapTraceOptions* options /* may be NULL */);
+
 /* ---- instanced ray queries: N transformed instances of the uploaded scene, or of objects of it, under a device-built top-level tree ----
  * The uploaded scene and the trees cap_bvh_build makes of it are read as OBJECT space; cap_instances_set installs a table of N
  * instances of it, each with an object-to-world transform and an 8-bit mask, and builds a top-level tree (TLAS) over the instances'

@@ -1,0 +1,92 @@
+#!/usr/bin/env python3
+"""Throughput of the closest-point query (cap_closest_points) on the 262 k-triangle hall -- not part of bench.py, no pass mark.
+
+    python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf] [--offset 1e-3]
+
+Point sets, each of --points points (rounded down to a cube for the grid):
+  grid      a regular grid through the scene's box, in raster order (x fastest);
+  shuffled  the same points in random order;
+  surface   points displaced by up to --offset x the scene's size off random points of random triangles.
+For scale, cap_trace_rays on the same number of uniformly random rays (origin in the box, direction on the sphere, tmax inf).
+One JSON line per set: host clock around cap_sync over `reps` back-to-back calls after `warmup` calls, the renderer on a stream of its
+own, points and records resident on the device; M points (rays) per second.  `hits` is the share of queries that found a triangle,
+`mean_dist` the mean distance of those in units of the scene's size.  The hall is tools/make_sponza_class.py at scale 1.0."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def timed(r, call, reps, warmup):
+    for _ in range(warmup):
+        call()
+    r.sync()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        call()
+    r.sync()
+    return (time.perf_counter() - t0) / reps
+
+
+def main():
+    import torch
+    from capsaicin_amd import capi
+    from query_bench import random_rays, scene, triangles
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--points", type=int, default=1 << 20)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--radius", type=float, default=float("inf"))
+    ap.add_argument("--offset", type=float, default=1e-3)
+    a = ap.parse_args()
+    rng = np.random.default_rng(2026)
+    dev = torch.device("cuda", 0)
+    L = capi.lib()
+    with tempfile.TemporaryDirectory() as tmp:
+        geo, _ = scene("hall", tmp)
+        tris = triangles(geo)
+        r = capi.Renderer(0)
+        r.upload_geometry(geo)
+        info = r.build_bvh()
+    lo, hi = np.float64(list(info.bounds_lo)), np.float64(list(info.bounds_hi))
+    size = float((hi - lo).max())
+    side = int(round(a.points ** (1.0 / 3.0)))
+    while side ** 3 > a.points:
+        side -= 1
+    n = side ** 3
+    ax = [np.linspace(lo[k], hi[k], side) for k in range(3)]
+    grid = np.stack(np.meshgrid(ax[2], ax[1], ax[0], indexing="ij"), -1).reshape(-1, 3)[:, ::-1]  # x fastest
+    g = rng.integers(0, len(tris), n)
+    b = rng.dirichlet((1, 1, 1), n)
+    surface = np.einsum("nk,nkj->nj", b, tris[g].astype(np.float64)) + (rng.random((n, 3)) - 0.5) * 2 * a.offset * size
+    sets = (("grid", grid), ("shuffled", grid[rng.permutation(n)]), ("surface", surface))
+    out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    head = dict(scene="hall", triangles=int(info.triangle_count), depth=int(info.max_depth), n=n, radius=a.radius, reps=a.reps)
+    for name, xyz in sets:
+        q = np.zeros((n, 4), np.float32)
+        q[:, 0:3], q[:, 3] = xyz, a.radius
+        pts = torch.as_tensor(q, device=dev).contiguous()
+        torch.cuda.synchronize()
+        sec = timed(r, lambda: capi._check(L.cap_closest_points(r.ctx, pts.data_ptr(), n, out.data_ptr(), None), "cap_closest_points"), a.reps, a.warmup)
+        rec = out.cpu().numpy()
+        hit = rec.view(np.uint32)[:, 6] != capi.MISS
+        print(json.dumps(dict(head, set=name, ms=round(sec * 1e3, 3), mpoints_per_s=round(n / sec / 1e6, 1), hits=round(float(hit.mean()), 4),
+                              mean_dist=round(float(np.sqrt(rec[hit, 3].astype(np.float64)).mean() / size), 5) if hit.any() else None)), flush=True)
+    rays = torch.as_tensor(random_rays(lo, hi, n, rng), device=dev).contiguous()
+    hits = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    sec = timed(r, lambda: capi._check(L.cap_trace_rays(r.ctx, rays.data_ptr(), n, hits.data_ptr(), 0), "cap_trace_rays"), a.reps, a.warmup)
+    print(json.dumps(dict(head, set="random rays (cap_trace_rays)", ms=round(sec * 1e3, 3), mrays_per_s=round(n / sec / 1e6, 1))), flush=True)
+    r.close()
+
+
+if __name__ == "__main__":
+    main()
