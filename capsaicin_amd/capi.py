@@ -136,13 +136,16 @@ FEATURE_FACE, FEATURE_EDGE_V0V1, FEATURE_EDGE_V1V2, FEATURE_EDGE_V2V0, FEATURE_V
 
 def closest_triangles(records):
     """(triangle ids, features) of (N, 8) closest-point records (columns 6 and 7 hold their bits) as int64; a miss reads MISS.  torch
-    in, torch out."""
+    in, torch out.  The (N, k, 8) pages of closest_points_multi give (N, k) ids and features."""
     if isinstance(records, np.ndarray):
+        if records.ndim == 3:
+            w = np.ascontiguousarray(records, np.float32)[..., 6:8].view(np.uint32).astype(np.int64)
+            return w[..., 0], w[..., 1]
         w = np.ascontiguousarray(records, np.float32).reshape(-1, 8)[:, 6:8].view(np.uint32).astype(np.int64)
         return w[:, 0], w[:, 1]
     import torch
-    w = records[:, 6:8].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-    return w[:, 0], w[:, 1]
+    w = records[..., 6:8].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    return w[..., 0], w[..., 1]
 
 
 OUTPUT_COMBINED, OUTPUT_DIRECT, OUTPUT_INDIRECT, OUTPUT_VARIANCE = range(4)  # SettingsComponent::output, gui_system.h:11-17
@@ -266,6 +269,7 @@ SYMBOLS = {
     "cap_trace_instances_occlusion": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_trace_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_closest_points": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
+    "cap_closest_points_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
     "cap_post_settings_default": (None, [C.POINTER(PostSettings)]),
     "cap_post_frame": (_i, [_vp, C.POINTER(PostSettings), _u32, C.POINTER(CameraData)]),
@@ -774,6 +778,56 @@ class Renderer:
                 return host_out
             return res
         return out
+
+    def closest_points_multi(self, points, k, counts=False, resume=None, sync=True, mask=None):
+        """The k triangles nearest to each point within its radius, in (dist2, triangle) order (cap_closest_points_multi): (N, k, 8)
+        float32 records as closest_points writes them, miss records (0, 0, 0, radius^2, 0, 0, MISS, 0) after a point's last candidate;
+        closest_triangles() reads the (N, k) ids and features.  counts=True also returns the number of ALL candidates per point, (N,)
+        int32, and turns off pruning by the k-th distance (k = 0: counts only, the records are (N, 0, 8)).  resume=<previous page> (the
+        (N, k, 8) result of a call with the same points) continues after it with CAP_MULTI_CONTINUE, writes the next page over it and
+        returns it.  points, sync and mask= as closest_points; numpy points (or a numpy resume page) give numpy results."""
+        import torch
+        options = self.trace_options(None, mask)
+        dev = torch.device("cuda", self.device)
+        host = isinstance(points, np.ndarray) or isinstance(resume, np.ndarray)
+        if isinstance(points, np.ndarray):
+            points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
+        if host:
+            sync = True  # the result is read back to the host
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
+            raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
+        n, k = points.shape[0], int(k)
+        if not 0 <= k <= self.MULTI_MAX_K:
+            raise CapError("k must be in 0 .. %d (page with resume=), got %d" % (self.MULTI_MAX_K, k))
+        if k == 0 and (not counts or resume is not None):
+            raise CapError("k = 0 counts only: pass counts=True and no resume page")
+        host_page = None
+        if resume is None:
+            page = torch.empty((n, k, 8), dtype=torch.float32, device=dev)
+        elif isinstance(resume, np.ndarray):
+            if resume.size != n * k * 8:
+                raise CapError("resume must be the (%d, %d, 8) float32 page of the previous call, got %s" % (n, k, resume.shape))
+            host_page = resume
+            page = torch.from_numpy(np.ascontiguousarray(resume, np.float32).reshape(n, k, 8)).to(dev)
+        else:
+            page = resume
+            if page.dtype != torch.float32 or tuple(page.shape) != (n, k, 8) or not page.is_contiguous() or page.device != dev:
+                raise CapError("resume must be the contiguous (%d, %d, 8) float32 page of the previous call" % (n, k))
+        cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
+        _check(lib().cap_closest_points_multi(self.ctx, C.c_void_p(points.data_ptr()), n, k, C.c_void_p(page.data_ptr()) if k else None,
+                                              C.c_void_p(cnt.data_ptr()) if counts else None, self.MULTI_CONTINUE if resume is not None else 0,
+                                              C.byref(options) if options is not None else None), "cap_closest_points_multi")
+        if sync:
+            self.sync()
+        if host:
+            h = page.cpu().numpy()
+            if host_page is not None:
+                host_page[...] = h.reshape(host_page.shape)
+                h = host_page
+            return (h, cnt.cpu().numpy()) if counts else h
+        return (page, cnt) if counts else page
 
     # ---- instanced ray queries (cap_instances_set, cap_trace_instances*) ----
     def set_objects(self, ranges):

@@ -180,6 +180,17 @@ struct ClosestArgs
 };
 constexpr float kClosestSlackScale = 1.0f / 262144.0f;  // 64 x 2^-24: the proof needs 52
 void launch_closest_points(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const RayFilter* f, uint32_t depth);
+// The k nearest and in-radius form (cap_closest_points_multi, point_query.hip k_closest_points_multi): a.out = pages of k CapClosest
+// records per point (NULL when k = 0); counts = n candidate counts or NULL (then the k-th distance prunes); resume: slot k - 1 of each
+// page is the cursor (CAP_MULTI_CONTINUE).  The list capacity is multi_bucket(k) >= k.
+struct ClosestMultiArgs
+{
+    ClosestArgs a;
+    uint32_t    k;
+    uint32_t*   counts;
+    uint32_t    resume;
+};
+void launch_closest_points_multi(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestMultiArgs& m, const RayFilter* f, uint32_t depth);
 
 // ---- instances (instance.hip): cap_instances_set, cap_trace_instances* ----
 // The table on the device.  rec: 4 float4 per instance = the three rows of W (world to object, row r = (W_r0, W_r1, W_r2, W_r3)) and

@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point query (cap_closest_points, point_query.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_closest_points_multi; point_query.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -297,6 +297,38 @@ int closest_points(CapContext* c, const char* what, const CapPointDesc* points, 
         return run.traced("k_closest_points", first);
     });
 }
+
+// cap_closest_points_multi (point_query.hip k_closest_points_multi): a point's first k candidates in (dist2, triangle) order and / or
+// the number of its candidates -- trace_multi's rules over closest_points' options and tree.  k = 1 without counts or cursor IS
+// cap_closest_points and takes its kernel.
+int closest_points_multi(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, uint32_t k, CapClosest* out, uint32_t* counts,
+                         uint32_t flags, const CapTraceOptions* options)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a point", what, options->ray_flags);
+    QueryFilter flt;
+    if (const int rc = multi_rules(c, what, k, flags, options, "output", out != nullptr, counts, flt)) return rc;
+    if (const int rc = query_state(c, what)) return rc;
+    if (n == 0) return CAP_OK;
+    if (!points || (k && !out)) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, (uint64_t)k * sizeof(CapClosest), 16),
+                                              range("counts", counts, sizeof(uint32_t), 4)}))
+        return rc;
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    const RayFilter* f      = flt.scene();
+    const bool       single = k == 1 && !counts && !(flags & CAP_MULTI_CONTINUE);
+    return for_each_chunk(run, points, n, [&](const QueryArgs& q, uint64_t first) {
+        const ClosestArgs a{q.rays, q.n, reinterpret_cast<float4*>(at(out, first * k)), run.slack};
+        if (single)
+        {
+            launch_closest_points(run.cfg, run.bvh, a, f, c->bvh_info.max_depth);
+            return run.traced("k_closest_points", first);
+        }
+        launch_closest_points_multi(run.cfg, run.bvh, ClosestMultiArgs{a, k, at(counts, first), (flags & CAP_MULTI_CONTINUE) ? 1u : 0u}, f, c->bvh_info.max_depth);
+        return run.traced("k_closest_points_multi", first);
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -353,5 +385,11 @@ int cap_trace_instances_multi(CapContext* c, const CapRayDesc* device_rays, uint
 int cap_closest_points(CapContext* c, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, const CapTraceOptions* options)
 {
     return closest_points(c, "cap_closest_points", device_points, n, device_out, options);
+}
+
+int cap_closest_points_multi(CapContext* c, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out, uint32_t* device_counts,
+                             uint32_t multi_flags, const CapTraceOptions* options)
+{
+    return closest_points_multi(c, "cap_closest_points_multi", device_points, n, k, device_out, device_counts, multi_flags, options);
 }
 }  // extern "C"

@@ -406,7 +406,7 @@ __global__ __launch_bounds__(kBlock, inst_blocks(STACK)) void k_query_inst(BvhDe
 }
 
 // ---- multi-hit over the instances (cap_trace_instances_multi) ----
-// A ray's first k pairs in (t, instance, triangle) order, the number of its pairs, or both: query.hip's HitList with the instance
+// A ray's first k pairs in (t, instance, triangle) order, the number of its pairs, or both: cap_hit_list.h's HitList with the instance
 // between t and the triangle.  K (t, inst, gid) triples in VGPRs, K a compile-time bucket >= k, every index a compile-time constant;
 // the first K - k slots hold (-inf, 0, 0) placeholders no hit passes (t > tmin >= -inf), the last k start as the miss (tmax, ~0, ~0).
 // A pair below slot K - 1 replaces it and bubbles towards the front by K - 1 compare-swaps.

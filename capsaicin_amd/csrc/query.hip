@@ -16,6 +16,7 @@
 //     within kQuerySafeScale * M the error is at most eps |1/d| (4 * 4 M + 3 M) = 19 eps M |1/d|, below the padding's 33.5 eps M |1/d|.
 //     A ray whose origin lies beyond is not traced here: its index goes to a list that the binary tree's kernel (kernels.hip
 //     k_query_binary, whose slab test carries its own relative slack) answers right behind this launch.
+#include "cap_hit_list.h"
 #include "cap_kernels.h"
 #include "cap_wide_trace.h"
 
@@ -365,36 +366,7 @@ void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, 
 // triangle with a lower id still displaces the k-th entry: the list is exact whatever the visiting order.
 // Paging (CAP_MULTI_CONTINUE): a hit is counted only above the cursor (t_c, g_c) read from slot k - 1 of the page, (-inf, 0) otherwise.
 // Hits below the cursor's t lie outside every page after it, so the box tests may take max(tmin, t_c) as their lower bound: still
-// inclusive, a triangle at t_c with a higher id is kept.
-template <int K>
-struct HitList
-{
-    float    t[K];
-    uint32_t g[K];
-    __device__ __forceinline__ void init(uint32_t k, float tmax)
-    {
-#pragma unroll
-        for (int j = 0; j < K; ++j)
-        {
-            const bool live = j >= K - (int)k;
-            t[j] = live ? tmax : -__builtin_inff(), g[j] = live ? kInvalidId : 0u;
-        }
-    }
-    __device__ __forceinline__ bool admits(float tt, uint32_t gg) const { return tt < t[K - 1] || (tt == t[K - 1] && gg < g[K - 1]); }
-    __device__ __forceinline__ void insert(float tt, uint32_t gg)
-    {
-        t[K - 1] = tt, g[K - 1] = gg;
-#pragma unroll
-        for (int j = K - 1; j > 0; --j)
-        {
-            const bool     sw = t[j] < t[j - 1] || (t[j] == t[j - 1] && g[j] < g[j - 1]);
-            const float    ta = t[j - 1], tb = t[j];
-            const uint32_t ga = g[j - 1], gb = g[j];
-            t[j - 1] = sw ? tb : ta, t[j] = sw ? ta : tb;
-            g[j - 1] = sw ? gb : ga, g[j] = sw ? ga : gb;
-        }
-    }
-};
+// inclusive, a triangle at t_c with a higher id is kept.  The list itself is HitList<K> of cap_hit_list.h.
 
 // The hit (t, gid) of the contract's rule, against a ray's cursor and list.  COUNT: every hit above the cursor adds one.
 template <int K, bool COUNT>

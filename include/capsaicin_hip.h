@@ -507,7 +507,7 @@ int cap_trace_rays_multi_ex(CapContext* ctx, const CapRayDesc* device_rays, uint
  * are stale after cap_scene_update_vertices.  options: instance_mask and the mesh-mask table act exactly as in the ray queries (a mesh
  * with mask 0 is invisible here too); any ray_flags bit is CAP_ERR_INVALID_ARG (facing and first hit mean nothing for a point), as are
  * non-zero reserved words and instance_mask > 0xFF; NULL or all-zero is the plain call.
- * Not covered: instances and objects (a non-rigid transform does not preserve nearest), k nearest, per-point masks, the sign of the
+ * Not covered: instances and objects (a non-rigid transform does not preserve nearest), per-point masks, the sign of the
  * distance (`feature` is what a caller needs to build it from the normals of the face, edge or vertex). */
 typedef struct CapPointDesc /* 16 B */
 {
@@ -534,6 +534,37 @@ enum
 };
 int cap_closest_points(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out,
                        const CapTraceOptions* options /* may be NULL */);
+
+/* ---- k nearest and in-radius closest-point queries: the SET of triangles near a point (contact generation, robust ICP, density) ----
+ * A point's candidates are exactly cap_closest_points': the triangles that pass the mask filter with dist2 <= r2,
+ * r2 = fl(radius * radius), by the per-triangle function above on the stored record; a NaN dist2 is never a candidate.  They are sorted
+ * by (dist2, triangle) ascending: equal dist2 goes to the lower id.  device_out[i * k + j], j < k, is point i's j-th nearest candidate
+ * as a full CapClosest; slots after its last candidate hold the miss record (0, 0, 0, r2, 0, 0, 0xFFFFFFFF, 0).  A triangle appears at
+ * most once per point.  With k = 1, no counts and no cursor every record is bit for bit what cap_closest_points returns.  Records
+ * are bit-identical to a float32 brute force, whichever builder made the tree.
+ *
+ * device_counts: NULL, or n uint32: the number of ALL candidates of point i, not capped at k (with CAP_MULTI_CONTINUE: of those above
+ * the cursor).  Asking for counts turns off pruning by the k-th distance: the walk is then bounded by the radius alone, so with
+ * radius = +inf it is a full traversal of the tree.  k = 0 counts only: device_out must be NULL and device_counts given.
+ *
+ * Paging (CAP_MULTI_CONTINUE): on entry, slot k - 1 of each point's page is read as a cursor (dist2_c, g_c) -- words 3 and 6 of that
+ * record; only candidates with (dist2, triangle) > (dist2_c, g_c) in lexicographic order count, and the next page is written over the
+ * old one.  A page that was not full ends in a miss record, whose cursor (r2, 0xFFFFFFFF) admits nothing: that point's next page is
+ * empty.  Calling again with the same points and buffer walks every candidate exactly once, equal-dist2 candidates on either side of
+ * a page boundary and candidates with dist2 == r2 included.  The cursor slot must hold what the previous call wrote there.
+ *
+ * Degenerate queries (a non-finite coordinate, a NaN or negative radius) are not traversed: k miss records with dist2 = 0 and count 0,
+ * with CAP_MULTI_CONTINUE too.  Everything else is as for cap_closest_points and cap_trace_rays_multi_ex: device pointers on the
+ * context's GPU, asynchronous on the context stream and ordered behind a render's second lane; n above 2^24 split into launches;
+ * nothing of the render's state is touched.  Errors: CAP_ERR_STATE before cap_bvh_build and while the trees are stale;
+ * CAP_ERR_INVALID_ARG for any ray_flags bit, non-zero reserved words, instance_mask > 0xFF, unknown multi flags, k > CAP_MULTI_MAX_K,
+ * k = 0 with output given or counts NULL, CAP_MULTI_CONTINUE with k = 0, NULL points (or output with k > 0), points or output not
+ * 16-byte or counts not 4-byte aligned, any overlap between the point, output and count ranges, and n * k records beyond the address
+ * space.  Nothing is written on an error; n = 0 does nothing.
+ * Not covered: a lower bound from the cursor (a later page walks the subtrees the earlier pages exhausted again), and what
+ * cap_closest_points leaves out. */
+int cap_closest_points_multi(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out,
+                             uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options /* may be NULL */);
 
 /* ---- instanced ray queries: N transformed instances of the uploaded scene, or of objects of it, under a device-built top-level tree ----
  * The uploaded scene and the trees cap_bvh_build makes of it are read as OBJECT space; cap_instances_set installs a table of N

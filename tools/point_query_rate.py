@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
-"""Throughput of the closest-point query (cap_closest_points) on the 262 k-triangle hall -- not part of bench.py, no pass mark.
+"""Throughput of the closest-point queries (cap_closest_points, cap_closest_points_multi) on the 262 k-triangle hall -- not part of
+bench.py, no pass mark.
 
-    python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf] [--offset 1e-3]
+    python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
+                                     [--k K [--counts]]
+
+--k K runs cap_closest_points_multi with pages of K records on the same point sets (--counts: with the candidate counts, which turns
+off pruning by the k-th distance; K = 0 needs it); the line then also carries k, counts and mean_candidates -- the mean of the counts,
+or without --counts the mean number of records listed per point (at most K).  `hits` and `mean_dist` are those of slot 0.  Without
+--k the tool runs cap_closest_points as before.  --radius-frac F sets the radius to F x the scene's size.
 
 Point sets, each of --points points (rounded down to a cube for the grid):
   grid      a regular grid through the scene's box, in raster order (x fastest);
@@ -45,7 +52,10 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--radius", type=float, default=float("inf"))
+    ap.add_argument("--radius-frac", type=float, default=None)
     ap.add_argument("--offset", type=float, default=1e-3)
+    ap.add_argument("--k", type=int, default=None)
+    ap.add_argument("--counts", action="store_true")
     a = ap.parse_args()
     rng = np.random.default_rng(2026)
     dev = torch.device("cuda", 0)
@@ -58,6 +68,10 @@ def main():
         info = r.build_bvh()
     lo, hi = np.float64(list(info.bounds_lo)), np.float64(list(info.bounds_hi))
     size = float((hi - lo).max())
+    if a.radius_frac is not None:
+        a.radius = a.radius_frac * size
+    if a.counts and a.k is None:
+        ap.error("--counts needs --k")
     side = int(round(a.points ** (1.0 / 3.0)))
     while side ** 3 > a.points:
         side -= 1
@@ -68,18 +82,32 @@ def main():
     b = rng.dirichlet((1, 1, 1), n)
     surface = np.einsum("nk,nkj->nj", b, tris[g].astype(np.float64)) + (rng.random((n, 3)) - 0.5) * 2 * a.offset * size
     sets = (("grid", grid), ("shuffled", grid[rng.permutation(n)]), ("surface", surface))
-    out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    out = torch.empty((n * max(a.k or 1, 1), 8), dtype=torch.float32, device=dev)
+    cnt = torch.empty((n,), dtype=torch.int32, device=dev) if a.counts else None
     head = dict(scene="hall", triangles=int(info.triangle_count), depth=int(info.max_depth), n=n, radius=a.radius, reps=a.reps)
+    if a.k is not None:
+        head.update(k=a.k, counts=a.counts)
     for name, xyz in sets:
         q = np.zeros((n, 4), np.float32)
         q[:, 0:3], q[:, 3] = xyz, a.radius
         pts = torch.as_tensor(q, device=dev).contiguous()
         torch.cuda.synchronize()
-        sec = timed(r, lambda: capi._check(L.cap_closest_points(r.ctx, pts.data_ptr(), n, out.data_ptr(), None), "cap_closest_points"), a.reps, a.warmup)
-        rec = out.cpu().numpy()
-        hit = rec.view(np.uint32)[:, 6] != capi.MISS
-        print(json.dumps(dict(head, set=name, ms=round(sec * 1e3, 3), mpoints_per_s=round(n / sec / 1e6, 1), hits=round(float(hit.mean()), 4),
-                              mean_dist=round(float(np.sqrt(rec[hit, 3].astype(np.float64)).mean() / size), 5) if hit.any() else None)), flush=True)
+        if a.k is None:
+            call = lambda: capi._check(L.cap_closest_points(r.ctx, pts.data_ptr(), n, out.data_ptr(), None), "cap_closest_points")
+        else:
+            call = lambda: capi._check(L.cap_closest_points_multi(r.ctx, pts.data_ptr(), n, a.k, out.data_ptr() if a.k else None,
+                                                                  cnt.data_ptr() if a.counts else None, 0, None), "cap_closest_points_multi")
+        sec = timed(r, call, a.reps, a.warmup)
+        line = dict(head, set=name, ms=round(sec * 1e3, 3), mpoints_per_s=round(n / sec / 1e6, 1))
+        if a.k != 0:
+            page = out.cpu().numpy().reshape(n, -1, 8)
+            listed = page.view(np.uint32)[:, :, 6] != capi.MISS
+            rec, hit = page[:, 0], listed[:, 0]
+            line.update(hits=round(float(hit.mean()), 4),
+                        mean_dist=round(float(np.sqrt(rec[hit, 3].astype(np.float64)).mean() / size), 5) if hit.any() else None)
+        if a.k is not None:
+            line.update(mean_candidates=round(float(cnt.cpu().numpy().astype(np.float64).mean() if a.counts else listed.sum(1).mean()), 3))
+        print(json.dumps(line), flush=True)
     rays = torch.as_tensor(random_rays(lo, hi, n, rng), device=dev).contiguous()
     hits = torch.empty((n, 4), dtype=torch.float32, device=dev)
     torch.cuda.synchronize()
