@@ -61,7 +61,7 @@ typedef struct CapMeshDesc
 typedef struct CapMaterial
 {
     float kd[3];
-    float roughness;
+    float roughness; /* GGX alpha = max(roughness^2, 1e-3): only the square enters; values above 1 are legal and are not Lambert */
     float ks[3];
     float pad0;
     float ke[3];

@@ -63,7 +63,7 @@ typedef struct OracleTexture
 typedef struct OracleMaterial
 {
     float kd[3];
-    float roughness; /* GGX alpha = roughness^2; >= 1 means pure Lambert */
+    float roughness; /* GGX alpha = max(roughness^2, 1e-3); values above 1 are legal (roughness 2: alpha 4) and are NOT Lambert */
     float ks[3];
     float pad0;
     float ke[3]; /* emitted radiance */
