@@ -244,6 +244,7 @@ SYMBOLS = {
     "cap_debug_switch_index": (_i, [C.c_char_p]),
     "cap_debug_pair_ids_dense": (_i, [_vp, _u32, _u32, _u32]),
     "cap_debug_query_ranges": (_i, [_u64, _u32, _vp, _vp, _vp]),
+    "cap_debug_closest_instance_bound": (_i, [_vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "cap_render": (_i, [_vp, _u32, _u32, _u32, _u32]),
     "cap_accum_reset": (_i, [_vp]),
     "cap_accum_import": (_i, [_vp, _vp, _u64]),
@@ -270,6 +271,7 @@ SYMBOLS = {
     "cap_trace_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_closest_points": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_points_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
+    "cap_closest_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
     "cap_post_settings_default": (None, [C.POINTER(PostSettings)]),
     "cap_post_frame": (_i, [_vp, C.POINTER(PostSettings), _u32, C.POINTER(CameraData)]),
@@ -778,6 +780,43 @@ class Renderer:
                 return host_out
             return res
         return out
+
+    def closest_instances(self, points, out=None, sync=True, mask=None):
+        """The (instance, triangle) nearest to each point in WORLD space over the instance table (cap_closest_instances): (records
+        (N, 8) float32, instances (N,) int32, -1 on a miss).  The records are closest_points' -- world-space closest point and dist2,
+        (u, v), the scene's triangle id and the feature: closest_triangles() reads those.  points, out, sync and mask= as
+        closest_points; numpy points give numpy results."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        host = isinstance(points, np.ndarray)
+        if host:
+            points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
+            sync = True  # the result is read back to the host
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
+            raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
+        n = points.shape[0]
+        host_out = None
+        if isinstance(out, np.ndarray):
+            host_out, out = out, None
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (n, 8) or not out.is_contiguous() or out.device != dev:
+            raise CapError("out must be a contiguous (%d, 8) float32 tensor on %s" % (n, dev))
+        inst = torch.empty((n,), dtype=torch.int32, device=dev)
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
+        options = self.trace_options(None, mask)
+        _check(lib().cap_closest_instances(self.ctx, C.c_void_p(points.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(inst.data_ptr()),
+                                           C.byref(options) if options is not None else None), "cap_closest_instances")
+        if sync:
+            self.sync()
+        if host or host_out is not None:
+            res = out.cpu().numpy()
+            if host_out is not None:
+                host_out[...] = res.reshape(host_out.shape)
+                res = host_out
+            return res, inst.cpu().numpy()
+        return out, inst
 
     def closest_points_multi(self, points, k, counts=False, resume=None, sync=True, mask=None):
         """The k triangles nearest to each point within its radius, in (dist2, triangle) order (cap_closest_points_multi): (N, k, 8)

@@ -133,6 +133,7 @@ struct CapContext
     DevBuf<float4>   inst_desc, inst_rec, inst_box, inst_tlas;
     DevBuf<uint32_t> inst_keys[2], inst_vals[2], inst_hist, inst_scan, inst_misc, inst_level_off;
     uint32_t         inst_count = 0, inst_top = 0, inst_nodes = 0;
+    DevBuf<float2>   inst_near;               // each instance's (g, Xw) for cap_closest_instances (cap_near.h)
     DevBuf<uint32_t> inst_obj;                // each instance's object index (cap_instances_set_ex)
     bool             inst_obj_on = false;     // ... given with the installed table (false: every instance shows object 0)
     InstObject       scene_object_host{};     // the scene as the one object of a context without an object table ...

@@ -191,6 +191,20 @@ struct ClosestMultiArgs
     uint32_t    resume;
 };
 void launch_closest_points_multi(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestMultiArgs& m, const RayFilter* f, uint32_t depth);
+// Over the instance table (cap_closest_instances, point_query.hip k_closest_inst): nearest in world space, on the instance's transformed
+// triangle.  a as above (a.slack is not read: the slack is per point and instance, cap_near.h); inst_out may be NULL.  descs: the
+// CapInstanceDesc records as the caller gave them (4 float4 each; the contract's world record is built from M, not from W), near and
+// xw_max: InstanceBuildArgs::near and misc + 7.  bvh, tl, f and depth as launch_query_instances'; bvh.tris_by_id the scene's records.
+struct TlasDev;
+struct ClosestInstArgs
+{
+    ClosestArgs     a;
+    uint32_t*       inst_out;
+    const float4*   descs;
+    const float2*   near;
+    const uint32_t* xw_max;
+};
+void launch_closest_instances(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstArgs& a, const TlasDev& tl, const RayFilter& f, uint32_t depth);
 
 // ---- instances (instance.hip): cap_instances_set, cap_trace_instances* ----
 // The table on the device.  rec: 4 float4 per instance = the three rows of W (world to object, row r = (W_r0, W_r1, W_r2, W_r3)) and
@@ -216,11 +230,12 @@ struct InstanceBuildArgs
     float4*      rec;
     float4*      box;
     float4*      tlas;
+    float2*      near;  // per instance (g, Xw): the distance prune of cap_closest_instances (cap_near.h); (0, 0) for an inert instance
     uint32_t*    keys[2];
     uint32_t*    vals[2];
     uint32_t*    hist;
     uint32_t*    scan;
-    uint32_t*    misc;  // 8 words: 6 ordered-uint bounds of the live boxes' centres, the inert count, -
+    uint32_t*    misc;  // 8 words: 6 ordered-uint bounds of the live boxes' centres, the inert count, the largest Xw as float bits
 };
 constexpr uint32_t kTlasMaxLevels = 25;  // n <= 2^24: levels 0 .. 24
 // level_off[0 .. top] and the total number of entries for n instances; returns top

@@ -1,0 +1,143 @@
+// cap_near.h — the arithmetic closest-point queries over instances (cap_closest_instances) prune with, host and device: the
+// per-instance world-to-object data of k_instance_setup (instance.hip), the two values the distance prune adds to it (g, Xw), the
+// per-point slack and the skip predicate of k_closest_inst (point_query.hip).  cap_debug_closest_instance_bound (context.hip) runs the
+// same functions on the host, so that the CPU tests exercise what ships.  DESIGN.md "Closest-point queries over instances" has the
+// argument for the constants.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+
+#include <hip/hip_runtime.h>
+
+namespace cap
+{
+constexpr float kNearEps = 5.9604644775390625e-8f;  // 2^-24
+constexpr float kNearC1  = 16.0f;                   // relative part of the bound: the proof needs 10.1, the bound's own roundings 4
+constexpr float kNearC2  = 96.0f;                   // slack = kNearC2 eps (|p|_inf + Xw): the proof needs 85
+
+__host__ __device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }
+__host__ __device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.40282347e38f; }
+
+// inverse of the affine map m (row-major 3x4) in double; false when it is singular or the result is not finite
+__host__ __device__ __forceinline__ bool invert_affine(const double m[12], double w[12])
+{
+    const double c00 = m[5] * m[10] - m[6] * m[9], c01 = m[6] * m[8] - m[4] * m[10], c02 = m[4] * m[9] - m[5] * m[8];
+    const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
+    if (!(fabs(det) > 0.0) || !finite_d(det)) return false;
+    const double id = 1.0 / det;
+    w[0] = c00 * id, w[1] = (m[2] * m[9] - m[1] * m[10]) * id, w[2] = (m[1] * m[6] - m[2] * m[5]) * id;
+    w[4] = c01 * id, w[5] = (m[0] * m[10] - m[2] * m[8]) * id, w[6] = (m[2] * m[4] - m[0] * m[6]) * id;
+    w[8] = c02 * id, w[9] = (m[1] * m[8] - m[0] * m[9]) * id, w[10] = (m[0] * m[5] - m[1] * m[4]) * id;
+    bool ok = true;
+    for (int r = 0; r < 3; ++r)
+    {
+        w[4 * r + 3] = -(w[4 * r] * m[3] + w[4 * r + 1] * m[7] + w[4 * r + 2] * m[11]);
+        for (int k = 0; k < 4; ++k) ok = ok && finite_d(w[4 * r + k]);
+    }
+    return ok;
+}
+__host__ __device__ __forceinline__ double norm_inf3(const double m[12])
+{
+    double n = 0.0;
+    for (int r = 0; r < 3; ++r) n = fmax(n, fabs(m[4 * r]) + fabs(m[4 * r + 1]) + fabs(m[4 * r + 2]));
+    return n;
+}
+
+// What an instance's transform m (binary32 entries held in double; live = they are finite and the object exists) gives every instanced
+// query: w = inverse(m) in double, wf = fl32(w) -- the stored W --, wd = wf in double, A = inverse(wd), kappa = |A| |wd| (row-sum norms).
+// Returns whether the instance is live (include/capsaicin_hip.h "Inert instances"); wf is all zero otherwise.
+__host__ __device__ __forceinline__ bool instance_inverse(const double m[12], bool live, double w[12], float wf[12], double wd[12], double A[12],
+                                                          double& nA, double& kappa, float max_condition)
+{
+    live = live && invert_affine(m, w);
+    for (int k = 0; k < 12; ++k) wf[k] = live ? (float)w[k] : 0.0f, wd[k] = (double)wf[k], live = live && finite_f(wf[k]);
+    live  = live && invert_affine(wd, A);
+    nA    = live ? norm_inf3(A) : 0.0;
+    kappa = nA * norm_inf3(wd);
+    return live && kappa <= (double)max_condition;
+}
+
+// g: a lower bound on the smallest singular value of m's 3x3 part, from w = inverse(m) in double.  S = w w^T is rotated towards its
+// diagonal by cyclic Jacobi sweeps (orthogonal similarities: the eigenvalues stay), then Gershgorin's discs bound its largest eigenvalue
+// from above WHATEVER the sweeps left off the diagonal: sigma_max(w)^2 <= max_i (S_ii + sum_j |S_ij|), and sigma_min(m) = 1 / sigma_max(w).
+// The sweeps only make the bound tight (five leave off-diagonal terms far below 1e-6 of the trace).  1e-6 relative is taken off for
+// everything done in double here and before (the inverse's own error is kappa x 2^-53, the rotations' a few 2^-53 each) and for the
+// rounding to binary32.
+__host__ __device__ __forceinline__ float near_sigma_min_bound(const double w[12])
+{
+    double s[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) s[i][j] = w[4 * i] * w[4 * j] + w[4 * i + 1] * w[4 * j + 1] + w[4 * i + 2] * w[4 * j + 2];
+    for (int sweep = 0; sweep < 5; ++sweep)
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q)
+            {
+                const double apq = s[p][q];
+                if (!(fabs(apq) > 0.0)) continue;
+                const double theta = (s[q][q] - s[p][p]) / (2.0 * apq);
+                const double t     = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+                const int    r = 3 - p - q;
+                const double app = s[p][p], aqq = s[q][q], arp = s[r][p], arq = s[r][q];
+                s[p][p] = app - t * apq, s[q][q] = aqq + t * apq;
+                s[p][q] = s[q][p] = 0.0;
+                s[r][p] = s[p][r] = c * arp - sn * arq;
+                s[r][q] = s[q][r] = sn * arp + c * arq;
+            }
+    double top = 0.0;
+    for (int i = 0; i < 3; ++i) top = fmax(top, fabs(s[i][0]) + fabs(s[i][1]) + fabs(s[i][2]));
+    if (!(top > 0.0) || !finite_d(top)) return 0.0f;
+    const float g = (float)((1.0 - 1e-6) / sqrt(top));
+    return finite_f(g) ? g : 0.0f;
+}
+
+// Xw: no world coordinate the contract's record arithmetic meets for a point of the object box [blo, bhi] exceeds it -- per row of m the
+// sum of the MAGNITUDES of the terms, so that it also bounds what cancels (an object far from its origin moved back to the world's).
+// Rounded upwards.
+__host__ __device__ __forceinline__ float near_world_extent(const double m[12], const double blo[3], const double bhi[3])
+{
+    double x = 0.0;
+    for (int r = 0; r < 3; ++r)
+    {
+        double row = fabs(m[4 * r + 3]);
+        for (int k = 0; k < 3; ++k) row += fabs(m[4 * r + k]) * fmax(fabs(blo[k]), fabs(bhi[k]));
+        x = fmax(x, row);
+    }
+    return nextafterf((float)x, INFINITY);
+}
+
+// the absolute part of the bound for point p (pmax = |p|_inf) against an instance of world extent xw
+__host__ __device__ __forceinline__ float near_slack(float pmax, float xw) { return (kNearC2 * kNearEps) * (pmax + xw); }
+
+// The squared distance beyond which a box is skipped while the best world distance is sqrt_best = sqrtf(best dist2): in world space (the
+// top level's boxes), and in the object space of an instance with g <= sigma_min.  Never below best itself; +inf while best is.
+__host__ __device__ __forceinline__ float near_bound2_world(float sqrt_best, float slack)
+{
+    const float b = (sqrt_best + slack) * (1.0f + kNearC1 * kNearEps);
+    return (b * b) * (1.0f + 4.0f * kNearEps);
+}
+__host__ __device__ __forceinline__ float near_bound2_object(float sqrt_best, float slack, float g)
+{
+    const float b = ((sqrt_best + slack) * (1.0f + kNearC1 * kNearEps)) / g;
+    return (b * b) * (1.0f + 4.0f * kNearEps);
+}
+
+// p' = W p + W_t, rows w0 .. w2 of the stored W: where the bottom-level boxes are measured from (not part of the contract)
+__host__ __device__ __forceinline__ void near_to_object(const float w[12], float px, float py, float pz, float& ox, float& oy, float& oz)
+{
+    ox = ((w[0] * px + w[1] * py) + w[2] * pz) + w[3];
+    oy = ((w[4] * px + w[5] * py) + w[6] * pz) + w[7];
+    oz = ((w[8] * px + w[9] * py) + w[10] * pz) + w[11];
+}
+
+// squared distance from p to the box [lo, hi], 0 inside
+__host__ __device__ __forceinline__ float box_dist2(float px, float py, float pz, float lox, float loy, float loz, float hix, float hiy, float hiz)
+{
+    const float dx = fmaxf(fmaxf(lox - px, px - hix), 0.f), dy = fmaxf(fmaxf(loy - py, py - hiy), 0.f), dz = fmaxf(fmaxf(loz - pz, pz - hiz), 0.f);
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// the walk's test: a strict >, so that a box at exactly the bound is opened (a NaN distance is opened too)
+__host__ __device__ __forceinline__ bool near_skip(float box_d2, float bound2) { return box_d2 > bound2; }
+}  // namespace cap

@@ -16,6 +16,7 @@
 #include <memory>
 
 #include "cap_context.h"
+#include "cap_near.h"
 #include "cap_wide.h"
 #include "query_ranges.h"
 
@@ -510,6 +511,34 @@ int cap_debug_query_ranges(uint64_t n, uint32_t count, const uint64_t* base, con
     }
     char msg[256];
     return query_ranges_ok("cap_debug_query_ranges", n, r, count, msg, sizeof(msg)) ? CAP_OK : fail(CAP_ERR_INVALID_ARG, "%s", msg);
+}
+
+// The per-instance data and the skip predicate of cap_closest_instances (cap_near.h: the functions k_instance_setup and k_closest_inst
+// run) for one transform, one object-space box, one world point and one best dist2.  No context, no device: tests/test_closest_instances.py.
+int cap_debug_closest_instance_bound(const float* transform, const float* box_lo, const float* box_hi, const float* point, float best_dist2,
+                                     float* world_to_object, float* g, float* xw, float* slack, uint32_t* skip)
+{
+    if (!transform || !box_lo || !box_hi || !point) return fail(CAP_ERR_INVALID_ARG, "cap_debug_closest_instance_bound: NULL input");
+    double m[12], w[12], wd[12], A[12], nA, kappa, blo[3], bhi[3];
+    float  wf[12];
+    bool   live = true;
+    for (int k = 0; k < 12; ++k) m[k] = (double)transform[k], live = live && finite_d(m[k]);
+    for (int k = 0; k < 3; ++k) blo[k] = (double)box_lo[k], bhi[k] = (double)box_hi[k];
+    live = instance_inverse(m, live, w, wf, wd, A, nA, kappa, (float)CAP_INSTANCE_MAX_CONDITION);
+    const float gi = live ? near_sigma_min_bound(w) : 0.0f, xi = live ? near_world_extent(m, blo, bhi) : 0.0f;
+    const float pmax = fmaxf(fabsf(point[0]), fmaxf(fabsf(point[1]), fabsf(point[2])));
+    const float sl   = near_slack(pmax, xi);
+    float       ox, oy, oz;
+    near_to_object(wf, point[0], point[1], point[2], ox, oy, oz);
+    const float bd2 = box_dist2(ox, oy, oz, box_lo[0], box_lo[1], box_lo[2], box_hi[0], box_hi[1], box_hi[2]);
+    if (world_to_object)
+        for (int k = 0; k < 12; ++k) world_to_object[k] = wf[k];
+    if (g) *g = gi;
+    if (xw) *xw = xi;
+    if (slack) *slack = sl;
+    // an inert instance is never entered: nothing to skip
+    if (skip) *skip = live && near_skip(bd2, near_bound2_object(sqrtf(best_dist2), sl, gi)) ? 1u : 0u;
+    return CAP_OK;
 }
 
 int cap_ctx_create(int device_id, void* hip_stream, CapContext** out_ctx)

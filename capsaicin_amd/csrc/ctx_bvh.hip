@@ -161,7 +161,7 @@ static int instances_rebuild(CapContext* c)
         a.objects = c->scene_object.p, a.n_objects = 1;
     }
     a.object_index = c->inst_obj_on ? c->inst_obj.p : nullptr;
-    a.rec = c->inst_rec.p, a.box = c->inst_box.p, a.tlas = c->inst_tlas.p;
+    a.rec = c->inst_rec.p, a.box = c->inst_box.p, a.tlas = c->inst_tlas.p, a.near = c->inst_near.p;
     a.keys[0] = c->inst_keys[0].p, a.keys[1] = c->inst_keys[1].p, a.vals[0] = c->inst_vals[0].p, a.vals[1] = c->inst_vals[1].p;
     a.hist = c->inst_hist.p, a.scan = c->inst_scan.p, a.misc = c->inst_misc.p;
     launch_instances_build(c->stream, a);
@@ -531,12 +531,13 @@ int instances_set(CapContext* c, const char* what, const CapInstanceDesc* descs,
     }
     uint32_t       off[kTlasMaxLevels], total = 0;
     const uint32_t top = tlas_layout(count, off, &total);
-    if (c->inst_desc.n < 4 * (size_t)count || c->inst_misc.n < 8 || c->inst_obj.n < count)
+    if (c->inst_desc.n < 4 * (size_t)count || c->inst_misc.n < 8 || c->inst_obj.n < count || c->inst_near.n < count)
     {
         HIP_TRY(hipStreamSynchronize(c->stream));  // (grown buffers replace ones an earlier query may still be reading)
         HIP_TRY(c->inst_desc.ensure(4 * (size_t)count));
         HIP_TRY(c->inst_rec.ensure(4 * (size_t)count));
         HIP_TRY(c->inst_box.ensure(2 * (size_t)count));
+        HIP_TRY(c->inst_near.ensure(count));
         HIP_TRY(c->inst_tlas.ensure(2 * ((size_t)count + (size_t)count + 2 * kTlasMaxLevels + 2)));
         for (int k = 0; k < 2; ++k)
         {

@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_closest_points_multi; point_query.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_closest_points_multi, cap_closest_instances; point_query.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -329,6 +329,31 @@ int closest_points_multi(CapContext* c, const char* what, const CapPointDesc* po
         return run.traced("k_closest_points_multi", first);
     });
 }
+
+// cap_closest_instances (point_query.hip k_closest_inst): closest_points' options over trace_instances' state and pools
+int closest_instances(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, CapClosest* out, uint32_t* inst, const CapTraceOptions* options)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a point", what, options->ray_flags);
+    QueryFilter flt;
+    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
+    if (const int rc = query_state(c, what)) return rc;
+    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
+    if (n == 0) return CAP_OK;
+    if (!points || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, sizeof(CapClosest), 16),
+                                              range("instances", inst, sizeof(uint32_t), 4)}))
+        return rc;
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    use_instance_pools(run);
+    return for_each_chunk(run, points, n, [&](const QueryArgs& q, uint64_t first) {
+        const ClosestInstArgs a{ClosestArgs{q.rays, q.n, reinterpret_cast<float4*>(out + first), 0.f}, at(inst, first), c->inst_desc.p, c->inst_near.p,
+                                c->inst_misc.p + 7};
+        launch_closest_instances(run.cfg, run.bvh, a, run.tl, flt.f, run.depth);
+        return run.traced("k_closest_inst", first);
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -391,5 +416,11 @@ int cap_closest_points_multi(CapContext* c, const CapPointDesc* device_points, u
                              uint32_t multi_flags, const CapTraceOptions* options)
 {
     return closest_points_multi(c, "cap_closest_points_multi", device_points, n, k, device_out, device_counts, multi_flags, options);
+}
+
+int cap_closest_instances(CapContext* c, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, uint32_t* device_instances,
+                          const CapTraceOptions* options)
+{
+    return closest_instances(c, "cap_closest_instances", device_points, n, device_out, device_instances, options);
 }
 }  // extern "C"

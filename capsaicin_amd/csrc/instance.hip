@@ -29,6 +29,7 @@
 //     kappa <= CAP_INSTANCE_MAX_CONDITION = 4096, the domain of the proof; an instance beyond it is inert.  The interval test keeps
 //     the binary tree's relative slack (4e-7 >= 6 eps: one subtraction, one rounded reciprocal, one product per plane).
 #include "cap_kernels.h"
+#include "cap_near.h"
 #include "cap_trace.h"
 
 #include "../../include/capsaicin_hip.h"
@@ -46,39 +47,15 @@ __device__ __forceinline__ uint32_t inst_float_to_ordered(float f)
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float inst_ordered_to_float(uint32_t o) { return u2f((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
-__device__ __forceinline__ bool  finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }
-__device__ __forceinline__ bool  finite_f(float x) { return fabsf(x) <= 3.40282347e38f; }
 
-// inverse of the affine map m (row-major 3x4) in double; false when it is singular or the result is not finite
-__device__ __forceinline__ bool invert_affine(const double m[12], double w[12])
-{
-    const double c00 = m[5] * m[10] - m[6] * m[9], c01 = m[6] * m[8] - m[4] * m[10], c02 = m[4] * m[9] - m[5] * m[8];
-    const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
-    if (!(fabs(det) > 0.0) || !finite_d(det)) return false;
-    const double id = 1.0 / det;
-    w[0] = c00 * id, w[1] = (m[2] * m[9] - m[1] * m[10]) * id, w[2] = (m[1] * m[6] - m[2] * m[5]) * id;
-    w[4] = c01 * id, w[5] = (m[0] * m[10] - m[2] * m[8]) * id, w[6] = (m[2] * m[4] - m[0] * m[6]) * id;
-    w[8] = c02 * id, w[9] = (m[1] * m[8] - m[0] * m[9]) * id, w[10] = (m[0] * m[5] - m[1] * m[4]) * id;
-    bool ok = true;
-    for (int r = 0; r < 3; ++r)
-    {
-        w[4 * r + 3] = -(w[4 * r] * m[3] + w[4 * r + 1] * m[7] + w[4 * r + 2] * m[11]);
-        for (int k = 0; k < 4; ++k) ok = ok && finite_d(w[4 * r + k]);
-    }
-    return ok;
-}
-__device__ __forceinline__ double norm_inf3(const double m[12])
-{
-    double n = 0.0;
-    for (int r = 0; r < 3; ++r) n = fmax(n, fabs(m[4 * r]) + fabs(m[4 * r + 1]) + fabs(m[4 * r + 2]));
-    return n;
-}
-
-// Per instance: W = fl32(inverse(M)), A = inverse(W), kappa, the inert decision, the padded world box and its inflation factor.
+// Per instance: W = fl32(inverse(M)), A = inverse(W), kappa, the inert decision, the padded world box and its inflation factor
+// (cap_near.h instance_inverse), and what cap_closest_instances prunes with: g <= sigma_min(M) and the world extent Xw (a.near, the
+// largest Xw of the table in a.misc[7]; both 0 for an inert instance).
 __global__ __launch_bounds__(kBlock) void k_instance_setup(InstanceBuildArgs a)
 {
     float    clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
     uint32_t inert = 0;
+    float    xw_max = 0.0f;
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += gridDim.x * kBlock)
     {
         const float* d = a.descs + 16 * (size_t)i;
@@ -89,13 +66,9 @@ __global__ __launch_bounds__(kBlock) void k_instance_setup(InstanceBuildArgs a)
         const InstObject& ob   = a.objects[live ? obj : 0u];
         for (int k = 0; k < 12; ++k) m[k] = (double)d[k], live = live && finite_d(m[k]);
         const uint32_t mask = f2u(d[12]) & 0xFFu;
-        live                = live && invert_affine(m, w);
-        float wf[12];
-        for (int k = 0; k < 12; ++k) wf[k] = live ? (float)w[k] : 0.0f, wd[k] = (double)wf[k], live = live && finite_f(wf[k]);
-        live               = live && invert_affine(wd, A);
-        const double nA    = live ? norm_inf3(A) : 0.0;
-        const double kappa = nA * norm_inf3(wd);
-        live               = live && kappa <= CAP_INSTANCE_MAX_CONDITION;
+        float          wf[12];
+        double         nA, kappa;
+        live = instance_inverse(m, live, w, wf, wd, A, nA, kappa, (float)CAP_INSTANCE_MAX_CONDITION);
         float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, kf = -1.0f;
         if (live)
         {
@@ -123,11 +96,13 @@ __global__ __launch_bounds__(kBlock) void k_instance_setup(InstanceBuildArgs a)
             }
             kf = (float)(2.0 * kInstSlack * kInstEps * kappa * 1.000001);
         }
+        float g = 0.0f, xw = 0.0f;
+        if (live) g = near_sigma_min_bound(w), xw = near_world_extent(m, ob.blo, ob.bhi);
         if (!live)
         {
             for (int k = 0; k < 12; ++k) wf[k] = 0.0f;
             for (int r = 0; r < 3; ++r) lo[r] = INFINITY, hi[r] = -INFINITY;
-            kf = -1.0f;
+            kf = -1.0f, g = 0.0f, xw = 0.0f;
             ++inert;
         }
         else
@@ -136,6 +111,8 @@ __global__ __launch_bounds__(kBlock) void k_instance_setup(InstanceBuildArgs a)
                 const float c = (lo[r] + hi[r]) * 0.5f;
                 if (finite_f(c)) clo[r] = fminf(clo[r], c), chi[r] = fmaxf(chi[r], c);
             }
+        xw_max    = fmaxf(xw_max, xw);
+        a.near[i] = make_float2(g, xw);
         a.rec[4 * (size_t)i + 0] = make_float4(wf[0], wf[1], wf[2], wf[3]);
         a.rec[4 * (size_t)i + 1] = make_float4(wf[4], wf[5], wf[6], wf[7]);
         a.rec[4 * (size_t)i + 2] = make_float4(wf[8], wf[9], wf[10], wf[11]);
@@ -156,6 +133,9 @@ __global__ __launch_bounds__(kBlock) void k_instance_setup(InstanceBuildArgs a)
     }
     for (int off = 32; off > 0; off >>= 1) inert += (uint32_t)__shfl_down((int)inert, off);
     if ((threadIdx.x & 63u) == 0 && inert) atomicAdd(&a.misc[6], inert);
+    // (non-negative floats order as their bits)
+    for (int off = 32; off > 0; off >>= 1) xw_max = fmaxf(xw_max, __shfl_down(xw_max, off));
+    if ((threadIdx.x & 63u) == 0 && xw_max > 0.0f) atomicMax(&a.misc[7], f2u(xw_max));
 }
 
 __device__ __forceinline__ uint32_t inst_expand_bits10(uint32_t v)

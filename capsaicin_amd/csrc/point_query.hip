@@ -16,8 +16,11 @@
 //
 // The multi form (cap_closest_points_multi, k_closest_points_multi) is the same walk with the sorted list HitList<K> of cap_hit_list.h
 // in the place of the single best pair; "best" above reads "k-th best", slot K - 1 of the list.
+//
+// The instanced form (cap_closest_instances, k_closest_inst) is at the end of the file: nearest in world space over the instance table.
 #include "cap_hit_list.h"
 #include "cap_kernels.h"
+#include "cap_near.h"  // box_dist2, and the bound of the instanced form
 
 namespace cap
 {
@@ -103,13 +106,6 @@ __device__ __forceinline__ ClosestPoint closest_record(const float4 t0, const fl
     c.d2 = dot_c(dx, dy, dz, dx, dy, dz);
     c.x = t0.x + mx, c.y = t0.y + my, c.z = t0.z + mz;
     return c;
-}
-
-// squared distance from p to the box [lo, hi], 0 inside
-__device__ __forceinline__ float box_dist2(float px, float py, float pz, float lox, float loy, float loz, float hix, float hiy, float hiz)
-{
-    const float dx = fmaxf(fmaxf(lox - px, px - hix), 0.f), dy = fmaxf(fmaxf(loy - py, py - hiy), 0.f), dz = fmaxf(fmaxf(loz - pz, pz - hiz), 0.f);
-    return (dx * dx + dy * dy) + dz * dz;
 }
 
 // The pruning bound of a best squared distance: 16 eps holds the proof's 8 eps, sqrtf's error and the roundings of the four operations here.
@@ -385,6 +381,223 @@ void launch_closest_multi(const LaunchCfg& cfg, const BvhDev& b, const ClosestMu
     default: launch_closest_multi_s<STACK, 16>(cfg, b, m, filter, f); break;
     }
 }
+
+// ---- over the instance table (cap_closest_instances) ----
+// For every point the pair (instance, triangle) minimal in (dist2, instance, triangle), dist2 the cascade's on the WORLD record
+//   v0w_r = fl(dot_c(M_r.xyz, v0) + M_r.w),  e1w_r = dot_c(M_r.xyz, e1),  e2w_r = dot_c(M_r.xyz, e2)
+// of the instance's transform M as the caller gave it (a.descs), no fused multiply-add: include/capsaicin_hip.h has the contract.
+// One loop with three kinds of step, as k_query_inst (instance.hip), so that the lanes of a wave that are at the top level advance
+// while others are inside an instance:
+//   * a top-level node: the implicit tree without a stack, `pending` bits per level; the two children ordered by the squared distance
+//     from p to their stored world boxes and pruned against bound2_top.  The two instances under a level-1 node wait in
+//     (todo0, todo1), the nearer first, each tested again against the bound as it stands when its turn comes;
+//   * entering an instance: mask, M, (g, Xw), the root, and p' = W p + W_t, which only the pruning sees;
+//   * a bottom-level node or leaf: k_closest_points' walk of the object's tree with its LDS stack of (box distance, child), the boxes
+//     measured from p' and pruned against bound2, the world bound mapped into object space through g <= sigma_min(M)
+//     (cap_near.h near_bound2_object).  A leaf builds the world record and runs the cascade.
+// Both bounds are computed again only when `best` improves; every test is a strict >, so an instance, subtree or triangle at exactly
+// the best distance is still opened and the lower (instance, triangle) wins whatever the visiting order.  DESIGN.md "Closest-point
+// queries over instances" has the argument that no skipped box holds a candidate.
+struct WorldRecord
+{
+    float4 t0, t1, t2;
+};
+__device__ __forceinline__ WorldRecord world_record(const float4 m0, const float4 m1, const float4 m2, const float4 t0, const float4 t1, const float4 t2)
+{
+    WorldRecord w;
+    w.t0 = make_float4(dot_c(m0.x, m0.y, m0.z, t0.x, t0.y, t0.z) + m0.w, dot_c(m1.x, m1.y, m1.z, t0.x, t0.y, t0.z) + m1.w,
+                       dot_c(m2.x, m2.y, m2.z, t0.x, t0.y, t0.z) + m2.w, dot_c(m0.x, m0.y, m0.z, t0.w, t1.x, t1.y));
+    w.t1 = make_float4(dot_c(m1.x, m1.y, m1.z, t0.w, t1.x, t1.y), dot_c(m2.x, m2.y, m2.z, t0.w, t1.x, t1.y), dot_c(m0.x, m0.y, m0.z, t1.z, t1.w, t2.x),
+                       dot_c(m1.x, m1.y, m1.z, t1.z, t1.w, t2.x));
+    w.t2 = make_float4(dot_c(m2.x, m2.y, m2.z, t1.z, t1.w, t2.x), 0.f, 0.f, 0.f);
+    return w;
+}
+
+// Workgroups per CU: the stack's LDS (and the 104 bytes of level offsets, which take the fifth workgroup of STACK = 16 away)
+constexpr int closest_inst_blocks(int STACK) { return STACK <= 16 ? 4 : STACK <= 24 ? 3 : STACK <= 32 ? 2 : 1; }
+
+// FILTER: a mesh-mask table is installed (f.tri_mask by global id); the instance's own mask is tested either way
+template <int STACK, bool FILTER>
+__global__ __launch_bounds__(kBlock, closest_inst_blocks(STACK)) void k_closest_inst(BvhDev bvh, ClosestInstArgs ia, TlasDev tl, RayFilter f)
+{
+    __shared__ uint2    lds_stack[STACK * kBlock];
+    __shared__ uint32_t lds_off[kTlasMaxLevels + 1];
+    uint2* const        stack = lds_stack + threadIdx.x;
+    if (threadIdx.x <= tl.top) lds_off[threadIdx.x] = tl.level_off[threadIdx.x];
+    __syncthreads();
+    const ClosestArgs& a      = ia.a;
+    const float        xw_all = u2f(ia.xw_max[0]);  // the largest Xw of the table: the top level's slack holds for every instance
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < a.n; j += gridDim.x * kBlock)
+    {
+        const float4 p = a.points[j];
+        if (!point_ok(p))
+        {
+            a.out[2 * (size_t)j]     = make_float4(0.f, 0.f, 0.f, 0.f);
+            a.out[2 * (size_t)j + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
+            if (ia.inst_out) ia.inst_out[j] = kInvalidId;
+            continue;
+        }
+        const float r2   = p.w * p.w;
+        const float pmax = fmaxf(fabsf(p.x), fmaxf(fabsf(p.y), fabsf(p.z)));
+        float       best = r2, sqrt_best = sqrtf(r2);
+        uint32_t    best_gid = kInvalidId, best_inst = kInvalidId;
+        const float slack_top  = near_slack(pmax, xw_all);
+        float       bound2_top = near_bound2_world(sqrt_best, slack_top);
+        // top level: the node whose two children (level - 1, 2 idx + {0, 1}) are tested next
+        uint32_t level = tl.top + 1u, idx = 0u, pending = 0u;
+        bool     top_done = false;
+        uint32_t todo0 = kInvalidId, todo1 = kInvalidId;
+        float    todo0_d = 0.f, todo1_d = 0.f;
+        // bottom level
+        bool     in_blas = false;
+        float4   m0 = make_float4(0.f, 0.f, 0.f, 0.f), m1 = m0, m2 = m0;
+        float    ox = 0.f, oy = 0.f, oz = 0.f, g = 1.f, slack = 0.f, bound2 = 0.f;
+        uint32_t inst = 0u, imask = 0u;
+        int      node = 0, sp = 0;
+        bool     walk = bvh.tri_count != 0u;
+        while (walk)
+        {
+            if (in_blas)
+            {
+                if (node >= 0)
+                {
+                    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2],
+                                 q3 = bvh.nodes[4 * node + 3];
+                    const float b0 = box_dist2(ox, oy, oz, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
+                    const float b1 = box_dist2(ox, oy, oz, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
+                    const int   c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+                    const bool  k0 = !near_skip(b0, bound2), k1 = !near_skip(b1, bound2);
+                    if (k0 && k1)
+                    {
+                        const bool swap = b1 < b0;
+                        if (sp < STACK) stack[(sp++) * kBlock] = make_uint2(f2u(swap ? b0 : b1), (uint32_t)(swap ? c0 : c1));
+                        node = swap ? c1 : c0;
+                        continue;
+                    }
+                    if (k0 || k1)
+                    {
+                        node = k0 ? c0 : c1;
+                        continue;
+                    }
+                }
+                else
+                {
+                    const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                    for (uint32_t leaf = first; leaf <= last; ++leaf)
+                    {
+                        const uint32_t gid = f2u(bvh.tris[4 * (size_t)leaf + 3].x);
+                        if constexpr (FILTER)
+                            if ((f.tri_mask[gid] & imask) == 0u) continue;
+                        const WorldRecord w  = world_record(m0, m1, m2, bvh.tris[4 * (size_t)leaf + 0], bvh.tris[4 * (size_t)leaf + 1], bvh.tris[4 * (size_t)leaf + 2]);
+                        const float       d2 = closest_dist2(w.t0, w.t1, w.t2, p.x, p.y, p.z);
+                        if (d2 < best || (d2 == best && (inst < best_inst || (inst == best_inst && gid < best_gid))))
+                        {
+                            if (d2 < best)
+                            {
+                                sqrt_best  = sqrtf(d2);
+                                bound2     = near_bound2_object(sqrt_best, slack, g);
+                                bound2_top = near_bound2_world(sqrt_best, slack_top);
+                            }
+                            best = d2, best_gid = gid, best_inst = inst;
+                        }
+                    }
+                }
+                in_blas = false;
+                while (sp > 0)
+                {
+                    const uint2 e = stack[(--sp) * kBlock];
+                    if (!near_skip(u2f(e.x), bound2))
+                    {
+                        node = (int)e.y, in_blas = true;
+                        break;
+                    }
+                }
+                continue;
+            }
+            if (todo0 != kInvalidId)
+            {
+                // enter an instance, if its box still passes against the bound as it is now
+                inst             = todo0;
+                const bool still = !near_skip(todo0_d, bound2_top);
+                todo0 = todo1, todo0_d = todo1_d, todo1 = kInvalidId;
+                if (!still) continue;
+                const float4 w3 = tl.rec[4 * (size_t)inst + 3];
+                imask           = f2u(w3.x) & f.mask;  // desc.mask & inclusion (0 for an inert instance): the mesh byte joins it per triangle
+                if (imask == 0u) continue;
+                const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
+                const float  w[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
+                near_to_object(w, p.x, p.y, p.z, ox, oy, oz);
+                m0 = ia.descs[4 * (size_t)inst], m1 = ia.descs[4 * (size_t)inst + 1], m2 = ia.descs[4 * (size_t)inst + 2];
+                const float2 nr = ia.near[inst];
+                g = nr.x, slack = near_slack(pmax, nr.y);
+                bound2  = near_bound2_object(sqrt_best, slack, g);
+                node    = (int)f2u(w3.y), sp = 0;
+                in_blas = true;
+                continue;
+            }
+            if (top_done) break;
+            const float4* c = tl.tlas + 2 * (size_t)(lds_off[level - 1u] + 2u * idx);
+            const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
+            const float   d0 = box_dist2(p.x, p.y, p.z, lo0.x, lo0.y, lo0.z, hi0.x, hi0.y, hi0.z);
+            const float   d1 = box_dist2(p.x, p.y, p.z, lo1.x, lo1.y, lo1.z, hi1.x, hi1.y, hi1.z);
+            // (a record with k < 0 holds nothing: an inert instance or the padding of a level)
+            const bool h0 = lo0.w >= 0.0f && !near_skip(d0, bound2_top), h1 = lo1.w >= 0.0f && !near_skip(d1, bound2_top);
+            const bool far_first = h0 && h1 && d1 < d0;
+            if (level > 1u)
+            {
+                if (h0 || h1)
+                {
+                    if (h0 && h1) pending |= 1u << (level - 1u);
+                    idx   = 2u * idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
+                    level = level - 1u;
+                    continue;
+                }
+            }
+            else if (h0 || h1)
+            {
+                // the children are instances: the nearer box first
+                const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
+                if (h0 && h1)
+                    todo0 = far_first ? i1 : i0, todo0_d = far_first ? d1 : d0, todo1 = far_first ? i0 : i1, todo1_d = far_first ? d0 : d1;
+                else
+                    todo0 = h0 ? i0 : i1, todo0_d = h0 ? d0 : d1;
+            }
+            const uint32_t owed = pending >> level;
+            if (owed == 0u)
+            {
+                top_done = true;
+                continue;
+            }
+            const uint32_t up = (uint32_t)__builtin_ctz(owed);
+            idx     = (idx >> up) ^ 1u;
+            level   = level + up;
+            pending = pending & ~(1u << level);
+        }
+        if (ia.inst_out) ia.inst_out[j] = best_inst;
+        if (best_gid == kInvalidId)
+        {
+            a.out[2 * (size_t)j]     = make_float4(0.f, 0.f, 0.f, r2);
+            a.out[2 * (size_t)j + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
+            continue;
+        }
+        // the winner's record again from the records in id order and its instance's transform: the same operations, the same bits
+        const float4*      rec = bvh.tris_by_id + 4 * (size_t)best_gid;
+        const float4*      md  = ia.descs + 4 * (size_t)best_inst;
+        const WorldRecord  w   = world_record(md[0], md[1], md[2], rec[0], rec[1], rec[2]);
+        const ClosestPoint c   = closest_record(w.t0, w.t1, w.t2, p.x, p.y, p.z);
+        a.out[2 * (size_t)j]     = make_float4(c.x, c.y, c.z, c.d2);
+        a.out[2 * (size_t)j + 1] = make_float4(c.u, c.v, u2f(best_gid), u2f(c.feature));
+    }
+}
+
+template <int STACK, bool FILTER>
+void launch_closest_inst_s(const LaunchCfg& cfg, const BvhDev& b, const ClosestInstArgs& a, const TlasDev& tl, const RayFilter& f)
+{
+    uint32_t want = (a.a.n + kBlock - 1) / kBlock;
+    if (want == 0) want = 1;
+    hipLaunchKernelGGL((k_closest_inst<STACK, FILTER>), dim3(resident_grid<k_closest_inst<STACK, FILTER>>(cfg, want)), dim3(kBlock), 0, cfg.stream, b, a,
+                       tl, f);
+}
 }  // namespace
 
 void launch_closest_points(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const RayFilter* f, uint32_t depth)
@@ -432,5 +645,33 @@ void launch_closest_points_multi(const LaunchCfg& cfg, const BvhDev& bvh, const 
         launch_closest_multi<32>(cfg, b, m, filter, rf);
     else
         launch_closest_multi<64>(cfg, b, m, filter, rf);
+}
+
+void launch_closest_instances(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstArgs& a, const TlasDev& tl, const RayFilter& f, uint32_t depth)
+{
+    const bool filter = f.tri_mask != nullptr;
+    // the bottom-level stack: a walk pushes at most one entry per level it descends
+#define CAP_CLOSEST_INST(S)                                   \
+    if (filter)                                               \
+        launch_closest_inst_s<S, true>(cfg, bvh, a, tl, f);   \
+    else                                                      \
+        launch_closest_inst_s<S, false>(cfg, bvh, a, tl, f);
+    if (depth <= 16)
+    {
+        CAP_CLOSEST_INST(16)
+    }
+    else if (depth <= 24)
+    {
+        CAP_CLOSEST_INST(24)
+    }
+    else if (depth <= 32)
+    {
+        CAP_CLOSEST_INST(32)
+    }
+    else
+    {
+        CAP_CLOSEST_INST(64)
+    }
+#undef CAP_CLOSEST_INST
 }
 }  // namespace cap

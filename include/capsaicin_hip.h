@@ -323,6 +323,16 @@ int cap_debug_pair_ids_dense(const float* pair_records, uint32_t pair_count, uin
  * every array is aligned, ends inside the address space and shares no byte with another one; else CAP_ERR_INVALID_ARG with the entry
  * points' message in cap_last_error().  Needs no device. */
 int cap_debug_query_ranges(uint64_t n, uint32_t count, const uint64_t* base, const uint64_t* stride, const uint32_t* align);
+/* The pruning arithmetic of cap_closest_instances (below) for ONE instance transform (12 floats, row-major 3x4), one object-space box
+ * (box_lo, box_hi: 3 floats each), one world point (3 floats) and one best squared distance, by the very functions the instance setup
+ * and the query kernel run.  Outputs, each may be NULL: world_to_object = the 12 floats of W as the table would store them; g = the
+ * proven lower bound on the smallest singular value of the transform's 3x3 part; xw = the world extent Xw of the box under the
+ * transform (no |coordinate| the world-record arithmetic meets exceeds it); slack = the absolute part of the bound for this point,
+ * 96 * 2^-24 * (|point|_inf + xw); skip = 1 if the walk would skip the box while the best dist2 is best_dist2, else 0.  An inert
+ * transform (the rule of cap_instances_set) gives W = 0, g = 0, xw = 0 and skip = 0.  CAP_ERR_INVALID_ARG for a NULL input.  Needs no
+ * device. */
+int cap_debug_closest_instance_bound(const float* transform, const float* box_lo, const float* box_hi, const float* point, float best_dist2,
+                                     float* world_to_object, float* g, float* xw, float* slack, uint32_t* skip);
 /* Traversal strategy of the trace kernels (same hits either way): AUTO picks EXHAUSTIVE for scenes of at most 64
  * triangles (wave-uniform test of every triangle, no stack) and STACK (LBVH + per-lane LDS stack) otherwise. */
 typedef enum CapTraversal
@@ -507,8 +517,8 @@ int cap_trace_rays_multi_ex(CapContext* ctx, const CapRayDesc* device_rays, uint
  * are stale after cap_scene_update_vertices.  options: instance_mask and the mesh-mask table act exactly as in the ray queries (a mesh
  * with mask 0 is invisible here too); any ray_flags bit is CAP_ERR_INVALID_ARG (facing and first hit mean nothing for a point), as are
  * non-zero reserved words and instance_mask > 0xFF; NULL or all-zero is the plain call.
- * Not covered: instances and objects (a non-rigid transform does not preserve nearest), per-point masks, the sign of the
- * distance (`feature` is what a caller needs to build it from the normals of the face, edge or vertex). */
+ * Not covered: per-point masks, the sign of the distance (`feature` is what a caller needs to build it from the normals of the face,
+ * edge or vertex).  Instances and objects: cap_closest_instances below, nearest in world space. */
 typedef struct CapPointDesc /* 16 B */
 {
     float point[3];
@@ -676,6 +686,52 @@ int cap_trace_instances_occlusion(CapContext* ctx, const CapRayDesc* device_rays
 int cap_trace_instances_multi(CapContext* ctx, const CapRayDesc* device_rays, uint64_t n, uint32_t k, CapHit* device_hits,
                               uint32_t* device_instances, uint32_t* device_counts, uint32_t multi_flags,
                               const CapTraceOptions* options /* may be NULL */);
+
+/* ---- closest-point queries over instances: the nearest (instance, triangle) to a point, in WORLD space ----
+ * cap_closest_points over the instance table of cap_instances_set(_ex): proximity and collision tests, ICP, snapping and distance
+ * fields against scenes built from instances, where a rigid-motion frame costs one cap_instances_set and no rebuild.  "Nearest" is
+ * defined where the caller means it, in world space, on the instance's TRANSFORMED triangle -- an affine transform that is not rigid
+ * does not preserve nearest, so the object-space answer would be a different one.  Any live instance works: rotation, non-uniform
+ * scale, shear, mirror.
+ *
+ * World record.  For instance i and triangle g take M = desc[i].transform exactly as the caller gave it (binary32, row-major 3x4; NOT
+ * the stored inverse W the ray queries are defined from) and the stored intersection record (v0, e1, e2) of g.  Per row r of M:
+ *   v0w_r = fl(dot_c(M_r.xyz, v0) + M_r.w)     e1w_r = dot_c(M_r.xyz, e1)     e2w_r = dot_c(M_r.xyz, e2)
+ *   dot_c(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z
+ * dot_c is the POINT queries' dot product: every operation one rounded binary32 operation in the order written, and -- unlike the
+ * instanced ray transform -- no fused multiply-add anywhere in this query, so that a vectorised float32 brute force is bit-identical.
+ * Per-triangle function: cap_closest_points' Voronoi cascade, unchanged, applied to (v0w, e1w, e2w) and the world point p; it gives
+ * dist2, u, v, feature and point = v0w + m.
+ *
+ * Candidates.  A pair (i, g) is a candidate iff instance i is not inert; with an object table, g is a triangle of i's object;
+ * desc[i].mask & mesh_mask[m] & instance_mask != 0 for g's mesh m (the instanced ray rule; instance_mask = 0 means 0xFF);
+ * and dist2 <= r2, r2 = fl(radius * radius).  A NaN dist2 is never a candidate.
+ * Answer: the candidate minimal in (dist2, i, g) lexicographic order; it depends on neither tree nor on the visiting order.
+ * device_out[j] is a CapClosest with point = the world-space closest point, dist2 = the world-space squared distance, (u, v) = the
+ * barycentric weights (they address the object-space triangle as well), triangle = the scene's global triangle id, feature as in
+ * cap_closest_points.  device_instances[j] (may be NULL) is the table index, 0xFFFFFFFF on a miss.  The miss record is exactly
+ * cap_closest_points': (0, 0, 0, r2, 0, 0, 0xFFFFFFFF, 0); degenerate points (a non-finite coordinate, a NaN or negative radius) are
+ * not traversed and give the miss record with dist2 = 0.
+ *
+ * Identities (each one is tested):
+ *   1. one identity instance, no negative zero in the scene: the records are bit-identical to cap_closest_points';
+ *   2. translations and vertices on a common power-of-two grid (every sum exact): the records equal cap_closest_points' over the
+ *      flattened scene, flat id = i * T + g for T triangles;
+ *   3. M (linear part and translation), and the point and radius, all scaled by 2^k: dist2 scales by 4^k and point by 2^k; u, v, feature
+ *      and the winner are unchanged, absent under- and overflow.
+ *
+ * Conventions are cap_closest_points' and cap_trace_instances': device pointers on the context's GPU, points and output 16-byte
+ * aligned, instances 4-byte aligned, no overlap between any two of the three ranges; asynchronous on the context stream and ordered
+ * behind a render's second lane; n above 2^24 split into launches, n = 0 does nothing; nothing is written on an error; nothing of the
+ * render's state is touched.  CAP_ERR_STATE before cap_bvh_build, while the trees are stale after cap_scene_update_vertices, and
+ * without an instance table.  CAP_ERR_INVALID_ARG for any ray_flags bit, non-zero reserved words, instance_mask > 0xFF, NULL points or
+ * output, misalignment, overlap.
+ * Pruning never decides: the top-level boxes and the objects' trees are pruned with a bound that is proven conservative for every
+ * live instance (DESIGN.md "Closest-point queries over instances"; cap_debug_closest_instance_bound shows its arithmetic).
+ * Not covered: k nearest, counts and paging over instances (cap_closest_points_multi has no instanced form yet), per-point masks, the
+ * sign of the distance, the wide view. */
+int cap_closest_instances(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out,
+                          uint32_t* device_instances /* may be NULL */, const CapTraceOptions* options /* may be NULL */);
 
 /* ---- objects: per-mesh-range bottom-level trees for the instanced queries ----
  * An object is the mesh range [first_mesh, first_mesh + mesh_count) of the uploaded scene: mesh_count >= 1, at least one triangle,

@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
-"""Throughput of the closest-point queries (cap_closest_points, cap_closest_points_multi) on the 262 k-triangle hall -- not part of
-bench.py, no pass mark.
+"""Throughput of the closest-point queries (cap_closest_points, cap_closest_points_multi, cap_closest_instances) on the 262 k-triangle
+hall -- not part of bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
-                                     [--k K [--counts]]
+                                     [--k K [--counts] | --instances N]
+
+--instances N runs cap_closest_instances on the hall under N transforms: instance 0 is the identity, the others stand on a square grid
+around it, 1.1 scene sizes apart, each turned about the vertical by an angle of its own (N = 1: the identity alone).  The point sets
+are the flat query's, in and around instance 0; each line carries the instanced rate and, as its baseline, cap_closest_points on the
+same points in the same process (flat_ms, flat_mpoints_per_s) and the ratio of the two rates.
 
 --k K runs cap_closest_points_multi with pages of K records on the same point sets (--counts: with the candidate counts, which turns
 off pruning by the k-th distance; K = 0 needs it); the line then also carries k, counts and mean_candidates -- the mean of the counts,
@@ -43,6 +48,22 @@ def timed(r, call, reps, warmup):
     return (time.perf_counter() - t0) / reps
 
 
+def hall_transforms(count, lo, hi, rng):
+    """(count, 3, 4) float32: the identity, then copies on a square grid in the ground plane around it, 1.1 scene sizes apart, each
+    turned about the vertical (y) through its own centre"""
+    size = float((hi - lo).max())
+    c = 0.5 * (lo + hi)
+    M = np.zeros((count, 3, 4), np.float64)
+    M[:, :, :3] = np.eye(3)
+    side = int(np.ceil(np.sqrt(count)))
+    for i in range(1, count):
+        a = rng.uniform(0.0, 2.0 * np.pi)
+        R = np.array([[np.cos(a), 0.0, np.sin(a)], [0.0, 1.0, 0.0], [-np.sin(a), 0.0, np.cos(a)]])
+        shift = np.array([(i % side) * 1.1 * size, 0.0, (i // side) * 1.1 * size])
+        M[i, :, :3], M[i, :, 3] = R, c + shift - R @ c
+    return M.astype(np.float32)
+
+
 def main():
     import torch
     from capsaicin_amd import capi
@@ -56,7 +77,10 @@ def main():
     ap.add_argument("--offset", type=float, default=1e-3)
     ap.add_argument("--k", type=int, default=None)
     ap.add_argument("--counts", action="store_true")
+    ap.add_argument("--instances", type=int, default=None)
     a = ap.parse_args()
+    if a.instances is not None and (a.k is not None or a.instances < 1):
+        ap.error("--instances N >= 1 runs cap_closest_instances alone: no --k")
     rng = np.random.default_rng(2026)
     dev = torch.device("cuda", 0)
     L = capi.lib()
@@ -83,6 +107,11 @@ def main():
     surface = np.einsum("nk,nkj->nj", b, tris[g].astype(np.float64)) + (rng.random((n, 3)) - 0.5) * 2 * a.offset * size
     sets = (("grid", grid), ("shuffled", grid[rng.permutation(n)]), ("surface", surface))
     out = torch.empty((n * max(a.k or 1, 1), 8), dtype=torch.float32, device=dev)
+    if a.instances is not None:
+        M = hall_transforms(a.instances, lo, hi, np.random.default_rng(2027))  # (a generator of its own: the point sets stay the flat runs')
+        info_i = r.set_instances(M)
+        inst = torch.empty((n,), dtype=torch.int32, device=dev)
+        flat_out = torch.empty((n, 8), dtype=torch.float32, device=dev)
     cnt = torch.empty((n,), dtype=torch.int32, device=dev) if a.counts else None
     head = dict(scene="hall", triangles=int(info.triangle_count), depth=int(info.max_depth), n=n, radius=a.radius, reps=a.reps)
     if a.k is not None:
@@ -92,7 +121,11 @@ def main():
         q[:, 0:3], q[:, 3] = xyz, a.radius
         pts = torch.as_tensor(q, device=dev).contiguous()
         torch.cuda.synchronize()
-        if a.k is None:
+        if a.instances is not None:
+            flat = lambda: capi._check(L.cap_closest_points(r.ctx, pts.data_ptr(), n, flat_out.data_ptr(), None), "cap_closest_points")
+            flat_sec = timed(r, flat, a.reps, a.warmup)
+            call = lambda: capi._check(L.cap_closest_instances(r.ctx, pts.data_ptr(), n, out.data_ptr(), inst.data_ptr(), None), "cap_closest_instances")
+        elif a.k is None:
             call = lambda: capi._check(L.cap_closest_points(r.ctx, pts.data_ptr(), n, out.data_ptr(), None), "cap_closest_points")
         else:
             call = lambda: capi._check(L.cap_closest_points_multi(r.ctx, pts.data_ptr(), n, a.k, out.data_ptr() if a.k else None,
@@ -105,9 +138,16 @@ def main():
             rec, hit = page[:, 0], listed[:, 0]
             line.update(hits=round(float(hit.mean()), 4),
                         mean_dist=round(float(np.sqrt(rec[hit, 3].astype(np.float64)).mean() / size), 5) if hit.any() else None)
+        if a.instances is not None:
+            same = float((out.view(torch.int32) == flat_out.view(torch.int32)).all(1).float().mean())
+            line.update(instances=a.instances, inert=int(info_i.inert), tlas_depth=int(info_i.tlas_depth), flat_ms=round(flat_sec * 1e3, 3),
+                        flat_mpoints_per_s=round(n / flat_sec / 1e6, 1), ratio_to_flat=round(flat_sec / sec, 3), same_as_flat=round(same, 4))
         if a.k is not None:
             line.update(mean_candidates=round(float(cnt.cpu().numpy().astype(np.float64).mean() if a.counts else listed.sum(1).mean()), 3))
         print(json.dumps(line), flush=True)
+    if a.instances is not None:
+        r.close()
+        return
     rays = torch.as_tensor(random_rays(lo, hi, n, rng), device=dev).contiguous()
     hits = torch.empty((n, 4), dtype=torch.float32, device=dev)
     torch.cuda.synchronize()
