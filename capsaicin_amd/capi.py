@@ -272,6 +272,7 @@ SYMBOLS = {
     "cap_closest_points": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_points_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_closest_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
+    "cap_closest_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
     "cap_post_settings_default": (None, [C.POINTER(PostSettings)]),
     "cap_post_frame": (_i, [_vp, C.POINTER(PostSettings), _u32, C.POINTER(CameraData)]),
@@ -867,6 +868,66 @@ class Renderer:
                 h = host_page
             return (h, cnt.cpu().numpy()) if counts else h
         return (page, cnt) if counts else page
+
+    def closest_instances_multi(self, points, k, counts=False, resume=None, sync=True, mask=None):
+        """The k (instance, triangle) pairs nearest to each point in WORLD space within its radius, in (dist2, instance, triangle) order
+        (cap_closest_instances_multi): (records (N, k, 8) float32 as closest_instances writes them, instances (N, k) int32, -1 in the
+        miss slots after a point's last pair[, counts (N,) int32 = the number of ALL candidate pairs per point with counts=True, which
+        turns off pruning by the k-th distance]).  k = 0: counts only, the records are (N, 0, 8) and the instances (N, 0).
+        resume=(records, instances) of the previous call with the same points continues after it with CAP_MULTI_CONTINUE and writes the
+        next pages over both.  closest_triangles() reads the (N, k) ids and features.  points, sync and mask= as closest_points; numpy
+        points (or numpy resume pages) give numpy results."""
+        import torch
+        options = self.trace_options(None, mask)
+        dev = torch.device("cuda", self.device)
+        if resume is not None and (not isinstance(resume, (tuple, list)) or len(resume) != 2):
+            raise CapError("resume must be the (records, instances) pair of the previous call")
+        host = isinstance(points, np.ndarray) or (resume is not None and any(isinstance(p, np.ndarray) for p in resume))
+        if isinstance(points, np.ndarray):
+            points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
+        if host:
+            sync = True  # the result is read back to the host
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
+            raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
+        n, k = points.shape[0], int(k)
+        if not 0 <= k <= self.MULTI_MAX_K:
+            raise CapError("k must be in 0 .. %d (page with resume=), got %d" % (self.MULTI_MAX_K, k))
+        if k == 0 and (not counts or resume is not None):
+            raise CapError("k = 0 counts only: pass counts=True and no resume pages")
+        host_pages = [None, None]
+        if resume is None:
+            rec = torch.empty((n, k, 8), dtype=torch.float32, device=dev)
+            inst = torch.empty((n, k), dtype=torch.int32, device=dev)
+        else:
+            pages = []
+            for j, (page, shape, dtype, np_dtype) in enumerate(((resume[0], (n, k, 8), torch.float32, np.float32),
+                                                                 (resume[1], (n, k), torch.int32, np.int32))):
+                if isinstance(page, np.ndarray):
+                    if page.size != int(np.prod(shape)):
+                        raise CapError("resume[%d] must hold the %s page of the previous call, got %s" % (j, shape, page.shape))
+                    host_pages[j] = page
+                    page = torch.from_numpy(np.ascontiguousarray(page, np_dtype).reshape(shape)).to(dev)
+                elif page.dtype != dtype or tuple(page.shape) != shape or not page.is_contiguous() or page.device != dev:
+                    raise CapError("resume[%d] must be the contiguous %s %s page of the previous call" % (j, shape, dtype))
+                pages.append(page)
+            rec, inst = pages
+        cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
+        _check(lib().cap_closest_instances_multi(self.ctx, C.c_void_p(points.data_ptr()), n, k, C.c_void_p(rec.data_ptr()) if k else None,
+                                                 C.c_void_p(inst.data_ptr()) if k else None, C.c_void_p(cnt.data_ptr()) if counts else None,
+                                                 self.MULTI_CONTINUE if resume is not None else 0, C.byref(options) if options is not None else None),
+               "cap_closest_instances_multi")
+        if sync:
+            self.sync()
+        if host:
+            out = [rec.cpu().numpy(), inst.cpu().numpy()]
+            for j in range(2):
+                if host_pages[j] is not None:
+                    host_pages[j][...] = out[j].reshape(host_pages[j].shape)
+                    out[j] = host_pages[j]
+            return (out[0], out[1], cnt.cpu().numpy()) if counts else (out[0], out[1])
+        return (rec, inst, cnt) if counts else (rec, inst)
 
     # ---- instanced ray queries (cap_instances_set, cap_trace_instances*) ----
     def set_objects(self, ranges):

@@ -205,6 +205,18 @@ struct ClosestInstArgs
     const uint32_t* xw_max;
 };
 void launch_closest_instances(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstArgs& a, const TlasDev& tl, const RayFilter& f, uint32_t depth);
+// The k nearest and in-radius form over the instance table (cap_closest_instances_multi, point_query.hip k_closest_inst_multi): ia.a.out
+// = pages of k CapClosest records per point and ia.inst_out = pages of k instances (both NULL when k = 0); counts, resume and the list
+// capacity as ClosestMultiArgs' -- the cursor is slot k - 1 of both pages.
+struct ClosestInstMultiArgs
+{
+    ClosestInstArgs ia;
+    uint32_t        k;
+    uint32_t*       counts;
+    uint32_t        resume;
+};
+void launch_closest_instances_multi(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstMultiArgs& m, const TlasDev& tl, const RayFilter& f,
+                                    uint32_t depth);
 
 // ---- instances (instance.hip): cap_instances_set, cap_trace_instances* ----
 // The table on the device.  rec: 4 float4 per instance = the three rows of W (world to object, row r = (W_r0, W_r1, W_r2, W_r3)) and

@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_closest_points_multi, cap_closest_instances; point_query.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi; point_query.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -354,6 +354,41 @@ int closest_instances(CapContext* c, const char* what, const CapPointDesc* point
         return run.traced("k_closest_inst", first);
     });
 }
+
+// cap_closest_instances_multi (point_query.hip k_closest_inst_multi): a point's first k candidate pairs in (dist2, instance, triangle)
+// order and / or the number of its pairs -- closest_points_multi's rules with the instance page as a fourth array, over
+// closest_instances' state and pools.  k = 1 without counts or cursor IS cap_closest_instances and takes its kernel.
+int closest_instances_multi(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, uint32_t k, CapClosest* out, uint32_t* inst,
+                            uint32_t* counts, uint32_t flags, const CapTraceOptions* options)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a point", what, options->ray_flags);
+    QueryFilter flt;
+    if (const int rc = multi_rules(c, what, k, flags, options, "output and instances", out || inst, counts, flt)) return rc;
+    if (const int rc = query_state(c, what)) return rc;
+    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
+    if (n == 0) return CAP_OK;
+    if (!points || (k && (!out || !inst))) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer (k = %u needs output and instances)", what, k);
+    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, (uint64_t)k * sizeof(CapClosest), 16),
+                                              range("instances", inst, (uint64_t)k * sizeof(uint32_t), 4), range("counts", counts, sizeof(uint32_t), 4)}))
+        return rc;
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    use_instance_pools(run);
+    const bool single = k == 1 && !counts && !(flags & CAP_MULTI_CONTINUE);
+    return for_each_chunk(run, points, n, [&](const QueryArgs& q, uint64_t first) {
+        const ClosestInstArgs a{ClosestArgs{q.rays, q.n, reinterpret_cast<float4*>(at(out, first * k)), 0.f}, at(inst, first * k), c->inst_desc.p,
+                                c->inst_near.p, c->inst_misc.p + 7};
+        if (single)
+        {
+            launch_closest_instances(run.cfg, run.bvh, a, run.tl, flt.f, run.depth);
+            return run.traced("k_closest_inst", first);
+        }
+        launch_closest_instances_multi(run.cfg, run.bvh, ClosestInstMultiArgs{a, k, at(counts, first), (flags & CAP_MULTI_CONTINUE) ? 1u : 0u}, run.tl, flt.f,
+                                       run.depth);
+        return run.traced("k_closest_inst_multi", first);
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -422,5 +457,11 @@ int cap_closest_instances(CapContext* c, const CapPointDesc* device_points, uint
                           const CapTraceOptions* options)
 {
     return closest_instances(c, "cap_closest_instances", device_points, n, device_out, device_instances, options);
+}
+
+int cap_closest_instances_multi(CapContext* c, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out,
+                                uint32_t* device_instances, uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options)
+{
+    return closest_instances_multi(c, "cap_closest_instances_multi", device_points, n, k, device_out, device_instances, device_counts, multi_flags, options);
 }
 }  // extern "C"

@@ -28,6 +28,7 @@
 //     planes (2 eps (X + k |o|)), 1 / (1 - g4 kappa) <= 1.001 and the distance-proportional error of the triangle test itself, for
 //     kappa <= CAP_INSTANCE_MAX_CONDITION = 4096, the domain of the proof; an instance beyond it is inert.  The interval test keeps
 //     the binary tree's relative slack (4e-7 >= 6 eps: one subtraction, one rounded reciprocal, one product per plane).
+#include "cap_hit_list.h"
 #include "cap_kernels.h"
 #include "cap_near.h"
 #include "cap_trace.h"
@@ -386,44 +387,8 @@ __global__ __launch_bounds__(kBlock, inst_blocks(STACK)) void k_query_inst(BvhDe
 }
 
 // ---- multi-hit over the instances (cap_trace_instances_multi) ----
-// A ray's first k pairs in (t, instance, triangle) order, the number of its pairs, or both: cap_hit_list.h's HitList with the instance
-// between t and the triangle.  K (t, inst, gid) triples in VGPRs, K a compile-time bucket >= k, every index a compile-time constant;
-// the first K - k slots hold (-inf, 0, 0) placeholders no hit passes (t > tmin >= -inf), the last k start as the miss (tmax, ~0, ~0).
-// A pair below slot K - 1 replaces it and bubbles towards the front by K - 1 compare-swaps.
-template <int K>
-struct InstHitList
-{
-    float    t[K];
-    uint32_t i[K], g[K];
-    static __device__ __forceinline__ bool before(float ta, uint32_t ia, uint32_t ga, float tb, uint32_t ib, uint32_t gb)
-    {
-        return ta < tb || (ta == tb && (ia < ib || (ia == ib && ga < gb)));
-    }
-    __device__ __forceinline__ void init(uint32_t k, float tmax)
-    {
-#pragma unroll
-        for (int j = 0; j < K; ++j)
-        {
-            const bool live = j >= K - (int)k;
-            t[j] = live ? tmax : -__builtin_inff(), i[j] = live ? kInvalidId : 0u, g[j] = live ? kInvalidId : 0u;
-        }
-    }
-    __device__ __forceinline__ bool admits(float tt, uint32_t ii, uint32_t gg) const { return before(tt, ii, gg, t[K - 1], i[K - 1], g[K - 1]); }
-    __device__ __forceinline__ void insert(float tt, uint32_t ii, uint32_t gg)
-    {
-        t[K - 1] = tt, i[K - 1] = ii, g[K - 1] = gg;
-#pragma unroll
-        for (int j = K - 1; j > 0; --j)
-        {
-            const bool     sw = before(t[j], i[j], g[j], t[j - 1], i[j - 1], g[j - 1]);
-            const float    ta = t[j - 1], tb = t[j];
-            const uint32_t ia = i[j - 1], ib = i[j], ga = g[j - 1], gb = g[j];
-            t[j - 1] = sw ? tb : ta, t[j] = sw ? ta : tb;
-            i[j - 1] = sw ? ib : ia, i[j] = sw ? ia : ib;
-            g[j - 1] = sw ? gb : ga, g[j] = sw ? ga : gb;
-        }
-    }
-};
+// A ray's first k pairs in (t, instance, triangle) order, the number of its pairs, or both, in cap_hit_list.h's InstHitList: HitList with
+// the instance between t and the triangle.
 
 // The object-space ray of the contract in instance `inst`: the twelve operations of k_query_inst's entry step, so the same bits.
 __device__ __forceinline__ void inst_object_ray(const TlasDev& tl, uint32_t inst, const Ray& rw, v3& o, v3& d)

@@ -17,7 +17,8 @@
 // The multi form (cap_closest_points_multi, k_closest_points_multi) is the same walk with the sorted list HitList<K> of cap_hit_list.h
 // in the place of the single best pair; "best" above reads "k-th best", slot K - 1 of the list.
 //
-// The instanced form (cap_closest_instances, k_closest_inst) is at the end of the file: nearest in world space over the instance table.
+// The instanced forms (cap_closest_instances, k_closest_inst; cap_closest_instances_multi, k_closest_inst_multi) are at the end of the
+// file: nearest, and the k nearest, in world space over the instance table.
 #include "cap_hit_list.h"
 #include "cap_kernels.h"
 #include "cap_near.h"  // box_dist2, and the bound of the instanced form
@@ -598,6 +599,252 @@ void launch_closest_inst_s(const LaunchCfg& cfg, const BvhDev& b, const ClosestI
     hipLaunchKernelGGL((k_closest_inst<STACK, FILTER>), dim3(resident_grid<k_closest_inst<STACK, FILTER>>(cfg, want)), dim3(kBlock), 0, cfg.stream, b, a,
                        tl, f);
 }
+
+// ---- k nearest and in-radius over the instance table (cap_closest_instances_multi) ----
+// A point's first k candidate pairs in (dist2, instance, triangle) order, the number of its pairs, or both: k_closest_inst's loop -- the
+// same three kinds of step, the (todo0, todo1) queue, the `still` re-check on entry -- with InstHitList<K> of cap_hit_list.h in the
+// place of (best, best_inst, best_gid), as k_closest_points_multi stands to k_closest_points.  The list moved to that header rather
+// than being copied here: k_query_inst_multi's code is unchanged by it (tools/kernel_regs.sh: the same rows).
+// Bounds: bound2 and bound2_top derive from slot K - 1's dist2 -- r2 until the list holds k pairs, then the k-th -- through one sqrtf,
+// computed again only when that slot's value changes (and bound2 on entering an instance, from the value as it stands); with COUNT
+// every pair within the radius has to be seen and both stay at r2's.  Every test is near_skip's strict >: an instance, subtree or
+// triangle at exactly the k-th distance is opened and an equal-dist2 pair with a lower (instance, triangle) still displaces the k-th
+// entry, so the list is exact whatever the visiting order (DESIGN.md "Multi closest-point queries over instances").
+// Offer: above the cursor (dist2_c, i_c, g_c) -- words 3 and 6 of slot k - 1 of the record page and slot k - 1 of the instance page,
+// (-inf, 0, 0) otherwise --; with COUNT `dist2 <= r2` itself and ++count (a pair may lie AT the limit, and one beyond it passes a miss
+// record's cursor (r2, ~0, ~0)); then admits / insert.  The cursor prunes nothing.
+// Write-out: only (dist2, inst, gid) live in the list; each listed pair's record is computed again from tris_by_id and descs[inst] as
+// k_closest_inst does for its winner.  The slot is picked by a chain of K selects inside a loop over the k slots; the cursor is read
+// before anything is written; k = 0 dereferences neither page.
+// The mesh-mask table is a wave-uniform test of f.tri_mask per leaf, as in k_query_inst_multi, not a template flag: with the list in
+// registers the flag would double 32 instantiations for the two SGPR pairs it saves.
+
+// Workgroups per CU: closest_inst_blocks(STACK) is what the LDS allows; the list's 3 K registers (and cursor and count) take it down to
+// the most that leave every instantiation without scratch (tools/kernel_regs.sh; the table is in DESIGN.md): up to K = 4 the LDS's four
+// (128 VGPRs; 93 to 99 used at K = 1, 126 to 128 at K = 4), two (256; about 200 used) at K = 8 -- three (168) spill 104 to 120 bytes --
+// and one (512; about 260 used) at K = 16 -- two spill 12 to 28 bytes.  The compiler keeps the list twice across insert()'s
+// compare-swaps, as in k_query_inst_multi, so a slot costs six registers rather than three.
+constexpr int closest_inst_multi_blocks(int STACK, int K)
+{
+    const int by_regs = K <= 4 ? 4 : K <= 8 ? 2 : 1;
+    return closest_inst_blocks(STACK) < by_regs ? closest_inst_blocks(STACK) : by_regs;
+}
+
+template <int STACK, int K, bool COUNT>
+__global__ __launch_bounds__(kBlock, closest_inst_multi_blocks(STACK, K)) void k_closest_inst_multi(BvhDev bvh, ClosestInstMultiArgs m, TlasDev tl,
+                                                                                                       RayFilter f)
+{
+    __shared__ uint2    lds_stack[STACK * kBlock];
+    __shared__ uint32_t lds_off[kTlasMaxLevels + 1];
+    uint2* const        stack = lds_stack + threadIdx.x;
+    if (threadIdx.x <= tl.top) lds_off[threadIdx.x] = tl.level_off[threadIdx.x];
+    __syncthreads();
+    const ClosestInstArgs& ia     = m.ia;
+    const float            xw_all = u2f(ia.xw_max[0]);
+    const int              skip   = K - (int)m.k;  // the placeholders
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < ia.a.n; j += gridDim.x * kBlock)
+    {
+        const float4    p     = ia.a.points[j];
+        float4* const   page  = ia.a.out + 2 * (size_t)j * m.k;
+        uint32_t* const ipage = ia.inst_out + (size_t)j * m.k;
+        const bool      ok    = point_ok(p);
+        const float     r2    = ok ? p.w * p.w : 0.f;
+        InstHitList<K>  L;
+        L.init(m.k, r2);
+        // the cursor: slot k - 1 of both pages when paging, else (-inf, 0, 0), below every pair
+        float    dc = -__builtin_inff();
+        uint32_t ic = 0u, gc = 0u, count = 0u;
+        if (m.resume && ok) dc = page[2 * (m.k - 1u)].w, gc = f2u(page[2 * (m.k - 1u) + 1].z), ic = ipage[m.k - 1u];
+        const float pmax      = fmaxf(fabsf(p.x), fmaxf(fabsf(p.y), fabsf(p.z)));
+        float       sqrt_kth  = sqrtf(r2);
+        const float slack_top = near_slack(pmax, xw_all);
+        float       bound2_top = near_bound2_world(sqrt_kth, slack_top);
+        // top level: the node whose two children (level - 1, 2 idx + {0, 1}) are tested next
+        uint32_t level = tl.top + 1u, idx = 0u, pending = 0u;
+        bool     top_done = false;
+        uint32_t todo0 = kInvalidId, todo1 = kInvalidId;
+        float    todo0_d = 0.f, todo1_d = 0.f;
+        // bottom level
+        bool     in_blas = false;
+        float4   m0 = make_float4(0.f, 0.f, 0.f, 0.f), m1 = m0, m2 = m0;
+        float    ox = 0.f, oy = 0.f, oz = 0.f, g = 1.f, slack = 0.f, bound2 = 0.f;
+        uint32_t inst = 0u, imask = 0u;
+        int      node = 0, sp = 0;
+        bool     walk = ok && bvh.tri_count != 0u;
+        while (walk)
+        {
+            if (in_blas)
+            {
+                if (node >= 0)
+                {
+                    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2],
+                                 q3 = bvh.nodes[4 * node + 3];
+                    const float b0 = box_dist2(ox, oy, oz, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
+                    const float b1 = box_dist2(ox, oy, oz, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
+                    const int   c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+                    const bool  k0 = !near_skip(b0, bound2), k1 = !near_skip(b1, bound2);
+                    if (k0 && k1)
+                    {
+                        const bool swap = b1 < b0;
+                        if (sp < STACK) stack[(sp++) * kBlock] = make_uint2(f2u(swap ? b0 : b1), (uint32_t)(swap ? c0 : c1));
+                        node = swap ? c1 : c0;
+                        continue;
+                    }
+                    if (k0 || k1)
+                    {
+                        node = k0 ? c0 : c1;
+                        continue;
+                    }
+                }
+                else
+                {
+                    const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                    for (uint32_t leaf = first; leaf <= last; ++leaf)
+                    {
+                        const uint32_t gid = f2u(bvh.tris[4 * (size_t)leaf + 3].x);
+                        if (f.tri_mask && (f.tri_mask[gid] & imask) == 0u) continue;
+                        const WorldRecord w  = world_record(m0, m1, m2, bvh.tris[4 * (size_t)leaf + 0], bvh.tris[4 * (size_t)leaf + 1], bvh.tris[4 * (size_t)leaf + 2]);
+                        const float       d2 = closest_dist2(w.t0, w.t1, w.t2, p.x, p.y, p.z);
+                        // k_closest_points_multi's offer with the instance between dist2 and the triangle; a NaN fails every comparison
+                        if (InstHitList<K>::before(dc, ic, gc, d2, inst, gid) && (!COUNT || d2 <= r2))
+                        {
+                            if (COUNT) ++count;
+                            if (L.admits(d2, inst, gid))
+                            {
+                                const float kth = L.t[K - 1];
+                                L.insert(d2, inst, gid);
+                                if (!COUNT && L.t[K - 1] != kth)
+                                {
+                                    sqrt_kth   = sqrtf(L.t[K - 1]);
+                                    bound2     = near_bound2_object(sqrt_kth, slack, g);
+                                    bound2_top = near_bound2_world(sqrt_kth, slack_top);
+                                }
+                            }
+                        }
+                    }
+                }
+                in_blas = false;
+                while (sp > 0)
+                {
+                    const uint2 e = stack[(--sp) * kBlock];
+                    if (!near_skip(u2f(e.x), bound2))
+                    {
+                        node = (int)e.y, in_blas = true;
+                        break;
+                    }
+                }
+                continue;
+            }
+            if (todo0 != kInvalidId)
+            {
+                // enter an instance, if its box still passes against the bound as it is now
+                inst             = todo0;
+                const bool still = !near_skip(todo0_d, bound2_top);
+                todo0 = todo1, todo0_d = todo1_d, todo1 = kInvalidId;
+                if (!still) continue;
+                const float4 w3 = tl.rec[4 * (size_t)inst + 3];
+                imask           = f2u(w3.x) & f.mask;  // desc.mask & inclusion (0 for an inert instance): the mesh byte joins it per triangle
+                if (imask == 0u) continue;
+                const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
+                const float  w[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
+                near_to_object(w, p.x, p.y, p.z, ox, oy, oz);
+                m0 = ia.descs[4 * (size_t)inst], m1 = ia.descs[4 * (size_t)inst + 1], m2 = ia.descs[4 * (size_t)inst + 2];
+                const float2 nr = ia.near[inst];
+                g = nr.x, slack = near_slack(pmax, nr.y);
+                bound2  = near_bound2_object(sqrt_kth, slack, g);
+                node    = (int)f2u(w3.y), sp = 0;
+                in_blas = true;
+                continue;
+            }
+            if (top_done) break;
+            const float4* c = tl.tlas + 2 * (size_t)(lds_off[level - 1u] + 2u * idx);
+            const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
+            const float   d0 = box_dist2(p.x, p.y, p.z, lo0.x, lo0.y, lo0.z, hi0.x, hi0.y, hi0.z);
+            const float   d1 = box_dist2(p.x, p.y, p.z, lo1.x, lo1.y, lo1.z, hi1.x, hi1.y, hi1.z);
+            // (a record with k < 0 holds nothing: an inert instance or the padding of a level)
+            const bool h0 = lo0.w >= 0.0f && !near_skip(d0, bound2_top), h1 = lo1.w >= 0.0f && !near_skip(d1, bound2_top);
+            const bool far_first = h0 && h1 && d1 < d0;
+            if (level > 1u)
+            {
+                if (h0 || h1)
+                {
+                    if (h0 && h1) pending |= 1u << (level - 1u);
+                    idx   = 2u * idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
+                    level = level - 1u;
+                    continue;
+                }
+            }
+            else if (h0 || h1)
+            {
+                // the children are instances: the nearer box first
+                const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
+                if (h0 && h1)
+                    todo0 = far_first ? i1 : i0, todo0_d = far_first ? d1 : d0, todo1 = far_first ? i0 : i1, todo1_d = far_first ? d0 : d1;
+                else
+                    todo0 = h0 ? i0 : i1, todo0_d = h0 ? d0 : d1;
+            }
+            const uint32_t owed = pending >> level;
+            if (owed == 0u)
+            {
+                top_done = true;
+                continue;
+            }
+            const uint32_t up = (uint32_t)__builtin_ctz(owed);
+            idx     = (idx >> up) ^ 1u;
+            level   = level + up;
+            pending = pending & ~(1u << level);
+        }
+        // (a point that was not traversed: the list as init left it, k miss records with dist2 = r2 = 0 and instance ~0, and count 0)
+        if (COUNT) m.counts[j] = count;
+        for (uint32_t s = 0; s < m.k; ++s)
+        {
+            uint32_t gid = kInvalidId, li = kInvalidId;
+#pragma unroll
+            for (int q = 0; q < K; ++q)
+                if (q - skip == (int)s) gid = L.g[q], li = L.i[q];
+            ipage[s] = li;
+            if (gid == kInvalidId)
+            {
+                page[2 * s]     = make_float4(0.f, 0.f, 0.f, r2);
+                page[2 * s + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
+                continue;
+            }
+            const float4*      rec = bvh.tris_by_id + 4 * (size_t)gid;
+            const float4*      md  = ia.descs + 4 * (size_t)li;
+            const WorldRecord  w   = world_record(md[0], md[1], md[2], rec[0], rec[1], rec[2]);
+            const ClosestPoint c   = closest_record(w.t0, w.t1, w.t2, p.x, p.y, p.z);
+            page[2 * s]     = make_float4(c.x, c.y, c.z, c.d2);
+            page[2 * s + 1] = make_float4(c.u, c.v, u2f(gid), u2f(c.feature));
+        }
+    }
+}
+
+template <int STACK, int K, bool COUNT>
+void launch_closest_inst_multi_k(const LaunchCfg& cfg, const BvhDev& b, const ClosestInstMultiArgs& m, const TlasDev& tl, const RayFilter& f)
+{
+    uint32_t want = (m.ia.a.n + kBlock - 1) / kBlock;
+    if (want == 0) want = 1;
+    hipLaunchKernelGGL((k_closest_inst_multi<STACK, K, COUNT>), dim3(resident_grid<k_closest_inst_multi<STACK, K, COUNT>>(cfg, want)), dim3(kBlock), 0,
+                       cfg.stream, b, m, tl, f);
+}
+
+template <int STACK>
+void launch_closest_inst_multi(const LaunchCfg& cfg, const BvhDev& b, const ClosestInstMultiArgs& m, const TlasDev& tl, const RayFilter& f)
+{
+#define CAP_CLOSEST_INST_MULTI(K)                                     \
+    if (m.counts)                                                     \
+        launch_closest_inst_multi_k<STACK, K, true>(cfg, b, m, tl, f);  \
+    else                                                              \
+        launch_closest_inst_multi_k<STACK, K, false>(cfg, b, m, tl, f);
+    switch (multi_bucket(m.k))
+    {
+    case 1: CAP_CLOSEST_INST_MULTI(1) break;
+    case 4: CAP_CLOSEST_INST_MULTI(4) break;
+    case 8: CAP_CLOSEST_INST_MULTI(8) break;
+    default: CAP_CLOSEST_INST_MULTI(16) break;
+    }
+#undef CAP_CLOSEST_INST_MULTI
+}
 }  // namespace
 
 void launch_closest_points(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const RayFilter* f, uint32_t depth)
@@ -673,5 +920,18 @@ void launch_closest_instances(const LaunchCfg& cfg, const BvhDev& bvh, const Clo
         CAP_CLOSEST_INST(64)
     }
 #undef CAP_CLOSEST_INST
+}
+
+void launch_closest_instances_multi(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstMultiArgs& m, const TlasDev& tl, const RayFilter& f,
+                                    uint32_t depth)
+{
+    if (depth <= 16)
+        launch_closest_inst_multi<16>(cfg, bvh, m, tl, f);
+    else if (depth <= 24)
+        launch_closest_inst_multi<24>(cfg, bvh, m, tl, f);
+    else if (depth <= 32)
+        launch_closest_inst_multi<32>(cfg, bvh, m, tl, f);
+    else
+        launch_closest_inst_multi<64>(cfg, bvh, m, tl, f);
 }
 }  // namespace cap

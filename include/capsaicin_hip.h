@@ -728,10 +728,51 @@ int cap_trace_instances_multi(CapContext* ctx, const CapRayDesc* device_rays, ui
  * output, misalignment, overlap.
  * Pruning never decides: the top-level boxes and the objects' trees are pruned with a bound that is proven conservative for every
  * live instance (DESIGN.md "Closest-point queries over instances"; cap_debug_closest_instance_bound shows its arithmetic).
- * Not covered: k nearest, counts and paging over instances (cap_closest_points_multi has no instanced form yet), per-point masks, the
- * sign of the distance, the wide view. */
+ * Not covered: per-point masks, the sign of the distance, the wide view.  The k nearest, counts and paging: cap_closest_instances_multi
+ * below. */
 int cap_closest_instances(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out,
                           uint32_t* device_instances /* may be NULL */, const CapTraceOptions* options /* may be NULL */);
+
+/* ---- k nearest and in-radius closest-point queries over instances: the SET of (instance, triangle) pairs near a point ----
+ * cap_closest_points_multi's pages, counts and paging over cap_closest_instances' candidates: contact generation against rigidly
+ * moving parts, robust ICP, "how many triangles of which instances lie within r", without flattening the scene.
+ * Candidates of a point: exactly cap_closest_instances' -- the pairs (instance i, triangle g) with i not inert; with an object table,
+ * g a triangle of i's object; desc[i].mask & mesh_mask[m] & instance_mask != 0 for g's mesh m; and dist2 <= r2 = fl(radius * radius),
+ * dist2 from the unchanged cascade on the world record built from M = desc[i].transform with dot_c, no fused multiply-add.  A NaN
+ * dist2 is never a candidate.  Sorted by (dist2, i, g) ascending, the order cap_closest_instances' tie rule defines; a pair appears at
+ * most once.
+ * Pages: device_out[j * k + s] and device_instances[j * k + s], s < k, are point j's s-th pair: a full world-space CapClosest as
+ * cap_closest_instances writes it, and the table index.  Slots after the last pair hold the miss record
+ * (0, 0, 0, r2, 0, 0, 0xFFFFFFFF, 0) and instance 0xFFFFFFFF.  With k = 1, no counts and no cursor, record and instance are bit for
+ * bit cap_closest_instances' (the call runs its kernel).  Records are bit-identical to a float32 brute force, whichever builder made
+ * the trees.
+ * device_counts: NULL, or n uint32: the number of ALL candidate pairs of point j, not capped at k (with CAP_MULTI_CONTINUE: of the
+ * pairs above the cursor).  Asking for counts turns off pruning by the k-th distance: the walk is then bounded by the radius alone.
+ * k = 0 counts only: device_out and device_instances must be NULL and device_counts given.
+ * Paging (CAP_MULTI_CONTINUE): on entry, slot k - 1 of each point's record page and of its instance page is read as the cursor
+ * (dist2_c, i_c, g_c) -- words 3 and 6 of the record, and the instance; only pairs with (dist2, i, g) > (dist2_c, i_c, g_c) in
+ * lexicographic order count, and the next pages are written over both arrays.  A short page ends in the miss record, whose cursor
+ * (r2, 0xFFFFFFFF, 0xFFFFFFFF) admits nothing.  Calling again with the same points and buffers walks every pair exactly once,
+ * equal-dist2 pairs of coinciding instances on either side of a page boundary and pairs with dist2 == r2 included.  Both cursor slots
+ * must hold what the previous call wrote there; device_instances is therefore required whenever k > 0, as in
+ * cap_trace_instances_multi.
+ * Degenerate points (a non-finite coordinate, a NaN or negative radius) are not traversed: k miss records with dist2 = 0, instance
+ * 0xFFFFFFFF and count 0, with CAP_MULTI_CONTINUE too.
+ * Everything else is as for cap_closest_instances and cap_trace_instances_multi: device pointers on the context's GPU; points and
+ * output 16-byte, instances and counts 4-byte aligned; no overlap between any two of the four ranges; asynchronous on the context
+ * stream, ordered behind a render's second lane; n above 2^24 split into launches with all three output pointers advanced per chunk,
+ * n = 0 does nothing; nothing of the render's state is touched.  Errors: CAP_ERR_STATE without an instance table, before
+ * cap_bvh_build and while the trees are stale; CAP_ERR_INVALID_ARG for any ray_flags bit, non-zero reserved words, instance_mask >
+ * 0xFF, unknown multi flags, k > CAP_MULTI_MAX_K, k = 0 with output or instances given or counts NULL, k > 0 with output or instances
+ * NULL, CAP_MULTI_CONTINUE with k = 0, NULL points, misalignment, overlap, and n * k records beyond the address space.  Nothing is
+ * written on an error.
+ * Pruning never decides: the bound of cap_closest_instances with the k-th distance in the place of the best (DESIGN.md "Multi
+ * closest-point queries over instances").
+ * Not covered: a lower bound from the cursor (later pages walk the exhausted subtrees and instances again), per-point masks, the sign
+ * of the distance, the wide view. */
+int cap_closest_instances_multi(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out,
+                                uint32_t* device_instances, uint32_t* device_counts, uint32_t multi_flags,
+                                const CapTraceOptions* options /* may be NULL */);
 
 /* ---- objects: per-mesh-range bottom-level trees for the instanced queries ----
  * An object is the mesh range [first_mesh, first_mesh + mesh_count) of the uploaded scene: mesh_count >= 1, at least one triangle,

@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
-"""Throughput of the closest-point queries (cap_closest_points, cap_closest_points_multi, cap_closest_instances) on the 262 k-triangle
-hall -- not part of bench.py, no pass mark.
+"""Throughput of the closest-point queries (cap_closest_points, cap_closest_points_multi, cap_closest_instances,
+cap_closest_instances_multi) on the 262 k-triangle hall -- not part of bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
-                                     [--k K [--counts] | --instances N]
+                                     [--k K [--counts]] [--instances N]
 
 --instances N runs cap_closest_instances on the hall under N transforms: instance 0 is the identity, the others stand on a square grid
 around it, 1.1 scene sizes apart, each turned about the vertical by an angle of its own (N = 1: the identity alone).  The point sets
 are the flat query's, in and around instance 0; each line carries the instanced rate and, as its baseline, cap_closest_points on the
 same points in the same process (flat_ms, flat_mpoints_per_s) and the ratio of the two rates.
+
+--instances N together with --k K [--counts] runs cap_closest_instances_multi on the same layout and point sets.  Each line carries,
+measured in the same process on the same points: (a) cap_closest_points_multi at the same k and counts (flat_ms, flat_mpoints_per_s,
+ratio_to_flat), (b) cap_closest_instances (single_ms, single_mpoints_per_s, ratio_to_single), and same_as_flat: the share of equal
+pages among the points no neighbour reaches -- those whose listed instances are all 0, the identity; flat_comparable is their share of
+all points.  A page without a neighbour's pair holds the flat query's candidates alone, so same_as_flat has to be 1.0.
 
 --k K runs cap_closest_points_multi with pages of K records on the same point sets (--counts: with the candidate counts, which turns
 off pruning by the k-th distance; K = 0 needs it); the line then also carries k, counts and mean_candidates -- the mean of the counts,
@@ -79,8 +85,9 @@ def main():
     ap.add_argument("--counts", action="store_true")
     ap.add_argument("--instances", type=int, default=None)
     a = ap.parse_args()
-    if a.instances is not None and (a.k is not None or a.instances < 1):
-        ap.error("--instances N >= 1 runs cap_closest_instances alone: no --k")
+    if a.instances is not None and a.instances < 1:
+        ap.error("--instances N needs N >= 1")
+    inst_multi = a.instances is not None and a.k is not None
     rng = np.random.default_rng(2026)
     dev = torch.device("cuda", 0)
     L = capi.lib()
@@ -110,8 +117,9 @@ def main():
     if a.instances is not None:
         M = hall_transforms(a.instances, lo, hi, np.random.default_rng(2027))  # (a generator of its own: the point sets stay the flat runs')
         info_i = r.set_instances(M)
-        inst = torch.empty((n,), dtype=torch.int32, device=dev)
-        flat_out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        inst = torch.empty((n * max(a.k or 1, 1),), dtype=torch.int32, device=dev)
+        flat_out = torch.empty((n * max(a.k or 1, 1), 8), dtype=torch.float32, device=dev)
+        single_out, flat_cnt = (torch.empty((n, 8), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)) if inst_multi else (None, None)
     cnt = torch.empty((n,), dtype=torch.int32, device=dev) if a.counts else None
     head = dict(scene="hall", triangles=int(info.triangle_count), depth=int(info.max_depth), n=n, radius=a.radius, reps=a.reps)
     if a.k is not None:
@@ -121,7 +129,16 @@ def main():
         q[:, 0:3], q[:, 3] = xyz, a.radius
         pts = torch.as_tensor(q, device=dev).contiguous()
         torch.cuda.synchronize()
-        if a.instances is not None:
+        if inst_multi:
+            flat = lambda: capi._check(L.cap_closest_points_multi(r.ctx, pts.data_ptr(), n, a.k, flat_out.data_ptr() if a.k else None,
+                                                                  flat_cnt.data_ptr() if a.counts else None, 0, None), "cap_closest_points_multi")
+            flat_sec = timed(r, flat, a.reps, a.warmup)
+            single = lambda: capi._check(L.cap_closest_instances(r.ctx, pts.data_ptr(), n, single_out.data_ptr(), None, None), "cap_closest_instances")
+            single_sec = timed(r, single, a.reps, a.warmup)
+            call = lambda: capi._check(L.cap_closest_instances_multi(r.ctx, pts.data_ptr(), n, a.k, out.data_ptr() if a.k else None,
+                                                                     inst.data_ptr() if a.k else None, cnt.data_ptr() if a.counts else None, 0, None),
+                                       "cap_closest_instances_multi")
+        elif a.instances is not None:
             flat = lambda: capi._check(L.cap_closest_points(r.ctx, pts.data_ptr(), n, flat_out.data_ptr(), None), "cap_closest_points")
             flat_sec = timed(r, flat, a.reps, a.warmup)
             call = lambda: capi._check(L.cap_closest_instances(r.ctx, pts.data_ptr(), n, out.data_ptr(), inst.data_ptr(), None), "cap_closest_instances")
@@ -138,7 +155,16 @@ def main():
             rec, hit = page[:, 0], listed[:, 0]
             line.update(hits=round(float(hit.mean()), 4),
                         mean_dist=round(float(np.sqrt(rec[hit, 3].astype(np.float64)).mean() / size), 5) if hit.any() else None)
-        if a.instances is not None:
+        if inst_multi:
+            line.update(instances=a.instances, inert=int(info_i.inert), tlas_depth=int(info_i.tlas_depth), flat_ms=round(flat_sec * 1e3, 3),
+                        flat_mpoints_per_s=round(n / flat_sec / 1e6, 1), ratio_to_flat=round(flat_sec / sec, 3), single_ms=round(single_sec * 1e3, 3),
+                        single_mpoints_per_s=round(n / single_sec / 1e6, 1), ratio_to_single=round(single_sec / sec, 3))
+            if a.k:
+                alone = (inst.view(n, a.k) <= 0).all(1)  # the identity instance or a miss in every slot: no neighbour reaches the page
+                equal = (out.view(torch.int32).view(n, -1) == flat_out.view(torch.int32).view(n, -1)).all(1)
+                line.update(flat_comparable=round(float(alone.float().mean()), 4),
+                            same_as_flat=round(float(equal[alone].float().mean()), 4) if bool(alone.any()) else None)
+        elif a.instances is not None:
             same = float((out.view(torch.int32) == flat_out.view(torch.int32)).all(1).float().mean())
             line.update(instances=a.instances, inert=int(info_i.inert), tlas_depth=int(info_i.tlas_depth), flat_ms=round(flat_sec * 1e3, 3),
                         flat_mpoints_per_s=round(n / flat_sec / 1e6, 1), ratio_to_flat=round(flat_sec / sec, 3), same_as_flat=round(same, 4))
