@@ -61,6 +61,17 @@ class RefitInfo(C.Structure):
     _fields_ = [("ms", C.c_double), ("expected_node_visits", C.c_double), ("expected_node_visits_built", C.c_double)]
 
 
+class PseudonormalsInfo(C.Structure):
+    """CapPseudonormalsInfo: what the weld of cap_pseudonormals_build found; the sign of signed_distance means inside / outside only
+    when closed == 1."""
+    _fields_ = [("vertices", C.c_uint32), ("edges", C.c_uint32), ("boundary_edges", C.c_uint32), ("nonmanifold_edges", C.c_uint32),
+                ("inconsistent_edges", C.c_uint32), ("degenerate_triangles", C.c_uint32), ("closed", C.c_uint32), ("reserved", C.c_uint32),
+                ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 VERTICES_DEVICE = 1  # CAP_VERTICES_DEVICE
 
 
@@ -271,6 +282,10 @@ SYMBOLS = {
     "cap_trace_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_closest_points": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_points_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
+    "cap_pseudonormals_build": (_i, [_vp, C.POINTER(PseudonormalsInfo)]),
+    "cap_pseudonormals_drop": (_i, [_vp]),
+    "cap_pseudonormals_readback": (_i, [_vp, _vp]),
+    "cap_signed_distance": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
@@ -781,6 +796,61 @@ class Renderer:
                 return host_out
             return res
         return out
+
+    # ---- signed distance (cap_pseudonormals_*, cap_signed_distance) ----
+    def build_pseudonormals(self):
+        """Build the angle-weighted pseudonormal table of the scene (cap_pseudonormals_build) and return its PseudonormalsInfo.  Needs
+        a built tree; build_bvh() and refit_bvh() keep an existing table current."""
+        info = PseudonormalsInfo()
+        _check(lib().cap_pseudonormals_build(self.ctx, C.byref(info)), "cap_pseudonormals_build")
+        return info
+
+    def drop_pseudonormals(self):
+        _check(lib().cap_pseudonormals_drop(self.ctx), "cap_pseudonormals_drop")
+
+    def pseudonormals(self):
+        """The table as a (T, 7, 3) float32 array: per global triangle id the unnormalised pseudonormals of the face, the edges v0v1,
+        v1v2, v2v0 and the vertices v0, v1, v2 (the FEATURE_* order)."""
+        table = np.zeros((int(self._tri_end[-1]) if len(self._tri_end) else 0, 7, 3), np.float32)
+        _check(lib().cap_pseudonormals_readback(self.ctx, _p(table)), "cap_pseudonormals_readback")
+        return table
+
+    def signed_distance(self, points, out=None, sync=True, mask=None):
+        """closest_points with the signed distance (cap_signed_distance): (records (N, 8) float32, signed (N,) float32).  The records
+        are closest_points', bit for bit; signed is -sqrt(dist2) where the point lies behind the pseudonormal of the feature the record
+        reports, +sqrt(dist2) otherwise, +inf on a miss.  Needs build_pseudonormals().  points, out, sync and mask= as closest_points;
+        numpy points give numpy results."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        host = isinstance(points, np.ndarray)
+        if host:
+            points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
+            sync = True  # the result is read back to the host
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
+            raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
+        n = points.shape[0]
+        host_out = None
+        if isinstance(out, np.ndarray):
+            host_out, out = out, None
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (n, 8) or not out.is_contiguous() or out.device != dev:
+            raise CapError("out must be a contiguous (%d, 8) float32 tensor on %s" % (n, dev))
+        signed = torch.empty((n,), dtype=torch.float32, device=dev)
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
+        options = self.trace_options(None, mask)
+        _check(lib().cap_signed_distance(self.ctx, C.c_void_p(points.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(signed.data_ptr()),
+                                         C.byref(options) if options is not None else None), "cap_signed_distance")
+        if sync:
+            self.sync()
+        if host or host_out is not None:
+            res = out.cpu().numpy()
+            if host_out is not None:
+                host_out[...] = res.reshape(host_out.shape)
+                res = host_out
+            return res, signed.cpu().numpy()
+        return out, signed
 
     def closest_instances(self, points, out=None, sync=True, mask=None):
         """The (instance, triangle) nearest to each point in WORLD space over the instance table (cap_closest_instances): (records

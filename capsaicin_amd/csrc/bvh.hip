@@ -716,6 +716,10 @@ int    launch_radix_sort_pairs(hipStream_t stream, uint32_t* const keys[2], uint
     return src;
 }
 
+// the radix sort's exclusive scan alone (pseudonormal.hip's weld ids): v[0 .. total) in place; scratch: bvh_scan_scratch_words(total) words
+size_t bvh_scan_scratch_words(uint32_t total) { return ((size_t)total + kScanTile - 1) / kScanTile; }
+void   launch_exclusive_scan_u32(hipStream_t stream, uint32_t* v, uint32_t total, uint32_t* scratch) { launch_exclusive_scan(stream, v, total, scratch); }
+
 // setup + Morton codes + radix sort; the sorted (key, triangle) arrays are a.keys[r], a.vals[r] for the returned r
 int launch_bvh_sort(hipStream_t stream, const BvhBuildArgs& a)
 {

@@ -160,6 +160,10 @@ struct CapContext
     CapBvhInfo       bvh_info{};
     bool             shade_tame = false;  // SceneDev::shade_tame of the shading records as cap_bvh_build / cap_bvh_refit last wrote them
     bool             bvh_ready = false;
+    // pseudonormal table of cap_signed_distance (cap_pseudonormals_build, pseudonormal.hip): 21 floats per triangle by global id
+    DevBuf<float>        pn_table;
+    bool                 pn_ready = false;  // a table exists (stale while bvh_stale; cap_bvh_build / cap_bvh_refit rebuild it)
+    CapPseudonormalsInfo pn_info{};
     // vertex updates and refit (cap_scene_update_vertices, cap_bvh_refit, refit.hip)
     bool                  bvh_stale = false;             // vertices changed since the trees were last brought up to date
     bool                  positions_host_stale = false;  // positions_host lags a device-side update (read back only when needed)

@@ -180,6 +180,14 @@ struct ClosestArgs
 };
 constexpr float kClosestSlackScale = 1.0f / 262144.0f;  // 64 x 2^-24: the proof needs 52
 void launch_closest_points(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const RayFilter* f, uint32_t depth);
+// cap_signed_distance (point_query.hip k_closest_points<.., true>): launch_closest_points, and signed_out[i] = the distance to the record's
+// closest point, negative where the record's delta points against the pseudonormal normals[21 triangle + 3 feature] (+inf without a record)
+struct SignedArgs
+{
+    const float* normals;
+    float*       signed_out;
+};
+void launch_signed_distance(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const SignedArgs& s, const RayFilter* f, uint32_t depth);
 // The k nearest and in-radius form (cap_closest_points_multi, point_query.hip k_closest_points_multi): a.out = pages of k CapClosest
 // records per point (NULL when k = 0); counts = n candidate counts or NULL (then the k-th distance prunes); resume: slot k - 1 of each
 // page is the cursor (CAP_MULTI_CONTINUE).  The list capacity is multi_bucket(k) >= k.
@@ -399,6 +407,8 @@ int    launch_bvh_sort(hipStream_t stream, const BvhBuildArgs& a);  // setup + M
 // keys[r] / vals[r] for the returned r.  hist: 256 * bvh_radix_blocks(n) words, scan: bvh_radix_scan_words(n) words of scratch.
 size_t bvh_radix_scan_words(uint32_t n);
 int    launch_radix_sort_pairs(hipStream_t stream, uint32_t* const keys[2], uint32_t* const vals[2], uint32_t n, uint32_t* hist, uint32_t* scan);
+size_t bvh_scan_scratch_words(uint32_t total);
+void   launch_exclusive_scan_u32(hipStream_t stream, uint32_t* v, uint32_t total, uint32_t* scratch);  // exclusive scan of v[0 .. total) in place
 // Agglomerative build with a surface-area distance over the Morton order (ploc.hip); same outputs as launch_bvh_build,
 // incl. the subtree counts in a.keys[1].  boxes: 4 * tri_count float4; ints: 3 * tri_count + 4 words.  Returns 0 on success.
 struct PlocScratch
@@ -433,6 +443,31 @@ struct WideCollapseArgs
 // level_begin (may be null): the first node of every level, then the node count -- level l = [level_begin[l], level_begin[l + 1])
 int      launch_wide_collapse(hipStream_t stream, WideCollapseArgs a, uint32_t* node_count, uint32_t* depth, uint32_t* top_nodes,
                           std::vector<uint32_t>* level_begin = nullptr);
+// ---- pseudonormal table (pseudonormal.hip, cap_pseudonormals_build): the sign of cap_signed_distance ----
+// table: 21 floats per triangle by global id, seven entries of three indexed by CAP_FEATURE_*.  Everything else is build scratch, C = 3 x
+// tri_count words each unless said; stats: 8 words = vertices, edges, boundary, non-manifold and inconsistent edges, degenerate triangles.
+struct PseudonormalArgs
+{
+    const float*    positions;
+    const uint32_t* indices;
+    const uint4*    tri_ids;
+    const uint4*    mesh_offsets;
+    uint32_t        tri_count;
+    float*          table;
+    uint32_t *      kx, *ky, *kz;  // the corners' position bits; then (dead mark, lower, higher weld id) of the half-edges
+    uint32_t*       keys[2];
+    uint32_t*       vals[2];
+    uint32_t*       weld;          // weld id per corner
+    uint32_t*       flag;          // run starts, then their exclusive scan
+    uint32_t*       hist;          // 256 * bvh_radix_blocks(C)
+    uint32_t*       scan;          // pseudonormal_scan_words(C)
+    double*         nf;            // the face normal, 3 per triangle
+    double*         ang;           // the corner angles, 3 per triangle
+    uint32_t*       stats;
+};
+size_t pseudonormal_scan_words(uint32_t corners);
+void   launch_pseudonormals_build(hipStream_t stream, const PseudonormalArgs& a);
+
 // ---- refit of the kept trees to moved vertices (refit.hip, cap_bvh_refit) ----
 // binary tree: triangle setup (bounds reset first), parent links from the nodes, the build's climb (bvh.hip k_refit) in leaf order
 void   launch_bvh_refit_climb(hipStream_t stream, const BvhBuildArgs& a);  // (bvh.hip) the climb alone

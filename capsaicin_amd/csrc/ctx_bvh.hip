@@ -169,7 +169,89 @@ static int instances_rebuild(CapContext* c)
     return CAP_OK;
 }
 
+// The pseudonormal table from the current vertices (pseudonormal.hip): what cap_pseudonormals_build, cap_bvh_build and cap_bvh_refit
+// share.  The scratch is the build's own -- the tree builders' buffers are sized by triangles, these by corners -- and goes when the
+// call returns.  Waits for the stream: the statistics are read back.  A failure drops the table.
+static int pseudonormals_rebuild(CapContext* c, const char* what)
+{
+    c->pn_ready = false;  // (until the table stands)
+    const uint32_t t = c->tri_count;
+    if (3ull * t >= (1ull << 32)) return fail(CAP_ERR_UNSUPPORTED, "%s: %u triangles have more than 2^32 - 1 corners", what, t);
+    const auto     wall0 = std::chrono::steady_clock::now();
+    const uint32_t n     = 3u * t;
+    uint32_t       stats[8] = {0};
+    if (t)
+    {
+        if (c->pn_table.n < 21 * (size_t)t)
+        {
+            HIP_TRY(hipStreamSynchronize(c->stream));  // (a grown table replaces one an earlier query may still be reading)
+            HIP_TRY(c->pn_table.ensure(21 * (size_t)t));
+        }
+        DevBuf<uint32_t> words, hist, scan, st;
+        DevBuf<double>   reals;
+        HIP_TRY(words.ensure(9 * (size_t)n));
+        HIP_TRY(hist.ensure(256 * bvh_radix_blocks(n)));
+        HIP_TRY(scan.ensure(pseudonormal_scan_words(n)));
+        HIP_TRY(st.ensure(8));
+        HIP_TRY(reals.ensure(2 * (size_t)n));
+        PseudonormalArgs a{};
+        a.positions = c->positions.p, a.indices = c->indices.p, a.tri_ids = c->tri_ids.p, a.mesh_offsets = c->mesh_offsets.p, a.tri_count = t;
+        a.table = c->pn_table.p;
+        uint32_t* w = words.p;
+        a.kx = w, a.ky = w + n, a.kz = w + 2 * (size_t)n, a.keys[0] = w + 3 * (size_t)n, a.keys[1] = w + 4 * (size_t)n;
+        a.vals[0] = w + 5 * (size_t)n, a.vals[1] = w + 6 * (size_t)n, a.weld = w + 7 * (size_t)n, a.flag = w + 8 * (size_t)n;
+        a.hist = hist.p, a.scan = scan.p, a.nf = reals.p, a.ang = reals.p + n, a.stats = st.p;
+        launch_pseudonormals_build(c->stream, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(stats, st.p, sizeof(stats), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    CapPseudonormalsInfo& pi = c->pn_info;
+    pi                       = CapPseudonormalsInfo{};
+    pi.vertices = stats[0], pi.edges = stats[1], pi.boundary_edges = stats[2], pi.nonmanifold_edges = stats[3], pi.inconsistent_edges = stats[4];
+    pi.degenerate_triangles = stats[5];
+    pi.closed   = (stats[2] | stats[3] | stats[4]) == 0 && stats[5] < t ? 1u : 0u;
+    pi.ms       = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    c->pn_ready = true;
+    return CAP_OK;
+}
+
 extern "C" {
+
+int cap_pseudonormals_build(CapContext* c, CapPseudonormalsInfo* out)
+{
+    static_assert(sizeof(CapPseudonormalsInfo) == 40, "the header's record");
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_pseudonormals_build: ctx is NULL");
+    if (const int rc = query_state(c, "cap_pseudonormals_build")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (const int rc = pseudonormals_rebuild(c, "cap_pseudonormals_build")) return rc;
+    if (out) *out = c->pn_info;
+    return CAP_OK;
+}
+
+int cap_pseudonormals_drop(CapContext* c)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_pseudonormals_drop: ctx is NULL");
+    if (c->pn_table.p)
+    {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (a query may still be reading it)
+        c->pn_table.release();
+    }
+    c->pn_ready = false;
+    return CAP_OK;
+}
+
+int cap_pseudonormals_readback(CapContext* c, float* host_normals)
+{
+    if (!c || !host_normals) return fail(CAP_ERR_INVALID_ARG, "cap_pseudonormals_readback: NULL argument");
+    if (const int rc = query_state(c, "cap_pseudonormals_readback")) return rc;
+    if (!c->pn_ready) return fail(CAP_ERR_STATE, "cap_pseudonormals_readback: call cap_pseudonormals_build first");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->tri_count) HIP_TRY(hipMemcpy(host_normals, c->pn_table.p, sizeof(float) * 21 * (size_t)c->tri_count, hipMemcpyDeviceToHost));
+    return CAP_OK;
+}
 
 int cap_bvh_build(CapContext* c)
 {
@@ -327,7 +409,8 @@ int cap_bvh_build(CapContext* c)
         c->inst_count = 0;  // (the instances' objects are gone)
         return rc;
     }
-    return instances_rebuild(c);  // (nothing without a table)
+    if (const int rc = instances_rebuild(c)) return rc;  // (nothing without a table)
+    return c->pn_ready ? pseudonormals_rebuild(c, "cap_bvh_build") : CAP_OK;  // the pseudonormal table, when one exists
 }
 
 int cap_scene_update_vertices(CapContext* c, const float* positions, const float* normals, const float* texcoords, uint32_t flags)
@@ -430,6 +513,8 @@ int cap_bvh_refit(CapContext* c, CapRefitInfo* out)
         return rc;
     }
     if (const int rc = instances_rebuild(c)) return rc;  // world boxes and TLAS from the new bounds (nothing without a table)
+    if (c->pn_ready)                                     // the pseudonormal table, when one exists: rebuilt, the weld included
+        if (const int rc = pseudonormals_rebuild(c, "cap_bvh_refit")) return rc;
     if (out)
     {
         out->ms                         = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();

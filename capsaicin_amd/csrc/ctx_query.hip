@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi; point_query.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi; point_query.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -298,6 +298,31 @@ int closest_points(CapContext* c, const char* what, const CapPointDesc* points, 
     });
 }
 
+// cap_signed_distance (point_query.hip k_closest_points<.., true>): closest_points with the signed array as a third range and the
+// pseudonormal table as part of the state
+int signed_distance(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, CapClosest* out, float* signed_out, const CapTraceOptions* options)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a point", what, options->ray_flags);
+    QueryFilter flt;
+    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
+    if (const int rc = query_state(c, what)) return rc;
+    if (!c->pn_ready) return fail(CAP_ERR_STATE, "%s: call cap_pseudonormals_build first", what);
+    if (n == 0) return CAP_OK;
+    if (!points || !out || !signed_out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, sizeof(CapClosest), 16),
+                                              range("signed", signed_out, sizeof(float), 4)}))
+        return rc;
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    const RayFilter* f = flt.scene();
+    return for_each_chunk(run, points, n, [&](const QueryArgs& q, uint64_t first) {
+        launch_signed_distance(run.cfg, run.bvh, ClosestArgs{q.rays, q.n, reinterpret_cast<float4*>(out + first), run.slack},
+                               SignedArgs{c->pn_table.p, signed_out + first}, f, c->bvh_info.max_depth);
+        return run.traced("k_closest_points<signed>", first);
+    });
+}
+
 // cap_closest_points_multi (point_query.hip k_closest_points_multi): a point's first k candidates in (dist2, triangle) order and / or
 // the number of its candidates -- trace_multi's rules over closest_points' options and tree.  k = 1 without counts or cursor IS
 // cap_closest_points and takes its kernel.
@@ -445,6 +470,12 @@ int cap_trace_instances_multi(CapContext* c, const CapRayDesc* device_rays, uint
 int cap_closest_points(CapContext* c, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, const CapTraceOptions* options)
 {
     return closest_points(c, "cap_closest_points", device_points, n, device_out, options);
+}
+
+int cap_signed_distance(CapContext* c, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, float* device_signed,
+                        const CapTraceOptions* options)
+{
+    return signed_distance(c, "cap_signed_distance", device_points, n, device_out, device_signed, options);
 }
 
 int cap_closest_points_multi(CapContext* c, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out, uint32_t* device_counts,

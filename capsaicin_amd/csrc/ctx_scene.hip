@@ -72,6 +72,8 @@ int cap_scene_upload(CapContext* c, const float* positions, const float* normals
     c->tri_mask_on = false;     // instance masks belong to the previous scene's meshes
     c->inst_count  = 0;         // ... and the instance table to its trees
     c->obj_count   = 0;         // ... and the object table to its mesh table
+    c->pn_ready    = false;     // ... and the pseudonormal table to its triangles
+    c->pn_table.release();
     return CAP_OK;
 }
 

@@ -14,6 +14,9 @@
 // tie rule are one comparison.  bound2 > best unless both are 0 or inf, and the test is a strict >: a subtree at exactly the best
 // distance is opened, its lower id may win.
 //
+// The signed form (cap_signed_distance) is the same kernel with the flag SIGNED: the sign of the winner's delta against the pseudonormal
+// of the feature it lies on (pseudonormal.hip builds the table), in an epilogue the unsigned instantiations do not have.
+//
 // The multi form (cap_closest_points_multi, k_closest_points_multi) is the same walk with the sorted list HitList<K> of cap_hit_list.h
 // in the place of the single best pair; "best" above reads "k-th best", slot K - 1 of the list.
 //
@@ -34,6 +37,7 @@ struct ClosestPoint
 {
     float    x, y, z, d2, u, v;
     uint32_t feature;
+    float    dx, dy, dz;  // delta = ap - m, what d2 is made of (cap_signed_distance's sign)
 };
 
 // (u, v, feature) of the cascade for the record (v0, e1, e2) and ap = p - v0
@@ -106,6 +110,7 @@ __device__ __forceinline__ ClosestPoint closest_record(const float4 t0, const fl
     const float dx = apx - mx, dy = apy - my, dz = apz - mz;
     c.d2 = dot_c(dx, dy, dz, dx, dy, dz);
     c.x = t0.x + mx, c.y = t0.y + my, c.z = t0.z + mz;
+    c.dx = dx, c.dy = dy, c.dz = dz;
     return c;
 }
 
@@ -128,8 +133,10 @@ constexpr int closest_blocks(int STACK) { return STACK <= 16 ? 5 : STACK <= 24 ?
 // FILTER: the mesh-mask table (RayFilter::tri_mask by global id), read before the cascade: a rejected triangle is as if it were not in
 // the scene.  One body, FILTER a template flag of the kernel itself: there is no older plain kernel whose schedule a shared function
 // could disturb, and the plain instantiation carries no trace of the filter (tools/kernel_regs.sh: the same registers).
-template <int STACK, bool FILTER>
-__global__ __launch_bounds__(kBlock, closest_blocks(STACK)) void k_closest_points(BvhDev bvh, ClosestArgs a, RayFilter f)
+// SIGNED (cap_signed_distance): the same walk and record, and an epilogue on the winner's own delta -- one 12-byte gather from the
+// pseudonormal table, dot_c, a square root.  Again a flag of the kernel: the unsigned instantiations keep their registers.
+template <int STACK, bool FILTER, bool SIGNED = false>
+__global__ __launch_bounds__(kBlock, closest_blocks(STACK)) void k_closest_points(BvhDev bvh, ClosestArgs a, RayFilter f, SignedArgs s)
 {
     __shared__ uint2 lds_stack[STACK * kBlock];
     uint2* const     stack = lds_stack + threadIdx.x;
@@ -140,6 +147,7 @@ __global__ __launch_bounds__(kBlock, closest_blocks(STACK)) void k_closest_point
         {
             a.out[2 * (size_t)i]     = make_float4(0.f, 0.f, 0.f, 0.f);
             a.out[2 * (size_t)i + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
+            if constexpr (SIGNED) s.signed_out[i] = __builtin_inff();
             continue;
         }
         const float r2       = p.w * p.w;
@@ -202,6 +210,7 @@ __global__ __launch_bounds__(kBlock, closest_blocks(STACK)) void k_closest_point
         {
             a.out[2 * (size_t)i]     = make_float4(0.f, 0.f, 0.f, r2);
             a.out[2 * (size_t)i + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
+            if constexpr (SIGNED) s.signed_out[i] = __builtin_inff();
             continue;
         }
         // the winner's record from the records in id order (byte copies of the tree's, see multi_write in query.hip)
@@ -209,16 +218,24 @@ __global__ __launch_bounds__(kBlock, closest_blocks(STACK)) void k_closest_point
         const ClosestPoint c   = closest_record(rec[0], rec[1], rec[2], p.x, p.y, p.z);
         a.out[2 * (size_t)i]     = make_float4(c.x, c.y, c.z, c.d2);
         a.out[2 * (size_t)i + 1] = make_float4(c.u, c.v, u2f(best_gid), u2f(c.feature));
+        if constexpr (SIGNED)
+        {
+            // d == 0 (dist2 == 0 among them) and a NaN take the positive sign
+            const float* const nn   = s.normals + 21 * (size_t)best_gid + 3u * c.feature;
+            const float        d    = dot_c(c.dx, c.dy, c.dz, nn[0], nn[1], nn[2]);
+            const float        dist = sqrtf(c.d2);
+            s.signed_out[i]         = d < 0.f ? -dist : dist;
+        }
     }
 }
 
-template <int STACK, bool FILTER>
-void launch_closest_s(const LaunchCfg& cfg, const BvhDev& b, const ClosestArgs& a, const RayFilter& f)
+template <int STACK, bool FILTER, bool SIGNED = false>
+void launch_closest_s(const LaunchCfg& cfg, const BvhDev& b, const ClosestArgs& a, const RayFilter& f, const SignedArgs& s = SignedArgs{})
 {
     uint32_t want = (a.n + kBlock - 1) / kBlock;
     if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_closest_points<STACK, FILTER>), dim3(resident_grid<k_closest_points<STACK, FILTER>>(cfg, want)), dim3(kBlock), 0, cfg.stream,
-                       b, a, f);
+    hipLaunchKernelGGL((k_closest_points<STACK, FILTER, SIGNED>), dim3(resident_grid<k_closest_points<STACK, FILTER, SIGNED>>(cfg, want)), dim3(kBlock),
+                       0, cfg.stream, b, a, f, s);
 }
 
 // ---- k nearest and in-radius (cap_closest_points_multi) ----
@@ -876,6 +893,36 @@ void launch_closest_points(const LaunchCfg& cfg, const BvhDev& bvh, const Closes
         CAP_CLOSEST(64)
     }
 #undef CAP_CLOSEST
+}
+
+void launch_signed_distance(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const SignedArgs& s, const RayFilter* f, uint32_t depth)
+{
+    BvhDev b   = bvh;
+    b.wide8_ok = 0;
+    const bool      filter = f && f->tri_mask;
+    const RayFilter rf     = f ? *f : RayFilter{};
+#define CAP_SIGNED(S)                                          \
+    if (filter)                                                \
+        launch_closest_s<S, true, true>(cfg, b, a, rf, s);     \
+    else                                                       \
+        launch_closest_s<S, false, true>(cfg, b, a, rf, s);
+    if (depth <= 16)
+    {
+        CAP_SIGNED(16)
+    }
+    else if (depth <= 24)
+    {
+        CAP_SIGNED(24)
+    }
+    else if (depth <= 32)
+    {
+        CAP_SIGNED(32)
+    }
+    else
+    {
+        CAP_SIGNED(64)
+    }
+#undef CAP_SIGNED
 }
 
 void launch_closest_points_multi(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestMultiArgs& m, const RayFilter* f, uint32_t depth)

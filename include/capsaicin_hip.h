@@ -517,8 +517,8 @@ int cap_trace_rays_multi_ex(CapContext* ctx, const CapRayDesc* device_rays, uint
  * are stale after cap_scene_update_vertices.  options: instance_mask and the mesh-mask table act exactly as in the ray queries (a mesh
  * with mask 0 is invisible here too); any ray_flags bit is CAP_ERR_INVALID_ARG (facing and first hit mean nothing for a point), as are
  * non-zero reserved words and instance_mask > 0xFF; NULL or all-zero is the plain call.
- * Not covered: per-point masks, the sign of the distance (`feature` is what a caller needs to build it from the normals of the face,
- * edge or vertex).  Instances and objects: cap_closest_instances below, nearest in world space. */
+ * Not covered: per-point masks.  The sign of the distance: cap_signed_distance below.  Instances and objects: cap_closest_instances
+ * below, nearest in world space. */
 typedef struct CapPointDesc /* 16 B */
 {
     float point[3];
@@ -773,6 +773,65 @@ int cap_closest_instances(CapContext* ctx, const CapPointDesc* device_points, ui
 int cap_closest_instances_multi(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out,
                                 uint32_t* device_instances, uint32_t* device_counts, uint32_t multi_flags,
                                 const CapTraceOptions* options /* may be NULL */);
+
+/* ---- signed distance: the pseudonormal table and cap_signed_distance ----
+ * cap_closest_points with a sign: negative inside a closed mesh.  The sign is that of dot(delta, N), N the angle-weighted pseudonormal
+ * (Baerentzen & Aanaes 2005) of the FEATURE the record reports -- the face, edge or vertex the closest point lies on -- not the face
+ * normal of the returned triangle: in an edge or vertex region the (dist2, lowest id) tie rule may return a face the point lies behind
+ * (DESIGN.md "Signed distance" has counts).  The library builds the table because only it holds the mesh's connectivity across
+ * duplicated vertices on the device, and keeps it current under cap_bvh_refit.
+ *
+ * The table (cap_pseudonormals_build) is made from the scene's ORIGINAL vertices, not the stored (v0, e1, e2) records, in binary64:
+ *   weld      two vertices are one iff their three binary32 coordinates are equal after mapping -0 to +0, across the whole scene and
+ *             all its meshes (OBJ material splits and triangle soups duplicate vertices); a non-finite coordinate welds to nothing;
+ *   degenerate  a triangle with a non-finite corner, two corners of one weld id, or (v1 - v0) x (v2 - v0) == 0 in binary64 takes part
+ *             in nothing -- no half-edge, no sum, no statistic but its own counter -- and its seven entries are +0;
+ *   face      Nf = normalize((v1 - v0) x (v2 - v0)), on the side of the n = e1 x e2 the ray queries decide facing from: a front-facing
+ *             hit comes from the positive side;
+ *   edge      between weld ids (a, b), undirected: the sum of Nf over the live triangles on it;
+ *   vertex    the sum of angle x Nf over the live corners at it, angle = atan2(|a x b|, a . b) of the two edges leaving the corner.
+ * The sums are not normalised (only the sign is used); they run in ascending (triangle, corner) order and each component is rounded
+ * ONCE to binary32 on store, so the same triangle list gives the same bits however its vertices are indexed or split over meshes.
+ * cap_pseudonormals_readback copies the table out: 7 x 3 floats per triangle by global id, the entries indexed by CAP_FEATURE_*
+ * (FACE, EDGE_V0V1, EDGE_V1V2, EDGE_V2V0, V0, V1, V2).  CapPseudonormalsInfo counts what the weld found; the sign means inside /
+ * outside only for a mesh with closed == 1 (every edge on exactly two triangles that traverse it in opposite directions).  The table
+ * and the query are defined for any mesh.
+ *
+ * cap_pseudonormals_build needs a built tree that is not stale (CAP_ERR_STATE); 3 x triangles >= 2^32 is CAP_ERR_UNSUPPORTED.  It
+ * waits for the device once (the statistics).  out may be NULL.  cap_pseudonormals_drop frees the table (CAP_OK without one).
+ * cap_pseudonormals_readback is CAP_ERR_STATE without a table or while the trees are stale.
+ * Life cycle: cap_scene_upload drops the table; cap_scene_update_vertices makes it stale together with the trees; cap_bvh_build and
+ * cap_bvh_refit rebuild it by the same routine when one exists -- the weld included, because moved vertices may weld differently;
+ * cap_scene_set_instance_masks, objects and instances do not touch it.  It always covers every triangle, whatever the masks.
+ * Memory: 84 B per triangle for the table, plus about 150 B per triangle of build scratch that is freed when the build returns.
+ *
+ * cap_signed_distance.  device_out[i] is bit for bit cap_closest_points' record: candidates, tie rule, masks, miss record and
+ * degenerate points are unchanged.  For a record (g, feature): d = dot(delta, N[g][feature]), delta the record's own
+ * fl(ap - fl(fl(e1*u) + fl(e2*v))) of the per-triangle function above, N the stored binary32 entry, dot the queries' unfused
+ * (a.x*b.x + a.y*b.y) + a.z*b.z; device_signed[i] = -sqrt(dist2) if d < 0, else +sqrt(dist2), sqrt the correctly rounded binary32
+ * square root.  d == 0 takes the positive sign (dist2 == 0 gives +0.0).  A miss or a degenerate point gives +inf.  So a float32
+ * computation on the read-back table and the record's (u, v) is bit-identical.
+ * Conventions are cap_closest_points' plus: device_signed is required and 4-byte aligned, no two of the three ranges overlap, and
+ * CAP_ERR_STATE also without a table.  Nothing is written on an error; n above 2^24 is split into launches.
+ * Not covered: the sign over instances (a mirror flips it, and a non-rigid transform changes both the angles and the normals, so it
+ * needs a table per instance or reweighting on the fly), the k-nearest forms, generalised winding numbers for open meshes. */
+typedef struct CapPseudonormalsInfo
+{
+    uint32_t vertices;             /* welded positions of the live triangles */
+    uint32_t edges;                /* undirected edges between them */
+    uint32_t boundary_edges;       /* ... with one triangle */
+    uint32_t nonmanifold_edges;    /* ... with more than two */
+    uint32_t inconsistent_edges;   /* ... with exactly two that traverse it in the same direction */
+    uint32_t degenerate_triangles;
+    uint32_t closed;               /* 1 iff the three edge defect counts are 0 and at least one triangle is live */
+    uint32_t reserved;
+    double   ms;                   /* wall time of the build */
+} CapPseudonormalsInfo;
+int cap_pseudonormals_build(CapContext* ctx, CapPseudonormalsInfo* out /* may be NULL */);
+int cap_pseudonormals_drop(CapContext* ctx);
+int cap_pseudonormals_readback(CapContext* ctx, float* host_normals /* 21 floats per triangle */);
+int cap_signed_distance(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, float* device_signed,
+                        const CapTraceOptions* options /* may be NULL */);
 
 /* ---- objects: per-mesh-range bottom-level trees for the instanced queries ----
  * An object is the mesh range [first_mesh, first_mesh + mesh_count) of the uploaded scene: mesh_count >= 1, at least one triangle,

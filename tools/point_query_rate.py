@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
-"""Throughput of the closest-point queries (cap_closest_points, cap_closest_points_multi, cap_closest_instances,
+"""Throughput of the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances,
 cap_closest_instances_multi) on the 262 k-triangle hall -- not part of bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
-                                     [--k K [--counts]] [--instances N]
+                                     [--k K [--counts]] [--instances N] [--signed]
+
+--signed runs cap_signed_distance after cap_pseudonormals_build.  Each line carries its rate and, measured in the same process on the
+same points, cap_closest_points as the baseline (flat_ms, flat_mpoints_per_s, time_over_flat = the signed call's time over the plain
+one's), same_records (the share of records equal to the plain call's: has to be 1.0), negative (the share of hits with a negative
+distance), and the table build: table_build_ms beside the tree's bvh_build_ms, and the weld's statistics.
 
 --instances N runs cap_closest_instances on the hall under N transforms: instance 0 is the identity, the others stand on a square grid
 around it, 1.1 scene sizes apart, each turned about the vertical by an angle of its own (N = 1: the identity alone).  The point sets
@@ -84,7 +89,10 @@ def main():
     ap.add_argument("--k", type=int, default=None)
     ap.add_argument("--counts", action="store_true")
     ap.add_argument("--instances", type=int, default=None)
+    ap.add_argument("--signed", action="store_true")
     a = ap.parse_args()
+    if a.signed and (a.k is not None or a.instances is not None):
+        ap.error("--signed runs alone: the sign is defined for cap_closest_points' record")
     if a.instances is not None and a.instances < 1:
         ap.error("--instances N needs N >= 1")
     inst_multi = a.instances is not None and a.k is not None
@@ -121,6 +129,10 @@ def main():
         flat_out = torch.empty((n * max(a.k or 1, 1), 8), dtype=torch.float32, device=dev)
         single_out, flat_cnt = (torch.empty((n, 8), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)) if inst_multi else (None, None)
     cnt = torch.empty((n,), dtype=torch.int32, device=dev) if a.counts else None
+    if a.signed:
+        pn = r.build_pseudonormals()
+        signed = torch.empty((n,), dtype=torch.float32, device=dev)
+        flat_out = torch.empty((n, 8), dtype=torch.float32, device=dev)
     head = dict(scene="hall", triangles=int(info.triangle_count), depth=int(info.max_depth), n=n, radius=a.radius, reps=a.reps)
     if a.k is not None:
         head.update(k=a.k, counts=a.counts)
@@ -142,6 +154,10 @@ def main():
             flat = lambda: capi._check(L.cap_closest_points(r.ctx, pts.data_ptr(), n, flat_out.data_ptr(), None), "cap_closest_points")
             flat_sec = timed(r, flat, a.reps, a.warmup)
             call = lambda: capi._check(L.cap_closest_instances(r.ctx, pts.data_ptr(), n, out.data_ptr(), inst.data_ptr(), None), "cap_closest_instances")
+        elif a.signed:
+            flat = lambda: capi._check(L.cap_closest_points(r.ctx, pts.data_ptr(), n, flat_out.data_ptr(), None), "cap_closest_points")
+            flat_sec = timed(r, flat, a.reps, a.warmup)
+            call = lambda: capi._check(L.cap_signed_distance(r.ctx, pts.data_ptr(), n, out.data_ptr(), signed.data_ptr(), None), "cap_signed_distance")
         elif a.k is None:
             call = lambda: capi._check(L.cap_closest_points(r.ctx, pts.data_ptr(), n, out.data_ptr(), None), "cap_closest_points")
         else:
@@ -168,10 +184,16 @@ def main():
             same = float((out.view(torch.int32) == flat_out.view(torch.int32)).all(1).float().mean())
             line.update(instances=a.instances, inert=int(info_i.inert), tlas_depth=int(info_i.tlas_depth), flat_ms=round(flat_sec * 1e3, 3),
                         flat_mpoints_per_s=round(n / flat_sec / 1e6, 1), ratio_to_flat=round(flat_sec / sec, 3), same_as_flat=round(same, 4))
+        if a.signed:
+            same = float((out.view(torch.int32) == flat_out.view(torch.int32)).all(1).float().mean())
+            sd = signed.cpu().numpy()
+            line.update(flat_ms=round(flat_sec * 1e3, 3), flat_mpoints_per_s=round(n / flat_sec / 1e6, 1), time_over_flat=round(sec / flat_sec, 4),
+                        same_records=round(same, 4), negative=round(float((sd[hit] < 0).mean()), 4) if hit.any() else None,
+                        table_build_ms=round(pn.ms, 3), bvh_build_ms=round(info.build_ms, 3), weld={k: v for k, v in pn.as_dict().items() if k != "ms"})
         if a.k is not None:
             line.update(mean_candidates=round(float(cnt.cpu().numpy().astype(np.float64).mean() if a.counts else listed.sum(1).mean()), 3))
         print(json.dumps(line), flush=True)
-    if a.instances is not None:
+    if a.instances is not None or a.signed:
         r.close()
         return
     rays = torch.as_tensor(random_rays(lo, hi, n, rng), device=dev).contiguous()
