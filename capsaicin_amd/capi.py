@@ -760,21 +760,21 @@ class Renderer:
         return out
 
     # ---- closest-point queries (cap_closest_points) ----
-    def closest_points(self, points, out=None, sync=True, mask=None):
-        """The triangle nearest to each point within its radius.  points: (N, 4) float32 = CapPointDesc rows (x, y, z, radius; +inf:
-        unbounded), a contiguous torch tensor on this context's device or a numpy array (staged through torch; the records come back as
-        numpy).  Returns (N, 8) float32 CapClosest records (closest point, dist2, u, v, triangle and feature bits: closest_triangles()
-        reads those); a miss is (0, 0, 0, radius^2, 0, 0, MISS, 0).  mask= is the instance inclusion mask (set_instance_masks).  sync as
-        trace_rays."""
+    def _stage_points(self, points):
+        """(device, points on it, N) of a closest-point call: a contiguous (N, 4) float32 tensor as it is, a numpy array staged through
+        torch"""
         import torch
         dev = torch.device("cuda", self.device)
-        host = isinstance(points, np.ndarray)
-        if host:
+        if isinstance(points, np.ndarray):
             points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
-            sync = True  # the result is read back to the host
         if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
             raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
-        n = points.shape[0]
+        return dev, points, points.shape[0]
+
+    def _records_out(self, out, n, dev):
+        """(the (n, 8) float32 record tensor, the caller's numpy array or None) of out=: a tensor is checked, a numpy array or None gets
+        a new one"""
+        import torch
         host_out = None
         if isinstance(out, np.ndarray):
             host_out, out = out, None
@@ -782,20 +782,69 @@ class Renderer:
             out = torch.empty((n, 8), dtype=torch.float32, device=dev)
         elif out.dtype != torch.float32 or tuple(out.shape) != (n, 8) or not out.is_contiguous() or out.device != dev:
             raise CapError("out must be a contiguous (%d, 8) float32 tensor on %s" % (n, dev))
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()  # the points (and out's allocation) were made on torch's stream
-        options = self.trace_options(None, mask)
-        _check(lib().cap_closest_points(self.ctx, C.c_void_p(points.data_ptr()), n, C.c_void_p(out.data_ptr()),
-                                        C.byref(options) if options is not None else None), "cap_closest_points")
+        return out, host_out
+
+    def _resume_page(self, page, shape, dtype, dev, bad_size, bad_layout):
+        """(one page of a multi query on the device, the caller's numpy page or None): a new one without a page to resume from, a numpy
+        page staged through torch, a tensor checked; bad_size / bad_layout are the messages of the two failures"""
+        import torch
+        if page is None:
+            return torch.empty(shape, dtype=dtype, device=dev), None
+        if isinstance(page, np.ndarray):
+            if page.size != int(np.prod(shape)):
+                raise CapError(bad_size)
+            return torch.from_numpy(np.ascontiguousarray(page, {torch.float32: np.float32, torch.int32: np.int32}[dtype]).reshape(shape)).to(dev), page
+        if page.dtype != dtype or tuple(page.shape) != tuple(shape) or not page.is_contiguous() or page.device != dev:
+            raise CapError(bad_layout)
+        return page, None
+
+    def _page_size(self, k, counts, resuming, pages):
+        k = int(k)
+        if not 0 <= k <= self.MULTI_MAX_K:
+            raise CapError("k must be in 0 .. %d (page with resume=), got %d" % (self.MULTI_MAX_K, k))
+        if k == 0 and (not counts or resuming):
+            raise CapError("k = 0 counts only: pass counts=True and no resume %s" % pages)
+        return k
+
+    def _results(self, sync, host, outputs, host_outputs):
+        """After the launch: waits for it with sync, then the outputs as the caller gets them -- the device tensors, or with host numpy
+        copies, written into the caller's own array where host_outputs holds one"""
         if sync:
             self.sync()
-        if host or host_out is not None:
-            res = out.cpu().numpy()
-            if host_out is not None:
-                host_out[...] = res.reshape(host_out.shape)
-                return host_out
-            return res
-        return out
+        if not host:
+            return list(outputs)
+        res = []
+        for out, mine in zip(outputs, host_outputs):
+            h = out.cpu().numpy()
+            if mine is not None:
+                mine[...] = h.reshape(mine.shape)
+                h = mine
+            res.append(h)
+        return res
+
+    def _closest_single(self, name, points, out, sync, mask, second=None):
+        """One record per point through the entry point `name`; second=<dtype>: it also fills an (N,) array of that type"""
+        import torch
+        host = isinstance(points, np.ndarray)
+        sync = sync or host  # the result is read back to the host
+        dev, points, n = self._stage_points(points)
+        out, host_out = self._records_out(out, n, dev)
+        extra = [] if second is None else [torch.empty((n,), dtype=second, device=dev)]
+        if sync:
+            torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
+        options = self.trace_options(None, mask)
+        _check(getattr(lib(), name)(self.ctx, C.c_void_p(points.data_ptr()), n, C.c_void_p(out.data_ptr()), *[C.c_void_p(t.data_ptr()) for t in extra],
+                                    C.byref(options) if options is not None else None), name)
+        res = self._results(sync, host or host_out is not None, [out] + extra, [host_out] + [None] * len(extra))
+        return res[0] if second is None else tuple(res)
+
+    def closest_points(self, points, out=None, sync=True, mask=None):
+        """The triangle nearest to each point within its radius.  points: (N, 4) float32 = CapPointDesc rows (x, y, z, radius; +inf:
+        unbounded), a contiguous torch tensor on this context's device or a numpy array (staged through torch; the records come back as
+        numpy).  Returns (N, 8) float32 CapClosest records (closest point, dist2, u, v, triangle and feature bits: closest_triangles()
+        reads those); a miss is (0, 0, 0, radius^2, 0, 0, MISS, 0).  mask= is the instance inclusion mask (set_instance_masks).  sync as
+        trace_rays."""
+        return self._closest_single("cap_closest_points", points, out, sync, mask)
 
     # ---- signed distance (cap_pseudonormals_*, cap_signed_distance) ----
     def build_pseudonormals(self):
@@ -821,36 +870,7 @@ class Renderer:
         reports, +sqrt(dist2) otherwise, +inf on a miss.  Needs build_pseudonormals().  points, out, sync and mask= as closest_points;
         numpy points give numpy results."""
         import torch
-        dev = torch.device("cuda", self.device)
-        host = isinstance(points, np.ndarray)
-        if host:
-            points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
-            sync = True  # the result is read back to the host
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
-            raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
-        n = points.shape[0]
-        host_out = None
-        if isinstance(out, np.ndarray):
-            host_out, out = out, None
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.float32, device=dev)
-        elif out.dtype != torch.float32 or tuple(out.shape) != (n, 8) or not out.is_contiguous() or out.device != dev:
-            raise CapError("out must be a contiguous (%d, 8) float32 tensor on %s" % (n, dev))
-        signed = torch.empty((n,), dtype=torch.float32, device=dev)
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
-        options = self.trace_options(None, mask)
-        _check(lib().cap_signed_distance(self.ctx, C.c_void_p(points.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(signed.data_ptr()),
-                                         C.byref(options) if options is not None else None), "cap_signed_distance")
-        if sync:
-            self.sync()
-        if host or host_out is not None:
-            res = out.cpu().numpy()
-            if host_out is not None:
-                host_out[...] = res.reshape(host_out.shape)
-                res = host_out
-            return res, signed.cpu().numpy()
-        return out, signed
+        return self._closest_single("cap_signed_distance", points, out, sync, mask, torch.float32)
 
     def closest_instances(self, points, out=None, sync=True, mask=None):
         """The (instance, triangle) nearest to each point in WORLD space over the instance table (cap_closest_instances): (records
@@ -858,36 +878,7 @@ class Renderer:
         (u, v), the scene's triangle id and the feature: closest_triangles() reads those.  points, out, sync and mask= as
         closest_points; numpy points give numpy results."""
         import torch
-        dev = torch.device("cuda", self.device)
-        host = isinstance(points, np.ndarray)
-        if host:
-            points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
-            sync = True  # the result is read back to the host
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
-            raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
-        n = points.shape[0]
-        host_out = None
-        if isinstance(out, np.ndarray):
-            host_out, out = out, None
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.float32, device=dev)
-        elif out.dtype != torch.float32 or tuple(out.shape) != (n, 8) or not out.is_contiguous() or out.device != dev:
-            raise CapError("out must be a contiguous (%d, 8) float32 tensor on %s" % (n, dev))
-        inst = torch.empty((n,), dtype=torch.int32, device=dev)
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
-        options = self.trace_options(None, mask)
-        _check(lib().cap_closest_instances(self.ctx, C.c_void_p(points.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(inst.data_ptr()),
-                                           C.byref(options) if options is not None else None), "cap_closest_instances")
-        if sync:
-            self.sync()
-        if host or host_out is not None:
-            res = out.cpu().numpy()
-            if host_out is not None:
-                host_out[...] = res.reshape(host_out.shape)
-                res = host_out
-            return res, inst.cpu().numpy()
-        return out, inst
+        return self._closest_single("cap_closest_instances", points, out, sync, mask, torch.int32)
 
     def closest_points_multi(self, points, k, counts=False, resume=None, sync=True, mask=None):
         """The k triangles nearest to each point within its radius, in (dist2, triangle) order (cap_closest_points_multi): (N, k, 8)
@@ -898,46 +889,21 @@ class Renderer:
         returns it.  points, sync and mask= as closest_points; numpy points (or a numpy resume page) give numpy results."""
         import torch
         options = self.trace_options(None, mask)
-        dev = torch.device("cuda", self.device)
         host = isinstance(points, np.ndarray) or isinstance(resume, np.ndarray)
-        if isinstance(points, np.ndarray):
-            points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
-        if host:
-            sync = True  # the result is read back to the host
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
-            raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
-        n, k = points.shape[0], int(k)
-        if not 0 <= k <= self.MULTI_MAX_K:
-            raise CapError("k must be in 0 .. %d (page with resume=), got %d" % (self.MULTI_MAX_K, k))
-        if k == 0 and (not counts or resume is not None):
-            raise CapError("k = 0 counts only: pass counts=True and no resume page")
-        host_page = None
-        if resume is None:
-            page = torch.empty((n, k, 8), dtype=torch.float32, device=dev)
-        elif isinstance(resume, np.ndarray):
-            if resume.size != n * k * 8:
-                raise CapError("resume must be the (%d, %d, 8) float32 page of the previous call, got %s" % (n, k, resume.shape))
-            host_page = resume
-            page = torch.from_numpy(np.ascontiguousarray(resume, np.float32).reshape(n, k, 8)).to(dev)
-        else:
-            page = resume
-            if page.dtype != torch.float32 or tuple(page.shape) != (n, k, 8) or not page.is_contiguous() or page.device != dev:
-                raise CapError("resume must be the contiguous (%d, %d, 8) float32 page of the previous call" % (n, k))
-        cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
+        sync = sync or host  # the result is read back to the host
+        dev, points, n = self._stage_points(points)
+        k = self._page_size(k, counts, resume is not None, "page")
+        page, host_page = self._resume_page(resume, (n, k, 8), torch.float32, dev,
+                                            "resume must be the (%d, %d, 8) float32 page of the previous call, got %s" % (n, k, getattr(resume, "shape", None)),
+                                            "resume must be the contiguous (%d, %d, 8) float32 page of the previous call" % (n, k))
+        cnt = [torch.empty((n,), dtype=torch.int32, device=dev)] if counts else []
         if sync:
             torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
         _check(lib().cap_closest_points_multi(self.ctx, C.c_void_p(points.data_ptr()), n, k, C.c_void_p(page.data_ptr()) if k else None,
-                                              C.c_void_p(cnt.data_ptr()) if counts else None, self.MULTI_CONTINUE if resume is not None else 0,
+                                              C.c_void_p(cnt[0].data_ptr()) if counts else None, self.MULTI_CONTINUE if resume is not None else 0,
                                               C.byref(options) if options is not None else None), "cap_closest_points_multi")
-        if sync:
-            self.sync()
-        if host:
-            h = page.cpu().numpy()
-            if host_page is not None:
-                host_page[...] = h.reshape(host_page.shape)
-                h = host_page
-            return (h, cnt.cpu().numpy()) if counts else h
-        return (page, cnt) if counts else page
+        res = self._results(sync, host, [page] + cnt, [host_page, None])
+        return tuple(res) if counts else res[0]
 
     def closest_instances_multi(self, points, k, counts=False, resume=None, sync=True, mask=None):
         """The k (instance, triangle) pairs nearest to each point in WORLD space within its radius, in (dist2, instance, triangle) order
@@ -949,55 +915,30 @@ class Renderer:
         points (or numpy resume pages) give numpy results."""
         import torch
         options = self.trace_options(None, mask)
-        dev = torch.device("cuda", self.device)
         if resume is not None and (not isinstance(resume, (tuple, list)) or len(resume) != 2):
             raise CapError("resume must be the (records, instances) pair of the previous call")
         host = isinstance(points, np.ndarray) or (resume is not None and any(isinstance(p, np.ndarray) for p in resume))
-        if isinstance(points, np.ndarray):
-            points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
-        if host:
-            sync = True  # the result is read back to the host
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
-            raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
-        n, k = points.shape[0], int(k)
-        if not 0 <= k <= self.MULTI_MAX_K:
-            raise CapError("k must be in 0 .. %d (page with resume=), got %d" % (self.MULTI_MAX_K, k))
-        if k == 0 and (not counts or resume is not None):
-            raise CapError("k = 0 counts only: pass counts=True and no resume pages")
-        host_pages = [None, None]
-        if resume is None:
-            rec = torch.empty((n, k, 8), dtype=torch.float32, device=dev)
-            inst = torch.empty((n, k), dtype=torch.int32, device=dev)
-        else:
-            pages = []
-            for j, (page, shape, dtype, np_dtype) in enumerate(((resume[0], (n, k, 8), torch.float32, np.float32),
-                                                                 (resume[1], (n, k), torch.int32, np.int32))):
-                if isinstance(page, np.ndarray):
-                    if page.size != int(np.prod(shape)):
-                        raise CapError("resume[%d] must hold the %s page of the previous call, got %s" % (j, shape, page.shape))
-                    host_pages[j] = page
-                    page = torch.from_numpy(np.ascontiguousarray(page, np_dtype).reshape(shape)).to(dev)
-                elif page.dtype != dtype or tuple(page.shape) != shape or not page.is_contiguous() or page.device != dev:
-                    raise CapError("resume[%d] must be the contiguous %s %s page of the previous call" % (j, shape, dtype))
-                pages.append(page)
-            rec, inst = pages
-        cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
+        sync = sync or host  # the result is read back to the host
+        dev, points, n = self._stage_points(points)
+        k = self._page_size(k, counts, resume is not None, "pages")
+        pages, host_pages = [], []
+        for j, (shape, dtype) in enumerate((((n, k, 8), torch.float32), ((n, k), torch.int32))):
+            given = None if resume is None else resume[j]
+            page, mine = self._resume_page(given, shape, dtype, dev,
+                                           "resume[%d] must hold the %s page of the previous call, got %s" % (j, shape, getattr(given, "shape", None)),
+                                           "resume[%d] must be the contiguous %s %s page of the previous call" % (j, shape, dtype))
+            pages.append(page)
+            host_pages.append(mine)
+        rec, inst = pages
+        cnt = [torch.empty((n,), dtype=torch.int32, device=dev)] if counts else []
         if sync:
             torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
         _check(lib().cap_closest_instances_multi(self.ctx, C.c_void_p(points.data_ptr()), n, k, C.c_void_p(rec.data_ptr()) if k else None,
-                                                 C.c_void_p(inst.data_ptr()) if k else None, C.c_void_p(cnt.data_ptr()) if counts else None,
+                                                 C.c_void_p(inst.data_ptr()) if k else None, C.c_void_p(cnt[0].data_ptr()) if counts else None,
                                                  self.MULTI_CONTINUE if resume is not None else 0, C.byref(options) if options is not None else None),
                "cap_closest_instances_multi")
-        if sync:
-            self.sync()
-        if host:
-            out = [rec.cpu().numpy(), inst.cpu().numpy()]
-            for j in range(2):
-                if host_pages[j] is not None:
-                    host_pages[j][...] = out[j].reshape(host_pages[j].shape)
-                    out[j] = host_pages[j]
-            return (out[0], out[1], cnt.cpu().numpy()) if counts else (out[0], out[1])
-        return (rec, inst, cnt) if counts else (rec, inst)
+        return tuple(self._results(sync, host, pages + cnt, host_pages + [None]))
+
 
     # ---- instanced ray queries (cap_instances_set, cap_trace_instances*) ----
     def set_objects(self, ranges):

@@ -277,140 +277,91 @@ int trace_instances_multi(CapContext* c, const char* what, const CapRayDesc* ray
     });
 }
 
-// cap_closest_points (point_query.hip k_closest_points): the binary tree alone
-int closest_points(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, CapClosest* out, const CapTraceOptions* options)
+// What one of the five closest-point entry points is, beside the points and the record array every one of them has: its further arrays
+// and its page rules.  One record per point (k = 1) unless multi.
+struct PointCall
+{
+    bool      with_sign  = false;    // cap_signed_distance: the pseudonormal table is part of the state ...
+    float*    signed_out = nullptr;  // ... and the signed array a third range
+    bool      instanced  = false;    // cap_closest_instances*: trace_instances' state and pools ...
+    uint32_t* inst       = nullptr;  // ... and the instance array, one entry per record (may be left out unless multi)
+    bool      multi      = false;    // cap_closest_*_multi: trace_multi's rules on k, counts and flags
+    uint32_t  k          = 1;
+    uint32_t* counts     = nullptr;
+    uint32_t  flags      = 0;
+};
+PointCall with_sign(float* signed_out)
+{
+    PointCall q;
+    q.with_sign = true, q.signed_out = signed_out;
+    return q;
+}
+PointCall over_instances(uint32_t* inst)
+{
+    PointCall q;
+    q.instanced = true, q.inst = inst;
+    return q;
+}
+PointCall paged(PointCall q, uint32_t k, uint32_t* counts, uint32_t flags)
+{
+    q.multi = true, q.k = k, q.counts = counts, q.flags = flags;
+    return q;
+}
+
+// The closest-point queries (point_query.hip): the binary tree alone, or with q.instanced the object trees under the instance table.
+// A multi call with k = 1, no counts and no cursor IS the single query and takes its kernel.
+int closest_query(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, CapClosest* out, const PointCall& q, const CapTraceOptions* options)
 {
     static_assert(sizeof(CapPointDesc) == sizeof(float4) && sizeof(CapClosest) == 2 * sizeof(float4), "point records are the kernel's float4 records");
+    const bool pairs = q.instanced && q.multi;  // a page of instances belongs to the page of records
     if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
     if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a point", what, options->ray_flags);
     QueryFilter flt;
-    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
+    if (const int rc = q.multi ? multi_rules(c, what, q.k, q.flags, options, pairs ? "output and instances" : "output", out || (pairs && q.inst), q.counts, flt)
+                               : query_filter(c, what, options, false, flt))
+        return rc;
     if (const int rc = query_state(c, what)) return rc;
+    if (q.with_sign && !c->pn_ready) return fail(CAP_ERR_STATE, "%s: call cap_pseudonormals_build first", what);
+    if (q.instanced && c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
     if (n == 0) return CAP_OK;
-    if (!points || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, sizeof(CapClosest), 16)})) return rc;
-    QueryRun run;
-    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
-    const RayFilter* f = flt.scene();
-    return for_each_chunk(run, points, n, [&](const QueryArgs& q, uint64_t first) {
-        launch_closest_points(run.cfg, run.bvh, ClosestArgs{q.rays, q.n, reinterpret_cast<float4*>(out + first), run.slack}, f, c->bvh_info.max_depth);
-        return run.traced("k_closest_points", first);
-    });
-}
-
-// cap_signed_distance (point_query.hip k_closest_points<.., true>): closest_points with the signed array as a third range and the
-// pseudonormal table as part of the state
-int signed_distance(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, CapClosest* out, float* signed_out, const CapTraceOptions* options)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a point", what, options->ray_flags);
-    QueryFilter flt;
-    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
-    if (const int rc = query_state(c, what)) return rc;
-    if (!c->pn_ready) return fail(CAP_ERR_STATE, "%s: call cap_pseudonormals_build first", what);
-    if (n == 0) return CAP_OK;
-    if (!points || !out || !signed_out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, sizeof(CapClosest), 16),
-                                              range("signed", signed_out, sizeof(float), 4)}))
+    if (!points || (q.k && !out) || (q.k && pairs && !q.inst) || (q.with_sign && !q.signed_out))
+        return pairs ? fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer (k = %u needs output and instances)", what, q.k) : fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, (uint64_t)q.k * sizeof(CapClosest), 16),
+                                              range("signed", q.signed_out, sizeof(float), 4), range("instances", q.inst, (uint64_t)q.k * sizeof(uint32_t), 4),
+                                              range("counts", q.counts, sizeof(uint32_t), 4)}))
         return rc;
     QueryRun run;
     if (const int rc = query_prepare(c, what, n, run, false)) return rc;
-    const RayFilter* f = flt.scene();
-    return for_each_chunk(run, points, n, [&](const QueryArgs& q, uint64_t first) {
-        launch_signed_distance(run.cfg, run.bvh, ClosestArgs{q.rays, q.n, reinterpret_cast<float4*>(out + first), run.slack},
-                               SignedArgs{c->pn_table.p, signed_out + first}, f, c->bvh_info.max_depth);
-        return run.traced("k_closest_points<signed>", first);
-    });
-}
-
-// cap_closest_points_multi (point_query.hip k_closest_points_multi): a point's first k candidates in (dist2, triangle) order and / or
-// the number of its candidates -- trace_multi's rules over closest_points' options and tree.  k = 1 without counts or cursor IS
-// cap_closest_points and takes its kernel.
-int closest_points_multi(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, uint32_t k, CapClosest* out, uint32_t* counts,
-                         uint32_t flags, const CapTraceOptions* options)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a point", what, options->ray_flags);
-    QueryFilter flt;
-    if (const int rc = multi_rules(c, what, k, flags, options, "output", out != nullptr, counts, flt)) return rc;
-    if (const int rc = query_state(c, what)) return rc;
-    if (n == 0) return CAP_OK;
-    if (!points || (k && !out)) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, (uint64_t)k * sizeof(CapClosest), 16),
-                                              range("counts", counts, sizeof(uint32_t), 4)}))
-        return rc;
-    QueryRun run;
-    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    if (q.instanced) use_instance_pools(run);
     const RayFilter* f      = flt.scene();
-    const bool       single = k == 1 && !counts && !(flags & CAP_MULTI_CONTINUE);
-    return for_each_chunk(run, points, n, [&](const QueryArgs& q, uint64_t first) {
-        const ClosestArgs a{q.rays, q.n, reinterpret_cast<float4*>(at(out, first * k)), run.slack};
-        if (single)
+    const uint32_t   resume = (q.flags & CAP_MULTI_CONTINUE) ? 1u : 0u;
+    const bool       single = q.k == 1 && !q.counts && !resume;
+    return for_each_chunk(run, points, n, [&](const QueryArgs& chunk, uint64_t first) {
+        // (the instanced kernels take their slack per point and instance: cap_near.h)
+        const ClosestArgs a{chunk.rays, chunk.n, reinterpret_cast<float4*>(at(out, first * q.k)), q.instanced ? 0.f : run.slack};
+        uint32_t* const   counts = at(q.counts, first);
+        if (!q.instanced)
         {
-            launch_closest_points(run.cfg, run.bvh, a, f, c->bvh_info.max_depth);
-            return run.traced("k_closest_points", first);
+            if (q.with_sign)
+            {
+                launch_signed_distance(run.cfg, run.bvh, a, SignedArgs{c->pn_table.p, q.signed_out + first}, f, c->bvh_info.max_depth);
+                return run.traced("k_closest_points<signed>", first);
+            }
+            if (single)
+            {
+                launch_closest_points(run.cfg, run.bvh, a, f, c->bvh_info.max_depth);
+                return run.traced("k_closest_points", first);
+            }
+            launch_closest_points_multi(run.cfg, run.bvh, ClosestMultiArgs{a, q.k, counts, resume}, f, c->bvh_info.max_depth);
+            return run.traced("k_closest_points_multi", first);
         }
-        launch_closest_points_multi(run.cfg, run.bvh, ClosestMultiArgs{a, k, at(counts, first), (flags & CAP_MULTI_CONTINUE) ? 1u : 0u}, f, c->bvh_info.max_depth);
-        return run.traced("k_closest_points_multi", first);
-    });
-}
-
-// cap_closest_instances (point_query.hip k_closest_inst): closest_points' options over trace_instances' state and pools
-int closest_instances(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, CapClosest* out, uint32_t* inst, const CapTraceOptions* options)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a point", what, options->ray_flags);
-    QueryFilter flt;
-    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
-    if (const int rc = query_state(c, what)) return rc;
-    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
-    if (n == 0) return CAP_OK;
-    if (!points || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, sizeof(CapClosest), 16),
-                                              range("instances", inst, sizeof(uint32_t), 4)}))
-        return rc;
-    QueryRun run;
-    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
-    use_instance_pools(run);
-    return for_each_chunk(run, points, n, [&](const QueryArgs& q, uint64_t first) {
-        const ClosestInstArgs a{ClosestArgs{q.rays, q.n, reinterpret_cast<float4*>(out + first), 0.f}, at(inst, first), c->inst_desc.p, c->inst_near.p,
-                                c->inst_misc.p + 7};
-        launch_closest_instances(run.cfg, run.bvh, a, run.tl, flt.f, run.depth);
-        return run.traced("k_closest_inst", first);
-    });
-}
-
-// cap_closest_instances_multi (point_query.hip k_closest_inst_multi): a point's first k candidate pairs in (dist2, instance, triangle)
-// order and / or the number of its pairs -- closest_points_multi's rules with the instance page as a fourth array, over
-// closest_instances' state and pools.  k = 1 without counts or cursor IS cap_closest_instances and takes its kernel.
-int closest_instances_multi(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, uint32_t k, CapClosest* out, uint32_t* inst,
-                            uint32_t* counts, uint32_t flags, const CapTraceOptions* options)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a point", what, options->ray_flags);
-    QueryFilter flt;
-    if (const int rc = multi_rules(c, what, k, flags, options, "output and instances", out || inst, counts, flt)) return rc;
-    if (const int rc = query_state(c, what)) return rc;
-    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
-    if (n == 0) return CAP_OK;
-    if (!points || (k && (!out || !inst))) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer (k = %u needs output and instances)", what, k);
-    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("output", out, (uint64_t)k * sizeof(CapClosest), 16),
-                                              range("instances", inst, (uint64_t)k * sizeof(uint32_t), 4), range("counts", counts, sizeof(uint32_t), 4)}))
-        return rc;
-    QueryRun run;
-    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
-    use_instance_pools(run);
-    const bool single = k == 1 && !counts && !(flags & CAP_MULTI_CONTINUE);
-    return for_each_chunk(run, points, n, [&](const QueryArgs& q, uint64_t first) {
-        const ClosestInstArgs a{ClosestArgs{q.rays, q.n, reinterpret_cast<float4*>(at(out, first * k)), 0.f}, at(inst, first * k), c->inst_desc.p,
-                                c->inst_near.p, c->inst_misc.p + 7};
+        const ClosestInstArgs ia{a, at(q.inst, first * q.k), c->inst_desc.p, c->inst_near.p, c->inst_misc.p + 7};
         if (single)
         {
-            launch_closest_instances(run.cfg, run.bvh, a, run.tl, flt.f, run.depth);
+            launch_closest_instances(run.cfg, run.bvh, ia, run.tl, flt.f, run.depth);
             return run.traced("k_closest_inst", first);
         }
-        launch_closest_instances_multi(run.cfg, run.bvh, ClosestInstMultiArgs{a, k, at(counts, first), (flags & CAP_MULTI_CONTINUE) ? 1u : 0u}, run.tl, flt.f,
-                                       run.depth);
+        launch_closest_instances_multi(run.cfg, run.bvh, ClosestInstMultiArgs{ia, q.k, counts, resume}, run.tl, flt.f, run.depth);
         return run.traced("k_closest_inst_multi", first);
     });
 }
@@ -469,30 +420,31 @@ int cap_trace_instances_multi(CapContext* c, const CapRayDesc* device_rays, uint
 
 int cap_closest_points(CapContext* c, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, const CapTraceOptions* options)
 {
-    return closest_points(c, "cap_closest_points", device_points, n, device_out, options);
+    return closest_query(c, "cap_closest_points", device_points, n, device_out, PointCall{}, options);
 }
 
 int cap_signed_distance(CapContext* c, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, float* device_signed,
                         const CapTraceOptions* options)
 {
-    return signed_distance(c, "cap_signed_distance", device_points, n, device_out, device_signed, options);
+    return closest_query(c, "cap_signed_distance", device_points, n, device_out, with_sign(device_signed), options);
 }
 
 int cap_closest_points_multi(CapContext* c, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out, uint32_t* device_counts,
                              uint32_t multi_flags, const CapTraceOptions* options)
 {
-    return closest_points_multi(c, "cap_closest_points_multi", device_points, n, k, device_out, device_counts, multi_flags, options);
+    return closest_query(c, "cap_closest_points_multi", device_points, n, device_out, paged(PointCall{}, k, device_counts, multi_flags), options);
 }
 
 int cap_closest_instances(CapContext* c, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, uint32_t* device_instances,
                           const CapTraceOptions* options)
 {
-    return closest_instances(c, "cap_closest_instances", device_points, n, device_out, device_instances, options);
+    return closest_query(c, "cap_closest_instances", device_points, n, device_out, over_instances(device_instances), options);
 }
 
 int cap_closest_instances_multi(CapContext* c, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out,
                                 uint32_t* device_instances, uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options)
 {
-    return closest_instances_multi(c, "cap_closest_instances_multi", device_points, n, k, device_out, device_instances, device_counts, multi_flags, options);
+    return closest_query(c, "cap_closest_instances_multi", device_points, n, device_out, paged(over_instances(device_instances), k, device_counts, multi_flags),
+                         options);
 }
 }  // extern "C"

@@ -22,6 +22,8 @@
 //
 // The instanced forms (cap_closest_instances, k_closest_inst; cap_closest_instances_multi, k_closest_inst_multi) are at the end of the
 // file: nearest, and the k nearest, in world space over the instance table.
+#include <type_traits>
+
 #include "cap_hit_list.h"
 #include "cap_kernels.h"
 #include "cap_near.h"  // box_dist2, and the bound of the instanced form
@@ -130,6 +132,68 @@ __device__ __forceinline__ bool point_ok(const float4 p)
 // Workgroups per CU: the stack is 8 B x STACK x kBlock of the CU's 160 KB of LDS
 constexpr int closest_blocks(int STACK) { return STACK <= 16 ? 5 : STACK <= 24 ? 3 : STACK <= 32 ? 2 : 1; }
 
+// ---- the steps every walk below is made of ----
+// An inner node of a scene or object tree, measured from (px, py, pz): one fetch yields both child boxes; the nearer child that survives
+// the prune is entered and the other one pushed with its box distance.  false: neither survives, the caller pops.  near_skip (cap_near.h)
+// is the strict > of the pruning argument above.  A walk pushes at most one entry per level it descends and STACK is at least the tree's
+// depth (with_stack_class below).
+template <int STACK>
+__device__ __forceinline__ bool closest_node_step(const BvhDev& bvh, float px, float py, float pz, float bound2, uint2* stack, int& node, int& sp)
+{
+    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2], q3 = bvh.nodes[4 * node + 3];
+    const float  b0 = box_dist2(px, py, pz, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
+    const float  b1 = box_dist2(px, py, pz, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
+    const int    c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+    const bool   k0 = !near_skip(b0, bound2), k1 = !near_skip(b1, bound2);
+    if (k0 && k1)
+    {
+        const bool swap = b1 < b0;
+        if (sp < STACK) stack[(sp++) * kBlock] = make_uint2(f2u(swap ? b0 : b1), (uint32_t)(swap ? c0 : c1));
+        node = swap ? c1 : c0;
+        return true;
+    }
+    if (k0 || k1)
+    {
+        node = k0 ? c0 : c1;
+        return true;
+    }
+    return false;
+}
+
+// The next stack entry that still passes the bound as it stands now, one LDS read per entry; false: the stack is empty
+__device__ __forceinline__ bool closest_pop(uint2* stack, int& sp, float bound2, int& node)
+{
+    while (sp > 0)
+    {
+        const uint2 e = stack[(--sp) * kBlock];
+        if (!near_skip(u2f(e.x), bound2))
+        {
+            node = (int)e.y;
+            return true;
+        }
+    }
+    return false;
+}
+
+// A record slot without a triangle: dist2 = r2, the point's squared radius (0 for a point that was not traversed)
+__device__ __forceinline__ void write_miss(float4* slot, float r2)
+{
+    slot[0] = make_float4(0.f, 0.f, 0.f, r2);
+    slot[1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
+}
+__device__ __forceinline__ void write_record(float4* slot, const ClosestPoint& c, uint32_t gid)
+{
+    slot[0] = make_float4(c.x, c.y, c.z, c.d2);
+    slot[1] = make_float4(c.u, c.v, u2f(gid), u2f(c.feature));
+}
+// Only (dist2, ids) live in registers during a walk: the record of a triangle that is written out is computed again from the records in
+// id order (byte copies of the tree's, see multi_write in query.hip) -- the same operations on the same words, the same dist2 bits.
+__device__ __forceinline__ ClosestPoint scene_record(const BvhDev& bvh, uint32_t gid, const float4 p)
+{
+    const float4* rec = bvh.tris_by_id + 4 * (size_t)gid;
+    return closest_record(rec[0], rec[1], rec[2], p.x, p.y, p.z);
+}
+
 // FILTER: the mesh-mask table (RayFilter::tri_mask by global id), read before the cascade: a rejected triangle is as if it were not in
 // the scene.  One body, FILTER a template flag of the kernel itself: there is no older plain kernel whose schedule a shared function
 // could disturb, and the plain instantiation carries no trace of the filter (tools/kernel_regs.sh: the same registers).
@@ -145,8 +209,7 @@ __global__ __launch_bounds__(kBlock, closest_blocks(STACK)) void k_closest_point
         const float4 p = a.points[i];
         if (!point_ok(p))
         {
-            a.out[2 * (size_t)i]     = make_float4(0.f, 0.f, 0.f, 0.f);
-            a.out[2 * (size_t)i + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
+            write_miss(a.out + 2 * (size_t)i, 0.f);
             if constexpr (SIGNED) s.signed_out[i] = __builtin_inff();
             continue;
         }
@@ -158,24 +221,7 @@ __global__ __launch_bounds__(kBlock, closest_blocks(STACK)) void k_closest_point
         {
             if (node >= 0)
             {
-                const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2],
-                             q3 = bvh.nodes[4 * node + 3];
-                const float b0 = box_dist2(p.x, p.y, p.z, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
-                const float b1 = box_dist2(p.x, p.y, p.z, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
-                const int   c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
-                const bool  k0 = !(b0 > bound2), k1 = !(b1 > bound2);
-                if (k0 && k1)
-                {
-                    const bool swap = b1 < b0;
-                    if (sp < STACK) stack[(sp++) * kBlock] = make_uint2(f2u(swap ? b0 : b1), (uint32_t)(swap ? c0 : c1));
-                    node = swap ? c1 : c0;
-                    continue;
-                }
-                if (k0 || k1)
-                {
-                    node = k0 ? c0 : c1;
-                    continue;
-                }
+                if (closest_node_step<STACK>(bvh, p.x, p.y, p.z, bound2, stack, node, sp)) continue;
             }
             else
             {
@@ -194,30 +240,16 @@ __global__ __launch_bounds__(kBlock, closest_blocks(STACK)) void k_closest_point
                     }
                 }
             }
-            bool more = false;
-            while (sp > 0)
-            {
-                const uint2 e = stack[(--sp) * kBlock];
-                if (!(u2f(e.x) > bound2))
-                {
-                    node = (int)e.y, more = true;
-                    break;
-                }
-            }
-            if (!more) break;
+            if (!closest_pop(stack, sp, bound2, node)) break;
         }
         if (best_gid == kInvalidId)
         {
-            a.out[2 * (size_t)i]     = make_float4(0.f, 0.f, 0.f, r2);
-            a.out[2 * (size_t)i + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
+            write_miss(a.out + 2 * (size_t)i, r2);
             if constexpr (SIGNED) s.signed_out[i] = __builtin_inff();
             continue;
         }
-        // the winner's record from the records in id order (byte copies of the tree's, see multi_write in query.hip)
-        const float4*      rec = bvh.tris_by_id + 4 * (size_t)best_gid;
-        const ClosestPoint c   = closest_record(rec[0], rec[1], rec[2], p.x, p.y, p.z);
-        a.out[2 * (size_t)i]     = make_float4(c.x, c.y, c.z, c.d2);
-        a.out[2 * (size_t)i + 1] = make_float4(c.u, c.v, u2f(best_gid), u2f(c.feature));
+        const ClosestPoint c = scene_record(bvh, best_gid, p);
+        write_record(a.out + 2 * (size_t)i, c, best_gid);
         if constexpr (SIGNED)
         {
             // d == 0 (dist2 == 0 among them) and a NaN take the positive sign
@@ -227,15 +259,6 @@ __global__ __launch_bounds__(kBlock, closest_blocks(STACK)) void k_closest_point
             s.signed_out[i]         = d < 0.f ? -dist : dist;
         }
     }
-}
-
-template <int STACK, bool FILTER, bool SIGNED = false>
-void launch_closest_s(const LaunchCfg& cfg, const BvhDev& b, const ClosestArgs& a, const RayFilter& f, const SignedArgs& s = SignedArgs{})
-{
-    uint32_t want = (a.n + kBlock - 1) / kBlock;
-    if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_closest_points<STACK, FILTER, SIGNED>), dim3(resident_grid<k_closest_points<STACK, FILTER, SIGNED>>(cfg, want)), dim3(kBlock),
-                       0, cfg.stream, b, a, f, s);
 }
 
 // ---- k nearest and in-radius (cap_closest_points_multi) ----
@@ -250,9 +273,8 @@ void launch_closest_s(const LaunchCfg& cfg, const BvhDev& b, const ClosestArgs& 
 // are counted and offered.  The cursor prunes nothing: a subtree wholly below it is still walked (skipping those whose farthest corner
 // lies below dist2_c is left out).  Unlike a ray's hit (t < tmax) a candidate may lie AT the limit, and a triangle beyond it passes a
 // miss record's cursor (r2, ~0) only by failing dist2 <= r2: COUNT tests that itself, the list's admits() implies it.
-// Write-out: only (dist2, gid) live in the list; each listed triangle's record is computed again from tris_by_id as k_closest_points
-// does for its winner -- the same operations on the same words, the same dist2 bits.  The slot is picked by a chain of K selects
-// inside a loop over the k slots rather than K unrolled cascades.
+// Write-out: scene_record per listed triangle.  The slot is picked by a chain of K selects inside a loop over the k slots rather than K
+// unrolled cascades.
 struct ClosestCursor
 {
     float    d2;
@@ -261,7 +283,7 @@ struct ClosestCursor
 
 // Workgroups per CU: closest_blocks(STACK) is what the LDS stack allows; the list's 2 K registers (and the cursor and count) take it
 // down to the most that leave every instantiation without scratch (tools/kernel_regs.sh; the table is in DESIGN.md): up to K = 8 the
-// list fits five (96 VGPRs; 77 used), K = 16 runs four (128; 110 used) -- five spill 48 to 52 bytes.  Only STACK = 16 has LDS for that many.
+// list fits five (96 VGPRs; 77 used), K = 16 runs four (128; 111 used) -- five spill 48 to 52 bytes.  Only STACK = 16 has LDS for that many.
 constexpr int closest_multi_blocks(int STACK, int K)
 {
     const int by_regs = K <= 8 ? 5 : 4;
@@ -293,24 +315,7 @@ __global__ __launch_bounds__(kBlock, closest_multi_blocks(STACK, K)) void k_clos
             {
                 if (node >= 0)
                 {
-                    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2],
-                                 q3 = bvh.nodes[4 * node + 3];
-                    const float b0 = box_dist2(p.x, p.y, p.z, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
-                    const float b1 = box_dist2(p.x, p.y, p.z, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
-                    const int   c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
-                    const bool  k0 = !(b0 > bound2), k1 = !(b1 > bound2);
-                    if (k0 && k1)
-                    {
-                        const bool swap = b1 < b0;
-                        if (sp < STACK) stack[(sp++) * kBlock] = make_uint2(f2u(swap ? b0 : b1), (uint32_t)(swap ? c0 : c1));
-                        node = swap ? c1 : c0;
-                        continue;
-                    }
-                    if (k0 || k1)
-                    {
-                        node = k0 ? c0 : c1;
-                        continue;
-                    }
+                    if (closest_node_step<STACK>(bvh, p.x, p.y, p.z, bound2, stack, node, sp)) continue;
                 }
                 else
                 {
@@ -335,17 +340,7 @@ __global__ __launch_bounds__(kBlock, closest_multi_blocks(STACK, K)) void k_clos
                         }
                     }
                 }
-                bool more = false;
-                while (sp > 0)
-                {
-                    const uint2 e = stack[(--sp) * kBlock];
-                    if (!(u2f(e.x) > bound2))
-                    {
-                        node = (int)e.y, more = true;
-                        break;
-                    }
-                }
-                if (!more) break;
+                if (!closest_pop(stack, sp, bound2, node)) break;
             }
         }
         // (a query that was not traversed: the list as init left it, k miss records with dist2 = r2 = 0, and count 0)
@@ -357,46 +352,10 @@ __global__ __launch_bounds__(kBlock, closest_multi_blocks(STACK, K)) void k_clos
             for (int j = 0; j < K; ++j)
                 if (j - skip == (int)s) gid = L.g[j];
             if (gid == kInvalidId)
-            {
-                page[2 * s]     = make_float4(0.f, 0.f, 0.f, r2);
-                page[2 * s + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
-                continue;
-            }
-            const float4*      rec = bvh.tris_by_id + 4 * (size_t)gid;
-            const ClosestPoint c   = closest_record(rec[0], rec[1], rec[2], p.x, p.y, p.z);
-            page[2 * s]     = make_float4(c.x, c.y, c.z, c.d2);
-            page[2 * s + 1] = make_float4(c.u, c.v, u2f(gid), u2f(c.feature));
+                write_miss(page + 2 * s, r2);
+            else
+                write_record(page + 2 * s, scene_record(bvh, gid, p), gid);
         }
-    }
-}
-
-template <int STACK, int K, bool COUNT, bool FILTER>
-void launch_closest_multi_k(const LaunchCfg& cfg, const BvhDev& b, const ClosestMultiArgs& m, const RayFilter& f)
-{
-    uint32_t want = (m.a.n + kBlock - 1) / kBlock;
-    if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_closest_points_multi<STACK, K, COUNT, FILTER>), dim3(resident_grid<k_closest_points_multi<STACK, K, COUNT, FILTER>>(cfg, want)),
-                       dim3(kBlock), 0, cfg.stream, b, m, f);
-}
-
-template <int STACK, int K>
-void launch_closest_multi_s(const LaunchCfg& cfg, const BvhDev& b, const ClosestMultiArgs& m, bool filter, const RayFilter& f)
-{
-    if (m.counts)
-        filter ? launch_closest_multi_k<STACK, K, true, true>(cfg, b, m, f) : launch_closest_multi_k<STACK, K, true, false>(cfg, b, m, f);
-    else
-        filter ? launch_closest_multi_k<STACK, K, false, true>(cfg, b, m, f) : launch_closest_multi_k<STACK, K, false, false>(cfg, b, m, f);
-}
-
-template <int STACK>
-void launch_closest_multi(const LaunchCfg& cfg, const BvhDev& b, const ClosestMultiArgs& m, bool filter, const RayFilter& f)
-{
-    switch (multi_bucket(m.k))
-    {
-    case 1: launch_closest_multi_s<STACK, 1>(cfg, b, m, filter, f); break;
-    case 4: launch_closest_multi_s<STACK, 4>(cfg, b, m, filter, f); break;
-    case 8: launch_closest_multi_s<STACK, 8>(cfg, b, m, filter, f); break;
-    default: launch_closest_multi_s<STACK, 16>(cfg, b, m, filter, f); break;
     }
 }
 
@@ -406,13 +365,11 @@ void launch_closest_multi(const LaunchCfg& cfg, const BvhDev& b, const ClosestMu
 // of the instance's transform M as the caller gave it (a.descs), no fused multiply-add: include/capsaicin_hip.h has the contract.
 // One loop with three kinds of step, as k_query_inst (instance.hip), so that the lanes of a wave that are at the top level advance
 // while others are inside an instance:
-//   * a top-level node: the implicit tree without a stack, `pending` bits per level; the two children ordered by the squared distance
-//     from p to their stored world boxes and pruned against bound2_top.  The two instances under a level-1 node wait in
-//     (todo0, todo1), the nearer first, each tested again against the bound as it stands when its turn comes;
-//   * entering an instance: mask, M, (g, Xw), the root, and p' = W p + W_t, which only the pruning sees;
-//   * a bottom-level node or leaf: k_closest_points' walk of the object's tree with its LDS stack of (box distance, child), the boxes
-//     measured from p' and pruned against bound2, the world bound mapped into object space through g <= sigma_min(M)
-//     (cap_near.h near_bound2_object).  A leaf builds the world record and runs the cascade.
+//   * a top-level node (top_step);
+//   * entering an instance (enter_instance);
+//   * a bottom-level node or leaf: the walk of the object's tree with its LDS stack of (box distance, child), the boxes measured from
+//     p' and pruned against bound2, the world bound mapped into object space through g <= sigma_min(M) (cap_near.h
+//     near_bound2_object).  A leaf builds the world record and runs the cascade.
 // Both bounds are computed again only when `best` improves; every test is a strict >, so an instance, subtree or triangle at exactly
 // the best distance is still opened and the lower (instance, triangle) wins whatever the visiting order.  DESIGN.md "Closest-point
 // queries over instances" has the argument that no skipped box holds a candidate.
@@ -429,6 +386,98 @@ __device__ __forceinline__ WorldRecord world_record(const float4 m0, const float
                        dot_c(m1.x, m1.y, m1.z, t1.z, t1.w, t2.x));
     w.t2 = make_float4(dot_c(m2.x, m2.y, m2.z, t1.z, t1.w, t2.x), 0.f, 0.f, 0.f);
     return w;
+}
+// scene_record for a listed pair: the world record again from the records in id order and the instance's transform
+__device__ __forceinline__ ClosestPoint instance_record(const BvhDev& bvh, const float4* descs, uint32_t inst, uint32_t gid, const float4 p)
+{
+    const float4*     rec = bvh.tris_by_id + 4 * (size_t)gid;
+    const float4*     md  = descs + 4 * (size_t)inst;
+    const WorldRecord w   = world_record(md[0], md[1], md[2], rec[0], rec[1], rec[2]);
+    return closest_record(w.t0, w.t1, w.t2, p.x, p.y, p.z);
+}
+
+// The top level: the implicit tree without a stack.  This state crosses top_step BY VALUE, in and out: handed over as eight reference
+// parameters it cost every instanced instantiation 20 bytes of scratch (DESIGN.md "Closest-point queries", "One copy of each step").
+struct TopWalk
+{
+    uint32_t level, idx;      // the node whose two children (level - 1, 2 idx + {0, 1}) are tested next
+    uint32_t pending;         // bit l: the other child of the node entered at level l is still owed
+    bool     done;            // nothing is owed any more
+    uint32_t todo0, todo1;    // the two instances under a level-1 node wait here, the nearer first (~0: none) ...
+    float    todo0_d, todo1_d;  // ... with their boxes' distances: each is tested again against the bound as it stands when its turn comes
+};
+__device__ __forceinline__ TopWalk top_start(const TlasDev& tl) { return TopWalk{tl.top + 1u, 0u, 0u, false, kInvalidId, kInvalidId, 0.f, 0.f}; }
+
+// One top-level node: the two children ordered by the squared distance from p to their stored world boxes and pruned against
+// bound2_top; then down into the nearer one, or their instances into the queue, or up to the nearest level that owes a child.
+__device__ __forceinline__ TopWalk top_step(const TlasDev& tl, const uint32_t* lds_off, float px, float py, float pz, float bound2_top, TopWalk t)
+{
+    const float4* c = tl.tlas + 2 * (size_t)(lds_off[t.level - 1u] + 2u * t.idx);
+    const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
+    const float   d0 = box_dist2(px, py, pz, lo0.x, lo0.y, lo0.z, hi0.x, hi0.y, hi0.z);
+    const float   d1 = box_dist2(px, py, pz, lo1.x, lo1.y, lo1.z, hi1.x, hi1.y, hi1.z);
+    // (a record with k < 0 holds nothing: an inert instance or the padding of a level)
+    const bool h0 = lo0.w >= 0.0f && !near_skip(d0, bound2_top), h1 = lo1.w >= 0.0f && !near_skip(d1, bound2_top);
+    const bool far_first = h0 && h1 && d1 < d0;
+    if (t.level > 1u)
+    {
+        if (h0 || h1)
+        {
+            if (h0 && h1) t.pending |= 1u << (t.level - 1u);
+            t.idx   = 2u * t.idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
+            t.level = t.level - 1u;
+            return t;
+        }
+    }
+    else if (h0 || h1)
+    {
+        // the children are instances: the nearer box first
+        const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
+        if (h0 && h1)
+            t.todo0 = far_first ? i1 : i0, t.todo0_d = far_first ? d1 : d0, t.todo1 = far_first ? i0 : i1, t.todo1_d = far_first ? d0 : d1;
+        else
+            t.todo0 = h0 ? i0 : i1, t.todo0_d = h0 ? d0 : d1;
+    }
+    const uint32_t owed = t.pending >> t.level;
+    if (owed == 0u)
+    {
+        t.done = true;
+        return t;
+    }
+    const uint32_t up = (uint32_t)__builtin_ctz(owed);
+    t.idx     = (t.idx >> up) ^ 1u;
+    t.level   = t.level + up;
+    t.pending = t.pending & ~(1u << t.level);
+    return t;
+}
+// the queue without its head
+__device__ __forceinline__ TopWalk top_pop(TopWalk t)
+{
+    t.todo0 = t.todo1, t.todo0_d = t.todo1_d, t.todo1 = kInvalidId;
+    return t;
+}
+
+// Entering an instance: its mask joined with the call's (the mesh byte joins it per triangle), M for the leaves' world records,
+// p' = W p + W_t, which only the pruning sees, (g, slack) of cap_near.h and the root of the object's tree.  The caller maps its bound into
+// object space: near_bound2_object(sqrt of its best or k-th dist2, slack, g).  false: the mask excludes the instance (0 for an inert one);
+// the mask word is loaded first and the rest only for an instance it lets in.  The results go straight into the kernel's own variables:
+// returned by value, or filled into one struct of the kernel's, they made the compiler allocate k_closest_inst_multi anew (DESIGN.md "One
+// copy of each step").
+__device__ __forceinline__ bool enter_instance(const TlasDev& tl, const ClosestInstArgs& ia, uint32_t mask, uint32_t inst, const float4 p, float pmax,
+                                               uint32_t& imask, float4& m0, float4& m1, float4& m2, float& ox, float& oy, float& oz, float& g, float& slack,
+                                               int& root)
+{
+    const float4 w3 = tl.rec[4 * (size_t)inst + 3];
+    imask           = f2u(w3.x) & mask;
+    if (imask == 0u) return false;
+    const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
+    const float  w[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
+    near_to_object(w, p.x, p.y, p.z, ox, oy, oz);
+    m0 = ia.descs[4 * (size_t)inst], m1 = ia.descs[4 * (size_t)inst + 1], m2 = ia.descs[4 * (size_t)inst + 2];
+    const float2 nr = ia.near[inst];
+    g = nr.x, slack = near_slack(pmax, nr.y);
+    root = (int)f2u(w3.y);
+    return true;
 }
 
 // Workgroups per CU: the stack's LDS (and the 104 bytes of level offsets, which take the fifth workgroup of STACK = 16 away)
@@ -450,8 +499,7 @@ __global__ __launch_bounds__(kBlock, closest_inst_blocks(STACK)) void k_closest_
         const float4 p = a.points[j];
         if (!point_ok(p))
         {
-            a.out[2 * (size_t)j]     = make_float4(0.f, 0.f, 0.f, 0.f);
-            a.out[2 * (size_t)j + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
+            write_miss(a.out + 2 * (size_t)j, 0.f);
             if (ia.inst_out) ia.inst_out[j] = kInvalidId;
             continue;
         }
@@ -461,12 +509,8 @@ __global__ __launch_bounds__(kBlock, closest_inst_blocks(STACK)) void k_closest_
         uint32_t    best_gid = kInvalidId, best_inst = kInvalidId;
         const float slack_top  = near_slack(pmax, xw_all);
         float       bound2_top = near_bound2_world(sqrt_best, slack_top);
-        // top level: the node whose two children (level - 1, 2 idx + {0, 1}) are tested next
-        uint32_t level = tl.top + 1u, idx = 0u, pending = 0u;
-        bool     top_done = false;
-        uint32_t todo0 = kInvalidId, todo1 = kInvalidId;
-        float    todo0_d = 0.f, todo1_d = 0.f;
-        // bottom level
+        TopWalk     t          = top_start(tl);
+        // bottom level: the instance being walked
         bool     in_blas = false;
         float4   m0 = make_float4(0.f, 0.f, 0.f, 0.f), m1 = m0, m2 = m0;
         float    ox = 0.f, oy = 0.f, oz = 0.f, g = 1.f, slack = 0.f, bound2 = 0.f;
@@ -479,24 +523,7 @@ __global__ __launch_bounds__(kBlock, closest_inst_blocks(STACK)) void k_closest_
             {
                 if (node >= 0)
                 {
-                    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2],
-                                 q3 = bvh.nodes[4 * node + 3];
-                    const float b0 = box_dist2(ox, oy, oz, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
-                    const float b1 = box_dist2(ox, oy, oz, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
-                    const int   c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
-                    const bool  k0 = !near_skip(b0, bound2), k1 = !near_skip(b1, bound2);
-                    if (k0 && k1)
-                    {
-                        const bool swap = b1 < b0;
-                        if (sp < STACK) stack[(sp++) * kBlock] = make_uint2(f2u(swap ? b0 : b1), (uint32_t)(swap ? c0 : c1));
-                        node = swap ? c1 : c0;
-                        continue;
-                    }
-                    if (k0 || k1)
-                    {
-                        node = k0 ? c0 : c1;
-                        continue;
-                    }
+                    if (closest_node_step<STACK>(bvh, ox, oy, oz, bound2, stack, node, sp)) continue;
                 }
                 else
                 {
@@ -520,108 +547,39 @@ __global__ __launch_bounds__(kBlock, closest_inst_blocks(STACK)) void k_closest_
                         }
                     }
                 }
-                in_blas = false;
-                while (sp > 0)
+                in_blas = closest_pop(stack, sp, bound2, node);
+                continue;
+            }
+            if (t.todo0 != kInvalidId)
+            {
+                // the head of the queue, if its box still passes against the bound as it is now
+                inst             = t.todo0;
+                const bool still = !near_skip(t.todo0_d, bound2_top);
+                t                = top_pop(t);
+                if (still && enter_instance(tl, ia, f.mask, inst, p, pmax, imask, m0, m1, m2, ox, oy, oz, g, slack, node))
                 {
-                    const uint2 e = stack[(--sp) * kBlock];
-                    if (!near_skip(u2f(e.x), bound2))
-                    {
-                        node = (int)e.y, in_blas = true;
-                        break;
-                    }
+                    bound2  = near_bound2_object(sqrt_best, slack, g);
+                    sp      = 0;
+                    in_blas = true;
                 }
                 continue;
             }
-            if (todo0 != kInvalidId)
-            {
-                // enter an instance, if its box still passes against the bound as it is now
-                inst             = todo0;
-                const bool still = !near_skip(todo0_d, bound2_top);
-                todo0 = todo1, todo0_d = todo1_d, todo1 = kInvalidId;
-                if (!still) continue;
-                const float4 w3 = tl.rec[4 * (size_t)inst + 3];
-                imask           = f2u(w3.x) & f.mask;  // desc.mask & inclusion (0 for an inert instance): the mesh byte joins it per triangle
-                if (imask == 0u) continue;
-                const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
-                const float  w[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
-                near_to_object(w, p.x, p.y, p.z, ox, oy, oz);
-                m0 = ia.descs[4 * (size_t)inst], m1 = ia.descs[4 * (size_t)inst + 1], m2 = ia.descs[4 * (size_t)inst + 2];
-                const float2 nr = ia.near[inst];
-                g = nr.x, slack = near_slack(pmax, nr.y);
-                bound2  = near_bound2_object(sqrt_best, slack, g);
-                node    = (int)f2u(w3.y), sp = 0;
-                in_blas = true;
-                continue;
-            }
-            if (top_done) break;
-            const float4* c = tl.tlas + 2 * (size_t)(lds_off[level - 1u] + 2u * idx);
-            const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
-            const float   d0 = box_dist2(p.x, p.y, p.z, lo0.x, lo0.y, lo0.z, hi0.x, hi0.y, hi0.z);
-            const float   d1 = box_dist2(p.x, p.y, p.z, lo1.x, lo1.y, lo1.z, hi1.x, hi1.y, hi1.z);
-            // (a record with k < 0 holds nothing: an inert instance or the padding of a level)
-            const bool h0 = lo0.w >= 0.0f && !near_skip(d0, bound2_top), h1 = lo1.w >= 0.0f && !near_skip(d1, bound2_top);
-            const bool far_first = h0 && h1 && d1 < d0;
-            if (level > 1u)
-            {
-                if (h0 || h1)
-                {
-                    if (h0 && h1) pending |= 1u << (level - 1u);
-                    idx   = 2u * idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
-                    level = level - 1u;
-                    continue;
-                }
-            }
-            else if (h0 || h1)
-            {
-                // the children are instances: the nearer box first
-                const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
-                if (h0 && h1)
-                    todo0 = far_first ? i1 : i0, todo0_d = far_first ? d1 : d0, todo1 = far_first ? i0 : i1, todo1_d = far_first ? d0 : d1;
-                else
-                    todo0 = h0 ? i0 : i1, todo0_d = h0 ? d0 : d1;
-            }
-            const uint32_t owed = pending >> level;
-            if (owed == 0u)
-            {
-                top_done = true;
-                continue;
-            }
-            const uint32_t up = (uint32_t)__builtin_ctz(owed);
-            idx     = (idx >> up) ^ 1u;
-            level   = level + up;
-            pending = pending & ~(1u << level);
+            if (t.done) break;
+            t = top_step(tl, lds_off, p.x, p.y, p.z, bound2_top, t);
         }
         if (ia.inst_out) ia.inst_out[j] = best_inst;
         if (best_gid == kInvalidId)
-        {
-            a.out[2 * (size_t)j]     = make_float4(0.f, 0.f, 0.f, r2);
-            a.out[2 * (size_t)j + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
-            continue;
-        }
-        // the winner's record again from the records in id order and its instance's transform: the same operations, the same bits
-        const float4*      rec = bvh.tris_by_id + 4 * (size_t)best_gid;
-        const float4*      md  = ia.descs + 4 * (size_t)best_inst;
-        const WorldRecord  w   = world_record(md[0], md[1], md[2], rec[0], rec[1], rec[2]);
-        const ClosestPoint c   = closest_record(w.t0, w.t1, w.t2, p.x, p.y, p.z);
-        a.out[2 * (size_t)j]     = make_float4(c.x, c.y, c.z, c.d2);
-        a.out[2 * (size_t)j + 1] = make_float4(c.u, c.v, u2f(best_gid), u2f(c.feature));
+            write_miss(a.out + 2 * (size_t)j, r2);
+        else
+            write_record(a.out + 2 * (size_t)j, instance_record(bvh, ia.descs, best_inst, best_gid, p), best_gid);
     }
 }
 
-template <int STACK, bool FILTER>
-void launch_closest_inst_s(const LaunchCfg& cfg, const BvhDev& b, const ClosestInstArgs& a, const TlasDev& tl, const RayFilter& f)
-{
-    uint32_t want = (a.a.n + kBlock - 1) / kBlock;
-    if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_closest_inst<STACK, FILTER>), dim3(resident_grid<k_closest_inst<STACK, FILTER>>(cfg, want)), dim3(kBlock), 0, cfg.stream, b, a,
-                       tl, f);
-}
-
 // ---- k nearest and in-radius over the instance table (cap_closest_instances_multi) ----
-// A point's first k candidate pairs in (dist2, instance, triangle) order, the number of its pairs, or both: k_closest_inst's loop -- the
-// same three kinds of step, the (todo0, todo1) queue, the `still` re-check on entry -- with InstHitList<K> of cap_hit_list.h in the
-// place of (best, best_inst, best_gid), as k_closest_points_multi stands to k_closest_points.  The list moved to that header rather
-// than being copied here: k_query_inst_multi's code is unchanged by it (tools/kernel_regs.sh: the same rows).
+// A point's first k candidate pairs in (dist2, instance, triangle) order, the number of its pairs, or both: k_closest_inst's loop with
+// InstHitList<K> of cap_hit_list.h in the place of (best, best_inst, best_gid), as k_closest_points_multi stands to k_closest_points.
+// The list moved to that header rather than being copied here: k_query_inst_multi's code is unchanged by it (tools/kernel_regs.sh: the
+// same rows).
 // Bounds: bound2 and bound2_top derive from slot K - 1's dist2 -- r2 until the list holds k pairs, then the k-th -- through one sqrtf,
 // computed again only when that slot's value changes (and bound2 on entering an instance, from the value as it stands); with COUNT
 // every pair within the radius has to be seen and both stay at r2's.  Every test is near_skip's strict >: an instance, subtree or
@@ -630,15 +588,14 @@ void launch_closest_inst_s(const LaunchCfg& cfg, const BvhDev& b, const ClosestI
 // Offer: above the cursor (dist2_c, i_c, g_c) -- words 3 and 6 of slot k - 1 of the record page and slot k - 1 of the instance page,
 // (-inf, 0, 0) otherwise --; with COUNT `dist2 <= r2` itself and ++count (a pair may lie AT the limit, and one beyond it passes a miss
 // record's cursor (r2, ~0, ~0)); then admits / insert.  The cursor prunes nothing.
-// Write-out: only (dist2, inst, gid) live in the list; each listed pair's record is computed again from tris_by_id and descs[inst] as
-// k_closest_inst does for its winner.  The slot is picked by a chain of K selects inside a loop over the k slots; the cursor is read
-// before anything is written; k = 0 dereferences neither page.
+// Write-out: instance_record per listed pair.  The slot is picked by a chain of K selects inside a loop over the k slots; the cursor is
+// read before anything is written; k = 0 dereferences neither page.
 // The mesh-mask table is a wave-uniform test of f.tri_mask per leaf, as in k_query_inst_multi, not a template flag: with the list in
 // registers the flag would double 32 instantiations for the two SGPR pairs it saves.
 
 // Workgroups per CU: closest_inst_blocks(STACK) is what the LDS allows; the list's 3 K registers (and cursor and count) take it down to
 // the most that leave every instantiation without scratch (tools/kernel_regs.sh; the table is in DESIGN.md): up to K = 4 the LDS's four
-// (128 VGPRs; 93 to 99 used at K = 1, 126 to 128 at K = 4), two (256; about 200 used) at K = 8 -- three (168) spill 104 to 120 bytes --
+// (128 VGPRs; 86 to 98 used at K = 1, 128 at K = 4 in the 16-entry class, which has not one to spare), two (256; about 200 used) at K = 8 -- three (168) spill 104 to 120 bytes --
 // and one (512; about 260 used) at K = 16 -- two spill 12 to 28 bytes.  The compiler keeps the list twice across insert()'s
 // compare-swaps, as in k_query_inst_multi, so a slot costs six registers rather than three.
 constexpr int closest_inst_multi_blocks(int STACK, int K)
@@ -676,12 +633,8 @@ __global__ __launch_bounds__(kBlock, closest_inst_multi_blocks(STACK, K)) void k
         float       sqrt_kth  = sqrtf(r2);
         const float slack_top = near_slack(pmax, xw_all);
         float       bound2_top = near_bound2_world(sqrt_kth, slack_top);
-        // top level: the node whose two children (level - 1, 2 idx + {0, 1}) are tested next
-        uint32_t level = tl.top + 1u, idx = 0u, pending = 0u;
-        bool     top_done = false;
-        uint32_t todo0 = kInvalidId, todo1 = kInvalidId;
-        float    todo0_d = 0.f, todo1_d = 0.f;
-        // bottom level
+        TopWalk     t          = top_start(tl);
+        // bottom level: the instance being walked
         bool     in_blas = false;
         float4   m0 = make_float4(0.f, 0.f, 0.f, 0.f), m1 = m0, m2 = m0;
         float    ox = 0.f, oy = 0.f, oz = 0.f, g = 1.f, slack = 0.f, bound2 = 0.f;
@@ -694,24 +647,7 @@ __global__ __launch_bounds__(kBlock, closest_inst_multi_blocks(STACK, K)) void k
             {
                 if (node >= 0)
                 {
-                    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2],
-                                 q3 = bvh.nodes[4 * node + 3];
-                    const float b0 = box_dist2(ox, oy, oz, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
-                    const float b1 = box_dist2(ox, oy, oz, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
-                    const int   c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
-                    const bool  k0 = !near_skip(b0, bound2), k1 = !near_skip(b1, bound2);
-                    if (k0 && k1)
-                    {
-                        const bool swap = b1 < b0;
-                        if (sp < STACK) stack[(sp++) * kBlock] = make_uint2(f2u(swap ? b0 : b1), (uint32_t)(swap ? c0 : c1));
-                        node = swap ? c1 : c0;
-                        continue;
-                    }
-                    if (k0 || k1)
-                    {
-                        node = k0 ? c0 : c1;
-                        continue;
-                    }
+                    if (closest_node_step<STACK>(bvh, ox, oy, oz, bound2, stack, node, sp)) continue;
                 }
                 else
                 {
@@ -740,76 +676,25 @@ __global__ __launch_bounds__(kBlock, closest_inst_multi_blocks(STACK, K)) void k
                         }
                     }
                 }
-                in_blas = false;
-                while (sp > 0)
+                in_blas = closest_pop(stack, sp, bound2, node);
+                continue;
+            }
+            if (t.todo0 != kInvalidId)
+            {
+                // the head of the queue, if its box still passes against the bound as it is now
+                inst             = t.todo0;
+                const bool still = !near_skip(t.todo0_d, bound2_top);
+                t                = top_pop(t);
+                if (still && enter_instance(tl, ia, f.mask, inst, p, pmax, imask, m0, m1, m2, ox, oy, oz, g, slack, node))
                 {
-                    const uint2 e = stack[(--sp) * kBlock];
-                    if (!near_skip(u2f(e.x), bound2))
-                    {
-                        node = (int)e.y, in_blas = true;
-                        break;
-                    }
+                    bound2  = near_bound2_object(sqrt_kth, slack, g);
+                    sp      = 0;
+                    in_blas = true;
                 }
                 continue;
             }
-            if (todo0 != kInvalidId)
-            {
-                // enter an instance, if its box still passes against the bound as it is now
-                inst             = todo0;
-                const bool still = !near_skip(todo0_d, bound2_top);
-                todo0 = todo1, todo0_d = todo1_d, todo1 = kInvalidId;
-                if (!still) continue;
-                const float4 w3 = tl.rec[4 * (size_t)inst + 3];
-                imask           = f2u(w3.x) & f.mask;  // desc.mask & inclusion (0 for an inert instance): the mesh byte joins it per triangle
-                if (imask == 0u) continue;
-                const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
-                const float  w[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
-                near_to_object(w, p.x, p.y, p.z, ox, oy, oz);
-                m0 = ia.descs[4 * (size_t)inst], m1 = ia.descs[4 * (size_t)inst + 1], m2 = ia.descs[4 * (size_t)inst + 2];
-                const float2 nr = ia.near[inst];
-                g = nr.x, slack = near_slack(pmax, nr.y);
-                bound2  = near_bound2_object(sqrt_kth, slack, g);
-                node    = (int)f2u(w3.y), sp = 0;
-                in_blas = true;
-                continue;
-            }
-            if (top_done) break;
-            const float4* c = tl.tlas + 2 * (size_t)(lds_off[level - 1u] + 2u * idx);
-            const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
-            const float   d0 = box_dist2(p.x, p.y, p.z, lo0.x, lo0.y, lo0.z, hi0.x, hi0.y, hi0.z);
-            const float   d1 = box_dist2(p.x, p.y, p.z, lo1.x, lo1.y, lo1.z, hi1.x, hi1.y, hi1.z);
-            // (a record with k < 0 holds nothing: an inert instance or the padding of a level)
-            const bool h0 = lo0.w >= 0.0f && !near_skip(d0, bound2_top), h1 = lo1.w >= 0.0f && !near_skip(d1, bound2_top);
-            const bool far_first = h0 && h1 && d1 < d0;
-            if (level > 1u)
-            {
-                if (h0 || h1)
-                {
-                    if (h0 && h1) pending |= 1u << (level - 1u);
-                    idx   = 2u * idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
-                    level = level - 1u;
-                    continue;
-                }
-            }
-            else if (h0 || h1)
-            {
-                // the children are instances: the nearer box first
-                const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
-                if (h0 && h1)
-                    todo0 = far_first ? i1 : i0, todo0_d = far_first ? d1 : d0, todo1 = far_first ? i0 : i1, todo1_d = far_first ? d0 : d1;
-                else
-                    todo0 = h0 ? i0 : i1, todo0_d = h0 ? d0 : d1;
-            }
-            const uint32_t owed = pending >> level;
-            if (owed == 0u)
-            {
-                top_done = true;
-                continue;
-            }
-            const uint32_t up = (uint32_t)__builtin_ctz(owed);
-            idx     = (idx >> up) ^ 1u;
-            level   = level + up;
-            pending = pending & ~(1u << level);
+            if (t.done) break;
+            t = top_step(tl, lds_off, p.x, p.y, p.z, bound2_top, t);
         }
         // (a point that was not traversed: the list as init left it, k miss records with dist2 = r2 = 0 and instance ~0, and count 0)
         if (COUNT) m.counts[j] = count;
@@ -821,164 +706,114 @@ __global__ __launch_bounds__(kBlock, closest_inst_multi_blocks(STACK, K)) void k
                 if (q - skip == (int)s) gid = L.g[q], li = L.i[q];
             ipage[s] = li;
             if (gid == kInvalidId)
-            {
-                page[2 * s]     = make_float4(0.f, 0.f, 0.f, r2);
-                page[2 * s + 1] = make_float4(0.f, 0.f, u2f(kInvalidId), 0.f);
-                continue;
-            }
-            const float4*      rec = bvh.tris_by_id + 4 * (size_t)gid;
-            const float4*      md  = ia.descs + 4 * (size_t)li;
-            const WorldRecord  w   = world_record(md[0], md[1], md[2], rec[0], rec[1], rec[2]);
-            const ClosestPoint c   = closest_record(w.t0, w.t1, w.t2, p.x, p.y, p.z);
-            page[2 * s]     = make_float4(c.x, c.y, c.z, c.d2);
-            page[2 * s + 1] = make_float4(c.u, c.v, u2f(gid), u2f(c.feature));
+                write_miss(page + 2 * s, r2);
+            else
+                write_record(page + 2 * s, instance_record(bvh, ia.descs, li, gid, p), gid);
         }
     }
 }
 
-template <int STACK, int K, bool COUNT>
-void launch_closest_inst_multi_k(const LaunchCfg& cfg, const BvhDev& b, const ClosestInstMultiArgs& m, const TlasDev& tl, const RayFilter& f)
+// ---- launchers ----
+// f(S) with S the smallest stack class that holds `depth` entries, as a std::integral_constant: a walk pushes at most one entry per level
+// it descends
+template <typename F>
+void with_stack_class(uint32_t depth, F&& f)
 {
-    uint32_t want = (m.ia.a.n + kBlock - 1) / kBlock;
-    if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_closest_inst_multi<STACK, K, COUNT>), dim3(resident_grid<k_closest_inst_multi<STACK, K, COUNT>>(cfg, want)), dim3(kBlock), 0,
-                       cfg.stream, b, m, tl, f);
+    if (depth <= 16)
+        f(std::integral_constant<int, 16>{});
+    else if (depth <= 24)
+        f(std::integral_constant<int, 24>{});
+    else if (depth <= 32)
+        f(std::integral_constant<int, 32>{});
+    else
+        f(std::integral_constant<int, 64>{});
+}
+// f(K) with K the list capacity of pages of k records
+template <typename F>
+void with_k_bucket(uint32_t k, F&& f)
+{
+    switch (multi_bucket(k))
+    {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
+    }
+}
+template <typename F>
+void with_flag(bool on, F&& f)
+{
+    if (on)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
 }
 
-template <int STACK>
-void launch_closest_inst_multi(const LaunchCfg& cfg, const BvhDev& b, const ClosestInstMultiArgs& m, const TlasDev& tl, const RayFilter& f)
+// One lane per point on the grid that is resident at once
+template <auto Kernel, typename... Args>
+void launch_points(const LaunchCfg& cfg, uint32_t n, const Args&... args)
 {
-#define CAP_CLOSEST_INST_MULTI(K)                                     \
-    if (m.counts)                                                     \
-        launch_closest_inst_multi_k<STACK, K, true>(cfg, b, m, tl, f);  \
-    else                                                              \
-        launch_closest_inst_multi_k<STACK, K, false>(cfg, b, m, tl, f);
-    switch (multi_bucket(m.k))
-    {
-    case 1: CAP_CLOSEST_INST_MULTI(1) break;
-    case 4: CAP_CLOSEST_INST_MULTI(4) break;
-    case 8: CAP_CLOSEST_INST_MULTI(8) break;
-    default: CAP_CLOSEST_INST_MULTI(16) break;
-    }
-#undef CAP_CLOSEST_INST_MULTI
+    uint32_t want = (n + kBlock - 1) / kBlock;
+    if (want == 0) want = 1;
+    hipLaunchKernelGGL(Kernel, dim3(resident_grid<Kernel>(cfg, want)), dim3(kBlock), 0, cfg.stream, args...);
+}
+
+// cap_closest_points and, SIGNED, cap_signed_distance
+template <bool SIGNED>
+void launch_closest(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const SignedArgs& s, const RayFilter* f, uint32_t depth)
+{
+    BvhDev b   = bvh;
+    b.wide8_ok = 0;
+    const RayFilter rf = f ? *f : RayFilter{};
+    with_stack_class(depth, [&](auto S) {
+        with_flag(f && f->tri_mask, [&](auto FILTER) { launch_points<k_closest_points<decltype(S)::value, decltype(FILTER)::value, SIGNED>>(cfg, a.n, b, a, rf, s); });
+    });
 }
 }  // namespace
 
 void launch_closest_points(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const RayFilter* f, uint32_t depth)
 {
-    BvhDev b   = bvh;
-    b.wide8_ok = 0;
-    const bool      filter = f && f->tri_mask;
-    const RayFilter rf     = f ? *f : RayFilter{};
-    // a walk pushes at most one entry per level it descends
-#define CAP_CLOSEST(S)                                    \
-    if (filter)                                           \
-        launch_closest_s<S, true>(cfg, b, a, rf);         \
-    else                                                  \
-        launch_closest_s<S, false>(cfg, b, a, rf);
-    if (depth <= 16)
-    {
-        CAP_CLOSEST(16)
-    }
-    else if (depth <= 24)
-    {
-        CAP_CLOSEST(24)
-    }
-    else if (depth <= 32)
-    {
-        CAP_CLOSEST(32)
-    }
-    else
-    {
-        CAP_CLOSEST(64)
-    }
-#undef CAP_CLOSEST
+    launch_closest<false>(cfg, bvh, a, SignedArgs{}, f, depth);
 }
 
 void launch_signed_distance(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const SignedArgs& s, const RayFilter* f, uint32_t depth)
 {
-    BvhDev b   = bvh;
-    b.wide8_ok = 0;
-    const bool      filter = f && f->tri_mask;
-    const RayFilter rf     = f ? *f : RayFilter{};
-#define CAP_SIGNED(S)                                          \
-    if (filter)                                                \
-        launch_closest_s<S, true, true>(cfg, b, a, rf, s);     \
-    else                                                       \
-        launch_closest_s<S, false, true>(cfg, b, a, rf, s);
-    if (depth <= 16)
-    {
-        CAP_SIGNED(16)
-    }
-    else if (depth <= 24)
-    {
-        CAP_SIGNED(24)
-    }
-    else if (depth <= 32)
-    {
-        CAP_SIGNED(32)
-    }
-    else
-    {
-        CAP_SIGNED(64)
-    }
-#undef CAP_SIGNED
+    launch_closest<true>(cfg, bvh, a, s, f, depth);
 }
 
 void launch_closest_points_multi(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestMultiArgs& m, const RayFilter* f, uint32_t depth)
 {
     BvhDev b   = bvh;
     b.wide8_ok = 0;
-    const bool      filter = f && f->tri_mask;
-    const RayFilter rf     = f ? *f : RayFilter{};
-    if (depth <= 16)
-        launch_closest_multi<16>(cfg, b, m, filter, rf);
-    else if (depth <= 24)
-        launch_closest_multi<24>(cfg, b, m, filter, rf);
-    else if (depth <= 32)
-        launch_closest_multi<32>(cfg, b, m, filter, rf);
-    else
-        launch_closest_multi<64>(cfg, b, m, filter, rf);
+    const RayFilter rf = f ? *f : RayFilter{};
+    with_stack_class(depth, [&](auto S) {
+        with_k_bucket(m.k, [&](auto K) {
+            with_flag(m.counts != nullptr, [&](auto COUNT) {
+                with_flag(f && f->tri_mask, [&](auto FILTER) {
+                    launch_points<k_closest_points_multi<decltype(S)::value, decltype(K)::value, decltype(COUNT)::value, decltype(FILTER)::value>>(cfg, m.a.n, b, m, rf);
+                });
+            });
+        });
+    });
 }
 
 void launch_closest_instances(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstArgs& a, const TlasDev& tl, const RayFilter& f, uint32_t depth)
 {
-    const bool filter = f.tri_mask != nullptr;
-    // the bottom-level stack: a walk pushes at most one entry per level it descends
-#define CAP_CLOSEST_INST(S)                                   \
-    if (filter)                                               \
-        launch_closest_inst_s<S, true>(cfg, bvh, a, tl, f);   \
-    else                                                      \
-        launch_closest_inst_s<S, false>(cfg, bvh, a, tl, f);
-    if (depth <= 16)
-    {
-        CAP_CLOSEST_INST(16)
-    }
-    else if (depth <= 24)
-    {
-        CAP_CLOSEST_INST(24)
-    }
-    else if (depth <= 32)
-    {
-        CAP_CLOSEST_INST(32)
-    }
-    else
-    {
-        CAP_CLOSEST_INST(64)
-    }
-#undef CAP_CLOSEST_INST
+    // (depth: of the deepest bottom-level tree)
+    with_stack_class(depth, [&](auto S) {
+        with_flag(f.tri_mask != nullptr, [&](auto FILTER) { launch_points<k_closest_inst<decltype(S)::value, decltype(FILTER)::value>>(cfg, a.a.n, bvh, a, tl, f); });
+    });
 }
 
 void launch_closest_instances_multi(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstMultiArgs& m, const TlasDev& tl, const RayFilter& f,
                                     uint32_t depth)
 {
-    if (depth <= 16)
-        launch_closest_inst_multi<16>(cfg, bvh, m, tl, f);
-    else if (depth <= 24)
-        launch_closest_inst_multi<24>(cfg, bvh, m, tl, f);
-    else if (depth <= 32)
-        launch_closest_inst_multi<32>(cfg, bvh, m, tl, f);
-    else
-        launch_closest_inst_multi<64>(cfg, bvh, m, tl, f);
+    with_stack_class(depth, [&](auto S) {
+        with_k_bucket(m.k, [&](auto K) {
+            with_flag(m.counts != nullptr, [&](auto COUNT) {
+                launch_points<k_closest_inst_multi<decltype(S)::value, decltype(K)::value, decltype(COUNT)::value>>(cfg, m.ia.a.n, bvh, m, tl, f);
+            });
+        });
+    });
 }
 }  // namespace cap
