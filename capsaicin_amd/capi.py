@@ -629,6 +629,8 @@ class Renderer:
     DEBUG_SELFTEST_SHADE_UNARY, DEBUG_SELFTEST_SHADE_DIV2, DEBUG_SHADE_TAME = 11, 12, 13
     DEBUG_CAMERA_CULL = 14
     DEBUG_MARK_FORM = 15  # form << 8 | dense; form 0 none, 1 by id, 2 carry chain, 3 carry chain over two words
+    DEBUG_SAMPLE_TABLE = 16  # 1: the last render's fused launches took the direction-sample terms from the per-batch table
+    DEBUG_SELFTEST_SAMPLE_TABLE = 17  # mismatching entries << 32 | (bounce, slot) rows of the last batch's table compared
 
     def debug_set(self, key, value):
         _check(lib().cap_debug_set(self.ctx, key, value), "cap_debug_set")

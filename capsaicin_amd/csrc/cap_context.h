@@ -190,6 +190,12 @@ struct CapContext
     uint32_t      last_class_capacity = 0;     // sub-queue capacity of the last cap_render batch (CAP_DEBUG_QUEUE_CANARY_*)
     uint32_t      tri_ids_dense = 0;           // pair_ids_dense() of the uploaded fan records (BvhDev::tri_ids_dense)
     uint32_t      last_mark_form = 0;          // launch_trace_shade()'s answer for bounce >= 1 of the last cap_render (CAP_DEBUG_MARK_FORM)
+    uint32_t      last_sample_table = 0;       // 1: the last cap_render's fused launches took the sample-table form (CAP_DEBUG_SAMPLE_TABLE)
+    struct LastTerms                           // the table the last batch of the last cap_render built (CAP_DEBUG_SELFTEST_SAMPLE_TABLE)
+    {
+        const FrameConst* frames = nullptr;    // its frame constants (a slot of frames_ring: intact until kFrameRing calls later)
+        uint32_t          n_slots = 0, num_bounces = 0, lane = 0;
+    } last_terms;
     uint32_t      last_cull_camera_pairs = 0;  // ShadeArgs::cull_camera_pairs of the last cap_render batch (CAP_DEBUG_CAMERA_CULL)
     uint32_t      traversal_mode  = CAP_TRAVERSAL_AUTO;
     uint32_t      bvh_build_mode  = CAP_BVH_BUILD_AUTO;
@@ -205,6 +211,7 @@ struct CapContext
     {
         hipStream_t      stream = nullptr;  // not owned: the context's `stream` (lane 0) or `stream2` (lane 1)
         DevBuf<float4>   hits, q_org[2], q_dir[2], q_thr[2], s_org, s_dir, s_con, pl_color, pl_direct, pl_albedo;
+        DevBuf<float4>   terms;        // per batch: direction-sample terms [sampling bounce][slot][4096] (ShadeArgs::sample_terms), if the form is on
         DevBuf<uint32_t> counters;     // per batch: ext[0..D], shadow[0..D]
         DevBuf<uint32_t> stack_spill;  // traversal-stack entries beyond the LDS part, per thread of the persistent grid
     } lane[2];

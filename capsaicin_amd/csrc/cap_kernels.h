@@ -41,6 +41,7 @@ enum CapSwitch : uint32_t
     SW_NO_NEE_PAIR_CULL,    // EXT model: next-event rays test every fan pair (read by the next cap_bvh_build / cap_materials_upload)
     SW_RAYGEN_KERNEL,       // dense scenes: the camera rays' identity queue written out by k_raygen_identity instead of generated in the trace kernel
     SW_NO_PLANE_CODE,       // small-scene path under albedo_in_w: bounce 0 writes the constant direct plane as before (ShadeArgs::code_in_color off)
+    SW_SAMPLE_TABLE,        // small-scene path, reference model: 0 never, 1 whenever the kernels have the form: direction-sample terms from the batch's table (ShadeArgs::sample_terms)
     SW_COUNT
 };
 struct SwitchTable
@@ -297,7 +298,13 @@ struct ShadeArgs
     CameraDev         cam;
     ScreenDev         screen;
     const FrameConst* frames;
-    const float4*     hits;
+    // One word, two readers that never meet: the stand-alone shade stage of the tree path reads `hits`; the fused small-scene kernels take
+    // their hit from registers and read `sample_terms` (see below).  Sharing it keeps the kernel arguments of every kernel as they were.
+    union
+    {
+        const float4* hits;
+        const float4* sample_terms;
+    };
     RayQueue          in;       // unused for the first bounce (identity queue)
     RayQueue          out;
     ShadowQueue       shadow;
@@ -335,6 +342,10 @@ struct ShadeArgs
     // read it is rewritten by every batch's bounce 0.  Set by the host only where every kernel involved has the form: the fused
     // kernel of bounce 0 (trace_shade_has_code_form), the small-scene any-hit kernels (launch_trace_any's code_plane) and the resolve.
     uint32_t          code_in_color;
+    // sample_terms (above; fused small-scene launches only, where it is always set): this bounce's block [frame slot][4096] of the batch's
+    // table of direction-sample terms (launch_sample_terms), or null: the sample travels in the queue entries and every vertex computes
+    // its own terms.  All launches of a batch take the same form (launch_trace_shade); the last bounce samples nothing and reads
+    // nothing through it.
 };
 // The first vertex's code (direct.w under albedo_in_w, color.w under code_in_color).  Three places must agree on it: shade_vertex
 // (the plane's word, and under CODE the spare word of a bounce-0 shadow entry), store_first_direct (+ kCodeLit) and the resolves.
@@ -354,6 +365,14 @@ bool launch_primary_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeAr
 uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback = false);
 // whether the reference model's bounce 0 of this scene has the form ShadeArgs::code_in_color asks for (the kernel of tame records in LDS)
 bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene);
+// ... and the form ShadeArgs::sample_terms asks for (the lean kernels)
+bool trace_shade_has_table_form(const BvhDev& bvh, const SceneDev& scene);
+// The batch's table of direction-sample terms: table[(b * n_slots + s) * 4096 + ((y mod 64) << 6 | x mod 64)] = (ca, cb, cos_theta, 0) of
+// hemisphere_terms() of the blue-noise sample of count = frames[s].frame_count * 25 + b, for b < num_bounces (the bounces that sample).
+void launch_sample_terms(hipStream_t stream, const float2* bluenoise, const FrameConst* frames, uint32_t n_slots, uint32_t num_bounces, float4* table);
+// out_device[0] += entries of such a table that differ from the per-vertex evaluation in any bit, out_device[1] += entries compared
+void launch_sample_terms_selftest(hipStream_t stream, const float2* bluenoise, const FrameConst* frames, uint32_t n_slots, uint32_t num_bounces,
+                                  const float4* table, unsigned long long* out_device);
 
 // ---- accumulate / exchange ----
 // accum[pl] += sum over slots (in slot order) of color*albedo + direct; .w counts frames.

@@ -71,7 +71,26 @@ __device__ __forceinline__ bool ortho_in_range(float a, float b, float g)
     const uint32_t     xa = (f2u(a) & 0x7fffffffu) - 1u, xb = (f2u(b) & 0x7fffffffu) - 1u;
     return (f2u(g) - kG0 < kG1 - kG0) & ((xa < xb ? xa : xb) >= kX0 - 1u);
 }
-__device__ __forceinline__ v3 map_to_hemisphere_tame(float r1, float r2, v3 n)
+// The direction sample in two parts.  hemisphere_terms: what depends on the blue-noise pair alone -- the same for every vertex that
+// draws (r1, r2), whatever it hit, which is what lets k_sample_terms (small_scene.hip) evaluate it once per (bounce, frame slot, position
+// in the 64 x 64 blue-noise period) instead of once per vertex.  hemisphere_dir_tame: the tangent frame, the combination and the final
+// normalize.  `terms` is a callable so that the per-vertex form evaluates it exactly where map_to_hemisphere_tame always has.
+struct HemiTerms
+{
+    float ca, cb, cos_theta;  // sin_theta * cos_psi, sin_theta * sin_psi, cos_theta
+};
+__device__ __forceinline__ HemiTerms hemisphere_terms(float r1, float r2)
+{
+    float sin_psi, cos_psi;
+    sincos_c((2.0f * kPi) * r1, sin_psi, cos_psi);
+    // r2 = x - floorf(x) is in [0, 1 - 2^-24] (0 on lanes without a sample): 1 - r2 in [2^-24, 1].  cos_theta^2 rounds into [2^-24, 1],
+    // so 1 - cos_theta^2 is 0 or in [2^-24, 1): the zero needs the fix-up
+    const float cos_theta = sqrt_pos(1.0f - r2);
+    const float sin_theta = sqrt_unscaled(1.0f - cos_theta * cos_theta);
+    return HemiTerms{sin_theta * cos_psi, sin_theta * sin_psi, cos_theta};
+}
+template <class Terms>
+__device__ __forceinline__ v3 hemisphere_dir_tame(v3 n, Terms terms)
 {
     // ortho_vector under one wave-uniform guard: a wave with a lane outside it takes the plain forms for these three operations and
     // for the final normalize3 (whose operand is 1 +- 1e-5 only for a finite orthonormal frame)
@@ -94,16 +113,15 @@ __device__ __forceinline__ v3 map_to_hemisphere_tame(float r1, float r2, v3 n)
     v3       u = zn ? mk3(0.0f, -q1, q2) : mk3(q1, -q2, 0.0f);
     const v3 v = cross3(u, n);
     u          = cross3(n, v);
-    float sin_psi, cos_psi;
-    sincos_c((2.0f * kPi) * r1, sin_psi, cos_psi);
-    // r2 = x - floorf(x) is in [0, 1 - 2^-24] (0 on lanes without a sample): 1 - r2 in [2^-24, 1].  cos_theta^2 rounds into [2^-24, 1],
-    // so 1 - cos_theta^2 is 0 or in [2^-24, 1): the zero needs the fix-up
-    const float cos_theta = sqrt_pos(1.0f - r2);
-    const float sin_theta = sqrt_unscaled(1.0f - cos_theta * cos_theta);
-    const float ca = sin_theta * cos_psi, cb = sin_theta * sin_psi;
+    const HemiTerms h = terms();
+    const float     cos_theta = h.cos_theta, ca = h.ca, cb = h.cb;
     const v3    d = mk3(fmaf(n.x, cos_theta, fmaf(v.x, cb, u.x * ca)), fmaf(n.y, cos_theta, fmaf(v.y, cb, u.y * ca)),
                         fmaf(n.z, cos_theta, fmaf(v.z, cb, u.z * ca)));
     return fast ? normalize3_tame(d) : normalize3(d);
+}
+__device__ __forceinline__ v3 map_to_hemisphere_tame(float r1, float r2, v3 n)
+{
+    return hemisphere_dir_tame(n, [=] { return hemisphere_terms(r1, r2); });
 }
 
 // math_functions.h:36-47
@@ -191,6 +209,7 @@ __device__ __forceinline__ uint32_t wave_append(bool emit, uint32_t* counter)
 //   TAME     the scene's shading records are tame (SceneDev::shade_tame): square roots and divisions in their unscaled forms
 //   LEAN     the lean per-chunk plumbing (see kChunkLean)
 //   CODE     bounce 0 under ShadeArgs::code_in_color: the first vertex's code goes to color.w and the direct plane is not written
+//   TAB      the direction sample's terms come from the batch's table (ShadeArgs::sample_terms) instead of being carried and computed
 struct ShadePre
 {
     bool  valid;
@@ -198,6 +217,7 @@ struct ShadePre
     float r1, r2;  // sampling.h:13-23 sample of (pixel, frame * 25 + bounce)
     float r3, r4, r5, r6;  // EXT only: B, A of the same texel; R, G of the texel of count + 7
     float r1n, r2n;        // CARRY only: the sample of the path's NEXT vertex (count + 1), handed on in the queue entry
+                           // TAB: the sample itself is never fetched; (r1, r2, r1n) hold hemisphere_terms' (ca, cb, cos_theta) of it from the table
     bool  indirect_on;     // false for the three pixels of a 2x2 block that get no indirect sample this frame (LOWRES_INDIRECT)
 };
 
@@ -259,7 +279,8 @@ __device__ __forceinline__ void     bluenoise_at(const float2* tex, uint32_t bas
 }
 // stage_frames() of the lean kernels.  All kMaxFrameSlots entries are defined (zeros behind n_slots), so that even a malformed path
 // id finds an offset <= 0x0303 in its slot's row.
-template <bool FIRST>
+// TAB: no kernel reads a sample's constants (they went into the table, k_sample_terms): the rows are copied as they are.
+template <bool FIRST, bool TAB = false>
 __device__ __forceinline__ void stage_frames_samples(const ShadeArgs& a, FrameConst* lds_frames, SlotSample* lds_first)
 {
     constexpr uint32_t kWords = (uint32_t)(sizeof(FrameConst) / 4);
@@ -274,7 +295,7 @@ __device__ __forceinline__ void stage_frames_samples(const ShadeArgs& a, FrameCo
         {
             const uint32_t sl = i / kWords, w = i - sl * kWords;
             v = src[i];
-            if (w == 7u || w == 11u)
+            if (!TAB && (w == 7u || w == 11u))
             {
                 const uint32_t next = src[sl * kWords + 2u] * 25u + a.bounce + 1u;
                 v = w == 7u ? bluenoise_offset(next) : f2u(bluenoise_shift(next));
@@ -282,7 +303,7 @@ __device__ __forceinline__ void stage_frames_samples(const ShadeArgs& a, FrameCo
         }
         dst[i] = v;
     }
-    if (FIRST)
+    if (FIRST && !TAB)
         for (uint32_t sl = threadIdx.x; sl < kMaxFrameSlots; sl += kBlock)
         {
             SlotSample ss = {0u, 0.0f};
@@ -318,17 +339,17 @@ __device__ __forceinline__ ShadePre shade_prefetch(const ShadeArgs& a, const Fra
     const uint32_t slot = pid >> kPidShift, pl = pid & kPidMask;
     if constexpr (C::LEAN)
     {
-        static_assert(C::CARRY && !C::EXT, "LEAN: the reference model's fused kernels");
+        static_assert((C::CARRY != C::TAB) && !C::EXT, "LEAN: the reference model's fused kernels, the sample carried or from the table");
         const uint32_t    sl = slot < kMaxFrameSlots ? slot : 0;
         const FrameConst& fc = lds_frames[sl];
-        uint32_t          base;
+        uint32_t          base;  // TAB: the position in the 64 x 64 period, (y mod 64) << 6 | x mod 64, from the same bits
         s.indirect_on = true;
         if (C::FIRST)
         {
             uint32_t x = 0, y = 0;
             s.valid = active && local_pixel_to_xy(a.screen, pl, x, y);
             if (fc.lowres_sel & 4u) s.indirect_on = (x & 1u) == ((fc.lowres_sel >> 1) & 1u) && (y & 1u) == (fc.lowres_sel & 1u);
-            base = bluenoise_base(x, y);
+            base = C::TAB ? ((y & 63u) << 6) | (x & 63u) : bluenoise_base(x, y);
         }
         else
         {
@@ -338,7 +359,8 @@ __device__ __forceinline__ ShadePre shade_prefetch(const ShadeArgs& a, const Fra
             // tx = gt - ty * tiles_x, of which only tx mod 8 is used: the low three bits of a product need those of its factors alone
             const uint32_t tx = gt + (ty & 7u) * ((0u - a.screen.tiles_x) & 7u);
             // x mod 64 = (tx mod 8) * 8 + (w & 7), y mod 64 = (ty mod 8) * 8 + (w >> 3) with w = pl & 63, placed as bluenoise_base() does
-            base = ((ty & 7u) << 13) | ((pl & 0x38u) << 7) | ((tx & 7u) << 5) | ((pl & 7u) << 2);
+            base = C::TAB ? ((ty & 7u) << 9) | ((pl & 0x38u) << 3) | ((tx & 7u) << 3) | (pl & 7u)
+                          : ((ty & 7u) << 13) | ((pl & 0x38u) << 7) | ((tx & 7u) << 5) | ((pl & 7u) << 2);
         }
         s.L = unread3(), s.I = unread3(), s.r1 = s.r2 = s.r1n = s.r2n = unread_f();
         s.r3 = s.r4 = s.r5 = s.r6 = 0.f;  // EXT only
@@ -346,6 +368,17 @@ __device__ __forceinline__ ShadePre shade_prefetch(const ShadeArgs& a, const Fra
         {
             s.L = mk3(fc.light_dir[0], fc.light_dir[1], fc.light_dir[2]);
             s.I = mk3(fc.light_intensity[0], fc.light_intensity[1], fc.light_intensity[2]);
+            if constexpr (C::TAB)
+            {
+                // one 16-byte load from this bounce's [slot][4096] block; every row below n_slots is defined, base < 4096 for any path id.
+                // The last bounce samples nothing (TAME) and loads nothing
+                if (a.bounce < a.num_bounces)
+                {
+                    const float4 q = a.sample_terms[((slot < a.n_slots ? slot : 0u) << 12) | base];
+                    s.r1 = q.x, s.r2 = q.y, s.r1n = q.z;
+                }
+                return s;
+            }
             if (C::FIRST)
             {
                 const SlotSample ss = lds_first[sl];
@@ -641,7 +674,10 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
                 const bool more = a.bounce < a.num_bounces;
                 if (!C::TAME || more)
                 {
-                    dir             = C::TAME ? map_to_hemisphere_tame(pre.r1, pre.r2, n) : map_to_hemisphere(pre.r1, pre.r2, n);
+                    if constexpr (C::TAB)
+                        dir = hemisphere_dir_tame(n, [&] { return HemiTerms{pre.r1, pre.r2, pre.r1n}; });
+                    else
+                        dir = C::TAME ? map_to_hemisphere_tame(pre.r1, pre.r2, n) : map_to_hemisphere(pre.r1, pre.r2, n);
                     const float ndd = dot3(n, dir);
                     // TAME: n and dir are unit vectors (or dir is NaN: numerator 0), so the numerator is 0 or in (0, 1.01].  From 2^-80 on
                     // the quotient has the bits of the plain one; below, it is some finite value < 2^-78, which `pdf < 1e-5f` rejects like

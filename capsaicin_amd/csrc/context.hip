@@ -283,10 +283,10 @@ SceneDev scene_dev(const CapContext* c)
 // cap_render tests to learn whether a call grows a lane (growing frees the old buffers, so the streams are drained first)
 struct LaneSizes
 {
-    size_t planes, queues, rings, counters;
+    size_t planes, queues, rings, counters, terms;
 };
 
-LaneSizes lane_sizes(const CapContext* c, uint32_t slots, uint32_t bounces)
+LaneSizes lane_sizes(const CapContext* c, uint32_t slots, uint32_t bounces, bool sample_table)
 {
     LaneSizes z;
     z.planes = (size_t)slots * c->screen.pixels_padded;
@@ -296,19 +296,22 @@ LaneSizes lane_sizes(const CapContext* c, uint32_t slots, uint32_t bounces)
     z.rings = std::max(z.queues, (size_t)std::max(c->cu_count, 1) * 8 * (kBlock / 64) * 128);
     // queue counters (ext + shadow share words) + chunk-grab counters of the fused and of the any-hit launch, per bounce
     z.counters = (3 * (size_t)(bounces + 1) + 1) * kQueueClasses * kCounterStride;  // + 1: the camera rays' identity queue
+    // the table of direction-sample terms (ShadeArgs::sample_terms): 4096 entries per frame slot and sampling bounce, 32 MB at 64 x 8
+    z.terms = sample_table ? (size_t)slots * bounces * 4096 : 0;
     return z;
 }
 
-bool lane_grows(const CapContext::Lane& L, const LaneSizes& z) { return L.pl_color.n < z.planes || L.counters.n < z.counters; }
+bool lane_grows(const CapContext::Lane& L, const LaneSizes& z) { return L.pl_color.n < z.planes || L.counters.n < z.counters || L.terms.n < z.terms; }
 
-int ensure_lane(CapContext* c, CapContext::Lane& L, uint32_t slots, uint32_t bounces)
+int ensure_lane(CapContext* c, CapContext::Lane& L, uint32_t slots, uint32_t bounces, bool sample_table)
 {
-    const LaneSizes z = lane_sizes(c, slots, bounces);
+    const LaneSizes z = lane_sizes(c, slots, bounces, sample_table);
     for (DevBuf<float4>* b : {&L.hits, &L.q_org[0], &L.q_org[1], &L.q_dir[0], &L.q_dir[1], &L.q_thr[0], &L.q_thr[1], &L.s_dir})
         HIP_TRY(b->ensure(z.queues));
     for (DevBuf<float4>* b : {&L.s_org, &L.s_con}) HIP_TRY(b->ensure(z.rings));
     for (DevBuf<float4>* b : {&L.pl_color, &L.pl_direct, &L.pl_albedo}) HIP_TRY(b->ensure(z.planes));
     HIP_TRY(L.counters.ensure(z.counters));
+    if (z.terms) HIP_TRY(L.terms.ensure(z.terms));
     // as much spill as lane 0, whose area cap_bvh_build allocates (for lane 0 itself: nothing to do)
     if (c->lane[0].stack_spill.n) HIP_TRY(L.stack_spill.ensure(c->lane[0].stack_spill.n));
     return CAP_OK;
@@ -450,7 +453,7 @@ static const char* const kSwitchNames[SW_COUNT] = {
     "CAP_NO_WIDE8", "CAP_LANE1_PRIORITY", "CAP_PLOC_RADIUS", "CAP_SAHDEV_LEAF", "CAP_WIDE_HOST_COLLAPSE", "CAP_TRACE_LAUNCHES", "CAP_NO_TWO_LANES",
     "CAP_LANE_SPLIT_MIN", "CAP_BLOCKS_PER_CU", "CAP_NO_CAMERA_CULL", "CAP_NO_ALBEDO_IN_W", "CAP_NO_INLINE_NEE", "CAP_NO_INLINE_PROBE", "CAP_NO_WAVE_RING",
     "CAP_ANY_REFILL", "CAP_PRIMARY_WIDE", "CAP_NO_PACKET", "CAP_NO_ANY_PROBE", "CAP_ANY_PROBE", "CAP_ANY_BLOCKS", "CAP_NO_PRIMARY_FUSE", "CAP_W8_REFILL",
-    "CAP_W8_GRID", "CAP_AUTO_SAH_TRIANGLES", "CAP_NO_NEE_PAIR_CULL", "CAP_RAYGEN_KERNEL", "CAP_NO_PLANE_CODE"};
+    "CAP_W8_GRID", "CAP_AUTO_SAH_TRIANGLES", "CAP_NO_NEE_PAIR_CULL", "CAP_RAYGEN_KERNEL", "CAP_NO_PLANE_CODE", "CAP_SAMPLE_TABLE"};
 
 static void switches_from_environment(SwitchTable& t)
 {
@@ -779,6 +782,26 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
         if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_debug_get: BVH not built");
         *value = ((uint64_t)c->last_mark_form << 8) | c->tri_ids_dense;
         return CAP_OK;
+    case CAP_DEBUG_SAMPLE_TABLE: *value = c->last_sample_table; return CAP_OK;
+    case CAP_DEBUG_SELFTEST_SAMPLE_TABLE:
+    {
+        const CapContext::LastTerms& lt = c->last_terms;
+        if (!c->last_sample_table || !lt.frames) return fail(CAP_ERR_STATE, "cap_debug_get: the last cap_render built no sample table");
+        HIP_TRY(hipSetDevice(c->device));
+        if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
+        DevBuf<unsigned long long> d;
+        unsigned long long         h[2] = {0, 0};
+        HIP_TRY(d.ensure(2));
+        HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(h), c->stream));
+        launch_sample_terms_selftest(c->stream, c->bluenoise.p, lt.frames, lt.n_slots, lt.num_bounces, c->lane[lt.lane].terms.p, d.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const unsigned long long expected = (unsigned long long)lt.n_slots * lt.num_bounces * 4096ull;
+        if (h[1] != expected) return fail(CAP_ERR_HIP, "cap_debug_get: the sample table self-test compared %llu of %llu entries", h[1], expected);
+        *value = (h[0] << 32) | (expected >> 12);  // mismatches << 32 | (bounce, slot) rows compared
+        return CAP_OK;
+    }
     case CAP_DEBUG_NEE_PAIRS:
         if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_debug_get: BVH not built");
         *value = ((uint64_t)(c->fan_pairs_nee.p ? c->fan_pair_nee_count : c->fan_pair_count) << 32) | c->fan_pair_count;
@@ -862,6 +885,8 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
     if (!n_frames) return CAP_OK;
     HIP_TRY(hipSetDevice(c->device));
     c->last_mark_form   = 0;
+    c->last_sample_table = 0;
+    c->last_terms        = CapContext::LastTerms{};
     const bool feedback = (flags & CAP_RENDER_GBUFFER_FEEDBACK) != 0;
     if (feedback)
     {
@@ -901,9 +926,15 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
     // drained (what cap_sync / cap_stats_get do anyway), and a growing allocation (which frees the old buffers).
     if (c->spans.size() > 2048 || c->pending.size() > 64 || c->post_marks.size() > 256)
         if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
-    const LaneSizes need = lane_sizes(c, slots, num_bounces);
+    // Direction-sample terms from a per-batch table (ShadeArgs::sample_terms): decided once per call, for every launch of every batch.
+    // Rebuilt by every batch and never kept across calls: frame_begin advances from call to call in real use.
+    // A/B switch CAP_SAMPLE_TABLE: 0 never, 1 whenever the kernels have the form (which is also the product's choice).
+    const bool sample_table = fused && !ext && !feedback && num_bounces >= 1 && c->sw.get(SW_SAMPLE_TABLE, 1) != 0 &&
+                              trace_shade_has_table_form(bvh_dev(c, c->lane[0]), scene_dev(c));
+    c->last_sample_table = sample_table ? 1u : 0u;
+    const LaneSizes need = lane_sizes(c, slots, num_bounces, sample_table);
     if (lane_grows(c->lane[0], need) || !c->accum.p || c->accum.n < Ppad) HIP_TRY(hipStreamSynchronize(c->stream));
-    if (ensure_lane(c, c->lane[0], slots, num_bounces) != CAP_OK || ensure_frame_buffers(c) != CAP_OK) return CAP_ERR_HIP;
+    if (ensure_lane(c, c->lane[0], slots, num_bounces, sample_table) != CAP_OK || ensure_frame_buffers(c) != CAP_OK) return CAP_ERR_HIP;
     if (policy.lane1_failed_before)
     {
         // this size has already failed: one lane, without asking again -- except every 32nd time, and at once when the device reports
@@ -923,7 +954,7 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
             HIP_TRY(hipStreamSynchronize(c->stream));  // growing frees the old buffers
             if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
         }
-        if (c->debug_fail_lane || ensure_lane(c, c->lane[1], slots, num_bounces) != CAP_OK || ensure_lane_streams(c) != CAP_OK)
+        if (c->debug_fail_lane || ensure_lane(c, c->lane[1], slots, num_bounces, sample_table) != CAP_OK || ensure_lane_streams(c) != CAP_OK)
         {
             // the second working set doubles the batch's memory (~28 GB at the default budget): without it the batches of this call
             // simply run one after the other on lane 0 -- counted in CapStats::lane1_dropped, and not tried again at this
@@ -1026,7 +1057,8 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
         const uint32_t max_count  = ns * Ppad;
 
         ShadeArgs sa{};
-        sa.scene = scene, sa.cam = cam, sa.screen = c->screen, sa.frames = frames, sa.hits = L.hits.p;
+        sa.scene = scene, sa.cam = cam, sa.screen = c->screen, sa.frames = frames;
+        if (!fused) sa.hits = L.hits.p;  // (fused: the same word is sample_terms, set per bounce)
         sa.planes = Planes{L.pl_color.p, L.pl_direct.p, L.pl_albedo.p, c->aov_geo.p, c->aov_nd.p};
         sa.n_slots = ns, sa.num_bounces = D, sa.max_count = max_count, sa.aov_slot = aov_slot, sa.shaded_counter = c->shaded_counter.p;
         {
@@ -1103,10 +1135,18 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
             const double per_pixel = (double)c->tri_count / std::max(1.0, (double)c->screen.width * c->screen.height);
             primary_wide = inside && (force >= 0 ? force != 0 : per_pixel >= kPrimaryWideTrianglesPerPixel);
         }
+        if (sample_table)
+        {
+            launch_sample_terms(L.stream, scene.bluenoise, frames, ns, D, L.terms.p);
+            c->last_terms = CapContext::LastTerms{frames, ns, D, lane};
+            if (trace_launch(c, "sample_terms batch %u", batch)) return fail(CAP_ERR_HIP, "sample_terms failed");
+        }
         for (uint32_t b = 0; b <= D; ++b)
         {
             const int pi = (int)(b & 1u), po = pi ^ 1;
             sa.bounce    = b;
+            // bounce b's [slot][4096] block; the last bounce samples nothing and reads nothing, but takes the same form of kernel
+            if (fused) sa.sample_terms = sample_table ? L.terms.p + (size_t)(b < D ? b : 0u) * ns * 4096 : nullptr;
             // (inline_nee: no shadow entries are written, so the shadow queue's two 16-byte planes carry the paths' gathered radiance)
             sa.in        = RayQueue{L.q_org[pi].p, L.q_dir[pi].p, L.q_thr[pi].p, b ? ext_count + (b - 1) * per_queue : nullptr, class_capacity,
                                     pi ? L.s_dir.p : L.s_org.p};

@@ -29,13 +29,17 @@ __device__ unsigned long long g_wave_times[2 * 16384];  // (start, end) s_memrea
 // vertex's normalize3 -- and with it everything downstream of a unit normal -- take the unscaled forms.  Chosen at launch like LDS;
 // only the reference model's kernels with the scene in LDS have the instantiation.
 // CODE: ShadeArgs::code_in_color, bounce 0's form without the direct plane.  Only the TAME kernel has it (trace_shade_has_code_form).
-template <bool FIRST_, bool EXT_, bool FB_, bool LDS_, bool TAME_, bool CODE_ = false>
+// TAB: the terms of a vertex's direction sample come from the batch's table (ShadeArgs::sample_terms, k_sample_terms below) and no
+// queue entry carries a sample.  Only the lean kernels have the form (trace_shade_has_table_form).
+template <bool FIRST_, bool EXT_, bool FB_, bool LDS_, bool TAME_, bool CODE_ = false, bool TAB_ = false>
 struct TraceShadeCfg
 {
+    // (TAB_ = kChunkLean in k_trace_shade_tab: a build without the lean plumbing compiles the plain kernel under that name, never launched)
     static_assert(!TAME_ || (!EXT_ && !FB_ && LDS_), "TAME: reference model, scene in LDS");
     static_assert(!CODE_ || (FIRST_ && TAME_), "CODE: bounce 0 of the reference model, scene in LDS, tame records");
-    static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_, LDS = LDS_, TAME = TAME_, CODE = CODE_;
-    static constexpr bool CARRY = !EXT, SKY_RMW = false;
+    static_assert(!TAB_ || (TAME_ && kChunkLean), "TAB: the lean kernels (reference model, scene in LDS, tame records)");
+    static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_, LDS = LDS_, TAME = TAME_, CODE = CODE_, TAB = TAB_;
+    static constexpr bool CARRY = !EXT && !TAB, SKY_RMW = false;
     static constexpr bool PROBE = !EXT && !FB && LDS;  // the producer-side shadow probe (ShadeArgs::inline_probe) and the per-wave ring
     // the lean per-chunk plumbing (see kChunkLean): the reference model's kernels with the scene in LDS and tame records.  (The
     // instantiations without TAME pay for it with 8 and 4 B of scratch, the EXT and feedback kernels were not tried: they keep round 8's.)
@@ -142,231 +146,22 @@ __device__ __forceinline__ void stage_probe_rows(const BvhDev& bvh, const ShadeA
     }
 }
 
+// Both kernels are small_scene_body.h and nothing else: k_trace_shade the thirteen forms without the sample table, under the names and
+// with the instructions they have always had, k_trace_shade_tab the three with it.
 template <bool FIRST, bool EXT, bool FB = false, bool LDS = false, bool TAME = false, bool CODE = false>
 __global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, EXT, FB, LDS, TAME, CODE>::kBlocksPerCu)) void k_trace_shade(BvhDev bvh, ShadeArgs a)
 {
-    using C = TraceShadeCfg<FIRST, EXT, FB, LDS, TAME, CODE>;
-    const uint32_t Ppad     = a.screen.pixels_padded;
-    // FIRST: the identity queue of the whole batch, chunk = slot * (Ppad / 64) + 64-pixel group.  Otherwise: chunk slots of the
-    // input queue.  Either way the grid is persistent (the LDS tables are staged once per workgroup, not once per frame slot).
-    const uint32_t cps      = Ppad >> 6;
-    const uint32_t chunks   = FIRST ? cps * a.n_slots : (a.in.class_capacity >> 6) * kQueueClasses;
-    uint32_t       n_shaded = 0, n_probed = 0;
-    __shared__ FrameConst lds_frames[kMaxFrameSlots];
-    __shared__ float4     lds_shade[LDS ? kShadeRec * kExhaustiveMax : 1];
-    __shared__ float4     lds_rec[LDS ? 4 * kExhaustiveMax : 1];
-    __shared__ float4     lds_probe[C::PROBE ? 2 * kMaxFrameSlots : 1];
-    __shared__ float      lds_pscore[C::PROBE ? kExhaustiveMax / 2 : 1];
-    __shared__ SlotSample lds_first[(C::LEAN && FIRST) ? kMaxFrameSlots : 1];  // bounce 0 only (512 B; bounce >= 1 stays at its 25 732 B)
-    __shared__ uint32_t   lds_probe_k;
-    __shared__ float4     lds_ring[(C::PROBE && !FIRST) ? (kBlock / 64) * kWaveRing : 1];  // per wave: (origin, path id) of its parked shadow rays
-    __shared__ float4     lds_org[C::ORG ? kExhaustiveMax : 1];
-    __shared__ float4     lds_bounds[C::ORG ? kExhaustiveMax / 2 : 1];
-    __shared__ float      lds_mat[C::XT ? 12 * kExhaustiveMax : 1];
-    __shared__ float      lds_lcdf[C::XT ? kExtLightsMax : 1];
-    __shared__ float4     lds_lrec[C::XT ? 4 * kExtLightsMax : 1];
-    const bool            ext_tabs = C::XT && a.scene.material_count <= kExhaustiveMax && a.scene.light_count <= kExtLightsMax;  // wave-uniform
-    if (LDS)
-    {
-        stage_scene_records(bvh, a, lds_shade, lds_rec);
-        if (C::XT && ext_tabs) stage_ext_tables(a, lds_mat, lds_lcdf, lds_lrec);
-        if (C::ORG) stage_camera_pairs(bvh, a, lds_org, lds_bounds);
-    }
-    if (C::PROBE && a.inline_probe) stage_probe_rows(bvh, a, lds_pscore, lds_probe_k, lds_probe);
-    if constexpr (C::LEAN)
-        stage_frames_samples<FIRST>(a, lds_frames, lds_first);  // ends with the workgroup barrier
-    else
-        stage_frames(a, lds_frames);  // ends with the workgroup barrier
-    ProbeArgs probe;
-    if (C::PROBE && a.inline_probe) probe.rows = lds_probe, probe.pairs = bvh.fan_pairs, probe.k = lds_probe_k;
-    // The probe's survivors stay with the wave that found them (ShadeArgs::wave_ring): parked in its own 128-entry ring and traced
-    // 64 at a time between chunks -- the any-hit kernel's loop on full waves, without its launch, its queue round trip, or any
-    // other wave.  No plane entry is shared: within one launch a path either escapes (sky term) or has a vertex (this shadow
-    // ray), and the previous bounce's additions were made by the previous launch.
-    uint32_t ring_head = 0, ring_n = 0;  // wave-uniform
-    if (C::PROBE && !FIRST && a.inline_probe && a.wave_ring)  // (bounce 0: more survivors per chunk, and a kernel short of registers: 2.4 -> 2.9 ms for the 0.35 ms of its any-hit launch)
-    {
-        probe.ring_org = lds_ring + (threadIdx.x >> 6) * kWaveRing;  // origins + path ids in LDS, the contributions in this wave's
-        probe.ring_con = a.shadow.contrib_pid + (size_t)wave_global_id() * kWaveRing;  // slice of the shadow queue's memory
-    }
-    auto trace_ring = [&](uint32_t count) {
-        // The ring is a cross-lane hand-off inside one wave: lane i stored entry `pos` (LDS origin, global contribution), lane j
-        // loads it here.  Commit 6a9000f put a scheduling barrier here after reading the ISA, not after a failure: nothing but
-        // may-alias analysis kept the compiler from hoisting these loads above the stores of the inlined shade_vertex.  The memory
-        // model's statement of the same thing: release after the stores (shade_vertex), acquire before the loads.
-        wave_handoff();
-        const uint32_t lane_ = threadIdx.x & 63u;
-        const bool     on    = lane_ < count;
-        const uint32_t pos   = (ring_head + lane_) & (kWaveRing - 1u);
-        float4         o     = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (on) o = probe.ring_org[pos];
-        const uint32_t spid = f2u(o.w);
-        const bool     good = on && (spid >> kPidShift) < a.n_slots && (spid & kPidMask) < Ppad;
-        const FrameConst& fc = lds_frames[good ? (spid >> kPidShift) : 0u];
-        const Ray  sr = make_ray(mk3(o.x, o.y, o.z), mk3(fc.light_dir[0], fc.light_dir[1], fc.light_dir[2]), kRayEps, good ? kRayFar : kRayEps);
-        // what the probe left over is mostly unoccluded, and the path id came out of LDS: the contribution and the plane entry are
-        // requested before the test and arrive under it
-        float4* const target = a.bounce == 0 ? a.planes.direct : a.planes.color;
-        const size_t  idx    = good ? (size_t)(spid >> kPidShift) * Ppad + (spid & kPidMask) : 0;
-        float4        c = make_float4(0.f, 0.f, 0.f, 0.f), cur = c;
-        if (good) c = probe.ring_con[pos], cur = target[idx];
-        const bool occluded = exhaustive_any<false>(bvh, sr);
-        // lighting.h:57-60: unoccluded -> the contribution evaluated at shading time is added
-        if (good && !occluded) target[idx] = make_float4(cur.x + c.x, cur.y + c.y, cur.z + c.z, cur.w);
-        ring_head = (ring_head + count) & (kWaveRing - 1u);
-        ring_n -= count;
-    };
-    const float4* shade_tab = LDS ? lds_shade : a.scene.shade_tris;
-    const float4* rec_tab   = LDS ? lds_rec : bvh.tris_by_id;
-    ExtTables     xtabs;
-    if (C::XT && ext_tabs) xtabs.materials = reinterpret_cast<const MaterialDev*>(lds_mat), xtabs.light_cdf = lds_lcdf, xtabs.light_rec = lds_lrec;
-    Stamps st;
-    st.start();
-    // Chunk slots from the class's work counter, like the any-hit kernel (with the priorities below: bounce 0 4.6 -> 4.1 ms,
-    // bounce >= 1 unchanged; before them it cost the bounce >= 1 kernel 7 %).  As there, the class's length is read once and
-    // the next grab is issued after the entry loads (see k_trace_any).
-    const uint32_t my_class = wave_global_id() % kQueueClasses;
-    const uint32_t lane     = threadIdx.x & 63u;
-    uint32_t       n_class  = 0;
-    if (!FIRST)
-    {
-        n_class = a.in.count[my_class * kCounterStride];
-        n_class = n_class < a.in.class_capacity ? n_class : a.in.class_capacity;
-    }
-    uint32_t grab = grab_issue(a.work, my_class);
-    while (true)
-    {
-        const uint32_t j = grab_value(grab);  // slot j of this class
-        uint32_t       i, pid = 0, slot = 0;
-        const uint32_t klass = my_class;      // the path's class for its whole life
-        bool           active;
-        v3             thr = mk3(1.0f, 1.0f, 1.0f);
-        Ray            r   = make_ray(mk3(0.f, 0.f, 0.f), mk3(0.f, 0.f, 1.f), 0.0f, 0.0f);  // empty interval: hits nothing
-        float          carried_r1 = 0.f, carried_r2 = 0.f;
-        if (FIRST)
-        {
-            const uint32_t chunk = class_chunk(j, my_class);
-            if (chunk >= chunks) break;  // (only in or past the last block of 64 chunks: every earlier block holds each class once)
-            grab   = grab_issue(a.work, my_class);
-            slot   = chunk / cps;  // wave-uniform
-            i      = (chunk - slot * cps) * 64 + lane;
-            active = true;
-            pid    = (slot << kPidShift) | i;
-            uint32_t x, y;
-            if (local_pixel_to_xy(a.screen, i, x, y))
-                r = make_ray(mk3(a.cam.position[0], a.cam.position[1], a.cam.position[2]),
-                             primary_dir(a.cam, a.screen, lds_frames[slot], x, y), 0.0f, kPrimaryFar);
-        }
-        else
-        {
-            if (j * 64u >= n_class) break;  // past the end of this class's sub-queue
-            active = j * 64u + lane < n_class;
-            if constexpr (C::LEAN)
-            {
-                // A lane past the end of the class's last chunk loads the class's LAST entry (n_class > j * 64 >= 0 here, and
-                // n_class <= class_capacity: inside the sub-queue) instead of taking defaults that cost a v_mov per register and chunk, and
-                // the entry's registers are used where they land.  Such a lane holds a real path's ray and id, but active == false, and
-                // that alone keeps it silent: has_ray == false clears its candidate mask (so it hits nothing and reads no record),
-                // pre.valid == false makes shade_vertex skip every store, count and emit for it, and the only tables it indexes -- the
-                // frame slot's rows -- it indexes with that real, in-range slot.
-                const uint32_t local = j * 64u + lane;
-                i                    = my_class * a.in.class_capacity + (local < n_class ? local : n_class - 1u);
-                const float4 o = a.in.org_tmin[i], d = a.in.dir_tmax[i], tp = a.in.thr_pid[i];
-                grab = grab_issue(a.work, my_class);
-                r    = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), kRayEps, kRayFar);
-                thr  = mk3(tp.x, tp.y, tp.z), pid = f2u(tp.w);
-                carried_r1 = o.w, carried_r2 = d.w;
-            }
-            else
-            {
-                i      = my_class * a.in.class_capacity + j * 64u + lane;
-                // extension rays: tmin / tmax are constants (rt_indirect.hlsl:154-157); with C::CARRY the .w slots hold the sample
-                float4 o = make_float4(0.f, 0.f, 0.f, 0.f), d = make_float4(0.f, 0.f, 1.f, 0.f), tp = make_float4(1.f, 1.f, 1.f, 0.f);
-                if (active) o = a.in.org_tmin[i], d = a.in.dir_tmax[i], tp = a.in.thr_pid[i];
-                grab = grab_issue(a.work, my_class);
-                if (active)
-                {
-                    r   = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), kRayEps, kRayFar);
-                    thr = mk3(tp.x, tp.y, tp.z), pid = f2u(tp.w);
-                    carried_r1 = o.w, carried_r2 = d.w;
-                }
-            }
-        }
-        float    t, u, v;
-        uint32_t gid;
-        STAMP(st, 0, true);  // queue entry arrived
-        // The triangle loop is the long, purely arithmetic phase; everything around it (queue reads, shading with its LDS gathers,
-        // the append atomic, the stores) is short and latency-bound.  Raising the wave's priority outside the loop lets those
-        // phases issue ahead of other waves' loops, so more memory operations are in flight per SIMD (closest 18.1 -> 17.5 ms;
-        // the opposite assignment: no gain).
-        uint32_t pair_mask = ~0u;
-        if (C::ORG)
-        {
-            // the tile of this chunk against the pairs' screen bounds: lane k answers for pair k
-            uint32_t tx = 0, ty = 0;
-            (void)local_pixel_to_xy(a.screen, i & ~63u, tx, ty);  // first pixel of the 8x8 tile
-            const float4 b    = lds_bounds[lane < kExhaustiveMax / 2 ? lane : 0u];
-            const bool   over = lane < bvh.fan_pair_count && b.x < (float)(tx + 8u) && b.z >= (float)tx && b.y < (float)(ty + 8u) && b.w >= (float)ty;
-            pair_mask         = (uint32_t)__ballot(over);
-        }
-        __builtin_amdgcn_s_setprio(0);
-#if !defined(CAP_CLOSEST_V1)
-        if constexpr (LDS && !C::ORG)
-        {
-            if (bvh.tri_count > 32u)  // wave-uniform, the same for the whole launch
-                exhaustive_closest_marked<true>(bvh, rec_tab, r, active, t, u, v, gid);
-            else
-                exhaustive_closest_marked<false>(bvh, rec_tab, r, active, t, u, v, gid);
-        }
-        else
-#endif
-            exhaustive_closest<C::ORG, !LDS>(bvh, rec_tab, r, t, u, v, gid, lds_org, pair_mask);
-        __builtin_amdgcn_s_setprio(3);
-        STAMP(st, 1, true);  // triangle loop + winner's record
-        const ShadePre pre = shade_prefetch<C>(a, lds_frames, active, pid, carried_r1, carried_r2, lds_first);
-        if (FIRST && slot == a.aov_slot)
-        {
-            // rt_primary_visibility.hlsl:46: (uv, asfloat(InstanceID), asfloat(PrimitiveIndex)); a miss keeps uv = 0, ids = ~0u
-            float4 g = make_float4(0.f, 0.f, u2f(kInvalidId), u2f(kInvalidId));
-            if (gid != kInvalidId)
-            {
-                const uint4 id = a.scene.tri_ids[gid];
-                g              = make_float4(u, v, u2f(id.x), u2f(id.y));
-            }
-            a.planes.aov_geo[i] = g;
-        }
-        if constexpr (EXT)
-        {
-            if (a.inline_nee)  // wave-uniform
-            {
-                v3 acc = mk3(0.f, 0.f, 0.f);
-                if (!FIRST && active)
-                {
-                    const float4 q = a.in.acc[i];
-                    acc            = mk3(q.x, q.y, q.z);
-                }
-                shade_vertex_ext<FIRST, true>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr, r.d, n_shaded, &bvh, acc, xtabs);
-            }
-            else
-                shade_vertex_ext<FIRST>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr, r.d, n_shaded, nullptr, mk3(0.f, 0.f, 0.f), xtabs);
-        }
-        else
-        {
-            shade_vertex<C>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr, n_shaded, st, probe, &n_probed, ring_head, &ring_n);
-            if (C::PROBE && ring_n >= 64u) trace_ring(64u);
-        }
-        STAMP(st, 4, false);  // stores issued
-    }
-    if (!FIRST && !EXT && !FB) st.flush();
-#ifdef CAP_STAMPS
-    if (!FIRST && !EXT && !FB && (threadIdx.x & 63u) == 0 && wave_global_id() < 16384)
-    {
-        g_wave_times[2 * wave_global_id() + 0] = st.t_begin;
-        g_wave_times[2 * wave_global_id() + 1] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
-    if (C::PROBE && ring_n != 0u) trace_ring(ring_n);  // what is left in this wave's ring
-    flush_stats(a.out.count + (size_t)my_class * kCounterStride, n_shaded, n_probed);
+    using C            = TraceShadeCfg<FIRST, EXT, FB, LDS, TAME, CODE>;
+    constexpr bool TAB = false;
+#include "small_scene_body.h"
+}
+// TAB: reference model, scene in LDS, tame records, the lean plumbing; bounce 0 with and without CODE, and bounce >= 1
+template <bool FIRST, bool CODE>
+__global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, false, false, true, true, CODE, kChunkLean>::kBlocksPerCu)) void k_trace_shade_tab(BvhDev bvh, ShadeArgs a)
+{
+    using C            = TraceShadeCfg<FIRST, false, false, true, true, CODE, kChunkLean>;
+    constexpr bool EXT = false, FB = false, LDS = true, TAB = kChunkLean;
+#include "small_scene_body.h"
 }
 
 #ifdef CAP_STAMPS
@@ -458,9 +253,63 @@ void launch_shade_forms_selftest(hipStream_t stream, unsigned long long* out_dev
     hipLaunchKernelGGL(k_shade_forms_selftest, dim3(4096), dim3(kBlock), 0, stream, out_device, which);
 }
 
-// The thirteen instantiations that exist, each under the tuple it was instantiated with.  Bounce 0 has no feedback form, the two
-// models and feedback exclude each other, TAME is the reference model with the scene in LDS and CODE its bounce 0 (TraceShadeCfg).
-enum : uint32_t { TS_FIRST = 1, TS_EXT = 2, TS_FB = 4, TS_LDS = 8, TS_TAME = 16, TS_CODE = 32 };
+// ---- the table of direction-sample terms (ShadeArgs::sample_terms, the TAB kernels).  A vertex's sample (r1, r2) is the blue-noise
+// texel of (pixel mod 64, count = frame_count * 25 + bounce) and what shading makes of it first -- hemisphere_terms: sincos, two square
+// roots -- depends on nothing else: 4 096 distinct results per (bounce, frame slot) where a batch shades up to a few hundred vertices per
+// entry.  One thread per (sampling bounce b < num_bounces, slot s, yy, xx); entry [b][s][(yy << 6) | xx] = (ca, cb, cos_theta, 0).  The texel,
+// the shift and the terms by the functions the kernels without the table run on the same operands: the same bits.
+__global__ __launch_bounds__(kBlock) void k_sample_terms(const float2* bluenoise, const FrameConst* frames, uint32_t n_slots, uint32_t num_bounces, float4* table)
+{
+    const uint32_t tid = blockIdx.x * kBlock + threadIdx.x, row = tid >> 12, at = tid & 4095u;  // the grid is rows * 4096 / kBlock blocks exactly
+    if (row >= n_slots * num_bounces) return;
+    const uint32_t b = row / n_slots, sl = row - b * n_slots;
+    const uint32_t count = frames[sl].frame_count * 25u + b;
+    float          r1, r2;
+    bluenoise_at(bluenoise, bluenoise_base(at & 63u, at >> 6), bluenoise_offset(count), bluenoise_shift(count), r1, r2);
+    const HemiTerms h = hemisphere_terms(r1, r2);
+    table[tid]        = make_float4(h.ca, h.cb, h.cos_theta, 0.0f);
+}
+
+void launch_sample_terms(hipStream_t stream, const float2* bluenoise, const FrameConst* frames, uint32_t n_slots, uint32_t num_bounces, float4* table)
+{
+    const uint32_t rows = n_slots * num_bounces;  // <= 64 * 255
+    if (!rows) return;
+    hipLaunchKernelGGL(k_sample_terms, dim3(rows * (4096u / kBlock)), dim3(kBlock), 0, stream, bluenoise, frames, n_slots, num_bounces, table);
+}
+
+// cap_debug_get(CAP_DEBUG_SELFTEST_SAMPLE_TABLE): every entry of a table against the sample as the kernels without the table draw it -- by
+// pixel and count (bluenoise4x4) -- and hemisphere_terms of it, bit for bit, the unused word included.  out[0]: mismatches, out[1]: entries.
+__global__ __launch_bounds__(kBlock) void k_sample_terms_selftest(const float2* bluenoise, const FrameConst* frames, uint32_t n_slots, uint32_t num_bounces,
+                                                                  const float4* table, unsigned long long* out)
+{
+    const uint32_t tid = blockIdx.x * kBlock + threadIdx.x, row = tid >> 12, at = tid & 4095u;
+    if (row >= n_slots * num_bounces) return;
+    const uint32_t b = row / n_slots, sl = row - b * n_slots;
+    float          r1, r2;
+    bluenoise4x4(bluenoise, at & 63u, at >> 6, frames[sl].frame_count * 25u + b, r1, r2);
+    const HemiTerms h = hemisphere_terms(r1, r2);
+    const float4    q = table[tid];
+    const bool      bad = f2u(q.x) != f2u(h.ca) || f2u(q.y) != f2u(h.cb) || f2u(q.z) != f2u(h.cos_theta) || f2u(q.w) != 0u;
+    const unsigned long long mb = __ballot(bad), mn = __ballot(true);
+    if ((threadIdx.x & 63u) == 0u)
+    {
+        if (mb) atomicAdd(&out[0], (unsigned long long)__popcll(mb));
+        atomicAdd(&out[1], (unsigned long long)__popcll(mn));
+    }
+}
+
+void launch_sample_terms_selftest(hipStream_t stream, const float2* bluenoise, const FrameConst* frames, uint32_t n_slots, uint32_t num_bounces,
+                                  const float4* table, unsigned long long* out_device)
+{
+    const uint32_t rows = n_slots * num_bounces;
+    if (!rows) return;
+    hipLaunchKernelGGL(k_sample_terms_selftest, dim3(rows * (4096u / kBlock)), dim3(kBlock), 0, stream, bluenoise, frames, n_slots, num_bounces, table, out_device);
+}
+
+// The sixteen instantiations that exist, each under the tuple it was instantiated with.  Bounce 0 has no feedback form, the two
+// models and feedback exclude each other, TAME is the reference model with the scene in LDS, CODE its bounce 0 and TAB its three lean
+// kernels with the sample table (TraceShadeCfg).
+enum : uint32_t { TS_FIRST = 1, TS_EXT = 2, TS_FB = 4, TS_LDS = 8, TS_TAME = 16, TS_CODE = 32, TS_TAB = 64 };
 struct TraceShadeKernel
 {
     uint32_t is;
@@ -469,15 +318,23 @@ struct TraceShadeKernel
 template <uint32_t IS>
 constexpr TraceShadeKernel trace_shade_kernel()
 {
-    return {IS, k_trace_shade<(IS & TS_FIRST) != 0, (IS & TS_EXT) != 0, (IS & TS_FB) != 0, (IS & TS_LDS) != 0, (IS & TS_TAME) != 0, (IS & TS_CODE) != 0>};
+    if constexpr ((IS & TS_TAB) != 0)
+    {
+        static_assert((IS & ~(TS_FIRST | TS_CODE)) == (TS_LDS | TS_TAME | TS_TAB), "TAB: the lean kernels");
+        return {IS, k_trace_shade_tab<(IS & TS_FIRST) != 0, (IS & TS_CODE) != 0>};
+    }
+    else
+        return {IS, k_trace_shade<(IS & TS_FIRST) != 0, (IS & TS_EXT) != 0, (IS & TS_FB) != 0, (IS & TS_LDS) != 0, (IS & TS_TAME) != 0, (IS & TS_CODE) != 0>};
 }
-constexpr TraceShadeKernel kTraceShadeKernels[13] = {
+// (a build without the lean plumbing, -DCAP_CHUNK_PLAIN, has no table form: trace_shade_has_table_form() says so and the last three are never looked up)
+constexpr TraceShadeKernel kTraceShadeKernels[16] = {
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_CODE>(),
     trace_shade_kernel<TS_FIRST | TS_EXT | TS_LDS>(), trace_shade_kernel<TS_FIRST | TS_EXT>(),
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME>(), trace_shade_kernel<TS_FIRST | TS_LDS>(), trace_shade_kernel<TS_FIRST>(),
     trace_shade_kernel<TS_EXT | TS_LDS>(), trace_shade_kernel<TS_EXT>(),
     trace_shade_kernel<TS_FB | TS_LDS>(), trace_shade_kernel<TS_FB>(),
     trace_shade_kernel<TS_LDS | TS_TAME>(), trace_shade_kernel<TS_LDS>(), trace_shade_kernel<0>(),
+    trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_CODE | TS_TAB>(), trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_TAB>(), trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB>(),
 };
 
 // the unscaled forms: reference model, scene in LDS, tame shading records (-DCAP_SHADE_IEEE keeps the plain sqrtf and `/`
@@ -491,6 +348,7 @@ static bool tame_kernels(const BvhDev& bvh, const SceneDev& scene)
 #endif
 }
 bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene) { return tame_kernels(bvh, scene); }
+bool trace_shade_has_table_form(const BvhDev& bvh, const SceneDev& scene) { return kChunkLean && tame_kernels(bvh, scene); }
 
 uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback)
 {
@@ -500,11 +358,15 @@ uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const Shade
     const bool tame  = !ext && !fb && tame_kernels(bvh, args.scene);
     const bool code  = first && args.code_in_color != 0u;
     assert(!code || tame);  // the host's condition for code_in_color: reference model and trace_shade_has_code_form()
-    const uint32_t is = (first ? TS_FIRST : 0u) | (ext ? TS_EXT : 0u) | (fb ? TS_FB : 0u) | (lds ? TS_LDS : 0u) | (tame ? TS_TAME : 0u) | (code ? TS_CODE : 0u);
+    // the sample table: every launch of a batch or none (a queue entry of the other form carries no sample), so the host decides once
+    // per batch, under its own condition -- reference model, no feedback, trace_shade_has_table_form()
+    const bool tab = args.sample_terms != nullptr;
+    assert(!tab || (tame && kChunkLean));
+    const uint32_t is = (first ? TS_FIRST : 0u) | (ext ? TS_EXT : 0u) | (fb ? TS_FB : 0u) | (lds ? TS_LDS : 0u) | (tame ? TS_TAME : 0u) | (code ? TS_CODE : 0u) | (tab ? TS_TAB : 0u);
     // the queue's persistent grid; bounce 0's queue is the identity queue of the batch, one entry per padded pixel and frame slot
     const uint32_t gx = queue_grid(cfg, first ? args.screen.pixels_padded * args.n_slots : args.max_count);
     const TraceShadeKernel* k = kTraceShadeKernels;
-    while (k->is != is && k + 1 < kTraceShadeKernels + 13) ++k;
+    while (k->is != is && k + 1 < kTraceShadeKernels + 16) ++k;
     assert(k->is == is);  // the table holds every tuple the lines above can derive
     hipLaunchKernelGGL(k->kernel, dim3(gx), dim3(kBlock), 0, cfg.stream, bvh, args);
     // the kernel's own conditions: the marked loop where it calls exhaustive_closest_marked, the carry chain where that takes it

@@ -302,6 +302,14 @@ enum
      * without the two-phase loop; 1: by triangle id (one bit word per triangle); 2: by position, one carry-chain step per triangle (dense
      * scenes); 3: the same over two words (33-64 triangles). */
     CAP_DEBUG_MARK_FORM            = 15,
+    /* SAMPLE_TABLE (get): 1 if the fused small-scene launches of the last cap_render took a vertex's direction-sample terms (sin / cos of
+     * the azimuth times sin theta, cos theta: functions of the blue-noise sample alone) from a table built once per batch -- 4 096 entries
+     * per frame slot and sampling bounce -- instead of computing them per vertex; 0 if they computed them (the switch CAP_SAMPLE_TABLE = 0,
+     * the EXT model, feedback, the tree path, untame records, num_bounces 0).  Same bits either way.
+     * SELFTEST_SAMPLE_TABLE (get, after such a render): every entry of the last batch's table against the per-vertex evaluation, on the
+     * device: entries that differ in any bit << 32 | (bounce, frame slot) rows compared, 4 096 entries each. */
+    CAP_DEBUG_SAMPLE_TABLE          = 16,
+    CAP_DEBUG_SELFTEST_SAMPLE_TABLE = 17,
     /* A/B and diagnostic switches of the build and render paths (which kernels trace the camera and the shadow rays, one or two batch
      * lanes, the builders' parameters ...): ONE table per context, key = SWITCH_BASE + cap_debug_switch_index("CAP_..."), the names being
      * the environment variables that fill the table once, at cap_ctx_create (tools set those around a whole process; nothing else in the
