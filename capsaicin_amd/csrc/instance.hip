@@ -4,7 +4,8 @@
 // binary tree each in a forest laid out as the scene's tree), read as object space -- and a table of N instances, each with an
 // object-to-world transform, a mask and the index of the object it shows.  This file holds the per-instance setup (inverse,
 // conditioning, world box: fp64 on the device, so device descriptors never travel to the host), the top-level tree over the world boxes,
-// the two-level query kernels and the relocation of an object's tree into the forest.  Below, "object" is the instance's object:
+// the two-level query kernels (made of four steps, each written once: ray_top_step and ray_enter_instance below, ray_node_step and
+// ray_pop of cap_query_walk.h) and the relocation of an object's tree into the forest.  Below, "object" is the instance's object:
 // without an object table the one object is the scene.
 //
 // Hit set (include/capsaicin_hip.h): defined from the STORED W = fl32(inverse(M)) and the rounded object-space ray
@@ -31,6 +32,7 @@
 #include "cap_hit_list.h"
 #include "cap_kernels.h"
 #include "cap_near.h"
+#include "cap_query_walk.h"
 #include "cap_trace.h"
 
 #include "../../include/capsaicin_hip.h"
@@ -232,14 +234,88 @@ __device__ __forceinline__ bool tlas_slab(const Ray& r, const float4 lo, const f
     return lo.w >= 0.0f && tn <= tf + 4e-7f * fabsf(tf);
 }
 
+// ---- the steps the two instanced ray kernels are made of ----
+// The bottom level is the binary tree's ray_node_step / ray_pop (cap_query_walk.h) on the object-space ray.
+// One top-level node (TopWalk, cap_query_walk.h): tlas_slab on its two children against the caller's far bound, rwb the world ray with
+// the caller's lower bound; then down into the nearer one, or their instances into the queue with their entry distances, or up to the
+// nearest level that owes a child.
+__device__ __forceinline__ TopWalk ray_top_step(const TlasDev& tl, const uint32_t* lds_off, const Ray& rwb, float omax, float tfar, TopWalk t)
+{
+    const float4* c = tl.tlas + 2 * (size_t)(lds_off[t.level - 1u] + 2u * t.idx);
+    const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
+    float         tn0, tn1;
+    const bool    h0 = tlas_slab(rwb, lo0, hi0, omax, tfar, tn0), h1 = tlas_slab(rwb, lo1, hi1, omax, tfar, tn1);
+    const bool    far_first = h0 && h1 && tn1 < tn0;
+    if (t.level > 1u)
+    {
+        if (h0 || h1)
+        {
+            if (h0 && h1) t.pending |= 1u << (t.level - 1u);
+            t.idx   = 2u * t.idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
+            t.level = t.level - 1u;
+            return t;
+        }
+    }
+    else if (h0 || h1)
+    {
+        // the children are instances: the nearer box first
+        const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
+        if (h0 && h1)
+            t.todo0 = far_first ? i1 : i0, t.todo0_d = far_first ? tn1 : tn0, t.todo1 = far_first ? i0 : i1, t.todo1_d = far_first ? tn0 : tn1;
+        else
+            t.todo0 = h0 ? i0 : i1, t.todo0_d = h0 ? tn0 : tn1;
+    }
+    const uint32_t owed = t.pending >> t.level;
+    if (owed == 0u)
+    {
+        t.done = true;
+        return t;
+    }
+    const uint32_t up = (uint32_t)__builtin_ctz(owed);
+    t.idx     = (t.idx >> up) ^ 1u;
+    t.level   = t.level + up;
+    t.pending = t.pending & ~(1u << t.level);
+    return t;
+}
+
+// The object-space ray of the contract in instance `inst`: twelve operations, no fused multiply-add.
+__device__ __forceinline__ void inst_object_ray(const TlasDev& tl, uint32_t inst, const Ray& rw, v3& o, v3& d)
+{
+    const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
+    const v3     r0 = mk3(w0.x, w0.y, w0.z), r1 = mk3(w1.x, w1.y, w1.z), r2 = mk3(w2.x, w2.y, w2.z);
+    o = mk3(dot3(r0, rw.o) + w0.w, dot3(r1, rw.o) + w1.w, dot3(r2, rw.o) + w2.w);
+    d = mk3(dot3(r0, rw.d), dot3(r1, rw.d), dot3(r2, rw.d));
+}
+
+// Entering the instance at the head of the queue, whose box the ray enters at tn: only if tn still passes against the caller's far
+// bound as it is now (the comparison tlas_slab made, with the bound the nearer instance left), the mask lets the instance in (desc.mask
+// & inclusion; the mesh byte joins it per triangle; 0 for an inert one) and the object-space ray is one the walk traces.  The root of
+// the object's tree rides in the record's mask word.  The results go through references into the kernel's own variables.
+__device__ __forceinline__ bool ray_enter_instance(const TlasDev& tl, uint32_t mask, uint32_t inst, float tn, float tfar, const Ray& rw, uint32_t& imask,
+                                                   Ray& r, int& root)
+{
+    if (!(tn <= tfar + 4e-7f * fabsf(tfar))) return false;
+    const float4 w3 = tl.rec[4 * (size_t)inst + 3];
+    imask           = f2u(w3.x) & mask;
+    if (imask == 0u) return false;
+    v3 o, d;
+    inst_object_ray(tl, inst, rw, o, d);
+    if (!query_ray_ok(make_float4(o.x, o.y, o.z, rw.tmin), make_float4(d.x, d.y, d.z, rw.tmax))) return false;
+    r    = make_ray(o, d, rw.tmin, rw.tmax);
+    root = (int)f2u(w3.y);
+    return true;
+}
+
 // Closest (MODE 0) / first accepted (1) / occlusion (2) over the instances, one ray per lane.
 // Top level: no stack.  The tree is implicit, so a node is (level, index), its sibling index ^ 1 and its ancestors index >> levels;
 // `pending` holds one bit per level, set where the walk went to the nearer of two children that both passed and still owes the other.
-// Bottom level: k_query_binary_f's walk of the object's binary tree on the object-space ray of the contract, with the shared best_t;
-// the lane's LDS slice is that walk's stack alone.  The tree's root rides in the instance record's mask word (w3.y): the scene's
-// root in the scene's pools, or the object's in the forest's (bvh.nodes / bvh.tris point at either; bvh.root is not read).
-// One loop, three kinds of step -- a top-level node, entering an instance (the ray transform: 12 FMAs and make_ray's divisions), a
-// bottom-level node or leaf -- so that the lanes of a wave that are at the top level advance while others are inside an instance.
+// Bottom level: k_query_binary_f's walk of the object's binary tree (ray_node_step / ray_pop) on the object-space ray of the contract,
+// with the shared best_t; the lane's LDS slice is that walk's stack alone.  The tree's root rides in the instance record's mask word
+// (w3.y): the scene's root in the scene's pools, or the object's in the forest's (bvh.nodes / bvh.tris point at either; bvh.root is
+// not read).
+// One loop, three kinds of step -- a top-level node (ray_top_step), entering an instance (ray_enter_instance: the ray transform, 12
+// multiply-adds and make_ray's divisions), a bottom-level node or leaf -- so that the lanes of a wave that are at the top level
+// advance while others are inside an instance.
 // The two instances under a level-1 node wait in (todo0, todo1), the nearer box first; each is entered only if its entry distance
 // still passes against best_t as it is then (the comparison tlas_slab made, with the bound the nearer instance left).
 constexpr int inst_blocks(int STACK) { return STACK <= 24 ? 6 : STACK <= 32 ? 4 : 2; }
@@ -260,11 +336,7 @@ __global__ __launch_bounds__(kBlock, inst_blocks(STACK)) void k_query_inst(BvhDe
         float        best_t = b.w, best_u = 0.f, best_v = 0.f;
         uint32_t     best_gid = kInvalidId, best_inst = kInvalidId;
         bool         found = false;  // MODE 1, 2: the query is over
-        // top level: the node whose two children (level - 1, 2 idx + {0, 1}) are tested next
-        uint32_t level = tl.top + 1u, idx = 0u, pending = 0u;
-        bool     top_done = false;
-        uint32_t todo0 = kInvalidId, todo1 = kInvalidId;
-        float    todo0_tn = 0.f, todo1_tn = 0.f;
+        TopWalk      top = top_start(tl);
         // bottom level
         bool     in_blas = false;
         Ray      r       = rw;
@@ -277,23 +349,7 @@ __global__ __launch_bounds__(kBlock, inst_blocks(STACK)) void k_query_inst(BvhDe
             {
                 if (node >= 0)
                 {
-                    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2], q3 = bvh.nodes[4 * node + 3];
-                    float      tn0, tn1;
-                    const bool h0 = slab(r, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, best_t, tn0);
-                    const bool h1 = slab(r, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, best_t, tn1);
-                    const int  c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
-                    if (h0 && h1)
-                    {
-                        const bool swap = tn1 < tn0;
-                        if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)(swap ? c0 : c1);
-                        node = swap ? c1 : c0;
-                        continue;
-                    }
-                    if (h0 || h1)
-                    {
-                        node = h0 ? c0 : c1;
-                        continue;
-                    }
+                    if (ray_node_step<STACK>(bvh, r, best_t, stack, node, sp)) continue;
                 }
                 else
                 {
@@ -314,67 +370,19 @@ __global__ __launch_bounds__(kBlock, inst_blocks(STACK)) void k_query_inst(BvhDe
                     }
                     if (found) break;
                 }
-                if (sp == 0)
-                    in_blas = false;
-                else
-                    node = (int)stack[(--sp) * kBlock];
+                in_blas = ray_pop(stack, sp, node);
                 continue;
             }
-            if (todo0 != kInvalidId)
+            if (top.todo0 != kInvalidId)
             {
-                // enter an instance: mask, then the object-space ray of the contract
-                inst = todo0;
-                const bool still = todo0_tn <= best_t + 4e-7f * fabsf(best_t);  // tlas_slab's comparison against the bound as it is now
-                todo0 = todo1, todo0_tn = todo1_tn, todo1 = kInvalidId;
-                if (!still) continue;
-                const float4 w3 = tl.rec[4 * (size_t)inst + 3];
-                imask           = f2u(w3.x) & f.mask;  // desc.mask & inclusion: the mesh byte joins it per triangle
-                if (imask == 0u) continue;
-                const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
-                const v3     r0 = mk3(w0.x, w0.y, w0.z), r1 = mk3(w1.x, w1.y, w1.z), r2 = mk3(w2.x, w2.y, w2.z);
-                const v3     o  = mk3(dot3(r0, rw.o) + w0.w, dot3(r1, rw.o) + w1.w, dot3(r2, rw.o) + w2.w);
-                const v3     d  = mk3(dot3(r0, rw.d), dot3(r1, rw.d), dot3(r2, rw.d));
-                if (!query_ray_ok(make_float4(o.x, o.y, o.z, rw.tmin), make_float4(d.x, d.y, d.z, rw.tmax))) continue;
-                r       = make_ray(o, d, rw.tmin, rw.tmax);
-                node    = (int)f2u(w3.y), sp = 0;
-                in_blas = true;
+                inst           = top.todo0;
+                const float tn = top.todo0_d;
+                top            = top_pop(top);
+                if (ray_enter_instance(tl, f.mask, inst, tn, best_t, rw, imask, r, node)) sp = 0, in_blas = true;
                 continue;
             }
-            if (top_done) break;
-            const float4* c = tl.tlas + 2 * (size_t)(lds_off[level - 1u] + 2u * idx);
-            const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
-            float         tn0, tn1;
-            const bool    h0 = tlas_slab(rw, lo0, hi0, omax, best_t, tn0), h1 = tlas_slab(rw, lo1, hi1, omax, best_t, tn1);
-            const bool    far_first = h0 && h1 && tn1 < tn0;
-            if (level > 1u)
-            {
-                if (h0 || h1)
-                {
-                    if (h0 && h1) pending |= 1u << (level - 1u);
-                    idx   = 2u * idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
-                    level = level - 1u;
-                    continue;
-                }
-            }
-            else if (h0 || h1)
-            {
-                // the children are instances: the nearer box first
-                const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
-                if (h0 && h1)
-                    todo0 = far_first ? i1 : i0, todo0_tn = far_first ? tn1 : tn0, todo1 = far_first ? i0 : i1, todo1_tn = far_first ? tn0 : tn1;
-                else
-                    todo0 = h0 ? i0 : i1, todo0_tn = h0 ? tn0 : tn1;
-            }
-            const uint32_t owed = pending >> level;
-            if (owed == 0u)
-            {
-                top_done = true;
-                continue;
-            }
-            const uint32_t up = (uint32_t)__builtin_ctz(owed);
-            idx     = (idx >> up) ^ 1u;
-            level   = level + up;
-            pending = pending & ~(1u << level);
+            if (top.done) break;
+            top = ray_top_step(tl, lds_off, rw, omax, best_t, top);
         }
         if (MODE == 2)
             static_cast<uint32_t*>(q.out)[j] = found ? 1u : 0u;
@@ -389,15 +397,6 @@ __global__ __launch_bounds__(kBlock, inst_blocks(STACK)) void k_query_inst(BvhDe
 // ---- multi-hit over the instances (cap_trace_instances_multi) ----
 // A ray's first k pairs in (t, instance, triangle) order, the number of its pairs, or both, in cap_hit_list.h's InstHitList: HitList with
 // the instance between t and the triangle.
-
-// The object-space ray of the contract in instance `inst`: the twelve operations of k_query_inst's entry step, so the same bits.
-__device__ __forceinline__ void inst_object_ray(const TlasDev& tl, uint32_t inst, const Ray& rw, v3& o, v3& d)
-{
-    const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
-    const v3     r0 = mk3(w0.x, w0.y, w0.z), r1 = mk3(w1.x, w1.y, w1.z), r2 = mk3(w2.x, w2.y, w2.z);
-    o = mk3(dot3(r0, rw.o) + w0.w, dot3(r1, rw.o) + w1.w, dot3(r2, rw.o) + w2.w);
-    d = mk3(dot3(r0, rw.d), dot3(r1, rw.d), dot3(r2, rw.d));
-}
 
 // Workgroups per CU: the LDS slice allows inst_blocks(STACK); the list's 3 K registers (and cursor, count, the second lower bound) take
 // it down to the most that leave every instantiation without scratch (tools/kernel_regs.sh; the table is in DESIGN.md): six (80
@@ -448,11 +447,7 @@ __global__ __launch_bounds__(kBlock, inst_multi_blocks(STACK, K)) void k_query_i
         const float lo  = fmaxf(rw.tmin, tc);  // the box tests' lower bound
         Ray         rwb = rw;
         rwb.tmin        = lo;
-        // top level: the node whose two children (level - 1, 2 idx + {0, 1}) are tested next
-        uint32_t level = tl.top + 1u, idx = 0u, pending = 0u;
-        bool     top_done = false;
-        uint32_t todo0 = kInvalidId, todo1 = kInvalidId;
-        float    todo0_tn = 0.f, todo1_tn = 0.f;
+        TopWalk     top = top_start(tl);
         // bottom level: r for the triangles, rb (its tmin = lo) for the boxes
         bool     in_blas = false;
         Ray      r = rw, rb = rwb;
@@ -466,23 +461,7 @@ __global__ __launch_bounds__(kBlock, inst_multi_blocks(STACK, K)) void k_query_i
             {
                 if (node >= 0)
                 {
-                    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2], q3 = bvh.nodes[4 * node + 3];
-                    float      tn0, tn1;
-                    const bool h0 = slab(rb, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, tfar, tn0);
-                    const bool h1 = slab(rb, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, tfar, tn1);
-                    const int  c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
-                    if (h0 && h1)
-                    {
-                        const bool swap = tn1 < tn0;
-                        if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)(swap ? c0 : c1);
-                        node = swap ? c1 : c0;
-                        continue;
-                    }
-                    if (h0 || h1)
-                    {
-                        node = h0 ? c0 : c1;
-                        continue;
-                    }
+                    if (ray_node_step<STACK>(bvh, rb, tfar, stack, node, sp)) continue;
                 }
                 else
                 {
@@ -502,66 +481,19 @@ __global__ __launch_bounds__(kBlock, inst_multi_blocks(STACK, K)) void k_query_i
                         }
                     }
                 }
-                if (sp == 0)
-                    in_blas = false;
-                else
-                    node = (int)stack[(--sp) * kBlock];
+                in_blas = ray_pop(stack, sp, node);
                 continue;
             }
-            if (todo0 != kInvalidId)
+            if (top.todo0 != kInvalidId)
             {
-                // enter an instance: mask, then the object-space ray of the contract
-                inst = todo0;
-                const bool still = todo0_tn <= tfar + 4e-7f * fabsf(tfar);  // tlas_slab's comparison against the bound as it is now
-                todo0 = todo1, todo0_tn = todo1_tn, todo1 = kInvalidId;
-                if (!still) continue;
-                const float4 w3 = tl.rec[4 * (size_t)inst + 3];
-                imask           = f2u(w3.x) & f.mask;  // desc.mask & inclusion: the mesh byte joins it per triangle
-                if (imask == 0u) continue;
-                v3 o, d;
-                inst_object_ray(tl, inst, rw, o, d);
-                if (!query_ray_ok(make_float4(o.x, o.y, o.z, rw.tmin), make_float4(d.x, d.y, d.z, rw.tmax))) continue;
-                r       = make_ray(o, d, rw.tmin, rw.tmax);
-                rb      = r, rb.tmin = lo;
-                node    = (int)f2u(w3.y), sp = 0;
-                in_blas = true;
+                inst           = top.todo0;
+                const float tn = top.todo0_d;
+                top            = top_pop(top);
+                if (ray_enter_instance(tl, f.mask, inst, tn, tfar, rw, imask, r, node)) rb = r, rb.tmin = lo, sp = 0, in_blas = true;
                 continue;
             }
-            if (top_done) break;
-            const float4* c = tl.tlas + 2 * (size_t)(lds_off[level - 1u] + 2u * idx);
-            const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
-            float         tn0, tn1;
-            const bool    h0 = tlas_slab(rwb, lo0, hi0, omax, tfar, tn0), h1 = tlas_slab(rwb, lo1, hi1, omax, tfar, tn1);
-            const bool    far_first = h0 && h1 && tn1 < tn0;
-            if (level > 1u)
-            {
-                if (h0 || h1)
-                {
-                    if (h0 && h1) pending |= 1u << (level - 1u);
-                    idx   = 2u * idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
-                    level = level - 1u;
-                    continue;
-                }
-            }
-            else if (h0 || h1)
-            {
-                // the children are instances: the nearer box first
-                const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
-                if (h0 && h1)
-                    todo0 = far_first ? i1 : i0, todo0_tn = far_first ? tn1 : tn0, todo1 = far_first ? i0 : i1, todo1_tn = far_first ? tn0 : tn1;
-                else
-                    todo0 = h0 ? i0 : i1, todo0_tn = h0 ? tn0 : tn1;
-            }
-            const uint32_t owed = pending >> level;
-            if (owed == 0u)
-            {
-                top_done = true;
-                continue;
-            }
-            const uint32_t up = (uint32_t)__builtin_ctz(owed);
-            idx     = (idx >> up) ^ 1u;
-            level   = level + up;
-            pending = pending & ~(1u << level);
+            if (top.done) break;
+            top = ray_top_step(tl, lds_off, rwb, omax, tfar, top);
         }
         if (COUNT) m.counts[j] = count;
         const int skip = K - (int)m.k;  // the placeholders
@@ -616,15 +548,6 @@ __global__ __launch_bounds__(kBlock) void k_forest_relocate(ForestRelocArgs a)
     }
     a.nodes[4 * (size_t)i + 3] = make_float4(u2f(link[0]), u2f(link[1]), u2f(link[2]), u2f(link[3]));
 }
-
-template <int STACK, int MODE>
-void launch_inst(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const TlasDev& tl, const RayFilter& f, uint32_t* inst_out)
-{
-    uint32_t want = (q.n + kBlock - 1) / kBlock;
-    if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_query_inst<STACK, MODE>), dim3(resident_grid<k_query_inst<STACK, MODE>>(cfg, want)), dim3(kBlock), 0, cfg.stream, bvh, q, tl, f,
-                       inst_out);
-}
 }  // namespace
 
 uint32_t tlas_layout(uint32_t n, uint32_t level_off[kTlasMaxLevels], uint32_t* total)
@@ -678,66 +601,26 @@ void launch_forest_relocate(hipStream_t stream, const ForestRelocArgs& a)
 void launch_query_instances(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const TlasDev& tl, const RayFilter& f, int mode, uint32_t* inst_out,
                             uint32_t depth)
 {
-#define CAP_INST(S)                                                  \
-    if (mode == 2)                                                   \
-        launch_inst<S, 2>(cfg, bvh, q, tl, f, nullptr);              \
-    else if (mode == 1)                                              \
-        launch_inst<S, 1>(cfg, bvh, q, tl, f, inst_out);             \
-    else                                                             \
-        launch_inst<S, 0>(cfg, bvh, q, tl, f, inst_out);
-    // the bottom-level stack: the binary tree's depth bounds it; an instanced object is usually small, and a 24-entry slice lets six
-    // workgroups share a CU's LDS where the 32-entry one of the plain binary kernels lets four
-    if (depth <= 24 && cfg.stack_entries <= 32)
-    {
-        CAP_INST(24)
-    }
-    else if (cfg.stack_entries <= 32)
-    {
-        CAP_INST(32)
-    }
-    else
-    {
-        CAP_INST(64)
-    }
-#undef CAP_INST
-}
-
-template <int STACK, int K, bool COUNT>
-static void launch_inst_multi_k(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, const TlasDev& tl, const RayFilter& f, uint32_t* inst_out)
-{
-    uint32_t want = (m.q.n + kBlock - 1) / kBlock;
-    if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_query_inst_multi<STACK, K, COUNT>), dim3(resident_grid<k_query_inst_multi<STACK, K, COUNT>>(cfg, want)), dim3(kBlock), 0,
-                       cfg.stream, bvh, m, tl, f, inst_out);
-}
-
-template <int STACK>
-static void launch_inst_multi_s(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, const TlasDev& tl, const RayFilter& f, uint32_t* inst_out)
-{
-#define CAP_INST_MULTI(K)                                                     \
-    if (m.counts)                                                             \
-        launch_inst_multi_k<STACK, K, true>(cfg, bvh, m, tl, f, inst_out);    \
-    else                                                                      \
-        launch_inst_multi_k<STACK, K, false>(cfg, bvh, m, tl, f, inst_out);
-    switch (multi_bucket(m.k))
-    {
-    case 1: CAP_INST_MULTI(1) break;
-    case 4: CAP_INST_MULTI(4) break;
-    case 8: CAP_INST_MULTI(8) break;
-    default: CAP_INST_MULTI(16) break;
-    }
-#undef CAP_INST_MULTI
+    with_instance_stack(cfg, depth, [&](auto S) {
+        constexpr int s = decltype(S)::value;
+        if (mode == 2)
+            launch_lanes<k_query_inst<s, 2>>(cfg, q.n, false, bvh, q, tl, f, (uint32_t*)nullptr);
+        else if (mode == 1)
+            launch_lanes<k_query_inst<s, 1>>(cfg, q.n, false, bvh, q, tl, f, inst_out);
+        else
+            launch_lanes<k_query_inst<s, 0>>(cfg, q.n, false, bvh, q, tl, f, inst_out);
+    });
 }
 
 void launch_query_instances_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, const TlasDev& tl, const RayFilter& f, uint32_t* inst_out,
                                   uint32_t depth)
 {
-    // the bottom-level stack as launch_query_instances chooses it
-    if (depth <= 24 && cfg.stack_entries <= 32)
-        launch_inst_multi_s<24>(cfg, bvh, m, tl, f, inst_out);
-    else if (cfg.stack_entries <= 32)
-        launch_inst_multi_s<32>(cfg, bvh, m, tl, f, inst_out);
-    else
-        launch_inst_multi_s<64>(cfg, bvh, m, tl, f, inst_out);
+    with_instance_stack(cfg, depth, [&](auto S) {
+        with_k_bucket(m.k, [&](auto K) {
+            with_flag(m.counts != nullptr, [&](auto COUNT) {
+                launch_lanes<k_query_inst_multi<decltype(S)::value, decltype(K)::value, decltype(COUNT)::value>>(cfg, m.q.n, false, bvh, m, tl, f, inst_out);
+            });
+        });
+    });
 }
 }  // namespace cap

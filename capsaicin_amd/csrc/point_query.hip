@@ -22,11 +22,10 @@
 //
 // The instanced forms (cap_closest_instances, k_closest_inst; cap_closest_instances_multi, k_closest_inst_multi) are at the end of the
 // file: nearest, and the k nearest, in world space over the instance table.
-#include <type_traits>
-
 #include "cap_hit_list.h"
 #include "cap_kernels.h"
 #include "cap_near.h"  // box_dist2, and the bound of the instanced form
+#include "cap_query_walk.h"  // TopWalk, and the launch dispatchers
 
 namespace cap
 {
@@ -136,7 +135,7 @@ constexpr int closest_blocks(int STACK) { return STACK <= 16 ? 5 : STACK <= 24 ?
 // An inner node of a scene or object tree, measured from (px, py, pz): one fetch yields both child boxes; the nearer child that survives
 // the prune is entered and the other one pushed with its box distance.  false: neither survives, the caller pops.  near_skip (cap_near.h)
 // is the strict > of the pruning argument above.  A walk pushes at most one entry per level it descends and STACK is at least the tree's
-// depth (with_stack_class below).
+// depth (with_stack_class, cap_query_walk.h).
 template <int STACK>
 __device__ __forceinline__ bool closest_node_step(const BvhDev& bvh, float px, float py, float pz, float bound2, uint2* stack, int& node, int& sp)
 {
@@ -396,18 +395,6 @@ __device__ __forceinline__ ClosestPoint instance_record(const BvhDev& bvh, const
     return closest_record(w.t0, w.t1, w.t2, p.x, p.y, p.z);
 }
 
-// The top level: the implicit tree without a stack.  This state crosses top_step BY VALUE, in and out: handed over as eight reference
-// parameters it cost every instanced instantiation 20 bytes of scratch (DESIGN.md "Closest-point queries", "One copy of each step").
-struct TopWalk
-{
-    uint32_t level, idx;      // the node whose two children (level - 1, 2 idx + {0, 1}) are tested next
-    uint32_t pending;         // bit l: the other child of the node entered at level l is still owed
-    bool     done;            // nothing is owed any more
-    uint32_t todo0, todo1;    // the two instances under a level-1 node wait here, the nearer first (~0: none) ...
-    float    todo0_d, todo1_d;  // ... with their boxes' distances: each is tested again against the bound as it stands when its turn comes
-};
-__device__ __forceinline__ TopWalk top_start(const TlasDev& tl) { return TopWalk{tl.top + 1u, 0u, 0u, false, kInvalidId, kInvalidId, 0.f, 0.f}; }
-
 // One top-level node: the two children ordered by the squared distance from p to their stored world boxes and pruned against
 // bound2_top; then down into the nearer one, or their instances into the queue, or up to the nearest level that owes a child.
 __device__ __forceinline__ TopWalk top_step(const TlasDev& tl, const uint32_t* lds_off, float px, float py, float pz, float bound2_top, TopWalk t)
@@ -450,13 +437,6 @@ __device__ __forceinline__ TopWalk top_step(const TlasDev& tl, const uint32_t* l
     t.pending = t.pending & ~(1u << t.level);
     return t;
 }
-// the queue without its head
-__device__ __forceinline__ TopWalk top_pop(TopWalk t)
-{
-    t.todo0 = t.todo1, t.todo0_d = t.todo1_d, t.todo1 = kInvalidId;
-    return t;
-}
-
 // Entering an instance: its mask joined with the call's (the mesh byte joins it per triangle), M for the leaves' world records,
 // p' = W p + W_t, which only the pruning sees, (g, slack) of cap_near.h and the root of the object's tree.  The caller maps its bound into
 // object space: near_bound2_object(sqrt of its best or k-th dist2, slack, g).  false: the mask excludes the instance (0 for an inert one);
@@ -714,50 +694,6 @@ __global__ __launch_bounds__(kBlock, closest_inst_multi_blocks(STACK, K)) void k
 }
 
 // ---- launchers ----
-// f(S) with S the smallest stack class that holds `depth` entries, as a std::integral_constant: a walk pushes at most one entry per level
-// it descends
-template <typename F>
-void with_stack_class(uint32_t depth, F&& f)
-{
-    if (depth <= 16)
-        f(std::integral_constant<int, 16>{});
-    else if (depth <= 24)
-        f(std::integral_constant<int, 24>{});
-    else if (depth <= 32)
-        f(std::integral_constant<int, 32>{});
-    else
-        f(std::integral_constant<int, 64>{});
-}
-// f(K) with K the list capacity of pages of k records
-template <typename F>
-void with_k_bucket(uint32_t k, F&& f)
-{
-    switch (multi_bucket(k))
-    {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 8: f(std::integral_constant<int, 8>{}); break;
-    default: f(std::integral_constant<int, 16>{}); break;
-    }
-}
-template <typename F>
-void with_flag(bool on, F&& f)
-{
-    if (on)
-        f(std::true_type{});
-    else
-        f(std::false_type{});
-}
-
-// One lane per point on the grid that is resident at once
-template <auto Kernel, typename... Args>
-void launch_points(const LaunchCfg& cfg, uint32_t n, const Args&... args)
-{
-    uint32_t want = (n + kBlock - 1) / kBlock;
-    if (want == 0) want = 1;
-    hipLaunchKernelGGL(Kernel, dim3(resident_grid<Kernel>(cfg, want)), dim3(kBlock), 0, cfg.stream, args...);
-}
-
 // cap_closest_points and, SIGNED, cap_signed_distance
 template <bool SIGNED>
 void launch_closest(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const SignedArgs& s, const RayFilter* f, uint32_t depth)

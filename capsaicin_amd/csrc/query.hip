@@ -16,8 +16,15 @@
 //     within kQuerySafeScale * M the error is at most eps |1/d| (4 * 4 M + 3 M) = 19 eps M |1/d|, below the padding's 33.5 eps M |1/d|.
 //     A ray whose origin lies beyond is not traced here: its index goes to a list that the binary tree's kernel (kernels.hip
 //     k_query_binary, whose slab test carries its own relative slack) answers right behind this launch.
+//
+// Each step is written once: the feed, the set-up, the load sequence and the tail of the three wide bodies below (closest / first,
+// occlusion, multi-hit) as helpers of this file; the binary tree's node step and pop, and the dispatch from run-time values to
+// instantiations, in cap_query_walk.h, shared with instance.hip and point_query.hip.  Leaf and triangle handling stay in the bodies:
+// what a triangle is offered to is what they differ in.  k_query_binary_multi and k_query_binary_multi_f alone keep their own
+// loops (see there).
 #include "cap_hit_list.h"
 #include "cap_kernels.h"
+#include "cap_query_walk.h"
 #include "cap_wide_trace.h"
 
 namespace cap
@@ -88,17 +95,14 @@ __device__ __forceinline__ void query_refill(QueryFeedState& s, const QueryArgs&
     }
 }
 
-// A lane's ray that the wide walk does not trace: the miss record of a degenerate ray, or the index of a ray for the binary tree.
-// Returns whether the wide walk takes it.
-template <bool ANY>
-__device__ __forceinline__ bool query_admit(const QueryArgs& q, float4 a, float4 b, uint32_t out)
+// A lane's ray that the wide walk does not trace: a degenerate ray, answered by write_miss(), or a ray for the binary tree, whose index
+// goes to the list.  Returns whether the wide walk takes it.
+template <typename Miss>
+__device__ __forceinline__ bool query_admit(const QueryArgs& q, float4 a, float4 b, uint32_t out, Miss write_miss)
 {
     if (!query_ray_ok(a, b))
     {
-        if (ANY)
-            static_cast<uint32_t*>(q.out)[out] = 0u;
-        else
-            static_cast<float4*>(q.out)[out] = make_float4(b.w, 0.f, 0.f, u2f(kInvalidId));
+        write_miss();
         return false;
     }
     if (!query_origin_safe(a, q.safe))
@@ -109,9 +113,95 @@ __device__ __forceinline__ bool query_admit(const QueryArgs& q, float4 a, float4
     return true;
 }
 
+// ---- what the three wide bodies below share ----
+// A lane's state stays in the kernel's own variables and crosses these helpers by reference: gathered into one struct, even with every
+// step written out in the kernel, k_query_closest8 spilled 24 bytes instead of 12 (DESIGN.md "Ray queries", "One copy of each step").
+// With these forms the three plain and the two filtered single-hit kernels compile to the parent's instruction counts.
+// Feed and stack set-up: the first chunk is on its way, every lane idle at the root.
+__device__ __forceinline__ void wide_start(const BvhDev& bvh, const QueryArgs& q, uint32_t& lane, float4*& rbuf, QueryFeedState& s, WideStack<kQueryLds>& st,
+                                           bool& alive, Ray& r, WideRay& w, WideCursor& c)
+{
+    __shared__ uint2  lds_stack[kQueryLds * kBlock];
+    __shared__ float4 lds_rays[2 * kBlock];  // per wave: 64 x (origin, tmin) then 64 x (direction, tmax)
+    lane = threadIdx.x & 63u;
+    rbuf = lds_rays + (threadIdx.x >> 6) * 128u;
+    s    = QueryFeedState{grab_issue(q.work, 0), 0, 0, 0, 0, 0, make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+    query_fetch(s, q, lane);
+    st    = WideStack<kQueryLds>{lds_stack + threadIdx.x, wide_spill_of_thread(bvh), 0};
+    alive = false;
+    r     = make_ray(mk3(0, 0, 0), mk3(0, 0, 1), 0.f, 0.f);
+    w     = make_wide_ray(r.o, r.d);
+    wide_cursor_root(c);
+}
+
+// The ray (a, b) starts at the root
+__device__ __forceinline__ void wide_take(float4 a, float4 b, Ray& r, WideRay& w, WideCursor& c, WideStack<kQueryLds>& st)
+{
+    r = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
+    w = make_wide_ray(r.o, r.d);
+    wide_cursor_root(c);
+    st.sp = 0;
+}
+
+__device__ __forceinline__ bool wide_feed_ended(const QueryFeedState& s) { return s.buf_pos >= s.buf_n && s.pend_n == 0; }
+
+// Pick the source, push the rest, load the record: one load sequence serves node and triangle lanes (see k_trace_closest8).  oct: the
+// visiting order, w.octinv or kAnyOct of it.  TRI48: a triangle lane reads 48 of its record's 64 bytes (the plain occlusion test needs no id).
+template <bool TRI48>
+__device__ __forceinline__ void wide_load(const BvhDev& bvh, uint32_t oct, bool alive, bool tri_lane, bool node_lane, WideCursor& c, WideStack<kQueryLds>& st,
+                                          WideNode& nd)
+{
+    const float4* src = bvh.nodes8;
+    if (tri_lane)
+        src = bvh.tris8 + 4 * (size_t)wide_pick_triangle(c);
+    else if (node_lane)
+    {
+        bool           rest;
+        const uint32_t node = wide_pick_child(c, oct, rest);
+        if (rest) st.push(c.g_base, c.g_mask);
+        src = bvh.nodes8 + (kWideNodeStride / 4u) * (size_t)node;
+    }
+#define CAP_DEF4(v) asm volatile("" : "=v"((v).x), "=v"((v).y), "=v"((v).z), "=v"((v).w))  // (see k_trace_closest8)
+    CAP_DEF4(nd.h0);
+    CAP_DEF4(nd.h1);
+    CAP_DEF4(nd.q2);
+    CAP_DEF4(nd.q3);
+    CAP_DEF4(nd.q4);
+#undef CAP_DEF4
+    if (alive)
+    {
+        nd.h0 = src[0], nd.h1 = src[1], nd.q2 = src[2];
+        if (!TRI48) nd.q3 = src[3];
+    }
+    if (node_lane)
+    {
+        if (TRI48) nd.q3 = src[3];
+        nd.q4 = src[4];
+    }
+}
+
+// The tail: a live lane with neither triangles nor children due takes the next stack entry; with none left write_out() stores its
+// answer and the lane retires.  The write-out is a parameter so that the branches nest as the bodies always had them: with a helper
+// that returns "write now" the list kernels were allocated anew (one more VGPR) and ran up to a quarter faster at K = 16 -- a
+// register-allocation effect that wants a change of its own, DESIGN.md.
+template <typename Write>
+__device__ __forceinline__ void wide_retire_or_pop(bool& alive, WideCursor& c, WideStack<kQueryLds>& st, Write write_out)
+{
+    if (alive && c.t_hits == 0u && (c.g_mask >> 24) == 0u)
+    {
+        if (st.sp == 0)
+        {
+            write_out();
+            alive = false;
+        }
+        else
+            st.pop(c);
+    }
+}
+
 // Ray flags and instance masks (cap_trace_*_ex): every kernel of this file exists in a plain and a filtered (_f) form; the wide ones
-// are made from one body, FILTER a template flag, and the plain kernels are instruction for instruction what they were without it.  The cull sits inside the
-// triangle test (tri_test_cull); the mask byte of a triangle is read only once the triangle has passed that test, and only when the
+// are made from one body, FILTER a template flag, and the plain kernels are instruction for instruction what they were without it.
+// The cull sits inside the triangle test (tri_test_cull); the mask byte of a triangle is read only once the triangle has passed that test, and only when the
 // call filters by mask (wave-uniform branch).  A rejected triangle is as if it were not in the scene: it never reaches best_t, the
 // list or the count, so nothing is pruned by it.
 __device__ __forceinline__ bool filter_admits(const RayFilter& f, uint32_t gid) { return !f.tri_mask || (f.tri_mask[gid] & f.mask) != 0u; }
@@ -131,63 +221,37 @@ __device__ __forceinline__ bool query_tri_test(const Ray& r, const float4 t0, co
 template <bool FILTER, bool FIRST>
 __device__ __forceinline__ void query_closest8(const BvhDev& bvh, const QueryArgs& q, uint32_t refill_idle, const RayFilter& f)
 {
-    __shared__ uint2  lds_stack[kQueryLds * kBlock];
-    __shared__ float4 lds_rays[2 * kBlock];  // per wave: 64 x (origin, tmin) then 64 x (direction, tmax)
-    const uint32_t lane = threadIdx.x & 63u;
-    float4* const  rbuf = lds_rays + (threadIdx.x >> 6) * 128u;
-    float4* const  hits = static_cast<float4*>(q.out);
-    QueryFeedState s{grab_issue(q.work, 0), 0, 0, 0, 0, 0, make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-    query_fetch(s, q, lane);
-
-    WideStack<kQueryLds> st{lds_stack + threadIdx.x, wide_spill_of_thread(bvh), 0};
-    bool              alive = false;
-    Ray               r     = make_ray(mk3(0, 0, 0), mk3(0, 0, 1), 0.f, 0.f);
-    WideRay           w     = make_wide_ray(r.o, r.d);
-    WideCursor        c;
-    wide_cursor_root(c);
+    float4* const        hits = static_cast<float4*>(q.out);
+    uint32_t             lane, out = 0;
+    float4*              rbuf;
+    QueryFeedState       s;
+    WideStack<kQueryLds> st;
+    bool                 alive;
+    Ray                  r;
+    WideRay              w;
+    WideCursor           c;
+    wide_start(bvh, q, lane, rbuf, s, st, alive, r, w, c);
     float    best_t = 0.f, best_u = 0.f, best_v = 0.f;
-    uint32_t best_gid = kInvalidId, out = 0;
+    uint32_t best_gid = kInvalidId;
     while (true)
     {
         unsigned long long m_alive = __ballot(alive);
         if (64u - (uint32_t)__popcll(m_alive) >= refill_idle)
             query_refill(s, q, rbuf, lane, alive, m_alive, [&](float4 a, float4 b, uint32_t i) {
-                if (!query_admit<false>(q, a, b, i)) return false;
-                r      = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
-                w      = make_wide_ray(r.o, r.d);
+                if (!query_admit(q, a, b, i, [&] { hits[i] = make_float4(b.w, 0.f, 0.f, u2f(kInvalidId)); })) return false;
+                wide_take(a, b, r, w, c, st);
+                out = i;
                 best_t = r.tmax, best_u = 0.f, best_v = 0.f, best_gid = kInvalidId;
-                out    = i;
-                wide_cursor_root(c);
-                st.sp = 0;
                 return true;
             });
         if (m_alive == 0ull)
         {
-            if (s.buf_pos >= s.buf_n && s.pend_n == 0) break;  // feed ended and every lane retired
+            if (wide_feed_ended(s)) break;  // feed ended and every lane retired
             continue;
         }
-        // one load sequence serves node and triangle lanes (see k_trace_closest8)
-        const bool    tri_lane = alive && c.t_hits != 0u, node_lane = alive && c.t_hits == 0u;
-        const float4* src      = bvh.nodes8;
-        if (tri_lane)
-            src = bvh.tris8 + 4 * (size_t)wide_pick_triangle(c);
-        else if (node_lane)
-        {
-            bool           rest;
-            const uint32_t node = wide_pick_child(c, w.octinv, rest);
-            if (rest) st.push(c.g_base, c.g_mask);
-            src = bvh.nodes8 + (kWideNodeStride / 4u) * (size_t)node;
-        }
-        WideNode nd;
-#define CAP_DEF4(v) asm volatile("" : "=v"((v).x), "=v"((v).y), "=v"((v).z), "=v"((v).w))  // (see k_trace_closest8)
-        CAP_DEF4(nd.h0);
-        CAP_DEF4(nd.h1);
-        CAP_DEF4(nd.q2);
-        CAP_DEF4(nd.q3);
-        CAP_DEF4(nd.q4);
-#undef CAP_DEF4
-        if (alive) nd.h0 = src[0], nd.h1 = src[1], nd.q2 = src[2], nd.q3 = src[3];
-        if (node_lane) nd.q4 = src[4];
+        const bool tri_lane = alive && c.t_hits != 0u, node_lane = alive && c.t_hits == 0u;
+        WideNode   nd;
+        wide_load<false>(bvh, w.octinv, alive, tri_lane, node_lane, c, st, nd);
         if (tri_lane)
         {
             float t, u, v;
@@ -207,16 +271,7 @@ __device__ __forceinline__ void query_closest8(const BvhDev& bvh, const QueryArg
             }
         }
         if (node_lane) wide_node_test(nd, w, r.tmin, best_t, c);
-        if (alive && c.t_hits == 0u && (c.g_mask >> 24) == 0u)
-        {
-            if (st.sp == 0)
-            {
-                hits[out] = make_float4(best_t, best_u, best_v, u2f(best_gid));
-                alive     = false;
-            }
-            else
-                st.pop(c);
-        }
+        wide_retire_or_pop(alive, c, st, [&] { hits[out] = make_float4(best_t, best_u, best_v, u2f(best_gid)); });
     }
 }
 
@@ -239,61 +294,34 @@ __global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_first8_f(BvhDev
 template <bool FILTER>
 __device__ __forceinline__ void query_any8(const BvhDev& bvh, const QueryArgs& q, uint32_t refill_idle, const RayFilter& f)
 {
-    __shared__ uint2  lds_stack[kQueryLds * kBlock];
-    __shared__ float4 lds_rays[2 * kBlock];
-    const uint32_t  lane = threadIdx.x & 63u;
-    float4* const   rbuf = lds_rays + (threadIdx.x >> 6) * 128u;
-    uint32_t* const occ  = static_cast<uint32_t*>(q.out);
-    QueryFeedState  s{grab_issue(q.work, 0), 0, 0, 0, 0, 0, make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-    query_fetch(s, q, lane);
-
-    WideStack<kQueryLds> st{lds_stack + threadIdx.x, wide_spill_of_thread(bvh), 0};
-    bool              alive = false;
-    Ray               r     = make_ray(mk3(0, 0, 0), mk3(0, 0, 1), 0.f, 0.f);
-    WideRay           w     = make_wide_ray(r.o, r.d);
-    WideCursor        c;
-    wide_cursor_root(c);
-    uint32_t out = 0;
+    uint32_t* const      occ = static_cast<uint32_t*>(q.out);
+    uint32_t             lane, out = 0;
+    float4*              rbuf;
+    QueryFeedState       s;
+    WideStack<kQueryLds> st;
+    bool                 alive;
+    Ray                  r;
+    WideRay              w;
+    WideCursor           c;
+    wide_start(bvh, q, lane, rbuf, s, st, alive, r, w, c);
     while (true)
     {
         unsigned long long m_alive = __ballot(alive);
         if (64u - (uint32_t)__popcll(m_alive) >= refill_idle)
             query_refill(s, q, rbuf, lane, alive, m_alive, [&](float4 a, float4 b, uint32_t i) {
-                if (!query_admit<true>(q, a, b, i)) return false;
-                r   = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
-                w   = make_wide_ray(r.o, r.d);
+                if (!query_admit(q, a, b, i, [&] { occ[i] = 0u; })) return false;
+                wide_take(a, b, r, w, c, st);
                 out = i;
-                wide_cursor_root(c);
-                st.sp = 0;
                 return true;
             });
         if (m_alive == 0ull)
         {
-            if (s.buf_pos >= s.buf_n && s.pend_n == 0) break;
+            if (wide_feed_ended(s)) break;
             continue;
         }
-        const bool    tri_lane = alive && c.t_hits != 0u, node_lane = alive && c.t_hits == 0u;
-        const float4* src      = bvh.nodes8;
-        if (tri_lane)
-            src = bvh.tris8 + 4 * (size_t)wide_pick_triangle(c);
-        else if (node_lane)
-        {
-            bool           rest;
-            const uint32_t node = wide_pick_child(c, kAnyOct(w.octinv), rest);
-            if (rest) st.push(c.g_base, c.g_mask);
-            src = bvh.nodes8 + (kWideNodeStride / 4u) * (size_t)node;
-        }
-        WideNode nd;
-#define CAP_DEF4(v) asm volatile("" : "=v"((v).x), "=v"((v).y), "=v"((v).z), "=v"((v).w))
-        CAP_DEF4(nd.h0);
-        CAP_DEF4(nd.h1);
-        CAP_DEF4(nd.q2);
-        CAP_DEF4(nd.q3);
-        CAP_DEF4(nd.q4);
-#undef CAP_DEF4
-        if (alive) nd.h0 = src[0], nd.h1 = src[1], nd.q2 = src[2];
-        if (FILTER && tri_lane) nd.q3 = src[3];
-        if (node_lane) nd.q3 = src[3], nd.q4 = src[4];  // (a plain occlusion test reads 48 of a triangle record's 64 bytes)
+        const bool tri_lane = alive && c.t_hits != 0u, node_lane = alive && c.t_hits == 0u;
+        WideNode   nd;
+        wide_load<!FILTER>(bvh, kAnyOct(w.octinv), alive, tri_lane, node_lane, c, st, nd);
         bool occluded = false;
         if constexpr (FILTER)
         {
@@ -308,16 +336,8 @@ __device__ __forceinline__ void query_any8(const BvhDev& bvh, const QueryArgs& q
             occ[out] = 1u;
             alive    = false;
         }
-        else if (alive && c.t_hits == 0u && (c.g_mask >> 24) == 0u)
-        {
-            if (st.sp == 0)
-            {
-                occ[out] = 0u;
-                alive    = false;
-            }
-            else
-                st.pop(c);
-        }
+        else
+            wide_retire_or_pop(alive, c, st, [&] { occ[out] = 0u; });
     }
 }
 
@@ -332,28 +352,46 @@ __global__ __launch_bounds__(kBlock, CAP_W8_BLOCKS) void k_query_any8_f(BvhDev b
 
 bool query8_stack_matches() { return (uint32_t)kQueryLds + kSpillEntries / 2u == wide8_stack_pairs(); }
 
-void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any, const RayFilter* f, bool first_hit)
+// ---- launching the wide kernels ----
+// The refill threshold (clamped as trace8.hip w8_refill_idle does)
+static uint32_t query_refill_idle(const LaunchCfg& cfg)
 {
-    uint32_t       g   = (q.n + kBlock - 1) / kBlock;
-    uint32_t       cap = cfg.cu_count ? cfg.cu_count * (uint32_t)CAP_W8_BLOCKS : cfg.grid_blocks;
+    const long v = (long)cfg.sw_get(SW_W8_REFILL, CAP_W8_REFILL);
+    return (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v);
+}
+
+// The persistent grid: one workgroup per kBlock rays, at most per_cu a CU, and no more threads than there are spill slices
+static uint32_t wide_query_grid(const LaunchCfg& cfg, const BvhDev& bvh, uint32_t n, int per_cu)
+{
+    uint32_t g   = (n + kBlock - 1) / kBlock;
+    uint32_t cap = cfg.cu_count ? cfg.cu_count * (uint32_t)per_cu : cfg.grid_blocks;
     if ((uint64_t)cap * kBlock > bvh.spill_threads) cap = bvh.spill_threads / kBlock;  // every thread owns a spill slice
     if (g > cap) g = cap;
-    if (g == 0) g = 1;
-    const long     v      = (long)cfg.sw_get(SW_W8_REFILL, CAP_W8_REFILL);  // (clamped as trace8.hip w8_refill_idle does)
-    const uint32_t refill = (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v);
-    if (f)
+    return g ? g : 1;
+}
+
+// Kernel(bvh, a, refill_idle[, filter]) over the n rays of a
+template <auto Kernel, typename Args, typename... Filter>
+static void launch_wide(const LaunchCfg& cfg, const BvhDev& bvh, int per_cu, const Args& a, uint32_t n, const Filter&... f)
+{
+    hipLaunchKernelGGL(Kernel, dim3(wide_query_grid(cfg, bvh, n, per_cu)), dim3(kBlock), 0, cfg.stream, bvh, a, query_refill_idle(cfg), f...);
+}
+
+void launch_query8(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, bool any, const RayFilter* f, bool first_hit)
+{
+    if (!f)
     {
         if (any)
-            hipLaunchKernelGGL(k_query_any8_f, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill, *f);
-        else if (first_hit)
-            hipLaunchKernelGGL(k_query_first8_f, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill, *f);
+            launch_wide<k_query_any8>(cfg, bvh, CAP_W8_BLOCKS, q, q.n);
         else
-            hipLaunchKernelGGL(k_query_closest8_f, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill, *f);
+            launch_wide<k_query_closest8>(cfg, bvh, CAP_W8_BLOCKS, q, q.n);
     }
     else if (any)
-        hipLaunchKernelGGL(k_query_any8, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill);
+        launch_wide<k_query_any8_f>(cfg, bvh, CAP_W8_BLOCKS, q, q.n, *f);
+    else if (first_hit)
+        launch_wide<k_query_first8_f>(cfg, bvh, CAP_W8_BLOCKS, q, q.n, *f);
     else
-        hipLaunchKernelGGL(k_query_closest8, dim3(g), dim3(kBlock), 0, cfg.stream, bvh, q, refill);
+        launch_wide<k_query_closest8_f>(cfg, bvh, CAP_W8_BLOCKS, q, q.n, *f);
 }
 
 // ---- multi-hit queries (cap_trace_rays_multi) ----
@@ -433,76 +471,42 @@ constexpr int multi8_blocks(int K) { return K <= 1 ? 5 : K <= 4 ? 4 : K <= 8 ? 3
 template <int K, bool COUNT, bool FILTER>
 __device__ __forceinline__ void query_multi8(const BvhDev& bvh, const MultiArgs& m, uint32_t refill_idle, const RayFilter& f)
 {
-    __shared__ uint2  lds_stack[kQueryLds * kBlock];
-    __shared__ float4 lds_rays[2 * kBlock];
-    const QueryArgs& q    = m.q;
-    const uint32_t   lane = threadIdx.x & 63u;
-    float4* const    rbuf = lds_rays + (threadIdx.x >> 6) * 128u;
-    QueryFeedState   s{grab_issue(q.work, 0), 0, 0, 0, 0, 0, make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-    query_fetch(s, q, lane);
-
-    WideStack<kQueryLds> st{lds_stack + threadIdx.x, wide_spill_of_thread(bvh), 0};
-    bool              alive = false;
-    Ray               r     = make_ray(mk3(0, 0, 0), mk3(0, 0, 1), 0.f, 0.f);
-    WideRay           w     = make_wide_ray(r.o, r.d);
-    WideCursor        c;
-    wide_cursor_root(c);
+    const QueryArgs&     q = m.q;
+    uint32_t             lane, out = 0;
+    float4*              rbuf;
+    QueryFeedState       s;
+    WideStack<kQueryLds> st;
+    bool                 alive;
+    Ray                  r;
+    WideRay              w;
+    WideCursor           c;
+    wide_start(bvh, q, lane, rbuf, s, st, alive, r, w, c);
     HitList<K> L;
     L.init(m.k, 0.f);
     float    tc = 0.f, lo = 0.f;
-    uint32_t gc = 0u, count = 0u, out = 0;
+    uint32_t gc = 0u, count = 0u;
     while (true)
     {
         unsigned long long m_alive = __ballot(alive);
         if (64u - (uint32_t)__popcll(m_alive) >= refill_idle)
             query_refill(s, q, rbuf, lane, alive, m_alive, [&](float4 a, float4 b, uint32_t i) {
-                if (!query_ray_ok(a, b))
-                {
-                    multi_write_miss(m, i, b.w);
-                    return false;
-                }
-                if (!query_origin_safe(a, q.safe))
-                {
-                    q.defer[atomicAdd(q.work + kCounterStride, 1u)] = i;
-                    return false;
-                }
-                r = make_ray(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
-                w = make_wide_ray(r.o, r.d);
+                if (!query_admit(q, a, b, i, [&] { multi_write_miss(m, i, b.w); })) return false;
+                wide_take(a, b, r, w, c, st);
+                out = i;
                 L.init(m.k, r.tmax);
                 multi_cursor(m, i, tc, gc);
                 lo    = fmaxf(r.tmin, tc);
                 count = 0u;
-                out   = i;
-                wide_cursor_root(c);
-                st.sp = 0;
                 return true;
             });
         if (m_alive == 0ull)
         {
-            if (s.buf_pos >= s.buf_n && s.pend_n == 0) break;
+            if (wide_feed_ended(s)) break;
             continue;
         }
-        const bool    tri_lane = alive && c.t_hits != 0u, node_lane = alive && c.t_hits == 0u;
-        const float4* src      = bvh.nodes8;
-        if (tri_lane)
-            src = bvh.tris8 + 4 * (size_t)wide_pick_triangle(c);
-        else if (node_lane)
-        {
-            bool           rest;
-            const uint32_t node = wide_pick_child(c, w.octinv, rest);
-            if (rest) st.push(c.g_base, c.g_mask);
-            src = bvh.nodes8 + (kWideNodeStride / 4u) * (size_t)node;
-        }
-        WideNode nd;
-#define CAP_DEF4(v) asm volatile("" : "=v"((v).x), "=v"((v).y), "=v"((v).z), "=v"((v).w))  // (see k_trace_closest8)
-        CAP_DEF4(nd.h0);
-        CAP_DEF4(nd.h1);
-        CAP_DEF4(nd.q2);
-        CAP_DEF4(nd.q3);
-        CAP_DEF4(nd.q4);
-#undef CAP_DEF4
-        if (alive) nd.h0 = src[0], nd.h1 = src[1], nd.q2 = src[2], nd.q3 = src[3];
-        if (node_lane) nd.q4 = src[4];
+        const bool tri_lane = alive && c.t_hits != 0u, node_lane = alive && c.t_hits == 0u;
+        WideNode   nd;
+        wide_load<false>(bvh, w.octinv, alive, tri_lane, node_lane, c, st, nd);
         if (tri_lane)
         {
             float t, u, v;
@@ -510,16 +514,7 @@ __device__ __forceinline__ void query_multi8(const BvhDev& bvh, const MultiArgs&
                 multi_offer<K, COUNT>(L, count, tc, gc, t, f2u(nd.q3.x));
         }
         if (node_lane) wide_node_test(nd, w, lo, COUNT ? r.tmax : L.t[K - 1], c);
-        if (alive && c.t_hits == 0u && (c.g_mask >> 24) == 0u)
-        {
-            if (st.sp == 0)
-            {
-                multi_write<K, COUNT>(m, bvh, out, r, L, count);
-                alive = false;
-            }
-            else
-                st.pop(c);
-        }
+        wide_retire_or_pop(alive, c, st, [&] { multi_write<K, COUNT>(m, bvh, out, r, L, count); });
     }
 }
 
@@ -537,6 +532,11 @@ __global__ __launch_bounds__(kBlock, multi8_blocks(K)) void k_query_multi8_f(Bvh
 // Multi-hit on the binary tree, one lane per ray: traverse_closest's loop (kernels.hip) with the list; every ray where the wide view
 // is not used, and the rays k_query_multi8 handed over.  Workgroups per CU as the binary query kernels (stack_residency: 4 with
 // 32-entry stacks, 2 with 64), except K = 16 on 32 entries: 3, for the registers.
+// These two kernels keep the node step and the pop written out, and stay two: their code is a knife-edge of the compiler.  Any other
+// spelling -- ray_node_step, ray_pop alone in place of the two pop lines, the step's arguments by value, one body with a FILTER
+// flag -- yields one and the same other allocation (K = 16: 113 VGPRs instead of 136, so four workgroups per CU instead of three)
+// and schedule: measured on the hall without the wide view, K = 16 ran 0.68-0.72 of the parent's time, K = 1 1.07-1.19 and counts
+// 1.04-1.13 on the incoherent ray sets.  A refactor takes neither (DESIGN.md "Ray queries", "One copy of each step").
 constexpr int multi_binary_blocks(int STACK, int K) { return STACK <= 32 ? (K <= 8 ? 4 : 3) : 2; }
 
 template <int STACK, int K, bool COUNT>
@@ -605,8 +605,8 @@ __global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, K)) void k_query
     }
 }
 
-// k_query_binary_multi under a filter (cap_trace_rays_multi_ex).  A kernel of its own rather than a second instantiation of one body:
-// here, unlike in the wide kernels, wrapping the loop in a shared function changed the plain kernel's instruction schedule.
+// k_query_binary_multi under a filter (cap_trace_rays_multi_ex): the same loop with tri_test_cull and the mask in the leaf.  A kernel
+// of its own rather than a second instantiation of one body, for the reason above.
 template <int STACK, int K, bool COUNT>
 __global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, K)) void k_query_binary_multi_f(BvhDev bvh, MultiArgs m, uint32_t deferred, RayFilter f)
 {
@@ -677,7 +677,7 @@ __global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, K)) void k_query
 
 // Closest / first / occlusion on the binary tree under a filter, one lane per ray: k_query_binary's place (kernels.hip) for the _ex
 // calls -- every ray where the wide view is not used, and the rays the filtered wide kernels handed over.  The loop is
-// traverse_closest's with tri_test_cull and the mask in front of the best record.  MODE 0: closest; 1: first accepted hit ends the
+// traverse_closest's over ray_node_step / ray_pop (cap_query_walk.h), with tri_test_cull and the mask in front of the best record.  MODE 0: closest; 1: first accepted hit ends the
 // walk; 2: occlusion (tri_occludes_cull, the division-free interval; the visiting order does not change the answer).
 template <int STACK, int MODE>
 __global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, 1)) void k_query_binary_f(BvhDev bvh, QueryArgs q, uint32_t deferred, RayFilter f)
@@ -699,24 +699,7 @@ __global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, 1)) void k_query
         {
             if (node >= 0)
             {
-                const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2],
-                             q3 = bvh.nodes[4 * node + 3];
-                float      tn0, tn1;
-                const bool h0 = slab(r, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, best_t, tn0);
-                const bool h1 = slab(r, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, best_t, tn1);
-                const int  c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
-                if (h0 && h1)
-                {
-                    const bool swap = tn1 < tn0;
-                    if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)(swap ? c0 : c1);
-                    node = swap ? c1 : c0;
-                    continue;
-                }
-                if (h0 || h1)
-                {
-                    node = h0 ? c0 : c1;
-                    continue;
-                }
+                if (ray_node_step<STACK>(bvh, r, best_t, stack, node, sp)) continue;
             }
             else
             {
@@ -737,8 +720,7 @@ __global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, 1)) void k_query
                 }
                 if (found) break;
             }
-            if (sp == 0) break;
-            node = (int)stack[(--sp) * kBlock];
+            if (!ray_pop(stack, sp, node)) break;
         }
         if (MODE == 2)
             static_cast<uint32_t*>(q.out)[i] = found ? 1u : 0u;
@@ -749,111 +731,51 @@ __global__ __launch_bounds__(kBlock, multi_binary_blocks(STACK, 1)) void k_query
 
 uint32_t multi_bucket(uint32_t k) { return k <= 1 ? 1u : k <= 4 ? 4u : k <= 8 ? 8u : 16u; }
 
-template <int K, bool COUNT>
-static void launch_multi8_k(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, uint32_t refill, const RayFilter* f)
-{
-    uint32_t g   = (m.q.n + kBlock - 1) / kBlock;
-    uint32_t cap = cfg.cu_count ? cfg.cu_count * (uint32_t)multi8_blocks(K) : cfg.grid_blocks;
-    if ((uint64_t)cap * kBlock > bvh.spill_threads) cap = bvh.spill_threads / kBlock;  // every thread owns a spill slice
-    if (g > cap) g = cap;
-    if (g == 0) g = 1;
-    if (f)
-        hipLaunchKernelGGL((k_query_multi8_f<K, COUNT>), dim3(g), dim3(kBlock), 0, cfg.stream, bvh, m, refill, *f);
-    else
-        hipLaunchKernelGGL((k_query_multi8<K, COUNT>), dim3(g), dim3(kBlock), 0, cfg.stream, bvh, m, refill);
-}
-
 void launch_query8_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, const RayFilter* f)
 {
-    const long     v      = (long)cfg.sw_get(SW_W8_REFILL, CAP_W8_REFILL);
-    const uint32_t refill = (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v);
-#define CAP_MULTI8(K)                                                         \
-    if (m.counts)                                                             \
-        launch_multi8_k<K, true>(cfg, bvh, m, refill, f);                     \
-    else                                                                      \
-        launch_multi8_k<K, false>(cfg, bvh, m, refill, f);
-    switch (multi_bucket(m.k))
-    {
-    case 1: CAP_MULTI8(1) break;
-    case 4: CAP_MULTI8(4) break;
-    case 8: CAP_MULTI8(8) break;
-    default: CAP_MULTI8(16) break;
-    }
-#undef CAP_MULTI8
+    with_k_bucket(m.k, [&](auto K) {
+        with_flag(m.counts != nullptr, [&](auto COUNT) {
+            constexpr int  k = decltype(K)::value;
+            constexpr bool c = decltype(COUNT)::value;
+            if (f)
+                launch_wide<k_query_multi8_f<k, c>>(cfg, bvh, multi8_blocks(k), m, m.q.n, *f);
+            else
+                launch_wide<k_query_multi8<k, c>>(cfg, bvh, multi8_blocks(k), m, m.q.n);
+        });
+    });
 }
 
-template <int STACK, int K, bool COUNT>
-static void launch_binary_multi_k(const LaunchCfg& cfg, const BvhDev& b, const MultiArgs& m, bool deferred, const RayFilter* f)
-{
-    uint32_t want = (m.q.n + kBlock - 1) / kBlock;
-    // (deferred: the count is on the device and is normally small -- one workgroup per CU at most)
-    if (deferred && cfg.cu_count && want > cfg.cu_count) want = cfg.cu_count;
-    if (want == 0) want = 1;
-    if (f)
-        hipLaunchKernelGGL((k_query_binary_multi_f<STACK, K, COUNT>), dim3(resident_grid<k_query_binary_multi_f<STACK, K, COUNT>>(cfg, want)),
-                           dim3(kBlock), 0, cfg.stream, b, m, deferred ? 1u : 0u, *f);
-    else
-        hipLaunchKernelGGL((k_query_binary_multi<STACK, K, COUNT>), dim3(resident_grid<k_query_binary_multi<STACK, K, COUNT>>(cfg, want)),
-                           dim3(kBlock), 0, cfg.stream, b, m, deferred ? 1u : 0u);
-}
-
-template <int STACK>
-static void launch_binary_multi_s(const LaunchCfg& cfg, const BvhDev& b, const MultiArgs& m, bool deferred, const RayFilter* f)
-{
-#define CAP_MULTI_BIN(K)                                                      \
-    if (m.counts)                                                             \
-        launch_binary_multi_k<STACK, K, true>(cfg, b, m, deferred, f);        \
-    else                                                                      \
-        launch_binary_multi_k<STACK, K, false>(cfg, b, m, deferred, f);
-    switch (multi_bucket(m.k))
-    {
-    case 1: CAP_MULTI_BIN(1) break;
-    case 4: CAP_MULTI_BIN(4) break;
-    case 8: CAP_MULTI_BIN(8) break;
-    default: CAP_MULTI_BIN(16) break;
-    }
-#undef CAP_MULTI_BIN
-}
-
+// The binary kernels, one lane per ray (launch_lanes: `deferred` caps the grid of a handed-over list)
 void launch_query_binary_multi(const LaunchCfg& cfg, const BvhDev& bvh, const MultiArgs& m, bool deferred, const RayFilter* f)
 {
     BvhDev b   = bvh;
     b.wide8_ok = 0;
-    if (cfg.stack_entries <= 32)
-        launch_binary_multi_s<32>(cfg, b, m, deferred, f);
-    else
-        launch_binary_multi_s<64>(cfg, b, m, deferred, f);
-}
-
-template <int STACK, int MODE>
-static void launch_binary_f(const LaunchCfg& cfg, const BvhDev& b, const QueryArgs& q, const RayFilter& f, bool deferred)
-{
-    uint32_t want = (q.n + kBlock - 1) / kBlock;
-    if (deferred && cfg.cu_count && want > cfg.cu_count) want = cfg.cu_count;  // (as launch_query_binary)
-    if (want == 0) want = 1;
-    hipLaunchKernelGGL((k_query_binary_f<STACK, MODE>), dim3(resident_grid<k_query_binary_f<STACK, MODE>>(cfg, want)), dim3(kBlock), 0, cfg.stream,
-                       b, q, deferred ? 1u : 0u, f);
+    with_binary_stack(cfg, [&](auto S) {
+        with_k_bucket(m.k, [&](auto K) {
+            with_flag(m.counts != nullptr, [&](auto COUNT) {
+                constexpr int  s = decltype(S)::value, k = decltype(K)::value;
+                constexpr bool c = decltype(COUNT)::value;
+                if (f)
+                    launch_lanes<k_query_binary_multi_f<s, k, c>>(cfg, m.q.n, deferred, b, m, deferred ? 1u : 0u, *f);
+                else
+                    launch_lanes<k_query_binary_multi<s, k, c>>(cfg, m.q.n, deferred, b, m, deferred ? 1u : 0u);
+            });
+        });
+    });
 }
 
 void launch_query_binary_filtered(const LaunchCfg& cfg, const BvhDev& bvh, const QueryArgs& q, const RayFilter& f, bool any, bool first_hit, bool deferred)
 {
     BvhDev b   = bvh;
     b.wide8_ok = 0;
-#define CAP_BIN_F(S)                                               \
-    if (any)                                                       \
-        launch_binary_f<S, 2>(cfg, b, q, f, deferred);             \
-    else if (first_hit)                                            \
-        launch_binary_f<S, 1>(cfg, b, q, f, deferred);             \
-    else                                                           \
-        launch_binary_f<S, 0>(cfg, b, q, f, deferred);
-    if (cfg.stack_entries <= 32)
-    {
-        CAP_BIN_F(32)
-    }
-    else
-    {
-        CAP_BIN_F(64)
-    }
-#undef CAP_BIN_F
+    with_binary_stack(cfg, [&](auto S) {
+        constexpr int s = decltype(S)::value;
+        if (any)
+            launch_lanes<k_query_binary_f<s, 2>>(cfg, q.n, deferred, b, q, deferred ? 1u : 0u, f);
+        else if (first_hit)
+            launch_lanes<k_query_binary_f<s, 1>>(cfg, q.n, deferred, b, q, deferred ? 1u : 0u, f);
+        else
+            launch_lanes<k_query_binary_f<s, 0>>(cfg, q.n, deferred, b, q, deferred ? 1u : 0u, f);
+    });
 }
 }  // namespace cap
