@@ -287,6 +287,7 @@ SYMBOLS = {
     "cap_pseudonormals_readback": (_i, [_vp, _vp]),
     "cap_signed_distance": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
+    "cap_signed_distance_instances": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_assemble_tiles": (_i, [_vp, _vp, _u32, _vp]),
     "cap_post_settings_default": (None, [C.POINTER(PostSettings)]),
@@ -825,13 +826,14 @@ class Renderer:
         return res
 
     def _closest_single(self, name, points, out, sync, mask, second=None):
-        """One record per point through the entry point `name`; second=<dtype>: it also fills an (N,) array of that type"""
+        """One record per point through the entry point `name`; second=<dtype>, or a tuple of them: it also fills an (N,) array of
+        each type, in the entry point's order"""
         import torch
         host = isinstance(points, np.ndarray)
         sync = sync or host  # the result is read back to the host
         dev, points, n = self._stage_points(points)
         out, host_out = self._records_out(out, n, dev)
-        extra = [] if second is None else [torch.empty((n,), dtype=second, device=dev)]
+        extra = [torch.empty((n,), dtype=t, device=dev) for t in (() if second is None else second if isinstance(second, tuple) else (second,))]
         if sync:
             torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
         options = self.trace_options(None, mask)
@@ -881,6 +883,15 @@ class Renderer:
         closest_points; numpy points give numpy results."""
         import torch
         return self._closest_single("cap_closest_instances", points, out, sync, mask, torch.int32)
+
+    def signed_distance_instances(self, points, out=None, sync=True, mask=None):
+        """closest_instances with the signed distance (cap_signed_distance_instances): (records (N, 8) float32, instances (N,) int32,
+        -1 on a miss, signed (N,) float32).  Records and instances are closest_instances', bit for bit; signed is the WORLD distance
+        sqrt(dist2), negative where the point's object-space image W p lies behind the pseudonormal of the feature nearest to it on
+        the winning instance's object, +inf on a miss.  Needs set_instances() and build_pseudonormals().  points, out, sync and mask=
+        as closest_instances; numpy points give numpy results."""
+        import torch
+        return self._closest_single("cap_signed_distance_instances", points, out, sync, mask, (torch.int32, torch.float32))
 
     def closest_points_multi(self, points, k, counts=False, resume=None, sync=True, mask=None):
         """The k triangles nearest to each point within its radius, in (dist2, triangle) order (cap_closest_points_multi): (N, k, 8)

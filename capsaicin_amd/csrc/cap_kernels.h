@@ -214,6 +214,11 @@ struct ClosestInstArgs
     const uint32_t* xw_max;
 };
 void launch_closest_instances(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstArgs& a, const TlasDev& tl, const RayFilter& f, uint32_t depth);
+// cap_signed_distance_instances (point_query.hip k_closest_inst<.., true>): launch_closest_instances, and s.signed_out[j] = the world
+// distance of the record, negative where the flat signed query at p' = W p over the winning instance's candidates says so (s.normals: the
+// scene's pseudonormal table).  a.a.slack is READ here: the scene's flat slack (kClosestSlackScale), which bounds the object-space walk.
+void launch_signed_distance_instances(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstArgs& a, const SignedArgs& s, const TlasDev& tl,
+                                      const RayFilter& f, uint32_t depth);
 // The k nearest and in-radius form over the instance table (cap_closest_instances_multi, point_query.hip k_closest_inst_multi): ia.a.out
 // = pages of k CapClosest records per point and ia.inst_out = pages of k instances (both NULL when k = 0); counts, resume and the list
 // capacity as ClosestMultiArgs' -- the cursor is slot k - 1 of both pages.

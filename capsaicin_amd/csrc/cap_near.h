@@ -123,7 +123,10 @@ __host__ __device__ __forceinline__ float near_bound2_object(float sqrt_best, fl
     return (b * b) * (1.0f + 4.0f * kNearEps);
 }
 
-// p' = W p + W_t, rows w0 .. w2 of the stored W: where the bottom-level boxes are measured from (not part of the contract)
+// p' = W p + W_t, rows w0 .. w2 of the stored W: where the bottom-level boxes are measured from.  Part of the contract of
+// cap_signed_distance_instances (include/capsaicin_hip.h), which reads its sign at p': per row
+//   p'_r = fl(fl(fl(fl(W_r0 p.x) + fl(W_r1 p.y)) + fl(W_r2 p.z)) + W_r3),
+// single rounded binary32 operations in this order, no fused multiply-add.  Do not reorder.
 __host__ __device__ __forceinline__ void near_to_object(const float w[12], float px, float py, float pz, float& ox, float& oy, float& oz)
 {
     ox = ((w[0] * px + w[1] * py) + w[2] * pz) + w[3];

@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi; point_query.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -277,11 +277,11 @@ int trace_instances_multi(CapContext* c, const char* what, const CapRayDesc* ray
     });
 }
 
-// What one of the five closest-point entry points is, beside the points and the record array every one of them has: its further arrays
+// What one of the six closest-point entry points is, beside the points and the record array every one of them has: its further arrays
 // and its page rules.  One record per point (k = 1) unless multi.
 struct PointCall
 {
-    bool      with_sign  = false;    // cap_signed_distance: the pseudonormal table is part of the state ...
+    bool      with_sign  = false;    // cap_signed_distance*: the pseudonormal table is part of the state ...
     float*    signed_out = nullptr;  // ... and the signed array a third range
     bool      instanced  = false;    // cap_closest_instances*: trace_instances' state and pools ...
     uint32_t* inst       = nullptr;  // ... and the instance array, one entry per record (may be left out unless multi)
@@ -296,9 +296,8 @@ PointCall with_sign(float* signed_out)
     q.with_sign = true, q.signed_out = signed_out;
     return q;
 }
-PointCall over_instances(uint32_t* inst)
+PointCall over_instances(uint32_t* inst, PointCall q = PointCall{})
 {
-    PointCall q;
     q.instanced = true, q.inst = inst;
     return q;
 }
@@ -337,8 +336,8 @@ int closest_query(CapContext* c, const char* what, const CapPointDesc* points, u
     const uint32_t   resume = (q.flags & CAP_MULTI_CONTINUE) ? 1u : 0u;
     const bool       single = q.k == 1 && !q.counts && !resume;
     return for_each_chunk(run, points, n, [&](const QueryArgs& chunk, uint64_t first) {
-        // (the instanced kernels take their slack per point and instance: cap_near.h)
-        const ClosestArgs a{chunk.rays, chunk.n, reinterpret_cast<float4*>(at(out, first * q.k)), q.instanced ? 0.f : run.slack};
+        // (the instanced kernels take their slack per point and instance: cap_near.h; the signed one's object-space walk takes the scene's)
+        const ClosestArgs a{chunk.rays, chunk.n, reinterpret_cast<float4*>(at(out, first * q.k)), q.instanced && !q.with_sign ? 0.f : run.slack};
         uint32_t* const   counts = at(q.counts, first);
         if (!q.instanced)
         {
@@ -356,6 +355,11 @@ int closest_query(CapContext* c, const char* what, const CapPointDesc* points, u
             return run.traced("k_closest_points_multi", first);
         }
         const ClosestInstArgs ia{a, at(q.inst, first * q.k), c->inst_desc.p, c->inst_near.p, c->inst_misc.p + 7};
+        if (q.with_sign)
+        {
+            launch_signed_distance_instances(run.cfg, run.bvh, ia, SignedArgs{c->pn_table.p, q.signed_out + first}, run.tl, flt.f, run.depth);
+            return run.traced("k_closest_inst<signed>", first);
+        }
         if (single)
         {
             launch_closest_instances(run.cfg, run.bvh, ia, run.tl, flt.f, run.depth);
@@ -439,6 +443,12 @@ int cap_closest_instances(CapContext* c, const CapPointDesc* device_points, uint
                           const CapTraceOptions* options)
 {
     return closest_query(c, "cap_closest_instances", device_points, n, device_out, over_instances(device_instances), options);
+}
+
+int cap_signed_distance_instances(CapContext* c, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, uint32_t* device_instances,
+                                  float* device_signed, const CapTraceOptions* options)
+{
+    return closest_query(c, "cap_signed_distance_instances", device_points, n, device_out, over_instances(device_instances, with_sign(device_signed)), options);
 }
 
 int cap_closest_instances_multi(CapContext* c, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out,

@@ -21,7 +21,8 @@
 // in the place of the single best pair; "best" above reads "k-th best", slot K - 1 of the list.
 //
 // The instanced forms (cap_closest_instances, k_closest_inst; cap_closest_instances_multi, k_closest_inst_multi) are at the end of the
-// file: nearest, and the k nearest, in world space over the instance table.
+// file: nearest, and the k nearest, in world space over the instance table.  cap_signed_distance_instances is k_closest_inst with
+// SIGNED: the world record, and the sign from a flat walk of the winning instance's object tree at p' = W p.
 #include "cap_hit_list.h"
 #include "cap_kernels.h"
 #include "cap_near.h"  // box_dist2, and the bound of the instanced form
@@ -174,6 +175,29 @@ __device__ __forceinline__ bool closest_pop(uint2* stack, int& sp, float bound2,
     return false;
 }
 
+// A leaf of a scene or object tree for the single nearest triangle in (dist2, triangle) order, measured from (px, py, pz) on the stored
+// records: the flat query's leaf, and the second phase of the signed instanced one (k_closest_inst), which walks an object's tree from
+// p'.  FILTER: tri_mask by global id against `mask`, read before the cascade.  A NaN dist2 fails both comparisons.
+template <bool FILTER>
+__device__ __forceinline__ void closest_leaf_step(const BvhDev& bvh, int node, const uint8_t* tri_mask, uint32_t mask, float slack, float px, float py,
+                                                  float pz, float& best, uint32_t& best_gid, float& bound2)
+{
+    const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+    for (uint32_t leaf = first; leaf <= last; ++leaf)
+    {
+        const uint32_t gid = f2u(bvh.tris[4 * (size_t)leaf + 3].x);
+        if constexpr (FILTER)
+            if ((tri_mask[gid] & mask) == 0u) continue;
+        const float4 t0 = bvh.tris[4 * (size_t)leaf + 0], t1 = bvh.tris[4 * (size_t)leaf + 1], t2 = bvh.tris[4 * (size_t)leaf + 2];
+        const float  d2 = closest_dist2(t0, t1, t2, px, py, pz);
+        if (d2 < best || (d2 == best && gid < best_gid))
+        {
+            if (d2 < best) bound2 = prune_bound2(d2, slack);
+            best = d2, best_gid = gid;
+        }
+    }
+}
+
 // A record slot without a triangle: dist2 = r2, the point's squared radius (0 for a point that was not traversed)
 __device__ __forceinline__ void write_miss(float4* slot, float r2)
 {
@@ -224,20 +248,7 @@ __global__ __launch_bounds__(kBlock, closest_blocks(STACK)) void k_closest_point
             }
             else
             {
-                const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
-                for (uint32_t leaf = first; leaf <= last; ++leaf)
-                {
-                    const uint32_t gid = f2u(bvh.tris[4 * (size_t)leaf + 3].x);
-                    if constexpr (FILTER)
-                        if ((f.tri_mask[gid] & f.mask) == 0u) continue;
-                    const float4 t0 = bvh.tris[4 * (size_t)leaf + 0], t1 = bvh.tris[4 * (size_t)leaf + 1], t2 = bvh.tris[4 * (size_t)leaf + 2];
-                    const float  d2 = closest_dist2(t0, t1, t2, p.x, p.y, p.z);
-                    if (d2 < best || (d2 == best && gid < best_gid))
-                    {
-                        if (d2 < best) bound2 = prune_bound2(d2, a.slack);
-                        best = d2, best_gid = gid;
-                    }
-                }
+                closest_leaf_step<FILTER>(bvh, node, f.tri_mask, f.mask, a.slack, p.x, p.y, p.z, best, best_gid, bound2);
             }
             if (!closest_pop(stack, sp, bound2, node)) break;
         }
@@ -463,9 +474,51 @@ __device__ __forceinline__ bool enter_instance(const TlasDev& tl, const ClosestI
 // Workgroups per CU: the stack's LDS (and the 104 bytes of level offsets, which take the fifth workgroup of STACK = 16 away)
 constexpr int closest_inst_blocks(int STACK) { return STACK <= 16 ? 4 : STACK <= 24 ? 3 : STACK <= 32 ? 2 : 1; }
 
-// FILTER: a mesh-mask table is installed (f.tri_mask by global id); the instance's own mask is tested either way
+// The sign of cap_signed_distance_instances for a point whose world winner is (inst, gid): the flat signed query at p' = W p over the
+// instance's own candidates, radius +inf -- inside and outside are the same in object space, whatever the transform (a mirror
+// included), and object space is where the pseudonormal table lives.  The walk is k_closest_points' on the object's tree from p', with
+// the flat bound prune_bound2(best', slack) and the scene's slack (DESIGN.md "Signed distance over instances"); best' is seeded with
+// the world winner's own triangle at p', a candidate by construction, so the walk starts with a tight bound and the winner under the
+// tie rule (dist2', triangle) is what it would be without the seed.  true: d = dot_c(delta', N[g'][feature']) < 0.  An overflowed p'
+// or no candidate with a dist2' that is not NaN: false.
 template <int STACK, bool FILTER>
-__global__ __launch_bounds__(kBlock, closest_inst_blocks(STACK)) void k_closest_inst(BvhDev bvh, ClosestInstArgs ia, TlasDev tl, RayFilter f)
+__device__ __forceinline__ bool object_sign_negative(const BvhDev& bvh, const TlasDev& tl, const RayFilter& f, const float* normals, float slack,
+                                                     uint32_t inst, uint32_t gid, const float4 p, uint2* stack)
+{
+    const float4   w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2], w3 = tl.rec[4 * (size_t)inst + 3];
+    const uint32_t imask = f2u(w3.x) & f.mask;
+    const float    w[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
+    float4         o     = make_float4(0.f, 0.f, 0.f, 0.f);
+    near_to_object(w, p.x, p.y, p.z, o.x, o.y, o.z);
+    if (!point_ok(o)) return false;
+    const float4* seed = bvh.tris_by_id + 4 * (size_t)gid;
+    const float   d2s  = closest_dist2(seed[0], seed[1], seed[2], o.x, o.y, o.z);
+    const bool    some = d2s == d2s;
+    float         best = some ? d2s : __builtin_inff(), bound2 = prune_bound2(best, slack);
+    uint32_t      best_gid = some ? gid : kInvalidId;
+    int           node = (int)f2u(w3.y), sp = 0;
+    for (;;)
+    {
+        if (node >= 0)
+        {
+            if (closest_node_step<STACK>(bvh, o.x, o.y, o.z, bound2, stack, node, sp)) continue;
+        }
+        else
+            closest_leaf_step<FILTER>(bvh, node, f.tri_mask, imask, slack, o.x, o.y, o.z, best, best_gid, bound2);
+        if (!closest_pop(stack, sp, bound2, node)) break;
+    }
+    if (best_gid == kInvalidId) return false;
+    const ClosestPoint c  = scene_record(bvh, best_gid, o);
+    const float* const nn = normals + 21 * (size_t)best_gid + 3u * c.feature;
+    return dot_c(c.dx, c.dy, c.dz, nn[0], nn[1], nn[2]) < 0.f;
+}
+
+// FILTER: a mesh-mask table is installed (f.tri_mask by global id); the instance's own mask is tested either way.
+// SIGNED (cap_signed_distance_instances): the same walk and record, then a second phase in the same lane on the same stack slice,
+// object_sign_negative above, and the signed value from the WORLD record's dist2.  A flag of the kernel: the unsigned instantiations keep
+// their registers (tools/kernel_regs.sh).  ia.a.slack is the scene's flat slack for the signed launch and is not read otherwise.
+template <int STACK, bool FILTER, bool SIGNED = false>
+__global__ __launch_bounds__(kBlock, closest_inst_blocks(STACK)) void k_closest_inst(BvhDev bvh, ClosestInstArgs ia, TlasDev tl, RayFilter f, SignedArgs s)
 {
     __shared__ uint2    lds_stack[STACK * kBlock];
     __shared__ uint32_t lds_off[kTlasMaxLevels + 1];
@@ -481,6 +534,7 @@ __global__ __launch_bounds__(kBlock, closest_inst_blocks(STACK)) void k_closest_
         {
             write_miss(a.out + 2 * (size_t)j, 0.f);
             if (ia.inst_out) ia.inst_out[j] = kInvalidId;
+            if constexpr (SIGNED) s.signed_out[j] = __builtin_inff();
             continue;
         }
         const float r2   = p.w * p.w;
@@ -549,9 +603,20 @@ __global__ __launch_bounds__(kBlock, closest_inst_blocks(STACK)) void k_closest_
         }
         if (ia.inst_out) ia.inst_out[j] = best_inst;
         if (best_gid == kInvalidId)
+        {
             write_miss(a.out + 2 * (size_t)j, r2);
-        else
-            write_record(a.out + 2 * (size_t)j, instance_record(bvh, ia.descs, best_inst, best_gid, p), best_gid);
+            if constexpr (SIGNED) s.signed_out[j] = __builtin_inff();
+            continue;
+        }
+        const ClosestPoint c = instance_record(bvh, ia.descs, best_inst, best_gid, p);
+        write_record(a.out + 2 * (size_t)j, c, best_gid);
+        if constexpr (SIGNED)
+        {
+            // dist2 == 0 is +0.0 whatever the object-space walk says
+            const float dist = sqrtf(c.d2);
+            const bool  neg  = c.d2 != 0.f && object_sign_negative<STACK, FILTER>(bvh, tl, f, s.normals, a.slack, best_inst, best_gid, p, stack);
+            s.signed_out[j]  = neg ? -dist : dist;
+        }
     }
 }
 
@@ -737,7 +802,15 @@ void launch_closest_instances(const LaunchCfg& cfg, const BvhDev& bvh, const Clo
 {
     // (depth: of the deepest bottom-level tree)
     with_stack_class(depth, [&](auto S) {
-        with_flag(f.tri_mask != nullptr, [&](auto FILTER) { launch_points<k_closest_inst<decltype(S)::value, decltype(FILTER)::value>>(cfg, a.a.n, bvh, a, tl, f); });
+        with_flag(f.tri_mask != nullptr, [&](auto FILTER) { launch_points<k_closest_inst<decltype(S)::value, decltype(FILTER)::value>>(cfg, a.a.n, bvh, a, tl, f, SignedArgs{}); });
+    });
+}
+
+void launch_signed_distance_instances(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstArgs& a, const SignedArgs& s, const TlasDev& tl,
+                                      const RayFilter& f, uint32_t depth)
+{
+    with_stack_class(depth, [&](auto S) {
+        with_flag(f.tri_mask != nullptr, [&](auto FILTER) { launch_points<k_closest_inst<decltype(S)::value, decltype(FILTER)::value, true>>(cfg, a.a.n, bvh, a, tl, f, s); });
     });
 }
 

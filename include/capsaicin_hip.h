@@ -736,8 +736,8 @@ int cap_trace_instances_multi(CapContext* ctx, const CapRayDesc* device_rays, ui
  * output, misalignment, overlap.
  * Pruning never decides: the top-level boxes and the objects' trees are pruned with a bound that is proven conservative for every
  * live instance (DESIGN.md "Closest-point queries over instances"; cap_debug_closest_instance_bound shows its arithmetic).
- * Not covered: per-point masks, the sign of the distance, the wide view.  The k nearest, counts and paging: cap_closest_instances_multi
- * below. */
+ * Not covered: per-point masks, the wide view.  The k nearest, counts and paging: cap_closest_instances_multi below.  The sign of the
+ * distance: cap_signed_distance_instances further below. */
 int cap_closest_instances(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out,
                           uint32_t* device_instances /* may be NULL */, const CapTraceOptions* options /* may be NULL */);
 
@@ -821,8 +821,8 @@ int cap_closest_instances_multi(CapContext* ctx, const CapPointDesc* device_poin
  * computation on the read-back table and the record's (u, v) is bit-identical.
  * Conventions are cap_closest_points' plus: device_signed is required and 4-byte aligned, no two of the three ranges overlap, and
  * CAP_ERR_STATE also without a table.  Nothing is written on an error; n above 2^24 is split into launches.
- * Not covered: the sign over instances (a mirror flips it, and a non-rigid transform changes both the angles and the normals, so it
- * needs a table per instance or reweighting on the fly), the k-nearest forms, generalised winding numbers for open meshes. */
+ * Not covered: the k-nearest forms, generalised winding numbers for open meshes.  The sign over instances:
+ * cap_signed_distance_instances below. */
 typedef struct CapPseudonormalsInfo
 {
     uint32_t vertices;             /* welded positions of the live triangles */
@@ -840,6 +840,50 @@ int cap_pseudonormals_drop(CapContext* ctx);
 int cap_pseudonormals_readback(CapContext* ctx, float* host_normals /* 21 floats per triangle */);
 int cap_signed_distance(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out, float* device_signed,
                         const CapTraceOptions* options /* may be NULL */);
+
+/* ---- signed distance over instances: cap_closest_instances with a sign, taken in object space ----
+ * "How deep inside which part": penetration depth and contact generation against rigidly moving parts, distance fields over scenes
+ * built from instances and animated by one cap_instances_set per frame.  The DISTANCE is the world one; the SIGN is read in the
+ * instance's object space, where the pseudonormal table lives.  For a closed mesh, inside and outside are invariant under any
+ * invertible affine map, a mirror included: a world point lies inside instance i exactly when its object-space image lies inside i's
+ * object.  So no table per instance, no transformed normals and no rule for which transforms are "rigid enough" are needed.
+ *
+ * Records.  device_out[j] and device_instances[j] (may be NULL) are bit for bit cap_closest_instances' answer: candidates, tie rule
+ * (dist2, i, g), masks, objects, miss record and degenerate points are all unchanged.
+ * Object-space point.  For a point p whose record is a hit in instance i, with W the stored world-to-object matrix as
+ * cap_instances_readback returns it, per row r:
+ *   p'_r = fl(fl(fl(fl(W_r0*p.x) + fl(W_r1*p.y)) + fl(W_r2*p.z)) + W_r3)
+ * every operation one rounded binary32 operation in the order written, no fused multiply-add.
+ * Sign record.  cap_signed_distance's winner for the point (p', radius = +inf) over instance i's candidates alone: the triangles of i's
+ * object (the whole scene without an object table) with desc[i].mask & mesh_mask[m] & instance_mask != 0 for the triangle's mesh m.
+ * The per-triangle function is cap_closest_points' cascade, unchanged, on the stored object-space record (v0, e1, e2); the sign record
+ * is the candidate minimal in (dist2', g'); a NaN dist2' is never a candidate.  d = dot_c(delta', N[g'][feature']): delta' that
+ * record's own delta, N the stored binary32 table entry, dot_c the point queries' unfused dot.  The point's own radius does not bound
+ * this walk, and the world winner's triangle is always among its candidates.  (g', feature') need not be the world record's (g,
+ * feature): a transform that is not a similarity does not preserve nearest.
+ * Signed value.  device_signed[j] = -sqrt(dist2) if d < 0 and dist2 != 0, else +sqrt(dist2): dist2 the WORLD record's, sqrt the
+ * correctly rounded binary32 square root.  dist2 == 0 gives +0.0 whatever the object-space walk says.  A miss or a degenerate point
+ * gives +inf.  If p' is degenerate by the points' own rule (a coordinate overflowed or is NaN), or no candidate has a dist2' that is
+ * not NaN, the sign is positive.  A float32 computation from the read-back W, the read-back table and the scene's triangles is
+ * therefore bit-identical.
+ * What the sign means: inside or outside only where the instance's VISIBLE triangles -- its object's, under the masks -- form a
+ * closed, consistently wound surface.  The table welds across the whole scene: objects that touch in object space share edges there
+ * and stop being closed, each for itself, so keep the objects of one scene apart (CapPseudonormalsInfo.closed reports the scene).  A
+ * mirrored instance of an outward-wound object is negative inside as well: facing, as everywhere in this ABI, is an object-space
+ * notion.
+ * Identity (tested): with one identity instance and no negative zero in the scene, records and signed values are bit-identical to
+ * cap_signed_distance's, for every radius.
+ * Conventions are cap_closest_instances' plus: device_signed is required and 4-byte aligned; no two of the four ranges (points,
+ * output, signed, and instances unless NULL) overlap.  CAP_ERR_STATE without an instance table, without a pseudonormal table, before
+ * cap_bvh_build and while the trees are stale.  CAP_ERR_INVALID_ARG exactly where cap_closest_instances has it, and for a NULL
+ * device_signed.  Nothing is written on an error.  n above 2^24 is split into launches with all three output pointers advanced; n = 0
+ * does nothing.  Asynchronous on the context stream; nothing of the render's state is touched.
+ * Pruning never decides: the world walk is cap_closest_instances', the object-space walk cap_closest_points' with the scene's slack
+ * (DESIGN.md "Signed distance over instances").
+ * Not covered: the sign of the k-nearest forms, generalised winding numbers for open meshes. */
+int cap_signed_distance_instances(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out,
+                                  uint32_t* device_instances /* may be NULL */, float* device_signed,
+                                  const CapTraceOptions* options /* may be NULL */);
 
 /* ---- objects: per-mesh-range bottom-level trees for the instanced queries ----
  * An object is the mesh range [first_mesh, first_mesh + mesh_count) of the uploaded scene: mesh_count >= 1, at least one triangle,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Throughput of the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances,
-cap_closest_instances_multi) on the 262 k-triangle hall -- not part of bench.py, no pass mark.
+cap_closest_instances_multi, cap_signed_distance_instances) on the 262 k-triangle hall -- not part of bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
                                      [--k K [--counts]] [--instances N] [--signed]
@@ -14,6 +14,14 @@ distance), and the table build: table_build_ms beside the tree's bvh_build_ms, a
 around it, 1.1 scene sizes apart, each turned about the vertical by an angle of its own (N = 1: the identity alone).  The point sets
 are the flat query's, in and around instance 0; each line carries the instanced rate and, as its baseline, cap_closest_points on the
 same points in the same process (flat_ms, flat_mpoints_per_s) and the ratio of the two rates.
+
+--instances N together with --signed runs cap_signed_distance_instances on the same layout and point sets after
+cap_pseudonormals_build.  Each line carries, measured in the same process on the same points: cap_closest_instances (unsigned_ms,
+unsigned_mpoints_per_s, time_over_unsigned = the signed call's time over it), cap_closest_points (flat_ms: for the points whose winner
+is instance 0, the identity, it is the flat walk from the same p' on the same object, so extra_over_flat = (ms - unsigned_ms) / flat_ms
+says what the second phase costs in flat walks), same_records (the share of points whose record and instance equal
+cap_closest_instances': has to be 1.0), in_identity (the share of points whose winner is instance 0) and negative (the share of hits
+with a negative distance).
 
 --instances N together with --k K [--counts] runs cap_closest_instances_multi on the same layout and point sets.  Each line carries,
 measured in the same process on the same points: (a) cap_closest_points_multi at the same k and counts (flat_ms, flat_mpoints_per_s,
@@ -91,11 +99,12 @@ def main():
     ap.add_argument("--instances", type=int, default=None)
     ap.add_argument("--signed", action="store_true")
     a = ap.parse_args()
-    if a.signed and (a.k is not None or a.instances is not None):
-        ap.error("--signed runs alone: the sign is defined for cap_closest_points' record")
+    if a.signed and a.k is not None:
+        ap.error("--signed does not go with --k: the sign is defined for the single record")
     if a.instances is not None and a.instances < 1:
         ap.error("--instances N needs N >= 1")
     inst_multi = a.instances is not None and a.k is not None
+    inst_signed = a.instances is not None and a.signed
     rng = np.random.default_rng(2026)
     dev = torch.device("cuda", 0)
     L = capi.lib()
@@ -133,6 +142,7 @@ def main():
         pn = r.build_pseudonormals()
         signed = torch.empty((n,), dtype=torch.float32, device=dev)
         flat_out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        plain_inst = torch.empty((n,), dtype=torch.int32, device=dev) if inst_signed else None
     head = dict(scene="hall", triangles=int(info.triangle_count), depth=int(info.max_depth), n=n, radius=a.radius, reps=a.reps)
     if a.k is not None:
         head.update(k=a.k, counts=a.counts)
@@ -141,7 +151,14 @@ def main():
         q[:, 0:3], q[:, 3] = xyz, a.radius
         pts = torch.as_tensor(q, device=dev).contiguous()
         torch.cuda.synchronize()
-        if inst_multi:
+        if inst_signed:
+            flat = lambda: capi._check(L.cap_closest_points(r.ctx, pts.data_ptr(), n, flat_out.data_ptr(), None), "cap_closest_points")
+            flat_sec = timed(r, flat, a.reps, a.warmup)
+            single = lambda: capi._check(L.cap_closest_instances(r.ctx, pts.data_ptr(), n, flat_out.data_ptr(), plain_inst.data_ptr(), None), "cap_closest_instances")
+            single_sec = timed(r, single, a.reps, a.warmup)
+            call = lambda: capi._check(L.cap_signed_distance_instances(r.ctx, pts.data_ptr(), n, out.data_ptr(), inst.data_ptr(), signed.data_ptr(), None),
+                                       "cap_signed_distance_instances")
+        elif inst_multi:
             flat = lambda: capi._check(L.cap_closest_points_multi(r.ctx, pts.data_ptr(), n, a.k, flat_out.data_ptr() if a.k else None,
                                                                   flat_cnt.data_ptr() if a.counts else None, 0, None), "cap_closest_points_multi")
             flat_sec = timed(r, flat, a.reps, a.warmup)
@@ -171,7 +188,15 @@ def main():
             rec, hit = page[:, 0], listed[:, 0]
             line.update(hits=round(float(hit.mean()), 4),
                         mean_dist=round(float(np.sqrt(rec[hit, 3].astype(np.float64)).mean() / size), 5) if hit.any() else None)
-        if inst_multi:
+        if inst_signed:
+            same = (out.view(torch.int32) == flat_out.view(torch.int32)).all(1) & (inst == plain_inst)
+            sd = signed.cpu().numpy()
+            line.update(instances=a.instances, inert=int(info_i.inert), tlas_depth=int(info_i.tlas_depth), unsigned_ms=round(single_sec * 1e3, 3),
+                        unsigned_mpoints_per_s=round(n / single_sec / 1e6, 1), time_over_unsigned=round(sec / single_sec, 4), flat_ms=round(flat_sec * 1e3, 3),
+                        extra_over_flat=round((sec - single_sec) / flat_sec, 4), same_records=round(float(same.float().mean()), 4),
+                        in_identity=round(float((inst == 0).float().mean()), 4), negative=round(float((sd[hit] < 0).mean()), 4) if hit.any() else None,
+                        table_build_ms=round(pn.ms, 3))
+        elif inst_multi:
             line.update(instances=a.instances, inert=int(info_i.inert), tlas_depth=int(info_i.tlas_depth), flat_ms=round(flat_sec * 1e3, 3),
                         flat_mpoints_per_s=round(n / flat_sec / 1e6, 1), ratio_to_flat=round(flat_sec / sec, 3), single_ms=round(single_sec * 1e3, 3),
                         single_mpoints_per_s=round(n / single_sec / 1e6, 1), ratio_to_single=round(single_sec / sec, 3))
@@ -184,7 +209,7 @@ def main():
             same = float((out.view(torch.int32) == flat_out.view(torch.int32)).all(1).float().mean())
             line.update(instances=a.instances, inert=int(info_i.inert), tlas_depth=int(info_i.tlas_depth), flat_ms=round(flat_sec * 1e3, 3),
                         flat_mpoints_per_s=round(n / flat_sec / 1e6, 1), ratio_to_flat=round(flat_sec / sec, 3), same_as_flat=round(same, 4))
-        if a.signed:
+        if a.signed and not inst_signed:
             same = float((out.view(torch.int32) == flat_out.view(torch.int32)).all(1).float().mean())
             sd = signed.cpu().numpy()
             line.update(flat_ms=round(flat_sec * 1e3, 3), flat_mpoints_per_s=round(n / flat_sec / 1e6, 1), time_over_flat=round(sec / flat_sec, 4),
