@@ -709,113 +709,70 @@ class Renderer:
             flags |= self.RAY_FLAG_ACCEPT_FIRST_HIT
         return TraceOptions(flags, 0 if mask is None else int(mask))
 
-    # ---- ray queries (cap_trace_rays / cap_trace_occlusion) ----
-    def trace_rays(self, rays, out=None, sync=True, cull=None, mask=None, first_hit=False):
-        """Closest hit of each ray.  rays: (N, 8) float32 = CapRayDesc rows (origin, tmin, direction, tmax), a contiguous torch tensor
-        on this context's device or a numpy array (staged through torch; the hits come back as numpy).  Returns (N, 4) float32 hit
-        records (t, u, v, triangle id bits: hit_triangles() reads them).  sync=True orders the call against torch's current stream
-        (waits for it before the launch) and waits for the context's stream before returning: right for a renderer on a stream of its
-        own.  sync=False only enqueues, on the context's stream: for a renderer created on torch's stream (as bench.py creates it).
-        cull="back" | "front" drops the triangles facing away from / towards the ray, mask= is the instance inclusion mask
-        (set_instance_masks), first_hit=True returns some hit instead of the closest (cap_trace_rays_ex)."""
-        return self._query(rays, out, sync, False, self.trace_options(cull, mask, first_hit))
+    # ---- queries: what the twelve wrappers below share ----
+    MULTI_MAX_K, MULTI_CONTINUE = 16, 1  # CAP_MULTI_MAX_K, CAP_MULTI_CONTINUE
 
-    def trace_occlusion(self, rays, out=None, sync=True, cull=None, mask=None):
-        """1 where some triangle occludes the ray's open interval (tmin, tmax), else 0: (N,) int32.  Arguments as trace_rays."""
-        return self._query(rays, out, sync, True, self.trace_options(cull, mask))
-
-    def _query(self, rays, out, sync, any_hit, options=None):
+    def _stage_records(self, records, width, what):
+        """(device, records on it, N) of a query's rays (width 8) or points (width 4), `what` the argument's name: a contiguous
+        (N, width) float32 tensor as it is, a numpy array staged through torch"""
         import torch
         dev = torch.device("cuda", self.device)
-        host = isinstance(rays, np.ndarray)
-        if host:
-            rays = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).to(dev)
-            sync = True  # the result is read back to the host
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.device != dev:
-            raise CapError("rays must be a contiguous (N, 8) float32 tensor on %s, got %s %s on %s" % (dev, rays.dtype, tuple(rays.shape), rays.device))
-        n = rays.shape[0]
-        shape, dtype = ((n,), torch.int32) if any_hit else ((n, 4), torch.float32)
+        if isinstance(records, np.ndarray):
+            records = torch.from_numpy(np.ascontiguousarray(records, np.float32).reshape(-1, width)).to(dev)
+        if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != width or not records.is_contiguous() or records.device != dev:
+            raise CapError("%s must be a contiguous (N, %d) float32 tensor on %s, got %s %s on %s"
+                           % (what, width, dev, records.dtype, tuple(records.shape), records.device))
+        return dev, records, records.shape[0]
+
+    def _out(self, out, shape, dtype, dev):
+        """(the tensor of that shape and dtype a query writes, the caller's numpy array or None) of out=: a tensor is checked, a numpy
+        array or None gets a new one"""
         host_out = None
         if isinstance(out, np.ndarray):
             host_out, out = out, None
         if out is None:
+            import torch
             out = torch.empty(shape, dtype=dtype, device=dev)
-        elif out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
-            raise CapError("out must be a contiguous %s %s tensor on %s" % (tuple(shape), dtype, dev))
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()  # the rays (and out's allocation) were made on torch's stream
-        if options is not None:
-            fn = lib().cap_trace_occlusion_ex if any_hit else lib().cap_trace_rays_ex
-            _check(fn(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), C.byref(options)),
-                   "cap_trace_occlusion_ex" if any_hit else "cap_trace_rays_ex")
-        else:
-            fn = lib().cap_trace_occlusion if any_hit else lib().cap_trace_rays
-            _check(fn(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), 0),
-                   "cap_trace_occlusion" if any_hit else "cap_trace_rays")
-        if sync:
-            self.sync()
-        if host or host_out is not None:
-            res = out.cpu().numpy()
-            if host_out is not None:
-                host_out[...] = res.reshape(host_out.shape)
-                return host_out
-            return res
-        return out
-
-    # ---- closest-point queries (cap_closest_points) ----
-    def _stage_points(self, points):
-        """(device, points on it, N) of a closest-point call: a contiguous (N, 4) float32 tensor as it is, a numpy array staged through
-        torch"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(points, np.ndarray):
-            points = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 4)).to(dev)
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device != dev:
-            raise CapError("points must be a contiguous (N, 4) float32 tensor on %s, got %s %s on %s" % (dev, points.dtype, tuple(points.shape), points.device))
-        return dev, points, points.shape[0]
-
-    def _records_out(self, out, n, dev):
-        """(the (n, 8) float32 record tensor, the caller's numpy array or None) of out=: a tensor is checked, a numpy array or None gets
-        a new one"""
-        import torch
-        host_out = None
-        if isinstance(out, np.ndarray):
-            host_out, out = out, None
-        if out is None:
-            out = torch.empty((n, 8), dtype=torch.float32, device=dev)
-        elif out.dtype != torch.float32 or tuple(out.shape) != (n, 8) or not out.is_contiguous() or out.device != dev:
-            raise CapError("out must be a contiguous (%d, 8) float32 tensor on %s" % (n, dev))
+        elif out.dtype != dtype or out.shape != shape or not out.is_contiguous() or out.device != dev:
+            raise CapError("out must be a contiguous %s %s tensor on %s, got %s %s on %s" % (shape, dtype, dev, out.dtype, tuple(out.shape), out.device))
         return out, host_out
 
-    def _resume_page(self, page, shape, dtype, dev, bad_size, bad_layout):
+    def _resume_page(self, page, shape, dtype, dev, what):
         """(one page of a multi query on the device, the caller's numpy page or None): a new one without a page to resume from, a numpy
-        page staged through torch, a tensor checked; bad_size / bad_layout are the messages of the two failures"""
-        import torch
-        if page is None:
-            return torch.empty(shape, dtype=dtype, device=dev), None
-        if isinstance(page, np.ndarray):
-            if page.size != int(np.prod(shape)):
-                raise CapError(bad_size)
-            return torch.from_numpy(np.ascontiguousarray(page, {torch.float32: np.float32, torch.int32: np.int32}[dtype]).reshape(shape)).to(dev), page
-        if page.dtype != dtype or tuple(page.shape) != tuple(shape) or not page.is_contiguous() or page.device != dev:
-            raise CapError(bad_layout)
-        return page, None
+        page of the right size staged through torch, a tensor checked; `what` names the argument"""
+        if page is None or isinstance(page, np.ndarray):
+            import torch
+            if page is None:
+                return torch.empty(shape, dtype=dtype, device=dev), None
+            if page.size == int(np.prod(shape)):
+                return torch.from_numpy(np.ascontiguousarray(page, np.float32 if dtype == torch.float32 else np.int32).reshape(shape)).to(dev), page
+        elif page.dtype == dtype and page.shape == shape and page.is_contiguous() and page.device == dev:
+            return page, None
+        raise CapError("%s must be the %s %s page of the previous call, a contiguous tensor on %s or a numpy array of its size, got %s %s"
+                       % (what, shape, dtype, dev, page.dtype, tuple(page.shape)))
 
-    def _page_size(self, k, counts, resuming, pages):
+    def _page_size(self, k, counts, resuming):
         k = int(k)
         if not 0 <= k <= self.MULTI_MAX_K:
             raise CapError("k must be in 0 .. %d (page with resume=), got %d" % (self.MULTI_MAX_K, k))
         if k == 0 and (not counts or resuming):
-            raise CapError("k = 0 counts only: pass counts=True and no resume %s" % pages)
+            raise CapError("k = 0 counts only: pass counts=True and no resume")
         return k
 
-    def _results(self, sync, host, outputs, host_outputs):
-        """After the launch: waits for it with sync, then the outputs as the caller gets them -- the device tensors, or with host numpy
-        copies, written into the caller's own array where host_outputs holds one"""
+    def _run(self, name, args, dev, sync, host, outputs, host_outputs):
+        """The one path of every query.  With sync, waits for torch's stream; calls the entry point `name` on this context with args --
+        a tensor goes as its pointer, a TraceOptions by reference, None as NULL, an integer as it is --; waits for the context's
+        stream with sync, and always before a read-back.  Returns the outputs as the caller gets them: the device tensors, or with
+        host numpy copies, written into the caller's own array where host_outputs holds one"""
         if sync:
+            import torch
+            torch.cuda.current_stream(dev).synchronize()  # the inputs (and the outputs' allocations) were made on torch's stream
+        _check(getattr(lib(), name)(self.ctx, *[a if a is None or type(a) is int else C.byref(a) if type(a) is TraceOptions
+                                                else C.c_void_p(a.data_ptr()) for a in args]), name)
+        if sync or host:
             self.sync()
         if not host:
-            return list(outputs)
+            return outputs
         res = []
         for out, mine in zip(outputs, host_outputs):
             h = out.cpu().numpy()
@@ -825,22 +782,75 @@ class Renderer:
             res.append(h)
         return res
 
-    def _closest_single(self, name, points, out, sync, mask, second=None):
-        """One record per point through the entry point `name`; second=<dtype>, or a tuple of them: it also fills an (N,) array of
-        each type, in the entry point's order"""
+    def _single(self, name, records, width, what, out, cols, dtype, sync, tail, second=()):
+        """One result per ray or point through the entry point `name`: out= is the (N, cols) array of `dtype` it writes ((N,) with
+        cols = 0), `second` the dtypes of the (N,) arrays it fills behind that, `tail` its arguments behind those.  Returns the first
+        array alone without `second`, else the tuple of all"""
+        host = isinstance(records, np.ndarray)  # then the results are read back to the host, which needs the sync
+        dev, records, n = self._stage_records(records, width, what)
+        out, host_out = self._out(out, (n, cols) if cols else (n,), dtype, dev)
+        extra = [out.new_empty((n,), dtype=t) for t in second]
+        res = self._run(name, (records, n, out, *extra, *tail), dev, sync or host, host or host_out is not None,
+                        [out] + extra, [host_out] + [None] * len(extra))
+        return tuple(res) if second else res[0]
+
+    def _multi(self, name, records, width, what, cols, instanced, k, counts, resume, sync, tail):
+        """Up to k results per ray or point through the entry point `name`: a page of (N, k, cols) float32 records and, instanced, one
+        of (N, k) int32 instances -- resume= is the previous call's page or, instanced, pair of pages --, then the (N,) int32 counts
+        with counts=True; `tail` is what the entry point takes behind the multi flags.  Returns the page alone where there is nothing
+        else, else the tuple"""
         import torch
-        host = isinstance(points, np.ndarray)
-        sync = sync or host  # the result is read back to the host
-        dev, points, n = self._stage_points(points)
-        out, host_out = self._records_out(out, n, dev)
-        extra = [torch.empty((n,), dtype=t, device=dev) for t in (() if second is None else second if isinstance(second, tuple) else (second,))]
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
-        options = self.trace_options(None, mask)
-        _check(getattr(lib(), name)(self.ctx, C.c_void_p(points.data_ptr()), n, C.c_void_p(out.data_ptr()), *[C.c_void_p(t.data_ptr()) for t in extra],
-                                    C.byref(options) if options is not None else None), name)
-        res = self._results(sync, host or host_out is not None, [out] + extra, [host_out] + [None] * len(extra))
-        return res[0] if second is None else tuple(res)
+        if not instanced:
+            given, names = [resume], ("resume",)
+        elif resume is None or (isinstance(resume, (tuple, list)) and len(resume) == 2):
+            given, names = [None, None] if resume is None else list(resume), ("resume[0]", "resume[1]")
+        else:
+            raise CapError("resume must be the (records, instances) pair of pages of the previous call")
+        host = isinstance(records, np.ndarray)  # numpy rays or points, or a numpy page: read back to the host, which needs the sync
+        dev, records, n = self._stage_records(records, width, what)
+        k = self._page_size(k, counts, resume is not None)
+        pages, host_pages = [], []
+        for page, page_name, (shape, dtype) in zip(given, names, (((n, k, cols), torch.float32), ((n, k), torch.int32))):
+            page, mine = self._resume_page(page, shape, dtype, dev, page_name)
+            pages.append(page)
+            host_pages.append(mine)
+            host = host or mine is not None
+        cnt = [torch.empty((n,), dtype=torch.int32, device=dev)] if counts else []
+        res = self._run(name, (records, n, k, *(pages if k else [None] * len(pages)), cnt[0] if counts else None,
+                               self.MULTI_CONTINUE if resume is not None else 0, *tail),
+                        dev, sync or host, host, pages + cnt, host_pages + [None])
+        return tuple(res) if instanced or counts else res[0]
+
+    @staticmethod
+    def _plain_or_ex(name, options, plain_tail):
+        """(entry point, its last arguments) of the three ray queries that have a plain form: that form with plain_tail when every
+        option is at its default, else the _ex form with the options"""
+        return (name, plain_tail) if options is None else (name + "_ex", (options,))
+
+    # ---- ray queries (cap_trace_rays / cap_trace_occlusion) ----
+    def trace_rays(self, rays, out=None, sync=True, cull=None, mask=None, first_hit=False):
+        """Closest hit of each ray.  rays: (N, 8) float32 = CapRayDesc rows (origin, tmin, direction, tmax), a contiguous torch tensor
+        on this context's device or a numpy array (staged through torch; the hits come back as numpy).  Returns (N, 4) float32 hit
+        records (t, u, v, triangle id bits: hit_triangles() reads them).  sync=True orders the call against torch's current stream
+        (waits for it before the launch) and waits for the context's stream before returning: right for a renderer on a stream of its
+        own.  sync=False only enqueues, on the context's stream: for a renderer created on torch's stream (as bench.py creates it).
+        cull="back" | "front" drops the triangles facing away from / towards the ray, mask= is the instance inclusion mask
+        (set_instance_masks), first_hit=True returns some hit instead of the closest (cap_trace_rays_ex)."""
+        import torch
+        name, tail = self._plain_or_ex("cap_trace_rays", self.trace_options(cull, mask, first_hit), (0,))
+        return self._single(name, rays, 8, "rays", out, 4, torch.float32, sync, tail)
+
+    def trace_occlusion(self, rays, out=None, sync=True, cull=None, mask=None):
+        """1 where some triangle occludes the ray's open interval (tmin, tmax), else 0: (N,) int32.  Arguments as trace_rays."""
+        import torch
+        name, tail = self._plain_or_ex("cap_trace_occlusion", self.trace_options(cull, mask), (0,))
+        return self._single(name, rays, 8, "rays", out, 0, torch.int32, sync, tail)
+
+    # ---- closest-point queries (cap_closest_points) ----
+    def _closest_single(self, name, points, out, sync, mask, second=()):
+        """One (N, 8) float32 record per point through the entry point `name`, and an (N,) array of each dtype in `second` behind it"""
+        import torch
+        return self._single(name, points, 4, "points", out, 8, torch.float32, sync, (self.trace_options(None, mask),), second)
 
     def closest_points(self, points, out=None, sync=True, mask=None):
         """The triangle nearest to each point within its radius.  points: (N, 4) float32 = CapPointDesc rows (x, y, z, radius; +inf:
@@ -874,7 +884,7 @@ class Renderer:
         reports, +sqrt(dist2) otherwise, +inf on a miss.  Needs build_pseudonormals().  points, out, sync and mask= as closest_points;
         numpy points give numpy results."""
         import torch
-        return self._closest_single("cap_signed_distance", points, out, sync, mask, torch.float32)
+        return self._closest_single("cap_signed_distance", points, out, sync, mask, (torch.float32,))
 
     def closest_instances(self, points, out=None, sync=True, mask=None):
         """The (instance, triangle) nearest to each point in WORLD space over the instance table (cap_closest_instances): (records
@@ -882,7 +892,7 @@ class Renderer:
         (u, v), the scene's triangle id and the feature: closest_triangles() reads those.  points, out, sync and mask= as
         closest_points; numpy points give numpy results."""
         import torch
-        return self._closest_single("cap_closest_instances", points, out, sync, mask, torch.int32)
+        return self._closest_single("cap_closest_instances", points, out, sync, mask, (torch.int32,))
 
     def signed_distance_instances(self, points, out=None, sync=True, mask=None):
         """closest_instances with the signed distance (cap_signed_distance_instances): (records (N, 8) float32, instances (N,) int32,
@@ -900,23 +910,7 @@ class Renderer:
         int32, and turns off pruning by the k-th distance (k = 0: counts only, the records are (N, 0, 8)).  resume=<previous page> (the
         (N, k, 8) result of a call with the same points) continues after it with CAP_MULTI_CONTINUE, writes the next page over it and
         returns it.  points, sync and mask= as closest_points; numpy points (or a numpy resume page) give numpy results."""
-        import torch
-        options = self.trace_options(None, mask)
-        host = isinstance(points, np.ndarray) or isinstance(resume, np.ndarray)
-        sync = sync or host  # the result is read back to the host
-        dev, points, n = self._stage_points(points)
-        k = self._page_size(k, counts, resume is not None, "page")
-        page, host_page = self._resume_page(resume, (n, k, 8), torch.float32, dev,
-                                            "resume must be the (%d, %d, 8) float32 page of the previous call, got %s" % (n, k, getattr(resume, "shape", None)),
-                                            "resume must be the contiguous (%d, %d, 8) float32 page of the previous call" % (n, k))
-        cnt = [torch.empty((n,), dtype=torch.int32, device=dev)] if counts else []
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
-        _check(lib().cap_closest_points_multi(self.ctx, C.c_void_p(points.data_ptr()), n, k, C.c_void_p(page.data_ptr()) if k else None,
-                                              C.c_void_p(cnt[0].data_ptr()) if counts else None, self.MULTI_CONTINUE if resume is not None else 0,
-                                              C.byref(options) if options is not None else None), "cap_closest_points_multi")
-        res = self._results(sync, host, [page] + cnt, [host_page, None])
-        return tuple(res) if counts else res[0]
+        return self._multi("cap_closest_points_multi", points, 4, "points", 8, False, k, counts, resume, sync, (self.trace_options(None, mask),))
 
     def closest_instances_multi(self, points, k, counts=False, resume=None, sync=True, mask=None):
         """The k (instance, triangle) pairs nearest to each point in WORLD space within its radius, in (dist2, instance, triangle) order
@@ -926,31 +920,7 @@ class Renderer:
         resume=(records, instances) of the previous call with the same points continues after it with CAP_MULTI_CONTINUE and writes the
         next pages over both.  closest_triangles() reads the (N, k) ids and features.  points, sync and mask= as closest_points; numpy
         points (or numpy resume pages) give numpy results."""
-        import torch
-        options = self.trace_options(None, mask)
-        if resume is not None and (not isinstance(resume, (tuple, list)) or len(resume) != 2):
-            raise CapError("resume must be the (records, instances) pair of the previous call")
-        host = isinstance(points, np.ndarray) or (resume is not None and any(isinstance(p, np.ndarray) for p in resume))
-        sync = sync or host  # the result is read back to the host
-        dev, points, n = self._stage_points(points)
-        k = self._page_size(k, counts, resume is not None, "pages")
-        pages, host_pages = [], []
-        for j, (shape, dtype) in enumerate((((n, k, 8), torch.float32), ((n, k), torch.int32))):
-            given = None if resume is None else resume[j]
-            page, mine = self._resume_page(given, shape, dtype, dev,
-                                           "resume[%d] must hold the %s page of the previous call, got %s" % (j, shape, getattr(given, "shape", None)),
-                                           "resume[%d] must be the contiguous %s %s page of the previous call" % (j, shape, dtype))
-            pages.append(page)
-            host_pages.append(mine)
-        rec, inst = pages
-        cnt = [torch.empty((n,), dtype=torch.int32, device=dev)] if counts else []
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()  # the points (and the outputs' allocations) were made on torch's stream
-        _check(lib().cap_closest_instances_multi(self.ctx, C.c_void_p(points.data_ptr()), n, k, C.c_void_p(rec.data_ptr()) if k else None,
-                                                 C.c_void_p(inst.data_ptr()) if k else None, C.c_void_p(cnt[0].data_ptr()) if counts else None,
-                                                 self.MULTI_CONTINUE if resume is not None else 0, C.byref(options) if options is not None else None),
-               "cap_closest_instances_multi")
-        return tuple(self._results(sync, host, pages + cnt, host_pages + [None]))
+        return self._multi("cap_closest_instances_multi", points, 4, "points", 8, True, k, counts, resume, sync, (self.trace_options(None, mask),))
 
 
     # ---- instanced ray queries (cap_instances_set, cap_trace_instances*) ----
@@ -1040,44 +1010,13 @@ class Renderer:
     def trace_instances(self, rays, out=None, sync=True, cull=None, mask=None, first_hit=False):
         """Closest hit of each ray over the instance table (cap_trace_instances): (hits (N, 4) float32, instance (N,) int32, -1 on a
         miss).  Records as trace_rays, with object-space (u, v) and the scene's triangle id.  Arguments as trace_rays."""
-        return self._query_instances(rays, out, sync, False, self.trace_options(cull, mask, first_hit))
+        import torch
+        return self._single("cap_trace_instances", rays, 8, "rays", out, 4, torch.float32, sync, (self.trace_options(cull, mask, first_hit),), (torch.int32,))
 
     def trace_instances_occlusion(self, rays, out=None, sync=True, cull=None, mask=None):
         """1 where some triangle of some instance occludes the ray's open interval, else 0: (N,) int32 (cap_trace_instances_occlusion)."""
-        return self._query_instances(rays, out, sync, True, self.trace_options(cull, mask))
-
-    def _query_instances(self, rays, out, sync, any_hit, options):
         import torch
-        dev = torch.device("cuda", self.device)
-        host = isinstance(rays, np.ndarray)
-        if host:
-            rays = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).to(dev)
-            sync = True  # the result is read back to the host
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.device != dev:
-            raise CapError("rays must be a contiguous (N, 8) float32 tensor on %s, got %s %s on %s" % (dev, rays.dtype, tuple(rays.shape), rays.device))
-        n = rays.shape[0]
-        shape, dtype = ((n,), torch.int32) if any_hit else ((n, 4), torch.float32)
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=dev)
-        elif out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
-            raise CapError("out must be a contiguous %s %s tensor on %s" % (tuple(shape), dtype, dev))
-        inst = None if any_hit else torch.empty((n,), dtype=torch.int32, device=dev)
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()  # the rays (and the outputs' allocations) were made on torch's stream
-        opt = C.byref(options) if options is not None else None
-        if any_hit:
-            _check(lib().cap_trace_instances_occlusion(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), opt),
-                   "cap_trace_instances_occlusion")
-        else:
-            _check(lib().cap_trace_instances(self.ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(inst.data_ptr()), opt),
-                   "cap_trace_instances")
-        if sync:
-            self.sync()
-        if any_hit:
-            return out.cpu().numpy() if host else out
-        return (out.cpu().numpy(), inst.cpu().numpy()) if host else (out, inst)
-
-    MULTI_MAX_K, MULTI_CONTINUE = 16, 1  # CAP_MULTI_MAX_K, CAP_MULTI_CONTINUE
+        return self._single("cap_trace_instances_occlusion", rays, 8, "rays", out, 0, torch.int32, sync, (self.trace_options(cull, mask),))
 
     def trace_rays_multi(self, rays, k, counts=False, resume=None, sync=True, cull=None, mask=None):
         """The first k hits of each ray in (t, triangle) order (cap_trace_rays_multi): (N, k, 4) float32 records as trace_rays writes
@@ -1086,49 +1025,8 @@ class Renderer:
         continues after it with CAP_MULTI_CONTINUE, writes the next page over it and returns it.  rays and sync as trace_rays; numpy
         rays (or a numpy resume page) give numpy results.  cull= and mask= as trace_rays: hits, counts and pages are those of the
         filtered hit set (cap_trace_rays_multi_ex)."""
-        import torch
-        options = self.trace_options(cull, mask)
-        dev = torch.device("cuda", self.device)
-        host = isinstance(rays, np.ndarray) or isinstance(resume, np.ndarray)
-        if isinstance(rays, np.ndarray):
-            rays = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).to(dev)
-        if host:
-            sync = True  # the result is read back to the host
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.device != dev:
-            raise CapError("rays must be a contiguous (N, 8) float32 tensor on %s, got %s %s on %s" % (dev, rays.dtype, tuple(rays.shape), rays.device))
-        n, k = rays.shape[0], int(k)
-        if not 0 <= k <= self.MULTI_MAX_K:
-            raise CapError("k must be in 0 .. %d (page with resume=), got %d" % (self.MULTI_MAX_K, k))
-        if k == 0 and (not counts or resume is not None):
-            raise CapError("k = 0 counts only: pass counts=True and no resume page")
-        host_page = None
-        if resume is None:
-            hits = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
-        elif isinstance(resume, np.ndarray):
-            host_page = resume
-            hits = torch.from_numpy(np.ascontiguousarray(resume, np.float32).reshape(n, k, 4)).to(dev)
-        else:
-            hits = resume
-            if hits.dtype != torch.float32 or tuple(hits.shape) != (n, k, 4) or not hits.is_contiguous() or hits.device != dev:
-                raise CapError("resume must be the contiguous (%d, %d, 4) float32 page of the previous call" % (n, k))
-        cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()  # the rays (and the outputs' allocations) were made on torch's stream
-        args = (self.ctx, C.c_void_p(rays.data_ptr()), n, k, C.c_void_p(hits.data_ptr()) if k else None,
-                C.c_void_p(cnt.data_ptr()) if counts else None, self.MULTI_CONTINUE if resume is not None else 0)
-        if options is not None:
-            _check(lib().cap_trace_rays_multi_ex(*args, C.byref(options)), "cap_trace_rays_multi_ex")
-        else:
-            _check(lib().cap_trace_rays_multi(*args), "cap_trace_rays_multi")
-        if sync:
-            self.sync()
-        if host:
-            h = hits.cpu().numpy()
-            if host_page is not None:
-                host_page[...] = h.reshape(host_page.shape)
-                h = host_page
-            return (h, cnt.cpu().numpy()) if counts else h
-        return (hits, cnt) if counts else hits
+        name, tail = self._plain_or_ex("cap_trace_rays_multi", self.trace_options(cull, mask), ())
+        return self._multi(name, rays, 8, "rays", 4, False, k, counts, resume, sync, tail)
 
     def trace_instances_multi(self, rays, k, counts=False, resume=None, sync=True, cull=None, mask=None):
         """The first k (instance, triangle) pairs of each ray over the instance table, in (t, instance, triangle) order
@@ -1137,57 +1035,7 @@ class Renderer:
         only, hits is (N, 0, 4) and instances (N, 0).  resume=(hits, instances) of the previous call with the same rays continues
         after it with CAP_MULTI_CONTINUE and writes the next pages over both.  rays, sync, cull= and mask= as trace_rays_multi; numpy
         rays (or numpy resume pages) give numpy results."""
-        import torch
-        options = self.trace_options(cull, mask)
-        dev = torch.device("cuda", self.device)
-        if resume is not None and (not isinstance(resume, (tuple, list)) or len(resume) != 2):
-            raise CapError("resume must be the (hits, instances) pair of the previous call")
-        host = isinstance(rays, np.ndarray) or (resume is not None and any(isinstance(p, np.ndarray) for p in resume))
-        if isinstance(rays, np.ndarray):
-            rays = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).to(dev)
-        if host:
-            sync = True  # the result is read back to the host
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.device != dev:
-            raise CapError("rays must be a contiguous (N, 8) float32 tensor on %s, got %s %s on %s" % (dev, rays.dtype, tuple(rays.shape), rays.device))
-        n, k = rays.shape[0], int(k)
-        if not 0 <= k <= self.MULTI_MAX_K:
-            raise CapError("k must be in 0 .. %d (page with resume=), got %d" % (self.MULTI_MAX_K, k))
-        if k == 0 and (not counts or resume is not None):
-            raise CapError("k = 0 counts only: pass counts=True and no resume pages")
-        host_pages = [None, None]
-        if resume is None:
-            hits = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
-            inst = torch.empty((n, k), dtype=torch.int32, device=dev)
-        else:
-            pages = []
-            for j, (page, shape, dtype, np_dtype) in enumerate(((resume[0], (n, k, 4), torch.float32, np.float32),
-                                                                 (resume[1], (n, k), torch.int32, np.int32))):
-                if isinstance(page, np.ndarray):
-                    if page.size != int(np.prod(shape)):
-                        raise CapError("resume[%d] must hold the %s page of the previous call, got %s" % (j, shape, page.shape))
-                    host_pages[j] = page
-                    page = torch.from_numpy(np.ascontiguousarray(page, np_dtype).reshape(shape)).to(dev)
-                elif page.dtype != dtype or tuple(page.shape) != shape or not page.is_contiguous() or page.device != dev:
-                    raise CapError("resume[%d] must be the contiguous %s %s page of the previous call" % (j, shape, dtype))
-                pages.append(page)
-            hits, inst = pages
-        cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
-        if sync:
-            torch.cuda.current_stream(dev).synchronize()  # the rays (and the outputs' allocations) were made on torch's stream
-        _check(lib().cap_trace_instances_multi(self.ctx, C.c_void_p(rays.data_ptr()), n, k, C.c_void_p(hits.data_ptr()) if k else None,
-                                               C.c_void_p(inst.data_ptr()) if k else None, C.c_void_p(cnt.data_ptr()) if counts else None,
-                                               self.MULTI_CONTINUE if resume is not None else 0, C.byref(options) if options is not None else None),
-               "cap_trace_instances_multi")
-        if sync:
-            self.sync()
-        if host:
-            out = [hits.cpu().numpy(), inst.cpu().numpy()]
-            for j in range(2):
-                if host_pages[j] is not None:
-                    host_pages[j][...] = out[j].reshape(host_pages[j].shape)
-                    out[j] = host_pages[j]
-            return (out[0], out[1], cnt.cpu().numpy()) if counts else (out[0], out[1])
-        return (hits, inst, cnt) if counts else (hits, inst)
+        return self._multi("cap_trace_instances_multi", rays, 8, "rays", 4, True, k, counts, resume, sync, (self.trace_options(cull, mask),))
 
     def triangle_to_instance_primitive(self, ids):
         """Global triangle ids (hit_triangles) -> (instance, primitive) = (mesh index, triangle index within the mesh), the pair
