@@ -72,6 +72,16 @@ class PseudonormalsInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class WindingInfo(C.Structure):
+    """CapWindingInfo: what cap_winding_build summed: the records of the dipole table, the triangles that contribute nothing, and the
+    whole tree's area, area-weighted normal sum (0 for a closed mesh, up to rounding) and area-weighted centroid."""
+    _fields_ = [("inner_nodes", C.c_uint32), ("degenerate_triangles", C.c_uint32), ("total_area", C.c_double), ("root_n", C.c_float * 3),
+                ("root_p", C.c_float * 3), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n in ("root_n", "root_p") else getattr(self, n)) for n, _ in self._fields_}
+
+
 VERTICES_DEVICE = 1  # CAP_VERTICES_DEVICE
 
 
@@ -286,6 +296,10 @@ SYMBOLS = {
     "cap_pseudonormals_drop": (_i, [_vp]),
     "cap_pseudonormals_readback": (_i, [_vp, _vp]),
     "cap_signed_distance": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
+    "cap_winding_build": (_i, [_vp, C.POINTER(WindingInfo)]),
+    "cap_winding_drop": (_i, [_vp]),
+    "cap_winding_readback": (_i, [_vp, _vp]),
+    "cap_winding_numbers": (_i, [_vp, _vp, _u64, C.c_float, _vp, _vp]),
     "cap_closest_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_signed_distance_instances": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
@@ -761,13 +775,13 @@ class Renderer:
 
     def _run(self, name, args, dev, sync, host, outputs, host_outputs):
         """The one path of every query.  With sync, waits for torch's stream; calls the entry point `name` on this context with args --
-        a tensor goes as its pointer, a TraceOptions by reference, None as NULL, an integer as it is --; waits for the context's
+        a tensor goes as its pointer, a TraceOptions by reference, None as NULL, an integer or a C.c_float as it is --; waits for the context's
         stream with sync, and always before a read-back.  Returns the outputs as the caller gets them: the device tensors, or with
         host numpy copies, written into the caller's own array where host_outputs holds one"""
         if sync:
             import torch
             torch.cuda.current_stream(dev).synchronize()  # the inputs (and the outputs' allocations) were made on torch's stream
-        _check(getattr(lib(), name)(self.ctx, *[a if a is None or type(a) is int else C.byref(a) if type(a) is TraceOptions
+        _check(getattr(lib(), name)(self.ctx, *[a if a is None or type(a) in (int, C.c_float) else C.byref(a) if type(a) is TraceOptions
                                                 else C.c_void_p(a.data_ptr()) for a in args]), name)
         if sync or host:
             self.sync()
@@ -878,13 +892,67 @@ class Renderer:
         _check(lib().cap_pseudonormals_readback(self.ctx, _p(table)), "cap_pseudonormals_readback")
         return table
 
-    def signed_distance(self, points, out=None, sync=True, mask=None):
+    def signed_distance(self, points, out=None, sync=True, mask=None, sign="pseudonormal", beta=2.0):
         """closest_points with the signed distance (cap_signed_distance): (records (N, 8) float32, signed (N,) float32).  The records
         are closest_points', bit for bit; signed is -sqrt(dist2) where the point lies behind the pseudonormal of the feature the record
         reports, +sqrt(dist2) otherwise, +inf on a miss.  Needs build_pseudonormals().  points, out, sync and mask= as closest_points;
-        numpy points give numpy results."""
+        numpy points give numpy results.
+        sign="winding" takes the sign from the winding number instead, for meshes that are not closed: the same two arrays, signed
+        negative exactly where winding_numbers(points, beta) >= 1/2, composed on the device from the two calls.  Needs build_winding()
+        as well, and takes no mask= (the winding number covers every triangle)."""
         import torch
-        return self._closest_single("cap_signed_distance", points, out, sync, mask, (torch.float32,))
+        if sign == "pseudonormal":
+            return self._closest_single("cap_signed_distance", points, out, sync, mask, (torch.float32,))
+        if sign != "winding":
+            raise CapError('sign must be "pseudonormal" or "winding", got %r' % (sign,))
+        if mask is not None:
+            raise CapError('sign="winding" takes no mask=: the winding number covers every triangle')
+        host = isinstance(points, np.ndarray)
+        dev, pts, n = self._stage_records(points, 4, "points")
+        rec, host_out = self._out(out, (n, 8), torch.float32, dev)
+        rec, signed = self._closest_single("cap_signed_distance", pts, rec, sync or host, None, (torch.float32,))
+        w = self.winding_numbers(pts, beta=beta, sync=sync or host)
+        signed = torch.where(w >= 0.5, -signed.abs(), signed.abs())
+        if not (host or host_out is not None):
+            return rec, signed
+        h = rec.cpu().numpy()
+        if host_out is not None:
+            host_out[...] = h.reshape(host_out.shape)
+            h = host_out
+        return h, signed.cpu().numpy()
+
+    # ---- winding numbers (cap_winding_*, cap_winding_numbers) ----
+    def build_winding(self):
+        """Build the dipole table of the scene's binary tree (cap_winding_build) and return its WindingInfo.  Needs a built tree;
+        build_bvh() and refit_bvh() keep an existing table current."""
+        info = WindingInfo()
+        _check(lib().cap_winding_build(self.ctx, C.byref(info)), "cap_winding_build")
+        return info
+
+    def drop_winding(self):
+        _check(lib().cap_winding_drop(self.ctx), "cap_winding_drop")
+
+    def winding_table(self):
+        """The table as an (inner nodes, 2, 8) float32 array, indexed as bvh_readback()'s nodes: per child slot the centroid p~, the
+        radius r, the normal sum N and the child's traversal code (bits: view as uint32)."""
+        table = np.zeros((max(self.bvh_info().triangle_count, 1) - 1, 2, 8), np.float32)
+        _check(lib().cap_winding_readback(self.ctx, _p(table)), "cap_winding_readback")
+        return table
+
+    def winding_numbers(self, points, beta=2.0, out=None, visits=False, sync=True):
+        """The generalised winding number of the scene about each point (cap_winding_numbers): (N,) float32, 1 inside and 0 outside a
+        closed mesh wound outwards, in between near holes; w >= 1/2 is the robust inside test.  Subtrees farther than beta x their
+        radius are replaced by their dipole: beta >= 1, larger is more exact and slower, inf sums every triangle exactly.
+        visits=True also returns an (N, 2) int32 array: the dipole terms and the exact triangle terms each walk added.  Needs
+        build_winding().  points (the radius column is not read), out and sync as closest_points; numpy points give numpy results."""
+        import torch
+        host = isinstance(points, np.ndarray)  # then the results are read back to the host, which needs the sync
+        dev, points, n = self._stage_records(points, 4, "points")
+        out, host_out = self._out(out, (n,), torch.float32, dev)
+        vis = [torch.empty((n, 2), dtype=torch.int32, device=dev)] if visits else []
+        res = self._run("cap_winding_numbers", (points, n, C.c_float(beta), out, vis[0] if visits else None), dev, sync or host,
+                        host or host_out is not None, [out] + vis, [host_out, None])
+        return tuple(res) if visits else res[0]
 
     def closest_instances(self, points, out=None, sync=True, mask=None):
         """The (instance, triangle) nearest to each point in WORLD space over the instance table (cap_closest_instances): (records

@@ -164,6 +164,10 @@ struct CapContext
     DevBuf<float>        pn_table;
     bool                 pn_ready = false;  // a table exists (stale while bvh_stale; cap_bvh_build / cap_bvh_refit rebuild it)
     CapPseudonormalsInfo pn_info{};
+    // dipole table of cap_winding_numbers (cap_winding_build, winding.hip): 4 float4 per inner node of the binary tree
+    DevBuf<float4>       wn_table;
+    bool                 wn_ready = false;  // a table exists (stale while bvh_stale; cap_bvh_build / cap_bvh_refit rebuild it)
+    CapWindingInfo       wn_info{};
     // vertex updates and refit (cap_scene_update_vertices, cap_bvh_refit, refit.hip)
     bool                  bvh_stale = false;             // vertices changed since the trees were last brought up to date
     bool                  positions_host_stale = false;  // positions_host lags a device-side update (read back only when needed)

@@ -492,6 +492,42 @@ struct PseudonormalArgs
 size_t pseudonormal_scan_words(uint32_t corners);
 void   launch_pseudonormals_build(hipStream_t stream, const PseudonormalArgs& a);
 
+// ---- winding numbers (winding.hip): the dipole table of cap_winding_build and the walk of cap_winding_numbers ----
+// table: 4 float4 per inner node of the binary tree, per child slot (p~.xyz, r) (N.xyz, asfloat(traversal child code)): the record of
+// include/capsaicin_hip.h ("winding numbers").  Everything else is build scratch: tri_sums 7 doubles per triangle in leaf order
+// (n_t, a_t, a_t c_t), sums 14 doubles per inner node (a slot's N, A, M), parent and flags one word per inner node, stats 2 words
+// (degenerate triangles, -), root 7 doubles (the whole tree's N, A, M).
+struct WindingBuildArgs
+{
+    const float*    positions;
+    const uint32_t* indices;
+    const uint4*    tri_ids;
+    const uint4*    mesh_offsets;
+    uint32_t        tri_count;
+    const float4*   nodes;
+    const uint32_t* leaf_tri;
+    float4*         table;
+    double*         tri_sums;
+    double*         sums;
+    uint32_t*       parent;
+    uint32_t*       flags;
+    uint32_t*       stats;
+    double*         root;
+};
+void launch_winding_build(hipStream_t stream, const WindingBuildArgs& a);
+// points = CapPointDesc records (the radius is not read), out = one float per point, visits = 2 words per point (far terms, exact
+// triangles) or NULL.  bvh.tris are the leaf-order records, bvh.root / tri_count the scene's; depth: the tree's max_depth.
+struct WindingArgs
+{
+    const float4* points;
+    uint32_t      n;
+    const float4* table;
+    float         beta;
+    float*        out;
+    uint32_t*     visits;
+};
+void launch_winding_numbers(const LaunchCfg& cfg, const BvhDev& bvh, const WindingArgs& a, uint32_t depth);
+
 // ---- refit of the kept trees to moved vertices (refit.hip, cap_bvh_refit) ----
 // binary tree: triangle setup (bounds reset first), parent links from the nodes, the build's climb (bvh.hip k_refit) in leaf order
 void   launch_bvh_refit_climb(hipStream_t stream, const BvhBuildArgs& a);  // (bvh.hip) the climb alone

@@ -216,7 +216,88 @@ static int pseudonormals_rebuild(CapContext* c, const char* what)
     return CAP_OK;
 }
 
+// The dipole table of cap_winding_numbers from the current vertices and the current binary tree (winding.hip): what cap_winding_build,
+// cap_bvh_build and cap_bvh_refit share, by pseudonormals_rebuild's rules.  The scratch goes when the call returns.  Waits for the
+// stream: the statistics are read back.  A failure drops the table.
+static int winding_rebuild(CapContext* c)
+{
+    c->wn_ready = false;  // (until the table stands)
+    const auto     wall0 = std::chrono::steady_clock::now();
+    const uint32_t t     = c->tri_count, inner = t >= 2 ? t - 1 : 0;
+    uint32_t       stats[2] = {0, 0};
+    double         root[7]  = {0, 0, 0, 0, 0, 0, 0};
+    if (t)
+    {
+        if (c->wn_table.n < 4 * (size_t)inner)
+        {
+            HIP_TRY(hipStreamSynchronize(c->stream));  // (a grown table replaces one an earlier query may still be reading)
+            HIP_TRY(c->wn_table.ensure(4 * (size_t)inner));
+        }
+        DevBuf<double>   reals;
+        DevBuf<uint32_t> words;
+        HIP_TRY(reals.ensure(7 * (size_t)t + 14 * (size_t)inner + 7));
+        HIP_TRY(words.ensure(2 * (size_t)inner + 2));
+        WindingBuildArgs a{};
+        a.positions = c->positions.p, a.indices = c->indices.p, a.tri_ids = c->tri_ids.p, a.mesh_offsets = c->mesh_offsets.p, a.tri_count = t;
+        a.nodes = c->nodes.p, a.leaf_tri = c->leaf_tri.p, a.table = c->wn_table.p;
+        a.tri_sums = reals.p, a.sums = reals.p + 7 * (size_t)t, a.root = a.sums + 14 * (size_t)inner;
+        a.parent = words.p, a.flags = words.p + inner, a.stats = words.p + 2 * (size_t)inner;
+        launch_winding_build(c->stream, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(stats, a.stats, sizeof(stats), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(root, a.root, sizeof(root), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    CapWindingInfo& wi = c->wn_info;
+    wi                 = CapWindingInfo{};
+    wi.inner_nodes = inner, wi.degenerate_triangles = stats[0], wi.total_area = root[3];
+    for (int k = 0; k < 3; ++k)
+    {
+        wi.root_n[k] = (float)root[k];
+        // (without area: the centre of the scene's bounds, as a child without area takes the centre of its box)
+        wi.root_p[k] = root[3] != 0.0 ? (float)(root[4 + k] / root[3]) : (float)(0.5 * ((double)c->bvh_info.bounds_lo[k] + (double)c->bvh_info.bounds_hi[k]));
+    }
+    wi.ms       = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    c->wn_ready = true;
+    return CAP_OK;
+}
+
 extern "C" {
+
+int cap_winding_build(CapContext* c, CapWindingInfo* out)
+{
+    static_assert(sizeof(CapWindingInfo) == 48, "the header's record");
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_winding_build: ctx is NULL");
+    if (const int rc = query_state(c, "cap_winding_build")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (const int rc = winding_rebuild(c)) return rc;
+    if (out) *out = c->wn_info;
+    return CAP_OK;
+}
+
+int cap_winding_drop(CapContext* c)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_winding_drop: ctx is NULL");
+    if (c->wn_table.p)
+    {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (a query may still be reading it)
+        c->wn_table.release();
+    }
+    c->wn_ready = false;
+    return CAP_OK;
+}
+
+int cap_winding_readback(CapContext* c, float* host_table)
+{
+    if (!c || !host_table) return fail(CAP_ERR_INVALID_ARG, "cap_winding_readback: NULL argument");
+    if (const int rc = query_state(c, "cap_winding_readback")) return rc;
+    if (!c->wn_ready) return fail(CAP_ERR_STATE, "cap_winding_readback: call cap_winding_build first");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->wn_info.inner_nodes) HIP_TRY(hipMemcpy(host_table, c->wn_table.p, sizeof(float4) * 4 * (size_t)c->wn_info.inner_nodes, hipMemcpyDeviceToHost));
+    return CAP_OK;
+}
 
 int cap_pseudonormals_build(CapContext* c, CapPseudonormalsInfo* out)
 {
@@ -259,6 +340,10 @@ int cap_bvh_build(CapContext* c)
     if (!c->scene_ready) return fail(CAP_ERR_STATE, "cap_bvh_build: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t n = c->tri_count;
+    // the dipole table belongs to the tree that is about to go (unlike the pseudonormal table, which is per triangle): it is not
+    // ready again until the rebuild at the end has made the new tree's, whatever fails on the way
+    const bool had_winding = c->wn_ready;
+    c->wn_ready            = false;
     HIP_TRY(c->shade_tris.ensure(kShadeRec * (size_t)n));
     // + 4 zero records: the exhaustive kernels test triangles in pairs and fetch one pair ahead (cap_exhaustive.h); a zero record
     // has det == 0 and is never hit
@@ -410,7 +495,9 @@ int cap_bvh_build(CapContext* c)
         return rc;
     }
     if (const int rc = instances_rebuild(c)) return rc;  // (nothing without a table)
-    return c->pn_ready ? pseudonormals_rebuild(c, "cap_bvh_build") : CAP_OK;  // the pseudonormal table, when one exists
+    if (c->pn_ready)  // the pseudonormal table, when one exists
+        if (const int rc = pseudonormals_rebuild(c, "cap_bvh_build")) return rc;
+    return had_winding ? winding_rebuild(c) : CAP_OK;  // the dipole table, when one existed: the new tree's
 }
 
 int cap_scene_update_vertices(CapContext* c, const float* positions, const float* normals, const float* texcoords, uint32_t flags)
@@ -515,6 +602,8 @@ int cap_bvh_refit(CapContext* c, CapRefitInfo* out)
     if (const int rc = instances_rebuild(c)) return rc;  // world boxes and TLAS from the new bounds (nothing without a table)
     if (c->pn_ready)                                     // the pseudonormal table, when one exists: rebuilt, the weld included
         if (const int rc = pseudonormals_rebuild(c, "cap_bvh_refit")) return rc;
+    if (c->wn_ready)                                     // the dipole table, when one exists: the moved triangles' moments, the refitted boxes' radii
+        if (const int rc = winding_rebuild(c)) return rc;
     if (out)
     {
         out->ms                         = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();

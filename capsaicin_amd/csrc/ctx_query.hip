@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip) and cap_winding_numbers (winding.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -369,9 +369,35 @@ int closest_query(CapContext* c, const char* what, const CapPointDesc* points, u
         return run.traced("k_closest_inst_multi", first);
     });
 }
+
+// cap_winding_numbers (winding.hip k_winding): the walk of the binary tree over the dipole table.  No options: the moments cover every
+// triangle, so there is no filter to check.
+int winding_query(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, float beta, float* winding, uint32_t* visits)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (!(beta >= 1.0f)) return fail(CAP_ERR_INVALID_ARG, "%s: beta = %g must be finite and >= 1, or +inf", what, (double)beta);  // (a NaN fails the comparison)
+    if (const int rc = query_state(c, what)) return rc;
+    if (!c->wn_ready) return fail(CAP_ERR_STATE, "%s: call cap_winding_build first", what);
+    if (n == 0) return CAP_OK;
+    if (!points || !winding) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("winding", winding, sizeof(float), 4),
+                                              range("visits", visits, 2 * sizeof(uint32_t), 4)}))
+        return rc;
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    return for_each_chunk(run, points, n, [&](const QueryArgs& chunk, uint64_t first) {
+        launch_winding_numbers(run.cfg, run.bvh, WindingArgs{chunk.rays, chunk.n, c->wn_table.p, beta, winding + first, at(visits, 2 * first)}, c->bvh_info.max_depth);
+        return run.traced("k_winding", first);
+    });
+}
 }  // namespace
 
 extern "C" {
+
+int cap_winding_numbers(CapContext* c, const CapPointDesc* device_points, uint64_t n, float beta, float* device_winding, uint32_t* device_visits)
+{
+    return winding_query(c, "cap_winding_numbers", device_points, n, beta, device_winding, device_visits);
+}
 
 int cap_trace_rays(CapContext* c, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, uint32_t flags)
 {

@@ -74,6 +74,8 @@ int cap_scene_upload(CapContext* c, const float* positions, const float* normals
     c->obj_count   = 0;         // ... and the object table to its mesh table
     c->pn_ready    = false;     // ... and the pseudonormal table to its triangles
     c->pn_table.release();
+    c->wn_ready    = false;     // ... and the dipole table to its tree
+    c->wn_table.release();
     return CAP_OK;
 }
 

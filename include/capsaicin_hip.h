@@ -821,8 +821,8 @@ int cap_closest_instances_multi(CapContext* ctx, const CapPointDesc* device_poin
  * computation on the read-back table and the record's (u, v) is bit-identical.
  * Conventions are cap_closest_points' plus: device_signed is required and 4-byte aligned, no two of the three ranges overlap, and
  * CAP_ERR_STATE also without a table.  Nothing is written on an error; n above 2^24 is split into launches.
- * Not covered: the k-nearest forms, generalised winding numbers for open meshes.  The sign over instances:
- * cap_signed_distance_instances below. */
+ * Not covered: the k-nearest forms.  The sign over instances: cap_signed_distance_instances below.  A sign for meshes that are not
+ * closed: cap_winding_numbers further below. */
 typedef struct CapPseudonormalsInfo
 {
     uint32_t vertices;             /* welded positions of the live triangles */
@@ -880,10 +880,86 @@ int cap_signed_distance(CapContext* ctx, const CapPointDesc* device_points, uint
  * does nothing.  Asynchronous on the context stream; nothing of the render's state is touched.
  * Pruning never decides: the world walk is cap_closest_instances', the object-space walk cap_closest_points' with the scene's slack
  * (DESIGN.md "Signed distance over instances").
- * Not covered: the sign of the k-nearest forms, generalised winding numbers for open meshes. */
+ * Not covered: the sign of the k-nearest forms. */
 int cap_signed_distance_instances(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, CapClosest* device_out,
                                   uint32_t* device_instances /* may be NULL */, float* device_signed,
                                   const CapTraceOptions* options /* may be NULL */);
+
+/* ---- winding numbers: the dipole table and cap_winding_numbers ----
+ * The generalised winding number (Jacobson et al. 2013) w(q) = (1 / 4 pi) sum_t Omega_t(q), Omega_t the signed solid angle triangle t
+ * subtends at q: 1 inside and 0 outside a closed mesh wound outwards (the side the ray queries call front), 5/6 at the centre of a
+ * cube with one face removed, and degrading smoothly with holes, duplicated triangles and self-intersections.  w >= 1/2 is the usual
+ * robust inside test for voxelisation, point classification and distance-field baking where cap_signed_distance's sign does not apply
+ * (CapPseudonormalsInfo.closed == 0).  The exact sum costs O(T) per point; the walk answers in O(log T) by replacing far subtrees with
+ * their first-order dipole (Barill et al. 2018).
+ *
+ * The table (cap_winding_build) hangs a dipole on every child of the scene's binary tree: one 64-byte record per inner node, indexed as
+ * cap_bvh_readback's nodes, 8 floats per child slot (slot 0, then slot 1):
+ *   words 0..2  p~, the area-weighted centroid of the child's subtree
+ *   word  3     r, the radius of a ball about the stored p~ that covers the child's stored box
+ *   words 4..6  N = sum of 1/2 (v1 - v0) x (v2 - v0) over the subtree
+ *   word  7     the child's code exactly as the tree holds it for traversal (words 14 and 15 of the node): a node index, or the leaf
+ *               code ~(first | (count - 1) << 27) of a range of the leaf order
+ * so the query reads one record per node step and never the box nodes.  A child's subtree is what lies below that code: the range of
+ * a leaf code, both slots of a node index.  From the scene's ORIGINAL vertices, in binary64:
+ *   triangle    n_t = 1/2 (v1 - v0) x (v2 - v0), a_t = |n_t| = sqrt((n.x*n.x + n.y*n.y) + n.z*n.z), c_t = ((v0 + v1) + v2) / 3;
+ *   degenerate  a triangle with a non-finite corner or n_t == 0 contributes nothing and is counted in CapWindingInfo;
+ *   sums        N = sum n_t, A = sum a_t, M = sum a_t c_t; a leaf code sums its triangles in leaf order starting from 0, a node index
+ *               adds slot 0 + slot 1 -- one fixed order, so the same tree and vertices give the same bytes on every run;
+ *   p~          M / A, or the centre 1/2 (lo + hi) of the child's stored box when A == 0; p~ and N are rounded once to binary32;
+ *   r           the distance from the STORED p~ to the farthest corner of the child's stored (padded) box,
+ *               sqrt((dx*dx + dy*dy) + dz*dz) with d_k = max(|lo_k - p~_k|, |hi_k - p~_k|), rounded to binary32 and stepped one ulp up.
+ * Every inner node has a record, also the nodes below a leaf code, which no walk reaches.  A tree whose root is a leaf (one triangle)
+ * has no records.  cap_winding_readback copies the table out, 16 floats per inner node.  CapWindingInfo: the inner nodes, the
+ * degenerate triangles, the total area A, N and p~ of the whole tree (p~ the centre of the scene bounds when A == 0), the wall time.
+ *
+ * Life cycle, cap_pseudonormals_*'s rule for rule: cap_winding_build needs a built tree that is not stale (CAP_ERR_STATE) and waits for
+ * the device once; out may be NULL.  cap_winding_drop frees the table (CAP_OK without one).  cap_winding_readback is CAP_ERR_STATE
+ * without a table or while the trees are stale.  cap_scene_upload drops the table; cap_scene_update_vertices makes it stale together
+ * with the trees; cap_bvh_build and cap_bvh_refit rebuild it by the same routine when one exists; cap_scene_set_instance_masks, objects
+ * and instances do not touch it.  It always covers every triangle, whatever the masks.  Memory: 64 B per inner node, plus about 180 B
+ * per triangle of build scratch that is freed when the build returns.
+ *
+ * cap_winding_numbers.  One walk per point q = device_points[i].point (the radius is not read), depth-first from the root with a
+ * binary64 accumulator.  At a node the two children are decided, all in binary32, every operation one rounded operation in the order
+ * written, no fused multiply-add, dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z:
+ *   d = fl(p~ - q), d2 = dot(d, d), lim = fl(beta * r); the child is FAR iff d2 > fl(lim * lim).
+ * A far child adds the term fl(dot(N, d) / fl(fl(k4 * d2) * sqrt(d2))), k4 = fl(4 pi) = 12.566371f, and counts in visits[0].  The far
+ * terms of a node are added first, slot 0 then slot 1; then the children that are not far are entered, slot 0's subtree before slot
+ * 1's.  A leaf code adds the exact term of each of its triangles in leaf order and adds their number to visits[1].  The exact term is
+ * Van Oosterom & Strackee's on the stored intersection record (v0, e1, e2, n = fl(e1 x e2)) of the ray queries:
+ *   a = fl(v0 - q), b = fl(a + e1), c = fl(a + e2), la = sqrt(dot(a, a)), lb = sqrt(dot(b, b)), lc = sqrt(dot(c, c)),
+ *   det = dot(a, n), den = (((la*lb)*lc + dot(a, b)*lc) + dot(b, c)*la) + dot(c, a)*lb,
+ *   term = fl(atan2f(det, den) * k2), k2 = fl(1 / (2 pi)) = 0.15915494f.
+ * A term that is NaN (a record with a non-finite word) adds nothing.  Each term is widened to binary64 and added; device_winding[i] is
+ * the accumulator rounded once to binary32.  The far / near decisions -- and so device_visits -- are reproducible bit for bit by a
+ * float32 restatement on the read-back tree and table; the value is reproducible run to run and depends on the device's atan2f, sqrt
+ * and division only within their rounding.  A root that is a leaf is summed exactly.
+ * beta must be finite and >= 1, or +inf (anything else, NaN included: CAP_ERR_INVALID_ARG).  Larger is more exact and slower; 2 keeps
+ * the error near 0.05 on closed test meshes, ample for the 1/2 threshold and not a precision claim.  +inf makes every comparison
+ * false: the exact sum over all triangles.  A point with a non-finite coordinate gets a quiet NaN and visits (0, 0).  An empty scene
+ * gives 0.0.
+ * Conventions are the point queries': device pointers on the context's GPU -- device_points 16-byte aligned, device_winding (4 B per
+ * point) and device_visits (8 B per point; may be NULL) 4-byte aligned --, no two ranges overlap; nothing is written on an error; n
+ * above 2^24 is split into launches, n = 0 does nothing; asynchronous on the context stream; nothing of the render's state is touched.
+ * CAP_ERR_STATE without a table, before cap_bvh_build and while the trees are stale.  There is no CapTraceOptions: the moments cover
+ * all triangles, so a mesh mask cannot be honoured.
+ * Not covered: instances and objects (w is additive over instances with the sign of det M; it needs moments in the top-level tree),
+ * masks, second- and third-order moments, a per-point beta, a wave-cooperative walk. */
+typedef struct CapWindingInfo
+{
+    uint32_t inner_nodes;          /* records in the table: triangles - 1, or 0 */
+    uint32_t degenerate_triangles;
+    double   total_area;           /* A of the whole tree */
+    float    root_n[3];            /* N of the whole tree: 0 for a closed mesh, up to rounding */
+    float    root_p[3];            /* p~ of the whole tree */
+    double   ms;                   /* wall time of the build */
+} CapWindingInfo;
+int cap_winding_build(CapContext* ctx, CapWindingInfo* out /* may be NULL */);
+int cap_winding_drop(CapContext* ctx);
+int cap_winding_readback(CapContext* ctx, float* host_table /* 16 floats per inner node */);
+int cap_winding_numbers(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, float beta, float* device_winding,
+                        uint32_t* device_visits /* may be NULL: 2 per point */);
 
 /* ---- objects: per-mesh-range bottom-level trees for the instanced queries ----
  * An object is the mesh range [first_mesh, first_mesh + mesh_count) of the uploaded scene: mesh_count >= 1, at least one triangle,

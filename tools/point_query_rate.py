@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Throughput of the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances,
-cap_closest_instances_multi, cap_signed_distance_instances) on the 262 k-triangle hall -- not part of bench.py, no pass mark.
+cap_closest_instances_multi, cap_signed_distance_instances) and of cap_winding_numbers on the 262 k-triangle hall -- not part of
+bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
-                                     [--k K [--counts]] [--instances N] [--signed]
+                                     [--k K [--counts]] [--instances N] [--signed] [--winding [--beta B]]
+
+--winding runs cap_winding_numbers at --beta B (default 2; inf sums every triangle exactly: use fewer --points) after
+cap_winding_build, on the same point sets (the radius is not read).  Each line carries its rate, mean_visits = the mean numbers of
+dipole terms and of exact triangle terms per point, inside (the share of points with w >= 1/2), and the table build:
+table_build_ms beside the tree's bvh_build_ms, and the table's statistics.
 
 --signed runs cap_signed_distance after cap_pseudonormals_build.  Each line carries its rate and, measured in the same process on the
 same points, cap_closest_points as the baseline (flat_ms, flat_mpoints_per_s, time_over_flat = the signed call's time over the plain
@@ -98,7 +104,11 @@ def main():
     ap.add_argument("--counts", action="store_true")
     ap.add_argument("--instances", type=int, default=None)
     ap.add_argument("--signed", action="store_true")
+    ap.add_argument("--winding", action="store_true")
+    ap.add_argument("--beta", type=float, default=2.0)
     a = ap.parse_args()
+    if a.winding and (a.signed or a.k is not None or a.instances is not None):
+        ap.error("--winding goes alone: the winding number takes no sign table, pages or instances")
     if a.signed and a.k is not None:
         ap.error("--signed does not go with --k: the sign is defined for the single record")
     if a.instances is not None and a.instances < 1:
@@ -144,6 +154,24 @@ def main():
         flat_out = torch.empty((n, 8), dtype=torch.float32, device=dev)
         plain_inst = torch.empty((n,), dtype=torch.int32, device=dev) if inst_signed else None
     head = dict(scene="hall", triangles=int(info.triangle_count), depth=int(info.max_depth), n=n, radius=a.radius, reps=a.reps)
+    if a.winding:
+        wn = r.build_winding()
+        w = torch.empty((n,), dtype=torch.float32, device=dev)
+        visits = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        for name, xyz in sets:
+            q = np.zeros((n, 4), np.float32)
+            q[:, 0:3] = xyz
+            pts = torch.as_tensor(q, device=dev).contiguous()
+            torch.cuda.synchronize()
+            sec = timed(r, lambda: capi._check(L.cap_winding_numbers(r.ctx, pts.data_ptr(), n, a.beta, w.data_ptr(), visits.data_ptr()), "cap_winding_numbers"),
+                        a.reps, a.warmup)
+            mean = visits.double().mean(0).cpu().numpy()
+            print(json.dumps(dict(head, set=name, beta=a.beta, ms=round(sec * 1e3, 3), mpoints_per_s=round(n / sec / 1e6, 2),
+                                  mean_visits=[round(float(mean[0]), 2), round(float(mean[1]), 2)], inside=round(float((w >= 0.5).float().mean()), 4),
+                                  table_build_ms=round(wn.ms, 3), bvh_build_ms=round(info.build_ms, 3),
+                                  table={k: v for k, v in wn.as_dict().items() if k != "ms"})), flush=True)
+        r.close()
+        return
     if a.k is not None:
         head.update(k=a.k, counts=a.counts)
     for name, xyz in sets:
