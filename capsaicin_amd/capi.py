@@ -565,7 +565,7 @@ class Renderer:
     BVH_BUILD_AUTO, BVH_BUILD_LBVH, BVH_BUILD_SAH, BVH_BUILD_PLOC, BVH_BUILD_SAH_DEVICE = 0, 1, 2, 3, 4  # CapBvhBuild
 
     def set_bvh_build(self, mode):
-        """0 auto (clustering build on the device above 64 triangles), 1 Morton hierarchy on the device, 2 SAH on the host, 3 clustering,
+        """0 auto (Morton hierarchy up to 64 triangles, clustering build above, device SAH from 4096 on), 1 Morton hierarchy on the device, 2 SAH on the host, 3 clustering,
         4 SAH on the device (surface-area splits down to small segments, clustering inside)."""
         _check(lib().cap_set_bvh_build(self.ctx, mode), "cap_set_bvh_build")
 

@@ -4,8 +4,9 @@
 // assignment, both leaf orders of the intersection records.  Only what the build derives from the vertices is recomputed, with the
 // build's own arithmetic: triangle setup (bvh.hip k_tri_setup), the binary boxes by the build's climb (bvh.hip k_refit) over parent
 // links derived from the nodes, the wide planes bottom-up through the collapse's quantiser (cap_wide_quant.h).  With unchanged
-// positions the trees come out byte for byte as the build left them; with moved ones the hits are those of a fresh build of the moved
-// scene (the hit rule never looks at boxes; DESIGN.md "Intersection contract").
+// positions the trees come out byte for byte as the build left them (one exception: where the device SAH build halved a segment by
+// position it stored the segment's box for both children, ploc.hip k_sah_split; the climb leaves each child's own union); with moved
+// ones the hits are those of a fresh build of the moved scene (the hit rule never looks at boxes; DESIGN.md "Intersection contract").
 //
 // One stream, no host round trip inside: the caller reads the scene bounds once (the wide padding depends on them) and syncs once.
 #include "cap_kernels.h"

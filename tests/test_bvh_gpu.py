@@ -78,8 +78,13 @@ def check_tree(nodes, leaves, tri_lo, tri_hi):
     return max_depth
 
 
-@pytest.mark.parametrize("build", [1, 2, 3, 4])  # on-device LBVH, host-side SAH, on-device clustering, on-device SAH: same layout, same invariants
-@pytest.mark.parametrize("seed,ntri", [(1, 1), (2, 2), (3, 3), (4, 33), (5, 1000), (6, 20000)])
+# on-device LBVH, host-side SAH, on-device clustering, on-device SAH: same layout, same invariants; the device builders also past one
+# scan tile of the radix sort's histogram (32768 triangles) and into its third
+INVARIANT_CASES = [(seed, ntri, build) for seed, ntri in [(1, 1), (2, 2), (3, 3), (4, 33), (5, 1000), (6, 20000)] for build in (1, 2, 3, 4)]
+INVARIANT_CASES += [(seed, ntri, build) for seed, ntri in [(7, 32769), (8, 65537)] for build in (1, 3, 4)]
+
+
+@pytest.mark.parametrize("seed,ntri,build", INVARIANT_CASES)
 def test_lbvh_invariants(native_lib, bluenoise, seed, ntri, build):
     pos, nrm, uv, idx, meshes = soup(seed, ntri)
     r = capi.Renderer(0)
