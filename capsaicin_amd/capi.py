@@ -646,6 +646,8 @@ class Renderer:
     DEBUG_MARK_FORM = 15  # form << 8 | dense; form 0 none, 1 by id, 2 carry chain, 3 carry chain over two words
     DEBUG_SAMPLE_TABLE = 16  # 1: the last render's fused launches took the direction-sample terms from the per-batch table
     DEBUG_SELFTEST_SAMPLE_TABLE = 17  # mismatching entries << 32 | (bounce, slot) rows of the last batch's table compared
+    DEBUG_CAMERA_TABLE = 18  # 1: the last render ran bounce 0 inside bounce 1's launch, from the per-batch table of camera vertices
+    DEBUG_SELFTEST_CAMERA_TABLE = 19  # mismatching entries << 32 | jitter groups << 16 | frame slots of the last batch compared
 
     def debug_set(self, key, value):
         _check(lib().cap_debug_set(self.ctx, key, value), "cap_debug_set")

@@ -200,6 +200,12 @@ struct CapContext
         const FrameConst* frames = nullptr;    // its frame constants (a slot of frames_ring: intact until kFrameRing calls later)
         uint32_t          n_slots = 0, num_bounces = 0, lane = 0;
     } last_terms;
+    uint32_t      last_camera_table = 0;       // 1: the last batch of the last cap_render ran bounce 0 from the camera-vertex table (CAP_DEBUG_CAMERA_TABLE)
+    struct LastCamera                          // that table (CAP_DEBUG_SELFTEST_CAMERA_TABLE): the batch's frame constants, slots, groups and lane
+    {
+        const FrameConst* frames = nullptr;
+        uint32_t          n_slots = 0, n_groups = 0, lane = 0;
+    } last_camera;
     uint32_t      last_cull_camera_pairs = 0;  // ShadeArgs::cull_camera_pairs of the last cap_render batch (CAP_DEBUG_CAMERA_CULL)
     uint32_t      traversal_mode  = CAP_TRAVERSAL_AUTO;
     uint32_t      bvh_build_mode  = CAP_BVH_BUILD_AUTO;
@@ -215,6 +221,7 @@ struct CapContext
     {
         hipStream_t      stream = nullptr;  // not owned: the context's `stream` (lane 0) or `stream2` (lane 1)
         DevBuf<float4>   hits, q_org[2], q_dir[2], q_thr[2], s_org, s_dir, s_con, pl_color, pl_direct, pl_albedo;
+        DevBuf<float4>   camera;       // per batch: camera vertices, two planes [jitter group][Ppad] (launch_camera_vertices), if the form is on
         DevBuf<float4>   terms;        // per batch: direction-sample terms [sampling bounce][slot][4096] (ShadeArgs::sample_terms), if the form is on
         DevBuf<uint32_t> counters;     // per batch: ext[0..D], shadow[0..D]
         DevBuf<uint32_t> stack_spill;  // traversal-stack entries beyond the LDS part, per thread of the persistent grid

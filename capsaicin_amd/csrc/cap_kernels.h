@@ -42,6 +42,7 @@ enum CapSwitch : uint32_t
     SW_RAYGEN_KERNEL,       // dense scenes: the camera rays' identity queue written out by k_raygen_identity instead of generated in the trace kernel
     SW_NO_PLANE_CODE,       // small-scene path under albedo_in_w: bounce 0 writes the constant direct plane as before (ShadeArgs::code_in_color off)
     SW_SAMPLE_TABLE,        // small-scene path, reference model: 0 never, 1 whenever the kernels have the form: direction-sample terms from the batch's table (ShadeArgs::sample_terms)
+    SW_NO_CAMERA_TABLE,     // small-scene path, reference model: bounce 0 stays a launch of its own (no camera-vertex table, no bounce-0 head in bounce 1's launch)
     SW_COUNT
 };
 struct SwitchTable
@@ -367,7 +368,12 @@ void launch_shade(const LaunchCfg& cfg, const ShadeArgs& args, bool ext, bool fe
 bool launch_primary_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, float4* hits, bool ext);
 // small-scene path: exhaustive closest hit fused with the shading of the vertex found (bounce 0 generates the camera rays)
 // returns how the launched kernel builds the closest-hit candidate mask (CAP_DEBUG_MARK_FORM's form)
-uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback = false);
+// camera_head: args.bounce == 1 and the launch does bounce 0 as well, as the head of every chunk of bounce 0's identity queue, from the
+// batch's table of camera vertices: args.in.org_tmin / dir_tmax = the table's two planes (launch_camera_vertices), args.in.thr_pid =
+// bounce 0's block of the sample table, args.in.count = bounce 0's counter lines; args.frames[s].pad1 = slot s's jitter group.  Needs
+// sample_terms, inline_probe and wave_ring, and a batch whose colour plane carries the code (code_in_color).  Its bounce-0 shadow rays go
+// through the wave rings: no any-hit launch follows bounce 0.
+uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback = false, bool camera_head = false);
 // whether the reference model's bounce 0 of this scene has the form ShadeArgs::code_in_color asks for (the kernel of tame records in LDS)
 bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene);
 // ... and the form ShadeArgs::sample_terms asks for (the lean kernels)
@@ -378,6 +384,12 @@ void launch_sample_terms(hipStream_t stream, const float2* bluenoise, const Fram
 // out_device[0] += entries of such a table that differ from the per-vertex evaluation in any bit, out_device[1] += entries compared
 void launch_sample_terms_selftest(hipStream_t stream, const float2* bluenoise, const FrameConst* frames, uint32_t n_slots, uint32_t num_bounces,
                                   const float4* table, unsigned long long* out_device);
+
+// The batch's table of camera vertices (small_scene.hip k_camera_vertices): one entry per (jitter group, padded pixel), rows = groups;
+// args.frames[g].pad2 = the first slot of group g.  selftest_out != null: rows = the batch's slots, nothing is written, every slot's own
+// bounce-0 vertex is compared with the entry of its group (args.frames[s].pad1): out[0] += mismatches, out[1] += entries compared.
+void launch_camera_vertices(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, uint32_t rows, float4* tab_p, float4* tab_n,
+                            unsigned long long* selftest_out = nullptr);
 
 // ---- accumulate / exchange ----
 // accum[pl] += sum over slots (in slot order) of color*albedo + direct; .w counts frames.

@@ -283,10 +283,10 @@ SceneDev scene_dev(const CapContext* c)
 // cap_render tests to learn whether a call grows a lane (growing frees the old buffers, so the streams are drained first)
 struct LaneSizes
 {
-    size_t planes, queues, rings, counters, terms;
+    size_t planes, queues, rings, counters, terms, camera;
 };
 
-LaneSizes lane_sizes(const CapContext* c, uint32_t slots, uint32_t bounces, bool sample_table)
+LaneSizes lane_sizes(const CapContext* c, uint32_t slots, uint32_t bounces, bool sample_table, uint32_t camera_groups)
 {
     LaneSizes z;
     z.planes = (size_t)slots * c->screen.pixels_padded;
@@ -298,20 +298,23 @@ LaneSizes lane_sizes(const CapContext* c, uint32_t slots, uint32_t bounces, bool
     z.counters = (3 * (size_t)(bounces + 1) + 1) * kQueueClasses * kCounterStride;  // + 1: the camera rays' identity queue
     // the table of direction-sample terms (ShadeArgs::sample_terms): 4096 entries per frame slot and sampling bounce, 32 MB at 64 x 8
     z.terms = sample_table ? (size_t)slots * bounces * 4096 : 0;
+    // the table of camera vertices (launch_camera_vertices): two planes of one entry per (jitter group, padded pixel), 0.5 GB at 8 groups of 1080p
+    z.camera = 2 * (size_t)camera_groups * c->screen.pixels_padded;
     return z;
 }
 
-bool lane_grows(const CapContext::Lane& L, const LaneSizes& z) { return L.pl_color.n < z.planes || L.counters.n < z.counters || L.terms.n < z.terms; }
+bool lane_grows(const CapContext::Lane& L, const LaneSizes& z) { return L.pl_color.n < z.planes || L.counters.n < z.counters || L.terms.n < z.terms || L.camera.n < z.camera; }
 
-int ensure_lane(CapContext* c, CapContext::Lane& L, uint32_t slots, uint32_t bounces, bool sample_table)
+int ensure_lane(CapContext* c, CapContext::Lane& L, uint32_t slots, uint32_t bounces, bool sample_table, uint32_t camera_groups)
 {
-    const LaneSizes z = lane_sizes(c, slots, bounces, sample_table);
+    const LaneSizes z = lane_sizes(c, slots, bounces, sample_table, camera_groups);
     for (DevBuf<float4>* b : {&L.hits, &L.q_org[0], &L.q_org[1], &L.q_dir[0], &L.q_dir[1], &L.q_thr[0], &L.q_thr[1], &L.s_dir})
         HIP_TRY(b->ensure(z.queues));
     for (DevBuf<float4>* b : {&L.s_org, &L.s_con}) HIP_TRY(b->ensure(z.rings));
     for (DevBuf<float4>* b : {&L.pl_color, &L.pl_direct, &L.pl_albedo}) HIP_TRY(b->ensure(z.planes));
     HIP_TRY(L.counters.ensure(z.counters));
     if (z.terms) HIP_TRY(L.terms.ensure(z.terms));
+    if (z.camera) HIP_TRY(L.camera.ensure(z.camera));
     // as much spill as lane 0, whose area cap_bvh_build allocates (for lane 0 itself: nothing to do)
     if (c->lane[0].stack_spill.n) HIP_TRY(L.stack_spill.ensure(c->lane[0].stack_spill.n));
     return CAP_OK;
@@ -453,7 +456,7 @@ static const char* const kSwitchNames[SW_COUNT] = {
     "CAP_NO_WIDE8", "CAP_LANE1_PRIORITY", "CAP_PLOC_RADIUS", "CAP_SAHDEV_LEAF", "CAP_WIDE_HOST_COLLAPSE", "CAP_TRACE_LAUNCHES", "CAP_NO_TWO_LANES",
     "CAP_LANE_SPLIT_MIN", "CAP_BLOCKS_PER_CU", "CAP_NO_CAMERA_CULL", "CAP_NO_ALBEDO_IN_W", "CAP_NO_INLINE_NEE", "CAP_NO_INLINE_PROBE", "CAP_NO_WAVE_RING",
     "CAP_ANY_REFILL", "CAP_PRIMARY_WIDE", "CAP_NO_PACKET", "CAP_NO_ANY_PROBE", "CAP_ANY_PROBE", "CAP_ANY_BLOCKS", "CAP_NO_PRIMARY_FUSE", "CAP_W8_REFILL",
-    "CAP_W8_GRID", "CAP_AUTO_SAH_TRIANGLES", "CAP_NO_NEE_PAIR_CULL", "CAP_RAYGEN_KERNEL", "CAP_NO_PLANE_CODE", "CAP_SAMPLE_TABLE"};
+    "CAP_W8_GRID", "CAP_AUTO_SAH_TRIANGLES", "CAP_NO_NEE_PAIR_CULL", "CAP_RAYGEN_KERNEL", "CAP_NO_PLANE_CODE", "CAP_SAMPLE_TABLE", "CAP_NO_CAMERA_TABLE"};
 
 static void switches_from_environment(SwitchTable& t)
 {
@@ -802,6 +805,32 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
         *value = (h[0] << 32) | (expected >> 12);  // mismatches << 32 | (bounce, slot) rows compared
         return CAP_OK;
     }
+    case CAP_DEBUG_CAMERA_TABLE: *value = c->last_camera_table; return CAP_OK;
+    case CAP_DEBUG_SELFTEST_CAMERA_TABLE:
+    {
+        const CapContext::LastCamera& lc = c->last_camera;
+        if (!c->last_camera_table || !lc.frames) return fail(CAP_ERR_STATE, "cap_debug_get: the last cap_render built no camera table");
+        HIP_TRY(hipSetDevice(c->device));
+        if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
+        DevBuf<unsigned long long> d;
+        unsigned long long         h[2] = {0, 0};
+        HIP_TRY(d.ensure(2));
+        HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(h), c->stream));
+        // the launch arguments the table was built with (camera, screen and scene as they are now: ask right after the render)
+        ShadeArgs sa{};
+        sa.scene = scene_dev(c), sa.cam = camera_dev(c->camera), sa.screen = c->screen, sa.frames = lc.frames, sa.n_slots = lc.n_slots;
+        sa.cull_camera_pairs = c->last_cull_camera_pairs;
+        LaunchCfg     cfg{c->stream, (uint32_t)c->cu_count * 6u, 0u, (uint32_t)c->cu_count};
+        float4* const tab = c->lane[lc.lane].camera.p;
+        launch_camera_vertices(cfg, bvh_dev(c, c->lane[lc.lane]), sa, lc.n_slots, tab, tab + (size_t)lc.n_groups * c->screen.pixels_padded, d.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const unsigned long long expected = (unsigned long long)lc.n_slots * c->screen.pixels_padded;
+        if (h[1] != expected) return fail(CAP_ERR_HIP, "cap_debug_get: the camera table self-test compared %llu of %llu entries", h[1], expected);
+        *value = (h[0] << 32) | ((uint64_t)lc.n_groups << 16) | lc.n_slots;  // mismatches << 32 | groups << 16 | slots compared
+        return CAP_OK;
+    }
     case CAP_DEBUG_NEE_PAIRS:
         if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_debug_get: BVH not built");
         *value = ((uint64_t)(c->fan_pairs_nee.p ? c->fan_pair_nee_count : c->fan_pair_count) << 32) | c->fan_pair_count;
@@ -932,9 +961,46 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
     const bool sample_table = fused && !ext && !feedback && num_bounces >= 1 && c->sw.get(SW_SAMPLE_TABLE, 1) != 0 &&
                               trace_shade_has_table_form(bvh_dev(c, c->lane[0]), scene_dev(c));
     c->last_sample_table = sample_table ? 1u : 0u;
-    const LaneSizes need = lane_sizes(c, slots, num_bounces, sample_table);
+    // Bounce 0 inside bounce 1's launch, from a table of camera vertices (launch_camera_vertices, launch_trace_shade's camera_head): decided
+    // once per call.  The lean table kernels of an untextured scene in an accumulate-only render, whose colour plane carries the first
+    // vertex's code and whose shadow rays go through the wave rings -- the conditions of albedo_in_w, code_in_color, inline_probe and
+    // wave_ring below, which a batch repeats for itself (the rings' size is the one it alone knows).  A/B switch CAP_NO_CAMERA_TABLE.
+    const bool camera_table = sample_table && !lowres && !(flags & CAP_RENDER_AOV) && !c->sw.on(SW_NO_CAMERA_TABLE) && !c->sw.on(SW_NO_ALBEDO_IN_W) &&
+                              !c->sw.on(SW_NO_PLANE_CODE) && !c->sw.on(SW_NO_INLINE_PROBE) && !c->sw.on(SW_NO_WAVE_RING) && c->debug_capacity_div <= 1 &&
+                              c->texture_host.empty() && trace_shade_has_code_form(bvh_dev(c, c->lane[0]), scene_dev(c));
+    c->last_camera_table = 0;
+    c->last_camera       = CapContext::LastCamera{};
+    // Jitter groups: the slots of a batch by the bits of (jitter_x, jitter_y).  slot_group[f]: the group of frame f within its batch,
+    // numbered in order of first appearance; group_first[batch start + g]: the first slot of group g.  A group need not be contiguous.
+    std::vector<uint32_t> slot_group, group_first, batch_groups;
+    uint32_t              camera_groups = 0;
+    if (camera_table)
+    {
+        slot_group.resize(n_frames), group_first.assign(n_frames, 0u);
+        for (uint32_t done = 0; done < n_frames; done += slots)
+        {
+            const uint32_t ns = std::min(slots, n_frames - done);
+            uint32_t       ng = 0;
+            for (uint32_t s = 0; s < ns; ++s)
+            {
+                float sx, sy, gx, gy;  // frame_const()'s jitter
+                halton23(frame_begin + done + s, sx, sy);
+                uint32_t g = 0;
+                for (; g < ng; ++g)
+                {
+                    halton23(frame_begin + done + group_first[done + g], gx, gy);
+                    if (memcmp(&gx, &sx, sizeof(float)) == 0 && memcmp(&gy, &sy, sizeof(float)) == 0) break;
+                }
+                if (g == ng) group_first[done + ng++] = s;
+                slot_group[done + s] = g;
+            }
+            batch_groups.push_back(ng);
+            camera_groups = std::max(camera_groups, ng);
+        }
+    }
+    const LaneSizes need = lane_sizes(c, slots, num_bounces, sample_table, camera_groups);
     if (lane_grows(c->lane[0], need) || !c->accum.p || c->accum.n < Ppad) HIP_TRY(hipStreamSynchronize(c->stream));
-    if (ensure_lane(c, c->lane[0], slots, num_bounces, sample_table) != CAP_OK || ensure_frame_buffers(c) != CAP_OK) return CAP_ERR_HIP;
+    if (ensure_lane(c, c->lane[0], slots, num_bounces, sample_table, camera_groups) != CAP_OK || ensure_frame_buffers(c) != CAP_OK) return CAP_ERR_HIP;
     if (policy.lane1_failed_before)
     {
         // this size has already failed: one lane, without asking again -- except every 32nd time, and at once when the device reports
@@ -954,7 +1020,7 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
             HIP_TRY(hipStreamSynchronize(c->stream));  // growing frees the old buffers
             if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
         }
-        if (c->debug_fail_lane || ensure_lane(c, c->lane[1], slots, num_bounces, sample_table) != CAP_OK || ensure_lane_streams(c) != CAP_OK)
+        if (c->debug_fail_lane || ensure_lane(c, c->lane[1], slots, num_bounces, sample_table, camera_groups) != CAP_OK || ensure_lane_streams(c) != CAP_OK)
         {
             // the second working set doubles the batch's memory (~28 GB at the default budget): without it the batches of this call
             // simply run one after the other on lane 0 -- counted in CapStats::lane1_dropped, and not tried again at this
@@ -983,7 +1049,12 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
         HIP_TRY(hipHostMalloc((void**)&c->frames_pinned[ring], sizeof(FrameConst) * n_frames, hipHostMallocDefault));
         c->frames_pinned_n[ring] = n_frames;
     }
-    for (uint32_t f = 0; f < n_frames; ++f) c->frames_pinned[ring][f] = frame_const(frame_begin + f, lowres);
+    for (uint32_t f = 0; f < n_frames; ++f)
+    {
+        FrameConst& fc = c->frames_pinned[ring][f] = frame_const(frame_begin + f, lowres);
+        // the two words nothing else reads in memory: the slot's jitter group, and the first slot of the group of this number
+        if (camera_table) memcpy(&fc.pad1, &slot_group[f], 4), memcpy(&fc.pad2, &group_first[f], 4);
+    }
     HIP_TRY(hipMemcpyAsync(c->frames_ring[ring].p, c->frames_pinned[ring], sizeof(FrameConst) * n_frames, hipMemcpyHostToDevice, c->stream));
     const bool st = (flags & CAP_RENDER_STAGE_TIMERS) != 0;
     if (c->textures_dirty)
@@ -1141,7 +1212,25 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
             c->last_terms = CapContext::LastTerms{frames, ns, D, lane};
             if (trace_launch(c, "sample_terms batch %u", batch)) return fail(CAP_ERR_HIP, "sample_terms failed");
         }
-        for (uint32_t b = 0; b <= D; ++b)
+        // The camera-vertex form of this batch: bounce 0's rays once per jitter group into the table, its per-slot remainder at the head of
+        // bounce 1's launch; no bounce-0 launch and no any-hit launch.  No gate on the slots per group: with ONE slot per group, where no
+        // camera ray is shared, the form is still the faster one -- 1080p, tools/camera_table_small.py, ms per render off -> on: 1 slot
+        // depth 1 0.1515 -> 0.1316, depth 2 0.2164 -> 0.1976; 2 slots 0.2261 -> 0.2017 and 0.3241 -> 0.2992 (docs/experiments.md (104)).
+        const bool     camera_head = camera_table && sa.code_in_color && sa.wave_ring;
+        const uint32_t n_groups    = camera_head ? batch_groups[batch] : 0u;
+        float4* const  tab_p = L.camera.p, *const tab_n = L.camera.p + (size_t)n_groups * Ppad;
+        if (camera_head)
+        {
+            StageTimer t(c, ST_PRIMARY, st);
+            launch_camera_vertices(cfg, bvh, sa, n_groups, tab_p, tab_n);
+            c->last_camera = CapContext::LastCamera{frames, ns, n_groups, lane};
+            // every CapStats field keeps its value between the two forms: bounce 0's shadow rays are still one any-hit pass of the batch,
+            // traced inside the fused launch instead of by a launch of their own
+            ++c->stats.launches_trace_any;
+            if (trace_launch(c, "camera_vertices batch %u", batch)) return fail(CAP_ERR_HIP, "camera_vertices failed");
+        }
+        c->last_camera_table = camera_head ? 1u : 0u;
+        for (uint32_t b = camera_head ? 1u : 0u; b <= D; ++b)
         {
             const int pi = (int)(b & 1u), po = pi ^ 1;
             sa.bounce    = b;
@@ -1154,10 +1243,13 @@ int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t 
                                     po ? L.s_dir.p : L.s_org.p};
             sa.shadow    = ShadowQueue{L.s_org.p, L.s_dir.p, L.s_con.p, sh_count + b * per_queue, class_capacity};
             sa.work      = work_shade + b * per_queue;
+            const bool head = camera_head && b == 1;
+            // (the input queue of that launch is bounce 0's identity queue: its three planes carry the table and bounce 0's sample terms)
+            if (head) sa.in = RayQueue{tab_p, tab_n, L.terms.p, ext_count, class_capacity, nullptr};
             if (fused)
             {
                 StageTimer t(c, b == 0 ? ST_PRIMARY : ST_CLOSEST, st);
-                const uint32_t form = launch_trace_shade(cfg, bvh, sa, ext, feedback);
+                const uint32_t form = launch_trace_shade(cfg, bvh, sa, ext, feedback, head);
                 if (b) ++c->stats.launches_trace_closest, c->last_mark_form = form;
                 if (trace_launch(c, "trace_shade bounce %u batch %u", b, batch)) return fail(CAP_ERR_HIP, "trace_shade failed");
             }

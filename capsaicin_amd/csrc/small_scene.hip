@@ -2,6 +2,7 @@
 // launcher, the per-phase clocks of the diagnostic build and the device self-test of the unscaled shading forms.
 #include "cap_shade.h"
 
+#include <algorithm>
 #include <cassert>
 
 namespace cap
@@ -31,14 +32,18 @@ __device__ unsigned long long g_wave_times[2 * 16384];  // (start, end) s_memrea
 // CODE: ShadeArgs::code_in_color, bounce 0's form without the direct plane.  Only the TAME kernel has it (trace_shade_has_code_form).
 // TAB: the terms of a vertex's direction sample come from the batch's table (ShadeArgs::sample_terms, k_sample_terms below) and no
 // queue entry carries a sample.  Only the lean kernels have the form (trace_shade_has_table_form).
-template <bool FIRST_, bool EXT_, bool FB_, bool LDS_, bool TAME_, bool CODE_ = false, bool TAB_ = false>
+// HEAD: the batch's first bounce >= 1 launch with bounce 0 inside it (ShadeArgs::in re-used for the camera table, see k_camera_vertices
+// below): the queue is bounce 0's identity queue, a chunk starts with the per-slot remainder of bounce 0 on its table entry and keeps the
+// ray that makes in registers.  Only the TAB bounce >= 1 kernel has the form (k_trace_shade_head).
+template <bool FIRST_, bool EXT_, bool FB_, bool LDS_, bool TAME_, bool CODE_ = false, bool TAB_ = false, bool HEAD_ = false>
 struct TraceShadeCfg
 {
     // (TAB_ = kChunkLean in k_trace_shade_tab: a build without the lean plumbing compiles the plain kernel under that name, never launched)
     static_assert(!TAME_ || (!EXT_ && !FB_ && LDS_), "TAME: reference model, scene in LDS");
     static_assert(!CODE_ || (FIRST_ && TAME_), "CODE: bounce 0 of the reference model, scene in LDS, tame records");
     static_assert(!TAB_ || (TAME_ && kChunkLean), "TAB: the lean kernels (reference model, scene in LDS, tame records)");
-    static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_, LDS = LDS_, TAME = TAME_, CODE = CODE_, TAB = TAB_;
+    static_assert(!HEAD_ || (TAB_ && !FIRST_), "HEAD: the lean bounce >= 1 kernel with the sample table");
+    static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_, LDS = LDS_, TAME = TAME_, CODE = CODE_, TAB = TAB_, HEAD = HEAD_;
     static constexpr bool CARRY = !EXT && !TAB, SKY_RMW = false;
     static constexpr bool PROBE = !EXT && !FB && LDS;  // the producer-side shadow probe (ShadeArgs::inline_probe) and the per-wave ring
     // the lean per-chunk plumbing (see kChunkLean): the reference model's kernels with the scene in LDS and tame records.  (The
@@ -146,8 +151,9 @@ __device__ __forceinline__ void stage_probe_rows(const BvhDev& bvh, const ShadeA
     }
 }
 
-// Both kernels are small_scene_body.h and nothing else: k_trace_shade the thirteen forms without the sample table, under the names and
-// with the instructions they have always had, k_trace_shade_tab the three with it.
+// All three kernels are small_scene_body.h and nothing else: k_trace_shade the thirteen forms without the sample table, under the names
+// and with the instructions they have always had, k_trace_shade_tab the three with it, k_trace_shade_head (below) bounce 1 with bounce 0
+// at the head of its chunks.
 template <bool FIRST, bool EXT, bool FB = false, bool LDS = false, bool TAME = false, bool CODE = false>
 __global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, EXT, FB, LDS, TAME, CODE>::kBlocksPerCu)) void k_trace_shade(BvhDev bvh, ShadeArgs a)
 {
@@ -161,6 +167,14 @@ __global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, false, false, true, t
 {
     using C            = TraceShadeCfg<FIRST, false, false, true, true, CODE, kChunkLean>;
     constexpr bool EXT = false, FB = false, LDS = true, TAB = kChunkLean;
+#include "small_scene_body.h"
+}
+
+// HEAD: bounce 1 of a batch with bounce 0 as the head of every chunk (TraceShadeCfg)
+__global__ __launch_bounds__(kBlock, (TraceShadeCfg<false, false, false, true, true, false, kChunkLean, kChunkLean>::kBlocksPerCu)) void k_trace_shade_head(BvhDev bvh, ShadeArgs a)
+{
+    using C              = TraceShadeCfg<false, false, false, true, true, false, kChunkLean, kChunkLean>;
+    constexpr bool FIRST = false, EXT = false, FB = false, LDS = true, TAB = kChunkLean;
 #include "small_scene_body.h"
 }
 
@@ -306,10 +320,103 @@ void launch_sample_terms_selftest(hipStream_t stream, const float2* bluenoise, c
     hipLaunchKernelGGL(k_sample_terms_selftest, dim3(rows * (4096u / kBlock)), dim3(kBlock), 0, stream, bluenoise, frames, n_slots, num_bounces, table, out_device);
 }
 
-// The sixteen instantiations that exist, each under the tuple it was instantiated with.  Bounce 0 has no feedback form, the two
+// ---- the table of camera vertices (the HEAD kernel).  The frame slots of a batch share few sub-pixel jitters (eight: halton23 of
+// frame_count mod 8), and bounce 0's camera ray, its closest hit and the vertex it interpolates depend on the slot through the jitter
+// alone.  The host groups the slots by the bits of (jitter_x, jitter_y) -- frames[s].pad1 = the group of slot s, frames[g].pad2 = the first
+// slot of group g -- and this kernel traces one camera ray per (group, padded pixel), one wave per 8 x 8 tile on a persistent grid:
+// tab_p[g * Ppad + pl] = (p, code), tab_n[g * Ppad + pl] = (n, 0), the code being the word bounce 0 puts into color.w (kCodePadding,
+// kCodeSky, kCodeKd, kCodeBlack; p = n = 0 without a vertex).  camera_vertex() is bounce 0's own sequence: the ray of
+// small_scene_body.h's FIRST branch, its tile's pair mask, exhaustive_closest<ORG>, and shade_vertex's record gather, p,
+// normalize3_tame(nm) and black test (untextured scene: the host's condition).  Same operations on the same operands: the same bits.
+__device__ __forceinline__ void camera_vertex(const BvhDev& bvh, const ShadeArgs& a, const FrameConst& fc, uint32_t i, const float4* lds_shade,
+                                              const float4* lds_rec, const float4* lds_org, const float4* lds_bounds, float4& cp, float4& cn)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    Ray            r    = make_ray(mk3(0.f, 0.f, 0.f), mk3(0.f, 0.f, 1.f), 0.0f, 0.0f);  // empty interval: hits nothing
+    uint32_t       x, y;
+    const bool     valid = local_pixel_to_xy(a.screen, i, x, y);
+    if (valid) r = make_ray(mk3(a.cam.position[0], a.cam.position[1], a.cam.position[2]), primary_dir(a.cam, a.screen, fc, x, y), 0.0f, kPrimaryFar);
+    uint32_t tx = 0, ty = 0;
+    (void)local_pixel_to_xy(a.screen, i & ~63u, tx, ty);  // first pixel of the 8x8 tile
+    const float4   b    = lds_bounds[lane < kExhaustiveMax / 2 ? lane : 0u];
+    const bool     over = lane < bvh.fan_pair_count && b.x < (float)(tx + 8u) && b.z >= (float)tx && b.y < (float)(ty + 8u) && b.w >= (float)ty;
+    const uint32_t pair_mask = (uint32_t)__ballot(over);
+    float          t, u, v;
+    uint32_t       gid;
+    exhaustive_closest<true, false>(bvh, lds_rec, r, t, u, v, gid, lds_org, pair_mask);
+    cp = make_float4(0.f, 0.f, 0.f, kCodePadding), cn = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (valid && gid == kInvalidId)
+        cp.w = kCodeSky;
+    else if (valid)
+    {
+        const float4* tab = lds_shade + kShadeRec * (size_t)gid;
+        const float4  s0 = tab[0], s1 = tab[1], s2 = tab[2], s3 = tab[3], s4 = tab[4], s5 = tab[5];
+        const float   w = (1.0f - u) - v;
+        auto          mix = [&](float c0, float c1, float c2) { return fmaf(c2, v, fmaf(c1, u, c0 * w)); };
+        const v3      nm = mk3(mix(s3.x, s4.x, s5.x), mix(s3.y, s4.y, s5.y), mix(s3.z, s4.z, s5.z));
+        const v3      n  = normalize3_tame(nm);
+        const v3      p  = mk3(mix(s0.x, s1.x, s2.x), mix(s0.y, s1.y, s2.y), mix(s0.z, s1.z, s2.z));
+        const float   kd = a.scene.kd_untextured;
+        cp = make_float4(p.x, p.y, p.z, kd < 1e-5f ? kCodeBlack : kCodeKd);
+        cn = make_float4(n.x, n.y, n.z, 0.0f);
+    }
+}
+// SELFTEST false: the table.  true (cap_debug_get(CAP_DEBUG_SELFTEST_CAMERA_TABLE)): one lane per (SLOT, padded pixel) evaluates bounce 0's
+// sequence with the slot's own frame constants and compares all eight words with the entry of the slot's group; out[0]: mismatches,
+// out[1]: entries compared.
+template <bool SELFTEST>
+__global__ __launch_bounds__(kBlock) void k_camera_vertices(BvhDev bvh, ShadeArgs a, uint32_t rows, float4* tab_p, float4* tab_n, unsigned long long* out)
+{
+    __shared__ float4 lds_shade[kShadeRec * kExhaustiveMax];
+    __shared__ float4 lds_rec[4 * kExhaustiveMax];
+    __shared__ float4 lds_org[kExhaustiveMax];
+    __shared__ float4 lds_bounds[kExhaustiveMax / 2];
+    stage_scene_records(bvh, a, lds_shade, lds_rec);
+    stage_camera_pairs(bvh, a, lds_org, lds_bounds);
+    __syncthreads();
+    const uint32_t Ppad = a.screen.pixels_padded, cps = Ppad >> 6, chunks = cps * rows, lane = threadIdx.x & 63u;
+    unsigned long long bad = 0, n = 0;
+    for (uint32_t chunk = wave_global_id(); chunk < chunks; chunk += gridDim.x * (kBlock / 64))
+    {
+        const uint32_t   row = chunk / cps, i = (chunk - row * cps) * 64 + lane;  // row: the group, or the slot (SELFTEST)
+        const FrameConst fc  = a.frames[SELFTEST ? row : f2u(a.frames[row].pad2)];
+        float4           cp, cn;
+        camera_vertex(bvh, a, fc, i, lds_shade, lds_rec, lds_org, lds_bounds, cp, cn);
+        const size_t at = (size_t)(SELFTEST ? f2u(fc.pad1) : row) * Ppad + i;
+        if (!SELFTEST)
+            tab_p[at] = cp, tab_n[at] = cn;
+        else
+        {
+            const float4 qp = tab_p[at], qn = tab_n[at];
+            const bool   differ = f2u(qp.x) != f2u(cp.x) || f2u(qp.y) != f2u(cp.y) || f2u(qp.z) != f2u(cp.z) || f2u(qp.w) != f2u(cp.w) ||
+                                f2u(qn.x) != f2u(cn.x) || f2u(qn.y) != f2u(cn.y) || f2u(qn.z) != f2u(cn.z) || f2u(qn.w) != f2u(cn.w);
+            bad += (unsigned long long)__popcll(__ballot(differ)), n += 64ull;
+        }
+    }
+    if (SELFTEST && lane == 0u)
+    {
+        if (bad) atomicAdd(&out[0], bad);
+        if (n) atomicAdd(&out[1], n);
+    }
+}
+
+void launch_camera_vertices(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, uint32_t rows, float4* tab_p, float4* tab_n,
+                            unsigned long long* selftest_out)
+{
+    assert(bvh.tri_count <= kExhaustiveMax && args.scene.shade_tame != 0 && args.scene.texture_count == 0);  // the host's condition for the form
+    const uint32_t chunks = (args.screen.pixels_padded >> 6) * rows;
+    if (!chunks) return;
+    const uint32_t gx = std::max(1u, std::min(cfg.grid_blocks, (chunks + kBlock / 64 - 1) / (kBlock / 64)));
+    if (selftest_out)
+        hipLaunchKernelGGL(k_camera_vertices<true>, dim3(gx), dim3(kBlock), 0, cfg.stream, bvh, args, rows, tab_p, tab_n, selftest_out);
+    else
+        hipLaunchKernelGGL(k_camera_vertices<false>, dim3(gx), dim3(kBlock), 0, cfg.stream, bvh, args, rows, tab_p, tab_n, selftest_out);
+}
+
+// The seventeen instantiations that exist, each under the tuple it was instantiated with.  Bounce 0 has no feedback form, the two
 // models and feedback exclude each other, TAME is the reference model with the scene in LDS, CODE its bounce 0 and TAB its three lean
 // kernels with the sample table (TraceShadeCfg).
-enum : uint32_t { TS_FIRST = 1, TS_EXT = 2, TS_FB = 4, TS_LDS = 8, TS_TAME = 16, TS_CODE = 32, TS_TAB = 64 };
+enum : uint32_t { TS_FIRST = 1, TS_EXT = 2, TS_FB = 4, TS_LDS = 8, TS_TAME = 16, TS_CODE = 32, TS_TAB = 64, TS_HEAD = 128 };
 struct TraceShadeKernel
 {
     uint32_t is;
@@ -318,7 +425,12 @@ struct TraceShadeKernel
 template <uint32_t IS>
 constexpr TraceShadeKernel trace_shade_kernel()
 {
-    if constexpr ((IS & TS_TAB) != 0)
+    if constexpr ((IS & TS_HEAD) != 0)
+    {
+        static_assert(IS == (TS_LDS | TS_TAME | TS_TAB | TS_HEAD), "HEAD: the lean bounce >= 1 kernel");
+        return {IS, k_trace_shade_head};
+    }
+    else if constexpr ((IS & TS_TAB) != 0)
     {
         static_assert((IS & ~(TS_FIRST | TS_CODE)) == (TS_LDS | TS_TAME | TS_TAB), "TAB: the lean kernels");
         return {IS, k_trace_shade_tab<(IS & TS_FIRST) != 0, (IS & TS_CODE) != 0>};
@@ -327,7 +439,7 @@ constexpr TraceShadeKernel trace_shade_kernel()
         return {IS, k_trace_shade<(IS & TS_FIRST) != 0, (IS & TS_EXT) != 0, (IS & TS_FB) != 0, (IS & TS_LDS) != 0, (IS & TS_TAME) != 0, (IS & TS_CODE) != 0>};
 }
 // (a build without the lean plumbing, -DCAP_CHUNK_PLAIN, has no table form: trace_shade_has_table_form() says so and the last three are never looked up)
-constexpr TraceShadeKernel kTraceShadeKernels[16] = {
+constexpr TraceShadeKernel kTraceShadeKernels[17] = {
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_CODE>(),
     trace_shade_kernel<TS_FIRST | TS_EXT | TS_LDS>(), trace_shade_kernel<TS_FIRST | TS_EXT>(),
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME>(), trace_shade_kernel<TS_FIRST | TS_LDS>(), trace_shade_kernel<TS_FIRST>(),
@@ -335,6 +447,7 @@ constexpr TraceShadeKernel kTraceShadeKernels[16] = {
     trace_shade_kernel<TS_FB | TS_LDS>(), trace_shade_kernel<TS_FB>(),
     trace_shade_kernel<TS_LDS | TS_TAME>(), trace_shade_kernel<TS_LDS>(), trace_shade_kernel<0>(),
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_CODE | TS_TAB>(), trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_TAB>(), trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB>(),
+    trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB | TS_HEAD>(),
 };
 
 // the unscaled forms: reference model, scene in LDS, tame shading records (-DCAP_SHADE_IEEE keeps the plain sqrtf and `/`
@@ -350,7 +463,7 @@ static bool tame_kernels(const BvhDev& bvh, const SceneDev& scene)
 bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene) { return tame_kernels(bvh, scene); }
 bool trace_shade_has_table_form(const BvhDev& bvh, const SceneDev& scene) { return kChunkLean && tame_kernels(bvh, scene); }
 
-uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback)
+uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback, bool camera_head)
 {
     const bool first = args.bounce == 0;
     const bool fb    = feedback && !ext && !first;  // (bounce 0 defines the planes' entries: nothing to reuse yet)
@@ -362,11 +475,14 @@ uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const Shade
     // per batch, under its own condition -- reference model, no feedback, trace_shade_has_table_form()
     const bool tab = args.sample_terms != nullptr;
     assert(!tab || (tame && kChunkLean));
-    const uint32_t is = (first ? TS_FIRST : 0u) | (ext ? TS_EXT : 0u) | (fb ? TS_FB : 0u) | (lds ? TS_LDS : 0u) | (tame ? TS_TAME : 0u) | (code ? TS_CODE : 0u) | (tab ? TS_TAB : 0u);
+    // bounce 0 as the head of bounce 1's chunks (TraceShadeCfg HEAD): the host's condition implies the lean table form, the probe and the ring
+    assert(!camera_head || (args.bounce == 1 && tab && args.inline_probe && args.wave_ring && args.in.org_tmin && args.in.dir_tmax && args.in.thr_pid));
+    const uint32_t is = (first ? TS_FIRST : 0u) | (ext ? TS_EXT : 0u) | (fb ? TS_FB : 0u) | (lds ? TS_LDS : 0u) | (tame ? TS_TAME : 0u) | (code ? TS_CODE : 0u) | (tab ? TS_TAB : 0u) |
+                        (camera_head ? TS_HEAD : 0u);
     // the queue's persistent grid; bounce 0's queue is the identity queue of the batch, one entry per padded pixel and frame slot
-    const uint32_t gx = queue_grid(cfg, first ? args.screen.pixels_padded * args.n_slots : args.max_count);
+    const uint32_t gx = queue_grid(cfg, (first || camera_head) ? args.screen.pixels_padded * args.n_slots : args.max_count);
     const TraceShadeKernel* k = kTraceShadeKernels;
-    while (k->is != is && k + 1 < kTraceShadeKernels + 16) ++k;
+    while (k->is != is && k + 1 < kTraceShadeKernels + 17) ++k;
     assert(k->is == is);  // the table holds every tuple the lines above can derive
     hipLaunchKernelGGL(k->kernel, dim3(gx), dim3(kBlock), 0, cfg.stream, bvh, args);
     // the kernel's own conditions: the marked loop where it calls exhaustive_closest_marked, the carry chain where that takes it

@@ -1,14 +1,15 @@
-// small_scene_body.h -- the body of the fused small-scene kernels, included by k_trace_shade and k_trace_shade_tab (small_scene.hip) and
-// by nothing else.  It reads the kernel's arguments `bvh` and `a`, its configuration type C (a TraceShadeCfg) and the flags FIRST, EXT, FB,
-// LDS and TAB as names; no include guard, on purpose.  Text and not a function: wrapped in a device function the thirteen kernels without the sample table no longer
+// small_scene_body.h -- the body of the fused small-scene kernels, included by k_trace_shade, k_trace_shade_tab and k_trace_shade_head
+// (small_scene.hip) and by nothing else.  It reads the kernel's arguments `bvh` and `a`, its configuration type C (a TraceShadeCfg) and the
+// flags FIRST, EXT, FB, LDS and TAB as names; no include guard, on purpose.  (What belongs to the third kernel alone stands under C::HEAD.)  Text and not a function: wrapped in a device function the thirteen kernels without the sample table no longer
 // compile to the instructions they had (tools/isa_compare.py against the commit before the table), which is what lets the switch
 // CAP_SAMPLE_TABLE = 0 stand for that commit in a measurement.
     const uint32_t Ppad     = a.screen.pixels_padded;
     // FIRST: the identity queue of the whole batch, chunk = slot * (Ppad / 64) + 64-pixel group.  Otherwise: chunk slots of the
     // input queue.  Either way the grid is persistent (the LDS tables are staged once per workgroup, not once per frame slot).
     const uint32_t cps      = Ppad >> 6;
-    const uint32_t chunks   = FIRST ? cps * a.n_slots : (a.in.class_capacity >> 6) * kQueueClasses;
+    const uint32_t chunks   = (FIRST || C::HEAD) ? cps * a.n_slots : (a.in.class_capacity >> 6) * kQueueClasses;
     uint32_t       n_shaded = 0, n_probed = 0;
+    uint32_t       head_ext = 0, head_shadow = 0, head_probed = 0, head_shaded = 0;  // HEAD: bounce 0's counts of this wave (wave-uniform)
     __shared__ FrameConst lds_frames[kMaxFrameSlots];
     __shared__ float4     lds_shade[LDS ? kShadeRec * kExhaustiveMax : 1];
     __shared__ float4     lds_rec[LDS ? 4 * kExhaustiveMax : 1];
@@ -69,7 +70,30 @@
         if (good) c = probe.ring_con[pos], cur = target[idx];
         const bool occluded = exhaustive_any<false>(bvh, sr);
         // lighting.h:57-60: unoccluded -> the contribution evaluated at shading time is added
-        if (good && !occluded) target[idx] = make_float4(cur.x + c.x, cur.y + c.y, cur.z + c.z, cur.w);
+        if constexpr (C::HEAD)
+        {
+            // A path can have a bounce-0 and a bounce-1 entry in this ring at once, in one trace or in two, in either order.  The rule
+            // that keeps them apart: NO TWO RING ENTRIES OF A PATH WRITE THE SAME BYTES.  A bounce-0 entry (spare word = the path's
+            // code, never 0) does what k_trace_any does for a CODE batch (store_first_direct): it stores the contribution into
+            // `direct` and the word color.w = code + kCodeLit, and loads nothing.  A bounce-1 entry (spare word 0) adds to color.xyz
+            // and stores those twelve bytes alone -- it does not carry w through as the other kernels' 16-B store does, so it can
+            // neither lose the bounce-0 entry's word nor be lost to it.  Both follow, in this wave's issue order, the head's own
+            // 16-B store of (0, 0, 0, code).
+            if (good && !occluded)
+            {
+                if (f2u(c.w) != 0u)
+                {
+                    a.planes.direct[idx] = make_float4(c.x, c.y, c.z, 0.0f);
+                    reinterpret_cast<float*>(a.planes.color + idx)[3] = c.w + kCodeLit;
+                }
+                else
+                {
+                    float* const t3 = reinterpret_cast<float*>(a.planes.color + idx);
+                    t3[0] = cur.x + c.x, t3[1] = cur.y + c.y, t3[2] = cur.z + c.z;
+                }
+            }
+        }
+        else if (good && !occluded) target[idx] = make_float4(cur.x + c.x, cur.y + c.y, cur.z + c.z, cur.w);
         ring_head = (ring_head + count) & (kWaveRing - 1u);
         ring_n -= count;
     };
@@ -85,7 +109,7 @@
     const uint32_t my_class = wave_global_id() % kQueueClasses;
     const uint32_t lane     = threadIdx.x & 63u;
     uint32_t       n_class  = 0;
-    if (!FIRST)
+    if (!FIRST && !C::HEAD)
     {
         n_class = a.in.count[my_class * kCounterStride];
         n_class = n_class < a.in.class_capacity ? n_class : a.in.class_capacity;
@@ -100,7 +124,73 @@
         v3             thr = mk3(1.0f, 1.0f, 1.0f);
         Ray            r   = make_ray(mk3(0.f, 0.f, 0.f), mk3(0.f, 0.f, 1.f), 0.0f, 0.0f);  // empty interval: hits nothing
         float          carried_r1 = 0.f, carried_r2 = 0.f;
-        if (FIRST)
+        if constexpr (C::HEAD)
+        {
+            // Bounce 0 of this chunk's 64 paths, from the camera vertex of their jitter group (k_camera_vertices: a.in.org_tmin =
+            // (p, code), a.in.dir_tmax = (n, -) per (group, padded pixel); the slot's group sits in its frame constants' pad1) and the
+            // slot's bounce-0 sample terms (a.in.thr_pid = that block of the table): shade_vertex<FIRST, CODE>'s own operations on the
+            // same operands.  What that kernel wrote into the extension queue stays in registers: r, thr, pid.
+            const uint32_t chunk = class_chunk(j, my_class);  // chunks and classes as FIRST deals them out
+            if (chunk >= chunks) break;
+            slot = chunk / cps;  // wave-uniform
+            i    = (chunk - slot * cps) * 64 + lane;
+            pid  = (slot << kPidShift) | i;
+            const FrameConst& fc = lds_frames[slot];
+            const size_t      at = (size_t)f2u(fc.pad1) * Ppad + i;
+            const float4      cp = a.in.org_tmin[at], cn = a.in.dir_tmax[at];
+            // the position in the 64 x 64 blue-noise period as shade_prefetch derives it at bounce >= 1
+            const uint32_t gt   = __umul24(i >> 6, a.screen.shard_count) + a.screen.shard_index;
+            const uint32_t ty   = tile_div(gt, a.screen.tiles_x_mul, a.screen.tiles_x_shift);
+            const uint32_t tx   = gt + (ty & 7u) * ((0u - a.screen.tiles_x) & 7u);
+            const uint32_t base = ((ty & 7u) << 9) | ((i & 0x38u) << 3) | ((tx & 7u) << 3) | (i & 7u);
+            const float4   q0   = a.in.thr_pid[(slot << 12) | base];
+            grab = grab_issue(a.work, my_class);
+            const v3 L = mk3(fc.light_dir[0], fc.light_dir[1], fc.light_dir[2]);
+            const v3 I = mk3(fc.light_intensity[0], fc.light_intensity[1], fc.light_intensity[2]);
+            // the plane's entry: (0, 0, 0, code) whatever the code says -- padding, sky, kd or black
+            a.planes.color[(size_t)slot * Ppad + i] = make_float4(0.f, 0.f, 0.f, cp.w);
+            const bool vtx = cp.w == kCodeKd || cp.w == kCodeBlack, lit = cp.w == kCodeKd;
+            const v3   p = mk3(cp.x, cp.y, cp.z), n = mk3(cn.x, cn.y, cn.z);
+            bool       emit_shadow = false, emit_ext = false;
+            v3         dir = unread3(), contrib = unread3();
+            float      f = unread_f();
+            if (lit)
+            {
+                const float kd  = a.scene.kd_untextured;
+                const float ndl = fmaxf(0.0f, dot3(n, L));
+                const v3    c   = mk3(((I.x * kd) * kInvPi) * ndl, ((I.y * kd) * kInvPi) * ndl, ((I.z * kd) * kInvPi) * ndl);
+                if (c.x != 0.0f || c.y != 0.0f || c.z != 0.0f) emit_shadow = true, contrib = c;
+                dir = hemisphere_dir_tame(n, [&] { return HemiTerms{q0.x, q0.y, q0.z}; });
+                const float ndd = dot3(n, dir);
+                const float pdf = div_unscaled(fmaxf(0.0f, ndd), kPi);
+                if (!(pdf < 1e-5f))
+                {
+                    f        = 1.0f * div_unscaled(kInvPi * fmaxf(ndd, 0.0f), pdf);  // thr = (1, 1, 1) * f
+                    emit_ext = true;  // (num_bounces >= 1, no low-resolution indirect: the host's condition for this form)
+                }
+            }
+            const bool occluded0 = pair_occludes_pre(make_ray(p, L, kRayEps, kRayFar), probe.pairs, probe.k, probe.rows[2u * slot], probe.rows[2u * slot + 1u]);
+            const bool probed0   = emit_shadow && occluded0;
+            emit_shadow          = emit_shadow && !occluded0;
+            const unsigned long long ms = __ballot(emit_shadow);
+            head_shaded += (uint32_t)__popcll(__ballot(vtx)), head_probed += (uint32_t)__popcll(__ballot(probed0));
+            head_ext += (uint32_t)__popcll(__ballot(emit_ext)), head_shadow += (uint32_t)__popcll(ms);
+            // the survivors into the wave's ring, marked by the code in the spare word (trace_ring)
+            if (emit_shadow)
+            {
+                const uint32_t pos  = (ring_head + ring_n + (uint32_t)__popcll(ms & ((1ull << lane) - 1ull))) & (kWaveRing - 1u);
+                probe.ring_org[pos] = make_float4(p.x, p.y, p.z, u2f(pid));
+                probe.ring_con[pos] = make_float4(contrib.x, contrib.y, contrib.z, kCodeKd);
+            }
+            ring_n += (uint32_t)__popcll(ms);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            if (ring_n >= 64u) trace_ring(64u);  // room for the 64 entries bounce 1 may park
+            active = emit_ext;
+            if (__ballot(active) == 0ull) continue;  // no lane of the wave has a ray: no loop, nothing to shade
+            r   = make_ray(p, dir, kRayEps, kRayFar);
+            thr = mk3(f, f, f);
+        }
+        else if (FIRST)
         {
             const uint32_t chunk = class_chunk(j, my_class);
             if (chunk >= chunks) break;  // (only in or past the last block of 64 chunks: every earlier block holds each class once)
@@ -224,3 +314,11 @@
 #endif
     if (C::PROBE && ring_n != 0u) trace_ring(ring_n);  // what is left in this wave's ring
     flush_stats(a.out.count + (size_t)my_class * kCounterStride, n_shaded, n_probed);
+    if constexpr (C::HEAD)
+    {
+        // bounce 0's own counter line of this class (a.in.count: the words its launch and its appends would have counted into) --
+        // extension and shadow entries in words 0 and 1, probed and shaded in 2 and 3, each pair one atomic per wave
+        unsigned long long* const line0 = reinterpret_cast<unsigned long long*>(a.in.count + (size_t)my_class * kCounterStride);
+        if (lane == 0u && (head_ext | head_shadow)) atomicAdd(line0, ((unsigned long long)head_shadow << 32) | (unsigned long long)head_ext);
+        if (lane == 0u && (head_probed | head_shaded)) atomicAdd(line0 + 1, ((unsigned long long)head_shaded << 32) | (unsigned long long)head_probed);
+    }

@@ -310,6 +310,16 @@ enum
      * device: entries that differ in any bit << 32 | (bounce, frame slot) rows compared, 4 096 entries each. */
     CAP_DEBUG_SAMPLE_TABLE          = 16,
     CAP_DEBUG_SELFTEST_SAMPLE_TABLE = 17,
+    /* CAMERA_TABLE (get): 1 if the last batch of the last cap_render ran bounce 0 inside bounce 1's launch -- the camera rays traced once
+     * per group of frame slots that share a sub-pixel jitter into a table of camera vertices, the per-slot shading of those vertices at the
+     * head of the first bounce >= 1 launch, the shadow rays through the wave rings -- and 0 if bounce 0 was a launch of its own (the switch
+     * CAP_NO_CAMERA_TABLE, CAP_RENDER_AOV, num_bounces 0, every render without the sample table or without the code in the colour plane).
+     * Same bits and the same CapStats either way: launches_trace_any still counts bounce 0's shadow rays as one any-hit pass per batch.
+     * SELFTEST_CAMERA_TABLE (get, right after such a render): bounce 0's camera vertex of every (frame slot, padded pixel) of the last
+     * batch, evaluated with the slot's own frame constants, against the table entry of the slot's group, on the device: entries that
+     * differ in any bit << 32 | groups << 16 | frame slots compared. */
+    CAP_DEBUG_CAMERA_TABLE          = 18,
+    CAP_DEBUG_SELFTEST_CAMERA_TABLE = 19,
     /* A/B and diagnostic switches of the build and render paths (which kernels trace the camera and the shadow rays, one or two batch
      * lanes, the builders' parameters ...): ONE table per context, key = SWITCH_BASE + cap_debug_switch_index("CAP_..."), the names being
      * the environment variables that fill the table once, at cap_ctx_create (tools set those around a whole process; nothing else in the
