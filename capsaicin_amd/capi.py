@@ -82,6 +82,19 @@ class WindingInfo(C.Structure):
         return {n: (list(getattr(self, n)) if n in ("root_n", "root_p") else getattr(self, n)) for n, _ in self._fields_}
 
 
+class WindingInstancesInfo(C.Structure):
+    """CapWindingInstancesInfo: the derived tables of cap_winding_instances: whether current ones exist (built), the instances and how
+    many of them contribute, the top-level tree's levels with their entry counts (padding included; host_top's layout), the forest's
+    dipole records, and the whole table's normal sum, weight and centroid.  Only instances, levels, entries and level_entries are
+    filled while built == 0."""
+    _fields_ = [("instances", C.c_uint32), ("contributing", C.c_uint32), ("levels", C.c_uint32), ("entries", C.c_uint32),
+                ("forest_records", C.c_uint32), ("built", C.c_uint32), ("level_entries", C.c_uint32 * 25), ("reserved", C.c_uint32),
+                ("total_weight", C.c_double), ("root_n", C.c_float * 3), ("root_p", C.c_float * 3)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n in ("root_n", "root_p", "level_entries") else getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 VERTICES_DEVICE = 1  # CAP_VERTICES_DEVICE
 
 
@@ -300,6 +313,10 @@ SYMBOLS = {
     "cap_winding_drop": (_i, [_vp]),
     "cap_winding_readback": (_i, [_vp, _vp]),
     "cap_winding_numbers": (_i, [_vp, _vp, _u64, C.c_float, _vp, _vp]),
+    "cap_winding_instances": (_i, [_vp, _vp, _u64, C.c_float, _vp, _vp]),
+    "cap_winding_instances_info": (_i, [_vp, C.POINTER(WindingInstancesInfo)]),
+    "cap_winding_instances_readback": (_i, [_vp, _vp, _vp, _vp]),
+    "cap_objects_readback": (_i, [_vp, _vp, _vp]),
     "cap_closest_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_signed_distance_instances": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
@@ -947,14 +964,53 @@ class Renderer:
         radius are replaced by their dipole: beta >= 1, larger is more exact and slower, inf sums every triangle exactly.
         visits=True also returns an (N, 2) int32 array: the dipole terms and the exact triangle terms each walk added.  Needs
         build_winding().  points (the radius column is not read), out and sync as closest_points; numpy points give numpy results."""
+        return self._winding("cap_winding_numbers", 2, points, beta, out, visits, sync)
+
+    def _winding(self, name, width, points, beta, out, visits, sync):
+        """winding_numbers and winding_instances: (N,) float32 through the entry point `name`, with an (N, width) int32 visits array"""
         import torch
         host = isinstance(points, np.ndarray)  # then the results are read back to the host, which needs the sync
         dev, points, n = self._stage_records(points, 4, "points")
         out, host_out = self._out(out, (n,), torch.float32, dev)
-        vis = [torch.empty((n, 2), dtype=torch.int32, device=dev)] if visits else []
-        res = self._run("cap_winding_numbers", (points, n, C.c_float(beta), out, vis[0] if visits else None), dev, sync or host,
+        vis = [torch.empty((n, width), dtype=torch.int32, device=dev)] if visits else []
+        res = self._run(name, (points, n, C.c_float(beta), out, vis[0] if visits else None), dev, sync or host,
                         host or host_out is not None, [out] + vis, [host_out, None])
         return tuple(res) if visits else res[0]
+
+    def winding_instances(self, points, beta=2.0, out=None, visits=False, sync=True):
+        """The generalised winding number of the instanced scene about each WORLD point (cap_winding_instances): (N,) float32, the
+        winding number of the scene flattened through the instance transforms -- 1 inside a closed part, a mirrored one included, 2
+        where two parts overlap, in between near holes; w >= 1/2 is the robust inside test.  An instance with mask 0 is switched off.
+        beta as winding_numbers.  visits=True also returns an (N, 4) int32 array: the dipole terms taken at the top level, the
+        instances entered, the dipole terms below instances and the exact triangle terms.  Needs set_instances() and build_winding();
+        the tables it derives from them are rebuilt on the stream when either changed.  points, out and sync as winding_numbers."""
+        return self._winding("cap_winding_instances", 4, points, beta, out, visits, sync)
+
+    def winding_instances_info(self):
+        """The WindingInstancesInfo of the derived tables (cap_winding_instances_info); never builds them."""
+        info = WindingInstancesInfo()
+        _check(lib().cap_winding_instances_info(self.ctx, C.byref(info)), "cap_winding_instances_info")
+        return info
+
+    def winding_instances_tables(self):
+        """(top (entries, 8), inst (N, 12), forest (forest nodes, 2, 8)) float32 of cap_winding_instances_readback, built first when
+        they are not current: per top-level entry (p~_w, r, N_w, word 7: the instance at level 0; r = -1: empty), in the tree's
+        layout (winding_instances_info().level_entries); per instance L row-major, |det L|, sigma, s; and with an object table the
+        forest's dipole table, indexed as objects_readback()'s nodes (without one the objects' table is winding_table())."""
+        info = self.winding_instances_info()
+        nodes = sum(int(o["triangle_count"]) - 1 for o in self.objects_info())
+        top, inst, forest = np.zeros((info.entries, 8), np.float32), np.zeros((info.instances, 12), np.float32), np.zeros((nodes, 2, 8), np.float32)
+        _check(lib().cap_winding_instances_readback(self.ctx, _p(top), _p(inst), _p(forest) if nodes else None), "cap_winding_instances_readback")
+        return top, inst, forest
+
+    def objects_readback(self):
+        """(nodes (forest nodes, 16) float32, leaf triangles (forest records,) uint32) of the object table's forest (cap_objects_readback),
+        as bvh_readback() gives the scene's tree: object k's nodes and records follow object k - 1's, child codes number the forest."""
+        info = self.objects_info()
+        nodes = np.zeros((sum(int(o["triangle_count"]) - 1 for o in info), 16), np.float32)
+        leaves = np.zeros(sum(int(o["triangle_count"]) for o in info), np.uint32)
+        _check(lib().cap_objects_readback(self.ctx, _p(nodes) if len(nodes) else None, _p(leaves) if len(leaves) else None), "cap_objects_readback")
+        return nodes, leaves
 
     def closest_instances(self, points, out=None, sync=True, mask=None):
         """The (instance, triangle) nearest to each point in WORLD space over the instance table (cap_closest_instances): (records
@@ -964,14 +1020,35 @@ class Renderer:
         import torch
         return self._closest_single("cap_closest_instances", points, out, sync, mask, (torch.int32,))
 
-    def signed_distance_instances(self, points, out=None, sync=True, mask=None):
+    def signed_distance_instances(self, points, out=None, sync=True, mask=None, sign="pseudonormal", beta=2.0):
         """closest_instances with the signed distance (cap_signed_distance_instances): (records (N, 8) float32, instances (N,) int32,
         -1 on a miss, signed (N,) float32).  Records and instances are closest_instances', bit for bit; signed is the WORLD distance
         sqrt(dist2), negative where the point's object-space image W p lies behind the pseudonormal of the feature nearest to it on
         the winning instance's object, +inf on a miss.  Needs set_instances() and build_pseudonormals().  points, out, sync and mask=
-        as closest_instances; numpy points give numpy results."""
+        as closest_instances; numpy points give numpy results.
+        sign="winding" takes the sign from the winding number over the instances instead, for parts that are not closed or are
+        mirrored: the same three arrays, signed negative exactly where winding_instances(points, beta) >= 1/2, composed on the device
+        from the two calls.  Needs build_winding() as well, and takes no mask=."""
         import torch
-        return self._closest_single("cap_signed_distance_instances", points, out, sync, mask, (torch.int32, torch.float32))
+        if sign == "pseudonormal":
+            return self._closest_single("cap_signed_distance_instances", points, out, sync, mask, (torch.int32, torch.float32))
+        if sign != "winding":
+            raise CapError('sign must be "pseudonormal" or "winding", got %r' % (sign,))
+        if mask is not None:
+            raise CapError('sign="winding" takes no mask=: the winding number covers every triangle')
+        host = isinstance(points, np.ndarray)
+        dev, pts, n = self._stage_records(points, 4, "points")
+        rec, host_out = self._out(out, (n, 8), torch.float32, dev)
+        rec, inst, signed = self._closest_single("cap_signed_distance_instances", pts, rec, sync or host, None, (torch.int32, torch.float32))
+        w = self.winding_instances(pts, beta=beta, sync=sync or host)
+        signed = torch.where(w >= 0.5, -signed.abs(), signed.abs())
+        if not (host or host_out is not None):
+            return rec, inst, signed
+        h = rec.cpu().numpy()
+        if host_out is not None:
+            host_out[...] = h.reshape(host_out.shape)
+            h = host_out
+        return h, inst.cpu().numpy(), signed.cpu().numpy()
 
     def closest_points_multi(self, points, k, counts=False, resume=None, sync=True, mask=None):
         """The k triangles nearest to each point within its radius, in (dist2, triangle) order (cap_closest_points_multi): (N, k, 8)

@@ -168,6 +168,15 @@ struct CapContext
     DevBuf<float4>       wn_table;
     bool                 wn_ready = false;  // a table exists (stale while bvh_stale; cap_bvh_build / cap_bvh_refit rebuild it)
     CapWindingInfo       wn_info{};
+    DevBuf<double>       wn_root;           // N, A, M of the whole tree as the build summed them (WindingBuildArgs::root)
+    // derived tables of cap_winding_instances (winding.hip), built on the stream ahead of the first query that finds them dirty and
+    // freed by cap_winding_drop: per-instance (L, |det L|, sigma, s), the top-level dipoles and their binary64 sums, the forest's dipole
+    // table with the objects' root sums, and the build scratch of the largest object (kept: nothing waits for the build to end)
+    DevBuf<float4>       wi_inst, wi_top, wi_forest;
+    DevBuf<double>       wi_top_sums, wi_obj_root, wi_reals;
+    DevBuf<uint32_t>     wi_words, wi_count;
+    bool                 wi_dirty = true, wi_forest_dirty = true;  // set wherever the instances, the objects, the trees or the table change
+    bool                 wi_built = false;  // the derived tables exist (current unless dirty)
     // vertex updates and refit (cap_scene_update_vertices, cap_bvh_refit, refit.hip)
     bool                  bvh_stale = false;             // vertices changed since the trees were last brought up to date
     bool                  positions_host_stale = false;  // positions_host lags a device-side update (read back only when needed)
@@ -291,4 +300,7 @@ int  ensure_positions_host(CapContext* c);
 int  upload_light_table(CapContext* c);
 // ctx_query.hip
 int query_state(CapContext* c, const char* what);  // CAP_ERR_STATE unless the trees are built and up to date
+// ctx_bvh.hip
+int  winding_instances_ensure(CapContext* c, const char* what);  // enqueues the build of cap_winding_instances' derived tables if they are dirty
+void winding_instances_release(CapContext* c);                   // frees them (the stream must be idle)
 }  // namespace cap

@@ -525,6 +525,12 @@ struct WindingBuildArgs
     uint32_t*       flags;
     uint32_t*       stats;
     double*         root;
+    // An object's tree in the forest (cap_winding_instances; zeros and NULL for the scene's tree): nodes, table, sums, parent and flags
+    // point at the object's own first node and are indexed from 0, while the child codes the nodes hold are the forest's -- node_base
+    // and rec_base are what k_forest_relocate added to them.  The forest keeps no leaf_tri: rec_ids = the object's leaf-order records,
+    // whose word 12 is the global triangle id.
+    uint32_t        node_base, rec_base;
+    const float4*   rec_ids;
 };
 void launch_winding_build(hipStream_t stream, const WindingBuildArgs& a);
 // points = CapPointDesc records (the radius is not read), out = one float per point, visits = 2 words per point (far terms, exact
@@ -539,6 +545,34 @@ struct WindingArgs
     uint32_t*     visits;
 };
 void launch_winding_numbers(const LaunchCfg& cfg, const BvhDev& bvh, const WindingArgs& a, uint32_t depth);
+// The derived tables of cap_winding_instances (winding.hip; include/capsaicin_hip.h "winding numbers over instances"), all on one stream:
+//   inst      3 float4 per instance: L row-major (9 words), |det L|, sigma, s = +1 / -1, or 0 for an instance that does not contribute
+//   top       2 float4 per TLAS entry, in the layout of `tlas`: (p~_w, r) (N_w, word 7); r = -1 marks an empty entry
+//   top_sums  7 doubles per TLAS entry (N_w, weight, weight p~_w): level 0 from the objects' root sums, a level above = entry 2 j + entry 2 j + 1
+//   obj_root  7 doubles per object (N, A, M of the whole object: WindingBuildArgs::root of its build)
+//   count     1 word: the contributing instances
+struct WindingInstBuildArgs
+{
+    const float4*   descs;  // CapInstanceDesc records
+    const float4*   rec;    // the instance records of k_instance_setup: word 12 the live mask, word 14 the object
+    const float4*   tlas;
+    uint32_t        n;
+    const double*   obj_root;
+    float4*         inst;
+    float4*         top;
+    double*         top_sums;
+    uint32_t*       count;
+};
+void launch_winding_instances_build(hipStream_t stream, const WindingInstBuildArgs& a);
+// cap_winding_instances (k_winding_inst): a = the points, beta and outputs as WindingArgs' with visits = 4 words per point, a.table the
+// dipole table of the pools bvh.nodes / bvh.tris refer to (the scene's, or the forest's); depth: the deepest tree below an instance.
+struct WindingInstArgs
+{
+    WindingArgs   a;
+    const float4* inst;
+    const float4* top;
+};
+void launch_winding_instances(const LaunchCfg& cfg, const BvhDev& bvh, const WindingInstArgs& a, const TlasDev& tl, uint32_t depth);
 
 // ---- refit of the kept trees to moved vertices (refit.hip, cap_bvh_refit) ----
 // binary tree: triangle setup (bounds reset first), parent links from the nodes, the build's climb (bvh.hip k_refit) in leaf order

@@ -83,6 +83,7 @@ static uint32_t object_builder(const CapContext* c, uint32_t n)
 static int objects_rebuild(CapContext* c, const char* what)
 {
     const uint32_t count = c->obj_count;
+    c->wi_dirty = c->wi_forest_dirty = true;  // cap_winding_instances' derived tables follow the forest
     if (count == 0) return CAP_OK;
     c->obj_count = 0;  // (until the forest stands)
     uint32_t max_n = 0;
@@ -147,6 +148,7 @@ static int objects_rebuild(CapContext* c, const char* what)
 static int instances_rebuild(CapContext* c)
 {
     const uint32_t n = c->inst_count;
+    c->wi_dirty      = true;  // cap_winding_instances' derived tables follow the instance table (a flag: nothing is built here)
     if (n == 0) return CAP_OK;
     InstanceBuildArgs a{};
     a.descs = reinterpret_cast<const float*>(c->inst_desc.p), a.n = n;
@@ -222,10 +224,13 @@ static int pseudonormals_rebuild(CapContext* c, const char* what)
 static int winding_rebuild(CapContext* c)
 {
     c->wn_ready = false;  // (until the table stands)
+    c->wi_dirty = c->wi_forest_dirty = true;  // cap_winding_instances' derived tables follow the table
     const auto     wall0 = std::chrono::steady_clock::now();
     const uint32_t t     = c->tri_count, inner = t >= 2 ? t - 1 : 0;
     uint32_t       stats[2] = {0, 0};
     double         root[7]  = {0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(c->wn_root.ensure(7));  // the whole tree's sums, kept: the scene as the one object of cap_winding_instances
+    if (!t) HIP_TRY(hipMemsetAsync(c->wn_root.p, 0, 7 * sizeof(double), c->stream));
     if (t)
     {
         if (c->wn_table.n < 4 * (size_t)inner)
@@ -235,12 +240,12 @@ static int winding_rebuild(CapContext* c)
         }
         DevBuf<double>   reals;
         DevBuf<uint32_t> words;
-        HIP_TRY(reals.ensure(7 * (size_t)t + 14 * (size_t)inner + 7));
+        HIP_TRY(reals.ensure(7 * (size_t)t + 14 * (size_t)inner));
         HIP_TRY(words.ensure(2 * (size_t)inner + 2));
         WindingBuildArgs a{};
         a.positions = c->positions.p, a.indices = c->indices.p, a.tri_ids = c->tri_ids.p, a.mesh_offsets = c->mesh_offsets.p, a.tri_count = t;
         a.nodes = c->nodes.p, a.leaf_tri = c->leaf_tri.p, a.table = c->wn_table.p;
-        a.tri_sums = reals.p, a.sums = reals.p + 7 * (size_t)t, a.root = a.sums + 14 * (size_t)inner;
+        a.tri_sums = reals.p, a.sums = reals.p + 7 * (size_t)t, a.root = c->wn_root.p;
         a.parent = words.p, a.flags = words.p + inner, a.stats = words.p + 2 * (size_t)inner;
         launch_winding_build(c->stream, a);
         HIP_TRY(hipGetLastError());
@@ -262,7 +267,125 @@ static int winding_rebuild(CapContext* c)
     return CAP_OK;
 }
 
+// The derived tables of cap_winding_instances (winding.hip), enqueued on the context stream ahead of the query that found them dirty: no
+// host wait, unless a buffer has to grow under a query that may still be reading it.  With an object table, first every object's dipole
+// table and root sums, by the scene's build on the object's node and record range of the forest (only when the forest, the trees or
+// the scene table changed: cap_instances_set alone leaves them); then the per-instance records and the top-level dipoles.
+int cap::winding_instances_ensure(CapContext* c, const char* what)
+{
+    if (c->wi_built && !c->wi_dirty && !c->wi_forest_dirty) return CAP_OK;
+    const uint32_t n = c->inst_count;
+    uint32_t       off[kTlasMaxLevels], total = 0;
+    tlas_layout(n, off, &total);
+    uint32_t forest_nodes = 0, max_n = 0;
+    for (uint32_t k = 0; k < c->obj_count; ++k) forest_nodes += c->obj_info[k].triangle_count - 1u, max_n = std::max(max_n, c->obj_info[k].triangle_count);
+    const size_t roots = 7 * (size_t)std::max(c->obj_count, 1u), reals = c->obj_count ? 7 * (size_t)max_n + 14 * (size_t)max_n : 0,
+                 words = c->obj_count ? 2 * (size_t)max_n + 2 : 0;
+    if (c->wi_inst.n < 3 * (size_t)n || c->wi_top.n < 2 * (size_t)total || c->wi_forest.n < 4 * (size_t)forest_nodes || c->wi_obj_root.n < roots ||
+        c->wi_reals.n < reals || c->wi_words.n < words || !c->wi_count.p)
+    {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (grown buffers replace ones an earlier query may still be reading)
+        HIP_TRY(c->wi_inst.ensure(3 * (size_t)n));
+        HIP_TRY(c->wi_top.ensure(2 * (size_t)total));
+        HIP_TRY(c->wi_top_sums.ensure(7 * (size_t)total));
+        HIP_TRY(c->wi_obj_root.ensure(roots));
+        HIP_TRY(c->wi_count.ensure(1));
+        if (c->obj_count)
+        {
+            if (c->wi_forest.n < 4 * (size_t)forest_nodes) c->wi_forest_dirty = true;
+            HIP_TRY(c->wi_forest.ensure(4 * (size_t)forest_nodes));
+            HIP_TRY(c->wi_reals.ensure(reals));
+            HIP_TRY(c->wi_words.ensure(words));
+        }
+    }
+    if (c->obj_count && c->wi_forest_dirty)
+        for (uint32_t k = 0; k < c->obj_count; ++k)
+        {
+            const CapObjectInfo& o = c->obj_info[k];
+            const uint32_t       t = o.triangle_count, inner = t - 1u;
+            WindingBuildArgs     a{};
+            a.positions = c->positions.p, a.indices = c->indices.p, a.tri_ids = c->tri_ids.p, a.mesh_offsets = c->mesh_offsets.p, a.tri_count = t;
+            a.nodes = c->forest_nodes.p + 4 * (size_t)c->obj_node_base[k], a.table = c->wi_forest.p + 4 * (size_t)c->obj_node_base[k];
+            a.rec_ids = c->forest_tris.p + 4 * (size_t)c->obj_rec_base[k], a.node_base = c->obj_node_base[k], a.rec_base = c->obj_rec_base[k];
+            a.tri_sums = c->wi_reals.p, a.sums = c->wi_reals.p + 7 * (size_t)t, a.root = c->wi_obj_root.p + 7 * (size_t)k;
+            a.parent = c->wi_words.p, a.flags = c->wi_words.p + inner, a.stats = c->wi_words.p + 2 * (size_t)inner;
+            launch_winding_build(c->stream, a);  // (the objects share the scratch: the stream orders them)
+        }
+    WindingInstBuildArgs b{};
+    b.descs = c->inst_desc.p, b.rec = c->inst_rec.p, b.tlas = c->inst_tlas.p, b.n = n;
+    b.obj_root = c->obj_count ? c->wi_obj_root.p : c->wn_root.p;
+    b.inst = c->wi_inst.p, b.top = c->wi_top.p, b.top_sums = c->wi_top_sums.p, b.count = c->wi_count.p;
+    launch_winding_instances_build(c->stream, b);
+    HIP_TRY(hipGetLastError());
+    c->wi_built = true, c->wi_dirty = c->wi_forest_dirty = false;
+    return trace_launch(c, "%s: derived tables of %u instances, %u forest records", what, n, forest_nodes);
+}
+
+void cap::winding_instances_release(CapContext* c)
+{
+    c->wi_inst.release(), c->wi_top.release(), c->wi_forest.release(), c->wi_top_sums.release(), c->wi_obj_root.release();
+    c->wi_reals.release(), c->wi_words.release(), c->wi_count.release();
+    c->wi_built = false, c->wi_dirty = c->wi_forest_dirty = true;
+}
+
+// what cap_winding_instances and its read-backs need of the context beyond query_state
+static int winding_instances_state(CapContext* c, const char* what)
+{
+    if (const int rc = query_state(c, what)) return rc;
+    if (!c->wn_ready) return fail(CAP_ERR_STATE, "%s: call cap_winding_build first", what);
+    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
+    return CAP_OK;
+}
+
 extern "C" {
+
+int cap_winding_instances_info(CapContext* c, CapWindingInstancesInfo* out)
+{
+    static_assert(sizeof(CapWindingInstancesInfo) == 160, "the header's record");
+    if (!c || !out) return fail(CAP_ERR_INVALID_ARG, "cap_winding_instances_info: NULL argument");
+    *out = CapWindingInstancesInfo{};
+    out->instances = c->inst_count;
+    if (c->inst_count)
+    {
+        uint32_t       off[kTlasMaxLevels], total = 0;
+        const uint32_t top = tlas_layout(c->inst_count, off, &total);
+        out->levels = top + 1u, out->entries = total;
+        for (uint32_t l = 0; l <= top; ++l) out->level_entries[l] = (l < top ? off[l + 1] : total) - off[l];
+    }
+    const bool current = c->wi_built && !c->wi_dirty && !c->wi_forest_dirty && c->wn_ready && c->bvh_ready && !c->bvh_stale && c->inst_count;
+    out->built = current ? 1u : 0u;
+    if (!current) return CAP_OK;
+    for (uint32_t k = 0; k < c->obj_count; ++k) out->forest_records += c->obj_info[k].triangle_count - 1u;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(&out->contributing, c->wi_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    // the whole table: the one entry of the last level
+    const size_t root = (size_t)out->entries - out->level_entries[out->levels - 1u];
+    double       s[7];
+    float        e[8];
+    HIP_TRY(hipMemcpy(s, c->wi_top_sums.p + 7 * root, sizeof(s), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(e, c->wi_top.p + 2 * root, sizeof(e), hipMemcpyDeviceToHost));
+    out->total_weight = s[3];
+    for (int k = 0; k < 3; ++k) out->root_n[k] = e[4 + k], out->root_p[k] = e[k];
+    return CAP_OK;
+}
+
+int cap_winding_instances_readback(CapContext* c, float* host_top, float* host_inst, float* host_forest)
+{
+    const char* what = "cap_winding_instances_readback";
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (const int rc = winding_instances_state(c, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (const int rc = winding_instances_ensure(c, what)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t off[kTlasMaxLevels], total = 0, forest_nodes = 0;
+    tlas_layout(c->inst_count, off, &total);
+    for (uint32_t k = 0; k < c->obj_count; ++k) forest_nodes += c->obj_info[k].triangle_count - 1u;
+    if (host_top) HIP_TRY(hipMemcpy(host_top, c->wi_top.p, sizeof(float4) * 2 * (size_t)total, hipMemcpyDeviceToHost));
+    if (host_inst) HIP_TRY(hipMemcpy(host_inst, c->wi_inst.p, sizeof(float4) * 3 * (size_t)c->inst_count, hipMemcpyDeviceToHost));
+    if (host_forest && forest_nodes) HIP_TRY(hipMemcpy(host_forest, c->wi_forest.p, sizeof(float4) * 4 * (size_t)forest_nodes, hipMemcpyDeviceToHost));
+    return CAP_OK;
+}
 
 int cap_winding_build(CapContext* c, CapWindingInfo* out)
 {
@@ -283,6 +406,12 @@ int cap_winding_drop(CapContext* c)
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipStreamSynchronize(c->stream));  // (a query may still be reading it)
         c->wn_table.release();
+    }
+    if (c->wi_built || c->wi_inst.p || c->wi_forest.p)
+    {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        winding_instances_release(c);
     }
     c->wn_ready = false;
     return CAP_OK;
@@ -700,6 +829,7 @@ int instances_set(CapContext* c, const char* what, const CapInstanceDesc* descs,
     if (count == 0)
     {
         c->inst_count = 0;  // host state: queries already enqueued keep the table they were given
+        c->wi_dirty   = true;
         if (out) *out = CapInstancesInfo{};
         return CAP_OK;
     }
@@ -806,6 +936,7 @@ int cap_objects_set(CapContext* c, const CapObjectRange* ranges, uint32_t count,
     // from here on the tables change: object indices lose their meaning, so the instance table goes with the old object table
     c->inst_count = 0;
     c->obj_count  = 0;
+    c->wi_dirty = c->wi_forest_dirty = true;
     if (count == 0)
     {
         if (out) *out = CapObjectsInfo{};
@@ -844,6 +975,23 @@ int cap_objects_info(CapContext* c, CapObjectInfo* out, uint32_t capacity, uint3
     if (count_out) *count_out = c->obj_count;
     const uint32_t n = std::min(capacity, c->obj_count);
     if (n) std::copy(c->obj_info.begin(), c->obj_info.begin() + n, out);
+    return CAP_OK;
+}
+
+int cap_objects_readback(CapContext* c, float* nodes, uint32_t* leaf_triangles)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_objects_readback: ctx is NULL");
+    if (const int rc = query_state(c, "cap_objects_readback")) return rc;
+    if (c->obj_count == 0) return fail(CAP_ERR_STATE, "cap_objects_readback: no object table installed");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t n_nodes = (size_t)c->obj_node_base.back() + c->obj_info.back().triangle_count - 1u;
+    const size_t n_recs  = (size_t)c->obj_rec_base.back() + c->obj_info.back().triangle_count;
+    if (nodes && n_nodes) HIP_TRY(hipMemcpy(nodes, c->forest_nodes.p, sizeof(float4) * 4 * n_nodes, hipMemcpyDeviceToHost));
+    // word 12 of each 64-byte record: the scene's triangle id
+    if (leaf_triangles)
+        HIP_TRY(hipMemcpy2D(leaf_triangles, sizeof(uint32_t), reinterpret_cast<const float*>(c->forest_tris.p) + 12, sizeof(float4) * 4, sizeof(uint32_t), n_recs,
+                            hipMemcpyDeviceToHost));
     return CAP_OK;
 }
 

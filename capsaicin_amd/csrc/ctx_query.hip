@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip) and cap_winding_numbers (winding.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip) and cap_winding_numbers and cap_winding_instances (winding.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -390,9 +390,40 @@ int winding_query(CapContext* c, const char* what, const CapPointDesc* points, u
         return run.traced("k_winding", first);
     });
 }
+
+// cap_winding_instances (winding.hip k_winding_inst): the two-level walk over the top-level dipoles and the objects' tables.  The derived
+// tables are brought up to date on the stream after the last check, ahead of the first launch.
+int winding_instances_query(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, float beta, float* winding, uint32_t* visits)
+{
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (!(beta >= 1.0f)) return fail(CAP_ERR_INVALID_ARG, "%s: beta = %g must be finite and >= 1, or +inf", what, (double)beta);  // (a NaN fails the comparison)
+    if (const int rc = query_state(c, what)) return rc;
+    if (!c->wn_ready) return fail(CAP_ERR_STATE, "%s: call cap_winding_build first", what);
+    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
+    if (n == 0) return CAP_OK;
+    if (!points || !winding) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("winding", winding, sizeof(float), 4),
+                                              range("visits", visits, 4 * sizeof(uint32_t), 4)}))
+        return rc;
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    if (const int rc = winding_instances_ensure(c, what)) return rc;
+    use_instance_pools(run);
+    const float4* table = c->obj_count ? c->wi_forest.p : c->wn_table.p;
+    return for_each_chunk(run, points, n, [&](const QueryArgs& chunk, uint64_t first) {
+        const WindingInstArgs a{WindingArgs{chunk.rays, chunk.n, table, beta, winding + first, at(visits, 4 * first)}, c->wi_inst.p, c->wi_top.p};
+        launch_winding_instances(run.cfg, run.bvh, a, run.tl, run.depth);
+        return run.traced("k_winding_inst", first);
+    });
+}
 }  // namespace
 
 extern "C" {
+
+int cap_winding_instances(CapContext* c, const CapPointDesc* device_points, uint64_t n, float beta, float* device_winding, uint32_t* device_visits)
+{
+    return winding_instances_query(c, "cap_winding_instances", device_points, n, beta, device_winding, device_visits);
+}
 
 int cap_winding_numbers(CapContext* c, const CapPointDesc* device_points, uint64_t n, float beta, float* device_winding, uint32_t* device_visits)
 {

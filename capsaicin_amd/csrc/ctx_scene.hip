@@ -76,6 +76,7 @@ int cap_scene_upload(CapContext* c, const float* positions, const float* normals
     c->pn_table.release();
     c->wn_ready    = false;     // ... and the dipole table to its tree
     c->wn_table.release();
+    winding_instances_release(c);
     return CAP_OK;
 }
 

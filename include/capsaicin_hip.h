@@ -954,8 +954,8 @@ int cap_signed_distance_instances(CapContext* ctx, const CapPointDesc* device_po
  * above 2^24 is split into launches, n = 0 does nothing; asynchronous on the context stream; nothing of the render's state is touched.
  * CAP_ERR_STATE without a table, before cap_bvh_build and while the trees are stale.  There is no CapTraceOptions: the moments cover
  * all triangles, so a mesh mask cannot be honoured.
- * Not covered: instances and objects (w is additive over instances with the sign of det M; it needs moments in the top-level tree),
- * masks, second- and third-order moments, a per-point beta, a wave-cooperative walk. */
+ * Not covered: masks, second- and third-order moments, a per-point beta, a wave-cooperative walk.  Instances and objects:
+ * cap_winding_instances below. */
 typedef struct CapWindingInfo
 {
     uint32_t inner_nodes;          /* records in the table: triangles - 1, or 0 */
@@ -970,6 +970,94 @@ int cap_winding_drop(CapContext* ctx);
 int cap_winding_readback(CapContext* ctx, float* host_table /* 16 floats per inner node */);
 int cap_winding_numbers(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, float beta, float* device_winding,
                         uint32_t* device_visits /* may be NULL: 2 per point */);
+
+/* ---- winding numbers over instances: world dipoles and cap_winding_instances ----
+ * The generalised winding number of the scene the instance table describes, flattened into world space: with M_i = desc[i].transform,
+ * L_i its linear part and s_i = sign(det L_i),
+ *   w(q) = sum_i s_i / (4 pi) sum_{t in object(i)} Omega(M_i t, q),
+ * Omega the signed solid angle of the WORLD-space triangle.  s_i makes a mirrored instance of an outward-wound closed mesh read 1
+ * inside: facing, as everywhere in this ABI, is an object-space notion.  Solid angle is not affine-invariant, so this is not
+ * w_object(W q) except for similarity transforms and closed meshes; it is the true winding number of the flattened scene, the robust
+ * inside test for assemblies of parts that weld into each other, are open, or are placed many times.
+ * An instance contributes iff it is not inert, desc.mask & 0xFF != 0 and det L_i is a finite number other than 0.  A mask of 0
+ * switches an instance off, as for rays; nothing else of the masks is honoured and there is no CapTraceOptions, for cap_winding_numbers'
+ * reason: the moments cover every triangle.
+ *
+ * Derived tables.  Three tables hang off the dipole table of cap_winding_build, the instance table and the object table; all are
+ * built in binary64 and rounded once per word, in one fixed order, so the same state gives the same bytes:
+ *   per instance   12 floats: L row-major (9), |det L|, sigma, s.  sigma = sqrt(||L||_1 ||L||_inf) rounded UP to binary32, an upper
+ *                  bound of ||L||_2 and exactly 1 for the identity.  s = +1 or -1, 0 for an instance that does not contribute.
+ *   top level      8 floats per entry of the top-level tree, in the tree's own layout (level 0 = the instances in the tree's order,
+ *                  padded to an even count; entry j of a level above = entries 2 j and 2 j + 1 of the level below): words 0..2 p~_w,
+ *                  word 3 r, words 4..6 N_w, word 7 the instance index at level 0 and 0xFFFFFFFF above.  Level 0, from the root sums
+ *                  (N, A, M) of the instance's object: N_w = s cof(L) N (the area vector transforms exactly under an affine map),
+ *                  p~_w = M_i (M / A), weight A |det L|^(2/3) (exact for similarities; any positive weight keeps p~_w inside the
+ *                  subtree).  A level above adds (N_w, weight, weight p~_w) of entry 2 j and entry 2 j + 1, in that order.  p~_w =
+ *                  the weighted sum over the weight, or the centre of the entry's stored world box when the weight is 0; r follows
+ *                  the scene table's rule on the entry's stored world box: the distance from the STORED p~_w to its farthest corner,
+ *                  stepped one ulp up.  An entry without a contributing instance below it is EMPTY: r = -1 and zeros.
+ *   forest         with an object table: the dipole table of every object's tree, 16 floats per forest node, by the rules of
+ *                  cap_winding_build on the object's triangles; word 7 holds the child code in the forest's numbering.  Without an
+ *                  object table the one object is the scene and its table is cap_winding_build's.  A one-triangle object has no
+ *                  records.
+ * They are derived state: cap_instances_set(_ex), cap_objects_set, cap_bvh_build, cap_bvh_refit and cap_winding_build only mark them
+ * dirty, and the first cap_winding_instances or cap_winding_instances_readback that finds them dirty rebuilds them on the context
+ * stream ahead of its own work, without a host wait (cap_instances_set alone leaves the forest's table as it is).  A context that never
+ * calls either has none.  cap_winding_drop and cap_scene_upload free them.  The scene table's bytes are never touched.
+ * Memory: 48 B per instance, 88 B per top-level entry, with an object table 64 B per forest node and 56 B per object, plus about 180 B
+ * per triangle of the largest object of build scratch, which is kept until cap_winding_drop.
+ * cap_winding_instances_readback copies them out (each pointer may be NULL): host_top 8 floats per top-level entry, host_inst 12
+ * floats per instance, host_forest 16 floats per forest node.  cap_winding_instances_info never builds anything: `built` says whether
+ * current tables exist, and only then are contributing, forest_records and the root words filled.
+ *
+ * cap_winding_instances.  One walk per point q, a binary64 accumulator, all decisions in binary32, every operation one rounded
+ * operation in the order written, no fused multiply-add, dot as cap_winding_numbers'.
+ * Top level: the implicit tree from its root.  At a node the two entries are decided, slot 0 then slot 1: an empty entry is skipped;
+ * otherwise cap_winding_numbers' far rule and far term on the world dipole (p~_w, r, N_w) and q, unchanged, counted in visits[0].
+ * The far terms of a node are added first; then the entries that are neither empty nor far are entered, slot 0's subtree first.  An
+ * entry of level 0 that is entered is an instance i, counted in visits[1]:
+ *   p'_r = fl(fl(fl(fl(W_r0*q.x) + fl(W_r1*q.y)) + fl(W_r2*q.z)) + W_r3), W the stored world-to-object matrix (cap_instances_readback);
+ *   if p' is degenerate by the points' own rule (a coordinate that is not finite) the instance adds nothing and is not counted.
+ * Then cap_winding_numbers' walk of the object's tree from the object's root over the object's table, with, for an object-space
+ * difference d', d_w = (dot(L_0, d'), dot(L_1, d'), dot(L_2, d')), L_r the rows of the stored L:
+ *   far rule    d' = fl(p~ - p'), d2 = dot(d_w, d_w), lim = fl(beta * fl(sigma * r)); FAR iff d2 > fl(lim * lim);
+ *   far term    fl(fl(|det L| * dot(N, d')) / fl(fl(k4 * d2) * sqrt(d2))), counted in visits[2] (the world area vector is cof(L) N,
+ *               and the cofactor cancels against L d');
+ *   exact term  a' = fl(v0 - p'), b' = fl(a' + e1), c' = fl(a' + e2); a, b, c their images under d_w; la, lb, lc, den from a, b, c as
+ *               in cap_winding_numbers; det = fl(|det L| * dot(a', n)), which is s det_w; term = fl(atan2f(det, den) * k2); a leaf
+ *               adds its number of triangles to visits[3].
+ * A NaN term adds nothing.  device_winding[j] is the accumulator rounded once.  A point with a non-finite coordinate gets a quiet NaN
+ * and visits (0, 0, 0, 0); a table without a contributing instance, or an empty scene, gives 0.0.  The decisions -- and so
+ * device_visits -- are reproducible bit for bit by a float32 restatement on the read-backs.
+ * Identity (tested): with one identity instance of a scene without negative zero, beta = +inf gives cap_winding_numbers' bits; at a
+ * finite beta so does every point whose visits[0] is 0, and visits[2], visits[3] are then cap_winding_numbers' pair.
+ * beta: finite and >= 1, or +inf (the exact sum); anything else is CAP_ERR_INVALID_ARG.  The error at beta = 2 is of the size of
+ * cap_winding_numbers' (DESIGN.md "Winding numbers over instances").
+ * Conventions are cap_winding_numbers': device_points 16-byte aligned, device_winding (4 B per point) and device_visits (16 B per
+ * point; may be NULL) 4-byte aligned, no two ranges overlap, nothing is written on an error, n above 2^24 is split into launches, n = 0
+ * does nothing, asynchronous on the context stream.  CAP_ERR_STATE without an instance table, without a winding table, before
+ * cap_bvh_build and while the trees are stale.
+ * Not covered: mesh masks and a per-call inclusion mask, higher moments, a per-point beta. */
+typedef struct CapWindingInstancesInfo /* 160 B */
+{
+    uint32_t instances;         /* of the installed table */
+    uint32_t contributing;
+    uint32_t levels;            /* of the top-level tree */
+    uint32_t entries;           /* of all levels, padding included: host_top holds 8 floats for each */
+    uint32_t forest_records;    /* 0 without an object table */
+    uint32_t built;             /* 1: derived tables exist and are current */
+    uint32_t level_entries[25]; /* entries per level, padding included: level l starts at the sum of the levels below */
+    uint32_t reserved;
+    double   total_weight;      /* of the whole table */
+    float    root_n[3];         /* N_w of the whole table */
+    float    root_p[3];         /* p~_w of the whole table */
+} CapWindingInstancesInfo;
+int cap_winding_instances(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, float beta, float* device_winding,
+                          uint32_t* device_visits /* may be NULL: 4 per point */);
+int cap_winding_instances_info(CapContext* ctx, CapWindingInstancesInfo* out);
+int cap_winding_instances_readback(CapContext* ctx, float* host_top /* 8 floats per top-level entry */,
+                                   float* host_inst /* 12 floats per instance */,
+                                   float* host_forest /* 16 floats per forest node; each may be NULL */);
 
 /* ---- objects: per-mesh-range bottom-level trees for the instanced queries ----
  * An object is the mesh range [first_mesh, first_mesh + mesh_count) of the uploaded scene: mesh_count >= 1, at least one triangle,
@@ -1009,6 +1097,9 @@ int cap_objects_set(CapContext* ctx, const CapObjectRange* ranges /* host */, ui
 /* the first min(capacity, count) entries into `out` (host; may be NULL when capacity is 0), the table's count into *count_out (may be
  * NULL); 0 objects without a table */
 int cap_objects_info(CapContext* ctx, CapObjectInfo* out, uint32_t capacity, uint32_t* count_out);
+/* the forest as cap_bvh_readback gives the scene's tree: 16 floats per forest node (object k's nodes follow object k - 1's, child codes
+ * in the forest's numbering) and the scene's triangle id of every forest record; each may be NULL.  CAP_ERR_STATE without a table. */
+int cap_objects_readback(CapContext* ctx, float* host_nodes, uint32_t* host_leaf_triangles);
 
 /* ---- multi-GPU tile exchange (one gather of tile radiance at frame end) ---- */
 /* floats in this context's tile-ordered radiance buffer: max_tiles_per_shard * 64 * 4 (same on every shard) */

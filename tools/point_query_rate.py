@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """Throughput of the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances,
-cap_closest_instances_multi, cap_signed_distance_instances) and of cap_winding_numbers on the 262 k-triangle hall -- not part of
+cap_closest_instances_multi, cap_signed_distance_instances) and of cap_winding_numbers and cap_winding_instances on the 262 k-triangle hall -- not part of
 bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
-                                     [--k K [--counts]] [--instances N] [--signed] [--winding [--beta B]]
+                                     [--k K [--counts]] [--instances N] [--signed] [--winding [--beta B]]  (--winding goes with --instances N)
 
 --winding runs cap_winding_numbers at --beta B (default 2; inf sums every triangle exactly: use fewer --points) after
 cap_winding_build, on the same point sets (the radius is not read).  Each line carries its rate, mean_visits = the mean numbers of
 dipole terms and of exact triangle terms per point, inside (the share of points with w >= 1/2), and the table build:
 table_build_ms beside the tree's bvh_build_ms, and the table's statistics.
+
+--instances N together with --winding runs cap_winding_instances on the --instances layout and the same point sets.  Each line carries
+its rate, mean_visits = the means of the four visit counts (far terms at the top level, instances entered, far terms below instances,
+exact triangles), inside, derived_build_ms = the host time of building the derived tables (per-instance records, top-level dipoles) and
+waiting for them, and as the scale cap_winding_numbers on the same points at the same beta in the same process (flat_ms,
+flat_mpoints_per_s, flat_mean_visits, ratio_to_flat = the instanced rate over the flat one; N = 1 is the identity alone).
 
 --signed runs cap_signed_distance after cap_pseudonormals_build.  Each line carries its rate and, measured in the same process on the
 same points, cap_closest_points as the baseline (flat_ms, flat_mpoints_per_s, time_over_flat = the signed call's time over the plain
@@ -107,8 +113,8 @@ def main():
     ap.add_argument("--winding", action="store_true")
     ap.add_argument("--beta", type=float, default=2.0)
     a = ap.parse_args()
-    if a.winding and (a.signed or a.k is not None or a.instances is not None):
-        ap.error("--winding goes alone: the winding number takes no sign table, pages or instances")
+    if a.winding and (a.signed or a.k is not None):
+        ap.error("--winding goes alone or with --instances N: the winding number takes no sign table or pages")
     if a.signed and a.k is not None:
         ap.error("--signed does not go with --k: the sign is defined for the single record")
     if a.instances is not None and a.instances < 1:
@@ -158,6 +164,13 @@ def main():
         wn = r.build_winding()
         w = torch.empty((n,), dtype=torch.float32, device=dev)
         visits = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        if a.instances is not None:
+            visits4 = torch.empty((n, 4), dtype=torch.int32, device=dev)
+            r.sync()
+            t0 = time.perf_counter()
+            capi._check(L.cap_winding_instances_readback(r.ctx, None, None, None), "cap_winding_instances_readback")  # builds, and waits
+            derived_ms = (time.perf_counter() - t0) * 1e3
+            wi = r.winding_instances_info()
         for name, xyz in sets:
             q = np.zeros((n, 4), np.float32)
             q[:, 0:3] = xyz
@@ -166,6 +179,18 @@ def main():
             sec = timed(r, lambda: capi._check(L.cap_winding_numbers(r.ctx, pts.data_ptr(), n, a.beta, w.data_ptr(), visits.data_ptr()), "cap_winding_numbers"),
                         a.reps, a.warmup)
             mean = visits.double().mean(0).cpu().numpy()
+            if a.instances is not None:
+                inside_flat = w >= 0.5
+                isec = timed(r, lambda: capi._check(L.cap_winding_instances(r.ctx, pts.data_ptr(), n, a.beta, w.data_ptr(), visits4.data_ptr()),
+                                                    "cap_winding_instances"), a.reps, a.warmup)
+                mean4 = visits4.double().mean(0).cpu().numpy()
+                print(json.dumps(dict(head, set=name, beta=a.beta, instances=a.instances, contributing=int(wi.contributing), tlas_depth=int(info_i.tlas_depth),
+                                      ms=round(isec * 1e3, 3), mpoints_per_s=round(n / isec / 1e6, 2), mean_visits=[round(float(x), 2) for x in mean4],
+                                      inside=round(float((w >= 0.5).float().mean()), 4), derived_build_ms=round(derived_ms, 3), flat_ms=round(sec * 1e3, 3),
+                                      flat_mpoints_per_s=round(n / sec / 1e6, 2), flat_mean_visits=[round(float(mean[0]), 2), round(float(mean[1]), 2)],
+                                      flat_inside=round(float(inside_flat.float().mean()), 4), ratio_to_flat=round(sec / isec, 3),
+                                      table_build_ms=round(wn.ms, 3))), flush=True)
+                continue
             print(json.dumps(dict(head, set=name, beta=a.beta, ms=round(sec * 1e3, 3), mpoints_per_s=round(n / sec / 1e6, 2),
                                   mean_visits=[round(float(mean[0]), 2), round(float(mean[1]), 2)], inside=round(float((w >= 0.5).float().mean()), 4),
                                   table_build_ms=round(wn.ms, 3), bvh_build_ms=round(info.build_ms, 3),
