@@ -1,5 +1,5 @@
-// cap_query_walk.h — what the per-lane query kernels of query.hip, instance.hip and point_query.hip share: the binary tree's node step
-// and pop for a ray, the state of the instance table's stack-free top-level walk, and the host-side dispatch from run-time values
+// cap_query_walk.h — what the per-lane query kernels of query.hip, instance.hip, point_query.hip and winding.hip share: the binary tree's
+// node step and pop for a ray, the state and the tail of the instance table's stack-free top-level walk, and the host-side dispatch from run-time values
 // (stack class, list capacity, flags) to kernel instantiations.  Every device helper is __forceinline__; how its state crosses it is
 // deliberate (DESIGN.md "How state crosses a helper decides what the compiler makes of it").
 #pragma once
@@ -67,6 +67,42 @@ __device__ __forceinline__ TopWalk top_start(const TlasDev& tl) { return TopWalk
 __device__ __forceinline__ TopWalk top_pop(TopWalk t)
 {
     t.todo0 = t.todo1, t.todo0_d = t.todo1_d, t.todo1 = kInvalidId;
+    return t;
+}
+
+// The tail of a top-level step, after the caller's own test of the node's two children (h0, h1: which pass; far_first: both pass and
+// child 1 goes first; i0, i1: word 7 of the two, the instances at level 1; d0, d1: their distances for the queue): down into the first
+// child that passes, marking the other as owed; or, at level 1, the instances into the queue; or up to the nearest level that owes a
+// child.
+__device__ __forceinline__ TopWalk top_advance(TopWalk t, bool h0, bool h1, bool far_first, uint32_t i0, uint32_t i1, float d0, float d1)
+{
+    if (t.level > 1u)
+    {
+        if (h0 || h1)
+        {
+            if (h0 && h1) t.pending |= 1u << (t.level - 1u);
+            t.idx   = 2u * t.idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
+            t.level = t.level - 1u;
+            return t;
+        }
+    }
+    else if (h0 || h1)
+    {
+        if (h0 && h1)
+            t.todo0 = far_first ? i1 : i0, t.todo0_d = far_first ? d1 : d0, t.todo1 = far_first ? i0 : i1, t.todo1_d = far_first ? d0 : d1;
+        else
+            t.todo0 = h0 ? i0 : i1, t.todo0_d = h0 ? d0 : d1;
+    }
+    const uint32_t owed = t.pending >> t.level;
+    if (owed == 0u)
+    {
+        t.done = true;
+        return t;
+    }
+    const uint32_t up = (uint32_t)__builtin_ctz(owed);
+    t.idx     = (t.idx >> up) ^ 1u;
+    t.level   = t.level + up;
+    t.pending = t.pending & ~(1u << t.level);
     return t;
 }
 

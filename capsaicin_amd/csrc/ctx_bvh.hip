@@ -218,6 +218,20 @@ static int pseudonormals_rebuild(CapContext* c, const char* what)
     return CAP_OK;
 }
 
+// One dipole build (winding.hip) over a tree of t triangles, the scene's (no recs, bases 0) or an object's at (node_base, rec_base) of the
+// forest's pools: its scratch, and its arguments from scratch of at least that size; root receives the tree's sums
+static size_t winding_scratch_reals(uint32_t t) { return t ? 7 * (size_t)t + 14 * (size_t)(t - 1) : 0; }  // per triangle, per inner node
+static size_t winding_scratch_words(uint32_t t) { return t ? 2 * (size_t)(t - 1) + 2 : 0; }               // per inner node, two counters
+static WindingBuildArgs winding_build_args(const CapContext* c, const float4* nodes, float4* table, const float4* recs, uint32_t node_base, uint32_t rec_base,
+                                           uint32_t t, double* reals, uint32_t* words, double* root)
+{
+    WindingBuildArgs a{c->positions.p, c->indices.p, c->tri_ids.p, c->mesh_offsets.p, t};  // (the rest zero)
+    a.nodes = nodes + 4 * (size_t)node_base, a.table = table + 4 * (size_t)node_base, a.node_base = node_base, a.rec_base = rec_base;
+    a.leaf_tri = c->leaf_tri.p, a.rec_ids = recs ? recs + 4 * (size_t)rec_base : nullptr;
+    a.tri_sums = reals, a.sums = reals + 7 * (size_t)t, a.root = root, a.parent = words, a.flags = words + (t - 1u), a.stats = words + 2 * (size_t)(t - 1u);
+    return a;
+}
+
 // The dipole table of cap_winding_numbers from the current vertices and the current binary tree (winding.hip): what cap_winding_build,
 // cap_bvh_build and cap_bvh_refit share, by pseudonormals_rebuild's rules.  The scratch goes when the call returns.  Waits for the
 // stream: the statistics are read back.  A failure drops the table.
@@ -240,13 +254,9 @@ static int winding_rebuild(CapContext* c)
         }
         DevBuf<double>   reals;
         DevBuf<uint32_t> words;
-        HIP_TRY(reals.ensure(7 * (size_t)t + 14 * (size_t)inner));
-        HIP_TRY(words.ensure(2 * (size_t)inner + 2));
-        WindingBuildArgs a{};
-        a.positions = c->positions.p, a.indices = c->indices.p, a.tri_ids = c->tri_ids.p, a.mesh_offsets = c->mesh_offsets.p, a.tri_count = t;
-        a.nodes = c->nodes.p, a.leaf_tri = c->leaf_tri.p, a.table = c->wn_table.p;
-        a.tri_sums = reals.p, a.sums = reals.p + 7 * (size_t)t, a.root = c->wn_root.p;
-        a.parent = words.p, a.flags = words.p + inner, a.stats = words.p + 2 * (size_t)inner;
+        HIP_TRY(reals.ensure(winding_scratch_reals(t)));
+        HIP_TRY(words.ensure(winding_scratch_words(t)));
+        const WindingBuildArgs a = winding_build_args(c, c->nodes.p, c->wn_table.p, nullptr, 0, 0, t, reals.p, words.p, c->wn_root.p);
         launch_winding_build(c->stream, a);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(stats, a.stats, sizeof(stats), hipMemcpyDeviceToHost, c->stream));
@@ -279,8 +289,7 @@ int cap::winding_instances_ensure(CapContext* c, const char* what)
     tlas_layout(n, off, &total);
     uint32_t forest_nodes = 0, max_n = 0;
     for (uint32_t k = 0; k < c->obj_count; ++k) forest_nodes += c->obj_info[k].triangle_count - 1u, max_n = std::max(max_n, c->obj_info[k].triangle_count);
-    const size_t roots = 7 * (size_t)std::max(c->obj_count, 1u), reals = c->obj_count ? 7 * (size_t)max_n + 14 * (size_t)max_n : 0,
-                 words = c->obj_count ? 2 * (size_t)max_n + 2 : 0;
+    const size_t roots = 7 * (size_t)std::max(c->obj_count, 1u), reals = winding_scratch_reals(max_n), words = winding_scratch_words(max_n);
     if (c->wi_inst.n < 3 * (size_t)n || c->wi_top.n < 2 * (size_t)total || c->wi_forest.n < 4 * (size_t)forest_nodes || c->wi_obj_root.n < roots ||
         c->wi_reals.n < reals || c->wi_words.n < words || !c->wi_count.p)
     {
@@ -299,18 +308,9 @@ int cap::winding_instances_ensure(CapContext* c, const char* what)
         }
     }
     if (c->obj_count && c->wi_forest_dirty)
-        for (uint32_t k = 0; k < c->obj_count; ++k)
-        {
-            const CapObjectInfo& o = c->obj_info[k];
-            const uint32_t       t = o.triangle_count, inner = t - 1u;
-            WindingBuildArgs     a{};
-            a.positions = c->positions.p, a.indices = c->indices.p, a.tri_ids = c->tri_ids.p, a.mesh_offsets = c->mesh_offsets.p, a.tri_count = t;
-            a.nodes = c->forest_nodes.p + 4 * (size_t)c->obj_node_base[k], a.table = c->wi_forest.p + 4 * (size_t)c->obj_node_base[k];
-            a.rec_ids = c->forest_tris.p + 4 * (size_t)c->obj_rec_base[k], a.node_base = c->obj_node_base[k], a.rec_base = c->obj_rec_base[k];
-            a.tri_sums = c->wi_reals.p, a.sums = c->wi_reals.p + 7 * (size_t)t, a.root = c->wi_obj_root.p + 7 * (size_t)k;
-            a.parent = c->wi_words.p, a.flags = c->wi_words.p + inner, a.stats = c->wi_words.p + 2 * (size_t)inner;
-            launch_winding_build(c->stream, a);  // (the objects share the scratch: the stream orders them)
-        }
+        for (uint32_t k = 0; k < c->obj_count; ++k)  // (the objects share the scratch: the stream orders them)
+            launch_winding_build(c->stream, winding_build_args(c, c->forest_nodes.p, c->wi_forest.p, c->forest_tris.p, c->obj_node_base[k], c->obj_rec_base[k],
+                                                               c->obj_info[k].triangle_count, c->wi_reals.p, c->wi_words.p, c->wi_obj_root.p + 7 * (size_t)k));
     WindingInstBuildArgs b{};
     b.descs = c->inst_desc.p, b.rec = c->inst_rec.p, b.tlas = c->inst_tlas.p, b.n = n;
     b.obj_root = c->obj_count ? c->wi_obj_root.p : c->wn_root.p;

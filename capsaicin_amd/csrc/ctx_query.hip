@@ -370,49 +370,39 @@ int closest_query(CapContext* c, const char* what, const CapPointDesc* points, u
     });
 }
 
-// cap_winding_numbers (winding.hip k_winding): the walk of the binary tree over the dipole table.  No options: the moments cover every
-// triangle, so there is no filter to check.
-int winding_query(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, float beta, float* winding, uint32_t* visits)
+// cap_winding_numbers (winding.hip k_winding: the walk of the binary tree over the dipole table) and, with `instanced`,
+// cap_winding_instances (k_winding_inst: the two-level walk over the top-level dipoles and the objects' tables; four visit words per point
+// instead of two).  No options: the moments cover every triangle, so there is no filter to check.  The derived tables of the instanced
+// form are brought up to date on the stream after the last check, ahead of the first launch.
+int winding_query(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, float beta, float* winding, uint32_t* visits, bool instanced)
 {
+    const uint32_t vw = instanced ? 4u : 2u;
     if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
     if (!(beta >= 1.0f)) return fail(CAP_ERR_INVALID_ARG, "%s: beta = %g must be finite and >= 1, or +inf", what, (double)beta);  // (a NaN fails the comparison)
     if (const int rc = query_state(c, what)) return rc;
     if (!c->wn_ready) return fail(CAP_ERR_STATE, "%s: call cap_winding_build first", what);
+    if (instanced && c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
     if (n == 0) return CAP_OK;
     if (!points || !winding) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
     if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("winding", winding, sizeof(float), 4),
-                                              range("visits", visits, 2 * sizeof(uint32_t), 4)}))
+                                              range("visits", visits, vw * sizeof(uint32_t), 4)}))
         return rc;
     QueryRun run;
     if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    if (instanced)
+    {
+        if (const int rc = winding_instances_ensure(c, what)) return rc;
+        use_instance_pools(run);
+    }
+    const float4* table = instanced && c->obj_count ? c->wi_forest.p : c->wn_table.p;
     return for_each_chunk(run, points, n, [&](const QueryArgs& chunk, uint64_t first) {
-        launch_winding_numbers(run.cfg, run.bvh, WindingArgs{chunk.rays, chunk.n, c->wn_table.p, beta, winding + first, at(visits, 2 * first)}, c->bvh_info.max_depth);
-        return run.traced("k_winding", first);
-    });
-}
-
-// cap_winding_instances (winding.hip k_winding_inst): the two-level walk over the top-level dipoles and the objects' tables.  The derived
-// tables are brought up to date on the stream after the last check, ahead of the first launch.
-int winding_instances_query(CapContext* c, const char* what, const CapPointDesc* points, uint64_t n, float beta, float* winding, uint32_t* visits)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (!(beta >= 1.0f)) return fail(CAP_ERR_INVALID_ARG, "%s: beta = %g must be finite and >= 1, or +inf", what, (double)beta);  // (a NaN fails the comparison)
-    if (const int rc = query_state(c, what)) return rc;
-    if (!c->wn_ready) return fail(CAP_ERR_STATE, "%s: call cap_winding_build first", what);
-    if (c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
-    if (n == 0) return CAP_OK;
-    if (!points || !winding) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    if (const int rc = check_ranges(what, n, {range("points", points, sizeof(CapPointDesc), 16), range("winding", winding, sizeof(float), 4),
-                                              range("visits", visits, 4 * sizeof(uint32_t), 4)}))
-        return rc;
-    QueryRun run;
-    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
-    if (const int rc = winding_instances_ensure(c, what)) return rc;
-    use_instance_pools(run);
-    const float4* table = c->obj_count ? c->wi_forest.p : c->wn_table.p;
-    return for_each_chunk(run, points, n, [&](const QueryArgs& chunk, uint64_t first) {
-        const WindingInstArgs a{WindingArgs{chunk.rays, chunk.n, table, beta, winding + first, at(visits, 4 * first)}, c->wi_inst.p, c->wi_top.p};
-        launch_winding_instances(run.cfg, run.bvh, a, run.tl, run.depth);
+        const WindingArgs a{chunk.rays, chunk.n, table, beta, winding + first, at(visits, vw * first)};
+        if (!instanced)
+        {
+            launch_winding_numbers(run.cfg, run.bvh, a, c->bvh_info.max_depth);
+            return run.traced("k_winding", first);
+        }
+        launch_winding_instances(run.cfg, run.bvh, WindingInstArgs{a, c->wi_inst.p, c->wi_top.p}, run.tl, run.depth);
         return run.traced("k_winding_inst", first);
     });
 }
@@ -422,12 +412,12 @@ extern "C" {
 
 int cap_winding_instances(CapContext* c, const CapPointDesc* device_points, uint64_t n, float beta, float* device_winding, uint32_t* device_visits)
 {
-    return winding_instances_query(c, "cap_winding_instances", device_points, n, beta, device_winding, device_visits);
+    return winding_query(c, "cap_winding_instances", device_points, n, beta, device_winding, device_visits, true);
 }
 
 int cap_winding_numbers(CapContext* c, const CapPointDesc* device_points, uint64_t n, float beta, float* device_winding, uint32_t* device_visits)
 {
-    return winding_query(c, "cap_winding_numbers", device_points, n, beta, device_winding, device_visits);
+    return winding_query(c, "cap_winding_numbers", device_points, n, beta, device_winding, device_visits, false);
 }
 
 int cap_trace_rays(CapContext* c, const CapRayDesc* device_rays, uint64_t n, CapHit* device_hits, uint32_t flags)

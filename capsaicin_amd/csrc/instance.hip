@@ -245,37 +245,7 @@ __device__ __forceinline__ TopWalk ray_top_step(const TlasDev& tl, const uint32_
     const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
     float         tn0, tn1;
     const bool    h0 = tlas_slab(rwb, lo0, hi0, omax, tfar, tn0), h1 = tlas_slab(rwb, lo1, hi1, omax, tfar, tn1);
-    const bool    far_first = h0 && h1 && tn1 < tn0;
-    if (t.level > 1u)
-    {
-        if (h0 || h1)
-        {
-            if (h0 && h1) t.pending |= 1u << (t.level - 1u);
-            t.idx   = 2u * t.idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
-            t.level = t.level - 1u;
-            return t;
-        }
-    }
-    else if (h0 || h1)
-    {
-        // the children are instances: the nearer box first
-        const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
-        if (h0 && h1)
-            t.todo0 = far_first ? i1 : i0, t.todo0_d = far_first ? tn1 : tn0, t.todo1 = far_first ? i0 : i1, t.todo1_d = far_first ? tn0 : tn1;
-        else
-            t.todo0 = h0 ? i0 : i1, t.todo0_d = h0 ? tn0 : tn1;
-    }
-    const uint32_t owed = t.pending >> t.level;
-    if (owed == 0u)
-    {
-        t.done = true;
-        return t;
-    }
-    const uint32_t up = (uint32_t)__builtin_ctz(owed);
-    t.idx     = (t.idx >> up) ^ 1u;
-    t.level   = t.level + up;
-    t.pending = t.pending & ~(1u << t.level);
-    return t;
+    return top_advance(t, h0, h1, h0 && h1 && tn1 < tn0, f2u(hi0.w), f2u(hi1.w), tn0, tn1);  // the nearer box first
 }
 
 // The object-space ray of the contract in instance `inst`: twelve operations, no fused multiply-add.

@@ -416,37 +416,7 @@ __device__ __forceinline__ TopWalk top_step(const TlasDev& tl, const uint32_t* l
     const float   d1 = box_dist2(px, py, pz, lo1.x, lo1.y, lo1.z, hi1.x, hi1.y, hi1.z);
     // (a record with k < 0 holds nothing: an inert instance or the padding of a level)
     const bool h0 = lo0.w >= 0.0f && !near_skip(d0, bound2_top), h1 = lo1.w >= 0.0f && !near_skip(d1, bound2_top);
-    const bool far_first = h0 && h1 && d1 < d0;
-    if (t.level > 1u)
-    {
-        if (h0 || h1)
-        {
-            if (h0 && h1) t.pending |= 1u << (t.level - 1u);
-            t.idx   = 2u * t.idx + ((h0 && h1) ? (far_first ? 1u : 0u) : (h1 ? 1u : 0u));
-            t.level = t.level - 1u;
-            return t;
-        }
-    }
-    else if (h0 || h1)
-    {
-        // the children are instances: the nearer box first
-        const uint32_t i0 = f2u(hi0.w), i1 = f2u(hi1.w);
-        if (h0 && h1)
-            t.todo0 = far_first ? i1 : i0, t.todo0_d = far_first ? d1 : d0, t.todo1 = far_first ? i0 : i1, t.todo1_d = far_first ? d0 : d1;
-        else
-            t.todo0 = h0 ? i0 : i1, t.todo0_d = h0 ? d0 : d1;
-    }
-    const uint32_t owed = t.pending >> t.level;
-    if (owed == 0u)
-    {
-        t.done = true;
-        return t;
-    }
-    const uint32_t up = (uint32_t)__builtin_ctz(owed);
-    t.idx     = (t.idx >> up) ^ 1u;
-    t.level   = t.level + up;
-    t.pending = t.pending & ~(1u << t.level);
-    return t;
+    return top_advance(t, h0, h1, h0 && h1 && d1 < d0, f2u(hi0.w), f2u(hi1.w), d0, d1);  // the nearer box first
 }
 // Entering an instance: its mask joined with the call's (the mesh byte joins it per triangle), M for the leaves' world records,
 // p' = W p + W_t, which only the pruning sees, (g, slack) of cap_near.h and the root of the object's tree.  The caller maps its bound into

@@ -16,6 +16,14 @@
 // instances"): the same build on an object's node and record range of the forest (WindingBuildArgs::node_base, rec_base, rec_ids), the
 // derived tables (k_wi_instances: L, |det L|, sigma per instance; k_wi_top_leaves / k_wi_top_level: one world dipole per top-level
 // entry, level by level in binary64) and the two-level walk k_winding_inst at the end of the file.
+//
+// Each step stands once (DESIGN.md "Winding numbers", "One copy of each step"):
+//   dipole_record                    (p~, r) (N, word 7) from sums and a stored box: k_wn_records, k_wi_top_leaves, k_wi_top_level
+//   winding_far<M>, winding_exact<M> the two terms in the metric M of the walk: WnFlat (nothing to map) or WiInst (L, |det L|, sigma)
+//   winding_node_step<STACK, M>      an inner node: two far tests, the far terms slot 0 then slot 1, push / descend
+//   winding_leaf_step<M>             a leaf's exact terms in leaf order
+//   winding_top_step                 a top-level node over instances; its tail is top_advance, the pop ray_pop (cap_query_walk.h)
+// k_winding is node step, leaf step and pop in WnFlat; k_winding_inst is the top step, the entry into an instance and the same three in WiInst.
 #include "cap_kernels.h"
 #include "cap_leaf.h"
 #include "cap_query_walk.h"  // with_stack_class, launch_points
@@ -116,24 +124,30 @@ __global__ __launch_bounds__(kBlock) void k_wn_climb(WindingBuildArgs a)
     }
 }
 
+// The record rule, for the scene's and objects' tables and for the top level over instances: (p~, r) (N, word 7) from the sums
+// (N, weight, weight x centre) and the stored box (lo.xyz, hi.xyz).  p~ is the binary64 quotient rounded once to binary32, or the box
+// centre where the weight is 0; r is measured from that ROUNDED p~ to the farthest corner and stepped one ulp up.
+__device__ __forceinline__ void dipole_record(float4* out, const double* s, const float* box, const float& word7)
+{
+    const double w = s[3];
+    float        pc[3];
+    for (int j = 0; j < 3; ++j) pc[j] = w != 0.0 ? (float)(s[4 + j] / w) : (float)(0.5 * ((double)box[j] + (double)box[3 + j]));
+    double far[3];
+    for (int j = 0; j < 3; ++j) far[j] = fmax(fabs((double)box[j] - (double)pc[j]), fabs((double)box[3 + j] - (double)pc[j]));
+    float r = (float)sqrt(ddot(far[0], far[1], far[2], far[0], far[1], far[2]));
+    if (r >= 0.f && r < __builtin_inff()) r = u2f(f2u(r) + 1u);  // one ulp up: the ball is never too small
+    out[0] = make_float4(pc[0], pc[1], pc[2], r);
+    out[1] = make_float4((float)s[0], (float)s[1], (float)s[2], word7);
+}
+
 __global__ __launch_bounds__(kBlock) void k_wn_records(WindingBuildArgs a)
 {
     const uint32_t k = blockIdx.x * kBlock + threadIdx.x, n = a.tri_count;
     if (k >= 2u * (n - 1u)) return;
     const uint32_t node = k >> 1, slot = k & 1u;
     const float*   q    = reinterpret_cast<const float*>(a.nodes + 4 * (size_t)node);
-    const float*   box  = q + 6u * slot;  // (lo.xyz, hi.xyz) of the child as the tree stores it
-    const double*  s    = a.sums + 14 * (size_t)node + 7u * slot;
-    const double   area = s[3];
-    float          pc[3];
-    for (int j = 0; j < 3; ++j) pc[j] = area != 0.0 ? (float)(s[4 + j] / area) : (float)(0.5 * ((double)box[j] + (double)box[3 + j]));
-    double far[3];
-    for (int j = 0; j < 3; ++j) far[j] = fmax(fabs((double)box[j] - (double)pc[j]), fabs((double)box[3 + j] - (double)pc[j]));
-    float r = (float)sqrt(ddot(far[0], far[1], far[2], far[0], far[1], far[2]));
-    if (r >= 0.f && r < __builtin_inff()) r = u2f(f2u(r) + 1u);  // one ulp up: the ball is never too small
-    float4* const out = a.table + 4 * (size_t)node + 2u * slot;
-    out[0]            = make_float4(pc[0], pc[1], pc[2], r);
-    out[1]            = make_float4((float)s[0], (float)s[1], (float)s[2], q[14 + slot]);
+    // (the child's box as the tree stores it, its sums, its code)
+    dipole_record(a.table + 4 * (size_t)node + 2u * slot, a.sums + 14 * (size_t)node + 7u * slot, q + 6u * slot, q[14 + slot]);
 }
 
 // ---- the walk ----
@@ -144,33 +158,115 @@ constexpr float k4Pi    = 12.566371f;   // fl(4 pi)
 // of four waves at most, and that leaves 64 VGPRs, which the walk fits without scratch (tools/kernel_regs.sh; DESIGN.md "Winding numbers")
 constexpr int winding_blocks(int STACK) { return STACK <= 16 ? 8 : STACK <= 24 ? 6 : STACK <= 32 ? 5 : 2; }
 
-// A child's dipole seen from p, all binary32 and unfused: far iff d2 > fl(fl(beta r)^2); then the first-order term
-__device__ __forceinline__ bool winding_far(const float4 pr, const float4 nc, const float4 p, float beta, float& term)
+// ---- the steps of both walks, each once (DESIGN.md "Winding numbers", "One copy of each step") ----
+// The metric a walk measures its terms in.  kMapped: differences go through L before lengths and dots are taken, radii through sigma,
+// numerators through |det L|; without it `if constexpr` leaves none of that behind.  kGuardFar: a NaN FAR term adds nothing
+// (cap_winding_instances, at the top level and below an instance) or is added and makes the result NaN (cap_winding_numbers): the two
+// contracts differ as they were written and this file keeps both.  A NaN EXACT term adds nothing in either.
+struct WnFlat  // the scene's own space: nothing to map
+{
+    static constexpr bool kMapped = false, kGuardFar = false;
+};
+struct WiInst  // below an instance: what the object walk keeps of the instance it is in
+{
+    static constexpr bool kMapped = true, kGuardFar = true;
+    float                 l[9], det, sigma;
+};
+__device__ __forceinline__ void wi_world(const WiInst& t, float x, float y, float z, float& wx, float& wy, float& wz)
+{
+    wx = dot_c(t.l[0], t.l[1], t.l[2], x, y, z), wy = dot_c(t.l[3], t.l[4], t.l[5], x, y, z), wz = dot_c(t.l[6], t.l[7], t.l[8], x, y, z);
+}
+
+// A child's dipole seen from p, all binary32 and unfused: far iff d2 > fl(fl(beta r)^2); then the first-order term.  Below an instance
+// p = p' = W q and the object-space dipole is measured in world space through d_w = L d': the world ball of radius sigma r covers the
+// image of the object-space ball; the world area vector is cof(L) N, and the cofactor cancels against L d'.
+template <typename M>
+__device__ __forceinline__ bool winding_far(const float4 pr, const float4 nc, const float4 p, const M& m, float beta, float& term)
 {
     const float dx = pr.x - p.x, dy = pr.y - p.y, dz = pr.z - p.z;
-    const float d2  = dot_c(dx, dy, dz, dx, dy, dz);
-    const float lim = beta * pr.w;
+    float       wx = dx, wy = dy, wz = dz, r = pr.w;
+    if constexpr (M::kMapped) wi_world(m, dx, dy, dz, wx, wy, wz), r = m.sigma * pr.w;
+    const float d2  = dot_c(wx, wy, wz, wx, wy, wz);
+    const float lim = beta * r;
     if (!(d2 > lim * lim)) return false;
-    term = dot_c(nc.x, nc.y, nc.z, dx, dy, dz) / ((k4Pi * d2) * sqrtf(d2));
+    float num = dot_c(nc.x, nc.y, nc.z, dx, dy, dz);
+    if constexpr (M::kMapped) num = m.det * num;
+    term = num / ((k4Pi * d2) * sqrtf(d2));
     return true;
 }
 
-// Van Oosterom & Strackee on the stored record (v0, e1, e2, n = fl(e1 x e2)): a = v0 - p, b = a + e1, c = a + e2, det = dot(a, n)
-__device__ __forceinline__ float winding_exact(const float4 t0, const float4 t1, const float4 t2, const float4 p)
+// Van Oosterom & Strackee on the stored record (v0, e1, e2, n = fl(e1 x e2)): a = v0 - p, b = a + e1, c = a + e2, det = dot(a, n).
+// Below an instance the lengths and dots are those of the world corners L a, L b, L c, and s det_w = |det L| dot(a, n).
+template <typename M>
+__device__ __forceinline__ float winding_exact(const float4 t0, const float4 t1, const float4 t2, const float4 p, const M& m)
 {
-    const float ax = t0.x - p.x, ay = t0.y - p.y, az = t0.z - p.z;
-    const float bx = ax + t0.w, by = ay + t1.x, bz = az + t1.y;
-    const float cx = ax + t1.z, cy = ay + t1.w, cz = az + t2.x;
+    const float ox = t0.x - p.x, oy = t0.y - p.y, oz = t0.z - p.z;
+    float       ax = ox, ay = oy, az = oz;
+    float       bx = ox + t0.w, by = oy + t1.x, bz = oz + t1.y;
+    float       cx = ox + t1.z, cy = oy + t1.w, cz = oz + t2.x;
+    if constexpr (M::kMapped) wi_world(m, ax, ay, az, ax, ay, az), wi_world(m, bx, by, bz, bx, by, bz), wi_world(m, cx, cy, cz, cx, cy, cz);
     const float la = sqrtf(dot_c(ax, ay, az, ax, ay, az)), lb = sqrtf(dot_c(bx, by, bz, bx, by, bz)), lc = sqrtf(dot_c(cx, cy, cz, cx, cy, cz));
-    const float det = dot_c(ax, ay, az, t2.y, t2.z, t2.w);
+    float       det = dot_c(ox, oy, oz, t2.y, t2.z, t2.w);
+    if constexpr (M::kMapped) det = m.det * det;
     const float den = (((la * lb) * lc + dot_c(ax, ay, az, bx, by, bz) * lc) + dot_c(bx, by, bz, cx, cy, cz) * la) + dot_c(cx, cy, cz, ax, ay, az) * lb;
     return atan2f(det, den) * kInv2Pi;
 }
 
-// One lane per point, a grid-stride loop.  At a node the far terms of its two slots are added first, slot 0 then slot 1; then the near
-// children are walked, slot 0's subtree before slot 1's (which waits as a node code in the lane's LDS column: at most one push per
-// level, STACK at least the tree's depth).  A leaf adds the exact term of each of its triangles in leaf order; a NaN term (a record
-// with a non-finite word) adds nothing.
+// A far term joins the sum by the rule of the walk G it was taken in
+template <typename G>
+__device__ __forceinline__ void winding_add_far(double& acc, float term)
+{
+    if constexpr (G::kGuardFar)
+        acc += term == term ? (double)term : 0.0;
+    else
+        acc += (double)term;
+}
+
+// An inner node of a dipole table: the far terms of its two slots are added first, slot 0 then slot 1; then the near children are
+// walked, slot 0's subtree before slot 1's (which waits as a node code in the lane's LDS column: at most one push per level, STACK at
+// least the tree's depth; the guard drops a push beyond it).  true: both are far, the caller pops.  node and sp cross by reference;
+// the leaf step takes and returns the sum by value (through a reference it cost k_winding 2 VGPRs).
+template <int STACK, typename M>
+__device__ __forceinline__ bool winding_node_step(const float4* table, const float4 p, const M& m, float beta, uint32_t* stack, double& acc, uint32_t& far,
+                                                  int& node, int& sp)
+{
+    const float4* rec = table + 4 * (size_t)node;
+    const float4  r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+    float         t0 = 0.f, t1 = 0.f;
+    const bool    f0 = winding_far(r0, r1, p, m, beta, t0), f1 = winding_far(r2, r3, p, m, beta, t1);
+    if (f0) winding_add_far<M>(acc, t0), ++far;
+    if (f1) winding_add_far<M>(acc, t1), ++far;
+    const int c0 = (int)f2u(r1.w), c1 = (int)f2u(r3.w);
+    if (!f0 && !f1)
+    {
+        if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)c1;
+        node = c0;
+        return false;
+    }
+    if (!f0 || !f1)
+    {
+        node = f0 ? c1 : c0;
+        return false;
+    }
+    return true;
+}
+
+// A leaf: the exact term of each of its triangles in leaf order; a NaN term (a record with a non-finite word) adds nothing
+template <typename M>
+__device__ __forceinline__ double winding_leaf_step(const float4* tris, int node, const float4 p, const M& m, double acc, uint32_t& exact)
+{
+    const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+    for (uint32_t leaf = first; leaf <= last; ++leaf)
+    {
+        const float t = winding_exact(tris[4 * (size_t)leaf + 0], tris[4 * (size_t)leaf + 1], tris[4 * (size_t)leaf + 2], p, m);
+        if (t == t) acc += (double)t;
+    }
+    exact += last - first + 1u;
+    return acc;
+}
+
+// One lane per point, a grid-stride loop over winding_node_step, winding_leaf_step and the pop.  (The pop is ray_pop's body: called
+// as ray_pop it gives this kernel another block layout and a 46th VGPR; k_winding_inst calls it.)
 template <int STACK>
 __global__ __launch_bounds__(kBlock, winding_blocks(STACK)) void k_winding(BvhDev bvh, WindingArgs w)
 {
@@ -188,35 +284,10 @@ __global__ __launch_bounds__(kBlock, winding_blocks(STACK)) void k_winding(BvhDe
         {
             if (node >= 0)
             {
-                const float4* rec = w.table + 4 * (size_t)node;
-                const float4  r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-                float         t0 = 0.f, t1 = 0.f;
-                const bool    f0 = winding_far(r0, r1, p, w.beta, t0), f1 = winding_far(r2, r3, p, w.beta, t1);
-                if (f0) acc += (double)t0, ++far;
-                if (f1) acc += (double)t1, ++far;
-                const int c0 = (int)f2u(r1.w), c1 = (int)f2u(r3.w);
-                if (!f0 && !f1)
-                {
-                    if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)c1;
-                    node = c0;
-                    continue;
-                }
-                if (!f0 || !f1)
-                {
-                    node = f0 ? c1 : c0;
-                    continue;
-                }
+                if (!winding_node_step<STACK>(w.table, p, WnFlat{}, w.beta, stack, acc, far, node, sp)) continue;
             }
             else
-            {
-                const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
-                for (uint32_t leaf = first; leaf <= last; ++leaf)
-                {
-                    const float t = winding_exact(bvh.tris[4 * (size_t)leaf + 0], bvh.tris[4 * (size_t)leaf + 1], bvh.tris[4 * (size_t)leaf + 2], p);
-                    if (t == t) acc += (double)t;
-                }
-                exact += last - first + 1u;
-            }
+                acc = winding_leaf_step(bvh.tris, node, p, WnFlat{}, acc, exact);
             if (sp == 0) break;
             node = (int)stack[(--sp) * kBlock];
         }
@@ -261,19 +332,11 @@ __device__ __forceinline__ void wi_store_empty(float4* e, uint32_t word7)
     e[1] = make_float4(0.f, 0.f, 0.f, u2f(word7));
 }
 
-// (p~_w, r) (N_w, word 7) of an entry from its sums and its stored world box: the scene table's rule (k_wn_records)
+// (p~_w, r) (N_w, word 7) of an entry from its sums and its stored world box
 __device__ __forceinline__ void wi_store_entry(float4* e, const double* s, const float4 lo, const float4 hi, uint32_t word7)
 {
-    const float  box[6] = {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z};
-    const double w      = s[3];
-    float        pc[3];
-    for (int j = 0; j < 3; ++j) pc[j] = w != 0.0 ? (float)(s[4 + j] / w) : (float)(0.5 * ((double)box[j] + (double)box[3 + j]));
-    double far[3];
-    for (int j = 0; j < 3; ++j) far[j] = fmax(fabs((double)box[j] - (double)pc[j]), fabs((double)box[3 + j] - (double)pc[j]));
-    float r = (float)sqrt(ddot(far[0], far[1], far[2], far[0], far[1], far[2]));
-    if (r >= 0.f && r < __builtin_inff()) r = u2f(f2u(r) + 1u);
-    e[0] = make_float4(pc[0], pc[1], pc[2], r);
-    e[1] = make_float4((float)s[0], (float)s[1], (float)s[2], u2f(word7));
+    const float box[6] = {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z};
+    dipole_record(e, s, box, u2f(word7));
 }
 
 // Level 0, entry j = the instance the TLAS holds there: N_w = s cof(L) N, p~_w = M p~, weight A |det L|^(2/3), from the root sums of the
@@ -333,56 +396,31 @@ __global__ __launch_bounds__(kBlock) void k_wi_top_level(WindingInstBuildArgs a,
 }
 
 // ---- winding numbers over instances: the walk ----
-struct WiInst  // what the object walk keeps of the instance it is in
-{
-    float l[9], det, sigma;
-};
-__device__ __forceinline__ void wi_world(const WiInst& t, float x, float y, float z, float& wx, float& wy, float& wz)
-{
-    wx = dot_c(t.l[0], t.l[1], t.l[2], x, y, z), wy = dot_c(t.l[3], t.l[4], t.l[5], x, y, z), wz = dot_c(t.l[6], t.l[7], t.l[8], x, y, z);
-}
-
-// winding_far below an instance: the object-space dipole seen from p' = W q, measured in world space through d_w = L d'.  The world ball
-// of radius sigma r covers the image of the object-space ball; the world area vector is cof(L) N, and the cofactor cancels against L d'.
-__device__ __forceinline__ bool winding_far_inst(const float4 pr, const float4 nc, const float4 p, const WiInst& t, float beta, float& term)
-{
-    const float dx = pr.x - p.x, dy = pr.y - p.y, dz = pr.z - p.z;
-    float       wx, wy, wz;
-    wi_world(t, dx, dy, dz, wx, wy, wz);
-    const float d2  = dot_c(wx, wy, wz, wx, wy, wz);
-    const float lim = beta * (t.sigma * pr.w);
-    if (!(d2 > lim * lim)) return false;
-    term = (t.det * dot_c(nc.x, nc.y, nc.z, dx, dy, dz)) / ((k4Pi * d2) * sqrtf(d2));
-    return true;
-}
-
-// winding_exact below an instance: lengths and dots of the world corners L a', L b', L c'; s det_w = |det L| dot(a', n)
-__device__ __forceinline__ float winding_exact_inst(const float4 t0, const float4 t1, const float4 t2, const float4 p, const WiInst& t)
-{
-    const float ox = t0.x - p.x, oy = t0.y - p.y, oz = t0.z - p.z;
-    float       ax, ay, az, bx, by, bz, cx, cy, cz;
-    wi_world(t, ox, oy, oz, ax, ay, az);
-    wi_world(t, ox + t0.w, oy + t1.x, oz + t1.y, bx, by, bz);
-    wi_world(t, ox + t1.z, oy + t1.w, oz + t2.x, cx, cy, cz);
-    const float la = sqrtf(dot_c(ax, ay, az, ax, ay, az)), lb = sqrtf(dot_c(bx, by, bz, bx, by, bz)), lc = sqrtf(dot_c(cx, cy, cz, cx, cy, cz));
-    const float det = t.det * dot_c(ox, oy, oz, t2.y, t2.z, t2.w);
-    const float den = (((la * lb) * lc + dot_c(ax, ay, az, bx, by, bz) * lc) + dot_c(bx, by, bz, cx, cy, cz) * la) + dot_c(cx, cy, cz, ax, ay, az) * lb;
-    return atan2f(det, den) * kInv2Pi;
-}
-
 // Workgroups per CU: the LDS slice (the stack and the 104 bytes of level offsets) allows 9, 6, 4 and 2; the instance's L, |det L| and
 // sigma, p' and the top-level state take the walk to 71 VGPRs, which seven workgroups of four waves still hold without scratch
 // (tools/kernel_regs.sh; DESIGN.md "Winding numbers over instances")
 constexpr int winding_inst_blocks(int STACK) { return STACK <= 16 ? 7 : STACK <= 24 ? 6 : STACK <= 32 ? 4 : 2; }
 
+// One top-level node (TopWalk, cap_query_walk.h; the queue's two distance words are not used): the far terms of its two entries are
+// added, slot 0 then slot 1, by winding_far on the world dipole; the near entries are what top_advance descends into, slot 0's subtree
+// first, or queues as instances at level 1.  An empty entry (r < 0) is neither far nor near.
+__device__ __forceinline__ TopWalk winding_top_step(const float4* top, const uint32_t* lds_off, const float4 q, float beta, double& acc, uint32_t& far_top,
+                                                    TopWalk t)
+{
+    const float4* e = top + 2 * (size_t)(lds_off[t.level - 1u] + 2u * t.idx);
+    const float4  r0 = e[0], r1 = e[1], r2 = e[2], r3 = e[3];
+    float         t0 = 0.f, t1 = 0.f;
+    const bool    f0 = r0.w >= 0.f && winding_far(r0, r1, q, WnFlat{}, beta, t0), f1 = r2.w >= 0.f && winding_far(r2, r3, q, WnFlat{}, beta, t1);
+    if (f0) winding_add_far<WiInst>(acc, t0), ++far_top;
+    if (f1) winding_add_far<WiInst>(acc, t1), ++far_top;
+    return top_advance(t, r0.w >= 0.f && !f0, r2.w >= 0.f && !f1, false, f2u(r1.w), f2u(r3.w), 0.f, 0.f);
+}
+
 // One lane per point, a grid-stride loop, one loop with three kinds of step as k_query_inst (instance.hip), so that the lanes of a wave
 // that are at the top level advance while others are inside an instance:
-//   * a top-level node (level, idx) of the implicit tree, without a stack: the far terms of its two entries are added, slot 0 then slot
-//     1, by winding_far on the world dipole; then the near entries are entered, slot 0's subtree first (`pending` holds one bit per
-//     level where slot 1 is still owed).  At level 1 the near entries are instances and wait in (todo0, todo1).  An empty entry (r < 0)
-//     is neither far nor near;
-//   * entering an instance: p' = W q by the point queries' formula; a degenerate p' leaves the instance out;
-//   * a node or leaf of the object's tree: k_winding's walk with winding_far_inst / winding_exact_inst.
+//   * a top-level node (winding_top_step);
+//   * entering the instance at the head of the queue: p' = W q by the point queries' formula; a degenerate p' leaves the instance out;
+//   * a node or leaf of the object's tree: k_winding's steps in the instance's metric.
 // visits: the far terms of the top level, the instances entered, the far terms below instances, the exact triangles.
 template <int STACK>
 __global__ __launch_bounds__(kBlock, winding_inst_blocks(STACK)) void k_winding_inst(BvhDev bvh, WindingInstArgs wa, TlasDev tl)
@@ -400,8 +438,8 @@ __global__ __launch_bounds__(kBlock, winding_inst_blocks(STACK)) void k_winding_
         double       acc = 0.0;
         uint32_t     far_top = 0u, entered = 0u, far = 0u, exact = 0u;
         const bool   ok = fabsf(q.x) < inf && fabsf(q.y) < inf && fabsf(q.z) < inf;  // (a NaN fails its comparison)
-        uint32_t     level = tl.top + 1u, idx = 0u, pending = 0u, todo0 = kInvalidId, todo1 = kInvalidId;
-        bool         done = false, in_obj = false;
+        TopWalk      top = top_start(tl);
+        bool         in_obj = false;
         WiInst       t{};
         float4       p = q;  // p' inside an instance
         int          node = 0, sp = 0;
@@ -411,45 +449,17 @@ __global__ __launch_bounds__(kBlock, winding_inst_blocks(STACK)) void k_winding_
             {
                 if (node >= 0)
                 {
-                    const float4* rec = w.table + 4 * (size_t)node;
-                    const float4  r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-                    float         t0 = 0.f, t1 = 0.f;
-                    const bool    f0 = winding_far_inst(r0, r1, p, t, w.beta, t0), f1 = winding_far_inst(r2, r3, p, t, w.beta, t1);
-                    if (f0) acc += t0 == t0 ? (double)t0 : 0.0, ++far;
-                    if (f1) acc += t1 == t1 ? (double)t1 : 0.0, ++far;
-                    const int c0 = (int)f2u(r1.w), c1 = (int)f2u(r3.w);
-                    if (!f0 && !f1)
-                    {
-                        if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)c1;
-                        node = c0;
-                        continue;
-                    }
-                    if (!f0 || !f1)
-                    {
-                        node = f0 ? c1 : c0;
-                        continue;
-                    }
+                    if (!winding_node_step<STACK>(w.table, p, t, w.beta, stack, acc, far, node, sp)) continue;
                 }
                 else
-                {
-                    const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
-                    for (uint32_t leaf = first; leaf <= last; ++leaf)
-                    {
-                        const float v = winding_exact_inst(bvh.tris[4 * (size_t)leaf + 0], bvh.tris[4 * (size_t)leaf + 1], bvh.tris[4 * (size_t)leaf + 2], p, t);
-                        if (v == v) acc += (double)v;
-                    }
-                    exact += last - first + 1u;
-                }
-                if (sp == 0)
-                    in_obj = false;
-                else
-                    node = (int)stack[(--sp) * kBlock];
+                    acc = winding_leaf_step(bvh.tris, node, p, t, acc, exact);
+                in_obj = ray_pop(stack, sp, node);
                 continue;
             }
-            if (todo0 != kInvalidId)
+            if (top.todo0 != kInvalidId)
             {
-                const uint32_t inst = todo0;
-                todo0 = todo1, todo1 = kInvalidId;
+                const uint32_t inst = top.todo0;
+                top                 = top_pop(top);
                 const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
                 p.x = (dot_c(w0.x, w0.y, w0.z, q.x, q.y, q.z)) + w0.w;
                 p.y = (dot_c(w1.x, w1.y, w1.z, q.x, q.y, q.z)) + w1.w;
@@ -462,40 +472,8 @@ __global__ __launch_bounds__(kBlock, winding_inst_blocks(STACK)) void k_winding_
                 sp = 0, in_obj = true, ++entered;
                 continue;
             }
-            if (done) break;
-            // a top-level node: its two entries
-            const float4* e = wa.top + 2 * (size_t)(lds_off[level - 1u] + 2u * idx);
-            const float4  r0 = e[0], r1 = e[1], r2 = e[2], r3 = e[3];
-            float         t0 = 0.f, t1 = 0.f;
-            const bool    f0 = r0.w >= 0.f && winding_far(r0, r1, q, w.beta, t0), f1 = r2.w >= 0.f && winding_far(r2, r3, q, w.beta, t1);
-            if (f0) acc += t0 == t0 ? (double)t0 : 0.0, ++far_top;
-            if (f1) acc += t1 == t1 ? (double)t1 : 0.0, ++far_top;
-            const bool n0 = r0.w >= 0.f && !f0, n1 = r2.w >= 0.f && !f1;
-            if (level > 1u)
-            {
-                if (n0 || n1)
-                {
-                    if (n0 && n1) pending |= 1u << (level - 1u);
-                    idx   = 2u * idx + (n0 ? 0u : 1u);
-                    level = level - 1u;
-                    continue;
-                }
-            }
-            else if (n0 || n1)
-            {
-                const uint32_t i0 = f2u(r1.w), i1 = f2u(r3.w);
-                todo0 = n0 ? i0 : i1, todo1 = n0 && n1 ? i1 : kInvalidId;
-            }
-            const uint32_t owed = pending >> level;
-            if (owed == 0u)
-            {
-                done = true;
-                continue;
-            }
-            const uint32_t up = (uint32_t)__builtin_ctz(owed);
-            idx     = (idx >> up) ^ 1u;
-            level   = level + up;
-            pending = pending & ~(1u << level);
+            if (top.done) break;
+            top = winding_top_step(wa.top, lds_off, q, w.beta, acc, far_top, top);
         }
         w.out[i] = ok ? (float)acc : __builtin_nanf("");
         if (w.visits)

@@ -9,7 +9,7 @@ from capsaicin_amd import capi
 from closest_point_support import arrays, around, bits, closest, context, queries, sphere
 from refit_support import cornell_scene
 from signed_distance_support import TRUTH_MESHES, mesh, truth_case, winding_number
-from winding_support import (BETAS, OPEN_MESHES, children, child_boxes, moments, octant_triangle, open_cube, punctured, query_case, unit_sphere, walk)
+from winding_support import (BETAS, OPEN_MESHES, children, child_boxes, moments, octant_triangle, open_cube, overflow_scene, punctured, query_case, unit_sphere, walk, walk32)
 
 pytestmark = pytest.mark.gpu
 
@@ -176,6 +176,30 @@ def test_known_answers(native_lib):
                 assert v.sum() >= 1
         finally:
             r.close()
+
+
+def test_far_term_overflow(native_lib):
+    """cap_winding_numbers adds a far term as it is: a NaN far term makes the result NaN (cap_winding_instances leaves such a term out;
+    test_winding_instances_gpu has the same scene).  Expected: winding_support.walk32 as it stands, visits bit for bit.  Every far term is
+    made of correctly rounded operations, so a value made of far terms alone has walk32's bits; an exact term differs from walk32's by
+    atan2f alone (2 ulp on the device, numpy's own error, one rounding of the product with 1 / (2 pi): under 5 ulp of a value of at most
+    1/2, 5 x 2^-25 < 2^-22 per term)."""
+    tris, pts = overflow_scene()
+    r = context([tris])
+    try:
+        r.build_winding()
+        nodes, order = r.bvh_readback()
+        want, want_visits = walk32(nodes, order, tris, r.winding_table(), pts, 2.0)
+        got, visits = raw_call(r, pts, 2.0)
+        print("far term overflow: gpu %r visits %r, walk32 %r visits %r" % (got.tolist(), visits.tolist(), want.tolist(), want_visits.tolist()))
+        assert want_visits.tolist() == [[2, 0], [2, 0], [0, 2]] and np.isnan(want[0]) and want[1] == 0.0, "the case is what it was built to be"
+        assert np.array_equal(visits.astype(np.int64), want_visits)
+        assert np.array_equal(np.isnan(got), np.isnan(want)) and np.isnan(got[0]), "a NaN far term is added: the result is NaN"
+        far_only = want_visits[:, 1] == 0
+        assert np.array_equal(bits(got[far_only]), bits(want[far_only].astype(np.float32)))
+        assert abs(float(got[2]) - want[2]) <= want_visits[2, 1] * 2.0 ** -22
+    finally:
+        r.close()
 
 
 def test_python_wrapper(native_lib):

@@ -13,7 +13,7 @@ from closest_point_support import arrays, bits, closest, context, queries
 from signed_distance_support import box, mesh, winding_number
 from winding_instances_support import (EMPTY, IDENTITY, State, affine, brute_force, contributes, grid_transforms, instance_records, level_offsets, off_surface,
                                        points_about, rotation, top_moments, walk, walk32, world_triangles)
-from winding_support import child_boxes, children, moments, octant_triangle, open_cube, punctured, root_code, triangle_sums, unit_sphere
+from winding_support import child_boxes, children, moments, octant_triangle, open_cube, overflow_scene, punctured, root_code, triangle_sums, unit_sphere
 
 pytestmark = pytest.mark.gpu
 
@@ -266,6 +266,29 @@ def test_one_identity_instance_is_the_scene_query(native_lib):
             assert same.sum() >= 300 and (np.isinf(beta) or (~same).sum() >= 50)
             assert np.array_equal(bits(got[same]), bits(flat[same])), "beta %s: cap_winding_numbers' bits" % beta
             assert np.array_equal(gv[same][:, 2:4], fv[same]) and (gv[same][:, 1] == 1).all()
+    finally:
+        r.close()
+
+
+def test_far_term_overflow(native_lib):
+    """cap_winding_instances leaves a NaN far term out, at the top level and below an instance (cap_winding_numbers adds it:
+    test_winding_gpu.test_far_term_overflow has the scene and the reasons of the bounds).  One identity instance; expected: walk32 as it
+    stands, visits bit for bit."""
+    tris, pts = overflow_scene()
+    r = context([tris])
+    try:
+        r.build_winding()
+        r.set_instances(IDENTITY[None])
+        got, visits = raw_call(r, pts, 2.0)
+        st, _, _ = device_state(r, tris, IDENTITY[None], None, None)
+        want, want_visits = walk32(st, pts, 2.0)
+        print("far term overflow: gpu %r visits %r, walk32 %r visits %r" % (got.tolist(), visits.tolist(), want.tolist(), want_visits.tolist()))
+        assert want_visits.tolist() == [[1, 0, 0, 0], [1, 0, 0, 0], [0, 1, 0, 2]] and want[0] == 0.0 and want[1] == 0.0, "the case is what it was built to be"
+        assert np.array_equal(visits.astype(np.int64), want_visits)
+        assert not np.isnan(got).any() and bits(got[0:1])[0] == 0, "a NaN far term adds nothing: 0.0 with one far term"
+        far_only = want_visits[:, 3] == 0
+        assert np.array_equal(bits(got[far_only]), bits(want[far_only].astype(np.float32)))
+        assert abs(float(got[2]) - want[2]) <= want_visits[2, 3] * 2.0 ** -22
     finally:
         r.close()
 

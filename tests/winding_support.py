@@ -270,6 +270,15 @@ def unit_sphere():
     return sphere(50, 50)
 
 
+def overflow_scene():
+    """two triangles with edges of 1e10 near the origin, both normals along +x, so that the root is an inner node with |N| = 5e19 per
+    slot; and three points: one whose d2 overflows to +inf and whose dot(N, d) overflows (the far term is inf / inf), one far with a
+    finite d2, one near both triangles"""
+    t = np.float32([[(0, 0, 0), (0, 1e10, 0), (0, 0, 1e10)]])
+    tris = np.concatenate([t, (t + np.float32([2e9, 3e9, -1e9])).astype(np.float32)])
+    return tris, queries(np.float32([(3e19, 0, 0), (1e15, 0, 0), (5e9, 3e9, 3e9)]))
+
+
 # ---- the query cases the CPU and GPU tests share ----
 OPEN_MESHES = {
     "open cube": open_cube,
