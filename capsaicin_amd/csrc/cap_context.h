@@ -1,5 +1,5 @@
-// cap_context.h — what the host units behind include/capsaicin_hip.h share (context.hip, ctx_scene.hip, ctx_bvh.hip, ctx_query.hip,
-// ctx_post.hip, ctx_comm.hip): the context and its buffers, the error reporting, and the helpers more than one unit calls.  Private to
+// cap_context.h — what the host units behind include/capsaicin_hip.h share (context.hip, ctx_render.hip, ctx_scene.hip, ctx_bvh.hip,
+// ctx_query.hip, ctx_post.hip, ctx_comm.hip): the context and its buffers, the error reporting, and the helpers more than one unit calls.  Private to
 // csrc/: nothing here is part of the ABI.
 #pragma once
 
@@ -79,6 +79,35 @@ struct TimedSpan
     hipEvent_t a, b;
     int        stage;
     int        also = ST_NONE;  // a span may count under a second label
+};
+
+// guard block of a context (ShadeArgs::shaded_counter): {-, malformed path ids seen by shade, by trace_any, last offender, appends
+// beyond a class's capacity, -, -, -}
+constexpr size_t kGuardWords = 8;
+
+// The counter block of a batch of `bounces` bounces (Lane::counters), in 32-bit words.  A queue has kQueueClasses x kCounterStride
+// words; per bounce and class one 64-bit word counts both queues, low half = extension entries, high half = shadow entries (one atomic
+// serves both), words 2 and 3 the probed shadow rays and the shaded vertices.  Three sections of one queue per bounce -- the queue
+// counters, the chunk-grab counters of the fused launch, those of the any-hit launch -- and behind them the camera rays' identity queue.
+// Only the first section is copied to the host (sync_and_collect).
+struct CounterLayout
+{
+    uint32_t bounces;
+    static constexpr size_t per_queue() { return (size_t)kQueueClasses * kCounterStride; }
+    size_t    section() const { return (size_t)(bounces + 1) * per_queue(); }
+    size_t    total() const { return 3 * section() + per_queue(); }
+    uint32_t* ext(uint32_t* base, uint32_t b) const { return base + b * per_queue(); }
+    uint32_t* shadow(uint32_t* base, uint32_t b) const { return base + 1 + b * per_queue(); }
+    uint32_t* work_shade(uint32_t* base, uint32_t b) const { return base + section() + b * per_queue(); }
+    uint32_t* work_any(uint32_t* base, uint32_t b) const { return base + 2 * section() + b * per_queue(); }
+    uint32_t* identity(uint32_t* base) const { return base + 3 * section(); }
+};
+
+// what sync_and_collect must know of a batch to sum its counters
+struct BatchCounted
+{
+    uint32_t num_bounces;
+    bool     shadow_queued;  // false: the batch's shadow rays were traced where they were generated, and never were queue entries
 };
 }  // namespace cap
 
@@ -232,7 +261,7 @@ struct CapContext
         DevBuf<float4>   hits, q_org[2], q_dir[2], q_thr[2], s_org, s_dir, s_con, pl_color, pl_direct, pl_albedo;
         DevBuf<float4>   camera;       // per batch: camera vertices, two planes [jitter group][Ppad] (launch_camera_vertices), if the form is on
         DevBuf<float4>   terms;        // per batch: direction-sample terms [sampling bounce][slot][4096] (ShadeArgs::sample_terms), if the form is on
-        DevBuf<uint32_t> counters;     // per batch: ext[0..D], shadow[0..D]
+        DevBuf<uint32_t> counters;     // per batch: CounterLayout
         DevBuf<uint32_t> stack_spill;  // traversal-stack entries beyond the LDS part, per thread of the persistent grid
     } lane[2];
     hipStream_t stream2 = nullptr;
@@ -270,7 +299,7 @@ struct CapContext
     std::vector<std::array<hipEvent_t, 6>> post_marks;  // pass-boundary events of every cap_post_frame since the last sync
     std::vector<hipEvent_t> event_pool;
     std::vector<uint32_t*> pinned_pool;
-    std::vector<std::pair<uint32_t*, uint32_t>> pending;  // (pinned counters, bounces) per batch, read at sync
+    std::vector<std::pair<uint32_t*, BatchCounted>> pending;  // (pinned copy of the counters' first section, what it counted) per batch, read at sync
     uint64_t*              pinned_shaded = nullptr;
 };
 
@@ -288,10 +317,13 @@ struct AovPlanes
 int        sync_and_collect(CapContext* c);
 hipEvent_t get_event(CapContext* c);
 CameraDev  camera_dev(const CapCameraData& cd);
+SceneDev   scene_dev(const CapContext* c);
 BvhDev     bvh_dev(const CapContext* c, const CapContext::Lane& lane);
 AovPlanes  aov_planes(const CapContext* c);
 int        trace_launch(const CapContext* c, const char* fmt, ...);
 void       launch_texture_footprints(hipStream_t stream, const uint32_t* src, uint4* dst, uint32_t width, uint32_t height);  // k_texture_footprints
+// ctx_render.hip: cap_render and everything only it calls; it crosses the boundary through the ABI header alone, and takes from
+// context.hip the helpers above, CounterLayout and the `pending` records it leaves for sync_and_collect
 // ctx_scene.hip
 bool pair_ids_dense(const float* pairs, uint32_t pair_count, uint32_t single_count, uint32_t tri_count);
 int  upload_fan_records(CapContext* c);

@@ -118,7 +118,7 @@ void launch_trace_any(const LaunchCfg& cfg, const BvhDev& bvh, const ShadowQueue
 // contribution there instead of adding it, and marks the path's word code_plane[plane index].w (code -> code + kCodeLit).
 // Only the two small-scene kernels of the reference model have the form (stack_entries == 0, !mostly_unoccluded).  Any other kernel
 // would ignore code_plane and ADD to a `direct` nobody has written, unmarked and without an error: launch_trace_any asserts the
-// condition, and the only caller that passes a plane derives it from code_in_color, whose own condition (context.hip) implies it.
+// condition, and the only caller that passes a plane derives it from code_in_color, whose own condition (ctx_render.hip plan_render) implies it.
 
 // The same for the reference model's shadow rays on the wide view with lane refill (trace8.hip): dense scenes, where a traversal step's
 // round trip ends in HBM.  Needs bvh.wide8_ok and the zeroed grab counters `work`.
@@ -358,7 +358,7 @@ struct ShadeArgs
 constexpr float kCodePadding = 0.f, kCodeSky = 1.f, kCodeKd = 2.f, kCodeBlack = 3.f;
 constexpr float kCodeLit = 4.f;  // code_in_color: added where the bounce-0 any-hit launch stored a contribution into `direct`
 // Pixels the bounce-0 kernel grows every fan pair's screen bounds by (small_scene.hip stage_camera_pairs).  The host's gate for
-// cull_camera_pairs (context.hip cap_render) allows a camera basis to move a projected point by an eighth of it.
+// cull_camera_pairs (ctx_render.hip) allows a camera basis to move a projected point by an eighth of it.
 constexpr float kCameraCullPad = 2.0f;
 // feedback: vertices of bounce >= 1 that the previous frame saw take its shaded colour and end the path (rt_indirect.hlsl:116-145;
 // reference shading model only)

@@ -1,19 +1,19 @@
-// context.hip — the context behind the C ABI of include/capsaicin_hip.h: creation, settings, the working sets of a render, the
-// per-batch wavefront loop (the MI355X counterpart of RaytracingSystem::Run, reference
-// src/systems/raytracing_system.cpp:230-318, ray passes only), readback, statistics.
+// context.hip — the context behind the C ABI of include/capsaicin_hip.h: creation and destruction, settings, cap_debug_*, accumulation,
+// readback, statistics, tiles, and the helpers the other units share (error reporting, sync_and_collect, the device views of the
+// camera, the scene and the tree).
 //
 // The product path is HIP only: every entry point that needs the GPU fails with CAP_ERR_HIP when no device or
 // kernel is available; there is no CPU fallback.
 //
-// The rest of the ABI by role: ctx_scene.hip (uploads, light table), ctx_bvh.hip (builds, refit, objects, instances), ctx_query.hip (ray
-// queries), ctx_post.hip (reconstruction chain), ctx_comm.hip (RCCL frame exchange); cap_context.h is what they share.
+// The rest of the ABI by role: ctx_render.hip (cap_render: plan, lanes, batches), ctx_scene.hip (uploads, light table), ctx_bvh.hip (builds,
+// refit, objects, instances), ctx_query.hip (ray queries), ctx_post.hip (reconstruction chain), ctx_comm.hip (RCCL frame exchange);
+// cap_context.h is what they share.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 
 #include "cap_context.h"
 #include "cap_near.h"
@@ -23,19 +23,6 @@
 namespace
 {
 thread_local std::string g_error;
-
-// camera rays take the per-lane wide kernel instead of the packet walk from this many triangles per pixel on (measured: cap_render;
-// 1.0 until the walk's node step was rewritten in round 6 -- at 1.0 the walk now wins by 6 % of the step, at 2.0 the two are level)
-constexpr double kPrimaryWideTrianglesPerPixel = 2.0;
-// shadow rays take the lane-refill kernel from this many bytes of wide nodes + intersection records on (measured: cap_render).
-// Round 6: never by default.  Until the per-chunk kernel's traversal was compiled per light octant (docs/experiments.md (86)) the refill
-// kernel won by 3 % from 512 MiB of tree on; now the per-chunk kernel wins by 6 - 8 % at 8.4 M and 16.8 M triangles (1.5 GB of tree),
-// as it always did below.  CAP_ANY_REFILL=1 still selects the refill kernel (tests/test_fallback_kernels_gpu.py keeps it honest).
-constexpr uint64_t kAnyRefillTreeBytes = ~0ull;
-
-// guard block of a context (ShadeArgs::shaded_counter): {-, malformed path ids seen by shade, by trace_any, last offender, appends
-// beyond a class's capacity, -, -, -}
-constexpr size_t kGuardWords = 8;
 }  // namespace
 
 namespace cap
@@ -90,10 +77,9 @@ int sync_and_collect(CapContext* c)
     c->post_marks.clear();
     for (auto& pc : c->pending)
     {
-        const uint32_t D = pc.second & 0xffffu;
-        const bool     queued = (pc.second >> 16) == 0u;  // false: the batch's shadow rays were traced where they were generated
-        const size_t per = (size_t)kQueueClasses * kCounterStride;
-        for (uint32_t b = 0; b <= D; ++b)
+        const bool   queued = pc.second.shadow_queued;
+        const size_t per = CounterLayout::per_queue();
+        for (uint32_t b = 0; b <= pc.second.num_bounces; ++b)
             for (uint32_t k = 0; k < kQueueClasses; ++k)
             {
                 c->stats.rays_extension += pc.first[b * per + k * kCounterStride];
@@ -145,6 +131,27 @@ CameraDev camera_dev(const CapCameraData& cd)
     d.sensor_x     = cd.sensor_size[0];
     d.sensor_y     = cd.sensor_size[1];
     return d;
+}
+
+SceneDev scene_dev(const CapContext* c)
+{
+    SceneDev s{};
+    s.shade_tris    = c->shade_tris.p;
+    s.tri_ids       = c->tri_ids.p;
+    s.mesh_texture  = c->mesh_texture.p;
+    s.textures      = c->textures.p;
+    s.texture_count = (uint32_t)c->texture_host.size();
+    s.bluenoise     = c->bluenoise.p;
+    s.kd_untextured = pow22_c(0.75f);
+    s.shade_tame    = c->shade_tame ? 1u : 0u;
+    s.bluenoise_ba  = c->bluenoise_ba.p;
+    s.materials     = reinterpret_cast<const MaterialDev*>(c->materials.p);
+    s.material_count = c->materials_ready ? c->mesh_count : 0u;
+    s.light_tris    = c->light_tris.p;
+    s.light_cdf     = c->light_cdf.p;
+    s.light_count   = c->light_count;
+    s.light_area    = c->light_area;
+    return s;
 }
 
 // the tree view of a launch whose traversal stacks spill into `lane`'s area
@@ -199,28 +206,6 @@ int trace_launch(const CapContext* c, const char* fmt, ...)
 
 namespace
 {
-struct StageTimer
-{
-    CapContext* c;
-    TimedSpan   sp;
-    bool        on;
-    StageTimer(CapContext* ctx, int stage, bool enabled = true, int also = ST_NONE) : c(ctx), on(enabled)
-    {
-        if (!on) return;
-        sp.stage = stage;
-        sp.also  = also;
-        sp.a     = get_event(c);
-        sp.b     = get_event(c);
-        (void)hipEventRecord(sp.a, c->stream);
-    }
-    ~StageTimer()
-    {
-        if (!on) return;
-        (void)hipEventRecord(sp.b, c->stream);
-        c->spans.push_back(sp);
-    }
-};
-
 void update_screen(CapContext* c, uint32_t w, uint32_t h, uint32_t shard_index, uint32_t shard_count)
 {
     ScreenDev& s  = c->screen;
@@ -239,185 +224,19 @@ void update_screen(CapContext* c, uint32_t w, uint32_t h, uint32_t shard_index, 
     c->aov_valid = false;
 }
 
-// lighting.h:20-33 + camera.h:41, evaluated once per frame on the host with the shared arithmetic contract
-FrameConst frame_const(uint32_t frame_count, bool lowres_indirect)
+// Launches something that counts into N zeroed 64-bit words on the context's stream and waits for them: h = the words.  (cap_debug_get's
+// self-tests and canary count; the buffer is released on every path: ADVICE r5)
+template <size_t N, class Launch>
+int count_on_device(CapContext* c, unsigned long long (&h)[N], Launch launch)
 {
-    FrameConst f{};
-    halton23(frame_count, f.jitter_x, f.jitter_y);
-    f.frame_count = frame_count;
-    // rt_indirect.hlsl:55-56: sp_offset = ((frame % 4) / 2, (frame % 4) % 2)
-    f.lowres_sel = lowres_indirect ? (4u | (((frame_count % 4u) / 2u) << 1) | ((frame_count % 4u) % 2u)) : 0u;
-    const float t = 2.0f * 3.14f * (float)(frame_count % 4096) / 4096.0f;
-    float       st, ct;
-    sincos_c(t, st, ct);
-    const v3 dir = normalize3(mk3(40.0f * st, 100.0f, 40.0f * ct));
-    f.light_dir[0] = dir.x, f.light_dir[1] = dir.y, f.light_dir[2] = dir.z;
-    f.light_intensity[0] = 1.0f * (2.0f * 14.0f + 0.0f);
-    f.light_intensity[1] = 1.0f * (2.0f * 12.0f + 0.0f);
-    f.light_intensity[2] = 1.0f * (2.0f * 10.0f + (2.0f + 2.0f * ct));
-    return f;
-}
-
-SceneDev scene_dev(const CapContext* c)
-{
-    SceneDev s{};
-    s.shade_tris    = c->shade_tris.p;
-    s.tri_ids       = c->tri_ids.p;
-    s.mesh_texture  = c->mesh_texture.p;
-    s.textures      = c->textures.p;
-    s.texture_count = (uint32_t)c->texture_host.size();
-    s.bluenoise     = c->bluenoise.p;
-    s.kd_untextured = pow22_c(0.75f);
-    s.shade_tame    = c->shade_tame ? 1u : 0u;
-    s.bluenoise_ba  = c->bluenoise_ba.p;
-    s.materials     = reinterpret_cast<const MaterialDev*>(c->materials.p);
-    s.material_count = c->materials_ready ? c->mesh_count : 0u;
-    s.light_tris    = c->light_tris.p;
-    s.light_cdf     = c->light_cdf.p;
-    s.light_count   = c->light_count;
-    s.light_area    = c->light_area;
-    return s;
-}
-
-// Element counts of one lane's working set for `slots` frame slots and `bounces` bounces: what ensure_lane allocates, and what
-// cap_render tests to learn whether a call grows a lane (growing frees the old buffers, so the streams are drained first)
-struct LaneSizes
-{
-    size_t planes, queues, rings, counters, terms, camera;
-};
-
-LaneSizes lane_sizes(const CapContext* c, uint32_t slots, uint32_t bounces, bool sample_table, uint32_t camera_groups)
-{
-    LaneSizes z;
-    z.planes = (size_t)slots * c->screen.pixels_padded;
-    z.queues = z.planes + (size_t)kQueueClasses * 64;  // queue regions round up to whole chunks per class
-    // the shadow queue's memory also holds the fused kernels' per-wave survivor rings (ShadeArgs::wave_ring): 128 entries for
-    // every wave of the largest persistent grid (8 workgroups per CU)
-    z.rings = std::max(z.queues, (size_t)std::max(c->cu_count, 1) * 8 * (kBlock / 64) * 128);
-    // queue counters (ext + shadow share words) + chunk-grab counters of the fused and of the any-hit launch, per bounce
-    z.counters = (3 * (size_t)(bounces + 1) + 1) * kQueueClasses * kCounterStride;  // + 1: the camera rays' identity queue
-    // the table of direction-sample terms (ShadeArgs::sample_terms): 4096 entries per frame slot and sampling bounce, 32 MB at 64 x 8
-    z.terms = sample_table ? (size_t)slots * bounces * 4096 : 0;
-    // the table of camera vertices (launch_camera_vertices): two planes of one entry per (jitter group, padded pixel), 0.5 GB at 8 groups of 1080p
-    z.camera = 2 * (size_t)camera_groups * c->screen.pixels_padded;
-    return z;
-}
-
-bool lane_grows(const CapContext::Lane& L, const LaneSizes& z) { return L.pl_color.n < z.planes || L.counters.n < z.counters || L.terms.n < z.terms || L.camera.n < z.camera; }
-
-int ensure_lane(CapContext* c, CapContext::Lane& L, uint32_t slots, uint32_t bounces, bool sample_table, uint32_t camera_groups)
-{
-    const LaneSizes z = lane_sizes(c, slots, bounces, sample_table, camera_groups);
-    for (DevBuf<float4>* b : {&L.hits, &L.q_org[0], &L.q_org[1], &L.q_dir[0], &L.q_dir[1], &L.q_thr[0], &L.q_thr[1], &L.s_dir})
-        HIP_TRY(b->ensure(z.queues));
-    for (DevBuf<float4>* b : {&L.s_org, &L.s_con}) HIP_TRY(b->ensure(z.rings));
-    for (DevBuf<float4>* b : {&L.pl_color, &L.pl_direct, &L.pl_albedo}) HIP_TRY(b->ensure(z.planes));
-    HIP_TRY(L.counters.ensure(z.counters));
-    if (z.terms) HIP_TRY(L.terms.ensure(z.terms));
-    if (z.camera) HIP_TRY(L.camera.ensure(z.camera));
-    // as much spill as lane 0, whose area cap_bvh_build allocates (for lane 0 itself: nothing to do)
-    if (c->lane[0].stack_spill.n) HIP_TRY(L.stack_spill.ensure(c->lane[0].stack_spill.n));
+    DevBuf<unsigned long long> d;
+    HIP_TRY(d.ensure(N));
+    HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(h), c->stream));
+    launch(d.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return CAP_OK;
-}
-
-// what a render needs beside its lanes: the AOV frame's geometry planes, the guard block, the accumulation buffer
-int ensure_frame_buffers(CapContext* c)
-{
-    HIP_TRY(c->aov_geo.ensure(c->screen.pixels_padded));
-    HIP_TRY(c->aov_nd.ensure(c->screen.pixels_padded));
-    if (!c->shaded_counter.p)
-    {
-        HIP_TRY(c->shaded_counter.ensure(kGuardWords));
-        HIP_TRY(hipMemsetAsync(c->shaded_counter.p, 0, kGuardWords * sizeof(uint64_t), c->stream));
-    }
-    if (!c->accum.p || c->accum.n < c->screen.pixels_padded)
-    {
-        HIP_TRY(c->accum.ensure(c->screen.pixels_padded));
-        HIP_TRY(hipMemsetAsync(c->accum.p, 0, sizeof(float4) * c->screen.pixels_padded, c->stream));
-        c->frames_accumulated = 0;
-    }
-    return CAP_OK;
-}
-
-// the second lane's stream and the events that order the two lanes
-int ensure_lane_streams(CapContext* c)
-{
-    if (!c->stream2)
-    {
-        // (A/B switch: the second lane's stream priority -- streams of different priority never share a hardware queue)
-        if (c->sw.v[SW_LANE1_PRIORITY] >= 0)
-            HIP_TRY(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, (int)c->sw.v[SW_LANE1_PRIORITY]));
-        else
-            HIP_TRY(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-    }
-    c->lane[1].stream = c->stream2;
-    for (hipEvent_t* e : {&c->lane_ev[0], &c->lane_ev[1], &c->fork_ev, &c->join_ev})
-        if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    return CAP_OK;
-}
-
-// How cap_render cuts a call into batches.
-struct BatchPolicy
-{
-    uint32_t slots;               // frame slots of a batch (the last one may fill fewer)
-    bool     two_lanes;           // consecutive batches alternate between the two lanes
-    bool     lane1_failed_before; // two_lanes, but a second working set of this size could not be allocated earlier
-};
-
-// Reads the context and changes nothing (it may ask the device how much memory is free).  tree_path: the render goes through the
-// tree kernels, not the small-scene fused ones.
-BatchPolicy batch_policy(const CapContext* c, uint32_t n_frames, uint32_t num_bounces, uint32_t flags, bool tree_path)
-{
-    const uint32_t Ppad = c->screen.pixels_padded;
-    // paths in flight per batch; measured on the headline workload (tools/batch_sweep.sh, end of round 2): 8 Mi 31.0 ms, 16 Mi 25.5,
-    // 32 Mi 22.1, 64 Mi 21.2, 128 Mi 21.1 per step -- every launch has a fixed cost (grid start, tables, tail) that fewer, larger
-    // batches amortise; 64 Mi paths are ~14 GB of queues and planes
-    uint64_t       budget = c->max_batch_paths ? c->max_batch_paths : (uint64_t)64 << 20;
-    if (!c->max_batch_paths && (uint64_t)n_frames * Ppad > budget)
-    {
-        // Twice that when the card has the room (round 6, docs/experiments.md (88)): the tree path has 27 launches per batch, most of
-        // them short, and gains 1.7 % (the 262 k hall at 128 spp: 92.1 -> 90.5 ms; round 4 measured 101.2 -> 99.4 and kept 64 Mi for
-        // its 14 GB per lane), the small-scene path 1.0 % (headline 20.22 -> 20.01 ms).  Taken when the working set is already that
-        // large or the device reports room for it with a margin -- 128 Mi paths are ~28 GB per lane of the card's 288, and the tree
-        // path runs two lanes; cap_set_batch_paths overrides either way.
-        const uint64_t big       = (uint64_t)128 << 20;
-        const uint64_t big_slots = std::max<uint64_t>(1, std::min<uint64_t>(big / std::max(1u, Ppad), kMaxFrameSlots));
-        bool           room      = c->lane[0].pl_color.n >= big_slots * Ppad && (!tree_path || c->lane[1].pl_color.n >= big_slots * Ppad);
-        if (!room)
-        {
-            size_t free_b = 0, total_b = 0;
-            room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 3u * big_slots * Ppad * 256u;  // ~208 B per path and lane
-        }
-        if (room) budget = big;
-    }
-    uint32_t       slots  = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(budget / std::max(1u, Ppad), kMaxFrameSlots));
-    slots                 = std::min(slots, n_frames);
-    // Two lanes (CapContext::Lane): consecutive batches alternate between two working sets on two streams, so that the tail of
-    // one batch's launch -- the last chunks, a workgroup at a time, with most of the chip idle -- is filled by the other batch's
-    // next launch instead of waiting for the stream's next kernel (measured with two contexts side by side, tools/dual_test.py:
-    // 21.0 -> 20.55 ms per step on the headline, 3.30 -> 3.05 ms for shard 0 of 8, 28.3 -> 27.1 ms on the 262 k scene).  A call
-    // that fits one batch is cut in two halves when the halves are still large.  Per-stage timers need one stream.
-    const bool no_two_lanes = c->sw.on(SW_NO_TWO_LANES);  // A/B switch
-    // Only on the tree path: its bounces are three launches each, and from the third bounce on they are short (the 262 k scene: 27
-    // launches per batch, the last 15 under 0.2 ms each) -- 28.3 -> 26.4 ms per 32 spp.  The small-scene path's nine long fused
-    // launches gain nothing measurable (20.45 -> 20.25 ms with the context's own stream, 20.56 -> 20.9 beside a torch stream).
-    bool two_lanes = !no_two_lanes && tree_path && c->bvh_info.stack_entries != 0 && !(flags & CAP_RENDER_GBUFFER_FEEDBACK) &&
-                     !(flags & CAP_RENDER_LOWRES_INDIRECT) && n_frames >= 2;
-    if (two_lanes && slots >= n_frames)
-    {
-        const uint64_t split_min = (uint64_t)c->sw.get(SW_LANE_SPLIT_MIN, (int64_t)4 << 20);  // A/B switch (shard 0 of 8 of the 262 k scene: 4.55 -> 4.35 ms with halves of 4 Mi paths)
-        if ((uint64_t)n_frames * Ppad >= split_min)
-            slots = (n_frames + 1) / 2;
-        else
-            two_lanes = false;
-    }
-    // (per-stage timers and launch tracing need one stream: the batches keep the size the two lanes gave them -- so that a stage-timed
-    // render launches what the plain one does -- and run one after the other on lane 0)
-    if ((flags & CAP_RENDER_STAGE_TIMERS) || c->sw.on(SW_TRACE_LAUNCHES)) two_lanes = false;
-    // (cap_render does not try a second working set of a size that has failed, or a larger one, again at once: see there)
-    const bool failed_before =
-        two_lanes && c->lane1_failed_paths && (uint64_t)slots * Ppad >= c->lane1_failed_paths && num_bounces >= c->lane1_failed_bounces;
-    return BatchPolicy{slots, two_lanes, failed_before};
 }
 }  // namespace
 
@@ -676,22 +495,18 @@ static int canary_count(CapContext* c, bool behind, uint64_t* value)
     CapContext::Lane& L = c->lane[0];
     if (!L.q_org[0].p || !c->last_class_capacity) return fail(CAP_ERR_STATE, "cap_debug_get: no render yet");
     HIP_TRY(hipSetDevice(c->device));
-    DevBuf<unsigned long long> dbuf;  // (released on every path: ADVICE r5)
-    HIP_TRY(dbuf.ensure(1));
-    unsigned long long* d = dbuf.p;
-    HIP_TRY(hipMemsetAsync(d, 0, sizeof(*d), c->stream));
-    const size_t used = std::min((size_t)kQueueClasses * c->last_class_capacity, L.q_org[0].n);
-    for (int k = 0; k < 2; ++k)
-        for (DevBuf<float4>* b : {&L.q_org[k], &L.q_dir[k], &L.q_thr[k]})
-        {
-            const size_t lo = behind ? used : 0, hi = behind ? b->n : used;
-            if (hi > lo) hipLaunchKernelGGL(k_canary_count, dim3(512), dim3(256), 0, c->stream, reinterpret_cast<const uint4*>(b->p), lo, hi, d);
-        }
-    HIP_TRY(hipGetLastError());
-    unsigned long long h = 0;
-    HIP_TRY(hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *value = h;
+    const size_t       used = std::min((size_t)kQueueClasses * c->last_class_capacity, L.q_org[0].n);
+    unsigned long long h[1];
+    if (int e = count_on_device(c, h, [&](unsigned long long* d) {
+            for (int k = 0; k < 2; ++k)
+                for (DevBuf<float4>* b : {&L.q_org[k], &L.q_dir[k], &L.q_thr[k]})
+                {
+                    const size_t lo = behind ? used : 0, hi = behind ? b->n : used;
+                    if (hi > lo) hipLaunchKernelGGL(k_canary_count, dim3(512), dim3(256), 0, c->stream, reinterpret_cast<const uint4*>(b->p), lo, hi, d);
+                }
+        }))
+        return e;
+    *value = h[0];
     return CAP_OK;
 }
 
@@ -742,14 +557,8 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
     case CAP_DEBUG_SELFTEST_DIV:
     {
         HIP_TRY(hipSetDevice(c->device));
-        DevBuf<unsigned long long> d;  // (released on every path: ADVICE r5)
-        unsigned long long         h[3] = {0, 0, 0};
-        HIP_TRY(d.ensure(3));
-        HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(h), c->stream));
-        launch_div_selftest(c->stream, d.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        unsigned long long h[3];
+        if (int e = count_on_device(c, h, [&](unsigned long long* d) { launch_div_selftest(c->stream, d); })) return e;
         // positive control: every normal float once + 2^30 operand pairs must have been compared
         const unsigned long long expected = (0x7f7fffffull - 0x00800000ull + 1ull) + (1ull << 30);
         if (h[2] != expected) return fail(CAP_ERR_HIP, "cap_debug_get: the division self-test compared %llu of %llu cases", h[2], expected);
@@ -760,14 +569,9 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
     case CAP_DEBUG_SELFTEST_SHADE_DIV2:
     {
         HIP_TRY(hipSetDevice(c->device));
-        DevBuf<unsigned long long> d;
-        unsigned long long         h[2] = {0, 0};
-        HIP_TRY(d.ensure(2));
-        HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(h), c->stream));
-        launch_shade_forms_selftest(c->stream, d.p, key == CAP_DEBUG_SELFTEST_SHADE_DIV2 ? 1u : 0u);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        unsigned long long h[2];
+        if (int e = count_on_device(c, h, [&](unsigned long long* d) { launch_shade_forms_selftest(c->stream, d, key == CAP_DEBUG_SELFTEST_SHADE_DIV2 ? 1u : 0u); }))
+            return e;
         // positive control: two square roots per normal float from 2^-96 on + 3 special operands, the normalize range [2^-3, 4],
         // x / pi over [0, 2] and f over at least half of it; at least 2^30 pairs inside ortho_vector's guard
         const unsigned long long floats_sqrt = 0x7f7fffffull - ((127ull - 96ull) << 23) + 1ull;
@@ -792,14 +596,11 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
         if (!c->last_sample_table || !lt.frames) return fail(CAP_ERR_STATE, "cap_debug_get: the last cap_render built no sample table");
         HIP_TRY(hipSetDevice(c->device));
         if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
-        DevBuf<unsigned long long> d;
-        unsigned long long         h[2] = {0, 0};
-        HIP_TRY(d.ensure(2));
-        HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(h), c->stream));
-        launch_sample_terms_selftest(c->stream, c->bluenoise.p, lt.frames, lt.n_slots, lt.num_bounces, c->lane[lt.lane].terms.p, d.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        unsigned long long h[2];
+        if (int e = count_on_device(c, h, [&](unsigned long long* d) {
+                launch_sample_terms_selftest(c->stream, c->bluenoise.p, lt.frames, lt.n_slots, lt.num_bounces, c->lane[lt.lane].terms.p, d);
+            }))
+            return e;
         const unsigned long long expected = (unsigned long long)lt.n_slots * lt.num_bounces * 4096ull;
         if (h[1] != expected) return fail(CAP_ERR_HIP, "cap_debug_get: the sample table self-test compared %llu of %llu entries", h[1], expected);
         *value = (h[0] << 32) | (expected >> 12);  // mismatches << 32 | (bounce, slot) rows compared
@@ -812,20 +613,17 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
         if (!c->last_camera_table || !lc.frames) return fail(CAP_ERR_STATE, "cap_debug_get: the last cap_render built no camera table");
         HIP_TRY(hipSetDevice(c->device));
         if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
-        DevBuf<unsigned long long> d;
-        unsigned long long         h[2] = {0, 0};
-        HIP_TRY(d.ensure(2));
-        HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(h), c->stream));
         // the launch arguments the table was built with (camera, screen and scene as they are now: ask right after the render)
         ShadeArgs sa{};
         sa.scene = scene_dev(c), sa.cam = camera_dev(c->camera), sa.screen = c->screen, sa.frames = lc.frames, sa.n_slots = lc.n_slots;
         sa.cull_camera_pairs = c->last_cull_camera_pairs;
         LaunchCfg     cfg{c->stream, (uint32_t)c->cu_count * 6u, 0u, (uint32_t)c->cu_count};
         float4* const tab = c->lane[lc.lane].camera.p;
-        launch_camera_vertices(cfg, bvh_dev(c, c->lane[lc.lane]), sa, lc.n_slots, tab, tab + (size_t)lc.n_groups * c->screen.pixels_padded, d.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        unsigned long long h[2];
+        if (int e = count_on_device(c, h, [&](unsigned long long* d) {
+                launch_camera_vertices(cfg, bvh_dev(c, c->lane[lc.lane]), sa, lc.n_slots, tab, tab + (size_t)lc.n_groups * c->screen.pixels_padded, d);
+            }))
+            return e;
         const unsigned long long expected = (unsigned long long)lc.n_slots * c->screen.pixels_padded;
         if (h[1] != expected) return fail(CAP_ERR_HIP, "cap_debug_get: the camera table self-test compared %llu of %llu entries", h[1], expected);
         *value = (h[0] << 32) | ((uint64_t)lc.n_groups << 16) | lc.n_slots;  // mismatches << 32 | groups << 16 | slots compared
@@ -899,476 +697,6 @@ int cap_sync(CapContext* c)
     if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_sync: ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
     return sync_and_collect(c);
-}
-
-int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t num_bounces, uint32_t flags)
-{
-    if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_render: ctx is NULL");
-    if (!c->bvh_ready) return fail(CAP_ERR_STATE, "cap_render: call cap_bvh_build first");
-    if (c->bvh_stale) return fail(CAP_ERR_STATE, "cap_render: vertices changed; call cap_bvh_refit or cap_bvh_build");
-    if (!c->camera_ready || !c->bluenoise_ready || !c->screen.width) return fail(CAP_ERR_STATE, "cap_render: camera, blue noise and resolution must be set");
-    const bool ext = (flags & CAP_RENDER_EXT_MATERIALS) != 0;
-    if (ext && !c->materials_ready) return fail(CAP_ERR_STATE, "cap_render: CAP_RENDER_EXT_MATERIALS needs cap_materials_upload (one material per mesh)");
-    static_assert(sizeof(MaterialDev) == sizeof(CapMaterial), "material layouts must match");
-    if (num_bounces > 255) return fail(CAP_ERR_INVALID_ARG, "cap_render: num_bounces %u exceeds 255", num_bounces);
-    if (!n_frames) return CAP_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    c->last_mark_form   = 0;
-    c->last_sample_table = 0;
-    c->last_terms        = CapContext::LastTerms{};
-    const bool feedback = (flags & CAP_RENDER_GBUFFER_FEEDBACK) != 0;
-    if (feedback)
-    {
-        // the branch reads the previous frame's reconstruction output: one frame per call, the whole image on this context
-        if (ext) return fail(CAP_ERR_UNSUPPORTED, "cap_render: CAP_RENDER_GBUFFER_FEEDBACK is defined for the reference shading model only");
-        if (n_frames != 1) return fail(CAP_ERR_INVALID_ARG, "cap_render: CAP_RENDER_GBUFFER_FEEDBACK renders one frame per call (n_frames is %u)", n_frames);
-        // sharded contexts: the previous frame's output reaches the non-root ranks through cap_feedback_import
-        if (!c->prev_camera_ready) return fail(CAP_ERR_STATE, "cap_render: CAP_RENDER_GBUFFER_FEEDBACK needs cap_prev_camera_set");
-        if (c->post_w != c->screen.width || c->post_h != c->screen.height)
-            if (int e = cap_post_reset(c)) return e;  // first frame: cleared histories, every vertex is a disocclusion
-    }
-
-    const bool lowres = (flags & CAP_RENDER_LOWRES_INDIRECT) != 0;
-    if (lowres)
-    {
-        // the half-resolution indirect image only exists per frame (2x2 interleave over four frames): nothing to accumulate
-        if (ext) return fail(CAP_ERR_UNSUPPORTED, "cap_render: CAP_RENDER_LOWRES_INDIRECT is defined for the reference shading model only");
-        if (n_frames != 1) return fail(CAP_ERR_INVALID_ARG, "cap_render: CAP_RENDER_LOWRES_INDIRECT renders one frame per call (n_frames is %u)", n_frames);
-        if ((c->screen.width | c->screen.height) & 1u) return fail(CAP_ERR_INVALID_ARG, "cap_render: CAP_RENDER_LOWRES_INDIRECT needs even width and height (%ux%u)", c->screen.width, c->screen.height);
-    }
-
-    // Which traversal path the render takes, decided here once: the small-scene kernels (closest hit and shading fused in one
-    // launch per bounce, every triangle tested) or the tree path.  stack_entries == 0 selects the former in the launchers.
-    if (c->traversal_mode == CAP_TRAVERSAL_EXHAUSTIVE && c->tri_count > 4096)
-        return fail(CAP_ERR_UNSUPPORTED, "cap_render: exhaustive traversal refused for %u triangles", c->tri_count);
-    const bool     tree_path     = c->traversal_mode == CAP_TRAVERSAL_EXHAUSTIVE ? false
-                                                                                 : !(c->traversal_mode == CAP_TRAVERSAL_AUTO && c->tri_count <= kExhaustiveMax);
-    const uint32_t stack_entries = tree_path ? c->bvh_info.stack_entries : 0u;
-    const bool     fused         = stack_entries == 0;  // small-scene path: closest hit and shading in one kernel per bounce
-
-    const uint32_t    Ppad      = c->screen.pixels_padded;
-    const BatchPolicy policy    = batch_policy(c, n_frames, num_bounces, flags, tree_path);
-    const uint32_t    slots     = policy.slots;
-    bool              two_lanes = policy.two_lanes;
-    // No host synchronisation with the previous call: everything it still uses is either ordered behind it on the stream (queues,
-    // counters, planes) or lives in another slot of the constants ring.  Only a long backlog of unread events / counters is
-    // drained (what cap_sync / cap_stats_get do anyway), and a growing allocation (which frees the old buffers).
-    if (c->spans.size() > 2048 || c->pending.size() > 64 || c->post_marks.size() > 256)
-        if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
-    // Direction-sample terms from a per-batch table (ShadeArgs::sample_terms): decided once per call, for every launch of every batch.
-    // Rebuilt by every batch and never kept across calls: frame_begin advances from call to call in real use.
-    // A/B switch CAP_SAMPLE_TABLE: 0 never, 1 whenever the kernels have the form (which is also the product's choice).
-    const bool sample_table = fused && !ext && !feedback && num_bounces >= 1 && c->sw.get(SW_SAMPLE_TABLE, 1) != 0 &&
-                              trace_shade_has_table_form(bvh_dev(c, c->lane[0]), scene_dev(c));
-    c->last_sample_table = sample_table ? 1u : 0u;
-    // Bounce 0 inside bounce 1's launch, from a table of camera vertices (launch_camera_vertices, launch_trace_shade's camera_head): decided
-    // once per call.  The lean table kernels of an untextured scene in an accumulate-only render, whose colour plane carries the first
-    // vertex's code and whose shadow rays go through the wave rings -- the conditions of albedo_in_w, code_in_color, inline_probe and
-    // wave_ring below, which a batch repeats for itself (the rings' size is the one it alone knows).  A/B switch CAP_NO_CAMERA_TABLE.
-    const bool camera_table = sample_table && !lowres && !(flags & CAP_RENDER_AOV) && !c->sw.on(SW_NO_CAMERA_TABLE) && !c->sw.on(SW_NO_ALBEDO_IN_W) &&
-                              !c->sw.on(SW_NO_PLANE_CODE) && !c->sw.on(SW_NO_INLINE_PROBE) && !c->sw.on(SW_NO_WAVE_RING) && c->debug_capacity_div <= 1 &&
-                              c->texture_host.empty() && trace_shade_has_code_form(bvh_dev(c, c->lane[0]), scene_dev(c));
-    c->last_camera_table = 0;
-    c->last_camera       = CapContext::LastCamera{};
-    // Jitter groups: the slots of a batch by the bits of (jitter_x, jitter_y).  slot_group[f]: the group of frame f within its batch,
-    // numbered in order of first appearance; group_first[batch start + g]: the first slot of group g.  A group need not be contiguous.
-    std::vector<uint32_t> slot_group, group_first, batch_groups;
-    uint32_t              camera_groups = 0;
-    if (camera_table)
-    {
-        slot_group.resize(n_frames), group_first.assign(n_frames, 0u);
-        for (uint32_t done = 0; done < n_frames; done += slots)
-        {
-            const uint32_t ns = std::min(slots, n_frames - done);
-            uint32_t       ng = 0;
-            for (uint32_t s = 0; s < ns; ++s)
-            {
-                float sx, sy, gx, gy;  // frame_const()'s jitter
-                halton23(frame_begin + done + s, sx, sy);
-                uint32_t g = 0;
-                for (; g < ng; ++g)
-                {
-                    halton23(frame_begin + done + group_first[done + g], gx, gy);
-                    if (memcmp(&gx, &sx, sizeof(float)) == 0 && memcmp(&gy, &sy, sizeof(float)) == 0) break;
-                }
-                if (g == ng) group_first[done + ng++] = s;
-                slot_group[done + s] = g;
-            }
-            batch_groups.push_back(ng);
-            camera_groups = std::max(camera_groups, ng);
-        }
-    }
-    const LaneSizes need = lane_sizes(c, slots, num_bounces, sample_table, camera_groups);
-    if (lane_grows(c->lane[0], need) || !c->accum.p || c->accum.n < Ppad) HIP_TRY(hipStreamSynchronize(c->stream));
-    if (ensure_lane(c, c->lane[0], slots, num_bounces, sample_table, camera_groups) != CAP_OK || ensure_frame_buffers(c) != CAP_OK) return CAP_ERR_HIP;
-    if (policy.lane1_failed_before)
-    {
-        // this size has already failed: one lane, without asking again -- except every 32nd time, and at once when the device reports
-        // room for it (memory can come back without any call on this context: another context closed, a co-tenant left)
-        size_t free_b = 0, total_b = 0;
-        const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > (size_t)slots * Ppad * 256u;  // a working set is ~208 B per path
-        if (!room && (++c->lane1_retry_tick % 32u) != 0u)
-        {
-            two_lanes = false;
-            ++c->stats.lane1_dropped;
-        }
-    }
-    if (two_lanes)
-    {
-        if (lane_grows(c->lane[1], need))
-        {
-            HIP_TRY(hipStreamSynchronize(c->stream));  // growing frees the old buffers
-            if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
-        }
-        if (c->debug_fail_lane || ensure_lane(c, c->lane[1], slots, num_bounces, sample_table, camera_groups) != CAP_OK || ensure_lane_streams(c) != CAP_OK)
-        {
-            // the second working set doubles the batch's memory (~28 GB at the default budget): without it the batches of this call
-            // simply run one after the other on lane 0 -- counted in CapStats::lane1_dropped, and not tried again at this
-            // size until something is freed
-            (void)hipGetLastError();
-            c->lane[1] = CapContext::Lane{};
-            c->lane1_failed_paths = (uint64_t)slots * Ppad, c->lane1_failed_bounces = num_bounces;  // (ensure_lane's size depends on both)
-            ++c->stats.lane1_dropped;
-            two_lanes = false;
-        }
-    }
-    c->lanes_last_render = two_lanes ? 2u : 1u;
-    const uint32_t ring = c->frames_next;
-    c->frames_next      = (c->frames_next + 1) % CapContext::kFrameRing;
-    if (!c->frames_event[ring]) HIP_TRY(hipEventCreateWithFlags(&c->frames_event[ring], hipEventDisableTiming));
-    HIP_TRY(hipEventSynchronize(c->frames_event[ring]));  // the call that used this slot kFrameRing calls ago: long done
-    if (c->frames_ring[ring].n < n_frames)
-    {
-        // (a larger buffer: the old one of this slot is idle by the event above)
-        HIP_TRY(c->frames_ring[ring].ensure(n_frames));
-    }
-    if (c->frames_pinned_n[ring] < n_frames)
-    {
-        if (c->frames_pinned[ring]) HIP_TRY(hipHostFree(c->frames_pinned[ring]));
-        c->frames_pinned[ring] = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&c->frames_pinned[ring], sizeof(FrameConst) * n_frames, hipHostMallocDefault));
-        c->frames_pinned_n[ring] = n_frames;
-    }
-    for (uint32_t f = 0; f < n_frames; ++f)
-    {
-        FrameConst& fc = c->frames_pinned[ring][f] = frame_const(frame_begin + f, lowres);
-        // the two words nothing else reads in memory: the slot's jitter group, and the first slot of the group of this number
-        if (camera_table) memcpy(&fc.pad1, &slot_group[f], 4), memcpy(&fc.pad2, &group_first[f], 4);
-    }
-    HIP_TRY(hipMemcpyAsync(c->frames_ring[ring].p, c->frames_pinned[ring], sizeof(FrameConst) * n_frames, hipMemcpyHostToDevice, c->stream));
-    const bool st = (flags & CAP_RENDER_STAGE_TIMERS) != 0;
-    if (c->textures_dirty)
-    {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->textures.ensure(std::max<size_t>(1, c->texture_host.size())));
-        if (!c->texture_host.empty())
-            HIP_TRY(hipMemcpy(c->textures.p, c->texture_host.data(), sizeof(TextureDev) * c->texture_host.size(), hipMemcpyHostToDevice));
-        c->textures_dirty = false;
-    }
-
-    // Persistent grids must be fully resident: a workgroup that cannot be co-scheduled runs as a second round after the first
-    // waves retire and doubles the kernel's tail.  blocks_per_cu is therefore the residency the kernels are built for
-    // (launch bounds in kernels.hip and small_scene.hip), not the 8 a register-light kernel could reach.
-    uint32_t blocks_per_cu = fused ? 6u : (stack_entries <= 32 ? 5u : 2u);  // measured: 4..8 within 4 %, 6 best
-    if (c->sw.v[SW_BLOCKS_PER_CU] >= 0) blocks_per_cu = (uint32_t)std::max<int64_t>(1, c->sw.v[SW_BLOCKS_PER_CU]);
-    const SceneDev  scene = scene_dev(c);
-    const CameraDev cam   = camera_dev(c->camera);
-    const uint32_t  D     = num_bounces;
-    std::unique_ptr<StageTimer> total(new StageTimer(c, ST_COUNT));  // its destructor closes the span on every exit path
-
-    const uint32_t n_batches = (n_frames + slots - 1) / slots;
-    // Every way out of this function after the fork -- the early returns of HIP_TRY and of the launch tracing included -- leaves the
-    // context's stream, the one callers order cap_sync / cap_readback / buffer growth behind, waiting for lane 1 (an error
-    // between fork and join used to leave lane-1 work running that nothing waited for).
-    struct LaneJoin
-    {
-        CapContext* c;
-        bool        armed = false;
-        ~LaneJoin()
-        {
-            if (!armed) return;
-            if (hipEventRecord(c->join_ev, c->stream2) != hipSuccess || hipStreamWaitEvent(c->stream, c->join_ev, 0) != hipSuccess)
-                (void)hipStreamSynchronize(c->stream2);
-        }
-    } lane_join{c};
-    if (two_lanes)
-    {
-        // lane 1 starts behind everything queued on the context's stream so far (the frame constants' upload, earlier calls)
-        HIP_TRY(hipEventRecord(c->fork_ev, c->stream));
-        HIP_TRY(hipStreamWaitEvent(c->stream2, c->fork_ev, 0));
-        lane_join.armed = true;
-    }
-    hipEvent_t last_resolve = nullptr;  // the accumulation buffer takes the batches in frame order, whichever lane ran them
-    uint32_t   batch        = 0;
-
-    for (uint32_t done = 0; done < n_frames; done += slots, ++batch)
-    {
-        const uint32_t    lane = two_lanes ? ((n_batches - 1u - batch) & 1u) : 0u;  // the last batch on lane 0
-        CapContext::Lane& L    = c->lane[lane];
-        const BvhDev      bvh  = bvh_dev(c, L);
-        LaunchCfg         cfg{L.stream, (uint32_t)c->cu_count * blocks_per_cu, stack_entries, (uint32_t)c->cu_count};
-        cfg.sw = &c->sw;
-        const uint32_t ns = std::min(slots, n_frames - done);
-        const FrameConst* frames = c->frames_ring[ring].p + done;
-        const size_t   per_queue     = (size_t)kQueueClasses * kCounterStride;  // counter words of one queue
-        // per bounce and class one 64-bit word: low half = extension entries, high half = shadow entries (one atomic serves both)
-        const size_t   counter_words = (size_t)(D + 1) * per_queue;
-        HIP_TRY(hipMemsetAsync(L.counters.p, 0, sizeof(uint32_t) * 3 * counter_words, L.stream));
-        uint32_t*      ext_count = L.counters.p;
-        uint32_t*      sh_count  = L.counters.p + 1;
-        uint32_t*      work_shade = L.counters.p + counter_words;      // + b * per_queue: grab counters of bounce b's fused launch
-        uint32_t*      work_any   = L.counters.p + 2 * counter_words;  // ... and of its any-hit launch
-        const uint32_t total_chunks   = ns * (Ppad >> 6);
-        uint32_t       class_capacity = ((total_chunks + kQueueClasses - 1) / kQueueClasses) * 64u;
-        // (tests of the append guard: sub-queues deliberately too small -- the appends beyond them must be dropped and counted)
-        if (c->debug_capacity_div > 1) class_capacity = std::max(64u, (class_capacity / c->debug_capacity_div) & ~63u);
-        c->last_class_capacity = class_capacity;
-        const bool     last_batch = done + ns >= n_frames;
-        const uint32_t aov_slot   = ((flags & CAP_RENDER_AOV) && last_batch) ? ns - 1 : ~0u;
-        const uint32_t max_count  = ns * Ppad;
-
-        ShadeArgs sa{};
-        sa.scene = scene, sa.cam = cam, sa.screen = c->screen, sa.frames = frames;
-        if (!fused) sa.hits = L.hits.p;  // (fused: the same word is sample_terms, set per bounce)
-        sa.planes = Planes{L.pl_color.p, L.pl_direct.p, L.pl_albedo.p, c->aov_geo.p, c->aov_nd.p};
-        sa.n_slots = ns, sa.num_bounces = D, sa.max_count = max_count, sa.aov_slot = aov_slot, sa.shaded_counter = c->shaded_counter.p;
-        {
-            // Screen-space culling of bounce 0 inverts primary_dir (camera.h:39-63) with the transpose of (right, up, forward), which is
-            // the inverse only for an orthonormal basis.  With G = the basis' Gram matrix and skew = max |G - I|, a ray through the
-            // sensor point (cx, cy, f) projects to (G c).x / (G c).z * f instead of cx: off by at most
-            //   skew * (f + 2 |cx| + |cy| + |cx| (|cx| + |cy|) / f)  <=  skew * (f + sx + sy / 2 + (sx + sy) sx / (4 f))
-            // on the sensor (|cx| <= sx / 2, |cy| <= sy / 2), i.e. skew * width * (f / sx + 1 + sy / (2 sx) + (sx + sy) / (4 f)) pixels,
-            // and likewise in y.  The tiles' test (small_scene.hip stage_camera_pairs) grows every bound by kCameraCullPad = 2 pixels for this, the
-            // rounding of the projection and nothing else (the jitter stays inside its pixel): the cull is on only while the worst-case
-            // shift on the sensor is at most an eighth of that pad.  The rest is for vertices off the sensor, whose error grows with
-            // the tangent of their angle to the axis (|cy| / f = 5, 79 degrees: five times the shift; tests/test_pair_culls_gpu.py C7
-            // renders both at 0.24 pixels).  A telephoto lens or a wide image tightens the tolerance (f / sx = 500 at 72 pixels: 7e-6); a basis made by
-            // normalising cross products (skew ~1e-7) passes up to f / sx * width ~ 2e6.  Beyond the tolerance every tile tests every pair.
-            const bool no_cull = c->sw.on(SW_NO_CAMERA_CULL);  // A/B switch
-            auto dotf = [](const float* x, const float* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
-            const CapCameraData& cd = c->camera;
-            const float skew = std::max({std::fabs(dotf(cd.right, cd.up)), std::fabs(dotf(cd.right, cd.forward)), std::fabs(dotf(cd.up, cd.forward)),
-                                         std::fabs(dotf(cd.right, cd.right) - 1.f), std::fabs(dotf(cd.up, cd.up) - 1.f),
-                                         std::fabs(dotf(cd.forward, cd.forward) - 1.f)});
-            const double f = cd.focal_length, sx = cd.sensor_size[0], sy = cd.sensor_size[1];
-            const double shift_x = (double)skew * c->screen.width * (f / sx + 1.0 + sy / (2.0 * sx) + (sx + sy) / (4.0 * f));
-            const double shift_y = (double)skew * c->screen.height * (f / sy + 1.0 + sx / (2.0 * sy) + (sx + sy) / (4.0 * f));
-            const bool   ortho   = skew < 1e-4f && shift_x <= 0.125 * (double)kCameraCullPad && shift_y <= 0.125 * (double)kCameraCullPad;  // (NaN: off)
-            sa.cull_camera_pairs = (ortho && !no_cull) ? 1u : 0u;
-            c->last_cull_camera_pairs = sa.cull_camera_pairs;
-        }
-        // Nobody reads this batch's planes but the resolve (plane read-backs and the reconstruction chain need CAP_RENDER_AOV)
-        const bool no_albedo_w = c->sw.on(SW_NO_ALBEDO_IN_W);  // A/B switch
-        sa.albedo_in_w = (!no_albedo_w && !feedback && !lowres && !(flags & CAP_RENDER_AOV) && (ext || scene.texture_count == 0)) ? 1u : 0u;  // (the EXT model's first-vertex albedo is 1: it folds kd into the throughput)
-        // ... and on the small-scene path the constants bounce 0 would write into `direct` stay unwritten (ShadeArgs::code_in_color).  The
-        // EXT model is left out: its bounce 0 adds emission to `direct` and its shadow rays are traced inline, so it keeps two planes.
-        const bool no_plane_code = c->sw.on(SW_NO_PLANE_CODE);  // A/B switch
-        sa.code_in_color = (sa.albedo_in_w && fused && !ext && !no_plane_code && trace_shade_has_code_form(bvh, scene)) ? 1u : 0u;
-        if (feedback)  // g_color_history = combined_history[(frame_count + 1) % 2], raytracing_system.cpp:1754-1759
-            sa.fb = FeedbackDev{camera_dev(c->prev_camera), c->post_prev_nd.p, c->post_chist[(frame_begin + 1) % 2].p};
-        const bool no_inline_nee = c->sw.on(SW_NO_INLINE_NEE);  // A/B switch
-        sa.inline_nee = (ext && fused && !no_inline_nee) ? 1u : 0u;
-        const bool no_inline_probe = c->sw.on(SW_NO_INLINE_PROBE);  // A/B switch
-        sa.inline_probe = (!ext && !feedback && fused && !no_inline_probe && c->tri_count <= kExhaustiveMax && bvh.fan_pair_count >= 1 &&
-                           bvh.fan_pair_count <= kExhaustiveMax / 2)
-                              ? 1u
-                              : 0u;
-        const bool no_wave_ring = c->sw.on(SW_NO_WAVE_RING);  // A/B switch
-        sa.wave_ring = (sa.inline_probe && !no_wave_ring && (size_t)cfg.grid_blocks * (kBlock / 64) * 128 <= std::min(L.s_org.n, L.s_con.n)) ? 1u : 0u;  // (a grid beyond what ensure_lane sized the rings for: CAP_BLOCKS_PER_CU)
-        LaunchCfg cfg_any    = cfg;
-        cfg_any.any_no_probe = sa.inline_probe;
-        bool primary_shaded = false;  // tree path: bounce 0's shading done by the camera-ray kernel
-        // Camera rays of a DENSE scene.  The packet walk (one node sequence per 8x8-pixel tile) is the fast form while a tile's 64
-        // rays meet few triangles: 9.3 per packet on the 262 k-triangle hall at 1080p (0.13 triangles per pixel).  At 16.8 M
-        // triangles (8 per pixel) a tile covers hundreds of leaves, every lane pays for every one of them, and the stage was 7.2 of the
-        // big_variant's 24 ms: there the rays go through k_trace_closest8 like extension rays do, one lane each.  Same hit rule, same
-        // bits.  The wide view's padding budget assumes ray origins inside the scene bounds (wide_builder.cpp): a camera outside them
-        // keeps the packet walk.
-        // Shadow rays of the reference model where the tree is far beyond the caches: the wide view with lane refill instead of chunk
-        // by chunk (trace8.hip k_trace_any8_refill).  Measured per 8 spp at 1080p, any-hit stage (tools/primary_ab.py): 262 k triangles
-        // (21 MB of wide nodes and intersection records) 1.89 -> 1.99 ms, 4.2 M (325 MB) 3.02 -> 3.02, 16.8 M (1.3 GB) 5.46 -> 4.01:
-        // lanes are throughput only where a step's round trip ends in HBM.  The switch sits at twice the 256-MiB Infinity Cache;
-        // A/B: CAP_ANY_REFILL=0|1.
-        bool any_refill = false;
-        if (!fused && !ext && bvh.wide8_ok && c->tri_count > kExhaustiveMax)
-        {
-            const int force = (int)c->sw.v[SW_ANY_REFILL];
-            const uint64_t tree_bytes = (uint64_t)c->wide8_nodes * kWideNodeStride * 4u + (uint64_t)c->tri_count * 64u;
-            any_refill = force >= 0 ? force != 0 : tree_bytes >= kAnyRefillTreeBytes;
-        }
-        bool primary_wide = false;
-        if (!fused && bvh.wide8_ok && c->tri_count > kExhaustiveMax)
-        {
-            const int force = (int)c->sw.v[SW_PRIMARY_WIDE];  // A/B switch: 0 never, 1 whenever allowed
-            bool inside = true;
-            for (int k = 0; k < 3; ++k)
-                inside = inside && c->camera.position[k] >= c->bvh_info.bounds_lo[k] && c->camera.position[k] <= c->bvh_info.bounds_hi[k];
-            const double per_pixel = (double)c->tri_count / std::max(1.0, (double)c->screen.width * c->screen.height);
-            primary_wide = inside && (force >= 0 ? force != 0 : per_pixel >= kPrimaryWideTrianglesPerPixel);
-        }
-        if (sample_table)
-        {
-            launch_sample_terms(L.stream, scene.bluenoise, frames, ns, D, L.terms.p);
-            c->last_terms = CapContext::LastTerms{frames, ns, D, lane};
-            if (trace_launch(c, "sample_terms batch %u", batch)) return fail(CAP_ERR_HIP, "sample_terms failed");
-        }
-        // The camera-vertex form of this batch: bounce 0's rays once per jitter group into the table, its per-slot remainder at the head of
-        // bounce 1's launch; no bounce-0 launch and no any-hit launch.  No gate on the slots per group: with ONE slot per group, where no
-        // camera ray is shared, the form is still the faster one -- 1080p, tools/camera_table_small.py, ms per render off -> on: 1 slot
-        // depth 1 0.1515 -> 0.1316, depth 2 0.2164 -> 0.1976; 2 slots 0.2261 -> 0.2017 and 0.3241 -> 0.2992 (docs/experiments.md (104)).
-        const bool     camera_head = camera_table && sa.code_in_color && sa.wave_ring;
-        const uint32_t n_groups    = camera_head ? batch_groups[batch] : 0u;
-        float4* const  tab_p = L.camera.p, *const tab_n = L.camera.p + (size_t)n_groups * Ppad;
-        if (camera_head)
-        {
-            StageTimer t(c, ST_PRIMARY, st);
-            launch_camera_vertices(cfg, bvh, sa, n_groups, tab_p, tab_n);
-            c->last_camera = CapContext::LastCamera{frames, ns, n_groups, lane};
-            // every CapStats field keeps its value between the two forms: bounce 0's shadow rays are still one any-hit pass of the batch,
-            // traced inside the fused launch instead of by a launch of their own
-            ++c->stats.launches_trace_any;
-            if (trace_launch(c, "camera_vertices batch %u", batch)) return fail(CAP_ERR_HIP, "camera_vertices failed");
-        }
-        c->last_camera_table = camera_head ? 1u : 0u;
-        for (uint32_t b = camera_head ? 1u : 0u; b <= D; ++b)
-        {
-            const int pi = (int)(b & 1u), po = pi ^ 1;
-            sa.bounce    = b;
-            // bounce b's [slot][4096] block; the last bounce samples nothing and reads nothing, but takes the same form of kernel
-            if (fused) sa.sample_terms = sample_table ? L.terms.p + (size_t)(b < D ? b : 0u) * ns * 4096 : nullptr;
-            // (inline_nee: no shadow entries are written, so the shadow queue's two 16-byte planes carry the paths' gathered radiance)
-            sa.in        = RayQueue{L.q_org[pi].p, L.q_dir[pi].p, L.q_thr[pi].p, b ? ext_count + (b - 1) * per_queue : nullptr, class_capacity,
-                                    pi ? L.s_dir.p : L.s_org.p};
-            sa.out       = RayQueue{L.q_org[po].p, L.q_dir[po].p, L.q_thr[po].p, ext_count + b * per_queue, class_capacity,
-                                    po ? L.s_dir.p : L.s_org.p};
-            sa.shadow    = ShadowQueue{L.s_org.p, L.s_dir.p, L.s_con.p, sh_count + b * per_queue, class_capacity};
-            sa.work      = work_shade + b * per_queue;
-            const bool head = camera_head && b == 1;
-            // (the input queue of that launch is bounce 0's identity queue: its three planes carry the table and bounce 0's sample terms)
-            if (head) sa.in = RayQueue{tab_p, tab_n, L.terms.p, ext_count, class_capacity, nullptr};
-            if (fused)
-            {
-                StageTimer t(c, b == 0 ? ST_PRIMARY : ST_CLOSEST, st);
-                const uint32_t form = launch_trace_shade(cfg, bvh, sa, ext, feedback, head);
-                if (b) ++c->stats.launches_trace_closest, c->last_mark_form = form;
-                if (trace_launch(c, "trace_shade bounce %u batch %u", b, batch)) return fail(CAP_ERR_HIP, "trace_shade failed");
-            }
-            else
-            {
-                if (b == 0)
-                {
-                    {
-                        StageTimer t(c, ST_PRIMARY, st);
-                        if (primary_wide)
-                        {
-                            // dense scene: camera rays as an identity queue through the wide per-lane kernel (see above)
-                            const uint32_t id_cap = (((max_count + kQueueClasses - 1) / kQueueClasses) + 63u) & ~63u;
-                            const RayQueue idq{L.q_org[0].p, L.q_dir[0].p, nullptr, L.counters.p + 3 * counter_words, id_cap, nullptr};
-                            if (c->sw.on(SW_RAYGEN_KERNEL) || bvh.tri_count == 0)  // A/B switch: the identity queue written out by its own kernel
-                            {
-                                launch_raygen_identity(cfg, cam, c->screen, frames, ns, idq);
-                                launch_trace_closest8(cfg, bvh, idq, max_count, L.hits.p, sa.work);
-                            }
-                            else
-                                launch_trace_closest8_camera(cfg, bvh, idq, max_count, L.hits.p, sa.work, cam, c->screen, frames, ns);
-                        }
-                        else
-                        {
-                            primary_shaded = launch_primary_shade(cfg, bvh, sa, L.hits.p, ext);
-                            if (!primary_shaded) launch_trace_primary(cfg, bvh, cam, c->screen, frames, ns, L.hits.p, sa.work);
-                        }
-                    }
-                    if (aov_slot != ~0u) launch_geo_aov(cfg, scene, L.hits.p + (size_t)aov_slot * Ppad, Ppad, c->aov_geo.p);
-                }
-                if (b != 0 || !primary_shaded)
-                {
-                    StageTimer t(c, ST_SHADE, st, b == 0 ? ST_DIRECT : ST_NONE);
-                    launch_shade(cfg, sa, ext, feedback);
-                    ++c->stats.launches_shade;
-                }
-            }
-            if (!sa.inline_nee && !(fused && sa.wave_ring && b != 0))
-            {
-                StageTimer t(c, ST_ANY, st, b == 0 ? ST_DIRECT : ST_NONE);
-                if (any_refill)
-                    launch_trace_any8_refill(cfg_any, bvh, sa.shadow, max_count, b == 0 ? L.pl_direct.p : L.pl_color.p, Ppad, ns, c->shaded_counter.p,
-                                             work_any + b * per_queue, frames);
-                else
-                    launch_trace_any(cfg_any, bvh, sa.shadow, max_count, b == 0 ? L.pl_direct.p : L.pl_color.p, Ppad, ns, c->shaded_counter.p,
-                                     work_any + b * per_queue, /* next-event estimation: most shadow rays reach the light */ ext, frames,
-                                     (b == 0 && sa.code_in_color) ? L.pl_color.p : nullptr);
-                ++c->stats.launches_trace_any;
-                if (trace_launch(c, "trace_any bounce %u batch %u", b, batch)) return fail(CAP_ERR_HIP, "trace_any failed");
-            }
-            if (!fused && b < D)
-            {
-                StageTimer t(c, ST_CLOSEST, st);
-                if (bvh.wide8_ok)  // bounce b + 1's slot of the fused kernels' grab counters is free on this path
-                    launch_trace_closest8(cfg, bvh, sa.out, max_count, L.hits.p, work_shade + (b + 1) * per_queue);
-                else
-                    launch_trace_closest(cfg, bvh, sa.out, max_count, L.hits.p);
-                ++c->stats.launches_trace_closest;
-            }
-        }
-        if (!lowres)
-        {
-            StageTimer t(c, ST_RESOLVE, st);
-            if (two_lanes && last_resolve) HIP_TRY(hipStreamWaitEvent(L.stream, last_resolve, 0));  // frame order of the additions
-            launch_resolve(cfg, sa.planes, ns, Ppad, c->accum.p, sa.albedo_in_w != 0u, scene.kd_untextured, sa.code_in_color != 0u);
-            if (two_lanes)
-            {
-                HIP_TRY(hipEventRecord(c->lane_ev[lane], L.stream));
-                last_resolve = c->lane_ev[lane];
-            }
-        }
-        // queue lengths of this batch -> pinned host memory, summed at the next sync
-        uint32_t* pinned = nullptr;
-        if (!c->pinned_pool.empty())
-        {
-            pinned = c->pinned_pool.back();
-            c->pinned_pool.pop_back();
-        }
-        else
-            HIP_TRY(hipHostMalloc((void**)&pinned, sizeof(uint32_t) * 2 * 256 * kQueueClasses * kCounterStride, hipHostMallocDefault));
-        HIP_TRY(hipMemcpyAsync(pinned, L.counters.p, sizeof(uint32_t) * counter_words, hipMemcpyDeviceToHost, L.stream));
-        c->pending.push_back({pinned, D | (sa.inline_nee ? 1u << 16 : 0u)});
-        HIP_TRY(hipGetLastError());
-
-        // primary rays: one per valid pixel per frame
-        uint64_t valid = 0;
-        for (uint32_t lt = 0; lt < c->screen.local_tiles; ++lt)
-        {
-            const uint32_t gt = lt * c->screen.shard_count + c->screen.shard_index;
-            const uint32_t ty = gt / c->screen.tiles_x, tx = gt % c->screen.tiles_x;
-            const uint32_t w = std::min(kTileDim, c->screen.width - tx * kTileDim), h = std::min(kTileDim, c->screen.height - ty * kTileDim);
-            valid += (uint64_t)w * h;
-        }
-        c->stats.rays_primary += valid * ns;
-        c->stats.frames += ns;
-        if (!lowres) c->frames_accumulated += ns;
-        c->last_slots = ns;
-        c->aov_valid  = aov_slot != ~0u;
-        c->aov_lowres = lowres;
-        c->aov_frame  = frame_begin + done + ns - 1;
-        // the next batch reuses counters/frames: serialise on the stream (already), and bound the event backlog
-        if (c->spans.size() > 4096)
-        {
-            total.reset();
-            if (two_lanes) HIP_TRY(hipStreamSynchronize(c->stream2));
-            if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
-            total.reset(new StageTimer(c, ST_COUNT));
-        }
-    }
-    if (two_lanes)
-    {
-        // the context's stream -- the one callers order their work behind -- ends the call behind lane 1 as well
-        HIP_TRY(hipEventRecord(c->join_ev, c->stream2));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->join_ev, 0));
-        lane_join.armed = false;
-    }
-    total.reset();
-    HIP_TRY(hipEventRecord(c->frames_event[ring], c->stream));
-    return CAP_OK;
 }
 
 int cap_readback(CapContext* c, CapBufferKind kind, float* dst)

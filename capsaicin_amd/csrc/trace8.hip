@@ -46,7 +46,7 @@ __device__ unsigned long long g_w8_counts[16];
 #endif
 
 // CAMERA: the queue is the camera rays' identity queue (entry i = frame slot i / Ppad, local pixel i % Ppad; class k owns entries
-// [k * capacity, min((k + 1) * capacity, total)): dense scenes, context.hip primary_wide) and is never materialised -- a chunk's rays are
+// [k * capacity, min((k + 1) * capacity, total)): dense scenes, ctx_render.hip primary_wide) and is never materialised -- a chunk's rays are
 // generated where the other instantiation loads them (the same primary_dir() on the same operands as k_raygen_identity, which this
 // replaces: 32 B written and read per camera ray and one launch less; docs/experiments.md (89)).
 struct CameraFeed

@@ -2,7 +2,7 @@
 
 The fused kernels of scenes of at most 64 triangles skip work on three decisions, each claimed to change no result bit:
   * the next-event pair cull of the EXT model (ctx_scene.hip update_nee_pairs): `nee_rule` restates its rule;
-  * the camera pair cull of bounce 0 (small_scene.hip stage_camera_pairs / pair_mask, host gate in context.hip cap_render): `camera_bounds` restates
+  * the camera pair cull of bounce 0 (small_scene.hip stage_camera_pairs / pair_mask, host gate in ctx_render.hip cull_camera_pairs): `camera_bounds` restates
     the bounds and the gate, `camera_truth` says which of the model's culls are wrong;
   * the occluder-first probes of the reference model: `probe_scores` restates the order they probe in.
 Everything is numpy: fp32 where the code under test works in fp32 (fused multiply-adds where it writes fmaf), float64 where it works in
@@ -276,7 +276,7 @@ def euler_camera(position, yaw, pitch, roll, w, h, focal=0.03, sensor_x=0.036):
 
 
 def camera_gate(cam):
-    """cap_render's gate: the cull is on iff skew = max |Gram - I| of (right, up, forward) is below 1e-4 and the worst-case shift of a
+    """cap_render's gate (ctx_render.hip cull_camera_pairs): the cull is on iff skew = max |Gram - I| of (right, up, forward) is below 1e-4 and the worst-case shift of a
     projected point on the sensor, skew * extent * (f / s + 1 + s' / (2 s) + (sx + sy) / (4 f)), is at most PAD / 8 in x and in y.
     Returns (gate, skew, shift_x, shift_y)."""
     def dotf(a, b):  # x[0] * y[0] + x[1] * y[1] + x[2] * y[2] in fp32, no contraction

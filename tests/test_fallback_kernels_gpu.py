@@ -1,5 +1,5 @@
 """The binary-tree kernels behind the wide view: k_trace_closest_refill<32|64> and k_trace_any<32|64> are what
-context.hip routes extension and shadow rays to when the compressed 8-wide view is deeper than the wide kernels' per-lane stacks
+ctx_render.hip routes extension and shadow rays to when the compressed 8-wide view is deeper than the wide kernels' per-lane stacks
 (21 levels: 262 k triangles are 8 deep, 16.8 M are 11), and under the A/B switch CAP_NO_WIDE8.  Nothing ran them in the driver's
 suite until round 4.  Here:
  * in-process: the depth bound is lowered with cap_debug_set(CAP_DEBUG_WIDE_DEPTH_LIMIT) so that an ordinary scene's wide view

@@ -1,7 +1,7 @@
 """The three culls of the fused small-scene kernels on scenes built to defeat them (tests/pair_cull_support.py; the models and the
 cases' design are checked on the CPU by tests/test_pair_culls.py):
   N  the next-event pair cull of the EXT model (ctx_scene.hip update_nee_pairs): CAP_DEBUG_NEE_PAIRS equals the model's counts;
-  C  the camera pair cull of bounce 0 (small_scene.hip stage_camera_pairs, the gate in cap_render): CAP_DEBUG_CAMERA_CULL equals the model's gate;
+  C  the camera pair cull of bounce 0 (small_scene.hip stage_camera_pairs, the gate in ctx_render.hip cull_camera_pairs): CAP_DEBUG_CAMERA_CULL equals the model's gate;
   P  the occluder-first probes of the reference model and the EXT model's inline next-event rays.
 Every case renders two frames of depth 3 with the cull on and equals the oracle bit for bit in every plane and the three ray counters;
 the same context then renders with the switch flipped and gives the same bits."""

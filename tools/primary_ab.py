@@ -1,4 +1,4 @@
-"""Camera rays: packet walk on the binary tree vs one lane per ray on the wide view (context.hip primary_wide), per scene density.
+"""Camera rays: packet walk on the binary tree vs one lane per ray on the wide view (ctx_render.hip plan_forms, primary_wide), per scene density.
     CAP_PRIMARY_WIDE=0|1 python tools/primary_ab.py SCALE [SPP]     -> stage split of a stage-timed render of the hall at that scale"""
 import os
 import sys
