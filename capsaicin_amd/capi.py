@@ -665,6 +665,8 @@ class Renderer:
     DEBUG_SELFTEST_SAMPLE_TABLE = 17  # mismatching entries << 32 | (bounce, slot) rows of the last batch's table compared
     DEBUG_CAMERA_TABLE = 18  # 1: the last render ran bounce 0 inside bounce 1's launch, from the per-batch table of camera vertices
     DEBUG_SELFTEST_CAMERA_TABLE = 19  # mismatching entries << 32 | jitter groups << 16 | frame slots of the last batch compared
+    DEBUG_GRAY_ENTRIES = 20  # 1: the last render's fused launches used 32-byte extension entries (one throughput word)
+    DEBUG_SELFTEST_GRAY = 21  # after a 48-byte render: entries with unequal throughput words << 32 | entries of the last batch's queues looked at
 
     def debug_set(self, key, value):
         _check(lib().cap_debug_set(self.ctx, key, value), "cap_debug_set")

@@ -244,6 +244,12 @@ struct CapContext
         const FrameConst* frames = nullptr;
         uint32_t          n_slots = 0, n_groups = 0, lane = 0;
     } last_camera;
+    uint32_t      last_gray_entries = 0;       // 1: the last cap_render's fused launches used 32-byte extension entries (CAP_DEBUG_GRAY_ENTRIES)
+    struct LastQueues                          // what the last batch of a 48-byte render left in the extension queues (CAP_DEBUG_SELFTEST_GRAY)
+    {
+        uint32_t num_bounces = 0, first_writer = 0, class_capacity = 0, lane = 0;  // first_writer: the first bounce that appended to a queue
+        bool     valid = false;
+    } last_queues;
     uint32_t      last_cull_camera_pairs = 0;  // ShadeArgs::cull_camera_pairs of the last cap_render batch (CAP_DEBUG_CAMERA_CULL)
     uint32_t      traversal_mode  = CAP_TRAVERSAL_AUTO;
     uint32_t      bvh_build_mode  = CAP_BVH_BUILD_AUTO;

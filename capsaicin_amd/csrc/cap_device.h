@@ -177,6 +177,11 @@ __device__ __forceinline__ v3 primary_dir(const CameraDev& cam, const ScreenDev&
 
 // Wavefront queues, all SoA planes of float4 (16 B per lane per access, 1 KiB per wave instruction).
 // Sub-queue k occupies entries [k * class_capacity, (k + 1) * class_capacity) and is counted by count[k * kCounterStride].
+// An entry has one of two layouts, the same for every launch of a batch (ctx_render.hip RenderPlan::gray_entries):
+//   48 bytes  org_tmin = (o.xyz, tmin)        dir_tmax = (d.xyz, tmax)             thr_pid = (throughput.xyz, asfloat(path id))
+//             (the lean kernels' tmin / tmax are constants nobody reads; with TraceShadeCfg::CARRY the two words hold the next sample)
+//   32 bytes  org_tmin = (o.xyz, throughput)  dir_tmax = (d.xyz, asfloat(path id)) thr_pid neither read nor written
+//             (TraceShadeCfg::GRAY: the sample-table kernels on a scene without textures, where the throughput is one float)
 struct RayQueue
 {
     float4*   org_tmin;  // (o.xyz, tmin)

@@ -43,6 +43,7 @@ enum CapSwitch : uint32_t
     SW_NO_PLANE_CODE,       // small-scene path under albedo_in_w: bounce 0 writes the constant direct plane as before (ShadeArgs::code_in_color off)
     SW_SAMPLE_TABLE,        // small-scene path, reference model: 0 never, 1 whenever the kernels have the form: direction-sample terms from the batch's table (ShadeArgs::sample_terms)
     SW_NO_CAMERA_TABLE,     // small-scene path, reference model: bounce 0 stays a launch of its own (no camera-vertex table, no bounce-0 head in bounce 1's launch)
+    SW_NO_GRAY_ENTRIES,     // small-scene path, sample-table kernels, untextured scene: the extension queue keeps its 48-byte entries (three throughput words)
     SW_COUNT
 };
 struct SwitchTable
@@ -373,11 +374,19 @@ bool launch_primary_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeAr
 // bounce 0's block of the sample table, args.in.count = bounce 0's counter lines; args.frames[s].pad1 = slot s's jitter group.  Needs
 // sample_terms, inline_probe and wave_ring, and a batch whose colour plane carries the code (code_in_color).  Its bounce-0 shadow rays go
 // through the wave rings: no any-hit launch follows bounce 0.
-uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback = false, bool camera_head = false);
+// gray: the extension queues args.in (not under camera_head, where it is the table) and args.out hold 32-byte entries (RayQueue) and
+// thr_pid is neither read nor written.  Needs sample_terms and trace_shade_has_gray_form(); every launch of a batch or none.
+uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback = false, bool camera_head = false,
+                            bool gray = false);
 // whether the reference model's bounce 0 of this scene has the form ShadeArgs::code_in_color asks for (the kernel of tame records in LDS)
 bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene);
 // ... and the form ShadeArgs::sample_terms asks for (the lean kernels)
 bool trace_shade_has_table_form(const BvhDev& bvh, const SceneDev& scene);
+// ... and 32-byte extension entries (launch_trace_shade's gray): the table kernels on a scene without textures
+bool trace_shade_has_gray_form(const BvhDev& bvh, const SceneDev& scene);
+// The premise of that form on a 48-byte queue: out_device[0] += entries of q, up to its class counts, whose three throughput words are not
+// bitwise equal; out_device[1] += entries looked at.
+void launch_gray_selftest(hipStream_t stream, const RayQueue& q, unsigned long long* out_device);
 // The batch's table of direction-sample terms: table[(b * n_slots + s) * 4096 + ((y mod 64) << 6 | x mod 64)] = (ca, cb, cos_theta, 0) of
 // hemisphere_terms() of the blue-noise sample of count = frames[s].frame_count * 25 + b, for b < num_bounces (the bounces that sample).
 void launch_sample_terms(hipStream_t stream, const float2* bluenoise, const FrameConst* frames, uint32_t n_slots, uint32_t num_bounces, float4* table);

@@ -210,6 +210,18 @@ __device__ __forceinline__ uint32_t wave_append(bool emit, uint32_t* counter)
 //   LEAN     the lean per-chunk plumbing (see kChunkLean)
 //   CODE     bounce 0 under ShadeArgs::code_in_color: the first vertex's code goes to color.w and the direct plane is not written
 //   TAB      the direction sample's terms come from the batch's table (ShadeArgs::sample_terms) instead of being carried and computed
+//   GRAY     the throughput is one float (C::Thr) and an extension entry two float4 (RayQueue, cap_device.h): an untextured scene, where
+//            the three components are the same operations on the same operands at every bounce
+// Text that serves both forms (small_scene_body.h) makes a throughput with thr_of<C::Thr>() -- the first of three equal components where
+// it is one float -- and hands it to code written for three components through thr3().
+template <class T>
+__device__ __forceinline__ T thr_of(float x, float y, float z);
+template <>
+__device__ __forceinline__ v3 thr_of<v3>(float x, float y, float z) { return mk3(x, y, z); }
+template <>
+__device__ __forceinline__ float thr_of<float>(float x, float, float) { return x; }
+__device__ __forceinline__ v3 thr3(v3 thr) { return thr; }
+__device__ __forceinline__ v3 thr3(float thr) { return mk3(thr, thr, thr); }
 struct ShadePre
 {
     bool  valid;
@@ -515,7 +527,7 @@ constexpr uint32_t kWaveRing = 128;  // <= 63 parked + <= 64 new
 // are whatever the registers hold.  The probe runs on all lanes and reads p: on a lane without a shadow ray its answer is discarded.
 template <class C>
 __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* shade_tab, const ShadePre& pre, uint32_t klass,
-                                             uint32_t pid, float4 hit, v3 thr, uint32_t& n_shaded, Stamps& st,
+                                             uint32_t pid, float4 hit, typename C::Thr thr, uint32_t& n_shaded, Stamps& st,
                                              const ProbeArgs probe = ProbeArgs(), uint32_t* n_probed = nullptr, uint32_t ring_head = 0,
                                              uint32_t* ring_n = nullptr)
 {
@@ -560,7 +572,16 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
                 // three no-return float atomics are plain IEEE adds in program order; unlike a load-add-store they do not make
                 // the wave wait for the old value.
                 // (A load-add-store here instead, as in k_trace_any: 16.4 -> 16.6 ms.)
-                if (C::SKY_RMW)
+                if constexpr (C::GRAY)
+                {
+                    // thr.x * 0.7f and thr.y * 0.7f are one product
+                    float*      c  = reinterpret_cast<float*>(a.planes.color + plane_idx);
+                    const float t7 = thr * 0.7f;
+                    atomicAdd(c + 0, t7);
+                    atomicAdd(c + 1, t7);
+                    atomicAdd(c + 2, thr * 0.85f);
+                }
+                else if (C::SKY_RMW)
                 {
                     // the tree path's shade stage: three scattered float atomics per escaping ray are three 64-B memory-side
                     // requests each; the path is this entry's only writer within the launch, so a 16-B load-add-store gives the
@@ -653,7 +674,8 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
                         // term above, where the atomics win by 1 %, here most vertices of a frame take this branch -- the previous frame saw
                         // them -- and 6 M atomics per launch cost more than the load's latency: real-time frame 0.648 -> 0.638 ms.
                         const float4 cur = a.planes.color[plane_idx];
-                        a.planes.color[plane_idx] = make_float4(cur.x + thr.x * hc.x, cur.y + thr.y * hc.y, cur.z + thr.z * hc.z, cur.w);
+                        const v3     th  = thr3(thr);  // (no feedback kernel is GRAY)
+                        a.planes.color[plane_idx] = make_float4(cur.x + th.x * hc.x, cur.y + th.y * hc.y, cur.z + th.z * hc.z, cur.w);
                     }
                 }
             }
@@ -665,7 +687,10 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
                 if (c.x != 0.0f || c.y != 0.0f || c.z != 0.0f)
                 {
                     emit_shadow = true;
-                    contrib     = C::FIRST ? c : thr * c;  // rt_direct_lighting.hlsl:77 / rt_indirect.hlsl:136
+                    if constexpr (C::GRAY)
+                        contrib = C::FIRST ? c : c * thr;
+                    else
+                        contrib = C::FIRST ? c : thr * c;  // rt_direct_lighting.hlsl:77 / rt_indirect.hlsl:136
                 }
                 // rt_indirect.hlsl:149-170
                 // the reference traces one more ray after the last bounce whose payload is never read (:91,:173): at that bounce
@@ -688,7 +713,12 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
                         const float fn = kInvPi * fmaxf(ndd, 0.0f);
                         const float f  = C::TAME ? div_unscaled(fn, pdf) : fn / pdf;
                         thr            = thr * f;
-                        if (!C::FIRST) thr = thr * kd;
+                        if constexpr (C::GRAY)
+                        {
+                            if (!C::FIRST) thr = thr * kd.x;  // kd = (k, k, k): the condition of the form
+                        }
+                        else if (!C::FIRST)
+                            thr = thr * kd;
                         emit_ext = more && (!C::FIRST || pre.indirect_on);
                     }
                 }
@@ -741,7 +771,15 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
             a.shadow.org_tmin[si]    = make_float4(p.x, p.y, p.z, u2f(pid));
             a.shadow.contrib_pid[si] = make_float4(contrib.x, contrib.y, contrib.z, C::CODE ? kCodeKd : 0.0f);
         }
-        if (emit_ext)
+        if constexpr (C::GRAY)
+        {
+            if (emit_ext)
+            {
+                a.out.org_tmin[ei] = make_float4(p.x, p.y, p.z, thr);
+                a.out.dir_tmax[ei] = make_float4(dir.x, dir.y, dir.z, u2f(pid));
+            }
+        }
+        else if (emit_ext)
         {
             a.out.org_tmin[ei] = make_float4(p.x, p.y, p.z, C::CARRY ? pre.r1n : kRayEps);
             a.out.dir_tmax[ei] = make_float4(dir.x, dir.y, dir.z, C::CARRY ? pre.r2n : kRayFar);

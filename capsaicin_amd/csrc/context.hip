@@ -275,7 +275,8 @@ static const char* const kSwitchNames[SW_COUNT] = {
     "CAP_NO_WIDE8", "CAP_LANE1_PRIORITY", "CAP_PLOC_RADIUS", "CAP_SAHDEV_LEAF", "CAP_WIDE_HOST_COLLAPSE", "CAP_TRACE_LAUNCHES", "CAP_NO_TWO_LANES",
     "CAP_LANE_SPLIT_MIN", "CAP_BLOCKS_PER_CU", "CAP_NO_CAMERA_CULL", "CAP_NO_ALBEDO_IN_W", "CAP_NO_INLINE_NEE", "CAP_NO_INLINE_PROBE", "CAP_NO_WAVE_RING",
     "CAP_ANY_REFILL", "CAP_PRIMARY_WIDE", "CAP_NO_PACKET", "CAP_NO_ANY_PROBE", "CAP_ANY_PROBE", "CAP_ANY_BLOCKS", "CAP_NO_PRIMARY_FUSE", "CAP_W8_REFILL",
-    "CAP_W8_GRID", "CAP_AUTO_SAH_TRIANGLES", "CAP_NO_NEE_PAIR_CULL", "CAP_RAYGEN_KERNEL", "CAP_NO_PLANE_CODE", "CAP_SAMPLE_TABLE", "CAP_NO_CAMERA_TABLE"};
+    "CAP_W8_GRID", "CAP_AUTO_SAH_TRIANGLES", "CAP_NO_NEE_PAIR_CULL", "CAP_RAYGEN_KERNEL", "CAP_NO_PLANE_CODE", "CAP_SAMPLE_TABLE", "CAP_NO_CAMERA_TABLE",
+    "CAP_NO_GRAY_ENTRIES"};
 
 static void switches_from_environment(SwitchTable& t)
 {
@@ -477,7 +478,8 @@ int cap_set_batch_paths(CapContext* c, uint64_t max_paths)
 }
 
 // Canary for the append-guard test (tests/test_append_guard_gpu.py): the extension queues' six planes of lane 0 are filled with one
-// word; after a render with undersized sub-queues every entry BEHIND the last class's sub-queue must still hold it.
+// word; after a render with undersized sub-queues every entry BEHIND the last class's sub-queue must still hold it.  (With 32-byte entries
+// the two thr_pid planes are never written: they keep the word throughout, BEHIND stays 0 for them and USED counts the other four.)
 constexpr uint32_t kCanaryWord = 0x7fc0da7au;  // (a quiet NaN nobody computes)
 __global__ __launch_bounds__(256) void k_canary_count(const uint4* p, size_t begin, size_t end, unsigned long long* out)
 {
@@ -627,6 +629,29 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
         const unsigned long long expected = (unsigned long long)lc.n_slots * c->screen.pixels_padded;
         if (h[1] != expected) return fail(CAP_ERR_HIP, "cap_debug_get: the camera table self-test compared %llu of %llu entries", h[1], expected);
         *value = (h[0] << 32) | ((uint64_t)lc.n_groups << 16) | lc.n_slots;  // mismatches << 32 | groups << 16 | slots compared
+        return CAP_OK;
+    }
+    case CAP_DEBUG_GRAY_ENTRIES: *value = c->last_gray_entries; return CAP_OK;
+    case CAP_DEBUG_SELFTEST_GRAY:
+    {
+        const CapContext::LastQueues& lq = c->last_queues;
+        if (!lq.valid || c->last_gray_entries) return fail(CAP_ERR_STATE, "cap_debug_get: the last cap_render left no 48-byte extension queues (small-scene path, CAP_NO_GRAY_ENTRIES)");
+        HIP_TRY(hipSetDevice(c->device));
+        if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
+        // Bounce b appends to queue (b & 1) ^ 1 and the last bounce appends nothing: the last two appending bounces' entries are intact,
+        // and so are their counter lines (cleared by the next batch).
+        const CapContext::Lane& L = c->lane[lq.lane];
+        const CounterLayout     lay{lq.num_bounces};
+        unsigned long long      h[2];
+        if (int e = count_on_device(c, h, [&](unsigned long long* d) {
+                for (uint32_t back = 1; back <= 2 && back <= lq.num_bounces && lq.num_bounces - back >= lq.first_writer; ++back)
+                {
+                    const uint32_t b = lq.num_bounces - back, po = (b & 1u) ^ 1u;
+                    launch_gray_selftest(c->stream, RayQueue{L.q_org[po].p, L.q_dir[po].p, L.q_thr[po].p, lay.ext(L.counters.p, b), lq.class_capacity, nullptr}, d);
+                }
+            }))
+            return e;
+        *value = (h[0] << 32) | std::min<unsigned long long>(h[1], 0xffffffffull);
         return CAP_OK;
     }
     case CAP_DEBUG_NEE_PAIRS:

@@ -148,6 +148,7 @@ struct RenderPlan
     uint32_t blocks_per_cu = 0;
     bool     sample_table = false;      // direction-sample terms from a per-batch table (ShadeArgs::sample_terms)
     bool     camera_table = false;      // the call sizes and groups for the camera-vertex table (camera_head: it also fits the rings)
+    bool     gray_entries = false;      // the extension queues hold 32-byte entries, one throughput word (launch_trace_shade's gray)
     // Jitter groups: the slots of a batch by the bits of (jitter_x, jitter_y).  slot_group[f]: the group of frame f within its batch,
     // numbered in order of first appearance; group_first[batch start + g]: the first slot of group g.  A group need not be contiguous.
     std::vector<uint32_t> slot_group, group_first, batch_groups;
@@ -349,6 +350,9 @@ int plan_render(const CapContext* c, uint32_t frame_begin, uint32_t n_frames, ui
     // calls: frame_begin advances from call to call in real use.
     // A/B switch CAP_SAMPLE_TABLE: 0 never, 1 whenever the kernels have the form (which is also the product's choice).
     p.sample_table = fused && !ext && !feedback && num_bounces >= 1 && c->sw.get(SW_SAMPLE_TABLE, 1) != 0 && trace_shade_has_table_form(bvh, scene);
+    // 32-byte extension entries: the table kernels on a scene without textures, where a throughput's three components are equal in every
+    // bit.  For every launch of every batch: an entry of one form means nothing to a kernel of the other.  A/B switch CAP_NO_GRAY_ENTRIES.
+    p.gray_entries = p.sample_table && trace_shade_has_gray_form(bvh, scene) && !c->sw.on(SW_NO_GRAY_ENTRIES);
     p.cull_camera_pairs = cull_camera_pairs(c) ? 1u : 0u;
     // Nobody reads a batch's planes but the resolve (plane read-backs and the reconstruction chain need CAP_RENDER_AOV)
     const bool no_albedo_w = c->sw.on(SW_NO_ALBEDO_IN_W);  // A/B switch
@@ -510,7 +514,7 @@ struct BatchRun
 int fused_bounce(CapContext* c, const RenderPlan& p, const Batch& bt, const BatchRun& r, const ShadeArgs& sa, bool head)
 {
     StageTimer     t(c, sa.bounce == 0 ? ST_PRIMARY : ST_CLOSEST, p.stage_timers);
-    const uint32_t form = launch_trace_shade(r.cfg, r.bvh, sa, p.ext, p.feedback, head);
+    const uint32_t form = launch_trace_shade(r.cfg, r.bvh, sa, p.ext, p.feedback, head, p.gray_entries);
     if (sa.bounce) ++c->stats.launches_trace_closest, c->last_mark_form = form;
     if (trace_launch(c, "trace_shade bounce %u batch %u", sa.bounce, bt.index)) return fail(CAP_ERR_HIP, "trace_shade failed");
     return CAP_OK;
@@ -627,6 +631,8 @@ int render_batch(CapContext* c, const RenderPlan& p, const Batch& bt, const Shad
         if (trace_launch(c, "camera_vertices batch %u", bt.index)) return fail(CAP_ERR_HIP, "camera_vertices failed");
     }
     c->last_camera_table = p.camera_head ? 1u : 0u;
+    // (the reference model's 48-byte queues of this batch, for CAP_DEBUG_SELFTEST_GRAY: under camera_head bounce 0 appends nothing)
+    c->last_queues = CapContext::LastQueues{D, p.camera_head ? 1u : 0u, class_capacity, bt.lane, p.fused && !p.ext && !p.gray_entries};
     for (uint32_t b = p.camera_head ? 1u : 0u; b <= D; ++b)
     {
         const int pi = (int)(b & 1u), po = pi ^ 1;
@@ -639,6 +645,8 @@ int render_batch(CapContext* c, const RenderPlan& p, const Batch& bt, const Shad
         sa.shadow = ShadowQueue{L.s_org.p, L.s_dir.p, L.s_con.p, r.lay.shadow(L.counters.p, b), class_capacity};
         sa.work   = r.lay.work_shade(L.counters.p, b);
         const bool head = p.camera_head && b == 1;
+        // (gray_entries: the same buffers; the two queues' thr_pid planes are neither read nor written, and an entry's words are RayQueue's
+        // 32-byte layout)
         // (the input queue of that launch is bounce 0's identity queue: its three planes carry the table and bounce 0's sample terms)
         if (head) sa.in = RayQueue{tab_p, tab_n, L.terms.p, r.lay.ext(L.counters.p, 0), class_capacity, nullptr};
         if (p.fused)
@@ -696,6 +704,7 @@ extern "C" int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames
     // the debug state of a call (cap_debug_get), from the plan; what a batch leaves is reset until the first batch writes it
     c->last_mark_form = 0, c->last_sample_table = p.sample_table ? 1u : 0u, c->last_cull_camera_pairs = p.cull_camera_pairs;
     c->last_terms = CapContext::LastTerms{}, c->last_camera_table = 0, c->last_camera = CapContext::LastCamera{};
+    c->last_gray_entries = p.gray_entries ? 1u : 0u, c->last_queues = CapContext::LastQueues{};
     if (p.feedback && (c->post_w != c->screen.width || c->post_h != c->screen.height))
         if (int e = cap_post_reset(c)) return e;  // first frame: cleared histories, every vertex is a disocclusion
     // No host synchronisation with the previous call: everything it still uses is either ordered behind it on the stream (queues,

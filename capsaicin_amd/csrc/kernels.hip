@@ -1055,7 +1055,8 @@ template <bool FIRST_, bool EXT_, bool FB_ = false>
 struct ShadeStageCfg
 {
     static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_;
-    static constexpr bool CARRY = false, SKY_RMW = true, PROBE = false, TAME = false, LEAN = false, CODE = false, TAB = false;
+    static constexpr bool CARRY = false, SKY_RMW = true, PROBE = false, TAME = false, LEAN = false, CODE = false, TAB = false, GRAY = false;
+    using Thr = v3;
 };
 
 // Stand-alone shade stage (used with the LBVH stack traversal): consumes the hit records of the preceding trace kernel.

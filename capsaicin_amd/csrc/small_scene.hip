@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cassert>
+#include <type_traits>
 
 namespace cap
 {
@@ -35,7 +36,10 @@ __device__ unsigned long long g_wave_times[2 * 16384];  // (start, end) s_memrea
 // HEAD: the batch's first bounce >= 1 launch with bounce 0 inside it (ShadeArgs::in re-used for the camera table, see k_camera_vertices
 // below): the queue is bounce 0's identity queue, a chunk starts with the per-slot remainder of bounce 0 on its table entry and keeps the
 // ray that makes in registers.  Only the TAB bounce >= 1 kernel has the form (k_trace_shade_head).
-template <bool FIRST_, bool EXT_, bool FB_, bool LDS_, bool TAME_, bool CODE_ = false, bool TAB_ = false, bool HEAD_ = false>
+// GRAY: the extension queue's 32-byte entries (RayQueue, cap_device.h) and the throughput as one float, for a scene without textures.  A
+// FIRST kernel writes them, the bounce >= 1 kernel reads and writes them, the HEAD kernel writes them.  Only the TAB kernels have the form
+// (k_trace_shade_tab_gray, k_trace_shade_head_gray), beside their 48-byte forms: trace_shade_has_gray_form.
+template <bool FIRST_, bool EXT_, bool FB_, bool LDS_, bool TAME_, bool CODE_ = false, bool TAB_ = false, bool HEAD_ = false, bool GRAY_ = false>
 struct TraceShadeCfg
 {
     // (TAB_ = kChunkLean in k_trace_shade_tab: a build without the lean plumbing compiles the plain kernel under that name, never launched)
@@ -43,7 +47,9 @@ struct TraceShadeCfg
     static_assert(!CODE_ || (FIRST_ && TAME_), "CODE: bounce 0 of the reference model, scene in LDS, tame records");
     static_assert(!TAB_ || (TAME_ && kChunkLean), "TAB: the lean kernels (reference model, scene in LDS, tame records)");
     static_assert(!HEAD_ || (TAB_ && !FIRST_), "HEAD: the lean bounce >= 1 kernel with the sample table");
-    static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_, LDS = LDS_, TAME = TAME_, CODE = CODE_, TAB = TAB_, HEAD = HEAD_;
+    static_assert(!GRAY_ || TAB_, "GRAY: the lean kernels with the sample table");
+    static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_, LDS = LDS_, TAME = TAME_, CODE = CODE_, TAB = TAB_, HEAD = HEAD_, GRAY = GRAY_;
+    using Thr = typename std::conditional<GRAY_, float, v3>::type;  // a path's throughput
     static constexpr bool CARRY = !EXT && !TAB, SKY_RMW = false;
     static constexpr bool PROBE = !EXT && !FB && LDS;  // the producer-side shadow probe (ShadeArgs::inline_probe) and the per-wave ring
     // the lean per-chunk plumbing (see kChunkLean): the reference model's kernels with the scene in LDS and tame records.  (The
@@ -151,9 +157,9 @@ __device__ __forceinline__ void stage_probe_rows(const BvhDev& bvh, const ShadeA
     }
 }
 
-// All three kernels are small_scene_body.h and nothing else: k_trace_shade the thirteen forms without the sample table, under the names
+// All five kernels are small_scene_body.h and nothing else: k_trace_shade the thirteen forms without the sample table, under the names
 // and with the instructions they have always had, k_trace_shade_tab the three with it, k_trace_shade_head (below) bounce 1 with bounce 0
-// at the head of its chunks.
+// at the head of its chunks, k_trace_shade_tab_gray and k_trace_shade_head_gray those four with 32-byte queue entries.
 template <bool FIRST, bool EXT, bool FB = false, bool LDS = false, bool TAME = false, bool CODE = false>
 __global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, EXT, FB, LDS, TAME, CODE>::kBlocksPerCu)) void k_trace_shade(BvhDev bvh, ShadeArgs a)
 {
@@ -174,6 +180,22 @@ __global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, false, false, true, t
 __global__ __launch_bounds__(kBlock, (TraceShadeCfg<false, false, false, true, true, false, kChunkLean, kChunkLean>::kBlocksPerCu)) void k_trace_shade_head(BvhDev bvh, ShadeArgs a)
 {
     using C              = TraceShadeCfg<false, false, false, true, true, false, kChunkLean, kChunkLean>;
+    constexpr bool FIRST = false, EXT = false, FB = false, LDS = true, TAB = kChunkLean;
+#include "small_scene_body.h"
+}
+
+// GRAY: the three table kernels and the head with 32-byte entries, beside their 48-byte forms -- which keep their names and their
+// instructions, so that the switch CAP_NO_GRAY_ENTRIES stands for the commit before these in a measurement
+template <bool FIRST, bool CODE>
+__global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, false, false, true, true, CODE, kChunkLean, false, kChunkLean>::kBlocksPerCu)) void k_trace_shade_tab_gray(BvhDev bvh, ShadeArgs a)
+{
+    using C            = TraceShadeCfg<FIRST, false, false, true, true, CODE, kChunkLean, false, kChunkLean>;
+    constexpr bool EXT = false, FB = false, LDS = true, TAB = kChunkLean;
+#include "small_scene_body.h"
+}
+__global__ __launch_bounds__(kBlock, (TraceShadeCfg<false, false, false, true, true, false, kChunkLean, kChunkLean, kChunkLean>::kBlocksPerCu)) void k_trace_shade_head_gray(BvhDev bvh, ShadeArgs a)
+{
+    using C              = TraceShadeCfg<false, false, false, true, true, false, kChunkLean, kChunkLean, kChunkLean>;
     constexpr bool FIRST = false, EXT = false, FB = false, LDS = true, TAB = kChunkLean;
 #include "small_scene_body.h"
 }
@@ -413,10 +435,43 @@ void launch_camera_vertices(const LaunchCfg& cfg, const BvhDev& bvh, const Shade
         hipLaunchKernelGGL(k_camera_vertices<false>, dim3(gx), dim3(kBlock), 0, cfg.stream, bvh, args, rows, tab_p, tab_n, selftest_out);
 }
 
-// The seventeen instantiations that exist, each under the tuple it was instantiated with.  Bounce 0 has no feedback form, the two
-// models and feedback exclude each other, TAME is the reference model with the scene in LDS, CODE its bounce 0 and TAB its three lean
-// kernels with the sample table (TraceShadeCfg).
-enum : uint32_t { TS_FIRST = 1, TS_EXT = 2, TS_FB = 4, TS_LDS = 8, TS_TAME = 16, TS_CODE = 32, TS_TAB = 64, TS_HEAD = 128 };
+// cap_debug_get(CAP_DEBUG_SELFTEST_GRAY): what the GRAY form rests on, looked up in a 48-byte queue a render left behind -- every entry
+// below its class's count (clamped to the capacity, as the consumers clamp it) has three bitwise equal throughput words.  out[0]: entries
+// that do not, out[1]: entries looked at.
+__global__ __launch_bounds__(kBlock) void k_gray_selftest(RayQueue q, unsigned long long* out)
+{
+    const uint32_t total = kQueueClasses * q.class_capacity;  // <= the queue's allocation (ctx_render.hip lane_sizes)
+    unsigned long long bad = 0, n = 0;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock)
+    {
+        const uint32_t klass = i / q.class_capacity, local = i - klass * q.class_capacity;
+        const uint32_t count = q.count[klass * kCounterStride];
+        bool           in = local < (count < q.class_capacity ? count : q.class_capacity), differ = false;
+        if (in)
+        {
+            const float4 tp = q.thr_pid[i];
+            differ          = f2u(tp.x) != f2u(tp.y) || f2u(tp.x) != f2u(tp.z);
+        }
+        bad += (unsigned long long)__popcll(__ballot(differ)), n += (unsigned long long)__popcll(__ballot(in));
+    }
+    if ((threadIdx.x & 63u) == 0u)
+    {
+        if (bad) atomicAdd(&out[0], bad);
+        if (n) atomicAdd(&out[1], n);
+    }
+}
+
+void launch_gray_selftest(hipStream_t stream, const RayQueue& q, unsigned long long* out_device)
+{
+    if (!q.class_capacity) return;
+    const uint32_t total = kQueueClasses * q.class_capacity;
+    hipLaunchKernelGGL(k_gray_selftest, dim3(std::min(4096u, (total + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, q, out_device);
+}
+
+// The twenty-one instantiations that exist, each under the tuple it was instantiated with.  Bounce 0 has no feedback form, the two
+// models and feedback exclude each other, TAME is the reference model with the scene in LDS, CODE its bounce 0, TAB its three lean
+// kernels with the sample table, HEAD the fourth and GRAY those four with 32-byte queue entries (TraceShadeCfg).
+enum : uint32_t { TS_FIRST = 1, TS_EXT = 2, TS_FB = 4, TS_LDS = 8, TS_TAME = 16, TS_CODE = 32, TS_TAB = 64, TS_HEAD = 128, TS_GRAY = 256 };
 struct TraceShadeKernel
 {
     uint32_t is;
@@ -427,8 +482,14 @@ constexpr TraceShadeKernel trace_shade_kernel()
 {
     if constexpr ((IS & TS_HEAD) != 0)
     {
-        static_assert(IS == (TS_LDS | TS_TAME | TS_TAB | TS_HEAD), "HEAD: the lean bounce >= 1 kernel");
-        return {IS, k_trace_shade_head};
+        static_assert((IS & ~TS_GRAY) == (TS_LDS | TS_TAME | TS_TAB | TS_HEAD), "HEAD: the lean bounce >= 1 kernel");
+        return {IS, (IS & TS_GRAY) != 0 ? k_trace_shade_head_gray : k_trace_shade_head};
+    }
+    else if constexpr ((IS & TS_GRAY) != 0)
+    {
+        static_assert((IS & ~(TS_FIRST | TS_CODE)) == (TS_LDS | TS_TAME | TS_TAB | TS_GRAY), "GRAY: the lean kernels with the sample table");
+        static_assert((IS & TS_FIRST) != 0 || (IS & TS_CODE) == 0, "CODE: bounce 0");
+        return {IS, k_trace_shade_tab_gray<(IS & TS_FIRST) != 0, (IS & TS_CODE) != 0>};
     }
     else if constexpr ((IS & TS_TAB) != 0)
     {
@@ -438,8 +499,9 @@ constexpr TraceShadeKernel trace_shade_kernel()
     else
         return {IS, k_trace_shade<(IS & TS_FIRST) != 0, (IS & TS_EXT) != 0, (IS & TS_FB) != 0, (IS & TS_LDS) != 0, (IS & TS_TAME) != 0, (IS & TS_CODE) != 0>};
 }
-// (a build without the lean plumbing, -DCAP_CHUNK_PLAIN, has no table form: trace_shade_has_table_form() says so and the last three are never looked up)
-constexpr TraceShadeKernel kTraceShadeKernels[17] = {
+// (a build without the lean plumbing, -DCAP_CHUNK_PLAIN, has no table form: trace_shade_has_table_form() says so and the last eight are never looked up)
+constexpr uint32_t         kTraceShadeKernelCount = 21;
+constexpr TraceShadeKernel kTraceShadeKernels[kTraceShadeKernelCount] = {
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_CODE>(),
     trace_shade_kernel<TS_FIRST | TS_EXT | TS_LDS>(), trace_shade_kernel<TS_FIRST | TS_EXT>(),
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME>(), trace_shade_kernel<TS_FIRST | TS_LDS>(), trace_shade_kernel<TS_FIRST>(),
@@ -448,6 +510,8 @@ constexpr TraceShadeKernel kTraceShadeKernels[17] = {
     trace_shade_kernel<TS_LDS | TS_TAME>(), trace_shade_kernel<TS_LDS>(), trace_shade_kernel<0>(),
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_CODE | TS_TAB>(), trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_TAB>(), trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB>(),
     trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB | TS_HEAD>(),
+    trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_CODE | TS_TAB | TS_GRAY>(), trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_TAB | TS_GRAY>(),
+    trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB | TS_GRAY>(), trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB | TS_HEAD | TS_GRAY>(),
 };
 
 // the unscaled forms: reference model, scene in LDS, tame shading records (-DCAP_SHADE_IEEE keeps the plain sqrtf and `/`
@@ -462,8 +526,10 @@ static bool tame_kernels(const BvhDev& bvh, const SceneDev& scene)
 }
 bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene) { return tame_kernels(bvh, scene); }
 bool trace_shade_has_table_form(const BvhDev& bvh, const SceneDev& scene) { return kChunkLean && tame_kernels(bvh, scene); }
+// the table kernels with 32-byte entries: kd = (k, k, k) at every vertex, which is what keeps a throughput's three components equal
+bool trace_shade_has_gray_form(const BvhDev& bvh, const SceneDev& scene) { return trace_shade_has_table_form(bvh, scene) && scene.texture_count == 0; }
 
-uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback, bool camera_head)
+uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback, bool camera_head, bool gray)
 {
     const bool first = args.bounce == 0;
     const bool fb    = feedback && !ext && !first;  // (bounce 0 defines the planes' entries: nothing to reuse yet)
@@ -477,12 +543,14 @@ uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const Shade
     assert(!tab || (tame && kChunkLean));
     // bounce 0 as the head of bounce 1's chunks (TraceShadeCfg HEAD): the host's condition implies the lean table form, the probe and the ring
     assert(!camera_head || (args.bounce == 1 && tab && args.inline_probe && args.wave_ring && args.in.org_tmin && args.in.dir_tmax && args.in.thr_pid));
+    // 32-byte entries: like the table, every launch of a batch or none (the host's condition: the table form and trace_shade_has_gray_form())
+    assert(!gray || (tab && args.scene.texture_count == 0));
     const uint32_t is = (first ? TS_FIRST : 0u) | (ext ? TS_EXT : 0u) | (fb ? TS_FB : 0u) | (lds ? TS_LDS : 0u) | (tame ? TS_TAME : 0u) | (code ? TS_CODE : 0u) | (tab ? TS_TAB : 0u) |
-                        (camera_head ? TS_HEAD : 0u);
+                        (camera_head ? TS_HEAD : 0u) | (gray ? TS_GRAY : 0u);
     // the queue's persistent grid; bounce 0's queue is the identity queue of the batch, one entry per padded pixel and frame slot
     const uint32_t gx = queue_grid(cfg, (first || camera_head) ? args.screen.pixels_padded * args.n_slots : args.max_count);
     const TraceShadeKernel* k = kTraceShadeKernels;
-    while (k->is != is && k + 1 < kTraceShadeKernels + 17) ++k;
+    while (k->is != is && k + 1 < kTraceShadeKernels + kTraceShadeKernelCount) ++k;
     assert(k->is == is);  // the table holds every tuple the lines above can derive
     hipLaunchKernelGGL(k->kernel, dim3(gx), dim3(kBlock), 0, cfg.stream, bvh, args);
     // the kernel's own conditions: the marked loop where it calls exhaustive_closest_marked, the carry chain where that takes it

@@ -1,6 +1,6 @@
-// small_scene_body.h -- the body of the fused small-scene kernels, included by k_trace_shade, k_trace_shade_tab and k_trace_shade_head
-// (small_scene.hip) and by nothing else.  It reads the kernel's arguments `bvh` and `a`, its configuration type C (a TraceShadeCfg) and the
-// flags FIRST, EXT, FB, LDS and TAB as names; no include guard, on purpose.  (What belongs to the third kernel alone stands under C::HEAD.)  Text and not a function: wrapped in a device function the thirteen kernels without the sample table no longer
+// small_scene_body.h -- the body of the fused small-scene kernels, included by k_trace_shade, k_trace_shade_tab, k_trace_shade_head and the
+// latter two's 32-byte-entry forms k_trace_shade_tab_gray and k_trace_shade_head_gray (small_scene.hip) and by nothing else.  It reads the kernel's arguments `bvh` and `a`, its configuration type C (a TraceShadeCfg) and the
+// flags FIRST, EXT, FB, LDS and TAB as names; no include guard, on purpose.  (What belongs to the head kernels alone stands under C::HEAD, what the 32-byte forms change under C::GRAY and in the type C::Thr.)  Text and not a function: wrapped in a device function the thirteen kernels without the sample table no longer
 // compile to the instructions they had (tools/isa_compare.py against the commit before the table), which is what lets the switch
 // CAP_SAMPLE_TABLE = 0 stand for that commit in a measurement.
     const uint32_t Ppad     = a.screen.pixels_padded;
@@ -121,7 +121,7 @@
         uint32_t       i, pid = 0, slot = 0;
         const uint32_t klass = my_class;      // the path's class for its whole life
         bool           active;
-        v3             thr = mk3(1.0f, 1.0f, 1.0f);
+        typename C::Thr thr = thr_of<typename C::Thr>(1.0f, 1.0f, 1.0f);  // (GRAY: one float, see TraceShadeCfg)
         Ray            r   = make_ray(mk3(0.f, 0.f, 0.f), mk3(0.f, 0.f, 1.f), 0.0f, 0.0f);  // empty interval: hits nothing
         float          carried_r1 = 0.f, carried_r2 = 0.f;
         if constexpr (C::HEAD)
@@ -188,7 +188,7 @@
             active = emit_ext;
             if (__ballot(active) == 0ull) continue;  // no lane of the wave has a ray: no loop, nothing to shade
             r   = make_ray(p, dir, kRayEps, kRayFar);
-            thr = mk3(f, f, f);
+            thr = thr_of<typename C::Thr>(f, f, f);
         }
         else if (FIRST)
         {
@@ -218,11 +218,22 @@
                 // frame slot's rows -- it indexes with that real, in-range slot.
                 const uint32_t local = j * 64u + lane;
                 i                    = my_class * a.in.class_capacity + (local < n_class ? local : n_class - 1u);
-                const float4 o = a.in.org_tmin[i], d = a.in.dir_tmax[i], tp = a.in.thr_pid[i];
-                grab = grab_issue(a.work, my_class);
-                r    = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), kRayEps, kRayFar);
-                thr  = mk3(tp.x, tp.y, tp.z), pid = f2u(tp.w);
-                if (!TAB) carried_r1 = o.w, carried_r2 = d.w;  // (TAB: the constants kRayEps / kRayFar again, not read)
+                if constexpr (C::GRAY)
+                {
+                    // the 32-byte entry: (o.xyz, thr) (d.xyz, asfloat(pid)); a lane past the end loads the last entry from these two arrays
+                    const float4 o = a.in.org_tmin[i], d = a.in.dir_tmax[i];
+                    grab = grab_issue(a.work, my_class);
+                    r    = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), kRayEps, kRayFar);
+                    thr  = thr_of<typename C::Thr>(o.w, o.w, o.w), pid = f2u(d.w);
+                }
+                else
+                {
+                    const float4 o = a.in.org_tmin[i], d = a.in.dir_tmax[i], tp = a.in.thr_pid[i];
+                    grab = grab_issue(a.work, my_class);
+                    r    = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), kRayEps, kRayFar);
+                    thr  = thr_of<typename C::Thr>(tp.x, tp.y, tp.z), pid = f2u(tp.w);
+                    if (!TAB) carried_r1 = o.w, carried_r2 = d.w;  // (TAB: the constants kRayEps / kRayFar again, not read)
+                }
             }
             else
             {
@@ -234,7 +245,7 @@
                 if (active)
                 {
                     r   = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), kRayEps, kRayFar);
-                    thr = mk3(tp.x, tp.y, tp.z), pid = f2u(tp.w);
+                    thr = thr_of<typename C::Thr>(tp.x, tp.y, tp.z), pid = f2u(tp.w);
                     carried_r1 = o.w, carried_r2 = d.w;
                 }
             }
@@ -292,10 +303,10 @@
                     const float4 q = a.in.acc[i];
                     acc            = mk3(q.x, q.y, q.z);
                 }
-                shade_vertex_ext<FIRST, true>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr, r.d, n_shaded, &bvh, acc, xtabs);
+                shade_vertex_ext<FIRST, true>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr3(thr), r.d, n_shaded, &bvh, acc, xtabs);
             }
             else
-                shade_vertex_ext<FIRST>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr, r.d, n_shaded, nullptr, mk3(0.f, 0.f, 0.f), xtabs);
+                shade_vertex_ext<FIRST>(a, shade_tab, pre, klass, pid, make_float4(u, v, u2f(gid), t), thr3(thr), r.d, n_shaded, nullptr, mk3(0.f, 0.f, 0.f), xtabs);
         }
         else
         {

@@ -320,6 +320,15 @@ enum
      * differ in any bit << 32 | groups << 16 | frame slots compared. */
     CAP_DEBUG_CAMERA_TABLE          = 18,
     CAP_DEBUG_SELFTEST_CAMERA_TABLE = 19,
+    /* GRAY_ENTRIES (get): 1 if the fused small-scene launches of the last cap_render used 32-byte extension-queue entries -- (origin,
+     * throughput) (direction, path id), the throughput being one float -- and 0 if they used the 48-byte entries with three throughput
+     * words (the switch CAP_NO_GRAY_ENTRIES, a scene with textures, every render without the sample table).  Same bits and the same
+     * CapStats either way: without textures the three components of a throughput are the same operations on the same operands.
+     * SELFTEST_GRAY (get, right after a render in the 48-byte form on the small-scene path): that premise on the device -- every entry the
+     * last batch left in its two extension queues, up to the class counts: entries whose three throughput words are not bitwise equal
+     * << 32 | entries looked at (saturating at 2^32 - 1). */
+    CAP_DEBUG_GRAY_ENTRIES          = 20,
+    CAP_DEBUG_SELFTEST_GRAY         = 21,
     /* A/B and diagnostic switches of the build and render paths (which kernels trace the camera and the shadow rays, one or two batch
      * lanes, the builders' parameters ...): ONE table per context, key = SWITCH_BASE + cap_debug_switch_index("CAP_..."), the names being
      * the environment variables that fill the table once, at cap_ctx_create (tools set those around a whole process; nothing else in the
