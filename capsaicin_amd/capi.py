@@ -165,6 +165,11 @@ class Closest(C.Structure):
                 ("feature", C.c_uint32)]
 
 
+class BoxDesc(C.Structure):
+    """CapBoxDesc (32 bytes): an axis-aligned box, lo and hi corner; the pad words are not read."""
+    _fields_ = [("lo", C.c_float * 3), ("pad0", C.c_float), ("hi", C.c_float * 3), ("pad1", C.c_float)]
+
+
 FEATURE_FACE, FEATURE_EDGE_V0V1, FEATURE_EDGE_V1V2, FEATURE_EDGE_V2V0, FEATURE_V0, FEATURE_V1, FEATURE_V2 = range(7)  # CAP_FEATURE_*
 
 
@@ -305,6 +310,7 @@ SYMBOLS = {
     "cap_trace_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_closest_points": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_points_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
+    "cap_overlap_boxes": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_pseudonormals_build": (_i, [_vp, C.POINTER(PseudonormalsInfo)]),
     "cap_pseudonormals_drop": (_i, [_vp]),
     "cap_pseudonormals_readback": (_i, [_vp, _vp]),
@@ -830,10 +836,10 @@ class Renderer:
         return tuple(res) if second else res[0]
 
     def _multi(self, name, records, width, what, cols, instanced, k, counts, resume, sync, tail):
-        """Up to k results per ray or point through the entry point `name`: a page of (N, k, cols) float32 records and, instanced, one
-        of (N, k) int32 instances -- resume= is the previous call's page or, instanced, pair of pages --, then the (N,) int32 counts
-        with counts=True; `tail` is what the entry point takes behind the multi flags.  Returns the page alone where there is nothing
-        else, else the tuple"""
+        """Up to k results per ray, point or box through the entry point `name`: a page of (N, k, cols) float32 records (cols = 0: of
+        (N, k) int32 ids) and, instanced, one of (N, k) int32 instances -- resume= is the previous call's page or, instanced, pair of
+        pages --, then the (N,) int32 counts with counts=True; `tail` is what the entry point takes behind the multi flags.  Returns
+        the page alone where there is nothing else, else the tuple"""
         import torch
         if not instanced:
             given, names = [resume], ("resume",)
@@ -845,7 +851,8 @@ class Renderer:
         dev, records, n = self._stage_records(records, width, what)
         k = self._page_size(k, counts, resume is not None)
         pages, host_pages = [], []
-        for page, page_name, (shape, dtype) in zip(given, names, (((n, k, cols), torch.float32), ((n, k), torch.int32))):
+        first = ((n, k, cols), torch.float32) if cols else ((n, k), torch.int32)
+        for page, page_name, (shape, dtype) in zip(given, names, (first, ((n, k), torch.int32))):
             page, mine = self._resume_page(page, shape, dtype, dev, page_name)
             pages.append(page)
             host_pages.append(mine)
@@ -1070,6 +1077,41 @@ class Renderer:
         next pages over both.  closest_triangles() reads the (N, k) ids and features.  points, sync and mask= as closest_points; numpy
         points (or numpy resume pages) give numpy results."""
         return self._multi("cap_closest_instances_multi", points, 4, "points", 8, True, k, counts, resume, sync, (self.trace_options(None, mask),))
+
+    # ---- box overlap queries (cap_overlap_boxes) ----
+    def overlap_boxes(self, boxes, k, counts=False, resume=None, sync=True, mask=None):
+        """The triangles that meet each closed axis-aligned box, the first k by triangle id (cap_overlap_boxes).  boxes: (N, 8) float32
+        = CapBoxDesc rows (lo, -, hi, -; columns 3 and 7 are not read), a contiguous torch tensor on this context's device or a numpy
+        array (staged through torch; the results come back as numpy).  Returns (N, k) int32 ids, -1 in the slots after a box's last
+        triangle.  counts=True also returns the number of ALL triangles that meet each box, (N,) int32 (k = 0: counts only, the ids are
+        (N, 0)).  resume=<previous page> (the (N, k) result of a call with the same boxes) continues after it with CAP_MULTI_CONTINUE,
+        writes the next page over it and returns it.  sync and mask= as closest_points."""
+        return self._multi("cap_overlap_boxes", boxes, 8, "boxes", 0, False, k, counts, resume, sync, (self.trace_options(None, mask),))
+
+    def voxel_occupancy(self, origin, cell, dims, mask=None):
+        """Surface voxelisation: the number of triangles that meet each cell of the grid of dims = (nx, ny, nz) cubes of edge `cell`
+        from `origin`, as a (nx, ny, nz) int32 tensor on this context's device (cap_overlap_boxes, counts only).  Per axis cell i spans
+        lo = fl(origin + fl(i * cell)) to hi = fl(origin + fl((i + 1) * cell)) in float32, so neighbours share their faces exactly and
+        a triangle lying in a shared face counts in both cells."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        dims = tuple(int(d) for d in dims)
+        if len(dims) != 3 or min(dims) < 1:
+            raise CapError("dims must be three positive cell counts, got %r" % (dims,))
+        origin = [float(o) for o in origin]
+        if len(origin) != 3:
+            raise CapError("origin must be three coordinates, got %r" % (origin,))
+        step = torch.tensor(float(cell), dtype=torch.float32, device=dev)
+        boxes = torch.zeros(dims + (8,), dtype=torch.float32, device=dev)
+        for axis, d in enumerate(dims):
+            o = torch.tensor(origin[axis], dtype=torch.float32, device=dev)
+            edges = o + torch.arange(d + 1, dtype=torch.float32, device=dev) * step  # (one rounded product, one rounded sum)
+            shape = [1, 1, 1]
+            shape[axis] = d
+            boxes[..., axis] = edges[:-1].reshape(shape)
+            boxes[..., 4 + axis] = edges[1:].reshape(shape)
+        _, cnt = self.overlap_boxes(boxes.reshape(-1, 8), 0, counts=True, mask=mask)
+        return cnt.reshape(dims)
 
 
     # ---- instanced ray queries (cap_instances_set, cap_trace_instances*) ----

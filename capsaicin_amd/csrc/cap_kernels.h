@@ -234,6 +234,23 @@ struct ClosestInstMultiArgs
 void launch_closest_instances_multi(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstMultiArgs& m, const TlasDev& tl, const RayFilter& f,
                                     uint32_t depth);
 
+// Box overlap queries (cap_overlap_boxes, overlap.hip k_overlap_boxes): boxes = CapBoxDesc records (two float4: lo, hi; the w words are
+// not read), out = pages of k triangle ids per box (NULL when k = 0), counts = n candidate counts or NULL, resume: slot k - 1 of each
+// page is the cursor (CAP_MULTI_CONTINUE).  slack: what the query box is grown by before it is compared with the node boxes,
+// kClosestSlackScale x the largest coordinate magnitude of the scene bounds (DESIGN.md "Box overlap queries").  depth and f as
+// launch_closest_points'; the list capacity is multi_bucket(k) >= k.
+struct OverlapArgs
+{
+    const float4* boxes;
+    uint32_t      n;
+    uint32_t*     out;
+    uint32_t      k;
+    uint32_t*     counts;
+    uint32_t      resume;
+    float         slack;
+};
+void launch_overlap_boxes(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapArgs& a, const RayFilter* f, uint32_t depth);
+
 // ---- instances (instance.hip): cap_instances_set, cap_trace_instances* ----
 // The table on the device.  rec: 4 float4 per instance = the three rows of W (world to object, row r = (W_r0, W_r1, W_r2, W_r3)) and
 // (asfloat(mask), asfloat(root of the object's tree), asfloat(object index), -); an inert instance has W = 0 and mask 0.  box: 2 float4 per instance = (lo.xyz, k) (hi.xyz, asfloat(index)),

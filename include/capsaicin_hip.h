@@ -603,6 +603,60 @@ int cap_closest_points(CapContext* ctx, const CapPointDesc* device_points, uint6
 int cap_closest_points_multi(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out,
                              uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options /* may be NULL */);
 
+/* ---- box overlap queries: the triangles that meet an axis-aligned box (collision broad phase, voxelisation, selection, clipping) ----
+ * For every box the triangles of the uploaded scene that meet the CLOSED box [lo, hi], on the scene's binary tree: the first k of them
+ * by triangle id, their number, or both, with cap_closest_points_multi's pages, counts, paging and masks.  Current under
+ * cap_scene_update_vertices + cap_bvh_refit like every other query.
+ *
+ * The predicate is the separating-axis test of a triangle and a box (Akenine-Moller 2001) with all 13 axes, defined on the STORED
+ * record (v0, e1, e2) as cap_closest_points' function is.  Every operation is one rounded binary32 operation in the order written, there
+ * is no fused multiply-add, dot is the point queries' dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z -- so a plain float32 brute force is
+ * bit-identical to the kernel.  Let a = v0, b = fl(v0 + e1), c = fl(v0 + e2).  The triangle meets the box unless one of these separates
+ * them (each is a pure comparison, the order of evaluation is free):
+ *   1. Box axes, absolute coordinates, exact comparisons: for x, y, z:  min(a_x, b_x, c_x) > hi_x  or  max(a_x, b_x, c_x) < lo_x.
+ *   2. The centred frame, component-wise: hl = lo*0.5, hh = hi*0.5, ctr = hl + hh, h = hh - hl (neither overflows for finite input);
+ *      P0 = a - ctr, P1 = b - ctr, P2 = c - ctr; edges f0 = e1, f1 = P2 - P1, f2 = P0 - P2.
+ *   3. Nine cross axes: for each edge f and each coordinate pair (m, n) in {(y, z), (z, x), (x, y)}:
+ *        s_j = f_m*P_j,n - f_n*P_j,m for j = 0, 1, 2 (all three are evaluated),  r = h_m*|f_n| + h_n*|f_m|;
+ *        min(s_0, s_1, s_2) > r  or  max(s_0, s_1, s_2) < -r.
+ *   4. The triangle's plane: n = (e1_y*e2_z - e1_z*e2_y, e1_z*e2_x - e1_x*e2_z, e1_x*e2_y - e1_y*e2_x), d = dot(n, P0),
+ *        r = (h_x*|n_x| + h_y*|n_y|) + h_z*|n_z|;  d > r  or  d < -r.
+ * min and max hand a NaN on, and a NaN fails its comparison: an axis with a NaN among its values separates nothing ("min > r" reads
+ * "all three > r").  Touching is overlap: a box face coplanar with a triangle, a box that shares only an edge or a corner with it, a
+ * point box (lo == hi) on a vertex or in the face all count; one ulp back they do not.  A zero-area triangle is a segment or a point
+ * to the axes above and is listed where that meets the box.
+ *
+ * The answer.  A box's candidates are the triangles that pass the mask filter (the mesh-mask table and instance_mask, exactly as in
+ * cap_closest_points) and the predicate, sorted by triangle id ascending.  device_triangles[i * k + j], j < k, is box i's j-th
+ * candidate; slots after the last hold 0xFFFFFFFF.  device_counts: NULL, or n uint32: the number of ALL candidates of box i, not capped
+ * at k (with CAP_MULTI_CONTINUE: of those above the cursor).  k = 0 counts only: device_triangles must be NULL and device_counts given.
+ * The answer depends on neither the tree, nor the builder, nor the visiting order.
+ *
+ * Paging (CAP_MULTI_CONTINUE): on entry, slot k - 1 of each box's page is read as the cursor g_c; only candidates with id > g_c count
+ * and are listed, and the next page is written over the old one.  A page that was not full ends in 0xFFFFFFFF, which admits nothing:
+ * that box's next page is empty.  Calling again with the same boxes and buffer walks every candidate exactly once.
+ *
+ * Degenerate boxes -- a non-finite coordinate, or lo > hi on some axis -- are not traversed: a page of 0xFFFFFFFF and count 0, with
+ * CAP_MULTI_CONTINUE too.  lo = -FLT_MAX, hi = FLT_MAX is a legal box and lists everything.  The pad words are not read.
+ *
+ * Conventions and errors are cap_closest_points_multi's: device pointers on the context's GPU, boxes 16-byte and ids and counts 4-byte
+ * aligned, ranges that do not overlap; asynchronous on the context stream and ordered behind a render's second lane; n above 2^24 split
+ * into launches, n = 0 does nothing; nothing of the render's state is touched; nothing is written on an error.  CAP_ERR_STATE before
+ * cap_bvh_build and while the trees are stale; CAP_ERR_INVALID_ARG for any ray_flags bit, non-zero reserved words,
+ * instance_mask > 0xFF, unknown multi flags, k > CAP_MULTI_MAX_K, k = 0 with a page given or counts NULL, CAP_MULTI_CONTINUE with
+ * k = 0, NULL boxes (or page with k > 0), misaligned or overlapping ranges, and n * k ids beyond the address space.
+ * Not covered: instances and objects (the boxes are in the scene's own space), oriented boxes, a lower bound from the cursor (a later
+ * page walks the whole box again), per-box masks. */
+typedef struct CapBoxDesc /* 32 B, 16-byte aligned */
+{
+    float lo[3];
+    float pad0; /* not read */
+    float hi[3];
+    float pad1; /* not read */
+} CapBoxDesc;
+int cap_overlap_boxes(CapContext* ctx, const CapBoxDesc* device_boxes, uint64_t n, uint32_t k, uint32_t* device_triangles /* n*k ids */,
+                      uint32_t* device_counts /* n or NULL */, uint32_t multi_flags, const CapTraceOptions* options /* may be NULL */);
+
 /* ---- instanced ray queries: N transformed instances of the uploaded scene, or of objects of it, under a device-built top-level tree ----
  * The uploaded scene and the trees cap_bvh_build makes of it are read as OBJECT space; cap_instances_set installs a table of N
  * instances of it, each with an object-to-world transform and an 8-bit mask, and builds a top-level tree (TLAS) over the instances'

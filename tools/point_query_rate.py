@@ -46,6 +46,11 @@ off pruning by the k-th distance; K = 0 needs it); the line then also carries k,
 or without --counts the mean number of records listed per point (at most K).  `hits` and `mean_dist` are those of slot 0.  Without
 --k the tool runs cap_closest_points as before.  --radius-frac F sets the radius to F x the scene's size.
 
+--boxes runs cap_overlap_boxes on cubes of half-extent --extent E x the scene's size (default 0.005) around the same point sets, pages
+of --k K ids (default 4; --counts: with the candidate counts, which cost the walk nothing): mboxes_per_s, mean_candidates and the share
+of empty boxes.  Beside it, measured in the same process, the nearest existing workload: cap_closest_points_multi with counts at the
+same K on the same centres, at the radius that gives the same mean candidate count (found by bisection: closest_multi_counts_*).
+
 Point sets, each of --points points (rounded down to a cube for the grid):
   grid      a regular grid through the scene's box, in raster order (x fastest);
   shuffled  the same points in random order;
@@ -112,7 +117,13 @@ def main():
     ap.add_argument("--signed", action="store_true")
     ap.add_argument("--winding", action="store_true")
     ap.add_argument("--beta", type=float, default=2.0)
+    ap.add_argument("--boxes", action="store_true")
+    ap.add_argument("--extent", type=float, default=0.005)
     a = ap.parse_args()
+    if a.boxes and (a.winding or a.signed or a.instances is not None):
+        ap.error("--boxes goes with --k, --counts and --extent only")
+    if a.boxes and a.k is None:
+        a.k = 4  # (before `out` below is sized: the comparison run writes pages of k records into it)
     if a.winding and (a.signed or a.k is not None):
         ap.error("--winding goes alone or with --instances N: the winding number takes no sign table or pages")
     if a.signed and a.k is not None:
@@ -134,7 +145,7 @@ def main():
     size = float((hi - lo).max())
     if a.radius_frac is not None:
         a.radius = a.radius_frac * size
-    if a.counts and a.k is None:
+    if a.counts and a.k is None and not a.boxes:
         ap.error("--counts needs --k")
     side = int(round(a.points ** (1.0 / 3.0)))
     while side ** 3 > a.points:
@@ -195,6 +206,48 @@ def main():
                                   mean_visits=[round(float(mean[0]), 2), round(float(mean[1]), 2)], inside=round(float((w >= 0.5).float().mean()), 4),
                                   table_build_ms=round(wn.ms, 3), bvh_build_ms=round(info.build_ms, 3),
                                   table={k: v for k, v in wn.as_dict().items() if k != "ms"})), flush=True)
+        r.close()
+        return
+    if a.boxes:
+        k = a.k
+        if k == 0 and not a.counts:
+            ap.error("--boxes --k 0 needs --counts")
+        half = a.extent * size
+        ids = torch.empty((n * max(k, 1),), dtype=torch.int32, device=dev)
+        box_cnt, near_cnt = torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+        head.update(k=k, counts=a.counts, extent=a.extent)
+        del head["radius"]
+        for name, xyz in sets:
+            b = np.zeros((n, 8), np.float32)
+            b[:, 0:3], b[:, 4:7] = xyz - half, xyz + half
+            boxes = torch.as_tensor(b, device=dev).contiguous()
+            q = np.zeros((n, 4), np.float32)
+            q[:, 0:3] = xyz
+            torch.cuda.synchronize()
+            sec = timed(r, lambda: capi._check(L.cap_overlap_boxes(r.ctx, boxes.data_ptr(), n, k, ids.data_ptr() if k else None,
+                                                                   box_cnt.data_ptr() if a.counts else None, 0, None), "cap_overlap_boxes"), a.reps, a.warmup)
+            capi._check(L.cap_overlap_boxes(r.ctx, boxes.data_ptr(), n, 0, None, box_cnt.data_ptr(), 0, None), "cap_overlap_boxes")
+            r.sync()
+            mean = float(box_cnt.double().mean())
+            # the nearest existing workload: cap_closest_points_multi --counts at the radius with the same mean candidate count (bisection)
+            rlo, rhi = 0.0, 4.0 * half
+            for _ in range(16):
+                q[:, 3] = 0.5 * (rlo + rhi)
+                pts = torch.as_tensor(q, device=dev).contiguous()
+                torch.cuda.synchronize()
+                capi._check(L.cap_closest_points_multi(r.ctx, pts.data_ptr(), n, 0, None, near_cnt.data_ptr(), 0, None), "cap_closest_points_multi")
+                r.sync()
+                if float(near_cnt.double().mean()) < mean:
+                    rlo = 0.5 * (rlo + rhi)
+                else:
+                    rhi = 0.5 * (rlo + rhi)
+            near_mean = float(near_cnt.double().mean())
+            near_sec = timed(r, lambda: capi._check(L.cap_closest_points_multi(r.ctx, pts.data_ptr(), n, k, out.data_ptr() if k else None, near_cnt.data_ptr(), 0, None),
+                                                    "cap_closest_points_multi"), a.reps, a.warmup)
+            print(json.dumps(dict(head, set=name, ms=round(sec * 1e3, 3), mboxes_per_s=round(n / sec / 1e6, 2), mean_candidates=round(mean, 3),
+                                  empty=round(float((box_cnt == 0).float().mean()), 4), closest_multi_counts_radius=float(q[0, 3]),
+                                  closest_multi_counts_mean_candidates=round(near_mean, 3), closest_multi_counts_ms=round(near_sec * 1e3, 3),
+                                  closest_multi_counts_mpoints_per_s=round(n / near_sec / 1e6, 2), ratio_to_closest_multi_counts=round(near_sec / sec, 3))), flush=True)
         r.close()
         return
     if a.k is not None:
