@@ -282,6 +282,7 @@ SYMBOLS = {
     "cap_debug_get": (_i, [_vp, _u32, C.POINTER(_u64)]),
     "cap_debug_switch_index": (_i, [C.c_char_p]),
     "cap_debug_pair_ids_dense": (_i, [_vp, _u32, _u32, _u32]),
+    "cap_debug_head_chunk": (_i, [_u32, _u32, _vp, _u32, _vp, _u64, _vp, _vp]),
     "cap_debug_query_ranges": (_i, [_u64, _u32, _vp, _vp, _vp]),
     "cap_debug_closest_instance_bound": (_i, [_vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "cap_render": (_i, [_vp, _u32, _u32, _u32, _u32]),
@@ -672,6 +673,8 @@ class Renderer:
     DEBUG_CAMERA_TABLE = 18  # 1: the last render ran bounce 0 inside bounce 1's launch, from the per-batch table of camera vertices
     DEBUG_SELFTEST_CAMERA_TABLE = 19  # mismatching entries << 32 | jitter groups << 16 | frame slots of the last batch compared
     DEBUG_GRAY_ENTRIES = 20  # 1: the last render's fused launches used 32-byte extension entries (one throughput word)
+    DEBUG_GROUP_WALK = 22  # slots per jitter group if the last batch's head kernel walked bounce 0's chunks group by group, 0: slot-major
+    DEBUG_CAMERA_TABLE_REUSED = 23  # 1: the last batch found its camera-vertex table built from the same inputs and launched no builder
     DEBUG_SELFTEST_GRAY = 21  # after a 48-byte render: entries with unequal throughput words << 32 | entries of the last batch's queues looked at
 
     def debug_set(self, key, value):

@@ -244,6 +244,25 @@ struct CapContext
         const FrameConst* frames = nullptr;
         uint32_t          n_slots = 0, n_groups = 0, lane = 0;
     } last_camera;
+    uint32_t      last_group_walk = 0;         // slots per jitter group if the last batch's head kernel took the group walk, 0: slot-major (CAP_DEBUG_GROUP_WALK)
+    uint32_t      last_camera_reused = 0;      // 1: the last batch of the last cap_render found its lane's camera-vertex table built (CAP_DEBUG_CAMERA_TABLE_REUSED)
+    // Everything a lane's camera-vertex table was built from (ctx_render.hip render_batch compares it bit for bit before it builds): what
+    // camera_vertex() and stage_camera_pairs() read -- camera, screen and shard, each group's jitter, the switches behind
+    // cull_camera_pairs, the scene's records by their generation and counts -- and where the table lies.  valid == false: build.
+    struct CameraTableKey
+    {
+        bool          valid = false;
+        CameraDev     cam{};
+        ScreenDev     screen{};
+        uint32_t      n_groups = 0, lane = 0, cull_camera_pairs = 0, tri_count = 0, fan_pair_count = 0, fan_single_count = 0, tri_ids_dense = 0;
+        uint32_t      kd_untextured = 0;       // its bits
+        uint32_t      jitter[kMaxFrameSlots][2] = {};  // (jitter_x, jitter_y) bits of each group's first slot, in group order
+        const float4* table = nullptr;         // Lane::camera's buffer and size: a regrown buffer is another table
+        size_t        table_n = 0;
+        const void*   records[4] = {};         // shade_tris, tris_by_id, fan_pairs, fan_singles
+        uint64_t      scene_generation = 0;
+    } camera_key[2];                           // per lane
+    uint64_t      scene_generation = 0;        // bumped by every entry point that can change a record the table's builder reads
     uint32_t      last_gray_entries = 0;       // 1: the last cap_render's fused launches used 32-byte extension entries (CAP_DEBUG_GRAY_ENTRIES)
     struct LastQueues                          // what the last batch of a 48-byte render left in the extension queues (CAP_DEBUG_SELFTEST_GRAY)
     {
@@ -265,7 +284,7 @@ struct CapContext
     {
         hipStream_t      stream = nullptr;  // not owned: the context's `stream` (lane 0) or `stream2` (lane 1)
         DevBuf<float4>   hits, q_org[2], q_dir[2], q_thr[2], s_org, s_dir, s_con, pl_color, pl_direct, pl_albedo;
-        DevBuf<float4>   camera;       // per batch: camera vertices, two planes [jitter group][Ppad] (launch_camera_vertices), if the form is on
+        DevBuf<float4>   camera;       // camera vertices, two planes [jitter group][Ppad] (launch_camera_vertices), if the form is on; kept from batch to batch (camera_key)
         DevBuf<float4>   terms;        // per batch: direction-sample terms [sampling bounce][slot][4096] (ShadeArgs::sample_terms), if the form is on
         DevBuf<uint32_t> counters;     // per batch: CounterLayout
         DevBuf<uint32_t> stack_spill;  // traversal-stack entries beyond the LDS part, per thread of the persistent grid

@@ -154,6 +154,41 @@ __host__ __device__ __forceinline__ uint32_t tile_div(uint32_t n, uint32_t mul, 
 #endif
 }
 
+// The group walk of the head kernels (small_scene_body.h under C::HEAD): which (frame slot, 64-pixel group) the dealt chunk index c of
+// bounce 0's identity queue stands for.  Slot-major, c = slot * cps + group64, the slots of a jitter group read one camera-table entry
+// a whole slot's sweep apart; here they read it back to back.  With m slots in every group and `order` the batch's slots sorted by
+// group (stable), the indices are cut into bands of m * cps -- one band per group, so that no more than m slots' sample-term blocks are
+// hot at once -- and inside a band the m members of a 64-pixel group follow each other:
+//   band = c / (m * cps), r = c % (m * cps), group64 = r / m, slot = order[band * m + r % m].
+// m = 1 with the identity order is the slot-major walk (groups of unequal sizes take it).  A bijection of [0, cps * n_slots) onto itself
+// for every permutation `order` of the n_slots = bands * m slots: the path's class stays chunk_class(c) of the DEALT index, class_chunk()
+// and the grab counters are untouched, and every class still receives ceil(chunks / 64) chunks -- the static capacity argument at kQueueClasses
+// asks nothing else of what a chunk index means.  Both divisions in tile_div()'s form (c < cps * n_slots <= 2^20 * 64 = 2^26).
+struct HeadWalk
+{
+    uint32_t m_shifts;              // m | shift of the division by m * cps << 8 | shift of the division by m << 16
+    uint32_t band_mul, member_mul;  // tile_div()'s multipliers of the two divisions
+    uint32_t order[kMaxFrameSlots / 4];  // the slots in walk order, one byte each
+};
+__host__ __device__ __forceinline__ void head_chunk(const HeadWalk& w, uint32_t cps, uint32_t c, uint32_t& slot, uint32_t& group64)
+{
+    const uint32_t m = w.m_shifts & 0xffu, band = tile_div(c, w.band_mul, (w.m_shifts >> 8) & 0xffu);
+    const uint32_t r = c - band * (m * cps);
+    group64 = tile_div(r, w.member_mul, (w.m_shifts >> 16) & 0xffu);
+    const uint32_t at = band * m + (r - group64 * m);
+    slot = (w.order[(at >> 2) & (kMaxFrameSlots / 4 - 1u)] >> ((at & 3u) * 8u)) & 0xffu;
+}
+inline HeadWalk head_walk(uint32_t m, uint32_t cps, const uint8_t* order, uint32_t n_slots)
+{
+    HeadWalk w{};
+    uint32_t s_band, s_member;
+    tile_div_setup(m * cps, w.band_mul, s_band);
+    tile_div_setup(m, w.member_mul, s_member);
+    w.m_shifts = m | (s_band << 8) | (s_member << 16);
+    for (uint32_t k = 0; k < n_slots && k < kMaxFrameSlots; ++k) w.order[k >> 2] |= (uint32_t)order[k] << ((k & 3u) * 8u);
+    return w;
+}
+
 __device__ __forceinline__ bool local_pixel_to_xy(const ScreenDev& sc, uint32_t pl, uint32_t& x, uint32_t& y)
 {
     const uint32_t lt = pl >> 6, w = pl & 63u;

@@ -44,6 +44,8 @@ enum CapSwitch : uint32_t
     SW_SAMPLE_TABLE,        // small-scene path, reference model: 0 never, 1 whenever the kernels have the form: direction-sample terms from the batch's table (ShadeArgs::sample_terms)
     SW_NO_CAMERA_TABLE,     // small-scene path, reference model: bounce 0 stays a launch of its own (no camera-vertex table, no bounce-0 head in bounce 1's launch)
     SW_NO_GRAY_ENTRIES,     // small-scene path, sample-table kernels, untextured scene: the extension queue keeps its 48-byte entries (three throughput words)
+    SW_NO_GROUP_WALK,       // head kernels: bounce 0's chunk indices walk the identity queue slot-major (no bands of jitter groups, cap_device.h head_chunk)
+    SW_NO_TABLE_REUSE,      // every batch rebuilds its camera-vertex table, whether or not its inputs changed (ctx_render.hip CameraTableKey)
     SW_COUNT
 };
 struct SwitchTable
@@ -340,7 +342,14 @@ struct ShadeArgs
     uint32_t          aov_slot;    // frame slot whose AOVs are kept, or ~0u
     uint64_t*         shaded_counter;
     uint32_t*         work;        // fused kernels: kQueueClasses chunk-grab counters of this launch (zeroed), kCounterStride apart
-    FeedbackDev       fb;          // read only by the feedback variants
+    // Eighty bytes, two readers that never meet (like hits / sample_terms above: the kernel arguments of every kernel stay as they were):
+    // the feedback variants read `fb`, the head kernels -- reference model without feedback -- read `walk`, the order in which bounce 0's
+    // chunk indices visit the batch's (frame slot, 64-pixel group) pairs (cap_device.h head_chunk; set per batch by render_batch)
+    union
+    {
+        FeedbackDev   fb;
+        HeadWalk      walk;
+    };
     // untextured scene, reference shading, accumulate-only render (nobody but the resolve reads the planes): the first vertex's albedo
     // is one of four constants, so the albedo plane is not used and direct.w carries a code instead of 1 (cap_shade.h shade_vertex)
     uint32_t          albedo_in_w;
@@ -371,6 +380,7 @@ struct ShadeArgs
     // its own terms.  All launches of a batch take the same form (launch_trace_shade); the last bounce samples nothing and reads
     // nothing through it.
 };
+static_assert(sizeof(HeadWalk) <= sizeof(FeedbackDev), "ShadeArgs::walk must not grow the kernel arguments");
 // The first vertex's code (direct.w under albedo_in_w, color.w under code_in_color).  Three places must agree on it: shade_vertex
 // (the plane's word, and under CODE the spare word of a bounce-0 shadow entry), store_first_direct (+ kCodeLit) and the resolves.
 constexpr float kCodePadding = 0.f, kCodeSky = 1.f, kCodeKd = 2.f, kCodeBlack = 3.f;

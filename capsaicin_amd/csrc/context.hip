@@ -276,7 +276,7 @@ static const char* const kSwitchNames[SW_COUNT] = {
     "CAP_LANE_SPLIT_MIN", "CAP_BLOCKS_PER_CU", "CAP_NO_CAMERA_CULL", "CAP_NO_ALBEDO_IN_W", "CAP_NO_INLINE_NEE", "CAP_NO_INLINE_PROBE", "CAP_NO_WAVE_RING",
     "CAP_ANY_REFILL", "CAP_PRIMARY_WIDE", "CAP_NO_PACKET", "CAP_NO_ANY_PROBE", "CAP_ANY_PROBE", "CAP_ANY_BLOCKS", "CAP_NO_PRIMARY_FUSE", "CAP_W8_REFILL",
     "CAP_W8_GRID", "CAP_AUTO_SAH_TRIANGLES", "CAP_NO_NEE_PAIR_CULL", "CAP_RAYGEN_KERNEL", "CAP_NO_PLANE_CODE", "CAP_SAMPLE_TABLE", "CAP_NO_CAMERA_TABLE",
-    "CAP_NO_GRAY_ENTRIES"};
+    "CAP_NO_GRAY_ENTRIES", "CAP_NO_GROUP_WALK", "CAP_NO_TABLE_REUSE"};
 
 static void switches_from_environment(SwitchTable& t)
 {
@@ -312,6 +312,17 @@ extern "C" int cap_debug_tile_divmod(uint32_t tiles_x, const uint32_t* n, uint64
         quotient[k]  = tile_div(n[k], mul, shift);
         remainder[k] = n[k] - quotient[k] * tiles_x;
     }
+    return CAP_OK;
+}
+
+// head_chunk() (cap_device.h), the head kernels' mapping of bounce 0's chunk indices, for tests/test_group_walk.py.  No device.
+int cap_debug_head_chunk(uint32_t cps, uint32_t m, const uint8_t* order, uint32_t n_slots, const uint32_t* c, uint64_t count, uint32_t* slot,
+                         uint32_t* group64)
+{
+    if (!order || !c || !slot || !group64 || !m || !cps || n_slots > kMaxFrameSlots || n_slots % m != 0u || (uint64_t)cps * n_slots > (1ull << kTileDivBits))
+        return CAP_ERR_INVALID_ARG;
+    const HeadWalk w = head_walk(m, cps, order, n_slots);
+    for (uint64_t k = 0; k < count; ++k) head_chunk(w, cps, c[k], slot[k], group64[k]);
     return CAP_OK;
 }
 
@@ -631,6 +642,8 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
         *value = (h[0] << 32) | ((uint64_t)lc.n_groups << 16) | lc.n_slots;  // mismatches << 32 | groups << 16 | slots compared
         return CAP_OK;
     }
+    case CAP_DEBUG_GROUP_WALK: *value = c->last_group_walk; return CAP_OK;
+    case CAP_DEBUG_CAMERA_TABLE_REUSED: *value = c->last_camera_reused; return CAP_OK;
     case CAP_DEBUG_GRAY_ENTRIES: *value = c->last_gray_entries; return CAP_OK;
     case CAP_DEBUG_SELFTEST_GRAY:
     {

@@ -466,6 +466,7 @@ int cap_pseudonormals_readback(CapContext* c, float* host_normals)
 int cap_bvh_build(CapContext* c)
 {
     if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_build: ctx is NULL");
+    ++c->scene_generation;  // (the camera-vertex table of an earlier cap_render no longer stands for the scene: CameraTableKey)
     if (!c->scene_ready) return fail(CAP_ERR_STATE, "cap_bvh_build: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t n = c->tri_count;
@@ -632,6 +633,7 @@ int cap_bvh_build(CapContext* c)
 int cap_scene_update_vertices(CapContext* c, const float* positions, const float* normals, const float* texcoords, uint32_t flags)
 {
     if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_scene_update_vertices: ctx is NULL");
+    ++c->scene_generation;  // (the camera-vertex table of an earlier cap_render no longer stands for the scene: CameraTableKey)
     if (!c->scene_ready) return fail(CAP_ERR_STATE, "cap_scene_update_vertices: no scene uploaded");
     if (flags & ~(uint32_t)CAP_VERTICES_DEVICE) return fail(CAP_ERR_INVALID_ARG, "cap_scene_update_vertices: unknown flags 0x%x", flags);
     const bool   device = (flags & CAP_VERTICES_DEVICE) != 0;
@@ -678,6 +680,7 @@ int cap_scene_update_vertices(CapContext* c, const float* positions, const float
 int cap_bvh_refit(CapContext* c, CapRefitInfo* out)
 {
     if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_bvh_refit: ctx is NULL");
+    ++c->scene_generation;  // (the camera-vertex table of an earlier cap_render no longer stands for the scene: CameraTableKey)
     if (!c->scene_ready || !c->bvh_ready) return fail(CAP_ERR_STATE, "cap_bvh_refit: no tree built since the last cap_scene_upload");
     HIP_TRY(hipSetDevice(c->device));
     const auto         wall0 = std::chrono::steady_clock::now();

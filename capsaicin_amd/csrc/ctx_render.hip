@@ -151,7 +151,10 @@ struct RenderPlan
     bool     gray_entries = false;      // the extension queues hold 32-byte entries, one throughput word (launch_trace_shade's gray)
     // Jitter groups: the slots of a batch by the bits of (jitter_x, jitter_y).  slot_group[f]: the group of frame f within its batch,
     // numbered in order of first appearance; group_first[batch start + g]: the first slot of group g.  A group need not be contiguous.
-    std::vector<uint32_t> slot_group, group_first, batch_groups;
+    // slot_order[batch start + k]: the batch's slots sorted by group, stable; batch_walk_m[batch]: the slots per group if every group
+    // of the batch has as many (every 64-frame batch: 8), else 0 -- the head kernels' group walk (cap_device.h head_chunk) or slot-major.
+    std::vector<uint32_t> slot_group, group_first, batch_groups, batch_walk_m;
+    std::vector<uint8_t>  slot_order;
     uint32_t camera_groups = 0;         // the most groups of any batch (what sizes Lane::camera)
     uint32_t cull_camera_pairs = 0, albedo_in_w = 0, code_in_color = 0, inline_nee = 0, inline_probe = 0;  // ShadeArgs' words of the same names
     bool     ring_form = false;         // the shadow rays of the probing kernels may go through the wave rings, if those are large enough
@@ -247,7 +250,7 @@ int ensure_lane_streams(CapContext* c)
 // The jitter groups of every batch of the plan (RenderPlan::slot_group): frame_const()'s jitter, compared bit for bit.
 void jitter_groups(RenderPlan& p)
 {
-    p.slot_group.resize(p.n_frames), p.group_first.assign(p.n_frames, 0u);
+    p.slot_group.resize(p.n_frames), p.group_first.assign(p.n_frames, 0u), p.slot_order.resize(p.n_frames);
     for (uint32_t done = 0; done < p.n_frames; done += p.slots)
     {
         const uint32_t ns = std::min(p.slots, p.n_frames - done);
@@ -265,7 +268,15 @@ void jitter_groups(RenderPlan& p)
             if (g == ng) p.group_first[done + ng++] = s;
             p.slot_group[done + s] = g;
         }
-        p.batch_groups.push_back(ng);
+        uint32_t at = 0, m = ns / ng;
+        for (uint32_t g = 0; g < ng; ++g)
+        {
+            const uint32_t from = at;
+            for (uint32_t s = 0; s < ns; ++s)
+                if (p.slot_group[done + s] == g) p.slot_order[done + at++] = (uint8_t)s;  // (ns <= kMaxFrameSlots = 64)
+            if (at - from != m) m = 0;
+        }
+        p.batch_groups.push_back(ng), p.batch_walk_m.push_back(m);
         p.camera_groups = std::max(p.camera_groups, ng);
     }
 }
@@ -590,6 +601,33 @@ void tree_next_hits(CapContext* c, const RenderPlan& p, const BatchRun& r, const
     ++c->stats.launches_trace_closest;
 }
 
+// What the camera-vertex table of batch `bt` is built from (CapContext::CameraTableKey), and whether two such keys name one table.
+CapContext::CameraTableKey camera_table_key(const CapContext* c, const RenderPlan& p, const Batch& bt, const BvhDev& bvh, const ShadeArgs& sa)
+{
+    CapContext::CameraTableKey k;
+    k.valid = true, k.cam = sa.cam, k.screen = sa.screen, k.n_groups = bt.groups, k.lane = bt.lane, k.cull_camera_pairs = sa.cull_camera_pairs;
+    k.tri_count = bvh.tri_count, k.fan_pair_count = bvh.fan_pair_count, k.fan_single_count = bvh.fan_single_count, k.tri_ids_dense = bvh.tri_ids_dense;
+    memcpy(&k.kd_untextured, &sa.scene.kd_untextured, 4);
+    for (uint32_t g = 0; g < bt.groups && g < kMaxFrameSlots; ++g)
+    {
+        float jx, jy;
+        halton23(p.frame_begin + bt.first + p.group_first[bt.first + g], jx, jy);  // frame_const()'s jitter of the group's first slot
+        memcpy(&k.jitter[g][0], &jx, 4), memcpy(&k.jitter[g][1], &jy, 4);
+    }
+    k.table = c->lane[bt.lane].camera.p, k.table_n = c->lane[bt.lane].camera.n;
+    k.records[0] = sa.scene.shade_tris, k.records[1] = bvh.tris_by_id, k.records[2] = bvh.fan_pairs, k.records[3] = bvh.fan_singles;
+    k.scene_generation = c->scene_generation;
+    return k;
+}
+bool same_camera_table(const CapContext::CameraTableKey& a, const CapContext::CameraTableKey& b)
+{
+    return a.valid && b.valid && memcmp(&a.cam, &b.cam, sizeof(CameraDev)) == 0 && memcmp(&a.screen, &b.screen, sizeof(ScreenDev)) == 0 &&
+           a.n_groups == b.n_groups && a.lane == b.lane && a.cull_camera_pairs == b.cull_camera_pairs && a.tri_count == b.tri_count &&
+           a.fan_pair_count == b.fan_pair_count && a.fan_single_count == b.fan_single_count && a.tri_ids_dense == b.tri_ids_dense &&
+           a.kd_untextured == b.kd_untextured && memcmp(a.jitter, b.jitter, sizeof(a.jitter)) == 0 && a.table == b.table && a.table_n == b.table_n &&
+           memcmp(a.records, b.records, sizeof(a.records)) == 0 && a.scene_generation == b.scene_generation;
+}
+
 // One batch: the launch sequence of its frame slots on its lane.  call_args: the ShadeArgs words that hold for the whole call.
 // last_resolve: the accumulation buffer takes the batches in frame order, whichever lane ran them.
 int render_batch(CapContext* c, const RenderPlan& p, const Batch& bt, const ShadeArgs& call_args, hipEvent_t& last_resolve)
@@ -623,14 +661,37 @@ int render_batch(CapContext* c, const RenderPlan& p, const Batch& bt, const Shad
     if (p.camera_head)
     {
         StageTimer t(c, ST_PRIMARY, p.stage_timers);
-        launch_camera_vertices(r.cfg, r.bvh, sa, bt.groups, tab_p, tab_n);
+        // The table depends on the slots through their groups' jitters alone, and any 64 consecutive frames hold the same eight: while
+        // the camera stands still -- progressive accumulation -- every batch of every call would build the table the lane already holds.
+        // Built only where its inputs differ from what the lane's table was built from.  A/B switch CAP_NO_TABLE_REUSE.
+        const CapContext::CameraTableKey key = camera_table_key(c, p, bt, r.bvh, sa);
+        CapContext::CameraTableKey&      have = c->camera_key[bt.lane];
+        const bool reuse = !c->sw.on(SW_NO_TABLE_REUSE) && same_camera_table(have, key);
+        if (!reuse)
+        {
+            have.valid = false;  // (until the launch is known to be queued)
+            launch_camera_vertices(r.cfg, r.bvh, sa, bt.groups, tab_p, tab_n);
+        }
+        c->last_camera_reused = reuse ? 1u : 0u;
         c->last_camera = CapContext::LastCamera{bt.frames, ns, bt.groups, bt.lane};
         // every CapStats field keeps its value between the two forms: bounce 0's shadow rays are still one any-hit pass of the batch,
         // traced inside the fused launch instead of by a launch of their own
         ++c->stats.launches_trace_any;
         if (trace_launch(c, "camera_vertices batch %u", bt.index)) return fail(CAP_ERR_HIP, "camera_vertices failed");
+        have = key;  // (a launch that could not be queued fails the call at the batch's end, and a failed call drops every key)
     }
     c->last_camera_table = p.camera_head ? 1u : 0u;
+    // The order of bounce 0's chunks in the head kernel: the group walk where every jitter group of the batch has m slots, else (and under
+    // the A/B switch CAP_NO_GROUP_WALK) slot-major, which is m = 1 with the identity order.
+    HeadWalk walk{};
+    if (p.camera_head)
+    {
+        const uint32_t m = c->sw.on(SW_NO_GROUP_WALK) ? 0u : p.batch_walk_m[bt.index];
+        uint8_t        identity[kMaxFrameSlots];
+        for (uint32_t s = 0; s < kMaxFrameSlots; ++s) identity[s] = (uint8_t)s;
+        walk = head_walk(m ? m : 1u, Ppad >> 6, m ? &p.slot_order[bt.first] : identity, ns);
+        c->last_group_walk = m;
+    }
     // (the reference model's 48-byte queues of this batch, for CAP_DEBUG_SELFTEST_GRAY: under camera_head bounce 0 appends nothing)
     c->last_queues = CapContext::LastQueues{D, p.camera_head ? 1u : 0u, class_capacity, bt.lane, p.fused && !p.ext && !p.gray_entries};
     for (uint32_t b = p.camera_head ? 1u : 0u; b <= D; ++b)
@@ -649,6 +710,7 @@ int render_batch(CapContext* c, const RenderPlan& p, const Batch& bt, const Shad
         // 32-byte layout)
         // (the input queue of that launch is bounce 0's identity queue: its three planes carry the table and bounce 0's sample terms)
         if (head) sa.in = RayQueue{tab_p, tab_n, L.terms.p, r.lay.ext(L.counters.p, 0), class_capacity, nullptr};
+        if (head) sa.walk = walk;
         if (p.fused)
         {
             if (int e = fused_bounce(c, p, bt, r, sa, head)) return e;
@@ -695,15 +757,23 @@ int render_batch(CapContext* c, const RenderPlan& p, const Batch& bt, const Shad
 }
 }  // namespace
 
+static int render_call(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t num_bounces, uint32_t flags);
 extern "C" int cap_render(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t num_bounces, uint32_t flags)
 {
     if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_render: ctx is NULL");
+    const int e = render_call(c, frame_begin, n_frames, num_bounces, flags);
+    // a call that was refused or failed vouches for no table: the next one builds
+    if (e != CAP_OK) c->camera_key[0].valid = c->camera_key[1].valid = false;
+    return e;
+}
+static int render_call(CapContext* c, uint32_t frame_begin, uint32_t n_frames, uint32_t num_bounces, uint32_t flags)
+{
     RenderPlan p;
     if (int e = plan_render(c, frame_begin, n_frames, num_bounces, flags, p)) return e;
     if (!p.n_batches) return CAP_OK;
     // the debug state of a call (cap_debug_get), from the plan; what a batch leaves is reset until the first batch writes it
     c->last_mark_form = 0, c->last_sample_table = p.sample_table ? 1u : 0u, c->last_cull_camera_pairs = p.cull_camera_pairs;
-    c->last_terms = CapContext::LastTerms{}, c->last_camera_table = 0, c->last_camera = CapContext::LastCamera{};
+    c->last_terms = CapContext::LastTerms{}, c->last_camera_table = 0, c->last_camera = CapContext::LastCamera{}, c->last_group_walk = 0, c->last_camera_reused = 0;
     c->last_gray_entries = p.gray_entries ? 1u : 0u, c->last_queues = CapContext::LastQueues{};
     if (p.feedback && (c->post_w != c->screen.width || c->post_h != c->screen.height))
         if (int e = cap_post_reset(c)) return e;  // first frame: cleared histories, every vertex is a disocclusion

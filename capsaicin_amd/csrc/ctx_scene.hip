@@ -13,6 +13,7 @@ int cap_scene_upload(CapContext* c, const float* positions, const float* normals
                      const CapMeshDesc* meshes, uint32_t vertex_count, uint32_t index_count, uint32_t mesh_count)
 {
     if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_scene_upload: ctx is NULL");
+    ++c->scene_generation;  // (the camera-vertex table of an earlier cap_render no longer stands for the scene: CameraTableKey)
     if ((vertex_count && (!positions || !normals || !texcoords)) || (index_count && !indices) || (mesh_count && !meshes))
         return fail(CAP_ERR_INVALID_ARG, "cap_scene_upload: NULL array with non-zero count");
     // validate the descriptors on the host: the kernels index with them unchecked
@@ -116,6 +117,7 @@ int cap_scene_set_instance_masks(CapContext* c, const uint8_t* masks, uint32_t m
 int cap_texture_upload(CapContext* c, uint32_t index, const uint8_t* rgba8, uint32_t width, uint32_t height)
 {
     if (!c) return fail(CAP_ERR_INVALID_ARG, "cap_texture_upload: ctx is NULL");
+    ++c->scene_generation;  // (the camera-vertex table of an earlier cap_render no longer stands for the scene: CameraTableKey)
     if (index >= 1024) return fail(CAP_ERR_INVALID_ARG, "texture index %u exceeds the reference's 1024-entry table", index);
     static const uint8_t zero_texel[4] = {0, 0, 0, 0};  // texture_system.cpp:47-56
     if (!rgba8) rgba8 = zero_texel, width = height = 1;
@@ -173,6 +175,7 @@ int cap_bluenoise_upload(CapContext* c, const uint8_t* rgba8)
 int cap_materials_upload(CapContext* c, const CapMaterial* materials, uint32_t mesh_count)
 {
     if (!c || (!materials && mesh_count)) return fail(CAP_ERR_INVALID_ARG, "cap_materials_upload: NULL argument");
+    ++c->scene_generation;  // (the camera-vertex table of an earlier cap_render no longer stands for the scene: CameraTableKey)
     if (!c->scene_ready || mesh_count != c->mesh_count) return fail(CAP_ERR_STATE, "cap_materials_upload: expected %u materials (one per mesh)", c->mesh_count);
     c->materials_host.assign(materials, materials + mesh_count);
     c->materials_ready = false;

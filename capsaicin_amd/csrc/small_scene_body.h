@@ -106,7 +106,9 @@
     // Chunk slots from the class's work counter, like the any-hit kernel (with the priorities below: bounce 0 4.6 -> 4.1 ms,
     // bounce >= 1 unchanged; before them it cost the bounce >= 1 kernel 7 %).  As there, the class's length is read once and
     // the next grab is issued after the entry loads (see k_trace_any).
-    const uint32_t my_class = wave_global_id() % kQueueClasses;
+    const uint32_t wave_class = wave_global_id() % kQueueClasses;
+    // (HEAD: as a scalar, so that what the loop derives from it once -- sub-queue bases, counter lines -- occupies no vector registers)
+    const uint32_t my_class = C::HEAD ? (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_class) : wave_class;
     const uint32_t lane     = threadIdx.x & 63u;
     uint32_t       n_class  = 0;
     if (!FIRST && !C::HEAD)
@@ -132,8 +134,11 @@
             // same operands.  What that kernel wrote into the extension queue stays in registers: r, thr, pid.
             const uint32_t chunk = class_chunk(j, my_class);  // chunks and classes as FIRST deals them out
             if (chunk >= chunks) break;
-            slot = chunk / cps;  // wave-uniform
-            i    = (chunk - slot * cps) * 64 + lane;
+            // which (slot, 64-pixel group) the dealt index stands for: the slots of a jitter group back to back (cap_device.h head_chunk,
+            // a bijection: the class stays my_class = chunk_class(chunk), so the sub-queues' static capacity holds as it did).  Wave-uniform.
+            uint32_t group64;
+            head_chunk(a.walk, cps, (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk), slot, group64);
+            i    = group64 * 64 + lane;
             pid  = (slot << kPidShift) | i;
             const FrameConst& fc = lds_frames[slot];
             const size_t      at = (size_t)f2u(fc.pad1) * Ppad + i;

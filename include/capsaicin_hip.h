@@ -329,6 +329,17 @@ enum
      * << 32 | entries looked at (saturating at 2^32 - 1). */
     CAP_DEBUG_GRAY_ENTRIES          = 20,
     CAP_DEBUG_SELFTEST_GRAY         = 21,
+    /* GROUP_WALK (get): how the head kernel of the last batch of the last cap_render (CAMERA_TABLE = 1) walked bounce 0's chunks.  m >= 1:
+     * every group of frame slots sharing a sub-pixel jitter had m slots, and the m slots of a group visited each 64-pixel group back to
+     * back, group after group, so that a camera-table entry is fetched once for its m readers (cap_debug_head_chunk below is the
+     * mapping).  0: slot-major, every slot sweeping the image on its own -- groups of unequal sizes, the switch CAP_NO_GROUP_WALK, or no
+     * head kernel.  Same bits and the same CapStats either way.
+     * CAMERA_TABLE_REUSED (get): 1 if the last batch of the last cap_render found the camera-vertex table of its working set already built
+     * from the same inputs -- camera, resolution and shard, the groups' jitters, the scene's records -- and launched no builder; 0 if it
+     * built the table (any of those changed, the switch CAP_NO_TABLE_REUSE, a failed call in between, or no table).  SELFTEST_CAMERA_TABLE
+     * checks a reused table like a built one. */
+    CAP_DEBUG_GROUP_WALK            = 22,
+    CAP_DEBUG_CAMERA_TABLE_REUSED   = 23,
     /* A/B and diagnostic switches of the build and render paths (which kernels trace the camera and the shadow rays, one or two batch
      * lanes, the builders' parameters ...): ONE table per context, key = SWITCH_BASE + cap_debug_switch_index("CAP_..."), the names being
      * the environment variables that fill the table once, at cap_ctx_create (tools set those around a whole process; nothing else in the
@@ -345,6 +356,12 @@ int cap_debug_switch_index(const char* name);
  * (float 18 = the first triangle's id as bits), single_count unpaired triangles, tri_count triangles in all.  1 if tri_count > 0, there is
  * no unpaired triangle, tri_count == 2 * pair_count and pair j's id is 2j for every j; else 0.  Needs no device. */
 int cap_debug_pair_ids_dense(const float* pair_records, uint32_t pair_count, uint32_t single_count, uint32_t tri_count);
+/* The head kernels' group walk (CAP_DEBUG_GROUP_WALK) on the host, by the function the kernels run: for a batch of n_slots = groups x m
+ * frame slots of cps 64-pixel groups each and `order` = its slots sorted by jitter group (n_slots bytes, a permutation), the frame slot
+ * and the 64-pixel group that each chunk index c[k] < cps * n_slots stands for.  m = 1 with the identity order is the slot-major walk.
+ * CAP_ERR_INVALID_ARG for a NULL array, m = 0, n_slots > 64 or not a multiple of m, cps * n_slots > 2^26.  Needs no device. */
+int cap_debug_head_chunk(uint32_t cps, uint32_t m, const uint8_t* order, uint32_t n_slots, const uint32_t* c, uint64_t count, uint32_t* slot,
+                         uint32_t* group64);
 /* The address checks every cap_trace_* entry point makes on its device arrays, on `count` <= 4 made-up ranges: array i holds n x stride[i]
  * bytes from base[i], and base[i] must be a multiple of align[i] (a power of two); stride[i] == 0: the caller left array i out.  CAP_OK if
  * every array is aligned, ends inside the address space and shares no byte with another one; else CAP_ERR_INVALID_ARG with the entry
