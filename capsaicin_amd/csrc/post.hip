@@ -179,7 +179,8 @@ __device__ __forceinline__ float luma_weight(float lc, float lp, float s) { retu
 
 // CapPostSettings::fast_weights: the same three weights through the hardware's transcendental instructions -- v_log_f32 / v_exp_f32
 // (base 2, 1 ulp) and v_rcp_f32 instead of the contract's polynomials and IEEE divisions: ~12 instructions where the exact forms
-// take ~110.  Not bit-comparable with the oracle; held to the tolerance stated in the header (tests/test_post_gpu.py).  The
+// take ~110.  Not bit-comparable with the oracle; held to the tolerance stated in the header (tests/test_post_gpu.py on rendered
+// frames, tests/test_post_planes_fast_gpu.py on crafted planes).  The
 // per-pixel reciprocals are hoisted: `neg_inv_s` = -log2(e) / sigma, or 0 where the reference's sigma is 0 (weight 1).
 constexpr float kLog2e = 1.44269504088896341f;
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
@@ -351,14 +352,32 @@ __device__ __forceinline__ v3 sample_bilinear_fast(const Img& t, f2 uv)
     const v3 v00 = xyz(ld(t, ux, uy)), v01 = xyz(ld(t, ux, uy + 1)), v10 = xyz(ld(t, ux + 1, uy)), v11 = xyz(ld(t, ux + 1, uy + 1));
     return lerp3(lerp3(v00, v10, wx), lerp3(v01, v11, wx), wy);
 }
+// resample_bicubic's centre tap for the FAST variants.  Its kernel weight is cubic(0)^2 = 1, so the reference's sum of weights is
+// 1 / (1 + luminance(value)) and its `tw > 1e-5 ? filtered / tw : 0` DECIDES: a history value brighter than 1e5 (a second moment
+// above 1.7e5, i.e. a luminance above ~400) resamples to 0.  The weight cancels in filtered / tw; the decision does not, so it is
+// kept: 1.0f / t > 1e-5f holds exactly for the floats t < 100000.0f (the division is correctly rounded, hence monotonic).
+__device__ __forceinline__ v3 bicubic_centre_fast(const Img& t, f2 uv)
+{
+    const v3 v = sample_bilinear_fast(t, uv);
+    return (1.0f + luminance(v) < 100000.0f) ? v : mk3(0.f, 0.f, 0.f);
+}
+// The FAST variants take the texel for SampleBilinear at a pixel centre where the tap IS the texel: where the centre survives the
+// reference's UV round trip, ((x + 0.5) / w) * w == x + 0.5, the fractional weights are exactly 0.  Elsewhere the reference blends a
+// neighbour in with a weight of the coordinate's rounding error (up to 2^-24 x: 6e-5 at x = 1000), which next to a texel a thousand
+// times brighter is no rounding error in the result, so those pixels take the tap itself; so do the last row and column, where
+// UVtoXY clamps to dim - 1 (utils.h:6-10) and the tap is a two-texel blend.  `uv` = the pixel centre as the exact code forms it.
+__device__ __forceinline__ bool centre_tap_is_texel(f2 uv, uint32_t x, uint32_t y, uint32_t w, uint32_t h)
+{
+    return x + 1u < w && y + 1u < h && uv.x * (float)w == (float)x + 0.5f && uv.y * (float)h == (float)y + 0.5f;
+}
 
 // temporal_accumulation.hlsl:213-325.  With UPSCALE2X (s.lowres_indirect) `color` is the half-resolution image (SampleColor uses its
 // size, :228-235) and a pixel that got no new sample this frame keeps its history (:307-313).
 // FAST (CapPostSettings::fast_weights): everything that DECIDES -- the reprojection, the disocclusion test, the history length -- is
 // the exact code on the same G-buffer and cameras, so the fast chain resets and blends exactly where the exact one does; only the
-// values are cheaper: the colour sample at a pixel centre is the texel (the reference's bilinear tap there has fractional weights of
-// 0 or one rounding error), and the bicubic history resample is its centre tap (the other eight sit where the Mitchell weight is
-// exactly 0 unless (c + 1) - c rounds: see resample_bicubic), without the weight that cancels in filtered / total.
+// values are cheaper: the colour sample at a pixel centre is the texel where the reference's bilinear tap is (centre_tap_is_texel),
+// and the bicubic history resample is its centre tap (the other eight sit where the Mitchell weight is exactly 0 unless (c + 1) - c
+// rounds: see resample_bicubic), without the weight that cancels in filtered / total but with its cut (bicubic_centre_fast).
 template <bool FAST>
 __global__ __launch_bounds__(kBlock) void k_accumulate(PostSettingsDev s, uint32_t frame_count, CameraDev cam, CameraDev prev_cam, Img color,
                                                        Img nd, Img color_history, Img moments_history, Img prev_nd, float4* out_color,
@@ -397,9 +416,8 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(PostSettingsDev s, uint32
         const float hl  = ld(moments_history, sat_uint(floorf(pxy.x)), sat_uint(floorf(pxy.y))).w;
         const f2    c0  = uv_to_xy(sp, W, H);
         const f2    cuv = f2{fminf(fmaxf(c0.x * fast_rcp((float)W), 0.0f), 1.0f), fminf(fmaxf(c0.y * fast_rcp((float)H), 0.0f), 1.0f)};
-        const v3    history = sample_bilinear_fast(color_history, cuv), mh = sample_bilinear_fast(moments_history, cuv);
-        // (the last row and column are NOT the texel: UVtoXY clamps to dim - 1, utils.h:6-10, so the reference's tap there is a two-texel blend)
-        const v3    c = (x + 1u < W && y + 1u < H) ? xyz(color.p[o]) : sample_bilinear(color, uv);
+        const v3    history = bicubic_centre_fast(color_history, cuv), mh = bicubic_centre_fast(moments_history, cuv);
+        const v3    c = centre_tap_is_texel(uv, x, y, W, H) ? xyz(color.p[o]) : sample_bilinear(color, uv);
         const float l = luminance(c);
         // closest_depth (:179-205): the centre texel, then the minimum over the non-zero depths of the 3 x 3
         float closest = dn[4];
@@ -879,9 +897,12 @@ __device__ __forceinline__ v3 clip_to_aabb(v3 pmin, v3 pmax, v3 p)
 
 // temporal_accumulation.hlsl:362-447
 // FAST (CapPostSettings::fast_weights): as in k_accumulate, what DECIDES (reprojection, velocity, the plain path) is the exact code;
-// the values use v_rcp_f32 / v_sqrt_f32, the bilinear tap at a whole-pixel position is the mean of its 2 x 2 texels (its fractional
-// weights are 0.5 up to one rounding error), the current colour at the pixel centre is the texel, and the history resample is the
-// bicubic's centre tap.
+// the values use v_rcp_f32 / v_sqrt_f32, the current colour at the pixel centre is the texel where the reference's tap is
+// (centre_tap_is_texel), and the history resample is the bicubic's centre tap with its cut (bicubic_centre_fast).
+// The neighbourhood box belongs to what decides: it says whether and where the history is clipped, and in a flat region its width is
+// 5 sqrt|m2 - m1^2| of a variance that is the cancellation residue of the two sums' own roundings -- another tap arithmetic or
+// summation (a 2 x 2 mean for the bilinear tap, fused squares) replaces that residue and moves the box by its own width, 1e-3 of the
+// colour, on inputs that are the same to the bit.  So the 25 taps, their sums and the box are the exact code in both modes.
 constexpr uint32_t kTaaTileW = 32 + 4, kTaaTileH = 8 + 4;  // the workgroup's 32 x 8 pixels + the 5 x 5 window's halo
 __device__ __forceinline__ v3 simple_tonemap_fast(v3 v) { return v * fast_rcp(1.0f + luminance(v)); }
 __device__ __forceinline__ v3 rgb2ycocg_fast(v3 c) { return mk3(0.25f * c.x + 0.5f * c.y + 0.25f * c.z, 0.5f * c.x - 0.5f * c.z, -0.25f * c.x + 0.5f * c.y - 0.25f * c.z); }
@@ -909,16 +930,8 @@ __global__ __launch_bounds__(kBlock) void k_taa(PostSettingsDev s, CameraDev cam
             int sx = x0 + (int)(e % kTaaTileW), sy = y0 + (int)(e / kTaaTileW);
             sx = sx < 0 ? 0 : (sx > (int)W - 1 ? (int)W - 1 : sx);
             sy = sy < 0 ? 0 : (sy > (int)H - 1 ? (int)H - 1 : sy);
-            if (FAST)
-            {
-                // SampleBilinear at uv = (sx, sy) / dim: footprint (sx - 1 .. sx, sy - 1 .. sy) with weights 0.5; at the left / top
-                // edge uint(floor(-0.5)) saturates to 0, so the footprint is (0 .. 1) there (utils.h:24-27)
-                const uint32_t ux = sx > 0 ? (uint32_t)sx - 1u : 0u, uy = sy > 0 ? (uint32_t)sy - 1u : 0u;
-                const v3 v00 = xyz(ld(color, ux, uy)), v01 = xyz(ld(color, ux, uy + 1)), v10 = xyz(ld(color, ux + 1, uy)), v11 = xyz(ld(color, ux + 1, uy + 1));
-                lds_tap[e] = rgb2ycocg_fast(simple_tonemap_fast(((v00 + v10) + (v01 + v11)) * 0.25f));
-            }
-            else
-                lds_tap[e] = rgb2ycocg(simple_tonemap(sample_bilinear(color, xy_to_uv(f2{(float)sx, (float)sy}, W, H))));
+            // (both modes: the taps build the box that DECIDES the clip -- see the comment above the kernel)
+            lds_tap[e] = rgb2ycocg(simple_tonemap(sample_bilinear(color, xy_to_uv(f2{(float)sx, (float)sy}, W, H))));
         }
         __syncthreads();
     }
@@ -945,10 +958,9 @@ __global__ __launch_bounds__(kBlock) void k_taa(PostSettingsDev s, CameraDev cam
     {
         const f2 c0  = uv_to_xy(puv, W, H);
         const f2 cuv = f2{fminf(fmaxf(c0.x * fast_rcp((float)W), 0.0f), 1.0f), fminf(fmaxf(c0.y * fast_rcp((float)H), 0.0f), 1.0f)};
-        history_rgb  = sample_bilinear_fast(history_img, cuv);
+        history_rgb  = bicubic_centre_fast(history_img, cuv);
     }
-    // (the last row and column are NOT the texel: UVtoXY clamps to dim - 1, utils.h:6-10, so the reference's tap there is a two-texel blend)
-    const v3 cur = (FAST && x + 1u < W && y + 1u < H) ? cur_early : sample_bilinear(color, uv);
+    const v3 cur = (FAST && centre_tap_is_texel(uv, x, y, W, H)) ? cur_early : sample_bilinear(color, uv);
     if (!FAST && plain)
     {
         out[o] = make_float4(cur.x, cur.y, cur.z, 1.0f);
@@ -980,7 +992,7 @@ __global__ __launch_bounds__(kBlock) void k_taa(PostSettingsDev s, CameraDev cam
         {
             const v3 v = lds_tap[(ly + 2 + j) * kTaaTileW + (lx + 2 + i)];
             m1 = m1 + v;
-            m2 = FAST ? mk3(fmaf(v.x, v.x, m2.x), fmaf(v.y, v.y, m2.y), fmaf(v.z, v.z, m2.z)) : m2 + v * v;
+            m2 = m2 + v * v;
         }
     const float inv_n = 1.0f / 25.0f;
     m1 = m1 * inv_n, m2 = m2 * inv_n;

@@ -14,7 +14,11 @@ four caller-made planes in tile order (tiles.extract(image, 0, 1)), O.PostChain.
   trace_accumulate         Gather and Accumulate alone (O.post_pass) with their histories carried: the images the later passes stage
 
 The renderer needs a resolution and a camera for this entry point, no scene.  Value contract of everything built here: colours
-finite, non-negative and at most 1e30; depths finite and non-negative (0 = sky).  `fast_weights` is not exercised."""
+finite, non-negative and at most 1e30; depths finite and non-negative (0 = sky).
+
+`fast_weights` (the toleranced mode, not an option of the oracle) runs on the same cases: run_gpu takes it as a key of the settings,
+run_oracle drops it, and `sensitivity` gives the bound it is held to (tests/test_post_planes_fast_gpu.py): what the oracle's exact
+chain itself answers to a 2^-16 relative change of its colour inputs."""
 import functools
 
 import numpy as np
@@ -133,8 +137,13 @@ def lowres_offset(frame_count):
     return (frame_count % 4) // 2, (frame_count % 4) % 2  # (ox, oy), rt_indirect.hlsl:53-59
 
 
+def oracle_settings(settings):
+    """O.PostSettings of a case's settings: `fast_weights` is the device's switch alone and has no field there."""
+    return O.PostSettings(**{k: v for k, v in dict(settings).items() if k != "fast_weights"})
+
+
 def run_oracle(w, h, settings, frames):
-    s = O.PostSettings(**settings)
+    s = oracle_settings(settings)
     chain = O.PostChain(w, h)
     out = []
     for fc, cam, prev, planes in frames:
@@ -146,7 +155,8 @@ def run_oracle(w, h, settings, frames):
 
 
 def run_gpu(r, settings, frames):
-    """`r`: a capi.Renderer with its resolution set (unsharded).  One upload, one cap_post_frame_gathered, one readback per frame."""
+    """`r`: a capi.Renderer with its resolution set (unsharded).  One upload, one cap_post_frame_gathered, one readback per frame.
+    settings may hold fast_weights = 1: the toleranced mode."""
     import torch
     from capsaicin_amd import capi, tiles
     s = capi.PostSettings(**settings)
@@ -165,7 +175,7 @@ def run_gpu(r, settings, frames):
 def trace_accumulate(w, h, settings, frames):
     """Gather -> Accumulate alone, histories carried as oracle_post_frame carries them (full-resolution form).
     -> per frame (accumulated colour | variance, moments | history length)."""
-    s = O.PostSettings(**settings)
+    s = oracle_settings(settings)
     assert not s.lowres_indirect
     z = np.zeros((h, w, 4), np.float32)
     chist, mhist, prev_nd, out = z, z, z, []
@@ -415,6 +425,41 @@ for _k in CAMERA_KINDS:
     case("g-camera-%s" % _k)(functools.partial(_camera_case, _k))
 
 
+def sky_ring(w=SW, h=SH):
+    """sky_pattern("frame") narrowed to the outermost texel ring."""
+    ys, xs = np.mgrid[0:h, 0:w]
+    return (xs < 1) | (ys < 1) | (xs >= w - 1) | (ys >= h - 1)
+
+
+@case("h-reproject-ring")
+def _reproject_ring():
+    """A yaw and a dolly at once: pixels beside the ring reproject INTO it -- a 3 x 3 of previous depths with taps outside the image,
+    around a centre that is a sky texel (closest_depth starts from 0) with geometry next to it."""
+    w, h = SW, SH
+    cams = [make_cam(w, h, pos=(0.0, 0.0, -0.05 * k), yaw=0.02 * k) for k in range(N_FRAMES)]
+    return Case(w, h, static_frames(w, h, noisy_two_walls(w, h, 71, sky=sky_ring(w, h)), cams=cams), camera="yaw+dolly")
+
+
+CONSTANT_VALUE = 0.37
+
+
+@case("h-constant")
+def _constant():
+    """Both walls, one constant indirect colour in every frame, albedo 1, no direct term, no sky; the yaw cameras and the cut.  The
+    exact output is that colour up to the chain's rounding, so a tap that reads what it should not -- outside the image, a stale
+    halo, the dummy position of a pixel that reprojects nowhere -- stands out by orders of magnitude."""
+    w, h = SW, SH
+    cams = [make_cam(w, h, yaw=0.02 * k) for k in range(N_FRAMES)]
+    prevs = {6: O.make_camera((100.0, 0.0, 0.0), (0.0, 0.0, 1.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), 0.036, 0.036 * h / w, 0.035)}
+
+    def make(f, cam):
+        p = two_walls(w, h, cam, value=CONSTANT_VALUE)
+        p["albedo"][..., 0:3] = 1.0
+        p["direct"][..., 0:3] = 0.0
+        return p
+    return Case(w, h, static_frames(w, h, make, cams=cams, prevs=prevs), camera="yaw+cut")
+
+
 @functools.lru_cache(maxsize=None)
 def oracle_outputs(name):
     """The oracle's frames of a case, computed once and shared (read-only) by the tests that need them."""
@@ -423,3 +468,53 @@ def oracle_outputs(name):
     for o in out:
         o.setflags(write=False)
     return out
+
+
+# ---- the exact chain's own sensitivity: what the toleranced mode is held to ----------------------------------------------------------
+DRAWS = 4                    # independent perturbations per case
+PERTURBATION = 2.0 ** -16    # relative, per texel, channel and frame: the size class of one rounding of a 1e-5-accurate weight
+S_FLOOR = 2.0 ** -20         # a sensitivity below this is taken as this (an output that no colour input reaches, e-sky-all-out3)
+BUDGET = 4.0                 # fast mode: Q <= BUDGET * max(S, S_FLOOR); reasons in DESIGN.md, "Reconstruction chain"
+ILL_CONDITIONED = 3e-2       # a frame whose own Smax exceeds this: its maximum means nothing, only Q50 and Q99 are judged
+SMALL_IMAGE = 256            # fewer pixels: the quantiles of a handful of channels are noise, only Qmax over the sequence is judged
+
+
+def rel_err(a, b):
+    """e(a, b) = |a - b| / (|b| + 1e-3) per colour channel: the measure of the header's stated tolerance."""
+    a, b = np.asarray(a, np.float64)[..., :3], np.asarray(b, np.float64)[..., :3]
+    return np.abs(a - b) / (np.abs(b) + 1e-3)
+
+
+def quantiles(e):
+    """(median, 99th percentile, maximum) of an array of errors; zeros for an empty one."""
+    e = np.asarray(e).ravel()
+    return (float(np.median(e)), float(np.percentile(e, 99)), float(e.max())) if e.size else (0.0, 0.0, 0.0)
+
+
+def perturbed_frames(name, draw):
+    """The case's frames with the .rgb of indirect, direct and albedo multiplied by float32(1 + u), u uniform in [-2^-16, 2^-16],
+    independently per texel, channel and frame.  normal_depth and the cameras are untouched, so every decision of the chain that
+    does not read a colour is the unperturbed run's."""
+    rng = np.random.default_rng([sorted(CASES).index(name), draw])
+    out = []
+    for fc, cam, prev, planes in CASES[name]().frames:
+        p = {k: v.copy() for k, v in planes.items()}
+        for k in ("indirect", "direct", "albedo"):
+            u = rng.uniform(-PERTURBATION, PERTURBATION, p[k][..., :3].shape)
+            p[k][..., :3] *= (1.0 + u).astype(np.float32)
+        out.append((fc, cam, prev, p))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sensitivity(name):
+    """-> float64 array (frames, 3): per frame S50, S99, Smax = the median, 99th percentile and maximum of
+    e(oracle on perturbed colours, oracle_outputs), each the largest over the DRAWS draws."""
+    c = CASES[name]()
+    exact = oracle_outputs(name)
+    s = np.zeros((len(exact), 3))
+    for draw in range(DRAWS):
+        got = run_oracle(c.w, c.h, c.settings, perturbed_frames(name, draw))
+        s = np.maximum(s, [quantiles(rel_err(g, b)) for g, b in zip(got, exact)])
+    s.setflags(write=False)
+    return s

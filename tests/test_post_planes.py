@@ -1,6 +1,9 @@
 """CPU side of the crafted-plane cases of the reconstruction chain (tests/post_planes_support.py): every case that is named after a
 path of post.hip proves with the restated predicates that its planes reach that path, the oracle's output is finite on all of them,
-sky pixels pass through in closed form, and the tiling helper the device side uploads through is the inverse of its assembly."""
+sky pixels pass through in closed form, and the tiling helper the device side uploads through is the inverse of its assembly.
+Also the conditions on the reference alone that the fast mode's bound rests on (S.sensitivity; tests/test_post_planes_fast_gpu.py):
+which frames are too ill-conditioned for their maximum to be judged, that every judged sensitivity is finite and non-zero, and
+that the perturbed draws take the exact run's decisions."""
 import numpy as np
 import pytest
 
@@ -203,3 +206,94 @@ def test_reach_sparse_disocclusion_and_dual_read():
         nown, nstaged = S.stencil_tile(c.w, c.h, nb[0], nb[1], 2)  # stages the patch from BlurDisocclusion's image in their halo
         assert np.all(at[nown] >= 8.0) and (patch & nstaged).any() and not (patch & nown).any()
     assert len(c.frames) > S.PATCH_FRAME + 2 and (hist[S.PATCH_FRAME + 1] < 8.0).sum() > patch.sum()  # then the patch's rim resets too
+
+
+# ---- the two cases the fast accumulate needs -----------------------------------------------------------------------------------------
+def test_reach_reprojection_into_the_outermost_ring():
+    """h-reproject-ring: in some frame a non-sky pixel reprojects (a) into the outermost texel ring, where the 3 x 3 of previous
+    depths has taps outside the image, and (b) onto a previous-frame sky texel that has geometry among its in-image neighbours --
+    closest_depth's start from a centre of 0.  Counted with the float64 restatements of the known-answer tests."""
+    import test_oracle_post_kat as K
+    c = S.CASES["h-reproject-ring"]()
+    w, h = c.w, c.h
+    ring = S.sky_ring(w, h)
+    frames_a, frames_b = 0, 0
+    for f in range(1, len(c.frames)):
+        _, cam, prev, p = c.frames[f]
+        nd, prev_nd = p["normal_depth"], c.frames[f - 1][3]["normal_depth"]
+        assert np.array_equal(S.is_background(nd[..., 3]), ring)
+        n_a = n_b = 0
+        for y, x in np.argwhere(~ring & ~S._box(w, h, 4, w - 4, 4, h - 4)):  # (only pixels near the border can land in the ring)
+            uv = (np.array([x, y], np.float64) + 0.5) / np.array([w, h], np.float64)
+            puv = K.image_plane_uv(prev, K.reconstruct_world_position(cam, uv, float(nd[y, x, 3])))
+            if puv[0] < 0 or puv[1] < 0 or puv[0] > 1 or puv[1] > 1:
+                continue
+            cx, cy = (int(v) for v in K.uv_to_xy(puv, w, h))
+            if not ring[cy, cx]:
+                continue
+            n_a += 1
+            around = prev_nd[max(cy - 1, 0):cy + 2, max(cx - 1, 0):cx + 2, 3]
+            n_b += int(prev_nd[cy, cx, 3] == 0.0 and (around != 0.0).any() and K.closest_depth(prev_nd, (cx, cy)) == 0.0)
+        frames_a += n_a > 0
+        frames_b += n_b > 0
+    assert frames_a >= 1 and frames_b >= 1
+    assert frames_a >= 6  # (as built: the yaw carries a column of pixels into the ring in every frame)
+
+
+def test_reach_constant_planes():
+    c = S.CASES["h-constant"]()
+    assert len({bytes(fr[1]) for fr in c.frames}) == len(c.frames)  # the camera turns every frame
+    assert bytes(c.frames[6][2]) != bytes(c.frames[5][1])  # and frame 6 reprojects through the cut
+    for _, _, _, p in c.frames:
+        assert np.all(p["indirect"][..., :3] == F(S.CONSTANT_VALUE)) and np.all(p["albedo"][..., :3] == 1.0) and np.all(p["direct"][..., :3] == 0.0)
+        assert not S.is_background(p["normal_depth"][..., 3]).any() and len(np.unique(S.second_wall_mask(c.w, c.h))) == 2
+    # the exact output is the constant within the fixed-point test's bound (tests/test_oracle_post.py), and the chain's answer to
+    # a relative input change of delta is of delta's order in the median once the zero history of frame 0 has decayed (that frame's
+    # TAA clip box is rounding noise wide, see the fixed-point test)
+    for out in S.oracle_outputs("h-constant"):
+        assert np.abs(out[..., :3] - S.CONSTANT_VALUE).max() < 5e-3
+    assert S.PERTURBATION / 8 < S.sensitivity("h-constant")[:, 0].min() < 2 * S.PERTURBATION
+
+
+# ---- conditions on the reference alone that the fast mode's bound rests on (tests/test_post_planes_fast_gpu.py) ------------------------
+def test_ill_conditioned_frames_are_the_stated_ones():
+    """A frame whose own Smax exceeds 3e-2 answers a 2^-16 input change with more than the header's largest stated error: its
+    maximum is not judged.  That happens in the late frames of d-luma-clamp only (1e6 fireflies beside a block at the clamp)."""
+    ill = [(n, f) for n in sorted(S.CASES) for f, s in enumerate(S.sensitivity(n)) if s[2] > S.ILL_CONDITIONED]
+    assert sum(len(S.CASES[n]().frames) for n in S.CASES) == 662 + 2 * S.N_FRAMES
+    assert {n for n, _ in ill} == {"d-luma-clamp"} and len(ill) <= 6, ill
+    assert all(f >= 7 for _, f in ill), ill
+
+
+@pytest.mark.parametrize("name", sorted(S.CASES))
+def test_sensitivity_is_finite_and_non_zero_where_it_is_judged(name):
+    """A zero S would leave the 2^-20 floor as the whole budget, an infinite one no bound at all.  All three colour planes are
+    perturbed for this: with the indirect plane alone output = 1 (the direct term) would not move.  Zero remains where the exact
+    output is identically 0 -- the variance image of an all-sky frame."""
+    c = S.CASES[name]()
+    s = S.sensitivity(name)
+    assert s.shape == (len(c.frames), 3) and np.all(np.isfinite(s)) and np.all(s[:, 0] <= s[:, 1]) and np.all(s[:, 1] <= s[:, 2])
+    if c.w * c.h < S.SMALL_IMAGE:
+        assert s[:, 2].max() > 0.0
+        return
+    for f, out in enumerate(S.oracle_outputs(name)):
+        if np.all(out[..., :3] == 0.0):
+            assert name == "e-sky-all-out3" and np.all(s[f] == 0.0)
+        else:
+            assert np.all(s[f] > 0.0), (f, s[f])
+
+
+@pytest.mark.parametrize("name", ["g-camera-yaw", "f-sparse-disocclusion", "h-reproject-ring"])
+def test_perturbed_draws_take_the_exact_runs_decisions(name):
+    """normal_depth and the cameras are not perturbed, so reset, reprojection and history length -- what Accumulate DECIDES, and what
+    BlurDisocclusion's pass-through reads -- are the unperturbed sequence's in every frame."""
+    c = S.CASES[name]()
+    exact = S.trace_accumulate(c.w, c.h, c.settings, c.frames)
+    seen = set()
+    for draw in (0, S.DRAWS - 1):
+        pert = S.trace_accumulate(c.w, c.h, c.settings, S.perturbed_frames(name, draw))
+        for (col, mom), (pcol, pmom) in zip(exact, pert):
+            assert np.array_equal(mom[..., 3], pmom[..., 3])
+            assert not np.array_equal(col[..., :3], pcol[..., :3])  # (the colours did move)
+            seen |= set(np.unique(mom[..., 3]).tolist())
+    assert 1.0 in seen and max(seen) >= 8.0  # resets and long histories both occur
