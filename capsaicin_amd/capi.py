@@ -285,6 +285,7 @@ SYMBOLS = {
     "cap_debug_head_chunk": (_i, [_u32, _u32, _vp, _u32, _vp, _u64, _vp, _vp]),
     "cap_debug_query_ranges": (_i, [_u64, _u32, _vp, _vp, _vp]),
     "cap_debug_closest_instance_bound": (_i, [_vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "cap_debug_overlap_instance_prune": (_i, [_vp] * 17),
     "cap_render": (_i, [_vp, _u32, _u32, _u32, _u32]),
     "cap_accum_reset": (_i, [_vp]),
     "cap_accum_import": (_i, [_vp, _vp, _u64]),
@@ -312,6 +313,7 @@ SYMBOLS = {
     "cap_closest_points": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_points_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_overlap_boxes": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
+    "cap_overlap_instances": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_pseudonormals_build": (_i, [_vp, C.POINTER(PseudonormalsInfo)]),
     "cap_pseudonormals_drop": (_i, [_vp]),
     "cap_pseudonormals_readback": (_i, [_vp, _vp]),
@@ -1091,11 +1093,17 @@ class Renderer:
         writes the next page over it and returns it.  sync and mask= as closest_points."""
         return self._multi("cap_overlap_boxes", boxes, 8, "boxes", 0, False, k, counts, resume, sync, (self.trace_options(None, mask),))
 
-    def voxel_occupancy(self, origin, cell, dims, mask=None):
-        """Surface voxelisation: the number of triangles that meet each cell of the grid of dims = (nx, ny, nz) cubes of edge `cell`
-        from `origin`, as a (nx, ny, nz) int32 tensor on this context's device (cap_overlap_boxes, counts only).  Per axis cell i spans
-        lo = fl(origin + fl(i * cell)) to hi = fl(origin + fl((i + 1) * cell)) in float32, so neighbours share their faces exactly and
-        a triangle lying in a shared face counts in both cells."""
+    def overlap_instances(self, boxes, k, counts=False, resume=None, sync=True, mask=None):
+        """The (instance, triangle) pairs whose world-space triangle meets each closed axis-aligned WORLD-space box, the first k in
+        (instance, triangle) order (cap_overlap_instances): (triangles (N, k) int32, instances (N, k) int32[, counts (N,) int32 = the
+        number of ALL pairs of each box with counts=True]), -1 in the slots after a box's last pair.  k = 0: counts only, both pages
+        are (N, 0).  resume=(triangles, instances) of the previous call with the same boxes continues after it with
+        CAP_MULTI_CONTINUE and writes the next pages over both.  Needs set_instances().  boxes, sync and mask= as overlap_boxes."""
+        return self._multi("cap_overlap_instances", boxes, 8, "boxes", 0, True, k, counts, resume, sync, (self.trace_options(None, mask),))
+
+    def _cell_boxes(self, origin, cell, dims):
+        """(dims, the (nx * ny * nz, 8) float32 CapBoxDesc rows of the grid's cells on this context's device): per axis cell i spans
+        lo = fl(origin + fl(i * cell)) to hi = fl(origin + fl((i + 1) * cell)) in float32, so neighbours share their faces exactly"""
         import torch
         dev = torch.device("cuda", self.device)
         dims = tuple(int(d) for d in dims)
@@ -1113,9 +1121,23 @@ class Renderer:
             shape[axis] = d
             boxes[..., axis] = edges[:-1].reshape(shape)
             boxes[..., 4 + axis] = edges[1:].reshape(shape)
-        _, cnt = self.overlap_boxes(boxes.reshape(-1, 8), 0, counts=True, mask=mask)
+        return dims, boxes.reshape(-1, 8)
+
+    def voxel_occupancy(self, origin, cell, dims, mask=None):
+        """Surface voxelisation: the number of triangles that meet each cell of the grid of dims = (nx, ny, nz) cubes of edge `cell`
+        from `origin`, as a (nx, ny, nz) int32 tensor on this context's device (cap_overlap_boxes, counts only).  Per axis cell i spans
+        lo = fl(origin + fl(i * cell)) to hi = fl(origin + fl((i + 1) * cell)) in float32, so neighbours share their faces exactly and
+        a triangle lying in a shared face counts in both cells."""
+        dims, boxes = self._cell_boxes(origin, cell, dims)
+        _, cnt = self.overlap_boxes(boxes, 0, counts=True, mask=mask)
         return cnt.reshape(dims)
 
+    def voxel_occupancy_instances(self, origin, cell, dims, mask=None):
+        """voxel_occupancy over the instance table: the number of (instance, triangle) pairs whose world-space triangle meets each cell
+        of the same grid, in world space (cap_overlap_instances, counts only).  Needs set_instances()."""
+        dims, boxes = self._cell_boxes(origin, cell, dims)
+        _, _, cnt = self.overlap_instances(boxes, 0, counts=True, mask=mask)
+        return cnt.reshape(dims)
 
     # ---- instanced ray queries (cap_instances_set, cap_trace_instances*) ----
     def set_objects(self, ranges):

@@ -252,6 +252,19 @@ struct OverlapArgs
     float         slack;
 };
 void launch_overlap_boxes(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapArgs& a, const RayFilter* f, uint32_t depth);
+// Over the instance table (cap_overlap_instances, overlap.hip k_overlap_inst): the boxes are in world space, a.out = pages of k triangle
+// ids and inst_out = pages of k instances (both NULL when k = 0) -- the cursor is slot k - 1 of both.  a.slack is not read: the slack is
+// per box and instance (cap_near.h overlap_slack).  descs, near and xw_max as ClosestInstArgs'; bvh, tl, f and depth as
+// launch_closest_instances'.
+struct OverlapInstArgs
+{
+    OverlapArgs     a;
+    uint32_t*       inst_out;
+    const float4*   descs;
+    const float2*   near;
+    const uint32_t* xw_max;
+};
+void launch_overlap_instances(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapInstArgs& a, const TlasDev& tl, const RayFilter& f, uint32_t depth);
 
 // ---- instances (instance.hip): cap_instances_set, cap_trace_instances* ----
 // The table on the device.  rec: 4 float4 per instance = the three rows of W (world to object, row r = (W_r0, W_r1, W_r2, W_r3)) and

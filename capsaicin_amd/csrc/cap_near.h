@@ -2,7 +2,8 @@
 // per-instance world-to-object data of k_instance_setup (instance.hip), the two values the distance prune adds to it (g, Xw), the
 // per-point slack and the skip predicate of k_closest_inst (point_query.hip).  cap_debug_closest_instance_bound (context.hip) runs the
 // same functions on the host, so that the CPU tests exercise what ships.  DESIGN.md "Closest-point queries over instances" has the
-// argument for the constants.
+// argument for the constants.  At the end: the same for box overlap queries over instances (cap_overlap_instances) -- the slack, the
+// object-space image of a world box and the skip test of k_overlap_inst (overlap.hip), which cap_debug_overlap_instance_prune runs.
 #pragma once
 
 #include <cmath>
@@ -143,4 +144,45 @@ __host__ __device__ __forceinline__ float box_dist2(float px, float py, float pz
 
 // the walk's test: a strict >, so that a box at exactly the bound is opened (a NaN distance is opened too)
 __host__ __device__ __forceinline__ bool near_skip(float box_d2, float bound2) { return box_d2 > bound2; }
+
+// ---- box overlap queries over instances (cap_overlap_instances, overlap.hip k_overlap_inst) ----
+// What the walk prunes with, host and device; cap_debug_overlap_instance_prune (context.hip) runs the same functions.  DESIGN.md "Box
+// overlap queries over instances" derives the constant: the argument needs 64, the two roundings of the slack and its division take
+// three eps more.
+constexpr float kOverlapC2 = 96.0f;
+
+// the largest coordinate magnitude of the query box
+__host__ __device__ __forceinline__ float overlap_box_max(float lox, float loy, float loz, float hix, float hiy, float hiz)
+{
+    return fmaxf(fmaxf(fmaxf(fabsf(lox), fabsf(loy)), fmaxf(fabsf(loz), fabsf(hix))), fmaxf(fabsf(hiy), fabsf(hiz)));
+}
+// slack_i = c2 eps (|box|_inf + Xw_i): what the world query box is grown by at the top level (xw = the table's largest Xw), and,
+// divided by g <= sigma_min, its object-space image inside instance i
+__host__ __device__ __forceinline__ float overlap_slack(float bmax, float xw) { return (kOverlapC2 * kNearEps) * (bmax + xw); }
+
+// The object-space image of the world box of centre c and half-extent h (BoxFrame's) under the stored W, grown by s:
+//   c'_r = fl(fl(fl(fl(W_r0 c.x) + fl(W_r1 c.y)) + fl(W_r2 c.z)) + W_r3)   (near_to_object),
+//   h'_r = fl(fl(fl(|W_r0| h.x) + fl(|W_r1| h.y)) + fl(|W_r2| h.z)),
+//   olo_r = fl(fl(c'_r - h'_r) - s),  ohi_r = fl(fl(c'_r + h'_r) + s).
+// Plain products and sums; an image that is not finite compares false with everything and so opens every node.
+__host__ __device__ __forceinline__ void overlap_image(const float w[12], float cx, float cy, float cz, float hx, float hy, float hz, float s, float olo[3],
+                                                       float ohi[3])
+{
+    float c[3];
+    near_to_object(w, cx, cy, cz, c[0], c[1], c[2]);
+    for (int r = 0; r < 3; ++r)
+    {
+        const float h = (fabsf(w[4 * r]) * hx + fabsf(w[4 * r + 1]) * hy) + fabsf(w[4 * r + 2]) * hz;
+        olo[r] = (c[r] - h) - s, ohi[r] = (c[r] + h) + s;
+    }
+}
+
+// The walk's test, at the top level (a stored world box against the world query box grown by the top-level slack) and below an instance
+// (a node box of the object's tree against the image): true = the box [blo, bhi] lies beyond [qlo, qhi] on some axis.  Every comparison
+// is strict and written "x < y": touching opens, and so does a NaN on either side.
+__host__ __device__ __forceinline__ bool overlap_miss(float blox, float bloy, float bloz, float bhix, float bhiy, float bhiz, float qlox, float qloy,
+                                                      float qloz, float qhix, float qhiy, float qhiz)
+{
+    return bhix < qlox || qhix < blox || bhiy < qloy || qhiy < bloy || bhiz < qloz || qhiz < bloz;
+}
 }  // namespace cap

@@ -50,6 +50,27 @@ __device__ __forceinline__ bool ray_pop(const uint32_t* stack, int& sp, int& nod
     return true;
 }
 
+// ---- the world record of an instanced triangle (cap_closest_instances' contract; cap_overlap_instances takes it unchanged) ----
+// dot of the contracts: no fused multiply-add (the build has -ffp-contract=off; fmaf is nowhere written)
+__device__ __forceinline__ float dot_c(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+// (v0w, e1w, e2w) of the stored record (t0, t1, t2) = (v0, e1, e2) under the rows m0 .. m2 of the instance's transform M as the caller
+// gave it:  v0w_r = fl(dot_c(M_r.xyz, v0) + M_r.w),  e1w_r = dot_c(M_r.xyz, e1),  e2w_r = dot_c(M_r.xyz, e2), packed like a stored record
+struct WorldRecord
+{
+    float4 t0, t1, t2;
+};
+__device__ __forceinline__ WorldRecord world_record(const float4 m0, const float4 m1, const float4 m2, const float4 t0, const float4 t1, const float4 t2)
+{
+    WorldRecord w;
+    w.t0 = make_float4(dot_c(m0.x, m0.y, m0.z, t0.x, t0.y, t0.z) + m0.w, dot_c(m1.x, m1.y, m1.z, t0.x, t0.y, t0.z) + m1.w,
+                       dot_c(m2.x, m2.y, m2.z, t0.x, t0.y, t0.z) + m2.w, dot_c(m0.x, m0.y, m0.z, t0.w, t1.x, t1.y));
+    w.t1 = make_float4(dot_c(m1.x, m1.y, m1.z, t0.w, t1.x, t1.y), dot_c(m2.x, m2.y, m2.z, t0.w, t1.x, t1.y), dot_c(m0.x, m0.y, m0.z, t1.z, t1.w, t2.x),
+                       dot_c(m1.x, m1.y, m1.z, t1.z, t1.w, t2.x));
+    w.t2 = make_float4(dot_c(m2.x, m2.y, m2.z, t1.z, t1.w, t2.x), 0.f, 0.f, 0.f);
+    return w;
+}
+
 // ---- the top level of the instanced kernels: the implicit tree without a stack ----
 // This state crosses a step BY VALUE, in and out (t = step(.., t)): handed over as eight reference parameters it cost every instanced
 // closest-point instantiation 20 bytes of scratch.

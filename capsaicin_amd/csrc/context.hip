@@ -378,6 +378,51 @@ int cap_debug_closest_instance_bound(const float* transform, const float* box_lo
     return CAP_OK;
 }
 
+// The prune of cap_overlap_instances (cap_near.h: the functions k_overlap_inst runs, over the per-instance data of k_instance_setup) for
+// one transform, one object box, one world box and one object-space box against one query box.  No context, no device:
+// tests/test_overlap_instances.py.
+int cap_debug_overlap_instance_prune(const float* transform, const float* object_lo, const float* object_hi, const float* world_lo, const float* world_hi,
+                                     const float* node_lo, const float* node_hi, const float* box_lo, const float* box_hi, float* world_to_object, float* g,
+                                     float* xw, float* slack, float* image_lo, float* image_hi, uint32_t* skip_top, uint32_t* skip_node)
+{
+    if (!transform || !object_lo || !object_hi || !world_lo || !world_hi || !node_lo || !node_hi || !box_lo || !box_hi)
+        return fail(CAP_ERR_INVALID_ARG, "cap_debug_overlap_instance_prune: NULL input");
+    double m[12], w[12], wd[12], A[12], nA, kappa, blo[3], bhi[3];
+    float  wf[12];
+    bool   live = true;
+    for (int k = 0; k < 12; ++k) m[k] = (double)transform[k], live = live && finite_d(m[k]);
+    for (int k = 0; k < 3; ++k) blo[k] = (double)object_lo[k], bhi[k] = (double)object_hi[k];
+    live = instance_inverse(m, live, w, wf, wd, A, nA, kappa, (float)CAP_INSTANCE_MAX_CONDITION);
+    const float gi = live ? near_sigma_min_bound(w) : 0.0f, xi = live ? near_world_extent(m, blo, bhi) : 0.0f;
+    // the kernel's frame of the box (overlap.hip box_frame) and its two slacks
+    const float hl[3] = {box_lo[0] * 0.5f, box_lo[1] * 0.5f, box_lo[2] * 0.5f}, hh[3] = {box_hi[0] * 0.5f, box_hi[1] * 0.5f, box_hi[2] * 0.5f};
+    const float bmax  = overlap_box_max(box_lo[0], box_lo[1], box_lo[2], box_hi[0], box_hi[1], box_hi[2]);
+    const float sl    = overlap_slack(bmax, xi);
+    float       olo[3] = {0.f, 0.f, 0.f}, ohi[3] = {0.f, 0.f, 0.f};
+    if (live) overlap_image(wf, hl[0] + hh[0], hl[1] + hh[1], hl[2] + hh[2], hh[0] - hl[0], hh[1] - hl[1], hh[2] - hl[2], sl / gi, olo, ohi);
+    if (world_to_object)
+        for (int k = 0; k < 12; ++k) world_to_object[k] = wf[k];
+    if (g) *g = gi;
+    if (xw) *xw = xi;
+    if (slack) *slack = sl;
+    for (int k = 0; k < 3; ++k)
+    {
+        if (image_lo) image_lo[k] = olo[k];
+        if (image_hi) image_hi[k] = ohi[k];
+    }
+    // an inert instance is never entered and has no world box: nothing to skip
+    if (skip_top)
+        *skip_top = live && overlap_miss(world_lo[0], world_lo[1], world_lo[2], world_hi[0], world_hi[1], world_hi[2], box_lo[0] - sl, box_lo[1] - sl,
+                                         box_lo[2] - sl, box_hi[0] + sl, box_hi[1] + sl, box_hi[2] + sl)
+                        ? 1u
+                        : 0u;
+    if (skip_node)
+        *skip_node = live && overlap_miss(node_lo[0], node_lo[1], node_lo[2], node_hi[0], node_hi[1], node_hi[2], olo[0], olo[1], olo[2], ohi[0], ohi[1], ohi[2])
+                         ? 1u
+                         : 0u;
+    return CAP_OK;
+}
+
 int cap_ctx_create(int device_id, void* hip_stream, CapContext** out_ctx)
 {
     if (!out_ctx) return fail(CAP_ERR_INVALID_ARG, "cap_ctx_create: out_ctx is NULL");

@@ -14,16 +14,17 @@
 //
 // The list is K ids in registers, ascending; it prunes nothing, so a walk with counts is the walk without them and the count is one
 // register and one wave-uniform store: not a template flag.
+//
+// The instanced form (cap_overlap_instances, k_overlap_inst) is at the end of the file: world-space boxes over the instance table, the
+// pairs (instance, triangle) whose world record meets the box, in (instance, triangle) order.
 #include "cap_kernels.h"
-#include "cap_query_walk.h"  // the launch dispatchers
+#include "cap_near.h"        // the prune of the instanced form
+#include "cap_query_walk.h"  // TopWalk, and the launch dispatchers
 
 namespace cap
 {
 namespace
 {
-// dot of the contract: no fused multiply-add (the build has -ffp-contract=off; fmaf is nowhere written)
-__device__ __forceinline__ float dot_c(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-
 // min(x0, x1, x2) > r and max(x0, x1, x2) < r of the contract, whose min and max hand a NaN on: three comparisons each, so that a NaN
 // among the three separates nothing (v_min3_f32 would drop it)
 __device__ __forceinline__ bool all_above(float x0, float x1, float x2, float r) { return x0 > r && x1 > r && x2 > r; }
@@ -115,6 +116,33 @@ struct IdList
     }
 };
 
+// An inner node against the grown query box [gl, gh]: one fetch yields both child boxes; a child is kept unless it lies beyond the box on
+// some axis (cap_near.h overlap_miss: strict, touching opens, a NaN opens); both kept: child 0 is entered and child 1 pushed; one kept:
+// it is entered.  false: neither is kept, the caller pops.  A walk pushes at most one entry per level it descends and STACK is at least
+// the tree's depth (with_stack_class); the guard drops a push beyond it rather than write outside the lane's LDS column.
+template <int STACK>
+__device__ __forceinline__ bool box_node_step(const BvhDev& bvh, float glx, float gly, float glz, float ghx, float ghy, float ghz, uint32_t* stack, int& node,
+                                              int& sp)
+{
+    // child 0: lo (q0.x q0.y q0.z) hi (q0.w q1.x q1.y); child 1: lo (q1.z q1.w q2.x) hi (q2.y q2.z q2.w)
+    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2], q3 = bvh.nodes[4 * node + 3];
+    const bool   k0 = !overlap_miss(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, glx, gly, glz, ghx, ghy, ghz);
+    const bool   k1 = !overlap_miss(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, glx, gly, glz, ghx, ghy, ghz);
+    const int    c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+    if (k0 && k1)
+    {
+        if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)c1;
+        node = c0;
+        return true;
+    }
+    if (k0 || k1)
+    {
+        node = k0 ? c0 : c1;
+        return true;
+    }
+    return false;
+}
+
 // Workgroups per CU.  The stack is 4 B x STACK x kBlock of the CU's 160 KB of LDS: 16 / 24 / 32 / 64 KB per workgroup, which admits
 // 10 / 6 / 5 / 2 of them.  A workgroup is one wave on each of the four SIMDs and a SIMD holds 8 waves, so 10 becomes 8.  The 512 VGPRs
 // of a SIMD lane shared by N waves leave 64 (N = 8), 72 (7), 80 (6), 96 (5) each, in granules of 8.  Compiled without a limit that
@@ -155,24 +183,7 @@ __global__ __launch_bounds__(kBlock, overlap_blocks(STACK, K)) void k_overlap_bo
             {
                 if (node >= 0)
                 {
-                    // child 0: lo (q0.x q0.y q0.z) hi (q0.w q1.x q1.y); child 1: lo (q1.z q1.w q2.x) hi (q2.y q2.z q2.w)
-                    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2], q3 = bvh.nodes[4 * node + 3];
-                    const bool   k0 = !(q0.w < glx || q0.x > ghx || q1.x < gly || q0.y > ghy || q1.y < glz || q0.z > ghz);
-                    const bool   k1 = !(q2.y < glx || q1.z > ghx || q2.z < gly || q1.w > ghy || q2.w < glz || q2.x > ghz);
-                    const int    c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
-                    // a walk pushes at most one entry per level it descends and STACK is at least the tree's depth (with_stack_class);
-                    // the guard drops a push beyond it rather than write outside the lane's LDS column
-                    if (k0 && k1)
-                    {
-                        if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)c1;
-                        node = c0;
-                        continue;
-                    }
-                    if (k0 || k1)
-                    {
-                        node = k0 ? c0 : c1;
-                        continue;
-                    }
+                    if (box_node_step<STACK>(bvh, glx, gly, glz, ghx, ghy, ghz, stack, node, sp)) continue;
                 }
                 else
                 {
@@ -207,6 +218,168 @@ __global__ __launch_bounds__(kBlock, overlap_blocks(STACK, K)) void k_overlap_bo
         }
     }
 }
+
+// ---- over the instance table (cap_overlap_instances) ----
+// For every WORLD-space box the pairs (instance, triangle) whose world record -- cap_closest_instances' (world_record, cap_query_walk.h),
+// from the transform M as the caller gave it -- meets the box under box_meets above, unchanged; the first k in (instance, triangle)
+// order, their number, or both.  One loop with three kinds of step, as k_closest_inst (point_query.hip), so that the lanes of a wave
+// that are at the top level advance while others are inside an instance:
+//   * a top-level node: its two children's stored world boxes against the query box grown by the top-level slack (no order, no bound:
+//     top_advance with far_first = false and distances of 0);
+//   * entering an instance: mask, cursor, M, and the object-space image of the query box (cap_near.h overlap_image), once per pair of
+//     box and instance;
+//   * a bottom-level node or leaf: box_node_step on the object's tree against the image; a leaf builds the world record and calls
+//     box_meets with the world-space BoxFrame.
+// Every skip is overlap_miss's strict "x < y": touching opens, and so does an image that is not finite (lo = -FLT_MAX, hi = 0 under a
+// scaling instance: c' + h' is -inf + inf).  DESIGN.md "Box overlap queries over instances" has the argument that no skipped box holds
+// a candidate.
+// The list is K keys (instance << 32 | triangle) in registers, ascending: two words per slot either way, and the 64-bit compare is one
+// v_cmp_lt_u64 where the lexicographic offer of two words is two compares and an and-or.  The cursor (i_c, g_c) is such a key; an
+// instance below i_c is not entered at all -- the major key of the order makes that exact, so it changes no result.
+template <int K>
+struct PairList
+{
+    uint64_t key[K];
+    __device__ __forceinline__ void init(uint32_t k)
+    {
+#pragma unroll
+        for (int j = 0; j < K; ++j) key[j] = j >= K - (int)k ? ~0ull : 0ull;
+    }
+    __device__ __forceinline__ void offer(uint64_t id)
+    {
+#pragma unroll
+        for (int j = K - 1; j > 0; --j) key[j] = max(key[j - 1], min(id, key[j]));
+        key[0] = min(id, key[0]);
+    }
+};
+
+// One top-level node: both children's stored world boxes against the grown query box (a record with k < 0 holds nothing: an inert
+// instance or the padding of a level); then down, or the instances into the queue, or up (top_advance)
+__device__ __forceinline__ TopWalk overlap_top_step(const TlasDev& tl, const uint32_t* lds_off, float glx, float gly, float glz, float ghx, float ghy,
+                                                    float ghz, TopWalk t)
+{
+    const float4* c = tl.tlas + 2 * (size_t)(lds_off[t.level - 1u] + 2u * t.idx);
+    const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
+    const bool    h0 = lo0.w >= 0.0f && !overlap_miss(lo0.x, lo0.y, lo0.z, hi0.x, hi0.y, hi0.z, glx, gly, glz, ghx, ghy, ghz);
+    const bool    h1 = lo1.w >= 0.0f && !overlap_miss(lo1.x, lo1.y, lo1.z, hi1.x, hi1.y, hi1.z, glx, gly, glz, ghx, ghy, ghz);
+    return top_advance(t, h0, h1, false, f2u(hi0.w), f2u(hi1.w), 0.f, 0.f);
+}
+
+// Workgroups per CU.  LDS as overlap_blocks', but for the 104 bytes of level offsets, which take the fifth workgroup of STACK = 32 away
+// (5 x 32 872 B is 520 B more than the CU has).  Registers (tools/kernel_regs.sh; the table is in DESIGN.md "Box overlap queries over
+// instances"): the walk holds M, the frame, the image and the top-level state beside the list's 2 K words.  Compiled without a limit
+// that binds (STACK = 64, two workgroups) the kernel takes 86 to 88 VGPRs at K = 1, 100 to 102 at K = 4, 116 to 118 at K = 8 and 148 to
+// 150 at K = 16: five waves per SIMD (96 each), four (128), four and three (168) are what those sizes admit anyway, so the limits below
+// cost no instantiation a register, let alone scratch.  (Four workgroups at K = 16 leave 128 and spill 84 to 92 bytes.)
+constexpr int overlap_inst_blocks(int STACK, int K)
+{
+    const int by_lds  = STACK <= 16 ? 8 : STACK <= 24 ? 6 : STACK <= 32 ? 4 : 2;
+    const int by_regs = K <= 1 ? 5 : K <= 8 ? 4 : 3;
+    return by_lds < by_regs ? by_lds : by_regs;
+}
+
+// FILTER: a mesh-mask table is installed (f.tri_mask by global id); the instance's own mask is tested either way.
+template <int STACK, int K, bool FILTER>
+__global__ __launch_bounds__(kBlock, overlap_inst_blocks(STACK, K)) void k_overlap_inst(BvhDev bvh, OverlapInstArgs ia, TlasDev tl, RayFilter f)
+{
+    __shared__ uint32_t lds_stack[STACK * kBlock];
+    __shared__ uint32_t lds_off[kTlasMaxLevels + 1];
+    uint32_t* const     stack = lds_stack + threadIdx.x;
+    if (threadIdx.x <= tl.top) lds_off[threadIdx.x] = tl.level_off[threadIdx.x];
+    __syncthreads();
+    const OverlapArgs& a      = ia.a;
+    const float        xw_all = u2f(ia.xw_max[0]);  // the largest Xw of the table: the top level's slack holds for every instance
+    const int          skip   = K - (int)a.k;        // the placeholders
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < a.n; j += gridDim.x * kBlock)
+    {
+        const float4    lo = a.boxes[2 * (size_t)j], hi = a.boxes[2 * (size_t)j + 1];
+        uint32_t* const page  = a.out + (size_t)j * a.k;
+        uint32_t* const ipage = ia.inst_out + (size_t)j * a.k;
+        PairList<K>     L;
+        L.init(a.k);
+        uint32_t count = 0u;
+        if (box_ok(lo, hi) && bvh.tri_count != 0u)
+        {
+            // only pairs above the cursor -- slot k - 1 of the box's two pages -- count and are listed; (~0, ~0) admits nothing
+            const bool     open = a.resume == 0u;
+            const uint32_t ic   = open ? 0u : ipage[a.k - 1u];
+            const uint64_t kc   = open ? 0ull : ((uint64_t)ic << 32) | page[a.k - 1u];
+            const BoxFrame b    = box_frame(lo, hi);
+            const float    bmax = overlap_box_max(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z);
+            const float    slack_top = overlap_slack(bmax, xw_all);
+            const float    glx = lo.x - slack_top, gly = lo.y - slack_top, glz = lo.z - slack_top;
+            const float    ghx = hi.x + slack_top, ghy = hi.y + slack_top, ghz = hi.z + slack_top;
+            TopWalk        t   = top_start(tl);
+            // bottom level: the instance being walked
+            bool     in_blas = false;
+            float4   m0 = make_float4(0.f, 0.f, 0.f, 0.f), m1 = m0, m2 = m0;
+            float    olo[3] = {0.f, 0.f, 0.f}, ohi[3] = {0.f, 0.f, 0.f};
+            uint32_t inst = 0u, imask = 0u;
+            int      node = 0, sp = 0;
+            for (;;)
+            {
+                if (in_blas)
+                {
+                    if (node >= 0)
+                    {
+                        if (box_node_step<STACK>(bvh, olo[0], olo[1], olo[2], ohi[0], ohi[1], ohi[2], stack, node, sp)) continue;
+                    }
+                    else
+                    {
+                        const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                        for (uint32_t leaf = first; leaf <= last; ++leaf)
+                        {
+                            const uint32_t gid = f2u(bvh.tris[4 * (size_t)leaf + 3].x);
+                            if constexpr (FILTER)
+                                if ((f.tri_mask[gid] & imask) == 0u) continue;
+                            const WorldRecord w = world_record(m0, m1, m2, bvh.tris[4 * (size_t)leaf + 0], bvh.tris[4 * (size_t)leaf + 1], bvh.tris[4 * (size_t)leaf + 2]);
+                            if (!box_meets(b, w.t0, w.t1, w.t2)) continue;
+                            const uint64_t key = ((uint64_t)inst << 32) | gid;
+                            if (open || key > kc)
+                            {
+                                ++count;
+                                L.offer(key);
+                            }
+                        }
+                    }
+                    in_blas = sp != 0;
+                    if (in_blas) node = (int)stack[(--sp) * kBlock];
+                    continue;
+                }
+                if (t.todo0 != kInvalidId)
+                {
+                    // the head of the queue: its mask joined with the call's (0 for an inert instance; the mesh byte joins it per
+                    // triangle), the cursor's instance, then M, the image of the box under the stored W and the root of the object's tree
+                    inst = t.todo0;
+                    t    = top_pop(t);
+                    const float4 w3 = tl.rec[4 * (size_t)inst + 3];
+                    imask           = f2u(w3.x) & f.mask;
+                    if (imask == 0u || inst < ic) continue;
+                    const float4 w0 = tl.rec[4 * (size_t)inst], w1 = tl.rec[4 * (size_t)inst + 1], w2 = tl.rec[4 * (size_t)inst + 2];
+                    const float  w[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
+                    const float2 nr = ia.near[inst];  // (g, Xw)
+                    overlap_image(w, b.cx, b.cy, b.cz, b.hx, b.hy, b.hz, overlap_slack(bmax, nr.y) / nr.x, olo, ohi);
+                    m0 = ia.descs[4 * (size_t)inst], m1 = ia.descs[4 * (size_t)inst + 1], m2 = ia.descs[4 * (size_t)inst + 2];
+                    node = (int)f2u(w3.y), sp = 0, in_blas = true;
+                    continue;
+                }
+                if (t.done) break;
+                t = overlap_top_step(tl, lds_off, glx, gly, glz, ghx, ghy, ghz, t);
+            }
+        }
+        // (a box that was not traversed: the list as init left it, k empty slots in both pages, and count 0)
+        if (a.counts) a.counts[j] = count;
+        for (uint32_t s = 0; s < a.k; ++s)
+        {
+            uint64_t key = ~0ull;
+#pragma unroll
+            for (int q = 0; q < K; ++q)
+                if (q - skip == (int)s) key = L.key[q];
+            page[s]  = (uint32_t)key;
+            ipage[s] = (uint32_t)(key >> 32);
+        }
+    }
+}
 }  // namespace
 
 void launch_overlap_boxes(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapArgs& a, const RayFilter* f, uint32_t depth)
@@ -218,6 +391,18 @@ void launch_overlap_boxes(const LaunchCfg& cfg, const BvhDev& bvh, const Overlap
         with_k_bucket(a.k, [&](auto K) {
             with_flag(f && f->tri_mask, [&](auto FILTER) {
                 launch_points<k_overlap_boxes<decltype(S)::value, decltype(K)::value, decltype(FILTER)::value>>(cfg, a.n, b, a, rf);
+            });
+        });
+    });
+}
+
+void launch_overlap_instances(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapInstArgs& a, const TlasDev& tl, const RayFilter& f, uint32_t depth)
+{
+    // (depth: of the deepest bottom-level tree)
+    with_stack_class(depth, [&](auto S) {
+        with_k_bucket(a.a.k, [&](auto K) {
+            with_flag(f.tri_mask != nullptr, [&](auto FILTER) {
+                launch_points<k_overlap_inst<decltype(S)::value, decltype(K)::value, decltype(FILTER)::value>>(cfg, a.a.n, bvh, a, tl, f);
             });
         });
     });

@@ -32,9 +32,6 @@ namespace cap
 {
 namespace
 {
-// dot of the contract: no fused multiply-add (the build has -ffp-contract=off; fmaf is nowhere written)
-__device__ __forceinline__ float dot_c(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-
 struct ClosestPoint
 {
     float    x, y, z, d2, u, v;
@@ -382,21 +379,7 @@ __global__ __launch_bounds__(kBlock, closest_multi_blocks(STACK, K)) void k_clos
 //     near_bound2_object).  A leaf builds the world record and runs the cascade.
 // Both bounds are computed again only when `best` improves; every test is a strict >, so an instance, subtree or triangle at exactly
 // the best distance is still opened and the lower (instance, triangle) wins whatever the visiting order.  DESIGN.md "Closest-point
-// queries over instances" has the argument that no skipped box holds a candidate.
-struct WorldRecord
-{
-    float4 t0, t1, t2;
-};
-__device__ __forceinline__ WorldRecord world_record(const float4 m0, const float4 m1, const float4 m2, const float4 t0, const float4 t1, const float4 t2)
-{
-    WorldRecord w;
-    w.t0 = make_float4(dot_c(m0.x, m0.y, m0.z, t0.x, t0.y, t0.z) + m0.w, dot_c(m1.x, m1.y, m1.z, t0.x, t0.y, t0.z) + m1.w,
-                       dot_c(m2.x, m2.y, m2.z, t0.x, t0.y, t0.z) + m2.w, dot_c(m0.x, m0.y, m0.z, t0.w, t1.x, t1.y));
-    w.t1 = make_float4(dot_c(m1.x, m1.y, m1.z, t0.w, t1.x, t1.y), dot_c(m2.x, m2.y, m2.z, t0.w, t1.x, t1.y), dot_c(m0.x, m0.y, m0.z, t1.z, t1.w, t2.x),
-                       dot_c(m1.x, m1.y, m1.z, t1.z, t1.w, t2.x));
-    w.t2 = make_float4(dot_c(m2.x, m2.y, m2.z, t1.z, t1.w, t2.x), 0.f, 0.f, 0.f);
-    return w;
-}
+// queries over instances" has the argument that no skipped box holds a candidate.  (world_record: cap_query_walk.h.)
 // scene_record for a listed pair: the world record again from the records in id order and the instance's transform
 __device__ __forceinline__ ClosestPoint instance_record(const BvhDev& bvh, const float4* descs, uint32_t inst, uint32_t gid, const float4 p)
 {

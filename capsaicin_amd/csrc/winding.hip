@@ -34,8 +34,7 @@ namespace
 {
 constexpr uint32_t kNoParent = 0xffffffffu;
 
-// dot of the contract: no fused multiply-add (the build has -ffp-contract=off)
-__device__ __forceinline__ float  dot_c(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+// dot of the contract (dot_c: cap_query_walk.h) in double: no fused multiply-add (the build has -ffp-contract=off)
 __device__ __forceinline__ double ddot(double ax, double ay, double az, double bx, double by, double bz) { return (ax * bx + ay * by) + az * bz; }
 
 __device__ __forceinline__ double load_agent(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

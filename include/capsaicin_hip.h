@@ -377,6 +377,18 @@ int cap_debug_query_ranges(uint64_t n, uint32_t count, const uint64_t* base, con
  * device. */
 int cap_debug_closest_instance_bound(const float* transform, const float* box_lo, const float* box_hi, const float* point, float best_dist2,
                                      float* world_to_object, float* g, float* xw, float* slack, uint32_t* skip);
+/* The pruning arithmetic of cap_overlap_instances (below) for ONE instance transform (12 floats, row-major 3x4), the object-space box
+ * of its object (object_lo, object_hi), one WORLD-space box (world_lo, world_hi: the instance's stored world box, a top-level node's, or
+ * a triangle's world vertex box standing for them), one OBJECT-space box (node_lo, node_hi: a node of the object's tree, or a triangle's
+ * vertex box standing for the nodes above it) and one world-space query box (box_lo, box_hi), by the very functions the instance setup
+ * and the query kernel run; 3 floats each.  Outputs, each may be NULL: world_to_object, g, xw as cap_debug_closest_instance_bound's;
+ * slack = 96 * 2^-24 * (|box|_inf + xw), what the query box is grown by at the top level (there with the table's largest xw) and,
+ * divided by g, what its image is grown by inside the instance; image_lo, image_hi = that image, 3 floats each; skip_top = 1 if the
+ * walk would skip the world box, skip_node = 1 if it would skip the object-space box, else 0.  An inert transform gives W = 0, g = 0,
+ * xw = 0, a zero image and no skip.  CAP_ERR_INVALID_ARG for a NULL input.  Needs no device. */
+int cap_debug_overlap_instance_prune(const float* transform, const float* object_lo, const float* object_hi, const float* world_lo, const float* world_hi,
+                                     const float* node_lo, const float* node_hi, const float* box_lo, const float* box_hi, float* world_to_object, float* g,
+                                     float* xw, float* slack, float* image_lo, float* image_hi, uint32_t* skip_top, uint32_t* skip_node);
 /* Traversal strategy of the trace kernels (same hits either way): AUTO picks EXHAUSTIVE for scenes of at most 64
  * triangles (wave-uniform test of every triangle, no stack) and STACK (LBVH + per-lane LDS stack) otherwise. */
 typedef enum CapTraversal
@@ -662,8 +674,8 @@ int cap_closest_points_multi(CapContext* ctx, const CapPointDesc* device_points,
  * cap_bvh_build and while the trees are stale; CAP_ERR_INVALID_ARG for any ray_flags bit, non-zero reserved words,
  * instance_mask > 0xFF, unknown multi flags, k > CAP_MULTI_MAX_K, k = 0 with a page given or counts NULL, CAP_MULTI_CONTINUE with
  * k = 0, NULL boxes (or page with k > 0), misaligned or overlapping ranges, and n * k ids beyond the address space.
- * Not covered: instances and objects (the boxes are in the scene's own space), oriented boxes, a lower bound from the cursor (a later
- * page walks the whole box again), per-box masks. */
+ * Not covered: oriented boxes, a lower bound from the cursor (a later page walks the whole box again), per-box masks.  The boxes are in
+ * the scene's own space; over instances and objects: cap_overlap_instances below. */
 typedef struct CapBoxDesc /* 32 B, 16-byte aligned */
 {
     float lo[3];
@@ -673,6 +685,52 @@ typedef struct CapBoxDesc /* 32 B, 16-byte aligned */
 } CapBoxDesc;
 int cap_overlap_boxes(CapContext* ctx, const CapBoxDesc* device_boxes, uint64_t n, uint32_t k, uint32_t* device_triangles /* n*k ids */,
                       uint32_t* device_counts /* n or NULL */, uint32_t multi_flags, const CapTraceOptions* options /* may be NULL */);
+
+/* ---- box overlap queries over instances: which triangles of which placed parts meet a world-space box ----
+ * cap_overlap_boxes over the instance table of cap_instances_set (and the objects of cap_objects_set), as cap_closest_instances_multi
+ * stands to cap_closest_points_multi.  The boxes are axis-aligned in WORLD space.
+ *
+ * Candidates.  A box's candidates are the pairs (instance i, triangle g) of cap_closest_instances: i is not inert; with an object table
+ * g is a triangle of i's object; desc[i].mask & mesh_mask[m] & instance_mask != 0 (m the mesh of g).  The pair is a candidate where its
+ * WORLD record meets the box under cap_overlap_boxes' predicate, unchanged.  The world record is cap_closest_instances', built from
+ * M = desc[i].transform as the caller gave it, with dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, one rounded binary32 operation per
+ * operation written and no fused multiply-add:
+ *   v0w_r = fl(dot(M_r.xyz, v0) + M_r.w),  e1w_r = dot(M_r.xyz, e1),  e2w_r = dot(M_r.xyz, e2),   r = x, y, z;
+ * the predicate's vertices are a = v0w, b = fl(v0w + e1w), c = fl(v0w + e2w), its e1 and e2 are e1w and e2w.  A NumPy float32 brute force
+ * over every (instance, triangle) is bit-identical, whichever builder made the trees.
+ *
+ * Order and pages.  The pairs sort by (i, g) ascending.  device_triangles[b * k + j] and device_instances[b * k + j], j < k, are box
+ * b's j-th pair; slots after the last pair hold 0xFFFFFFFF in both pages.  device_counts: NULL, or n uint32: the number of ALL
+ * candidates of the box, not capped at k (with CAP_MULTI_CONTINUE: of those above the cursor).  k = 0 counts only: both pages must be
+ * NULL and device_counts given.
+ *
+ * Paging (CAP_MULTI_CONTINUE): on entry slot k - 1 of both pages is read as the cursor (i_c, g_c); only pairs lexicographically above
+ * it count and are listed, and the next pages are written over the old ones.  (0xFFFFFFFF, 0xFFFFFFFF) -- a page that was not full --
+ * admits nothing.  device_instances is therefore required whenever k > 0, as in cap_closest_instances_multi.
+ *
+ * Degenerate boxes are cap_overlap_boxes': not traversed, pages of 0xFFFFFFFF, count 0.  lo = -FLT_MAX, hi = FLT_MAX is legal and
+ * lists every live, unmasked pair.
+ *
+ * Identities (tested on the reference and on the device):
+ *   1. One identity instance gives cap_overlap_boxes' ids and counts: 1*x + 0*y + 0*z is exact for finite x -- only the sign of a zero
+ *      can change, and no comparison of the predicate sees it.
+ *   2. With pure translations, vertices and boxes on a common power-of-two grid (every sum exact) the answer is the flattened scene's
+ *      under cap_overlap_boxes, with flat id = i * T + g, T the scene's triangle count.
+ *   3. Scaling every M (matrix and translation) and every box by 2^j changes nothing, short of overflow and underflow.
+ *
+ * Conventions and errors are cap_closest_instances_multi's word for word, with the four ranges "boxes", "triangles", "instances" and
+ * "counts": device pointers on the context's GPU, boxes 16-byte and triangles, instances and counts 4-byte aligned, ranges that do not
+ * overlap; asynchronous on the context stream; n above 2^24 split into launches with all three outputs advanced per chunk, n = 0 does
+ * nothing; nothing is written on an error.  CAP_ERR_STATE without an instance table, before cap_bvh_build and while the trees are
+ * stale; CAP_ERR_INVALID_ARG for any ray_flags bit, non-zero reserved words, instance_mask > 0xFF, unknown multi flags,
+ * k > CAP_MULTI_MAX_K, k = 0 with a page given or counts NULL, CAP_MULTI_CONTINUE with k = 0, NULL boxes (or either page with k > 0),
+ * misaligned or overlapping ranges.
+ * Pruning is conservative for every live instance (DESIGN.md "Box overlap queries over instances"; cap_debug_overlap_instance_prune
+ * shows its arithmetic).  Not covered: oriented boxes, per-box masks, the wide view, a lower bound inside an instance from the cursor's
+ * triangle (an instance below the cursor's is not entered; the cursor's own is walked again). */
+int cap_overlap_instances(CapContext* ctx, const CapBoxDesc* device_boxes, uint64_t n, uint32_t k, uint32_t* device_triangles /* n*k */,
+                          uint32_t* device_instances /* n*k */, uint32_t* device_counts /* n or NULL */, uint32_t multi_flags,
+                          const CapTraceOptions* options /* may be NULL */);
 
 /* ---- instanced ray queries: N transformed instances of the uploaded scene, or of objects of it, under a device-built top-level tree ----
  * The uploaded scene and the trees cap_bvh_build makes of it are read as OBJECT space; cap_instances_set installs a table of N

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Throughput of the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances,
-cap_closest_instances_multi, cap_signed_distance_instances) and of cap_winding_numbers and cap_winding_instances on the 262 k-triangle hall -- not part of
+cap_closest_instances_multi, cap_signed_distance_instances), of the box overlap queries (cap_overlap_boxes, cap_overlap_instances) and of cap_winding_numbers and cap_winding_instances on the 262 k-triangle hall -- not part of
 bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
@@ -50,6 +50,9 @@ or without --counts the mean number of records listed per point (at most K).  `h
 of --k K ids (default 4; --counts: with the candidate counts, which cost the walk nothing): mboxes_per_s, mean_candidates and the share
 of empty boxes.  Beside it, measured in the same process, the nearest existing workload: cap_closest_points_multi with counts at the
 same K on the same centres, at the radius that gives the same mean candidate count (found by bisection: closest_multi_counts_*).
+--boxes together with --instances N runs cap_overlap_instances on the --instances layout with the same cubes as world boxes:
+mboxes_per_s, mean_candidates (pairs per box) and the share of empty boxes, and from the same process the flat cap_overlap_boxes rate
+on the same boxes (flat_ms, flat_mboxes_per_s, flat_mean_candidates, ratio_to_flat).
 
 Point sets, each of --points points (rounded down to a cube for the grid):
   grid      a regular grid through the scene's box, in raster order (x fastest);
@@ -120,8 +123,8 @@ def main():
     ap.add_argument("--boxes", action="store_true")
     ap.add_argument("--extent", type=float, default=0.005)
     a = ap.parse_args()
-    if a.boxes and (a.winding or a.signed or a.instances is not None):
-        ap.error("--boxes goes with --k, --counts and --extent only")
+    if a.boxes and (a.winding or a.signed):
+        ap.error("--boxes goes with --k, --counts, --extent and --instances only")
     if a.boxes and a.k is None:
         a.k = 4  # (before `out` below is sized: the comparison run writes pages of k records into it)
     if a.winding and (a.signed or a.k is not None):
@@ -130,7 +133,7 @@ def main():
         ap.error("--signed does not go with --k: the sign is defined for the single record")
     if a.instances is not None and a.instances < 1:
         ap.error("--instances N needs N >= 1")
-    inst_multi = a.instances is not None and a.k is not None
+    inst_multi = a.instances is not None and a.k is not None and not a.boxes
     inst_signed = a.instances is not None and a.signed
     rng = np.random.default_rng(2026)
     dev = torch.device("cuda", 0)
@@ -229,6 +232,18 @@ def main():
             capi._check(L.cap_overlap_boxes(r.ctx, boxes.data_ptr(), n, 0, None, box_cnt.data_ptr(), 0, None), "cap_overlap_boxes")
             r.sync()
             mean = float(box_cnt.double().mean())
+            if a.instances is not None:
+                # cap_overlap_instances on the same world boxes (the point sets lie in instance 0, the identity), beside the flat rate above
+                isec = timed(r, lambda: capi._check(L.cap_overlap_instances(r.ctx, boxes.data_ptr(), n, k, ids.data_ptr() if k else None,
+                                                                            inst.data_ptr() if k else None, box_cnt.data_ptr() if a.counts else None, 0, None),
+                                                    "cap_overlap_instances"), a.reps, a.warmup)
+                capi._check(L.cap_overlap_instances(r.ctx, boxes.data_ptr(), n, 0, None, None, box_cnt.data_ptr(), 0, None), "cap_overlap_instances")
+                r.sync()
+                print(json.dumps(dict(head, set=name, instances=a.instances, inert=int(info_i.inert), tlas_depth=int(info_i.tlas_depth), ms=round(isec * 1e3, 3),
+                                      mboxes_per_s=round(n / isec / 1e6, 2), mean_candidates=round(float(box_cnt.double().mean()), 3),
+                                      empty=round(float((box_cnt == 0).float().mean()), 4), flat_ms=round(sec * 1e3, 3),
+                                      flat_mboxes_per_s=round(n / sec / 1e6, 2), flat_mean_candidates=round(mean, 3), ratio_to_flat=round(sec / isec, 3))), flush=True)
+                continue
             # the nearest existing workload: cap_closest_points_multi --counts at the radius with the same mean candidate count (bisection)
             rlo, rhi = 0.0, 4.0 * half
             for _ in range(16):
