@@ -170,6 +170,12 @@ class BoxDesc(C.Structure):
     _fields_ = [("lo", C.c_float * 3), ("pad0", C.c_float), ("hi", C.c_float * 3), ("pad1", C.c_float)]
 
 
+class TriangleDesc(C.Structure):
+    """CapTriangleDesc (48 bytes): a query triangle a, b, c and the global id of the scene triangle that is no candidate
+    (0xFFFFFFFF: none); the pad words are not read."""
+    _fields_ = [("a", C.c_float * 3), ("skip", C.c_uint32), ("b", C.c_float * 3), ("pad0", C.c_uint32), ("c", C.c_float * 3), ("pad1", C.c_uint32)]
+
+
 FEATURE_FACE, FEATURE_EDGE_V0V1, FEATURE_EDGE_V1V2, FEATURE_EDGE_V2V0, FEATURE_V0, FEATURE_V1, FEATURE_V2 = range(7)  # CAP_FEATURE_*
 
 
@@ -314,6 +320,7 @@ SYMBOLS = {
     "cap_closest_points_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_overlap_boxes": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_overlap_instances": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
+    "cap_overlap_triangles": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_pseudonormals_build": (_i, [_vp, C.POINTER(PseudonormalsInfo)]),
     "cap_pseudonormals_drop": (_i, [_vp]),
     "cap_pseudonormals_readback": (_i, [_vp, _vp]),
@@ -546,6 +553,7 @@ class Renderer:
         self.device = device
         self._tri_end = np.zeros(0, np.int64)  # inclusive prefix sums of the uploaded mesh table's triangle counts
         self._vertex_count = 0
+        self._scene_host = None  # (positions (V, 3) float32 or the device tensor of the last update, indices, meshes (M, 8)): scene_triangle_queries
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -563,11 +571,13 @@ class Renderer:
                                       a[4].shape[0]), "cap_scene_upload")
         self._set_mesh_table(a[4])
         self._vertex_count = a[0].size // 3
+        self._scene_host = (a[0].reshape(-1, 3).copy(), a[3].copy(), a[4].copy())
 
     def upload_geometry(self, geo):
         _check(lib().cap_scene_upload_geometry(self.ctx, geo.h), "cap_scene_upload_geometry")
         self._set_mesh_table(geo.meshes)
         self._vertex_count = int(geo.view.vertex_count)
+        self._scene_host = (geo.positions.reshape(-1, 3).copy(), geo.indices.copy(), np.array(geo.meshes, np.uint32).reshape(-1, 8))
 
     def _set_mesh_table(self, meshes):
         self._tri_end = np.cumsum(np.asarray(meshes, np.uint32).reshape(-1, 8)[:, 2].astype(np.int64) // 3)
@@ -612,6 +622,9 @@ class Renderer:
                     raise CapError("update_vertices: tensors must be on %s, got %s" % (dev, a.device))
             torch.cuda.current_stream(dev).synchronize()  # the arrays were written on torch's stream
         _check(lib().cap_scene_update_vertices(self.ctx, ptrs[0], ptrs[1], ptrs[2], flags), "cap_scene_update_vertices")
+        if positions is not None and self._scene_host is not None:
+            kept = positions.reshape(-1, 3).copy() if isinstance(positions, np.ndarray) else positions.detach().reshape(-1, 3).clone()
+            self._scene_host = (kept,) + self._scene_host[1:]
 
     def refit_bvh(self):
         """Refit the trees of the last build_bvh() to the current vertices; returns RefitInfo (ms, expected_node_visits,
@@ -1100,6 +1113,49 @@ class Renderer:
         are (N, 0).  resume=(triangles, instances) of the previous call with the same boxes continues after it with
         CAP_MULTI_CONTINUE and writes the next pages over both.  Needs set_instances().  boxes, sync and mask= as overlap_boxes."""
         return self._multi("cap_overlap_instances", boxes, 8, "boxes", 0, True, k, counts, resume, sync, (self.trace_options(None, mask),))
+
+    # ---- triangle overlap queries (cap_overlap_triangles) ----
+    def overlap_triangles(self, tris, k, counts=False, resume=None, sync=True, mask=None):
+        """The scene triangles that meet each query triangle, the first k by triangle id (cap_overlap_triangles).  tris: (N, 12) float32
+        = CapTriangleDesc rows (a, skip, b, -, c, -): column 3 carries the BITS of `skip`, the global id of a scene triangle that is no
+        candidate (0xFFFFFFFF: none); columns 7 and 11 are not read.  triangle_queries() packs them, scene_triangle_queries() makes
+        them of the scene's own triangles.  A contiguous torch tensor on this context's device or a numpy array (staged through torch;
+        the results come back as numpy).  The return value, counts=, resume=, sync and mask= are overlap_boxes'."""
+        return self._multi("cap_overlap_triangles", tris, 12, "tris", 0, False, k, counts, resume, sync, (self.trace_options(None, mask),))
+
+    @staticmethod
+    def triangle_queries(a, b, c, skip=None):
+        """(N, 12) float32 CapTriangleDesc rows of (N, 3) vertices a, b, c; skip: None (0xFFFFFFFF: nothing is skipped) or N global
+        triangle ids, whose bits go into column 3.  The pad columns hold 0."""
+        a, b, c = (np.asarray(x, np.float32).reshape(-1, 3) for x in (a, b, c))
+        if not len(a) == len(b) == len(c):
+            raise CapError("triangle_queries: a, b and c must have one row per triangle, got %d, %d and %d" % (len(a), len(b), len(c)))
+        q = np.zeros((len(a), 12), np.float32)
+        q[:, 0:3], q[:, 4:7], q[:, 8:11] = a, b, c
+        ids = np.full(len(a), 0xFFFFFFFF, np.uint32) if skip is None else np.asarray(skip, np.int64).astype(np.uint32).reshape(-1)
+        if len(ids) != len(a):
+            raise CapError("triangle_queries: skip must hold one id per triangle, got %d for %d" % (len(ids), len(a)))
+        q.view(np.uint32)[:, 3] = ids
+        return q
+
+    def scene_triangle_queries(self, ids):
+        """The (N, 12) float32 query rows of the scene's own triangles `ids` (global ids): the vertices as uploaded (or as last
+        updated), with `skip` set to the triangle's own id -- the starting point of a self-intersection test.  A triangle that shares
+        a vertex or an edge with the query touches it and is listed: filtering adjacency out is the caller's job."""
+        if self._scene_host is None:
+            raise CapError("scene_triangle_queries: no scene uploaded")
+        pos, idx, meshes = self._scene_host
+        if not isinstance(pos, np.ndarray):  # the device tensor of the last update_vertices
+            pos = pos.cpu().numpy()
+        ids = np.asarray(ids, np.int64).reshape(-1)
+        total = int(self._tri_end[-1]) if len(self._tri_end) else 0
+        if len(ids) and (ids.min() < 0 or ids.max() >= total):
+            raise CapError("scene_triangle_queries: ids must be in 0 .. %d" % (total - 1))
+        mesh = np.searchsorted(self._tri_end, ids, side="right")
+        first = np.concatenate([[0], self._tri_end[:-1]])[mesh] if len(ids) else ids
+        at = meshes[mesh, 3].astype(np.int64)[:, None] + 3 * (ids - first)[:, None] + np.arange(3)
+        v = pos[meshes[mesh, 1].astype(np.int64)[:, None] + idx[at].astype(np.int64)]
+        return self.triangle_queries(v[:, 0], v[:, 1], v[:, 2], ids)
 
     def _cell_boxes(self, origin, cell, dims):
         """(dims, the (nx * ny * nz, 8) float32 CapBoxDesc rows of the grid's cells on this context's device): per axis cell i spans

@@ -252,6 +252,20 @@ struct OverlapArgs
     float         slack;
 };
 void launch_overlap_boxes(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapArgs& a, const RayFilter* f, uint32_t depth);
+// Triangle overlap queries (cap_overlap_triangles, overlap.hip k_overlap_triangles): queries = CapTriangleDesc records (three float4: (a,
+// skip bits) (b, -) (c, -)); out, k, counts, resume, slack, depth and f as OverlapArgs' -- the walk is the box query's against the box
+// of the query's three vertices.
+struct OverlapTriArgs
+{
+    const float4* queries;
+    uint32_t      n;
+    uint32_t*     out;
+    uint32_t      k;
+    uint32_t*     counts;
+    uint32_t      resume;
+    float         slack;
+};
+void launch_overlap_triangles(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapTriArgs& a, const RayFilter* f, uint32_t depth);
 // Over the instance table (cap_overlap_instances, overlap.hip k_overlap_inst): the boxes are in world space, a.out = pages of k triangle
 // ids and inst_out = pages of k instances (both NULL when k = 0) -- the cursor is slot k - 1 of both.  a.slack is not read: the slack is
 // per box and instance (cap_near.h overlap_slack).  descs, near and xw_max as ClosestInstArgs'; bvh, tl, f and depth as

@@ -1,9 +1,10 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip), cap_overlap_boxes and cap_overlap_instances (overlap.hip) and cap_winding_numbers and cap_winding_instances (winding.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip), cap_overlap_boxes, cap_overlap_instances and cap_overlap_triangles (overlap.hip) and cap_winding_numbers and cap_winding_instances (winding.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
 #include <initializer_list>
+#include <type_traits>
 
 #include "cap_context.h"
 #include "query_ranges.h"
@@ -372,23 +373,29 @@ int closest_query(CapContext* c, const char* what, const CapPointDesc* points, u
 
 // cap_overlap_boxes (overlap.hip k_overlap_boxes): the triangles that meet each box, pages of k ids and / or counts, on the binary tree
 // alone; with `instanced` cap_overlap_instances (k_overlap_inst): world-space boxes over the instance table, pages of k (triangle,
-// instance) pairs.  closest_query's checks for a multi call, word for word, with "boxes", "triangles" and "instances" as the arrays' names.
-int overlap_query(CapContext* c, const char* what, const CapBoxDesc* boxes, uint64_t n, uint32_t k, uint32_t* ids, uint32_t* inst, bool instanced,
+// instance) pairs; with Record = CapTriangleDesc cap_overlap_triangles (k_overlap_triangles): the triangles that meet each query
+// triangle.  closest_query's checks for a multi call, word for word, with "boxes" (or "queries"), "triangles" and "instances" as the
+// arrays' names.
+template <typename Record>
+int overlap_query(CapContext* c, const char* what, const Record* queries, uint64_t n, uint32_t k, uint32_t* ids, uint32_t* inst, bool instanced,
                   uint32_t* counts, uint32_t flags, const CapTraceOptions* options)
 {
+    constexpr bool tri = std::is_same<Record, CapTriangleDesc>::value;
     static_assert(sizeof(CapBoxDesc) == 2 * sizeof(float4), "a box record is the kernel's two float4");
+    static_assert(sizeof(CapTriangleDesc) == 3 * sizeof(float4), "a triangle record is the kernel's three float4");
     if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
-    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a box", what, options->ray_flags);
+    if (options && options->ray_flags)
+        return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: facing and first hit have no meaning for a %s", what, options->ray_flags, tri ? "triangle" : "box");
     QueryFilter flt;
     if (const int rc = multi_rules(c, what, k, flags, options, instanced ? "triangles and instances" : "triangles", ids || (instanced && inst), counts, flt))
         return rc;
     if (const int rc = query_state(c, what)) return rc;
     if (instanced && c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
     if (n == 0) return CAP_OK;
-    if (!boxes || (k && !ids) || (k && instanced && !inst))
+    if (!queries || (k && !ids) || (k && instanced && !inst))
         return instanced ? fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer (k = %u needs triangles and instances)", what, k)
                          : fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    if (const int rc = check_ranges(what, n, {range("boxes", boxes, sizeof(CapBoxDesc), 16), range("triangles", ids, (uint64_t)k * sizeof(uint32_t), 4),
+    if (const int rc = check_ranges(what, n, {range(tri ? "queries" : "boxes", queries, sizeof(Record), 16), range("triangles", ids, (uint64_t)k * sizeof(uint32_t), 4),
                                               range("instances", inst, (uint64_t)k * sizeof(uint32_t), 4), range("counts", counts, sizeof(uint32_t), 4)}))
         return rc;
     QueryRun run;
@@ -396,7 +403,13 @@ int overlap_query(CapContext* c, const char* what, const CapBoxDesc* boxes, uint
     if (instanced) use_instance_pools(run);
     const RayFilter* f      = flt.scene();
     const uint32_t   resume = (flags & CAP_MULTI_CONTINUE) ? 1u : 0u;
-    return for_each_chunk(run, boxes, n, [&](const QueryArgs& chunk, uint64_t first) {
+    return for_each_chunk(run, queries, n, [&](const QueryArgs& chunk, uint64_t first) {
+        if constexpr (tri)
+        {
+            launch_overlap_triangles(run.cfg, run.bvh, OverlapTriArgs{chunk.rays, chunk.n, at(ids, first * k), k, at(counts, first), resume, run.slack}, f,
+                                     c->bvh_info.max_depth);
+            return run.traced("k_overlap_triangles", first);
+        }
         // (the instanced kernel takes its slack per box and instance: cap_near.h)
         const OverlapArgs a{chunk.rays, chunk.n, at(ids, first * k), k, at(counts, first), resume, instanced ? 0.f : run.slack};
         if (!instanced)
@@ -460,6 +473,12 @@ int cap_overlap_instances(CapContext* c, const CapBoxDesc* device_boxes, uint64_
                           uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options)
 {
     return overlap_query(c, "cap_overlap_instances", device_boxes, n, k, device_triangles, device_instances, true, device_counts, multi_flags, options);
+}
+
+int cap_overlap_triangles(CapContext* c, const CapTriangleDesc* device_queries, uint64_t n, uint32_t k, uint32_t* device_triangles, uint32_t* device_counts,
+                          uint32_t multi_flags, const CapTraceOptions* options)
+{
+    return overlap_query(c, "cap_overlap_triangles", device_queries, n, k, device_triangles, nullptr, false, device_counts, multi_flags, options);
 }
 
 int cap_winding_instances(CapContext* c, const CapPointDesc* device_points, uint64_t n, float beta, float* device_winding, uint32_t* device_visits)

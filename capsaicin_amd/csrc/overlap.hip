@@ -17,6 +17,9 @@
 //
 // The instanced form (cap_overlap_instances, k_overlap_inst) is at the end of the file: world-space boxes over the instance table, the
 // pairs (instance, triangle) whose world record meets the box, in (instance, triangle) order.
+//
+// Behind the instanced form: the triangle form (cap_overlap_triangles, k_overlap_triangles) -- a query triangle for the box, a 17-axis
+// triangle-against-triangle predicate for the 13 axes, the same walk against the box of the query's vertices.
 #include "cap_kernels.h"
 #include "cap_near.h"        // the prune of the instanced form
 #include "cap_query_walk.h"  // TopWalk, and the launch dispatchers
@@ -380,6 +383,195 @@ __global__ __launch_bounds__(kBlock, overlap_inst_blocks(STACK, K)) void k_overl
         }
     }
 }
+
+// ---- triangle against triangle (cap_overlap_triangles) ----
+// For every query triangle (A0, A1, A2) the scene triangles that meet it, by the 17-axis separating-axis predicate of
+// include/capsaicin_hip.h ("triangle overlap queries") in the frame at A0; pages, counts and cursor as k_overlap_boxes, whose walk this is.
+//
+// Pruning: step 1 of the predicate -- the coordinate axes, on absolute coordinates, exact -- makes "the predicate holds" imply "the box
+// of the COMPUTED scene vertices meets the box [min A, max A] of the query's vertices" exactly: that is step (i) of DESIGN.md "Box overlap
+// queries", Pruning, with [lo, hi] = [min A, max A], and steps (ii) to (iv) follow unchanged.  So the walk is box_node_step against that
+// box grown by run.slack.
+//
+// Per query, once: p1, p2, n = cross(p1, p2), the three cross(n, f_i) and the [min s, max s] intervals of those four axes -- the
+// operations of the contract, hoisted.  An interval with a NaN among its three values is stored as [-inf, +inf], which nothing lies
+// beyond: the axis separates nothing, as the contract says.
+__device__ __forceinline__ v3    cross_c(v3 u, v3 v) { return v3{u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x}; }
+__device__ __forceinline__ float dot_c(v3 a, v3 b) { return dot_c(a.x, a.y, a.z, b.x, b.y, b.z); }
+
+// min > max of the contract for two triples, where min and max hand a NaN on: every t above every s or every t below every s, and
+// nothing with a NaN among the six.  fminf and fmaxf drop a NaN, so the three unordered tests stand beside them.
+__device__ __forceinline__ bool axis_separates(float s0, float s1, float s2, float t0, float t1, float t2)
+{
+    const bool  nan  = __builtin_isunordered(s0, s1) || __builtin_isunordered(s2, t0) || __builtin_isunordered(t1, t2);
+    const float smin = fminf(fminf(s0, s1), s2), smax = fmaxf(fmaxf(s0, s1), s2);
+    const float tmin = fminf(fminf(t0, t1), t2), tmax = fmaxf(fmaxf(t0, t1), t2);
+    return !nan && (tmin > smax || tmax < smin);
+}
+
+// [min s, max s] of one of the query's own axes; with a NaN among them [-inf, +inf]
+struct Interval
+{
+    float lo, hi;
+};
+__device__ __forceinline__ Interval interval_of(float s0, float s1, float s2)
+{
+    const float inf = __builtin_inff();
+    const bool  nan = __builtin_isunordered(s0, s1) || __builtin_isunordered(s2, s2);
+    return Interval{nan ? -inf : fminf(fminf(s0, s1), s2), nan ? inf : fmaxf(fmaxf(s0, s1), s2)};
+}
+
+struct TriFrame
+{
+    v3       a0, p1, p2;    // A0; p1 = A1 - A0, p2 = A2 - A0 (p0 = A0 - A0 is +0)
+    v3       lo, hi;        // min / max of the three vertices, absolute: the coordinate axes
+    v3       n, c0, c1, c2; // cross(p1, p2); cross(n, f_i), f0 = p1, f1 = p2 - p1, f2 = p0 - p2
+    Interval in, i0, i1, i2;
+};
+__device__ __forceinline__ Interval interval_on(v3 L, v3 p0, v3 p1, v3 p2) { return interval_of(dot_c(L, p0), dot_c(L, p1), dot_c(L, p2)); }
+__device__ __forceinline__ TriFrame tri_frame(const float4 qa, const float4 qb, const float4 qc)
+{
+    TriFrame t;
+    const v3 a1 = mk3(qb.x, qb.y, qb.z), a2 = mk3(qc.x, qc.y, qc.z);
+    t.a0 = mk3(qa.x, qa.y, qa.z);
+    t.lo = mk3(fminf(fminf(t.a0.x, a1.x), a2.x), fminf(fminf(t.a0.y, a1.y), a2.y), fminf(fminf(t.a0.z, a1.z), a2.z));
+    t.hi = mk3(fmaxf(fmaxf(t.a0.x, a1.x), a2.x), fmaxf(fmaxf(t.a0.y, a1.y), a2.y), fmaxf(fmaxf(t.a0.z, a1.z), a2.z));
+    const v3 p0 = t.a0 - t.a0;
+    t.p1 = a1 - t.a0, t.p2 = a2 - t.a0;
+    t.n  = cross_c(t.p1, t.p2);
+    t.c0 = cross_c(t.n, t.p1), t.c1 = cross_c(t.n, t.p2 - t.p1), t.c2 = cross_c(t.n, p0 - t.p2);
+    t.in = interval_on(t.n, p0, t.p1, t.p2);
+    t.i0 = interval_on(t.c0, p0, t.p1, t.p2), t.i1 = interval_on(t.c1, p0, t.p1, t.p2), t.i2 = interval_on(t.c2, p0, t.p1, t.p2);
+    return t;
+}
+
+// one of the query's own axes against the scene triangle: the t_j beyond the stored interval
+__device__ __forceinline__ bool own_axis(v3 L, Interval s, v3 q0, v3 q1, v3 q2)
+{
+    const float t0 = dot_c(L, q0), t1 = dot_c(L, q1), t2 = dot_c(L, q2);
+    return all_above(t0, t1, t2, s.hi) || all_below(t0, t1, t2, s.lo);
+}
+// an axis that depends on the scene triangle: all six values
+__device__ __forceinline__ bool pair_axis(v3 L, v3 p0, v3 p1, v3 p2, v3 q0, v3 q1, v3 q2)
+{
+    return axis_separates(dot_c(L, p0), dot_c(L, p1), dot_c(L, p2), dot_c(L, q0), dot_c(L, q1), dot_c(L, q2));
+}
+
+// The predicate of the contract for the record (t0, t1, t2) = (v0, e1, e2): one rounded binary32 operation per operation written there.
+// Three groups of axes with one return each: the coordinate axes, the two normals, the other fifteen.
+__device__ __forceinline__ bool tri_meets(const TriFrame& t, const float4 t0, const float4 t1, const float4 t2)
+{
+    const v3 b0 = mk3(t0.x, t0.y, t0.z), e1 = mk3(t0.w, t1.x, t1.y), e2 = mk3(t1.z, t1.w, t2.x);
+    const v3 b1 = b0 + e1, b2 = b0 + e2;
+    // 1. the coordinate axes, absolute coordinates
+    if (all_above(b0.x, b1.x, b2.x, t.hi.x) || all_below(b0.x, b1.x, b2.x, t.lo.x) || all_above(b0.y, b1.y, b2.y, t.hi.y) ||
+        all_below(b0.y, b1.y, b2.y, t.lo.y) || all_above(b0.z, b1.z, b2.z, t.hi.z) || all_below(b0.z, b1.z, b2.z, t.lo.z))
+        return false;
+    // 2. the frame at A0
+    const v3 p0 = t.a0 - t.a0;
+    const v3 q0 = b0 - t.a0, q1 = b1 - t.a0, q2 = b2 - t.a0;
+    // 3. the two normals
+    const v3 m = cross_c(e1, e2);
+    if (own_axis(t.n, t.in, q0, q1, q2) || pair_axis(m, p0, t.p1, t.p2, q0, q1, q2)) return false;
+    // the nine cross(f_i, g_j), the three cross(n, f_i), the three cross(m, g_j)
+    const v3 f[3] = {t.p1, t.p2 - t.p1, p0 - t.p2};
+    const v3 g[3] = {e1, q2 - q1, q0 - q2};
+    bool     sep  = own_axis(t.c0, t.i0, q0, q1, q2) || own_axis(t.c1, t.i1, q0, q1, q2) || own_axis(t.c2, t.i2, q0, q1, q2);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+    {
+        sep |= pair_axis(cross_c(m, g[j]), p0, t.p1, t.p2, q0, q1, q2);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) sep |= pair_axis(cross_c(f[i], g[j]), p0, t.p1, t.p2, q0, q1, q2);
+    }
+    return !sep;
+}
+
+// a query that is traversed: nine finite coordinates (a NaN fails its comparison)
+__device__ __forceinline__ bool tri_ok(const float4 a, const float4 b, const float4 c)
+{
+    const float inf = __builtin_inff();
+    return fabsf(a.x) < inf && fabsf(a.y) < inf && fabsf(a.z) < inf && fabsf(b.x) < inf && fabsf(b.y) < inf && fabsf(b.z) < inf && fabsf(c.x) < inf &&
+           fabsf(c.y) < inf && fabsf(c.z) < inf;
+}
+
+// Workgroups per CU.  LDS is overlap_blocks'.  Registers: the frame is 35 words beside the grown box, the list and the walk, and the
+// fifteen axes of the last group keep the scene triangle's nine frame coordinates and six edge words live across them.  Compiled
+// without a limit that binds (STACK = 64, two workgroups) the kernel takes 99 (K = 1), 106 (4), 114 (8) and 130 (16) VGPRs
+// (tools/kernel_regs.sh; the table is in DESIGN.md "Triangle overlap queries"): four waves per SIMD leave 128 each and three leave 168,
+// which those sizes admit anyway, so the limits below cost no instantiation a register, let alone scratch.
+constexpr int overlap_tri_blocks(int STACK, int K)
+{
+    const int by_lds  = STACK <= 16 ? 8 : STACK <= 24 ? 6 : STACK <= 32 ? 5 : 2;
+    const int by_regs = K <= 8 ? 4 : 3;
+    return by_lds < by_regs ? by_lds : by_regs;
+}
+
+// FILTER as in k_overlap_boxes.  a.queries: three float4 per query, (a, skip) (b, -) (c, -); a scene triangle whose global id is
+// `skip` is as if it were not in the scene, like one the mask rejects.
+template <int STACK, int K, bool FILTER>
+__global__ __launch_bounds__(kBlock, overlap_tri_blocks(STACK, K)) void k_overlap_triangles(BvhDev bvh, OverlapTriArgs a, RayFilter f)
+{
+    __shared__ uint32_t lds_stack[STACK * kBlock];
+    uint32_t* const     stack = lds_stack + threadIdx.x;
+    const int           skip  = K - (int)a.k;  // the placeholders
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += gridDim.x * kBlock)
+    {
+        const float4    qa = a.queries[3 * (size_t)i], qb = a.queries[3 * (size_t)i + 1], qc = a.queries[3 * (size_t)i + 2];
+        uint32_t* const page = a.out + (size_t)i * a.k;
+        IdList<K>       L;
+        L.init(a.k);
+        uint32_t count = 0u;
+        if (tri_ok(qa, qb, qc))
+        {
+            // only ids above the cursor -- slot k - 1 of the query's page -- count and are listed; ~0 (a short page's last slot) admits nothing
+            const bool     open = a.resume == 0u;
+            const uint32_t gc   = open ? 0u : page[a.k - 1u];
+            const uint32_t own  = f2u(qa.w);
+            const TriFrame t    = tri_frame(qa, qb, qc);
+            const float    glx = t.lo.x - a.slack, gly = t.lo.y - a.slack, glz = t.lo.z - a.slack;
+            const float    ghx = t.hi.x + a.slack, ghy = t.hi.y + a.slack, ghz = t.hi.z + a.slack;
+            int            node = bvh.root, sp = 0;
+            while (bvh.tri_count != 0u)
+            {
+                if (node >= 0)
+                {
+                    if (box_node_step<STACK>(bvh, glx, gly, glz, ghx, ghy, ghz, stack, node, sp)) continue;
+                }
+                else
+                {
+                    const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                    for (uint32_t leaf = first; leaf <= last; ++leaf)
+                    {
+                        const uint32_t gid = f2u(bvh.tris[4 * (size_t)leaf + 3].x);
+                        if (gid == own) continue;
+                        if constexpr (FILTER)
+                            if ((f.tri_mask[gid] & f.mask) == 0u) continue;
+                        const float4 t0 = bvh.tris[4 * (size_t)leaf + 0], t1 = bvh.tris[4 * (size_t)leaf + 1], t2 = bvh.tris[4 * (size_t)leaf + 2];
+                        if (!tri_meets(t, t0, t1, t2)) continue;
+                        if (open || gid > gc)
+                        {
+                            ++count;
+                            L.offer(gid);
+                        }
+                    }
+                }
+                if (sp == 0) break;
+                node = (int)stack[(--sp) * kBlock];
+            }
+        }
+        // (a query that was not traversed: the list as init left it, k empty slots, and count 0)
+        if (a.counts) a.counts[i] = count;
+        for (uint32_t s = 0; s < a.k; ++s)
+        {
+            uint32_t gid = kInvalidId;
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (j - skip == (int)s) gid = L.g[j];
+            page[s] = gid;
+        }
+    }
+}
 }  // namespace
 
 void launch_overlap_boxes(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapArgs& a, const RayFilter* f, uint32_t depth)
@@ -403,6 +595,19 @@ void launch_overlap_instances(const LaunchCfg& cfg, const BvhDev& bvh, const Ove
         with_k_bucket(a.a.k, [&](auto K) {
             with_flag(f.tri_mask != nullptr, [&](auto FILTER) {
                 launch_points<k_overlap_inst<decltype(S)::value, decltype(K)::value, decltype(FILTER)::value>>(cfg, a.a.n, bvh, a, tl, f);
+            });
+        });
+    });
+}
+void launch_overlap_triangles(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapTriArgs& a, const RayFilter* f, uint32_t depth)
+{
+    BvhDev b   = bvh;
+    b.wide8_ok = 0;
+    const RayFilter rf = f ? *f : RayFilter{};
+    with_stack_class(depth, [&](auto S) {
+        with_k_bucket(a.k, [&](auto K) {
+            with_flag(f && f->tri_mask, [&](auto FILTER) {
+                launch_points<k_overlap_triangles<decltype(S)::value, decltype(K)::value, decltype(FILTER)::value>>(cfg, a.n, b, a, rf);
             });
         });
     });

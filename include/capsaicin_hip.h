@@ -732,6 +732,62 @@ int cap_overlap_instances(CapContext* ctx, const CapBoxDesc* device_boxes, uint6
                           uint32_t* device_instances /* n*k */, uint32_t* device_counts /* n or NULL */, uint32_t multi_flags,
                           const CapTraceOptions* options /* may be NULL */);
 
+/* ---- triangle overlap queries: the triangles of the scene that meet a given triangle (contact, self-intersection, cutting, clearance) ----
+ * cap_overlap_boxes with a triangle for the box: for every query triangle (a, b, c) the triangles of the uploaded scene that meet it,
+ * on the scene's binary tree -- the first k of them by triangle id, their number, or both.  Current under cap_scene_update_vertices +
+ * cap_bvh_refit like every other query.  A segment (two vertices equal) and a point (all three equal) are legal queries.
+ *
+ * The predicate is the separating-axis test of two triangles with 17 axes, in the frame of the query's first vertex, defined on the
+ * query's vertices as given and on the STORED record (v0, e1, e2) of the scene triangle.  Every operation written is one rounded
+ * binary32 operation, there is no fused multiply-add, dot is the point queries' dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z and
+ * cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x) -- so a plain float32 brute force is bit-identical to the
+ * kernel.  Query vertices A0 = a, A1 = b, A2 = c.  Scene vertices B0 = v0, B1 = fl(v0 + e1), B2 = fl(v0 + e2): the computed vertices
+ * of cap_overlap_boxes.  The triangles meet unless one of these separates them (each is a pure comparison, the order of evaluation is
+ * free):
+ *   1. Coordinate axes, absolute coordinates, exact comparisons: for x, y, z:
+ *        min(B0, B1, B2) > max(A0, A1, A2)  or  max(B0, B1, B2) < min(A0, A1, A2).
+ *   2. The frame at A0: p_j = A_j - A0 (so p_0 = 0), q_j = B_j - A0; query edges f0 = p1, f1 = p2 - p1, f2 = p0 - p2; scene edges
+ *      g0 = e1 (as stored), g1 = q2 - q1, g2 = q0 - q2; normals n = cross(p1, p2), m = cross(e1, e2).
+ *   3. Seventeen axes L: n; m; cross(f_i, g_j) for the nine pairs; cross(n, f_i), i = 0, 1, 2; cross(m, g_j), j = 0, 1, 2.  For each,
+ *        s_j = dot(L, p_j), t_j = dot(L, q_j) for j = 0, 1, 2 (all six are evaluated);
+ *        min(t_0, t_1, t_2) > max(s_0, s_1, s_2)  or  max(t_0, t_1, t_2) < min(s_0, s_1, s_2).
+ * min and max hand a NaN on, and a NaN fails its comparison: an axis with a NaN among its six values separates nothing.  A zero axis
+ * has s = t = 0 and separates nothing.  Touching is overlap: a shared vertex, a shared edge, a vertex in a face and coplanar contact all
+ * count; one ulp back, where the frame is exact, they do not.
+ *
+ * Completeness.  For two triangles of non-zero area the 17 axes are the complete set in the reals: the facet normals of the Minkowski
+ * difference (n, m and the nine cross(f_i, g_j)) and, for the coplanar case, in which all of those are parallel to n, the in-plane
+ * edge normals cross(n, f_i) and cross(m, g_j).  Step 1 is what the walk prunes with; in the reals it is implied and costs nothing.
+ * Degenerate triangles.  With a zero-area triangle on either side the axes can fail to separate a pair that does not meet (two coplanar
+ * segments that do not cross: every cross product of the pair vanishes or lies along the common normal) and such a pair is listed.
+ * They never separate a pair that meets.  A point query a = b = c and a segment query against scene triangles of non-zero area are
+ * still decided, by m, cross(f, g_j) and cross(m, g_j).
+ * The float32 function is the definition: where a product rounds, a contact can be lost or won by an ulp.  It is not symmetric in
+ * float32 -- swapping the roles of the two triangles changes the frame, which is the query's.
+ *
+ * skip: a scene triangle whose global id equals `skip` is no candidate -- applied like the mask, it is neither counted nor listed.
+ * 0xFFFFFFFF (no triangle has that id) or any id beyond the scene skips nothing.  A query built from the scene's own triangle g with
+ * skip = g lists what touches g, its edge and vertex neighbours included: filtering adjacency is the caller's.
+ *
+ * Candidates (mask filter and predicate), their order (id ascending), pages, the 0xFFFFFFFF fill, device_counts (all candidates, not
+ * capped at k; with CAP_MULTI_CONTINUE: of those above the cursor), k = 0 counts only, the CAP_MULTI_CONTINUE cursor in slot k - 1,
+ * masks, conventions, errors and their order are cap_overlap_boxes' word for word, with the three ranges "queries" (48 B per query,
+ * 16-byte aligned), "triangles" and "counts" (4-byte aligned).  A query with a non-finite coordinate is not traversed: a page of
+ * 0xFFFFFFFF and count 0, with CAP_MULTI_CONTINUE too.  The pad words are not read.
+ * Not covered: instances and objects; a node cull finer than the box of the query's vertices; the intersection segment itself;
+ * adjacency filtering; exactness for zero-area pairs; per-query masks. */
+typedef struct CapTriangleDesc /* 48 B, 16-byte aligned */
+{
+    float    a[3];
+    uint32_t skip; /* a scene triangle with this global id is no candidate; 0xFFFFFFFF: none */
+    float    b[3];
+    uint32_t pad0; /* not read */
+    float    c[3];
+    uint32_t pad1; /* not read */
+} CapTriangleDesc;
+int cap_overlap_triangles(CapContext* ctx, const CapTriangleDesc* device_queries, uint64_t n, uint32_t k, uint32_t* device_triangles /* n*k ids */,
+                          uint32_t* device_counts /* n or NULL */, uint32_t multi_flags, const CapTraceOptions* options /* may be NULL */);
+
 /* ---- instanced ray queries: N transformed instances of the uploaded scene, or of objects of it, under a device-built top-level tree ----
  * The uploaded scene and the trees cap_bvh_build makes of it are read as OBJECT space; cap_instances_set installs a table of N
  * instances of it, each with an object-to-world transform and an 8-bit mask, and builds a top-level tree (TLAS) over the instances'

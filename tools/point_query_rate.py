@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Throughput of the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances,
-cap_closest_instances_multi, cap_signed_distance_instances), of the box overlap queries (cap_overlap_boxes, cap_overlap_instances) and of cap_winding_numbers and cap_winding_instances on the 262 k-triangle hall -- not part of
+cap_closest_instances_multi, cap_signed_distance_instances), of the box overlap queries (cap_overlap_boxes, cap_overlap_instances), of cap_overlap_triangles and of cap_winding_numbers and cap_winding_instances on the 262 k-triangle hall -- not part of
 bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
@@ -53,6 +53,11 @@ same K on the same centres, at the radius that gives the same mean candidate cou
 --boxes together with --instances N runs cap_overlap_instances on the --instances layout with the same cubes as world boxes:
 mboxes_per_s, mean_candidates (pairs per box) and the share of empty boxes, and from the same process the flat cap_overlap_boxes rate
 on the same boxes (flat_ms, flat_mboxes_per_s, flat_mean_candidates, ratio_to_flat).
+
+--triangles runs cap_overlap_triangles on one query triangle per point: vertices uniform in the cube of edge --extent E x the scene's
+size (default 0.005) around the point, so its edges are about E x the scene's size -- pages of --k K ids (default 4; --counts as for --boxes):
+mtriangles_per_s, mean_candidates and the share of empty queries.  Beside it, measured in the same process, cap_overlap_boxes on the
+bounding boxes of the same triangles (boxes_ms, mboxes_per_s, boxes_mean_candidates) and ratio_to_boxes = triangle rate / box rate.
 
 Point sets, each of --points points (rounded down to a cube for the grid):
   grid      a regular grid through the scene's box, in raster order (x fastest);
@@ -122,10 +127,13 @@ def main():
     ap.add_argument("--beta", type=float, default=2.0)
     ap.add_argument("--boxes", action="store_true")
     ap.add_argument("--extent", type=float, default=0.005)
+    ap.add_argument("--triangles", action="store_true")
     a = ap.parse_args()
     if a.boxes and (a.winding or a.signed):
         ap.error("--boxes goes with --k, --counts, --extent and --instances only")
-    if a.boxes and a.k is None:
+    if a.triangles and (a.winding or a.signed or a.boxes or a.instances is not None):
+        ap.error("--triangles goes with --k, --counts and --extent only")
+    if (a.boxes or a.triangles) and a.k is None:
         a.k = 4  # (before `out` below is sized: the comparison run writes pages of k records into it)
     if a.winding and (a.signed or a.k is not None):
         ap.error("--winding goes alone or with --instances N: the winding number takes no sign table or pages")
@@ -148,7 +156,7 @@ def main():
     size = float((hi - lo).max())
     if a.radius_frac is not None:
         a.radius = a.radius_frac * size
-    if a.counts and a.k is None and not a.boxes:
+    if a.counts and a.k is None and not a.boxes and not a.triangles:
         ap.error("--counts needs --k")
     side = int(round(a.points ** (1.0 / 3.0)))
     while side ** 3 > a.points:
@@ -209,6 +217,34 @@ def main():
                                   mean_visits=[round(float(mean[0]), 2), round(float(mean[1]), 2)], inside=round(float((w >= 0.5).float().mean()), 4),
                                   table_build_ms=round(wn.ms, 3), bvh_build_ms=round(info.build_ms, 3),
                                   table={k: v for k, v in wn.as_dict().items() if k != "ms"})), flush=True)
+        r.close()
+        return
+    if a.triangles:
+        k = a.k
+        if k == 0 and not a.counts:
+            ap.error("--triangles --k 0 needs --counts")
+        ids = torch.empty((n * max(k, 1),), dtype=torch.int32, device=dev)
+        tri_cnt, box_cnt = torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+        head.update(k=k, counts=a.counts, extent=a.extent)
+        del head["radius"]
+        for name, xyz in sets:
+            v = (xyz[:, None, :] + (rng.random((n, 3, 3)) - 0.5) * a.extent * size).astype(np.float32)
+            qs = torch.as_tensor(capi.Renderer.triangle_queries(v[:, 0], v[:, 1], v[:, 2]), device=dev).contiguous()
+            b = np.zeros((n, 8), np.float32)
+            b[:, 0:3], b[:, 4:7] = v.min(1), v.max(1)
+            boxes = torch.as_tensor(b, device=dev).contiguous()
+            torch.cuda.synchronize()
+            sec = timed(r, lambda: capi._check(L.cap_overlap_triangles(r.ctx, qs.data_ptr(), n, k, ids.data_ptr() if k else None,
+                                                                       tri_cnt.data_ptr() if a.counts else None, 0, None), "cap_overlap_triangles"), a.reps, a.warmup)
+            bsec = timed(r, lambda: capi._check(L.cap_overlap_boxes(r.ctx, boxes.data_ptr(), n, k, ids.data_ptr() if k else None,
+                                                                    box_cnt.data_ptr() if a.counts else None, 0, None), "cap_overlap_boxes"), a.reps, a.warmup)
+            capi._check(L.cap_overlap_triangles(r.ctx, qs.data_ptr(), n, 0, None, tri_cnt.data_ptr(), 0, None), "cap_overlap_triangles")
+            capi._check(L.cap_overlap_boxes(r.ctx, boxes.data_ptr(), n, 0, None, box_cnt.data_ptr(), 0, None), "cap_overlap_boxes")
+            r.sync()
+            print(json.dumps(dict(head, set=name, ms=round(sec * 1e3, 3), mtriangles_per_s=round(n / sec / 1e6, 2),
+                                  mean_candidates=round(float(tri_cnt.double().mean()), 3), empty=round(float((tri_cnt == 0).float().mean()), 4),
+                                  boxes_ms=round(bsec * 1e3, 3), mboxes_per_s=round(n / bsec / 1e6, 2),
+                                  boxes_mean_candidates=round(float(box_cnt.double().mean()), 3), ratio_to_boxes=round(bsec / sec, 3))), flush=True)
         r.close()
         return
     if a.boxes:
