@@ -292,6 +292,7 @@ SYMBOLS = {
     "cap_debug_query_ranges": (_i, [_u64, _u32, _vp, _vp, _vp]),
     "cap_debug_closest_instance_bound": (_i, [_vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "cap_debug_overlap_instance_prune": (_i, [_vp] * 17),
+    "cap_debug_overlap_world_node": (_i, [_vp] * 12),
     "cap_render": (_i, [_vp, _u32, _u32, _u32, _u32]),
     "cap_accum_reset": (_i, [_vp]),
     "cap_accum_import": (_i, [_vp, _vp, _u64]),
@@ -321,6 +322,7 @@ SYMBOLS = {
     "cap_overlap_boxes": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_overlap_instances": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_overlap_triangles": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
+    "cap_overlap_triangles_instances": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_pseudonormals_build": (_i, [_vp, C.POINTER(PseudonormalsInfo)]),
     "cap_pseudonormals_drop": (_i, [_vp]),
     "cap_pseudonormals_readback": (_i, [_vp, _vp]),
@@ -1123,10 +1125,19 @@ class Renderer:
         the results come back as numpy).  The return value, counts=, resume=, sync and mask= are overlap_boxes'."""
         return self._multi("cap_overlap_triangles", tris, 12, "tris", 0, False, k, counts, resume, sync, (self.trace_options(None, mask),))
 
+    def overlap_triangles_instances(self, tris, k, counts=False, resume=None, sync=True, mask=None):
+        """The (instance, triangle) pairs whose world-space triangle meets each WORLD-space query triangle, the first k in (instance,
+        triangle) order (cap_overlap_triangles_instances).  tris: (N, 12) float32 CapTriangleDesc rows as overlap_triangles', with
+        column 7 carrying the BITS of `skip_instance`: the pair (skip_instance, skip) is no candidate (skip = 0xFFFFFFFF: nothing is
+        skipped).  triangle_queries() packs them, instance_triangle_queries() makes them of the placed scene's own triangles.  The
+        return value, counts=, resume=, sync and mask= are overlap_instances'.  Needs set_instances()."""
+        return self._multi("cap_overlap_triangles_instances", tris, 12, "tris", 0, True, k, counts, resume, sync, (self.trace_options(None, mask),))
+
     @staticmethod
-    def triangle_queries(a, b, c, skip=None):
+    def triangle_queries(a, b, c, skip=None, skip_instance=None):
         """(N, 12) float32 CapTriangleDesc rows of (N, 3) vertices a, b, c; skip: None (0xFFFFFFFF: nothing is skipped) or N global
-        triangle ids, whose bits go into column 3.  The pad columns hold 0."""
+        triangle ids, whose bits go into column 3; skip_instance: None (column 7 stays 0) or N instance indices, whose bits go into
+        column 7 -- read by overlap_triangles_instances alone.  The last pad column holds 0."""
         a, b, c = (np.asarray(x, np.float32).reshape(-1, 3) for x in (a, b, c))
         if not len(a) == len(b) == len(c):
             raise CapError("triangle_queries: a, b and c must have one row per triangle, got %d, %d and %d" % (len(a), len(b), len(c)))
@@ -1136,7 +1147,35 @@ class Renderer:
         if len(ids) != len(a):
             raise CapError("triangle_queries: skip must hold one id per triangle, got %d for %d" % (len(ids), len(a)))
         q.view(np.uint32)[:, 3] = ids
+        if skip_instance is not None:
+            inst = np.asarray(skip_instance, np.int64).astype(np.uint32).reshape(-1)
+            if len(inst) != len(a):
+                raise CapError("triangle_queries: skip_instance must hold one index per triangle, got %d for %d" % (len(inst), len(a)))
+            q.view(np.uint32)[:, 7] = inst
         return q
+
+    def instance_triangle_queries(self, transforms, instances, ids):
+        """The (N, 12) float32 query rows of the scene's triangles `ids` (global ids) as placed by transforms[instances] ((I, 3, 4)
+        object-to-world, as given to set_instances): the vertices of the WORLD record of cap_closest_instances -- v0w,
+        fl(v0w + e1w), fl(v0w + e2w), in float32 by the contract's arithmetic -- with the skip pair set to (instance, id): the
+        starting point of a self-contact test of an assembly with overlap_triangles_instances."""
+        f32 = np.float32
+        M = np.asarray(transforms, f32).reshape(-1, 3, 4)
+        inst = np.asarray(instances, np.int64).reshape(-1)
+        ids = np.asarray(ids, np.int64).reshape(-1)
+        if len(inst) != len(ids):
+            raise CapError("instance_triangle_queries: one instance per id, got %d for %d" % (len(inst), len(ids)))
+        if len(inst) and (inst.min() < 0 or inst.max() >= len(M)):
+            raise CapError("instance_triangle_queries: instances must be in 0 .. %d" % (len(M) - 1))
+        q = self.scene_triangle_queries(ids)
+        v0, e1, e2 = q[:, 0:3], q[:, 4:7] - q[:, 0:3], q[:, 8:11] - q[:, 0:3]  # the stored record: e = fl(v - v0)
+        m = M[inst]
+        with np.errstate(all="ignore"):
+            dot = lambda r, v: (m[:, r, 0] * v[:, 0] + m[:, r, 1] * v[:, 1]) + m[:, r, 2] * v[:, 2]
+            v0w = np.stack([dot(r, v0) + m[:, r, 3] for r in range(3)], -1)
+            e1w, e2w = np.stack([dot(r, e1) for r in range(3)], -1), np.stack([dot(r, e2) for r in range(3)], -1)
+            assert v0w.dtype == f32 and e1w.dtype == f32
+            return self.triangle_queries(v0w, v0w + e1w, v0w + e2w, ids, inst)
 
     def scene_triangle_queries(self, ids):
         """The (N, 12) float32 query rows of the scene's own triangles `ids` (global ids): the vertices as uploaded (or as last

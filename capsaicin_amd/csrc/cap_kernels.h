@@ -279,6 +279,19 @@ struct OverlapInstArgs
     const uint32_t* xw_max;
 };
 void launch_overlap_instances(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapInstArgs& a, const TlasDev& tl, const RayFilter& f, uint32_t depth);
+// Triangle overlap queries over the instance table (cap_overlap_triangles_instances, overlap.hip k_overlap_tri_inst): the queries are in
+// world space and their second w word is the skip pair's instance; a.out and inst_out are the two pages of OverlapInstArgs, a.slack is
+// not read (the slack is per query and instance).  The rest as OverlapInstArgs'.
+struct OverlapTriInstArgs
+{
+    OverlapTriArgs  a;
+    uint32_t*       inst_out;
+    const float4*   descs;
+    const float2*   near;
+    const uint32_t* xw_max;
+};
+void launch_overlap_triangles_instances(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapTriInstArgs& a, const TlasDev& tl, const RayFilter& f,
+                                        uint32_t depth);
 
 // ---- instances (instance.hip): cap_instances_set, cap_trace_instances* ----
 // The table on the device.  rec: 4 float4 per instance = the three rows of W (world to object, row r = (W_r0, W_r1, W_r2, W_r3)) and

@@ -185,4 +185,29 @@ __host__ __device__ __forceinline__ bool overlap_miss(float blox, float bloy, fl
 {
     return bhix < qlox || qhix < blox || bhiy < qloy || qhiy < bloy || bhiz < qloz || qhiz < bloz;
 }
+
+// ---- triangle overlap queries over instances (cap_overlap_triangles_instances, overlap.hip k_overlap_tri_inst) ----
+// The object-space image of the query box is no conservative prune for the triangle predicate (DESIGN.md "Triangle overlap queries over
+// instances" has the counterexample), so below an instance the walk maps every node box to WORLD space instead and tests it there.
+// The world box of the object-space box [lo, hi] under the transform m (row-major 3x4, M as the caller gave it):
+//   c_k = fl(fl(0.5 lo_k) + fl(0.5 hi_k)),  h_k = fl(fl(0.5 hi_k) - fl(0.5 lo_k)),
+//   cw_r = fl(fl(fl(fl(M_r0 c_0) + fl(M_r1 c_1)) + fl(M_r2 c_2)) + M_r3),
+//   hw_r = fl(fl(fl(|M_r0| h_0) + fl(|M_r1| h_1)) + fl(|M_r2| h_2)),
+//   wlo_r = fl(cw_r - hw_r),  whi_r = fl(cw_r + hw_r).
+// Plain products and sums in this order, no fused multiply-add; |M| is a source modifier on the device.  The result errs by at most
+// 11 eps Xw per component against the exact box of M([lo, hi]); a result that is not finite compares false and opens the node.
+// cap_debug_overlap_world_node (context.hip) runs the same function.
+__host__ __device__ __forceinline__ void overlap_world_box(const float m[12], float lox, float loy, float loz, float hix, float hiy, float hiz, float wlo[3],
+                                                           float whi[3])
+{
+    const float hlx = lox * 0.5f, hly = loy * 0.5f, hlz = loz * 0.5f, hhx = hix * 0.5f, hhy = hiy * 0.5f, hhz = hiz * 0.5f;
+    const float cx = hlx + hhx, cy = hly + hhy, cz = hlz + hhz;
+    const float hx = hhx - hlx, hy = hhy - hly, hz = hhz - hlz;
+    for (int r = 0; r < 3; ++r)
+    {
+        const float cw = ((m[4 * r] * cx + m[4 * r + 1] * cy) + m[4 * r + 2] * cz) + m[4 * r + 3];
+        const float hw = (fabsf(m[4 * r]) * hx + fabsf(m[4 * r + 1]) * hy) + fabsf(m[4 * r + 2]) * hz;
+        wlo[r] = cw - hw, whi[r] = cw + hw;
+    }
+}
 }  // namespace cap

@@ -423,6 +423,41 @@ int cap_debug_overlap_instance_prune(const float* transform, const float* object
     return CAP_OK;
 }
 
+// The bottom-level prune of cap_overlap_triangles_instances (cap_near.h: the functions k_overlap_tri_inst's world_node_step runs) for one
+// transform, one object box, one object-space node box and one world query box.  No context, no device:
+// tests/test_overlap_triangles_instances.py.
+int cap_debug_overlap_world_node(const float* transform, const float* object_lo, const float* object_hi, const float* node_lo, const float* node_hi,
+                                 const float* query_lo, const float* query_hi, float* xw, float* slack, float* world_lo, float* world_hi, uint32_t* skip_node)
+{
+    if (!transform || !object_lo || !object_hi || !node_lo || !node_hi || !query_lo || !query_hi)
+        return fail(CAP_ERR_INVALID_ARG, "cap_debug_overlap_world_node: NULL input");
+    double m[12], w[12], wd[12], A[12], nA, kappa, blo[3], bhi[3];
+    float  wf[12], mf[12];
+    bool   live = true;
+    for (int k = 0; k < 12; ++k) mf[k] = transform[k], m[k] = (double)transform[k], live = live && finite_d(m[k]);
+    for (int k = 0; k < 3; ++k) blo[k] = (double)object_lo[k], bhi[k] = (double)object_hi[k];
+    live = instance_inverse(m, live, w, wf, wd, A, nA, kappa, (float)CAP_INSTANCE_MAX_CONDITION);
+    const float xi   = live ? near_world_extent(m, blo, bhi) : 0.0f;
+    const float bmax = overlap_box_max(query_lo[0], query_lo[1], query_lo[2], query_hi[0], query_hi[1], query_hi[2]);
+    const float sl   = live ? overlap_slack(bmax, xi) : 0.0f;
+    float       wlo[3] = {0.f, 0.f, 0.f}, whi[3] = {0.f, 0.f, 0.f};
+    if (live) overlap_world_box(mf, node_lo[0], node_lo[1], node_lo[2], node_hi[0], node_hi[1], node_hi[2], wlo, whi);
+    if (xw) *xw = xi;
+    if (slack) *slack = sl;
+    for (int k = 0; k < 3; ++k)
+    {
+        if (world_lo) world_lo[k] = wlo[k];
+        if (world_hi) world_hi[k] = whi[k];
+    }
+    // an inert instance is never entered: nothing to skip
+    if (skip_node)
+        *skip_node = live && overlap_miss(wlo[0], wlo[1], wlo[2], whi[0], whi[1], whi[2], query_lo[0] - sl, query_lo[1] - sl, query_lo[2] - sl,
+                                          query_hi[0] + sl, query_hi[1] + sl, query_hi[2] + sl)
+                         ? 1u
+                         : 0u;
+    return CAP_OK;
+}
+
 int cap_ctx_create(int device_id, void* hip_stream, CapContext** out_ctx)
 {
     if (!out_ctx) return fail(CAP_ERR_INVALID_ARG, "cap_ctx_create: out_ctx is NULL");

@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip), cap_overlap_boxes, cap_overlap_instances and cap_overlap_triangles (overlap.hip) and cap_winding_numbers and cap_winding_instances (winding.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip), cap_overlap_boxes, cap_overlap_instances, cap_overlap_triangles and cap_overlap_triangles_instances (overlap.hip) and cap_winding_numbers and cap_winding_instances (winding.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -374,7 +374,8 @@ int closest_query(CapContext* c, const char* what, const CapPointDesc* points, u
 // cap_overlap_boxes (overlap.hip k_overlap_boxes): the triangles that meet each box, pages of k ids and / or counts, on the binary tree
 // alone; with `instanced` cap_overlap_instances (k_overlap_inst): world-space boxes over the instance table, pages of k (triangle,
 // instance) pairs; with Record = CapTriangleDesc cap_overlap_triangles (k_overlap_triangles): the triangles that meet each query
-// triangle.  closest_query's checks for a multi call, word for word, with "boxes" (or "queries"), "triangles" and "instances" as the
+// triangle, and with both cap_overlap_triangles_instances (k_overlap_tri_inst): world-space query triangles over the instance table.
+// closest_query's checks for a multi call, word for word, with "boxes" (or "queries"), "triangles" and "instances" as the
 // arrays' names.
 template <typename Record>
 int overlap_query(CapContext* c, const char* what, const Record* queries, uint64_t n, uint32_t k, uint32_t* ids, uint32_t* inst, bool instanced,
@@ -406,9 +407,16 @@ int overlap_query(CapContext* c, const char* what, const Record* queries, uint64
     return for_each_chunk(run, queries, n, [&](const QueryArgs& chunk, uint64_t first) {
         if constexpr (tri)
         {
-            launch_overlap_triangles(run.cfg, run.bvh, OverlapTriArgs{chunk.rays, chunk.n, at(ids, first * k), k, at(counts, first), resume, run.slack}, f,
-                                     c->bvh_info.max_depth);
-            return run.traced("k_overlap_triangles", first);
+            // (the instanced kernel takes its slack per query and instance: cap_near.h)
+            const OverlapTriArgs a{chunk.rays, chunk.n, at(ids, first * k), k, at(counts, first), resume, instanced ? 0.f : run.slack};
+            if (!instanced)
+            {
+                launch_overlap_triangles(run.cfg, run.bvh, a, f, c->bvh_info.max_depth);
+                return run.traced("k_overlap_triangles", first);
+            }
+            launch_overlap_triangles_instances(run.cfg, run.bvh, OverlapTriInstArgs{a, at(inst, first * k), c->inst_desc.p, c->inst_near.p, c->inst_misc.p + 7},
+                                               run.tl, flt.f, run.depth);
+            return run.traced("k_overlap_tri_inst", first);
         }
         // (the instanced kernel takes its slack per box and instance: cap_near.h)
         const OverlapArgs a{chunk.rays, chunk.n, at(ids, first * k), k, at(counts, first), resume, instanced ? 0.f : run.slack};
@@ -479,6 +487,13 @@ int cap_overlap_triangles(CapContext* c, const CapTriangleDesc* device_queries, 
                           uint32_t multi_flags, const CapTraceOptions* options)
 {
     return overlap_query(c, "cap_overlap_triangles", device_queries, n, k, device_triangles, nullptr, false, device_counts, multi_flags, options);
+}
+
+int cap_overlap_triangles_instances(CapContext* c, const CapTriangleDesc* device_queries, uint64_t n, uint32_t k, uint32_t* device_triangles,
+                                    uint32_t* device_instances, uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options)
+{
+    return overlap_query(c, "cap_overlap_triangles_instances", device_queries, n, k, device_triangles, device_instances, true, device_counts, multi_flags,
+                         options);
 }
 
 int cap_winding_instances(CapContext* c, const CapPointDesc* device_points, uint64_t n, float beta, float* device_winding, uint32_t* device_visits)

@@ -19,7 +19,9 @@
 // pairs (instance, triangle) whose world record meets the box, in (instance, triangle) order.
 //
 // Behind the instanced form: the triangle form (cap_overlap_triangles, k_overlap_triangles) -- a query triangle for the box, a 17-axis
-// triangle-against-triangle predicate for the 13 axes, the same walk against the box of the query's vertices.
+// triangle-against-triangle predicate for the 13 axes, the same walk against the box of the query's vertices.  And last its instanced
+// form (cap_overlap_triangles_instances, k_overlap_tri_inst): k_overlap_inst's loop with the triangle predicate, pruned in world space
+// below an instance as well (world_node_step).
 #include "cap_kernels.h"
 #include "cap_near.h"        // the prune of the instanced form
 #include "cap_query_walk.h"  // TopWalk, and the launch dispatchers
@@ -255,6 +257,20 @@ struct PairList
         key[0] = min(id, key[0]);
     }
 };
+// the two pages of one query: slot s is list entry s + skip (skip = K - k placeholders in front), through the chain of K selects
+template <int K>
+__device__ __forceinline__ void write_pair_pages(const PairList<K>& L, uint32_t k, int skip, uint32_t* page, uint32_t* ipage)
+{
+    for (uint32_t s = 0; s < k; ++s)
+    {
+        uint64_t key = ~0ull;
+#pragma unroll
+        for (int q = 0; q < K; ++q)
+            if (q - skip == (int)s) key = L.key[q];
+        page[s]  = (uint32_t)key;
+        ipage[s] = (uint32_t)(key >> 32);
+    }
+}
 
 // One top-level node: both children's stored world boxes against the grown query box (a record with k < 0 holds nothing: an inert
 // instance or the padding of a level); then down, or the instances into the queue, or up (top_advance)
@@ -372,15 +388,7 @@ __global__ __launch_bounds__(kBlock, overlap_inst_blocks(STACK, K)) void k_overl
         }
         // (a box that was not traversed: the list as init left it, k empty slots in both pages, and count 0)
         if (a.counts) a.counts[j] = count;
-        for (uint32_t s = 0; s < a.k; ++s)
-        {
-            uint64_t key = ~0ull;
-#pragma unroll
-            for (int q = 0; q < K; ++q)
-                if (q - skip == (int)s) key = L.key[q];
-            page[s]  = (uint32_t)key;
-            ipage[s] = (uint32_t)(key >> 32);
-        }
+        write_pair_pages(L, a.k, skip, page, ipage);
     }
 }
 
@@ -572,6 +580,158 @@ __global__ __launch_bounds__(kBlock, overlap_tri_blocks(STACK, K)) void k_overla
         }
     }
 }
+
+// ---- triangle against triangle over the instance table (cap_overlap_triangles_instances) ----
+// For every WORLD-space query triangle the pairs (instance, triangle) whose world record (world_record, from M as given) meets it under
+// tri_meets above, unchanged; pages, counts and cursor as k_overlap_inst, whose three-kind-of-step loop this is.  What differs is the
+// prune below an instance.  k_overlap_inst tests the object's node boxes against the object-space image of the query box, which rests
+// on the box predicate bringing a candidate within 15 eps U of the box itself.  The triangle predicate gives only its step 1 -- the
+// computed world vertex box meets [min A, max A] -- and for the pairs the 17 axes cannot decide (two coplanar segments that do not
+// cross) the scene triangle need not come anywhere near the query's box in any other frame.  So the walk prunes in WORLD space below
+// an instance as well: every child box of the object's tree is mapped to its world box under M (cap_near.h overlap_world_box) and kept
+// unless that misses [min A, max A] grown by the instance's slack.  DESIGN.md "Triangle overlap queries over instances" has the
+// argument (it needs c2 = 26 of the shipped 96).
+//
+// An inner node of the object's tree against the grown world query box [gl, gh]: box_node_step with both child boxes mapped to world
+// space first.  m: the 12 words of M.  The push, the enter and the guard are box_node_step's.
+template <int STACK>
+__device__ __forceinline__ bool world_node_step(const BvhDev& bvh, const float m[12], float glx, float gly, float glz, float ghx, float ghy, float ghz,
+                                                uint32_t* stack, int& node, int& sp)
+{
+    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2], q3 = bvh.nodes[4 * node + 3];
+    float        lo0[3], hi0[3], lo1[3], hi1[3];
+    overlap_world_box(m, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, lo0, hi0);
+    overlap_world_box(m, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, lo1, hi1);
+    const bool k0 = !overlap_miss(lo0[0], lo0[1], lo0[2], hi0[0], hi0[1], hi0[2], glx, gly, glz, ghx, ghy, ghz);
+    const bool k1 = !overlap_miss(lo1[0], lo1[1], lo1[2], hi1[0], hi1[1], hi1[2], glx, gly, glz, ghx, ghy, ghz);
+    const int  c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+    if (k0 && k1)
+    {
+        if (sp < STACK) stack[(sp++) * kBlock] = (uint32_t)c1;
+        node = c0;
+        return true;
+    }
+    if (k0 || k1)
+    {
+        node = k0 ? c0 : c1;
+        return true;
+    }
+    return false;
+}
+
+// Workgroups per CU.  LDS is overlap_inst_blocks' (the stack and the 104 bytes of level offsets).  Registers (tools/kernel_regs.sh; the
+// table is in DESIGN.md "Triangle overlap queries over instances"): the triangle frame's 35 words, M, the two grown boxes and the
+// top-level state beside the list's 2 K words.  Compiled without a limit that binds (STACK = 64, two workgroups) the kernel takes 134
+// to 135 VGPRs at K = 1, 147 to 149 at K = 4, 164 to 165 at K = 8 and 196 to 197 at K = 16: three waves per SIMD leave 168 each and
+// two leave 256, which those sizes admit anyway, so the limits below cost no instantiation a register, let alone scratch.  (Four
+// workgroups at K = 1 leave 128 and spill 12 bytes.)
+constexpr int overlap_tri_inst_blocks(int STACK, int K)
+{
+    const int by_lds  = STACK <= 16 ? 8 : STACK <= 24 ? 6 : STACK <= 32 ? 4 : 2;
+    const int by_regs = K <= 8 ? 3 : 2;
+    return by_lds < by_regs ? by_lds : by_regs;
+}
+
+// FILTER as in k_overlap_inst.  ia.a.queries: three float4 per query, (a, skip) (b, skip_instance) (c, -): the pair (skip_instance, skip)
+// is as if it were not in the table, like one the masks reject; no triangle has the id ~0, so a skip of ~0 skips nothing.
+template <int STACK, int K, bool FILTER>
+__global__ __launch_bounds__(kBlock, overlap_tri_inst_blocks(STACK, K)) void k_overlap_tri_inst(BvhDev bvh, OverlapTriInstArgs ia, TlasDev tl, RayFilter f)
+{
+    __shared__ uint32_t lds_stack[STACK * kBlock];
+    __shared__ uint32_t lds_off[kTlasMaxLevels + 1];
+    uint32_t* const     stack = lds_stack + threadIdx.x;
+    if (threadIdx.x <= tl.top) lds_off[threadIdx.x] = tl.level_off[threadIdx.x];
+    __syncthreads();
+    const OverlapTriArgs& a      = ia.a;
+    const float           xw_all = u2f(ia.xw_max[0]);  // the largest Xw of the table: the top level's slack holds for every instance
+    const int             skip   = K - (int)a.k;        // the placeholders
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < a.n; j += gridDim.x * kBlock)
+    {
+        const float4    qa = a.queries[3 * (size_t)j], qb = a.queries[3 * (size_t)j + 1], qc = a.queries[3 * (size_t)j + 2];
+        uint32_t* const page  = a.out + (size_t)j * a.k;
+        uint32_t* const ipage = ia.inst_out + (size_t)j * a.k;
+        PairList<K>     L;
+        L.init(a.k);
+        uint32_t count = 0u;
+        if (tri_ok(qa, qb, qc) && bvh.tri_count != 0u)
+        {
+            // only pairs above the cursor -- slot k - 1 of the query's two pages -- count and are listed; (~0, ~0) admits nothing
+            const bool     open = a.resume == 0u;
+            const uint32_t ic   = open ? 0u : ipage[a.k - 1u];
+            const uint64_t kc   = open ? 0ull : ((uint64_t)ic << 32) | page[a.k - 1u];
+            const uint64_t own  = ((uint64_t)f2u(qb.w) << 32) | f2u(qa.w);  // the skip pair as a key
+            const TriFrame t    = tri_frame(qa, qb, qc);
+            const float    bmax = overlap_box_max(t.lo.x, t.lo.y, t.lo.z, t.hi.x, t.hi.y, t.hi.z);
+            const float    slack_top = overlap_slack(bmax, xw_all);
+            const float    glx = t.lo.x - slack_top, gly = t.lo.y - slack_top, glz = t.lo.z - slack_top;
+            const float    ghx = t.hi.x + slack_top, ghy = t.hi.y + slack_top, ghz = t.hi.z + slack_top;
+            TopWalk        w   = top_start(tl);
+            // bottom level: the instance being walked, its M and the world query box grown by its own slack
+            bool     in_blas = false;
+            float    m[12]   = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            float    slack   = 0.f;
+            uint32_t inst = 0u, imask = 0u;
+            int      node = 0, sp = 0;
+            for (;;)
+            {
+                if (in_blas)
+                {
+                    if (node >= 0)
+                    {
+                        if (world_node_step<STACK>(bvh, m, t.lo.x - slack, t.lo.y - slack, t.lo.z - slack, t.hi.x + slack, t.hi.y + slack, t.hi.z + slack, stack,
+                                                   node, sp))
+                            continue;
+                    }
+                    else
+                    {
+                        const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                        for (uint32_t leaf = first; leaf <= last; ++leaf)
+                        {
+                            const uint32_t gid = f2u(bvh.tris[4 * (size_t)leaf + 3].x);
+                            const uint64_t key = ((uint64_t)inst << 32) | gid;
+                            if (key == own) continue;
+                            if constexpr (FILTER)
+                                if ((f.tri_mask[gid] & imask) == 0u) continue;
+                            const WorldRecord r = world_record(make_float4(m[0], m[1], m[2], m[3]), make_float4(m[4], m[5], m[6], m[7]),
+                                                               make_float4(m[8], m[9], m[10], m[11]), bvh.tris[4 * (size_t)leaf + 0],
+                                                               bvh.tris[4 * (size_t)leaf + 1], bvh.tris[4 * (size_t)leaf + 2]);
+                            if (!tri_meets(t, r.t0, r.t1, r.t2)) continue;
+                            if (open || key > kc)
+                            {
+                                ++count;
+                                L.offer(key);
+                            }
+                        }
+                    }
+                    in_blas = sp != 0;
+                    if (in_blas) node = (int)stack[(--sp) * kBlock];
+                    continue;
+                }
+                if (w.todo0 != kInvalidId)
+                {
+                    // the head of the queue: its mask joined with the call's (0 for an inert instance; the mesh byte joins it per
+                    // triangle), the cursor's instance, then M, the instance's slack and the root of the object's tree
+                    inst = w.todo0;
+                    w    = top_pop(w);
+                    const float4 w3 = tl.rec[4 * (size_t)inst + 3];
+                    imask           = f2u(w3.x) & f.mask;
+                    if (imask == 0u || inst < ic) continue;
+                    const float4 m0 = ia.descs[4 * (size_t)inst], m1 = ia.descs[4 * (size_t)inst + 1], m2 = ia.descs[4 * (size_t)inst + 2];
+                    m[0] = m0.x, m[1] = m0.y, m[2] = m0.z, m[3] = m0.w, m[4] = m1.x, m[5] = m1.y, m[6] = m1.z, m[7] = m1.w;
+                    m[8] = m2.x, m[9] = m2.y, m[10] = m2.z, m[11] = m2.w;
+                    slack = overlap_slack(bmax, ia.near[inst].y);  // (g, Xw): no division by g, the test stays in world space
+                    node = (int)f2u(w3.y), sp = 0, in_blas = true;
+                    continue;
+                }
+                if (w.done) break;
+                w = overlap_top_step(tl, lds_off, glx, gly, glz, ghx, ghy, ghz, w);
+            }
+        }
+        // (a query that was not traversed: the list as init left it, k empty slots in both pages, and count 0)
+        if (a.counts) a.counts[j] = count;
+        write_pair_pages(L, a.k, skip, page, ipage);
+    }
+}
 }  // namespace
 
 void launch_overlap_boxes(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapArgs& a, const RayFilter* f, uint32_t depth)
@@ -595,6 +755,18 @@ void launch_overlap_instances(const LaunchCfg& cfg, const BvhDev& bvh, const Ove
         with_k_bucket(a.a.k, [&](auto K) {
             with_flag(f.tri_mask != nullptr, [&](auto FILTER) {
                 launch_points<k_overlap_inst<decltype(S)::value, decltype(K)::value, decltype(FILTER)::value>>(cfg, a.a.n, bvh, a, tl, f);
+            });
+        });
+    });
+}
+void launch_overlap_triangles_instances(const LaunchCfg& cfg, const BvhDev& bvh, const OverlapTriInstArgs& a, const TlasDev& tl, const RayFilter& f,
+                                        uint32_t depth)
+{
+    // (depth: of the deepest bottom-level tree)
+    with_stack_class(depth, [&](auto S) {
+        with_k_bucket(a.a.k, [&](auto K) {
+            with_flag(f.tri_mask != nullptr, [&](auto FILTER) {
+                launch_points<k_overlap_tri_inst<decltype(S)::value, decltype(K)::value, decltype(FILTER)::value>>(cfg, a.a.n, bvh, a, tl, f);
             });
         });
     });

@@ -389,6 +389,16 @@ int cap_debug_closest_instance_bound(const float* transform, const float* box_lo
 int cap_debug_overlap_instance_prune(const float* transform, const float* object_lo, const float* object_hi, const float* world_lo, const float* world_hi,
                                      const float* node_lo, const float* node_hi, const float* box_lo, const float* box_hi, float* world_to_object, float* g,
                                      float* xw, float* slack, float* image_lo, float* image_hi, uint32_t* skip_top, uint32_t* skip_node);
+/* The bottom-level prune of cap_overlap_triangles_instances (below) for ONE instance transform (12 floats, row-major 3x4), the
+ * object-space box of its object (object_lo, object_hi), one OBJECT-space node box (node_lo, node_hi: a node of the object's tree, or a
+ * triangle's vertex box standing for the nodes above it) and one WORLD-space query box (query_lo, query_hi: the min and max of a query
+ * triangle's vertices), by the very functions the query kernel runs; 3 floats each.  Outputs, each may be NULL: xw as
+ * cap_debug_closest_instance_bound's; slack = 96 * 2^-24 * (|query box|_inf + xw), what the query box is grown by inside the instance;
+ * world_lo, world_hi = the world box of the node under the transform as the walk computes it, 3 floats each; skip_node = 1 if the walk
+ * would skip the node, else 0.  An inert transform gives zeros and no skip.  CAP_ERR_INVALID_ARG for a NULL input.  Needs no device. */
+int cap_debug_overlap_world_node(const float* transform, const float* object_lo, const float* object_hi, const float* node_lo, const float* node_hi,
+                                 const float* query_lo, const float* query_hi, float* xw, float* slack, float* world_lo, float* world_hi,
+                                 uint32_t* skip_node);
 /* Traversal strategy of the trace kernels (same hits either way): AUTO picks EXHAUSTIVE for scenes of at most 64
  * triangles (wave-uniform test of every triangle, no stack) and STACK (LBVH + per-lane LDS stack) otherwise. */
 typedef enum CapTraversal
@@ -774,19 +784,75 @@ int cap_overlap_instances(CapContext* ctx, const CapBoxDesc* device_boxes, uint6
  * masks, conventions, errors and their order are cap_overlap_boxes' word for word, with the three ranges "queries" (48 B per query,
  * 16-byte aligned), "triangles" and "counts" (4-byte aligned).  A query with a non-finite coordinate is not traversed: a page of
  * 0xFFFFFFFF and count 0, with CAP_MULTI_CONTINUE too.  The pad words are not read.
- * Not covered: instances and objects; a node cull finer than the box of the query's vertices; the intersection segment itself;
- * adjacency filtering; exactness for zero-area pairs; per-query masks. */
+ * Not covered: a node cull finer than the box of the query's vertices; the intersection segment itself; adjacency filtering; exactness
+ * for zero-area pairs; per-query masks.  The queries are in the scene's own space; over instances and objects:
+ * cap_overlap_triangles_instances below. */
 typedef struct CapTriangleDesc /* 48 B, 16-byte aligned */
 {
     float    a[3];
     uint32_t skip; /* a scene triangle with this global id is no candidate; 0xFFFFFFFF: none */
     float    b[3];
-    uint32_t pad0; /* not read */
+    uint32_t pad0; /* cap_overlap_triangles: not read.  cap_overlap_triangles_instances: skip_instance -- the pair (skip_instance, skip)
+                      is no candidate; with skip = 0xFFFFFFFF nothing is skipped, whatever this word holds */
     float    c[3];
     uint32_t pad1; /* not read */
 } CapTriangleDesc;
 int cap_overlap_triangles(CapContext* ctx, const CapTriangleDesc* device_queries, uint64_t n, uint32_t k, uint32_t* device_triangles /* n*k ids */,
                           uint32_t* device_counts /* n or NULL */, uint32_t multi_flags, const CapTraceOptions* options /* may be NULL */);
+
+/* ---- triangle overlap queries over instances: which triangles of which placed parts a world-space triangle cuts ----
+ * cap_overlap_triangles over the instance table of cap_instances_set (and the objects of cap_objects_set), as cap_overlap_instances
+ * stands to cap_overlap_boxes: what a collision pipeline over an assembly asks with the world-space triangles of a moving part.  The
+ * query triangles are in WORLD space; the record is the same 48-byte CapTriangleDesc.
+ *
+ * Candidates.  A query's candidates are the pairs (instance i, triangle g) of cap_overlap_instances, by the same rules: i is not inert;
+ * with an object table g is a triangle of i's object; desc[i].mask & mesh_mask[m] & instance_mask != 0 (m the mesh of g).  The pair is
+ * a candidate where its WORLD record (v0w, e1w, e2w) meets the query under cap_overlap_triangles' 17-axis predicate, unchanged.  The
+ * world record is cap_closest_instances', built from M = desc[i].transform as the caller gave it with
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, one rounded binary32 operation per operation written and no fused multiply-add:
+ *   v0w_r = fl(dot(M_r.xyz, v0) + M_r.w),  e1w_r = dot(M_r.xyz, e1),  e2w_r = dot(M_r.xyz, e2),   r = x, y, z;
+ * the predicate's scene vertices are B0 = v0w, B1 = fl(v0w + e1w), B2 = fl(v0w + e2w), its g0 is e1w as computed and its
+ * m = cross(e1w, e2w).  A NumPy float32 brute force over every (query, instance, triangle) is bit-identical, whichever builder made
+ * the trees.
+ *
+ * The skip pair.  This call reads the pad0 word as skip_instance: a pair with i == skip_instance and g == skip is no candidate --
+ * applied like the mask, it is neither counted nor listed.  A skip of 0xFFFFFFFF skips nothing, whatever pad0 holds, so zeroed pads
+ * with the default skip stay harmless.  pad1 is not read.  A query built from the world record of triangle g of instance i with the
+ * skip pair (i, g) lists what touches that placed triangle in the rest of the assembly and in its own instance: self-contact of an
+ * instance against the assembly.  Skipping a whole instance per query is not covered; per call the instance masks do it.
+ *
+ * Order, pages, counts and paging are cap_overlap_instances' word for word.  The pairs sort by (i, g) ascending.
+ * device_triangles[q * k + j] and device_instances[q * k + j], j < k, are query q's j-th pair; slots after the last pair hold
+ * 0xFFFFFFFF in both pages.  device_counts: NULL, or n uint32: the number of ALL candidates of the query, not capped at k (with
+ * CAP_MULTI_CONTINUE: of those above the cursor).  k = 0 counts only: both pages must be NULL and device_counts given.  With
+ * CAP_MULTI_CONTINUE slot k - 1 of both pages is read on entry as the cursor (i_c, g_c); only pairs lexicographically above it count
+ * and are listed, and the next pages are written over the old ones.  (0xFFFFFFFF, 0xFFFFFFFF) -- a page that was not full -- admits
+ * nothing.  device_instances is therefore required whenever k > 0.
+ *
+ * A query with a non-finite coordinate is not traversed: pages of 0xFFFFFFFF and count 0, with CAP_MULTI_CONTINUE too.
+ *
+ * Identities (tested on the reference and on the device):
+ *   1. One identity instance gives cap_overlap_triangles' ids and counts (1*x + 0*y + 0*z is exact for finite x; only the sign of a
+ *      zero can change, and no comparison of the predicate sees it); there skip_instance = 0.
+ *   2. With pure translations, vertices and queries on a common power-of-two grid (every sum exact) the answer is the flattened
+ *      scene's under cap_overlap_triangles, with flat id = i * T + g, T the scene's triangle count.
+ *   3. Scaling every M (matrix and translation) and every query by 2^j changes nothing, short of overflow and underflow.
+ *
+ * Conventions, errors and their order are cap_overlap_instances' word for word, with the four ranges "queries" (48 B per query,
+ * 16-byte aligned), "triangles", "instances" and "counts" (4-byte aligned): device pointers on the context's GPU, ranges that do not
+ * overlap; asynchronous on the context stream; n above 2^24 split into launches with all three outputs advanced per chunk, n = 0 does
+ * nothing; nothing is written on an error.  CAP_ERR_STATE without an instance table, before cap_bvh_build and while the trees are
+ * stale; CAP_ERR_INVALID_ARG for any ray_flags bit, non-zero reserved words, instance_mask > 0xFF, unknown multi flags,
+ * k > CAP_MULTI_MAX_K, k = 0 with a page given or counts NULL, CAP_MULTI_CONTINUE with k = 0, NULL queries (or either page with
+ * k > 0), misaligned or overlapping ranges.
+ * Pruning is conservative for every live instance: the walk tests the world box of every node of the object's tree against the box of
+ * the query's vertices -- not the object-space image of that box, which the triangle predicate does not justify (DESIGN.md "Triangle
+ * overlap queries over instances"; cap_debug_overlap_world_node shows the arithmetic).  Not covered: a finer node cull; per-query
+ * masks and whole-instance skip; the intersection segment; a lower bound inside an instance from the cursor's triangle (an instance
+ * below the cursor's is not entered; the cursor's own is walked again). */
+int cap_overlap_triangles_instances(CapContext* ctx, const CapTriangleDesc* device_queries, uint64_t n, uint32_t k, uint32_t* device_triangles /* n*k */,
+                                    uint32_t* device_instances /* n*k */, uint32_t* device_counts /* n or NULL */, uint32_t multi_flags,
+                                    const CapTraceOptions* options /* may be NULL */);
 
 /* ---- instanced ray queries: N transformed instances of the uploaded scene, or of objects of it, under a device-built top-level tree ----
  * The uploaded scene and the trees cap_bvh_build makes of it are read as OBJECT space; cap_instances_set installs a table of N

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Throughput of the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances,
-cap_closest_instances_multi, cap_signed_distance_instances), of the box overlap queries (cap_overlap_boxes, cap_overlap_instances), of cap_overlap_triangles and of cap_winding_numbers and cap_winding_instances on the 262 k-triangle hall -- not part of
+cap_closest_instances_multi, cap_signed_distance_instances), of the box overlap queries (cap_overlap_boxes, cap_overlap_instances), of cap_overlap_triangles and cap_overlap_triangles_instances and of cap_winding_numbers and cap_winding_instances on the 262 k-triangle hall -- not part of
 bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
@@ -58,6 +58,10 @@ on the same boxes (flat_ms, flat_mboxes_per_s, flat_mean_candidates, ratio_to_fl
 size (default 0.005) around the point, so its edges are about E x the scene's size -- pages of --k K ids (default 4; --counts as for --boxes):
 mtriangles_per_s, mean_candidates and the share of empty queries.  Beside it, measured in the same process, cap_overlap_boxes on the
 bounding boxes of the same triangles (boxes_ms, mboxes_per_s, boxes_mean_candidates) and ratio_to_boxes = triangle rate / box rate.
+--triangles together with --instances N runs cap_overlap_triangles_instances on the --instances layout with the same triangles as world
+queries: mtriangles_per_s, mean_pairs and the share of empty queries, and from the same process the flat cap_overlap_triangles rate on
+the same queries (flat_ms, flat_mtriangles_per_s, flat_mean_candidates, ratio_to_flat = the instanced rate over the flat one) and
+cap_overlap_instances on the triangles' bounding boxes (boxes_ms, mboxes_per_s, boxes_mean_pairs, ratio_to_boxes).
 
 Point sets, each of --points points (rounded down to a cube for the grid):
   grid      a regular grid through the scene's box, in raster order (x fastest);
@@ -131,8 +135,8 @@ def main():
     a = ap.parse_args()
     if a.boxes and (a.winding or a.signed):
         ap.error("--boxes goes with --k, --counts, --extent and --instances only")
-    if a.triangles and (a.winding or a.signed or a.boxes or a.instances is not None):
-        ap.error("--triangles goes with --k, --counts and --extent only")
+    if a.triangles and (a.winding or a.signed or a.boxes):
+        ap.error("--triangles goes with --k, --counts, --extent and --instances only")
     if (a.boxes or a.triangles) and a.k is None:
         a.k = 4  # (before `out` below is sized: the comparison run writes pages of k records into it)
     if a.winding and (a.signed or a.k is not None):
@@ -141,7 +145,7 @@ def main():
         ap.error("--signed does not go with --k: the sign is defined for the single record")
     if a.instances is not None and a.instances < 1:
         ap.error("--instances N needs N >= 1")
-    inst_multi = a.instances is not None and a.k is not None and not a.boxes
+    inst_multi = a.instances is not None and a.k is not None and not a.boxes and not a.triangles
     inst_signed = a.instances is not None and a.signed
     rng = np.random.default_rng(2026)
     dev = torch.device("cuda", 0)
@@ -239,6 +243,28 @@ def main():
             bsec = timed(r, lambda: capi._check(L.cap_overlap_boxes(r.ctx, boxes.data_ptr(), n, k, ids.data_ptr() if k else None,
                                                                     box_cnt.data_ptr() if a.counts else None, 0, None), "cap_overlap_boxes"), a.reps, a.warmup)
             capi._check(L.cap_overlap_triangles(r.ctx, qs.data_ptr(), n, 0, None, tri_cnt.data_ptr(), 0, None), "cap_overlap_triangles")
+            if a.instances is not None:
+                # cap_overlap_triangles_instances on the same world triangles (the point sets lie in instance 0, the identity), beside the flat
+                # rate above and cap_overlap_instances on the triangles' bounding boxes
+                r.sync()
+                flat_mean = float(tri_cnt.double().mean())
+                isec = timed(r, lambda: capi._check(L.cap_overlap_triangles_instances(r.ctx, qs.data_ptr(), n, k, ids.data_ptr() if k else None,
+                                                                                      inst.data_ptr() if k else None, tri_cnt.data_ptr() if a.counts else None,
+                                                                                      0, None), "cap_overlap_triangles_instances"), a.reps, a.warmup)
+                bsec = timed(r, lambda: capi._check(L.cap_overlap_instances(r.ctx, boxes.data_ptr(), n, k, ids.data_ptr() if k else None,
+                                                                            inst.data_ptr() if k else None, box_cnt.data_ptr() if a.counts else None, 0, None),
+                                                    "cap_overlap_instances"), a.reps, a.warmup)
+                capi._check(L.cap_overlap_triangles_instances(r.ctx, qs.data_ptr(), n, 0, None, None, tri_cnt.data_ptr(), 0, None),
+                            "cap_overlap_triangles_instances")
+                capi._check(L.cap_overlap_instances(r.ctx, boxes.data_ptr(), n, 0, None, None, box_cnt.data_ptr(), 0, None), "cap_overlap_instances")
+                r.sync()
+                print(json.dumps(dict(head, set=name, instances=a.instances, inert=int(info_i.inert), tlas_depth=int(info_i.tlas_depth), ms=round(isec * 1e3, 3),
+                                      mtriangles_per_s=round(n / isec / 1e6, 2), mean_pairs=round(float(tri_cnt.double().mean()), 3),
+                                      empty=round(float((tri_cnt == 0).float().mean()), 4), flat_ms=round(sec * 1e3, 3),
+                                      flat_mtriangles_per_s=round(n / sec / 1e6, 2), flat_mean_candidates=round(flat_mean, 3), ratio_to_flat=round(sec / isec, 3),
+                                      boxes_ms=round(bsec * 1e3, 3), mboxes_per_s=round(n / bsec / 1e6, 2),
+                                      boxes_mean_pairs=round(float(box_cnt.double().mean()), 3), ratio_to_boxes=round(bsec / isec, 3))), flush=True)
+                continue
             capi._check(L.cap_overlap_boxes(r.ctx, boxes.data_ptr(), n, 0, None, box_cnt.data_ptr(), 0, None), "cap_overlap_boxes")
             r.sync()
             print(json.dumps(dict(head, set=name, ms=round(sec * 1e3, 3), mtriangles_per_s=round(n / sec / 1e6, 2),
