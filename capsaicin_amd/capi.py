@@ -165,6 +165,16 @@ class Closest(C.Structure):
                 ("feature", C.c_uint32)]
 
 
+class SweepDesc(C.Structure):
+    """CapSweepDesc (32 bytes): a sphere of `radius` whose centre moves from origin along direction for t in [0, tmax]."""
+    _fields_ = [("origin", C.c_float * 3), ("radius", C.c_float), ("direction", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class SweepHit(C.Structure):
+    """CapSweepHit (32 bytes): Closest's layout with the time of first contact where dist2 is (tmax and MISS on a miss)."""
+    _fields_ = [("point", C.c_float * 3), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("triangle", C.c_uint32), ("feature", C.c_uint32)]
+
+
 class BoxDesc(C.Structure):
     """CapBoxDesc (32 bytes): an axis-aligned box, lo and hi corner; the pad words are not read."""
     _fields_ = [("lo", C.c_float * 3), ("pad0", C.c_float), ("hi", C.c_float * 3), ("pad1", C.c_float)]
@@ -318,6 +328,7 @@ SYMBOLS = {
     "cap_trace_instances_occlusion": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_trace_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_closest_points": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
+    "cap_sweep_spheres": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_points_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_overlap_boxes": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_overlap_instances": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
@@ -921,6 +932,26 @@ class Renderer:
         reads those); a miss is (0, 0, 0, radius^2, 0, 0, MISS, 0).  mask= is the instance inclusion mask (set_instance_masks).  sync as
         trace_rays."""
         return self._closest_single("cap_closest_points", points, out, sync, mask)
+
+    # ---- sphere sweep queries (cap_sweep_spheres) ----
+    def sweep_spheres(self, sweeps, out=None, sync=True, mask=None):
+        """The first contact of each moving sphere with the scene.  sweeps: (N, 8) float32 = CapSweepDesc rows (origin, radius,
+        direction, tmax; sweep_queries() packs them), a contiguous torch tensor on this context's device or a numpy array (staged
+        through torch; the records come back as numpy).  Returns (N, 8) float32 CapSweepHit records: the contact point on the triangle,
+        the time t of first contact in units of the direction, u, v, and the triangle and feature bits -- CapClosest's layout, so
+        closest_triangles() reads those; a miss is (0, 0, 0, tmax, 0, 0, MISS, 0).  The centre at contact is origin + t * direction,
+        the contact normal points from the contact point to it.  mask= is the instance inclusion mask (set_instance_masks).  sync as
+        trace_rays."""
+        import torch
+        return self._single("cap_sweep_spheres", sweeps, 8, "sweeps", out, 8, torch.float32, sync, (self.trace_options(None, mask),))
+
+    @staticmethod
+    def sweep_queries(origin, radius, direction, tmax=np.inf):
+        """(N, 8) float32 CapSweepDesc rows of (N, 3) origins and directions; radius and tmax are scalars or N values"""
+        o = np.asarray(origin, np.float32).reshape(-1, 3)
+        q = np.zeros((len(o), 8), np.float32)
+        q[:, 0:3], q[:, 3], q[:, 4:7], q[:, 7] = o, radius, np.asarray(direction, np.float32).reshape(-1, 3), tmax
+        return q
 
     # ---- signed distance (cap_pseudonormals_*, cap_signed_distance) ----
     def build_pseudonormals(self):

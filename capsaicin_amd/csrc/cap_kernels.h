@@ -193,6 +193,21 @@ struct SignedArgs
     float*       signed_out;
 };
 void launch_signed_distance(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestArgs& a, const SignedArgs& s, const RayFilter* f, uint32_t depth);
+// Sphere sweep queries (cap_sweep_spheres, sweep.hip k_sweep_spheres): sweeps = CapSweepDesc records (two float4: origin, radius;
+// direction, tmax), out = CapSweepHit records (two float4 per sweep).  mag: the largest coordinate magnitude of the scene bounds, which
+// with the sweep's own origin and radius makes the absolute part of its prune radius (DESIGN.md "Sphere sweep queries").  depth and f
+// as launch_closest_points'.
+struct SweepArgs
+{
+    const float4* sweeps;
+    uint32_t      n;
+    float4*       out;
+    float         mag;
+};
+constexpr float kSweepAccept     = 1.0f + 8.0f * 5.9604644775390625e-8f;  // 1 + kappa of the contract's part (C): kappa = 8 x 2^-24
+constexpr float kSweepNudge      = 16.0f * 5.9604644775390625e-8f;        // what a refused candidate's step is lengthened by, x the coordinates' size
+constexpr float kSweepSlackScale = 1.0f / 131072.0f;                      // 128 x 2^-24: the prune argument needs 58
+void launch_sweep_spheres(const LaunchCfg& cfg, const BvhDev& bvh, const SweepArgs& a, const RayFilter* f, uint32_t depth);
 // The k nearest and in-radius form (cap_closest_points_multi, point_query.hip k_closest_points_multi): a.out = pages of k CapClosest
 // records per point (NULL when k = 0); counts = n candidate counts or NULL (then the k-th distance prunes); resume: slot k - 1 of each
 // page is the cursor (CAP_MULTI_CONTINUE).  The list capacity is multi_bucket(k) >= k.

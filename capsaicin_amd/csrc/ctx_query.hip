@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip), cap_overlap_boxes, cap_overlap_instances, cap_overlap_triangles and cap_overlap_triangles_instances (overlap.hip) and cap_winding_numbers and cap_winding_instances (winding.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip), cap_sweep_spheres (sweep.hip), cap_overlap_boxes, cap_overlap_instances, cap_overlap_triangles and cap_overlap_triangles_instances (overlap.hip) and cap_winding_numbers and cap_winding_instances (winding.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -32,6 +32,7 @@ struct QueryRun
     LaunchCfg   cfg;
     float       safe;
     float       slack;  // closest-point queries: the absolute part of the pruning bound
+    float       mag;    // sphere sweeps: the largest coordinate magnitude of the scene bounds, rounded up
     uint64_t    per;    // rays per launch
     TlasDev     tl;     // instanced queries (use_instance_pools): the top-level tree ...
     uint32_t    depth;  // ... and the depth of the deepest tree below it
@@ -65,6 +66,7 @@ int query_prepare(CapContext* c, const char* what, uint64_t n, QueryRun& run, bo
                       std::fabs((double)c->bvh_info.bounds_hi[k])});
     run.safe = (float)(kQuerySafeScale * m);
     run.slack = (float)((double)kClosestSlackScale * m);  // (m >= the largest |coordinate|: the bound only grows)
+    run.mag   = std::nextafter((float)m, INFINITY);
     return CAP_OK;
 }
 
@@ -371,6 +373,28 @@ int closest_query(CapContext* c, const char* what, const CapPointDesc* points, u
     });
 }
 
+// cap_sweep_spheres (sweep.hip k_sweep_spheres): the first contact of each moving sphere with the scene, on the binary tree alone.
+// cap_closest_points' checks, with "sweeps" and "hits" as the arrays' names.
+int sweep_query(CapContext* c, const char* what, const CapSweepDesc* sweeps, uint64_t n, CapSweepHit* out, const CapTraceOptions* options)
+{
+    static_assert(sizeof(CapSweepDesc) == 2 * sizeof(float4) && sizeof(CapSweepHit) == 2 * sizeof(float4), "sweep records are the kernel's float4 records");
+    if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
+    if (options && options->ray_flags) return fail(CAP_ERR_INVALID_ARG, "%s: ray_flags 0x%x: a sweep is two-sided and has one first contact", what, options->ray_flags);
+    QueryFilter flt;
+    if (const int rc = query_filter(c, what, options, false, flt)) return rc;
+    if (const int rc = query_state(c, what)) return rc;
+    if (n == 0) return CAP_OK;
+    if (!sweeps || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
+    if (const int rc = check_ranges(what, n, {range("sweeps", sweeps, sizeof(CapSweepDesc), 16), range("hits", out, sizeof(CapSweepHit), 16)})) return rc;
+    QueryRun run;
+    if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    const RayFilter* f = flt.scene();
+    return for_each_chunk(run, sweeps, n, [&](const QueryArgs& chunk, uint64_t first) {
+        launch_sweep_spheres(run.cfg, run.bvh, SweepArgs{chunk.rays, chunk.n, reinterpret_cast<float4*>(out + first), run.mag}, f, c->bvh_info.max_depth);
+        return run.traced("k_sweep_spheres", first);
+    });
+}
+
 // cap_overlap_boxes (overlap.hip k_overlap_boxes): the triangles that meet each box, pages of k ids and / or counts, on the binary tree
 // alone; with `instanced` cap_overlap_instances (k_overlap_inst): world-space boxes over the instance table, pages of k (triangle,
 // instance) pairs; with Record = CapTriangleDesc cap_overlap_triangles (k_overlap_triangles): the triangles that meet each query
@@ -470,6 +494,11 @@ int winding_query(CapContext* c, const char* what, const CapPointDesc* points, u
 }  // namespace
 
 extern "C" {
+
+int cap_sweep_spheres(CapContext* c, const CapSweepDesc* device_sweeps, uint64_t n, CapSweepHit* device_out, const CapTraceOptions* options)
+{
+    return sweep_query(c, "cap_sweep_spheres", device_sweeps, n, device_out, options);
+}
 
 int cap_overlap_boxes(CapContext* c, const CapBoxDesc* device_boxes, uint64_t n, uint32_t k, uint32_t* device_triangles, uint32_t* device_counts,
                       uint32_t multi_flags, const CapTraceOptions* options)

@@ -642,6 +642,81 @@ int cap_closest_points(CapContext* ctx, const CapPointDesc* device_points, uint6
 int cap_closest_points_multi(CapContext* ctx, const CapPointDesc* device_points, uint64_t n, uint32_t k, CapClosest* device_out,
                              uint32_t* device_counts, uint32_t multi_flags, const CapTraceOptions* options /* may be NULL */);
 
+/* ---- sphere sweep queries: the first contact of a moving sphere with the scene (character and camera controllers, continuous
+ * collision detection, thick-ray picking, clearance along a path) ----
+ * For every sweep the first time t in [0, tmax] at which the sphere of radius r centred at c(t) = o + t d touches a triangle of the
+ * uploaded scene, and where it touches.  Lengths are in units of d; d is not normalised for the caller.  Walks the binary tree of the
+ * scene and stays current under cap_scene_update_vertices + cap_bvh_refit like every other query.
+ *
+ * The per-triangle function is defined on the stored record (v0, e1, e2) and the computed vertices B1 = fl(v0 + e1), B2 = fl(v0 + e2).
+ * Every operation is one rounded binary32 operation in the order written, there is no fused multiply-add anywhere, division and sqrt
+ * are correctly rounded, dot and cross are the forms of the closest-point and triangle overlap contracts, and a vector operation is
+ * component-wise -- so a plain float32 brute force is bit-identical to the kernel.  r2 = fl(r r), dd = dot(d, d).
+ *   (A) Start overlap.  cap_closest_points' cascade at o.  If its dist2 <= r2 the triangle's time is t = 0 and its record is that
+ *       cascade's; (B) and (C) are not evaluated.
+ *   (B) Candidate times, only if dd != 0 (d = 0, or so small that dd underflows to 0, is a static overlap test: part (A) alone).  A
+ *       time counts iff it satisfies the conditions written with it and t > 0 && t <= tmax; every condition is a comparison that a NaN
+ *       fails.  The triangle's candidate is the smallest time that counts (none: no contact); it is finite.
+ *       root(a, b, c):  disc = b*b - a*c,  t = (-b - sqrt(disc)) / a,  counts iff a > 0.
+ *       vertex(m):      root(dd, dot(m, d), dot(m, m) - r2).
+ *       edge(m, e):     ee = dot(e, e), me = dot(m, e), de = dot(d, e), md = dot(m, d), mm = dot(m, m),
+ *                       t = root(ee*dd - de*de, ee*md - de*me, ee*(mm - r2) - me*me),  s = me + t*de,  counts iff s >= 0 && s <= ee.
+ *       With m0 = o - v0, m1 = o - B1, m2 = o - B2 the seven pieces are
+ *       plane:    n = cross(e1, e2), nn = dot(n, n), h = dot(n, m0), nd = dot(n, d),
+ *                 num = |h| - r*sqrt(nn),  den = (h >= 0 ? -nd : nd),  t = num / den,
+ *                 w = (o + t*d) - v0,  a = dot(cross(w, e2), n),  b = dot(cross(e1, w), n),
+ *                 counts iff den > 0 && a >= 0 && b >= 0 && a + b <= nn   (the offset plane on o's side, the foot point inside);
+ *       edges:    edge(m0, e1), edge(m0, e2), edge(m1, e2 - e1);
+ *       vertices: vertex(m0), vertex(m1), vertex(m2).
+ *       The candidate is then polished: c is a binary32 point up to an ulp of |o| + t |d| off the line, so for a time that is right to
+ *       the last bit the centre lands outside the offset surface as often as inside.  At most three evaluations k = 0, 1, 2 from
+ *       t_0 = the candidate: c = o + t_k*d, cap_closest_points' cascade at c gives dist2 and point.  If (C) accepts, t = t_k.  Else,
+ *       for k < 2, a Newton step on the distance, lengthened by a nudge of sixteen roundings of the coordinates' size:
+ *         dist = sqrt(dist2),  g = c - point,  rate = -dot(g, d),  size = max(|c|_inf, |point|_inf) + r,
+ *         t_(k+1) = t_k + (((dist - r) + (16 x 2^-24)*size) * dist) / rate,   counts iff rate > 0 && t_(k+1) <= tmax;
+ *       a step that does not count, or a third refusal, leaves the triangle without a contact.  Times only grow.
+ *   (C) Verification and record.  c = o + t*d (fl(o + fl(t d)) per component), cap_closest_points' cascade at c.  The candidate is
+ *       accepted iff that dist2 <= fl(r2 * (1 + kappa)), kappa = 8 x 2^-24 (1 + kappa is a binary32 number).  The hit's point, u, v
+ *       and feature are that cascade's words, bit for bit.
+ * So every reported contact is, by the library's own closest-point function, a centre position that touches the triangle: the contact
+ * normal is (c - point) and the penetration at a start overlap r - |o - point|.  kappa covers the roundings that scale with r
+ * (DESIGN.md "Sphere sweep queries" derives it); those that scale with the coordinates are what the polish is for, and a polished
+ * contact penetrates by a few of those roundings.  With exactly representable data the first evaluation accepts and t is the entry
+ * time itself.  From an origin many scene sizes away the quadratics of (B) cancel and the candidate is off by about 2^-24 |o|^2 / r:
+ * three evaluations may not reach the surface, and such a sweep can miss; start it near the scene.
+ *
+ * The answer.  Among the triangles that pass the mask filter and have a contact, the one minimal in (t, triangle) lexicographic order,
+ * the tie rule of every other query: the answer depends on neither the tree, nor the builder, nor the visiting order.  The miss record
+ * is (0, 0, 0, tmax, 0, 0, 0xFFFFFFFF, 0).  Degenerate queries -- a non-finite origin or direction component, a radius or tmax that is
+ * NaN or negative -- are not traversed and give the miss record with t = 0.  tmax = +inf is legal; r = 0 is legal (then (C) asks for a computed dist2 of exactly 0: use a small positive radius for a thick ray), has this arithmetic
+ * and is not promised equal to cap_trace_rays; r = +inf is a start overlap with every triangle whose cascade is not NaN.  A NaN anywhere
+ * in a triangle's evaluation fails its comparisons and the triangle is never an answer; a triangle with two coinciding vertices behaves
+ * as in the closest-point contract.
+ *
+ * Conventions are cap_closest_points': device pointers on the context's GPU, both 16-byte aligned, ranges ("sweeps", "hits") that do
+ * not overlap; asynchronous on the context stream and ordered behind a render's second lane; n above 2^24 split into launches, n = 0
+ * does nothing; nothing of the render's state is touched; nothing is written on an error.  CAP_ERR_STATE before cap_bvh_build and
+ * while the trees are stale.  options: instance_mask and the mesh-mask table act by mesh as for points; any ray_flags bit is
+ * CAP_ERR_INVALID_ARG (the sweep is two-sided), as are non-zero reserved words and instance_mask > 0xFF; NULL is the plain call.
+ * Not covered: instances, k nearest contacts and paging, other swept shapes, per-query masks, a time of exit, rotation. */
+typedef struct CapSweepDesc /* 32 B, 16-aligned: DXR RayDesc's shape with the radius where tmin is */
+{
+    float origin[3];
+    float radius; /* >= 0 */
+    float direction[3];
+    float tmax; /* >= 0; +inf: unbounded */
+} CapSweepDesc;
+typedef struct CapSweepHit /* 32 B: CapClosest's layout with t where dist2 is */
+{
+    float    point[3]; /* the contact point on the triangle */
+    float    t;        /* the time of first contact; tmax on a miss */
+    float    u, v;     /* point = v0 + u*e1 + v*e2 */
+    uint32_t triangle; /* global id; 0xFFFFFFFF = miss */
+    uint32_t feature;  /* CAP_FEATURE_*: where on the triangle the contact lies */
+} CapSweepHit;
+int cap_sweep_spheres(CapContext* ctx, const CapSweepDesc* device_sweeps, uint64_t n, CapSweepHit* device_out,
+                      const CapTraceOptions* options /* may be NULL */);
+
 /* ---- box overlap queries: the triangles that meet an axis-aligned box (collision broad phase, voxelisation, selection, clipping) ----
  * For every box the triangles of the uploaded scene that meet the CLOSED box [lo, hi], on the scene's binary tree: the first k of them
  * by triangle id, their number, or both, with cap_closest_points_multi's pages, counts, paging and masks.  Current under

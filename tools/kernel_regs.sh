@@ -4,7 +4,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 LLVM=/opt/rocm/lib/llvm/bin
 objs=("$@")
-[ ${#objs[@]} -eq 0 ] && objs=("$ROOT"/capsaicin_amd/csrc/{kernels,small_scene,planes,trace8,query,point_query,pseudonormal,winding,overlap,instance,bvh,ploc,post,context}.o)
+[ ${#objs[@]} -eq 0 ] && objs=("$ROOT"/capsaicin_amd/csrc/{kernels,small_scene,planes,trace8,query,point_query,sweep,pseudonormal,winding,overlap,instance,bvh,ploc,post,context}.o)
 # (the ctx_*.o host units hold no kernel)
 tmp=$(mktemp -d)
 for o in "${objs[@]}"; do

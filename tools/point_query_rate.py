@@ -5,6 +5,7 @@ bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
                                      [--k K [--counts]] [--instances N] [--signed] [--winding [--beta B]]  (--winding goes with --instances N)
+                                     [--sweeps]
 
 --winding runs cap_winding_numbers at --beta B (default 2; inf sums every triangle exactly: use fewer --points) after
 cap_winding_build, on the same point sets (the radius is not read).  Each line carries its rate, mean_visits = the mean numbers of
@@ -62,6 +63,11 @@ bounding boxes of the same triangles (boxes_ms, mboxes_per_s, boxes_mean_candida
 queries: mtriangles_per_s, mean_pairs and the share of empty queries, and from the same process the flat cap_overlap_triangles rate on
 the same queries (flat_ms, flat_mtriangles_per_s, flat_mean_candidates, ratio_to_flat = the instanced rate over the flat one) and
 cap_overlap_instances on the triangles' bounding boxes (boxes_ms, mboxes_per_s, boxes_mean_pairs, ratio_to_boxes).
+
+--sweeps [--radius R | --radius-frac F] runs cap_sweep_spheres: one sweep per point of the same point sets towards a fixed pseudo-random
+unit direction, tmax inf, radius R (default 0.01 x the scene's size): msweeps_per_s, the share of misses and of start overlaps, and
+from the same process cap_trace_rays on the same origins and directions as the yardstick (rays_ms, mrays_per_s, ray_misses,
+ratio_to_rays = the sweep rate over the ray rate).
 
 Point sets, each of --points points (rounded down to a cube for the grid):
   grid      a regular grid through the scene's box, in raster order (x fastest);
@@ -132,7 +138,12 @@ def main():
     ap.add_argument("--boxes", action="store_true")
     ap.add_argument("--extent", type=float, default=0.005)
     ap.add_argument("--triangles", action="store_true")
+    ap.add_argument("--sweeps", action="store_true")
     a = ap.parse_args()
+    if a.sweeps and (a.winding or a.signed or a.boxes or a.triangles or a.k is not None or a.instances is not None):
+        ap.error("--sweeps goes with --radius or --radius-frac only")
+    if a.sweeps and a.radius == float("inf") and a.radius_frac is None:
+        a.radius_frac = 0.01
     if a.boxes and (a.winding or a.signed):
         ap.error("--boxes goes with --k, --counts, --extent and --instances only")
     if a.triangles and (a.winding or a.signed or a.boxes):
@@ -221,6 +232,29 @@ def main():
                                   mean_visits=[round(float(mean[0]), 2), round(float(mean[1]), 2)], inside=round(float((w >= 0.5).float().mean()), 4),
                                   table_build_ms=round(wn.ms, 3), bvh_build_ms=round(info.build_ms, 3),
                                   table={k: v for k, v in wn.as_dict().items() if k != "ms"})), flush=True)
+        r.close()
+        return
+    if a.sweeps:
+        # one sweep per point towards a fixed pseudo-random direction (unit length, tmax inf), and cap_trace_rays on the same origins and
+        # directions from the same process as the yardstick
+        d = rng.normal(size=(n, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        hits4 = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        for name, xyz in sets:
+            sw = torch.as_tensor(capi.Renderer.sweep_queries(xyz, a.radius, d), device=dev).contiguous()
+            ry = sw.clone()
+            ry[:, 3] = 0.0  # (the radius word is a ray's tmin)
+            torch.cuda.synchronize()
+            sec = timed(r, lambda: capi._check(L.cap_sweep_spheres(r.ctx, sw.data_ptr(), n, out.data_ptr(), None), "cap_sweep_spheres"), a.reps, a.warmup)
+            rsec = timed(r, lambda: capi._check(L.cap_trace_rays(r.ctx, ry.data_ptr(), n, hits4.data_ptr(), 0), "cap_trace_rays"), a.reps, a.warmup)
+            ids = out[:n, 6].contiguous().view(torch.int32)
+            miss = ids == -1
+            start = (~miss) & (out[:n, 3] == 0)
+            print(json.dumps(dict(head, set=name, radius_frac=a.radius / size, ms=round(sec * 1e3, 3), msweeps_per_s=round(n / sec / 1e6, 2),
+                                  misses=round(float(miss.float().mean()), 4), start_overlaps=round(float(start.float().mean()), 4),
+                                  rays_ms=round(rsec * 1e3, 3), mrays_per_s=round(n / rsec / 1e6, 2),
+                                  ray_misses=round(float((hits4[:, 3].contiguous().view(torch.int32) == -1).float().mean()), 4),
+                                  ratio_to_rays=round(rsec / sec, 3))), flush=True)
         r.close()
         return
     if a.triangles:
