@@ -703,6 +703,8 @@ class Renderer:
     DEBUG_GRAY_ENTRIES = 20  # 1: the last render's fused launches used 32-byte extension entries (one throughput word)
     DEBUG_GROUP_WALK = 22  # slots per jitter group if the last batch's head kernel walked bounce 0's chunks group by group, 0: slot-major
     DEBUG_CAMERA_TABLE_REUSED = 23  # 1: the last batch found its camera-vertex table built from the same inputs and launched no builder
+    DEBUG_SKY_PLANE = 24  # 1: the last render's fused launches stored the sky term into the sky plane and the resolve added it
+    DEBUG_SKY_PLANE_NONZERO = 25  # after such a render: entries of the last batch's sky plane that are not +0 (its escapes at bounce >= 1)
     DEBUG_SELFTEST_GRAY = 21  # after a 48-byte render: entries with unequal throughput words << 32 | entries of the last batch's queues looked at
 
     def debug_set(self, key, value):

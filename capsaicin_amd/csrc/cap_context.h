@@ -269,6 +269,10 @@ struct CapContext
         uint32_t num_bounces = 0, first_writer = 0, class_capacity = 0, lane = 0;  // first_writer: the first bounce that appended to a queue
         bool     valid = false;
     } last_queues;
+    struct LastSky                             // the sky-plane form of the last cap_render (CAP_DEBUG_SKY_PLANE) and its last batch's plane (.._NONZERO)
+    {
+        uint32_t form = 0, n_slots = 0, lane = 0;
+    } last_sky;
     uint32_t      last_cull_camera_pairs = 0;  // ShadeArgs::cull_camera_pairs of the last cap_render batch (CAP_DEBUG_CAMERA_CULL)
     uint32_t      traversal_mode  = CAP_TRAVERSAL_AUTO;
     uint32_t      bvh_build_mode  = CAP_BVH_BUILD_AUTO;
@@ -284,6 +288,7 @@ struct CapContext
     {
         hipStream_t      stream = nullptr;  // not owned: the context's `stream` (lane 0) or `stream2` (lane 1)
         DevBuf<float4>   hits, q_org[2], q_dir[2], q_thr[2], s_org, s_dir, s_con, pl_color, pl_direct, pl_albedo;
+        DevBuf<float>    pl_sky;       // [frame slot][Ppad] the sky plane (Planes::sky), if the form is on; zeroed by every batch's head launch
         DevBuf<float4>   camera;       // camera vertices, two planes [jitter group][Ppad] (launch_camera_vertices), if the form is on; kept from batch to batch (camera_key)
         DevBuf<float4>   terms;        // per batch: direction-sample terms [sampling bounce][slot][4096] (ShadeArgs::sample_terms), if the form is on
         DevBuf<uint32_t> counters;     // per batch: CounterLayout

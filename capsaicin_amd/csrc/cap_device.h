@@ -287,8 +287,16 @@ struct Planes
 {
     float4* color;   // [frame slot][Ppad]  indirect radiance (rt_indirect.hlsl color)
     float4* direct;  // [frame slot][Ppad]
-    float4* albedo;  // [frame slot][Ppad]
-    float4* aov_geo;           // [Ppad] last frame only (CAP_RENDER_AOV)
+    // One word, two readers that never meet (like ShadeArgs::hits / sample_terms: the kernel arguments of every kernel stay as they were).
+    // `albedo` is neither read nor written under ShadeArgs::albedo_in_w; the sky-plane form (ctx_render.hip RenderPlan::sky_plane), which
+    // implies it, carries its plane here: `sky`, one float per (frame slot, padded pixel), indexed like `color` -- the throughput of the
+    // path where it escaped at bounce >= 1, else +0 (cap_shade.h shade_vertex, planes.hip k_resolve_coded_sky).
+    union
+    {
+        float4* albedo;  // [frame slot][Ppad]
+        float*  sky;     // [frame slot][Ppad]
+    };
+    float4* aov_geo;          // [Ppad] last frame only (CAP_RENDER_AOV)
     float4* aov_normal_depth;  // [Ppad]
 };
 }  // namespace cap

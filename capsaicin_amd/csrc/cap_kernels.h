@@ -46,6 +46,7 @@ enum CapSwitch : uint32_t
     SW_NO_GRAY_ENTRIES,     // small-scene path, sample-table kernels, untextured scene: the extension queue keeps its 48-byte entries (three throughput words)
     SW_NO_GROUP_WALK,       // head kernels: bounce 0's chunk indices walk the identity queue slot-major (no bands of jitter groups, cap_device.h head_chunk)
     SW_NO_TABLE_REUSE,      // every batch rebuilds its camera-vertex table, whether or not its inputs changed (ctx_render.hip CameraTableKey)
+    SW_NO_SKY_PLANE,        // small-scene path, head form with 32-byte entries: the sky term stays three float atomics on the colour plane (no ShadeArgs::planes.sky)
     SW_COUNT
 };
 struct SwitchTable
@@ -458,8 +459,12 @@ bool launch_primary_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeAr
 // through the wave rings: no any-hit launch follows bounce 0.
 // gray: the extension queues args.in (not under camera_head, where it is the table) and args.out hold 32-byte entries (RayQueue) and
 // thr_pid is neither read nor written.  Needs sample_terms and trace_shade_has_gray_form(); every launch of a batch or none.
+// sky_plane: a path that escapes at bounce >= 1 stores its throughput into args.planes.sky and adds nothing to the colour plane; the
+// head launch zeroes the plane for the whole batch and launch_resolve(.., sky_plane) adds the term.  Needs gray, the batch's first
+// launch to be the camera_head one and code_in_color (whose albedo_in_w frees the word of Planes that carries the plane); every launch
+// of a batch and its resolve, or none.
 uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback = false, bool camera_head = false,
-                            bool gray = false);
+                            bool gray = false, bool sky_plane = false);
 // whether the reference model's bounce 0 of this scene has the form ShadeArgs::code_in_color asks for (the kernel of tame records in LDS)
 bool trace_shade_has_code_form(const BvhDev& bvh, const SceneDev& scene);
 // ... and the form ShadeArgs::sample_terms asks for (the lean kernels)
@@ -484,8 +489,11 @@ void launch_camera_vertices(const LaunchCfg& cfg, const BvhDev& bvh, const Shade
 
 // ---- accumulate / exchange ----
 // accum[pl] += sum over slots (in slot order) of color*albedo + direct; .w counts frames.
+// sky_plane (with code_in_color): color.xyz + planes.sky * (0.7, 0.7, 0.85) stands for color.xyz (launch_trace_shade's sky_plane)
 void launch_resolve(const LaunchCfg& cfg, const Planes& planes, uint32_t n_slots, uint32_t pixels_padded, float4* accum,
-                    bool albedo_in_w = false, float kd_untextured = 0.0f, bool code_in_color = false);
+                    bool albedo_in_w = false, float kd_untextured = 0.0f, bool code_in_color = false, bool sky_plane = false);
+// out_device[0] += the words of sky[0 .. n) that are not +0 (CAP_DEBUG_SKY_PLANE_NONZERO)
+void launch_sky_nonzero(hipStream_t stream, const float* sky, size_t n, unsigned long long* out_device);
 // plane_kind: 0 copy, 1 combined (color*albedo+direct from the three planes at slot offset), 2 mean (xyz / w)
 void launch_untile(const LaunchCfg& cfg, const ScreenDev& screen, const float4* src, const float4* albedo, const float4* direct,
                    int plane_kind, float4* image);

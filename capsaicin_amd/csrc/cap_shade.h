@@ -212,6 +212,7 @@ __device__ __forceinline__ uint32_t wave_append(bool emit, uint32_t* counter)
 //   TAB      the direction sample's terms come from the batch's table (ShadeArgs::sample_terms) instead of being carried and computed
 //   GRAY     the throughput is one float (C::Thr) and an extension entry two float4 (RayQueue, cap_device.h): an untextured scene, where
 //            the three components are the same operations on the same operands at every bounce
+//   SKYP     GRAY at bounce >= 1: the sky term is one store of the throughput into ShadeArgs::planes.sky, added by the resolve
 // Text that serves both forms (small_scene_body.h) makes a throughput with thr_of<C::Thr>() -- the first of three equal components where
 // it is one float -- and hands it to code written for three components through thr3().
 template <class T>
@@ -572,7 +573,23 @@ __device__ __forceinline__ void shade_vertex(const ShadeArgs& a, const float4* s
                 // three no-return float atomics are plain IEEE adds in program order; unlike a load-add-store they do not make
                 // the wave wait for the old value.
                 // (A load-add-store here instead, as in k_trace_any: 16.4 -> 16.6 ms.)
-                if constexpr (C::GRAY)
+                if constexpr (C::GRAY && C::SKYP)
+                {
+                    // The sky plane (TraceShadeCfg SKYP): the colour plane is not touched at all.  A path that escapes is finished --
+                    // within this launch it has no vertex, hence no ring entry, and every earlier addition to its color.xyz was made
+                    // by an earlier launch (in the head kernel: its bounce-0 ring entry writes `direct` and color.w only) -- so this
+                    // term is the LAST addition its color.xyz would ever receive, and the whole term is one float.  The lane stores
+                    // thr and k_resolve_coded_sky (planes.hip), which holds the path's colour entry in a register anyway, computes
+                    // color.x + thr * 0.7f, color.y + thr * 0.7f, color.z + thr * 0.85f: the atomics' IEEE additions, on the same
+                    // operands, after the same earlier ones.  (-ffp-contract=off, csrc/Makefile, keeps products and sums apart there
+                    // as here.)  Every other path's entry holds the head's +0, and x + (+0) == x in every bit unless x is -0, which
+                    // color.xyz never is: it starts at +0 (the head's store) and only receives contributions c * thr with
+                    // c = ((I * kd) * kInvPi) * fmaxf(0, n.L) of a positive light and a kd >= 1e-5 (a smaller one is `black` and adds
+                    // nothing) and thr a product of such kd and of quotients of fmaxf(., 0) terms: sums of non-negative numbers.  A NaN
+                    // thr gives the NaN the atomic would have given: the same product enters the same addition.
+                    a.planes.sky[plane_idx] = thr;
+                }
+                else if constexpr (C::GRAY)
                 {
                     // thr.x * 0.7f and thr.y * 0.7f are one product
                     float*      c  = reinterpret_cast<float*>(a.planes.color + plane_idx);

@@ -276,7 +276,7 @@ static const char* const kSwitchNames[SW_COUNT] = {
     "CAP_LANE_SPLIT_MIN", "CAP_BLOCKS_PER_CU", "CAP_NO_CAMERA_CULL", "CAP_NO_ALBEDO_IN_W", "CAP_NO_INLINE_NEE", "CAP_NO_INLINE_PROBE", "CAP_NO_WAVE_RING",
     "CAP_ANY_REFILL", "CAP_PRIMARY_WIDE", "CAP_NO_PACKET", "CAP_NO_ANY_PROBE", "CAP_ANY_PROBE", "CAP_ANY_BLOCKS", "CAP_NO_PRIMARY_FUSE", "CAP_W8_REFILL",
     "CAP_W8_GRID", "CAP_AUTO_SAH_TRIANGLES", "CAP_NO_NEE_PAIR_CULL", "CAP_RAYGEN_KERNEL", "CAP_NO_PLANE_CODE", "CAP_SAMPLE_TABLE", "CAP_NO_CAMERA_TABLE",
-    "CAP_NO_GRAY_ENTRIES", "CAP_NO_GROUP_WALK", "CAP_NO_TABLE_REUSE"};
+    "CAP_NO_GRAY_ENTRIES", "CAP_NO_GROUP_WALK", "CAP_NO_TABLE_REUSE", "CAP_NO_SKY_PLANE"};
 
 static void switches_from_environment(SwitchTable& t)
 {
@@ -725,6 +725,19 @@ int cap_debug_get(CapContext* c, uint32_t key, uint64_t* value)
     case CAP_DEBUG_GROUP_WALK: *value = c->last_group_walk; return CAP_OK;
     case CAP_DEBUG_CAMERA_TABLE_REUSED: *value = c->last_camera_reused; return CAP_OK;
     case CAP_DEBUG_GRAY_ENTRIES: *value = c->last_gray_entries; return CAP_OK;
+    case CAP_DEBUG_SKY_PLANE: *value = c->last_sky.form; return CAP_OK;
+    case CAP_DEBUG_SKY_PLANE_NONZERO:
+    {
+        const CapContext::LastSky& ls = c->last_sky;
+        const size_t               n  = (size_t)ls.n_slots * c->screen.pixels_padded;
+        if (!ls.form || !n || c->lane[ls.lane].pl_sky.n < n) return fail(CAP_ERR_STATE, "cap_debug_get: the last cap_render wrote no sky plane");
+        HIP_TRY(hipSetDevice(c->device));
+        if (sync_and_collect(c) != CAP_OK) return CAP_ERR_HIP;
+        unsigned long long h[1];
+        if (int e = count_on_device(c, h, [&](unsigned long long* d) { launch_sky_nonzero(c->stream, c->lane[ls.lane].pl_sky.p, n, d); })) return e;
+        *value = h[0];
+        return CAP_OK;
+    }
     case CAP_DEBUG_SELFTEST_GRAY:
     {
         const CapContext::LastQueues& lq = c->last_queues;

@@ -149,6 +149,7 @@ struct RenderPlan
     bool     sample_table = false;      // direction-sample terms from a per-batch table (ShadeArgs::sample_terms)
     bool     camera_table = false;      // the call sizes and groups for the camera-vertex table (camera_head: it also fits the rings)
     bool     gray_entries = false;      // the extension queues hold 32-byte entries, one throughput word (launch_trace_shade's gray)
+    bool     sky_plane = false;         // the sky term as one store into Planes::sky, added by the resolve (launch_trace_shade's sky_plane); plan_render: the call sizes for it, plan_forms: it runs
     // Jitter groups: the slots of a batch by the bits of (jitter_x, jitter_y).  slot_group[f]: the group of frame f within its batch,
     // numbered in order of first appearance; group_first[batch start + g]: the first slot of group g.  A group need not be contiguous.
     // slot_order[batch start + k]: the batch's slots sorted by group, stable; batch_walk_m[batch]: the slots per group if every group
@@ -176,7 +177,7 @@ struct Batch
 // call grows a lane (growing frees the old buffers, so the streams are drained first)
 struct LaneSizes
 {
-    size_t planes, queues, rings, counters, terms, camera;
+    size_t planes, queues, rings, counters, terms, camera, sky;
 };
 
 LaneSizes lane_sizes(const CapContext* c, const RenderPlan& p)
@@ -192,10 +193,12 @@ LaneSizes lane_sizes(const CapContext* c, const RenderPlan& p)
     z.terms = p.sample_table ? (size_t)p.slots * p.num_bounces * 4096 : 0;
     // the table of camera vertices (launch_camera_vertices): two planes of one entry per (jitter group, padded pixel), 0.5 GB at 8 groups of 1080p
     z.camera = 2 * (size_t)p.camera_groups * c->screen.pixels_padded;
+    // the sky plane (Planes::sky): one float per path, 0.53 GB at 64 slots of 1080p
+    z.sky = p.sky_plane ? z.planes : 0;
     return z;
 }
 
-bool lane_grows(const CapContext::Lane& L, const LaneSizes& z) { return L.pl_color.n < z.planes || L.counters.n < z.counters || L.terms.n < z.terms || L.camera.n < z.camera; }
+bool lane_grows(const CapContext::Lane& L, const LaneSizes& z) { return L.pl_color.n < z.planes || L.counters.n < z.counters || L.terms.n < z.terms || L.camera.n < z.camera || L.pl_sky.n < z.sky; }
 
 int ensure_lane(CapContext* c, CapContext::Lane& L, const LaneSizes& z)
 {
@@ -206,6 +209,7 @@ int ensure_lane(CapContext* c, CapContext::Lane& L, const LaneSizes& z)
     HIP_TRY(L.counters.ensure(z.counters));
     if (z.terms) HIP_TRY(L.terms.ensure(z.terms));
     if (z.camera) HIP_TRY(L.camera.ensure(z.camera));
+    if (z.sky) HIP_TRY(L.pl_sky.ensure(z.sky));
     // as much spill as lane 0, whose area cap_bvh_build allocates (for lane 0 itself: nothing to do)
     if (c->lane[0].stack_spill.n) HIP_TRY(L.stack_spill.ensure(c->lane[0].stack_spill.n));
     return CAP_OK;
@@ -386,6 +390,11 @@ int plan_render(const CapContext* c, uint32_t frame_begin, uint32_t n_frames, ui
     // A/B switch CAP_NO_CAMERA_TABLE.
     p.camera_table = p.sample_table && p.code_in_color && p.ring_form && !c->sw.on(SW_NO_CAMERA_TABLE) && c->debug_capacity_div <= 1;
     if (p.camera_table) jitter_groups(p);
+    // The sky term of an escaping path as one store into a write-only plane, added by the resolve, instead of three float atomics on
+    // the colour plane: the 32-byte kernels of a batch whose first launch is the head (it zeroes the plane) and whose resolve is the
+    // coded one (it adds the term).  code_in_color implies albedo_in_w, whose unused `albedo` word of Planes carries the plane, and no
+    // AOV.  This much sizes the plane; like camera_head, whether it runs is plan_forms' to say.  A/B switch CAP_NO_SKY_PLANE.
+    p.sky_plane = p.gray_entries && p.camera_table && p.code_in_color && !c->sw.on(SW_NO_SKY_PLANE);
 
     // primary rays: one per valid pixel per frame
     for (uint32_t lt = 0; lt < c->screen.local_tiles; ++lt)
@@ -454,6 +463,7 @@ void plan_forms(const CapContext* c, RenderPlan& p)
     // is shared, the form is still the faster one -- 1080p, tools/camera_table_small.py, ms per render off -> on: 1 slot depth 1
     // 0.1515 -> 0.1316, depth 2 0.2164 -> 0.1976; 2 slots 0.2261 -> 0.2017 and 0.3241 -> 0.2992 (docs/experiments.md (104)).
     p.camera_head = p.camera_table && p.wave_ring;
+    p.sky_plane   = p.sky_plane && p.camera_head;  // (gray_entries && camera_head && code_in_color, the switch off)
     // Camera rays of a DENSE scene.  The packet walk (one node sequence per 8x8-pixel tile) is the fast form while a tile's 64
     // rays meet few triangles: 9.3 per packet on the 262 k-triangle hall at 1080p (0.13 triangles per pixel).  At 16.8 M
     // triangles (8 per pixel) a tile covers hundreds of leaves, every lane pays for every one of them, and the stage was 7.2 of the
@@ -525,7 +535,7 @@ struct BatchRun
 int fused_bounce(CapContext* c, const RenderPlan& p, const Batch& bt, const BatchRun& r, const ShadeArgs& sa, bool head)
 {
     StageTimer     t(c, sa.bounce == 0 ? ST_PRIMARY : ST_CLOSEST, p.stage_timers);
-    const uint32_t form = launch_trace_shade(r.cfg, r.bvh, sa, p.ext, p.feedback, head, p.gray_entries);
+    const uint32_t form = launch_trace_shade(r.cfg, r.bvh, sa, p.ext, p.feedback, head, p.gray_entries, p.sky_plane);
     if (sa.bounce) ++c->stats.launches_trace_closest, c->last_mark_form = form;
     if (trace_launch(c, "trace_shade bounce %u batch %u", sa.bounce, bt.index)) return fail(CAP_ERR_HIP, "trace_shade failed");
     return CAP_OK;
@@ -648,7 +658,8 @@ int render_batch(CapContext* c, const RenderPlan& p, const Batch& bt, const Shad
     ShadeArgs sa = call_args;
     sa.frames    = bt.frames;
     if (!p.fused) sa.hits = L.hits.p;  // (fused: the same word is sample_terms, set per bounce)
-    sa.planes = Planes{L.pl_color.p, L.pl_direct.p, L.pl_albedo.p, c->aov_geo.p, c->aov_nd.p};
+    sa.planes = Planes{L.pl_color.p, L.pl_direct.p, {L.pl_albedo.p}, c->aov_geo.p, c->aov_nd.p};
+    if (p.sky_plane) sa.planes.sky = L.pl_sky.p, c->last_sky = CapContext::LastSky{1u, ns, bt.lane};  // (albedo_in_w: nobody reads `albedo`)
     sa.n_slots = ns, sa.max_count = ns * Ppad, sa.aov_slot = (p.aov && bt.last) ? ns - 1 : ~0u;
 
     if (p.sample_table)
@@ -726,7 +737,7 @@ int render_batch(CapContext* c, const RenderPlan& p, const Batch& bt, const Shad
     {
         StageTimer t(c, ST_RESOLVE, p.stage_timers);
         if (p.two_lanes && last_resolve) HIP_TRY(hipStreamWaitEvent(L.stream, last_resolve, 0));  // frame order of the additions
-        launch_resolve(r.cfg, sa.planes, ns, Ppad, c->accum.p, p.albedo_in_w != 0u, sa.scene.kd_untextured, p.code_in_color != 0u);
+        launch_resolve(r.cfg, sa.planes, ns, Ppad, c->accum.p, p.albedo_in_w != 0u, sa.scene.kd_untextured, p.code_in_color != 0u, p.sky_plane);
         if (p.two_lanes)
         {
             HIP_TRY(hipEventRecord(c->lane_ev[bt.lane], L.stream));
@@ -774,7 +785,7 @@ static int render_call(CapContext* c, uint32_t frame_begin, uint32_t n_frames, u
     // the debug state of a call (cap_debug_get), from the plan; what a batch leaves is reset until the first batch writes it
     c->last_mark_form = 0, c->last_sample_table = p.sample_table ? 1u : 0u, c->last_cull_camera_pairs = p.cull_camera_pairs;
     c->last_terms = CapContext::LastTerms{}, c->last_camera_table = 0, c->last_camera = CapContext::LastCamera{}, c->last_group_walk = 0, c->last_camera_reused = 0;
-    c->last_gray_entries = p.gray_entries ? 1u : 0u, c->last_queues = CapContext::LastQueues{};
+    c->last_gray_entries = p.gray_entries ? 1u : 0u, c->last_queues = CapContext::LastQueues{}, c->last_sky = CapContext::LastSky{};
     if (p.feedback && (c->post_w != c->screen.width || c->post_h != c->screen.height))
         if (int e = cap_post_reset(c)) return e;  // first frame: cleared histories, every vertex is a disocclusion
     // No host synchronisation with the previous call: everything it still uses is either ordered behind it on the stream (queues,

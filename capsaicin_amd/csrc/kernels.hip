@@ -1055,7 +1055,7 @@ template <bool FIRST_, bool EXT_, bool FB_ = false>
 struct ShadeStageCfg
 {
     static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_;
-    static constexpr bool CARRY = false, SKY_RMW = true, PROBE = false, TAME = false, LEAN = false, CODE = false, TAB = false, GRAY = false;
+    static constexpr bool CARRY = false, SKY_RMW = true, PROBE = false, TAME = false, LEAN = false, CODE = false, TAB = false, GRAY = false, SKYP = false;
     using Thr = v3;
 };
 

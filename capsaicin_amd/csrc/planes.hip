@@ -2,6 +2,8 @@
 // the geometry AOV.
 #include "cap_kernels.h"
 
+#include <algorithm>
+
 namespace cap
 {
 // ------------------------------------------------------------------------------------------------
@@ -80,17 +82,80 @@ __global__ __launch_bounds__(kBlock) void k_resolve_coded(Planes planes, uint32_
     }
 }
 
+// The sky-plane form (launch_trace_shade's sky_plane): k_resolve_coded, and the sky term of every path added here.  planes.sky holds the
+// throughput of a path that escaped at bounce >= 1 and +0 for every other (cap_shade.h shade_vertex has the argument why the sums
+// below are the bits the atomics on the colour plane left).  The eight sky loads of a group go out with its eight colour loads: no
+// round trip is added.  t7 serves x and y as it does in the kernels' atomic form; the products stay products and the sums sums
+// (-ffp-contract=off).
+__global__ __launch_bounds__(kBlock) void k_resolve_coded_sky(Planes planes, uint32_t n_slots, uint32_t Ppad, float4* accum, float kd_untextured)
+{
+    constexpr uint32_t kGroup = 8;
+    for (uint32_t pl = blockIdx.x * kBlock + threadIdx.x; pl < Ppad; pl += gridDim.x * kBlock)
+    {
+        float4 acc = accum[pl];
+        for (uint32_t s0 = 0; s0 < n_slots; s0 += kGroup)
+        {
+            float4 c[kGroup], d[kGroup];
+            float  s[kGroup];
+#pragma unroll
+            for (uint32_t k = 0; k < kGroup; ++k)
+            {
+                c[k] = make_float4(0.f, 0.f, 0.f, 0.f), s[k] = 0.0f;
+                if (s0 + k < n_slots) c[k] = planes.color[(size_t)(s0 + k) * Ppad + pl], s[k] = planes.sky[(size_t)(s0 + k) * Ppad + pl];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < kGroup; ++k)
+            {
+                d[k] = c[k].w == kCodeSky ? make_float4(0.7f, 0.7f, 0.85f, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (c[k].w >= kCodeLit) d[k] = planes.direct[(size_t)(s0 + k) * Ppad + pl];  // (never on a slot behind n_slots: its c is 0)
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < kGroup; ++k)
+                if (s0 + k < n_slots)
+                {
+                    const float code = c[k].w >= kCodeLit ? c[k].w - kCodeLit : c[k].w;
+                    const float al   = code == kCodeSky ? 1.0f : (code == kCodeKd ? kd_untextured : 0.0f);
+                    const float t7 = s[k] * 0.7f, t85 = s[k] * 0.85f;
+                    const float cx = c[k].x + t7, cy = c[k].y + t7, cz = c[k].z + t85;
+                    acc.x = acc.x + (cx * al + d[k].x);
+                    acc.y = acc.y + (cy * al + d[k].y);
+                    acc.z = acc.z + (cz * al + d[k].z);
+                    acc.w = acc.w + 1.0f;
+                }
+        }
+        accum[pl] = acc;
+    }
+}
+
 void launch_resolve(const LaunchCfg& cfg, const Planes& planes, uint32_t n_slots, uint32_t Ppad, float4* accum, bool albedo_in_w,
-                    float kd_untextured, bool code_in_color)
+                    float kd_untextured, bool code_in_color, bool sky_plane)
 {
     uint32_t g = (Ppad + kBlock - 1) / kBlock;
     if (g > 4096) g = 4096;
-    if (code_in_color)
+    if (sky_plane)  // (the host's condition implies code_in_color)
+        hipLaunchKernelGGL(k_resolve_coded_sky, dim3(g ? g : 1), dim3(kBlock), 0, cfg.stream, planes, n_slots, Ppad, accum, kd_untextured);
+    else if (code_in_color)
         hipLaunchKernelGGL(k_resolve_coded, dim3(g ? g : 1), dim3(kBlock), 0, cfg.stream, planes, n_slots, Ppad, accum, kd_untextured);
     else if (albedo_in_w)
         hipLaunchKernelGGL(k_resolve<true>, dim3(g ? g : 1), dim3(kBlock), 0, cfg.stream, planes, n_slots, Ppad, accum, kd_untextured);
     else
         hipLaunchKernelGGL(k_resolve<false>, dim3(g ? g : 1), dim3(kBlock), 0, cfg.stream, planes, n_slots, Ppad, accum, kd_untextured);
+}
+
+// cap_debug_get(CAP_DEBUG_SKY_PLANE_NONZERO): the words of a sky plane that are not +0 (a -0 or a NaN counts: the head stores +0)
+__global__ __launch_bounds__(kBlock) void k_sky_nonzero(const float* sky, size_t n, unsigned long long* out)
+{
+    unsigned long long m = 0;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) m += f2u(sky[i]) != 0u ? 1u : 0u;
+    for (int off = 32; off > 0; off >>= 1) m += __shfl_down(m, off);
+    if ((threadIdx.x & 63u) == 0 && m) atomicAdd(out, m);
+}
+
+void launch_sky_nonzero(hipStream_t stream, const float* sky, size_t n, unsigned long long* out_device)
+{
+    if (!n) return;
+    const size_t g = std::min<size_t>(4096, (n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_sky_nonzero, dim3((uint32_t)g), dim3(kBlock), 0, stream, sky, n, out_device);
 }
 
 __global__ __launch_bounds__(kBlock) void k_untile(ScreenDev sc, const float4* src, const float4* albedo, const float4* direct,

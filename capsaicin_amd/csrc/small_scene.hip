@@ -39,7 +39,11 @@ __device__ unsigned long long g_wave_times[2 * 16384];  // (start, end) s_memrea
 // GRAY: the extension queue's 32-byte entries (RayQueue, cap_device.h) and the throughput as one float, for a scene without textures.  A
 // FIRST kernel writes them, the bounce >= 1 kernel reads and writes them, the HEAD kernel writes them.  Only the TAB kernels have the form
 // (k_trace_shade_tab_gray, k_trace_shade_head_gray), beside their 48-byte forms: trace_shade_has_gray_form.
-template <bool FIRST_, bool EXT_, bool FB_, bool LDS_, bool TAME_, bool CODE_ = false, bool TAB_ = false, bool HEAD_ = false, bool GRAY_ = false>
+// SKYP: the sky term of an escaping path goes to ShadeArgs::planes.sky as one plain store instead of three float atomics on the colour
+// plane, and the resolve adds it (shade_vertex's escape branch has the argument).  The head zeroes the plane next to its store of the
+// code.  Only the GRAY bounce >= 1 kernel and the GRAY head have the form (k_trace_shade_tab_gray_sky, k_trace_shade_head_gray_sky).
+template <bool FIRST_, bool EXT_, bool FB_, bool LDS_, bool TAME_, bool CODE_ = false, bool TAB_ = false, bool HEAD_ = false, bool GRAY_ = false,
+          bool SKYP_ = false>
 struct TraceShadeCfg
 {
     // (TAB_ = kChunkLean in k_trace_shade_tab: a build without the lean plumbing compiles the plain kernel under that name, never launched)
@@ -48,7 +52,9 @@ struct TraceShadeCfg
     static_assert(!TAB_ || (TAME_ && kChunkLean), "TAB: the lean kernels (reference model, scene in LDS, tame records)");
     static_assert(!HEAD_ || (TAB_ && !FIRST_), "HEAD: the lean bounce >= 1 kernel with the sample table");
     static_assert(!GRAY_ || TAB_, "GRAY: the lean kernels with the sample table");
+    static_assert(!SKYP_ || (GRAY_ && !FIRST_), "SKYP: the 32-byte bounce >= 1 kernel and its head form");
     static constexpr bool FIRST = FIRST_, EXT = EXT_, FB = FB_, LDS = LDS_, TAME = TAME_, CODE = CODE_, TAB = TAB_, HEAD = HEAD_, GRAY = GRAY_;
+    static constexpr bool SKYP = SKYP_;
     using Thr = typename std::conditional<GRAY_, float, v3>::type;  // a path's throughput
     static constexpr bool CARRY = !EXT && !TAB, SKY_RMW = false;
     static constexpr bool PROBE = !EXT && !FB && LDS;  // the producer-side shadow probe (ShadeArgs::inline_probe) and the per-wave ring
@@ -157,9 +163,10 @@ __device__ __forceinline__ void stage_probe_rows(const BvhDev& bvh, const ShadeA
     }
 }
 
-// All five kernels are small_scene_body.h and nothing else: k_trace_shade the thirteen forms without the sample table, under the names
+// All seven kernels are small_scene_body.h and nothing else: k_trace_shade the thirteen forms without the sample table, under the names
 // and with the instructions they have always had, k_trace_shade_tab the three with it, k_trace_shade_head (below) bounce 1 with bounce 0
-// at the head of its chunks, k_trace_shade_tab_gray and k_trace_shade_head_gray those four with 32-byte queue entries.
+// at the head of its chunks, k_trace_shade_tab_gray and k_trace_shade_head_gray those four with 32-byte queue entries,
+// k_trace_shade_tab_gray_sky and k_trace_shade_head_gray_sky the two of those that run at bounce >= 1 with the sky plane.
 template <bool FIRST, bool EXT, bool FB = false, bool LDS = false, bool TAME = false, bool CODE = false>
 __global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, EXT, FB, LDS, TAME, CODE>::kBlocksPerCu)) void k_trace_shade(BvhDev bvh, ShadeArgs a)
 {
@@ -196,6 +203,21 @@ __global__ __launch_bounds__(kBlock, (TraceShadeCfg<FIRST, false, false, true, t
 __global__ __launch_bounds__(kBlock, (TraceShadeCfg<false, false, false, true, true, false, kChunkLean, kChunkLean, kChunkLean>::kBlocksPerCu)) void k_trace_shade_head_gray(BvhDev bvh, ShadeArgs a)
 {
     using C              = TraceShadeCfg<false, false, false, true, true, false, kChunkLean, kChunkLean, kChunkLean>;
+    constexpr bool FIRST = false, EXT = false, FB = false, LDS = true, TAB = kChunkLean;
+#include "small_scene_body.h"
+}
+
+// SKYP: the 32-byte bounce >= 1 kernel and the 32-byte head with the sky plane, beside the two above -- which keep their names and their
+// instructions, so that the switch CAP_NO_SKY_PLANE stands for the commit before these in a measurement
+__global__ __launch_bounds__(kBlock, (TraceShadeCfg<false, false, false, true, true, false, kChunkLean, false, kChunkLean, kChunkLean>::kBlocksPerCu)) void k_trace_shade_tab_gray_sky(BvhDev bvh, ShadeArgs a)
+{
+    using C              = TraceShadeCfg<false, false, false, true, true, false, kChunkLean, false, kChunkLean, kChunkLean>;
+    constexpr bool FIRST = false, EXT = false, FB = false, LDS = true, TAB = kChunkLean;
+#include "small_scene_body.h"
+}
+__global__ __launch_bounds__(kBlock, (TraceShadeCfg<false, false, false, true, true, false, kChunkLean, kChunkLean, kChunkLean, kChunkLean>::kBlocksPerCu)) void k_trace_shade_head_gray_sky(BvhDev bvh, ShadeArgs a)
+{
+    using C              = TraceShadeCfg<false, false, false, true, true, false, kChunkLean, kChunkLean, kChunkLean, kChunkLean>;
     constexpr bool FIRST = false, EXT = false, FB = false, LDS = true, TAB = kChunkLean;
 #include "small_scene_body.h"
 }
@@ -468,10 +490,11 @@ void launch_gray_selftest(hipStream_t stream, const RayQueue& q, unsigned long l
     hipLaunchKernelGGL(k_gray_selftest, dim3(std::min(4096u, (total + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, q, out_device);
 }
 
-// The twenty-one instantiations that exist, each under the tuple it was instantiated with.  Bounce 0 has no feedback form, the two
+// The twenty-three instantiations that exist, each under the tuple it was instantiated with.  Bounce 0 has no feedback form, the two
 // models and feedback exclude each other, TAME is the reference model with the scene in LDS, CODE its bounce 0, TAB its three lean
-// kernels with the sample table, HEAD the fourth and GRAY those four with 32-byte queue entries (TraceShadeCfg).
-enum : uint32_t { TS_FIRST = 1, TS_EXT = 2, TS_FB = 4, TS_LDS = 8, TS_TAME = 16, TS_CODE = 32, TS_TAB = 64, TS_HEAD = 128, TS_GRAY = 256 };
+// kernels with the sample table, HEAD the fourth, GRAY those four with 32-byte queue entries and SKYP the two of those that run at
+// bounce >= 1 with the sky plane (TraceShadeCfg).
+enum : uint32_t { TS_FIRST = 1, TS_EXT = 2, TS_FB = 4, TS_LDS = 8, TS_TAME = 16, TS_CODE = 32, TS_TAB = 64, TS_HEAD = 128, TS_GRAY = 256, TS_SKYP = 512 };
 struct TraceShadeKernel
 {
     uint32_t is;
@@ -480,7 +503,12 @@ struct TraceShadeKernel
 template <uint32_t IS>
 constexpr TraceShadeKernel trace_shade_kernel()
 {
-    if constexpr ((IS & TS_HEAD) != 0)
+    if constexpr ((IS & TS_SKYP) != 0)
+    {
+        static_assert((IS & ~TS_HEAD) == (TS_LDS | TS_TAME | TS_TAB | TS_GRAY | TS_SKYP), "SKYP: the 32-byte bounce >= 1 kernel and its head form");
+        return {IS, (IS & TS_HEAD) != 0 ? k_trace_shade_head_gray_sky : k_trace_shade_tab_gray_sky};
+    }
+    else if constexpr ((IS & TS_HEAD) != 0)
     {
         static_assert((IS & ~TS_GRAY) == (TS_LDS | TS_TAME | TS_TAB | TS_HEAD), "HEAD: the lean bounce >= 1 kernel");
         return {IS, (IS & TS_GRAY) != 0 ? k_trace_shade_head_gray : k_trace_shade_head};
@@ -499,8 +527,8 @@ constexpr TraceShadeKernel trace_shade_kernel()
     else
         return {IS, k_trace_shade<(IS & TS_FIRST) != 0, (IS & TS_EXT) != 0, (IS & TS_FB) != 0, (IS & TS_LDS) != 0, (IS & TS_TAME) != 0, (IS & TS_CODE) != 0>};
 }
-// (a build without the lean plumbing, -DCAP_CHUNK_PLAIN, has no table form: trace_shade_has_table_form() says so and the last eight are never looked up)
-constexpr uint32_t         kTraceShadeKernelCount = 21;
+// (a build without the lean plumbing, -DCAP_CHUNK_PLAIN, has no table form: trace_shade_has_table_form() says so and the last ten are never looked up)
+constexpr uint32_t         kTraceShadeKernelCount = 23;
 constexpr TraceShadeKernel kTraceShadeKernels[kTraceShadeKernelCount] = {
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_CODE>(),
     trace_shade_kernel<TS_FIRST | TS_EXT | TS_LDS>(), trace_shade_kernel<TS_FIRST | TS_EXT>(),
@@ -512,6 +540,7 @@ constexpr TraceShadeKernel kTraceShadeKernels[kTraceShadeKernelCount] = {
     trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB | TS_HEAD>(),
     trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_CODE | TS_TAB | TS_GRAY>(), trace_shade_kernel<TS_FIRST | TS_LDS | TS_TAME | TS_TAB | TS_GRAY>(),
     trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB | TS_GRAY>(), trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB | TS_HEAD | TS_GRAY>(),
+    trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB | TS_GRAY | TS_SKYP>(), trace_shade_kernel<TS_LDS | TS_TAME | TS_TAB | TS_HEAD | TS_GRAY | TS_SKYP>(),
 };
 
 // the unscaled forms: reference model, scene in LDS, tame shading records (-DCAP_SHADE_IEEE keeps the plain sqrtf and `/`
@@ -529,7 +558,7 @@ bool trace_shade_has_table_form(const BvhDev& bvh, const SceneDev& scene) { retu
 // the table kernels with 32-byte entries: kd = (k, k, k) at every vertex, which is what keeps a throughput's three components equal
 bool trace_shade_has_gray_form(const BvhDev& bvh, const SceneDev& scene) { return trace_shade_has_table_form(bvh, scene) && scene.texture_count == 0; }
 
-uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback, bool camera_head, bool gray)
+uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const ShadeArgs& args, bool ext, bool feedback, bool camera_head, bool gray, bool sky_plane)
 {
     const bool first = args.bounce == 0;
     const bool fb    = feedback && !ext && !first;  // (bounce 0 defines the planes' entries: nothing to reuse yet)
@@ -545,8 +574,11 @@ uint32_t launch_trace_shade(const LaunchCfg& cfg, const BvhDev& bvh, const Shade
     assert(!camera_head || (args.bounce == 1 && tab && args.inline_probe && args.wave_ring && args.in.org_tmin && args.in.dir_tmax && args.in.thr_pid));
     // 32-byte entries: like the table, every launch of a batch or none (the host's condition: the table form and trace_shade_has_gray_form())
     assert(!gray || (tab && args.scene.texture_count == 0));
+    // the sky plane: every launch of a batch or none -- the head zeroes what the later launches store into and the resolve adds (the
+    // host's condition: 32-byte entries, the head form and the code in the colour plane, whose albedo_in_w frees the plane's word)
+    assert(!sky_plane || (gray && !first && args.albedo_in_w && args.code_in_color && args.planes.sky));
     const uint32_t is = (first ? TS_FIRST : 0u) | (ext ? TS_EXT : 0u) | (fb ? TS_FB : 0u) | (lds ? TS_LDS : 0u) | (tame ? TS_TAME : 0u) | (code ? TS_CODE : 0u) | (tab ? TS_TAB : 0u) |
-                        (camera_head ? TS_HEAD : 0u) | (gray ? TS_GRAY : 0u);
+                        (camera_head ? TS_HEAD : 0u) | (gray ? TS_GRAY : 0u) | (sky_plane ? TS_SKYP : 0u);
     // the queue's persistent grid; bounce 0's queue is the identity queue of the batch, one entry per padded pixel and frame slot
     const uint32_t gx = queue_grid(cfg, (first || camera_head) ? args.screen.pixels_padded * args.n_slots : args.max_count);
     const TraceShadeKernel* k = kTraceShadeKernels;

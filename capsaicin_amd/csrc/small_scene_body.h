@@ -154,6 +154,11 @@
             const v3 I = mk3(fc.light_intensity[0], fc.light_intensity[1], fc.light_intensity[2]);
             // the plane's entry: (0, 0, 0, code) whatever the code says -- padding, sky, kd or black
             a.planes.color[(size_t)slot * Ppad + i] = make_float4(0.f, 0.f, 0.f, cp.w);
+            // SKYP: and the sky plane's, +0 for every lane that stores a code -- padding and sky pixels included, and before the `continue`
+            // of a wave without rays -- so that the resolve finds the previous batch's value nowhere.  A lane whose own path escapes at
+            // bounce 1 stores its throughput over this zero further down (shade_vertex): same lane, same address, program order, which
+            // is what the ring's 12-byte stores rest on too (trace_ring).
+            if constexpr (C::SKYP) a.planes.sky[(size_t)slot * Ppad + i] = 0.0f;
             const bool vtx = cp.w == kCodeKd || cp.w == kCodeBlack, lit = cp.w == kCodeKd;
             const v3   p = mk3(cp.x, cp.y, cp.z), n = mk3(cn.x, cn.y, cn.z);
             bool       emit_shadow = false, emit_ext = false;

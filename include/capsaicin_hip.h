@@ -340,6 +340,15 @@ enum
      * checks a reused table like a built one. */
     CAP_DEBUG_GROUP_WALK            = 22,
     CAP_DEBUG_CAMERA_TABLE_REUSED   = 23,
+    /* SKY_PLANE (get): 1 if the fused small-scene launches of the last cap_render wrote the sky term of a path that escapes at bounce >= 1
+     * as one store of its throughput into a plane of one float per (frame slot, padded pixel), which the resolve adds to the path's
+     * colour -- and 0 if they added it to the colour plane with three float atomics (the switch CAP_NO_SKY_PLANE, and every render
+     * without GRAY_ENTRIES, without CAMERA_TABLE or with CAP_RENDER_AOV).  Same bits and the same CapStats either way: the resolve's
+     * additions are the atomics', on the same operands in the same order.
+     * SKY_PLANE_NONZERO (get, right after such a render): the entries of the last batch's plane that are not +0, counted on the device:
+     * the paths of that batch that escaped at bounce >= 1 with a throughput other than +0. */
+    CAP_DEBUG_SKY_PLANE             = 24,
+    CAP_DEBUG_SKY_PLANE_NONZERO     = 25,
     /* A/B and diagnostic switches of the build and render paths (which kernels trace the camera and the shadow rays, one or two batch
      * lanes, the builders' parameters ...): ONE table per context, key = SWITCH_BASE + cap_debug_switch_index("CAP_..."), the names being
      * the environment variables that fill the table once, at cap_ctx_create (tools set those around a whole process; nothing else in the
