@@ -303,6 +303,7 @@ SYMBOLS = {
     "cap_debug_closest_instance_bound": (_i, [_vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "cap_debug_overlap_instance_prune": (_i, [_vp] * 17),
     "cap_debug_overlap_world_node": (_i, [_vp] * 12),
+    "cap_debug_sweep_instance_prune": (_i, [_vp] * 6 + [C.c_float] + [_vp] * 7),
     "cap_render": (_i, [_vp, _u32, _u32, _u32, _u32]),
     "cap_accum_reset": (_i, [_vp]),
     "cap_accum_import": (_i, [_vp, _vp, _u64]),
@@ -329,6 +330,7 @@ SYMBOLS = {
     "cap_trace_instances_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_closest_points": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
     "cap_sweep_spheres": (_i, [_vp, _vp, _u64, _vp, C.POINTER(TraceOptions)]),
+    "cap_sweep_instances": (_i, [_vp, _vp, _u64, _vp, _vp, C.POINTER(TraceOptions)]),
     "cap_closest_points_multi": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_overlap_boxes": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
     "cap_overlap_instances": (_i, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, C.POINTER(TraceOptions)]),
@@ -946,6 +948,14 @@ class Renderer:
         trace_rays."""
         import torch
         return self._single("cap_sweep_spheres", sweeps, 8, "sweeps", out, 8, torch.float32, sync, (self.trace_options(None, mask),))
+
+    def sweep_instances(self, sweeps, out=None, sync=True, mask=None):
+        """The first contact of each moving sphere with the instance table, in WORLD space (cap_sweep_instances): (records (N, 8)
+        float32, instances (N,) int32, -1 on a miss).  The records are sweep_spheres' -- world-space contact point, the time t, (u, v),
+        the scene's triangle id and the feature: closest_triangles() reads those; the winner is minimal in (t, instance, triangle).
+        Needs set_instances().  sweeps, out, sync and mask= as sweep_spheres; numpy sweeps give numpy results."""
+        import torch
+        return self._single("cap_sweep_instances", sweeps, 8, "sweeps", out, 8, torch.float32, sync, (self.trace_options(None, mask),), (torch.int32,))
 
     @staticmethod
     def sweep_queries(origin, radius, direction, tmax=np.inf):

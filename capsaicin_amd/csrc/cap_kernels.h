@@ -252,6 +252,19 @@ struct ClosestInstMultiArgs
 void launch_closest_instances_multi(const LaunchCfg& cfg, const BvhDev& bvh, const ClosestInstMultiArgs& m, const TlasDev& tl, const RayFilter& f,
                                     uint32_t depth);
 
+// Sphere sweeps over the instance table (cap_sweep_instances, sweep.hip k_sweep_inst; a = SweepArgs above): the sweeps are in world space, a.out as above and inst_out the
+// instance of each record (may be NULL).  a.mag is not read: the prune radius is per sweep and instance (cap_near.h
+// sweep_prune_radius).  descs, near and xw_max as ClosestInstArgs'; bvh, tl, f and depth as launch_closest_instances'.
+struct SweepInstArgs
+{
+    SweepArgs       a;
+    uint32_t*       inst_out;
+    const float4*   descs;
+    const float2*   near;
+    const uint32_t* xw_max;
+};
+void launch_sweep_instances(const LaunchCfg& cfg, const BvhDev& bvh, const SweepInstArgs& a, const TlasDev& tl, const RayFilter& f, uint32_t depth);
+
 // Box overlap queries (cap_overlap_boxes, overlap.hip k_overlap_boxes): boxes = CapBoxDesc records (two float4: lo, hi; the w words are
 // not read), out = pages of k triangle ids per box (NULL when k = 0), counts = n candidate counts or NULL, resume: slot k - 1 of each
 // page is the cursor (CAP_MULTI_CONTINUE).  slack: what the query box is grown by before it is compared with the node boxes,

@@ -210,4 +210,50 @@ __host__ __device__ __forceinline__ void overlap_world_box(const float m[12], fl
         wlo[r] = cw - hw, whi[r] = cw + hw;
     }
 }
+
+// ---- sphere sweep queries (cap_sweep_spheres, cap_sweep_instances; sweep.hip) ----
+// The walk's time comparisons and its box test, host and device: both kernels and cap_debug_sweep_instance_prune (context.hip) run them.
+constexpr float kSweepPad  = 1.0f + 8.0f * 5.9604645e-8f;  // the slab test's relative padding
+constexpr float kSweepTiny = 1.17549435e-38f;              // ... and its absolute one: the smallest normal number
+constexpr float kSweepHuge = 3.40282347e38f;
+
+
+// the far side of every time comparison of the walk
+__host__ __device__ __forceinline__ float sweep_padded(float t) { return t * kSweepPad + kSweepTiny; }
+
+// What a lane keeps of its sweep for the walk: the origin, 1 / d per component and the prune radius
+struct SweepRay
+{
+    float ox, oy, oz, ix, iy, iz, grow;
+};
+
+// The ray against the box [lo, hi] grown by grow, over [0, far]: true = not rejected, tn = the entry time (0 inside), xp = the padded
+// exit it is compared with.  A component of d that is 0 gives +-inf or, on a plane through o, a NaN, which v_min / v_max drop: that
+// slab then constrains nothing it should not.
+__host__ __device__ __forceinline__ bool sweep_slab_times(const SweepRay& s, float lox, float loy, float loz, float hix, float hiy, float hiz, float far,
+                                                          float& tn, float& xp)
+{
+    const float ax = ((lox - s.grow) - s.ox) * s.ix, bx = ((hix + s.grow) - s.ox) * s.ix;
+    const float ay = ((loy - s.grow) - s.oy) * s.iy, by = ((hiy + s.grow) - s.oy) * s.iy;
+    const float az = ((loz - s.grow) - s.oz) * s.iz, bz = ((hiz + s.grow) - s.oz) * s.iz;
+    const float en = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), 0.f));
+    const float ex = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), far));
+    tn             = fminf(en, kSweepHuge);
+    xp             = sweep_padded(ex);
+    return tn <= xp;
+}
+__host__ __device__ __forceinline__ bool sweep_slab(const SweepRay& s, float lox, float loy, float loz, float hix, float hiy, float hiz, float far, float& tn)
+{
+    float xp;
+    return sweep_slab_times(s, lox, loy, loz, hix, hiy, hiz, far, tn, xp);
+}
+
+// ---- sphere sweep queries over instances (cap_sweep_instances, sweep.hip k_sweep_inst) ----
+// The prune radius of a sweep of radius r from an origin with |o|_inf = omax against an instance of world extent xw (the table's largest
+// at the top level): R = fl(r + fl(C eps . fl(fl(omax + xw) + r))), what every world box -- the stored ones of the top level, the images
+// of the object's node boxes under overlap_world_box below -- is grown by before the slab test of the world ray.  DESIGN.md "Sphere
+// sweep queries over instances" counts what it holds: the argument needs 87 of the 128.  cap_debug_sweep_instance_prune runs the same
+// function.
+constexpr float kSweepInstC = 128.0f;
+__host__ __device__ __forceinline__ float sweep_prune_radius(float r, float omax, float xw) { return r + (kSweepInstC * kNearEps) * ((omax + xw) + r); }
 }  // namespace cap

@@ -458,6 +458,45 @@ int cap_debug_overlap_world_node(const float* transform, const float* object_lo,
     return CAP_OK;
 }
 
+// The bottom-level prune of cap_sweep_instances (cap_near.h: the functions k_sweep_inst's sweep_world_node_step runs) for one transform,
+// one object box, one object-space node box, one sweep (origin, radius, direction, tmax: the tmax word is not read) and one far bound.
+// No context, no device: tests/test_sweep_instances.py.
+int cap_debug_sweep_instance_prune(const float* transform, const float* object_lo, const float* object_hi, const float* node_lo, const float* node_hi,
+                                   const float* sweep, float far_bound, float* xw, float* radius, float* world_lo, float* world_hi, float* entry,
+                                   float* exit_padded, uint32_t* skip_node)
+{
+    if (!transform || !object_lo || !object_hi || !node_lo || !node_hi || !sweep) return fail(CAP_ERR_INVALID_ARG, "cap_debug_sweep_instance_prune: NULL input");
+    double m[12], w[12], wd[12], A[12], nA, kappa, blo[3], bhi[3];
+    float  wf[12], mf[12];
+    bool   live = true;
+    for (int k = 0; k < 12; ++k) mf[k] = transform[k], m[k] = (double)transform[k], live = live && finite_d(m[k]);
+    for (int k = 0; k < 3; ++k) blo[k] = (double)object_lo[k], bhi[k] = (double)object_hi[k];
+    live = instance_inverse(m, live, w, wf, wd, A, nA, kappa, (float)CAP_INSTANCE_MAX_CONDITION);
+    const float xi   = live ? near_world_extent(m, blo, bhi) : 0.0f;
+    const float omax = fmaxf(fabsf(sweep[0]), fmaxf(fabsf(sweep[1]), fabsf(sweep[2])));
+    const float R    = live ? sweep_prune_radius(sweep[3], omax, xi) : 0.0f;
+    float       wlo[3] = {0.f, 0.f, 0.f}, whi[3] = {0.f, 0.f, 0.f}, tn = 0.f, xp = 0.f;
+    bool        keep = true;
+    if (live)
+    {
+        const SweepRay s{sweep[0], sweep[1], sweep[2], 1.0f / sweep[4], 1.0f / sweep[5], 1.0f / sweep[6], R};
+        overlap_world_box(mf, node_lo[0], node_lo[1], node_lo[2], node_hi[0], node_hi[1], node_hi[2], wlo, whi);
+        keep = sweep_slab_times(s, wlo[0], wlo[1], wlo[2], whi[0], whi[1], whi[2], far_bound, tn, xp);
+    }
+    if (xw) *xw = xi;
+    if (radius) *radius = R;
+    for (int k = 0; k < 3; ++k)
+    {
+        if (world_lo) world_lo[k] = wlo[k];
+        if (world_hi) world_hi[k] = whi[k];
+    }
+    if (entry) *entry = tn;
+    if (exit_padded) *exit_padded = xp;
+    // an inert instance is never entered: nothing to skip
+    if (skip_node) *skip_node = live && !keep ? 1u : 0u;
+    return CAP_OK;
+}
+
 int cap_ctx_create(int device_id, void* hip_stream, CapContext** out_ctx)
 {
     if (!out_ctx) return fail(CAP_ERR_INVALID_ARG, "cap_ctx_create: out_ctx is NULL");

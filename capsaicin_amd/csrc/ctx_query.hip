@@ -1,5 +1,5 @@
 // ctx_query.hip — the ray-query entry points (cap_trace_*) over the launchers of query.hip (scene trees; binary tree: kernels.hip
-// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip), cap_sweep_spheres (sweep.hip), cap_overlap_boxes, cap_overlap_instances, cap_overlap_triangles and cap_overlap_triangles_instances (overlap.hip) and cap_winding_numbers and cap_winding_instances (winding.hip).  Every entry point checks in this order and touches the device only after the last
+// k_query_binary) and instance.hip (instance table), and the closest-point queries (cap_closest_points, cap_signed_distance, cap_closest_points_multi, cap_closest_instances, cap_closest_instances_multi, cap_signed_distance_instances; point_query.hip), cap_sweep_spheres and cap_sweep_instances (sweep.hip), cap_overlap_boxes, cap_overlap_instances, cap_overlap_triangles and cap_overlap_triangles_instances (overlap.hip) and cap_winding_numbers and cap_winding_instances (winding.hip).  Every entry point checks in this order and touches the device only after the last
 // check: ctx, flags, filter, k rules, state, n == 0 (CAP_OK), NULL pointers, ranges (query_ranges.h).
 #include <algorithm>
 #include <cmath>
@@ -373,9 +373,11 @@ int closest_query(CapContext* c, const char* what, const CapPointDesc* points, u
     });
 }
 
-// cap_sweep_spheres (sweep.hip k_sweep_spheres): the first contact of each moving sphere with the scene, on the binary tree alone.
-// cap_closest_points' checks, with "sweeps" and "hits" as the arrays' names.
-int sweep_query(CapContext* c, const char* what, const CapSweepDesc* sweeps, uint64_t n, CapSweepHit* out, const CapTraceOptions* options)
+// cap_sweep_spheres (sweep.hip k_sweep_spheres): the first contact of each moving sphere with the scene, on the binary tree alone;
+// with `instanced` cap_sweep_instances (k_sweep_inst): world-space sweeps over the instance table, `inst` the instance of each record
+// (may be left out).  cap_closest_points' and cap_closest_instances' checks, with "sweeps", "hits" and "instances" as the arrays' names.
+int sweep_query(CapContext* c, const char* what, const CapSweepDesc* sweeps, uint64_t n, CapSweepHit* out, uint32_t* inst, bool instanced,
+                const CapTraceOptions* options)
 {
     static_assert(sizeof(CapSweepDesc) == 2 * sizeof(float4) && sizeof(CapSweepHit) == 2 * sizeof(float4), "sweep records are the kernel's float4 records");
     if (!c) return fail(CAP_ERR_INVALID_ARG, "%s: ctx is NULL", what);
@@ -383,15 +385,26 @@ int sweep_query(CapContext* c, const char* what, const CapSweepDesc* sweeps, uin
     QueryFilter flt;
     if (const int rc = query_filter(c, what, options, false, flt)) return rc;
     if (const int rc = query_state(c, what)) return rc;
+    if (instanced && c->inst_count == 0) return fail(CAP_ERR_STATE, "%s: call cap_instances_set first", what);
     if (n == 0) return CAP_OK;
     if (!sweeps || !out) return fail(CAP_ERR_INVALID_ARG, "%s: NULL device pointer", what);
-    if (const int rc = check_ranges(what, n, {range("sweeps", sweeps, sizeof(CapSweepDesc), 16), range("hits", out, sizeof(CapSweepHit), 16)})) return rc;
+    if (const int rc = check_ranges(what, n, {range("sweeps", sweeps, sizeof(CapSweepDesc), 16), range("hits", out, sizeof(CapSweepHit), 16),
+                                              range("instances", inst, sizeof(uint32_t), 4)}))
+        return rc;
     QueryRun run;
     if (const int rc = query_prepare(c, what, n, run, false)) return rc;
+    if (instanced) use_instance_pools(run);
     const RayFilter* f = flt.scene();
     return for_each_chunk(run, sweeps, n, [&](const QueryArgs& chunk, uint64_t first) {
-        launch_sweep_spheres(run.cfg, run.bvh, SweepArgs{chunk.rays, chunk.n, reinterpret_cast<float4*>(out + first), run.mag}, f, c->bvh_info.max_depth);
-        return run.traced("k_sweep_spheres", first);
+        // (the instanced kernel takes its prune radius per sweep and instance: cap_near.h)
+        const SweepArgs a{chunk.rays, chunk.n, reinterpret_cast<float4*>(out + first), instanced ? 0.f : run.mag};
+        if (!instanced)
+        {
+            launch_sweep_spheres(run.cfg, run.bvh, a, f, c->bvh_info.max_depth);
+            return run.traced("k_sweep_spheres", first);
+        }
+        launch_sweep_instances(run.cfg, run.bvh, SweepInstArgs{a, at(inst, first), c->inst_desc.p, c->inst_near.p, c->inst_misc.p + 7}, run.tl, flt.f, run.depth);
+        return run.traced("k_sweep_inst", first);
     });
 }
 
@@ -497,7 +510,13 @@ extern "C" {
 
 int cap_sweep_spheres(CapContext* c, const CapSweepDesc* device_sweeps, uint64_t n, CapSweepHit* device_out, const CapTraceOptions* options)
 {
-    return sweep_query(c, "cap_sweep_spheres", device_sweeps, n, device_out, options);
+    return sweep_query(c, "cap_sweep_spheres", device_sweeps, n, device_out, nullptr, false, options);
+}
+
+int cap_sweep_instances(CapContext* c, const CapSweepDesc* device_sweeps, uint64_t n, CapSweepHit* device_out, uint32_t* device_instances,
+                        const CapTraceOptions* options)
+{
+    return sweep_query(c, "cap_sweep_instances", device_sweeps, n, device_out, device_instances, true, options);
 }
 
 int cap_overlap_boxes(CapContext* c, const CapBoxDesc* device_boxes, uint64_t n, uint32_t k, uint32_t* device_triangles, uint32_t* device_counts,

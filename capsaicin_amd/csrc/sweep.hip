@@ -16,16 +16,13 @@
 // product that underflows.  No test is strict: a box whose entry time equals `best` is opened, its lower id may win.
 #include "cap_closest.h"
 #include "cap_kernels.h"
+#include "cap_near.h"
 #include "cap_query_walk.h"
 
 namespace cap
 {
 namespace
 {
-constexpr float kSweepPad  = 1.0f + 8.0f * 5.9604645e-8f;  // the slab test's relative padding
-constexpr float kSweepTiny = 1.17549435e-38f;              // ... and its absolute one: the smallest normal number
-constexpr float kSweepHuge = 3.40282347e38f;
-
 __device__ __forceinline__ bool sweep_ok(const float4 q0, const float4 q1)
 {
     const float inf = __builtin_inff();
@@ -33,28 +30,7 @@ __device__ __forceinline__ bool sweep_ok(const float4 q0, const float4 q1)
            q1.w >= 0.f;  // (a NaN fails its comparison)
 }
 
-// the far side of every time comparison of the walk
-__device__ __forceinline__ float sweep_padded(float t) { return t * kSweepPad + kSweepTiny; }
-
-// What a lane keeps of its sweep for the walk: the origin, 1 / d per component and the prune radius
-struct SweepRay
-{
-    float ox, oy, oz, ix, iy, iz, grow;
-};
-
-// The ray against the box [lo, hi] grown by grow, over [0, far]: true = not rejected, tn = the entry time (0 inside).  A component
-// of d that is 0 gives +-inf or, on a plane through o, a NaN, which v_min / v_max drop: that slab then constrains nothing it should not.
-__device__ __forceinline__ bool sweep_slab(const SweepRay& s, float lox, float loy, float loz, float hix, float hiy, float hiz, float far, float& tn)
-{
-    const float ax = ((lox - s.grow) - s.ox) * s.ix, bx = ((hix + s.grow) - s.ox) * s.ix;
-    const float ay = ((loy - s.grow) - s.oy) * s.iy, by = ((hiy + s.grow) - s.oy) * s.iy;
-    const float az = ((loz - s.grow) - s.oz) * s.iz, bz = ((hiz + s.grow) - s.oz) * s.iz;
-    const float en = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), 0.f));
-    const float ex = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), far));
-    tn             = fminf(en, kSweepHuge);
-    return tn <= sweep_padded(ex);
-}
-
+// (sweep_padded, SweepRay and sweep_slab, the walk's time comparisons and its box test, are in cap_near.h: the debug entry runs them too)
 template <int STACK>
 __device__ __forceinline__ bool sweep_node_step(const BvhDev& bvh, const SweepRay& s, float best, uint2* stack, int& node, int& sp)
 {
@@ -150,6 +126,40 @@ __device__ __forceinline__ float sweep_candidate(const float4 t0, const float4 t
     return tc;
 }
 
+// Parts (A), (B) with its polish and (C) for one triangle record (t0, t1, t2) -- the stored one, or the world record of an instanced
+// triangle: the triangle's contact time, or a NaN where it has none or cannot beat `best` (wins_tie: it would win a tie at `best`).
+// The caller's comparison  t < best || (t == best && wins_tie)  then fails by itself.  It is the leaf body of k_sweep_spheres below,
+// operation for operation; that kernel keeps its own copy of the text, because calling this function from it cost it a register (70
+// VGPRs for 69, tools/kernel_regs.sh), and its code is held to what it was.
+__device__ __forceinline__ float sweep_contact(const float4 t0, const float4 t1, const float4 t2, const float4 q0, const float4 q1, float r2, float r2k,
+                                               float dd, float best, bool wins_tie)
+{
+    const float none = __builtin_nanf("");
+    // (A) a start overlap is a contact at t = 0
+    if (closest_dist2(t0, t1, t2, q0.x, q0.y, q0.z) <= r2) return 0.f;
+    // (B) the candidate, compared with best before (C) is paid for; best == 0 admits no t > 0
+    if (!(best > 0.f)) return none;
+    float t = sweep_candidate(t0, t1, t2, q0, q1, r2, dd);
+    if (!(t < best || (t == best && wins_tie))) return none;
+    // (C) the centre at the candidate time touches the triangle by the closest-point function itself; (B)'s polish:
+    // a centre that rounding left outside is moved inwards by a Newton step on the distance plus the nudge, twice at the most
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k)
+    {
+        const float        cx = q0.x + t * q1.x, cy = q0.y + t * q1.y, cz = q0.z + t * q1.z;
+        const ClosestPoint c  = closest_record(t0, t1, t2, cx, cy, cz);
+        if (c.d2 <= r2k) return t;
+        if (k == 2) break;
+        const float dist = sqrtf(c.d2);
+        const float rate = -dot_c(cx - c.x, cy - c.y, cz - c.z, q1.x, q1.y, q1.z);
+        const float size = fmaxf(fmaxf(fmaxf(fabsf(cx), fabsf(cy)), fabsf(cz)), fmaxf(fmaxf(fabsf(c.x), fabsf(c.y)), fabsf(c.z))) + q0.w;
+        const float tn   = t + (((dist - q0.w) + kSweepNudge * size) * dist) / rate;
+        if (!(rate > 0.f && tn <= q1.w)) break;
+        t = tn;
+    }
+    return none;
+}
+
 __device__ __forceinline__ void sweep_write_miss(float4* slot, float t)
 {
     slot[0] = make_float4(0.f, 0.f, 0.f, t);
@@ -196,6 +206,7 @@ __global__ __launch_bounds__(kBlock, sweep_blocks(STACK)) void k_sweep_spheres(B
                     const uint32_t gid = f2u(bvh.tris[4 * (size_t)leaf + 3].x);
                     if constexpr (FILTER)
                         if ((f.tri_mask[gid] & f.mask) == 0u) continue;
+                    // (from here to the comparison below: sweep_contact above, word for word -- change both or neither)
                     const float4 t0 = bvh.tris[4 * (size_t)leaf + 0], t1 = bvh.tris[4 * (size_t)leaf + 1], t2 = bvh.tris[4 * (size_t)leaf + 2];
                     // (A) a start overlap is a contact at t = 0
                     float t = 0.f;
@@ -243,7 +254,171 @@ __global__ __launch_bounds__(kBlock, sweep_blocks(STACK)) void k_sweep_spheres(B
         a.out[2 * (size_t)i + 1] = make_float4(c.u, c.v, u2f(best_gid), u2f(c.feature));
     }
 }
+// ---- over the instance table (cap_sweep_instances) ----
+// For every WORLD-space sweep the pair (instance, triangle) minimal in (t, instance, triangle), the per-pair function being
+// sweep_contact above, unchanged, on the world record of cap_closest_instances (world_record, from M as the caller gave it).  One loop
+// with three kinds of step, as k_closest_inst (point_query.hip), so that the lanes of a wave that are at the top level advance while
+// others are inside an instance.  The prune stays in world space at both levels: at the top the stored world boxes, below an instance
+// every child box of the object's tree mapped to its world box under M (cap_near.h overlap_world_box), each given sweep_slab against
+// the world ray over [0, best] and grown by R_i = sweep_prune_radius(r, |o|_inf, Xw_i) -- the table's largest Xw at the top level.  No
+// object-space ray is walked: the rounding of W d would be multiplied by t, and tmax = +inf is legal.  DESIGN.md "Sphere sweep queries
+// over instances" has the argument.  The top level's ordering key is the entry time; every test is <=, so a box, instance or triangle
+// entered exactly at `best` is opened and the lower (instance, triangle) wins.
+__device__ __forceinline__ TopWalk sweep_top_step(const TlasDev& tl, const uint32_t* lds_off, const SweepRay& s, float best, TopWalk t)
+{
+    const float4* c = tl.tlas + 2 * (size_t)(lds_off[t.level - 1u] + 2u * t.idx);
+    const float4  lo0 = c[0], hi0 = c[1], lo1 = c[2], hi1 = c[3];
+    float         d0, d1;
+    const bool    k0 = sweep_slab(s, lo0.x, lo0.y, lo0.z, hi0.x, hi0.y, hi0.z, best, d0);
+    const bool    k1 = sweep_slab(s, lo1.x, lo1.y, lo1.z, hi1.x, hi1.y, hi1.z, best, d1);
+    // (a record with k < 0 holds nothing: an inert instance or the padding of a level)
+    const bool h0 = lo0.w >= 0.0f && k0, h1 = lo1.w >= 0.0f && k1;
+    return top_advance(t, h0, h1, h0 && h1 && d1 < d0, f2u(hi0.w), f2u(hi1.w), d0, d1);  // the earlier entry first
+}
+
+// An inner node of the object's tree: sweep_node_step with both child boxes mapped to world space first.  m: the 12 words of M.
+template <int STACK>
+__device__ __forceinline__ bool sweep_world_node_step(const BvhDev& bvh, const float m[12], const SweepRay& s, float best, uint2* stack, int& node, int& sp)
+{
+    const float4 q0 = bvh.nodes[4 * node + 0], q1 = bvh.nodes[4 * node + 1], q2 = bvh.nodes[4 * node + 2], q3 = bvh.nodes[4 * node + 3];
+    float        lo0[3], hi0[3], lo1[3], hi1[3], t0, t1;
+    overlap_world_box(m, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, lo0, hi0);
+    overlap_world_box(m, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, lo1, hi1);
+    const bool k0 = sweep_slab(s, lo0[0], lo0[1], lo0[2], hi0[0], hi0[1], hi0[2], best, t0);
+    const bool k1 = sweep_slab(s, lo1[0], lo1[1], lo1[2], hi1[0], hi1[1], hi1[2], best, t1);
+    const int  c0 = (int)f2u(q3.z), c1 = (int)f2u(q3.w);
+    if (k0 && k1)
+    {
+        const bool swap = t1 < t0;
+        if (sp < STACK) stack[(sp++) * kBlock] = make_uint2(f2u(swap ? t0 : t1), (uint32_t)(swap ? c0 : c1));
+        node = swap ? c1 : c0;
+        return true;
+    }
+    if (k0 || k1)
+    {
+        node = k0 ? c0 : c1;
+        return true;
+    }
+    return false;
+}
+
+// Workgroups per CU: the stack's LDS and the 104 bytes of level offsets, as closest_inst_blocks (point_query.hip).  Registers
+// (tools/kernel_regs.sh; the table is in DESIGN.md "Sphere sweep queries over instances").
+constexpr int sweep_inst_blocks(int STACK) { return STACK <= 16 ? 4 : STACK <= 24 ? 3 : STACK <= 32 ? 2 : 1; }
+
+// FILTER: a mesh-mask table is installed (f.tri_mask by global id); the instance's own mask is tested either way, at entry.
+template <int STACK, bool FILTER>
+__global__ __launch_bounds__(kBlock, sweep_inst_blocks(STACK)) void k_sweep_inst(BvhDev bvh, SweepInstArgs ia, TlasDev tl, RayFilter f)
+{
+    __shared__ uint2    lds_stack[STACK * kBlock];
+    __shared__ uint32_t lds_off[kTlasMaxLevels + 1];
+    uint2* const        stack = lds_stack + threadIdx.x;
+    if (threadIdx.x <= tl.top) lds_off[threadIdx.x] = tl.level_off[threadIdx.x];
+    __syncthreads();
+    const SweepArgs& a      = ia.a;
+    const float      xw_all = u2f(ia.xw_max[0]);  // the largest Xw of the table: the top level's prune radius holds for every instance
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < a.n; j += gridDim.x * kBlock)
+    {
+        const float4 q0 = a.sweeps[2 * (size_t)j], q1 = a.sweeps[2 * (size_t)j + 1];
+        if (!sweep_ok(q0, q1))
+        {
+            sweep_write_miss(a.out + 2 * (size_t)j, 0.f);
+            if (ia.inst_out) ia.inst_out[j] = kInvalidId;
+            continue;
+        }
+        const float r2 = q0.w * q0.w, r2k = r2 * kSweepAccept;
+        const float dd = dot_c(q1.x, q1.y, q1.z, q1.x, q1.y, q1.z);
+        // (dd == 0: part (A) only, nothing beyond t = 0 can be an answer)
+        float       best     = dd == 0.f ? 0.f : q1.w;
+        uint32_t    best_gid = kInvalidId, best_inst = kInvalidId;
+        const float omax     = fmaxf(fabsf(q0.x), fmaxf(fabsf(q0.y), fabsf(q0.z)));
+        SweepRay    s{q0.x, q0.y, q0.z, 1.0f / q1.x, 1.0f / q1.y, 1.0f / q1.z, 0.f};
+        const float grow_top = sweep_prune_radius(q0.w, omax, xw_all);
+        TopWalk     t        = top_start(tl);
+        // bottom level: the instance being walked, its M and its own prune radius
+        bool     in_blas = false;
+        float    m[12]   = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float    grow    = 0.f;
+        uint32_t inst = 0u, imask = 0u;
+        int      node = 0, sp = 0;
+        bool     walk = bvh.tri_count != 0u;
+        while (walk)
+        {
+            if (in_blas)
+            {
+                s.grow = grow;
+                if (node >= 0)
+                {
+                    if (sweep_world_node_step<STACK>(bvh, m, s, best, stack, node, sp)) continue;
+                }
+                else
+                {
+                    const uint32_t code = (uint32_t)~node, first = code & kLeafFirstMask, last = first + (code >> kLeafCountShift);
+                    for (uint32_t leaf = first; leaf <= last; ++leaf)
+                    {
+                        const uint32_t gid = f2u(bvh.tris[4 * (size_t)leaf + 3].x);
+                        if constexpr (FILTER)
+                            if ((f.tri_mask[gid] & imask) == 0u) continue;
+                        const WorldRecord w = world_record(make_float4(m[0], m[1], m[2], m[3]), make_float4(m[4], m[5], m[6], m[7]),
+                                                           make_float4(m[8], m[9], m[10], m[11]), bvh.tris[4 * (size_t)leaf + 0],
+                                                           bvh.tris[4 * (size_t)leaf + 1], bvh.tris[4 * (size_t)leaf + 2]);
+                        const bool  wins = inst < best_inst || (inst == best_inst && gid < best_gid);
+                        const float tc   = sweep_contact(w.t0, w.t1, w.t2, q0, q1, r2, r2k, dd, best, wins);
+                        if (tc < best || (tc == best && wins)) best = tc, best_inst = inst, best_gid = gid;
+                    }
+                }
+                in_blas = sweep_pop(stack, sp, best, node);
+                continue;
+            }
+            if (t.todo0 != kInvalidId)
+            {
+                // the head of the queue, if its entry time still passes against the bound as it is now: its mask joined with the
+                // call's (0 for an inert instance; the mesh byte joins it per triangle), then M, the instance's prune radius and
+                // the root of the object's tree
+                inst             = t.todo0;
+                const bool still = t.todo0_d <= sweep_padded(best);
+                t                = top_pop(t);
+                if (!still) continue;
+                const float4 w3 = tl.rec[4 * (size_t)inst + 3];
+                imask           = f2u(w3.x) & f.mask;
+                if (imask == 0u) continue;
+                const float4 m0 = ia.descs[4 * (size_t)inst], m1 = ia.descs[4 * (size_t)inst + 1], m2 = ia.descs[4 * (size_t)inst + 2];
+                m[0] = m0.x, m[1] = m0.y, m[2] = m0.z, m[3] = m0.w, m[4] = m1.x, m[5] = m1.y, m[6] = m1.z, m[7] = m1.w;
+                m[8] = m2.x, m[9] = m2.y, m[10] = m2.z, m[11] = m2.w;
+                grow = sweep_prune_radius(q0.w, omax, ia.near[inst].y);  // (g, Xw): g is not read, the test stays in world space
+                node = (int)f2u(w3.y), sp = 0, in_blas = true;
+                continue;
+            }
+            if (t.done) break;
+            s.grow = grow_top;
+            t      = sweep_top_step(tl, lds_off, s, best, t);
+        }
+        if (ia.inst_out) ia.inst_out[j] = best_inst;
+        if (best_gid == kInvalidId)
+        {
+            sweep_write_miss(a.out + 2 * (size_t)j, q1.w);
+            continue;
+        }
+        // the winner's world record again, from the records in id order and the instance's transform, the same operations
+        const float4*      rec = bvh.tris_by_id + 4 * (size_t)best_gid;
+        const float4*      md  = ia.descs + 4 * (size_t)best_inst;
+        const WorldRecord  w   = world_record(md[0], md[1], md[2], rec[0], rec[1], rec[2]);
+        const bool         at0 = best == 0.f;
+        const ClosestPoint c   = closest_record(w.t0, w.t1, w.t2, at0 ? q0.x : q0.x + best * q1.x, at0 ? q0.y : q0.y + best * q1.y,
+                                                at0 ? q0.z : q0.z + best * q1.z);
+        a.out[2 * (size_t)j]     = make_float4(c.x, c.y, c.z, best);
+        a.out[2 * (size_t)j + 1] = make_float4(c.u, c.v, u2f(best_gid), u2f(c.feature));
+    }
+}
 }  // namespace
+
+void launch_sweep_instances(const LaunchCfg& cfg, const BvhDev& bvh, const SweepInstArgs& a, const TlasDev& tl, const RayFilter& f, uint32_t depth)
+{
+    // (depth: of the deepest bottom-level tree)
+    with_stack_class(depth, [&](auto S) {
+        with_flag(f.tri_mask != nullptr, [&](auto FILTER) { launch_points<k_sweep_inst<decltype(S)::value, decltype(FILTER)::value>>(cfg, a.a.n, bvh, a, tl, f); });
+    });
+}
 
 void launch_sweep_spheres(const LaunchCfg& cfg, const BvhDev& bvh, const SweepArgs& a, const RayFilter* f, uint32_t depth)
 {

@@ -408,6 +408,18 @@ int cap_debug_overlap_instance_prune(const float* transform, const float* object
 int cap_debug_overlap_world_node(const float* transform, const float* object_lo, const float* object_hi, const float* node_lo, const float* node_hi,
                                  const float* query_lo, const float* query_hi, float* xw, float* slack, float* world_lo, float* world_hi,
                                  uint32_t* skip_node);
+/* The bottom-level prune of cap_sweep_instances (below) for ONE instance transform (12 floats, row-major 3x4), the object-space box of
+ * its object (object_lo, object_hi), one OBJECT-space node box (node_lo, node_hi: a node of the object's tree, or a triangle's vertex box
+ * standing for the nodes above it), one WORLD-space sweep (8 floats, a CapSweepDesc: origin, radius, direction, tmax; the tmax word is
+ * not read) and the far bound of the test (the walk's best time so far, or tmax), by the very functions the query kernel runs.  Outputs,
+ * each may be NULL: xw as cap_debug_closest_instance_bound's; radius = R = fl(r + 128 * 2^-24 * (|origin|_inf + xw + r)), what the
+ * node's world box is grown by; world_lo, world_hi = the world box of the node under the transform as the walk computes it, 3 floats
+ * each; entry = the time the ray enters the grown box (0 inside), exit_padded = what it is compared with, fl(fl(min(exit, far) *
+ * (1 + 8 * 2^-24)) + 2^-126); skip_node = 1 if the walk would skip the node (entry > exit_padded), else 0.  An inert transform gives
+ * zeros and no skip.  CAP_ERR_INVALID_ARG for a NULL input.  Needs no device. */
+int cap_debug_sweep_instance_prune(const float* transform, const float* object_lo, const float* object_hi, const float* node_lo, const float* node_hi,
+                                   const float* sweep, float far_bound, float* xw, float* radius, float* world_lo, float* world_hi, float* entry,
+                                   float* exit_padded, uint32_t* skip_node);
 /* Traversal strategy of the trace kernels (same hits either way): AUTO picks EXHAUSTIVE for scenes of at most 64
  * triangles (wave-uniform test of every triangle, no stack) and STACK (LBVH + per-lane LDS stack) otherwise. */
 typedef enum CapTraversal
@@ -707,7 +719,8 @@ int cap_closest_points_multi(CapContext* ctx, const CapPointDesc* device_points,
  * does nothing; nothing of the render's state is touched; nothing is written on an error.  CAP_ERR_STATE before cap_bvh_build and
  * while the trees are stale.  options: instance_mask and the mesh-mask table act by mesh as for points; any ray_flags bit is
  * CAP_ERR_INVALID_ARG (the sweep is two-sided), as are non-zero reserved words and instance_mask > 0xFF; NULL is the plain call.
- * Not covered: instances, k nearest contacts and paging, other swept shapes, per-query masks, a time of exit, rotation. */
+ * Not covered: k nearest contacts and paging, other swept shapes, per-query masks, a time of exit, rotation.  cap_sweep_instances
+ * (below) is the form over the instance table. */
 typedef struct CapSweepDesc /* 32 B, 16-aligned: DXR RayDesc's shape with the radius where tmin is */
 {
     float origin[3];
@@ -725,6 +738,51 @@ typedef struct CapSweepHit /* 32 B: CapClosest's layout with t where dist2 is */
 } CapSweepHit;
 int cap_sweep_spheres(CapContext* ctx, const CapSweepDesc* device_sweeps, uint64_t n, CapSweepHit* device_out,
                       const CapTraceOptions* options /* may be NULL */);
+
+/* ---- sphere sweep queries over instances: the first contact of a moving sphere with an assembly of placed parts ----
+ * cap_sweep_spheres over the instance table of cap_instances_set: for every WORLD-space sweep the first time t in [0, tmax] at which the
+ * sphere touches a triangle of an instance, where, and of which instance.  A non-rigid transform does not keep a sphere a sphere, so
+ * nothing is evaluated in object space: the answer is defined, and the trees are pruned, in world space.  CapSweepDesc and CapSweepHit
+ * are unchanged.
+ *
+ * Candidates are cap_closest_instances' pairs (i, g) by its rules: instance i is live, g is a triangle of i's object (every triangle
+ * of the scene without an object table), and desc[i].mask & mesh_mask[m] & instance_mask != 0, m the mesh of g.
+ *
+ * The per-pair function is cap_sweep_spheres' -- parts (A), (B) with its polish (the nudge of sixteen roundings, at most three
+ * evaluations) and (C) with kappa = 8 x 2^-24, operation by operation as written there -- evaluated on the WORLD RECORD of
+ * cap_closest_instances in the place of the stored record: from M = desc[i].transform as the caller gave it and the stored (v0, e1, e2),
+ *   v0w_r = fl(dot_c(M_r.xyz, v0) + M_r.w),  e1w_r = dot_c(M_r.xyz, e1),  e2w_r = dot_c(M_r.xyz, e2),
+ *   dot_c(a, b) = fl(fl(fl(a.x b.x) + fl(a.y b.y)) + fl(a.z b.z)),
+ * no fused multiply-add; the computed vertices are B1 = fl(v0w + e1w) and B2 = fl(v0w + e2w).  The sweep's origin, direction, radius
+ * and tmax enter as given.  So a float32 brute force -- the world records, then cap_sweep_spheres' per-triangle function on each --
+ * is bit-identical to the kernel.
+ *
+ * The answer.  Among the candidate pairs that have a contact, the one minimal in (t, instance, triangle) lexicographic order: it
+ * depends on neither the trees, nor the builders, nor the visiting order.  The hit's point, u, v and feature are the cascade's words on
+ * the winner's world record at c = fl(o + fl(t d)), or at o itself when t = 0; point is in world space; triangle is the scene's global
+ * id.  device_instances[j] (may be NULL) is the winner's index in the instance table, 0xFFFFFFFF on a miss and for a degenerate sweep.
+ * The miss record (0, 0, 0, tmax, 0, 0, 0xFFFFFFFF, 0) and the degenerate sweeps with their record (t = 0) are cap_sweep_spheres'.
+ * Inert instances (below, "Inert instances") contribute nothing.
+ *
+ * Three identities hold and are tested.  (1) One identity instance (M = I with translation +0) gives cap_sweep_spheres' record bit for
+ * bit, with one exception: the world record turns a -0 into +0 -- a vertex coordinate by v0w_r = fl(dot_c(M_r.xyz, v0) + 0), an edge
+ * component by dot_c itself, whose products with the zeros of M_r are +0 or -0 and sum to -0 only when all three are -0 -- so a
+ * triangle with a vertex coordinate or an edge component -0 enters as if that word were +0, and a word of the record's point (or of
+ * u, v) that depends on the sign of such a zero may differ in the sign of a zero, nothing else.  (2) Pure translations, with vertices,
+ * translations and sweeps on a common power-of-two grid coarse enough that every v0 + translation is exact, give the answer of the
+ * flattened scene with flat id i T + g (T the triangle count).  (3) Scaling every M (translation included), every origin, every radius
+ * and every direction by 2^j leaves t, u, v, both ids and the feature unchanged and scales point by 2^j, short of overflow and
+ * underflow: no absolute term enters the per-pair function, so the identity is exact.
+ *
+ * Conventions, errors and their order are cap_sweep_spheres': any ray_flags bit, non-zero reserved words and instance_mask > 0xFF are
+ * CAP_ERR_INVALID_ARG; then CAP_ERR_STATE before cap_bvh_build and while the trees are stale, and CAP_ERR_STATE without an instance
+ * table, where the other instanced queries have it; then n = 0 does nothing; NULL sweeps or output; the ranges "sweeps" and "hits"
+ * (32 bytes each, 16-byte aligned) and, when given, "instances" (4 bytes each, 4-byte aligned), none of which may overlap another.
+ * Nothing is written on an error; n above 2^24 is split into launches; nothing of the render's state is touched.  The query is
+ * current under cap_scene_update_vertices + cap_bvh_refit, under cap_instances_set again and under cap_objects_set.
+ * Not covered: k nearest contacts and paging, other swept shapes, a time of exit, rotation, per-query masks. */
+int cap_sweep_instances(CapContext* ctx, const CapSweepDesc* device_sweeps, uint64_t n, CapSweepHit* device_out,
+                        uint32_t* device_instances /* may be NULL */, const CapTraceOptions* options /* may be NULL */);
 
 /* ---- box overlap queries: the triangles that meet an axis-aligned box (collision broad phase, voxelisation, selection, clipping) ----
  * For every box the triangles of the uploaded scene that meet the CLOSED box [lo, hi], on the scene's binary tree: the first k of them

@@ -5,7 +5,7 @@ bench.py, no pass mark.
 
     python tools/point_query_rate.py [--points 1048576] [--reps 10] [--warmup 2] [--radius inf | --radius-frac F] [--offset 1e-3]
                                      [--k K [--counts]] [--instances N] [--signed] [--winding [--beta B]]  (--winding goes with --instances N)
-                                     [--sweeps]
+                                     [--sweeps [--instances N]]
 
 --winding runs cap_winding_numbers at --beta B (default 2; inf sums every triangle exactly: use fewer --points) after
 cap_winding_build, on the same point sets (the radius is not read).  Each line carries its rate, mean_visits = the mean numbers of
@@ -68,6 +68,12 @@ cap_overlap_instances on the triangles' bounding boxes (boxes_ms, mboxes_per_s, 
 unit direction, tmax inf, radius R (default 0.01 x the scene's size): msweeps_per_s, the share of misses and of start overlaps, and
 from the same process cap_trace_rays on the same origins and directions as the yardstick (rays_ms, mrays_per_s, ray_misses,
 ratio_to_rays = the sweep rate over the ray rate).
+--sweeps together with --instances N runs cap_sweep_instances on the --instances layout with the same sweeps as world sweeps:
+msweeps_per_s, the share of misses, of start overlaps and of winners in instance 0, and from the same process (a) cap_sweep_spheres on
+the same sweeps (scene_ms, scene_msweeps_per_s, ratio_to_scene), (b) cap_sweep_instances over ONE identity instance (identity_ms,
+identity_msweeps_per_s, identity_to_scene = its rate over the scene form's: the cost of the instanced walk by itself;
+identity_same_as_scene: its records equal the scene form's bit for bit) and (c) cap_closest_instances on the origins (closest_ms,
+closest_mpoints_per_s, ratio_to_closest).
 
 Point sets, each of --points points (rounded down to a cube for the grid):
   grid      a regular grid through the scene's box, in raster order (x fastest);
@@ -140,8 +146,8 @@ def main():
     ap.add_argument("--triangles", action="store_true")
     ap.add_argument("--sweeps", action="store_true")
     a = ap.parse_args()
-    if a.sweeps and (a.winding or a.signed or a.boxes or a.triangles or a.k is not None or a.instances is not None):
-        ap.error("--sweeps goes with --radius or --radius-frac only")
+    if a.sweeps and (a.winding or a.signed or a.boxes or a.triangles or a.k is not None):
+        ap.error("--sweeps goes with --radius, --radius-frac and --instances only")
     if a.sweeps and a.radius == float("inf") and a.radius_frac is None:
         a.radius_frac = 0.01
     if a.boxes and (a.winding or a.signed):
@@ -250,11 +256,36 @@ def main():
             ids = out[:n, 6].contiguous().view(torch.int32)
             miss = ids == -1
             start = (~miss) & (out[:n, 3] == 0)
-            print(json.dumps(dict(head, set=name, radius_frac=a.radius / size, ms=round(sec * 1e3, 3), msweeps_per_s=round(n / sec / 1e6, 2),
-                                  misses=round(float(miss.float().mean()), 4), start_overlaps=round(float(start.float().mean()), 4),
-                                  rays_ms=round(rsec * 1e3, 3), mrays_per_s=round(n / rsec / 1e6, 2),
-                                  ray_misses=round(float((hits4[:, 3].contiguous().view(torch.int32) == -1).float().mean()), 4),
-                                  ratio_to_rays=round(rsec / sec, 3))), flush=True)
+            line = dict(head, set=name, radius_frac=a.radius / size, ms=round(sec * 1e3, 3), msweeps_per_s=round(n / sec / 1e6, 2),
+                        misses=round(float(miss.float().mean()), 4), start_overlaps=round(float(start.float().mean()), 4),
+                        rays_ms=round(rsec * 1e3, 3), mrays_per_s=round(n / rsec / 1e6, 2),
+                        ray_misses=round(float((hits4[:, 3].contiguous().view(torch.int32) == -1).float().mean()), 4), ratio_to_rays=round(rsec / sec, 3))
+            if a.instances is not None:
+                # cap_sweep_instances on the same world sweeps (the point sets lie in instance 0, the identity) under the --instances layout;
+                # from the same process the scene form above, the instanced walk over ONE identity instance -- what the two-level loop
+                # and the per-node world boxes cost by themselves -- and cap_closest_instances on the origins
+                call = lambda: capi._check(L.cap_sweep_instances(r.ctx, sw.data_ptr(), n, flat_out.data_ptr(), inst.data_ptr(), None), "cap_sweep_instances")
+                r.set_instances(M[:1])
+                one_sec = timed(r, call, a.reps, a.warmup)
+                same = bool((flat_out[:n].view(torch.int32) == out[:n].view(torch.int32)).all())
+                r.set_instances(M)
+                isec = timed(r, call, a.reps, a.warmup)
+                imiss = inst[:n] == -1
+                istart = (~imiss) & (flat_out[:n, 3] == 0)
+                in_identity = float((inst[:n] == 0).float().mean())
+                pts = sw[:, 0:4].clone().contiguous()
+                pts[:, 3] = float("inf")
+                torch.cuda.synchronize()
+                csec = timed(r, lambda: capi._check(L.cap_closest_instances(r.ctx, pts.data_ptr(), n, flat_out.data_ptr(), inst.data_ptr(), None),
+                                                    "cap_closest_instances"), a.reps, a.warmup)
+                line = dict(head, set=name, radius_frac=a.radius / size, instances=a.instances, inert=int(info_i.inert), tlas_depth=int(info_i.tlas_depth),
+                            ms=round(isec * 1e3, 3), msweeps_per_s=round(n / isec / 1e6, 2), misses=round(float(imiss.float().mean()), 4),
+                            start_overlaps=round(float(istart.float().mean()), 4), in_identity=round(in_identity, 4),
+                            identity_ms=round(one_sec * 1e3, 3), identity_msweeps_per_s=round(n / one_sec / 1e6, 2), identity_same_as_scene=same,
+                            scene_ms=line["ms"], scene_msweeps_per_s=line["msweeps_per_s"], identity_to_scene=round(sec / one_sec, 3),
+                            ratio_to_scene=round(sec / isec, 3), closest_ms=round(csec * 1e3, 3), closest_mpoints_per_s=round(n / csec / 1e6, 2),
+                            ratio_to_closest=round(csec / isec, 3))
+            print(json.dumps(line), flush=True)
         r.close()
         return
     if a.triangles:
